@@ -18,9 +18,16 @@ Other workloads (each prints the same kind of JSON line w
   w3  texture frames: ORB-1000 + 500 AKAZE-like rows, mixed SearchForInitialization + SearchByProjection, one frame per call
   w4  346x260, 8 levels, 2 000 features + brute-force 2-NN 2000 x 2000, one frame per call
 
-Prints ONE JSON line (rank 0): metric/value/unit + `roofline` for the dominant kernel (live HIP-event timing on the launch stream)
-+ `cpu_baseline` (the CPU oracle, -O3 -march=native build, on a bounded sample of the same workload: 1 thread with p50/p95, and
-all cores).
+Prints ONE JSON line (rank 0): metric/value/unit/ms_per_step of the timed steps.  A plain run does nothing else: it sets up, warms
+up, times `--steps` steps and prints.  `--full` adds everything beyond the headline: `roofline` for the dominant kernel (live HIP-event
+timing on the launch stream) and per-kernel times, `cpu_baseline` (the CPU oracle, -O3 -march=native build, on a bounded sample of the
+same workload: 1 thread with p50/p95, and all cores), `verified` (the last timed step's outputs against the oracle's), and on the
+default w2 line the `side` and `streaming` objects.  The options that tune those legs (--cpu-slices, --cpu-pool, --no-prof, --stream,
+--latency-calls, --no-side) act only with --full.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step (the arrays its caller receives) as DIR/<name>.npy in
+float32 / float64, at most 64 MB in all (larger outputs: a fixed, seeded sample of slices); inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse, gc
 import json
@@ -40,19 +47,26 @@ METRIC = "front-end frames/s (event-accumulate + extract + match) per GPU; HBM G
 PROFILE_INPUTS = "profiles/roofline_inputs.json"
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E peak 8 TB/s (spec)
 CPU_POOL = 16              # worker processes of the all-cores CPU baseline (a one-GPU box's CPU share)
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: the most all files together may hold (64 MB)
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline and per-kernel times, the CPU baseline, the "
+                         "verification against the CPU oracle, the w1 single-slice latency, the w3/w4 batched mode and, on the default "
+                         "w2 line, the streamed input and the `side` runs of the other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--workload", choices=["w1", "w2", "w3", "w4", "w1full"], default="w2")
     ap.add_argument("--batch", type=int, default=0, help="time-slices per step per GPU (0 = the workload's default: 128 for w2, 1024 for w1)")
     ap.add_argument("--events", type=int, default=0, help="events per slice (0 = the workload's default: 1 000 000 for w2, 2 000 for w1)")
-    ap.add_argument("--cpu-slices", type=int, default=-1, help="slices / frames timed for the 1-thread CPU baseline (0 = skip, -1 = workload default)")
-    ap.add_argument("--cpu-pool", type=int, default=CPU_POOL, help="processes of the all-cores CPU baseline (0 = skip)")
-    ap.add_argument("--no-prof", action="store_true", help="skip per-kernel HIP-event timing")
+    ap.add_argument("--cpu-slices", type=int, default=-1, help="--full: slices / frames timed for the 1-thread CPU baseline (0 = skip, -1 = workload default)")
+    ap.add_argument("--cpu-pool", type=int, default=CPU_POOL, help="--full: processes of the all-cores CPU baseline (0 = skip)")
+    ap.add_argument("--no-prof", action="store_true", help="--full: skip per-kernel HIP-event timing")
     ap.add_argument("--sequences", type=int, default=1,
                     help="independent event sequences processed concurrently per GPU, each on its own context / HIP stream; "
                          "steps alternate between them (a step is still one batch of one sequence)")
@@ -63,15 +77,19 @@ def parse():
                     help="raw: sensor-pixel events (x,y,t,p) + the calibrator's undistortion maps resolved on the GPU; "
                          "float: events already undistorted by the loader (EventData)")
     ap.add_argument("--stream", action="store_true",
-                    help="w2: also time the batch with its events arriving from pinned host memory: double-buffered H2D on a copy stream "
+                    help="w2 --full: also time the batch with its events arriving from pinned host memory: double-buffered H2D on a copy stream "
                          "overlapped with the previous batch on the compute stream, for the 16-byte and the 4-byte wire record")
-    ap.add_argument("--latency-calls", type=int, default=300, help="w1: single-slice calls timed for the latency figures (0 = skip)")
+    ap.add_argument("--latency-calls", type=int, default=300, help="w1 --full: single-slice calls timed for the latency figures (0 = skip)")
     ap.add_argument("--no-side", action="store_true",
-                    help="default w2 line only: skip the `side` object (short verified runs of w1, w3, w4, the float input and the streamed "
+                    help="default w2 --full line only: skip the `side` object (short verified runs of w1, w3, w4, the float input and the streamed "
                          "input, so that one line carries a number for every BASELINE config)")
     a = ap.parse_args()
-    # the `side` object rides on the default line: w2, raw input, one GPU, one sequence
-    a.side = (not a.no_side) and a.workload == "w2" and a.input == "raw" and a.gpus == 1 and a.sequences == 1 and not a.no_prof
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:                          # a plain run: the timed steps and nothing else
+        a.cpu_slices, a.cpu_pool, a.no_prof, a.stream, a.latency_calls = 0, 0, True, False, 0
+    # the `side` object rides on the default --full line: w2, raw input, one GPU, one sequence
+    a.side = a.full and (not a.no_side) and a.workload == "w2" and a.input == "raw" and a.gpus == 1 and a.sequences == 1 and not a.no_prof
     if a.side:
         a.stream = True
     return a
@@ -211,6 +229,50 @@ def _bits_equal(a, b):
 def _verified(checked, mismatches, units, what):
     return {"units": units, "mismatches": len(mismatches), "compared": checked, "what": what,
             **({"first_mismatches": mismatches[:8]} if mismatches else {})}
+
+
+def _as_float(a):
+    """An output array in float32 / float64 without loss: float32 stays, 8/16-bit integers -> float32, wider integers and
+    booleans -> float64, structured records -> one float64 column per field (last axis)."""
+    a = np.asarray(a)
+    if a.dtype.names:
+        return np.stack([_as_float(a[f]).astype(np.float64) for f in a.dtype.names], axis=-1)
+    if a.dtype in (np.float32, np.float64):
+        return a
+    if a.dtype.kind in "iu" and a.dtype.itemsize <= 2:
+        return a.astype(np.float32)
+    return a.astype(np.float64)
+
+
+def _ragged(arrs, width):
+    """Per-unit arrays of varying length (None = not produced) -> (units, width, ...) zero-padded + the lengths (-1 for None)."""
+    arrs = [None if x is None else _as_float(x) for x in arrs]
+    proto = next((x for x in arrs if x is not None), np.zeros(0, np.float32))
+    out = np.zeros((len(arrs), width) + proto.shape[1:], proto.dtype)
+    for i, x in enumerate(arrs):
+        if x is not None:
+            out[i, :len(x)] = x[:width]
+    return out, np.array([-1 if x is None else len(x) for x in arrs], np.float64)
+
+
+def _sample_units(nunits, unit_bytes):
+    """Indices of the units a dump keeps: all of them when they fit in DUMP_BYTES, else a fixed, seeded sample in ascending order."""
+    keep = int(min(nunits, max(1, DUMP_BYTES // max(unit_bytes, 1))))
+    if keep == nunits:
+        return np.arange(nunits)
+    return np.sort(np.random.default_rng(0).choice(nunits, keep, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 / float64 (the caller samples to stay within DUMP_BYTES)."""
+    arrays = {k: _as_float(v) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError("bench.py: the outputs to dump hold %d bytes, more than %d" % (total, DUMP_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v))
+    print("bench.py: %d outputs of the last timed step (%.1f MB) written to %s" % (len(arrays), total / 1e6, dirname), file=sys.stderr)
 
 
 def _gen_slice(args):
@@ -540,7 +602,7 @@ def side_runs(env, main_out):
             ("w4", run_frames, dict(workload="w4", steps=6, warmup=1, cpu_slices=8, cpu_pool=0)),
             ("w2_float_input", run_batch, dict(workload="w2", input="float", steps=6, warmup=2, cpu_slices=4, cpu_pool=0)))
     for name, fn, over in plan:
-        v = dict(vars(a)); v.update(over); v.update(side=False, stream=False, batch=0, events=0)
+        v = dict(vars(a)); v.update(over); v.update(side=False, stream=False, batch=0, events=0, dump_outputs=None)
         env2 = dict(env); env2["a"] = argparse.Namespace(**v)
         t0 = time.perf_counter()
         try:
@@ -550,7 +612,7 @@ def side_runs(env, main_out):
             side[name] = {"error": "%s: %s" % (type(e).__name__, e), "verified": {"mismatches": 1, "what": "the side run failed"}}
     t0 = time.perf_counter()
     try:
-        v = dict(vars(a)); v.update(steps=6, warmup=1)
+        v = dict(vars(a)); v.update(steps=6, warmup=1, dump_outputs=None)
         env2 = dict(env); env2["a"] = argparse.Namespace(**v)
         side["stereo"] = run_stereo(env2)
         side["stereo"]["wall_s"] = time.perf_counter() - t0
@@ -756,6 +818,8 @@ def run_batch(env):
         return out
 
     dt = timed_steps(env, step, arm_prof)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, batch_outputs(seqs[(step_no[0] - 1) % S], B, W, H, want_desc, match))
     prof = {}
     if not a.no_prof:
         prof = collect_prof()
@@ -865,6 +929,33 @@ def run_batch(env):
     return out
 
 
+def batch_outputs(seq, B, W, H, want_desc, match):
+    """What one batch call hands its caller (eorb_fe_run_batch*_dev's output buffers), for --dump-outputs: per slice the u8 event image,
+    the keypoint count and records (one column per cv::KeyPoint field), the descriptors and the matches against the previous slice.
+    Rows past a slice's count (past the previous slice's count for matches) are set to 0: the library leaves them unwritten."""
+    from eorb_slam_amd import synth
+    _, fb, bf = seq
+    cap = fb.cap
+    n = bf["n"].cpu().numpy()[:B].astype(np.int64)
+    per = W * H * 4 + cap * 7 * 8 + (cap * 32 * 4 if want_desc else 0) + (cap * 8 + 8 if (want_desc and match) else 0) + 8 + 8
+    idx = _sample_units(B, per)
+    valid = np.arange(cap)[None, :] < n[idx, None]
+    kp = bf["kp"].cpu().numpy().view(synth.KP_DTYPE).reshape(B, cap)[idx]
+    kp[~valid] = np.zeros((), synth.KP_DTYPE)
+    out = {"slices": idx, "image": bf["img"].cpu().numpy().reshape(B, H, W)[idx], "n_keypoints": n[idx], "keypoints": kp}
+    if want_desc:
+        desc = bf["desc"].cpu().numpy().reshape(B, cap, 32)[idx]
+        desc[~valid] = 0
+        out["descriptors"] = desc
+        if match:
+            m = bf["m"].cpu().numpy().reshape(B, cap)[idx]
+            nprev = np.where(idx > 0, n[np.maximum(idx - 1, 0)], 0)
+            m[np.arange(cap)[None, :] >= nprev[:, None]] = 0
+            out["matches12"] = m
+            out["n_matches"] = bf["nm"].cpu().numpy()[:B][idx]
+    return out
+
+
 def verify_batch(g, ref, want_desc, match):
     """The GPU's outputs of the last timed step against the oracle's for the same slices (the `for k` order of
     src/Event/EventConversion.cc:231-263 decides every float): float image, running extremes, u8 image, keypoint records,
@@ -948,14 +1039,16 @@ def run_frames(env):
         P = level_pixels(W, H, 1.2, 8)
         ncpu = 24 if a.cpu_slices < 0 else a.cpu_slices
     FR = 16                                   # frames per step
+    keep = bool(a.dump_outputs)               # (--dump-outputs: the step keeps its frames' results)
 
     def step():
-        for _ in range(FR):
-            one()
+        st["last"] = [one(keep) for _ in range(FR)]
 
     def arm():
         st["nk"].clear(); st["nm"].clear()
     dt = timed_steps(env, step, arm)
+    if keep and rank == 0:
+        dump_outputs(a.dump_outputs, frame_outputs(st["last"], ge.cap, a.workload))
     nk, nm = list(st["nk"]), list(st["nm"])
     # the per-kernel times come from a second pass over the same steps: with one frame per call the profiling scopes (two event
     # records per kernel group) are a visible share of a call, and the value above is the product's, not the profiler's
@@ -983,7 +1076,7 @@ def run_frames(env):
                          "pass over the same steps")
             out["roofline"] = r
             out["kernels_ms_per_step"] = per_step
-        if world == 1:
+        if world == 1 and a.full:
             # throughput mode of the same extraction (+ SearchForInitialization of frame b against b-1, ORB rows only): the frames
             # resident in HBM, one call per batch of 32 (eorb_fe_run_batch_images_dev)
             fbi = fe.FrontEndBatch(W, H, 1.0, False, max_batch=nfr, max_events=1, match=True, want_desc=True, windowSize=100, nnratio=0.9,
@@ -1035,6 +1128,49 @@ def run_frames(env):
     return out
 
 
+def frame_outputs(res, cap, workload):
+    """What the last step's calls returned (w3: the extractor's keypoints + descriptors, SearchForInitialization and SearchByProjection
+    against the previous frame; w4: keypoints + descriptors, the 2-NN indices and distances), one row per frame, zero-padded to the
+    extractor's capacity (+ the 500 AKAZE-like rows of a w3 frame) with the lengths beside them, for --dump-outputs."""
+    out = {}
+    out["keypoints"], out["n_keypoints"] = _ragged([r["kps"] for r in res], cap)
+    out["descriptors"], _ = _ragged([r["desc"] for r in res], cap)
+    if workload == "w3":
+        out["matches12"], out["n_matches12"] = _ragged([r.get("m12") for r in res], cap + 500)
+        out["n_matches_init"] = np.array([r.get("n1", -1) for r in res], np.float64)
+        out["cur_mappoints"], _ = _ragged([r.get("cur_mp") for r in res], cap + 500)
+        out["n_matches_proj"] = np.array([r.get("n2", -1) for r in res], np.float64)
+    else:
+        out["knn_idx"] = np.stack([r["idx"] for r in res]); out["knn_dist"] = np.stack([r["dist"] for r in res])
+    return out
+
+
+def chain_outputs(res):
+    """What EvImBuilder::Track returned for every chunk of the last step (w1full), for --dump-outputs: per chunk the state, the
+    dispatch flag, the next chunk size and the match count; the INIT keypoints, the LK points / status / error, and on a dispatch the
+    contest's focus scores, winner, winner image and L2 keypoints, one row per chunk, zero-padded, with the lengths beside them."""
+    def col(key, none=-1.0):
+        return np.array([none if r.get(key) is None else float(r[key]) for r in res], np.float64)
+
+    def rag(get):
+        arrs = [get(r) for r in res]
+        return _ragged(arrs, max([len(x) for x in arrs if x is not None] + [1]))
+    mci = [r.get("mci") or {} for r in res]
+    out = {"state": col("state"), "dispatched": col("dispatched"), "chunk_size": col("chunk_size"), "skipped": col("skipped", 0.0),
+           "n_matches": col("nMatches"), "med_px_disp": col("medPxDisp"),
+           "winner": np.array([m.get("winner", -1) for m in mci], np.float64)}
+    for name, get in (("init_keypoints", lambda r: r.get("kps")), ("lk_points", lambda r: r.get("pts")), ("lk_status", lambda r: r.get("status")),
+                      ("lk_err", lambda r: r.get("err")), ("matches12", lambda r: r.get("matches12")),
+                      ("focus", lambda r: None if r.get("mci") is None else np.atleast_1d(r["mci"]["focus"])),
+                      ("l2_keypoints", lambda r: None if r.get("mci") is None else r["mci"]["l2_kps"])):
+        out[name], out["len_" + name] = rag(get)
+    imgs = [m.get("image") for m in mci]
+    if any(x is not None for x in imgs):
+        shape = next(x for x in imgs if x is not None).shape
+        out["winner_image"] = np.stack([np.zeros(shape, np.float32) if x is None else _as_float(x) for x in imgs])
+    return out
+
+
 def run_chain(env):
     """w1full: config 1 as the reference executes it.  One step = one pass of EvImBuilder::Track's chunk loop over a synthetic stream
     (128 000 events: about 70 chunks of 2 000 ... 5 000 events, about 20 dispatches), one chunk per call through the one-call seams."""
@@ -1049,6 +1185,8 @@ def run_chain(env):
         g.resetAll()
         last["res"] = fe.feed_chunks(g, evs, synth.l1_mci_poses)
     dt = timed_steps(env, step)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, chain_outputs(last["res"]))
     nchunks = len(last["res"])
     ndisp = sum(r["dispatched"] for r in last["res"])
     prof = {}

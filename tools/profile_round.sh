@@ -3,13 +3,14 @@
 #   per workload: rocprofv3 --kernel-trace --stats, then separate --pmc passes (FETCH_SIZE, WRITE_SIZE, two SQ passes) of the same bench
 #   command -> gpurun_out/<tag>_<w>_kernel_stats.csv and one entry of gpurun_out/<tag>_roofline_inputs.json (also copied to
 #   profiles/roofline_inputs.json: bench.py reads `roofline.traffic` / `roofline.issue` from there while the sources' hash matches),
-#   then the bench lines themselves: gpurun_out/<tag>_bench.json (default command) and gpurun_out/<tag>_<w>_bench.json.
+#   then the full bench lines themselves (bench.py --full): <tag>_bench.json (default command) and <tag>_<w>_bench.json next to them.
 #   Progress goes to gpurun_out/<tag>_progress.txt.  Copy what is to be judged into profiles/.
 tag=$1; shift
 WL=${@:-w2 w1 w3 w4 w1full}
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
 PROG=$R/gpurun_out/${tag}_progress.txt; : > $PROG
+OUT=${PROG%/*}                       # the folder this script writes its results to
 rm -f $R/gpurun_out/${tag}_roofline_inputs.json
 for w in $WL; do
   case $w in
@@ -38,10 +39,10 @@ done
 cd $R
 mkdir -p profiles && cp gpurun_out/${tag}_roofline_inputs.json profiles/roofline_inputs.json      # (so that the bench lines below carry the measured traffic)
 echo "$(date +%T) bench lines" >> $PROG
-python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || { tail -5 gpurun_out/${tag}_bench.err >> $PROG; exit 1; }
+python bench.py --full > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err || { tail -5 $OUT/${tag}_bench.err >> $PROG; exit 1; }
 for w in $WL; do
   [ $w = w2 ] && continue
-  python bench.py --workload $w > gpurun_out/${tag}_${w}_bench.json 2>> gpurun_out/${tag}_bench.err || { tail -5 gpurun_out/${tag}_bench.err >> $PROG; exit 1; }
+  python bench.py --full --workload $w > $OUT/${tag}_${w}_bench.json 2>> $OUT/${tag}_bench.err || { tail -5 $OUT/${tag}_bench.err >> $PROG; exit 1; }
 done
 python3 - "$tag" <<'PY'
 import json, sys
