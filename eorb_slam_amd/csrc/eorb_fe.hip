@@ -28,6 +28,15 @@ int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H);
 int orb_err_flag(eorb_ctx* c, int B, int* flag);
 int orb_err_flag_to(eorb_ctx* c, int B, int32_t* d_dst);
 int bf_knn2_dev(eorb_ctx* c, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int32_t* d_idx2, int32_t* d_dist2);
+int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR, int cap, int32_t* d_lap, int32_t* d_idx2,
+                     int32_t* d_kdist2, int32_t* d_cand, int32_t* d_dist2);
+int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A);
+constexpr int kTcMaxKpsHost = 8192;             // = kTcMaxKps (match.hip): nL + nR of a two-camera matcher
+int search_bow_fisheye_dev(eorb_ctx* c, const eorb_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
+                           const uint32_t* kf_nodes, const int32_t* kf_off, const int32_t* kf_idx, int kf_nn,
+                           const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc, const uint32_t* f_nodes, const int32_t* f_off,
+                           const int32_t* f_idx, int f_nn, int32_t* match_f, int8_t* bin_f, int32_t* histo, int32_t* nmatches,
+                           float nnratio, int checkOri);
 int search_proj_last_dev(eorb_ctx* c, const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride,
                          const uint8_t* cur_is_orb, const eorb_keypoint* last_kps, int n_last, const uint8_t* last_is_orb,
                          const uint8_t* valid, const float* uv, const uint8_t* mp_desc, const uint8_t* mp_obs,
@@ -1552,10 +1561,11 @@ static int bow_common(eorb_ctx* c, int kf_kf,
         const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
         const eorb_keypoint* f_kps, int n_f, const uint8_t* f_desc, const uint8_t* f_has_mp,
         const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
-        int32_t* match_out, float nnratio, int checkOri, int* nmatches)
+        int32_t* match_out, float nnratio, int checkOri, int* nmatches, int fisheye_nL = -1)
 {
     if (!c) return EORB_E_ARG;
     if (n_kf < 0 || n_f < 0 || kf_nn < 0 || f_nn < 0 || !match_out) return set_err(c, EORB_E_ARG, "search_by_bow: bad arguments");
+    if (fisheye_nL > n_f) return set_err(c, EORB_E_ARG, "search_by_bow_fisheye: nL %d > %d frame features", fisheye_nL, n_f);
     fe_enter(c);
     if (nmatches) *nmatches = 0;
     const int nout = kf_kf ? n_kf : n_f;
@@ -1591,6 +1601,13 @@ static int bow_common(eorb_ctx* c, int kf_kf,
     int32_t* hist = (int32_t*)c->m_j.p;
     int32_t* d_match_f = (int32_t*)c->m_h.p;
     int32_t* d_match12 = d_match_f + n_f;
+    if (fisheye_nL >= 0)
+        rc = search_bow_fisheye_dev(c, (const eorb_keypoint*)c->m_a.p, (const uint8_t*)c->m_b.p, (const uint8_t*)c->m_e.p,
+                                    (const uint32_t*)B, B + kf_nn, B + kf_nn + kf_nn + 1, kf_nn,
+                                    (const eorb_keypoint*)c->m_c.p, n_f, fisheye_nL, (const uint8_t*)c->m_d.p,
+                                    (const uint32_t*)(B + fbase), B + fbase + f_nn, B + fbase + f_nn + f_nn + 1, f_nn,
+                                    d_match_f, (int8_t*)c->m_g.p, hist, hist + 32, nnratio, checkOri);
+    else
     rc = search_bow_dev(c, (const eorb_keypoint*)c->m_a.p, (const uint8_t*)c->m_b.p, (const uint8_t*)c->m_e.p,
                         (const uint32_t*)B, B + kf_nn, B + kf_nn + kf_nn + 1, kf_nn,
                         (const eorb_keypoint*)c->m_c.p, n_f, (const uint8_t*)c->m_d.p,
@@ -1627,6 +1644,191 @@ int eorb_search_by_bow_kf(eorb_ctx* c,
     if (c && !has_mp2 && n2 > 0) return set_err(c, EORB_E_ARG, "search_by_bow_kf: has_mp2 is required");
     return bow_common(c, 1, kps1, n1, desc1, has_mp1, nodes1, node_off1, idx1, nn1, kps2, n2, desc2, has_mp2,
                       nodes2, node_off2, idx2, nn2, match12, nnratio, checkOri, nmatches);
+}
+
+int eorb_search_by_bow_fisheye(eorb_ctx* c,
+        const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
+        const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
+        const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc,
+        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
+        int32_t* match_f, float nnratio, int checkOri, int* nmatches)
+{
+    if (c && nL < 0) return set_err(c, EORB_E_ARG, "search_by_bow_fisheye: nL %d", nL);
+    return bow_common(c, 0, kf_kps, n_kf, kf_desc, kf_has_mp, kf_nodes, kf_node_off, kf_idx, kf_nn, f_kps, n_f, f_desc, nullptr,
+                      f_nodes, f_node_off, f_idx, f_nn, match_f, nnratio, checkOri, nmatches, nL);
+}
+
+// ---- two-camera frames: the frame seam and the tracking matchers ------------------------------------------------------------
+int eorb_frame_fisheye(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRight, int W, int H, int stride,
+                       int lapL0, int lapL1, int lapR0, int lapR1,
+                       eorb_keypoint* kpsL, uint8_t* descL, int* nL, int* monoLeft,
+                       eorb_keypoint* kpsR, uint8_t* descR, int* nR, int* monoRight, int cap,
+                       int32_t* right_idx, int32_t* dist2, int* ncand)
+{
+    if (!c) return EORB_E_ARG;
+    if (nL) *nL = 0; if (nR) *nR = 0; if (monoLeft) *monoLeft = 0; if (monoRight) *monoRight = 0; if (ncand) *ncand = 0;
+    if (!imLeft || !imRight || W <= 0 || H <= 0) return EORB_E_EMPTY;
+    OrbState& o = c->orb;
+    if (!o.configured) return set_err(c, EORB_E_NOTCONF, "eorb_frame_fisheye: not configured");
+    if (W != o.W || H != o.H || stride < W || cap < 0) return set_err(c, EORB_E_ARG, "eorb_frame_fisheye: the images do not match the configured %dx%d", o.W, o.H);
+    fe_enter(c);
+    int rc;
+    const size_t mo = (size_t)o.max_out;
+    Arena A(c);
+    const size_t o_imL = A.in2d(imLeft, H, (size_t)W, (size_t)stride), o_imR = A.in2d(imRight, H, (size_t)W, (size_t)stride);
+    // outputs, contiguous: {n[2], mono[2], candidates, flags[2]} | keypoints [2] | descriptors [2] | candidates | distances; then the
+    // knn scratch
+    const size_t o_n = A.reserve(64), o_kp = A.reserve(sizeof(eorb_keypoint) * mo * 2), o_desc = A.reserve(32 * mo * 2);
+    const size_t o_cand = A.reserve(sizeof(int32_t) * mo), o_d2 = A.reserve(2 * sizeof(int32_t) * mo);
+    const size_t o_end = A.reserve(0);
+    const size_t o_idx = A.reserve(2 * sizeof(int32_t) * mo), o_kd = A.reserve(2 * sizeof(int32_t) * mo);
+    if ((rc = A.upload())) return rc;
+    int32_t* dn = A.dev<int32_t>(o_n);
+    EORB_HIP(c, hipMemsetAsync(dn, 0, 64, c->stream));
+    // ExtractORB(0, imLeft, mvLappingArea of mpCamera) and ExtractORB(1, imRight, mvLappingArea of mpCamera2) (Frame.cc:1124-1129):
+    // two launches, each with its own lapping area
+    rc = orb_extract_dev(c, A.dev<uint8_t>(o_imL), W, 0, 1, lapL0, lapL1, 1, A.dev<eorb_keypoint>(o_kp), A.dev<uint8_t>(o_desc), nullptr, dn, dn + 2, dn + 5);
+    if (rc) return rc;
+    rc = orb_extract_dev(c, A.dev<uint8_t>(o_imR), W, 0, 1, lapR0, lapR1, 1, A.dev<eorb_keypoint>(o_kp) + mo, A.dev<uint8_t>(o_desc) + 32 * mo,
+                         nullptr, dn + 1, dn + 3, dn + 6);
+    if (rc) return rc;
+    if ((rc = fisheye_lowe_dev(c, A.dev<uint8_t>(o_desc), A.dev<uint8_t>(o_desc) + 32 * mo, (int)mo, dn, A.dev<int32_t>(o_idx), A.dev<int32_t>(o_kd),
+                               A.dev<int32_t>(o_cand), A.dev<int32_t>(o_d2)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_n, o_end - o_n, &h))) return rc;
+    const int32_t* hn = (const int32_t*)(h + o_n);
+    if (hn[5] || hn[6]) return set_err(c, EORB_E_CAPACITY, "eorb_frame_fisheye: internal capacity exceeded (flags %d, %d)", hn[5], hn[6]);
+    if (hn[0] > cap || hn[1] > cap) return set_err(c, EORB_E_CAPACITY, "eorb_frame_fisheye: %d / %d keypoints > caller capacity %d", hn[0], hn[1], cap);
+    if (hn[0] > 0) {
+        if (kpsL) memcpy(kpsL, h + o_kp, sizeof(eorb_keypoint) * (size_t)hn[0]);
+        if (descL) memcpy(descL, h + o_desc, 32 * (size_t)hn[0]);
+        if (right_idx) memcpy(right_idx, h + o_cand, sizeof(int32_t) * (size_t)hn[0]);
+        if (dist2) memcpy(dist2, h + o_d2, 2 * sizeof(int32_t) * (size_t)hn[0]);
+    }
+    if (hn[1] > 0) {
+        if (kpsR) memcpy(kpsR, h + o_kp + sizeof(eorb_keypoint) * mo, sizeof(eorb_keypoint) * (size_t)hn[1]);
+        if (descR) memcpy(descR, h + o_desc + 32 * mo, 32 * (size_t)hn[1]);
+    }
+    if (nL) *nL = hn[0];
+    if (nR) *nR = hn[1];
+    if (monoLeft) *monoLeft = hn[2];
+    if (monoRight) *monoRight = hn[3];
+    if (ncand) *ncand = hn[4];
+    return EORB_OK;
+}
+
+// the searched two-camera frame's checks shared by the two projection matchers: sizes, octaves (the kernel keeps levels in 8 bits),
+// slot states (-3 .. nq - 1)
+static int twocam_frame_check(eorb_ctx* c, const char* who, const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
+                              const int32_t* slots, int nq)
+{
+    const int nT = nL + nR;
+    if (nL < 0 || nR < 0 || nq < 0 || stride < 32 || !slots || (nT > 0 && (!kps || !desc))) return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
+    if (nT > kTcMaxKpsHost) return set_err(c, EORB_E_CAPACITY, "%s: %d keypoints > %d", who, nT, kTcMaxKpsHost);
+    if (nq >= (1 << 24)) return set_err(c, EORB_E_CAPACITY, "%s: %d queries >= 2^24", who, nq);
+    for (int i = 0; i < nT; i++) {
+        if (kps[i].octave < 0 || kps[i].octave > 127) return set_err(c, EORB_E_ARG, "%s: keypoint %d has octave %d outside [0, 127]", who, i, kps[i].octave);
+        if (slots[i] < -3 || slots[i] >= nq) return set_err(c, EORB_E_ARG, "%s: slot %d holds %d", who, i, slots[i]);
+    }
+    return EORB_OK;
+}
+
+int eorb_search_by_projection_map_fisheye(eorb_ctx* c,
+        const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride, const int32_t* l2r, const int32_t* r2l,
+        int M, const uint8_t* in_view, const float* proj_xy, const int32_t* level, const float* view_cos, const float* level_scale,
+        const uint8_t* in_view_r, const float* proj_xy_r, const int32_t* level_r, const float* view_cos_r, const float* level_scale_r,
+        const uint8_t* mp_desc, const uint8_t* mp_obs, const eorb_grid_bounds* gb, int32_t* frame_mp, float th, float nnratio,
+        int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    if (nmatches) *nmatches = 0;
+    if (!gb || M < 0 || (M > 0 && (!in_view || !proj_xy || !level || !view_cos || !level_scale || !in_view_r || !proj_xy_r || !level_r ||
+                                   !view_cos_r || !level_scale_r || !mp_desc || !mp_obs)) ||
+        (nL > 0 && !l2r) || (nR > 0 && !r2l))
+        return set_err(c, EORB_E_ARG, "search_by_projection_map_fisheye: bad arguments");
+    int rc;
+    if ((rc = twocam_frame_check(c, "search_by_projection_map_fisheye", kps, nL, nR, desc, stride, frame_mp, M))) return rc;
+    for (int i = 0; i < nL; i++) if (l2r[i] < -1 || l2r[i] >= nR) return set_err(c, EORB_E_ARG, "search_by_projection_map_fisheye: l2r[%d] = %d", i, l2r[i]);
+    for (int i = 0; i < nR; i++) if (r2l[i] < -1 || r2l[i] >= nL) return set_err(c, EORB_E_ARG, "search_by_projection_map_fisheye: r2l[%d] = %d", i, r2l[i]);
+    fe_enter(c);
+    const int nT = nL + nR;
+    if (M == 0 || nT == 0) return EORB_OK;
+    Arena A(c);
+    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)nT), o_d = A.in(desc, (size_t)stride * nT);
+    const size_t o_l2r = A.in(l2r, sizeof(int32_t) * (size_t)nL), o_r2l = A.in(r2l, sizeof(int32_t) * (size_t)nR);
+    const size_t o_md = A.in(mp_desc, 32 * (size_t)M);
+    // per map point and camera: proj x, proj y, view cos, level scale
+    std::vector<float> f4(8 * (size_t)M);
+    for (int m = 0; m < M; m++) {
+        float* l = &f4[4 * (size_t)m]; float* r = &f4[4 * ((size_t)M + m)];
+        l[0] = proj_xy[2 * m]; l[1] = proj_xy[2 * m + 1]; l[2] = view_cos[m]; l[3] = level_scale[m];
+        r[0] = proj_xy_r[2 * m]; r[1] = proj_xy_r[2 * m + 1]; r[2] = view_cos_r[m]; r[3] = level_scale_r[m];
+    }
+    const size_t o_f4 = A.in(f4.data(), sizeof(float) * f4.size());
+    const size_t o_lv = A.in(level, sizeof(int32_t) * (size_t)M), o_lvr = A.in(level_r, sizeof(int32_t) * (size_t)M);
+    const size_t o_iv = A.in(in_view, M), o_ivr = A.in(in_view_r, M), o_ob = A.in(mp_obs, M);
+    const size_t o_nm = A.in(nullptr, 16);
+    const size_t o_fm = A.in(frame_mp, sizeof(int32_t) * (size_t)nT);
+    if ((rc = A.upload())) return rc;
+    TcArgs T{};
+    T.kps = A.dev<eorb_keypoint>(o_k); T.nL = nL; T.nR = nR; T.desc = A.dev<uint8_t>(o_d); T.stride = stride;
+    T.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
+    T.nq = M; T.mp_desc = A.dev<uint8_t>(o_md); T.mp_obs = A.dev<uint8_t>(o_ob); T.th = th; T.nnratio = nnratio;
+    T.in_view = A.dev<uint8_t>(o_iv); T.qf = A.dev<float4>(o_f4); T.qlevel = A.dev<int32_t>(o_lv);
+    T.in_view_r = A.dev<uint8_t>(o_ivr); T.qf_r = A.dev<float4>(o_f4) + M; T.qlevel_r = A.dev<int32_t>(o_lvr);
+    T.l2r = A.dev<int32_t>(o_l2r); T.r2l = A.dev<int32_t>(o_r2l);
+    T.slots = A.dev<int32_t>(o_fm); T.nmatches = A.dev<int32_t>(o_nm);
+    if ((rc = twocam_walk_dev(c, 0, T))) return rc;
+    const char* h;
+    if ((rc = A.download(o_nm, o_fm + sizeof(int32_t) * (size_t)nT - o_nm, &h))) return rc;
+    memcpy(frame_mp, h + o_fm, sizeof(int32_t) * (size_t)nT);
+    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
+    return EORB_OK;
+}
+
+int eorb_search_by_projection_last_fisheye(eorb_ctx* c,
+        const eorb_keypoint* cur_kps, int nL, int nR, const uint8_t* cur_desc, int cur_stride,
+        const eorb_keypoint* last_kps, int n_last, const uint8_t* valid, const float* uv, const float* uv_r,
+        const uint8_t* mp_desc, const uint8_t* mp_obs, const float* level_scale, const eorb_grid_bounds* gb,
+        int32_t* cur_mp, float th, int mode, int checkOri, int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    if (nmatches) *nmatches = 0;
+    if (!gb || n_last < 0 || mode < 0 || mode > 2 ||
+        (n_last > 0 && (!last_kps || !valid || !uv || !uv_r || !mp_desc || !mp_obs || !level_scale)))
+        return set_err(c, EORB_E_ARG, "search_by_projection_last_fisheye: bad arguments");
+    int rc;
+    if ((rc = twocam_frame_check(c, "search_by_projection_last_fisheye", cur_kps, nL, nR, cur_desc, cur_stride, cur_mp, n_last))) return rc;
+    fe_enter(c);
+    const int nT = nL + nR;
+    if (n_last == 0 || nT == 0) return EORB_OK;
+    Arena A(c);
+    const size_t o_k = A.in(cur_kps, sizeof(eorb_keypoint) * (size_t)nT), o_d = A.in(cur_desc, (size_t)cur_stride * nT);
+    const size_t o_lk = A.in(last_kps, sizeof(eorb_keypoint) * (size_t)n_last), o_md = A.in(mp_desc, 32 * (size_t)n_last);
+    std::vector<float> f5(5 * (size_t)n_last);
+    for (int i = 0; i < n_last; i++) {
+        float* f = &f5[5 * (size_t)i];
+        f[0] = uv[2 * i]; f[1] = uv[2 * i + 1]; f[2] = uv_r[2 * i]; f[3] = uv_r[2 * i + 1]; f[4] = level_scale[i];
+    }
+    const size_t o_f5 = A.in(f5.data(), sizeof(float) * f5.size());
+    const size_t o_va = A.in(valid, n_last), o_ob = A.in(mp_obs, n_last);
+    const size_t o_nm = A.in(nullptr, 16);
+    const size_t o_mp = A.in(cur_mp, sizeof(int32_t) * (size_t)nT);
+    const size_t o_rec = A.reserve(2 * sizeof(int32_t) * (size_t)n_last);
+    if ((rc = A.upload())) return rc;
+    TcArgs T{};
+    T.kps = A.dev<eorb_keypoint>(o_k); T.nL = nL; T.nR = nR; T.desc = A.dev<uint8_t>(o_d); T.stride = cur_stride;
+    T.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
+    T.nq = n_last; T.mp_desc = A.dev<uint8_t>(o_md); T.mp_obs = A.dev<uint8_t>(o_ob); T.th = th;
+    T.valid = A.dev<uint8_t>(o_va); T.quv = A.dev<float>(o_f5); T.qkps = A.dev<eorb_keypoint>(o_lk); T.mode = mode; T.checkOri = checkOri;
+    T.rec = A.dev<int32_t>(o_rec);
+    T.slots = A.dev<int32_t>(o_mp); T.nmatches = A.dev<int32_t>(o_nm);
+    if ((rc = twocam_walk_dev(c, 1, T))) return rc;
+    const char* h;
+    if ((rc = A.download(o_nm, o_mp + sizeof(int32_t) * (size_t)nT - o_nm, &h))) return rc;
+    memcpy(cur_mp, h + o_mp, sizeof(int32_t) * (size_t)nT);
+    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
+    return EORB_OK;
 }
 
 int eorb_search_for_triangulation(eorb_ctx* c,

@@ -30,9 +30,17 @@ constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;      // ORBmatcher.
 template <int LPQ>
 __global__ __launch_bounds__(256) void bf_knn2_kernel(const uint8_t* __restrict__ q, int nq,
                                                       const uint8_t* __restrict__ t, int nt,
-                                                      int32_t* __restrict__ idx2, int32_t* __restrict__ dist2)
+                                                      int32_t* __restrict__ idx2, int32_t* __restrict__ dist2,
+                                                      const int32_t* __restrict__ lap = nullptr)
 {
     __shared__ uint64_t tile[256 * 4];
+    if (lap) {
+        // the lapping rows of a two-camera frame, counts read on the device: lap = {nL, nR, monoLeft, monoRight} (orb_extract_dev's
+        // n / mono outputs); queries = left rows monoLeft.., train = right rows monoRight.. (ComputeStereoFishEyeMatches, Frame.cc:1216-1228)
+        const int mq = lap[2], mt = lap[3];
+        q += (size_t)mq * 32; nq = max(lap[0] - mq, 0);
+        t += (size_t)mt * 32; nt = max(lap[1] - mt, 0);
+    }
     const int tid = threadIdx.x;
     const int part = tid & (LPQ - 1);
     const int qi = blockIdx.x * (256 / LPQ) + tid / LPQ;
@@ -1750,6 +1758,386 @@ int bf_knn2_dev(eorb_ctx* c, const uint8_t* d_q, int nq, const uint8_t* d_t, int
     else if (nq >= 8 * 512) bf_knn2_kernel<32><<<(nq + 7) / 8, 256, 0, c->stream>>>(d_q, nq, d_t, nt, d_idx2, d_dist2);
     else bf_knn2_kernel<64><<<(nq + 3) / 4, 256, 0, c->stream>>>(d_q, nq, d_t, nt, d_idx2, d_dist2);
     EORB_LAUNCH_CHECK(c, "bf_knn2_kernel");
+    return EORB_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------------
+// Two-camera (fisheye stereo) frames: Frame::Frame(imLeft, imRight, ..., pCamera, pCamera2, Tlr) (src/Frame.cc:1101-1208) and the
+// numKPtsLeft() != -1 branches of the tracking matchers.  A frame holds nL left keypoints followed by nR right ones (mvKeys, then
+// mvKeysRight; descriptors concatenated, :1176) and two grids over the same bounds (AssignFeaturesToGrid :431-460: the left grid
+// holds mvKeys, the right one mvKeysRight).
+
+// ComputeStereoFishEyeMatches (:1210-1250) after the knnMatch of the lapping rows (bf_knn2_kernel with `lap`): Lowe's test
+// "size() >= 2 && [0].distance < [1].distance * 0.7" (:1233; float distances against a double product).  Per left keypoint:
+// cand = right keypoint index (trainIdx + monoRight) or -1, dist2 = the two knn distances (-1: none / outside the lapping area).
+// lap = {nL, nR, monoLeft, monoRight}; lap[4] counts the candidates (zeroed by the caller).
+__global__ __launch_bounds__(256) void fisheye_lowe_kernel(int32_t* __restrict__ lap, const int32_t* __restrict__ idx2,
+                                                           const int32_t* __restrict__ kdist2, int cap, int32_t* __restrict__ cand,
+                                                           int32_t* __restrict__ dist2)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nL = lap[0], mL = lap[2], mR = lap[3];
+    if (i >= cap || i >= nL) return;
+    int c = -1, d0 = -1, d1 = -1;
+    if (i >= mL) {
+        const int qi = i - mL;
+        const int i0 = idx2[2 * qi], i1 = idx2[2 * qi + 1];
+        if (i0 >= 0) d0 = kdist2[2 * qi];
+        if (i1 >= 0) d1 = kdist2[2 * qi + 1];
+        if (i1 >= 0 && (double)(float)d0 < (double)(float)d1 * 0.7) { c = i0 + mR; atomicAdd(&lap[4], 1); }
+    }
+    cand[i] = c; dist2[2 * i] = d0; dist2[2 * i + 1] = d1;
+}
+
+int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR, int cap, int32_t* d_lap, int32_t* d_idx2,
+                     int32_t* d_kdist2, int32_t* d_cand, int32_t* d_dist2)
+{
+    if (cap <= 0) return EORB_OK;
+    ProfScope ps(c, "fisheye_stereo_matches");
+    // (the launch covers every row a frame can have: the kernel takes the counts from the device)
+    bf_knn2_kernel<64><<<(cap + 3) / 4, 256, 0, c->stream>>>(d_descL, cap, d_descR, cap, d_idx2, d_kdist2, d_lap);
+    fisheye_lowe_kernel<<<(cap + 255) / 256, 256, 0, c->stream>>>(d_lap, d_idx2, d_kdist2, cap, d_cand, d_dist2);
+    EORB_LAUNCH_CHECK(c, "fisheye stereo matches");
+    return EORB_OK;
+}
+
+// The two tracking SearchByProjection overloads on a two-camera frame (ORBmatcher.cc:44-219 and :1969-2187).  Every query makes a
+// left and a right sub-query, and a match can claim two slots (the partner links); later queries see those slots through the
+// Observations() > 0 test in both camera spaces, so the sub-queries run in the reference's order.  One workgroup builds both grids
+// in LDS (cell starts, keypoint positions, levels, slot states); then one wavefront walks the sub-queries: lanes over the window's
+// cells, each lane over its cell's keypoints, the two smallest keys by wave reduction.  key = dist << 44 | cell << 32 | index << 8
+// | level + 1: the reference's candidate order (cell ix, cell iy, insertion index) rides in the key for the tie-breaks, as in
+// win_key.  Descriptors are read from global memory (only those of window candidates).
+constexpr int kTcCells = kGridCols * kGridRows;
+constexpr int kTcMaxKps = 8192;                  // nL + nR: 16 B of LDS each next to the 2 x 3072 cell starts
+constexpr int32_t kTcObs = 1 << 30;              // slot state bit: the slot's map point has Observations() > 0
+
+
+struct TcLds {
+    uint32_t* cst;                               // 2 * kTcCells: after the build, cst[x] = end of cell x = start of cell x + 1
+    float2* pos; int32_t* slot; uint16_t* item; int8_t* lgate; int8_t* lbest;
+};
+
+__device__ __forceinline__ void tc_top2(uint64_t key, uint64_t& k0, uint64_t& k1)
+{
+    if (key < k0) { k1 = k0; k0 = key; }
+    else if (key < k1) k1 = key;
+}
+
+__device__ __forceinline__ void tc_wave_top2(uint64_t& k0, uint64_t& k1)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint64_t o0 = __shfl_xor(k0, d, 64), o1 = __shfl_xor(k1, d, 64);
+        const uint64_t l0 = k0 < o0 ? k0 : o0, h0 = k0 < o0 ? o0 : k0, s1 = k1 < o1 ? k1 : o1;
+        k0 = l0; k1 = h0 < s1 ? h0 : s1;
+    }
+}
+
+// Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel, bRight = cam) (src/Frame.cc:710-781) + the Observations() > 0 skip +
+// DescriptorDistance.  The level gate reads getKPtLevelMono(j) (:763), i.e. lgate (see the build).  Result: the two smallest keys
+// in every lane; *hit = the window was not empty (before the slot test).
+__device__ void tc_search(const TcArgs& A, const TcLds& S, int cam, float qx, float qy, float r, int minL, int maxL,
+                          const uint64_t* qd, int lane, uint64_t& k0, uint64_t& k1, bool& hit)
+{
+    k0 = k1 = ~0ull; hit = false;
+    int cx0, cx1, cy0, cy1;
+    if (!cell_range(A.g, qx, qy, r, cx0, cx1, cy0, cy1)) return;
+    const int ncy = cy1 - cy0 + 1, nc = (cx1 - cx0 + 1) * ncy;
+    const bool chk = (minL > 0) || (maxL >= 0);
+    bool any = false;
+    for (int ci = lane; ci < nc; ci += 64) {
+        const int ix = cx0 + ci / ncy, iy = cy0 + ci % ncy;
+        const int cell = ix * kGridRows + iy, x = cam * kTcCells + cell;
+        const uint32_t e = S.cst[x];
+        for (uint32_t p = x ? S.cst[x - 1] : 0u; p < e; p++) {
+            const int gi = S.item[p];
+            if (chk) {
+                const int lv = S.lgate[gi];
+                if (lv < minL) continue;
+                if (maxL >= 0 && lv > maxL) continue;
+            }
+            const float2 P = S.pos[gi];
+            if (!(fabsf(P.x - qx) < r && fabsf(P.y - qy) < r)) continue;
+            any = true;
+            const int32_t sv = S.slot[gi];
+            if (sv == -2 || (sv >= 0 && (sv & kTcObs))) continue;              // getMapPoint(idx)->Observations() > 0
+            uint64_t t0, t1, t2, t3;
+            load_desc32(A.desc + (size_t)gi * A.stride, t0, t1, t2, t3);
+            const int dist = __popcll(qd[0] ^ t0) + __popcll(qd[1] ^ t1) + __popcll(qd[2] ^ t2) + __popcll(qd[3] ^ t3);
+            if (dist >= 256) continue;                                          // (never below bestDist = 256)
+            tc_top2(((uint64_t)dist << 44) | ((uint64_t)cell << 32) | ((uint64_t)(uint32_t)gi << 8) | (uint64_t)((S.lbest[gi] + 1) & 0xff), k0, k1);
+        }
+    }
+    hit = __ballot(any) != 0;
+    tc_wave_top2(k0, k1);
+}
+
+__device__ __forceinline__ int tc_dist(uint64_t k) { return k == ~0ull ? 256 : (int)(k >> 44); }
+__device__ __forceinline__ int tc_idx(uint64_t k) { return (int)((k >> 8) & 0xffffffu); }
+__device__ __forceinline__ int tc_level(uint64_t k) { return k == ~0ull ? -1 : (int)(k & 0xffu) - 1; }
+
+// slot write by lane 0, seen by the wavefront's next sub-query
+__device__ __forceinline__ void tc_set(const TcLds& S, int lane, int gi, int32_t v)
+{
+    if (lane == 0) S.slot[gi] = v;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void twocam_walk_kernel(TcArgs A)
+{
+    extern __shared__ unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int nL = A.nL, nT = A.nL + A.nR;
+    TcLds S;
+    S.cst = (uint32_t*)smem;
+    S.pos = (float2*)(smem + (((size_t)2 * kTcCells * 4 + 15) & ~(size_t)15));
+    S.slot = (int32_t*)(S.pos + nT);
+    S.item = (uint16_t*)(S.slot + nT);
+    S.lgate = (int8_t*)(S.item + nT);
+    S.lbest = S.lgate + nT;
+    __shared__ uint32_t s_part[256];
+    __shared__ int s_hist[HISTO_LENGTH];
+    // ---- both grids (AssignFeaturesToGrid :431-460): counts, scan, placement ----
+    for (int i = tid; i < 2 * kTcCells; i += blockDim.x) S.cst[i] = 0;
+    if (tid < HISTO_LENGTH) s_hist[tid] = 0;
+    __syncthreads();
+    for (int gi = tid; gi < nT; gi += blockDim.x) {
+        const eorb_keypoint k = A.kps[gi];
+        const int cam = gi >= nL;
+        S.pos[gi] = make_float2(k.x, k.y);
+        S.lbest[gi] = (int8_t)k.octave;
+        // getKPtLevelMono(j) = mvKeysUn[j].octave for the right grid's j too (Frame.cc:763, :1417-1420): LEFT keypoint j; for j >= nL
+        // (past mvKeysUn) the right keypoint's own octave (upstream ORB-SLAM3's reading)
+        const int j = gi - nL;
+        S.lgate[gi] = (int8_t)(cam && j < nL ? A.kps[j].octave : k.octave);
+        int32_t v = A.slots[gi];
+        if (v >= 0 && A.mp_obs[v]) v |= kTcObs;
+        S.slot[gi] = v;
+        const int px = (int)roundf((k.x - A.g.minX) * A.g.invW), py = (int)roundf((k.y - A.g.minY) * A.g.invH);   // PosInGrid :783-793
+        if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) atomicAdd(&S.cst[cam * kTcCells + px * kGridRows + py], 1u);
+    }
+    __syncthreads();
+    {   // exclusive scan of the 2 * kTcCells counts: chunk per thread, then the chunk totals
+        const int per = (2 * kTcCells + (int)blockDim.x - 1) / (int)blockDim.x;
+        const int lo = tid * per, hi = min(lo + per, 2 * kTcCells);
+        uint32_t sum = 0;
+        for (int i = lo; i < hi; i++) sum += S.cst[i];
+        s_part[tid] = sum;
+        __syncthreads();
+        for (int o = 1; o < (int)blockDim.x; o <<= 1) {
+            const uint32_t add = tid >= o ? s_part[tid - o] : 0u;
+            __syncthreads();
+            s_part[tid] += add;
+            __syncthreads();
+        }
+        uint32_t run = tid ? s_part[tid - 1] : 0u;
+        for (int i = lo; i < hi; i++) { const uint32_t n = S.cst[i]; S.cst[i] = run; run += n; }
+    }
+    __syncthreads();
+    for (int gi = tid; gi < nT; gi += blockDim.x) {
+        const float2 P = S.pos[gi];
+        const int px = (int)roundf((P.x - A.g.minX) * A.g.invW), py = (int)roundf((P.y - A.g.minY) * A.g.invH);
+        if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows)
+            S.item[atomicAdd(&S.cst[(gi >= nL) * kTcCells + px * kGridRows + py], 1u)] = (uint16_t)gi;   // (order inside a cell: the key's index)
+    }
+    __syncthreads();
+    if (tid >= 64) return;
+    // ---- the sub-queries, in the reference's order ----
+    int nm = 0, nrec = 0;
+    for (int q = 0; q < A.nq; q++) {
+        uint64_t qd[4];
+        const uint64_t* dq = (const uint64_t*)(A.mp_desc + (size_t)q * 32);
+        uint64_t k0, k1; bool hit;
+        if (KIND == 0) {
+            const bool iv = A.in_view[q] != 0, ivr = A.in_view_r[q] != 0 && A.qlevel_r[q] != -1;
+            if (!iv && !ivr) continue;
+            qd[0] = dq[0]; qd[1] = dq[1]; qd[2] = dq[2]; qd[3] = dq[3];
+            const int32_t mark = q | (A.mp_obs[q] ? kTcObs : 0);
+            if (iv) {
+                const float4 f = A.qf[q];
+                const int lev = A.qlevel[q];
+                float r = ((double)f.z > 0.998) ? 2.5f : 4.0f;                  // RadiusByViewingCos (:221-227)
+                if (A.th != 1.0f) r *= A.th;                                    // bFactor (:49, :70-71)
+                tc_search(A, S, 0, f.x, f.y, r * f.w, lev - 1, lev, qd, lane, k0, k1, hit);
+                const int bestDist = tc_dist(k0);
+                if (bestDist <= TH_HIGH) {
+                    const int bestLevel = tc_level(k0), bestLevel2 = tc_level(k1), bestDist2 = tc_dist(k1);
+                    if (bestLevel == bestLevel2 && (float)bestDist > A.nnratio * (float)bestDist2) continue;   // :130: no right search either
+                    const int bestIdx = tc_idx(k0);
+                    tc_set(S, lane, bestIdx, mark); nm++;
+                    const int rj = A.l2r[bestIdx];
+                    if (rj != -1) { tc_set(S, lane, nL + rj, mark); nm++; }     // :136-137
+                }
+            }
+            if (ivr) {
+                const float4 f = A.qf_r[q];
+                const int lev = A.qlevel_r[q];
+                const float r = ((double)f.z > 0.998) ? 2.5f : 4.0f;            // mTrackViewCosR, no th (:152)
+                tc_search(A, S, 1, f.x, f.y, r * f.w, lev - 1, lev, qd, lane, k0, k1, hit);
+                const int bestDist = tc_dist(k0);
+                if (bestDist <= TH_HIGH) {
+                    const int bestLevel = tc_level(k0), bestLevel2 = tc_level(k1), bestDist2 = tc_dist(k1);
+                    if (bestLevel == bestLevel2 && (float)bestDist > A.nnratio * (float)bestDist2) continue;
+                    const int bestIdx = tc_idx(k0) - nL;
+                    const int li = A.r2l[bestIdx];
+                    if (li != -1) { tc_set(S, lane, li, mark); nm++; }         // :204-205
+                    tc_set(S, lane, nL + bestIdx, mark); nm++;
+                }
+            }
+        } else {
+            if (!A.valid[q]) continue;
+            qd[0] = dq[0]; qd[1] = dq[1]; qd[2] = dq[2]; qd[3] = dq[3];
+            const float* u = A.quv + (size_t)q * 5;
+            const eorb_keypoint qk = A.qkps[q];
+            const int oct = qk.octave;                                          // getKPtLevelMono(i) (:2014, :2114)
+            const float radius = A.th * u[4];
+            const int minL = A.mode == 1 ? oct : (A.mode == 2 ? 0 : oct - 1);
+            const int maxL = A.mode == 1 ? -1 : (A.mode == 2 ? oct : oct + 1);
+            const int32_t mark = q | (A.mp_obs[q] ? kTcObs : 0);
+            tc_search(A, S, 0, u[0], u[1], radius, minL, maxL, qd, lane, k0, k1, hit);
+            if (!hit) continue;                                                 // vIndices2.empty() (:2032-2033): no right search
+            if (tc_dist(k0) <= TH_HIGH) {
+                const int gi = tc_idx(k0);
+                tc_set(S, lane, gi, mark); nm++;
+                if (A.checkOri) {
+                    const int bin = rot_bin(qk.angle, A.kps[gi].angle);
+                    if (lane == 0) { A.rec[nrec] = gi << 5 | bin; s_hist[bin]++; }
+                    nrec++;
+                }
+            }
+            tc_search(A, S, 1, u[2], u[3], radius, minL, maxL, qd, lane, k0, k1, hit);    // (:2116-2123: no bounds check)
+            if (tc_dist(k0) <= TH_HIGH) {
+                const int gi = tc_idx(k0);
+                tc_set(S, lane, gi, mark); nm++;
+                if (A.checkOri) {
+                    const int bin = rot_bin(qk.angle, A.kps[gi].angle);         // rotHist gets nL + j (:2155)
+                    if (lane == 0) { A.rec[nrec] = gi << 5 | bin; s_hist[bin]++; }
+                    nrec++;
+                }
+            }
+        }
+    }
+    if (KIND == 1 && A.checkOri) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        int h[HISTO_LENGTH];
+        for (int i = 0; i < HISTO_LENGTH; i++) h[i] = s_hist[i];
+        int i1, i2, i3;
+        three_maxima(h, HISTO_LENGTH, i1, i2, i3);                              // ComputeThreeMaxima (:2167-2184): both camera spaces
+        int drop = 0;
+        for (int e = lane; e < nrec; e += 64) {
+            const int32_t rv = A.rec[e];
+            const int b = rv & 31;
+            if (b != i1 && b != i2 && b != i3) { S.slot[rv >> 5] = -1; drop++; }   // setMapPoint(NULL); nmatches-- per entry
+        }
+        nm -= wave_sum_i32(drop);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
+    for (int gi = lane; gi < nT; gi += 64) {
+        const int32_t v = S.slot[gi];
+        A.slots[gi] = v >= 0 ? (v & ~kTcObs) : v;
+    }
+    if (lane == 0) *A.nmatches = nm;
+}
+
+int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A)
+{
+    const int nT = A.nL + A.nR;
+    if (nT > kTcMaxKps) return set_err(c, EORB_E_CAPACITY, "two-camera matcher: %d keypoints > %d", nT, kTcMaxKps);
+    const size_t lds = (((size_t)2 * kTcCells * 4 + 15) & ~(size_t)15) + (size_t)nT * 16;
+    static bool attr[2] = {false, false};
+    if (!attr[kind]) {
+        EORB_HIP(c, hipFuncSetAttribute(kind ? (const void*)twocam_walk_kernel<1> : (const void*)twocam_walk_kernel<0>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
+        attr[kind] = true;
+    }
+    ProfScope ps(c, kind ? "twocam_last" : "twocam_map");
+    if (kind) twocam_walk_kernel<1><<<1, 256, lds, c->stream>>>(A);
+    else twocam_walk_kernel<0><<<1, 256, lds, c->stream>>>(A);
+    EORB_LAUNCH_CHECK(c, "twocam_walk_kernel");
+    return EORB_OK;
+}
+
+// SearchByBoW(KeyFrame*, Frame&) on a two-camera frame (ORBmatcher.cc:276-478): per KeyFrame feature two best / second-best pairs,
+// one over the frame's left features (index < nL) and one over its right ones (:357-377); the right best is taken only inside
+// "if(bestDist1 <= TH_LOW)" (:410) and its ratio test is "... || true" (:412).  A frame feature belongs to one vocabulary node, so
+// nodes run concurrently as in search_bow_kernel: one wavefront per node, KeyFrame features in order, lanes over the node's frame
+// features.  The rotation check reuses search_bow_finish_kernel (every frame slot is matched at most once).
+__global__ __launch_bounds__(256) void search_bow_fisheye_kernel(BowArgs A, int nL)
+{
+    const int lane = threadIdx.x & 63;
+    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+    for (int a = gw; a < A.kf_nn; a += nw) {
+        const uint32_t node = A.kf_nodes[a];
+        int lo = -1;
+        for (int base = 0; base < A.f_nn && lo < 0; base += 64) {
+            const int pos = base + lane;
+            const uint64_t hit = __ballot(pos < A.f_nn && A.f_nodes[pos] == node);
+            if (hit) lo = base + __ffsll((unsigned long long)hit) - 1;
+        }
+        if (lo < 0) continue;
+        const int f0 = A.f_off[lo], f1 = A.f_off[lo + 1];
+        for (int iKF = A.kf_off[a]; iKF < A.kf_off[a + 1]; iKF++) {
+            const int realIdxKF = A.kf_idx[iKF];
+            if (!A.kf_has_mp[realIdxKF]) continue;
+            const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)realIdxKF * 32);
+            const uint64_t q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3];
+            uint64_t l0 = ~0ull, l1 = ~0ull, r0 = ~0ull, r1 = ~0ull;         // key = dist << 32 | iF (vector order breaks ties)
+            for (int iF = f0 + lane; iF < f1; iF += 64) {
+                const int realIdxF = A.f_idx[iF];
+                if (__hip_atomic_load(&A.match_f[realIdxF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) continue;
+                const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)realIdxF * 32);
+                const int dist = __popcll(q0 ^ tp[0]) + __popcll(q1 ^ tp[1]) + __popcll(q2 ^ tp[2]) + __popcll(q3 ^ tp[3]);
+                if (dist >= 256) continue;
+                const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)iF;
+                if (realIdxF < nL) tc_top2(key, l0, l1); else tc_top2(key, r0, r1);
+            }
+            tc_wave_top2(l0, l1);
+            tc_wave_top2(r0, r1);
+            const int bestDist1 = l0 == ~0ull ? 256 : (int)(l0 >> 32);
+            if (bestDist1 > TH_LOW) continue;
+            const int bestDist2 = l1 == ~0ull ? 256 : (int)(l1 >> 32);
+            if (lane == 0) {
+                const float ka = A.kf_kps[realIdxKF].angle;
+                if ((float)bestDist1 < A.nnratio * (float)bestDist2) {
+                    const int bestIdxF = A.f_idx[(int)(l0 & 0xffffffffu)];
+                    __hip_atomic_store(&A.match_f[bestIdxF], realIdxKF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    atomicAdd(A.nmatches, 1);
+                    if (A.checkOri) { const int bin = rot_bin(ka, A.f_kps[bestIdxF].angle); A.bin_f[bestIdxF] = (int8_t)bin; atomicAdd(&A.histo[bin], 1); }
+                }
+                if (r0 != ~0ull && (int)(r0 >> 32) <= TH_LOW) {                  // ratio "|| true" (:412)
+                    const int bestIdxFR = A.f_idx[(int)(r0 & 0xffffffffu)];
+                    __hip_atomic_store(&A.match_f[bestIdxFR], realIdxKF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    atomicAdd(A.nmatches, 1);
+                    if (A.checkOri) { const int bin = rot_bin(ka, A.f_kps[bestIdxFR].angle); A.bin_f[bestIdxFR] = (int8_t)bin; atomicAdd(&A.histo[bin], 1); }
+                }
+            }
+            __threadfence();          // the next KeyFrame feature of this node must see match_f
+        }
+    }
+}
+
+int search_bow_fisheye_dev(eorb_ctx* c, const eorb_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
+                           const uint32_t* kf_nodes, const int32_t* kf_off, const int32_t* kf_idx, int kf_nn,
+                           const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc, const uint32_t* f_nodes, const int32_t* f_off,
+                           const int32_t* f_idx, int f_nn, int32_t* match_f, int8_t* bin_f, int32_t* histo, int32_t* nmatches,
+                           float nnratio, int checkOri)
+{
+    BowArgs A{kf_kps, kf_desc, kf_has_mp, kf_nodes, kf_off, kf_idx, kf_nn, f_kps, n_f, f_desc, f_nodes, f_off, f_idx, f_nn,
+              match_f, bin_f, histo, nmatches, nnratio, checkOri, 0, nullptr, nullptr, 0};
+    ProfScope ps(c, "search_bow_fisheye");
+    bow_init_kernel<<<(std::max(n_f, 32) + 255) / 256, 256, 0, c->stream>>>(match_f, bin_f, n_f, histo, nmatches, nullptr, 0);
+    if (kf_nn > 0 && f_nn > 0) {
+        const int blocks = std::min((kf_nn + 3) / 4, 1024);
+        search_bow_fisheye_kernel<<<blocks, 256, 0, c->stream>>>(A, nL);
+        if (checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A);
+    }
+    EORB_LAUNCH_CHECK(c, "search_bow_fisheye kernels");
     return EORB_OK;
 }
 

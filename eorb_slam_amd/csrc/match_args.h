@@ -33,4 +33,18 @@ struct BowVoc {
     const int32_t* child_off; const int32_t* child_ids; const uint8_t* node_desc; const int32_t* word_id; const double* weight;
 };
 
+// two-camera tracking matchers (match.hip twocam_walk_kernel): the searched frame holds nL left keypoints, then nR right ones
+struct TcArgs {
+    const eorb_keypoint* kps; int nL, nR; const uint8_t* desc; int stride; GridB g;
+    int nq; const uint8_t* mp_desc; const uint8_t* mp_obs; float th; float nnratio;
+    // map points (KIND 0): x, y, viewCos, levelScale per camera; predicted levels; stereo links of the frame
+    const uint8_t* in_view; const float4* qf; const int32_t* qlevel;
+    const uint8_t* in_view_r; const float4* qf_r; const int32_t* qlevel_r;
+    const int32_t* l2r; const int32_t* r2l;
+    // last frame (KIND 1): u, v, u_r, v_r, levelScale per query; the query keypoints (octave, angle); window mode
+    const uint8_t* valid; const float* quv; const eorb_keypoint* qkps; int mode; int checkOri;
+    int32_t* rec;                                // KIND 1: (slot << 5 | bin) of every match in order, 2 * nq entries
+    int32_t* slots; int32_t* nmatches;
+};
+
 }  // namespace eorb

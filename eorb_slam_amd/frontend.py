@@ -297,6 +297,27 @@ class ORBextractor:
         a, b = nL.value, nR.value
         return dict(kpsL=kL[:a].copy(), descL=dL[:a].copy(), kpsR=kR[:b].copy(), descR=dR[:b].copy(), uRight=ur[:a].copy(), depth=dp[:a].copy(), nmatches=nm.value)
 
+    def fisheye(self, imLeft, imRight, vLappingAreaLeft, vLappingAreaRight):
+        """Frame::Frame(imLeft, imRight, ..., pCamera, pCamera2, Tlr) (src/Frame.cc:1101-1208): both extractions, each with its camera's
+        lapping area, and ComputeStereoFishEyeMatches (:1210-1250) up to TriangulateMatches, in one call.  Returns dict(kpsL, descL,
+        monoLeft, kpsR, descR, monoRight, right_idx (candidate right keypoint per left keypoint, -1 none), dist2 (nL x 2 knn distances,
+        -1 none), ncand)."""
+        imL = np.ascontiguousarray(imLeft, np.uint8); imR = np.ascontiguousarray(imRight, np.uint8)
+        H, W = imL.shape
+        if imR.shape != imL.shape:
+            raise ValueError("left and right image differ in size")
+        cap = self.cap
+        kL = np.zeros(cap, KP_DTYPE); kR = np.zeros(cap, KP_DTYPE); dL = np.zeros((cap, 32), np.uint8); dR = np.zeros((cap, 32), np.uint8)
+        cand = np.zeros(cap, np.int32); d2 = np.zeros((cap, 2), np.int32)
+        nL, nR, mL, mR, nc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.L.eorb_frame_fisheye(self.ctx.h, _p(imL), _p(imR), W, H, imL.strides[0],
+                                                     int(vLappingAreaLeft[0]), int(vLappingAreaLeft[1]), int(vLappingAreaRight[0]), int(vLappingAreaRight[1]),
+                                                     _p(kL), _p(dL), C.byref(nL), C.byref(mL), _p(kR), _p(dR), C.byref(nR), C.byref(mR), cap,
+                                                     _p(cand), _p(d2), C.byref(nc)))
+        a, b = nL.value, nR.value
+        return dict(kpsL=kL[:a].copy(), descL=dL[:a].copy(), monoLeft=mL.value, kpsR=kR[:b].copy(), descR=dR[:b].copy(), monoRight=mR.value,
+                    right_idx=cand[:a].copy(), dist2=d2[:a].copy(), ncand=nc.value)
+
     def GetLevels(self):
         return self.nlevels
 
@@ -438,6 +459,68 @@ class ORBmatcher:
                                                   _p(mp_desc), _p(mp_obs), _p(mio), _p(ls), C.byref(F.gb), _p(fm),
                                                   float(th), self.mfNNratio, C.byref(nm)))
         return nm.value, fm
+
+
+    def SearchByProjectionMapFisheye(self, kps, nL, desc, l2r, r2l, gb, left, right, mp_desc, mp_obs, frame_mp, th):
+        """The two-camera path of SearchByProjection(Frame &F, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:44-219).  kps / desc:
+        nL left then the right keypoints; l2r / r2l = mvLeftToRightMatch / mvRightToLeftMatch; gb = grid_bounds(...); left / right =
+        (in_view, proj_xy, level, view_cos, level_scale) per map point for each camera (right level -1: no right search).
+        Returns (nmatches, frame_mp)."""
+        kps = np.ascontiguousarray(kps, KP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
+        nR = len(kps) - nL
+        l2r = np.ascontiguousarray(l2r, np.int32); r2l = np.ascontiguousarray(r2l, np.int32)
+        if nR < 0 or len(l2r) != nL or len(r2l) != nR or len(desc) != len(kps):
+            raise ValueError("kps / desc hold nL + nR rows, l2r nL and r2l nR")
+        cams = []
+        for iv, pxy, lv, vc, ls in (left, right):
+            cams.append((np.ascontiguousarray(iv, np.uint8), np.ascontiguousarray(pxy, np.float32), np.ascontiguousarray(lv, np.int32),
+                         np.ascontiguousarray(vc, np.float32), np.ascontiguousarray(ls, np.float32)))
+        mp_desc = np.ascontiguousarray(mp_desc, np.uint8); mp_obs = np.ascontiguousarray(mp_obs, np.uint8)
+        M = len(mp_obs)
+        if any(len(a) != M for cam in cams for a in cam):
+            raise ValueError("every per-map-point array holds M entries")
+        fm = np.ascontiguousarray(frame_mp, np.int32).copy(); nm = C.c_int(0)
+        c = self.ctx
+        (a0, a1, a2, a3, a4), (b0, b1, b2, b3, b4) = cams
+        c.check(c.L.eorb_search_by_projection_map_fisheye(c.h, _p(kps), nL, nR, _p(desc), desc.shape[1] if desc.ndim == 2 else 32, _p(l2r), _p(r2l), M,
+                                                          _p(a0), _p(a1), _p(a2), _p(a3), _p(a4), _p(b0), _p(b1), _p(b2), _p(b3), _p(b4),
+                                                          _p(mp_desc), _p(mp_obs), C.byref(gb), _p(fm), float(th), self.mfNNratio, C.byref(nm)))
+        return nm.value, fm
+
+    def SearchByProjectionLastFisheye(self, kps, nL, desc, gb, last_kps, valid, uv, uv_r, mp_desc, mp_obs, cur_mp, th, level_scale, mode=0):
+        """The two-camera path of SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1969-2187).  kps / desc:
+        the current frame's nL left then right keypoints; queries = every last-frame point (last_kps in index order), uv / uv_r its
+        left / right projections, valid the host gates.  Returns (nmatches, cur_mp)."""
+        kps = np.ascontiguousarray(kps, KP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
+        last_kps = np.ascontiguousarray(last_kps, KP_DTYPE)
+        valid = np.ascontiguousarray(valid, np.uint8); uv = np.ascontiguousarray(uv, np.float32); uv_r = np.ascontiguousarray(uv_r, np.float32)
+        mp_desc = np.ascontiguousarray(mp_desc, np.uint8); mp_obs = np.ascontiguousarray(mp_obs, np.uint8)
+        ls = np.ascontiguousarray(level_scale, np.float32)
+        nq = len(last_kps)
+        if len(valid) != nq or len(uv) != nq or len(uv_r) != nq or len(mp_obs) != nq or len(ls) != nq or len(desc) != len(kps) or nL > len(kps):
+            raise ValueError("per-query arrays hold one entry per last-frame point")
+        cm = np.ascontiguousarray(cur_mp, np.int32).copy(); nm = C.c_int(0)
+        c = self.ctx
+        c.check(c.L.eorb_search_by_projection_last_fisheye(c.h, _p(kps), nL, len(kps) - nL, _p(desc), desc.shape[1] if desc.ndim == 2 else 32,
+                                                           _p(last_kps), nq, _p(valid), _p(uv), _p(uv_r), _p(mp_desc), _p(mp_obs), _p(ls),
+                                                           C.byref(gb), _p(cm), float(th), int(mode), int(self.mbCheckOrientation), C.byref(nm)))
+        return nm.value, cm
+
+
+def SearchByBoWFisheye(kf_kps, kf_desc, kf_has_mp, kf_fv, f_kps, nL, f_desc, f_fv, nnratio=0.7, checkOri=True, ctx=None):
+    """The two-camera path of SearchByBoW(KeyFrame*, Frame&, ...) (src/ORBmatcher.cc:276-478): frame features = nL left, then right.
+    Returns (nmatches, match_f)."""
+    c = ctx or default_context()
+    kf_kps = np.ascontiguousarray(kf_kps, KP_DTYPE); f_kps = np.ascontiguousarray(f_kps, KP_DTYPE)
+    kf_desc = np.ascontiguousarray(kf_desc, np.uint8); f_desc = np.ascontiguousarray(f_desc, np.uint8)
+    hm = np.ascontiguousarray(kf_has_mp, np.uint8)
+    kn, ko, ki = [np.ascontiguousarray(a, t) for a, t in zip(kf_fv, (np.uint32, np.int32, np.int32))]
+    fn, fo, fi = [np.ascontiguousarray(a, t) for a, t in zip(f_fv, (np.uint32, np.int32, np.int32))]
+    m = np.full(len(f_kps), -1, np.int32); nm = C.c_int(0)
+    c.check(c.L.eorb_search_by_bow_fisheye(c.h, _p(kf_kps), len(kf_kps), _p(kf_desc), _p(hm), _p(kn), _p(ko), _p(ki), len(kn),
+                                           _p(f_kps), len(f_kps), int(nL), _p(f_desc), _p(fn), _p(fo), _p(fi), len(fn), _p(m), float(nnratio),
+                                           int(checkOri), C.byref(nm)))
+    return nm.value, m
 
 
 def SearchByBoW(kf_kps, kf_desc, kf_has_mp, kf_fv, f_kps, f_desc, f_fv, nnratio=0.7, checkOri=True, ctx=None):

@@ -384,6 +384,28 @@ public:
         if (nr) std::memcpy(mDescriptorsRight.ptr(), dr.ptr(), (size_t)nr * 32);
         return nm;
     }
+    // Frame::Frame(imLeft, imRight, ..., pCamera, pCamera2, Tlr) (src/Frame.cc:1101-1208): ExtractORB on both images with each camera's
+    // mvLappingArea (:1124-1129) + ComputeStereoFishEyeMatches (:1210-1250) up to TriangulateMatches.  Fills mvKeys, mDescriptors,
+    // monoLeft, mvKeysRight, mDescriptorsRight, monoRight and, per left keypoint, the candidate right keypoint (-1 none) that passed
+    // Lowe's test; the caller triangulates the candidates (KannalaBrandt8::TriangulateMatches) into mvLeftToRightMatch,
+    // mvRightToLeftMatch and mvDepth.  Returns the number of candidates.
+    int ComputeStereoFishEyeMatches(const eorb_host::Mat8& imLeft, const eorb_host::Mat8& imRight, const std::vector<int>& vLappingAreaLeft,
+                                    const std::vector<int>& vLappingAreaRight, std::vector<eorb_host::KeyPoint>& mvKeys,
+                                    eorb_host::Mat8& mDescriptors, int& monoLeft, std::vector<eorb_host::KeyPoint>& mvKeysRight,
+                                    eorb_host::Mat8& mDescriptorsRight, int& monoRight, std::vector<int>& vCandRight) {
+        mvKeys.assign(cap_, eorb_host::KeyPoint{}); mvKeysRight.assign(cap_, eorb_host::KeyPoint{});
+        eorb_host::Mat8 dl(cap_, 32), dr(cap_, 32);
+        vCandRight.assign(cap_, -1);
+        int nl = 0, nr = 0, nc = 0;
+        ctx_.check(eorb_frame_fisheye(ctx_.get(), imLeft.ptr(), imRight.ptr(), imLeft.cols, imLeft.rows, imLeft.cols, vLappingAreaLeft[0],
+                                      vLappingAreaLeft[1], vLappingAreaRight[0], vLappingAreaRight[1], mvKeys.data(), dl.ptr(), &nl, &monoLeft,
+                                      mvKeysRight.data(), dr.ptr(), &nr, &monoRight, cap_, vCandRight.data(), nullptr, &nc));
+        mvKeys.resize(nl); mvKeysRight.resize(nr); vCandRight.resize(nl);
+        mDescriptors = eorb_host::Mat8(nl, 32); mDescriptorsRight = eorb_host::Mat8(nr, 32);
+        if (nl) std::memcpy(mDescriptors.ptr(), dl.ptr(), (size_t)nl * 32);
+        if (nr) std::memcpy(mDescriptorsRight.ptr(), dr.ptr(), (size_t)nr * 32);
+        return nc;
+    }
     int GetLevels() const { return p_.nlevels; }
     float GetScaleFactor() const { return p_.scaleFactor; }
     std::vector<float> GetScaleFactors() const { return mvScaleFactor; }
@@ -435,6 +457,48 @@ public:
                                    kfFV.off.data(), kfFV.idx.data(), (int)kfFV.nodes.size(), F.kps->data(), F.numAllKPts(), F.desc->ptr(),
                                    fFV.nodes.data(), fFV.off.data(), fFV.idx.data(), (int)fFV.nodes.size(), match_f.data(),
                                    mfNNratio, mbCheckOrientation, &nm));
+        return nm;
+    }
+    // the two-camera frame (numKPtsLeft() != -1): F holds Nleft left keypoints, then the right ones (:276-478)
+    int SearchByBoW(const FrameView& KF, const std::vector<uint8_t>& kfHasMP, const FeatureVector& kfFV, const FrameView& F, int Nleft,
+                    const FeatureVector& fFV, std::vector<int>& match_f) {
+        auto& c = eorb_host::thread_context();
+        match_f.assign(F.numAllKPts(), -1); int nm = 0;
+        c.check(eorb_search_by_bow_fisheye(c.get(), KF.kps->data(), KF.numAllKPts(), KF.desc->ptr(), kfHasMP.data(), kfFV.nodes.data(),
+                                           kfFV.off.data(), kfFV.idx.data(), (int)kfFV.nodes.size(), F.kps->data(), F.numAllKPts(), Nleft,
+                                           F.desc->ptr(), fFV.nodes.data(), fFV.off.data(), fFV.idx.data(), (int)fFV.nodes.size(),
+                                           match_f.data(), mfNNratio, mbCheckOrientation, &nm));
+        return nm;
+    }
+    // what Frame::isInFrustum leaves in a map point for one camera (mbTrackInView[R], mTrackProjX[R]/Y[R], mnTrackScaleLevel[R],
+    // mTrackViewCos[R]) plus getORBScaleFactor(level), per map point
+    struct TrackView { std::vector<uint8_t> inView; std::vector<float> projXY, viewCos, levelScale; std::vector<int> level; };
+    // SearchByProjection(Frame& F, const vector<MapPoint*>&, th) on a two-camera frame (:44-219): F = Nleft left then right keypoints,
+    // l2r / r2l = mvLeftToRightMatch / mvRightToLeftMatch, frameMP in/out as eorb_search_by_projection_map_fisheye
+    int SearchByProjection(const FrameView& F, int Nleft, const std::vector<int>& l2r, const std::vector<int>& r2l, const TrackView& left,
+                           const TrackView& right, const eorb_host::Mat8& mpDesc, const std::vector<uint8_t>& mpObs,
+                           std::vector<int>& frameMP, float th) {
+        auto& c = eorb_host::thread_context();
+        int nm = 0;
+        c.check(eorb_search_by_projection_map_fisheye(c.get(), F.kps->data(), Nleft, F.numAllKPts() - Nleft, F.desc->ptr(), F.desc->cols,
+                                                      l2r.data(), r2l.data(), (int)mpObs.size(), left.inView.data(), left.projXY.data(),
+                                                      left.level.data(), left.viewCos.data(), left.levelScale.data(), right.inView.data(),
+                                                      right.projXY.data(), right.level.data(), right.viewCos.data(), right.levelScale.data(),
+                                                      mpDesc.ptr(), mpObs.data(), &F.gb, frameMP.data(), th, mfNNratio, &nm));
+        return nm;
+    }
+    // SearchByProjection(CurrentFrame, LastFrame, th, bMono) on a two-camera frame (:1969-2187): queries = every LastFrame point (its
+    // keypoints in index order), uv / uvR = left / right projections, mode 0 / 1 (bForward) / 2 (bBackward); curMP in/out
+    int SearchByProjection(const FrameView& Cur, int Nleft, const std::vector<eorb_host::KeyPoint>& lastKps, const std::vector<uint8_t>& valid,
+                           const std::vector<float>& uv, const std::vector<float>& uvR, const eorb_host::Mat8& mpDesc,
+                           const std::vector<uint8_t>& mpObs, const std::vector<float>& levelScale, std::vector<int>& curMP, float th,
+                           int mode) {
+        auto& c = eorb_host::thread_context();
+        int nm = 0;
+        c.check(eorb_search_by_projection_last_fisheye(c.get(), Cur.kps->data(), Nleft, Cur.numAllKPts() - Nleft, Cur.desc->ptr(),
+                                                       Cur.desc->cols, lastKps.data(), (int)lastKps.size(), valid.data(), uv.data(),
+                                                       uvR.data(), mpDesc.ptr(), mpObs.data(), levelScale.data(), &Cur.gb, curMP.data(),
+                                                       th, mode, mbCheckOrientation, &nm));
         return nm;
     }
     // SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (:833-973)

@@ -300,6 +300,69 @@ int eorb_frame_stereo(eorb_ctx* ctx, const uint8_t* imLeft, const uint8_t* imRig
                       eorb_keypoint* kpsL, uint8_t* descL, int* nL, eorb_keypoint* kpsR, uint8_t* descR, int* nR, int cap,
                       float* uRight, float* depth, int* nmatches);
 
+/* ---- two-camera (fisheye stereo) frames ------------------------------------------------------------------------------------
+ * Frame::Frame(imLeft, imRight, ..., pCamera, pCamera2, Tlr) (src/Frame.cc:1101-1208; built by Tracking.cc:245-256 for STEREO /
+ * IMU_STEREO with a second camera, KannalaBrandt8) and the numKPtsLeft() != -1 branches of the tracking matchers.  Such a frame holds
+ * nL left keypoints followed by nR right ones (mvKeys, then mvKeysRight), descriptors concatenated the same way (cv::vconcat :1176),
+ * map-point slots frame_mp[nL + nR].  Both grids use the caller's eorb_grid_bounds (ComputeImageBounds(imLeft), :1145-1148): the
+ * left grid holds the mvKeys positions (distorted: getDistKPtMono :758-760), the right grid the mvKeysRight positions.  Projection,
+ * isInFrustum, isBad, far-point and outlier gates stay on the host, as for the mono entry points.
+ * Right grid level gate: GetFeaturesInArea(..., bRight = true) tests getKPtLevelMono(j) = mvKeysUn[j].octave (:763, :1417-1420),
+ * i.e. the octave of LEFT keypoint j, for right keypoint j; for j >= nL the reference reads past mvKeysUn (nL entries, :1191) and
+ * this library uses the right keypoint's own octave (upstream ORB-SLAM3's reading).  The query octave getKPtLevelMono(i) of a
+ * last-frame point i >= nL_last follows the same rule: the caller passes the last frame's keypoints in index order.
+ * Limits: nL + nR <= 8192 keypoints per searched frame (octaves 0..127), fewer than 2^24 queries; EORB_E_CAPACITY beyond. */
+
+/* replaces the hot path of the fisheye constructor (src/Frame.cc:1101-1208) and ComputeStereoFishEyeMatches (:1210-1250) up to
+ * the triangulation: ExtractORB on both images with each camera's lapping area (mvLappingArea of mpCamera: lapL0/lapL1, of mpCamera2:
+ * lapR0/lapR1, :1124-1129), then knnMatch(k = 2) of the left lapping descriptors (rows monoLeft..) against the right ones (rows
+ * monoRight..) (:1228, the tie rule of eorb_hamming_bf_knn2) and Lowe's test "size() >= 2 && d0 < d1 * 0.7" (:1233, in double).
+ * Out: keypoints / descriptors / monoIndex of both images; per left keypoint right_idx[nL] = the candidate right keypoint index
+ * (trainIdx + monoRight) or -1, dist2[2 * nL] = the two knn distances (-1: none, or outside the lapping area); *ncand = candidates.
+ * KannalaBrandt8::TriangulateMatches (an SVD per candidate) stays on the host: it turns the candidates into mvLeftToRightMatch,
+ * mvRightToLeftMatch and mvDepth.  One upload, one wait, one download. */
+int eorb_frame_fisheye(eorb_ctx* ctx, const uint8_t* imLeft, const uint8_t* imRight, int W, int H, int stride,
+                       int lapL0, int lapL1, int lapR0, int lapR1,
+                       eorb_keypoint* kpsL, uint8_t* descL, int* nL, int* monoLeft,
+                       eorb_keypoint* kpsR, uint8_t* descR, int* nR, int* monoRight, int cap,
+                       int32_t* right_idx, int32_t* dist2, int* ncand);
+
+/* replaces the two-camera path of ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:44-219).
+ * Per map point, left (mbTrackInView, mTrackProjX/Y, mnTrackScaleLevel, mTrackViewCos, getORBScaleFactor(level)) and right
+ * (mbTrackInViewR, mTrackProjXR/YR, mnTrackScaleLevelR (-1: skip), mTrackViewCosR, its scale factor); l2r[nL] / r2l[nR] =
+ * mvLeftToRightMatch / mvRightToLeftMatch.  frame_mp[nL + nR] in/out as in eorb_search_by_projection_map.  Reproduced: a left
+ * ratio rejection skips the right block (the `continue` at :130); the right radius ignores th (:152); a left match also writes
+ * slot nL + l2r[best] (:136-137) and a right match slot r2l[best] (:204-205), each counted; no mvuRight gate (:95). */
+int eorb_search_by_projection_map_fisheye(eorb_ctx* ctx,
+        const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride, const int32_t* l2r, const int32_t* r2l,
+        int M, const uint8_t* in_view, const float* proj_xy, const int32_t* level, const float* view_cos, const float* level_scale,
+        const uint8_t* in_view_r, const float* proj_xy_r, const int32_t* level_r, const float* view_cos_r, const float* level_scale_r,
+        const uint8_t* mp_desc, const uint8_t* mp_obs, const eorb_grid_bounds* gb, int32_t* frame_mp, float th, float nnratio,
+        int* nmatches);
+
+/* replaces the two-camera path of ORBmatcher::SearchByProjection(CurF, LastF, th, bMono) (src/ORBmatcher.cc:1969-2187).  Queries:
+ * all n_last = nL_last + nR_last points of the last frame; valid / uv = the left projection (invzc, bounds and outlier folded
+ * into valid), uv_r = mpCamera->project(mTrl * x3Dc) (no bounds check in the reference), last_kps = the query keypoints in index
+ * order (octave, angle), level_scale = getORBScaleFactor(octave), mp_desc / mp_obs per query.  cur_mp[nL + nR] in/out and mode as
+ * in eorb_search_by_projection_last; a right match writes nL + j.  Reproduced: the right search runs only when the left window was
+ * not empty (:2033), whatever the left search found; one rotation histogram holds both cameras' matches (:2155, :2167-2184). */
+int eorb_search_by_projection_last_fisheye(eorb_ctx* ctx,
+        const eorb_keypoint* cur_kps, int nL, int nR, const uint8_t* cur_desc, int cur_stride,
+        const eorb_keypoint* last_kps, int n_last, const uint8_t* valid, const float* uv, const float* uv_r,
+        const uint8_t* mp_desc, const uint8_t* mp_obs, const float* level_scale, const eorb_grid_bounds* gb,
+        int32_t* cur_mp, float th, int mode, int checkOri, int* nmatches);
+
+/* replaces the two-camera path of ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBmatcher.cc:276-478):
+ * inputs as eorb_search_by_bow, frame features = nL left then the right ones (n_f in all).  Two best / second-best pairs, over
+ * frame indices below nL and over the rest (:357-377); the right best is taken only inside "if(bestDist1 <= TH_LOW)" (:410) and
+ * its ratio test always passes ("|| true", :412).  kf_kps in the KeyFrame's index order (its right keypoints after its left ones). */
+int eorb_search_by_bow_fisheye(eorb_ctx* ctx,
+        const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
+        const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
+        const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc,
+        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
+        int32_t* match_f, float nnratio, int checkOri, int* nmatches);
+
 /* replaces the mono branch of ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBmatcher.cc:276-478;
  * MixedMatcher.cpp:148-356).  DBoW2::FeatureVector as CSR (node ids ascending, offsets, feature indices in vector
  * order).  kf_has_mp[i] = map point present and !isBad().  match_f[n_f] out = KeyFrame feature index or -1. */
