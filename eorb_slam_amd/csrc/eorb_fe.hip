@@ -90,97 +90,15 @@ int ensure(eorb_ctx* c, DevBuf& b, size_t bytes)
     return EORB_OK;
 }
 
-// ---- buffers that travel one by one (up() / down()): pinned bump allocators + copy kernels ----
-// A pageable hipMemcpyAsync is staged by the runtime and waits; eight of them plus three downloads made a 19 us matcher a 110 us call.
-// up(): memcpy into pinned memory, a kernel reads it over the link; down(): a kernel writes pinned memory, the host copy happens at the
-// entry's stream wait (fe_stream_sync), which also empties both allocators.  What does not fit without waiting goes through the copy engine.
-// up to eight copies in one launch (blockIdx.y = segment): an entry's buffers go up together and its results come back together
-struct CopySegs8 { unsigned char* dst[8]; const unsigned char* src[8]; size_t n[8]; int align[8]; int count; };
-__global__ void copy_segs_kernel(CopySegs8 S)
+// every stream wait of an entry point: what it enqueued has completed, its staging slots are free again
+static hipError_t fe_stream_sync(eorb_ctx* c)
 {
-    const int sg = blockIdx.y;
-    const unsigned char* src = S.src[sg]; unsigned char* dst = S.dst[sg];
-    const size_t n = S.n[sg];
-    const int align = S.align[sg];
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)gridDim.x * blockDim.x;
-    if (align == 16) {
-        const size_t n16 = n >> 4;
-        for (size_t i = t; i < n16; i += nt) ((uint4*)dst)[i] = ((const uint4*)src)[i];
-        for (size_t i = (n16 << 4) + t; i < n; i += nt) dst[i] = src[i];
-    } else if (align == 4) {
-        const size_t n4 = n >> 2;
-        for (size_t i = t; i < n4; i += nt) ((uint32_t*)dst)[i] = ((const uint32_t*)src)[i];
-        for (size_t i = (n4 << 2) + t; i < n; i += nt) dst[i] = src[i];
-    } else
-        for (size_t i = t; i < n; i += nt) dst[i] = src[i];
-}
-static int launch_copy_queue(eorb_ctx* c, std::vector<eorb_ctx::CopySeg>& q)
-{
-    for (size_t i0 = 0; i0 < q.size(); i0 += 8) {
-        CopySegs8 S{};
-        size_t units = 1;
-        S.count = (int)std::min<size_t>(8, q.size() - i0);
-        for (int k = 0; k < S.count; k++) {
-            const auto& e = q[i0 + k];
-            const uintptr_t a = (uintptr_t)e.src | (uintptr_t)e.dst;
-            S.dst[k] = (unsigned char*)e.dst; S.src[k] = (const unsigned char*)e.src; S.n[k] = e.n;
-            S.align[k] = !(a & 15) ? 16 : (!(a & 3) ? 4 : 1);
-            units = std::max(units, (e.n + (size_t)S.align[k] - 1) / (size_t)S.align[k]);
-        }
-        copy_segs_kernel<<<dim3((unsigned)std::min<size_t>((units + 255) / 256, 128), (unsigned)S.count), 256, 0, c->stream>>>(S);
-        EORB_LAUNCH_CHECK(c, "copy_segs_kernel");
-    }
-    q.clear();
-    return EORB_OK;
-}
-// the uploads staged by up() so far, in one launch: call behind an entry's last up(), in front of its first kernel
-int up_flush(eorb_ctx* c) { return c->up_queue.empty() ? EORB_OK : launch_copy_queue(c, c->up_queue); }
-static void* pin_bump(eorb_ctx::PinBump& b, size_t bytes)            // 256-byte granules; nullptr: not without waiting for queued work
-{
-    const size_t need = (bytes + 255) & ~(size_t)255;
-    if (b.used + need > b.cap) {
-        if (b.used) return nullptr;
-        if (b.p) { hipHostFree(b.p); b.p = nullptr; b.cap = 0; }
-        const size_t want = std::max<size_t>(2 * need, (size_t)1 << 20);
-        if (hipHostMalloc(&b.p, want, hipHostMallocDefault) != hipSuccess) { b.p = nullptr; return nullptr; }
-        b.cap = want;
-    }
-    void* r = (char*)b.p + b.used;
-    b.used += need;
-    return r;
-}
-void pinned_release_lazy(eorb_ctx* c);
-// every stream wait of an entry point: the queued copies are done -- results to their host destinations, the staging memory free again
-hipError_t fe_stream_sync(eorb_ctx* c)
-{
-    if (!c->up_queue.empty() && launch_copy_queue(c, c->up_queue) != EORB_OK) return hipErrorUnknown;
-    if (!c->dn_queue.empty() && launch_copy_queue(c, c->dn_queue) != EORB_OK) return hipErrorUnknown;
     const hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) {
-        for (const auto& d : c->dn_pending) memcpy(d.dst, (const char*)c->dn_pin.p + d.off, d.bytes);
-        pinned_release_lazy(c);
-    }
-    c->dn_pending.clear(); c->dn_queue.clear(); c->up_queue.clear(); c->dn_pin.used = 0; c->up_pin.used = 0;
+    if (e == hipSuccess) pinned_release_lazy(c);
     return e;
 }
-// entry prologue: the context's device; whatever an entry that failed half-way left pending is dropped (its destinations may be gone)
-void fe_enter(eorb_ctx* c)
-{
-    hipSetDevice(c->device);
-    if (!c->dn_pending.empty()) c->dn_pending.clear();
-    if (!c->dn_queue.empty()) c->dn_queue.clear();
-    if (!c->up_queue.empty()) c->up_queue.clear();
-}
-static int down(eorb_ctx* c, void* dst, const void* src, size_t bytes)
-{
-    if (!bytes) return EORB_OK;
-    static const long kmax = [] { const char* e = getenv("EORB_DOWNLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }();
-    void* p = (long)bytes <= kmax ? pin_bump(c->dn_pin, bytes) : nullptr;
-    if (!p) { EORB_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); return EORB_OK; }
-    c->dn_queue.push_back({p, src, bytes});
-    c->dn_pending.push_back({dst, (size_t)((char*)p - (char*)c->dn_pin.p), bytes});
-    return EORB_OK;
-}
+// entry prologue: the context's device
+static void fe_enter(eorb_ctx* c) { hipSetDevice(c->device); }
 
 void* pinned(eorb_ctx* c, size_t bytes)
 {
@@ -260,7 +178,8 @@ static void free_buf(DevBuf& b) { if (b.p) hipFree(b.p); b.p = nullptr; b.cap = 
 // Host-buffer entry points are called once per frame (src/Frame.cc:467-482, src/Tracking.cc:1420, EvImBuilder.cpp:1345): their
 // latency is launches and copies, not kernels.  A call lays ALL its inputs and outputs out in one device arena: the inputs are
 // packed into a pinned slot and cross PCIe in ONE copy (a pageable hipMemcpy2DAsync of a 346x260 image alone cost > 1 ms), the
-// outputs come back in ONE copy into a pinned landing buffer.
+// outputs come back in ONE copy into a pinned landing buffer.  Beyond 1 MB the copy engine moves them: staged inputs in 4 MB pieces,
+// and an array of 4 MB or more straight between the caller's buffer and the arena (Arena::upload, Arena::download_to).
 // upload of a call's inputs by a kernel that reads the pinned staging buffer over the link (16 bytes per thread, coalesced): for the few
 // hundred KB of a one-frame call the copy engine's turn plus its hand-over to the first kernel cost more (SearchByProjection: copy 11 us +
 // 12-15 us idle before the first kernel) than these reads
@@ -270,14 +189,22 @@ __global__ void arena_upload_kernel(const uint4* __restrict__ src, uint4* __rest
 }
 
 struct Arena {
+    static constexpr size_t kPiece = (size_t)4 << 20;      // large calls: staged copy-engine transfers go in pieces of this size, larger arrays go directly
     eorb_ctx* c;
     size_t total = 0, in_end = 0;
-    struct Part { const void* src; size_t off, bytes; int rows; size_t row_bytes, stride; };
+    struct Part { const void* src; size_t off, bytes; int rows; size_t row_bytes, stride; bool pack = false; };
     std::vector<Part> parts;
     explicit Arena(eorb_ctx* cc) : c(cc) {}
     size_t take(size_t bytes) { const size_t o = total; total = (total + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; }
     // inputs first (they form the prefix that is uploaded), then reserve() for device-only / output regions
     size_t in(const void* h, size_t bytes) { const size_t o = take(bytes); if (h && bytes) parts.push_back({h, o, bytes, 0, 0, 0}); in_end = total; return o; }
+    // float events, packed to the 16-byte record (eorb_pack_events) straight into the staging buffer
+    size_t in_events(const eorb_event* ev, size_t n)
+    {
+        const size_t o = in(ev, sizeof(eorb_event16) * n);
+        if (ev && n) parts.back().pack = true;
+        return o;
+    }
     size_t in2d(const void* h, int rows, size_t row_bytes, size_t stride)
     {
         const size_t o = take((size_t)rows * row_bytes);
@@ -301,18 +228,37 @@ struct Arena {
         if (!in_end) return EORB_OK;
         char* hp = (char*)pinned(c, in_end);
         if (!hp) return set_err(c, EORB_E_HIP, "pinned alloc failed");
+        static const long kmax = [] { const char* e = getenv("EORB_UPLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }();      // (bytes; 0: always the copy engine)
+        // the copy engine takes the staging buffer in pieces of kPiece as it fills: tens of MB are copied in while the host packs the rest;
+        // an array of kPiece or more goes straight from the caller's buffer (the runtime copies pageable memory of that size in place,
+        // twice as fast as through a staging buffer: 16 MB in 0.30 ms against 0.50 ms)
+        const bool engine = !host_inputs && (long)in_end > kmax;
+        size_t sent = 0;
+        auto send = [&](size_t upto) {
+            const hipError_t e = upto > sent ? hipMemcpyAsync((char*)c->arena.p + sent, hp + sent, upto - sent, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+            sent = upto;
+            return e;
+        };
         for (const Part& p : parts) {
-            if (p.rows) for (int r = 0; r < p.rows; r++) memcpy(hp + p.off + (size_t)r * p.row_bytes, (const char*)p.src + (size_t)r * p.stride, p.row_bytes);
-            else memcpy(hp + p.off, p.src, p.bytes);
+            if (engine && !p.rows && !p.pack && p.bytes >= kPiece) {
+                EORB_HIP(c, send(p.off));
+                EORB_HIP(c, hipMemcpyAsync((char*)c->arena.p + p.off, p.src, p.bytes, hipMemcpyHostToDevice, c->stream));
+                sent = p.off + p.bytes;
+            } else if (p.rows) for (int r = 0; r < p.rows; r++) memcpy(hp + p.off + (size_t)r * p.row_bytes, (const char*)p.src + (size_t)r * p.stride, p.row_bytes);
+            else for (size_t q = 0; q < p.bytes; q += kPiece) {
+                const size_t m = std::min(kPiece, p.bytes - q);
+                if (p.pack) eorb_pack_events((const eorb_event*)p.src + q / sizeof(eorb_event16), m / sizeof(eorb_event16), (eorb_event16*)(hp + p.off + q));
+                else memcpy(hp + p.off + q, (const char*)p.src + q, m);
+                if (engine && p.off + q + m - sent >= kPiece) EORB_HIP(c, send(p.off + q + m));
+            }
         }
         if (host_inputs) { host_base = hp; pinned_commit(c, true); return EORB_OK; }
-        static const long kmax = [] { const char* e = getenv("EORB_UPLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }();      // (bytes; 0: always the copy engine)
-        if ((long)in_end <= kmax) {
+        if (engine) EORB_HIP(c, send(in_end));
+        else {
             const size_t n16 = (in_end + 15) / 16;          // (offsets and sizes of the arena are multiples of 256; the staging buffer is at least as long)
             arena_upload_kernel<<<(unsigned)std::min<size_t>((n16 + 255) / 256, 512), 256, 0, c->stream>>>((const uint4*)hp, (uint4*)c->arena.p, n16);
             EORB_LAUNCH_CHECK(c, "arena_upload_kernel");
-        } else
-            EORB_HIP(c, hipMemcpyAsync(c->arena.p, hp, in_end, hipMemcpyHostToDevice, c->stream));
+        }
         pinned_commit(c, true);
         return EORB_OK;
     }
@@ -320,18 +266,23 @@ struct Arena {
     // download_begin / download_wait: the same in two halves -- what the caller launches in between (work the results do not depend on:
     // the LK reference kept for the next call) runs after the copy and is not waited for.
     size_t dl_off = 0;
+    static long download_kmax() { static const long k = [] { const char* e = getenv("EORB_DOWNLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }(); return k; }      // (bytes; 0: always the copy engine)
+    int landing(size_t bytes)
+    {
+        if (c->dl_cap >= bytes) return EORB_OK;
+        if (c->dl_pinned) { hipHostFree(c->dl_pinned); c->dl_pinned = nullptr; c->dl_cap = 0; }
+        const size_t want = bytes + bytes / 2 + 4096;
+        if (hipHostMalloc(&c->dl_pinned, want, hipHostMallocDefault) != hipSuccess) { c->dl_pinned = nullptr; return set_err(c, EORB_E_HIP, "pinned alloc failed"); }
+        c->dl_cap = want;
+        return EORB_OK;
+    }
     int download_begin(size_t off, size_t bytes)
     {
-        if (c->dl_cap < bytes) {
-            if (c->dl_pinned) { hipHostFree(c->dl_pinned); c->dl_pinned = nullptr; c->dl_cap = 0; }
-            const size_t want = bytes + bytes / 2 + 4096;
-            if (hipHostMalloc(&c->dl_pinned, want, hipHostMallocDefault) != hipSuccess) { c->dl_pinned = nullptr; return set_err(c, EORB_E_HIP, "pinned alloc failed"); }
-            c->dl_cap = want;
-        }
+        int rc = landing(bytes);
+        if (rc) return rc;
         // (the way back like the way in: up to a few hundred KB a kernel writes the pinned buffer; offsets of the arena are multiples of
         // 256 and both buffers longer than the rounded size)
-        static const long kmax = [] { const char* e = getenv("EORB_DOWNLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }();      // (bytes; 0: always the copy engine)
-        if ((long)bytes <= kmax && !(off & 15)) {
+        if ((long)bytes <= download_kmax() && !(off & 15)) {
             const size_t n16 = (bytes + 15) / 16;
             arena_upload_kernel<<<(unsigned)std::min<size_t>((n16 + 255) / 256, 512), 256, 0, c->stream>>>((const uint4*)((char*)c->arena.p + off), (uint4*)c->dl_pinned, n16);
             EORB_LAUNCH_CHECK(c, "arena download kernel");
@@ -365,7 +316,35 @@ struct Arena {
         // (profiling: the scopes' events are collected when the stream is idle -- eorb_prof_* synchronise before they read)
         return EORB_OK;
     }
+    // download() + memcpy(dst, ...) for one result; from kPiece on the copy engine writes the caller's buffer itself (as for the inputs)
+    int download_to(void* dst, size_t off, size_t bytes)
+    {
+        int rc;
+        if (bytes < kPiece) {
+            const char* h;
+            if ((rc = download(off, bytes, &h))) return rc;
+            memcpy(dst, h + off, bytes);
+            return EORB_OK;
+        }
+        EORB_HIP(c, hipMemcpyAsync(dst, (char*)c->arena.p + off, bytes, hipMemcpyDeviceToHost, c->stream));
+        EORB_HIP(c, fe_stream_sync(c));
+        return EORB_OK;
+    }
 };
+
+// setup data that persists across calls (undistortion maps, vocabulary): `fill` writes it into a pinned slot, one copy into `b`, one wait
+template <typename Fill> static int upload_persistent(eorb_ctx* c, DevBuf& b, size_t bytes, Fill fill)
+{
+    int rc = ensure(c, b, bytes);
+    if (rc) return rc;
+    char* hp = (char*)pinned(c, bytes);
+    if (!hp) return set_err(c, EORB_E_HIP, "pinned alloc failed");
+    fill(hp);
+    EORB_HIP(c, hipMemcpyAsync(b.p, hp, bytes, hipMemcpyHostToDevice, c->stream));
+    pinned_commit(c, true);
+    EORB_HIP(c, fe_stream_sync(c));
+    return EORB_OK;
+}
 
 }  // namespace eorb
 
@@ -403,8 +382,8 @@ void eorb_destroy(eorb_ctx* c)
     prof_collect(c);
     DevBuf* bufs[] = {&c->ev16, &c->chunks, &c->segoff, &c->entries, &c->img_f32, &c->img_u8, &c->minmax, &c->tile_order, &c->order_hist, &c->lut, &c->src_info, &c->stamps, &c->sl_tab, &c->sl_tile, &c->sl_rows, &c->sl_trace, &c->dd_tab, &c->dd_src_info, &c->dd_stamps, &c->dd_sl_tab, &c->dd_sl_tile, &c->dd_sl_rows, &c->dd_ev, &c->dd_cnt, &c->focus_sd, &c->voc, &c->klt_pyr, &c->klt_der, &c->klt_scratch, &c->pyr, &c->score,
                       &c->blur, &c->cell_cnt, &c->cell_cand, &c->lvl_cnt, &c->lvl_kp, &c->kp_angle, &c->out_kp, &c->out_desc,
-                      &c->out_oob, &c->out_n, &c->oct_scratch, &c->in_img, &c->m_a, &c->m_b, &c->m_c, &c->m_d, &c->m_e, &c->m_f,
-                      &c->m_g, &c->m_h, &c->m_i, &c->m_j, &c->fe_prev_kp, &c->fe_prev_desc, &c->fe_prev_n, &c->fe_pm,
+                      &c->out_oob, &c->out_n, &c->oct_scratch, &c->fe_prev_kp, &c->fe_prev_desc, &c->fe_prev_n, &c->fe_pm,
+                      &c->fe_matches12, &c->fe_nmatches,
                       &c->orb.tabs, &c->orb.geom, &c->status, &c->win_ws, &c->win_total, &c->arena, &c->l1_ref_img, &c->l1_ref_pts, &c->ev_info, &c->ev_stamps, &c->pd_hash, &c->pd_lut, &c->pd_src_info, &c->pd_sl_tab, &c->pd_sl_tile, &c->pd_sl_rows, &c->pd_cnt};
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& s : c->pinned) { if (s.ev) hipEventDestroy(s.ev); if (s.p) hipHostFree(s.p); }
@@ -412,8 +391,6 @@ void eorb_destroy(eorb_ctx* c)
     if (c->dl_pinned) hipHostFree(c->dl_pinned);
     if (c->dl_event) hipEventDestroy(c->dl_event);
     if (c->rb_pinned) hipHostFree(c->rb_pinned);
-    if (c->up_pin.p) hipHostFree(c->up_pin.p);
-    if (c->dn_pin.p) hipHostFree(c->dn_pin.p);
     for (hipEvent_t e : c->sl_ev) if (e) hipEventDestroy(e);
     if (c->sl_side) hipStreamDestroy(c->sl_side);
     if (c->sl_pstream) hipStreamDestroy(c->sl_pstream);
@@ -590,10 +567,11 @@ void* eorb_dev_alloc(eorb_ctx* c, size_t bytes)
     if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { set_err(c, EORB_E_HIP, "hipMalloc(%zu) failed", bytes); return nullptr; }
     return p;
 }
-int eorb_dev_free(eorb_ctx* c, void* p) { if (!c) return EORB_E_ARG; hipStreamSynchronize(c->stream); EORB_HIP(c, hipFree(p)); return EORB_OK; }
+int eorb_dev_free(eorb_ctx* c, void* p) { if (!c) return EORB_E_ARG; fe_enter(c); hipStreamSynchronize(c->stream); EORB_HIP(c, hipFree(p)); return EORB_OK; }
 int eorb_dev_upload(eorb_ctx* c, void* d, const void* h, size_t bytes)
 {
     if (!c) return EORB_E_ARG;
+    fe_enter(c);
     EORB_HIP(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
     EORB_HIP(c, fe_stream_sync(c));
     return EORB_OK;
@@ -601,6 +579,7 @@ int eorb_dev_upload(eorb_ctx* c, void* d, const void* h, size_t bytes)
 int eorb_dev_download(eorb_ctx* c, void* h, const void* d, size_t bytes)
 {
     if (!c) return EORB_E_ARG;
+    fe_enter(c);
     EORB_HIP(c, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
     EORB_HIP(c, fe_stream_sync(c));
     return EORB_OK;
@@ -685,8 +664,6 @@ int eorb_ev2im_gauss(eorb_ctx* c, const eorb_event* ev, size_t n, int W, int H, 
     return ev_host_common(c, ev, n, W, H, sigma, pol, normalized, 0, out_f32, out_u8, minmax, nullptr);
 }
 
-static int up(eorb_ctx* c, DevBuf& b, const void* h, size_t bytes);
-
 // ---- raw sensor events + undistortion maps ----------------------------------------------------------
 int eorb_set_undistort_maps(eorb_ctx* c, const float* mapX, const float* mapY, int LW, int LH, int checkInImage)
 {
@@ -695,12 +672,11 @@ int eorb_set_undistort_maps(eorb_ctx* c, const float* mapX, const float* mapY, i
         return set_err(c, EORB_E_ARG, "set_undistort_maps: bad arguments");
     fe_enter(c);
     const size_t n = (size_t)LW * LH;
-    std::vector<float> xy(2 * n);
-    for (size_t i = 0; i < n; i++) { xy[2 * i] = mapX[i]; xy[2 * i + 1] = mapY[i]; }
     int rc;
-    if ((rc = up(c, c->lut, xy.data(), sizeof(float) * 2 * n))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    EORB_HIP(c, fe_stream_sync(c));
+    if ((rc = upload_persistent(c, c->lut, sizeof(float) * 2 * n, [&](char* hp) {
+            float* xy = (float*)hp;
+            for (size_t i = 0; i < n; i++) { xy[2 * i] = mapX[i]; xy[2 * i + 1] = mapY[i]; }
+        }))) return rc;
     c->lut_w = LW; c->lut_h = LH; c->lut_check = checkInImage != 0;
     c->lut_key_W = c->lut_key_H = c->lut_key_mode = -1; c->lut_key_sigma = -1.f;      // derived tables are stale
     return EORB_OK;
@@ -719,17 +695,18 @@ int eorb_undistort_events(eorb_ctx* c, const eorb_raw_event* raw, size_t n, int 
             return set_err(c, EORB_E_ARG, "undistort_events: event %zu at (%u,%u) lies outside the %dx%d maps", i, raw[i].x, raw[i].y,
                            c->lut_w, c->lut_h);
     int rc;
-    if ((rc = up(c, c->ev16, raw, sizeof(eorb_raw_event) * n))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    if ((rc = ensure(c, c->entries, sizeof(eorb_event) * n))) return rc;
     const int nblk = (int)((n + 1023) / 1024);
-    if ((rc = ensure(c, c->segoff, sizeof(uint32_t) * ((size_t)nblk + 2)))) return rc;
-    if ((rc = ev_undistort_dev(c, (const eorb_raw_event*)c->ev16.p, n, W, H, tsFactor, (eorb_event*)c->entries.p, (uint32_t*)c->segoff.p))) return rc;
-    uint32_t kept = 0;
-    EORB_HIP(c, hipMemcpyAsync(&kept, (uint32_t*)c->segoff.p + nblk, 4, hipMemcpyDeviceToHost, c->stream));
-    EORB_HIP(c, fe_stream_sync(c));
-    if (kept) EORB_HIP(c, hipMemcpyAsync(out, c->entries.p, sizeof(eorb_event) * kept, hipMemcpyDeviceToHost, c->stream));
-    EORB_HIP(c, fe_stream_sync(c));
+    Arena A(c);
+    const size_t o_raw = A.in(raw, sizeof(eorb_raw_event) * n);
+    // block sums (the kept count at [nblk]) | kept events
+    const size_t o_blk = A.reserve(sizeof(uint32_t) * ((size_t)nblk + 2)), o_out = A.reserve(sizeof(eorb_event) * n);
+    if ((rc = A.upload())) return rc;
+    if ((rc = ev_undistort_dev(c, A.dev<eorb_raw_event>(o_raw), n, W, H, tsFactor, A.dev<eorb_event>(o_out), A.dev<uint32_t>(o_blk)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_blk, sizeof(uint32_t) * ((size_t)nblk + 1), &h))) return rc;
+    uint32_t kept;
+    memcpy(&kept, h + o_blk + sizeof(uint32_t) * (size_t)nblk, 4);
+    if (kept && (rc = A.download_to(out, o_out, sizeof(eorb_event) * kept))) return rc;
     *n_out = kept;
     return EORB_OK;
 }
@@ -746,25 +723,25 @@ int eorb_parse_events_text(eorb_ctx* c, const char* text, size_t nbytes, eorb_ra
     // the line capacity is bounded by the caller's event capacity plus what the text could hold otherwise
     const size_t max_lines = nbytes / 2 + 2;
     int rc;
-    if ((rc = up(c, c->in_img, text, nbytes))) return rc;
-    if ((rc = up_flush(c))) return rc;
     const size_t nblk = (nbytes + 1023) / 1024;
+    Arena A(c);
+    const size_t o_text = A.in(text, nbytes), o_out = A.reserve(sizeof(eorb_raw_event) * max_lines);
+    if ((rc = A.upload())) return rc;
     // workspaces: lineend u64 | parsed events | status | block sums
     if ((rc = ensure(c, c->entries, sizeof(uint64_t) * max_lines))) return rc;
     if ((rc = ensure(c, c->ev16, sizeof(eorb_raw_event) * max_lines))) return rc;
     if ((rc = ensure(c, c->segoff, max_lines + 64))) return rc;
     if ((rc = ensure(c, c->tile_order, sizeof(uint32_t) * (std::max(nblk, (max_lines + 1023) / 1024) + 8)))) return rc;
-    if ((rc = ensure(c, c->chunks, sizeof(eorb_raw_event) * max_lines))) return rc;
     uint32_t res[3];
-    if ((rc = ev_parse_text_dev(c, (const char*)c->in_img.p, nbytes, (uint64_t*)c->entries.p, (eorb_raw_event*)c->ev16.p,
-                                (uint8_t*)c->segoff.p, (eorb_raw_event*)c->chunks.p, (uint32_t*)c->tile_order.p, max_lines, res))) return rc;
+    if ((rc = ev_parse_text_dev(c, A.dev<char>(o_text), nbytes, (uint64_t*)c->entries.p, (eorb_raw_event*)c->ev16.p,
+                                (uint8_t*)c->segoff.p, A.dev<eorb_raw_event>(o_out), (uint32_t*)c->tile_order.p, max_lines, res))) return rc;
+    pinned_release_lazy(c);                              // (ev_parse_text_dev has waited for the stream)
     if (res[2] != 0xffffffffu) {
         if (bad_line) *bad_line = (int64_t)res[2];
         return set_err(c, EORB_E_ARG, "parse_events_text: line %u is outside the accepted \"ts x y p\" grammar", res[2]);
     }
     if (res[1] > cap) return set_err(c, EORB_E_CAPACITY, "parse_events_text: %u events, room for %zu", res[1], cap);
-    if (res[1]) EORB_HIP(c, hipMemcpyAsync(out, c->chunks.p, sizeof(eorb_raw_event) * (size_t)res[1], hipMemcpyDeviceToHost, c->stream));
-    EORB_HIP(c, fe_stream_sync(c));
+    if (res[1] && (rc = A.download_to(out, o_out, sizeof(eorb_raw_event) * (size_t)res[1]))) return rc;
     *n_out = res[1];
     return EORB_OK;
 }
@@ -802,42 +779,34 @@ static int mci_common(eorb_ctx* c, const eorb_event* ev, size_t n, const eorb_ca
         return EORB_OK;
     }
     if (n > 0x7fffffff) return set_err(c, EORB_E_CAPACITY, "ev2mci: too many events");
-    int rc;
-    if ((rc = ensure(c, c->ev16, sizeof(eorb_event16) * n))) return rc;
-    if ((rc = ensure(c, c->m_a, sizeof(eorb_event16) * n))) return rc;
-    if ((rc = ensure(c, c->img_f32, sizeof(float) * npix))) return rc;
-    if ((rc = ensure(c, c->img_u8, npix))) return rc;
-    if ((rc = ensure(c, c->minmax, 64))) return rc;
-    std::vector<eorb_event16> packed(n);
-    eorb_pack_events(ev, n, packed.data());
-    EORB_HIP(c, hipMemcpyAsync(c->m_a.p, packed.data(), sizeof(eorb_event16) * n, hipMemcpyHostToDevice, c->stream));
-    const float* d_depth = nullptr;
-    if (depth) {
-        if ((rc = up(c, c->m_b, depth, sizeof(float) * n))) return rc;
-        if ((rc = up_flush(c))) return rc;
-        d_depth = (const float*)c->m_b.p;
-    }
-    EORB_HIP(c, fe_stream_sync(c));
     if (cam->model != 0 && cam->model != 1) return set_err(c, EORB_E_ARG, "ev2mci: camera model %d unknown", cam->model);
-    if (se3) rc = ev_warp_se3_dev(c, (const eorb_event16*)c->m_a.p, (eorb_event16*)c->ev16.p, (int)n, cam, angle, axis, t, medDepth, d_depth);
-    else rc = ev_warp_se2_dev(c, (const eorb_event16*)c->m_a.p, (eorb_event16*)c->ev16.p, (int)n, cam, params, nparams);
+    int rc;
+    Arena A(c);
+    const size_t o_ev = A.in_events(ev, n), o_depth = A.in(depth, depth ? sizeof(float) * n : 0);
+    const size_t o_warp = A.reserve(sizeof(eorb_event16) * n);
+    // outputs, contiguous: min/max (encoded | decoded) | u8 image | f32 image
+    const size_t o_mm = A.reserve(64), o_u8 = A.reserve(npix), o_f32 = A.reserve(sizeof(float) * npix);
+    if ((rc = A.upload())) return rc;
+    const float* d_depth = depth ? A.dev<float>(o_depth) : nullptr;
+    eorb_event16* d_warp = A.dev<eorb_event16>(o_warp);
+    if (se3) rc = ev_warp_se3_dev(c, A.dev<eorb_event16>(o_ev), d_warp, (int)n, cam, angle, axis, t, medDepth, d_depth);
+    else rc = ev_warp_se2_dev(c, A.dev<eorb_event16>(o_ev), d_warp, (int)n, cam, params, nparams);
     if (rc) return rc;
     int64_t offs[2] = {0, (int64_t)n};
-    uint32_t* mm = (uint32_t*)c->minmax.p;
-    float* mmf = (float*)((char*)c->minmax.p + 16);
+    uint32_t* mm = A.dev<uint32_t>(o_mm);
+    float* mmf = A.dev<float>(o_mm + 16);
     // (warped events: no two share a position -- the position table of the bulk float form would only be filled and thrown away)
     const int64_t dd_saved = c->dbg_dd_min; c->dbg_dd_min = 0;
-    rc = ev_accumulate_dev(c, c->ev16.p, 0, offs, 1, W, H, sigma, pol, 0, (float*)c->img_f32.p, (uint8_t*)c->img_u8.p,
-                           normalized, mm);
+    rc = ev_accumulate_dev(c, d_warp, 0, offs, 1, W, H, sigma, pol, 0, A.dev<float>(o_f32), A.dev<uint8_t>(o_u8), normalized, mm);
     c->dbg_dd_min = dd_saved;
     if (rc) return rc;
     if ((rc = ev_decode_minmax(c, mm, mmf, 1))) return rc;
-    float hmm[2];
-    EORB_HIP(c, hipMemcpyAsync(hmm, mmf, 8, hipMemcpyDeviceToHost, c->stream));
-    if (out_f32) EORB_HIP(c, hipMemcpyAsync(out_f32, c->img_f32.p, sizeof(float) * npix, hipMemcpyDeviceToHost, c->stream));
-    if (out_u8 && normalized) EORB_HIP(c, hipMemcpyAsync(out_u8, c->img_u8.p, npix, hipMemcpyDeviceToHost, c->stream));
-    EORB_HIP(c, fe_stream_sync(c));
-    if (minmax) { minmax[0] = hmm[0]; minmax[1] = hmm[1]; }
+    const size_t end = out_f32 ? o_f32 + sizeof(float) * npix : ((out_u8 && normalized) ? o_u8 + npix : o_mm + 64);
+    const char* h;
+    if ((rc = A.download(o_mm, end - o_mm, &h))) return rc;
+    if (out_f32) memcpy(out_f32, h + o_f32, sizeof(float) * npix);
+    if (out_u8 && normalized) memcpy(out_u8, h + o_u8, npix);
+    if (minmax) memcpy(minmax, h + o_mm + 16, 8);
     return EORB_OK;
 }
 
@@ -879,12 +848,13 @@ int eorb_measure_image_focus_n(eorb_ctx* c, const float* imgs, int n, int W, int
     if (!imgs || !focus || W <= 0 || H <= 0 || n < 1 || n > 64) return set_err(c, EORB_E_ARG, "measure_image_focus: bad arguments");
     fe_enter(c);
     int rc;
-    if ((rc = up(c, c->img_f32, imgs, sizeof(float) * (size_t)W * H * n))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    if ((rc = ensure(c, c->minmax, 256))) return rc;
-    if ((rc = ev_focus_dev(c, (const float*)c->img_f32.p, n, W, H, (float*)c->minmax.p))) return rc;
-    EORB_HIP(c, hipMemcpyAsync(focus, c->minmax.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-    EORB_HIP(c, fe_stream_sync(c));
+    Arena A(c);
+    const size_t o_img = A.in(imgs, sizeof(float) * (size_t)W * H * n), o_focus = A.reserve(sizeof(float) * n);
+    if ((rc = A.upload())) return rc;
+    if ((rc = ev_focus_dev(c, A.dev<float>(o_img), n, W, H, A.dev<float>(o_focus)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_focus, sizeof(float) * n, &h))) return rc;
+    memcpy(focus, h + o_focus, sizeof(float) * n);
     return EORB_OK;
 }
 int eorb_measure_image_focus(eorb_ctx* c, const float* img, int W, int H, float* focus) { return eorb_measure_image_focus_n(c, img, 1, W, H, focus); }
@@ -896,13 +866,13 @@ int eorb_normalize_minmax_u8(eorb_ctx* c, const float* img, int W, int H, uint8_
     fe_enter(c);
     const size_t npix = (size_t)W * H;
     int rc;
-    if ((rc = up(c, c->img_f32, img, sizeof(float) * npix))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    if ((rc = ensure(c, c->img_u8, npix))) return rc;
-    if ((rc = ensure(c, c->minmax, 64))) return rc;
-    if ((rc = ev_cvnormalize_dev(c, (const float*)c->img_f32.p, (int)npix, (uint32_t*)c->minmax.p, (uint8_t*)c->img_u8.p))) return rc;
-    EORB_HIP(c, hipMemcpyAsync(out, c->img_u8.p, npix, hipMemcpyDeviceToHost, c->stream));
-    EORB_HIP(c, fe_stream_sync(c));
+    Arena A(c);
+    const size_t o_img = A.in(img, sizeof(float) * npix), o_mm = A.reserve(64), o_u8 = A.reserve(npix);
+    if ((rc = A.upload())) return rc;
+    if ((rc = ev_cvnormalize_dev(c, A.dev<float>(o_img), (int)npix, A.dev<uint32_t>(o_mm), A.dev<uint8_t>(o_u8)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_u8, npix, &h))) return rc;
+    memcpy(out, h + o_u8, npix);
     return EORB_OK;
 }
 
@@ -1315,24 +1285,23 @@ static int tracked_common(eorb_ctx* c, const uint8_t* img, int W, int H, int str
     if (n == 0) return EORB_OK;
     fe_enter(c);
     int rc;
-    if ((rc = ensure(c, c->in_img, (size_t)W * H))) return rc;
-    if ((rc = ensure(c, c->out_kp, sizeof(eorb_keypoint) * (size_t)std::max(n, o.max_out)))) return rc;
-    if ((rc = ensure(c, c->m_a, 32 * (size_t)std::max(n, o.max_out)))) return rc;
-    if ((rc = ensure(c, c->m_b, (size_t)std::max(n, o.max_out)))) return rc;
-    if ((rc = ensure(c, c->m_c, 32 * (size_t)n))) return rc;
-    if (stride == W) EORB_HIP(c, hipMemcpyAsync(c->in_img.p, img, (size_t)W * H, hipMemcpyHostToDevice, c->stream));
-    else EORB_HIP(c, hipMemcpy2DAsync(c->in_img.p, W, img, stride, W, H, hipMemcpyHostToDevice, c->stream));
-    EORB_HIP(c, hipMemcpyAsync(c->out_kp.p, kps_in, sizeof(eorb_keypoint) * n, hipMemcpyHostToDevice, c->stream));
-    if (ref) EORB_HIP(c, hipMemcpyAsync(c->m_c.p, ref, 32 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = orb_pyramid_blur_dev(c, (const uint8_t*)c->in_img.p, W))) return rc;
-    if ((rc = orb_tracked_dev(c, (eorb_keypoint*)c->out_kp.p, n, mode, (const uint8_t*)c->m_c.p, (uint8_t*)c->m_a.p, (uint8_t*)c->m_b.p))) return rc;
+    Arena A(c);
+    const size_t o_img = A.in2d(img, H, (size_t)W, (size_t)stride), o_ref = A.in(ref, ref ? 32 * (size_t)n : 0);
+    // keypoints (in / out: mode 1 writes their octaves) | outputs of mode 0, contiguous: descriptors | oob
+    const size_t o_kp = A.in(kps_in, sizeof(eorb_keypoint) * (size_t)n);
+    const size_t o_desc = A.reserve(32 * (size_t)n), o_oob = A.reserve((size_t)n);
+    if ((rc = A.upload())) return rc;
+    if ((rc = orb_pyramid_blur_dev(c, A.dev<uint8_t>(o_img), W))) return rc;
+    if ((rc = orb_tracked_dev(c, A.dev<eorb_keypoint>(o_kp), n, mode, A.dev<uint8_t>(o_ref), A.dev<uint8_t>(o_desc), A.dev<uint8_t>(o_oob)))) return rc;
+    const char* h;
     if (mode == 0) {
-        EORB_HIP(c, hipMemcpyAsync(desc, c->m_a.p, 32 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-        if (oob) EORB_HIP(c, hipMemcpyAsync(oob, c->m_b.p, n, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = A.download(o_desc, (oob ? o_oob + n : o_desc + 32 * (size_t)n) - o_desc, &h))) return rc;
+        memcpy(desc, h + o_desc, 32 * (size_t)n);
+        if (oob) memcpy(oob, h + o_oob, (size_t)n);
     } else {
-        EORB_HIP(c, hipMemcpyAsync(kps_io, c->out_kp.p, sizeof(eorb_keypoint) * n, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = A.download(o_kp, sizeof(eorb_keypoint) * (size_t)n, &h))) return rc;
+        memcpy(kps_io, h + o_kp, sizeof(eorb_keypoint) * (size_t)n);
     }
-    EORB_HIP(c, fe_stream_sync(c));
     return EORB_OK;
 }
 
@@ -1351,30 +1320,6 @@ int eorb_orb_assign_level_by_best_desc(eorb_ctx* c, const uint8_t* img, int W, i
 }
 
 // ---- matchers, host buffers ------------------------------------------------------------------------------
-static int up_to(eorb_ctx* c, void* d_dst, const void* h, size_t bytes);
-static int up(eorb_ctx* c, DevBuf& b, const void* h, size_t bytes)
-{
-    int rc = ensure(c, b, bytes);
-    if (rc) return rc;
-    return up_to(c, b.p, h, bytes);
-}
-// h -> d_dst (room for bytes rounded up to 16 there), staged in pinned memory and launched by up_flush()
-static int up_to(eorb_ctx* c, void* d_dst, const void* h, size_t bytes)
-{
-    struct { void* p; } b{d_dst};
-    if (!bytes || !h) return EORB_OK;
-    static const long kmax = [] { const char* e = getenv("EORB_UPLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }();
-    void* p = (long)bytes <= kmax ? pin_bump(c->up_pin, bytes) : nullptr;
-    if (!p) {                                           // (the caller's buffer may be a local: consumed before the return)
-        EORB_HIP(c, hipMemcpyAsync(b.p, h, bytes, hipMemcpyHostToDevice, c->stream));
-        EORB_HIP(c, hipStreamSynchronize(c->stream));
-        return EORB_OK;
-    }
-    memcpy(p, h, bytes);
-    c->up_queue.push_back({b.p, p, bytes});              // (launched by up_flush(): all of an entry's buffers in one kernel)
-    return EORB_OK;
-}
-
 int eorb_search_for_initialization(eorb_ctx* c,
         const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* is_orb1,
         const eorb_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const uint8_t* is_orb2,
@@ -1575,14 +1520,13 @@ static int bow_common(eorb_ctx* c, int kf_kf,
     for (int i = 0; i < nki; i++) if (kf_idx[i] < 0 || kf_idx[i] >= n_kf) return set_err(c, EORB_E_ARG, "search_by_bow: KeyFrame index out of range");
     for (int i = 0; i < nfi; i++) if (f_idx[i] < 0 || f_idx[i] >= n_f) return set_err(c, EORB_E_ARG, "search_by_bow: frame index out of range");
     int rc;
-    if ((rc = up(c, c->m_a, kf_kps, sizeof(eorb_keypoint) * n_kf))) return rc;
-    if ((rc = up(c, c->m_b, kf_desc, 32 * (size_t)n_kf))) return rc;
-    if ((rc = up(c, c->m_c, f_kps, sizeof(eorb_keypoint) * n_f))) return rc;
-    if ((rc = up(c, c->m_d, f_desc, 32 * (size_t)n_f))) return rc;
+    Arena A(c);
+    const size_t o_kk = A.in(kf_kps, sizeof(eorb_keypoint) * n_kf), o_kd = A.in(kf_desc, 32 * (size_t)n_kf);
+    const size_t o_fk = A.in(f_kps, sizeof(eorb_keypoint) * n_f), o_fd = A.in(f_desc, 32 * (size_t)n_f);
     std::vector<uint8_t> flags((size_t)n_kf + n_f, 1);
     memcpy(flags.data(), kf_has_mp, n_kf);
     if (f_has_mp) memcpy(flags.data() + n_kf, f_has_mp, n_f);
-    if ((rc = up(c, c->m_e, flags.data(), flags.size()))) return rc;
+    const size_t o_fl = A.in(flags.data(), flags.size());
     // CSR blocks: [kf_nodes | kf_off | kf_idx] and [f_nodes | f_off | f_idx]
     std::vector<int32_t> blk;
     blk.insert(blk.end(), (const int32_t*)kf_nodes, (const int32_t*)kf_nodes + kf_nn);
@@ -1592,34 +1536,33 @@ static int bow_common(eorb_ctx* c, int kf_kf,
     blk.insert(blk.end(), (const int32_t*)f_nodes, (const int32_t*)f_nodes + f_nn);
     blk.insert(blk.end(), f_node_off, f_node_off + f_nn + 1);
     blk.insert(blk.end(), f_idx, f_idx + nfi);
-    if ((rc = up(c, c->m_f, blk.data(), sizeof(int32_t) * blk.size()))) return rc;
-    if ((rc = ensure(c, c->m_h, sizeof(int32_t) * (size_t)(n_f + n_kf)))) return rc;
-    if ((rc = ensure(c, c->m_g, (size_t)std::max(n_f, n_kf)))) return rc;
-    if ((rc = ensure(c, c->m_j, sizeof(int32_t) * 40))) return rc;
-    if ((rc = up_flush(c))) return rc;                  // (no wait here: up() has consumed the host buffers when it returns)
-    const int32_t* B = (const int32_t*)c->m_f.p;
-    int32_t* hist = (int32_t*)c->m_j.p;
-    int32_t* d_match_f = (int32_t*)c->m_h.p;
-    int32_t* d_match12 = d_match_f + n_f;
+    const size_t o_blk = A.in(blk.data(), sizeof(int32_t) * blk.size());
+    // outputs, contiguous: histogram (nmatches at [32]) | frame matches | KeyFrame matches; then the rotation bins
+    const size_t o_hist = A.reserve(sizeof(int32_t) * 40), o_mf = A.reserve(sizeof(int32_t) * n_f), o_m12 = A.reserve(sizeof(int32_t) * n_kf);
+    const size_t o_bin = A.reserve((size_t)std::max(n_f, n_kf));
+    if ((rc = A.upload())) return rc;
+    const int32_t* B = A.dev<int32_t>(o_blk);
+    int32_t* hist = A.dev<int32_t>(o_hist);
+    const uint8_t* fl = A.dev<uint8_t>(o_fl);
     if (fisheye_nL >= 0)
-        rc = search_bow_fisheye_dev(c, (const eorb_keypoint*)c->m_a.p, (const uint8_t*)c->m_b.p, (const uint8_t*)c->m_e.p,
+        rc = search_bow_fisheye_dev(c, A.dev<eorb_keypoint>(o_kk), A.dev<uint8_t>(o_kd), fl,
                                     (const uint32_t*)B, B + kf_nn, B + kf_nn + kf_nn + 1, kf_nn,
-                                    (const eorb_keypoint*)c->m_c.p, n_f, fisheye_nL, (const uint8_t*)c->m_d.p,
+                                    A.dev<eorb_keypoint>(o_fk), n_f, fisheye_nL, A.dev<uint8_t>(o_fd),
                                     (const uint32_t*)(B + fbase), B + fbase + f_nn, B + fbase + f_nn + f_nn + 1, f_nn,
-                                    d_match_f, (int8_t*)c->m_g.p, hist, hist + 32, nnratio, checkOri);
+                                    A.dev<int32_t>(o_mf), A.dev<int8_t>(o_bin), hist, hist + 32, nnratio, checkOri);
     else
-    rc = search_bow_dev(c, (const eorb_keypoint*)c->m_a.p, (const uint8_t*)c->m_b.p, (const uint8_t*)c->m_e.p,
+    rc = search_bow_dev(c, A.dev<eorb_keypoint>(o_kk), A.dev<uint8_t>(o_kd), fl,
                         (const uint32_t*)B, B + kf_nn, B + kf_nn + kf_nn + 1, kf_nn,
-                        (const eorb_keypoint*)c->m_c.p, n_f, (const uint8_t*)c->m_d.p,
+                        A.dev<eorb_keypoint>(o_fk), n_f, A.dev<uint8_t>(o_fd),
                         (const uint32_t*)(B + fbase), B + fbase + f_nn, B + fbase + f_nn + f_nn + 1, f_nn,
-                        d_match_f, (int8_t*)c->m_g.p, hist, hist + 32, nnratio, checkOri, kf_kf,
-                        (const uint8_t*)c->m_e.p + n_kf, d_match12, n_kf);
+                        A.dev<int32_t>(o_mf), A.dev<int8_t>(o_bin), hist, hist + 32, nnratio, checkOri, kf_kf,
+                        fl + n_kf, A.dev<int32_t>(o_m12), n_kf);
     if (rc) return rc;
-    int nm = 0;
-    { const int rc_dn = down(c, match_out, kf_kf ? d_match12 : d_match_f, sizeof(int32_t) * nout); if (rc_dn) return rc_dn; }
-    { const int rc_dn = down(c, &nm, hist + 32, 4); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
-    if (nmatches) *nmatches = nm;
+    const size_t o_out = kf_kf ? o_m12 : o_mf;
+    const char* h;
+    if ((rc = A.download(o_hist, o_out + sizeof(int32_t) * nout - o_hist, &h))) return rc;
+    memcpy(match_out, h + o_out, sizeof(int32_t) * nout);
+    if (nmatches) memcpy(nmatches, h + o_hist + sizeof(int32_t) * 32, 4);
     return EORB_OK;
 }
 
@@ -1854,13 +1797,10 @@ int eorb_search_for_triangulation(eorb_ctx* c,
         if (elig2[i] && (kps2[i].octave < 0 || kps2[i].octave >= nlevels))
             return set_err(c, EORB_E_ARG, "search_for_triangulation: pKF2 keypoint %d has octave %d outside [0,%d)", i, kps2[i].octave, nlevels);
     int rc;
-    if ((rc = up(c, c->m_a, kps1, sizeof(eorb_keypoint) * n1))) return rc;
-    if ((rc = up(c, c->m_b, desc1, (size_t)stride1 * n1))) return rc;
-    if ((rc = up(c, c->m_c, kps2, sizeof(eorb_keypoint) * n2))) return rc;
-    if ((rc = up(c, c->m_d, desc2, (size_t)stride2 * n2))) return rc;
-    std::vector<uint8_t> flags((size_t)n1 + n2);
-    memcpy(flags.data(), elig1, n1); memcpy(flags.data() + n1, elig2, n2);
-    if ((rc = up(c, c->m_e, flags.data(), flags.size()))) return rc;
+    Arena A(c);
+    const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * n1), o_d1 = A.in(desc1, (size_t)stride1 * n1);
+    const size_t o_k2 = A.in(kps2, sizeof(eorb_keypoint) * n2), o_d2 = A.in(desc2, (size_t)stride2 * n2);
+    const size_t o_e1 = A.in(elig1, n1), o_e2 = A.in(elig2, n2);
     std::vector<int32_t> blk;
     blk.insert(blk.end(), (const int32_t*)nodes1, (const int32_t*)nodes1 + nn1);
     blk.insert(blk.end(), node_off1, node_off1 + nn1 + 1);
@@ -1869,34 +1809,30 @@ int eorb_search_for_triangulation(eorb_ctx* c,
     blk.insert(blk.end(), (const int32_t*)nodes2, (const int32_t*)nodes2 + nn2);
     blk.insert(blk.end(), node_off2, node_off2 + nn2 + 1);
     blk.insert(blk.end(), idx2, idx2 + nfi);
-    if ((rc = up(c, c->m_f, blk.data(), sizeof(int32_t) * blk.size()))) return rc;
-    std::vector<float> lv(2 * (size_t)nlevels);
-    memcpy(lv.data(), scale2, sizeof(float) * nlevels); memcpy(lv.data() + nlevels, sigma2_2, sizeof(float) * nlevels);
-    if ((rc = up(c, c->m_i, lv.data(), sizeof(float) * lv.size()))) return rc;
-    if ((rc = ensure(c, c->m_h, sizeof(int32_t) * (size_t)n1))) return rc;
-    if ((rc = ensure(c, c->m_g, (size_t)n1))) return rc;
-    if ((rc = ensure(c, c->m_j, sizeof(int32_t) * 40))) return rc;
-    if ((rc = up_flush(c))) return rc;                  // (no wait here: up() has consumed the host buffers when it returns)
-    const int32_t* B = (const int32_t*)c->m_f.p;
-    int32_t* hist = (int32_t*)c->m_j.p;
-    TriArgs A{};
-    A.kps1 = (const eorb_keypoint*)c->m_a.p; A.n1 = n1; A.desc1 = (const uint8_t*)c->m_b.p; A.stride1 = stride1;
-    A.elig1 = (const uint8_t*)c->m_e.p;
-    A.nodes1 = (const uint32_t*)B; A.off1 = B + nn1; A.idx1 = B + nn1 + nn1 + 1; A.nn1 = nn1;
-    A.kps2 = (const eorb_keypoint*)c->m_c.p; A.n2 = n2; A.desc2 = (const uint8_t*)c->m_d.p; A.stride2 = stride2;
-    A.elig2 = (const uint8_t*)c->m_e.p + n1;
-    A.nodes2 = (const uint32_t*)(B + fbase); A.off2 = B + fbase + nn2; A.idx2 = B + fbase + nn2 + nn2 + 1; A.nn2 = nn2;
-    A.epx = ep[0]; A.epy = ep[1];
-    for (int i = 0; i < 9; i++) A.F[i] = F12[i];
-    A.scale2 = (const float*)c->m_i.p; A.sigma2_2 = (const float*)c->m_i.p + nlevels; A.nlevels = nlevels;
-    A.bCoarse = bCoarse; A.checkOri = checkOri;
-    A.match12 = (int32_t*)c->m_h.p; A.bin1 = (int8_t*)c->m_g.p; A.histo = hist; A.nmatches = hist + 32;
-    if ((rc = search_tri_dev(c, A))) return rc;
-    int nm = 0;
-    { const int rc_dn = down(c, match12, c->m_h.p, sizeof(int32_t) * (size_t)n1); if (rc_dn) return rc_dn; }
-    { const int rc_dn = down(c, &nm, hist + 32, 4); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
-    if (nmatches) *nmatches = nm;
+    const size_t o_blk = A.in(blk.data(), sizeof(int32_t) * blk.size());
+    const size_t o_sc = A.in(scale2, sizeof(float) * nlevels), o_sg = A.in(sigma2_2, sizeof(float) * nlevels);
+    // outputs, contiguous: histogram (nmatches at [32]) | matches; then the rotation bins
+    const size_t o_hist = A.reserve(sizeof(int32_t) * 40), o_m12 = A.reserve(sizeof(int32_t) * (size_t)n1), o_bin = A.reserve((size_t)n1);
+    if ((rc = A.upload())) return rc;
+    const int32_t* B = A.dev<int32_t>(o_blk);
+    int32_t* hist = A.dev<int32_t>(o_hist);
+    TriArgs T{};
+    T.kps1 = A.dev<eorb_keypoint>(o_k1); T.n1 = n1; T.desc1 = A.dev<uint8_t>(o_d1); T.stride1 = stride1;
+    T.elig1 = A.dev<uint8_t>(o_e1);
+    T.nodes1 = (const uint32_t*)B; T.off1 = B + nn1; T.idx1 = B + nn1 + nn1 + 1; T.nn1 = nn1;
+    T.kps2 = A.dev<eorb_keypoint>(o_k2); T.n2 = n2; T.desc2 = A.dev<uint8_t>(o_d2); T.stride2 = stride2;
+    T.elig2 = A.dev<uint8_t>(o_e2);
+    T.nodes2 = (const uint32_t*)(B + fbase); T.off2 = B + fbase + nn2; T.idx2 = B + fbase + nn2 + nn2 + 1; T.nn2 = nn2;
+    T.epx = ep[0]; T.epy = ep[1];
+    for (int i = 0; i < 9; i++) T.F[i] = F12[i];
+    T.scale2 = A.dev<float>(o_sc); T.sigma2_2 = A.dev<float>(o_sg); T.nlevels = nlevels;
+    T.bCoarse = bCoarse; T.checkOri = checkOri;
+    T.match12 = A.dev<int32_t>(o_m12); T.bin1 = A.dev<int8_t>(o_bin); T.histo = hist; T.nmatches = hist + 32;
+    if ((rc = search_tri_dev(c, T))) return rc;
+    const char* h;
+    if ((rc = A.download(o_hist, o_m12 + sizeof(int32_t) * (size_t)n1 - o_hist, &h))) return rc;
+    memcpy(match12, h + o_m12, sizeof(int32_t) * (size_t)n1);
+    if (nmatches) memcpy(nmatches, h + o_hist + sizeof(int32_t) * 32, 4);
     return EORB_OK;
 }
 
@@ -1915,41 +1851,33 @@ static int kf_radius_common(eorb_ctx* c,
     for (int m = 0; m < M; m++) { best_idx[m] = -1; best_dist[m] = 256; }
     if (M == 0 || n == 0) return EORB_OK;
     int rc;
-    if ((rc = up(c, c->m_a, kps, sizeof(eorb_keypoint) * n))) return rc;
-    if ((rc = up(c, c->m_b, desc, (size_t)stride * n))) return rc;
-    if ((rc = up(c, c->m_c, uv, sizeof(float) * 2 * (size_t)M))) return rc;
-    std::vector<int32_t> qi(2 * (size_t)M);
-    memcpy(qi.data(), radius, sizeof(float) * M); memcpy(qi.data() + M, level, sizeof(int32_t) * M);
-    if ((rc = up(c, c->m_d, qi.data(), sizeof(int32_t) * qi.size()))) return rc;
-    std::vector<uint8_t> fl((size_t)M + n, 0);
-    memcpy(fl.data(), valid, M);
-    if (taken) memcpy(fl.data() + M, taken, n);
-    if ((rc = up(c, c->m_e, fl.data(), fl.size()))) return rc;
-    if ((rc = up(c, c->m_f, q_desc, 32 * (size_t)M))) return rc;
-    if (inv_sigma2 && (rc = up(c, c->m_i, inv_sigma2, sizeof(float) * nlevels))) return rc;
-    if (uright) {                                    // uright[n] | q_ur[M]
-        std::vector<float> st((size_t)n + M);
-        memcpy(st.data(), uright, sizeof(float) * n); memcpy(st.data() + n, q_ur, sizeof(float) * M);
-        if ((rc = up(c, c->m_j, st.data(), sizeof(float) * st.size()))) return rc;
-    }
-    if ((rc = ensure(c, c->m_h, sizeof(int32_t) * 2 * (size_t)M))) return rc;
-    if ((rc = ensure(c, c->m_g, sizeof(uint16_t) * (size_t)n))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    RadArgs A{};
-    A.kps = (const eorb_keypoint*)c->m_a.p; A.n = n; A.desc = (const uint8_t*)c->m_b.p; A.stride = stride;
-    A.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
-    A.cell = (const uint16_t*)c->m_g.p;
-    A.M = M; A.valid = (const uint8_t*)c->m_e.p; A.uv = (const float*)c->m_c.p;
-    A.radius = (const float*)c->m_d.p; A.level = (const int32_t*)c->m_d.p + M; A.q_desc = (const uint8_t*)c->m_f.p;
-    A.inv_sigma2 = inv_sigma2 ? (const float*)c->m_i.p : nullptr; A.nlevels = nlevels;
-    A.uright = uright ? (const float*)c->m_j.p : nullptr; A.q_ur = uright ? (const float*)c->m_j.p + n : nullptr;
-    A.taken = taken ? (uint8_t*)c->m_e.p + M : nullptr; A.accept_thr = accept_thr;
-    A.best_idx = (int32_t*)c->m_h.p; A.best_dist = (int32_t*)c->m_h.p + M;
-    if ((rc = kf_radius_dev(c, A, (uint16_t*)c->m_g.p))) return rc;
-    { const int rc_dn = down(c, best_idx, c->m_h.p, sizeof(int32_t) * (size_t)M); if (rc_dn) return rc_dn; }
-    { const int rc_dn = down(c, best_dist, (int32_t*)c->m_h.p + M, sizeof(int32_t) * (size_t)M); if (rc_dn) return rc_dn; }
-    if (taken) { const int rc_dn = down(c, taken, (uint8_t*)c->m_e.p + M, (size_t)n); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
+    Arena A(c);
+    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * n), o_d = A.in(desc, (size_t)stride * n);
+    const size_t o_uv = A.in(uv, sizeof(float) * 2 * (size_t)M), o_rad = A.in(radius, sizeof(float) * M), o_lv = A.in(level, sizeof(int32_t) * M);
+    const size_t o_va = A.in(valid, M), o_qd = A.in(q_desc, 32 * (size_t)M);
+    const size_t o_is = A.in(inv_sigma2, inv_sigma2 ? sizeof(float) * nlevels : 0);
+    const size_t o_ur = A.in(uright, uright ? sizeof(float) * n : 0), o_qur = A.in(q_ur, q_ur ? sizeof(float) * M : 0);
+    // outputs, contiguous: taken (in / out) | best index | best distance; then the keypoints' cells
+    const size_t o_tk = A.in(taken, taken ? (size_t)n : 0);
+    const size_t o_bi = A.reserve(sizeof(int32_t) * M), o_bd = A.reserve(sizeof(int32_t) * M), o_cell = A.reserve(sizeof(uint16_t) * n);
+    if ((rc = A.upload())) return rc;
+    RadArgs R{};
+    R.kps = A.dev<eorb_keypoint>(o_k); R.n = n; R.desc = A.dev<uint8_t>(o_d); R.stride = stride;
+    R.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
+    R.cell = A.dev<uint16_t>(o_cell);
+    R.M = M; R.valid = A.dev<uint8_t>(o_va); R.uv = A.dev<float>(o_uv);
+    R.radius = A.dev<float>(o_rad); R.level = A.dev<int32_t>(o_lv); R.q_desc = A.dev<uint8_t>(o_qd);
+    R.inv_sigma2 = inv_sigma2 ? A.dev<float>(o_is) : nullptr; R.nlevels = nlevels;
+    R.uright = uright ? A.dev<float>(o_ur) : nullptr; R.q_ur = uright ? A.dev<float>(o_qur) : nullptr;
+    R.taken = taken ? A.dev<uint8_t>(o_tk) : nullptr; R.accept_thr = accept_thr;
+    R.best_idx = A.dev<int32_t>(o_bi); R.best_dist = A.dev<int32_t>(o_bd);
+    if ((rc = kf_radius_dev(c, R, A.dev<uint16_t>(o_cell)))) return rc;
+    const size_t first = taken ? o_tk : o_bi;
+    const char* h;
+    if ((rc = A.download(first, o_bd + sizeof(int32_t) * M - first, &h))) return rc;
+    memcpy(best_idx, h + o_bi, sizeof(int32_t) * M);
+    memcpy(best_dist, h + o_bd, sizeof(int32_t) * M);
+    if (taken) memcpy(taken, h + o_tk, (size_t)n);
     return EORB_OK;
 }
 
@@ -2002,16 +1930,15 @@ int eorb_bow_set_vocabulary(eorb_ctx* c, int nnodes, int L, const int32_t* child
     off[3] = off[2] + al(32 * (size_t)nnodes);
     off[4] = off[3] + al(sizeof(int32_t) * (size_t)nnodes);
     off[5] = off[4] + al(sizeof(double) * (size_t)nnodes);
-    std::vector<uint8_t> blob(off[5], 0);
-    memcpy(blob.data() + off[0], child_off, sizeof(int32_t) * ((size_t)nnodes + 1));
-    memcpy(blob.data() + off[1], child_ids, sizeof(int32_t) * (size_t)nch);
-    memcpy(blob.data() + off[2], node_desc, 32 * (size_t)nnodes);
-    memcpy(blob.data() + off[3], word_id, sizeof(int32_t) * (size_t)nnodes);
-    memcpy(blob.data() + off[4], weight, sizeof(double) * (size_t)nnodes);
     int rc;
-    if ((rc = up(c, c->voc, blob.data(), blob.size()))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    EORB_HIP(c, fe_stream_sync(c));
+    if ((rc = upload_persistent(c, c->voc, off[5], [&](char* hp) {
+            memset(hp, 0, off[5]);
+            memcpy(hp + off[0], child_off, sizeof(int32_t) * ((size_t)nnodes + 1));
+            memcpy(hp + off[1], child_ids, sizeof(int32_t) * (size_t)nch);
+            memcpy(hp + off[2], node_desc, 32 * (size_t)nnodes);
+            memcpy(hp + off[3], word_id, sizeof(int32_t) * (size_t)nnodes);
+            memcpy(hp + off[4], weight, sizeof(double) * (size_t)nnodes);
+        }))) return rc;
     c->voc_nnodes = nnodes; c->voc_L = L;
     for (int i = 0; i < 5; i++) c->voc_off[i] = off[i];
     return EORB_OK;
@@ -2030,36 +1957,35 @@ int eorb_bow_transform(eorb_ctx* c, const uint8_t* desc, int n, int stride, int 
     *n_words = 0; *n_fvnodes = 0; fv_off[0] = 0;
     if (n == 0 || c->voc_nnodes <= 1) return EORB_OK;                       // empty() (:1132)
     int rc;
-    if ((rc = up(c, c->m_a, desc, (size_t)stride * n))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    // workspace: word_of u32 | node_of u32 | bow_word u32 | fv_node u32 | fv_off i32 (+1) | fv_idx i32 | counts | w_of f64 | bow_val f64
     const size_t N = (size_t)n;
-    if ((rc = ensure(c, c->m_b, 4 * (6 * N + 8) + 8 * (2 * N + 2)))) return rc;
-    uint32_t* w32 = (uint32_t*)c->m_b.p;
-    uint32_t* d_word_of = w32, *d_node_of = w32 + N, *d_bow_word = w32 + 2 * N, *d_fv_node = w32 + 3 * N;
-    int32_t* d_fv_off = (int32_t*)(w32 + 4 * N), *d_fv_idx = (int32_t*)(w32 + 5 * N + 2), *d_counts = (int32_t*)(w32 + 6 * N + 4);
-    double* d_w_of = (double*)(w32 + 6 * N + 8), *d_bow_val = d_w_of + N + 1;
+    Arena A(c);
+    const size_t o_desc = A.in(desc, (size_t)stride * n);
+    // outputs, contiguous: counts | bow_word | bow_val | fv_off (+1) | fv_node | fv_idx | word_of | node_of; then w_of
+    const size_t o_cnt = A.reserve(16), o_bw = A.reserve(4 * N), o_bv = A.reserve(8 * (N + 1)), o_fo = A.reserve(4 * (N + 2));
+    const size_t o_fn = A.reserve(4 * N), o_fi = A.reserve(4 * (N + 2)), o_wo = A.reserve(4 * N), o_no = A.reserve(4 * N);
+    const size_t o_wf = A.reserve(8 * (N + 1));
+    if ((rc = A.upload())) return rc;
     const char* vb = (const char*)c->voc.p;
     BowVoc V{c->voc_nnodes, c->voc_L, (const int32_t*)(vb + c->voc_off[0]), (const int32_t*)(vb + c->voc_off[1]),
              (const uint8_t*)(vb + c->voc_off[2]), (const int32_t*)(vb + c->voc_off[3]), (const double*)(vb + c->voc_off[4])};
-    if ((rc = bow_transform_dev(c, (const uint8_t*)c->m_a.p, n, stride, V, levelsup, weighting, norm, d_word_of, d_w_of, d_node_of,
-                                d_bow_word, d_bow_val, d_fv_node, d_fv_off, d_fv_idx, d_counts))) return rc;
-    int32_t cnt[2] = {0, 0};
-    { const int rc_dn = down(c, cnt, d_counts, 8); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
+    if ((rc = bow_transform_dev(c, A.dev<uint8_t>(o_desc), n, stride, V, levelsup, weighting, norm, A.dev<uint32_t>(o_wo), A.dev<double>(o_wf),
+                                A.dev<uint32_t>(o_no), A.dev<uint32_t>(o_bw), A.dev<double>(o_bv), A.dev<uint32_t>(o_fn), A.dev<int32_t>(o_fo),
+                                A.dev<int32_t>(o_fi), A.dev<int32_t>(o_cnt)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_cnt, 8, &h))) return rc;
+    int32_t cnt[2];
+    memcpy(cnt, h + o_cnt, 8);
     *n_words = cnt[0]; *n_fvnodes = cnt[1];
-    if (cnt[0]) {
-        { const int rc_dn = down(c, bow_word, d_bow_word, 4 * (size_t)cnt[0]); if (rc_dn) return rc_dn; }
-        { const int rc_dn = down(c, bow_val, d_bow_val, 8 * (size_t)cnt[0]); if (rc_dn) return rc_dn; }
-    }
-    { const int rc_dn = down(c, fv_off, d_fv_off, 4 * ((size_t)cnt[1] + 1)); if (rc_dn) return rc_dn; }
-    if (cnt[1]) { const int rc_dn = down(c, fv_node, d_fv_node, 4 * (size_t)cnt[1]); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
-    const int nfeat = fv_off[cnt[1]];
-    if (nfeat) { const int rc_dn = down(c, fv_idx, d_fv_idx, 4 * (size_t)nfeat); if (rc_dn) return rc_dn; }
-    if (word_of) { const int rc_dn = down(c, word_of, d_word_of, 4 * N); if (rc_dn) return rc_dn; }
-    if (node_of) { const int rc_dn = down(c, node_of, d_node_of, 4 * N); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
+    // the second range ends with the last array asked for: node_of, word_of or the feature vector's indices
+    const size_t end = node_of ? o_no + 4 * N : (word_of ? o_wo + 4 * N : o_fi + 4 * (N + 2));
+    if ((rc = A.download(o_bw, end - o_bw, &h))) return rc;
+    memcpy(bow_word, h + o_bw, 4 * (size_t)cnt[0]);
+    memcpy(bow_val, h + o_bv, 8 * (size_t)cnt[0]);
+    memcpy(fv_off, h + o_fo, 4 * ((size_t)cnt[1] + 1));
+    memcpy(fv_node, h + o_fn, 4 * (size_t)cnt[1]);
+    memcpy(fv_idx, h + o_fi, 4 * (size_t)fv_off[cnt[1]]);
+    if (word_of) memcpy(word_of, h + o_wo, 4 * N);
+    if (node_of) memcpy(node_of, h + o_no, 4 * N);
     return EORB_OK;
 }
 
@@ -2075,20 +2001,19 @@ int eorb_calc_optical_flow_pyr_lk(eorb_ctx* c, const uint8_t* prev, const uint8_
     if (n == 0) return EORB_OK;
     int rc;
     const size_t ib = (size_t)stride * H;
-    if ((rc = ensure(c, c->in_img, 2 * ib))) return rc;
-    if ((rc = up_to(c, c->in_img.p, prev, ib)) || (rc = up_to(c, (uint8_t*)c->in_img.p + ib, next, ib))) return rc;
-    if ((rc = up(c, c->m_a, prev_pts, sizeof(float) * 2 * (size_t)n))) return rc;
-    if ((rc = up(c, c->m_b, next_pts, sizeof(float) * 2 * (size_t)n))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    if ((rc = ensure(c, c->m_c, (size_t)n + 16))) return rc;
-    if ((rc = ensure(c, c->m_d, sizeof(float) * (size_t)n))) return rc;
-    if ((rc = klt_track_dev(c, (const uint8_t*)c->in_img.p, (const uint8_t*)c->in_img.p + ib, W, H, stride, (const float*)c->m_a.p,
-                            (float*)c->m_b.p, n, win, maxLevel, maxCount, epsilon, flags, minEigThreshold, (uint8_t*)c->m_c.p,
-                            (float*)c->m_d.p))) return rc;
-    { const int rc_dn = down(c, next_pts, c->m_b.p, sizeof(float) * 2 * (size_t)n); if (rc_dn) return rc_dn; }
-    { const int rc_dn = down(c, status, c->m_c.p, (size_t)n); if (rc_dn) return rc_dn; }
-    { const int rc_dn = down(c, err, c->m_d.p, sizeof(float) * (size_t)n); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
+    Arena A(c);
+    const size_t o_prev = A.in(prev, ib), o_next = A.in(next, ib), o_pp = A.in(prev_pts, sizeof(float) * 2 * (size_t)n);
+    // outputs, contiguous: next points (in / out) | status | err
+    const size_t o_np = A.in(next_pts, sizeof(float) * 2 * (size_t)n);
+    const size_t o_st = A.reserve((size_t)n + 16), o_err = A.reserve(sizeof(float) * (size_t)n);
+    if ((rc = A.upload())) return rc;
+    if ((rc = klt_track_dev(c, A.dev<uint8_t>(o_prev), A.dev<uint8_t>(o_next), W, H, stride, A.dev<float>(o_pp), A.dev<float>(o_np), n, win,
+                            maxLevel, maxCount, epsilon, flags, minEigThreshold, A.dev<uint8_t>(o_st), A.dev<float>(o_err)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_np, o_err + sizeof(float) * (size_t)n - o_np, &h))) return rc;
+    memcpy(next_pts, h + o_np, sizeof(float) * 2 * (size_t)n);
+    memcpy(status, h + o_st, (size_t)n);
+    memcpy(err, h + o_err, sizeof(float) * (size_t)n);
     return EORB_OK;
 }
 
@@ -2105,20 +2030,20 @@ int eorb_hamming_window_match(eorb_ctx* c, const uint8_t* q_desc, int nq, int q_
     for (int q = 0; q < nq; q++) if (cand_offsets[q + 1] < cand_offsets[q]) return set_err(c, EORB_E_ARG, "hamming_window_match: offsets not monotone");
     for (int k = 0; k < ncand; k++) if (cand_idx[k] < 0 || cand_idx[k] >= nt) return set_err(c, EORB_E_ARG, "hamming_window_match: candidate %d out of range", cand_idx[k]);
     int rc;
-    if ((rc = up(c, c->m_a, q_desc, (size_t)q_stride * nq))) return rc;
-    if ((rc = up(c, c->m_b, t_desc, (size_t)t_stride * std::max(nt, 1)))) return rc;
-    if ((rc = up(c, c->m_c, cand_offsets, sizeof(int32_t) * ((size_t)nq + 1)))) return rc;
-    if ((rc = up(c, c->m_d, cand_idx, sizeof(int32_t) * (size_t)std::max(ncand, 1)))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    if ((rc = ensure(c, c->m_h, sizeof(int32_t) * 4 * (size_t)nq))) return rc;
-    if ((rc = window_match_dev(c, (const uint8_t*)c->m_a.p, nq, q_stride, (const uint8_t*)c->m_b.p, t_stride, (const int32_t*)c->m_c.p,
-                               (const int32_t*)c->m_d.p, (int32_t*)c->m_h.p))) return rc;
-    int32_t* o = (int32_t*)c->m_h.p;
-    { const int rc_dn = down(c, best_idx, o, 4 * (size_t)nq); if (rc_dn) return rc_dn; }
-    { const int rc_dn = down(c, best_d, o + nq, 4 * (size_t)nq); if (rc_dn) return rc_dn; }
-    { const int rc_dn = down(c, second_idx, o + 2 * (size_t)nq, 4 * (size_t)nq); if (rc_dn) return rc_dn; }
-    { const int rc_dn = down(c, second_d, o + 3 * (size_t)nq, 4 * (size_t)nq); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
+    Arena A(c);
+    const size_t o_q = A.in(q_desc, (size_t)q_stride * nq), o_t = A.in(t_desc, (size_t)t_stride * nt);
+    const size_t o_off = A.in(cand_offsets, sizeof(int32_t) * ((size_t)nq + 1)), o_cand = A.in(cand_idx, sizeof(int32_t) * (size_t)ncand);
+    const size_t o_out = A.reserve(sizeof(int32_t) * 4 * (size_t)nq);      // best index | best distance | second index | second distance
+    if ((rc = A.upload())) return rc;
+    if ((rc = window_match_dev(c, A.dev<uint8_t>(o_q), nq, q_stride, A.dev<uint8_t>(o_t), t_stride, A.dev<int32_t>(o_off),
+                               A.dev<int32_t>(o_cand), A.dev<int32_t>(o_out)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_out, sizeof(int32_t) * 4 * (size_t)nq, &h))) return rc;
+    const int32_t* o = (const int32_t*)(h + o_out);
+    memcpy(best_idx, o, 4 * (size_t)nq);
+    memcpy(best_d, o + nq, 4 * (size_t)nq);
+    memcpy(second_idx, o + 2 * (size_t)nq, 4 * (size_t)nq);
+    memcpy(second_d, o + 3 * (size_t)nq, 4 * (size_t)nq);
     return EORB_OK;
 }
 
@@ -2131,13 +2056,14 @@ int eorb_distinctive_descriptors(eorb_ctx* c, const uint8_t* desc, const int32_t
     fe_enter(c);
     const int n = offsets[M];
     int rc;
-    if ((rc = up(c, c->m_a, desc, 32 * (size_t)std::max(n, 1)))) return rc;
-    if ((rc = up(c, c->m_b, offsets, sizeof(int32_t) * (size_t)(M + 1)))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    if ((rc = ensure(c, c->m_h, sizeof(int32_t) * (size_t)M))) return rc;
-    if ((rc = distinctive_dev(c, (const uint8_t*)c->m_a.p, (const int32_t*)c->m_b.p, M, (int32_t*)c->m_h.p))) return rc;
-    { const int rc_dn = down(c, best, c->m_h.p, sizeof(int32_t) * (size_t)M); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
+    Arena A(c);
+    const size_t o_desc = A.in(desc, 32 * (size_t)n), o_off = A.in(offsets, sizeof(int32_t) * (size_t)(M + 1));
+    const size_t o_best = A.reserve(sizeof(int32_t) * (size_t)M);
+    if ((rc = A.upload())) return rc;
+    if ((rc = distinctive_dev(c, A.dev<uint8_t>(o_desc), A.dev<int32_t>(o_off), M, A.dev<int32_t>(o_best)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_best, sizeof(int32_t) * (size_t)M, &h))) return rc;
+    memcpy(best, h + o_best, sizeof(int32_t) * (size_t)M);
     return EORB_OK;
 }
 
@@ -2148,12 +2074,13 @@ int eorb_sort_by_response(eorb_ctx* c, const eorb_keypoint* kps, int n, int32_t*
     if (n == 0) return EORB_OK;
     fe_enter(c);
     int rc;
-    if ((rc = up(c, c->m_a, kps, sizeof(eorb_keypoint) * n))) return rc;
-    if ((rc = up_flush(c))) return rc;
-    if ((rc = ensure(c, c->m_h, sizeof(int32_t) * n))) return rc;
-    if ((rc = sort_response_dev(c, (const eorb_keypoint*)c->m_a.p, n, (int32_t*)c->m_h.p))) return rc;
-    { const int rc_dn = down(c, perm, c->m_h.p, sizeof(int32_t) * n); if (rc_dn) return rc_dn; }
-    EORB_HIP(c, fe_stream_sync(c));
+    Arena A(c);
+    const size_t o_kp = A.in(kps, sizeof(eorb_keypoint) * n), o_perm = A.reserve(sizeof(int32_t) * n);
+    if ((rc = A.upload())) return rc;
+    if ((rc = sort_response_dev(c, A.dev<eorb_keypoint>(o_kp), n, A.dev<int32_t>(o_perm)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_perm, sizeof(int32_t) * n, &h))) return rc;
+    memcpy(perm, h + o_perm, sizeof(int32_t) * n);
     return EORB_OK;
 }
 
@@ -2209,8 +2136,8 @@ int eorb_fe_configure(eorb_ctx* c, const eorb_fe_config* cfg)
     if ((rc = ensure(c, c->fe_prev_kp, sizeof(eorb_keypoint) * cap * (B + 1)))) return rc;
     if ((rc = ensure(c, c->fe_prev_desc, 32 * cap * (B + 1)))) return rc;
     if ((rc = ensure(c, c->fe_prev_n, sizeof(int32_t) * (2 * B + 4)))) return rc;
-    if ((rc = ensure(c, c->m_h, sizeof(int32_t) * cap * B))) return rc;   // matches12 (when the caller passes none)
-    if ((rc = ensure(c, c->m_j, sizeof(int32_t) * (B + 1)))) return rc;    // nmatches
+    if ((rc = ensure(c, c->fe_matches12, sizeof(int32_t) * cap * B))) return rc;
+    if ((rc = ensure(c, c->fe_nmatches, sizeof(int32_t) * (B + 1)))) return rc;
     EORB_HIP(c, hipMemsetAsync(c->fe_prev_n.p, 0, sizeof(int32_t) * (2 * B + 4), c->stream));
     c->fe_configured = true;
     c->fe_has_prev = false;
@@ -2266,8 +2193,8 @@ static int fe_run_batch_common(eorb_ctx* c, const void* d_events, int raw, const
         gb.invW = (float)kGridCols / (gb.maxX - gb.minX); gb.invH = (float)kGridRows / (gb.maxY - gb.minY);
         const int first = c->fe_has_prev ? 0 : 1;                  // pair p: slice p-1 (slot p) vs slice p (slot p+1)
         const int npairs = B - first;
-        int32_t* m12 = d_matches12 ? d_matches12 : (int32_t*)c->m_h.p;
-        int32_t* nm = d_nmatches ? d_nmatches : (int32_t*)c->m_j.p;
+        int32_t* m12 = d_matches12 ? d_matches12 : (int32_t*)c->fe_matches12.p;
+        int32_t* nm = d_nmatches ? d_nmatches : (int32_t*)c->fe_nmatches.p;
         if (!c->fe_has_prev) {
             EORB_HIP(c, hipMemsetAsync(nm, 0, sizeof(int32_t), c->stream));
             EORB_HIP(c, hipMemsetAsync(m12, 0xff, sizeof(int32_t) * cap, c->stream));
@@ -2333,10 +2260,13 @@ int eorb_fe_last_f32_dev(eorb_ctx* c, const float** d_f32, float* h_minmax, int 
     if (d_f32) *d_f32 = (const float*)c->img_f32.p;
     if (h_minmax && B) {
         fe_enter(c);
-        std::vector<uint32_t> enc(2 * (size_t)B);
-        { const int rc_dn = down(c, enc.data(), c->minmax.p, sizeof(uint32_t) * enc.size()); if (rc_dn) return rc_dn; }
+        const size_t nenc = 2 * (size_t)B;
+        const uint32_t* enc = (const uint32_t*)pinned(c, sizeof(uint32_t) * nenc);      // (2 x max_batch words: more than readback_buf holds)
+        if (!enc) return set_err(c, EORB_E_HIP, "pinned alloc failed");
+        EORB_HIP(c, hipMemcpyAsync((void*)enc, c->minmax.p, sizeof(uint32_t) * nenc, hipMemcpyDeviceToHost, c->stream));
+        pinned_commit(c, true);
         EORB_HIP(c, fe_stream_sync(c));
-        for (size_t k = 0; k < enc.size(); k++) {           // the order-preserving integer encoding of the gather kernels' atomics
+        for (size_t k = 0; k < nenc; k++) {                 // the order-preserving integer encoding of the gather kernels' atomics
             const uint32_t e = enc[k], u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
             memcpy(&h_minmax[k], &u, 4);
         }
