@@ -17,7 +17,7 @@ EXPORTS = [
     "eorb_orb_configure", "eorb_orb_max_keypoints", "eorb_orb_get_tables", "eorb_orb_extract",
     "eorb_search_for_initialization", "eorb_search_by_projection_last", "eorb_search_by_projection_map", "eorb_search_by_projection_kf", "eorb_search_by_projection_last_stereo", "eorb_search_by_projection_map_stereo", "eorb_frame_stereo",
     "eorb_frame_fisheye", "eorb_search_by_projection_map_fisheye", "eorb_search_by_projection_last_fisheye", "eorb_search_by_bow_fisheye",
-    "eorb_hamming_bf_knn2", "eorb_search_by_bow", "eorb_search_by_bow_kf", "eorb_distinctive_descriptors", "eorb_hamming_window_match", "eorb_calc_optical_flow_pyr_lk", "eorb_bow_set_vocabulary", "eorb_bow_transform", "eorb_search_for_triangulation", "eorb_kf_radius_match", "eorb_kf_radius_match_stereo", "eorb_sort_by_response", "eorb_resolve_num_mixed",
+    "eorb_hamming_bf_knn2", "eorb_search_by_bow", "eorb_search_by_bow_kf", "eorb_distinctive_descriptors", "eorb_hamming_window_match", "eorb_calc_optical_flow_pyr_lk", "eorb_bow_set_vocabulary", "eorb_bow_transform", "eorb_search_for_triangulation", "eorb_search_for_triangulation_kb8", "eorb_kb8_triangulate_matches", "eorb_kf_radius_match", "eorb_kf_radius_match_stereo", "eorb_sort_by_response", "eorb_resolve_num_mixed",
     "eorb_orb_tracked_descriptors", "eorb_orb_assign_level_by_best_desc",
     "eorb_fe_configure", "eorb_fe_run_batch_dev", "eorb_fe_last_f32_dev",
     "eorb_ev_slice_extract", "eorb_ev_slice_track", "eorb_ev_slice_image", "eorb_ev_mc_contest",
@@ -193,6 +193,11 @@ def lib():
     L.eorb_search_for_triangulation.restype = ci
     L.eorb_search_for_triangulation.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, ci,
                                                 vp, vp, vp, vp, ci, ci, ci, vp, pi]
+    L.eorb_search_for_triangulation_kb8.restype = ci
+    L.eorb_search_for_triangulation_kb8.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, vp, ci,
+                                                    vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, pi]
+    L.eorb_kb8_triangulate_matches.restype = ci
+    L.eorb_kb8_triangulate_matches.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp]
     L.eorb_kf_radius_match.restype = ci
     L.eorb_kf_radius_match.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, cf, vp, vp]
     L.eorb_kf_radius_match_stereo.restype = ci

@@ -56,6 +56,9 @@ int search_bow_dev(eorb_ctx* c, const eorb_keypoint* kf_kps, const uint8_t* kf_d
                    const int32_t* f_idx, int f_nn, int32_t* match_f, int8_t* bin_f, int32_t* histo, int32_t* nmatches,
                    float nnratio, int checkOri, int kf_kf, const uint8_t* f_has_mp, int32_t* match12, int n_kf);
 int search_tri_dev(eorb_ctx* c, const TriArgs& A);
+int search_tri_kb8_dev(eorb_ctx* c, const TriKbArgs& K);
+int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const eorb_keypoint* kps1,
+                      const eorb_keypoint* kps2, int n, const float* sig1, const float* sig2, float* out);
 int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell);
 int bow_transform_dev(eorb_ctx* c, const uint8_t* d_desc, int n, int stride, const BowVoc& V, int levelsup, int weighting, int norm,
                       uint32_t* d_word_of, double* d_w_of, uint32_t* d_node_of, uint32_t* d_bow_word, double* d_bow_val,
@@ -1774,28 +1777,30 @@ int eorb_search_by_projection_last_fisheye(eorb_ctx* c,
     return EORB_OK;
 }
 
-int eorb_search_for_triangulation(eorb_ctx* c,
+// the BoW-node walk of SearchForTriangulation (:975-1214) shared by both camera models: kb == nullptr runs the Pinhole test on
+// F12, otherwise KannalaBrandt8::epipolarConstrain with kb's cameras and poses.  One upload, one wait, one download.
+static int search_tri_common(eorb_ctx* c, const char* what,
         const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
         const eorb_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
         const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
-        const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
-        int bCoarse, int checkOri, int32_t* match12, int* nmatches)
+        const float* ep, const float* F12, const float* scale2, const float* sigma2_2, const float* sigma2_1, int nlevels,
+        int bCoarse, int checkOri, TriKbArgs* kb, int32_t* match12, int* nmatches)
 {
-    if (!c) return EORB_E_ARG;
-    if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !match12 || stride1 < 32 || stride2 < 32 || !ep || !F12 || !scale2 || !sigma2_2 ||
-        nlevels <= 0 || nlevels > 64)
-        return set_err(c, EORB_E_ARG, "search_for_triangulation: bad arguments");
     fe_enter(c);
     if (nmatches) *nmatches = 0;
     for (int i = 0; i < n1; i++) match12[i] = -1;
     if (n1 == 0 || n2 == 0 || nn1 == 0 || nn2 == 0) return EORB_OK;
     const int nki = node_off1[nn1], nfi = node_off2[nn2];
-    for (int i = 0; i < nki; i++) if (idx1[i] < 0 || idx1[i] >= n1) return set_err(c, EORB_E_ARG, "search_for_triangulation: pKF1 index out of range");
-    for (int i = 0; i < nfi; i++) if (idx2[i] < 0 || idx2[i] >= n2) return set_err(c, EORB_E_ARG, "search_for_triangulation: pKF2 index out of range");
+    for (int i = 0; i < nki; i++) if (idx1[i] < 0 || idx1[i] >= n1) return set_err(c, EORB_E_ARG, "%s: pKF1 index out of range", what);
+    for (int i = 0; i < nfi; i++) if (idx2[i] < 0 || idx2[i] >= n2) return set_err(c, EORB_E_ARG, "%s: pKF2 index out of range", what);
     for (int i = 0; i < n2; i++)
         if (elig2[i] && (kps2[i].octave < 0 || kps2[i].octave >= nlevels))
-            return set_err(c, EORB_E_ARG, "search_for_triangulation: pKF2 keypoint %d has octave %d outside [0,%d)", i, kps2[i].octave, nlevels);
+            return set_err(c, EORB_E_ARG, "%s: pKF2 keypoint %d has octave %d outside [0,%d)", what, i, kps2[i].octave, nlevels);
+    if (kb)
+        for (int i = 0; i < n1; i++)
+            if ((elig1[i] & 1) && (kps1[i].octave < 0 || kps1[i].octave >= nlevels))
+                return set_err(c, EORB_E_ARG, "%s: pKF1 keypoint %d has octave %d outside [0,%d)", what, i, kps1[i].octave, nlevels);
     int rc;
     Arena A(c);
     const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * n1), o_d1 = A.in(desc1, (size_t)stride1 * n1);
@@ -1811,6 +1816,7 @@ int eorb_search_for_triangulation(eorb_ctx* c,
     blk.insert(blk.end(), idx2, idx2 + nfi);
     const size_t o_blk = A.in(blk.data(), sizeof(int32_t) * blk.size());
     const size_t o_sc = A.in(scale2, sizeof(float) * nlevels), o_sg = A.in(sigma2_2, sizeof(float) * nlevels);
+    const size_t o_s1 = kb ? A.in(sigma2_1, sizeof(float) * nlevels) : 0;
     // outputs, contiguous: histogram (nmatches at [32]) | matches; then the rotation bins
     const size_t o_hist = A.reserve(sizeof(int32_t) * 40), o_m12 = A.reserve(sizeof(int32_t) * (size_t)n1), o_bin = A.reserve((size_t)n1);
     if ((rc = A.upload())) return rc;
@@ -1824,16 +1830,98 @@ int eorb_search_for_triangulation(eorb_ctx* c,
     T.elig2 = A.dev<uint8_t>(o_e2);
     T.nodes2 = (const uint32_t*)(B + fbase); T.off2 = B + fbase + nn2; T.idx2 = B + fbase + nn2 + nn2 + 1; T.nn2 = nn2;
     T.epx = ep[0]; T.epy = ep[1];
-    for (int i = 0; i < 9; i++) T.F[i] = F12[i];
+    if (F12) for (int i = 0; i < 9; i++) T.F[i] = F12[i];
     T.scale2 = A.dev<float>(o_sc); T.sigma2_2 = A.dev<float>(o_sg); T.nlevels = nlevels;
     T.bCoarse = bCoarse; T.checkOri = checkOri;
     T.match12 = A.dev<int32_t>(o_m12); T.bin1 = A.dev<int8_t>(o_bin); T.histo = hist; T.nmatches = hist + 32;
-    if ((rc = search_tri_dev(c, T))) return rc;
+    if (kb) {
+        kb->T = T; kb->sigma2_1 = A.dev<float>(o_s1);
+        if ((rc = search_tri_kb8_dev(c, *kb))) return rc;
+    } else if ((rc = search_tri_dev(c, T))) return rc;
     const char* h;
     if ((rc = A.download(o_hist, o_m12 + sizeof(int32_t) * (size_t)n1 - o_hist, &h))) return rc;
     memcpy(match12, h + o_m12, sizeof(int32_t) * (size_t)n1);
     if (nmatches) memcpy(nmatches, h + o_hist + sizeof(int32_t) * 32, 4);
     return EORB_OK;
+}
+
+int eorb_search_for_triangulation(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
+        const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !match12 || stride1 < 32 || stride2 < 32 || !ep || !F12 || !scale2 || !sigma2_2 ||
+        nlevels <= 0 || nlevels > 64)
+        return set_err(c, EORB_E_ARG, "search_for_triangulation: bad arguments");
+    return search_tri_common(c, "search_for_triangulation", kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1,
+                             kps2, n2, desc2, stride2, elig2, nodes2, node_off2, idx2, nn2, ep, F12, scale2, sigma2_2, nullptr,
+                             nlevels, bCoarse, checkOri, nullptr, match12, nmatches);
+}
+
+int eorb_search_for_triangulation_kb8(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_keypoint* kps2, int n2, int nleft2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
+        const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
+        const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !match12 || stride1 < 32 || stride2 < 32 || !cam1 || !cam2 || !Rt || !ep ||
+        !scale2 || !sigma2_1 || !sigma2_2 || nlevels <= 0 || nlevels > 64 || nleft1 < -1 || nleft2 < -1 || nleft1 > n1 || nleft2 > n2)
+        return set_err(c, EORB_E_ARG, "search_for_triangulation_kb8: bad arguments");
+    fe_enter(c);
+    if (nmatches) *nmatches = 0;
+    for (int i = 0; i < n1; i++) match12[i] = -1;
+    const bool twocam = nleft1 >= 0;
+    if ((nleft1 < 0) != (nleft2 < 0))      // the reference leaves R12 an empty cv::Mat (:1000-1014)
+        return set_err(c, EORB_E_CONFIG, "search_for_triangulation_kb8: one keyframe has two cameras and the other one");
+    const int nc1 = twocam ? 2 : 1;
+    for (int k = 0; k < nc1; k++)
+        if (cam1[k].model != 1)
+            return set_err(c, EORB_E_CONFIG, "search_for_triangulation_kb8: pKF1's camera %d is not KannalaBrandt8 "
+                                             "(Pinhole pCamera1: eorb_search_for_triangulation)", k);
+    for (int k = 0; k < nc1; k++)
+        if (cam2[k].model != 0 && cam2[k].model != 1)
+            return set_err(c, EORB_E_ARG, "search_for_triangulation_kb8: pKF2's camera %d has model %d", k, cam2[k].model);
+    TriKbArgs K{};
+    K.nleft1 = nleft1; K.nleft2 = nleft2;
+    for (int k = 0; k < 2; k++) { K.cam1[k] = cam1[k < nc1 ? k : 0]; K.cam2[k] = cam2[k < nc1 ? k : 0]; }
+    for (int i = 0; i < (twocam ? 48 : 12); i++) K.Rt[i] = Rt[i];
+    return search_tri_common(c, "search_for_triangulation_kb8", kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1,
+                             kps2, n2, desc2, stride2, elig2, nodes2, node_off2, idx2, nn2, ep, nullptr, scale2, sigma2_2, sigma2_1,
+                             nlevels, bCoarse, checkOri, &K, match12, nmatches);
+}
+
+int eorb_kb8_triangulate_matches(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt,
+        const eorb_keypoint* kps1, const eorb_keypoint* kps2, int n, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        float* z1)
+{
+    if (!c) return EORB_E_ARG;
+    if (!cam1 || !cam2 || !Rt || n < 0 || (n > 0 && (!kps1 || !kps2 || !z1)) || !sigma2_1 || !sigma2_2 || nlevels <= 0 || nlevels > 64)
+        return set_err(c, EORB_E_ARG, "kb8_triangulate_matches: bad arguments");
+    if (cam1->model != 1 || (cam2->model != 0 && cam2->model != 1))
+        return set_err(c, EORB_E_CONFIG, "kb8_triangulate_matches: camera 1 must be KannalaBrandt8, camera 2 Pinhole or KannalaBrandt8");
+    fe_enter(c);
+    if (n == 0) return EORB_OK;
+    for (int i = 0; i < n; i++)
+        if (kps1[i].octave < 0 || kps1[i].octave >= nlevels || kps2[i].octave < 0 || kps2[i].octave >= nlevels)
+            return set_err(c, EORB_E_ARG, "kb8_triangulate_matches: pair %d has an octave outside [0,%d)", i, nlevels);
+    int rc;
+    Arena A(c);
+    const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * (size_t)n), o_k2 = A.in(kps2, sizeof(eorb_keypoint) * (size_t)n);
+    const size_t o_s1 = A.in(sigma2_1, sizeof(float) * nlevels), o_s2 = A.in(sigma2_2, sizeof(float) * nlevels);
+    const size_t o_z = A.reserve(sizeof(float) * (size_t)n);
+    if ((rc = A.upload())) return rc;
+    if ((rc = kb8_tri_batch_dev(c, cam1, cam2, Rt, A.dev<eorb_keypoint>(o_k1), A.dev<eorb_keypoint>(o_k2), n, A.dev<float>(o_s1),
+                                A.dev<float>(o_s2), A.dev<float>(o_z))))
+        return rc;
+    return A.download_to(z1, o_z, sizeof(float) * (size_t)n);
 }
 
 static int kf_radius_common(eorb_ctx* c,

@@ -18,6 +18,7 @@
 // All kernels are batched over time-slices (blockIdx ranges over slices x tiles / chunks).
 #include "eorb_ctx.h"
 #include "dev_math.h"
+#include "kb8_dev.h"
 #include "ev_common.h"
 #include <math.h>
 #include <algorithm>
@@ -1328,33 +1329,7 @@ __global__ void ev_decode_minmax_kernel(const uint32_t* mm, float* out, int B)
 // Motion-compensated accumulation: ev2mci_gg_f (src/Event/EventConversion.cc:280-531) = a per-event warp
 // followed by exactly the ev2im_gauss splat.  The warp kernels rewrite (x, y) of the 16-byte records; the splat is the
 // pipeline above.
-// GeometricCamera of the warp: model 0 = Pinhole (CameraModels/Pinhole.cpp:30-62), 1 = KannalaBrandt8 (KannalaBrandt8.cpp:87-190)
-struct WarpCam { int model; float fx, fy, cx, cy, k0, k1, k2, k3, precision; };
-
-// pCamera->unproject(cv::Point2f) -> (X, Y, 1)
-__device__ __forceinline__ void cam_unproject(const WarpCam& c, float x, float y, float& X, float& Y)
-{
-    const float pwx = (x - c.cx) / c.fx, pwy = (y - c.cy) / c.fy;
-    if (c.model == 0) { X = pwx; Y = pwy; return; }
-    // Newton iterations on theta, all in float (:164-187)
-    float scale = 1.f;
-    float theta_d = sqrtf(pwx * pwx + pwy * pwy);
-    theta_d = fminf(fmaxf((float)(-3.1415926535897932384626433832795 / 2.f), theta_d), (float)(3.1415926535897932384626433832795 / 2.f));
-    if ((double)theta_d > 1e-8) {
-        float theta = theta_d;
-        for (int j = 0; j < 10; j++) {
-            const float theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
-            const float k0_theta2 = c.k0 * theta2, k1_theta4 = c.k1 * theta4;
-            const float k2_theta6 = c.k2 * theta6, k3_theta8 = c.k3 * theta8;
-            const float theta_fix = (theta * (1 + k0_theta2 + k1_theta4 + k2_theta6 + k3_theta8) - theta_d) /
-                                    (1 + 3 * k0_theta2 + 5 * k1_theta4 + 7 * k2_theta6 + 9 * k3_theta8);
-            theta = theta - theta_fix;
-            if (fabsf(theta_fix) < c.precision) break;
-        }
-        scale = dev_tanf(theta) / theta_d;
-    }
-    X = pwx * scale; Y = pwy * scale;
-}
+// GeometricCamera of the warp: WarpCam, cam_unproject and kb8_project_f live in kb8_dev.h (shared with match.hip)
 
 struct WarpSE3 {
     WarpCam cam;
@@ -1447,15 +1422,7 @@ __global__ void ev_warp_se2_kernel(const eorb_event16* __restrict__ in, eorb_eve
         o.y = P.cam.fy * yp / 1.f + P.cam.cy;
     } else {
         // KannalaBrandt8::project(cv::Point3f(xp, yp, 1.f)) (:87-103), float throughout
-        const float x2_plus_y2 = xp * xp + yp * yp;
-        const float theta = dev_atan2f(sqrtf(x2_plus_y2), 1.f);
-        const float psi = dev_atan2f(yp, xp);
-        const float theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2, theta9 = theta7 * theta2;
-        const float r = theta + P.cam.k0 * theta3 + P.cam.k1 * theta5 + P.cam.k2 * theta7 + P.cam.k3 * theta9;
-        float ps, pc;
-        dev_sincosf(psi, &ps, &pc);
-        o.x = P.cam.fx * r * pc + P.cam.cx;
-        o.y = P.cam.fy * r * ps + P.cam.cy;
+        kb8_project_f(P.cam, xp, yp, 1.f, o.x, o.y);
     }
     out[k] = o;
 }

@@ -18,6 +18,7 @@
 #include "eorb_ctx.h"
 #include "match_args.h"
 #include "dev_math.h"
+#include "kb8_dev.h"
 #include <algorithm>
 
 namespace eorb {
@@ -1280,6 +1281,116 @@ int search_tri_dev(eorb_ctx* c, const TriArgs& A)
         search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(B);
     }
     EORB_LAUNCH_CHECK(c, "search_for_triangulation kernels");
+    return EORB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the same walk with pCamera1 = KannalaBrandt8 (:975-1214): epipolarConstrain = TriangulateMatches(...) > KB8_DEF_TH_EPC
+// (KannalaBrandt8.cpp:315-320, :416-486).  Two-camera keyframes (nleft >= 0) pick one of four poses and cameras per
+// (left/right, left/right) pair (:1107-1137) and skip the epipole test; bStereo is false for them (:1051, :1079).  The check
+// has no side effects, so a lane runs it only for a candidate that would beat its own best key: the minimum over passing
+// candidates is the reference's answer.
+
+__global__ __launch_bounds__(256) void search_tri_kb8_kernel(TriKbArgs K)
+{
+    const TriArgs& A = K.T;
+    const int lane = threadIdx.x & 63;
+    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+    const int total = A.off1[A.nn1];
+    const bool twocam = K.nleft1 >= 0;
+    for (int p = gw; p < total; p += nw) {
+        const int id1 = A.idx1[p];
+        const uint8_t e1 = A.elig1[id1];
+        if (!(e1 & 1)) continue;
+        int lo = 0, hi = A.nn1;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.off1[mid] <= p) lo = mid; else hi = mid; }
+        const uint32_t node = A.nodes1[lo];
+        int l2 = 0, h2 = A.nn2;
+        while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (A.nodes2[mid] < node) l2 = mid + 1; else h2 = mid; }
+        if (l2 >= A.nn2 || A.nodes2[l2] != node) continue;
+        const eorb_keypoint kp1 = A.kps1[id1];
+        const int bRight1 = twocam && id1 >= K.nleft1;
+        const bool bStereo1 = !twocam && (e1 & 2);
+        const float sig1 = K.sigma2_1[kp1.octave];
+        uint64_t q0, q1, q2, q3;
+        load_desc32(A.desc1 + (size_t)id1 * A.stride1, q0, q1, q2, q3);
+        uint64_t k0 = ~0ull;
+        for (int i2 = A.off2[l2] + lane; i2 < A.off2[l2 + 1]; i2 += 64) {
+            const int id2 = A.idx2[i2];
+            const uint8_t e2 = A.elig2[id2];
+            if (!(e2 & 1)) continue;
+            uint64_t t0, t1, t2, t3;
+            load_desc32(A.desc2 + (size_t)id2 * A.stride2, t0, t1, t2, t3);
+            const int dist = __popcll(q0 ^ t0) + __popcll(q1 ^ t1) + __popcll(q2 ^ t2) + __popcll(q3 ^ t3);
+            if (dist > TH_LOW) continue;
+            const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)(~(uint32_t)i2);
+            if (key >= k0) continue;                                           // cannot change this lane's answer
+            const eorb_keypoint kp2 = A.kps2[id2];
+            if (kp2.octave < 0 || kp2.octave >= A.nlevels) continue;            // rejected on the host already
+            if (!twocam && !bStereo1 && !(e2 & 2)) {                            // :1097-1105
+                const float distex = A.epx - kp2.x, distey = A.epy - kp2.y;
+                if (distex * distex + distey * distey < 100 * A.scale2[kp2.octave]) continue;
+            }
+            if (!A.bCoarse) {
+                const int bRight2 = twocam && id2 >= K.nleft2;
+                const int pose = twocam ? (bRight1 << 1 | bRight2) : 0;       // ll, lr, rl, rr
+                const WarpCam c1 = warp_cam_of(K.cam1[twocam ? bRight1 : 0]);
+                const WarpCam c2 = warp_cam_of(K.cam2[twocam ? bRight2 : 0]);
+                const float z1 = kb8_triangulate_matches(c1, c2, kp1.x, kp1.y, kp2.x, kp2.y, K.Rt + 12 * pose, K.Rt + 12 * pose + 9,
+                                                         sig1, A.sigma2_2[kp2.octave]);
+                if (!(z1 > 0.0001f)) continue;                                  // KB8_DEF_TH_EPC
+            }
+            k0 = key;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k0, d, 64); k0 = o < k0 ? o : k0; }
+        if (lane == 0 && k0 != ~0ull) {
+            const int bestIdx2 = A.idx2[(int)(~(uint32_t)(k0 & 0xffffffffu))];
+            A.match12[id1] = bestIdx2;
+            atomicAdd(A.nmatches, 1);
+            if (A.checkOri) {
+                const int bin = rot_bin(kp1.angle, A.kps2[bestIdx2].angle);
+                A.bin1[id1] = (int8_t)bin;
+                atomicAdd(&A.histo[bin], 1);
+            }
+        }
+    }
+}
+
+int search_tri_kb8_dev(eorb_ctx* c, const TriKbArgs& K)
+{
+    const TriArgs& A = K.T;
+    ProfScope ps(c, "search_for_triangulation_kb8");
+    bow_init_kernel<<<(std::max(A.n1, 32) + 255) / 256, 256, 0, c->stream>>>(A.match12, A.bin1, A.n1, A.histo, A.nmatches, nullptr, 0);
+    search_tri_kb8_kernel<<<std::min((A.n1 + 3) / 4 + 1, 2048), 256, 0, c->stream>>>(K);
+    if (A.checkOri) {
+        BowArgs B{};
+        B.kf_kf = 1; B.n_kf = A.n1; B.match12 = A.match12; B.bin_f = A.bin1; B.histo = A.histo; B.nmatches = A.nmatches;
+        search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(B);
+    }
+    EORB_LAUNCH_CHECK(c, "search_for_triangulation_kb8 kernels");
+    return EORB_OK;
+}
+
+// KannalaBrandt8::TriangulateMatches over n keypoint pairs (one thread each): z1 or -1
+__global__ void kb8_tri_batch_kernel(WarpCam c1, WarpCam c2, Pose12 P, const eorb_keypoint* __restrict__ kps1,
+                                     const eorb_keypoint* __restrict__ kps2, int n, const float* __restrict__ sig1,
+                                     const float* __restrict__ sig2, float* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const eorb_keypoint a = kps1[i], b = kps2[i];
+    out[i] = kb8_triangulate_matches(c1, c2, a.x, a.y, b.x, b.y, P.v, P.v + 9, sig1[a.octave], sig2[b.octave]);
+}
+
+int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const eorb_keypoint* kps1,
+                      const eorb_keypoint* kps2, int n, const float* sig1, const float* sig2, float* out)
+{
+    ProfScope ps(c, "kb8_triangulate_matches");
+    Pose12 P;
+    for (int i = 0; i < 12; i++) P.v[i] = Rt[i];
+    kb8_tri_batch_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(warp_cam_of(*cam1), warp_cam_of(*cam2), P, kps1, kps2, n, sig1, sig2, out);
+    EORB_LAUNCH_CHECK(c, "kb8_tri_batch_kernel");
     return EORB_OK;
 }
 

@@ -17,6 +17,17 @@ struct TriArgs {
     int32_t* match12; int8_t* bin1; int32_t* histo; int32_t* nmatches;
 };
 
+// SearchForTriangulation with KannalaBrandt8::epipolarConstrain (match.hip search_tri_kb8_kernel); T.F is unused
+struct Pose12 { float v[12]; };              // R row-major, t
+
+struct TriKbArgs {
+    TriArgs T;
+    int nleft1, nleft2;                             // numAllKPtsLeft(): both -1 (monocular) or both >= 0 (two cameras)
+    eorb_camera cam1[2], cam2[2];                   // mpCamera, mpCamera2 of pKF1 / pKF2
+    float Rt[48];                                   // ll, lr, rl, rr: R12 row-major then t12 (monocular: Rt[0..11])
+    const float* sigma2_1;
+};
+
 struct RadArgs {
     const eorb_keypoint* kps; int n; const uint8_t* desc; int stride; GridB g;
     const uint16_t* cell;                           // n: ix*48+iy or 0xFFFF (Frame::PosInGrid), from kf_cells_kernel

@@ -573,6 +573,69 @@ def SearchForTriangulation(kps1, desc1, elig1, fv1, kps2, desc2, elig2, fv2, ep,
     return nm.value, np.stack([k, m[k]], axis=1).astype(np.int32)
 
 
+def _cams(cams):
+    """one camera or a (mpCamera, mpCamera2) pair -> eorb_camera[2] (see _lib.camera for the tuple forms)"""
+    if len(cams) and np.ndim(cams[0]) == 0:
+        cams = (cams, cams)
+    pair = (_lib.Camera * 2)()
+    for k in range(2):
+        pair[k] = _lib.camera(cams[min(k, len(cams) - 1)])
+    return pair
+
+
+def SearchForTriangulationKB8(kps1, nleft1, desc1, elig1, fv1, kps2, nleft2, desc2, elig2, fv2, cams1, cams2, Rt, ep, scale2,
+                              sigma2_1, sigma2_2, bCoarse=False, checkOri=True, ctx=None):
+    """ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:975-1214) with a KannalaBrandt8 pCamera1, monocular (nleft1 = nleft2 =
+    -1, Rt = (R12, t12)) or two-camera keyframes (nleft = numAllKPtsLeft(), kps = left then right, Rt = 4 poses ll, lr, rl, rr).
+    cams = a camera tuple (monocular) or (mpCamera, mpCamera2); Rt = (k, 12) or (k, 3, 4) float rows [R | t].
+    Returns (nmatches, vMatchedPairs as (k,2) int32)."""
+    c = ctx or default_context()
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
+    desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
+    e1 = np.ascontiguousarray(elig1, np.uint8); e2 = np.ascontiguousarray(elig2, np.uint8)
+    n1, o1, i1 = [np.ascontiguousarray(a, t) for a, t in zip(fv1, (np.uint32, np.int32, np.int32))]
+    n2, o2, i2 = [np.ascontiguousarray(a, t) for a, t in zip(fv2, (np.uint32, np.int32, np.int32))]
+    rt = np.zeros(48, np.float32)
+    r = np.asarray(Rt, np.float32).reshape(-1)
+    rt[:len(r)] = r
+    ep = np.ascontiguousarray(ep, np.float32)
+    sc = np.ascontiguousarray(scale2, np.float32)
+    s1 = np.ascontiguousarray(sigma2_1, np.float32); s2 = np.ascontiguousarray(sigma2_2, np.float32)
+    m = np.full(len(kps1), -1, np.int32); nm = C.c_int(0)
+    c1, c2 = _cams(cams1), _cams(cams2)
+    c.check(c.L.eorb_search_for_triangulation_kb8(c.h, _p(kps1), len(kps1), int(nleft1), _p(desc1), desc1.shape[1], _p(e1), _p(n1), _p(o1),
+                                                  _p(i1), len(n1), _p(kps2), len(kps2), int(nleft2), _p(desc2), desc2.shape[1], _p(e2),
+                                                  _p(n2), _p(o2), _p(i2), len(n2), C.byref(c1), C.byref(c2), _p(rt), _p(ep), _p(sc),
+                                                  _p(s1), _p(s2), len(s2), int(bCoarse), int(checkOri), _p(m), C.byref(nm)))
+    k = np.nonzero(m >= 0)[0]
+    return nm.value, np.stack([k, m[k]], axis=1).astype(np.int32)
+
+
+def KB8TriangulateMatches(cam1, cam2, Rt, kps1, kps2, sigma2_1, sigma2_2, ctx=None):
+    """KannalaBrandt8::TriangulateMatches (src/CameraModels/KannalaBrandt8.cpp:416-486) for each pair (kps1[i], kps2[i]); Rt = R12 | t12
+    (12 floats).  Returns z1 per pair (float32), -1 where the reference returns -1."""
+    c = ctx or default_context()
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
+    assert len(kps1) == len(kps2)
+    rt = np.ascontiguousarray(np.asarray(Rt, np.float32).reshape(12))
+    s1 = np.ascontiguousarray(sigma2_1, np.float32); s2 = np.ascontiguousarray(sigma2_2, np.float32)
+    z = np.empty(len(kps1), np.float32)
+    c1, c2 = _lib.camera(cam1), _lib.camera(cam2)
+    c.check(c.L.eorb_kb8_triangulate_matches(c.h, C.byref(c1), C.byref(c2), _p(rt), _p(kps1), _p(kps2), len(kps1), _p(s1), _p(s2),
+                                             len(s1), _p(z)))
+    return z
+
+
+def FuseRightMatch(kps, nleft, desc, gb, valid, uv, radius, level, q_desc, inv_sigma2, ctx=None):
+    """Search core of Fuse(pKF, vpMapPoints, th, bRight=true) (src/ORBmatcher.cc:1512-1578) on a two-camera KeyFrame: the radius match
+    over the right block (right keypoints, grid and descriptors), every right keypoint gated as monocular (the reference reads
+    mvuRight with the right-camera index, :1541).  kps / desc hold the nleft left rows then the right ones; gb = the right grid's
+    bounds.  Returns (best_idx as keyframe indices, i.e. right index + nleft, or -1; best_dist)."""
+    bi, bd = KeyFrameRadiusMatch(np.ascontiguousarray(kps[nleft:]), np.ascontiguousarray(desc[nleft:]), gb, valid, uv, radius, level,
+                                 q_desc, inv_sigma2=inv_sigma2, ctx=ctx)
+    return np.where(bi >= 0, bi + nleft, -1).astype(np.int32), bd
+
+
 def KeyFrameRadiusMatch(kps, desc, gb, valid, uv, radius, level, q_desc, inv_sigma2=None, taken=None, accept_thr=0.0, ctx=None,
                         uright=None, q_ur=None):
     """Search core of Fuse / SearchBySim3 / SearchByProjection(KeyFrame*, Scw, ...) (src/ORBmatcher.cc:1512-1578, :1829-1860,

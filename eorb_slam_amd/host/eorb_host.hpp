@@ -528,6 +528,36 @@ public:
         for (size_t i = 0; i < m12.size(); i++) if (m12[i] >= 0) vMatchedPairs.emplace_back(i, (size_t)m12[i]);     // :1203-1211
         return nm;
     }
+    // SearchForTriangulation (:975-1214) with a KannalaBrandt8 pCamera1: nLeft = numAllKPtsLeft() of each keyframe (-1: monocular,
+    // Rt[0..11] = R12 | t12; >= 0: two cameras, Rt = ll, lr, rl, rr), cams = {mpCamera, mpCamera2} (see include/eorb_fe.h)
+    int SearchForTriangulation(const FrameView& KF1, int nLeft1, const std::vector<uint8_t>& elig1, const FeatureVector& FV1,
+                               const FrameView& KF2, int nLeft2, const std::vector<uint8_t>& elig2, const FeatureVector& FV2,
+                               const eorb_camera cams1[2], const eorb_camera cams2[2], const float Rt[48], const float ep[2],
+                               const std::vector<float>& scale2, const std::vector<float>& sigma2_1, const std::vector<float>& sigma2_2,
+                               std::vector<std::pair<size_t, size_t>>& vMatchedPairs, bool bCoarse = false) {
+        auto& c = eorb_host::thread_context();
+        std::vector<int> m12(KF1.numAllKPts(), -1); int nm = 0;
+        c.check(eorb_search_for_triangulation_kb8(c.get(), KF1.kps->data(), KF1.numAllKPts(), nLeft1, KF1.desc->ptr(), KF1.desc->cols,
+                                                  elig1.data(), FV1.nodes.data(), FV1.off.data(), FV1.idx.data(), (int)FV1.nodes.size(),
+                                                  KF2.kps->data(), KF2.numAllKPts(), nLeft2, KF2.desc->ptr(), KF2.desc->cols, elig2.data(),
+                                                  FV2.nodes.data(), FV2.off.data(), FV2.idx.data(), (int)FV2.nodes.size(), cams1, cams2,
+                                                  Rt, ep, scale2.data(), sigma2_1.data(), sigma2_2.data(), (int)sigma2_2.size(), bCoarse,
+                                                  mbCheckOrientation, m12.data(), &nm));
+        vMatchedPairs.clear();
+        for (size_t i = 0; i < m12.size(); i++) if (m12[i] >= 0) vMatchedPairs.emplace_back(i, (size_t)m12[i]);     // :1203-1211
+        return nm;
+    }
+    // Fuse(pKF, vpMapPoints, th, bRight = true) (:1407-1578) on a two-camera KeyFrame: the search core over the right block.
+    // KFRight = the right keypoints and descriptors (desc + Nleft * stride) with the right grid's bounds; uv / radius / level from
+    // the map points projected by mpCamera2 (:1463-1513).  The returned indices are right-camera indices plus nLeft (:1567).
+    // The reference reads mvuRight[idx] with the right-camera index (:1541): -1 below Nleft (Frame.cc:1221) and past the vector
+    // otherwise; this treats every right keypoint as monocular (the 5.99 gate).
+    void FuseRightMatch(const FrameView& KFRight, int nLeft, const std::vector<uint8_t>& valid, const std::vector<float>& uv,
+                        const std::vector<float>& radius, const std::vector<int>& level, const eorb_host::Mat8& mpDesc,
+                        const std::vector<float>& invSigma2, std::vector<int>& bestIdx, std::vector<int>& bestDist) {
+        KeyFrameRadiusMatch(KFRight, valid, uv, radius, level, mpDesc, &invSigma2, nullptr, 0.f, bestIdx, bestDist);
+        for (int& i : bestIdx) if (i >= 0) i += nLeft;
+    }
     // search core of Fuse / SearchBySim3 / SearchByProjection(KF, Scw): see eorb_kf_radius_match
     void KeyFrameRadiusMatch(const FrameView& KF, const std::vector<uint8_t>& valid, const std::vector<float>& uv,
                              const std::vector<float>& radius, const std::vector<int>& level, const eorb_host::Mat8& mpDesc,

@@ -398,6 +398,36 @@ int eorb_search_for_triangulation(eorb_ctx* ctx,
         const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
         int bCoarse, int checkOri, int32_t* match12, int* nmatches);
 
+/* the same matcher when pCamera1 is KannalaBrandt8 (fisheye: MVSEC, TUM-VI): epipolarConstrain = TriangulateMatches(...) >
+ * KB8_DEF_TH_EPC (src/CameraModels/KannalaBrandt8.cpp:315-320, :416-486), and the two-camera branch (:1007-1017, :1058-1135).
+ * nleft1 / nleft2 = numAllKPtsLeft():
+ *   both -1: monocular keyframes; kps = getUndistKPtMono; Rt[0..11] = R12 (row-major) then t12 (:1001-1002); the epipole test
+ *            ep / scale2 (:1097-1104) applies, with elig bit 1 (bStereo) as in eorb_search_for_triangulation;
+ *   both >= 0: two-camera keyframes; kps = the nleft distorted left keypoints then the right ones; Rt[48] = ll, lr, rl, rr
+ *            (:1005-1013), each R row-major then t; the pose and cameras follow (idx1 >= nleft1, idx2 >= nleft2); no epipole
+ *            test and bStereo false (elig bit 1 ignored); ep / scale2 are still read;
+ *   one -1 and the other not: EORB_E_CONFIG (the reference's R12 is an empty cv::Mat there).
+ * cam1[2] / cam2[2] = mpCamera, mpCamera2 of pKF1 / pKF2 (only [0] read for monocular pairs).  pCamera1 (cam1[0], and cam1[1] for
+ * two cameras) must be model 1, else EORB_E_CONFIG: a Pinhole pCamera1 is eorb_search_for_triangulation.  pCamera2 may be
+ * either model.  sigma2_1 / sigma2_2 = getORBLevelSigma2 of pKF1 / pKF2 (both keyframes share nlevels); eligible keypoints of
+ * both keyframes need an octave in [0, nlevels).  Outputs as eorb_search_for_triangulation: ties go to the last passing
+ * candidate, the rotation histogram keeps its three maxima.  One upload, one wait, one download. */
+int eorb_search_for_triangulation_kb8(eorb_ctx* ctx,
+        const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_keypoint* kps2, int n2, int nleft2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
+        const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
+        const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int* nmatches);
+
+/* KannalaBrandt8::TriangulateMatches (src/CameraModels/KannalaBrandt8.cpp:416-486) over n pairs (kps1[i], kps2[i]):
+ * z1[i] = the triangulated depth in camera 1, or -1.  cam1 must be model 1 (EORB_E_CONFIG otherwise), cam2 either model;
+ * Rt[12] = R12 row-major then t12; the sigmas are read at each keypoint's octave. */
+int eorb_kb8_triangulate_matches(eorb_ctx* ctx, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt,
+        const eorb_keypoint* kps1, const eorb_keypoint* kps2, int n, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        float* z1);
+
 /* replaces the search core shared by ORBmatcher::Fuse (src/ORBmatcher.cc:1512-1578 and :1700-1720), SearchBySim3
  * (:1829-1860, :1909-1940) and SearchByProjection(KeyFrame*, Scw, ...) (:548-588, :667-706): for every projected map point
  * m (valid[m], uv, radius = th*getORBScaleFactor(level), predicted level, descriptor) the best keypoint among
