@@ -1,6 +1,6 @@
 // kb8_dev.h -- device GeometricCamera math shared by the motion-compensated warps (ev_accum.hip) and the KannalaBrandt8
 // SearchForTriangulation (match.hip).  Same fixed IEEE operation order as dev_math.h (-ffp-contract=off); the CPU
-// restatement is tests/kb8tri/orc_kb8tri.c (cameras also oracle/orc_events.c).  DESIGN.md §2 lists each OpenCV choice.
+// restatement is oracle/orc_kb8tri.c (cameras: oracle/orc_events.c).  DESIGN.md §2 lists each OpenCV choice.
 #pragma once
 #include "dev_math.h"
 #include "../../include/eorb_fe.h"

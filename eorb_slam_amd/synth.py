@@ -3,8 +3,8 @@
 Real EvETHZ / MVSEC recordings are not available offline; these generators reproduce their SHAPES:
 240x180 DAVIS event slices (integer raw pixels, optionally LUT-undistorted with the EvETHZ
 intrinsics of Examples/Event/EvETHZ.yaml:62-70, as the reference's loader does at
-src/Event/EventLoader.cpp:111-125 / src/Utils/MyCalibrator.cpp:164-179), textured grey frames and
-256-bit descriptor sets.  Pure numpy, deterministic per seed.
+src/Event/EventLoader.cpp:111-125 / src/Utils/MyCalibrator.cpp:164-179), textured grey frames, 256-bit descriptor sets,
+two-camera (fisheye) frame inputs and KannalaBrandt8 keyframe pairs.  Pure numpy, deterministic per seed.
 """
 import numpy as np
 
@@ -234,3 +234,175 @@ def stereo_pair(seed, W=346, H=260, dmax=14):
     right = (1 - fr) * left[rows, x0] + fr * left[rows, np.minimum(x0 + 1, W + 31)]
     right = np.clip(np.rint(right + rng.normal(0, 1.0, right.shape)), 0, 255).astype(np.uint8)
     return np.ascontiguousarray(left[:, :W]), right
+
+
+def feature_vector_of(node_of, rng):
+    """DBoW2::FeatureVector as CSR from a node id per feature: (node ids ascending, offsets, feature indices; inside a node the
+    insertion order shuffled)"""
+    ids = np.unique(node_of)
+    off = [0]; idx = []
+    for nid in ids:
+        m = np.nonzero(node_of == nid)[0]; rng.shuffle(m); idx.extend(m.tolist()); off.append(len(idx))
+    return ids.astype(np.uint32), np.array(off, np.int32), np.array(idx, np.int32)
+
+
+def flip_bits(d, nbits, rng):
+    """a copy of descriptor d with nbits of its first 256 bits flipped"""
+    d = d.copy()
+    for b in rng.choice(256, nbits, replace=False):
+        d[b >> 3] ^= np.uint8(1 << (b & 7))
+    return d
+
+
+# ---- two-camera (fisheye stereo) frames: TUM-VI sized ----
+def image_pair(W=512, H=512, seed=5, shift=(2, -7)):
+    """a textured image and the same scene shifted: a stand-in for a fisheye stereo pair (TUM-VI 512 x 512)"""
+    img = texture_image(W, H, seed=seed)
+    return img, np.roll(img, shift, axis=(0, 1))
+
+
+def map_inputs(kps, nL, scale_factors, rng, M=None, src=None):
+    """map points near a two-camera frame's keypoints: (left, right, mp_desc, mp_obs), left / right = (in_view, proj_xy, level,
+    view_cos, level_scale) per map point; src = (kps, desc) the map points are drawn from"""
+    sk, sd = src
+    M = len(sk) if M is None else M
+    pick = rng.integers(0, len(sk), M)
+    k = sk[pick]
+    nl = len(scale_factors)
+    cams = []
+    for cam in range(2):
+        iv = (rng.uniform(size=M) < (0.9 if cam == 0 else 0.7)).astype(np.uint8)
+        pxy = np.stack([k["x"] + rng.normal(0, 1.0, M), k["y"] + rng.normal(0, 1.0, M)], axis=1).astype(np.float32)
+        if cam:
+            pxy[:, 0] += rng.normal(-6.0, 1.0, M)
+        lv = np.clip(k["octave"] + rng.integers(-1, 2, M), 0, nl - 1).astype(np.int32)
+        if cam:
+            lv[rng.uniform(size=M) < 0.1] = -1
+        vc = rng.uniform(0.99, 1.0, M).astype(np.float32)
+        ls = np.asarray(scale_factors, np.float32)[np.clip(lv, 0, nl - 1)]
+        cams.append((iv, pxy, lv, vc, ls))
+    mp_obs = (rng.uniform(size=M) < 0.6).astype(np.uint8)
+    return cams[0], cams[1], sd[pick].copy(), mp_obs
+
+
+# ---- keyframe pairs for SearchForTriangulation with KannalaBrandt8 cameras ----
+# KB8 parameters chosen for the tests (a 346 x 260 event camera and a 512 x 512 fisheye pair), not taken from any configuration
+CAM_MONO = (226.0, 226.5, 172.0, 131.0, -0.02, 0.004, -0.001, 0.0002)
+CAM_L = (190.5, 190.2, 254.9, 256.8, 0.0034, 0.0007, -0.0021, 0.0003)
+CAM_R = (190.1, 189.9, 256.2, 255.1, 0.0030, 0.0011, -0.0018, 0.0002)
+NLEV, SCALE = 8, 1.2
+
+
+def level_tables(nlev=NLEV, sf=SCALE):
+    """mvScaleFactor and mvLevelSigma2 in float"""
+    s = [np.float32(1.0)]
+    for _ in range(1, nlev):
+        s.append(np.float32(s[-1] * np.float32(sf)))
+    s = np.array(s, np.float32)
+    return s, (s * s).astype(np.float32)
+
+
+def rot(ax, ay, az):
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]); Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return (Rz @ Ry @ Rx).astype(np.float32)
+
+
+def rel_pose(Ra, ta, Rb, tb):
+    """R12, t12 of camera a (1) w.r.t. camera b (2): R1w R2w^T, -R1w R2w^T t2w + t1w (float rows, computed in float64 then rounded)"""
+    R = (Ra.astype(np.float64) @ Rb.T.astype(np.float64)).astype(np.float32)
+    t = (-(R.astype(np.float64) @ tb.astype(np.float64)) + ta).astype(np.float32)
+    return np.concatenate([R.reshape(9), t]).astype(np.float32)
+
+
+def project_np(c, P):
+    """KB8 / Pinhole projection in float64 (test-data generation only; the oracle's float path decides every outcome)"""
+    P = np.asarray(P, np.float64)
+    if len(c) == 4:
+        return np.stack([c[0] * P[:, 0] / P[:, 2] + c[2], c[1] * P[:, 1] / P[:, 2] + c[3]], axis=1)
+    th = np.arctan2(np.hypot(P[:, 0], P[:, 1]), P[:, 2]); psi = np.arctan2(P[:, 1], P[:, 0])
+    r = th + c[4] * th ** 3 + c[5] * th ** 5 + c[6] * th ** 7 + c[7] * th ** 9
+    return np.stack([c[0] * r * np.cos(psi) + c[2], c[1] * r * np.sin(psi) + c[3]], axis=1)
+
+
+def keyframe_pair(seed=0, twocam=False, npts=600, ndistract=150, nties=30, stride=32, nnodes=60, size=None, ep_near=True):
+    """A keyframe pair seeing one 3D scene.  Returns a dict of the matcher's inputs (kps / nleft / desc / elig / fv per keyframe,
+    cams, Rt, ep, scale2, sigma2).  True observations carry near-duplicate descriptors (<= 10 flipped bits); distractors copy a
+    point's descriptor with 12-30 flipped bits at a random position (pass Hamming, fail geometry); ties copy an observation of
+    pKF2 with its exact descriptor 0.2-1.5 px away.  stride 61: Mixed rows, ~15 % of them non-ORB (elig 0: the type gate)."""
+    rng = np.random.default_rng(seed)
+    scale, sigma2 = level_tables()
+    if twocam:
+        W = H = 512 if size is None else size
+        cams = (CAM_L, CAM_R)
+        Rrl, trl = rot(0.002, -0.01, 0.003), np.array([-0.11, 0.001, 0.002], np.float32)   # right camera w.r.t. left
+    else:
+        W, H = (346, 260) if size is None else size
+        cams = (CAM_MONO,)
+        Rrl, trl = None, None
+    R1, t1 = np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
+    R2 = rot(0.03, -0.08, 0.02); t2 = np.array([-0.35, 0.04, 0.06], np.float32)
+    poses = {(0, 0): (R1, t1), (1, 0): (R2, t2)}
+    if twocam:
+        poses[(0, 1)] = ((Rrl.astype(np.float64) @ R1).astype(np.float32), (Rrl.astype(np.float64) @ t1 + trl).astype(np.float32))
+        poses[(1, 1)] = ((Rrl.astype(np.float64) @ R2).astype(np.float32), (Rrl.astype(np.float64) @ t2 + trl).astype(np.float32))
+    z = rng.uniform(1.5, 9.0, npts)
+    X = np.stack([rng.uniform(-1.1, 1.1, npts) * z, rng.uniform(-0.9, 0.9, npts) * z, z], axis=1)
+    base = rng.integers(0, 256, (npts, 32), dtype=np.uint8)
+    node = rng.integers(0, nnodes, npts) * 7 + 3
+    ang = rng.uniform(0, 360, npts)
+    ncam = 2 if twocam else 1
+    kf = []
+    for k in range(2):
+        blocks = []
+        for cidx in range(ncam):
+            R, t = poses[(k, cidx)]
+            Pc = X @ R.T.astype(np.float64) + t
+            uv = project_np(cams[cidx], Pc)
+            vis = (Pc[:, 2] > 0.2) & (uv[:, 0] >= 0) & (uv[:, 0] < W) & (uv[:, 1] >= 0) & (uv[:, 1] < H)
+            vis &= rng.uniform(size=npts) < 0.9
+            pid = np.nonzero(vis)[0]
+            rows = []
+            for p in pid:
+                rows.append((uv[p, 0] + rng.normal(0, 0.4), uv[p, 1] + rng.normal(0, 0.4), p, flip_bits(base[p], rng.integers(0, 11), rng)))
+            for _ in range(ndistract // ncam):
+                p = rng.integers(npts)
+                rows.append((rng.uniform(0, W), rng.uniform(0, H), p, flip_bits(base[p], rng.integers(12, 31), rng)))
+            if k == 1:
+                for j in rng.choice(len(pid), min(nties // ncam, len(pid)), replace=False):
+                    x, y, p, d = rows[j]
+                    rows.append((x + rng.uniform(-1.5, 1.5), y + rng.uniform(-1.5, 1.5), p, d.copy()))
+            order = rng.permutation(len(rows))
+            blocks.append([rows[i] for i in order])
+        allrows = [r for b in blocks for r in b]
+        n = len(allrows)
+        kps = np.zeros(n, KP_DTYPE)
+        kps["x"] = np.array([r[0] for r in allrows], np.float32); kps["y"] = np.array([r[1] for r in allrows], np.float32)
+        kps["octave"] = rng.integers(0, 4, n); kps["size"] = 31.0; kps["class_id"] = -1
+        pids = np.array([r[2] for r in allrows])
+        a = ang[pids] + (rng.normal(0, 4, n) if k else 0) + np.where(rng.uniform(size=n) < 0.1, rng.uniform(0, 360, n), 0)
+        kps["angle"] = np.mod(a, 360).astype(np.float32)
+        desc = np.zeros((n, stride), np.uint8)
+        desc[:, :32] = np.stack([r[3] for r in allrows])
+        if stride > 32:
+            desc[:, 32:] = rng.integers(0, 256, (n, stride - 32), dtype=np.uint8)
+        elig = (rng.uniform(size=n) < 0.85).astype(np.uint8)
+        if stride > 32:
+            elig[rng.uniform(size=n) < 0.15] = 0                         # non-ORB rows of a Mixed keyframe
+        if not twocam:
+            elig |= ((rng.uniform(size=n) < 0.1) << 1).astype(np.uint8) & (elig << 1)
+        nodes = node[pids].copy()
+        nodes[rng.uniform(size=n) < 0.05] = 1                              # a node the other keyframe may lack
+        fv = feature_vector_of(nodes, rng)
+        kf.append(dict(kps=kps, nleft=len(blocks[0]) if twocam else -1, desc=desc, elig=elig, fv=fv))
+    if twocam:
+        Rt = np.concatenate([rel_pose(*poses[(0, a)], *poses[(1, b)]) for a, b in ((0, 0), (0, 1), (1, 0), (1, 1))])
+    else:
+        Rt = rel_pose(R1, t1, R2, t2)
+    k2 = kf[1]["kps"]
+    ep = (k2["x"][0] + 4.0, k2["y"][0]) if ep_near else (-1000.0, -1000.0)
+    camsp = cams if twocam else cams[0]
+    return dict(kps1=kf[0]["kps"], nleft1=kf[0]["nleft"], desc1=kf[0]["desc"], elig1=kf[0]["elig"], fv1=kf[0]["fv"],
+                kps2=kf[1]["kps"], nleft2=kf[1]["nleft"], desc2=kf[1]["desc"], elig2=kf[1]["elig"], fv2=kf[1]["fv"],
+                cams1=camsp, cams2=camsp, Rt=Rt, ep=np.array(ep, np.float32), scale2=scale, sigma2_1=sigma2, sigma2_2=sigma2)

@@ -116,6 +116,10 @@ long orc_parse_events_text(const char* text, size_t nbytes, orc_raw_event* out, 
 typedef struct { float fx, fy, cx, cy; } orc_pinhole;          /* Pinhole::mvParameters (float), CameraModels/Pinhole.cpp */
 /* GeometricCamera: model 0 = Pinhole, 1 = KannalaBrandt8 (mvParameters[4..7] = k1..k4, precision = KB8_DEF_PRECISION 1e-6) */
 typedef struct { int model; float fx, fy, cx, cy; float k[4]; float precision; } orc_camera;
+/* GeometricCamera::unproject -> r = (X, Y, 1) (Pinhole.cpp:59-62; KannalaBrandt8.cpp:157-190, Newton on theta in float) and
+ * project(cv::Point3f) in float (Pinhole.cpp:30-39; KannalaBrandt8.cpp:86-109): the warps below and TriangulateMatches */
+void orc_camera_unproject(const orc_camera* cam, float x, float y, float r[3]);
+void orc_camera_project(const orc_camera* cam, const float p[3], float* u, float* v);
 void orc_mci_warp_se3_cam(const orc_event* ev, size_t n, const orc_camera* cam, double angle, const double axis[3],
                           const double tt[3], float medDepth, const float* depth_per_event, float* uv_out);
 void orc_mci_warp_se2_cam(const orc_event* ev, size_t n, const orc_camera* cam, const float* params2D, int nparams, float* uv_out);
@@ -296,6 +300,17 @@ int orc_search_for_triangulation(const orc_keypoint* kps1, int n1, const uint8_t
                                  const uint32_t* nodes2, const int32_t* off2, const int32_t* idx2, int nn2,
                                  const float ep[2], const float F12[9], const float* scale2, const float* sigma2_2,
                                  int bCoarse, int checkOri, int32_t* match12);
+/* the same walk with pCamera1 a KannalaBrandt8 (KannalaBrandt8::epipolarConstrain, below).  nleft = numAllKPtsLeft(): -1
+ * monocular (kps = mvKeysUn); >= 0 the nleft distorted left keypoints then the right ones, on both keyframes or neither.
+ * cam1 / cam2 = pKFi->mpCamera, mpCamera2; Rt[4][12] = (R row-major, t) of ll, lr, rl, rr (:1005-1013), a monocular pair reads
+ * Rt[0] = R12, t12 (:1001-1002).  elig bit 1 (bStereo) and ep are read for monocular pairs only (:1051, :1079, :1097). */
+int orc_search_for_triangulation_kb8(const orc_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+                                     const uint32_t* nodes1, const int32_t* off1, const int32_t* idx1, int nn1,
+                                     const orc_keypoint* kps2, int n2, int nleft2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+                                     const uint32_t* nodes2, const int32_t* off2, const int32_t* idx2, int nn2,
+                                     const orc_camera cam1[2], const orc_camera cam2[2], const float Rt[48], const float ep[2],
+                                     const float* scale2, const float* sigma2_1, const float* sigma2_2, int bCoarse, int checkOri,
+                                     int32_t* match12);
 
 /* the search core shared by ORBmatcher::Fuse (:1512-1578, :1619-1741), SearchBySim3 (:1829-1860, :1909-1940) and
  * SearchByProjection(KeyFrame*, Scw, ...) (:548-588): for query m (a projected map point: uv, radius = th*scaleFactor(level),
@@ -364,6 +379,48 @@ void orc_bf_knn2(const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* id
  * images are read); uRight / depth [N] out (-1: no match); returns the number of correlated matches before the median cut. */
 int orc_compute_stereo_matches(const orc_orb* eL, const orc_orb* eR, const orc_keypoint* kL, int N, const uint8_t* dL,
                                const orc_keypoint* kR, int Nr, const uint8_t* dR, float mb, float mbf, float* uRight, float* depth);
+
+/* ---- KannalaBrandt8 triangulation: src/CameraModels/KannalaBrandt8.cpp (orc_kb8tri.c) ------------------------------------- */
+/* cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on a 4x4 float matrix (JacobiSVDImpl_<float>): A and Vt row-major, W descending */
+void orc_svd4(const float A[16], double W[4], float Vt[16]);
+/* KannalaBrandt8::TriangulateMatches (:416-486): z1 of the triangulated point, or -1; p3D (may be NULL) = the point */
+float orc_kb8_triangulate_matches(const orc_camera* cam1, const orc_camera* cam2, const orc_keypoint* kp1, const orc_keypoint* kp2,
+                                  const float R12[9], const float t12[3], float sigmaLevel, float unc, float* p3D);
+/* KannalaBrandt8::epipolarConstrain (:315-320): TriangulateMatches > KB8_DEF_TH_EPC */
+int orc_kb8_epipolar_constrain(const orc_camera* cam1, const orc_camera* cam2, const orc_keypoint* kp1, const orc_keypoint* kp2,
+                               const float R12[9], const float t12[3], float sigmaLevel, float unc);
+/* out[i] = TriangulateMatches of (kps1[i], kps2[i]) with Rt = (R12, t12) and the sigma tables indexed by octave */
+void orc_kb8_triangulate_batch(const orc_camera* cam1, const orc_camera* cam2, const float Rt[12], const orc_keypoint* kps1,
+                               const orc_keypoint* kps2, int n, const float* sigma2_1, const float* sigma2_2, float* out);
+
+/* ---- two-camera (fisheye stereo) frames: src/Frame.cc:1101-1250 and ORBmatcher.cc's numKPtsLeft() != -1 branches (orc_twocam.c) */
+/* A frame's keypoints are its nL left ones, then its nR right ones; slots (frame_mp / cur_mp) as in orc_search_by_projection_last. */
+/* Frame::ComputeStereoFishEyeMatches (Frame.cc:1210-1250) up to TriangulateMatches: cand[nL] = trainIdx + monoRight of a left
+ * keypoint passing Lowe's test (-1 otherwise), dist2[2 nL] = its two knn distances (-1 none).  Returns the number of candidates. */
+int orc_fisheye_matches(const uint8_t* descL, int nL, int monoLeft, const uint8_t* descR, int nR, int monoRight, int32_t* cand, int32_t* dist2);
+/* SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cc:44-219): per map point m the left camera's in_view / proj_xy / level /
+ * view_cos / level_scale (= F.getORBScaleFactor(level)) and the right camera's (_r; level_r = mnTrackScaleLevelR, -1 = skip);
+ * l2r / r2l = mvLeftToRightMatch / mvRightToLeftMatch */
+int orc_search_by_projection_map_fisheye(const orc_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
+                                         const orc_grid_bounds* gb, const int32_t* l2r, const int32_t* r2l, int M,
+                                         const uint8_t* in_view, const float* proj_xy, const int32_t* level, const float* view_cos,
+                                         const float* level_scale, const uint8_t* in_view_r, const float* proj_xy_r, const int32_t* level_r,
+                                         const float* view_cos_r, const float* level_scale_r, const uint8_t* mp_desc, const uint8_t* mp_obs,
+                                         int32_t* frame_mp, float th, float nnratio);
+/* SearchByProjection(CurF, LastF, th, bMono) (:1969-2187): per last-frame point i valid / uv (the left projection, bounds and
+ * outliers folded in, :1998-2012), uv_r = mpCamera->project(mTrl x3Dc) (:2093-2095); last_kps in index order (octave =
+ * getKPtLevelMono(i), angle); level_scale = getORBScaleFactor(octave); mode 0 / 1 forward / 2 backward */
+int orc_search_by_projection_last_fisheye(const orc_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
+                                          const orc_grid_bounds* gb, const orc_keypoint* last_kps, int n_last, const uint8_t* valid,
+                                          const float* uv, const float* uv_r, const uint8_t* mp_desc, const uint8_t* mp_obs,
+                                          const float* level_scale, int32_t* cur_mp, float th, int mode, int checkOri);
+/* SearchByBoW(pKF, F, vpMapPointMatches) (:276-478): feature vectors as in orc_search_by_bow; the frame's n_f features are nL left
+ * then right ones; kf_kps in the KeyFrame's index order (:391-393); match_f[n_f] out */
+int orc_search_by_bow_fisheye(const orc_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
+                              const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
+                              const orc_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc,
+                              const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
+                              int32_t* match_f, float nnratio, int checkOri);
 
 #ifdef __cplusplus
 }

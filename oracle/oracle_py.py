@@ -44,6 +44,13 @@ def _camera(cam):
     return c
 
 
+def _camera_pair(cams):
+    """one camera (used for both) or (mpCamera, mpCamera2) -> Camera[2]"""
+    if np.ndim(cams[0]) == 0:
+        cams = (cams, cams)
+    return (Camera * 2)(_camera(cams[0]), _camera(cams[-1]))
+
+
 class GridBounds(C.Structure):
     _fields_ = [("minX", C.c_float), ("minY", C.c_float), ("maxX", C.c_float), ("maxY", C.c_float),
                 ("invW", C.c_float), ("invH", C.c_float)]
@@ -192,12 +199,32 @@ def lib(fast=False):
     L.orc_resolve_num_mixed.restype = None
     L.orc_resolve_num_mixed.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]
     L.orc_bf_knn2.restype = None; L.orc_bf_knn2.argtypes = [vp, ci, vp, ci, vp, vp]
+    pc = C.POINTER(Camera)
+    L.orc_camera_unproject.restype = None; L.orc_camera_unproject.argtypes = [pc, cf, cf, vp]
+    L.orc_camera_project.restype = None; L.orc_camera_project.argtypes = [pc, vp, C.POINTER(cf), C.POINTER(cf)]
+    L.orc_svd4.restype = None; L.orc_svd4.argtypes = [vp, vp, vp]
+    L.orc_kb8_triangulate_matches.restype = cf; L.orc_kb8_triangulate_matches.argtypes = [pc, pc, vp, vp, vp, vp, cf, cf, vp]
+    L.orc_kb8_triangulate_batch.restype = None; L.orc_kb8_triangulate_batch.argtypes = [pc, pc, vp, vp, vp, ci, vp, vp, vp]
+    L.orc_search_for_triangulation_kb8.restype = ci
+    L.orc_search_for_triangulation_kb8.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, vp, ci] * 2 + [vp] * 7 + [ci, ci, vp]
+    L.orc_fisheye_matches.restype = ci; L.orc_fisheye_matches.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp]
+    L.orc_search_by_projection_map_fisheye.restype = ci
+    L.orc_search_by_projection_map_fisheye.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, ci] + [vp] * 13 + [cf, cf]
+    L.orc_search_by_projection_last_fisheye.restype = ci
+    L.orc_search_by_projection_last_fisheye.argtypes = [vp, ci, ci, vp, ci, vp, vp, ci] + [vp] * 7 + [cf, ci, ci]
+    L.orc_search_by_bow_fisheye.restype = ci
+    L.orc_search_by_bow_fisheye.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, ci, vp, cf, ci]
     _libs[key] = L
     return L
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _fv(fv):
+    """a DBoW2 FeatureVector as CSR: (node ids uint32[nn] ascending, node offsets int32[nn+1], feature indices int32[])"""
+    return [np.ascontiguousarray(a, t) for a, t in zip(fv, (np.uint32, np.int32, np.int32))]
 
 
 # ---- events -----------------------------------------------------------------------------------
@@ -461,8 +488,8 @@ def search_by_bow(kf_kps, kf_desc, kf_has_mp, kf_fv, f_kps, f_desc, f_fv, nnrati
     kf_kps = np.ascontiguousarray(kf_kps, KP_DTYPE); f_kps = np.ascontiguousarray(f_kps, KP_DTYPE)
     kf_desc = np.ascontiguousarray(kf_desc, np.uint8); f_desc = np.ascontiguousarray(f_desc, np.uint8)
     hm = np.ascontiguousarray(kf_has_mp, np.uint8)
-    kn, ko, ki = [np.ascontiguousarray(a, t) for a, t in zip(kf_fv, (np.uint32, np.int32, np.int32))]
-    fn, fo, fi = [np.ascontiguousarray(a, t) for a, t in zip(f_fv, (np.uint32, np.int32, np.int32))]
+    kn, ko, ki = _fv(kf_fv)
+    fn, fo, fi = _fv(f_fv)
     m = np.full(len(f_kps), -1, np.int32)
     n = lib().orc_search_by_bow(_p(kf_kps), len(kf_kps), _p(kf_desc), _p(hm), _p(kn), _p(ko), _p(ki), len(kn),
                                 _p(f_kps), len(f_kps), _p(f_desc), _p(fn), _p(fo), _p(fi), len(fn), _p(m), nnratio, int(checkOri))
@@ -520,8 +547,8 @@ def search_by_bow_kf(kps1, desc1, has_mp1, fv1, kps2, desc2, has_mp2, fv2, nnrat
     kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
     desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
     h1 = np.ascontiguousarray(has_mp1, np.uint8); h2 = np.ascontiguousarray(has_mp2, np.uint8)
-    n1, o1, i1 = [np.ascontiguousarray(a, t) for a, t in zip(fv1, (np.uint32, np.int32, np.int32))]
-    n2, o2, i2 = [np.ascontiguousarray(a, t) for a, t in zip(fv2, (np.uint32, np.int32, np.int32))]
+    n1, o1, i1 = _fv(fv1)
+    n2, o2, i2 = _fv(fv2)
     m = np.full(len(kps1), -1, np.int32)
     n = lib().orc_search_by_bow_kf(_p(kps1), len(kps1), _p(desc1), _p(h1), _p(n1), _p(o1), _p(i1), len(n1),
                                    _p(kps2), len(kps2), _p(desc2), _p(h2), _p(n2), _p(o2), _p(i2), len(n2), _p(m), nnratio, int(checkOri))
@@ -539,14 +566,34 @@ def search_for_triangulation(kps1, desc1, elig1, fv1, kps2, desc2, elig2, fv2, e
     kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
     desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
     e1 = np.ascontiguousarray(elig1, np.uint8); e2 = np.ascontiguousarray(elig2, np.uint8)
-    n1, o1, i1 = [np.ascontiguousarray(a, t) for a, t in zip(fv1, (np.uint32, np.int32, np.int32))]
-    n2, o2, i2 = [np.ascontiguousarray(a, t) for a, t in zip(fv2, (np.uint32, np.int32, np.int32))]
+    n1, o1, i1 = _fv(fv1)
+    n2, o2, i2 = _fv(fv2)
     ep = np.ascontiguousarray(ep, np.float32); F = np.ascontiguousarray(F12, np.float32).reshape(9)
     sc = np.ascontiguousarray(scale2, np.float32); sg = np.ascontiguousarray(sigma2_2, np.float32)
     m = np.full(len(kps1), -1, np.int32)
     n = lib().orc_search_for_triangulation(_p(kps1), len(kps1), _p(desc1), desc1.shape[1], _p(e1), _p(n1), _p(o1), _p(i1), len(n1),
                                            _p(kps2), len(kps2), _p(desc2), desc2.shape[1], _p(e2), _p(n2), _p(o2), _p(i2), len(n2),
                                            _p(ep), _p(F), _p(sc), _p(sg), int(coarse), int(checkOri), _p(m))
+    return n, m
+
+
+def search_for_triangulation_kb8(kps1, nleft1, desc1, elig1, fv1, kps2, nleft2, desc2, elig2, fv2, cams1, cams2, Rt, ep, scale2, sigma2_1,
+                                 sigma2_2, coarse=False, checkOri=True, fast=False):
+    """the walk with a KannalaBrandt8 pCamera1.  nleft: -1 monocular, else the left keypoint count of a two-camera keyframe; cams: one
+    camera, or (mpCamera, mpCamera2); Rt: R12 | t12, or the four poses ll, lr, rl, rr."""
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
+    desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
+    e1 = np.ascontiguousarray(elig1, np.uint8); e2 = np.ascontiguousarray(elig2, np.uint8)
+    n1, o1, i1 = _fv(fv1)
+    n2, o2, i2 = _fv(fv2)
+    rt = np.zeros(48, np.float32); r = np.asarray(Rt, np.float32).reshape(-1); rt[:len(r)] = r
+    ep = np.ascontiguousarray(ep, np.float32); sc = np.ascontiguousarray(scale2, np.float32)
+    s1 = np.ascontiguousarray(sigma2_1, np.float32); s2 = np.ascontiguousarray(sigma2_2, np.float32)
+    m = np.full(len(kps1), -1, np.int32)
+    n = lib(fast).orc_search_for_triangulation_kb8(_p(kps1), len(kps1), int(nleft1), _p(desc1), desc1.shape[1], _p(e1), _p(n1), _p(o1), _p(i1),
+                                                   len(n1), _p(kps2), len(kps2), int(nleft2), _p(desc2), desc2.shape[1], _p(e2), _p(n2), _p(o2),
+                                                   _p(i2), len(n2), _camera_pair(cams1), _camera_pair(cams2), _p(rt), _p(ep), _p(sc), _p(s1),
+                                                   _p(s2), int(coarse), int(checkOri), _p(m))
     return n, m
 
 
@@ -648,3 +695,90 @@ def hamming_window_match(q_desc, t_desc, cand_offsets, cand_idx):
     L.orc_hamming_window_match(_p(q), C.c_int(nq), C.c_int(q.shape[1] if nq else 32), _p(t), C.c_int(t.shape[1] if len(t) else 32), _p(co), _p(ci),
                                _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]))
     return tuple(o[:nq] for o in out)
+
+
+# ---- two-camera (fisheye stereo) frames: keypoints and descriptors are the nL left rows, then the right ones ------------------
+def fisheye_matches(descL, monoLeft, descR, monoRight, fast=False):
+    """ComputeStereoFishEyeMatches up to TriangulateMatches: (number of candidates, right index of each left keypoint or -1, the two
+    knn distances or -1)"""
+    dL = np.ascontiguousarray(descL, np.uint8); dR = np.ascontiguousarray(descR, np.uint8)
+    cand = np.zeros(len(dL), np.int32); d2 = np.zeros((len(dL), 2), np.int32)
+    n = lib(fast).orc_fisheye_matches(_p(dL), len(dL), monoLeft, _p(dR), len(dR), monoRight, _p(cand), _p(d2))
+    return n, cand, d2
+
+
+def search_by_projection_map_fisheye(kps, nL, desc, gb, l2r, r2l, left, right, mp_desc, mp_obs, frame_mp, th, nnratio, fast=False):
+    """left / right: per camera (in_view, proj_xy, level, view_cos, level_scale) of every map point"""
+    kps = np.ascontiguousarray(kps, KP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
+    l2r = np.ascontiguousarray(l2r, np.int32); r2l = np.ascontiguousarray(r2l, np.int32)
+    cams = [np.ascontiguousarray(a, t) for c in (left, right) for a, t in zip(c, (np.uint8, np.float32, np.int32, np.float32, np.float32))]
+    mp_desc = np.ascontiguousarray(mp_desc, np.uint8); mp_obs = np.ascontiguousarray(mp_obs, np.uint8)
+    fm = np.ascontiguousarray(frame_mp, np.int32).copy()
+    n = lib(fast).orc_search_by_projection_map_fisheye(_p(kps), nL, len(kps) - nL, _p(desc), 32, C.byref(gb), _p(l2r), _p(r2l), len(mp_obs),
+                                                       *[_p(a) for a in cams], _p(mp_desc), _p(mp_obs), _p(fm), float(th), float(nnratio))
+    return n, fm
+
+
+def search_by_projection_last_fisheye(kps, nL, desc, gb, last_kps, valid, uv, uv_r, mp_desc, mp_obs, cur_mp, th, level_scale, mode, checkOri,
+                                      fast=False):
+    kps = np.ascontiguousarray(kps, KP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8); lk = np.ascontiguousarray(last_kps, KP_DTYPE)
+    valid = np.ascontiguousarray(valid, np.uint8); uv = np.ascontiguousarray(uv, np.float32); uv_r = np.ascontiguousarray(uv_r, np.float32)
+    mp_desc = np.ascontiguousarray(mp_desc, np.uint8); mp_obs = np.ascontiguousarray(mp_obs, np.uint8)
+    ls = np.ascontiguousarray(level_scale, np.float32)
+    cm = np.ascontiguousarray(cur_mp, np.int32).copy()
+    n = lib(fast).orc_search_by_projection_last_fisheye(_p(kps), nL, len(kps) - nL, _p(desc), 32, C.byref(gb), _p(lk), len(lk), _p(valid), _p(uv),
+                                                        _p(uv_r), _p(mp_desc), _p(mp_obs), _p(ls), _p(cm), float(th), int(mode), int(checkOri))
+    return n, cm
+
+
+def search_by_bow_fisheye(kf_kps, kf_desc, kf_has_mp, kf_fv, f_kps, nL, f_desc, f_fv, nnratio, checkOri, fast=False):
+    kf_kps = np.ascontiguousarray(kf_kps, KP_DTYPE); f_kps = np.ascontiguousarray(f_kps, KP_DTYPE)
+    kf_desc = np.ascontiguousarray(kf_desc, np.uint8); f_desc = np.ascontiguousarray(f_desc, np.uint8)
+    hm = np.ascontiguousarray(kf_has_mp, np.uint8)
+    kn, ko, ki = _fv(kf_fv)
+    fn, fo, fi = _fv(f_fv)
+    m = np.full(len(f_kps), -1, np.int32)
+    n = lib(fast).orc_search_by_bow_fisheye(_p(kf_kps), _p(kf_desc), _p(hm), _p(kn), _p(ko), _p(ki), len(kn), _p(f_kps), len(f_kps), int(nL),
+                                            _p(f_desc), _p(fn), _p(fo), _p(fi), len(fn), _p(m), float(nnratio), int(checkOri))
+    return n, m
+
+
+# ---- KannalaBrandt8 cameras and TriangulateMatches; cameras as _camera() takes them ------------------------------------------
+def svd4(A, fast=False):
+    """cv::SVD::compute of a 4x4 float matrix: (W descending, Vt)"""
+    A = np.ascontiguousarray(A, np.float32).reshape(16)
+    W = np.zeros(4, np.float64); Vt = np.zeros(16, np.float32)
+    lib(fast).orc_svd4(_p(A), _p(W), _p(Vt))
+    return W, Vt.reshape(4, 4)
+
+
+def unproject(cam, x, y, fast=False):
+    r = np.zeros(3, np.float32)
+    lib(fast).orc_camera_unproject(C.byref(_camera(cam)), float(x), float(y), _p(r))
+    return r
+
+
+def project(cam, p, fast=False):
+    p = np.ascontiguousarray(p, np.float32); u = C.c_float(); v = C.c_float()
+    lib(fast).orc_camera_project(C.byref(_camera(cam)), _p(p), C.byref(u), C.byref(v))
+    return np.float32(u.value), np.float32(v.value)
+
+
+def triangulate_matches(cam1, cam2, kp1, kp2, R12, t12, sigma1, sigma2, fast=False):
+    """(z1 or -1, the triangulated point)"""
+    k1 = np.ascontiguousarray([kp1], KP_DTYPE); k2 = np.ascontiguousarray([kp2], KP_DTYPE)
+    R = np.ascontiguousarray(R12, np.float32).reshape(9); t = np.ascontiguousarray(t12, np.float32).reshape(3)
+    x = np.zeros(3, np.float32)
+    z = lib(fast).orc_kb8_triangulate_matches(C.byref(_camera(cam1)), C.byref(_camera(cam2)), _p(k1), _p(k2), _p(R), _p(t), float(sigma1),
+                                              float(sigma2), _p(x))
+    return np.float32(z), x
+
+
+def triangulate_batch(cam1, cam2, Rt, kps1, kps2, sigma2_1, sigma2_2, fast=False):
+    """z1 (or -1) of (kps1[i], kps2[i]) for every i; Rt = R12 | t12"""
+    k1 = np.ascontiguousarray(kps1, KP_DTYPE); k2 = np.ascontiguousarray(kps2, KP_DTYPE)
+    rt = np.ascontiguousarray(np.asarray(Rt, np.float32).reshape(12))
+    s1 = np.ascontiguousarray(sigma2_1, np.float32); s2 = np.ascontiguousarray(sigma2_2, np.float32)
+    out = np.zeros(len(k1), np.float32)
+    lib(fast).orc_kb8_triangulate_batch(C.byref(_camera(cam1)), C.byref(_camera(cam2)), _p(rt), _p(k1), _p(k2), len(k1), _p(s1), _p(s2), _p(out))
+    return out

@@ -97,10 +97,13 @@ int orc_ev2im_gauss(const orc_event* ev, size_t n, int W, int H, float sigma, in
 }
 
 /* ---- motion-compensated accumulation: EventConversion.cc:280-531 ------------------------------------------------- */
-/* KannalaBrandt8::unproject (src/CameraModels/KannalaBrandt8.cpp:163-190): Newton iterations on theta in float, std::tan(float) */
-static void kb8_unproject(const orc_camera* c, float x, float y, float* X, float* Y)
+/* GeometricCamera::unproject -> (X, Y, 1): Pinhole.cpp:59-62; KannalaBrandt8.cpp:157-190 (Newton iterations on theta in float,
+ * std::tan(float)) */
+void orc_camera_unproject(const orc_camera* c, float x, float y, float r[3])
 {
     const float pwx = (x - c->cx) / c->fx, pwy = (y - c->cy) / c->fy;
+    r[2] = 1.f;
+    if (c->model == 0) { r[0] = pwx; r[1] = pwy; return; }
     float scale = 1.f;
     float theta_d = sqrtf(pwx * pwx + pwy * pwy);
     theta_d = fminf(fmaxf((float)(-3.1415926535897932384626433832795 / 2.f), theta_d), (float)(3.1415926535897932384626433832795 / 2.f));
@@ -117,15 +120,17 @@ static void kb8_unproject(const orc_camera* c, float x, float y, float* X, float
         }
         scale = orc_tanf(theta) / theta_d;
     }
-    *X = pwx * scale; *Y = pwy * scale;
+    r[0] = pwx * scale; r[1] = pwy * scale;
 }
-/* KannalaBrandt8::project(cv::Point3f) (:87-103); cos / sin of the float angle resolve to the float overloads (<math.h> of
- * libstdc++ is reached through opencv2/opencv.hpp -> flann/lsh_table.h: unpinned, as for the other libm calls) */
-static void kb8_project_f(const orc_camera* c, float X, float Y, float Z, float* u, float* v)
+/* GeometricCamera::project(cv::Point3f), float throughout: Pinhole.cpp:30-39; KannalaBrandt8.cpp:86-109 (cos / sin of the float
+ * angle resolve to the float overloads: <math.h> of libstdc++ is reached through opencv2/opencv.hpp -> flann/lsh_table.h; unpinned,
+ * as for the other libm calls) */
+void orc_camera_project(const orc_camera* c, const float p[3], float* u, float* v)
 {
-    const float x2_plus_y2 = X * X + Y * Y;
-    const float theta = orc_atan2f(sqrtf(x2_plus_y2), Z);
-    const float psi = orc_atan2f(Y, X);
+    if (c->model == 0) { *u = c->fx * p[0] / p[2] + c->cx; *v = c->fy * p[1] / p[2] + c->cy; return; }
+    const float x2_plus_y2 = p[0] * p[0] + p[1] * p[1];
+    const float theta = orc_atan2f(sqrtf(x2_plus_y2), p[2]);
+    const float psi = orc_atan2f(p[1], p[0]);
     const float theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2, theta9 = theta7 * theta2;
     const float r = theta + c->k[0] * theta3 + c->k[1] * theta5 + c->k[2] * theta7 + c->k[3] * theta9;
     *u = c->fx * r * orc_cosf_any(psi) + c->cx;
@@ -160,10 +165,9 @@ void orc_mci_warp_se3_cam(const orc_event* ev, size_t n, const orc_camera* cam, 
     const double invDT = 1.0 / DT;
     for (size_t k = 0; k < n; k++) {
         const double etRate = (t1 - ev[k].ts) * invDT;
-        float X, Y;
-        if (cam->model == 1) kb8_unproject(cam, ev[k].x, ev[k].y, &X, &Y);
-        else { X = (ev[k].x - cam->cx) / cam->fx; Y = (ev[k].y - cam->cy) / cam->fy; }       /* Pinhole::unproject (Pinhole.cpp:59-62) */
-        const double P[3] = { (double)X, (double)Y, (double)1.f };
+        float r[3];
+        orc_camera_unproject(cam, ev[k].x, ev[k].y, r);
+        const double P[3] = { (double)r[0], (double)r[1], (double)r[2] };
         /* Eigen::AngleAxisd(omega.angle()*etRate, omega.axis()).toRotationMatrix() */
         const double a = angle * etRate;
         const double sn = orc_dsin(a), c = orc_dcos(a);
@@ -215,20 +219,14 @@ void orc_mci_warp_se2_cam(const orc_event* ev, size_t n, const orc_camera* cam, 
     const float scDiff = 1.f - sc;
     for (size_t k = 0; k < n; k++) {
         const float tk = (float)(t1 - ev[k].ts);
-        float X, Y;
-        if (cam->model == 1) kb8_unproject(cam, ev[k].x, ev[k].y, &X, &Y);
-        else { X = (ev[k].x - cam->cx) / cam->fx; Y = (ev[k].y - cam->cy) / cam->fy; }
-        const float Z = 1.f;
+        float r[3];
+        orc_camera_unproject(cam, ev[k].x, ev[k].y, r);
+        const float X = r[0], Y = r[1];
         const float theta_k = tk * omega0;
         const float currSc = scDiff * (1 - tk * invDT) + sc;
         const float cs = orc_cosf(theta_k), sn = orc_sinf(theta_k);
-        const float xp = currSc * (X * cs - Y * sn) + vx0 * tk;
-        const float yp = currSc * (X * sn + Y * cs) + vy0 * tk;
-        if (cam->model == 1) kb8_project_f(cam, xp, yp, Z, &uv[2 * k], &uv[2 * k + 1]);
-        else {                                         /* Pinhole::project(cv::Point3f) :30-33 */
-            uv[2 * k] = cam->fx * xp / Z + cam->cx;
-            uv[2 * k + 1] = cam->fy * yp / Z + cam->cy;
-        }
+        const float p[3] = { currSc * (X * cs - Y * sn) + vx0 * tk, currSc * (X * sn + Y * cs) + vy0 * tk, r[2] };
+        orc_camera_project(cam, p, &uv[2 * k], &uv[2 * k + 1]);
     }
 }
 

@@ -4,17 +4,10 @@
  * (src/Frame.cc:431-460, 710-793) of the reference.  Everything here is reference-owned
  * arithmetic (no OpenCV numerics) except cv::BFMatcher::knnMatch semantics (orc_bf_knn2).
  */
-#include "eorb_oracle.h"
+#include "orc_matcher.h"
 #include <limits.h>
-#include <math.h>
 #include <stdlib.h>
 #include <string.h>
-
-#define FRAME_GRID_ROWS 48      /* include/Frame.h:45 */
-#define FRAME_GRID_COLS 64      /* include/Frame.h:46 */
-#define TH_HIGH 100             /* ORBmatcher.cc:36 */
-#define TH_LOW 50               /* :37 */
-#define HISTO_LENGTH 30         /* :38 */
 
 /* ORBmatcher::DescriptorDistance :2360-2378 (reads 8 x int32 whatever the descriptor width) */
 int orc_descriptor_distance(const uint8_t* a, const uint8_t* b)
@@ -46,27 +39,11 @@ void orc_three_maxima(const int* sizes, int L, int* ind1, int* ind2, int* ind3)
 }
 
 /* ---- Frame grid ------------------------------------------------------------------------------- */
-struct orc_frame {
-    int N;
-    const orc_keypoint* kps;
-    const uint8_t* desc; int desc_stride;
-    const uint8_t* is_orb;
-    orc_grid_bounds gb;
-    int* cell_start;        /* COLS*ROWS+1, cell id = ix*ROWS + iy */
-    int* cell_items;        /* insertion order inside each cell */
-};
-
 void orc_grid_bounds_for_image(int W, int H, orc_grid_bounds* gb)
 {
     gb->minX = 0.0f; gb->maxX = (float)W; gb->minY = 0.0f; gb->maxY = (float)H;   /* Frame.cc:862-866 */
     gb->invW = (float)FRAME_GRID_COLS / (gb->maxX - gb->minX);                  /* :362-363 */
     gb->invH = (float)FRAME_GRID_ROWS / (gb->maxY - gb->minY);
-}
-
-static int frame_level(const orc_frame* f, int i)
-{   /* Frame::getKPtLevelMono / MixedFrame::getKPtLevelMono (MixedFrame.cpp:438-446) */
-    if (!f->is_orb || f->is_orb[i]) return f->kps[i].octave;
-    return f->kps[i].class_id;
 }
 
 static int pos_in_grid(const orc_frame* f, const orc_keypoint* kp, int* px, int* py)
@@ -75,6 +52,12 @@ static int pos_in_grid(const orc_frame* f, const orc_keypoint* kp, int* px, int*
     *py = (int)roundf((kp->y - f->gb.minY) * f->gb.invH);
     if (*px < 0 || *px >= FRAME_GRID_COLS || *py < 0 || *py >= FRAME_GRID_ROWS) return 0;
     return 1;
+}
+
+static int frame_level(const orc_frame* f, int i)
+{   /* Frame::getKPtLevelMono / MixedFrame::getKPtLevelMono (MixedFrame.cpp:438-446) */
+    if (!f->is_orb || f->is_orb[i]) return f->kps[i].octave;
+    return f->kps[i].class_id;
 }
 
 orc_frame* orc_frame_create(const orc_keypoint* kps, int N, const uint8_t* desc, int desc_stride,
@@ -141,16 +124,6 @@ int orc_get_features_in_area(const orc_frame* f, float x, float y, float r, int 
     return n;
 }
 
-static int rot_bin(float a1, float a2)
-{   /* ORBmatcher.cc:790-796 / :2082-2087 */
-    const float factor = 1.0f / HISTO_LENGTH;
-    float rot = a1 - a2;
-    if (rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == HISTO_LENGTH) bin = 0;
-    return bin;
-}
-
 /* ORBmatcher::SearchForInitialization :714-831 ; MixedMatcher.cpp:20-145 adds the isORB gate */
 int orc_search_for_initialization(const orc_frame* F1, const orc_frame* F2, float* prev_matched,
                                   int* matches12, int windowSize, float nnratio, int checkOri)
@@ -215,16 +188,6 @@ int orc_search_for_initialization(const orc_frame* F1, const orc_frame* F2, floa
     for (int i = 0; i < HISTO_LENGTH; i++) free(rotHist[i]);
     free(matchedDist); free(matches21); free(idxs);
     return nmatches;
-}
-
-/* occupancy rule shared by the projection matchers (:91-93, :2045-2047):
- * a candidate holding a map point with Observations()>0 is skipped. */
-static int holds_observed(const int* slot_mp, int idx, const uint8_t* mp_obs)
-{
-    int v = slot_mp[idx];
-    if (v == -1 || v == -3) return 0;
-    if (v == -2) return 1;
-    return mp_obs[v] != 0;
 }
 
 /* ORBmatcher::SearchByProjection(Frame& cur, const Frame& last, th, bMono) :1969-2187, mono */
@@ -323,7 +286,7 @@ int orc_search_by_projection_map_stereo(const orc_frame* F, int M, const uint8_t
     for (int m = 0; m < M; m++) {
         if (!in_view[m]) continue;
         const int nPredictedLevel = level[m];
-        float r = (view_cos[m] > 0.998) ? 2.5f : 4.0f;          /* RadiusByViewingCos :221-227 */
+        float r = radius_by_viewing_cos(view_cos[m]);
         if (bFactor) r *= th;
         const float rs = r * level_scale[m];
         int nc = orc_get_features_in_area(F, proj_xy[2 * m], proj_xy[2 * m + 1], rs,
@@ -553,15 +516,19 @@ static int epipolar_ok(const orc_keypoint* kp1, const orc_keypoint* kp2, const f
     return dsqr < 3.84f * unc;                       /* DEF_EC_DIST_COEF, include/CameraModels/Pinhole.h:36 */
 }
 
-/* ORBmatcher::SearchForTriangulation :975-1214 (mono: no mpCamera2, mvuRight < 0, bOnlyStereo = false) */
-int orc_search_for_triangulation(const orc_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
-                                 const uint32_t* nodes1, const int32_t* off1, const int32_t* idx1, int nn1,
-                                 const orc_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
-                                 const uint32_t* nodes2, const int32_t* off2, const int32_t* idx2, int nn2,
-                                 const float ep[2], const float F12[9], const float* scale2, const float* sigma2_2,
-                                 int bCoarse, int checkOri, int32_t* match12)
+/* ORBmatcher::SearchForTriangulation :975-1214 with bOnlyStereo = false.  The geometric test is pCamera1->epipolarConstrain (:1139):
+ * Pinhole's with F12 given (F12 != NULL), or KannalaBrandt8's with the pose and cameras of (bRight1, bRight2) (:1107-1137).  Both
+ * are free of side effects, so testing bCoarse first changes nothing.  nleft1 >= 0: two-camera keyframes (pKF1->mpCamera2; the
+ * caller checks pKF2 has one too), whose bStereo is false and which skip the epipole test (:1051, :1079, :1097). */
+static int search_for_triangulation(const orc_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+                                    const uint32_t* nodes1, const int32_t* off1, const int32_t* idx1, int nn1,
+                                    const orc_keypoint* kps2, int nleft2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+                                    const uint32_t* nodes2, const int32_t* off2, const int32_t* idx2, int nn2,
+                                    const float* F12, const orc_camera* cam1, const orc_camera* cam2, const float* Rt,
+                                    const float ep[2], const float* scale2, const float* sigma2_1, const float* sigma2_2,
+                                    int bCoarse, int checkOri, int32_t* match12)
 {
-    (void)n2;
+    const int twocam = nleft1 >= 0;
     int nmatches = 0;
     for (int i = 0; i < n1; i++) match12[i] = -1;
     int* rotHist[HISTO_LENGTH]; int rotN[HISTO_LENGTH];
@@ -572,7 +539,8 @@ int orc_search_for_triangulation(const orc_keypoint* kps1, int n1, const uint8_t
             for (int i1 = off1[a]; i1 < off1[a + 1]; i1++) {
                 const int id1 = idx1[i1];
                 if (!(elig1[id1] & 1)) continue;                             /* pMP1 (:1046) / !isORBDescValid; bit 1: bStereo1 (:1051) */
-                const orc_keypoint* kp1 = &kps1[id1];
+                const orc_keypoint* kp1 = &kps1[id1];                        /* :1058-1060 */
+                const int bRight1 = twocam && id1 >= nleft1;                 /* :1062 */
                 const uint8_t* d1 = desc1 + (size_t)stride1 * id1;
                 int bestDist = TH_LOW, bestIdx2 = -1;
                 for (int i2 = off2[b]; i2 < off2[b + 1]; i2++) {
@@ -580,12 +548,18 @@ int orc_search_for_triangulation(const orc_keypoint* kps1, int n1, const uint8_t
                     if (!(elig2[id2] & 1)) continue;                         /* vbMatched2 is never set in this function */
                     const int dist = orc_descriptor_distance(d1, desc2 + (size_t)stride2 * id2);
                     if (dist > TH_LOW || dist > bestDist) continue;
-                    const orc_keypoint* kp2 = &kps2[id2];
-                    if (!((elig1[id1] | elig2[id2]) & 2)) {                  /* if(!bStereo1 && !bStereo2 && !pKF1->mpCamera2) :1093 */
+                    const orc_keypoint* kp2 = &kps2[id2];                    /* :1092-1094 */
+                    const int bRight2 = twocam && id2 >= nleft2;             /* :1095 */
+                    if (!twocam && !((elig1[id1] | elig2[id2]) & 2)) {       /* if(!bStereo1 && !bStereo2 && !pKF1->mpCamera2) :1097 */
                         const float distex = ep[0] - kp2->x, distey = ep[1] - kp2->y;
                         if (distex * distex + distey * distey < 100 * scale2[kp2->octave]) continue;
                     }
-                    if (epipolar_ok(kp1, kp2, F12, sigma2_2[kp2->octave]) || bCoarse) { bestIdx2 = id2; bestDist = dist; }
+                    const int pose = bRight1 << 1 | bRight2;                 /* ll, lr, rl, rr */
+                    if (bCoarse || (F12 ? epipolar_ok(kp1, kp2, F12, sigma2_2[kp2->octave])
+                                        : orc_kb8_epipolar_constrain(&cam1[bRight1], &cam2[bRight2], kp1, kp2, Rt + 12 * pose, Rt + 12 * pose + 9,
+                                                                     sigma2_1[kp1->octave], sigma2_2[kp2->octave]))) {
+                        bestIdx2 = id2; bestDist = dist;
+                    }
                 }
                 if (bestIdx2 >= 0) {
                     match12[id1] = bestIdx2;
@@ -613,6 +587,31 @@ int orc_search_for_triangulation(const orc_keypoint* kps1, int n1, const uint8_t
     }
     for (int i = 0; i < HISTO_LENGTH; i++) free(rotHist[i]);
     return nmatches;
+}
+
+int orc_search_for_triangulation(const orc_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+                                 const uint32_t* nodes1, const int32_t* off1, const int32_t* idx1, int nn1,
+                                 const orc_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+                                 const uint32_t* nodes2, const int32_t* off2, const int32_t* idx2, int nn2,
+                                 const float ep[2], const float F12[9], const float* scale2, const float* sigma2_2,
+                                 int bCoarse, int checkOri, int32_t* match12)
+{
+    (void)n2;
+    return search_for_triangulation(kps1, n1, -1, desc1, stride1, elig1, nodes1, off1, idx1, nn1, kps2, -1, desc2, stride2, elig2,
+                                    nodes2, off2, idx2, nn2, F12, NULL, NULL, NULL, ep, scale2, NULL, sigma2_2, bCoarse, checkOri, match12);
+}
+
+int orc_search_for_triangulation_kb8(const orc_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+                                     const uint32_t* nodes1, const int32_t* off1, const int32_t* idx1, int nn1,
+                                     const orc_keypoint* kps2, int n2, int nleft2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+                                     const uint32_t* nodes2, const int32_t* off2, const int32_t* idx2, int nn2,
+                                     const orc_camera cam1[2], const orc_camera cam2[2], const float Rt[48], const float ep[2],
+                                     const float* scale2, const float* sigma2_1, const float* sigma2_2, int bCoarse, int checkOri,
+                                     int32_t* match12)
+{
+    (void)n2;
+    return search_for_triangulation(kps1, n1, nleft1, desc1, stride1, elig1, nodes1, off1, idx1, nn1, kps2, nleft2, desc2, stride2, elig2,
+                                    nodes2, off2, idx2, nn2, NULL, cam1, cam2, Rt, ep, scale2, sigma2_1, sigma2_2, bCoarse, checkOri, match12);
 }
 
 /* Fuse :1512-1578 / Fuse(Scw) :1619-1741 / SearchBySim3 :1829-1860 / SearchByProjection(KF,Scw) :548-588 search core */

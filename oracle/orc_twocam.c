@@ -3,35 +3,17 @@
  * sequentially in strict IEEE C.  Frame::Frame(imLeft, imRight, ..., pCamera, pCamera2, Tlr) (src/Frame.cc:1101-1208),
  * Frame::ComputeStereoFishEyeMatches (:1210-1250) up to TriangulateMatches, and the numKPtsLeft() != -1 branches of
  * ORBmatcher::SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:44-219), SearchByProjection(CurF, LastF, th, bMono)
- * (:1969-2187) and SearchByBoW(pKF, F, vpMapPointMatches) (:276-478).  Links oracle/_build/liboracle.so for
- * orc_descriptor_distance, orc_three_maxima and orc_bf_knn2.
+ * (:1969-2187) and SearchByBoW(pKF, F, vpMapPointMatches) (:276-478).
  *
- * A frame holds nL left keypoints then nR right ones (mvKeys, mvKeysRight); slots frame_mp[nL + nR]:
- * -1 none, k >= 0 query k of this call (Observations() > 0 iff obs[k]), -2 foreign observed, -3 foreign unobserved.
+ * A frame holds nL left keypoints then nR right ones (mvKeys, mvKeysRight); slots frame_mp[nL + nR] as holds_observed reads them.
  */
-#include <math.h>
-#include <stdint.h>
+#include "orc_matcher.h"
 #include <stdlib.h>
-#include <string.h>
-
-typedef struct { float x, y, size, angle, response; int32_t octave, class_id; } tc_keypoint;   /* cv::KeyPoint, 28 B */
-typedef struct { float minX, minY, maxX, maxY, invW, invH; } tc_bounds;                          /* eorb_grid_bounds */
-
-int  orc_descriptor_distance(const uint8_t* a, const uint8_t* b);                   /* ORBmatcher.cc:2360-2378 */
-void orc_three_maxima(const int* sizes, int L, int* ind1, int* ind2, int* ind3);    /* :2314-2355 */
-void orc_bf_knn2(const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx2, int32_t* dist2);   /* Frame.cc:1228 */
-
-#define FRAME_GRID_ROWS 48      /* include/Frame.h:45 */
-#define FRAME_GRID_COLS 64      /* include/Frame.h:46 */
-#define TH_HIGH 100             /* ORBmatcher.cc:36 */
-#define TH_LOW 50               /* :37 */
-#define HISTO_LENGTH 30         /* :38 */
-#define NCELL (FRAME_GRID_COLS * FRAME_GRID_ROWS)
 
 /* ---- ComputeStereoFishEyeMatches (:1210-1250) without TriangulateMatches ------------------------------------------- */
 /* cand[nL] = trainIdx + monoRight of a left keypoint passing Lowe's test (-1 otherwise), dist2[2 nL] = the knn distances (-1 none) */
-int orc_tc_fisheye_matches(const uint8_t* descL, int nL, int monoLeft, const uint8_t* descR, int nR, int monoRight,
-                           int32_t* cand, int32_t* dist2)
+int orc_fisheye_matches(const uint8_t* descL, int nL, int monoLeft, const uint8_t* descR, int nR, int monoRight,
+                        int32_t* cand, int32_t* dist2)
 {
     const int nq = nL - monoLeft, nt = nR - monoRight;
     int n = 0;
@@ -54,74 +36,50 @@ int orc_tc_fisheye_matches(const uint8_t* descL, int nL, int monoLeft, const uin
 
 /* ---- the two grids (AssignFeaturesToGrid :431-460) -------------------------------------------------------------------- */
 typedef struct {
-    int nL, nR;
-    const tc_keypoint* kps;
-    const uint8_t* desc; int stride;
-    tc_bounds gb;
-    int* start[2]; int* items[2];      /* per camera: cell starts (NCELL + 1) and camera-local indices in insertion order */
-} tc_frame;
+    int nL;
+    const orc_keypoint* kps;
+    orc_frame* grid[2];                /* mGrid / mGridRight: each camera's keypoints, camera-local indices */
+} twocam_frame;
 
-static int pos_in_grid(const tc_bounds* gb, const tc_keypoint* kp, int* px, int* py)
-{   /* Frame::PosInGrid :783-793 */
-    *px = (int)roundf((kp->x - gb->minX) * gb->invW);
-    *py = (int)roundf((kp->y - gb->minY) * gb->invH);
-    return !(*px < 0 || *px >= FRAME_GRID_COLS || *py < 0 || *py >= FRAME_GRID_ROWS);
-}
-
-static void frame_init(tc_frame* f, const tc_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride, const tc_bounds* gb)
+static void frame_init(twocam_frame* f, const orc_keypoint* kps, int nL, int nR, const orc_grid_bounds* gb)
 {
-    f->nL = nL; f->nR = nR; f->kps = kps; f->desc = desc; f->stride = stride; f->gb = *gb;
-    for (int cam = 0; cam < 2; cam++) {
-        const int base = cam ? nL : 0, n = cam ? nR : nL;
-        int* cnt = (int*)calloc(NCELL + 1, sizeof(int));
-        int* cid = (int*)malloc(sizeof(int) * (n ? n : 1));
-        for (int j = 0; j < n; j++) {
-            int px, py;
-            cid[j] = pos_in_grid(gb, &kps[base + j], &px, &py) ? px * FRAME_GRID_ROWS + py : -1;   /* mGrid / mGridRight */
-            if (cid[j] >= 0) cnt[cid[j] + 1]++;
-        }
-        for (int c = 0; c < NCELL; c++) cnt[c + 1] += cnt[c];
-        int* fill = (int*)malloc(sizeof(int) * NCELL);
-        memcpy(fill, cnt, sizeof(int) * NCELL);
-        f->items[cam] = (int*)malloc(sizeof(int) * (n ? n : 1));
-        for (int j = 0; j < n; j++) if (cid[j] >= 0) f->items[cam][fill[cid[j]]++] = j;
-        f->start[cam] = cnt;
-        free(fill); free(cid);
-    }
+    f->nL = nL; f->kps = kps;
+    f->grid[0] = orc_frame_create(kps, nL, NULL, 0, NULL, gb);
+    f->grid[1] = orc_frame_create(kps + nL, nR, NULL, 0, NULL, gb);
 }
 
-static void frame_free(tc_frame* f) { for (int c = 0; c < 2; c++) { free(f->start[c]); free(f->items[c]); } }
+static void frame_free(twocam_frame* f) { orc_frame_destroy(f->grid[0]); orc_frame_destroy(f->grid[1]); }
 
 /* Frame::getKPtLevelMono(j) = mvKeysUn[j].octave (:1417-1420).  mvKeysUn holds the nL left keypoints (:1191); past them (j >= nL,
  * an out-of-range read in the reference) the right keypoint's own octave, as upstream ORB-SLAM3 reads it. */
-static int level_mono(const tc_frame* f, int j) { return j < f->nL ? f->kps[j].octave : f->kps[f->nL + j].octave; }
+static int level_mono(const twocam_frame* f, int j) { return j < f->nL ? f->kps[j].octave : f->kps[f->nL + j].octave; }
 
 /* Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel, bRight) (:710-781); returns camera-local indices in the reference's order */
-static int features_in_area(const tc_frame* f, float x, float y, float r, int minLevel, int maxLevel, int bRight, int* out)
+static int features_in_area(const twocam_frame* f, float x, float y, float r, int minLevel, int maxLevel, int bRight, int* out)
 {
+    const orc_frame* g = f->grid[bRight];
     int n = 0;
     const float factorX = r, factorY = r;
-    int t = (int)floorf((x - f->gb.minX - factorX) * f->gb.invW);
+    int t = (int)floorf((x - g->gb.minX - factorX) * g->gb.invW);
     const int nMinCellX = t > 0 ? t : 0;
     if (nMinCellX >= FRAME_GRID_COLS) return 0;
-    t = (int)ceilf((x - f->gb.minX + factorX) * f->gb.invW);
+    t = (int)ceilf((x - g->gb.minX + factorX) * g->gb.invW);
     const int nMaxCellX = t < FRAME_GRID_COLS - 1 ? t : FRAME_GRID_COLS - 1;
     if (nMaxCellX < 0) return 0;
-    t = (int)floorf((y - f->gb.minY - factorY) * f->gb.invH);
+    t = (int)floorf((y - g->gb.minY - factorY) * g->gb.invH);
     const int nMinCellY = t > 0 ? t : 0;
     if (nMinCellY >= FRAME_GRID_ROWS) return 0;
-    t = (int)ceilf((y - f->gb.minY + factorY) * f->gb.invH);
+    t = (int)ceilf((y - g->gb.minY + factorY) * g->gb.invH);
     const int nMaxCellY = t < FRAME_GRID_ROWS - 1 ? t : FRAME_GRID_ROWS - 1;
     if (nMaxCellY < 0) return 0;
     const int bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-    const int base = bRight ? f->nL : 0;
     for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
         for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
             const int c = ix * FRAME_GRID_ROWS + iy;
-            for (int p = f->start[bRight][c]; p < f->start[bRight][c + 1]; p++) {
-                const int j = f->items[bRight][p];
+            for (int p = g->cell_start[c]; p < g->cell_start[c + 1]; p++) {
+                const int j = g->cell_items[p];
                 /* kpUn = getDistKPtMono(j) (left) / getKPtRight(j) (right) (:751-753) */
-                const tc_keypoint* kp = &f->kps[base + j];
+                const orc_keypoint* kp = &g->kps[j];
                 if (bCheckLevels) {
                     const int level = level_mono(f, j);                       /* :763: the LEFT keypoint j, even for bRight */
                     if (level < minLevel) continue;
@@ -134,39 +92,18 @@ static int features_in_area(const tc_frame* f, float x, float y, float r, int mi
     return n;
 }
 
-/* getMapPoint(idx) && getMapPoint(idx)->Observations() > 0 (:91-93, :160-162, :2045-2047, :2128-2130) */
-static int holds_observed(const int32_t* slot, int idx, const uint8_t* obs)
-{
-    const int v = slot[idx];
-    if (v == -1 || v == -3) return 0;
-    if (v == -2) return 1;
-    return obs[v] != 0;
-}
-
-static float radius_by_viewing_cos(float viewCos) { return viewCos > 0.998 ? 2.5f : 4.0f; }   /* :221-227 */
-
-static int rot_bin(float a1, float a2)
-{   /* :2139-2145 */
-    const float factor = 1.0f / HISTO_LENGTH;
-    float rot = a1 - a2;
-    if (rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == HISTO_LENGTH) bin = 0;
-    return bin;
-}
-
 /* ---- SearchByProjection(F, vpMapPoints, th) :44-219, numKPtsLeft() != -1 ------------------------------------------------ */
 /* per map point m: left in_view / proj_xy / level / view_cos / level_scale (= F.getORBScaleFactor(level)), right the same with _r
  * (level_r = mnTrackScaleLevelR, -1 = skip); l2r / r2l = mvLeftToRightMatch / mvRightToLeftMatch */
-int orc_tc_search_by_projection_map(const tc_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride, const tc_bounds* gb,
-                                    const int32_t* l2r, const int32_t* r2l, int M,
-                                    const uint8_t* in_view, const float* proj_xy, const int32_t* level, const float* view_cos, const float* level_scale,
-                                    const uint8_t* in_view_r, const float* proj_xy_r, const int32_t* level_r, const float* view_cos_r,
-                                    const float* level_scale_r, const uint8_t* mp_desc, const uint8_t* mp_obs,
-                                    int32_t* frame_mp, float th, float nnratio)
+int orc_search_by_projection_map_fisheye(const orc_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
+                                         const orc_grid_bounds* gb, const int32_t* l2r, const int32_t* r2l, int M,
+                                         const uint8_t* in_view, const float* proj_xy, const int32_t* level, const float* view_cos,
+                                         const float* level_scale, const uint8_t* in_view_r, const float* proj_xy_r, const int32_t* level_r,
+                                         const float* view_cos_r, const float* level_scale_r, const uint8_t* mp_desc, const uint8_t* mp_obs,
+                                         int32_t* frame_mp, float th, float nnratio)
 {
-    tc_frame F;
-    frame_init(&F, kps, nL, nR, desc, stride, gb);
+    twocam_frame F;
+    frame_init(&F, kps, nL, nR, gb);
     int nmatches = 0;
     const int bFactor = th != 1.0;                                            /* :49 */
     int* idxs = (int*)malloc(sizeof(int) * (nL + nR + 1));
@@ -237,13 +174,13 @@ int orc_tc_search_by_projection_map(const tc_keypoint* kps, int nL, int nR, cons
 /* queries: the n_last points of the last frame; valid / uv = the left projection with invzc < 0, bounds and outliers folded in
  * (:1998-2012); uv_r = mpCamera->project(mTrl x3Dc) (:2093-2095); last_kps in index order (octave = getKPtLevelMono(i), with
  * the rule of level_mono for i >= nL_last; angle); level_scale = getORBScaleFactor(octave); mode 0 / 1 forward / 2 backward */
-int orc_tc_search_by_projection_last(const tc_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride, const tc_bounds* gb,
-                                     const tc_keypoint* last_kps, int n_last, const uint8_t* valid, const float* uv, const float* uv_r,
-                                     const uint8_t* mp_desc, const uint8_t* mp_obs, const float* level_scale,
-                                     int32_t* cur_mp, float th, int mode, int checkOri)
+int orc_search_by_projection_last_fisheye(const orc_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
+                                          const orc_grid_bounds* gb, const orc_keypoint* last_kps, int n_last, const uint8_t* valid,
+                                          const float* uv, const float* uv_r, const uint8_t* mp_desc, const uint8_t* mp_obs,
+                                          const float* level_scale, int32_t* cur_mp, float th, int mode, int checkOri)
 {
-    tc_frame F;
-    frame_init(&F, kps, nL, nR, desc, stride, gb);
+    twocam_frame F;
+    frame_init(&F, kps, nL, nR, gb);
     int nmatches = 0;
     int* rotHist[HISTO_LENGTH]; int rotN[HISTO_LENGTH];
     for (int i = 0; i < HISTO_LENGTH; i++) { rotHist[i] = (int*)malloc(sizeof(int) * (2 * n_last + 1)); rotN[i] = 0; }
@@ -305,11 +242,11 @@ int orc_tc_search_by_projection_last(const tc_keypoint* kps, int nL, int nR, con
 /* ---- SearchByBoW(pKF, F, vpMapPointMatches) :276-478, numKPtsLeft() != -1 ---------------------------------------------- */
 /* feature vectors as CSR (node ids ascending); the frame's features are nL left then the right ones (n_f in all); kf_kps in the
  * KeyFrame's index order (:391-393 picks its right keypoint for realIdxKF >= NLeft); match_f[n_f] out */
-int orc_tc_search_by_bow(const tc_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
-                         const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
-                         const tc_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc,
-                         const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
-                         int32_t* match_f, float nnratio, int checkOri)
+int orc_search_by_bow_fisheye(const orc_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
+                              const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
+                              const orc_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc,
+                              const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
+                              int32_t* match_f, float nnratio, int checkOri)
 {
     int nmatches = 0;
     for (int i = 0; i < n_f; i++) match_f[i] = -1;

@@ -1,11 +1,10 @@
-"""GPU parity of the two-camera (fisheye stereo) entry points against the two-camera oracle (tests/twocam/orc_twocam.c):
+"""GPU parity of the two-camera (fisheye stereo) entry points against the two-camera oracle (oracle/orc_twocam.c):
 eorb_frame_fisheye, eorb_search_by_projection_map_fisheye, eorb_search_by_projection_last_fisheye, eorb_search_by_bow_fisheye.
 TUM-VI sized frames: 512 x 512, 8 levels."""
 import numpy as np
 import pytest
 
 from eorb_slam_amd import synth
-from twocam import oracle_tc as T
 
 pytestmark = pytest.mark.gpu
 
@@ -26,32 +25,27 @@ def ctx(fe):
     c.close()
 
 
-@pytest.fixture(scope="module")
-def tc(oracle, tmp_path_factory):
-    return T.TwoCamOracle(tmp_path_factory.mktemp("twocam"), oracle)
-
-
 def _orb(oracle, nfeat):
     return oracle.OrbExtractor(nfeat, 1.2, 8, 20, 7, edgeTh=19)
 
 
-def _oracle_frame(oracle, tc, nfeat, imL, imR, lapL, lapR):
+def _oracle_frame(oracle, nfeat, imL, imR, lapL, lapR):
     e = _orb(oracle, nfeat)
     mL, kL, dL, _ = e.extract(imL, lapL)
     mR, kR, dR, _ = e.extract(imR, lapR)
-    n, cand, d2 = tc.fisheye_matches(dL, mL, dR, mR)
+    n, cand, d2 = oracle.fisheye_matches(dL, mL, dR, mR)
     return dict(kpsL=kL, descL=dL, monoLeft=mL, kpsR=kR, descR=dR, monoRight=mR, right_idx=cand, dist2=d2, ncand=n)
 
 
 _frames = {}
 
 
-def _frame(oracle, tc, nfeat=1500, seed=5, shift=(2, -7)):
+def _frame(oracle, nfeat=1500, seed=5, shift=(2, -7)):
     """an oracle two-camera frame (full lapping areas) and its concatenated keypoints / descriptors / links"""
     key = (nfeat, seed, shift)
     if key not in _frames:
-        imL, imR = T.image_pair(W, H, seed, shift)
-        f = _oracle_frame(oracle, tc, nfeat, imL, imR, (0, W - 1), (0, W - 1))
+        imL, imR = synth.image_pair(W, H, seed, shift)
+        f = _oracle_frame(oracle, nfeat, imL, imR, (0, W - 1), (0, W - 1))
         nL, nR = len(f["kpsL"]), len(f["kpsR"])
         l2r = np.where(f["right_idx"] >= 0, f["right_idx"], -1).astype(np.int32)
         r2l = np.full(nR, -1, np.int32)
@@ -63,11 +57,11 @@ def _frame(oracle, tc, nfeat=1500, seed=5, shift=(2, -7)):
 # ---- the frame seam --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nfeat", [1000, 1500])
 @pytest.mark.parametrize("laps", [((0, 511), (0, 511)), ((0, 300), (200, 511))])
-def test_frame_fisheye(oracle, fe, ctx, tc, nfeat, laps):
-    imL, imR = T.image_pair(W, H, seed=5 + nfeat // 500)
+def test_frame_fisheye(oracle, fe, ctx, nfeat, laps):
+    imL, imR = synth.image_pair(W, H, seed=5 + nfeat // 500)
     ge = fe.ORBextractor(nfeat, 1.2, 8, 20, 7, 19, imSize=(W, H), ctx=ctx)
     g = ge.fisheye(imL, imR, laps[0], laps[1])
-    o = _oracle_frame(oracle, tc, nfeat, imL, imR, laps[0], laps[1])
+    o = _oracle_frame(oracle, nfeat, imL, imR, laps[0], laps[1])
     for side in ("L", "R"):
         assert np.array_equal(o["kps" + side].view(np.uint8), g["kps" + side].view(np.uint8)), side
         assert np.array_equal(o["desc" + side], g["desc" + side]), side
@@ -89,7 +83,7 @@ def test_frame_fisheye_errors(fe, ctx):
     assert rc == E_NOTCONF
     ge = fe.ORBextractor(1000, 1.2, 8, 20, 7, 19, imSize=(W, H), ctx=c)
     assert c.L.eorb_frame_fisheye(c.h, fe._p(img), fe._p(img), W + 1, H, W + 1, 0, W, 0, W, None, None, None, None, None, None, None, None, 0, None, None, None) == E_ARG
-    imL, imR = T.image_pair(W, H, seed=9)
+    imL, imR = synth.image_pair(W, H, seed=9)
     with pytest.raises(fe.EorbError) as e:
         ge.cap = 10                                                          # caller capacity below the keypoint count
         ge.fisheye(imL, imR, (0, 511), (0, 511))
@@ -98,19 +92,19 @@ def test_frame_fisheye_errors(fe, ctx):
 
 
 # ---- SearchByProjection(F, map points) ------------------------------------------------------------------------------------------
-def _map_case(oracle, tc, seed, M=None):
-    kps, desc, nL, l2r, r2l = _frame(oracle, tc)
+def _map_case(oracle, seed, M=None):
+    kps, desc, nL, l2r, r2l = _frame(oracle)
     rng = np.random.default_rng(seed)
-    left, right, mp_desc, mp_obs = T.map_inputs(kps, nL, _orb(oracle, 1500).scale_factors, rng, M, src=(kps, desc))
+    left, right, mp_desc, mp_obs = synth.map_inputs(kps, nL, _orb(oracle, 1500).scale_factors, rng, M, src=(kps, desc))
     fm = np.full(len(kps), -1, np.int32); fm[::29] = -2; fm[7::31] = -3
     return kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm
 
 
 @pytest.mark.parametrize("th", [1.0, 3.0])
-def test_map_fisheye(oracle, fe, ctx, tc, th):
-    kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm = _map_case(oracle, tc, 31)
-    gb = T.bounds(W, H)
-    on, ofm = tc.map(kps, nL, desc, gb, l2r, r2l, left, right, mp_desc, mp_obs, fm, th, 0.8)
+def test_map_fisheye(oracle, fe, ctx, th):
+    kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm = _map_case(oracle, 31)
+    gb = oracle.grid_bounds(W, H)
+    on, ofm = oracle.search_by_projection_map_fisheye(kps, nL, desc, gb, l2r, r2l, left, right, mp_desc, mp_obs, fm, th, 0.8)
     m = fe.ORBmatcher(0.8, True, ctx)
     for _ in range(2):                                                      # the second call reuses the context's arena
         gn, gfm = m.SearchByProjectionMapFisheye(kps, nL, desc, l2r, r2l, gb, left, right, mp_desc, mp_obs, fm, th)
@@ -118,41 +112,41 @@ def test_map_fisheye(oracle, fe, ctx, tc, th):
     assert on > 200 and (ofm[nL:] >= 0).sum() > 100
 
 
-def test_map_fisheye_one_camera_empty(oracle, fe, ctx, tc):
-    kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm = _map_case(oracle, tc, 32)
-    gb = T.bounds(W, H)
+def test_map_fisheye_one_camera_empty(oracle, fe, ctx):
+    kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm = _map_case(oracle, 32)
+    gb = oracle.grid_bounds(W, H)
     m = fe.ORBmatcher(0.8, True, ctx)
     # nR = 0: the left keypoints only (no links)
     k0, d0 = kps[:nL], desc[:nL]
-    on, ofm = tc.map(k0, nL, d0, gb, np.full(nL, -1, np.int32), np.zeros(0, np.int32), left, right, mp_desc, mp_obs, fm[:nL], 1.0, 0.8)
+    on, ofm = oracle.search_by_projection_map_fisheye(k0, nL, d0, gb, np.full(nL, -1, np.int32), np.zeros(0, np.int32), left, right, mp_desc, mp_obs, fm[:nL], 1.0, 0.8)
     gn, gfm = m.SearchByProjectionMapFisheye(k0, nL, d0, np.full(nL, -1, np.int32), np.zeros(0, np.int32), gb, left, right, mp_desc, mp_obs, fm[:nL], 1.0)
     assert on == gn and np.array_equal(ofm, gfm) and on > 100
     # nL = 0: the right keypoints only
     k1, d1 = kps[nL:], desc[nL:]
     nR = len(k1)
-    on, ofm = tc.map(k1, 0, d1, gb, np.zeros(0, np.int32), np.full(nR, -1, np.int32), left, right, mp_desc, mp_obs, fm[nL:], 1.0, 0.8)
+    on, ofm = oracle.search_by_projection_map_fisheye(k1, 0, d1, gb, np.zeros(0, np.int32), np.full(nR, -1, np.int32), left, right, mp_desc, mp_obs, fm[nL:], 1.0, 0.8)
     gn, gfm = m.SearchByProjectionMapFisheye(k1, 0, d1, np.zeros(0, np.int32), np.full(nR, -1, np.int32), gb, left, right, mp_desc, mp_obs, fm[nL:], 1.0)
     assert on == gn and np.array_equal(ofm, gfm) and on > 50
 
 
-def test_map_fisheye_crowded(oracle, fe, ctx, tc):
+def test_map_fisheye_crowded(oracle, fe, ctx):
     """hundreds of keypoints in a few cells of both grids and every map point searching there"""
-    kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm = _map_case(oracle, tc, 33, M=600)
+    kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm = _map_case(oracle, 33, M=600)
     rng = np.random.default_rng(34)
     kps = kps.copy()
     kps["x"] = (250 + rng.uniform(0, 12, len(kps))).astype(np.float32); kps["y"] = (250 + rng.uniform(0, 12, len(kps))).astype(np.float32)
     for cam in (left, right):
         cam[1][:] = (256, 256); cam[3][:] = 0.5                             # r = 4 x scale: every search covers the crowd
-    gb = T.bounds(W, H)
-    on, ofm = tc.map(kps, nL, desc, gb, l2r, r2l, left, right, mp_desc, mp_obs, fm, 3.0, 0.9)
+    gb = oracle.grid_bounds(W, H)
+    on, ofm = oracle.search_by_projection_map_fisheye(kps, nL, desc, gb, l2r, r2l, left, right, mp_desc, mp_obs, fm, 3.0, 0.9)
     gn, gfm = fe.ORBmatcher(0.9, True, ctx).SearchByProjectionMapFisheye(kps, nL, desc, l2r, r2l, gb, left, right, mp_desc, mp_obs, fm, 3.0)
     assert on == gn and np.array_equal(ofm, gfm) and on > 20
 
 
 # ---- SearchByProjection(CurF, LastF) ---------------------------------------------------------------------------------------------
-def _last_case(oracle, tc, seed):
-    kps, desc, nL, l2r, r2l = _frame(oracle, tc)
-    lk, ld, nLl, _, _ = _frame(oracle, tc, seed=5, shift=(5, -3))
+def _last_case(oracle, seed):
+    kps, desc, nL, l2r, r2l = _frame(oracle)
+    lk, ld, nLl, _, _ = _frame(oracle, seed=5, shift=(5, -3))
     rng = np.random.default_rng(seed)
     nq = len(lk)
     valid = (rng.uniform(size=nq) < 0.85).astype(np.uint8)
@@ -167,55 +161,55 @@ def _last_case(oracle, tc, seed):
 
 @pytest.mark.parametrize("mode", [0, 1, 2])
 @pytest.mark.parametrize("ori", [True, False])
-def test_last_fisheye(oracle, fe, ctx, tc, mode, ori):
-    kps, desc, nL, lk, valid, uv, uv_r, ld, mp_obs, cur, ls = _last_case(oracle, tc, 41)
-    gb = T.bounds(W, H)
-    on, ocm = tc.last(kps, nL, desc, gb, lk, valid, uv, uv_r, ld, mp_obs, cur, 7.0, ls, mode, ori)
+def test_last_fisheye(oracle, fe, ctx, mode, ori):
+    kps, desc, nL, lk, valid, uv, uv_r, ld, mp_obs, cur, ls = _last_case(oracle, 41)
+    gb = oracle.grid_bounds(W, H)
+    on, ocm = oracle.search_by_projection_last_fisheye(kps, nL, desc, gb, lk, valid, uv, uv_r, ld, mp_obs, cur, 7.0, ls, mode, ori)
     gn, gcm = fe.ORBmatcher(0.9, ori, ctx).SearchByProjectionLastFisheye(kps, nL, desc, gb, lk, valid, uv, uv_r, ld, mp_obs, cur, 7.0, ls, mode)
     assert on == gn and np.array_equal(ocm, gcm)
     assert on > 100 and (ocm[nL:] >= 0).sum() > 30
 
 
-def test_last_fisheye_one_camera_empty(oracle, fe, ctx, tc):
-    kps, desc, nL, lk, valid, uv, uv_r, ld, mp_obs, cur, ls = _last_case(oracle, tc, 42)
-    gb = T.bounds(W, H)
+def test_last_fisheye_one_camera_empty(oracle, fe, ctx):
+    kps, desc, nL, lk, valid, uv, uv_r, ld, mp_obs, cur, ls = _last_case(oracle, 42)
+    gb = oracle.grid_bounds(W, H)
     m = fe.ORBmatcher(0.9, True, ctx)
     for sl, n in ((slice(0, nL), nL), (slice(nL, None), 0)):
-        on, ocm = tc.last(kps[sl], n, desc[sl], gb, lk, valid, uv, uv_r, ld, mp_obs, cur[sl], 7.0, ls, 0, True)
+        on, ocm = oracle.search_by_projection_last_fisheye(kps[sl], n, desc[sl], gb, lk, valid, uv, uv_r, ld, mp_obs, cur[sl], 7.0, ls, 0, True)
         gn, gcm = m.SearchByProjectionLastFisheye(kps[sl], n, desc[sl], gb, lk, valid, uv, uv_r, ld, mp_obs, cur[sl], 7.0, ls, 0)
         assert on == gn and np.array_equal(ocm, gcm)
 
 
 # ---- SearchByBoW(KF, F) -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ori", [True, False])
-def test_bow_fisheye(oracle, fe, ctx, tc, ori):
-    kps, desc, nL, _, _ = _frame(oracle, tc)
-    kk, kd, _, _, _ = _frame(oracle, tc, seed=5, shift=(5, -3))
+def test_bow_fisheye(oracle, fe, ctx, ori):
+    kps, desc, nL, _, _ = _frame(oracle)
+    kk, kd, _, _, _ = _frame(oracle, seed=5, shift=(5, -3))
     rng = np.random.default_rng(51)
     nn = 120
-    kfv = T.feature_vector_of(rng.integers(0, nn, len(kk)), rng)
+    kfv = synth.feature_vector_of(rng.integers(0, nn, len(kk)), rng)
     node_kf = np.zeros(len(kk), np.int64)
     for a in range(len(kfv[0])):
         node_kf[kfv[2][kfv[1][a]:kfv[1][a + 1]]] = kfv[0][a]
     dx = kps["x"][:, None] - (kk["x"][None, :] - 3); dy = kps["y"][:, None] - (kk["y"][None, :] - 5)
     near = np.argmin(dx * dx + dy * dy, axis=1)
-    ffv = T.feature_vector_of(np.where(rng.uniform(size=len(kps)) < 0.85, node_kf[near], rng.integers(0, nn, len(kps))), rng)
+    ffv = synth.feature_vector_of(np.where(rng.uniform(size=len(kps)) < 0.85, node_kf[near], rng.integers(0, nn, len(kps))), rng)
     has_mp = (rng.uniform(size=len(kk)) < 0.8).astype(np.uint8)
     for ratio in (0.7, 0.95):
-        on, om = tc.bow(kk, kd, has_mp, kfv, kps, nL, desc, ffv, ratio, ori)
+        on, om = oracle.search_by_bow_fisheye(kk, kd, has_mp, kfv, kps, nL, desc, ffv, ratio, ori)
         gn, gm = fe.SearchByBoWFisheye(kk, kd, has_mp, kfv, kps, nL, desc, ffv, ratio, ori, ctx=ctx)
         assert on == gn and np.array_equal(om, gm)
         assert (om[nL:] >= 0).sum() > 20
     for n in (0, len(kps)):                                                 # nL = 0 / nR = 0
-        on, om = tc.bow(kk, kd, has_mp, kfv, kps, n, desc, ffv, 0.7, ori)
+        on, om = oracle.search_by_bow_fisheye(kk, kd, has_mp, kfv, kps, n, desc, ffv, 0.7, ori)
         gn, gm = fe.SearchByBoWFisheye(kk, kd, has_mp, kfv, kps, n, desc, ffv, 0.7, ori, ctx=ctx)
         assert on == gn and np.array_equal(om, gm)
 
 
 # ---- errors --------------------------------------------------------------------------------------------------------------------------
-def test_matcher_errors(oracle, fe, ctx, tc):
-    kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm = _map_case(oracle, tc, 61)
-    gb = T.bounds(W, H)
+def test_matcher_errors(oracle, fe, ctx):
+    kps, desc, nL, l2r, r2l, left, right, mp_desc, mp_obs, fm = _map_case(oracle, 61)
+    gb = oracle.grid_bounds(W, H)
     m = fe.ORBmatcher(0.8, True, ctx)
 
     def code(f, *a):
@@ -239,5 +233,5 @@ def test_matcher_errors(oracle, fe, ctx, tc):
     assert code(m.SearchByProjectionLastFisheye, kps, nL, desc, gb, lk, np.ones(10, np.uint8), z, z, desc[:10], np.ones(10, np.uint8),
                 np.full(len(kps), -1, np.int32), 1.0, np.ones(10, np.float32), 3) == E_ARG
     rng = np.random.default_rng(1)
-    fv = T.feature_vector_of(rng.integers(0, 5, len(kps)), rng)
+    fv = synth.feature_vector_of(rng.integers(0, 5, len(kps)), rng)
     assert code(fe.SearchByBoWFisheye, kps, desc, np.ones(len(kps), np.uint8), fv, kps, len(kps) + 1, desc, fv, 0.7, True, ctx) == E_ARG

@@ -1,103 +1,97 @@
-"""Known answers of the KannalaBrandt8 SearchForTriangulation oracle (tests/kb8tri/orc_kb8tri.c): the 4x4 Jacobi SVD,
+"""Known answers of the KannalaBrandt8 SearchForTriangulation oracle (oracle/orc_kb8tri.c, orc_match.c): the 4x4 Jacobi SVD,
 KannalaBrandt8::TriangulateMatches (src/CameraModels/KannalaBrandt8.cpp:416-486), the reductions of the walk (:975-1214) to the
 Pinhole oracle when bCoarse skips the geometry, and one case per quirk.  CPU only."""
 import numpy as np
 import pytest
 
-from kb8tri import oracle_kt as K
+from eorb_slam_amd import synth
 
-
-@pytest.fixture(scope="module")
-def kt(oracle, tmp_path_factory):
-    return K.KB8TriOracle(tmp_path_factory.mktemp("kb8tri_cpu"), oracle)
-
-
-_, SIG = K.level_tables()
-R2 = K.rot(0.03, -0.08, 0.02)
+_, SIG = synth.level_tables()
+R2 = synth.rot(0.03, -0.08, 0.02)
 T2 = np.array([-0.35, 0.04, 0.06], np.float32)
-RT = K.rel_pose(np.eye(3, dtype=np.float32), np.zeros(3, np.float32), R2, T2)      # R12 | t12 with camera 1 = world
+RT = synth.rel_pose(np.eye(3, dtype=np.float32), np.zeros(3, np.float32), R2, T2)      # R12 | t12 with camera 1 = world
 
 
 def _kp(x, y, octave=0, angle=0.0):
-    k = np.zeros(1, K.KP)[0]
+    k = np.zeros(1, synth.KP_DTYPE)[0]
     k["x"], k["y"], k["octave"], k["angle"], k["size"], k["class_id"] = x, y, octave, angle, 31.0, -1
     return k
 
 
-def _corr(kt, X, cam1=K.CAM_MONO, cam2=K.CAM_MONO, Rt=RT):
+def _corr(oracle, X, cam1=synth.CAM_MONO, cam2=synth.CAM_MONO, Rt=RT):
     """the keypoints of camera-1 point X in both cameras (the oracle's own float projection)"""
     R = Rt[:9].reshape(3, 3).astype(np.float64); t = Rt[9:].astype(np.float64)
     X2 = R.T @ (np.asarray(X, np.float64) - t)
-    u1, v1 = kt.project(cam1, np.asarray(X, np.float32))
-    u2, v2 = kt.project(cam2, X2.astype(np.float32))
+    u1, v1 = oracle.project(cam1, np.asarray(X, np.float32))
+    u2, v2 = oracle.project(cam2, X2.astype(np.float32))
     return _kp(u1, v1), _kp(u2, v2)
 
 
 # ---- the SVD ---------------------------------------------------------------------------------------------------------------------
-def test_svd_diagonal_sorted(kt):
-    W, Vt = kt.svd4(np.diag([1.0, 4.0, 2.0, 3.0]))
+def test_svd_diagonal_sorted(oracle):
+    W, Vt = oracle.svd4(np.diag([1.0, 4.0, 2.0, 3.0]))
     assert np.allclose(W, [4, 3, 2, 1])
     assert np.array_equal(np.abs(Vt), np.eye(4)[[1, 3, 2, 0]])
 
 
-def test_svd_null_vector_of_rank3(kt):
+def test_svd_null_vector_of_rank3(oracle):
     rng = np.random.default_rng(7)
     P = np.array([0.3, -1.2, 4.5, 1.0])
     A = rng.normal(size=(4, 4))
     A -= np.outer(A @ P, P) / (P @ P)                                    # rows orthogonal to P: A P = 0
-    W, Vt = kt.svd4(A.astype(np.float32))
+    W, Vt = oracle.svd4(A.astype(np.float32))
     assert W[3] < 1e-5 * W[0]
     v = Vt[3].astype(np.float64)
     assert np.allclose(v[:3] / v[3], P[:3], rtol=1e-3, atol=1e-3)
     assert np.allclose(Vt.astype(np.float64) @ Vt.T.astype(np.float64), np.eye(4), atol=1e-5)
 
 
-def test_svd_orthonormal(kt):
+def test_svd_orthonormal(oracle):
     rng = np.random.default_rng(8)
     for _ in range(20):
-        W, Vt = kt.svd4(rng.normal(size=(4, 4)).astype(np.float32) * 10)
+        W, Vt = oracle.svd4(rng.normal(size=(4, 4)).astype(np.float32) * 10)
         assert np.all(np.diff(W) <= 0)
         assert np.allclose(Vt.astype(np.float64) @ Vt.T.astype(np.float64), np.eye(4), atol=2e-6)
 
 
 # ---- TriangulateMatches --------------------------------------------------------------------------------------------------------
-def test_exact_correspondence_depth(kt):
+def test_exact_correspondence_depth(oracle):
     for X in ([0.4, -0.2, 3.0], [-1.5, 0.8, 6.5], [0.0, 0.1, 1.8]):
-        k1, k2 = _corr(kt, X)
-        z, x3 = kt.triangulate_matches(K.CAM_MONO, K.CAM_MONO, k1, k2, RT[:9], RT[9:], SIG[0], SIG[0])
+        k1, k2 = _corr(oracle, X)
+        z, x3 = oracle.triangulate_matches(synth.CAM_MONO, synth.CAM_MONO, k1, k2, RT[:9], RT[9:], SIG[0], SIG[0])
         assert z > 0 and abs(z - X[2]) < 2e-3 * X[2], (z, X)
         assert np.allclose(x3, X, rtol=3e-3, atol=3e-3)
 
 
-def test_parallel_rays_rejected(kt):
-    k1, k2 = _corr(kt, [0.4, -0.2, 3.0])
+def test_parallel_rays_rejected(oracle):
+    k1, k2 = _corr(oracle, [0.4, -0.2, 3.0])
     zero = np.concatenate([np.eye(3, dtype=np.float32).reshape(9), np.zeros(3, np.float32)])
-    z, _ = kt.triangulate_matches(K.CAM_MONO, K.CAM_MONO, k1, k1, zero[:9], zero[9:], SIG[0], SIG[0])    # zero baseline
+    z, _ = oracle.triangulate_matches(synth.CAM_MONO, synth.CAM_MONO, k1, k1, zero[:9], zero[9:], SIG[0], SIG[0])    # zero baseline
     assert z == -1
     far = np.float32(RT[9:] * 1e-4)                                      # a point very far away: cos parallax > 0.9998
-    z, _ = kt.triangulate_matches(K.CAM_MONO, K.CAM_MONO, k1, k1, RT[:9], far, SIG[0], SIG[0])
+    z, _ = oracle.triangulate_matches(synth.CAM_MONO, synth.CAM_MONO, k1, k1, RT[:9], far, SIG[0], SIG[0])
     assert z == -1
 
 
-def test_behind_camera_rejected(kt):
+def test_behind_camera_rejected(oracle):
     """the rays of a true correspondence with the baseline reversed meet behind both cameras"""
     for X in ([0.4, -0.2, 3.0], [-1.0, 0.5, 5.0]):
-        k1, k2 = _corr(kt, X)
-        z, _ = kt.triangulate_matches(K.CAM_MONO, K.CAM_MONO, k1, k2, RT[:9], RT[9:], SIG[0], SIG[0])
+        k1, k2 = _corr(oracle, X)
+        z, _ = oracle.triangulate_matches(synth.CAM_MONO, synth.CAM_MONO, k1, k2, RT[:9], RT[9:], SIG[0], SIG[0])
         assert z > 0
-        z, x3 = kt.triangulate_matches(K.CAM_MONO, K.CAM_MONO, k1, k2, RT[:9], -RT[9:], SIG[0], SIG[0])
+        z, x3 = oracle.triangulate_matches(synth.CAM_MONO, synth.CAM_MONO, k1, k2, RT[:9], -RT[9:], SIG[0], SIG[0])
         assert z == -1
 
 
-def test_reprojection_threshold(kt):
+def test_reprojection_threshold(oracle):
     """a kp2 shifted across the epipolar line (along y: the baseline is mostly along x): the largest passing shift lies between
     1x and 3x sqrt(5.991 sigma^2); just inside passes, just outside fails"""
-    k1, k2 = _corr(kt, [0.4, -0.2, 3.0])
+    k1, k2 = _corr(oracle, [0.4, -0.2, 3.0])
     sig = SIG[2]
 
     def ok(s):
         k = k2.copy(); k["y"] = np.float32(k2["y"] + s)
-        z, _ = kt.triangulate_matches(K.CAM_MONO, K.CAM_MONO, k1, k, RT[:9], RT[9:], SIG[0], sig)
+        z, _ = oracle.triangulate_matches(synth.CAM_MONO, synth.CAM_MONO, k1, k, RT[:9], RT[9:], SIG[0], sig)
         return z > np.float32(0.0001)
 
     lo, hi = 0.0, 20.0
@@ -119,22 +113,22 @@ def _pinhole_coarse(oracle, s, elig1, elig2, ori):
 
 @pytest.mark.parametrize("ori", [False, True])
 @pytest.mark.parametrize("stride", [32, 61])
-def test_mono_coarse_equals_pinhole_oracle(kt, oracle, ori, stride):
-    s = K.scene(seed=21, stride=stride)
-    n, m = kt.search(**s, coarse=True, checkOri=ori)
+def test_mono_coarse_equals_pinhole_oracle(oracle, ori, stride):
+    s = synth.keyframe_pair(seed=21, stride=stride)
+    n, m = oracle.search_for_triangulation_kb8(**s, coarse=True, checkOri=ori)
     on, om = _pinhole_coarse(oracle, s, s["elig1"], s["elig2"], ori)
     assert n > 20 and n == on and np.array_equal(m, om)
 
 
 @pytest.mark.parametrize("ori", [False, True])
-def test_twocam_coarse_equals_pinhole_oracle_without_epipole(kt, oracle, ori):
-    s = K.scene(seed=22, twocam=True)
-    n, m = kt.search(**s, coarse=True, checkOri=ori)
+def test_twocam_coarse_equals_pinhole_oracle_without_epipole(oracle, ori):
+    s = synth.keyframe_pair(seed=22, twocam=True)
+    n, m = oracle.search_for_triangulation_kb8(**s, coarse=True, checkOri=ori)
     on, om = _pinhole_coarse(oracle, s, s["elig1"] | 2, s["elig2"] | 2, ori)
     assert n > 20 and n == on and np.array_equal(m, om)
     # and the epipole test is really skipped: with it, the Pinhole oracle differs
     s["ep"] = np.array([s["kps2"]["x"][s["fv2"][2][0]], s["kps2"]["y"][s["fv2"][2][0]]], np.float32)
-    n2, m2 = kt.search(**s, coarse=True, checkOri=False)
+    n2, m2 = oracle.search_for_triangulation_kb8(**s, coarse=True, checkOri=False)
     on2, _ = _pinhole_coarse(oracle, s, s["elig1"], s["elig2"], False)
     n3, _ = _pinhole_coarse(oracle, s, s["elig1"] | 2, s["elig2"] | 2, False)
     assert n2 == n3 and on2 <= n3
@@ -144,56 +138,56 @@ def test_twocam_coarse_equals_pinhole_oracle_without_epipole(kt, oracle, ori):
 def _one_node(kps1, d1, kps2, d2, nleft1=-1, nleft2=-1):
     fv1 = (np.array([5], np.uint32), np.array([0, len(kps1)], np.int32), np.arange(len(kps1), dtype=np.int32))
     fv2 = (np.array([5], np.uint32), np.array([0, len(kps2)], np.int32), np.arange(len(kps2), dtype=np.int32))
-    return dict(kps1=np.array(kps1, K.KP), nleft1=nleft1, desc1=np.array(d1, np.uint8), elig1=np.ones(len(kps1), np.uint8), fv1=fv1,
-                kps2=np.array(kps2, K.KP), nleft2=nleft2, desc2=np.array(d2, np.uint8), elig2=np.ones(len(kps2), np.uint8), fv2=fv2)
+    return dict(kps1=np.array(kps1, synth.KP_DTYPE), nleft1=nleft1, desc1=np.array(d1, np.uint8), elig1=np.ones(len(kps1), np.uint8), fv1=fv1,
+                kps2=np.array(kps2, synth.KP_DTYPE), nleft2=nleft2, desc2=np.array(d2, np.uint8), elig2=np.ones(len(kps2), np.uint8), fv2=fv2)
 
 
-def _mono(kt, kps1, d1, kps2, d2, coarse=False):
+def _mono(oracle, kps1, d1, kps2, d2, coarse=False):
     s = _one_node(kps1, d1, kps2, d2)
-    scale, sig = K.level_tables()
-    return kt.search(**s, cams1=K.CAM_MONO, cams2=K.CAM_MONO, Rt=RT, ep=np.array([-1e4, -1e4], np.float32), scale2=scale,
-                     sigma2_1=sig, sigma2_2=sig, coarse=coarse, checkOri=False)
+    scale, sig = synth.level_tables()
+    return oracle.search_for_triangulation_kb8(**s, cams1=synth.CAM_MONO, cams2=synth.CAM_MONO, Rt=RT, ep=np.array([-1e4, -1e4], np.float32),
+                                               scale2=scale, sigma2_1=sig, sigma2_2=sig, coarse=coarse, checkOri=False)
 
 
 def _desc(rng, base, nbits):
-    return K._flip(base, nbits, rng)
+    return synth.flip_bits(base, nbits, rng)
 
 
-def test_last_wins_among_equal_distances(kt):
+def test_last_wins_among_equal_distances(oracle):
     rng = np.random.default_rng(1)
     base = rng.integers(0, 256, 32, dtype=np.uint8)
-    k1, k2 = _corr(kt, [0.4, -0.2, 3.0])
+    k1, k2 = _corr(oracle, [0.4, -0.2, 3.0])
     d = _desc(rng, base, 4)
-    n, m = _mono(kt, [k1], [base], [k2, k2, _kp(10.0, 10.0)], [d, d, d])
+    n, m = _mono(oracle, [k1], [base], [k2, k2, _kp(10.0, 10.0)], [d, d, d])
     assert n == 1 and m[0] == 1                                          # both pass at distance 4: the later one
-    n, m = _mono(kt, [k1], [base], [k2, k2, k2], [d, d, _desc(rng, base, 5)])
+    n, m = _mono(oracle, [k1], [base], [k2, k2, k2], [d, d, _desc(rng, base, 5)])
     assert n == 1 and m[0] == 1
 
 
-def test_farther_candidate_skipped(kt):
+def test_farther_candidate_skipped(oracle):
     """dist > bestDist: a later candidate that passes the geometry at a larger distance never replaces the best"""
     rng = np.random.default_rng(2)
     base = rng.integers(0, 256, 32, dtype=np.uint8)
-    k1, k2 = _corr(kt, [0.4, -0.2, 3.0])
+    k1, k2 = _corr(oracle, [0.4, -0.2, 3.0])
     near, far = _desc(rng, base, 3), _desc(rng, base, 9)
-    n, m = _mono(kt, [k1], [base], [k2, k2], [near, far])
+    n, m = _mono(oracle, [k1], [base], [k2, k2], [near, far])
     assert n == 1 and m[0] == 0
-    n, m = _mono(kt, [k1], [base], [k2, k2], [far, near])
+    n, m = _mono(oracle, [k1], [base], [k2, k2], [far, near])
     assert n == 1 and m[0] == 1
     # a closer candidate that fails the geometry does not block a farther one that passes
-    n, m = _mono(kt, [k1], [base], [k2, _kp(20.0, 200.0)], [far, near])
+    n, m = _mono(oracle, [k1], [base], [k2, _kp(20.0, 200.0)], [far, near])
     assert n == 1 and m[0] == 0
 
 
 @pytest.mark.parametrize("b1", [0, 1])
 @pytest.mark.parametrize("b2", [0, 1])
-def test_pose_pairing_by_index(kt, b1, b2):
+def test_pose_pairing_by_index(oracle, b1, b2):
     """two-camera keyframes: the pose and cameras come from (idx1 >= Nleft1, idx2 >= Nleft2): ll, lr, rl, rr (:1107-1137)"""
     rng = np.random.default_rng(3 + 2 * b1 + b2)
     base = rng.integers(0, 256, 32, dtype=np.uint8)
-    cams = (K.CAM_L, K.CAM_R)
+    cams = (synth.CAM_L, synth.CAM_R)
     Rt = RT.copy()
-    k1, k2 = _corr(kt, [0.3, 0.1, 2.5], cams[b1], cams[b2], Rt)
+    k1, k2 = _corr(oracle, [0.3, 0.1, 2.5], cams[b1], cams[b2], Rt)
     filler = _kp(5.0, 5.0)
     kps1 = [k1, filler] if b1 == 0 else [filler, k1]                   # nleft1 = 1: index 1 is the right camera
     kps2 = [k2, filler] if b2 == 0 else [filler, k2]
@@ -201,11 +195,11 @@ def test_pose_pairing_by_index(kt, b1, b2):
     d1 = [base, junk] if b1 == 0 else [junk, base]
     d2 = [_desc(rng, base, 2), junk] if b2 == 0 else [junk, _desc(rng, base, 2)]
     s = _one_node(kps1, d1, kps2, d2, nleft1=1, nleft2=1)
-    scale, sig = K.level_tables()
+    scale, sig = synth.level_tables()
     zero = np.concatenate([np.eye(3, dtype=np.float32).reshape(9), np.zeros(3, np.float32)])
     for pose in range(4):
         R4 = np.concatenate([Rt if p == pose else zero for p in range(4)])
-        n, m = kt.search(**s, cams1=cams, cams2=cams, Rt=R4, ep=np.array([0, 0], np.float32), scale2=scale, sigma2_1=sig,
-                         sigma2_2=sig, checkOri=False)
+        n, m = oracle.search_for_triangulation_kb8(**s, cams1=cams, cams2=cams, Rt=R4, ep=np.array([0, 0], np.float32), scale2=scale,
+                                                   sigma2_1=sig, sigma2_2=sig, checkOri=False)
         want = pose == 2 * b1 + b2
         assert (n == 1 and m[b1] == b2) if want else n == 0, (pose, n, m)

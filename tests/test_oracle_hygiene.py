@@ -15,7 +15,8 @@ sys.path.insert(0, ROOT)
 def test_timing_build_equals_parity_build():
     """liboracle_fast.so (-O3 -march=native, bench.py's cpu_baseline and the full-size GPU tests) against liboracle.so (-O2, the
     parity build): one 200 000-event slice -> f32 image, extremes, u8 image; ORB-1000 on two such images; SearchForInitialization
-    between them; brute-force 2-NN.  Bit for bit."""
+    between them; brute-force 2-NN; the two-camera SearchByProjection(F, map points) and the KannalaBrandt8 SearchForTriangulation
+    on a two-camera keyframe pair.  Bit for bit."""
     from oracle import oracle_py as o
     from eorb_slam_amd import synth
     W, H = 240, 180
@@ -47,6 +48,14 @@ def test_timing_build_equals_parity_build():
     assert out[0][0] == out[1][0] and np.array_equal(out[0][1], out[1][1])
     for x, y in zip(out[0][2], out[1][2]):
         assert np.array_equal(x, y)
+    s = synth.keyframe_pair(seed=40, twocam=True)
+    kps, desc, nL = s["kps1"], s["desc1"], s["nleft1"]
+    left, right, mp_desc, mp_obs = synth.map_inputs(kps, nL, s["scale2"], np.random.default_rng(5), src=(kps, desc))
+    free = np.full(len(kps), -1, np.int32)
+    out = [(o.search_by_projection_map_fisheye(kps, nL, desc, o.grid_bounds(512, 512), free[:nL], free[nL:], left, right, mp_desc, mp_obs,
+                                               free, 3.0, 0.8, fast=fast), o.search_for_triangulation_kb8(**s, fast=fast)) for fast in (False, True)]
+    for (n, m), (fn, fm) in zip(out[0], out[1]):
+        assert n == fn > 500 and np.array_equal(m, fm)
 
 
 def _sanitizer_lib(name):
@@ -55,16 +64,17 @@ def _sanitizer_lib(name):
 
 
 def test_oracle_is_clean_under_asan_and_ubsan():
-    """make -C oracle asan, then the known-answer and golden tests of the oracle run against that build (every ctypes call into it:
-    heap / stack overflows, use after free, signed overflow, misaligned or out-of-range accesses abort the child process)."""
+    """make -C oracle asan, then the known-answer, golden, two-camera and KB8 triangulation tests of the oracle run against that build
+    (every ctypes call into it: heap / stack overflows, use after free, signed overflow, misaligned or out-of-range accesses abort the
+    child process)."""
     libasan = _sanitizer_lib("libasan.so")
     if not libasan:
         pytest.skip("no libasan")
     env = dict(os.environ, EORB_ORACLE_VARIANT="asan", LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider",
-                        os.path.join(ROOT, "tests", "test_oracle_kat.py"), os.path.join(ROOT, "tests", "test_golden.py"),
-                        os.path.join(ROOT, "tests", "test_golden_v2.py")], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
+    files = ("test_oracle_kat.py", "test_golden.py", "test_golden_v2.py", "test_twocam_oracle.py", "test_kb8tri_oracle.py")
+    p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider"] +
+                       [os.path.join(ROOT, "tests", f) for f in files], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     tail = (p.stdout + p.stderr)[-3000:]
     assert p.returncode == 0, tail
     assert "AddressSanitizer" not in p.stdout + p.stderr and "runtime error" not in p.stdout + p.stderr, tail

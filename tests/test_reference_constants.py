@@ -64,7 +64,7 @@ def test_matcher_constants_equal_reference():
     prod = _read(ROOT, "eorb_slam_amd/csrc/match.hip")
     m = re.search(r"constexpr int TH_HIGH = (\d+), TH_LOW = (\d+), HISTO_LENGTH = (\d+);", prod)
     assert m and tuple(int(g) for g in m.groups()) == th
-    orc = _read(ROOT, "oracle/orc_match.c")
+    orc = _read(ROOT, "oracle/orc_matcher.h")                         # the oracle's matchers (orc_match.c, orc_twocam.c) include it
     assert (_const(orc, r"#define TH_HIGH (\d+)"), _const(orc, r"#define TH_LOW (\d+)"), _const(orc, r"#define HISTO_LENGTH (\d+)")) == th
     assert ref["mixed_matcher_uses_class_constants"]                    # the Mixed variants (src/MixedMatcher.cpp) use the same class constants
 
@@ -75,7 +75,7 @@ def test_frame_grid_equals_reference():
     assert (rows, cols) == (48, 64)
     ctxh = _read(ROOT, "eorb_slam_amd/csrc/eorb_ctx.h")
     assert _const(ctxh, r"constexpr int kGridCols = (\d+);") == cols and _const(ctxh, r"constexpr int kGridRows = (\d+);") == rows
-    orc = _read(ROOT, "oracle/orc_match.c")
+    orc = _read(ROOT, "oracle/orc_matcher.h")
     assert _const(orc, r"#define FRAME_GRID_ROWS (\d+)") == rows and _const(orc, r"#define FRAME_GRID_COLS (\d+)") == cols
 
 

@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
 """Per-call latency of eorb_search_for_triangulation_kb8 (SearchForTriangulation with a KannalaBrandt8 pCamera1) and the KB8
-triangulation oracle's time for the same call on one core.  Prints one JSON object (and writes it to --out).
+oracle's time for the same call on one core (its timing build, -O3 -march=native, as bench.py's cpu_baseline).  Prints one JSON
+object (and writes it to --out).
 
   twocam   two-camera keyframes on 512 x 512 (about 1 000 left + 1 000 right features per keyframe), bCoarse = 0, checkOri
   mono     monocular keyframes on 346 x 260 (MVSEC sized, about 1 500 features per keyframe), bCoarse = 0, checkOri
 
-The keyframe pairs are tests/kb8tri's synthetic scenes (3D points seen by both keyframes, near-duplicate descriptors, distractors).
+The keyframe pairs are synth.keyframe_pair's scenes (3D points seen by both keyframes, near-duplicate descriptors, distractors).
 Run it under `rocprofv3 --kernel-trace --stats -d DIR -o kb8tri -- python tools/kb8tri_latency.py` for the kernel summary."""
-import argparse, json, os, sys, tempfile
+import argparse, json, os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 def main():
@@ -19,14 +20,12 @@ def main():
     ap.add_argument("--cpu-calls", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    from eorb_slam_amd import frontend as fe
+    from eorb_slam_amd import frontend as fe, synth
     from oracle import oracle_py as oracle
-    from kb8tri import oracle_kt as K
     from twocam_latency import _med, _sources_hash
-    kt = K.KB8TriOracle(tempfile.mkdtemp(), oracle)
     ctx = fe.Context()
-    scenes = {"twocam": K.scene(seed=40, twocam=True, npts=980, ndistract=260, nnodes=250),
-              "mono": K.scene(seed=41, npts=1950, ndistract=230, nnodes=250)}
+    scenes = {"twocam": synth.keyframe_pair(seed=40, twocam=True, npts=980, ndistract=260, nnodes=250),
+              "mono": synth.keyframe_pair(seed=41, npts=1950, ndistract=230, nnodes=250)}
     res = {"sources_hash": _sources_hash(), "sizes": {}, "gpu": {}, "oracle_1core": {}}
     for name, s in scenes.items():
         def g():
@@ -35,7 +34,7 @@ def main():
                                                 s["sigma2_1"], s["sigma2_2"], False, True, ctx=ctx)
 
         def c():
-            return kt.search(**s, coarse=False, checkOri=True)
+            return oracle.search_for_triangulation_kb8(**s, coarse=False, checkOri=True, fast=True)
         gn, _ = g()
         on, _ = c()
         assert gn == on
