@@ -73,6 +73,9 @@ struct OrbState {
     int oct_dyn[2] = {0, 0}, oct_dyn_lds[2] = {0, 0};   // dynamic placement in use (its direct-pass cap, -1: none), its LDS bytes
     int oct_all_lds[2] = {0, 0};   // every item of that placement is in LDS: the kernel variant with LDS-typed pointers
     int oct_scratch[2] = {0, 0};   // per (slice, level) global scratch bytes
+    // what the last call left in the context's pyr / blur / cell_cnt / cell_cand buffers (eorb_debug_stage): its slices (0: nothing),
+    // whether it blurred the levels, whether it ran FAST
+    int last_B = 0; bool last_blur = false, last_cells = false;
     DevBuf tabs;             // resize tables (short/int), level geometry, pattern, umax
     DevBuf geom;
 };
@@ -232,6 +235,7 @@ int stereo_match_dev(eorb_ctx* c, const eorb_keypoint* d_kps, const uint8_t* d_d
 int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t img_slice_bytes, int B, int lap0, int lap1,
                     int want_desc, eorb_keypoint* d_kps, uint8_t* d_desc, uint8_t* d_oob, int32_t* d_n, int32_t* d_mono,
                     int32_t* d_flag_out = nullptr);      // d_flag_out: receives the overflow flag of this extraction (host entry point)
+int orb_debug_stage(eorb_ctx* c, const char* name, int slice, int level, void* out, size_t cap_bytes, int* dim0, int* dim1);
 // match.hip
 int search_init_dev(eorb_ctx* c, int npairs,
                     const eorb_keypoint* kps1, const int32_t* n1, size_t kp1_stride, const uint8_t* desc1, int dstride1, size_t desc1_slice,

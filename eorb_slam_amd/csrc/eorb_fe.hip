@@ -444,6 +444,13 @@ int eorb_debug_option(eorb_ctx* c, const char* name, int value)
     return set_err(c, EORB_E_ARG, "debug option '%s' unknown", name);
 }
 
+int eorb_debug_stage(eorb_ctx* c, const char* name, int slice, int level, void* out, size_t cap_bytes, int* dim0, int* dim1)
+{
+    if (!c || !name) return EORB_E_ARG;
+    fe_enter(c);
+    return orb_debug_stage(c, name, slice, level, out, cap_bytes, dim0, dim1);
+}
+
 long long eorb_debug_counter(eorb_ctx* c, const char* name)
 {
     if (!c || !name) return -1;

@@ -1502,7 +1502,7 @@ static int cv_round_d(double v) { return (int)lrint(v); }
 int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H)
 {
     OrbState& o = c->orb;
-    o.configured = false;
+    o.configured = false; o.last_B = 0;
     if (!p || p->nlevels < 1 || p->nlevels > kMaxLevels || W <= 0 || H <= 0 || p->nfeatures < 0)
         return set_err(c, EORB_E_ARG, "orb_configure: bad parameters");
     o.p = *p; o.W = W; o.H = H; o.nlevels = p->nlevels;
@@ -1714,6 +1714,7 @@ int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t im
     const DevGeom* G = (const DevGeom*)o.geom.p;
     uint8_t* pyr = (uint8_t*)c->pyr.p;
     int32_t* err_flag = (int32_t*)((char*)c->lvl_cnt.p + nb * o.nlevels * sizeof(int32_t));
+    o.last_B = B; o.last_blur = want_desc != 0; o.last_cells = true;
     {
         ProfScope ps(c, "orb_pyr");
         const int n0 = o.lv[0].bw * o.lv[0].bh;
@@ -1803,6 +1804,58 @@ int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t im
     return EORB_OK;
 }
 
+// eorb_debug_stage: what the last extraction left in the context's workspaces, copied to the host.  Reads only: no kernel, no
+// allocation on the device.
+int orb_debug_stage(eorb_ctx* c, const char* name, int slice, int level, void* out, size_t cap_bytes, int* dim0, int* dim1)
+{
+    OrbState& o = c->orb;
+    if (!o.configured || o.last_B <= 0) return set_err(c, EORB_E_NOTCONF, "debug_stage: no extraction since the last eorb_orb_configure");
+    if (slice < 0 || slice >= o.last_B) return set_err(c, EORB_E_ARG, "debug_stage: slice %d outside the last call's %d", slice, o.last_B);
+    if (level < 0 || level >= o.nlevels) return set_err(c, EORB_E_ARG, "debug_stage: level %d outside [0, %d)", level, o.nlevels);
+    const LevelGeom& L = o.lv[level];
+    EORB_HIP(c, hipStreamSynchronize(c->stream));
+    const bool is_pyr = !strcmp(name, "pyr"), is_blur = !strcmp(name, "blur");
+    if (is_pyr || is_blur) {
+        if (is_blur && !o.last_blur) return set_err(c, EORB_E_ARG, "debug_stage: the last call computed no descriptors, its levels are not blurred");
+        const int d0 = is_pyr ? L.bh : L.h, d1 = is_pyr ? L.bw : L.w;
+        if (dim0) *dim0 = d0;
+        if (dim1) *dim1 = d1;
+        if (!out) return EORB_OK;
+        const size_t bytes = (size_t)d0 * d1;
+        if (cap_bytes < bytes) return set_err(c, EORB_E_ARG, "debug_stage: '%s' of level %d needs %zu bytes, %zu given", name, level, bytes, cap_bytes);
+        const uint8_t* src = is_pyr ? (const uint8_t*)c->pyr.p + (size_t)slice * o.pyr_bytes + L.buf_off
+                                    : (const uint8_t*)c->blur.p + (size_t)slice * o.roi_bytes + L.roi_off;
+        EORB_HIP(c, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+        return EORB_OK;
+    }
+    if (!strcmp(name, "cand")) {
+        if (!o.last_cells) return set_err(c, EORB_E_ARG, "debug_stage: the last call built the pyramid only, it detected no corners");
+        const int nc = L.nCols * L.nRows;
+        std::vector<int32_t> cnt((size_t)nc);
+        std::vector<uint32_t> cand((size_t)nc * o.cell_cap);
+        const size_t cell0 = (size_t)slice * o.ncells + L.cell_off;
+        EORB_HIP(c, hipMemcpy(cnt.data(), (const int32_t*)c->cell_cnt.p + cell0, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        EORB_HIP(c, hipMemcpy(cand.data(), (const uint32_t*)c->cell_cand.p + cell0 * o.cell_cap, cand.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        size_t total = 0;
+        for (int i = 0; i < nc; i++) total += (size_t)std::min(std::max(cnt[i], 0), o.cell_cap);
+        if (dim0) *dim0 = (int)total;
+        if (dim1) *dim1 = 3;
+        if (!out) return EORB_OK;
+        if (cap_bytes < total * 3 * sizeof(float))
+            return set_err(c, EORB_E_ARG, "debug_stage: 'cand' of level %d needs %zu bytes, %zu given", level, total * 3 * sizeof(float), cap_bytes);
+        float* rec = (float*)out;
+        for (int i = 0; i < nc; i++) {
+            const int n = std::min(std::max(cnt[i], 0), o.cell_cap);
+            for (int k = 0; k < n; k++) {       // fast_cells_kernel's record: x | y << 12 | score << 24, relative to the level's minimum border
+                const uint32_t v = cand[(size_t)i * o.cell_cap + k];
+                *rec++ = (float)(v & 0xfffu); *rec++ = (float)((v >> 12) & 0xfffu); *rec++ = (float)(v >> 24);
+            }
+        }
+        return EORB_OK;
+    }
+    return set_err(c, EORB_E_ARG, "debug_stage: stage '%s' unknown (pyr, blur, cand)", name);
+}
+
 // pyramid + blurred planes of ONE image (the front half of operator(), shared by the tracked-keypoint helpers)
 int orb_pyramid_blur_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride)
 {
@@ -1813,6 +1866,7 @@ int orb_pyramid_blur_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride)
     if ((rc = ensure(c, c->blur, (size_t)o.roi_bytes))) return rc;
     const DevGeom* G = (const DevGeom*)o.geom.p;
     uint8_t* pyr = (uint8_t*)c->pyr.p;
+    o.last_B = 1; o.last_blur = true; o.last_cells = false;
     ProfScope ps(c, "orb_pyr_blur");
     const int n0 = o.lv[0].bw * o.lv[0].bh;
     pyr_level0_kernel<<<dim3((n0 + 255) / 256, 1), 256, 0, c->stream>>>(d_img, img_stride, 0, G, pyr, nullptr);

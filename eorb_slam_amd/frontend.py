@@ -64,6 +64,16 @@ class Context:
     def debug_counter(self, name):
         return int(self.L.eorb_debug_counter(self.h, name.encode()))
 
+    def debug_stage(self, name, level, slice=0):
+        """Test hook, not part of the reference's interface: a stage of the last extraction (eorb_debug_stage).  "pyr": the bordered
+        level buffer (bh, bw) u8; "blur": the blurred level (h, w) u8; "cand": the level's FAST candidates (n, 3) f32 = x, y, response."""
+        d0, d1 = C.c_int(0), C.c_int(0)
+        self.check(self.L.eorb_debug_stage(self.h, name.encode(), int(slice), int(level), None, 0, C.byref(d0), C.byref(d1)))
+        out = np.zeros((d0.value, d1.value), np.float32 if name == "cand" else np.uint8)
+        self.check(self.L.eorb_debug_stage(self.h, name.encode(), int(slice), int(level), out.ctypes.data_as(C.c_void_p), out.nbytes,
+                                           C.byref(d0), C.byref(d1)))
+        return out
+
     # profiling ------------------------------------------------------------------------------------
     def prof_enable(self, on=True):
         self.check(self.L.eorb_prof_enable(self.h, int(on)))

@@ -118,6 +118,19 @@ int         eorb_debug_option(eorb_ctx* ctx, const char* name, int value);
  * the register-row kernel (synchronises); "slot_rank_ok": 1 when the scatter takes its ranks from LDS atomics.
  * Returns the value, or -1 for an unknown name. */
 long long   eorb_debug_counter(eorb_ctx* ctx, const char* name);
+/* test hook, not part of the reference's interface: the intermediate images of the extractor, for stage-by-stage comparison with
+ * the CPU oracle.  Waits for the ctx stream, then copies what the LAST extraction of the context left in its workspaces:
+ *   "pyr"   the bordered buffer of pyramid level `level`, bh rows of bw bytes (bw = w + 2 * edge).  The kernels write the WHOLE
+ *           bordered buffer (level 0 and every resized level, BORDER_REFLECT_101 included), so all of it is comparable;
+ *   "blur"  the blurred level the descriptors read, h rows of w bytes; EORB_E_ARG when that call computed no descriptors;
+ *   "cand"  the level's FAST candidates after the per-cell iniThFAST / minThFAST rule, i.e. the octree's input: dim0 records of
+ *           three floats (x, y, response), x and y relative to the level's minimum border like the reference's vToDistributeKeys,
+ *           in no particular order; EORB_E_ARG after eorb_orb_tracked_descriptors / _assign_level_by_best_desc (pyramid only).
+ * slice: the frame of a batched call (eorb_fe_run_batch_*), the image of eorb_frame_stereo (0 left, 1 right); 0 otherwise.
+ * dim0 / dim1 (may be NULL) receive rows / columns ("cand": records / 3).  out == NULL: only the dimensions are returned.
+ * Unknown name, level or slice out of range, cap_bytes too small: EORB_E_ARG; no extraction since the last eorb_orb_configure:
+ * EORB_E_NOTCONF.  The hook launches nothing and allocates nothing on the device, and the extractor keeps no buffer for it. */
+int         eorb_debug_stage(eorb_ctx* ctx, const char* name, int slice, int level, void* out, size_t cap_bytes, int* dim0, int* dim1);
 const char* eorb_last_error(eorb_ctx* ctx);
 const char* eorb_version(void);
 /* per-kernel HIP-event timing on the ctx stream (off by default; used by bench.py) */

@@ -64,7 +64,7 @@ def _sanitizer_lib(name):
 
 
 def test_oracle_is_clean_under_asan_and_ubsan():
-    """make -C oracle asan, then the known-answer, golden, two-camera and KB8 triangulation tests of the oracle run against that build
+    """make -C oracle asan, then the known-answer, stage, golden, two-camera and KB8 triangulation tests of the oracle run against that build
     (every ctypes call into it: heap / stack overflows, use after free, signed overflow, misaligned or out-of-range accesses abort the
     child process)."""
     libasan = _sanitizer_lib("libasan.so")
@@ -72,7 +72,7 @@ def test_oracle_is_clean_under_asan_and_ubsan():
         pytest.skip("no libasan")
     env = dict(os.environ, EORB_ORACLE_VARIANT="asan", LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    files = ("test_oracle_kat.py", "test_golden.py", "test_golden_v2.py", "test_twocam_oracle.py", "test_kb8tri_oracle.py")
+    files = ("test_oracle_kat.py", "test_oracle_stages.py", "test_golden.py", "test_golden_v2.py", "test_twocam_oracle.py", "test_kb8tri_oracle.py")
     p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider"] +
                        [os.path.join(ROOT, "tests", f) for f in files], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     tail = (p.stdout + p.stderr)[-3000:]
