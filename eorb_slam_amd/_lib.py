@@ -14,6 +14,7 @@ EXPORTS = [
     "eorb_create", "eorb_destroy", "eorb_sync", "eorb_debug_option", "eorb_debug_counter", "eorb_debug_stage", "eorb_last_error", "eorb_version",
     "eorb_prof_enable", "eorb_prof_reset", "eorb_prof_only", "eorb_prof_count", "eorb_prof_get",
     "eorb_ev2im", "eorb_ev2im_gauss", "eorb_set_undistort_maps", "eorb_undistort_events", "eorb_parse_events_text", "eorb_ev2im_gauss_raw", "eorb_ev2im_raw", "eorb_fe_run_batch_raw_dev", "eorb_fe_run_batch_raw4_dev", "eorb_fe_run_batch_raw2_dev", "eorb_fe_run_batch_images_dev", "eorb_ev2mci_se3", "eorb_ev2mci_se2", "eorb_ev2mci_se3_cam", "eorb_ev2mci_se2_cam", "eorb_measure_image_focus", "eorb_measure_image_focus_n", "eorb_normalize_minmax_u8",
+    "eorb_set_calibration", "eorb_undistort_keypoints", "eorb_undistort_points", "eorb_generate_undistort_maps", "eorb_frame_mono",
     "eorb_orb_configure", "eorb_orb_max_keypoints", "eorb_orb_get_tables", "eorb_orb_extract",
     "eorb_search_for_initialization", "eorb_search_by_projection_last", "eorb_search_by_projection_map", "eorb_search_by_projection_kf", "eorb_search_by_projection_last_stereo", "eorb_search_by_projection_map_stereo", "eorb_frame_stereo",
     "eorb_frame_fisheye", "eorb_search_by_projection_map_fisheye", "eorb_search_by_projection_last_fisheye", "eorb_search_by_bow_fisheye",
@@ -50,6 +51,38 @@ def camera(cam):
             c.k[i] = float(cam[4 + i])
         c.precision = float(cam[8]) if len(cam) > 8 else 1e-6
     return c
+
+
+class Calib(C.Structure):
+    """eorb_calib: MyCalibrator's K, distortion coefficients, R and P (src/Utils/MyCalibrator.cpp:11-17)"""
+    _fields_ = [("model", C.c_int), ("K", C.c_float * 9), ("dist", C.c_float * 8), ("n_dist", C.c_int),
+                ("R", C.c_float * 9), ("has_R", C.c_int), ("P", C.c_float * 12), ("p_cols", C.c_int)]
+
+
+def calib(model, K, dist, R=None, P=None):
+    """model 0 pinhole / 1 fisheye, K 3x3, dist (4, 5 or 8 / 4 coefficients), R 3x3 or None (cv::Mat()), P 3x3 / 3x4 or None"""
+    import numpy as np
+    q = Calib()
+    q.model = int(model)
+    K = np.asarray(K, np.float32).reshape(9)
+    dist = np.asarray(dist, np.float32).reshape(-1)
+    for i in range(9):
+        q.K[i] = float(K[i])
+    for i in range(min(len(dist), 8)):
+        q.dist[i] = float(dist[i])
+    q.n_dist = len(dist)
+    if R is not None:
+        R = np.asarray(R, np.float32).reshape(9)
+        for i in range(9):
+            q.R[i] = float(R[i])
+        q.has_R = 1
+    if P is not None:
+        P = np.asarray(P, np.float32)
+        q.p_cols = int(P.shape[1])
+        P = P.reshape(-1)
+        for i in range(min(len(P), 12)):
+            q.P[i] = float(P[i])
+    return q
 
 
 class KltParams(C.Structure):
@@ -151,6 +184,12 @@ def lib():
     L.eorb_measure_image_focus.restype = ci; L.eorb_measure_image_focus.argtypes = [vp, vp, ci, ci, C.POINTER(cf)]
     L.eorb_measure_image_focus_n.restype = ci; L.eorb_measure_image_focus_n.argtypes = [vp, vp, ci, ci, ci, vp]
     L.eorb_normalize_minmax_u8.restype = ci; L.eorb_normalize_minmax_u8.argtypes = [vp, vp, ci, ci, vp]
+    L.eorb_set_calibration.restype = ci; L.eorb_set_calibration.argtypes = [vp, C.POINTER(Calib)]
+    L.eorb_undistort_keypoints.restype = ci; L.eorb_undistort_keypoints.argtypes = [vp, vp, ci, vp]
+    L.eorb_undistort_points.restype = ci; L.eorb_undistort_points.argtypes = [vp, vp, ci, vp]
+    L.eorb_generate_undistort_maps.restype = ci; L.eorb_generate_undistort_maps.argtypes = [vp, ci, ci, ci, vp, vp]
+    L.eorb_frame_mono.restype = ci
+    L.eorb_frame_mono.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, pi, pi, vp]
     L.eorb_orb_configure.restype = ci; L.eorb_orb_configure.argtypes = [vp, C.POINTER(OrbParams), ci, ci]
     L.eorb_orb_max_keypoints.restype = ci; L.eorb_orb_max_keypoints.argtypes = [vp]
     L.eorb_orb_get_tables.restype = ci; L.eorb_orb_get_tables.argtypes = [vp, vp, vp, vp, pi]

@@ -80,6 +80,15 @@ struct OrbState {
     DevBuf geom;
 };
 
+// eorb_set_calibration in the form the kernels of calib.hip take by value: everything widened to double on the host once, RR = P(3x3) * R
+// (cv::undistortPoints / cv::fisheye::undistortPoints)
+struct CalibDev {
+    int model, gate;         // gate: MyCalibrator::isDistorted (:46-50) for the point calls, dist[0] != 0.0 for ComputeImageBounds
+    double fx, fy, cx, cy, ifx, ify;
+    double k[12];            // k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 (absent: 0); fisheye: k[0..3]
+    double RR[9];
+};
+
 }  // namespace eorb
 
 struct eorb_ctx {
@@ -148,6 +157,8 @@ struct eorb_ctx {
     eorb::DevBuf l1_ref_img, l1_ref_pts;
     int l1_nref = -1, l1_W = 0, l1_H = 0;
     size_t l1_img_off = 0; unsigned long long arena_gen = 0, l1_img_gen = 0;      // the last slice's u8 image inside the arena (eorb_ev_slice_image)
+    // eorb_set_calibration: the caller's record, its device form, and the form Frame::ComputeImageBounds uses (pinhole, R = I, P = K)
+    bool calib_set = false; eorb_calib calib{}; eorb::CalibDev calib_dev{}, calib_bounds{};
     // DBoW2 vocabulary (device copy) for eorb_bow_transform
     eorb::DevBuf voc;
     int voc_nnodes = 0, voc_L = 0; size_t voc_off[5] = {0, 0, 0, 0, 0};
@@ -236,6 +247,10 @@ int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t im
                     int want_desc, eorb_keypoint* d_kps, uint8_t* d_desc, uint8_t* d_oob, int32_t* d_n, int32_t* d_mono,
                     int32_t* d_flag_out = nullptr);      // d_flag_out: receives the overflow flag of this extraction (host entry point)
 int orb_debug_stage(eorb_ctx* c, const char* name, int slice, int level, void* out, size_t cap_bytes, int* dim0, int* dim1);
+// calib.hip
+int calib_points_dev(eorb_ctx* c, const CalibDev& P, const float* d_in, float* d_out, int n, int rec_floats);
+int calib_frame_dev(eorb_ctx* c, const eorb_keypoint* d_kps, const int32_t* d_n, int cap, eorb_keypoint* d_un, float* d_bounds, int W, int H);
+int calib_maps_dev(eorb_ctx* c, int LW, int LH, float* d_lut, float* d_mx, float* d_my);
 // match.hip
 int search_init_dev(eorb_ctx* c, int npairs,
                     const eorb_keypoint* kps1, const int32_t* n1, size_t kp1_stride, const uint8_t* desc1, int dstride1, size_t desc1_slice,

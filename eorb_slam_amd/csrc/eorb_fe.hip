@@ -675,6 +675,14 @@ int eorb_ev2im_gauss(eorb_ctx* c, const eorb_event* ev, size_t n, int W, int H, 
 }
 
 // ---- raw sensor events + undistortion maps ----------------------------------------------------------
+// the maps are in c->lut (uploaded, or written there by calib_maps_dev): everything derived from them is stale
+static int install_maps(eorb_ctx* c, int LW, int LH, int checkInImage)
+{
+    c->lut_w = LW; c->lut_h = LH; c->lut_check = checkInImage != 0;
+    c->lut_key_W = c->lut_key_H = c->lut_key_mode = -1; c->lut_key_sigma = -1.f;      // derived tables are stale
+    return EORB_OK;
+}
+
 int eorb_set_undistort_maps(eorb_ctx* c, const float* mapX, const float* mapY, int LW, int LH, int checkInImage)
 {
     if (!c) return EORB_E_ARG;
@@ -687,9 +695,60 @@ int eorb_set_undistort_maps(eorb_ctx* c, const float* mapX, const float* mapY, i
             float* xy = (float*)hp;
             for (size_t i = 0; i < n; i++) { xy[2 * i] = mapX[i]; xy[2 * i + 1] = mapY[i]; }
         }))) return rc;
-    c->lut_w = LW; c->lut_h = LH; c->lut_check = checkInImage != 0;
-    c->lut_key_W = c->lut_key_H = c->lut_key_mode = -1; c->lut_key_sigma = -1.f;      // derived tables are stale
-    return EORB_OK;
+    return install_maps(c, LW, LH, checkInImage);
+}
+
+// MyCalibrator::generateUndistMaps (src/Utils/MyCalibrator.cpp:52-102) on the device: the kernel writes c->lut, install_maps does the rest
+int eorb_generate_undistort_maps(eorb_ctx* c, int LW, int LH, int checkInImage, float* mapX, float* mapY)
+{
+    if (!c) return EORB_E_ARG;
+    if (!c->calib_set) return set_err(c, EORB_E_NOTCONF, "generate_undistort_maps: eorb_set_calibration not called");
+    if (LW <= 0 || LH <= 0 || LW > 65535 || LH > 65535 || (int64_t)LW * LH >= (1ll << 31) || (mapX == nullptr) != (mapY == nullptr))
+        return set_err(c, EORB_E_ARG, "generate_undistort_maps: bad arguments");
+    fe_enter(c);
+    const size_t n = (size_t)LW * LH;
+    int rc;
+    if ((rc = ensure(c, c->lut, sizeof(float) * 2 * n))) return rc;
+    Arena A(c);
+    const size_t o_x = A.reserve(mapX ? sizeof(float) * n : 0), o_y = A.reserve(mapX ? sizeof(float) * n : 0);
+    if ((rc = A.upload())) return rc;
+    if ((rc = calib_maps_dev(c, LW, LH, (float*)c->lut.p, mapX ? A.dev<float>(o_x) : nullptr, mapX ? A.dev<float>(o_y) : nullptr))) return rc;
+    if (mapX) {
+        const char* h;
+        if ((rc = A.download(o_x, o_y + sizeof(float) * n - o_x, &h))) return rc;
+        memcpy(mapX, h + o_x, sizeof(float) * n);
+        memcpy(mapY, h + o_y, sizeof(float) * n);
+    } else
+        EORB_HIP(c, fe_stream_sync(c));
+    return install_maps(c, LW, LH, checkInImage);
+}
+
+// MyCalibrator::undistKeyPoints* (:198-283) / undistPoint* (:119-156): records of rec_floats floats whose first two are the point
+static int undistort_common(eorb_ctx* c, const char* who, const float* in, int n, float* out, int rec_floats)
+{
+    if (!c) return EORB_E_ARG;
+    if (n < 0 || (n && (!in || !out))) return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
+    if (!n) return EORB_OK;                                   // empty vector: nothing to do (:202-205)
+    if (!c->calib_set) return set_err(c, EORB_E_NOTCONF, "%s: eorb_set_calibration not called", who);
+    const size_t bytes = sizeof(float) * rec_floats * (size_t)n;
+    if (!c->calib_dev.gate) { if (out != in) memmove(out, in, bytes); return EORB_OK; }      // vUndistKPts = vDistKPts (:206-210)
+    fe_enter(c);
+    int rc;
+    Arena A(c);
+    const size_t o_in = A.in(in, bytes), o_out = A.reserve(bytes);
+    if ((rc = A.upload())) return rc;
+    if ((rc = calib_points_dev(c, c->calib_dev, A.dev<float>(o_in), A.dev<float>(o_out), n, rec_floats))) return rc;
+    return A.download_to(out, o_out, bytes);
+}
+
+int eorb_undistort_keypoints(eorb_ctx* c, const eorb_keypoint* in, int n, eorb_keypoint* out)
+{
+    return undistort_common(c, "undistort_keypoints", (const float*)in, n, (float*)out, 7);
+}
+
+int eorb_undistort_points(eorb_ctx* c, const float* xy, int n, float* xy_out)
+{
+    return undistort_common(c, "undistort_points", xy, n, xy_out, 2);
 }
 
 int eorb_undistort_events(eorb_ctx* c, const eorb_raw_event* raw, size_t n, int W, int H, double tsFactor, eorb_event* out, size_t* n_out)
@@ -1230,6 +1289,67 @@ int eorb_orb_extract(eorb_ctx* c, const uint8_t* img, int W, int H, int stride, 
         if (kps) memcpy(kps, h + o_kp, sizeof(eorb_keypoint) * (size_t)hn[0]);
         if (want_desc && desc) memcpy(desc, h + o_desc, 32 * (size_t)hn[0]);
         if (oob) memcpy(oob, h + o_oob, (size_t)hn[0]);
+    }
+    if (n_out) *n_out = hn[0];
+    if (mono_index) *mono_index = hn[1];
+    return EORB_OK;
+}
+
+// Frame::Frame(imGray, ...) (src/Frame.cc:229-266): eorb_orb_extract with undistKeyPoints (:246-252) and ComputeImageBounds (:840-867)
+// behind the extraction on the device -- the keypoints do not cross the link in between
+int eorb_frame_mono(eorb_ctx* c, const uint8_t* img, int W, int H, int stride, int lap0, int lap1, int want_desc,
+                    eorb_keypoint* kps, eorb_keypoint* kps_un, uint8_t* desc, uint8_t* oob, int cap,
+                    int* n_out, int* mono_index, float bounds[4])
+{
+    if (!c) return EORB_E_ARG;
+    if (n_out) *n_out = 0;
+    if (!img || W <= 0 || H <= 0) return EORB_E_EMPTY;
+    OrbState& o = c->orb;
+    if (!o.configured) return set_err(c, EORB_E_NOTCONF, "eorb_frame_mono: not configured");
+    if (!c->calib_set) return set_err(c, EORB_E_NOTCONF, "eorb_frame_mono: eorb_set_calibration not called");
+    if (W != o.W || H != o.H) return set_err(c, EORB_E_ARG, "image %dx%d does not match the configured %dx%d", W, H, o.W, o.H);
+    if (stride < W) return set_err(c, EORB_E_ARG, "stride < width");
+    fe_enter(c);
+    int rc;
+    const size_t mo = (size_t)o.max_out;
+    Arena A(c);
+    static const int zc_env = [] { const char* e = getenv("EORB_IMAGE_ZERO_COPY"); return e ? atoi(e) : 1; }();
+    A.host_inputs = zc_env != 0 && (size_t)W * H <= ((size_t)1 << 20);
+    const size_t o_img = A.in2d(img, H, (size_t)W, (size_t)stride);
+    // outputs, contiguous: {n, mono, flag, pad, corners[4][2]} | keypoints | undistorted keypoints | descriptors | oob
+    const size_t o_n = A.reserve(48), o_kp = A.reserve(sizeof(eorb_keypoint) * mo), o_un = A.reserve(sizeof(eorb_keypoint) * mo),
+                 o_desc = A.reserve(32 * mo), o_oob = A.reserve(mo);
+    if ((rc = A.upload())) return rc;
+    int32_t* dn = A.dev<int32_t>(o_n);
+    rc = orb_extract_dev(c, A.in_ptr<uint8_t>(o_img), W, (size_t)W * H, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(o_kp),
+                         A.dev<uint8_t>(o_desc), A.dev<uint8_t>(o_oob), dn, dn + 1, dn + 2);
+    A.inputs_done();
+    if (rc) return rc;
+    const bool gate = c->calib_dev.gate != 0;
+    if ((rc = calib_frame_dev(c, A.dev<eorb_keypoint>(o_kp), dn, (int)mo, A.dev<eorb_keypoint>(o_un), (float*)(dn + 4), W, H))) return rc;
+    const size_t ncopy = std::min<size_t>(mo, (size_t)std::max(cap, 0));
+    const size_t end = !ncopy ? o_n + 48 : (oob ? o_oob + ncopy : ((want_desc && desc) ? o_desc + 32 * ncopy :
+                       ((kps_un && gate) ? o_un + sizeof(eorb_keypoint) * ncopy : ((kps || kps_un) ? o_kp + sizeof(eorb_keypoint) * ncopy : o_n + 48))));
+    const char* h;
+    if ((rc = A.download(o_n, end - o_n, &h))) return rc;
+    const int32_t* hn = (const int32_t*)(h + o_n);
+    if (hn[2]) return set_err(c, EORB_E_CAPACITY, "eorb_frame_mono: internal capacity exceeded (flag %d)", hn[2]);
+    if (hn[0] > cap) return set_err(c, EORB_E_CAPACITY, "eorb_frame_mono: %d keypoints > caller capacity %d", hn[0], cap);
+    if (hn[0] > 0) {
+        if (kps) memcpy(kps, h + o_kp, sizeof(eorb_keypoint) * (size_t)hn[0]);
+        if (kps_un) memcpy(kps_un, h + (gate ? o_un : o_kp), sizeof(eorb_keypoint) * (size_t)hn[0]);      // gate closed: vUndistKPts = vDistKPts
+        if (want_desc && desc) memcpy(desc, h + o_desc, 32 * (size_t)hn[0]);
+        if (oob) memcpy(oob, h + o_oob, (size_t)hn[0]);
+    }
+    if (bounds) {
+        if (c->calib_bounds.gate) {                           // Frame.cc:855-858: std::min(a, b) = b < a ? b : a, std::max(a, b) = a < b ? b : a
+            float q[8];
+            memcpy(q, hn + 4, sizeof q);                      // corners (0, 0), (W, 0), (0, H), (W, H)
+            bounds[0] = (q[4] < q[0]) ? q[4] : q[0];
+            bounds[1] = (q[2] < q[6]) ? q[6] : q[2];
+            bounds[2] = (q[3] < q[1]) ? q[3] : q[1];
+            bounds[3] = (q[5] < q[7]) ? q[7] : q[5];
+        } else { bounds[0] = 0.0f; bounds[1] = (float)W; bounds[2] = 0.0f; bounds[3] = (float)H; }
     }
     if (n_out) *n_out = hn[0];
     if (mono_index) *mono_index = hn[1];

@@ -275,6 +275,46 @@ def cv_normalize_minmax_u8(image, ctx=None):
     return out
 
 
+class MyCalibrator:
+    """EORB_SLAM::MyCalibrator (src/Utils/MyCalibrator.cpp): K, distortion coefficients, R and P held by the context
+    (eorb_set_calibration); undistKeyPoints / undistPoint / generateUndistMaps run on the device.  P = None stays cv::Mat() here: the
+    reference's constructor fills it with K for a pinhole camera (:25-27), and so should its caller."""
+
+    def __init__(self, K, distCoefs, imageSize, R=None, P=None, isFishEye=False, ctx=None):
+        self.ctx = ctx or default_context()
+        self.mImWidth, self.mImHeight = int(imageSize[0]), int(imageSize[1])
+        self.calib = _lib.calib(1 if isFishEye else 0, K, distCoefs, R, P)
+        self.ctx.check(self.ctx.L.eorb_set_calibration(self.ctx.h, C.byref(self.calib)))
+
+    @classmethod
+    def from_dict(cls, d, ctx=None):
+        """a calibration of synth.CALIBRATIONS"""
+        return cls(d["K"], d["dist"], d["size"], d["R"], d["P"], d["model"] == 1, ctx=ctx)
+
+    def undistKeyPoints(self, vDistKPts):
+        """:181-283 -> the undistorted keypoints (a copy when the calibration is not distorted; empty in, empty out)"""
+        kps = np.ascontiguousarray(vDistKPts, KP_DTYPE)
+        out = np.zeros(len(kps), KP_DTYPE)
+        self.ctx.check(self.ctx.L.eorb_undistort_keypoints(self.ctx.h, _p(kps), len(kps), _p(out)))
+        return out
+
+    def undistPoint(self, pts):
+        """:104-156 over (n, 2) points (or one (x, y))"""
+        xy = np.ascontiguousarray(pts, np.float32)
+        out = np.zeros_like(xy)
+        self.ctx.check(self.ctx.L.eorb_undistort_points(self.ctx.h, _p(xy), xy.size // 2, _p(out)))
+        return out
+
+    def generateUndistMaps(self, checkInImage=True, download=True, size=None):
+        """:52-102: builds the maps on the device and installs them as EvImConverter.set_undistort_maps would; returns
+        (mUndistMapX, mUndistMapY) when download"""
+        LW, LH = size or (self.mImWidth, self.mImHeight)
+        mx = np.zeros((LH, LW), np.float32) if download else None
+        my = np.zeros((LH, LW), np.float32) if download else None
+        self.ctx.check(self.ctx.L.eorb_generate_undistort_maps(self.ctx.h, LW, LH, int(checkInImage), _p(mx), _p(my)))
+        return (mx, my) if download else None
+
+
 class ORBextractor:
     """ORB_SLAM3::ORBextractor (include/ORBextractor.h:49-139).  One instance per thread, like the reference."""
 
@@ -327,6 +367,21 @@ class ORBextractor:
         a, b = nL.value, nR.value
         return dict(kpsL=kL[:a].copy(), descL=dL[:a].copy(), monoLeft=mL.value, kpsR=kR[:b].copy(), descR=dR[:b].copy(), monoRight=mR.value,
                     right_idx=cand[:a].copy(), dist2=d2[:a].copy(), ncand=nc.value)
+
+    def frame_mono(self, image, vLappingArea=(0, 1000), want_desc=True):
+        """The monocular Frame constructor's hot path (src/Frame.cc:229-266) in one call: ExtractORB, undistKeyPoints of the context's
+        calibration (MyCalibrator / eorb_set_calibration) and ComputeImageBounds.  Returns dict(mono, kps (mvKeys), kps_un (mvKeysUn),
+        desc, oob, bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY))."""
+        image = np.ascontiguousarray(image, np.uint8)
+        H, W = image.shape
+        kps = np.empty(self.cap, KP_DTYPE); un = np.empty(self.cap, KP_DTYPE)
+        desc = np.empty((self.cap, 32), np.uint8); oob = np.empty(self.cap, np.uint8); bounds = np.zeros(4, np.float32)
+        n = C.c_int(); mono = C.c_int()
+        self.ctx.check(self.ctx.L.eorb_frame_mono(self.ctx.h, _p(image), W, H, image.strides[0], vLappingArea[0], vLappingArea[1], int(want_desc),
+                                                  _p(kps), _p(un), _p(desc), _p(oob), self.cap, C.byref(n), C.byref(mono), _p(bounds)))
+        k = n.value
+        return dict(mono=mono.value, kps=kps[:k].copy(), kps_un=un[:k].copy(), desc=(desc[:k].copy() if want_desc else None), oob=oob[:k].copy(),
+                    bounds=bounds)
 
     def GetLevels(self):
         return self.nlevels

@@ -40,7 +40,7 @@ public:
     Context& operator=(const Context&) = delete;
     eorb_ctx* get() const { return h_; }
     void check(int rc) const { if (rc != EORB_OK) throw Error(rc, eorb_last_error(h_)); }
-    unsigned maps_epoch = 0, voc_epoch = 0;          // which shared state of the pool this context has loaded
+    unsigned maps_epoch = 0, voc_epoch = 0, calib_epoch = 0;      // which shared state of the pool this context has loaded
 private:
     eorb_ctx* h_ = nullptr;
 };
@@ -79,6 +79,25 @@ public:
         std::lock_guard<std::mutex> g(m_);
         maps_ = std::move(m); maps_epoch_.store(maps_epoch_.load(std::memory_order_relaxed) + 1, std::memory_order_release);
     }
+    // the calibrator's K, distortion coefficients, R and P (MyCalibrator.cpp:11-17): every context of the process
+    // (`load` = eorb_set_calibration, named by the caller: the pool itself then links against a library without that entry, such as
+    // the stub the thread-sanitizer test of the pool uses)
+    void set_calibration(const eorb_calib& q, int (*load)(eorb_ctx*, const eorb_calib*)) {
+        auto p = std::make_shared<eorb_calib>(q);
+        std::lock_guard<std::mutex> g(m_);
+        calib_load_ = load;
+        calib_ = std::move(p); calib_epoch_.store(calib_epoch_.load(std::memory_order_relaxed) + 1, std::memory_order_release);
+    }
+    // maps that context `c` has just built on the device (eorb_generate_undistort_maps) and downloaded: the other contexts upload them,
+    // `c` already holds them
+    void set_maps_built_by(Context& c, const std::vector<float>& mapX, const std::vector<float>& mapY, int LW, int LH, bool check) {
+        auto m = std::make_shared<Maps>(); m->mapX = mapX; m->mapY = mapY; m->LW = LW; m->LH = LH; m->check = check;
+        std::lock_guard<std::mutex> g(m_);
+        maps_ = std::move(m);
+        const unsigned e = maps_epoch_.load(std::memory_order_relaxed) + 1;
+        maps_epoch_.store(e, std::memory_order_release);
+        c.maps_epoch = e;
+    }
     void set_vocabulary(Voc v) {
         auto p = std::make_shared<Voc>(std::move(v));
         std::lock_guard<std::mutex> g(m_);
@@ -94,6 +113,12 @@ public:
             if (m) c.check(eorb_set_undistort_maps(c.get(), m->mapX.data(), m->mapY.data(), m->LW, m->LH, m->check));
             c.maps_epoch = e;
         }
+        if (c.calib_epoch != calib_epoch_.load(std::memory_order_acquire)) {
+            std::shared_ptr<const eorb_calib> q; unsigned e;
+            { std::lock_guard<std::mutex> g(m_); q = calib_; e = calib_epoch_.load(std::memory_order_relaxed); }
+            if (q) c.check(calib_load_(c.get(), q.get()));
+            c.calib_epoch = e;
+        }
         if (c.voc_epoch != voc_epoch_.load(std::memory_order_acquire)) {
             std::shared_ptr<const Voc> v; unsigned e;
             { std::lock_guard<std::mutex> g(m_); v = voc_; e = voc_epoch_.load(std::memory_order_relaxed); }
@@ -108,6 +133,8 @@ private:
     std::vector<Context*> free_;
     std::shared_ptr<const Maps> maps_; std::atomic<unsigned> maps_epoch_{0};
     std::shared_ptr<const Voc> voc_; std::atomic<unsigned> voc_epoch_{0};
+    std::shared_ptr<const eorb_calib> calib_; std::atomic<unsigned> calib_epoch_{0};
+    int (*calib_load_)(eorb_ctx*, const eorb_calib*) = nullptr;      // written under m_ before the epoch's release store
 };
 
 // the calling thread's context: borrowed from the pool for the lifetime of the thread
@@ -194,6 +221,64 @@ struct EventDataStore {
         out.resize(n);
         return out;
     }
+};
+
+// EORB_SLAM::MyCalibrator (src/Utils/MyCalibrator.cpp): K, distCoefs, R, P as CV_32F values (empty vectors = cv::Mat()); the points go
+// through cv::undistortPoints / cv::fisheye::undistortPoints on the device.  The calibration is process-wide state of the pool, like
+// the maps: every thread's context loads it before its next call.  P stays as given: the reference's constructor replaces an empty P
+// of a pinhole camera by K (:25-27), and so should the caller of this one.
+class MyCalibrator {
+public:
+    MyCalibrator(const float K[9], const std::vector<float>& distCoefs, int imWidth, int imHeight, const std::vector<float>& R = {},
+                 const std::vector<float>& P = {}, bool isFishEye = false) : mImWidth(imWidth), mImHeight(imHeight) {
+        q_ = eorb_calib{};
+        q_.model = isFishEye ? 1 : 0;
+        std::memcpy(q_.K, K, sizeof q_.K);
+        q_.n_dist = (int)distCoefs.size();
+        for (size_t i = 0; i < distCoefs.size() && i < 8; i++) q_.dist[i] = distCoefs[i];
+        if (R.size() == 9) { std::memcpy(q_.R, R.data(), sizeof q_.R); q_.has_R = 1; }
+        else if (!R.empty()) throw eorb_host::Error(EORB_E_ARG, "MyCalibrator: R must be 3x3");
+        if (P.size() == 9 || P.size() == 12) { std::memcpy(q_.P, P.data(), P.size() * sizeof(float)); q_.p_cols = (int)P.size() / 3; }
+        else if (!P.empty()) throw eorb_host::Error(EORB_E_ARG, "MyCalibrator: P must be 3x3 or 3x4");
+        auto& c = eorb_host::thread_context();
+        c.check(eorb_set_calibration(c.get(), &q_));                         // (validates the record before the pool hands it out)
+        eorb_host::ContextPool::instance().set_calibration(q_, &eorb_set_calibration);
+    }
+    const eorb_calib& calibration() const { return q_; }
+    // :46-50
+    static bool isDistorted(const std::vector<float>& distCoefs) { return distCoefs.size() >= 4 && std::fabs((double)distCoefs[0]) > 1e-9; }
+    // :181-283; an empty input leaves vUndistKPts alone (:202-205)
+    void undistKeyPoints(const std::vector<eorb_host::KeyPoint>& vDistKPts, std::vector<eorb_host::KeyPoint>& vUndistKPts) const {
+        if (vDistKPts.empty()) return;
+        auto& c = eorb_host::thread_context();
+        std::vector<eorb_host::KeyPoint> out(vDistKPts.size());
+        c.check(eorb_undistort_keypoints(c.get(), vDistKPts.data(), (int)vDistKPts.size(), out.data()));
+        vUndistKPts.swap(out);
+    }
+    // :104-156, one point or n points (x, y interleaved)
+    void undistPoint(float x, float y, float& ux, float& uy) const {
+        const float in[2] = {x, y}; float out[2];
+        auto& c = eorb_host::thread_context();
+        c.check(eorb_undistort_points(c.get(), in, 1, out));
+        ux = out[0]; uy = out[1];
+    }
+    std::vector<float> undistPoints(const std::vector<float>& xy) const {
+        std::vector<float> out(xy.size());
+        auto& c = eorb_host::thread_context();
+        c.check(eorb_undistort_points(c.get(), xy.data(), (int)(xy.size() / 2), out.data()));
+        return out;
+    }
+    // :52-102: mUndistMapX / mUndistMapY built on the device, installed in this thread's context and recorded in the pool for the others
+    void generateUndistMaps(bool checkInImage = true) {
+        auto& c = eorb_host::thread_context();
+        mUndistMapX.assign((size_t)mImWidth * mImHeight, 0.f); mUndistMapY.assign((size_t)mImWidth * mImHeight, 0.f);
+        c.check(eorb_generate_undistort_maps(c.get(), mImWidth, mImHeight, checkInImage, mUndistMapX.data(), mUndistMapY.data()));
+        eorb_host::ContextPool::instance().set_maps_built_by(c, mUndistMapX, mUndistMapY, mImWidth, mImHeight, checkInImage);
+    }
+    std::vector<float> mUndistMapX, mUndistMapY;
+private:
+    int mImWidth, mImHeight;
+    eorb_calib q_;
 };
 
 // The data path of EORB_SLAM::EvImBuilder::Track (src/Event/EvImBuilder.cpp:1300-1515) over the one-call seams: per chunk of
@@ -406,6 +491,27 @@ public:
         if (nr) std::memcpy(mDescriptorsRight.ptr(), dr.ptr(), (size_t)nr * 32);
         return nc;
     }
+    // Frame::Frame(imGray, ...) (src/Frame.cc:229-266): ExtractORB, undistKeyPoints (:246-252) and ComputeImageBounds (:840-867) in one
+    // call; calib = MyCalibrator::calibration().  Fills mvKeys, mvKeysUn, mDescriptors and bounds = mnMinX, mnMaxX, mnMinY, mnMaxY;
+    // returns monoIndex, -1 for an empty image.
+    int ExtractMono(const eorb_host::Mat8& image, const std::vector<int>& vLappingArea, const eorb_calib& calib,
+                    std::vector<eorb_host::KeyPoint>& mvKeys, std::vector<eorb_host::KeyPoint>& mvKeysUn, eorb_host::Mat8& mDescriptors,
+                    float bounds[4]) {
+        if (image.empty()) return -1;
+        if (!has_calib_ || std::memcmp(&calib_, &calib, sizeof calib) != 0) {
+            ctx_.check(eorb_set_calibration(ctx_.get(), &calib));
+            calib_ = calib; has_calib_ = true;
+        }
+        mvKeys.assign(cap_, eorb_host::KeyPoint{}); mvKeysUn.assign(cap_, eorb_host::KeyPoint{});
+        eorb_host::Mat8 d(cap_, 32);
+        int n = 0, mono = 0;
+        ctx_.check(eorb_frame_mono(ctx_.get(), image.ptr(), image.cols, image.rows, image.cols, vLappingArea[0], vLappingArea[1], 1,
+                                   mvKeys.data(), mvKeysUn.data(), d.ptr(), nullptr, cap_, &n, &mono, bounds));
+        mvKeys.resize(n); mvKeysUn.resize(n);
+        mDescriptors = eorb_host::Mat8(n, 32);
+        if (n) std::memcpy(mDescriptors.ptr(), d.ptr(), (size_t)n * 32);
+        return mono;
+    }
     int GetLevels() const { return p_.nlevels; }
     float GetScaleFactor() const { return p_.scaleFactor; }
     std::vector<float> GetScaleFactors() const { return mvScaleFactor; }
@@ -418,6 +524,7 @@ private:
     ORBxParams p_;
     eorb_host::Context ctx_;
     int cap_ = 0, edge_ = 0;
+    eorb_calib calib_{}; bool has_calib_ = false;
 };
 
 // the part of a Frame the matchers read (undistorted keypoints, descriptors, image bounds)

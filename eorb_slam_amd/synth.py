@@ -406,3 +406,70 @@ def keyframe_pair(seed=0, twocam=False, npts=600, ndistract=150, nties=30, strid
     return dict(kps1=kf[0]["kps"], nleft1=kf[0]["nleft"], desc1=kf[0]["desc"], elig1=kf[0]["elig"], fv1=kf[0]["fv"],
                 kps2=kf[1]["kps"], nleft2=kf[1]["nleft"], desc2=kf[1]["desc"], elig2=kf[1]["elig"], fv2=kf[1]["fv"],
                 cams1=camsp, cams2=camsp, Rt=Rt, ep=np.array(ep, np.float32), scale2=scale, sigma2_1=sigma2, sigma2_2=sigma2)
+
+
+# ---- camera calibrations (eorb_calib of include/eorb_fe.h): model 0 = Pinhole / cv::undistortPoints, 1 = KannalaBrandt8 /
+# cv::fisheye::undistortPoints; K, dist as the reference reads them from its settings (CV_32F); R = None: cv::Mat(); P = None: cv::Mat()
+def _K(fx, fy, cx, cy):
+    return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32)
+
+
+def _calibration(model, K, dist, size, R=None, P="K"):
+    return dict(model=model, K=K, dist=np.asarray(dist, np.float32), size=size, R=None if R is None else np.asarray(R, np.float32),
+                P=(K.copy() if isinstance(P, str) else (None if P is None else np.asarray(P, np.float32))))
+
+
+_K_ETHZ = _K(EVETHZ_K["fx"], EVETHZ_K["fy"], EVETHZ_K["cx"], EVETHZ_K["cy"])
+_D_ETHZ = [EVETHZ_K["k1"], EVETHZ_K["k2"], EVETHZ_K["p1"], EVETHZ_K["p2"]]
+_K_EUROC = _K(458.654, 457.296, 367.215, 248.375)
+_K_MVSEC = _K(226.38018519795807, 226.15002947047415, 173.6470807871759, 133.73271487507847)
+
+CALIBRATIONS = {
+    # Examples/Event/EvETHZ.yaml:59-73 (PinHole, k1 k2 p1 p2, 240 x 180); the call sites pass R = cv::Mat(), P = mK (Frame.cc:248)
+    "EvETHZ": _calibration(0, _K_ETHZ, _D_ETHZ, (240, 180)),
+    # Examples/Event/EuRoC.yaml:58-87 (PinHole, 752 x 480)
+    "EuRoC": _calibration(0, _K_EUROC, [-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05], (752, 480)),
+    # Examples/Event/EvMVSEC_ETHZ.yaml:54-89 (KannalaBrandt8, equidistant k1..k4, 346 x 260)
+    "MVSEC_KB8": _calibration(1, _K_MVSEC, [-0.048031442223833355, 0.011330957517194437, -0.055378166304281135, 0.021500973881459395],
+                              (346, 260)),
+    # the five- and eight-coefficient forms of cv::undistortPoints (k3; k4 k5 k6 of the rational model)
+    "pinhole5": _calibration(0, _K_ETHZ, _D_ETHZ + [0.021], (240, 180)),
+    "pinhole8": _calibration(0, _K_EUROC, [-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05, 0.011, 0.013, -0.006, 0.002], (752, 480)),
+    # a rectifying rotation and a 3 x 4 projection that is not K (a stereo-rectified pair's R1 / P1 shape), both models
+    "pinhole_RP": _calibration(0, _K_EUROC, [-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05], (752, 480),
+                               R=None, P=[[435.2, 0, 367.45, 0], [0, 435.2, 252.2, 0], [0, 0, 1, 0]]),
+    "fisheye_RP": _calibration(1, _K_MVSEC, [-0.048031442223833355, 0.011330957517194437, -0.055378166304281135, 0.021500973881459395],
+                               (346, 260), R=None, P=[[190.98, 0, 172.9, -12.5], [0, 190.97, 130.9, 0], [0, 0, 1, 0]]),
+    # normalised coordinates out (P = cv::Mat()), and the closed gate: |k1| <= 1e-9 with the other coefficients large
+    "pinhole_noP": _calibration(0, _K_ETHZ, _D_ETHZ, (240, 180), P=None),
+    "gate_closed": _calibration(0, _K_ETHZ, [1e-10, 0.5, 0.1, -0.2], (240, 180)),
+}
+
+
+def _small_rotation(ax=0.011, ay=-0.007, az=0.004):
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]); Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return (Rz @ Ry @ Rx).astype(np.float32)
+
+
+CALIBRATIONS["pinhole_RP"]["R"] = _small_rotation()
+CALIBRATIONS["fisheye_RP"]["R"] = _small_rotation(-0.006, 0.009, -0.003)
+
+
+def calib_keypoints(n, W, H, seed=0, margin=0.1, nlevels=4):
+    """n seeded keypoints inside the image plus a margin (fraction of the size) around it: integer, half-pixel and arbitrary
+    sub-pixel positions, every other field filled so that a copy can be told from a default."""
+    rng = np.random.RandomState(seed)
+    kps = np.zeros(n, KP_DTYPE)
+    x = rng.uniform(-margin * W, (1 + margin) * W, n); y = rng.uniform(-margin * H, (1 + margin) * H, n)
+    kind = rng.randint(0, 3, n)
+    x = np.where(kind == 0, np.round(x), np.where(kind == 1, np.round(x * 2) / 2, x))
+    y = np.where(kind == 0, np.round(y), np.where(kind == 1, np.round(y * 2) / 2, y))
+    kps["x"] = x.astype(np.float32); kps["y"] = y.astype(np.float32)
+    kps["octave"] = rng.randint(0, nlevels, n)
+    kps["size"] = (31.0 * 1.2 ** kps["octave"]).astype(np.float32)
+    kps["angle"] = rng.uniform(0, 360, n).astype(np.float32)
+    kps["response"] = rng.uniform(1, 200, n).astype(np.float32)
+    kps["class_id"] = rng.randint(-1, 1000, n)
+    return kps

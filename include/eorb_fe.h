@@ -156,7 +156,7 @@ int eorb_ev2im_gauss(eorb_ctx* ctx, const eorb_event* ev, size_t n, int W, int H
 
 /* ---- raw sensor events through the undistortion maps ------------------------------
  * mapX / mapY = MyCalibrator::mUndistMapX / mUndistMapY (Utils/MyCalibrator.cpp:60-101, LH x LW floats each, built by the
- * caller with cv::undistortPoints as the reference does).  checkInImage = the flag the loader passes to
+ * caller with cv::undistortPoints as the reference does, or on the device by eorb_generate_undistort_maps below).  checkInImage = the flag the loader passes to
  * getEventChunkRectified (EventLoader.cpp:264-305): events whose undistorted point fails MyCalibrator::isInImage(x, y)
  * for the accumulation image (:31-34) are dropped. */
 int eorb_set_undistort_maps(eorb_ctx* ctx, const float* mapX, const float* mapY, int LW, int LH, int checkInImage);
@@ -214,6 +214,48 @@ int eorb_measure_image_focus(eorb_ctx* ctx, const float* img, int W, int H, floa
 int eorb_measure_image_focus_n(eorb_ctx* ctx, const float* imgs, int n, int W, int H, float* focus);
 /* replaces cv::normalize(img, img, 255, 0, NORM_MINMAX, CV_8UC1) at src/Event/EvImBuilder.cpp:976,1055,1076,1140 */
 int eorb_normalize_minmax_u8(eorb_ctx* ctx, const float* img, int W, int H, uint8_t* out);
+
+/* ---- camera calibration: undistorted points, keypoints and the calibrator's maps ------------------------------------------
+ * MyCalibrator (src/Utils/MyCalibrator.cpp) keeps K, the distortion coefficients, R and P (:11-29) and sends every point through
+ * cv::undistortPoints (Pinhole) or cv::fisheye::undistortPoints (KannalaBrandt8) of OpenCV 3.4.1; both are restated in double, in
+ * the operation order of their scalar paths.  The calibration is per-context state like the maps and the
+ * vocabulary.  R: 3 x 3 row-major; P: 3 rows of p_cols floats, of which the left 3 x 3 block is used. */
+typedef struct eorb_calib {
+    int   model;        /* 0 = pinhole (cv::undistortPoints), 1 = fisheye (cv::fisheye::undistortPoints) */
+    float K[9];         /* CV_32F 3x3 as the reference holds it (mK) */
+    float dist[8];      /* pinhole: k1 k2 p1 p2 [k3 [k4 k5 k6]]; fisheye: k1..k4 */
+    int   n_dist;       /* pinhole 4, 5 or 8; fisheye 4; anything else EORB_E_ARG */
+    float R[9];  int has_R;     /* 0 = cv::Mat(): identity */
+    float P[12]; int p_cols;    /* 0 = cv::Mat() (normalised coordinates out), 3 or 4 (left 3x3 block used) */
+} eorb_calib;
+
+/* replaces MyCalibrator::MyCalibrator's members (:11-17): copied into the context; bad model / n_dist / has_R / p_cols: EORB_E_ARG */
+int eorb_set_calibration(eorb_ctx* ctx, const eorb_calib* calib);
+
+/* replaces MyCalibrator::undistKeyPointsPinhole / undistKeyPointsFishEye (src/Utils/MyCalibrator.cpp:198-283; callers Frame.cc:246-252,
+ * :339-340, :1186-1192, MixedFrame.cpp:133,138, EventFrame.cpp:435-446): out[i] = in[i] with pt undistorted, every other field
+ * copied.  n == 0: EORB_OK, nothing written (:202-205).  When MyCalibrator::isDistorted fails (:46-50: fabs(dist[0]) > 1e-9 in
+ * double) out is a copy of in, whatever the other coefficients are (:206-210).  No calibration: EORB_E_NOTCONF. */
+int eorb_undistort_keypoints(eorb_ctx* ctx, const eorb_keypoint* in, int n, eorb_keypoint* out);
+
+/* replaces MyCalibrator::undistPointPinhole / undistPointFishEye (:119-156) over n points (x, y) -> xy_out (n x 2); same gate */
+int eorb_undistort_points(eorb_ctx* ctx, const float* xy, int n, float* xy_out);
+
+/* replaces MyCalibrator::generateUndistMapsPinhole / FishEye (:64-102): map[y][x] = undistPoint((float)x, (float)y) for every
+ * sensor pixel, written on the device into the context's maps, which are then installed exactly as eorb_set_undistort_maps
+ * installs uploaded ones (checkInImage as there): afterwards every raw-event entry point behaves as if the caller had uploaded
+ * them.  mapX / mapY (LH x LW floats each, optional): the maps downloaded.  Gate closed: the identity maps (float)x, (float)y. */
+int eorb_generate_undistort_maps(eorb_ctx* ctx, int LW, int LH, int checkInImage, float* mapX, float* mapY);
+
+/* replaces the hot path of the monocular Frame constructor (src/Frame.cc:229-266): ExtractORB (:240), undistKeyPoints on the
+ * keypoints while they are still on the device (:246-252) and Frame::ComputeImageBounds (:840-867).  kps / desc / oob / n_out /
+ * mono_index exactly as eorb_orb_extract; kps_un[cap] = eorb_undistort_keypoints of kps; bounds = mnMinX, mnMaxX, mnMinY, mnMaxY.
+ * ComputeImageBounds has its own gate, dist[0] != 0.0 (:842), and always calls cv::undistortPoints(corners, K, dist, cv::Mat(), K)
+ * (:851): the pinhole arithmetic on all n_dist coefficients with R = identity and P = K, whatever model, R and P the calibration
+ * holds; gate closed: 0, W, 0, H.  One upload, one wait, one download. */
+int eorb_frame_mono(eorb_ctx* ctx, const uint8_t* img, int W, int H, int stride, int lap0, int lap1, int want_desc,
+                    eorb_keypoint* kps, eorb_keypoint* kps_un, uint8_t* desc, uint8_t* oob, int cap,
+                    int* n_out, int* mono_index, float bounds[4]);
 
 /* ---- ORB extractor (host buffers) --------------------------------------------------------------- */
 /* replaces ORBextractor::ORBextractor, src/ORBextractor.cc:420-489: scale tables, per-level quotas,
