@@ -22,6 +22,7 @@ EXPORTS = [
     "eorb_orb_tracked_descriptors", "eorb_orb_assign_level_by_best_desc",
     "eorb_fe_configure", "eorb_fe_run_batch_dev", "eorb_fe_last_f32_dev",
     "eorb_ev_slice_extract", "eorb_ev_slice_track", "eorb_ev_slice_image", "eorb_ev_mc_contest",
+    "eorb_project_frustum", "eorb_project_last_frame", "eorb_project_keyframe_points", "eorb_search_local_points", "eorb_search_local_points_fisheye", "eorb_search_by_projection_last_pose", "eorb_search_by_projection_kf_pose",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
 ]
@@ -51,6 +52,20 @@ def camera(cam):
             c.k[i] = float(cam[4 + i])
         c.precision = float(cam[8]) if len(cam) > 8 else 1e-6
     return c
+
+
+class View(C.Structure):
+    """eorb_view: one camera of a frame and its pose (the scale tables are host pointers: keep the arrays alive)"""
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("Ow", C.c_float * 3), ("cam", Camera),
+                ("minX", C.c_float), ("maxX", C.c_float), ("minY", C.c_float), ("maxY", C.c_float), ("mbf", C.c_float),
+                ("nlevels", C.c_int), ("log_scale", C.c_float), ("scale_factors", C.c_void_p),
+                ("ak_nlevels", C.c_int), ("ak_log_scale", C.c_float), ("ak_scale_factors", C.c_void_p)]
+
+
+class FrustumOut(C.Structure):
+    """eorb_frustum_out: what isInFrustum leaves in a MapPoint, one array per member (any may be NULL)"""
+    _fields_ = [("in_view", C.c_void_p), ("proj_xy", C.c_void_p), ("proj_xr", C.c_void_p), ("level", C.c_void_p),
+                ("view_cos", C.c_void_p), ("depth", C.c_void_p), ("level_scale", C.c_void_p), ("reason", C.c_void_p)]
 
 
 class Calib(C.Structure):
@@ -265,6 +280,24 @@ def lib():
     L.eorb_ev_mc_contest.restype = ci
     L.eorb_ev_mc_contest.argtypes = [vp, vp, C.c_size_t, C.POINTER(Camera), C.POINTER(Se3Motion), C.POINTER(Se3Motion), vp, ci, ci, ci, cf,
                                      vp, pi, vp, vp, ci, ci, vp, ci, pi]
+    L.eorb_project_frustum.restype = ci
+    L.eorb_project_frustum.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, cf, vp, pi]
+    L.eorb_project_last_frame.restype = ci
+    L.eorb_project_last_frame.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.eorb_project_keyframe_points.restype = ci
+    L.eorb_project_keyframe_points.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.eorb_search_local_points.restype = ci
+    L.eorb_search_local_points.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, cf, vp, vp, C.POINTER(GridBounds), vp, cf, cf,
+                                           vp, ci, cf, vp, pi, pi]
+    L.eorb_search_local_points_fisheye.restype = ci
+    L.eorb_search_local_points_fisheye.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, cf, vp, vp, C.POINTER(GridBounds),
+                                                   vp, cf, cf, ci, cf, vp, pi, pi]
+    L.eorb_search_by_projection_last_pose.restype = ci
+    L.eorb_search_by_projection_last_pose.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.POINTER(GridBounds), vp, cf, ci, ci,
+                                                      vp, vp, vp, pi]
+    L.eorb_search_by_projection_kf_pose.restype = ci
+    L.eorb_search_by_projection_kf_pose.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, C.POINTER(GridBounds), vp, cf, ci, ci,
+                                                    vp, vp, vp, pi]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]
     L.eorb_selfcheck_math.restype = ci; L.eorb_selfcheck_math.argtypes = [vp, ci, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.eorb_pack_events.restype = None; L.eorb_pack_events.argtypes = [vp, C.c_size_t, vp]

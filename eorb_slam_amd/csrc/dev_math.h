@@ -290,6 +290,47 @@ __device__ __forceinline__ float dev_atan2f(float y, float x)
     return (z - pi_lo) - pi;
 }
 
+// ---- logf: glibc's e_logf.c (>= 2.27), whole float domain.  MapPoint::PredictScale (src/MapPoint.cc:570-593) calls log(float ratio)
+// with <cmath>'s overloads in scope: std::log(float) = logf.  16 intervals of the mantissa around OFF, a degree-3 polynomial in double;
+// checked against the CPU restatement by eorb_selfcheck_math (which = 6), that one against the host logf (tests/test_proj_ref.py).
+__device__ __constant__ static const double kLogfTab[32] = {      // invc, logc per interval
+    0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2, 0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2,
+    0x1.49539f0f010bp+0, -0x1.01eae7f513a67p-2, 0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3,
+    0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3, 0x1.25e227b0b8eap+0, -0x1.1aa2bc79c81p-3,
+    0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4, 0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4,
+    0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5, 0x1p+0, 0x0p+0,
+    0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5, 0x1.ca4b31f026aap-1, 0x1.c5e53aa362eb4p-4,
+    0x1.b2036576afce6p-1, 0x1.526e57720db08p-3, 0x1.9c2d163a1aa2dp-1, 0x1.bc2860d22477p-3,
+    0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2, 0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2,
+};
+__device__ __forceinline__ float dev_logf(float x)
+{
+    const double Ln2 = 0x1.62e42fefa39efp-1;
+    const double A0 = -0x1.00ea348b88334p-2, A1 = 0x1.5575b0be00b6ap-2, A2 = -0x1.ffffef20a4123p-2;
+    uint32_t ix = __float_as_uint(x);
+    if (ix == 0x3f800000u) return 0.0f;
+    if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {
+        if (ix * 2 == 0) return -__uint_as_float(0x7f800000u);            // log(+-0) = -inf
+        if (ix == 0x7f800000u) return x;                                  // log(inf) = inf
+        if ((ix & 0x80000000u) || ix * 2 >= 0xff000000u) return __uint_as_float(0x7fc00000u);
+        ix = __float_as_uint(x * 0x1p23f);                                // subnormal: normalise
+        ix -= 23u << 23;
+    }
+    const uint32_t tmp = ix - 0x3f330000u;
+    const int i = (int)((tmp >> 19) % 16);
+    const int k = (int32_t)tmp >> 23;
+    const uint32_t iz = ix - (tmp & (0x1ffu << 23));
+    const double invc = kLogfTab[2 * i], logc = kLogfTab[2 * i + 1];
+    const double z = (double)__uint_as_float(iz);
+    const double r = z * invc - 1;
+    const double y0 = logc + (double)k * Ln2;
+    const double r2 = r * r;
+    double y = A1 * r + A2;
+    y = A0 * r2 + y;
+    y = y * r2 + (y0 + r);
+    return (float)y;
+}
+
 __device__ __forceinline__ int dev_cvround(float v) { return __float2int_rn(v); }
 
 // popcount of a 256-bit XOR: ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:2360-2378)

@@ -2,6 +2,7 @@
 // batched HBM-resident front end.  No CPU fallback anywhere: every entry point launches HIP kernels.
 #include "eorb_ctx.h"
 #include "match_args.h"
+#include "project_args.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -1209,7 +1210,7 @@ int eorb_selfcheck_division(eorb_ctx* c, float lo, float hi, float sigma, uint64
 
 int eorb_selfcheck_math(eorb_ctx* c, int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* hash)
 {
-    if (!c || !hash || which < 0 || which > 5 || hi_bits < lo_bits) return c ? set_err(c, EORB_E_ARG, "selfcheck_math: bad arguments") : EORB_E_ARG;
+    if (!c || !hash || which < 0 || which > 6 || hi_bits < lo_bits) return c ? set_err(c, EORB_E_ARG, "selfcheck_math: bad arguments") : EORB_E_ARG;
     fe_enter(c);
     unsigned long long h = 0;
     int rc = ev_mathhash(c, which, lo_bits, hi_bits, &h);
@@ -1629,6 +1630,421 @@ int eorb_search_by_projection_map_stereo(eorb_ctx* c,
     if (c && (!uright || !proj_xr)) return set_err(c, EORB_E_ARG, "search_by_projection_map_stereo: mvuRight and mTrackProjXR are needed");
     return proj_map_common(c, kps, n, desc, stride, is_orb, M, in_view, proj_xy, level, view_cos, mp_desc, mp_obs, mp_is_orb, level_scale, gb,
                            frame_mp, th, nnratio, nmatches, uright, proj_xr);
+}
+
+// ---- map points projected on the device (project.hip) ---------------------------------------------------------------------------
+static int twocam_frame_check(eorb_ctx* c, const char* who, const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
+                              const int32_t* slots, int nq);
+static int view_check(eorb_ctx* c, const char* who, const eorb_view* v, bool has_is_orb)
+{
+    if (!v) return set_err(c, EORB_E_ARG, "%s: null view", who);
+    if (v->nlevels < 1 || v->nlevels > 128 || !v->scale_factors) return set_err(c, EORB_E_ARG, "%s: nlevels %d outside 1..128 or no scale factors", who, v->nlevels);
+    if (v->ak_nlevels < 0 || v->ak_nlevels > 128 || (v->ak_nlevels > 0 && !v->ak_scale_factors))
+        return set_err(c, EORB_E_ARG, "%s: ak_nlevels %d outside 0..128 or no AKAZE scale factors", who, v->ak_nlevels);
+    if (v->cam.model != 0 && v->cam.model != 1) return set_err(c, EORB_E_ARG, "%s: camera model %d", who, v->cam.model);
+    if (has_is_orb && v->ak_nlevels == 0) return set_err(c, EORB_E_ARG, "%s: descriptor kinds given for a view without AKAZE tables", who);
+    return EORB_OK;
+}
+
+struct ViewOff { size_t sf, ak; };
+static ViewOff view_in(Arena& A, const eorb_view* v)
+{
+    ViewOff o;
+    o.sf = A.in(v->scale_factors, sizeof(float) * (size_t)v->nlevels);
+    o.ak = A.in(v->ak_scale_factors, v->ak_nlevels > 0 ? sizeof(float) * (size_t)v->ak_nlevels : 0);
+    return o;
+}
+static ProjView view_dev(const Arena& A, const eorb_view* v, const ViewOff& o)      // after A.upload()
+{
+    ProjView P{};
+    memcpy(P.R, v->R, sizeof(P.R)); memcpy(P.t, v->t, sizeof(P.t)); memcpy(P.Ow, v->Ow, sizeof(P.Ow));
+    P.cam = warp_cam_of(v->cam);
+    P.minX = v->minX; P.maxX = v->maxX; P.minY = v->minY; P.maxY = v->maxY; P.mbf = v->mbf;
+    P.nlevels = v->nlevels; P.log_scale = v->log_scale; P.sf = A.dev<float>(o.sf);
+    P.ak_nlevels = v->ak_nlevels; P.ak_log_scale = v->ak_log_scale; P.ak_sf = v->ak_nlevels > 0 ? A.dev<float>(o.ak) : nullptr;
+    return P;
+}
+
+// the arena regions of one view's eorb_frustum_out, contiguous in the struct's order; then the matcher's records
+struct FrustumOff { size_t iv, xy, xr, lv, vc, dp, ls, rs, end, rec, srch; };
+static FrustumOff frustum_reserve(Arena& A, int M)
+{
+    const size_t m = (size_t)M;
+    FrustumOff o;
+    o.iv = A.reserve(m); o.xy = A.reserve(8 * m); o.xr = A.reserve(4 * m); o.lv = A.reserve(4 * m); o.vc = A.reserve(4 * m);
+    o.dp = A.reserve(4 * m); o.ls = A.reserve(4 * m); o.rs = A.reserve(m);
+    o.end = A.total;
+    return o;
+}
+static void frustum_reserve_recs(Arena& A, int M, FrustumOff& o) { o.rec = A.reserve(16 * (size_t)M); o.srch = A.reserve((size_t)M); }
+static FrustumDev frustum_dev(const Arena& A, const FrustumOff& o)
+{
+    return FrustumDev{A.dev<uint8_t>(o.iv), A.dev<float2>(o.xy), A.dev<float>(o.xr), A.dev<int32_t>(o.lv), A.dev<float>(o.vc),
+                      A.dev<float>(o.dp), A.dev<float>(o.ls), A.dev<uint8_t>(o.rs), A.dev<float4>(o.rec), A.dev<uint8_t>(o.srch)};
+}
+static void frustum_copy_out(const char* h, const FrustumOff& o, int M, const eorb_frustum_out& out)
+{
+    const size_t m = (size_t)M;
+    if (out.in_view) memcpy(out.in_view, h + o.iv, m);
+    if (out.proj_xy) memcpy(out.proj_xy, h + o.xy, 8 * m);
+    if (out.proj_xr) memcpy(out.proj_xr, h + o.xr, 4 * m);
+    if (out.level) memcpy(out.level, h + o.lv, 4 * m);
+    if (out.view_cos) memcpy(out.view_cos, h + o.vc, 4 * m);
+    if (out.depth) memcpy(out.depth, h + o.dp, 4 * m);
+    if (out.level_scale) memcpy(out.level_scale, h + o.ls, 4 * m);
+    if (out.reason) memcpy(out.reason, h + o.rs, m);
+}
+
+// the map points of mode A and their arena offsets
+struct PointsOff { size_t pos, nrm, mind, maxd, skip, orb; };
+static PointsOff points_in(Arena& A, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                           const uint8_t* skip, const uint8_t* is_orb)
+{
+    const size_t m = (size_t)M;
+    PointsOff o;
+    o.pos = A.in(pos, 12 * m); o.nrm = A.in(normal, normal ? 12 * m : 0);
+    o.mind = A.in(min_dist, min_dist ? 4 * m : 0); o.maxd = A.in(max_dist, max_dist ? 4 * m : 0);
+    o.skip = A.in(skip, skip ? m : 0); o.orb = A.in(is_orb, is_orb ? m : 0);
+    return o;
+}
+
+int eorb_project_frustum(eorb_ctx* c, const eorb_view* views, int nviews, int M, const float* pos, const float* normal,
+                         const float* min_dist, const float* max_dist, const uint8_t* skip, const uint8_t* mp_is_orb, float cos_limit,
+                         const eorb_frustum_out* out, int* n_in_view)
+{
+    if (!c) return EORB_E_ARG;
+    if (n_in_view) *n_in_view = 0;
+    if (M < 0 || nviews < 1 || nviews > 2 || !views || (M > 0 && (!pos || !normal || !min_dist || !max_dist)))
+        return set_err(c, EORB_E_ARG, "project_frustum: bad arguments");
+    int rc;
+    for (int v = 0; v < nviews; v++) if ((rc = view_check(c, "project_frustum", views + v, mp_is_orb != nullptr))) return rc;
+    fe_enter(c);
+    if (M == 0) return EORB_OK;
+    Arena A(c);
+    const PointsOff po = points_in(A, M, pos, normal, min_dist, max_dist, skip, mp_is_orb);
+    ViewOff vo[2] = {view_in(A, views), nviews > 1 ? view_in(A, views + 1) : ViewOff{0, 0}};
+    // outputs, contiguous: n_in_view | view 0 | view 1; then the matcher records (not downloaded)
+    const size_t o_n = A.reserve(16);
+    FrustumOff fo[2];
+    for (int v = 0; v < nviews; v++) fo[v] = frustum_reserve(A, M);
+    for (int v = 0; v < nviews; v++) frustum_reserve_recs(A, M, fo[v]);
+    if ((rc = A.upload())) return rc;
+    FrustumArgs F{};
+    for (int v = 0; v < nviews; v++) { F.V[v] = view_dev(A, views + v, vo[v]); F.O[v] = frustum_dev(A, fo[v]); }
+    F.nviews = nviews; F.M = M;
+    F.pos = A.dev<float>(po.pos); F.normal = A.dev<float>(po.nrm); F.min_dist = A.dev<float>(po.mind); F.max_dist = A.dev<float>(po.maxd);
+    F.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; F.is_orb = mp_is_orb ? A.dev<uint8_t>(po.orb) : nullptr;
+    F.cos_limit = cos_limit; F.far = 0; F.th_far = 0.f; F.n_in_view = A.dev<int32_t>(o_n);
+    if ((rc = project_frustum_dev(c, F))) return rc;
+    const char* h;
+    if ((rc = A.download(o_n, fo[nviews - 1].end - o_n, &h))) return rc;
+    if (out) for (int v = 0; v < nviews; v++) frustum_copy_out(h, fo[v], M, out[v]);
+    if (n_in_view) *n_in_view = *(const int32_t*)(h + o_n);
+    return EORB_OK;
+}
+
+static int last_octave_check(eorb_ctx* c, const char* who, const eorb_view* v, const eorb_keypoint* kps, const uint8_t* is_orb, int n)
+{
+    for (int i = 0; i < n; i++) {
+        const int nl = (is_orb && !is_orb[i] && v->ak_nlevels > 0) ? v->ak_nlevels : v->nlevels;
+        if (kps[i].octave < 0 || kps[i].octave >= nl) return set_err(c, EORB_E_ARG, "%s: keypoint %d has octave %d outside [0, %d)", who, i, kps[i].octave, nl);
+    }
+    return EORB_OK;
+}
+
+int eorb_project_last_frame(eorb_ctx* c, const eorb_view* view, const eorb_camera* cam_r, const float* Trl, int n, const float* pos,
+                            const uint8_t* skip, const eorb_keypoint* last_kps, const uint8_t* last_is_orb,
+                            uint8_t* valid, float* uv, float* proj_ur, float* level_scale, float* uv_r)
+{
+    if (!c) return EORB_E_ARG;
+    if (n < 0 || (n > 0 && (!pos || !last_kps)) || ((Trl != nullptr) != (cam_r != nullptr)) || (uv_r && !Trl))
+        return set_err(c, EORB_E_ARG, "project_last_frame: bad arguments");
+    int rc;
+    if ((rc = view_check(c, "project_last_frame", view, last_is_orb != nullptr))) return rc;
+    if (cam_r && cam_r->model != 0 && cam_r->model != 1) return set_err(c, EORB_E_ARG, "project_last_frame: camera model %d", cam_r->model);
+    if ((rc = last_octave_check(c, "project_last_frame", view, last_kps, last_is_orb, n))) return rc;
+    fe_enter(c);
+    if (n == 0) return EORB_OK;
+    const size_t m = (size_t)n;
+    Arena A(c);
+    const size_t o_pos = A.in(pos, 12 * m), o_skip = A.in(skip, skip ? m : 0), o_k = A.in(last_kps, sizeof(eorb_keypoint) * m);
+    const size_t o_orb = A.in(last_is_orb, last_is_orb ? m : 0);
+    const ViewOff vo = view_in(A, view);
+    // outputs, contiguous: valid | uv | proj_ur | level_scale | uv_r; then the matcher's record
+    const size_t o_va = A.reserve(m), o_uv = A.reserve(8 * m), o_ur = A.reserve(4 * m), o_ls = A.reserve(4 * m), o_uvr = A.reserve(8 * m);
+    const size_t o_end = A.total, o_rec = A.reserve(12 * m);
+    if ((rc = A.upload())) return rc;
+    LastArgs L{};
+    L.V = view_dev(A, view, vo);
+    L.has_r = Trl ? 1 : 0;
+    if (Trl) { L.cam_r = warp_cam_of(*cam_r); memcpy(L.Trl, Trl, sizeof(L.Trl)); }
+    L.n = n; L.pos = A.dev<float>(o_pos); L.skip = skip ? A.dev<uint8_t>(o_skip) : nullptr; L.kps = A.dev<eorb_keypoint>(o_k);
+    L.is_orb = last_is_orb ? A.dev<uint8_t>(o_orb) : nullptr;
+    L.valid = A.dev<uint8_t>(o_va); L.uv = A.dev<float2>(o_uv); L.proj_ur = A.dev<float>(o_ur); L.level_scale = A.dev<float>(o_ls);
+    L.uv_r = A.dev<float2>(o_uvr); L.rec3 = A.dev<float>(o_rec);
+    if ((rc = project_last_dev(c, L))) return rc;
+    const char* h;
+    if ((rc = A.download(o_va, o_end - o_va, &h))) return rc;
+    if (valid) memcpy(valid, h + o_va, m);
+    if (uv) memcpy(uv, h + o_uv, 8 * m);
+    if (proj_ur) memcpy(proj_ur, h + o_ur, 4 * m);
+    if (level_scale) memcpy(level_scale, h + o_ls, 4 * m);
+    if (uv_r) memcpy(uv_r, h + o_uvr, 8 * m);
+    return EORB_OK;
+}
+
+int eorb_project_keyframe_points(eorb_ctx* c, const eorb_view* view, int n, const float* pos, const float* min_dist,
+                                 const float* max_dist, const uint8_t* skip, const uint8_t* mp_is_orb,
+                                 uint8_t* valid, float* uv, int32_t* level, float* level_scale, float* dist3d)
+{
+    if (!c) return EORB_E_ARG;
+    if (n < 0 || (n > 0 && (!pos || !min_dist || !max_dist))) return set_err(c, EORB_E_ARG, "project_keyframe_points: bad arguments");
+    int rc;
+    if ((rc = view_check(c, "project_keyframe_points", view, mp_is_orb != nullptr))) return rc;
+    fe_enter(c);
+    if (n == 0) return EORB_OK;
+    const size_t m = (size_t)n;
+    Arena A(c);
+    const PointsOff po = points_in(A, n, pos, nullptr, min_dist, max_dist, skip, mp_is_orb);
+    const ViewOff vo = view_in(A, view);
+    const size_t o_va = A.reserve(m), o_uv = A.reserve(8 * m), o_lv = A.reserve(4 * m), o_ls = A.reserve(4 * m), o_d3 = A.reserve(4 * m);
+    const size_t o_end = A.total, o_rec = A.reserve(12 * m);
+    if ((rc = A.upload())) return rc;
+    KfArgs K{};
+    K.V = view_dev(A, view, vo);
+    K.n = n; K.pos = A.dev<float>(po.pos); K.min_dist = A.dev<float>(po.mind); K.max_dist = A.dev<float>(po.maxd);
+    K.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; K.is_orb = mp_is_orb ? A.dev<uint8_t>(po.orb) : nullptr;
+    K.valid = A.dev<uint8_t>(o_va); K.uv = A.dev<float2>(o_uv); K.level = A.dev<int32_t>(o_lv); K.level_scale = A.dev<float>(o_ls);
+    K.dist3d = A.dev<float>(o_d3); K.rec3 = A.dev<float>(o_rec);
+    if ((rc = project_kf_dev(c, K))) return rc;
+    const char* h;
+    if ((rc = A.download(o_va, o_end - o_va, &h))) return rc;
+    if (valid) memcpy(valid, h + o_va, m);
+    if (uv) memcpy(uv, h + o_uv, 8 * m);
+    if (level) memcpy(level, h + o_lv, 4 * m);
+    if (level_scale) memcpy(level_scale, h + o_ls, 4 * m);
+    if (dist3d) memcpy(dist3d, h + o_d3, 4 * m);
+    return EORB_OK;
+}
+
+int eorb_search_local_points(eorb_ctx* c,
+        const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const uint8_t* is_orb,
+        const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+        const uint8_t* skip, const uint8_t* mp_is_orb, float cos_limit,
+        const uint8_t* mp_desc, const uint8_t* mp_obs, const eorb_grid_bounds* gb, int32_t* frame_mp, float th, float nnratio,
+        const float* uright, int bFarPoints, float thFarPoints,
+        const eorb_frustum_out* out, int* n_in_view, int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    if (nmatches) *nmatches = 0;
+    if (n_in_view) *n_in_view = 0;
+    if (n < 0 || M < 0 || !gb || !frame_mp || stride < 32 || (n > 0 && (!kps || !desc)) ||
+        (M > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !mp_obs)))
+        return set_err(c, EORB_E_ARG, "search_local_points: bad arguments");
+    int rc;
+    if ((rc = view_check(c, "search_local_points", view, mp_is_orb != nullptr))) return rc;
+    fe_enter(c);
+    if (M == 0) return EORB_OK;
+    Arena A(c);
+    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)n), o_d = A.in(desc, (size_t)stride * n), o_o = A.in(is_orb, is_orb ? n : 0);
+    const size_t o_md = A.in(mp_desc, 32 * (size_t)M), o_ob = A.in(mp_obs, M);
+    const size_t o_ur2 = A.in(uright, uright ? sizeof(float) * (size_t)n : 0);
+    const PointsOff po = points_in(A, M, pos, normal, min_dist, max_dist, skip, mp_is_orb);
+    const ViewOff vo = view_in(A, view);
+    // outputs, contiguous: {nmatches, n_in_view} | slots (in/out) | the projection arrays
+    const size_t o_nm = A.in(nullptr, 16);
+    const size_t o_fm = A.in(frame_mp, sizeof(int32_t) * (size_t)n);
+    FrustumOff fo = frustum_reserve(A, M);
+    frustum_reserve_recs(A, M, fo);
+    if ((rc = A.upload())) return rc;
+    FrustumArgs F{};
+    F.V[0] = view_dev(A, view, vo); F.O[0] = frustum_dev(A, fo);
+    F.nviews = 1; F.M = M;
+    F.pos = A.dev<float>(po.pos); F.normal = A.dev<float>(po.nrm); F.min_dist = A.dev<float>(po.mind); F.max_dist = A.dev<float>(po.maxd);
+    F.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; F.is_orb = mp_is_orb ? A.dev<uint8_t>(po.orb) : nullptr;
+    F.cos_limit = cos_limit; F.far = bFarPoints != 0; F.th_far = thFarPoints; F.n_in_view = A.dev<int32_t>(o_nm) + 1;
+    if ((rc = project_frustum_dev(c, F))) return rc;
+    if (n > 0) {
+        rc = search_proj_map_dev(c, A.dev<eorb_keypoint>(o_k), n, A.dev<uint8_t>(o_d), stride, is_orb ? A.dev<uint8_t>(o_o) : nullptr, M,
+                                 F.O[0].search, F.O[0].rec, F.O[0].level, A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob),
+                                 mp_is_orb ? A.dev<uint8_t>(po.orb) : nullptr, *gb, A.dev<int32_t>(o_fm), th, nnratio, A.dev<int32_t>(o_nm),
+                                 uright ? A.dev<float>(o_ur2) : nullptr, uright ? F.O[0].proj_xr : nullptr);
+        if (rc) return rc;
+    } else EORB_HIP(c, hipMemsetAsync(A.dev<int32_t>(o_nm), 0, sizeof(int32_t), c->stream));
+    const char* h;
+    if ((rc = A.download(o_nm, (out ? fo.end : o_fm + sizeof(int32_t) * (size_t)n) - o_nm, &h))) return rc;
+    memcpy(frame_mp, h + o_fm, sizeof(int32_t) * (size_t)n);
+    if (out) frustum_copy_out(h, fo, M, *out);
+    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
+    if (n_in_view) *n_in_view = *((const int32_t*)(h + o_nm) + 1);
+    return EORB_OK;
+}
+
+int eorb_search_local_points_fisheye(eorb_ctx* c,
+        const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride, const int32_t* l2r, const int32_t* r2l,
+        const eorb_view* views, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+        const uint8_t* skip, float cos_limit,
+        const uint8_t* mp_desc, const uint8_t* mp_obs, const eorb_grid_bounds* gb, int32_t* frame_mp, float th, float nnratio,
+        int bFarPoints, float thFarPoints,
+        const eorb_frustum_out* out, int* n_in_view, int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    if (nmatches) *nmatches = 0;
+    if (n_in_view) *n_in_view = 0;
+    if (!gb || M < 0 || !views || (M > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !mp_obs)) || (nL > 0 && !l2r) || (nR > 0 && !r2l))
+        return set_err(c, EORB_E_ARG, "search_local_points_fisheye: bad arguments");
+    int rc;
+    for (int v = 0; v < 2; v++) if ((rc = view_check(c, "search_local_points_fisheye", views + v, false))) return rc;
+    if ((rc = twocam_frame_check(c, "search_local_points_fisheye", kps, nL, nR, desc, stride, frame_mp, M))) return rc;
+    for (int i = 0; i < nL; i++) if (l2r[i] < -1 || l2r[i] >= nR) return set_err(c, EORB_E_ARG, "search_local_points_fisheye: l2r[%d] = %d", i, l2r[i]);
+    for (int i = 0; i < nR; i++) if (r2l[i] < -1 || r2l[i] >= nL) return set_err(c, EORB_E_ARG, "search_local_points_fisheye: r2l[%d] = %d", i, r2l[i]);
+    fe_enter(c);
+    const int nT = nL + nR;
+    if (M == 0) return EORB_OK;
+    Arena A(c);
+    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)nT), o_d = A.in(desc, (size_t)stride * nT);
+    const size_t o_l2r = A.in(l2r, sizeof(int32_t) * (size_t)nL), o_r2l = A.in(r2l, sizeof(int32_t) * (size_t)nR);
+    const size_t o_md = A.in(mp_desc, 32 * (size_t)M), o_ob = A.in(mp_obs, M);
+    const PointsOff po = points_in(A, M, pos, normal, min_dist, max_dist, skip, nullptr);
+    const ViewOff vo[2] = {view_in(A, views), view_in(A, views + 1)};
+    const size_t o_nm = A.in(nullptr, 16);
+    const size_t o_fm = A.in(frame_mp, sizeof(int32_t) * (size_t)nT);
+    FrustumOff fo[2];
+    for (int v = 0; v < 2; v++) fo[v] = frustum_reserve(A, M);
+    // the two views' records back to back: the two-camera matcher reads qf_r = qf + M in the host-buffer entry point, any pointer here
+    for (int v = 0; v < 2; v++) frustum_reserve_recs(A, M, fo[v]);
+    if ((rc = A.upload())) return rc;
+    FrustumArgs F{};
+    for (int v = 0; v < 2; v++) { F.V[v] = view_dev(A, views + v, vo[v]); F.O[v] = frustum_dev(A, fo[v]); }
+    F.nviews = 2; F.M = M;
+    F.pos = A.dev<float>(po.pos); F.normal = A.dev<float>(po.nrm); F.min_dist = A.dev<float>(po.mind); F.max_dist = A.dev<float>(po.maxd);
+    F.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; F.is_orb = nullptr;
+    F.cos_limit = cos_limit; F.far = bFarPoints != 0; F.th_far = thFarPoints; F.n_in_view = A.dev<int32_t>(o_nm) + 1;
+    if ((rc = project_frustum_dev(c, F))) return rc;
+    if (nT > 0) {
+        TcArgs T{};
+        T.kps = A.dev<eorb_keypoint>(o_k); T.nL = nL; T.nR = nR; T.desc = A.dev<uint8_t>(o_d); T.stride = stride;
+        T.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
+        T.nq = M; T.mp_desc = A.dev<uint8_t>(o_md); T.mp_obs = A.dev<uint8_t>(o_ob); T.th = th; T.nnratio = nnratio;
+        T.in_view = F.O[0].search; T.qf = F.O[0].rec; T.qlevel = F.O[0].level;
+        T.in_view_r = F.O[1].search; T.qf_r = F.O[1].rec; T.qlevel_r = F.O[1].level;
+        T.l2r = A.dev<int32_t>(o_l2r); T.r2l = A.dev<int32_t>(o_r2l);
+        T.slots = A.dev<int32_t>(o_fm); T.nmatches = A.dev<int32_t>(o_nm);
+        if ((rc = twocam_walk_dev(c, 0, T))) return rc;
+    } else EORB_HIP(c, hipMemsetAsync(A.dev<int32_t>(o_nm), 0, sizeof(int32_t), c->stream));
+    const char* h;
+    if ((rc = A.download(o_nm, (out ? fo[1].end : o_fm + sizeof(int32_t) * (size_t)nT) - o_nm, &h))) return rc;
+    memcpy(frame_mp, h + o_fm, sizeof(int32_t) * (size_t)nT);
+    if (out) for (int v = 0; v < 2; v++) frustum_copy_out(h, fo[v], M, out[v]);
+    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
+    if (n_in_view) *n_in_view = *((const int32_t*)(h + o_nm) + 1);
+    return EORB_OK;
+}
+
+// modes B and C in front of the last-frame matcher.  kf: the semantics of eorb_search_by_projection_kf (query level = the predicted
+// level, every occupied slot skipped, ORBdist in place of TH_HIGH)
+static int proj_pose_common(eorb_ctx* c, const char* who, bool kf,
+        const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride, const uint8_t* cur_is_orb,
+        const eorb_view* view, const eorb_keypoint* q_kps, int nq, const uint8_t* q_is_orb,
+        const float* pos, const float* min_dist, const float* max_dist, const uint8_t* skip, const uint8_t* mp_desc, const uint8_t* mp_obs,
+        const eorb_grid_bounds* gb, int32_t* cur_mp, float th, int mode, int checkOri, int dist_th, const float* cur_uright,
+        uint8_t* valid, float* uv, int32_t* level, int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    if (nmatches) *nmatches = 0;
+    if (n_cur < 0 || nq < 0 || !gb || !cur_mp || cur_stride < 32 || (n_cur > 0 && (!cur_kps || !cur_desc)) ||
+        (nq > 0 && (!q_kps || !pos || !mp_desc || (kf ? (!min_dist || !max_dist) : !mp_obs))) || mode < 0 || mode > 2)
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
+    int rc;
+    if ((rc = view_check(c, who, view, q_is_orb != nullptr))) return rc;
+    if (!kf && (rc = last_octave_check(c, who, view, q_kps, q_is_orb, nq))) return rc;
+    fe_enter(c);
+    if (nq == 0) return EORB_OK;
+    const size_t m = (size_t)nq;
+    std::vector<uint8_t> obs;
+    std::vector<int32_t> slots;
+    if (kf) {
+        obs.assign(m, 1);
+        slots.assign(cur_mp, cur_mp + n_cur);
+        for (int i = 0; i < n_cur; i++) if (slots[i] != -1) slots[i] = -2;
+    }
+    Arena A(c);
+    const size_t o_ck = A.in(cur_kps, sizeof(eorb_keypoint) * (size_t)n_cur), o_cd = A.in(cur_desc, (size_t)cur_stride * n_cur);
+    const size_t o_co = A.in(cur_is_orb, cur_is_orb ? n_cur : 0);
+    const size_t o_qk = A.in(q_kps, sizeof(eorb_keypoint) * m), o_qo = A.in(q_is_orb, q_is_orb ? m : 0);
+    const size_t o_md = A.in(mp_desc, 32 * m), o_ob = A.in(kf ? obs.data() : mp_obs, m);
+    const size_t o_ur2 = A.in(cur_uright, cur_uright ? sizeof(float) * (size_t)n_cur : 0);
+    const PointsOff po = points_in(A, nq, pos, nullptr, min_dist, max_dist, skip, nullptr);
+    const ViewOff vo = view_in(A, view);
+    // outputs, contiguous: nmatches | slots (in/out) | valid | uv | level
+    const size_t o_nm = A.in(nullptr, 16);
+    const size_t o_mp = A.in(kf ? slots.data() : cur_mp, sizeof(int32_t) * (size_t)n_cur);
+    const size_t o_va = A.reserve(m), o_uv = A.reserve(8 * m), o_lv = A.reserve(4 * m);
+    const size_t o_end = A.total;
+    const size_t o_ls = A.reserve(4 * m), o_x = A.reserve(4 * m), o_uvr = A.reserve(8 * m), o_rec = A.reserve(12 * m);
+    const size_t o_q2 = A.reserve(sizeof(eorb_keypoint) * m);
+    if ((rc = A.upload())) return rc;
+    const eorb_keypoint* d_q = A.dev<eorb_keypoint>(o_qk);
+    const uint8_t* d_qo = q_is_orb ? A.dev<uint8_t>(o_qo) : nullptr;
+    if (kf) {
+        KfArgs K{};
+        K.V = view_dev(A, view, vo);
+        K.n = nq; K.pos = A.dev<float>(po.pos); K.min_dist = A.dev<float>(po.mind); K.max_dist = A.dev<float>(po.maxd);
+        K.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; K.is_orb = d_qo;
+        K.valid = A.dev<uint8_t>(o_va); K.uv = A.dev<float2>(o_uv); K.level = A.dev<int32_t>(o_lv); K.level_scale = A.dev<float>(o_ls);
+        K.dist3d = A.dev<float>(o_x); K.rec3 = A.dev<float>(o_rec); K.kf_kps = d_q; K.q_kps = A.dev<eorb_keypoint>(o_q2);
+        if ((rc = project_kf_dev(c, K))) return rc;
+        d_q = K.q_kps;
+    } else {
+        LastArgs L{};
+        L.V = view_dev(A, view, vo);
+        L.n = nq; L.pos = A.dev<float>(po.pos); L.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; L.kps = d_q; L.is_orb = d_qo;
+        L.valid = A.dev<uint8_t>(o_va); L.uv = A.dev<float2>(o_uv); L.proj_ur = A.dev<float>(o_x); L.level_scale = A.dev<float>(o_ls);
+        L.uv_r = A.dev<float2>(o_uvr); L.rec3 = A.dev<float>(o_rec);
+        if ((rc = project_last_dev(c, L))) return rc;
+    }
+    if (n_cur > 0) {
+        rc = search_proj_last_dev(c, A.dev<eorb_keypoint>(o_ck), n_cur, A.dev<uint8_t>(o_cd), cur_stride,
+                                  cur_is_orb ? A.dev<uint8_t>(o_co) : nullptr, d_q, nq, d_qo, A.dev<uint8_t>(o_va), A.dev<float>(o_rec),
+                                  A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob), dist_th, *gb, A.dev<int32_t>(o_mp), th, mode, checkOri,
+                                  A.dev<int32_t>(o_nm), cur_uright ? A.dev<float>(o_ur2) : nullptr, cur_uright ? A.dev<float>(o_x) : nullptr);
+        if (rc) return rc;
+    } else EORB_HIP(c, hipMemsetAsync(A.dev<int32_t>(o_nm), 0, sizeof(int32_t), c->stream));
+    const char* h;
+    const bool proj_out = valid || uv || level;
+    if ((rc = A.download(o_nm, (proj_out ? o_end : o_mp + sizeof(int32_t) * (size_t)n_cur) - o_nm, &h))) return rc;
+    const int32_t* hs = (const int32_t*)(h + o_mp);
+    if (kf) { for (int i = 0; i < n_cur; i++) if (hs[i] >= 0) cur_mp[i] = hs[i]; }
+    else memcpy(cur_mp, hs, sizeof(int32_t) * (size_t)n_cur);
+    if (valid) memcpy(valid, h + o_va, m);
+    if (uv) memcpy(uv, h + o_uv, 8 * m);
+    if (level) memcpy(level, h + o_lv, 4 * m);
+    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
+    return EORB_OK;
+}
+
+int eorb_search_by_projection_last_pose(eorb_ctx* c,
+        const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride, const uint8_t* cur_is_orb,
+        const eorb_view* view, const eorb_keypoint* last_kps, int n_last, const uint8_t* last_is_orb,
+        const float* pos, const uint8_t* skip, const uint8_t* mp_desc, const uint8_t* mp_obs,
+        const eorb_grid_bounds* gb, int32_t* cur_mp, float th, int mode, int checkOri, const float* cur_uright,
+        uint8_t* valid, float* uv, int* nmatches)
+{
+    return proj_pose_common(c, "search_by_projection_last_pose", false, cur_kps, n_cur, cur_desc, cur_stride, cur_is_orb, view, last_kps, n_last,
+                            last_is_orb, pos, nullptr, nullptr, skip, mp_desc, mp_obs, gb, cur_mp, th, mode, checkOri, 100 /* TH_HIGH */,
+                            cur_uright, valid, uv, nullptr, nmatches);
+}
+
+int eorb_search_by_projection_kf_pose(eorb_ctx* c,
+        const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride, const uint8_t* cur_is_orb,
+        const eorb_view* view, const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_is_orb,
+        const float* pos, const float* min_dist, const float* max_dist, const uint8_t* skip, const uint8_t* mp_desc,
+        const eorb_grid_bounds* gb, int32_t* cur_mp, float th, int ORBdist, int checkOri,
+        uint8_t* valid, float* uv, int32_t* level, int* nmatches)
+{
+    return proj_pose_common(c, "search_by_projection_kf_pose", true, cur_kps, n_cur, cur_desc, cur_stride, cur_is_orb, view, kf_kps, n_kf,
+                            kf_is_orb, pos, min_dist, max_dist, skip, mp_desc, nullptr, gb, cur_mp, th, 0, checkOri, ORBdist,
+                            nullptr, valid, uv, level, nmatches);
 }
 
 static int bow_common(eorb_ctx* c, int kf_kf,

@@ -2536,6 +2536,7 @@ __global__ void ev_mathhash_kernel(int which, uint32_t lo_bits, uint32_t hi_bits
         if (which == 0) y = dev_expf_nonpos<true>(-x, tab);
         else if (which == 3) y = dev_tanf(x);
         else if (which == 4) y = dev_atanf(x);
+        else if (which == 6) y = dev_logf(x);
         else { float sn, cs; dev_sincosf(x, &sn, &cs); y = (which == 1) ? sn : cs; }
         h += (((unsigned long long)ub * 0x9E3779B97F4A7C15ull) ^ (unsigned long long)__float_as_uint(y)) * 0xC2B2AE3D27D4EB4Full;
     }

@@ -572,6 +572,181 @@ class ORBmatcher:
         return nm.value, cm
 
 
+# ---- map points projected on the device (eorb_project_* and the fused searches of include/eorb_fe.h) ------------------------------
+def view(R, t, Ow, cam, bounds, nlevels, log_scale, scale_factors, mbf=0.0, ak_nlevels=0, ak_log_scale=0.0, ak_scale_factors=None):
+    """eorb_view: R 3x3 / t / Ow = mRcw, mtcw, mOw (the right camera's: Frame.cc:1257-1263); cam as _lib.camera takes it;
+    bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY); the ORB (and, for a MixedFrame, AKAZE) level count, log scale factor and scale factors"""
+    v = _lib.View()
+    for dst, src, k in ((v.R, R, 9), (v.t, t, 3), (v.Ow, Ow, 3)):
+        a = np.asarray(src, np.float32).reshape(-1)
+        for i in range(k):
+            dst[i] = float(a[i])
+    v.cam = cam if isinstance(cam, _lib.Camera) else _lib.camera(cam)
+    v.minX, v.maxX, v.minY, v.maxY = [float(b) for b in bounds]
+    v.mbf = float(mbf)
+    v.nlevels = int(nlevels); v.log_scale = float(log_scale)
+    v._sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, np.float32)      # (kept alive with the record)
+    v.scale_factors = None if v._sf is None else v._sf.ctypes.data
+    v.ak_nlevels = int(ak_nlevels); v.ak_log_scale = float(ak_log_scale)
+    v._ak = None if ak_scale_factors is None else np.ascontiguousarray(ak_scale_factors, np.float32)
+    v.ak_scale_factors = None if v._ak is None else v._ak.ctypes.data
+    return v
+
+
+def _views(views):
+    """one eorb_view or a (left, right) pair -> (ctypes array, count)"""
+    vs = [views] if isinstance(views, _lib.View) else list(views)
+    arr = (_lib.View * len(vs))(*vs)
+    arr._keep = vs
+    return arr, len(vs)
+
+
+_FRUSTUM_FIELDS = (("in_view", np.uint8, 1), ("proj_xy", np.float32, 2), ("proj_xr", np.float32, 1), ("level", np.int32, 1),
+                   ("view_cos", np.float32, 1), ("depth", np.float32, 1), ("level_scale", np.float32, 1), ("reason", np.uint8, 1))
+
+
+def _frustum_out(nviews, M):
+    """-> (ctypes array of eorb_frustum_out, list of dicts of the arrays behind it)"""
+    recs = (_lib.FrustumOut * nviews)()
+    outs = []
+    for v in range(nviews):
+        d = {}
+        for name, dt, k in _FRUSTUM_FIELDS:
+            d[name] = np.zeros((M, k) if k > 1 else M, dt)
+            setattr(recs[v], name, d[name].ctypes.data if M else None)
+        outs.append(d)
+    return recs, outs
+
+
+def _points(pos, normal, min_dist, max_dist, skip, mp_is_orb):
+    f = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)
+    return f(pos, np.float32), f(normal, np.float32), f(min_dist, np.float32), f(max_dist, np.float32), f(skip, np.uint8), f(mp_is_orb, np.uint8)
+
+
+def isInFrustum(views, pos, normal, min_dist, max_dist, viewingCosLimit=0.5, skip=None, mp_is_orb=None, ctx=None):
+    """Frame::isInFrustum over M map points (src/Frame.cc:548-637): views = one eorb_view (Nleft == -1) or (left, right).
+    -> (n_in_view, out) with out a dict per view: in_view, proj_xy, proj_xr, level, view_cos, depth, level_scale, reason (one dict,
+    not a list, for a single view)."""
+    c = ctx or default_context()
+    pos, normal, min_dist, max_dist, skip, mp_is_orb = _points(pos, normal, min_dist, max_dist, skip, mp_is_orb)
+    M = len(min_dist)
+    va, nv = _views(views)
+    recs, outs = _frustum_out(nv, M)
+    n = C.c_int(0)
+    c.check(c.L.eorb_project_frustum(c.h, va, nv, M, _p(pos), _p(normal), _p(min_dist), _p(max_dist), _p(skip), _p(mp_is_orb),
+                                     float(viewingCosLimit), recs, C.byref(n)))
+    return n.value, (outs[0] if isinstance(views, _lib.View) else outs)
+
+
+def ProjectLastFrame(view_, pos, last_kps, skip=None, last_is_orb=None, cam_r=None, Trl=None, ctx=None):
+    """the projection of SearchByProjection(CurrentFrame, LastFrame) (src/ORBmatcher.cc:1999-2022, :2092-2095).
+    -> dict(valid, uv, proj_ur, level_scale[, uv_r with cam_r and Trl = (R | t), 12 floats])"""
+    c = ctx or default_context()
+    pos = np.ascontiguousarray(pos, np.float32); kps = np.ascontiguousarray(last_kps, KP_DTYPE); n = len(kps)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    lio = None if last_is_orb is None else np.ascontiguousarray(last_is_orb, np.uint8)
+    o = dict(valid=np.zeros(n, np.uint8), uv=np.zeros((n, 2), np.float32), proj_ur=np.zeros(n, np.float32), level_scale=np.zeros(n, np.float32))
+    camr = trl = None
+    if Trl is not None:
+        camr = cam_r if isinstance(cam_r, _lib.Camera) else _lib.camera(cam_r)
+        trl = np.ascontiguousarray(Trl, np.float32).reshape(12)
+        o["uv_r"] = np.zeros((n, 2), np.float32)
+    c.check(c.L.eorb_project_last_frame(c.h, C.byref(view_), None if camr is None else C.byref(camr), _p(trl), n, _p(pos), _p(skip), _p(kps),
+                                        _p(lio), _p(o["valid"]), _p(o["uv"]), _p(o["proj_ur"]), _p(o["level_scale"]), _p(o.get("uv_r"))))
+    return o
+
+
+def ProjectKeyFramePoints(view_, pos, min_dist, max_dist, skip=None, mp_is_orb=None, ctx=None):
+    """the projection of SearchByProjection(CurrentFrame, pKF, sAlreadyFound) (src/ORBmatcher.cc:2215-2239)
+    -> dict(valid, uv, level, level_scale, dist3d)"""
+    c = ctx or default_context()
+    pos, _, min_dist, max_dist, skip, mp_is_orb = _points(pos, None, min_dist, max_dist, skip, mp_is_orb)
+    n = len(min_dist)
+    o = dict(valid=np.zeros(n, np.uint8), uv=np.zeros((n, 2), np.float32), level=np.zeros(n, np.int32), level_scale=np.zeros(n, np.float32),
+             dist3d=np.zeros(n, np.float32))
+    c.check(c.L.eorb_project_keyframe_points(c.h, C.byref(view_), n, _p(pos), _p(min_dist), _p(max_dist), _p(skip), _p(mp_is_orb),
+                                             _p(o["valid"]), _p(o["uv"]), _p(o["level"]), _p(o["level_scale"]), _p(o["dist3d"])))
+    return o
+
+
+def SearchLocalPoints(F, view_, pos, normal, min_dist, max_dist, mp_desc, mp_obs, frame_mp, th=1.0, nnratio=0.8, viewingCosLimit=0.5,
+                      skip=None, mp_is_orb=None, uright=None, bFarPoints=False, thFarPoints=0.0, ctx=None):
+    """Tracking::SearchLocalPoints for a one-camera frame (src/Tracking.cc:2390-2430): isInFrustum and SearchByProjection(F,
+    vpMapPoints, th, bFarPoints, thFarPoints) in one call.  -> (nmatches, frame_mp, n_in_view, projection dict)"""
+    c = ctx or default_context()
+    pos, normal, min_dist, max_dist, skip, mp_is_orb = _points(pos, normal, min_dist, max_dist, skip, mp_is_orb)
+    M = len(min_dist)
+    mp_desc = np.ascontiguousarray(mp_desc, np.uint8); mp_obs = np.ascontiguousarray(mp_obs, np.uint8)
+    ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+    fm = np.ascontiguousarray(frame_mp, np.int32).copy()
+    recs, outs = _frustum_out(1, M)
+    nm, nv = C.c_int(0), C.c_int(0)
+    c.check(c.L.eorb_search_local_points(c.h, _p(F.kps), F.N, _p(F.desc), F.desc.shape[1] if F.desc.ndim == 2 else 32, _p(F.is_orb),
+                                         C.byref(view_), M, _p(pos), _p(normal), _p(min_dist), _p(max_dist), _p(skip), _p(mp_is_orb),
+                                         float(viewingCosLimit), _p(mp_desc), _p(mp_obs), C.byref(F.gb), _p(fm), float(th), float(nnratio),
+                                         _p(ur), int(bFarPoints), float(thFarPoints), recs, C.byref(nv), C.byref(nm)))
+    return nm.value, fm, nv.value, outs[0]
+
+
+def SearchLocalPointsFisheye(kps, nL, desc, l2r, r2l, gb, views, pos, normal, min_dist, max_dist, mp_desc, mp_obs, frame_mp, th=1.0,
+                             nnratio=0.8, viewingCosLimit=0.5, skip=None, bFarPoints=False, thFarPoints=0.0, ctx=None):
+    """the same for a two-camera frame: views = (left, right).  -> (nmatches, frame_mp, n_in_view, [left dict, right dict])"""
+    c = ctx or default_context()
+    kps = np.ascontiguousarray(kps, KP_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
+    nR = len(kps) - nL
+    l2r = np.ascontiguousarray(l2r, np.int32); r2l = np.ascontiguousarray(r2l, np.int32)
+    if nR < 0 or len(l2r) != nL or len(r2l) != nR or len(desc) != len(kps):
+        raise ValueError("kps / desc hold nL + nR rows, l2r nL and r2l nR")
+    pos, normal, min_dist, max_dist, skip, _ = _points(pos, normal, min_dist, max_dist, skip, None)
+    M = len(min_dist)
+    mp_desc = np.ascontiguousarray(mp_desc, np.uint8); mp_obs = np.ascontiguousarray(mp_obs, np.uint8)
+    fm = np.ascontiguousarray(frame_mp, np.int32).copy()
+    va, nviews = _views(views)
+    if nviews != 2:
+        raise ValueError("a two-camera frame has two views")
+    recs, outs = _frustum_out(2, M)
+    nm, nv = C.c_int(0), C.c_int(0)
+    c.check(c.L.eorb_search_local_points_fisheye(c.h, _p(kps), nL, nR, _p(desc), desc.shape[1] if desc.ndim == 2 else 32, _p(l2r), _p(r2l),
+                                                 va, M, _p(pos), _p(normal), _p(min_dist), _p(max_dist), _p(skip), float(viewingCosLimit),
+                                                 _p(mp_desc), _p(mp_obs), C.byref(gb), _p(fm), float(th), float(nnratio), int(bFarPoints),
+                                                 float(thFarPoints), recs, C.byref(nv), C.byref(nm)))
+    return nm.value, fm, nv.value, outs
+
+
+def SearchByProjectionLastPose(Cur, view_, Last, pos, mp_desc, mp_obs, cur_mp, th, mode=0, checkOri=True, skip=None, uright=None, ctx=None):
+    """TrackWithMotionModel's search: the projection of the last frame's points and SearchByProjection(CurrentFrame, LastFrame, th,
+    bMono) in one call.  -> (nmatches, cur_mp, valid, uv)"""
+    c = ctx or default_context()
+    pos = np.ascontiguousarray(pos, np.float32)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    mp_desc = np.ascontiguousarray(mp_desc, np.uint8); mp_obs = np.ascontiguousarray(mp_obs, np.uint8)
+    ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+    cm = np.ascontiguousarray(cur_mp, np.int32).copy(); nm = C.c_int(0)
+    valid = np.zeros(Last.N, np.uint8); uv = np.zeros((Last.N, 2), np.float32)
+    c.check(c.L.eorb_search_by_projection_last_pose(c.h, _p(Cur.kps), Cur.N, _p(Cur.desc), Cur.desc.shape[1] if Cur.desc.ndim == 2 else 32,
+                                                    _p(Cur.is_orb), C.byref(view_), _p(Last.kps), Last.N, _p(Last.is_orb), _p(pos), _p(skip),
+                                                    _p(mp_desc), _p(mp_obs), C.byref(Cur.gb), _p(cm), float(th), int(mode), int(checkOri),
+                                                    _p(ur), _p(valid), _p(uv), C.byref(nm)))
+    return nm.value, cm, valid, uv
+
+
+def SearchByProjectionKFPose(Cur, view_, kf_kps, pos, min_dist, max_dist, mp_desc, cur_mp, th, ORBdist, checkOri=True, skip=None,
+                             kf_is_orb=None, ctx=None):
+    """Relocalization's search: the projection of pKF's map points and SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th,
+    ORBdist) in one call.  -> (nmatches, cur_mp, valid, uv, level)"""
+    c = ctx or default_context()
+    kf_kps = np.ascontiguousarray(kf_kps, KP_DTYPE); n = len(kf_kps)
+    pos, _, min_dist, max_dist, skip, kio = _points(pos, None, min_dist, max_dist, skip, kf_is_orb)
+    mp_desc = np.ascontiguousarray(mp_desc, np.uint8)
+    cm = np.ascontiguousarray(cur_mp, np.int32).copy(); nm = C.c_int(0)
+    valid = np.zeros(n, np.uint8); uv = np.zeros((n, 2), np.float32); level = np.zeros(n, np.int32)
+    c.check(c.L.eorb_search_by_projection_kf_pose(c.h, _p(Cur.kps), Cur.N, _p(Cur.desc), Cur.desc.shape[1] if Cur.desc.ndim == 2 else 32,
+                                                  _p(Cur.is_orb), C.byref(view_), _p(kf_kps), n, _p(kio), _p(pos), _p(min_dist), _p(max_dist),
+                                                  _p(skip), _p(mp_desc), C.byref(Cur.gb), _p(cm), float(th), int(ORBdist), int(checkOri),
+                                                  _p(valid), _p(uv), _p(level), C.byref(nm)))
+    return nm.value, cm, valid, uv, level
+
+
 def SearchByBoWFisheye(kf_kps, kf_desc, kf_has_mp, kf_fv, f_kps, nL, f_desc, f_fv, nnratio=0.7, checkOri=True, ctx=None):
     """The two-camera path of SearchByBoW(KeyFrame*, Frame&, ...) (src/ORBmatcher.cc:276-478): frame features = nL left, then right.
     Returns (nmatches, match_f)."""

@@ -537,8 +537,78 @@ struct FrameView {
     int numAllKPts() const { return (int)kps->size(); }
 };
 
+// the pose-dependent part of a Frame that Frame::isInFrustum reads (mRcw, mtcw, mOw, mpCamera, the image bounds, mbf and the ORB
+// scale tables): an eorb_view that owns its tables.  The right camera of a two-camera frame is a second FramePose with
+// Rrl*mRcw, Rrl*mtcw + trl and mRwc*tlr + mOw (Frame.cc:1257-1263).
+struct FramePose {
+    eorb_view v{};
+    std::vector<float> scaleFactors;
+    FramePose(const float Rcw[9], const float tcw[3], const float Ow[3], const eorb_camera& cam, const eorb_grid_bounds& gb, float mbf,
+              const std::vector<float>& mvScaleFactor, float logScaleFactor) : scaleFactors(mvScaleFactor) {
+        std::memcpy(v.R, Rcw, sizeof(v.R)); std::memcpy(v.t, tcw, sizeof(v.t)); std::memcpy(v.Ow, Ow, sizeof(v.Ow));
+        v.cam = cam; v.minX = gb.minX; v.maxX = gb.maxX; v.minY = gb.minY; v.maxY = gb.maxY; v.mbf = mbf;
+        v.nlevels = (int)scaleFactors.size(); v.log_scale = logScaleFactor; v.scale_factors = scaleFactors.data();
+    }
+    FramePose(const FramePose& o) : v(o.v), scaleFactors(o.scaleFactors) { v.scale_factors = scaleFactors.data(); }
+    FramePose& operator=(const FramePose&) = delete;
+};
+
+// the local map points as Tracking::SearchLocalPoints reads them (Tracking.cc:2390-2408), one entry per MapPoint*: GetWorldPos,
+// GetNormal, mfMinDistance / mfMaxDistance, skip = isBad() or already matched in this frame, GetDescriptor, Observations() > 0
+struct MapPointsView {
+    std::vector<float> worldPos, normal, minDistance, maxDistance;
+    std::vector<uint8_t> skip, observed;
+    eorb_host::Mat8 descriptors;
+    int size() const { return (int)minDistance.size(); }
+};
+
+// what Frame::isInFrustum leaves in the map points: mbTrackInView, mTrackProjX/Y, mTrackProjXR, mnTrackScaleLevel, mTrackViewCos,
+// mTrackDepth (+ the scale factor of the level and the reject reason of include/eorb_fe.h)
+struct TrackedPoints {
+    std::vector<uint8_t> inView, reason;
+    std::vector<float> projXY, projXR, viewCos, depth, levelScale;
+    std::vector<int> level;
+    eorb_frustum_out bind(size_t M) {
+        inView.assign(M, 0); reason.assign(M, 0); projXY.assign(2 * M, -1.f); projXR.assign(M, 0.f); viewCos.assign(M, 0.f);
+        depth.assign(M, 0.f); levelScale.assign(M, 0.f); level.assign(M, -1);
+        return eorb_frustum_out{inView.data(), projXY.data(), projXR.data(), level.data(), viewCos.data(), depth.data(), levelScale.data(), reason.data()};
+    }
+};
+
+// Frame::isInFrustum(pMP, viewingCosLimit) over every local map point (Frame.cc:548-625; two cameras: right != nullptr, :626-636,
+// trackedRight receives the *R members).  Returns the number of points in view (nToMatch).
+inline int isInFrustum(const FramePose& F, const MapPointsView& mps, float viewingCosLimit, TrackedPoints& tracked,
+                       const FramePose* right = nullptr, TrackedPoints* trackedRight = nullptr) {
+    auto& c = eorb_host::thread_context();
+    const int M = mps.size();
+    eorb_view views[2] = {F.v, right ? right->v : F.v};
+    eorb_frustum_out out[2] = {tracked.bind((size_t)M), (right && trackedRight) ? trackedRight->bind((size_t)M) : eorb_frustum_out{}};
+    int n = 0;
+    c.check(eorb_project_frustum(c.get(), views, right ? 2 : 1, M, mps.worldPos.data(), mps.normal.data(), mps.minDistance.data(),
+                                 mps.maxDistance.data(), mps.skip.empty() ? nullptr : mps.skip.data(), nullptr, viewingCosLimit, out, &n));
+    return n;
+}
+
 class ORBmatcher {             // include/ORBmatcher.h:40-116
 public:
+    // Tracking::SearchLocalPoints (Tracking.cc:2390-2430) in one call: isInFrustum over the local map points, then
+    // SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) (:44-219).  frameMP in/out as eorb_search_by_projection_map;
+    // uRight = F.mvuRight for a rectified-stereo / RGB-D frame.  tracked: for IncreaseVisible and mmProjectPoints; *nToMatch = points in view.
+    int SearchLocalPoints(const FrameView& F, const FramePose& pose, const MapPointsView& mps, std::vector<int>& frameMP, float th,
+                          bool bFarPoints, float thFarPoints, TrackedPoints& tracked, int* nToMatch = nullptr,
+                          const std::vector<float>* uRight = nullptr, float viewingCosLimit = 0.5f) {
+        auto& c = eorb_host::thread_context();
+        const int M = mps.size();
+        const eorb_frustum_out out = tracked.bind((size_t)M);
+        int nm = 0, nv = 0;
+        c.check(eorb_search_local_points(c.get(), F.kps->data(), F.numAllKPts(), F.desc->ptr(), F.desc->cols, nullptr, &pose.v, M,
+                                         mps.worldPos.data(), mps.normal.data(), mps.minDistance.data(), mps.maxDistance.data(),
+                                         mps.skip.empty() ? nullptr : mps.skip.data(), nullptr, viewingCosLimit, mps.descriptors.ptr(),
+                                         mps.observed.data(), &F.gb, frameMP.data(), th, mfNNratio, uRight ? uRight->data() : nullptr,
+                                         bFarPoints, thFarPoints, &out, &nv, &nm));
+        if (nToMatch) *nToMatch = nv;
+        return nm;
+    }
     static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;
     explicit ORBmatcher(float nnratio = 0.6f, bool checkOri = true) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
     // vbPrevMatched: (x,y) per F1 keypoint, updated in place; vnMatches12 resized to F1.numAllKPts()

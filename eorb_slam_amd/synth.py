@@ -473,3 +473,63 @@ def calib_keypoints(n, W, H, seed=0, margin=0.1, nlevels=4):
     kps["response"] = rng.uniform(1, 200, n).astype(np.float32)
     kps["class_id"] = rng.randint(-1, 1000, n)
     return kps
+
+
+# ---- map points around a posed camera (the projector: eorb_project_frustum and its kin) ----------------------------------------
+def scale_tables(nlevels=8, scaleFactor=1.2):
+    """mvScaleFactor as ORBextractor builds it (float products, src/ORBextractor.cc:430-437) and mfLogScaleFactor = log(float)"""
+    sf = np.ones(nlevels, np.float32)
+    for i in range(1, nlevels):
+        sf[i] = sf[i - 1] * np.float32(scaleFactor)
+    return sf, np.float32(np.log(np.float32(scaleFactor)))
+
+
+def map_scene(seed, M, W=346, H=260, f=280.0, nlevels=8, scaleFactor=1.2, angle=0.3):
+    """M seeded map points around a camera rotated by `angle` rad about a random axis, made so that every outcome of
+    Frame::isInFrustum occurs often: positions uniform in the camera-frame box [-6, 6] x [-5, 5] x [-2, 12], normals tilted 0-100
+    degrees from the viewing ray, maxD = dist * 1.2^U(-3, nlevels + 2), minD = maxD / 1.2^(nlevels - 1).
+    -> dict(R, t, Ow, pos, normal, min_dist, max_dist, cam = (fx, fy, cx, cy), bounds = (minX, maxX, minY, maxY), nlevels,
+    log_scale, scale_factors); everything float32."""
+    r = np.random.default_rng(seed)
+    ax = r.normal(size=3); ax /= np.linalg.norm(ax)
+    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    R = (np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * K @ K).astype(np.float32)
+    t = r.uniform(-1, 1, 3).astype(np.float32)
+    Ow = (-R.T.astype(np.float64) @ t).astype(np.float32)
+    Pc = np.stack([r.uniform(-6, 6, M), r.uniform(-5, 5, M), r.uniform(-2, 12, M)], 1)
+    P = ((Pc - t) @ R.astype(np.float64)).astype(np.float32)            # R^T (Pc - t)
+    PO = P.astype(np.float64) - Ow
+    dist = np.linalg.norm(PO, axis=1)
+    n = PO / np.maximum(dist, 1e-12)[:, None]
+    tilt = r.uniform(0, np.deg2rad(100), M)
+    o = np.cross(n, r.normal(size=(M, 3)))
+    o /= np.maximum(np.linalg.norm(o, axis=1), 1e-12)[:, None]
+    nrm = (np.cos(tilt)[:, None] * n + np.sin(tilt)[:, None] * o).astype(np.float32)
+    dmax = (dist * scaleFactor ** r.uniform(-3, nlevels + 2, M)).astype(np.float32)
+    dmin = (dmax / scaleFactor ** (nlevels - 1)).astype(np.float32)
+    sf, log_scale = scale_tables(nlevels, scaleFactor)
+    return dict(R=R, t=t, Ow=Ow, pos=np.ascontiguousarray(P), normal=np.ascontiguousarray(nrm), min_dist=dmin, max_dist=dmax,
+                cam=(float(f), float(f), W / 2.0, H / 2.0), bounds=(0.0, float(W), 0.0, float(H)), nlevels=nlevels,
+                log_scale=log_scale, scale_factors=sf)
+
+
+def planted_frame(valid, uv, level, q_desc, n, W, H, nlevels=8, seed=0, jitter=1.5, max_flips=30, frac=0.7, dlevel=(-1, 0)):
+    """n keypoints and descriptors of a frame that observes some of the projected queries: up to frac * n of the valid ones get a
+    keypoint within `jitter` pixels of uv, at level + one of dlevel, with the query's descriptor and up to max_flips bits flipped; the
+    other keypoints are random.  -> (kps, desc n x 32, src = the planted query of each keypoint or -1), shuffled."""
+    rng = np.random.default_rng(seed)
+    idx = np.flatnonzero(np.asarray(valid) != 0)
+    pick = rng.choice(idx, min(len(idx), int(frac * n)), replace=False) if len(idx) else idx
+    kps = random_keypoints(n, W, H, nlevels=nlevels, seed=seed + 1)
+    desc = random_descriptors(n, seed=seed + 2)
+    src = np.full(n, -1, np.int32)
+    k = len(pick)
+    uv = np.asarray(uv, np.float32).reshape(-1, 2)
+    kps["x"][:k] = uv[pick, 0] + rng.uniform(-jitter, jitter, k).astype(np.float32)
+    kps["y"][:k] = uv[pick, 1] + rng.uniform(-jitter, jitter, k).astype(np.float32)
+    kps["octave"][:k] = np.clip(np.asarray(level)[pick] + rng.choice(dlevel, k), 0, nlevels - 1)
+    for j, q in enumerate(pick):
+        desc[j] = flip_bits(q_desc[q], int(rng.integers(0, max_flips + 1)), rng)
+    src[:k] = pick
+    perm = rng.permutation(n)
+    return kps[perm], np.ascontiguousarray(desc[perm]), src[perm]

@@ -297,7 +297,8 @@ int eorb_search_for_initialization(eorb_ctx* ctx,
         int windowSize, float nnratio, int checkOri, int* nmatches);
 
 /* replaces the mono branch of ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono)
- * (src/ORBmatcher.cc:1969-2187; MixedMatcher.cpp:693-).  Projection stays on the host:
+ * (src/ORBmatcher.cc:1969-2187; MixedMatcher.cpp:693-).  The projection is the caller's, on the host or with
+ * eorb_project_last_frame; eorb_search_by_projection_last_pose does both in one call:
  * valid/uv per last-frame keypoint, mp_desc (n_last x 32), mp_obs; cur_mp in/out
  * (-1 none, k>=0 last-frame point k, -2 foreign observed, -3 foreign unobserved).
  * mode 0: levels [o-1,o+1]; 1 forward (>= o); 2 backward ([0,o]). */
@@ -311,7 +312,7 @@ int eorb_search_by_projection_last(eorb_ctx* ctx,
 /* replaces ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, sAlreadyFound, th, ORBdist)
  * (src/ORBmatcher.cc:2189-2312; MixedMatcher.cpp:928-1063; relocalisation, f3).  One query per pKF feature i:
  * valid[i] = map point present, !isBad(), not in sAlreadyFound, projection inside the image and distance gates passed
- * (:2207-2234, on the host); uv, pred_level = PredictScale, level_scale = getORBScaleFactor / getAKAZEScaleFactor of that level,
+ * (:2207-2234, by the caller: eorb_project_keyframe_points, or eorb_search_by_projection_kf_pose for both steps); uv, pred_level = PredictScale, level_scale = getORBScaleFactor / getAKAZEScaleFactor of that level,
  * mp_desc = pMP->GetDescriptor().  cur_mp in/out: -1 free, anything else occupied; a match writes i (the pKF feature index). */
 int eorb_search_by_projection_kf(eorb_ctx* ctx,
         const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride, const uint8_t* cur_is_orb,
@@ -361,7 +362,8 @@ int eorb_frame_stereo(eorb_ctx* ctx, const uint8_t* imLeft, const uint8_t* imRig
  * nL left keypoints followed by nR right ones (mvKeys, then mvKeysRight), descriptors concatenated the same way (cv::vconcat :1176),
  * map-point slots frame_mp[nL + nR].  Both grids use the caller's eorb_grid_bounds (ComputeImageBounds(imLeft), :1145-1148): the
  * left grid holds the mvKeys positions (distorted: getDistKPtMono :758-760), the right grid the mvKeysRight positions.  Projection,
- * isInFrustum, isBad, far-point and outlier gates stay on the host, as for the mono entry points.
+ * isInFrustum, isBad, far-point and outlier gates are the caller's, as for the mono entry points; eorb_project_frustum with
+ * two views, eorb_project_last_frame with Trl and eorb_search_local_points_fisheye move the projection to the device.
  * Right grid level gate: GetFeaturesInArea(..., bRight = true) tests getKPtLevelMono(j) = mvKeysUn[j].octave (:763, :1417-1420),
  * i.e. the octave of LEFT keypoint j, for right keypoint j; for j >= nL the reference reads past mvKeysUn (nL entries, :1191) and
  * this library uses the right keypoint's own octave (upstream ORB-SLAM3's reading).  The query octave getKPtLevelMono(i) of a
@@ -417,6 +419,106 @@ int eorb_search_by_bow_fisheye(eorb_ctx* ctx,
         const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc,
         const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
         int32_t* match_f, float nnratio, int checkOri, int* nmatches);
+
+/* ---- map points projected on the device -----------------------------------------------------------------------------------
+ * Frame::isInFrustum (src/Frame.cc:548-637, isInFrustumChecks :1252-1325), MapPoint::PredictScale (src/MapPoint.cc:570-593) and the
+ * projection loops of the tracking matchers (src/ORBmatcher.cc:1999-2022, :2092-2095, :2215-2239), one thread per map point, in the
+ * reference's operation order: cv::Mat products on OpenCV 3.4.1's small-matrix path, cv::norm / Mat::dot accumulated in double,
+ * std::log(float) = glibc's logf ("Parity choices of the projector").  The standalone entry points return what
+ * the existing matchers take, so the host loops they replace become optional; the fused ones run projector and matcher behind one
+ * upload, one wait and one download and return exactly what the two calls in sequence return. */
+
+/* one camera of a frame and its pose */
+typedef struct eorb_view {
+    float R[9], t[3], Ow[3];           /* mRcw (row-major), mtcw, mOw; right camera: Rrl*mRcw, Rrl*mtcw+trl, mRwc*tlr+mOw (Frame.cc:1257-1263, computed by the caller) */
+    eorb_camera cam;                   /* mpCamera / mpCamera2 */
+    float minX, maxX, minY, maxY, mbf; /* mnMinX .. mnMaxY, mbf (0 without a rectified right image) */
+    int nlevels;    float log_scale;    const float* scale_factors;     /* getORBNLevels, getORBLogScaleFactor, getORBScaleFactor(0 .. nlevels - 1) */
+    int ak_nlevels; float ak_log_scale; const float* ak_scale_factors;  /* MixedFrame only, else 0 / NULL (MapPoint.cc:580-584) */
+} eorb_view;
+
+/* what isInFrustum leaves in a MapPoint, per point; any pointer may be NULL.  A rejected point keeps proj_xy = (-1, -1) until its
+ * bounds test has passed (then uv, as the mono branch leaves mTrackProjX/Y), level = -1, proj_xr = level_scale = 0, view_cos = 0
+ * unless it was computed (reason 6); depth = cv::norm(Pc) is written for every point that was not skipped.
+ * reason (test aid): 0 in view, 1 skipped by the caller, 2 negative depth, 3 x bounds, 4 y bounds, 5 distance, 6 view cosine,
+ * 7 non-finite projection (this library's rule: the reference goes on with a NaN there). */
+typedef struct eorb_frustum_out {
+    uint8_t* in_view;      /* mbTrackInView / mbTrackInViewR */
+    float*   proj_xy;      /* 2 per point: mTrackProjX, mTrackProjY */
+    float*   proj_xr;      /* mTrackProjXR = uv.x - mbf * (1.0f / PcZ) */
+    int32_t* level;        /* mnTrackScaleLevel */
+    float*   view_cos;     /* mTrackViewCos */
+    float*   depth;        /* mTrackDepth */
+    float*   level_scale;  /* scale factor of `level` in the table PredictScale chose */
+    uint8_t* reason;
+} eorb_frustum_out;
+
+/* Frame::isInFrustum over M map points and nviews = 1 (Nleft == -1) or 2 (left, right) views.  pos / normal: 3 floats per point
+ * (GetWorldPos, GetNormal); min_dist / max_dist = mfMinDistance / mfMaxDistance (the 0.8f / 1.2f of Get*DistanceInvariance are
+ * applied here); skip[m] != 0 (optional): the caller's isBad / already-matched points (Tracking.cc:2390-2400), left untouched;
+ * mp_is_orb (optional): isORBMapPoint, non-ORB points use the AKAZE tables of a mixed view.  out[v] belongs to views[v];
+ * *n_in_view = points in view of at least one view (nToMatch).  M == 0: EORB_OK, nothing written. */
+int eorb_project_frustum(eorb_ctx* ctx, const eorb_view* views, int nviews, int M, const float* pos, const float* normal,
+                         const float* min_dist, const float* max_dist, const uint8_t* skip, const uint8_t* mp_is_orb, float cos_limit,
+                         const eorb_frustum_out* out, int* n_in_view);
+
+/* the projection of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1999-2022): view = the current frame, pos =
+ * the world position of last-frame point i, skip[i] != 0 (optional) = no map point or an outlier (:1995-1997), last_kps = the last
+ * frame's keypoints (octave; getKPtLevelMono), last_is_orb (optional) as mp_is_orb above.  Out, all optional: valid (invzc >= 0, inside
+ * the bounds, finite), uv, proj_ur = uv.x - mbf * invzc (:2051), level_scale = the scale factor of the octave.  Trl (optional, 12
+ * floats: R row-major then t) and cam_r: uv_r = cam_r->project(Trl * x3Dc) (:2093-2095, no bounds test; the reference passes mpCamera
+ * there).  Octaves outside [0, nlevels): EORB_E_ARG. */
+int eorb_project_last_frame(eorb_ctx* ctx, const eorb_view* view, const eorb_camera* cam_r, const float* Trl, int n, const float* pos,
+                            const uint8_t* skip, const eorb_keypoint* last_kps, const uint8_t* last_is_orb,
+                            uint8_t* valid, float* uv, float* proj_ur, float* level_scale, float* uv_r);
+
+/* the projection of ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (:2215-2239; relocalisation).  No
+ * depth-sign test: a point behind the camera is projected like any other.  view->Ow = -Rcw.t()*tcw (:2196, the caller's); skip[i] != 0
+ * = no map point, isBad() or in sAlreadyFound.  Out, all optional: valid, uv, level = PredictScale(dist3D), level_scale, dist3d. */
+int eorb_project_keyframe_points(eorb_ctx* ctx, const eorb_view* view, int n, const float* pos, const float* min_dist,
+                                 const float* max_dist, const uint8_t* skip, const uint8_t* mp_is_orb,
+                                 uint8_t* valid, float* uv, int32_t* level, float* level_scale, float* dist3d);
+
+/* Tracking::SearchLocalPoints (src/Tracking.cc:2390-2430) for a one-camera frame: eorb_project_frustum of one view, then
+ * eorb_search_by_projection_map (uright == NULL) or eorb_search_by_projection_map_stereo (uright = mvuRight, proj_xr from the
+ * projector) over its results.  bFarPoints / thFarPoints (ORBmatcher.cc:57): a point with depth > thFarPoints stays in_view in `out`
+ * but is not searched.  out (optional): the projection arrays, for IncreaseVisible and mmProjectPoints. */
+int eorb_search_local_points(eorb_ctx* ctx,
+        const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const uint8_t* is_orb,
+        const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+        const uint8_t* skip, const uint8_t* mp_is_orb, float cos_limit,
+        const uint8_t* mp_desc, const uint8_t* mp_obs, const eorb_grid_bounds* gb, int32_t* frame_mp, float th, float nnratio,
+        const float* uright, int bFarPoints, float thFarPoints,
+        const eorb_frustum_out* out, int* n_in_view, int* nmatches);
+
+/* the same for a two-camera frame: eorb_project_frustum of views[2], then eorb_search_by_projection_map_fisheye.  The far-point gate
+ * reads the left view's depth when the left view accepted the point, else the right view's (the reference reads mTrackDepth, which the
+ * right view never writes: a stale member when only the right view accepted). */
+int eorb_search_local_points_fisheye(eorb_ctx* ctx,
+        const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride, const int32_t* l2r, const int32_t* r2l,
+        const eorb_view* views, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+        const uint8_t* skip, float cos_limit,
+        const uint8_t* mp_desc, const uint8_t* mp_obs, const eorb_grid_bounds* gb, int32_t* frame_mp, float th, float nnratio,
+        int bFarPoints, float thFarPoints,
+        const eorb_frustum_out* out, int* n_in_view, int* nmatches);
+
+/* TrackWithMotionModel's search: eorb_project_last_frame, then eorb_search_by_projection_last (cur_uright == NULL) or
+ * eorb_search_by_projection_last_stereo.  mode (0 none, 1 forward, 2 backward) stays the caller's: tlc is 3 x 3 host algebra.
+ * valid / uv (optional): the projection, as eorb_project_last_frame returns it. */
+int eorb_search_by_projection_last_pose(eorb_ctx* ctx,
+        const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride, const uint8_t* cur_is_orb,
+        const eorb_view* view, const eorb_keypoint* last_kps, int n_last, const uint8_t* last_is_orb,
+        const float* pos, const uint8_t* skip, const uint8_t* mp_desc, const uint8_t* mp_obs,
+        const eorb_grid_bounds* gb, int32_t* cur_mp, float th, int mode, int checkOri, const float* cur_uright,
+        uint8_t* valid, float* uv, int* nmatches);
+
+/* Relocalization's search: eorb_project_keyframe_points, then eorb_search_by_projection_kf. */
+int eorb_search_by_projection_kf_pose(eorb_ctx* ctx,
+        const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride, const uint8_t* cur_is_orb,
+        const eorb_view* view, const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_is_orb,
+        const float* pos, const float* min_dist, const float* max_dist, const uint8_t* skip, const uint8_t* mp_desc,
+        const eorb_grid_bounds* gb, int32_t* cur_mp, float th, int ORBdist, int checkOri,
+        uint8_t* valid, float* uv, int32_t* level, int* nmatches);
 
 /* replaces the mono branch of ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBmatcher.cc:276-478;
  * MixedMatcher.cpp:148-356).  DBoW2::FeatureVector as CSR (node ids ascending, offsets, feature indices in vector
@@ -678,7 +780,8 @@ int eorb_fe_run_batch_images_dev(eorb_ctx* ctx, const uint8_t* d_images, int B, 
 int eorb_selfcheck_division(eorb_ctx* ctx, float lo, float hi, float sigma, uint64_t* mismatches);
 
 /* self-check used by tests: order-independent 64-bit hash of a device math function over every float whose bit pattern
- * lies in [lo_bits, hi_bits]: which = 0 exp(-x) as used by exp_XY2f, 1 sin(x), 2 cos(x) as used by computeOrbDescriptor.
+ * lies in [lo_bits, hi_bits]: which = 0 exp(-x) as used by exp_XY2f, 1 sin(x), 2 cos(x) as used by computeOrbDescriptor,
+ * 3 tan(x), 4 atan(x), 5 atan2 over generated pairs (KannalaBrandt8), 6 log(x) as used by MapPoint::PredictScale.
  * The CPU oracle computes the same hash of its own functions: equality proves the two agree on every input. */
 int eorb_selfcheck_math(eorb_ctx* ctx, int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* hash);
 

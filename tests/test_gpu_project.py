@@ -1,0 +1,458 @@
+"""Map points projected on the device (GPU): eorb_project_frustum / _last_frame / _keyframe_points and the fused searches against
+the CPU restatement (tests/proj_ref) and, for the matcher half, the oracle -- bit for bit."""
+import ctypes as C
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import proj_ref                                     # noqa: E402
+from eorb_slam_amd import synth                     # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+W, H = 346, 260
+E_ARG = -4
+# Examples/Event/EvMVSEC_ETHZ.yaml: KannalaBrandt8
+KB8 = (226.38018519795807, 226.15002947047415, 173.6470807871759, 133.73271487507847,
+       -0.048031442223833355, 0.011330957517194437, -0.055378166304281135, 0.021500973881459395)
+FIELDS = [f[0] for f in proj_ref.FRUSTUM_FIELDS]
+
+
+@pytest.fixture(scope="module")
+def fe():
+    from eorb_slam_amd import frontend
+    return frontend
+
+
+@pytest.fixture(scope="module")
+def ctx(fe):
+    c = fe.Context()
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def ref(oracle):
+    """proj_ref with the oracle's KannalaBrandt8 projection plugged in"""
+    proj_ref.use_oracle_camera(oracle)
+    return proj_ref
+
+
+def _view_kw(s, cam=None, mbf=0.0, mixed=False):
+    kw = dict(R=s["R"], t=s["t"], Ow=s["Ow"], cam=cam or s["cam"], bounds=s["bounds"], nlevels=s["nlevels"], log_scale=s["log_scale"],
+              scale_factors=s["scale_factors"], mbf=mbf)
+    if mixed:
+        ak, akl = synth.scale_tables(4, 1.4)
+        kw.update(ak_nlevels=4, ak_log_scale=akl, ak_scale_factors=ak)
+    return kw
+
+
+def _right_kw(kw):
+    """the right camera of a two-camera frame: Rrl*mRcw, Rrl*mtcw + trl, mRwc*tlr + mOw (Frame.cc:1257-1263), computed by the caller"""
+    Rrl = synth.rot(0.004, -0.02, 0.003).astype(np.float64)
+    trl = np.array([-0.11, 0.002, 0.001])
+    R = np.asarray(kw["R"], np.float64); t = np.asarray(kw["t"], np.float64)
+    tlr = -Rrl.T @ trl
+    r = dict(kw)
+    r.update(R=(Rrl @ R).astype(F32), t=(Rrl @ t + trl).astype(F32), Ow=(R.T @ tlr + np.asarray(kw["Ow"], np.float64)).astype(F32))
+    return r, np.concatenate([Rrl.reshape(-1), trl]).astype(F32)
+
+
+def _eq(got, want, keys=FIELDS):
+    for k in keys:
+        assert got[k].tobytes() == want[k].tobytes(), k
+
+
+# ---- device math ------------------------------------------------------------------------------------------------------------------
+def test_device_logf_equals_the_restatement_on_every_input(ctx):
+    """every float in [2^-10, 2^20] (251 658 241 inputs), the hash of eorb_selfcheck_math's other rows"""
+    lo = int(F32(2.0 ** -10).view(np.uint32)); hi = int(F32(2.0 ** 20).view(np.uint32))
+    got = C.c_uint64(0)
+    ctx.check(ctx.L.eorb_selfcheck_math(ctx.h, 6, lo, hi, C.byref(got)))
+    assert got.value == proj_ref.math_hash(6, lo, hi)
+
+
+def test_device_logf_subnormals_and_specials(ctx):
+    for lo, hi in ((0, 1 << 16), (0x007f0000, 0x00810000), (0x3f7fff00, 0x3f800100), (0x7f7fff00, 0x7f800000)):
+        got = C.c_uint64(0)
+        ctx.check(ctx.L.eorb_selfcheck_math(ctx.h, 6, lo, hi, C.byref(got)))
+        assert got.value == proj_ref.math_hash(6, lo, hi), (lo, hi)
+
+
+# ---- mode A -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("M", [0, 1, 63, 64, 65, 1000, 4099])
+@pytest.mark.parametrize("cfg", ["pinhole", "pinhole_skip", "kb8", "two", "mixed"])
+def test_frustum_equals_the_restatement(fe, ctx, ref, M, cfg):
+    s = synth.map_scene(7, M)
+    kw = _view_kw(s, cam=KB8 if cfg in ("kb8", "two") else None, mbf=35.0 if cfg != "two" else 0.0, mixed=cfg == "mixed")
+    kws = [kw, _right_kw(kw)[0]] if cfg == "two" else [kw]
+    skip = (np.arange(M) % 3 == 2).astype(np.uint8) if cfg in ("pinhole_skip", "two") else None
+    is_orb = (np.random.default_rng(3).random(M) < 0.6).astype(np.uint8) if cfg == "mixed" else None
+    args = (s["pos"], s["normal"], s["min_dist"], s["max_dist"])
+    wn, want = ref.frustum([ref.view(**k) for k in kws], *args, cos_limit=0.5, skip=skip, mp_is_orb=is_orb)
+    gviews = [fe.view(**k) for k in kws]
+    gn, got = fe.isInFrustum(gviews if cfg == "two" else gviews[0], *args, viewingCosLimit=0.5, skip=skip, mp_is_orb=is_orb, ctx=ctx)
+    got = got if cfg == "two" else [got]
+    assert gn == wn
+    for g, w in zip(got, want):
+        _eq(g, w)
+    if M == 1000:
+        # the reference itself: every outcome and every level often enough that the comparison is not one of empty sets
+        for w in want:
+            cnt = np.bincount(w["reason"], minlength=8)
+            lv = np.bincount(w["level"][w["in_view"] == 1], minlength=8)
+            if cfg == "pinhole":
+                assert all(cnt[r] >= 50 for r in (0, 2, 3, 4, 5, 6)), cnt
+                assert all(lv[:8] >= 5), lv
+            elif cfg == "pinhole_skip":
+                assert cnt[1] == 333 and all(cnt[r] >= 30 for r in (0, 2, 3, 4, 5, 6)), cnt
+            else:
+                assert cnt[0] >= 50 and cnt[2] >= 50 and cnt[5] >= 50 and cnt[6] >= 50, cnt
+        if cfg == "mixed":
+            w = want[0]
+            ak = (is_orb == 0) & (w["in_view"] == 1)
+            assert ak.sum() >= 20 and w["level"][ak].max() == 3 and w["level"][(is_orb == 1) & (w["in_view"] == 1)].max() == 7
+        if cfg == "two":
+            only_r = (want[0]["in_view"] == 0) & (want[1]["in_view"] == 1)
+            assert only_r.sum() >= 1 and wn == int(((want[0]["in_view"] | want[1]["in_view"]) != 0).sum())
+
+
+def test_frustum_sweep_of_four_million_points(fe, ctx, ref):
+    """2^22 generated points (the same generator on both sides: synth.map_scene), every output array compared"""
+    M = 1 << 22
+    s = synth.map_scene(21, M)
+    kw = _view_kw(s, mbf=35.0)
+    args = (s["pos"], s["normal"], s["min_dist"], s["max_dist"])
+    wn, (want,) = ref.frustum(ref.view(**kw), *args, cos_limit=0.5, timing=True)
+    gn, got = fe.isInFrustum(fe.view(**kw), *args, viewingCosLimit=0.5, ctx=ctx)
+    assert gn == wn and wn > M // 20
+    _eq(got, want)
+
+
+# ---- modes B and C ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 65, 1500])
+@pytest.mark.parametrize("cfg", ["pinhole", "kb8_right"])
+def test_last_frame_projection_equals_the_restatement(fe, ctx, ref, n, cfg):
+    s = synth.map_scene(9, n)
+    kw = _view_kw(s, cam=KB8 if cfg == "kb8_right" else None, mbf=35.0)
+    kps = synth.random_keypoints(n, W, H, nlevels=8, seed=5)
+    skip = (np.arange(n) % 5 == 4).astype(np.uint8)
+    extra = {}
+    if cfg == "kb8_right":
+        extra = dict(cam_r=KB8, Trl=_right_kw(kw)[1])
+    want = ref.last_frame(ref.view(**kw), s["pos"], kps, skip=skip, **extra)
+    got = fe.ProjectLastFrame(fe.view(**kw), s["pos"], kps, skip=skip, ctx=ctx, **extra)
+    assert sorted(got) == sorted(want)
+    _eq(got, want, sorted(want))
+    if n == 1500:
+        assert 100 <= int(want["valid"].sum()) <= n - 100
+        assert len(np.unique(want["level_scale"])) == 8
+        if extra:
+            v = want["valid"] == 1
+            assert np.all(np.any(want["uv_r"][v] != want["uv"][v], axis=1)) and np.all(want["proj_ur"][v] != 0)
+
+
+@pytest.mark.parametrize("n", [1, 65, 1500])
+@pytest.mark.parametrize("cfg", ["pinhole", "kb8", "mixed"])
+def test_keyframe_projection_equals_the_restatement(fe, ctx, ref, n, cfg):
+    s = synth.map_scene(10, n)
+    # every tenth point mirrored through the camera centre: the same pinhole projection and distance, a negative depth
+    R64, t64 = s["R"].astype(np.float64), s["t"].astype(np.float64)
+    Pc = s["pos"][::10].astype(np.float64) @ R64.T + t64
+    s["pos"][::10] = ((-Pc - t64) @ R64).astype(F32)
+    kw = _view_kw(s, cam=KB8 if cfg == "kb8" else None, mixed=cfg == "mixed")
+    skip = (np.arange(n) % 5 == 4).astype(np.uint8)
+    is_orb = (np.random.default_rng(4).random(n) < 0.6).astype(np.uint8) if cfg == "mixed" else None
+    want = ref.keyframe_points(ref.view(**kw), s["pos"], s["min_dist"], s["max_dist"], skip=skip, mp_is_orb=is_orb)
+    got = fe.ProjectKeyFramePoints(fe.view(**kw), s["pos"], s["min_dist"], s["max_dist"], skip=skip, mp_is_orb=is_orb, ctx=ctx)
+    _eq(got, want, sorted(want))
+    if n == 1500:
+        assert 100 <= int(want["valid"].sum()) <= n - 100
+        if cfg == "pinhole":
+            # no depth-sign test: some accepted points lie behind the camera
+            z = (s["pos"].astype(np.float64) @ s["R"].astype(np.float64).T + s["t"])[:, 2]
+            assert ((z < -0.01) & (want["valid"] == 1)).sum() >= 3
+
+
+# ---- the fused searches -------------------------------------------------------------------------------------------------------------
+N_KP, M_MP = 1000, 1500
+
+
+def _slots(n, seed):
+    rng = np.random.default_rng(seed)
+    fm = np.full(n, -1, np.int32)
+    fm[rng.random(n) < 0.08] = -2
+    fm[rng.random(n) < 0.04] = -3
+    return fm
+
+
+@functools.lru_cache(None)
+def _local_scene():
+    s = synth.map_scene(11, M_MP)
+    kw = _view_kw(s, mbf=35.0)
+    args = (s["pos"], s["normal"], s["min_dist"], s["max_dist"])
+    skip = (np.arange(M_MP) % 11 == 10).astype(np.uint8)
+    _, (r,) = proj_ref.frustum(proj_ref.view(**kw), *args, cos_limit=0.5, skip=skip)
+    mp_desc = synth.random_descriptors(M_MP, seed=12)
+    kps, desc, src = synth.planted_frame(r["in_view"], r["proj_xy"], r["level"], mp_desc, N_KP, W, H, seed=13)
+    rng = np.random.default_rng(14)
+    mp_obs = (rng.random(M_MP) < 0.9).astype(np.uint8)
+    # mvuRight: none for a third of the keypoints; near the projected right coordinate for most observations, far for some
+    ur = np.where(src >= 0, r["proj_xr"][np.maximum(src, 0)] + rng.uniform(-1, 1, N_KP), kps["x"] - rng.uniform(1, 30, N_KP)).astype(F32)
+    ur[rng.random(N_KP) < 0.15] += 25.0
+    ur[rng.random(N_KP) < 0.33] = -1.0
+    th_far = float(np.median(r["depth"][r["in_view"] == 1]))
+    return dict(kw=kw, args=args, skip=skip, mp_desc=mp_desc, mp_obs=mp_obs, kps=kps, desc=desc, uright=ur, fm=_slots(N_KP, 15), th_far=th_far)
+
+
+@pytest.mark.parametrize("th", [1.0, 3.0])
+@pytest.mark.parametrize("far", [False, True])
+@pytest.mark.parametrize("stereo", [False, True])
+def test_search_local_points(fe, ctx, ref, oracle, th, far, stereo):
+    sc = _local_scene()
+    ur = sc["uright"] if stereo else None
+    wn, (r,) = ref.frustum(ref.view(**sc["kw"]), *sc["args"], cos_limit=0.5, skip=sc["skip"], far=far, th_far=sc["th_far"])
+    OF = oracle.Frame(sc["kps"], sc["desc"], W, H)
+    on, ofm = oracle.search_by_projection_map(OF, r["search"], r["proj_xy"], r["level"], r["view_cos"], sc["mp_desc"], sc["mp_obs"], sc["fm"], th,
+                                              0.8, r["level_scale"], uright=ur, proj_xr=r["proj_xr"] if stereo else None)
+    F = fe.FrameView(sc["kps"], sc["desc"], W, H)
+    v = fe.view(**sc["kw"])
+    for _ in range(2):                                                      # the second call reuses the context's arena
+        gm, gfm, gn, g = fe.SearchLocalPoints(F, v, *sc["args"], sc["mp_desc"], sc["mp_obs"], sc["fm"], th=th, nnratio=0.8, viewingCosLimit=0.5,
+                                              skip=sc["skip"], uright=ur, bFarPoints=far, thFarPoints=sc["th_far"], ctx=ctx)
+        assert (gm, gn) == (on, wn) and np.array_equal(gfm, ofm)
+        _eq(g, r)
+    assert on >= 40 and wn >= 150
+    if far:
+        assert 20 <= int(r["search"].sum()) < int(r["in_view"].sum())         # far points stay in view, are not searched
+    # the product's own two calls
+    n2, p = fe.isInFrustum(v, *sc["args"], viewingCosLimit=0.5, skip=sc["skip"], ctx=ctx)
+    search = p["in_view"] & ~((p["depth"] > F32(sc["th_far"])) & far).astype(np.uint8)
+    cm, cfm = fe.ORBmatcher(0.8, True, ctx).SearchByProjectionMap(F, search, p["proj_xy"], p["level"], p["view_cos"], sc["mp_desc"], sc["mp_obs"],
+                                                                  sc["fm"], th, p["level_scale"], uright=ur, proj_xr=p["proj_xr"] if stereo else None)
+    assert (cm, n2) == (gm, gn) and np.array_equal(cfm, gfm)
+
+
+@functools.lru_cache(None)
+def _fisheye_scene():
+    nL, nR = 600, 400
+    s = synth.map_scene(16, M_MP)
+    kwl = _view_kw(s, cam=KB8)
+    kwr, _ = _right_kw(kwl)
+    args = (s["pos"], s["normal"], s["min_dist"], s["max_dist"])
+    skip = (np.arange(M_MP) % 11 == 10).astype(np.uint8)
+    _, (l, r) = proj_ref.frustum([proj_ref.view(**kwl), proj_ref.view(**kwr)], *args, cos_limit=0.5, skip=skip)
+    mp_desc = synth.random_descriptors(M_MP, seed=17)
+    kl, dl, _ = synth.planted_frame(l["in_view"], l["proj_xy"], l["level"], mp_desc, nL, W, H, seed=18)
+    kr, dr, _ = synth.planted_frame(r["in_view"], r["proj_xy"], r["level"], mp_desc, nR, W, H, seed=19)
+    rng = np.random.default_rng(20)
+    l2r = np.full(nL, -1, np.int32); r2l = np.full(nR, -1, np.int32)
+    a = rng.choice(nL, 150, replace=False); b = rng.choice(nR, 150, replace=False)
+    l2r[a] = b; r2l[b] = a
+    mp_obs = (rng.random(M_MP) < 0.9).astype(np.uint8)
+    # thFarPoints between the two depths of a point that only the right view accepts (the one nearest the median depth): the rule
+    # "the left depth when the left view accepted the point, else the right one" decides whether it is searched
+    either = (l["in_view"] | r["in_view"]) == 1
+    med = np.median(np.where(l["in_view"] == 1, l["depth"], r["depth"])[either])
+    only_r = np.flatnonzero((l["in_view"] == 0) & (r["in_view"] == 1) & (l["depth"] != r["depth"]))
+    probe = int(only_r[np.argmin(np.abs(r["depth"][only_r] - med))])
+    th_far = float(F32((np.float64(l["depth"][probe]) + np.float64(r["depth"][probe])) / 2))
+    return dict(kws=(kwl, kwr), args=args, skip=skip, mp_desc=mp_desc, mp_obs=mp_obs, kps=np.concatenate([kl, kr]), desc=np.concatenate([dl, dr]),
+                nL=nL, l2r=l2r, r2l=r2l, fm=_slots(nL + nR, 21), th_far=th_far, probe=probe)
+
+
+@pytest.mark.parametrize("th", [1.0, 3.0])
+@pytest.mark.parametrize("far", [False, True])
+def test_search_local_points_fisheye(fe, ctx, ref, oracle, th, far):
+    sc = _fisheye_scene()
+    wn, want = ref.frustum([ref.view(**k) for k in sc["kws"]], *sc["args"], cos_limit=0.5, skip=sc["skip"], far=far, th_far=sc["th_far"])
+    gb = oracle.grid_bounds(W, H)
+    cams = [(w["search"], w["proj_xy"], w["level"], w["view_cos"], w["level_scale"]) for w in want]
+    on, ofm = oracle.search_by_projection_map_fisheye(sc["kps"], sc["nL"], sc["desc"], gb, sc["l2r"], sc["r2l"], cams[0], cams[1], sc["mp_desc"],
+                                                      sc["mp_obs"], sc["fm"], th, 0.8)
+    views = [fe.view(**k) for k in sc["kws"]]
+    ggb = fe.grid_bounds(W, H)
+    gm, gfm, gn, got = fe.SearchLocalPointsFisheye(sc["kps"], sc["nL"], sc["desc"], sc["l2r"], sc["r2l"], ggb, views, *sc["args"], sc["mp_desc"],
+                                                   sc["mp_obs"], sc["fm"], th=th, nnratio=0.8, viewingCosLimit=0.5, skip=sc["skip"],
+                                                   bFarPoints=far, thFarPoints=sc["th_far"], ctx=ctx)
+    assert (gm, gn) == (on, wn) and np.array_equal(gfm, ofm)
+    for g, w in zip(got, want):
+        _eq(g, w)
+    assert on >= 40 and (ofm[sc["nL"]:] >= 0).sum() >= 10 and (ofm[:sc["nL"]] >= 0).sum() >= 10
+    only_r = (want[0]["in_view"] == 0) & (want[1]["in_view"] == 1)
+    assert only_r.sum() >= 1
+    if far:
+        # the gate reads the left depth where the left view accepted the point, else the right one
+        k, thf = sc["probe"], F32(sc["th_far"])
+        assert only_r[k] and (want[0]["depth"][k] > thf) != (want[1]["depth"][k] > thf)
+        assert want[1]["search"][k] == (0 if want[1]["depth"][k] > thf else 1)
+        assert int(want[0]["search"].sum()) < int(want[0]["in_view"].sum())
+    # the product's own two calls
+    n2, p = fe.isInFrustum(views, *sc["args"], viewingCosLimit=0.5, skip=sc["skip"], ctx=ctx)
+    d = np.where(p[0]["in_view"] == 1, p[0]["depth"], p[1]["depth"])
+    gate = (d > F32(sc["th_far"])) & far
+    two = [((q["in_view"] == 1) & ~gate).astype(np.uint8) for q in p]
+    cm, cfm = fe.ORBmatcher(0.8, True, ctx).SearchByProjectionMapFisheye(
+        sc["kps"], sc["nL"], sc["desc"], sc["l2r"], sc["r2l"], ggb,
+        (two[0], p[0]["proj_xy"], p[0]["level"], p[0]["view_cos"], p[0]["level_scale"]),
+        (two[1], p[1]["proj_xy"], p[1]["level"], p[1]["view_cos"], p[1]["level_scale"]), sc["mp_desc"], sc["mp_obs"], sc["fm"], th)
+    assert (cm, n2) == (gm, gn) and np.array_equal(cfm, gfm)
+
+
+@functools.lru_cache(None)
+def _last_scene():
+    s = synth.map_scene(22, M_MP)
+    kw = _view_kw(s, mbf=35.0)
+    last_kps = synth.random_keypoints(M_MP, W, H, nlevels=8, seed=23)
+    skip = (np.arange(M_MP) % 7 == 6).astype(np.uint8)
+    r = proj_ref.last_frame(proj_ref.view(**kw), s["pos"], last_kps, skip=skip)
+    mp_desc = synth.random_descriptors(M_MP, seed=24)
+    kps, desc, src = synth.planted_frame(r["valid"], r["uv"], last_kps["octave"], mp_desc, N_KP, W, H, seed=25, dlevel=(-1, 0, 1))
+    rng = np.random.default_rng(26)
+    mp_obs = (rng.random(M_MP) < 0.9).astype(np.uint8)
+    ur = np.where(src >= 0, r["proj_ur"][np.maximum(src, 0)] + rng.uniform(-1, 1, N_KP), kps["x"] - rng.uniform(1, 30, N_KP)).astype(F32)
+    ur[rng.random(N_KP) < 0.15] += 25.0
+    ur[rng.random(N_KP) < 0.33] = -1.0
+    return dict(kw=kw, pos=s["pos"], last_kps=last_kps, skip=skip, mp_desc=mp_desc, mp_obs=mp_obs, kps=kps, desc=desc, uright=ur, cm=_slots(N_KP, 27))
+
+
+@pytest.mark.parametrize("th", [1.0, 3.0])
+@pytest.mark.parametrize("ori", [True, False])
+@pytest.mark.parametrize("stereo,mode", [(False, 0), (True, 0), (True, 1), (True, 2)])
+def test_search_by_projection_last_pose(fe, ctx, ref, oracle, th, ori, stereo, mode):
+    sc = _last_scene()
+    th = th * 7.0                                                           # (the reference's th = 7 or 15 for this search: th 1 and 3 scaled)
+    ur = sc["uright"] if stereo else None
+    r = ref.last_frame(ref.view(**sc["kw"]), sc["pos"], sc["last_kps"], skip=sc["skip"])
+    OC = oracle.Frame(sc["kps"], sc["desc"], W, H); OL = oracle.Frame(sc["last_kps"], np.zeros((M_MP, 32), np.uint8), W, H)
+    on, ocm = oracle.search_by_projection_last(OC, OL, r["valid"], r["uv"], sc["mp_desc"], sc["mp_obs"], sc["cm"], th, r["level_scale"], mode=mode,
+                                               checkOri=ori, uright=ur, proj_ur=r["proj_ur"] if stereo else None)
+    Cur = fe.FrameView(sc["kps"], sc["desc"], W, H); Last = fe.FrameView(sc["last_kps"], np.zeros((M_MP, 32), np.uint8), W, H)
+    v = fe.view(**sc["kw"])
+    gm, gcm, gvalid, guv = fe.SearchByProjectionLastPose(Cur, v, Last, sc["pos"], sc["mp_desc"], sc["mp_obs"], sc["cm"], th, mode=mode,
+                                                         checkOri=ori, skip=sc["skip"], uright=ur, ctx=ctx)
+    assert gm == on and np.array_equal(gcm, ocm)
+    assert gvalid.tobytes() == r["valid"].tobytes() and guv.tobytes() == r["uv"].tobytes()
+    assert on >= 30
+    # the product's own two calls
+    p = fe.ProjectLastFrame(v, sc["pos"], sc["last_kps"], skip=sc["skip"], ctx=ctx)
+    cm, ccm = fe.ORBmatcher(0.8, ori, ctx).SearchByProjectionLast(Cur, Last, p["valid"], p["uv"], sc["mp_desc"], sc["mp_obs"], sc["cm"], th,
+                                                                  p["level_scale"], mode=mode, uright=ur, proj_ur=p["proj_ur"] if stereo else None)
+    assert cm == gm and np.array_equal(ccm, gcm)
+
+
+@functools.lru_cache(None)
+def _kf_scene():
+    s = synth.map_scene(28, M_MP)
+    kw = _view_kw(s)
+    kf_kps = synth.random_keypoints(M_MP, W, H, nlevels=8, seed=29)
+    skip = (np.arange(M_MP) % 7 == 6).astype(np.uint8)
+    r = proj_ref.keyframe_points(proj_ref.view(**kw), s["pos"], s["min_dist"], s["max_dist"], skip=skip)
+    mp_desc = synth.random_descriptors(M_MP, seed=30)
+    kps, desc, _ = synth.planted_frame(r["valid"], r["uv"], r["level"], mp_desc, N_KP, W, H, seed=31, dlevel=(-1, 0, 1))
+    cm = np.full(N_KP, -1, np.int32)
+    cm[np.random.default_rng(32).random(N_KP) < 0.1] = 5                    # occupied slots: skipped, kept
+    return dict(kw=kw, pos=s["pos"], min_dist=s["min_dist"], max_dist=s["max_dist"], kf_kps=kf_kps, skip=skip, mp_desc=mp_desc, kps=kps,
+                desc=desc, cm=cm)
+
+
+@pytest.mark.parametrize("th", [1.0, 3.0])
+@pytest.mark.parametrize("ori", [True, False])
+def test_search_by_projection_kf_pose(fe, ctx, ref, oracle, th, ori):
+    sc = _kf_scene()
+    th = th * 10.0                                                          # (Relocalization searches with th = 10, then 3: coarse windows here)
+    r = ref.keyframe_points(ref.view(**sc["kw"]), sc["pos"], sc["min_dist"], sc["max_dist"], skip=sc["skip"])
+    OC = oracle.Frame(sc["kps"], sc["desc"], W, H)
+    on, ocm = oracle.search_by_projection_kf(OC, sc["kf_kps"], None, r["valid"], r["uv"], r["level"], r["level_scale"], sc["mp_desc"], sc["cm"], th,
+                                             100, ori)
+    Cur = fe.FrameView(sc["kps"], sc["desc"], W, H)
+    v = fe.view(**sc["kw"])
+    gm, gcm, gvalid, guv, glevel = fe.SearchByProjectionKFPose(Cur, v, sc["kf_kps"], sc["pos"], sc["min_dist"], sc["max_dist"], sc["mp_desc"],
+                                                               sc["cm"], th, 100, checkOri=ori, skip=sc["skip"], ctx=ctx)
+    assert gm == on and np.array_equal(gcm, ocm)
+    assert gvalid.tobytes() == r["valid"].tobytes() and guv.tobytes() == r["uv"].tobytes() and glevel.tobytes() == r["level"].tobytes()
+    assert on >= 30 and np.all(gcm[sc["cm"] == 5] == 5)
+    # the product's own two calls
+    p = fe.ProjectKeyFramePoints(v, sc["pos"], sc["min_dist"], sc["max_dist"], skip=sc["skip"], ctx=ctx)
+    cm, ccm = fe.ORBmatcher(0.8, ori, ctx).SearchByProjectionKF(Cur, sc["kf_kps"], None, p["valid"], p["uv"], p["level"], p["level_scale"],
+                                                                sc["mp_desc"], sc["cm"], th, 100)
+    assert cm == gm and np.array_equal(ccm, gcm)
+
+
+# ---- argument errors and M == 0 -----------------------------------------------------------------------------------------------------
+def test_argument_errors_and_empty_calls(fe, ctx):
+    s = synth.map_scene(33, 8)
+    kw = _view_kw(s)
+    v = fe.view(**kw)
+    L, h, p = ctx.L, ctx.h, fe._p
+    n = C.c_int(-7)
+    A = (p(s["pos"]), p(s["normal"]), p(s["min_dist"]), p(s["max_dist"]))
+
+    def frustum(view, M=8, a=A, is_orb=None, nviews=1):
+        return L.eorb_project_frustum(h, C.byref(view) if view is not None else None, nviews, M, a[0], a[1], a[2], a[3], None, is_orb, 0.5, None,
+                                      C.byref(n))
+    assert frustum(v) == 0 and 0 <= n.value <= 8
+    assert frustum(v, M=-1) == E_ARG
+    assert frustum(None) == E_ARG
+    assert frustum(v, nviews=3) == E_ARG and frustum(v, nviews=0) == E_ARG
+    for i in range(4):                                                      # each required array
+        a = list(A); a[i] = None
+        assert frustum(v, a=a) == E_ARG
+    for nl in (0, -1, 129):
+        assert frustum(fe.view(**dict(kw, nlevels=nl))) == E_ARG
+    assert frustum(fe.view(**dict(kw, nlevels=128, scale_factors=np.ones(128, F32)))) == 0
+    assert frustum(fe.view(**dict(kw, scale_factors=None))) == E_ARG
+    bad = fe.view(**kw); bad.cam.model = 2
+    assert frustum(bad) == E_ARG
+    assert frustum(v, is_orb=p(np.ones(8, np.uint8))) == E_ARG               # descriptor kinds without AKAZE tables
+    ak, akl = synth.scale_tables(4, 1.4)
+    assert frustum(fe.view(**dict(kw, ak_nlevels=4, ak_log_scale=akl, ak_scale_factors=ak)), is_orb=p(np.ones(8, np.uint8))) == 0
+    assert frustum(fe.view(**dict(kw, ak_nlevels=4, ak_log_scale=akl)), is_orb=p(np.ones(8, np.uint8))) == E_ARG
+    assert b"nlevels" in L.eorb_last_error(h) or b"AKAZE" in L.eorb_last_error(h)
+    # M == 0: EORB_OK, nothing written (not even through the pointers)
+    sentinel = np.full(4, 77, np.uint8)
+    out = fe._lib.FrustumOut(); out.in_view = sentinel.ctypes.data; out.reason = sentinel.ctypes.data
+    n.value = -7
+    assert L.eorb_project_frustum(h, C.byref(v), 1, 0, None, None, None, None, None, None, 0.5, C.byref(out), C.byref(n)) == 0
+    assert n.value == 0 and np.all(sentinel == 77)
+    assert L.eorb_project_last_frame(h, C.byref(v), None, None, 0, None, None, None, None, p(sentinel), None, None, None, None) == 0
+    assert L.eorb_project_keyframe_points(h, C.byref(v), 0, None, None, None, None, None, p(sentinel), None, None, None, None) == 0
+    assert np.all(sentinel == 77)
+    # modes B and C
+    kps = synth.random_keypoints(8, W, H, nlevels=8, seed=1)
+    assert L.eorb_project_last_frame(h, C.byref(v), None, None, 8, A[0], None, p(kps), None, None, None, None, None, None) == 0
+    assert L.eorb_project_last_frame(h, C.byref(v), None, None, -1, A[0], None, p(kps), None, None, None, None, None, None) == E_ARG
+    assert L.eorb_project_last_frame(h, C.byref(v), None, None, 8, None, None, p(kps), None, None, None, None, None, None) == E_ARG
+    assert L.eorb_project_last_frame(h, C.byref(v), None, None, 8, A[0], None, None, None, None, None, None, None, None) == E_ARG
+    trl = np.zeros(12, F32)
+    assert L.eorb_project_last_frame(h, C.byref(v), None, p(trl), 8, A[0], None, p(kps), None, None, None, None, None, None) == E_ARG   # Trl without a camera
+    k2 = kps.copy(); k2["octave"][3] = 8
+    assert L.eorb_project_last_frame(h, C.byref(v), None, None, 8, A[0], None, p(k2), None, None, None, None, None, None) == E_ARG     # octave outside the tables
+    assert L.eorb_project_keyframe_points(h, C.byref(v), 8, A[0], A[2], A[3], None, None, None, None, None, None, None) == 0
+    assert L.eorb_project_keyframe_points(h, C.byref(v), 8, A[0], None, A[3], None, None, None, None, None, None, None) == E_ARG
+    assert L.eorb_project_keyframe_points(h, C.byref(bad), 8, A[0], A[2], A[3], None, None, None, None, None, None, None) == E_ARG
+    # the fused entries
+    F = fe.FrameView(synth.random_keypoints(16, W, H, nlevels=8, seed=2), synth.random_descriptors(16, seed=3), W, H)
+    fm = np.full(16, -1, np.int32); nm = C.c_int(-7)
+    md = synth.random_descriptors(8, seed=4); ob = np.ones(8, np.uint8)
+
+    def local(view=v, M=8, pos=A[0], gb=C.byref(F.gb), slots=p(fm)):
+        return L.eorb_search_local_points(h, p(F.kps), 16, p(F.desc), 32, None, C.byref(view), M, pos, A[1], A[2], A[3], None, None, 0.5,
+                                          p(md), p(ob), gb, slots, 1.0, 0.8, None, 0, 0.0, None, C.byref(n), C.byref(nm))
+    assert local() == 0
+    assert local(M=-1) == E_ARG and local(pos=None) == E_ARG and local(gb=None) == E_ARG and local(slots=None) == E_ARG and local(view=bad) == E_ARG
+    before = fm.copy(); n.value = nm.value = -7
+    assert local(M=0) == 0 and n.value == 0 and nm.value == 0 and np.array_equal(fm, before)
+    assert L.eorb_search_by_projection_last_pose(h, p(F.kps), 16, p(F.desc), 32, None, C.byref(v), p(kps), 8, None, A[0], None, p(md), p(ob),
+                                                 C.byref(F.gb), p(fm), 7.0, 3, 1, None, None, None, C.byref(nm)) == E_ARG                # mode 3
+    assert L.eorb_search_by_projection_last_pose(h, p(F.kps), 16, p(F.desc), 32, None, C.byref(v), p(kps), 8, None, None, None, p(md), p(ob),
+                                                 C.byref(F.gb), p(fm), 7.0, 0, 1, None, None, None, C.byref(nm)) == E_ARG                # no positions
+    assert L.eorb_search_by_projection_kf_pose(h, p(F.kps), 16, p(F.desc), 32, None, C.byref(v), p(kps), 8, None, A[0], None, A[3], None, p(md),
+                                               C.byref(F.gb), p(fm), 10.0, 100, 1, None, None, None, C.byref(nm)) == E_ARG               # no min_dist
+    assert L.eorb_search_by_projection_kf_pose(h, p(F.kps), 16, p(F.desc), 32, None, C.byref(v), p(kps), 0, None, None, None, None, None, None,
+                                               C.byref(F.gb), p(fm), 10.0, 100, 1, None, None, None, C.byref(nm)) == 0
