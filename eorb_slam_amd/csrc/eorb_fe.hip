@@ -33,11 +33,6 @@ int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR
                      int32_t* d_kdist2, int32_t* d_cand, int32_t* d_dist2);
 int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A);
 constexpr int kTcMaxKpsHost = 8192;             // = kTcMaxKps (match.hip): nL + nR of a two-camera matcher
-int search_bow_fisheye_dev(eorb_ctx* c, const eorb_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
-                           const uint32_t* kf_nodes, const int32_t* kf_off, const int32_t* kf_idx, int kf_nn,
-                           const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc, const uint32_t* f_nodes, const int32_t* f_off,
-                           const int32_t* f_idx, int f_nn, int32_t* match_f, int8_t* bin_f, int32_t* histo, int32_t* nmatches,
-                           float nnratio, int checkOri);
 int search_proj_last_dev(eorb_ctx* c, const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride,
                          const uint8_t* cur_is_orb, const eorb_keypoint* last_kps, int n_last, const uint8_t* last_is_orb,
                          const uint8_t* valid, const float* uv, const uint8_t* mp_desc, const uint8_t* mp_obs,
@@ -51,13 +46,6 @@ int search_proj_map_dev(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint
 
 int orb_pyramid_blur_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride);
 int orb_tracked_dev(eorb_ctx* c, eorb_keypoint* d_kps, int n, int mode, const uint8_t* d_ref, uint8_t* d_desc, uint8_t* d_oob);
-int search_bow_dev(eorb_ctx* c, const eorb_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
-                   const uint32_t* kf_nodes, const int32_t* kf_off, const int32_t* kf_idx, int kf_nn,
-                   const eorb_keypoint* f_kps, int n_f, const uint8_t* f_desc, const uint32_t* f_nodes, const int32_t* f_off,
-                   const int32_t* f_idx, int f_nn, int32_t* match_f, int8_t* bin_f, int32_t* histo, int32_t* nmatches,
-                   float nnratio, int checkOri, int kf_kf, const uint8_t* f_has_mp, int32_t* match12, int n_kf);
-int search_tri_dev(eorb_ctx* c, const TriArgs& A);
-int search_tri_kb8_dev(eorb_ctx* c, const TriKbArgs& K);
 int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const eorb_keypoint* kps1,
                       const eorb_keypoint* kps2, int n, const float* sig1, const float* sig2, float* out);
 int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell);
@@ -2047,6 +2035,34 @@ int eorb_search_by_projection_kf_pose(eorb_ctx* c,
                             nullptr, valid, uv, level, nmatches);
 }
 
+// The two feature vectors of a node walk (SearchByBoW, SearchForTriangulation) as the caller holds them.  queue() checks every
+// index against its side's feature count and lays [nodes | off | idx] of both sides out as one input of the arena; after
+// A.upload(), dev(A, side) is that side with device pointers.
+struct HostFv { const uint32_t* nodes; const int32_t* off; const int32_t* idx; int nn, n_features; const char* name; };
+struct FvPair {
+    std::vector<int32_t> blk; size_t o_blk = 0, base[2] = {0, 0}; int nn[2] = {0, 0};
+    int queue(eorb_ctx* c, Arena& A, const char* what, const HostFv& s0, const HostFv& s1)
+    {
+        const HostFv* side[2] = {&s0, &s1};
+        for (int k = 0; k < 2; k++) {
+            const HostFv& s = *side[k];
+            const int ni = s.off[s.nn];
+            for (int i = 0; i < ni; i++) if (s.idx[i] < 0 || s.idx[i] >= s.n_features) return set_err(c, EORB_E_ARG, "%s: %s index out of range", what, s.name);
+            base[k] = blk.size(); nn[k] = s.nn;
+            blk.insert(blk.end(), (const int32_t*)s.nodes, (const int32_t*)s.nodes + s.nn);
+            blk.insert(blk.end(), s.off, s.off + s.nn + 1);
+            blk.insert(blk.end(), s.idx, s.idx + ni);
+        }
+        o_blk = A.in(blk.data(), sizeof(int32_t) * blk.size());
+        return EORB_OK;
+    }
+    FeatVec dev(const Arena& A, int k) const
+    {
+        const int32_t* B = A.dev<int32_t>(o_blk) + base[k];
+        return FeatVec{(const uint32_t*)B, B + nn[k], B + nn[k] + nn[k] + 1, nn[k]};
+    }
+};
+
 static int bow_common(eorb_ctx* c, int kf_kf,
         const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
         const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
@@ -2062,48 +2078,28 @@ static int bow_common(eorb_ctx* c, int kf_kf,
     const int nout = kf_kf ? n_kf : n_f;
     for (int i = 0; i < nout; i++) match_out[i] = -1;
     if (n_kf == 0 || n_f == 0 || kf_nn == 0 || f_nn == 0) return EORB_OK;
-    const int nki = kf_node_off[kf_nn], nfi = f_node_off[f_nn];
-    for (int i = 0; i < nki; i++) if (kf_idx[i] < 0 || kf_idx[i] >= n_kf) return set_err(c, EORB_E_ARG, "search_by_bow: KeyFrame index out of range");
-    for (int i = 0; i < nfi; i++) if (f_idx[i] < 0 || f_idx[i] >= n_f) return set_err(c, EORB_E_ARG, "search_by_bow: frame index out of range");
     int rc;
     Arena A(c);
+    FvPair fv;
+    if ((rc = fv.queue(c, A, "search_by_bow", {kf_nodes, kf_node_off, kf_idx, kf_nn, n_kf, "KeyFrame"}, {f_nodes, f_node_off, f_idx, f_nn, n_f, "frame"})))
+        return rc;
     const size_t o_kk = A.in(kf_kps, sizeof(eorb_keypoint) * n_kf), o_kd = A.in(kf_desc, 32 * (size_t)n_kf);
     const size_t o_fk = A.in(f_kps, sizeof(eorb_keypoint) * n_f), o_fd = A.in(f_desc, 32 * (size_t)n_f);
     std::vector<uint8_t> flags((size_t)n_kf + n_f, 1);
     memcpy(flags.data(), kf_has_mp, n_kf);
     if (f_has_mp) memcpy(flags.data() + n_kf, f_has_mp, n_f);
     const size_t o_fl = A.in(flags.data(), flags.size());
-    // CSR blocks: [kf_nodes | kf_off | kf_idx] and [f_nodes | f_off | f_idx]
-    std::vector<int32_t> blk;
-    blk.insert(blk.end(), (const int32_t*)kf_nodes, (const int32_t*)kf_nodes + kf_nn);
-    blk.insert(blk.end(), kf_node_off, kf_node_off + kf_nn + 1);
-    blk.insert(blk.end(), kf_idx, kf_idx + nki);
-    const size_t fbase = blk.size();
-    blk.insert(blk.end(), (const int32_t*)f_nodes, (const int32_t*)f_nodes + f_nn);
-    blk.insert(blk.end(), f_node_off, f_node_off + f_nn + 1);
-    blk.insert(blk.end(), f_idx, f_idx + nfi);
-    const size_t o_blk = A.in(blk.data(), sizeof(int32_t) * blk.size());
     // outputs, contiguous: histogram (nmatches at [32]) | frame matches | KeyFrame matches; then the rotation bins
     const size_t o_hist = A.reserve(sizeof(int32_t) * 40), o_mf = A.reserve(sizeof(int32_t) * n_f), o_m12 = A.reserve(sizeof(int32_t) * n_kf);
     const size_t o_bin = A.reserve((size_t)std::max(n_f, n_kf));
     if ((rc = A.upload())) return rc;
-    const int32_t* B = A.dev<int32_t>(o_blk);
     int32_t* hist = A.dev<int32_t>(o_hist);
     const uint8_t* fl = A.dev<uint8_t>(o_fl);
-    if (fisheye_nL >= 0)
-        rc = search_bow_fisheye_dev(c, A.dev<eorb_keypoint>(o_kk), A.dev<uint8_t>(o_kd), fl,
-                                    (const uint32_t*)B, B + kf_nn, B + kf_nn + kf_nn + 1, kf_nn,
-                                    A.dev<eorb_keypoint>(o_fk), n_f, fisheye_nL, A.dev<uint8_t>(o_fd),
-                                    (const uint32_t*)(B + fbase), B + fbase + f_nn, B + fbase + f_nn + f_nn + 1, f_nn,
-                                    A.dev<int32_t>(o_mf), A.dev<int8_t>(o_bin), hist, hist + 32, nnratio, checkOri);
-    else
-    rc = search_bow_dev(c, A.dev<eorb_keypoint>(o_kk), A.dev<uint8_t>(o_kd), fl,
-                        (const uint32_t*)B, B + kf_nn, B + kf_nn + kf_nn + 1, kf_nn,
-                        A.dev<eorb_keypoint>(o_fk), n_f, A.dev<uint8_t>(o_fd),
-                        (const uint32_t*)(B + fbase), B + fbase + f_nn, B + fbase + f_nn + f_nn + 1, f_nn,
-                        A.dev<int32_t>(o_mf), A.dev<int8_t>(o_bin), hist, hist + 32, nnratio, checkOri, kf_kf,
-                        fl + n_kf, A.dev<int32_t>(o_m12), n_kf);
-    if (rc) return rc;
+    const BowArgs B{A.dev<eorb_keypoint>(o_kk), A.dev<uint8_t>(o_kd), fl, fv.dev(A, 0),
+                    A.dev<eorb_keypoint>(o_fk), n_f, A.dev<uint8_t>(o_fd), fv.dev(A, 1),
+                    A.dev<int32_t>(o_mf), A.dev<int8_t>(o_bin), hist, hist + 32, nnratio, checkOri, kf_kf,
+                    fl + n_kf, A.dev<int32_t>(o_m12), n_kf};
+    if ((rc = fisheye_nL >= 0 ? search_bow_fisheye_dev(c, B, fisheye_nL) : search_bow_dev(c, B))) return rc;
     const size_t o_out = kf_kf ? o_m12 : o_mf;
     const char* h;
     if ((rc = A.download(o_hist, o_out + sizeof(int32_t) * nout - o_hist, &h))) return rc;
@@ -2334,9 +2330,10 @@ static int search_tri_common(eorb_ctx* c, const char* what,
     if (nmatches) *nmatches = 0;
     for (int i = 0; i < n1; i++) match12[i] = -1;
     if (n1 == 0 || n2 == 0 || nn1 == 0 || nn2 == 0) return EORB_OK;
-    const int nki = node_off1[nn1], nfi = node_off2[nn2];
-    for (int i = 0; i < nki; i++) if (idx1[i] < 0 || idx1[i] >= n1) return set_err(c, EORB_E_ARG, "%s: pKF1 index out of range", what);
-    for (int i = 0; i < nfi; i++) if (idx2[i] < 0 || idx2[i] >= n2) return set_err(c, EORB_E_ARG, "%s: pKF2 index out of range", what);
+    int rc;
+    Arena A(c);
+    FvPair fv;
+    if ((rc = fv.queue(c, A, what, {nodes1, node_off1, idx1, nn1, n1, "pKF1"}, {nodes2, node_off2, idx2, nn2, n2, "pKF2"}))) return rc;
     for (int i = 0; i < n2; i++)
         if (elig2[i] && (kps2[i].octave < 0 || kps2[i].octave >= nlevels))
             return set_err(c, EORB_E_ARG, "%s: pKF2 keypoint %d has octave %d outside [0,%d)", what, i, kps2[i].octave, nlevels);
@@ -2344,43 +2341,27 @@ static int search_tri_common(eorb_ctx* c, const char* what,
         for (int i = 0; i < n1; i++)
             if ((elig1[i] & 1) && (kps1[i].octave < 0 || kps1[i].octave >= nlevels))
                 return set_err(c, EORB_E_ARG, "%s: pKF1 keypoint %d has octave %d outside [0,%d)", what, i, kps1[i].octave, nlevels);
-    int rc;
-    Arena A(c);
     const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * n1), o_d1 = A.in(desc1, (size_t)stride1 * n1);
     const size_t o_k2 = A.in(kps2, sizeof(eorb_keypoint) * n2), o_d2 = A.in(desc2, (size_t)stride2 * n2);
     const size_t o_e1 = A.in(elig1, n1), o_e2 = A.in(elig2, n2);
-    std::vector<int32_t> blk;
-    blk.insert(blk.end(), (const int32_t*)nodes1, (const int32_t*)nodes1 + nn1);
-    blk.insert(blk.end(), node_off1, node_off1 + nn1 + 1);
-    blk.insert(blk.end(), idx1, idx1 + nki);
-    const size_t fbase = blk.size();
-    blk.insert(blk.end(), (const int32_t*)nodes2, (const int32_t*)nodes2 + nn2);
-    blk.insert(blk.end(), node_off2, node_off2 + nn2 + 1);
-    blk.insert(blk.end(), idx2, idx2 + nfi);
-    const size_t o_blk = A.in(blk.data(), sizeof(int32_t) * blk.size());
     const size_t o_sc = A.in(scale2, sizeof(float) * nlevels), o_sg = A.in(sigma2_2, sizeof(float) * nlevels);
     const size_t o_s1 = kb ? A.in(sigma2_1, sizeof(float) * nlevels) : 0;
     // outputs, contiguous: histogram (nmatches at [32]) | matches; then the rotation bins
     const size_t o_hist = A.reserve(sizeof(int32_t) * 40), o_m12 = A.reserve(sizeof(int32_t) * (size_t)n1), o_bin = A.reserve((size_t)n1);
     if ((rc = A.upload())) return rc;
-    const int32_t* B = A.dev<int32_t>(o_blk);
     int32_t* hist = A.dev<int32_t>(o_hist);
     TriArgs T{};
     T.kps1 = A.dev<eorb_keypoint>(o_k1); T.n1 = n1; T.desc1 = A.dev<uint8_t>(o_d1); T.stride1 = stride1;
-    T.elig1 = A.dev<uint8_t>(o_e1);
-    T.nodes1 = (const uint32_t*)B; T.off1 = B + nn1; T.idx1 = B + nn1 + nn1 + 1; T.nn1 = nn1;
+    T.elig1 = A.dev<uint8_t>(o_e1); T.fv1 = fv.dev(A, 0);
     T.kps2 = A.dev<eorb_keypoint>(o_k2); T.n2 = n2; T.desc2 = A.dev<uint8_t>(o_d2); T.stride2 = stride2;
-    T.elig2 = A.dev<uint8_t>(o_e2);
-    T.nodes2 = (const uint32_t*)(B + fbase); T.off2 = B + fbase + nn2; T.idx2 = B + fbase + nn2 + nn2 + 1; T.nn2 = nn2;
+    T.elig2 = A.dev<uint8_t>(o_e2); T.fv2 = fv.dev(A, 1);
     T.epx = ep[0]; T.epy = ep[1];
     if (F12) for (int i = 0; i < 9; i++) T.F[i] = F12[i];
     T.scale2 = A.dev<float>(o_sc); T.sigma2_2 = A.dev<float>(o_sg); T.nlevels = nlevels;
     T.bCoarse = bCoarse; T.checkOri = checkOri;
     T.match12 = A.dev<int32_t>(o_m12); T.bin1 = A.dev<int8_t>(o_bin); T.histo = hist; T.nmatches = hist + 32;
-    if (kb) {
-        kb->T = T; kb->sigma2_1 = A.dev<float>(o_s1);
-        if ((rc = search_tri_kb8_dev(c, *kb))) return rc;
-    } else if ((rc = search_tri_dev(c, T))) return rc;
+    if (kb) { kb->T = T; kb->sigma2_1 = A.dev<float>(o_s1); }
+    if ((rc = search_tri_dev(c, T, kb))) return rc;
     const char* h;
     if ((rc = A.download(o_hist, o_m12 + sizeof(int32_t) * (size_t)n1 - o_hist, &h))) return rc;
     memcpy(match12, h + o_m12, sizeof(int32_t) * (size_t)n1);

@@ -1013,38 +1013,85 @@ int search_proj_map_dev(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint
 
 
 // ---------------------------------------------------------------------------------------------------
+// Pieces shared by the walks over two DBoW2 feature vectors (SearchByBoW, its two-camera form, SearchForTriangulation) and by
+// tc_search: 64-bit keys (distance on top, candidate order below) reduced over the wavefront by shuffles.  (The window matcher
+// keeps its DPP forms wave_top2 / wave_min_u64.)
+__device__ __forceinline__ void top2_insert(uint64_t key, uint64_t& k0, uint64_t& k1)
+{   // (k0 <= k1 going in and out; selects, not branches: stores through a chosen reference would put the keys in scratch memory)
+    const uint64_t hi = key < k0 ? k0 : key;
+    k0 = key < k0 ? key : k0;
+    k1 = hi < k1 ? hi : k1;
+}
+
+// every lane's (k0 <= k1) -> the wavefront's two smallest keys, in every lane
+__device__ __forceinline__ void shfl_top2(uint64_t& k0, uint64_t& k1)
+{
+    uint64_t a = k0, b = k1;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint64_t o0 = __shfl_xor(a, d, 64), o1 = __shfl_xor(b, d, 64);
+        const uint64_t l0 = a < o0 ? a : o0, h0 = a < o0 ? o0 : a, s1 = b < o1 ? b : o1;
+        a = l0; b = h0 < s1 ? h0 : s1;
+    }
+    k0 = a; k1 = b;
+}
+
+__device__ __forceinline__ uint64_t shfl_min(uint64_t k)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k, d, 64); k = o < k ? o : k; }
+    return k;
+}
+
+// position of `node` in fv.nodes or -1 (ids are ascending and unique: the reference's lower_bound walk).  The lanes look at 64
+// positions at a time -- one memory round trip, not the seven dependent ones of a binary search.
+__device__ __forceinline__ int find_node(const FeatVec& fv, uint32_t node, int lane)
+{
+    for (int base = 0; base < fv.nn; base += 64) {
+        const int pos = base + lane;
+        const uint64_t hit = __ballot(pos < fv.nn && fv.nodes[pos] == node);
+        if (hit) return base + __ffsll((unsigned long long)hit) - 1;
+    }
+    return -1;
+}
+
+// one lane records a match: slot, counter, rotation bin (rotHist holds binAt: idx1 for (KF, KF), else bestIdxF) and histogram.
+// ATOMIC: match_f is read by the wavefront's next KeyFrame feature through global memory (relaxed, agent scope).
+template <bool ATOMIC>
+__device__ __forceinline__ void bow_commit(const BowArgs& A, int realIdxKF, int bestIdxF, int binAt)
+{
+    if (ATOMIC) __hip_atomic_store(&A.match_f[bestIdxF], realIdxKF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else A.match_f[bestIdxF] = realIdxKF;
+    atomicAdd(A.nmatches, 1);
+    if (A.kf_kf) A.match12[realIdxKF] = bestIdxF;
+    if (A.checkOri) {
+        const int bin = rot_bin(A.kf_kps[realIdxKF].angle, A.f_kps[bestIdxF].angle);
+        A.bin_f[binAt] = (int8_t)bin;
+        atomicAdd(&A.histo[bin], 1);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (:276-478), mono branch.  A frame feature belongs to
 // exactly one vocabulary node, so the greedy state (vpMapPointMatches) never crosses nodes: shared nodes are matched
 // concurrently (one wavefront each), KeyFrame features of a node sequentially, the node's frame features over the lanes.
-struct BowArgs {
-    const eorb_keypoint* kf_kps; const uint8_t* kf_desc; const uint8_t* kf_has_mp;
-    const uint32_t* kf_nodes; const int32_t* kf_off; const int32_t* kf_idx; int kf_nn;
-    const eorb_keypoint* f_kps; int n_f; const uint8_t* f_desc;
-    const uint32_t* f_nodes; const int32_t* f_off; const int32_t* f_idx; int f_nn;
-    int32_t* match_f; int8_t* bin_f; int32_t* histo; int32_t* nmatches;
-    float nnratio; int checkOri;
-    int kf_kf;                       // 1: SearchByBoW(KF, KF) (:833-973): output per idx1, vbMatched2 flags, strict TH_LOW
-    const uint8_t* f_has_mp; int32_t* match12; int n_kf;
-};
+__device__ __forceinline__ bool bow_accept(const BowArgs& A, uint64_t k0, uint64_t k1)
+{
+    if (k0 == ~0ull || (int)(k0 >> 32) >= 256) return false;
+    const int bestDist1 = (int)(k0 >> 32);
+    const int bestDist2 = (k1 != ~0ull && (int)(k1 >> 32) < 256) ? (int)(k1 >> 32) : 256;
+    return (A.kf_kf ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW) && (float)bestDist1 < A.nnratio * (float)bestDist2;
+}
 
 __global__ __launch_bounds__(256) void search_bow_kernel(BowArgs A)
 {
     const int lane = threadIdx.x & 63;
     const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    for (int a = gw; a < A.kf_nn; a += nw) {
-        // the frame node with the same id (both lists ascending): binary search = the reference's lower_bound walk
-        const uint32_t node = A.kf_nodes[a];
-        // (node ids are unique in a FeatureVector: the lanes look at 64 positions at a time -- one memory round trip, not the seven
-        // dependent ones of a binary search)
-        int lo = -1;
-        for (int base = 0; base < A.f_nn && lo < 0; base += 64) {
-            const int pos = base + lane;
-            const uint64_t hit = __ballot(pos < A.f_nn && A.f_nodes[pos] == node);
-            if (hit) lo = base + __ffsll((unsigned long long)hit) - 1;
-        }
+    for (int a = gw; a < A.kf_fv.nn; a += nw) {
+        const int lo = find_node(A.f_fv, A.kf_fv.nodes[a], lane);
         if (lo < 0) continue;
-        const int f0 = A.f_off[lo], f1 = A.f_off[lo + 1];
-        const int k0n = A.kf_off[a], k1n = A.kf_off[a + 1];
+        const int f0 = A.f_fv.off[lo], f1 = A.f_fv.off[lo + 1];
+        const int k0n = A.kf_fv.off[a], k1n = A.kf_fv.off[a + 1];
         if (f1 - f0 <= 64 && k1n - k0n <= 64) {
             // The usual node (about ten features on either side): everything it touches is loaded once -- lane = frame feature for the
             // candidates, lane = KeyFrame feature for the queries, handed round by shuffles.  A frame feature belongs to this node
@@ -1053,14 +1100,14 @@ __global__ __launch_bounds__(256) void search_bow_kernel(BowArgs A)
             const int nF = f1 - f0, nK = k1n - k0n;
             int idxF = -1; bool availF = false; uint64_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
             if (lane < nF) {
-                idxF = A.f_idx[f0 + lane];
+                idxF = A.f_fv.idx[f0 + lane];
                 availF = A.match_f[idxF] < 0 && !(A.kf_kf && !A.f_has_mp[idxF]);
                 const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)idxF * 32);
                 t0 = tp[0]; t1 = tp[1]; t2 = tp[2]; t3 = tp[3];
             }
             int idxK = -1; bool hasK = false; uint64_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
             if (lane < nK) {
-                idxK = A.kf_idx[k0n + lane];
+                idxK = A.kf_fv.idx[k0n + lane];
                 hasK = A.kf_has_mp[idxK] != 0;
                 const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)idxK * 32);
                 q0 = dq[0]; q1 = dq[1]; q2 = dq[2]; q3 = dq[3];
@@ -1074,85 +1121,50 @@ __global__ __launch_bounds__(256) void search_bow_kernel(BowArgs A)
                     const int dist = __popcll(b0 ^ t0) + __popcll(b1 ^ t1) + __popcll(b2 ^ t2) + __popcll(b3 ^ t3);
                     k0 = ((uint64_t)dist << 32) | (uint32_t)lane;          // candidate order = vector order = lane order
                 }
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    const uint64_t o0 = __shfl_xor(k0, d, 64), o1 = __shfl_xor(k1, d, 64);
-                    const uint64_t l0 = k0 < o0 ? k0 : o0, h0 = k0 < o0 ? o0 : k0, s1 = k1 < o1 ? k1 : o1;
-                    k0 = l0; k1 = h0 < s1 ? h0 : s1;
-                }
-                if (k0 != ~0ull && (int)(k0 >> 32) < 256) {
-                    const int bestDist1 = (int)(k0 >> 32);
-                    const int bestDist2 = (k1 != ~0ull && (int)(k1 >> 32) < 256) ? (int)(k1 >> 32) : 256;
-                    if ((A.kf_kf ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW) && (float)bestDist1 < A.nnratio * (float)bestDist2) {
-                        const int win = (int)(k0 & 63u);
-                        const int bestIdxF = __shfl(idxF, win, 64);
-                        if (lane == win) availF = false;
-                        if (lane == 0) {
-                            A.match_f[bestIdxF] = realIdxKF;
-                            atomicAdd(A.nmatches, 1);
-                            if (A.kf_kf) A.match12[realIdxKF] = bestIdxF;
-                            if (A.checkOri) {
-                                const int bin = rot_bin(A.kf_kps[realIdxKF].angle, A.f_kps[bestIdxF].angle);
-                                A.bin_f[A.kf_kf ? realIdxKF : bestIdxF] = (int8_t)bin;
-                                atomicAdd(&A.histo[bin], 1);
-                            }
-                        }
-                    }
+                shfl_top2(k0, k1);
+                if (bow_accept(A, k0, k1)) {
+                    const int win = (int)(k0 & 63u);
+                    const int bestIdxF = __shfl(idxF, win, 64);
+                    if (lane == win) availF = false;
+                    if (lane == 0) bow_commit<false>(A, realIdxKF, bestIdxF, A.kf_kf ? realIdxKF : bestIdxF);
                 }
             }
             continue;
         }
-        for (int iKF = A.kf_off[a]; iKF < A.kf_off[a + 1]; iKF++) {
-            const int realIdxKF = A.kf_idx[iKF];
+        for (int iKF = k0n; iKF < k1n; iKF++) {
+            const int realIdxKF = A.kf_fv.idx[iKF];
             if (!A.kf_has_mp[realIdxKF]) continue;
             const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)realIdxKF * 32);
             const uint64_t q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3];
             // candidate order = vector order (iF): key = dist << 32 | iF keeps the reference's first-wins tie rule
             uint64_t k0 = ~0ull, k1 = ~0ull;
             for (int iF = f0 + lane; iF < f1; iF += 64) {
-                const int realIdxF = A.f_idx[iF];
+                const int realIdxF = A.f_fv.idx[iF];
                 if (__hip_atomic_load(&A.match_f[realIdxF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) continue;   // vpMapPointMatches[realIdxF] / vbMatched2
                 if (A.kf_kf && !A.f_has_mp[realIdxF]) continue;                      // !pMP2 || pMP2->isBad()
                 const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)realIdxF * 32);
                 const int dist = __popcll(q0 ^ tp[0]) + __popcll(q1 ^ tp[1]) + __popcll(q2 ^ tp[2]) + __popcll(q3 ^ tp[3]);
-                const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)iF;
-                if (key < k0) { k1 = k0; k0 = key; }
-                else if (key < k1) k1 = key;
+                top2_insert(((uint64_t)dist << 32) | (uint32_t)iF, k0, k1);
             }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const uint64_t o0 = __shfl_xor(k0, d, 64), o1 = __shfl_xor(k1, d, 64);
-                const uint64_t l0 = k0 < o0 ? k0 : o0, h0 = k0 < o0 ? o0 : k0, s1 = k1 < o1 ? k1 : o1;
-                k0 = l0; k1 = h0 < s1 ? h0 : s1;
-            }
-            if (k0 != ~0ull && (int)(k0 >> 32) < 256) {
-                const int bestDist1 = (int)(k0 >> 32);
-                const int bestDist2 = (k1 != ~0ull && (int)(k1 >> 32) < 256) ? (int)(k1 >> 32) : 256;
-                if ((A.kf_kf ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW) && (float)bestDist1 < A.nnratio * (float)bestDist2) {
-                    if (lane == 0) {
-                        const int bestIdxF = A.f_idx[(int)(k0 & 0xffffffffu)];
-                        __hip_atomic_store(&A.match_f[bestIdxF], realIdxKF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        atomicAdd(A.nmatches, 1);
-                        if (A.kf_kf) A.match12[realIdxKF] = bestIdxF;
-                        if (A.checkOri) {
-                            const int bin = rot_bin(A.kf_kps[realIdxKF].angle, A.f_kps[bestIdxF].angle);
-                            A.bin_f[A.kf_kf ? realIdxKF : bestIdxF] = (int8_t)bin;      // rotHist holds idx1 (KF,KF) or bestIdxF (KF,F)
-                            atomicAdd(&A.histo[bin], 1);
-                        }
-                    }
-                    __threadfence();          // the next KeyFrame feature of this node must see match_f
+            shfl_top2(k0, k1);
+            if (bow_accept(A, k0, k1)) {
+                if (lane == 0) {
+                    const int bestIdxF = A.f_fv.idx[(int)(k0 & 0xffffffffu)];
+                    bow_commit<true>(A, realIdxKF, bestIdxF, A.kf_kf ? realIdxKF : bestIdxF);
                 }
+                __threadfence();          // the next KeyFrame feature of this node must see match_f
             }
         }
     }
 }
 
-__global__ void search_bow_finish_kernel(BowArgs A)
+// the rotation check's end (ComputeThreeMaxima + the erase loop) over the n slots of out whose bins were recorded
+__global__ void search_bow_finish_kernel(int32_t* out, const int8_t* bin, int n, int32_t* histo, int32_t* nmatches)
 {
     __shared__ int keep;
     if (threadIdx.x == 0) {
         int h[HISTO_LENGTH];
-        for (int i = 0; i < HISTO_LENGTH; i++) h[i] = A.histo[i];
+        for (int i = 0; i < HISTO_LENGTH; i++) h[i] = histo[i];
         int i1, i2, i3;
         three_maxima(h, HISTO_LENGTH, i1, i2, i3);
         int k = 0;
@@ -1161,13 +1173,11 @@ __global__ void search_bow_finish_kernel(BowArgs A)
     }
     __syncthreads();
     int dec = 0;
-    const int nout = A.kf_kf ? A.n_kf : A.n_f;
-    int32_t* out = A.kf_kf ? A.match12 : A.match_f;
-    for (int i = threadIdx.x; i < nout; i += blockDim.x) {
-        const int b = A.bin_f[i];
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int b = bin[i];
         if (b >= 0 && !(keep & (1 << b)) && out[i] >= 0) { out[i] = -1; dec++; }
     }
-    if (dec) atomicSub(A.nmatches, dec);
+    if (dec) atomicSub(nmatches, dec);
 }
 
 __global__ void bow_init_kernel(int32_t* match_f, int8_t* bin_f, int n_f, int32_t* histo, int32_t* nmatches, int32_t* match12, int n_kf)
@@ -1180,21 +1190,16 @@ __global__ void bow_init_kernel(int32_t* match_f, int8_t* bin_f, int n_f, int32_
     if (i == 0) *nmatches = 0;
 }
 
-int search_bow_dev(eorb_ctx* c, const eorb_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
-                   const uint32_t* kf_nodes, const int32_t* kf_off, const int32_t* kf_idx, int kf_nn,
-                   const eorb_keypoint* f_kps, int n_f, const uint8_t* f_desc, const uint32_t* f_nodes, const int32_t* f_off,
-                   const int32_t* f_idx, int f_nn, int32_t* match_f, int8_t* bin_f, int32_t* histo, int32_t* nmatches,
-                   float nnratio, int checkOri, int kf_kf, const uint8_t* f_has_mp, int32_t* match12, int n_kf)
+int search_bow_dev(eorb_ctx* c, const BowArgs& A)
 {
-    BowArgs A{kf_kps, kf_desc, kf_has_mp, kf_nodes, kf_off, kf_idx, kf_nn, f_kps, n_f, f_desc, f_nodes, f_off, f_idx, f_nn,
-              match_f, bin_f, histo, nmatches, nnratio, checkOri, kf_kf, f_has_mp, match12, n_kf};
     ProfScope ps(c, "search_bow");
-    bow_init_kernel<<<(std::max(std::max(n_f, n_kf), 32) + 255) / 256, 256, 0, c->stream>>>(match_f, bin_f, n_f, histo, nmatches,
-                                                                                          kf_kf ? match12 : nullptr, n_kf);
-    if (kf_nn > 0 && f_nn > 0) {
-        const int blocks = std::min((kf_nn + 3) / 4, 1024);
+    bow_init_kernel<<<(std::max(std::max(A.n_f, A.n_kf), 32) + 255) / 256, 256, 0, c->stream>>>(A.match_f, A.bin_f, A.n_f, A.histo, A.nmatches,
+                                                                                              A.kf_kf ? A.match12 : nullptr, A.n_kf);
+    if (A.kf_fv.nn > 0 && A.f_fv.nn > 0) {
+        const int blocks = std::min((A.kf_fv.nn + 3) / 4, 1024);
         search_bow_kernel<<<blocks, 256, 0, c->stream>>>(A);
-        if (checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A);
+        if (A.checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A.kf_kf ? A.match12 : A.match_f, A.bin_f, A.kf_kf ? A.n_kf : A.n_f,
+                                                                           A.histo, A.nmatches);
     }
     EORB_LAUNCH_CHECK(c, "search_bow kernels");
     return EORB_OK;
@@ -1205,6 +1210,13 @@ int search_bow_dev(eorb_ctx* c, const eorb_keypoint* kf_kps, const uint8_t* kf_d
 // vbMatched2 is never written in the reference, so every pKF1 feature is independent: one wave per feature-vector entry of
 // pKF1, lanes over the pKF2 features of the same vocabulary node.  The sequential update rule (skip dist > bestDist, replace
 // on pass) keeps the passing candidate with the least distance, the LAST one among equals: key = dist << 32 | ~position.
+// The geometric check has no side effects, so a lane runs it only for a candidate that would beat its own best key: the minimum
+// over passing candidates is the reference's answer.
+//
+// tri_walk is the whole walk; a geometry policy G supplies what depends on pCamera1:
+//   G(args, id1, e1, kp1)   the per-pKF1-feature setup
+//   epipole_gate(e2)        whether the epipole-distance test applies to this pair (:1093-1105)
+//   ok(id2, kp2)            pCamera1->epipolarConstrain(...) (:1107-1137)
 
 __device__ __forceinline__ bool epipolar_ok(float x1, float y1, float x2, float y2, const float* F, float unc)
 {   // Pinhole::epipolarConstrain (src/CameraModels/Pinhole.cpp:142-156) with F12 given
@@ -1218,105 +1230,29 @@ __device__ __forceinline__ bool epipolar_ok(float x1, float y1, float x2, float 
     return dsqr < 3.84f * unc;
 }
 
-__global__ __launch_bounds__(256) void search_tri_kernel(TriArgs A)
+template <class G, class Args>
+__device__ __forceinline__ void tri_walk(const TriArgs& A, const Args& GA)
 {
     const int lane = threadIdx.x & 63;
     const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    const int total = A.off1[A.nn1];
+    const int total = A.fv1.off[A.fv1.nn];
     for (int p = gw; p < total; p += nw) {
-        const int id1 = A.idx1[p];
+        const int id1 = A.fv1.idx[p];
         const uint8_t e1 = A.elig1[id1];                // bit 0: eligible; bit 1: rectified-stereo keypoint (mvuRight >= 0, bStereo1 :1051)
         if (!(e1 & 1)) continue;
-        int lo = 0, hi = A.nn1;                         // node a with off1[a] <= p < off1[a+1]
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.off1[mid] <= p) lo = mid; else hi = mid; }
-        const uint32_t node = A.nodes1[lo];
-        int l2 = 0, h2 = A.nn2;
-        while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (A.nodes2[mid] < node) l2 = mid + 1; else h2 = mid; }
-        if (l2 >= A.nn2 || A.nodes2[l2] != node) continue;
+        int lo = 0, hi = A.fv1.nn;                      // node a with off1[a] <= p < off1[a+1]
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.fv1.off[mid] <= p) lo = mid; else hi = mid; }
+        const uint32_t node = A.fv1.nodes[lo];
+        int l2 = 0, h2 = A.fv2.nn;
+        while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (A.fv2.nodes[mid] < node) l2 = mid + 1; else h2 = mid; }
+        if (l2 >= A.fv2.nn || A.fv2.nodes[l2] != node) continue;
         const eorb_keypoint kp1 = A.kps1[id1];
+        const G g(GA, id1, e1, kp1);
         uint64_t q0, q1, q2, q3;
         load_desc32(A.desc1 + (size_t)id1 * A.stride1, q0, q1, q2, q3);
         uint64_t k0 = ~0ull;
-        for (int i2 = A.off2[l2] + lane; i2 < A.off2[l2 + 1]; i2 += 64) {
-            const int id2 = A.idx2[i2];
-            const uint8_t e2 = A.elig2[id2];
-            if (!(e2 & 1)) continue;
-            uint64_t t0, t1, t2, t3;
-            load_desc32(A.desc2 + (size_t)id2 * A.stride2, t0, t1, t2, t3);
-            const int dist = __popcll(q0 ^ t0) + __popcll(q1 ^ t1) + __popcll(q2 ^ t2) + __popcll(q3 ^ t3);
-            if (dist > TH_LOW) continue;
-            const eorb_keypoint kp2 = A.kps2[id2];
-            if (kp2.octave < 0 || kp2.octave >= A.nlevels) continue;            // rejected on the host already
-            if (!((e1 | e2) & 2)) {                                            // "if(!bStereo1 && !bStereo2 && !pKF1->mpCamera2)" :1093
-                const float distex = A.epx - kp2.x, distey = A.epy - kp2.y;
-                if (distex * distex + distey * distey < 100 * A.scale2[kp2.octave]) continue;
-            }
-            if (!(A.bCoarse || epipolar_ok(kp1.x, kp1.y, kp2.x, kp2.y, A.F, A.sigma2_2[kp2.octave]))) continue;
-            const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)(~(uint32_t)i2);
-            if (key < k0) k0 = key;
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k0, d, 64); k0 = o < k0 ? o : k0; }
-        if (lane == 0 && k0 != ~0ull) {
-            const int bestIdx2 = A.idx2[(int)(~(uint32_t)(k0 & 0xffffffffu))];
-            A.match12[id1] = bestIdx2;
-            atomicAdd(A.nmatches, 1);
-            if (A.checkOri) {
-                const int bin = rot_bin(kp1.angle, A.kps2[bestIdx2].angle);
-                A.bin1[id1] = (int8_t)bin;
-                atomicAdd(&A.histo[bin], 1);
-            }
-        }
-    }
-}
-
-int search_tri_dev(eorb_ctx* c, const TriArgs& A)
-{
-    ProfScope ps(c, "search_for_triangulation");
-    bow_init_kernel<<<(std::max(A.n1, 32) + 255) / 256, 256, 0, c->stream>>>(A.match12, A.bin1, A.n1, A.histo, A.nmatches, nullptr, 0);
-    search_tri_kernel<<<std::min((A.n1 + 3) / 4 + 1, 2048), 256, 0, c->stream>>>(A);
-    if (A.checkOri) {
-        BowArgs B{};
-        B.kf_kf = 1; B.n_kf = A.n1; B.match12 = A.match12; B.bin_f = A.bin1; B.histo = A.histo; B.nmatches = A.nmatches;
-        search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(B);
-    }
-    EORB_LAUNCH_CHECK(c, "search_for_triangulation kernels");
-    return EORB_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// the same walk with pCamera1 = KannalaBrandt8 (:975-1214): epipolarConstrain = TriangulateMatches(...) > KB8_DEF_TH_EPC
-// (KannalaBrandt8.cpp:315-320, :416-486).  Two-camera keyframes (nleft >= 0) pick one of four poses and cameras per
-// (left/right, left/right) pair (:1107-1137) and skip the epipole test; bStereo is false for them (:1051, :1079).  The check
-// has no side effects, so a lane runs it only for a candidate that would beat its own best key: the minimum over passing
-// candidates is the reference's answer.
-
-__global__ __launch_bounds__(256) void search_tri_kb8_kernel(TriKbArgs K)
-{
-    const TriArgs& A = K.T;
-    const int lane = threadIdx.x & 63;
-    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    const int total = A.off1[A.nn1];
-    const bool twocam = K.nleft1 >= 0;
-    for (int p = gw; p < total; p += nw) {
-        const int id1 = A.idx1[p];
-        const uint8_t e1 = A.elig1[id1];
-        if (!(e1 & 1)) continue;
-        int lo = 0, hi = A.nn1;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.off1[mid] <= p) lo = mid; else hi = mid; }
-        const uint32_t node = A.nodes1[lo];
-        int l2 = 0, h2 = A.nn2;
-        while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (A.nodes2[mid] < node) l2 = mid + 1; else h2 = mid; }
-        if (l2 >= A.nn2 || A.nodes2[l2] != node) continue;
-        const eorb_keypoint kp1 = A.kps1[id1];
-        const int bRight1 = twocam && id1 >= K.nleft1;
-        const bool bStereo1 = !twocam && (e1 & 2);
-        const float sig1 = K.sigma2_1[kp1.octave];
-        uint64_t q0, q1, q2, q3;
-        load_desc32(A.desc1 + (size_t)id1 * A.stride1, q0, q1, q2, q3);
-        uint64_t k0 = ~0ull;
-        for (int i2 = A.off2[l2] + lane; i2 < A.off2[l2 + 1]; i2 += 64) {
-            const int id2 = A.idx2[i2];
+        for (int i2 = A.fv2.off[l2] + lane; i2 < A.fv2.off[l2 + 1]; i2 += 64) {
+            const int id2 = A.fv2.idx[i2];
             const uint8_t e2 = A.elig2[id2];
             if (!(e2 & 1)) continue;
             uint64_t t0, t1, t2, t3;
@@ -1327,25 +1263,16 @@ __global__ __launch_bounds__(256) void search_tri_kb8_kernel(TriKbArgs K)
             if (key >= k0) continue;                                           // cannot change this lane's answer
             const eorb_keypoint kp2 = A.kps2[id2];
             if (kp2.octave < 0 || kp2.octave >= A.nlevels) continue;            // rejected on the host already
-            if (!twocam && !bStereo1 && !(e2 & 2)) {                            // :1097-1105
+            if (g.epipole_gate(e2)) {
                 const float distex = A.epx - kp2.x, distey = A.epy - kp2.y;
                 if (distex * distex + distey * distey < 100 * A.scale2[kp2.octave]) continue;
             }
-            if (!A.bCoarse) {
-                const int bRight2 = twocam && id2 >= K.nleft2;
-                const int pose = twocam ? (bRight1 << 1 | bRight2) : 0;       // ll, lr, rl, rr
-                const WarpCam c1 = warp_cam_of(K.cam1[twocam ? bRight1 : 0]);
-                const WarpCam c2 = warp_cam_of(K.cam2[twocam ? bRight2 : 0]);
-                const float z1 = kb8_triangulate_matches(c1, c2, kp1.x, kp1.y, kp2.x, kp2.y, K.Rt + 12 * pose, K.Rt + 12 * pose + 9,
-                                                         sig1, A.sigma2_2[kp2.octave]);
-                if (!(z1 > 0.0001f)) continue;                                  // KB8_DEF_TH_EPC
-            }
+            if (!(A.bCoarse || g.ok(id2, kp2))) continue;
             k0 = key;
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k0, d, 64); k0 = o < k0 ? o : k0; }
+        k0 = shfl_min(k0);
         if (lane == 0 && k0 != ~0ull) {
-            const int bestIdx2 = A.idx2[(int)(~(uint32_t)(k0 & 0xffffffffu))];
+            const int bestIdx2 = A.fv2.idx[(int)(~(uint32_t)(k0 & 0xffffffffu))];
             A.match12[id1] = bestIdx2;
             atomicAdd(A.nmatches, 1);
             if (A.checkOri) {
@@ -1357,18 +1284,46 @@ __global__ __launch_bounds__(256) void search_tri_kb8_kernel(TriKbArgs K)
     }
 }
 
-int search_tri_kb8_dev(eorb_ctx* c, const TriKbArgs& K)
-{
-    const TriArgs& A = K.T;
-    ProfScope ps(c, "search_for_triangulation_kb8");
-    bow_init_kernel<<<(std::max(A.n1, 32) + 255) / 256, 256, 0, c->stream>>>(A.match12, A.bin1, A.n1, A.histo, A.nmatches, nullptr, 0);
-    search_tri_kb8_kernel<<<std::min((A.n1 + 3) / 4 + 1, 2048), 256, 0, c->stream>>>(K);
-    if (A.checkOri) {
-        BowArgs B{};
-        B.kf_kf = 1; B.n_kf = A.n1; B.match12 = A.match12; B.bin_f = A.bin1; B.histo = A.histo; B.nmatches = A.nmatches;
-        search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(B);
+struct TriPinhole {                  // pCamera1 = Pinhole: the test on F12
+    const TriArgs& A; const uint8_t e1; const float x1, y1;
+    __device__ __forceinline__ TriPinhole(const TriArgs& a, int, uint8_t e, const eorb_keypoint& kp1) : A(a), e1(e), x1(kp1.x), y1(kp1.y) {}
+    __device__ __forceinline__ bool epipole_gate(uint8_t e2) const { return !((e1 | e2) & 2); }      // "if(!bStereo1 && !bStereo2 && !pKF1->mpCamera2)" :1093
+    __device__ __forceinline__ bool ok(int, const eorb_keypoint& kp2) const { return epipolar_ok(x1, y1, kp2.x, kp2.y, A.F, A.sigma2_2[kp2.octave]); }
+};
+
+// pCamera1 = KannalaBrandt8: epipolarConstrain = TriangulateMatches(...) > KB8_DEF_TH_EPC (KannalaBrandt8.cpp:315-320, :416-486).
+// Two-camera keyframes (nleft >= 0) pick one of four poses and cameras per (left/right, left/right) pair (:1107-1137) and skip
+// the epipole test; bStereo is false for them (:1051, :1079).
+struct TriKb8 {
+    const TriKbArgs& K; const int bRight1; const bool bStereo1; const float x1, y1, sig1;
+    __device__ __forceinline__ TriKb8(const TriKbArgs& k, int id1, uint8_t e1, const eorb_keypoint& kp1)
+        : K(k), bRight1(k.nleft1 >= 0 && id1 >= k.nleft1), bStereo1(k.nleft1 < 0 && (e1 & 2)), x1(kp1.x), y1(kp1.y), sig1(k.sigma2_1[kp1.octave]) {}
+    __device__ __forceinline__ bool twocam() const { return K.nleft1 >= 0; }
+    __device__ __forceinline__ bool epipole_gate(uint8_t e2) const { return !twocam() && !bStereo1 && !(e2 & 2); }      // :1097-1105
+    __device__ __forceinline__ bool ok(int id2, const eorb_keypoint& kp2) const
+    {
+        const int bRight2 = twocam() && id2 >= K.nleft2;
+        const int pose = twocam() ? (bRight1 << 1 | bRight2) : 0;       // ll, lr, rl, rr
+        const WarpCam c1 = warp_cam_of(K.cam1[twocam() ? bRight1 : 0]);
+        const WarpCam c2 = warp_cam_of(K.cam2[twocam() ? bRight2 : 0]);
+        return kb8_triangulate_matches(c1, c2, x1, y1, kp2.x, kp2.y, K.Rt + 12 * pose, K.Rt + 12 * pose + 9, sig1,
+                                       K.T.sigma2_2[kp2.octave]) > 0.0001f;       // KB8_DEF_TH_EPC
     }
-    EORB_LAUNCH_CHECK(c, "search_for_triangulation_kb8 kernels");
+};
+
+// two entry points, not one with a run-time camera switch: the Pinhole walk needs a third of the KannalaBrandt8 one's registers
+__global__ __launch_bounds__(256) void search_tri_kernel(TriArgs A) { tri_walk<TriPinhole>(A, A); }
+__global__ __launch_bounds__(256) void search_tri_kb8_kernel(TriKbArgs K) { tri_walk<TriKb8>(K.T, K); }
+
+int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K)
+{
+    ProfScope ps(c, K ? "search_for_triangulation_kb8" : "search_for_triangulation");
+    const int blocks = std::min((A.n1 + 3) / 4 + 1, 2048);
+    bow_init_kernel<<<(std::max(A.n1, 32) + 255) / 256, 256, 0, c->stream>>>(A.match12, A.bin1, A.n1, A.histo, A.nmatches, nullptr, 0);
+    if (K) search_tri_kb8_kernel<<<blocks, 256, 0, c->stream>>>(*K);
+    else search_tri_kernel<<<blocks, 256, 0, c->stream>>>(A);
+    if (A.checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A.match12, A.bin1, A.n1, A.histo, A.nmatches);
+    EORB_LAUNCH_CHECK(c, K ? "search_for_triangulation_kb8 kernels" : "search_for_triangulation kernels");
     return EORB_OK;
 }
 
@@ -1930,22 +1885,6 @@ struct TcLds {
     float2* pos; int32_t* slot; uint16_t* item; int8_t* lgate; int8_t* lbest;
 };
 
-__device__ __forceinline__ void tc_top2(uint64_t key, uint64_t& k0, uint64_t& k1)
-{
-    if (key < k0) { k1 = k0; k0 = key; }
-    else if (key < k1) k1 = key;
-}
-
-__device__ __forceinline__ void tc_wave_top2(uint64_t& k0, uint64_t& k1)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint64_t o0 = __shfl_xor(k0, d, 64), o1 = __shfl_xor(k1, d, 64);
-        const uint64_t l0 = k0 < o0 ? k0 : o0, h0 = k0 < o0 ? o0 : k0, s1 = k1 < o1 ? k1 : o1;
-        k0 = l0; k1 = h0 < s1 ? h0 : s1;
-    }
-}
-
 // Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel, bRight = cam) (src/Frame.cc:710-781) + the Observations() > 0 skip +
 // DescriptorDistance.  The level gate reads getKPtLevelMono(j) (:763), i.e. lgate (see the build).  Result: the two smallest keys
 // in every lane; *hit = the window was not empty (before the slot test).
@@ -1978,11 +1917,11 @@ __device__ void tc_search(const TcArgs& A, const TcLds& S, int cam, float qx, fl
             load_desc32(A.desc + (size_t)gi * A.stride, t0, t1, t2, t3);
             const int dist = __popcll(qd[0] ^ t0) + __popcll(qd[1] ^ t1) + __popcll(qd[2] ^ t2) + __popcll(qd[3] ^ t3);
             if (dist >= 256) continue;                                          // (never below bestDist = 256)
-            tc_top2(((uint64_t)dist << 44) | ((uint64_t)cell << 32) | ((uint64_t)(uint32_t)gi << 8) | (uint64_t)((S.lbest[gi] + 1) & 0xff), k0, k1);
+            top2_insert(((uint64_t)dist << 44) | ((uint64_t)cell << 32) | ((uint64_t)(uint32_t)gi << 8) | (uint64_t)((S.lbest[gi] + 1) & 0xff), k0, k1);
         }
     }
     hit = __ballot(any) != 0;
-    tc_wave_top2(k0, k1);
+    shfl_top2(k0, k1);
 }
 
 __device__ __forceinline__ int tc_dist(uint64_t k) { return k == ~0ull ? 256 : (int)(k >> 44); }
@@ -2183,49 +2122,38 @@ __global__ __launch_bounds__(256) void search_bow_fisheye_kernel(BowArgs A, int 
 {
     const int lane = threadIdx.x & 63;
     const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    for (int a = gw; a < A.kf_nn; a += nw) {
-        const uint32_t node = A.kf_nodes[a];
-        int lo = -1;
-        for (int base = 0; base < A.f_nn && lo < 0; base += 64) {
-            const int pos = base + lane;
-            const uint64_t hit = __ballot(pos < A.f_nn && A.f_nodes[pos] == node);
-            if (hit) lo = base + __ffsll((unsigned long long)hit) - 1;
-        }
+    for (int a = gw; a < A.kf_fv.nn; a += nw) {
+        const int lo = find_node(A.f_fv, A.kf_fv.nodes[a], lane);
         if (lo < 0) continue;
-        const int f0 = A.f_off[lo], f1 = A.f_off[lo + 1];
-        for (int iKF = A.kf_off[a]; iKF < A.kf_off[a + 1]; iKF++) {
-            const int realIdxKF = A.kf_idx[iKF];
+        const int f0 = A.f_fv.off[lo], f1 = A.f_fv.off[lo + 1];
+        for (int iKF = A.kf_fv.off[a]; iKF < A.kf_fv.off[a + 1]; iKF++) {
+            const int realIdxKF = A.kf_fv.idx[iKF];
             if (!A.kf_has_mp[realIdxKF]) continue;
             const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)realIdxKF * 32);
             const uint64_t q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3];
             uint64_t l0 = ~0ull, l1 = ~0ull, r0 = ~0ull, r1 = ~0ull;         // key = dist << 32 | iF (vector order breaks ties)
             for (int iF = f0 + lane; iF < f1; iF += 64) {
-                const int realIdxF = A.f_idx[iF];
+                const int realIdxF = A.f_fv.idx[iF];
                 if (__hip_atomic_load(&A.match_f[realIdxF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) continue;
                 const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)realIdxF * 32);
                 const int dist = __popcll(q0 ^ tp[0]) + __popcll(q1 ^ tp[1]) + __popcll(q2 ^ tp[2]) + __popcll(q3 ^ tp[3]);
                 if (dist >= 256) continue;
                 const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)iF;
-                if (realIdxF < nL) tc_top2(key, l0, l1); else tc_top2(key, r0, r1);
+                if (realIdxF < nL) top2_insert(key, l0, l1); else top2_insert(key, r0, r1);
             }
-            tc_wave_top2(l0, l1);
-            tc_wave_top2(r0, r1);
+            shfl_top2(l0, l1);
+            shfl_top2(r0, r1);
             const int bestDist1 = l0 == ~0ull ? 256 : (int)(l0 >> 32);
             if (bestDist1 > TH_LOW) continue;
             const int bestDist2 = l1 == ~0ull ? 256 : (int)(l1 >> 32);
             if (lane == 0) {
-                const float ka = A.kf_kps[realIdxKF].angle;
                 if ((float)bestDist1 < A.nnratio * (float)bestDist2) {
-                    const int bestIdxF = A.f_idx[(int)(l0 & 0xffffffffu)];
-                    __hip_atomic_store(&A.match_f[bestIdxF], realIdxKF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    atomicAdd(A.nmatches, 1);
-                    if (A.checkOri) { const int bin = rot_bin(ka, A.f_kps[bestIdxF].angle); A.bin_f[bestIdxF] = (int8_t)bin; atomicAdd(&A.histo[bin], 1); }
+                    const int bestIdxF = A.f_fv.idx[(int)(l0 & 0xffffffffu)];
+                    bow_commit<true>(A, realIdxKF, bestIdxF, bestIdxF);
                 }
                 if (r0 != ~0ull && (int)(r0 >> 32) <= TH_LOW) {                  // ratio "|| true" (:412)
-                    const int bestIdxFR = A.f_idx[(int)(r0 & 0xffffffffu)];
-                    __hip_atomic_store(&A.match_f[bestIdxFR], realIdxKF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    atomicAdd(A.nmatches, 1);
-                    if (A.checkOri) { const int bin = rot_bin(ka, A.f_kps[bestIdxFR].angle); A.bin_f[bestIdxFR] = (int8_t)bin; atomicAdd(&A.histo[bin], 1); }
+                    const int bestIdxFR = A.f_fv.idx[(int)(r0 & 0xffffffffu)];
+                    bow_commit<true>(A, realIdxKF, bestIdxFR, bestIdxFR);
                 }
             }
             __threadfence();          // the next KeyFrame feature of this node must see match_f
@@ -2233,20 +2161,14 @@ __global__ __launch_bounds__(256) void search_bow_fisheye_kernel(BowArgs A, int 
     }
 }
 
-int search_bow_fisheye_dev(eorb_ctx* c, const eorb_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
-                           const uint32_t* kf_nodes, const int32_t* kf_off, const int32_t* kf_idx, int kf_nn,
-                           const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc, const uint32_t* f_nodes, const int32_t* f_off,
-                           const int32_t* f_idx, int f_nn, int32_t* match_f, int8_t* bin_f, int32_t* histo, int32_t* nmatches,
-                           float nnratio, int checkOri)
+int search_bow_fisheye_dev(eorb_ctx* c, const BowArgs& A, int nL)
 {
-    BowArgs A{kf_kps, kf_desc, kf_has_mp, kf_nodes, kf_off, kf_idx, kf_nn, f_kps, n_f, f_desc, f_nodes, f_off, f_idx, f_nn,
-              match_f, bin_f, histo, nmatches, nnratio, checkOri, 0, nullptr, nullptr, 0};
     ProfScope ps(c, "search_bow_fisheye");
-    bow_init_kernel<<<(std::max(n_f, 32) + 255) / 256, 256, 0, c->stream>>>(match_f, bin_f, n_f, histo, nmatches, nullptr, 0);
-    if (kf_nn > 0 && f_nn > 0) {
-        const int blocks = std::min((kf_nn + 3) / 4, 1024);
+    bow_init_kernel<<<(std::max(A.n_f, 32) + 255) / 256, 256, 0, c->stream>>>(A.match_f, A.bin_f, A.n_f, A.histo, A.nmatches, nullptr, 0);
+    if (A.kf_fv.nn > 0 && A.f_fv.nn > 0) {
+        const int blocks = std::min((A.kf_fv.nn + 3) / 4, 1024);
         search_bow_fisheye_kernel<<<blocks, 256, 0, c->stream>>>(A, nL);
-        if (checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A);
+        if (A.checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A.match_f, A.bin_f, A.n_f, A.histo, A.nmatches);
     }
     EORB_LAUNCH_CHECK(c, "search_bow_fisheye kernels");
     return EORB_OK;

@@ -7,11 +7,22 @@ namespace eorb {
 
 struct GridB { float minX, minY, invW, invH; };
 
+// DBoW2::FeatureVector as CSR, device resident: node ids ascending, off[nn + 1], feature indices
+struct FeatVec { const uint32_t* nodes; const int32_t* off; const int32_t* idx; int nn; };
+
+// SearchByBoW (match.hip search_bow_kernel, search_bow_fisheye_kernel)
+struct BowArgs {
+    const eorb_keypoint* kf_kps; const uint8_t* kf_desc; const uint8_t* kf_has_mp; FeatVec kf_fv;
+    const eorb_keypoint* f_kps; int n_f; const uint8_t* f_desc; FeatVec f_fv;
+    int32_t* match_f; int8_t* bin_f; int32_t* histo; int32_t* nmatches;
+    float nnratio; int checkOri;
+    int kf_kf;                       // 1: SearchByBoW(KF, KF) (:833-973): output per idx1, vbMatched2 flags, strict TH_LOW
+    const uint8_t* f_has_mp; int32_t* match12; int n_kf;
+};
+
 struct TriArgs {
-    const eorb_keypoint* kps1; int n1; const uint8_t* desc1; int stride1; const uint8_t* elig1;
-    const uint32_t* nodes1; const int32_t* off1; const int32_t* idx1; int nn1;
-    const eorb_keypoint* kps2; int n2; const uint8_t* desc2; int stride2; const uint8_t* elig2;
-    const uint32_t* nodes2; const int32_t* off2; const int32_t* idx2; int nn2;
+    const eorb_keypoint* kps1; int n1; const uint8_t* desc1; int stride1; const uint8_t* elig1; FeatVec fv1;
+    const eorb_keypoint* kps2; int n2; const uint8_t* desc2; int stride2; const uint8_t* elig2; FeatVec fv2;
     float epx, epy; float F[9]; const float* scale2; const float* sigma2_2; int nlevels;
     int bCoarse, checkOri;
     int32_t* match12; int8_t* bin1; int32_t* histo; int32_t* nmatches;
@@ -27,6 +38,11 @@ struct TriKbArgs {
     float Rt[48];                                   // ll, lr, rl, rr: R12 row-major then t12 (monocular: Rt[0..11])
     const float* sigma2_1;
 };
+
+// launchers (match.hip); fisheye: the frame holds nL left features, then right ones; K: the KannalaBrandt8 walk (K->T is the block)
+int search_bow_dev(eorb_ctx* c, const BowArgs& A);
+int search_bow_fisheye_dev(eorb_ctx* c, const BowArgs& A, int nL);
+int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K = nullptr);
 
 struct RadArgs {
     const eorb_keypoint* kps; int n; const uint8_t* desc; int stride; GridB g;

@@ -747,6 +747,11 @@ def SearchByProjectionKFPose(Cur, view_, kf_kps, pos, min_dist, max_dist, mp_des
     return nm.value, cm, valid, uv, level
 
 
+def _fv(fv):
+    """a feature vector's CSR triple as contiguous (nodes uint32, node_off int32, idx int32)"""
+    return [np.ascontiguousarray(a, t) for a, t in zip(fv, (np.uint32, np.int32, np.int32))]
+
+
 def SearchByBoWFisheye(kf_kps, kf_desc, kf_has_mp, kf_fv, f_kps, nL, f_desc, f_fv, nnratio=0.7, checkOri=True, ctx=None):
     """The two-camera path of SearchByBoW(KeyFrame*, Frame&, ...) (src/ORBmatcher.cc:276-478): frame features = nL left, then right.
     Returns (nmatches, match_f)."""
@@ -754,8 +759,8 @@ def SearchByBoWFisheye(kf_kps, kf_desc, kf_has_mp, kf_fv, f_kps, nL, f_desc, f_f
     kf_kps = np.ascontiguousarray(kf_kps, KP_DTYPE); f_kps = np.ascontiguousarray(f_kps, KP_DTYPE)
     kf_desc = np.ascontiguousarray(kf_desc, np.uint8); f_desc = np.ascontiguousarray(f_desc, np.uint8)
     hm = np.ascontiguousarray(kf_has_mp, np.uint8)
-    kn, ko, ki = [np.ascontiguousarray(a, t) for a, t in zip(kf_fv, (np.uint32, np.int32, np.int32))]
-    fn, fo, fi = [np.ascontiguousarray(a, t) for a, t in zip(f_fv, (np.uint32, np.int32, np.int32))]
+    kn, ko, ki = _fv(kf_fv)
+    fn, fo, fi = _fv(f_fv)
     m = np.full(len(f_kps), -1, np.int32); nm = C.c_int(0)
     c.check(c.L.eorb_search_by_bow_fisheye(c.h, _p(kf_kps), len(kf_kps), _p(kf_desc), _p(hm), _p(kn), _p(ko), _p(ki), len(kn),
                                            _p(f_kps), len(f_kps), int(nL), _p(f_desc), _p(fn), _p(fo), _p(fi), len(fn), _p(m), float(nnratio),
@@ -770,8 +775,8 @@ def SearchByBoW(kf_kps, kf_desc, kf_has_mp, kf_fv, f_kps, f_desc, f_fv, nnratio=
     kf_kps = np.ascontiguousarray(kf_kps, KP_DTYPE); f_kps = np.ascontiguousarray(f_kps, KP_DTYPE)
     kf_desc = np.ascontiguousarray(kf_desc, np.uint8); f_desc = np.ascontiguousarray(f_desc, np.uint8)
     hm = np.ascontiguousarray(kf_has_mp, np.uint8)
-    kn, ko, ki = [np.ascontiguousarray(a, t) for a, t in zip(kf_fv, (np.uint32, np.int32, np.int32))]
-    fn, fo, fi = [np.ascontiguousarray(a, t) for a, t in zip(f_fv, (np.uint32, np.int32, np.int32))]
+    kn, ko, ki = _fv(kf_fv)
+    fn, fo, fi = _fv(f_fv)
     m = np.full(len(f_kps), -1, np.int32); nm = C.c_int(0)
     c.check(c.L.eorb_search_by_bow(c.h, _p(kf_kps), len(kf_kps), _p(kf_desc), _p(hm), _p(kn), _p(ko), _p(ki), len(kn),
                                    _p(f_kps), len(f_kps), _p(f_desc), _p(fn), _p(fo), _p(fi), len(fn), _p(m), float(nnratio),
@@ -785,8 +790,8 @@ def SearchByBoW_KF(kps1, desc1, has_mp1, fv1, kps2, desc2, has_mp2, fv2, nnratio
     kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
     desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
     h1 = np.ascontiguousarray(has_mp1, np.uint8); h2 = np.ascontiguousarray(has_mp2, np.uint8)
-    n1, o1, i1 = [np.ascontiguousarray(a, t) for a, t in zip(fv1, (np.uint32, np.int32, np.int32))]
-    n2, o2, i2 = [np.ascontiguousarray(a, t) for a, t in zip(fv2, (np.uint32, np.int32, np.int32))]
+    n1, o1, i1 = _fv(fv1)
+    n2, o2, i2 = _fv(fv2)
     m = np.full(len(kps1), -1, np.int32); nm = C.c_int(0)
     c.check(c.L.eorb_search_by_bow_kf(c.h, _p(kps1), len(kps1), _p(desc1), _p(h1), _p(n1), _p(o1), _p(i1), len(n1),
                                       _p(kps2), len(kps2), _p(desc2), _p(h2), _p(n2), _p(o2), _p(i2), len(n2), _p(m),
@@ -801,8 +806,8 @@ def SearchForTriangulation(kps1, desc1, elig1, fv1, kps2, desc2, elig2, fv2, ep,
     kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
     desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
     e1 = np.ascontiguousarray(elig1, np.uint8); e2 = np.ascontiguousarray(elig2, np.uint8)
-    n1, o1, i1 = [np.ascontiguousarray(a, t) for a, t in zip(fv1, (np.uint32, np.int32, np.int32))]
-    n2, o2, i2 = [np.ascontiguousarray(a, t) for a, t in zip(fv2, (np.uint32, np.int32, np.int32))]
+    n1, o1, i1 = _fv(fv1)
+    n2, o2, i2 = _fv(fv2)
     ep = np.ascontiguousarray(ep, np.float32); F = np.ascontiguousarray(F12, np.float32).reshape(9)
     sc = np.ascontiguousarray(scale2, np.float32); sg = np.ascontiguousarray(sigma2_2, np.float32)
     m = np.full(len(kps1), -1, np.int32); nm = C.c_int(0)
@@ -833,8 +838,8 @@ def SearchForTriangulationKB8(kps1, nleft1, desc1, elig1, fv1, kps2, nleft2, des
     kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
     desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
     e1 = np.ascontiguousarray(elig1, np.uint8); e2 = np.ascontiguousarray(elig2, np.uint8)
-    n1, o1, i1 = [np.ascontiguousarray(a, t) for a, t in zip(fv1, (np.uint32, np.int32, np.int32))]
-    n2, o2, i2 = [np.ascontiguousarray(a, t) for a, t in zip(fv2, (np.uint32, np.int32, np.int32))]
+    n1, o1, i1 = _fv(fv1)
+    n2, o2, i2 = _fv(fv2)
     rt = np.zeros(48, np.float32)
     r = np.asarray(Rt, np.float32).reshape(-1)
     rt[:len(r)] = r

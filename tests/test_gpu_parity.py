@@ -634,14 +634,19 @@ def test_tracked_descriptors_and_level_assignment(oracle, fe):
 
 def _feature_vector(nfeat, nnodes, rng):
     """A DBoW2::FeatureVector stand-in: every feature falls into exactly one node (node ids ascending)."""
-    node_of = rng.integers(0, nnodes, nfeat)
-    ids = np.unique(node_of)
-    off = [0]; idx = []
-    for nid in ids:
-        members = np.nonzero(node_of == nid)[0]
-        rng.shuffle(members)                       # vector order inside a node is the insertion order, not sorted
-        idx.extend(members.tolist()); off.append(len(idx))
-    return (ids.astype(np.uint32) * 7 + 3), np.array(off, np.int32), np.array(idx, np.int32)
+    return synth.feature_vector_of(rng.integers(0, nnodes, nfeat) * 7 + 3, rng)
+
+
+def _correlated_fvs(k1, k2, shift, nn, rng):
+    """Feature vectors in which spatially matching features mostly share a vocabulary node."""
+    fv1 = _feature_vector(len(k1), nn, rng)
+    node1 = np.zeros(len(k1), np.int64)
+    for a in range(len(fv1[0])):
+        node1[fv1[2][fv1[1][a]:fv1[1][a + 1]]] = fv1[0][a]
+    dx = k2["x"][:, None] - (k1["x"][None, :] - shift); dy = k2["y"][:, None] - (k1["y"][None, :] + shift)
+    near = np.argmin(dx * dx + dy * dy, axis=1)
+    node2 = np.where(rng.uniform(size=len(k2)) < 0.85, node1[near], rng.integers(0, nn, len(k2)) * 7 + 3)
+    return fv1, synth.feature_vector_of(node2, rng)
 
 
 @pytest.mark.parametrize("ori", [True, False])
@@ -649,19 +654,7 @@ def test_search_by_bow(oracle, fe, ctx, ori):
     k1, d1, k2, d2 = _two_frames(oracle, seed=41, shift=2)
     rng = np.random.default_rng(11)
     # correlated node assignment: matching features mostly share a node, as a vocabulary tree would give
-    nn = 60
-    kfv = _feature_vector(len(k1), nn, rng)
-    # frame features inherit the node of their spatially nearest KeyFrame feature most of the time
-    node_kf = np.zeros(len(k1), np.int64)
-    for a in range(len(kfv[0])):
-        node_kf[kfv[2][kfv[1][a]:kfv[1][a + 1]]] = kfv[0][a]
-    dx = k2["x"][:, None] - (k1["x"][None, :] - 2); dy = k2["y"][:, None] - (k1["y"][None, :] + 2)
-    near = np.argmin(dx * dx + dy * dy, axis=1)
-    node_f = np.where(rng.uniform(size=len(k2)) < 0.85, node_kf[near], rng.integers(0, nn, len(k2)) * 7 + 3)
-    ids = np.unique(node_f); off = [0]; idx = []
-    for nid in ids:
-        m = np.nonzero(node_f == nid)[0]; rng.shuffle(m); idx.extend(m.tolist()); off.append(len(idx))
-    ffv = (ids.astype(np.uint32), np.array(off, np.int32), np.array(idx, np.int32))
+    kfv, ffv = _correlated_fvs(k1, k2, 2, 60, rng)
     has_mp = (rng.uniform(size=len(k1)) < 0.8).astype(np.uint8)
     for ratio in (0.7, 0.95):
         on, om = oracle.search_by_bow(k1, d1, has_mp, kfv, k2, d2, ffv, ratio, ori)
@@ -675,18 +668,7 @@ def test_search_by_bow_keyframes(oracle, fe, ctx, ori):
     """f3: ORBmatcher::SearchByBoW(KF, KF) (:833-973): strict TH_LOW, vbMatched2, output per idx1."""
     k1, d1, k2, d2 = _two_frames(oracle, seed=43, shift=3)
     rng = np.random.default_rng(12)
-    nn = 50
-    fv1 = _feature_vector(len(k1), nn, rng)
-    node1 = np.zeros(len(k1), np.int64)
-    for a in range(len(fv1[0])):
-        node1[fv1[2][fv1[1][a]:fv1[1][a + 1]]] = fv1[0][a]
-    dx = k2["x"][:, None] - (k1["x"][None, :] - 3); dy = k2["y"][:, None] - (k1["y"][None, :] + 3)
-    near = np.argmin(dx * dx + dy * dy, axis=1)
-    node2 = np.where(rng.uniform(size=len(k2)) < 0.85, node1[near], rng.integers(0, nn, len(k2)) * 7 + 3)
-    ids = np.unique(node2); off = [0]; idx = []
-    for nid in ids:
-        m = np.nonzero(node2 == nid)[0]; rng.shuffle(m); idx.extend(m.tolist()); off.append(len(idx))
-    fv2 = (ids.astype(np.uint32), np.array(off, np.int32), np.array(idx, np.int32))
+    fv1, fv2 = _correlated_fvs(k1, k2, 3, 50, rng)
     h1 = (rng.uniform(size=len(k1)) < 0.8).astype(np.uint8)
     h2 = (rng.uniform(size=len(k2)) < 0.8).astype(np.uint8)
     for ratio in (0.7, 0.95):
@@ -701,19 +683,52 @@ def test_search_by_bow_keyframes(oracle, fe, ctx, ori):
     assert gn == 0 and np.all(gm == -1)
 
 
-def _correlated_fvs(k1, k2, shift, nn, rng):
-    """Feature vectors in which spatially matching features mostly share a vocabulary node."""
-    fv1 = _feature_vector(len(k1), nn, rng)
-    node1 = np.zeros(len(k1), np.int64)
-    for a in range(len(fv1[0])):
-        node1[fv1[2][fv1[1][a]:fv1[1][a + 1]]] = fv1[0][a]
-    dx = k2["x"][:, None] - (k1["x"][None, :] - shift); dy = k2["y"][:, None] - (k1["y"][None, :] + shift)
-    near = np.argmin(dx * dx + dy * dy, axis=1)
-    node2 = np.where(rng.uniform(size=len(k2)) < 0.85, node1[near], rng.integers(0, nn, len(k2)) * 7 + 3)
-    ids = np.unique(node2); off = [0]; idx = []
-    for nid in ids:
-        m = np.nonzero(node2 == nid)[0]; rng.shuffle(m); idx.extend(m.tolist()); off.append(len(idx))
-    return fv1, (ids.astype(np.uint32), np.array(off, np.int32), np.array(idx, np.int32))
+def _cap_nodes(fv, caps, x):
+    """fv with node a cut to its caps[a] leftmost features (None: all), vector order kept; the rest appear in no node, which is
+    legal input.  Cutting both frames by image position keeps most of a node's true pairs on both sides."""
+    nodes, off, idx = fv
+    keep = []
+    for a in range(len(nodes)):
+        m = idx[off[a]:off[a + 1]]
+        keep.append(m if caps[a] is None else m[np.sort(np.argsort(x[m], kind="stable")[:caps[a]])])
+    return nodes, np.cumsum([0] + [len(k) for k in keep]).astype(np.int32), np.concatenate(keep).astype(np.int32)
+
+
+def _node_of(fv, n):
+    node = np.full(n, -1, np.int64)
+    for a in range(len(fv[0])):
+        node[fv[2][fv[1][a]:fv[1][a + 1]]] = a
+    return node
+
+
+@pytest.mark.parametrize("ori", [True, False])
+def test_search_by_bow_node_sizes(oracle, fe, ctx, ori):
+    """Both paths of search_bow_kernel: a node with at most 64 features on either side is matched in registers, any other one
+    through match_f in global memory.  Seven nodes, capped (KeyFrame side, frame side) to sit on both sides of that limit."""
+    k1, d1, k2, d2 = _two_frames(oracle, seed=41, shift=2)
+    rng = np.random.default_rng(5)
+    fv1, fv2 = _correlated_fvs(k1, k2, 2, 7, rng)
+    assert len(fv1[0]) == 7 and np.array_equal(fv1[0], fv2[0])
+    caps = [(None, None), (None, 40), (40, None), (30, 30), (64, 64), (65, 30), (30, 65)]
+    sizes = [(int(np.diff(fv1[1])[a]), int(np.diff(fv2[1])[a])) for a in range(7)]
+    assert all(s1 > 65 and s2 > 65 for s1, s2 in sizes), sizes          # every cap bites and "all" is past the limit
+    fv1 = _cap_nodes(fv1, [c[0] for c in caps], k1["x"] - 2); fv2 = _cap_nodes(fv2, [c[1] for c in caps], k2["x"])
+    h1 = (rng.uniform(size=len(k1)) < 0.8).astype(np.uint8)
+    h2 = (rng.uniform(size=len(k2)) < 0.8).astype(np.uint8)
+    node1, node2 = _node_of(fv1, len(k1)), _node_of(fv2, len(k2))
+    for ratio in (0.7, 0.95):
+        on, om = oracle.search_by_bow(k1, d1, h1, fv1, k2, d2, fv2, ratio, ori)
+        per_node = np.bincount(node2[om >= 0], minlength=7)
+        print("KF,F ratio", ratio, "ori", ori, "per node", per_node.tolist(), "total", on)
+        assert per_node.min() >= 5, per_node
+        gn, gm = fe.SearchByBoW(k1, d1, h1, fv1, k2, d2, fv2, ratio, ori, ctx=ctx)
+        assert on == gn and np.array_equal(om, gm)
+        on, om = oracle.search_by_bow_kf(k1, d1, h1, fv1, k2, d2, h2, fv2, ratio, ori)
+        per_node = np.bincount(node1[om >= 0], minlength=7)
+        print("KF,KF ratio", ratio, "ori", ori, "per node", per_node.tolist(), "total", on)
+        assert per_node.min() >= 5, per_node
+        gn, gm = fe.SearchByBoW_KF(k1, d1, h1, fv1, k2, d2, h2, fv2, ratio, ori, ctx=ctx)
+        assert on == gn and np.array_equal(om, gm)
 
 
 @pytest.mark.parametrize("ori,coarse", [(True, False), (False, False), (True, True)])
