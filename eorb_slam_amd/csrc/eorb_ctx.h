@@ -145,7 +145,7 @@ struct eorb_ctx {
     eorb::DevBuf win_ws;                 // candidate lists of the two-phase window matchers
     eorb::DevBuf win_total;              // their per-pair entry counters: zero between calls (phase 2 puts its pair's back), win_total_n of them known to be
     size_t win_total_n = 0;
-    unsigned win_attr_done = 0;          // bit KIND: the window matchers' kernels of that kind have their LDS opt-in on this context's device
+    unsigned lds_optin = 0;              // bit per matcher kernel whose dynamic-LDS opt-in was made on this context's device (match.hip lds_optin)
     eorb::DevBuf arena;                  // host-buffer entry points: all inputs / outputs of one call, one H2D and one D2H copy
     void* dl_pinned = nullptr; size_t dl_cap = 0;      // pinned landing buffer of the D2H copy (the call synchronises before reading it)
     hipEvent_t dl_event = nullptr;                     // recorded behind that copy: what the call waits for
@@ -224,6 +224,20 @@ int ev_direct_slices_dev(eorb_ctx* c, const void* d_events, int raw, const int64
 int ev_undistort_dev(eorb_ctx* c, const eorb_raw_event* d_raw, size_t n, int W, int H, double tsFactor, eorb_event* d_out, uint32_t* d_blk);
 int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, uint64_t* d_lineend, eorb_raw_event* d_ev, uint8_t* d_status,
                       eorb_raw_event* d_out, uint32_t* d_blk, size_t max_lines, uint32_t h_res[3]);
+int ev_decode_minmax(eorb_ctx* c, const uint32_t* d_enc, float* d_out, int B);
+int ev_divcheck(eorb_ctx* c, float lo, float hi, float sigma, unsigned long long* bad_out);
+int ev_diag_read(unsigned long long* out16);
+int ev_trace_read(unsigned long long* out, int n);
+int ev_warp_se3_dev(eorb_ctx* c, const eorb_event16* d_in, eorb_event16* d_out, int n, const eorb_camera* cam, double angle,
+                    const double axis[3], const double tt[3], float medDepth, const float* d_depth);
+int ev_warp_se2_dev(eorb_ctx* c, const eorb_event16* d_in, eorb_event16* d_out, int n, const eorb_camera* cam, const float* params, int nparams);
+int ev_focus_dev(eorb_ctx* c, const float* d_img, int nimg, int W, int H, float* d_out);
+int ev_cvnormalize_dev(eorb_ctx* c, const float* d_img, int npix, uint32_t* d_mm, uint8_t* d_out);
+int ev_mathhash(eorb_ctx* c, int which, uint32_t lo_bits, uint32_t hi_bits, unsigned long long* out);
+int ev_cvnormalize_n_dev(eorb_ctx* c, const float* d_imgs, int nimg, int npix, uint32_t* d_mm, uint8_t* d_outs);
+int ev_contest_select_dev(eorb_ctx* c, const float* d_focus_img, const int img_of[4], int half_img, const uint8_t* d_u8s, int npix,
+                          float* d_focus_out, int* d_winner, uint8_t* d_out);
+int ev_kp_points_dev(eorb_ctx* c, const eorb_keypoint* d_kps, const int32_t* d_n, int cap, float* d_pts);
 // ev_slots.hip
 int ev_slots_prepare_launch(eorb_ctx* c, int W, int H, int h, int TX, int TY);
 int ev_slots_prepare(eorb_ctx* c, int W, int H, int h, int TX, int TY, const float* d_stamps /* nullptr: taps from c->lut */, int stamp_stride, int SWP,
@@ -246,18 +260,16 @@ int stereo_match_dev(eorb_ctx* c, const eorb_keypoint* d_kps, const uint8_t* d_d
 int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t img_slice_bytes, int B, int lap0, int lap1,
                     int want_desc, eorb_keypoint* d_kps, uint8_t* d_desc, uint8_t* d_oob, int32_t* d_n, int32_t* d_mono,
                     int32_t* d_flag_out = nullptr);      // d_flag_out: receives the overflow flag of this extraction (host entry point)
+int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H);
+int orb_err_flag(eorb_ctx* c, int B, int* flag);
+int orb_err_flag_to(eorb_ctx* c, int B, int32_t* d_dst);
+int orb_pyramid_blur_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride);
+int orb_tracked_dev(eorb_ctx* c, eorb_keypoint* d_kps, int n, int mode, const uint8_t* d_ref, uint8_t* d_desc, uint8_t* d_oob);
 int orb_debug_stage(eorb_ctx* c, const char* name, int slice, int level, void* out, size_t cap_bytes, int* dim0, int* dim1);
 // calib.hip
 int calib_points_dev(eorb_ctx* c, const CalibDev& P, const float* d_in, float* d_out, int n, int rec_floats);
 int calib_frame_dev(eorb_ctx* c, const eorb_keypoint* d_kps, const int32_t* d_n, int cap, eorb_keypoint* d_un, float* d_bounds, int W, int H);
 int calib_maps_dev(eorb_ctx* c, int LW, int LH, float* d_lut, float* d_mx, float* d_my);
-// match.hip
-int search_init_dev(eorb_ctx* c, int npairs,
-                    const eorb_keypoint* kps1, const int32_t* n1, size_t kp1_stride, const uint8_t* desc1, int dstride1, size_t desc1_slice,
-                    const uint8_t* is_orb1,
-                    const eorb_keypoint* kps2, const int32_t* n2, size_t kp2_stride, const uint8_t* desc2, int dstride2, size_t desc2_slice,
-                    const uint8_t* is_orb2, int cap1, int cap2,
-                    eorb_grid_bounds gb, float* prev_matched, int32_t* matches12, int windowSize, float nnratio,
-                    int checkOri, int32_t* nmatches);
+// match.hip: match_args.h
 
 }  // namespace eorb

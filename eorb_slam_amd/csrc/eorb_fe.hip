@@ -11,52 +11,6 @@
 
 namespace eorb {
 
-int ev_decode_minmax(eorb_ctx* c, const uint32_t* d_enc, float* d_out, int B);
-int ev_divcheck(eorb_ctx* c, float lo, float hi, float sigma, unsigned long long* bad_out);
-int ev_diag_read(unsigned long long* out16);
-int ev_trace_read(unsigned long long* out, int n);
-int ev_warp_se3_dev(eorb_ctx* c, const eorb_event16* d_in, eorb_event16* d_out, int n, const eorb_camera* cam, double angle,
-                    const double axis[3], const double tt[3], float medDepth, const float* d_depth);
-int ev_warp_se2_dev(eorb_ctx* c, const eorb_event16* d_in, eorb_event16* d_out, int n, const eorb_camera* cam, const float* params, int nparams);
-int ev_focus_dev(eorb_ctx* c, const float* d_img, int nimg, int W, int H, float* d_out);
-int ev_cvnormalize_dev(eorb_ctx* c, const float* d_img, int npix, uint32_t* d_mm, uint8_t* d_out);
-int ev_mathhash(eorb_ctx* c, int which, uint32_t lo_bits, uint32_t hi_bits, unsigned long long* out);
-int ev_cvnormalize_n_dev(eorb_ctx* c, const float* d_imgs, int nimg, int npix, uint32_t* d_mm, uint8_t* d_outs);
-int ev_contest_select_dev(eorb_ctx* c, const float* d_focus_img, const int img_of[4], int half_img, const uint8_t* d_u8s, int npix,
-                          float* d_focus_out, int* d_winner, uint8_t* d_out);
-int ev_kp_points_dev(eorb_ctx* c, const eorb_keypoint* d_kps, const int32_t* d_n, int cap, float* d_pts);
-int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H);
-int orb_err_flag(eorb_ctx* c, int B, int* flag);
-int orb_err_flag_to(eorb_ctx* c, int B, int32_t* d_dst);
-int bf_knn2_dev(eorb_ctx* c, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int32_t* d_idx2, int32_t* d_dist2);
-int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR, int cap, int32_t* d_lap, int32_t* d_idx2,
-                     int32_t* d_kdist2, int32_t* d_cand, int32_t* d_dist2);
-int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A);
-constexpr int kTcMaxKpsHost = 8192;             // = kTcMaxKps (match.hip): nL + nR of a two-camera matcher
-int search_proj_last_dev(eorb_ctx* c, const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride,
-                         const uint8_t* cur_is_orb, const eorb_keypoint* last_kps, int n_last, const uint8_t* last_is_orb,
-                         const uint8_t* valid, const float* uv, const uint8_t* mp_desc, const uint8_t* mp_obs,
-                         int dist_th, eorb_grid_bounds gb, int32_t* cur_mp, float th, int mode, int checkOri,
-                         int32_t* nmatches, const float* cur_uright = nullptr, const float* q_ur = nullptr);
-int search_proj_map_dev(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const uint8_t* is_orb,
-                        int M, const uint8_t* in_view, const float4* mp_f4 /* projX, projY, viewCos, levelScale */,
-                        const int32_t* level, const uint8_t* mp_desc, const uint8_t* mp_obs, const uint8_t* mp_is_orb,
-                        eorb_grid_bounds gb, int32_t* frame_mp, float th, float nnratio, int32_t* nmatches,
-                        const float* uright = nullptr, const float* q_ur = nullptr);
-
-int orb_pyramid_blur_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride);
-int orb_tracked_dev(eorb_ctx* c, eorb_keypoint* d_kps, int n, int mode, const uint8_t* d_ref, uint8_t* d_desc, uint8_t* d_oob);
-int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const eorb_keypoint* kps1,
-                      const eorb_keypoint* kps2, int n, const float* sig1, const float* sig2, float* out);
-int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell);
-int bow_transform_dev(eorb_ctx* c, const uint8_t* d_desc, int n, int stride, const BowVoc& V, int levelsup, int weighting, int norm,
-                      uint32_t* d_word_of, double* d_w_of, uint32_t* d_node_of, uint32_t* d_bow_word, double* d_bow_val,
-                      uint32_t* d_fv_node, int32_t* d_fv_off, int32_t* d_fv_idx, int32_t* d_counts);
-int window_match_dev(eorb_ctx* c, const uint8_t* d_q, int nq, int q_stride, const uint8_t* d_t, int t_stride, const int32_t* d_off,
-                     const int32_t* d_cand, int32_t* d_out);
-int distinctive_dev(eorb_ctx* c, const uint8_t* d_desc, const int32_t* d_offsets, int M, int32_t* d_best);
-int sort_response_dev(eorb_ctx* c, const eorb_keypoint* d_kps, int n, int32_t* d_perm);
-
 int set_err(eorb_ctx* c, int code, const char* fmt, ...)
 {
     char buf[512];
@@ -1478,12 +1432,89 @@ int eorb_search_for_initialization(eorb_ctx* c,
     return EORB_OK;
 }
 
+// ---- marshalling shared by the projection matchers: "queue into the arena, then (after A.upload()) the device view" ---------------
+// a mono searched frame
+struct FrameOff { size_t k, d, o, ur; int n, stride; bool has_o, has_ur; };
+static FrameOff frame_in(Arena& A, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const uint8_t* is_orb, const float* uright)
+{
+    return FrameOff{A.in(kps, sizeof(eorb_keypoint) * (size_t)n), A.in(desc, (size_t)stride * n), A.in(is_orb, is_orb ? n : 0),
+                    A.in(uright, uright ? sizeof(float) * (size_t)n : 0), n, stride, is_orb != nullptr, uright != nullptr};
+}
+static FrameDev frame_dev(const Arena& A, const FrameOff& o)
+{
+    return FrameDev{A.dev<eorb_keypoint>(o.k), o.n, A.dev<uint8_t>(o.d), o.stride, o.has_o ? A.dev<uint8_t>(o.o) : nullptr, o.has_ur ? A.dev<float>(o.ur) : nullptr};
+}
+
+// the result region {nmatches, n_in_view | slots (in/out)}: the head of a call's contiguous outputs.  reloc: relocalisation
+// (SearchByProjection(CurrentFrame, pKF, sAlreadyFound)) -- every occupied slot is skipped (:2255-2256), only new matches are written back
+struct ResultOff { size_t nm, slots, end; std::vector<int32_t> masked; };
+static ResultOff result_in(Arena& A, const int32_t* slots, int n, bool reloc = false)
+{
+    ResultOff o;
+    if (reloc) { o.masked.assign(slots, slots + n); for (int32_t& s : o.masked) if (s != -1) s = -2; }
+    o.nm = A.in(nullptr, 16); o.slots = A.in(reloc ? o.masked.data() : slots, sizeof(int32_t) * (size_t)n); o.end = o.slots + sizeof(int32_t) * (size_t)n;
+    return o;
+}
+// the call's one download, arena[o.nm, end): the counts and the slots; host: for what the caller copies out of the rest
+static int result_out(Arena& A, const ResultOff& o, size_t end, int32_t* slots, int* nmatches, int* n_in_view = nullptr, const char** host = nullptr)
+{
+    const char* h;
+    const int rc = A.download(o.nm, end - o.nm, &h);
+    if (rc) return rc;
+    const int32_t* cnt = (const int32_t*)(h + o.nm); const int32_t* got = (const int32_t*)(h + o.slots);
+    if (o.masked.empty()) memcpy(slots, got, o.end - o.slots);
+    else for (size_t i = 0; i < o.masked.size(); i++) if (got[i] >= 0) slots[i] = got[i];
+    if (nmatches) *nmatches = cnt[0];
+    if (n_in_view) *n_in_view = cnt[1];
+    if (host) *host = h;
+    return EORB_OK;
+}
+// a fused call on an empty frame: the projection ran, no matcher did
+static int result_no_matches(eorb_ctx* c, const Arena& A, const ResultOff& o) { EORB_HIP(c, hipMemsetAsync(A.dev<int32_t>(o.nm), 0, sizeof(int32_t), c->stream)); return EORB_OK; }
+
+// a two-camera searched frame (nL left keypoints, then nR right ones) with its stereo links (NULL: the matcher takes none).  The
+// checks: sizes, octaves (the kernel keeps levels in 8 bits), slot states (-3 .. nq - 1), the links' ranges
+struct TcFrameOff { size_t k, d, l2r, r2l; int nL, nR, stride; bool links; };
+static int twocam_frame_in(eorb_ctx* c, Arena& A, const char* who, const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
+                           const int32_t* slots, int nq, const int32_t* l2r, const int32_t* r2l, TcFrameOff& o)
+{
+    const int nT = nL + nR;
+    if (nL < 0 || nR < 0 || nq < 0 || stride < 32 || !slots || (nT > 0 && (!kps || !desc))) return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
+    if (nT > kTcMaxKps) return set_err(c, EORB_E_CAPACITY, "%s: %d keypoints > %d", who, nT, kTcMaxKps);
+    if (nq >= (1 << 24)) return set_err(c, EORB_E_CAPACITY, "%s: %d queries >= 2^24", who, nq);
+    for (int i = 0; i < nT; i++) {
+        if (kps[i].octave < 0 || kps[i].octave > 127) return set_err(c, EORB_E_ARG, "%s: keypoint %d has octave %d outside [0, 127]", who, i, kps[i].octave);
+        if (slots[i] < -3 || slots[i] >= nq) return set_err(c, EORB_E_ARG, "%s: slot %d holds %d", who, i, slots[i]);
+    }
+    for (int i = 0; l2r && i < nL; i++) if (l2r[i] < -1 || l2r[i] >= nR) return set_err(c, EORB_E_ARG, "%s: l2r[%d] = %d", who, i, l2r[i]);
+    for (int i = 0; r2l && i < nR; i++) if (r2l[i] < -1 || r2l[i] >= nL) return set_err(c, EORB_E_ARG, "%s: r2l[%d] = %d", who, i, r2l[i]);
+    o.k = A.in(kps, sizeof(eorb_keypoint) * (size_t)nT); o.d = A.in(desc, (size_t)stride * nT);
+    o.l2r = A.in(l2r, l2r ? sizeof(int32_t) * (size_t)nL : 0); o.r2l = A.in(r2l, r2l ? sizeof(int32_t) * (size_t)nR : 0);
+    o.nL = nL; o.nR = nR; o.stride = stride; o.links = l2r || r2l;
+    return EORB_OK;
+}
+// the block of the two-camera walk.  Q (KIND 0): the map points' records of the left and the right camera; KIND 1 adds its own fields
+struct CamQuery { const uint8_t* search; const float4* rec; const int32_t* level; };      // searched or not | projX, projY, viewCos, levelScale | predicted level
+static TcArgs twocam_args(const Arena& A, const TcFrameOff& f, const eorb_grid_bounds* gb, int nq, size_t o_md, size_t o_ob, float th, const ResultOff& r,
+                          const CamQuery* Q = nullptr, float nnratio = 0.f)
+{
+    TcArgs T{};
+    T.kps = A.dev<eorb_keypoint>(f.k); T.nL = f.nL; T.nR = f.nR; T.desc = A.dev<uint8_t>(f.d); T.stride = f.stride; T.g = grid_b(*gb);
+    T.nq = nq; T.mp_desc = A.dev<uint8_t>(o_md); T.mp_obs = A.dev<uint8_t>(o_ob); T.th = th; T.nnratio = nnratio;
+    if (f.links) { T.l2r = A.dev<int32_t>(f.l2r); T.r2l = A.dev<int32_t>(f.r2l); }
+    if (Q) { T.in_view = Q[0].search; T.qf = Q[0].rec; T.qlevel = Q[0].level; T.in_view_r = Q[1].search; T.qf_r = Q[1].rec; T.qlevel_r = Q[1].level; }
+    T.slots = A.dev<int32_t>(r.slots); T.nmatches = A.dev<int32_t>(r.nm);
+    return T;
+}
+
+// ---- matchers, projections given by the caller -----------------------------------------------------------------------------------
+// reloc: the slot semantics of eorb_search_by_projection_kf (result_in)
 static int proj_last_common(eorb_ctx* c,
         const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride, const uint8_t* cur_is_orb,
         const eorb_keypoint* last_kps, int n_last, const uint8_t* last_is_orb,
         const uint8_t* valid, const float* uv, const uint8_t* mp_desc, const uint8_t* mp_obs,
         const float* level_scale, const eorb_grid_bounds* gb, int32_t* cur_mp, float th, int mode, int checkOri,
-        int dist_th, int* nmatches, const float* cur_uright = nullptr, const float* q_ur = nullptr)
+        int dist_th, int* nmatches, const float* cur_uright = nullptr, const float* q_ur = nullptr, bool reloc = false)
 {
     if (!c) return EORB_E_ARG;
     if (n_cur < 0 || n_last < 0 || !gb || !cur_mp || cur_stride < 32 || !level_scale || ((cur_uright != nullptr) != (q_ur != nullptr)))
@@ -1493,29 +1524,21 @@ static int proj_last_common(eorb_ctx* c,
     if (n_last == 0 || n_cur == 0) return EORB_OK;
     int rc;
     Arena A(c);
-    const size_t o_ck = A.in(cur_kps, sizeof(eorb_keypoint) * (size_t)n_cur), o_cd = A.in(cur_desc, (size_t)cur_stride * n_cur);
+    const FrameOff fr = frame_in(A, cur_kps, n_cur, cur_desc, cur_stride, cur_is_orb, cur_uright);
     const size_t o_lk = A.in(last_kps, sizeof(eorb_keypoint) * (size_t)n_last), o_md = A.in(mp_desc, 32 * (size_t)n_last);
-    const size_t o_co = A.in(cur_is_orb, cur_is_orb ? n_cur : 0), o_lo = A.in(last_is_orb, last_is_orb ? n_last : 0);
+    const size_t o_lo = A.in(last_is_orb, last_is_orb ? n_last : 0);
     std::vector<float> f3(3 * (size_t)n_last);
     for (int i = 0; i < n_last; i++) { f3[3 * i] = uv[2 * i]; f3[3 * i + 1] = uv[2 * i + 1]; f3[3 * i + 2] = level_scale[i]; }
     const size_t o_f3 = A.in(f3.data(), sizeof(float) * f3.size());
     const size_t o_va = A.in(valid, n_last), o_ob = A.in(mp_obs, n_last);
-    const size_t o_ur2 = A.in(cur_uright, cur_uright ? sizeof(float) * (size_t)n_cur : 0), o_qur = A.in(q_ur, q_ur ? sizeof(float) * (size_t)n_last : 0);
-    // outputs, contiguous: nmatches | slots (in/out)
-    const size_t o_nm = A.in(nullptr, 16);
-    const size_t o_mp = A.in(cur_mp, sizeof(int32_t) * (size_t)n_cur);
+    const size_t o_qur = A.in(q_ur, q_ur ? sizeof(float) * (size_t)n_last : 0);
+    const ResultOff r = result_in(A, cur_mp, n_cur, reloc);
     if ((rc = A.upload())) return rc;
-    rc = search_proj_last_dev(c, A.dev<eorb_keypoint>(o_ck), n_cur, A.dev<uint8_t>(o_cd), cur_stride,
-                              cur_is_orb ? A.dev<uint8_t>(o_co) : nullptr, A.dev<eorb_keypoint>(o_lk), n_last,
-                              last_is_orb ? A.dev<uint8_t>(o_lo) : nullptr, A.dev<uint8_t>(o_va), A.dev<float>(o_f3),
-                              A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob), dist_th, *gb, A.dev<int32_t>(o_mp), th,
-                              mode, checkOri, A.dev<int32_t>(o_nm), cur_uright ? A.dev<float>(o_ur2) : nullptr, q_ur ? A.dev<float>(o_qur) : nullptr);
-    if (rc) return rc;
-    const char* h;
-    if ((rc = A.download(o_nm, o_mp + sizeof(int32_t) * (size_t)n_cur - o_nm, &h))) return rc;
-    memcpy(cur_mp, h + o_mp, sizeof(int32_t) * (size_t)n_cur);
-    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
-    return EORB_OK;
+    const ProjLastArgs P{frame_dev(A, fr), grid_b(*gb), A.dev<eorb_keypoint>(o_lk), n_last, last_is_orb ? A.dev<uint8_t>(o_lo) : nullptr,
+                         A.dev<uint8_t>(o_va), A.dev<float>(o_f3), A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob),
+                         q_ur ? A.dev<float>(o_qur) : nullptr, th, mode, checkOri, dist_th, A.dev<int32_t>(r.slots), A.dev<int32_t>(r.nm)};
+    if ((rc = search_proj_last_dev(c, P))) return rc;
+    return result_out(A, r, r.end, cur_mp, nmatches);
 }
 
 int eorb_search_by_projection_last(eorb_ctx* c,
@@ -1553,14 +1576,9 @@ int eorb_search_by_projection_kf(eorb_ctx* c,
     // current frame skipped (:2255-2256) and ORBdist in place of TH_HIGH (:2271)
     std::vector<eorb_keypoint> q(kf_kps, kf_kps + n_kf);
     for (int i = 0; i < n_kf; i++) { q[i].octave = pred_level[i]; q[i].class_id = pred_level[i]; }
-    std::vector<uint8_t> obs((size_t)n_kf, 1);
-    std::vector<int32_t> slots(cur_mp, cur_mp + (n_cur > 0 ? n_cur : 0));
-    for (int i = 0; i < n_cur; i++) if (slots[i] != -1) slots[i] = -2;
-    const int rc = proj_last_common(c, cur_kps, n_cur, cur_desc, cur_stride, cur_is_orb, q.data(), n_kf, kf_is_orb, valid, uv, mp_desc,
-                                    obs.data(), level_scale, gb, slots.data(), th, 0, checkOri, ORBdist, nmatches);
-    if (rc) return rc;
-    for (int i = 0; i < n_cur; i++) if (slots[i] >= 0) cur_mp[i] = slots[i];
-    return EORB_OK;
+    const std::vector<uint8_t> obs((size_t)n_kf, 1);
+    return proj_last_common(c, cur_kps, n_cur, cur_desc, cur_stride, cur_is_orb, q.data(), n_kf, kf_is_orb, valid, uv, mp_desc,
+                            obs.data(), level_scale, gb, cur_mp, th, 0, checkOri, ORBdist, nmatches, nullptr, nullptr, true);
 }
 
 static int proj_map_common(eorb_ctx* c,
@@ -1576,27 +1594,21 @@ static int proj_map_common(eorb_ctx* c,
     if (M == 0 || n == 0) return EORB_OK;
     int rc;
     Arena A(c);
-    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)n), o_d = A.in(desc, (size_t)stride * n), o_o = A.in(is_orb, is_orb ? n : 0);
+    const FrameOff fr = frame_in(A, kps, n, desc, stride, is_orb, uright);
     const size_t o_md = A.in(mp_desc, 32 * (size_t)M);
     // per map point record: proj x, proj y, view cos, level scale (floats) | level (int) | in_view, obs, is_orb (bytes)
     std::vector<float> f4(4 * (size_t)M);
     for (int m = 0; m < M; m++) { f4[4 * m] = proj_xy[2 * m]; f4[4 * m + 1] = proj_xy[2 * m + 1]; f4[4 * m + 2] = view_cos[m]; f4[4 * m + 3] = level_scale[m]; }
     const size_t o_f4 = A.in(f4.data(), sizeof(float) * f4.size()), o_lv = A.in(level, sizeof(int32_t) * (size_t)M);
     const size_t o_iv = A.in(in_view, M), o_ob = A.in(mp_obs, M), o_mo = A.in(mp_is_orb, mp_is_orb ? M : 0);
-    const size_t o_ur2 = A.in(uright, uright ? sizeof(float) * (size_t)n : 0), o_qur = A.in(proj_xr, proj_xr ? sizeof(float) * (size_t)M : 0);
-    const size_t o_nm = A.in(nullptr, 16);
-    const size_t o_fm = A.in(frame_mp, sizeof(int32_t) * (size_t)n);
+    const size_t o_qur = A.in(proj_xr, proj_xr ? sizeof(float) * (size_t)M : 0);
+    const ResultOff r = result_in(A, frame_mp, n);
     if ((rc = A.upload())) return rc;
-    rc = search_proj_map_dev(c, A.dev<eorb_keypoint>(o_k), n, A.dev<uint8_t>(o_d), stride, is_orb ? A.dev<uint8_t>(o_o) : nullptr, M,
-                             A.dev<uint8_t>(o_iv), A.dev<float4>(o_f4), A.dev<int32_t>(o_lv), A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob),
-                             mp_is_orb ? A.dev<uint8_t>(o_mo) : nullptr, *gb, A.dev<int32_t>(o_fm), th, nnratio, A.dev<int32_t>(o_nm),
-                             uright ? A.dev<float>(o_ur2) : nullptr, proj_xr ? A.dev<float>(o_qur) : nullptr);
-    if (rc) return rc;
-    const char* h;
-    if ((rc = A.download(o_nm, o_fm + sizeof(int32_t) * (size_t)n - o_nm, &h))) return rc;
-    memcpy(frame_mp, h + o_fm, sizeof(int32_t) * (size_t)n);
-    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
-    return EORB_OK;
+    const ProjMapArgs P{frame_dev(A, fr), grid_b(*gb), M, A.dev<uint8_t>(o_iv), A.dev<float4>(o_f4), A.dev<int32_t>(o_lv),
+                        A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob), mp_is_orb ? A.dev<uint8_t>(o_mo) : nullptr,
+                        proj_xr ? A.dev<float>(o_qur) : nullptr, th, nnratio, A.dev<int32_t>(r.slots), A.dev<int32_t>(r.nm)};
+    if ((rc = search_proj_map_dev(c, P))) return rc;
+    return result_out(A, r, r.end, frame_mp, nmatches);
 }
 
 int eorb_search_by_projection_map(eorb_ctx* c,
@@ -1621,8 +1633,6 @@ int eorb_search_by_projection_map_stereo(eorb_ctx* c,
 }
 
 // ---- map points projected on the device (project.hip) ---------------------------------------------------------------------------
-static int twocam_frame_check(eorb_ctx* c, const char* who, const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
-                              const int32_t* slots, int nq);
 static int view_check(eorb_ctx* c, const char* who, const eorb_view* v, bool has_is_orb)
 {
     if (!v) return set_err(c, EORB_E_ARG, "%s: null view", who);
@@ -1683,17 +1693,51 @@ static void frustum_copy_out(const char* h, const FrustumOff& o, int M, const eo
     if (out.reason) memcpy(out.reason, h + o.rs, m);
 }
 
-// the map points of mode A and their arena offsets
-struct PointsOff { size_t pos, nrm, mind, maxd, skip, orb; };
+// the points of modes A, B and C and their arena offsets (is_orb: per map point, or per query keypoint in mode B)
+struct PointsOff { size_t pos, nrm, mind, maxd, skip, orb; bool has_skip, has_orb; };
 static PointsOff points_in(Arena& A, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
                            const uint8_t* skip, const uint8_t* is_orb)
 {
     const size_t m = (size_t)M;
-    PointsOff o;
-    o.pos = A.in(pos, 12 * m); o.nrm = A.in(normal, normal ? 12 * m : 0);
-    o.mind = A.in(min_dist, min_dist ? 4 * m : 0); o.maxd = A.in(max_dist, max_dist ? 4 * m : 0);
-    o.skip = A.in(skip, skip ? m : 0); o.orb = A.in(is_orb, is_orb ? m : 0);
-    return o;
+    return PointsOff{A.in(pos, 12 * m), A.in(normal, normal ? 12 * m : 0), A.in(min_dist, min_dist ? 4 * m : 0), A.in(max_dist, max_dist ? 4 * m : 0),
+                     A.in(skip, skip ? m : 0), A.in(is_orb, is_orb ? m : 0), skip != nullptr, is_orb != nullptr};
+}
+
+// mode A over nviews views
+static FrustumArgs frustum_args(const Arena& A, const eorb_view* views, int nviews, const ViewOff* vo, const FrustumOff* fo, int M, const PointsOff& po,
+                                float cos_limit, int far, float th_far, int32_t* n_in_view)
+{
+    FrustumArgs F{};
+    for (int v = 0; v < nviews; v++) { F.V[v] = view_dev(A, views + v, vo[v]); F.O[v] = frustum_dev(A, fo[v]); }
+    F.nviews = nviews; F.M = M;
+    F.pos = A.dev<float>(po.pos); F.normal = A.dev<float>(po.nrm); F.min_dist = A.dev<float>(po.mind); F.max_dist = A.dev<float>(po.maxd);
+    F.skip = po.has_skip ? A.dev<uint8_t>(po.skip) : nullptr; F.is_orb = po.has_orb ? A.dev<uint8_t>(po.orb) : nullptr;
+    F.cos_limit = cos_limit; F.far = far; F.th_far = th_far; F.n_in_view = n_in_view;
+    return F;
+}
+
+// the output regions of modes B (ur = proj_ur, uvr) and C (lv = level, d3 = dist3d).  Each entry point reserves them in the order of
+// its own outputs
+struct PoseOff { size_t va, uv, lv, ls, ur, uvr, d3, rec; };
+static LastArgs last_args(const Arena& A, const eorb_view* view, const ViewOff& vo, int n, const PointsOff& po, const eorb_keypoint* d_kps, const PoseOff& o)
+{
+    LastArgs L{};
+    L.V = view_dev(A, view, vo);
+    L.n = n; L.pos = A.dev<float>(po.pos); L.skip = po.has_skip ? A.dev<uint8_t>(po.skip) : nullptr; L.kps = d_kps;
+    L.is_orb = po.has_orb ? A.dev<uint8_t>(po.orb) : nullptr;
+    L.valid = A.dev<uint8_t>(o.va); L.uv = A.dev<float2>(o.uv); L.proj_ur = A.dev<float>(o.ur); L.level_scale = A.dev<float>(o.ls);
+    L.uv_r = A.dev<float2>(o.uvr); L.rec3 = A.dev<float>(o.rec);
+    return L;
+}
+static KfArgs kf_args(const Arena& A, const eorb_view* view, const ViewOff& vo, int n, const PointsOff& po, const PoseOff& o)
+{
+    KfArgs K{};
+    K.V = view_dev(A, view, vo);
+    K.n = n; K.pos = A.dev<float>(po.pos); K.min_dist = A.dev<float>(po.mind); K.max_dist = A.dev<float>(po.maxd);
+    K.skip = po.has_skip ? A.dev<uint8_t>(po.skip) : nullptr; K.is_orb = po.has_orb ? A.dev<uint8_t>(po.orb) : nullptr;
+    K.valid = A.dev<uint8_t>(o.va); K.uv = A.dev<float2>(o.uv); K.level = A.dev<int32_t>(o.lv); K.level_scale = A.dev<float>(o.ls);
+    K.dist3d = A.dev<float>(o.d3); K.rec3 = A.dev<float>(o.rec);
+    return K;
 }
 
 int eorb_project_frustum(eorb_ctx* c, const eorb_view* views, int nviews, int M, const float* pos, const float* normal,
@@ -1717,13 +1761,7 @@ int eorb_project_frustum(eorb_ctx* c, const eorb_view* views, int nviews, int M,
     for (int v = 0; v < nviews; v++) fo[v] = frustum_reserve(A, M);
     for (int v = 0; v < nviews; v++) frustum_reserve_recs(A, M, fo[v]);
     if ((rc = A.upload())) return rc;
-    FrustumArgs F{};
-    for (int v = 0; v < nviews; v++) { F.V[v] = view_dev(A, views + v, vo[v]); F.O[v] = frustum_dev(A, fo[v]); }
-    F.nviews = nviews; F.M = M;
-    F.pos = A.dev<float>(po.pos); F.normal = A.dev<float>(po.nrm); F.min_dist = A.dev<float>(po.mind); F.max_dist = A.dev<float>(po.maxd);
-    F.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; F.is_orb = mp_is_orb ? A.dev<uint8_t>(po.orb) : nullptr;
-    F.cos_limit = cos_limit; F.far = 0; F.th_far = 0.f; F.n_in_view = A.dev<int32_t>(o_n);
-    if ((rc = project_frustum_dev(c, F))) return rc;
+    if ((rc = project_frustum_dev(c, frustum_args(A, views, nviews, vo, fo, M, po, cos_limit, 0, 0.f, A.dev<int32_t>(o_n))))) return rc;
     const char* h;
     if ((rc = A.download(o_n, fo[nviews - 1].end - o_n, &h))) return rc;
     if (out) for (int v = 0; v < nviews; v++) frustum_copy_out(h, fo[v], M, out[v]);
@@ -1755,29 +1793,26 @@ int eorb_project_last_frame(eorb_ctx* c, const eorb_view* view, const eorb_camer
     if (n == 0) return EORB_OK;
     const size_t m = (size_t)n;
     Arena A(c);
-    const size_t o_pos = A.in(pos, 12 * m), o_skip = A.in(skip, skip ? m : 0), o_k = A.in(last_kps, sizeof(eorb_keypoint) * m);
-    const size_t o_orb = A.in(last_is_orb, last_is_orb ? m : 0);
+    const PointsOff po = points_in(A, n, pos, nullptr, nullptr, nullptr, skip, last_is_orb);
+    const size_t o_k = A.in(last_kps, sizeof(eorb_keypoint) * m);
     const ViewOff vo = view_in(A, view);
     // outputs, contiguous: valid | uv | proj_ur | level_scale | uv_r; then the matcher's record
-    const size_t o_va = A.reserve(m), o_uv = A.reserve(8 * m), o_ur = A.reserve(4 * m), o_ls = A.reserve(4 * m), o_uvr = A.reserve(8 * m);
-    const size_t o_end = A.total, o_rec = A.reserve(12 * m);
+    PoseOff o{};
+    o.va = A.reserve(m); o.uv = A.reserve(8 * m); o.ur = A.reserve(4 * m); o.ls = A.reserve(4 * m); o.uvr = A.reserve(8 * m);
+    const size_t o_end = A.total;
+    o.rec = A.reserve(12 * m);
     if ((rc = A.upload())) return rc;
-    LastArgs L{};
-    L.V = view_dev(A, view, vo);
+    LastArgs L = last_args(A, view, vo, n, po, A.dev<eorb_keypoint>(o_k), o);
     L.has_r = Trl ? 1 : 0;
     if (Trl) { L.cam_r = warp_cam_of(*cam_r); memcpy(L.Trl, Trl, sizeof(L.Trl)); }
-    L.n = n; L.pos = A.dev<float>(o_pos); L.skip = skip ? A.dev<uint8_t>(o_skip) : nullptr; L.kps = A.dev<eorb_keypoint>(o_k);
-    L.is_orb = last_is_orb ? A.dev<uint8_t>(o_orb) : nullptr;
-    L.valid = A.dev<uint8_t>(o_va); L.uv = A.dev<float2>(o_uv); L.proj_ur = A.dev<float>(o_ur); L.level_scale = A.dev<float>(o_ls);
-    L.uv_r = A.dev<float2>(o_uvr); L.rec3 = A.dev<float>(o_rec);
     if ((rc = project_last_dev(c, L))) return rc;
     const char* h;
-    if ((rc = A.download(o_va, o_end - o_va, &h))) return rc;
-    if (valid) memcpy(valid, h + o_va, m);
-    if (uv) memcpy(uv, h + o_uv, 8 * m);
-    if (proj_ur) memcpy(proj_ur, h + o_ur, 4 * m);
-    if (level_scale) memcpy(level_scale, h + o_ls, 4 * m);
-    if (uv_r) memcpy(uv_r, h + o_uvr, 8 * m);
+    if ((rc = A.download(o.va, o_end - o.va, &h))) return rc;
+    if (valid) memcpy(valid, h + o.va, m);
+    if (uv) memcpy(uv, h + o.uv, 8 * m);
+    if (proj_ur) memcpy(proj_ur, h + o.ur, 4 * m);
+    if (level_scale) memcpy(level_scale, h + o.ls, 4 * m);
+    if (uv_r) memcpy(uv_r, h + o.uvr, 8 * m);
     return EORB_OK;
 }
 
@@ -1795,23 +1830,20 @@ int eorb_project_keyframe_points(eorb_ctx* c, const eorb_view* view, int n, cons
     Arena A(c);
     const PointsOff po = points_in(A, n, pos, nullptr, min_dist, max_dist, skip, mp_is_orb);
     const ViewOff vo = view_in(A, view);
-    const size_t o_va = A.reserve(m), o_uv = A.reserve(8 * m), o_lv = A.reserve(4 * m), o_ls = A.reserve(4 * m), o_d3 = A.reserve(4 * m);
-    const size_t o_end = A.total, o_rec = A.reserve(12 * m);
+    // outputs, contiguous: valid | uv | level | level_scale | dist3d; then the matcher's record
+    PoseOff o{};
+    o.va = A.reserve(m); o.uv = A.reserve(8 * m); o.lv = A.reserve(4 * m); o.ls = A.reserve(4 * m); o.d3 = A.reserve(4 * m);
+    const size_t o_end = A.total;
+    o.rec = A.reserve(12 * m);
     if ((rc = A.upload())) return rc;
-    KfArgs K{};
-    K.V = view_dev(A, view, vo);
-    K.n = n; K.pos = A.dev<float>(po.pos); K.min_dist = A.dev<float>(po.mind); K.max_dist = A.dev<float>(po.maxd);
-    K.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; K.is_orb = mp_is_orb ? A.dev<uint8_t>(po.orb) : nullptr;
-    K.valid = A.dev<uint8_t>(o_va); K.uv = A.dev<float2>(o_uv); K.level = A.dev<int32_t>(o_lv); K.level_scale = A.dev<float>(o_ls);
-    K.dist3d = A.dev<float>(o_d3); K.rec3 = A.dev<float>(o_rec);
-    if ((rc = project_kf_dev(c, K))) return rc;
+    if ((rc = project_kf_dev(c, kf_args(A, view, vo, n, po, o)))) return rc;
     const char* h;
-    if ((rc = A.download(o_va, o_end - o_va, &h))) return rc;
-    if (valid) memcpy(valid, h + o_va, m);
-    if (uv) memcpy(uv, h + o_uv, 8 * m);
-    if (level) memcpy(level, h + o_lv, 4 * m);
-    if (level_scale) memcpy(level_scale, h + o_ls, 4 * m);
-    if (dist3d) memcpy(dist3d, h + o_d3, 4 * m);
+    if ((rc = A.download(o.va, o_end - o.va, &h))) return rc;
+    if (valid) memcpy(valid, h + o.va, m);
+    if (uv) memcpy(uv, h + o.uv, 8 * m);
+    if (level) memcpy(level, h + o.lv, 4 * m);
+    if (level_scale) memcpy(level_scale, h + o.ls, 4 * m);
+    if (dist3d) memcpy(dist3d, h + o.d3, 4 * m);
     return EORB_OK;
 }
 
@@ -1834,37 +1866,26 @@ int eorb_search_local_points(eorb_ctx* c,
     fe_enter(c);
     if (M == 0) return EORB_OK;
     Arena A(c);
-    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)n), o_d = A.in(desc, (size_t)stride * n), o_o = A.in(is_orb, is_orb ? n : 0);
+    const FrameOff fr = frame_in(A, kps, n, desc, stride, is_orb, uright);
     const size_t o_md = A.in(mp_desc, 32 * (size_t)M), o_ob = A.in(mp_obs, M);
-    const size_t o_ur2 = A.in(uright, uright ? sizeof(float) * (size_t)n : 0);
     const PointsOff po = points_in(A, M, pos, normal, min_dist, max_dist, skip, mp_is_orb);
     const ViewOff vo = view_in(A, view);
     // outputs, contiguous: {nmatches, n_in_view} | slots (in/out) | the projection arrays
-    const size_t o_nm = A.in(nullptr, 16);
-    const size_t o_fm = A.in(frame_mp, sizeof(int32_t) * (size_t)n);
+    const ResultOff r = result_in(A, frame_mp, n);
     FrustumOff fo = frustum_reserve(A, M);
     frustum_reserve_recs(A, M, fo);
     if ((rc = A.upload())) return rc;
-    FrustumArgs F{};
-    F.V[0] = view_dev(A, view, vo); F.O[0] = frustum_dev(A, fo);
-    F.nviews = 1; F.M = M;
-    F.pos = A.dev<float>(po.pos); F.normal = A.dev<float>(po.nrm); F.min_dist = A.dev<float>(po.mind); F.max_dist = A.dev<float>(po.maxd);
-    F.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; F.is_orb = mp_is_orb ? A.dev<uint8_t>(po.orb) : nullptr;
-    F.cos_limit = cos_limit; F.far = bFarPoints != 0; F.th_far = thFarPoints; F.n_in_view = A.dev<int32_t>(o_nm) + 1;
+    const FrustumArgs F = frustum_args(A, view, 1, &vo, &fo, M, po, cos_limit, bFarPoints != 0, thFarPoints, A.dev<int32_t>(r.nm) + 1);
     if ((rc = project_frustum_dev(c, F))) return rc;
     if (n > 0) {
-        rc = search_proj_map_dev(c, A.dev<eorb_keypoint>(o_k), n, A.dev<uint8_t>(o_d), stride, is_orb ? A.dev<uint8_t>(o_o) : nullptr, M,
-                                 F.O[0].search, F.O[0].rec, F.O[0].level, A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob),
-                                 mp_is_orb ? A.dev<uint8_t>(po.orb) : nullptr, *gb, A.dev<int32_t>(o_fm), th, nnratio, A.dev<int32_t>(o_nm),
-                                 uright ? A.dev<float>(o_ur2) : nullptr, uright ? F.O[0].proj_xr : nullptr);
-        if (rc) return rc;
-    } else EORB_HIP(c, hipMemsetAsync(A.dev<int32_t>(o_nm), 0, sizeof(int32_t), c->stream));
+        const ProjMapArgs P{frame_dev(A, fr), grid_b(*gb), M, F.O[0].search, F.O[0].rec, F.O[0].level, A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob),
+                            F.is_orb, uright ? F.O[0].proj_xr : nullptr, th, nnratio, A.dev<int32_t>(r.slots), A.dev<int32_t>(r.nm)};
+        rc = search_proj_map_dev(c, P);
+    } else rc = result_no_matches(c, A, r);
+    if (rc) return rc;
     const char* h;
-    if ((rc = A.download(o_nm, (out ? fo.end : o_fm + sizeof(int32_t) * (size_t)n) - o_nm, &h))) return rc;
-    memcpy(frame_mp, h + o_fm, sizeof(int32_t) * (size_t)n);
+    if ((rc = result_out(A, r, out ? fo.end : r.end, frame_mp, nmatches, n_in_view, &h))) return rc;
     if (out) frustum_copy_out(h, fo, M, *out);
-    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
-    if (n_in_view) *n_in_view = *((const int32_t*)(h + o_nm) + 1);
     return EORB_OK;
 }
 
@@ -1883,49 +1904,27 @@ int eorb_search_local_points_fisheye(eorb_ctx* c,
         return set_err(c, EORB_E_ARG, "search_local_points_fisheye: bad arguments");
     int rc;
     for (int v = 0; v < 2; v++) if ((rc = view_check(c, "search_local_points_fisheye", views + v, false))) return rc;
-    if ((rc = twocam_frame_check(c, "search_local_points_fisheye", kps, nL, nR, desc, stride, frame_mp, M))) return rc;
-    for (int i = 0; i < nL; i++) if (l2r[i] < -1 || l2r[i] >= nR) return set_err(c, EORB_E_ARG, "search_local_points_fisheye: l2r[%d] = %d", i, l2r[i]);
-    for (int i = 0; i < nR; i++) if (r2l[i] < -1 || r2l[i] >= nL) return set_err(c, EORB_E_ARG, "search_local_points_fisheye: r2l[%d] = %d", i, r2l[i]);
+    Arena A(c);
+    TcFrameOff fr;
+    if ((rc = twocam_frame_in(c, A, "search_local_points_fisheye", kps, nL, nR, desc, stride, frame_mp, M, l2r, r2l, fr))) return rc;
     fe_enter(c);
     const int nT = nL + nR;
     if (M == 0) return EORB_OK;
-    Arena A(c);
-    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)nT), o_d = A.in(desc, (size_t)stride * nT);
-    const size_t o_l2r = A.in(l2r, sizeof(int32_t) * (size_t)nL), o_r2l = A.in(r2l, sizeof(int32_t) * (size_t)nR);
     const size_t o_md = A.in(mp_desc, 32 * (size_t)M), o_ob = A.in(mp_obs, M);
     const PointsOff po = points_in(A, M, pos, normal, min_dist, max_dist, skip, nullptr);
     const ViewOff vo[2] = {view_in(A, views), view_in(A, views + 1)};
-    const size_t o_nm = A.in(nullptr, 16);
-    const size_t o_fm = A.in(frame_mp, sizeof(int32_t) * (size_t)nT);
+    const ResultOff r = result_in(A, frame_mp, nT);
     FrustumOff fo[2];
     for (int v = 0; v < 2; v++) fo[v] = frustum_reserve(A, M);
-    // the two views' records back to back: the two-camera matcher reads qf_r = qf + M in the host-buffer entry point, any pointer here
     for (int v = 0; v < 2; v++) frustum_reserve_recs(A, M, fo[v]);
     if ((rc = A.upload())) return rc;
-    FrustumArgs F{};
-    for (int v = 0; v < 2; v++) { F.V[v] = view_dev(A, views + v, vo[v]); F.O[v] = frustum_dev(A, fo[v]); }
-    F.nviews = 2; F.M = M;
-    F.pos = A.dev<float>(po.pos); F.normal = A.dev<float>(po.nrm); F.min_dist = A.dev<float>(po.mind); F.max_dist = A.dev<float>(po.maxd);
-    F.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; F.is_orb = nullptr;
-    F.cos_limit = cos_limit; F.far = bFarPoints != 0; F.th_far = thFarPoints; F.n_in_view = A.dev<int32_t>(o_nm) + 1;
+    const FrustumArgs F = frustum_args(A, views, 2, vo, fo, M, po, cos_limit, bFarPoints != 0, thFarPoints, A.dev<int32_t>(r.nm) + 1);
     if ((rc = project_frustum_dev(c, F))) return rc;
-    if (nT > 0) {
-        TcArgs T{};
-        T.kps = A.dev<eorb_keypoint>(o_k); T.nL = nL; T.nR = nR; T.desc = A.dev<uint8_t>(o_d); T.stride = stride;
-        T.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
-        T.nq = M; T.mp_desc = A.dev<uint8_t>(o_md); T.mp_obs = A.dev<uint8_t>(o_ob); T.th = th; T.nnratio = nnratio;
-        T.in_view = F.O[0].search; T.qf = F.O[0].rec; T.qlevel = F.O[0].level;
-        T.in_view_r = F.O[1].search; T.qf_r = F.O[1].rec; T.qlevel_r = F.O[1].level;
-        T.l2r = A.dev<int32_t>(o_l2r); T.r2l = A.dev<int32_t>(o_r2l);
-        T.slots = A.dev<int32_t>(o_fm); T.nmatches = A.dev<int32_t>(o_nm);
-        if ((rc = twocam_walk_dev(c, 0, T))) return rc;
-    } else EORB_HIP(c, hipMemsetAsync(A.dev<int32_t>(o_nm), 0, sizeof(int32_t), c->stream));
+    const CamQuery Q[2] = {{F.O[0].search, F.O[0].rec, F.O[0].level}, {F.O[1].search, F.O[1].rec, F.O[1].level}};
+    if ((rc = nT > 0 ? twocam_walk_dev(c, 0, twocam_args(A, fr, gb, M, o_md, o_ob, th, r, Q, nnratio)) : result_no_matches(c, A, r))) return rc;
     const char* h;
-    if ((rc = A.download(o_nm, (out ? fo[1].end : o_fm + sizeof(int32_t) * (size_t)nT) - o_nm, &h))) return rc;
-    memcpy(frame_mp, h + o_fm, sizeof(int32_t) * (size_t)nT);
+    if ((rc = result_out(A, r, out ? fo[1].end : r.end, frame_mp, nmatches, n_in_view, &h))) return rc;
     if (out) for (int v = 0; v < 2; v++) frustum_copy_out(h, fo[v], M, out[v]);
-    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
-    if (n_in_view) *n_in_view = *((const int32_t*)(h + o_nm) + 1);
     return EORB_OK;
 }
 
@@ -1949,65 +1948,41 @@ static int proj_pose_common(eorb_ctx* c, const char* who, bool kf,
     fe_enter(c);
     if (nq == 0) return EORB_OK;
     const size_t m = (size_t)nq;
-    std::vector<uint8_t> obs;
-    std::vector<int32_t> slots;
-    if (kf) {
-        obs.assign(m, 1);
-        slots.assign(cur_mp, cur_mp + n_cur);
-        for (int i = 0; i < n_cur; i++) if (slots[i] != -1) slots[i] = -2;
-    }
+    const std::vector<uint8_t> obs(kf ? m : 0, 1);
     Arena A(c);
-    const size_t o_ck = A.in(cur_kps, sizeof(eorb_keypoint) * (size_t)n_cur), o_cd = A.in(cur_desc, (size_t)cur_stride * n_cur);
-    const size_t o_co = A.in(cur_is_orb, cur_is_orb ? n_cur : 0);
-    const size_t o_qk = A.in(q_kps, sizeof(eorb_keypoint) * m), o_qo = A.in(q_is_orb, q_is_orb ? m : 0);
+    const FrameOff fr = frame_in(A, cur_kps, n_cur, cur_desc, cur_stride, cur_is_orb, cur_uright);
+    const size_t o_qk = A.in(q_kps, sizeof(eorb_keypoint) * m);
     const size_t o_md = A.in(mp_desc, 32 * m), o_ob = A.in(kf ? obs.data() : mp_obs, m);
-    const size_t o_ur2 = A.in(cur_uright, cur_uright ? sizeof(float) * (size_t)n_cur : 0);
-    const PointsOff po = points_in(A, nq, pos, nullptr, min_dist, max_dist, skip, nullptr);
+    const PointsOff po = points_in(A, nq, pos, nullptr, min_dist, max_dist, skip, q_is_orb);
     const ViewOff vo = view_in(A, view);
-    // outputs, contiguous: nmatches | slots (in/out) | valid | uv | level
-    const size_t o_nm = A.in(nullptr, 16);
-    const size_t o_mp = A.in(kf ? slots.data() : cur_mp, sizeof(int32_t) * (size_t)n_cur);
-    const size_t o_va = A.reserve(m), o_uv = A.reserve(8 * m), o_lv = A.reserve(4 * m);
+    // outputs, contiguous: nmatches | slots (in/out) | valid | uv | level; then what only the matcher reads
+    const ResultOff r = result_in(A, cur_mp, n_cur, kf);
+    PoseOff o{};
+    o.va = A.reserve(m); o.uv = A.reserve(8 * m); o.lv = A.reserve(4 * m);
     const size_t o_end = A.total;
-    const size_t o_ls = A.reserve(4 * m), o_x = A.reserve(4 * m), o_uvr = A.reserve(8 * m), o_rec = A.reserve(12 * m);
+    o.ls = A.reserve(4 * m); o.ur = o.d3 = A.reserve(4 * m); o.uvr = A.reserve(8 * m); o.rec = A.reserve(12 * m);      // (ur, d3: one region, by mode)
     const size_t o_q2 = A.reserve(sizeof(eorb_keypoint) * m);
     if ((rc = A.upload())) return rc;
     const eorb_keypoint* d_q = A.dev<eorb_keypoint>(o_qk);
-    const uint8_t* d_qo = q_is_orb ? A.dev<uint8_t>(o_qo) : nullptr;
     if (kf) {
-        KfArgs K{};
-        K.V = view_dev(A, view, vo);
-        K.n = nq; K.pos = A.dev<float>(po.pos); K.min_dist = A.dev<float>(po.mind); K.max_dist = A.dev<float>(po.maxd);
-        K.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; K.is_orb = d_qo;
-        K.valid = A.dev<uint8_t>(o_va); K.uv = A.dev<float2>(o_uv); K.level = A.dev<int32_t>(o_lv); K.level_scale = A.dev<float>(o_ls);
-        K.dist3d = A.dev<float>(o_x); K.rec3 = A.dev<float>(o_rec); K.kf_kps = d_q; K.q_kps = A.dev<eorb_keypoint>(o_q2);
-        if ((rc = project_kf_dev(c, K))) return rc;
+        KfArgs K = kf_args(A, view, vo, nq, po, o);
+        K.kf_kps = d_q; K.q_kps = A.dev<eorb_keypoint>(o_q2);
+        rc = project_kf_dev(c, K);
         d_q = K.q_kps;
-    } else {
-        LastArgs L{};
-        L.V = view_dev(A, view, vo);
-        L.n = nq; L.pos = A.dev<float>(po.pos); L.skip = skip ? A.dev<uint8_t>(po.skip) : nullptr; L.kps = d_q; L.is_orb = d_qo;
-        L.valid = A.dev<uint8_t>(o_va); L.uv = A.dev<float2>(o_uv); L.proj_ur = A.dev<float>(o_x); L.level_scale = A.dev<float>(o_ls);
-        L.uv_r = A.dev<float2>(o_uvr); L.rec3 = A.dev<float>(o_rec);
-        if ((rc = project_last_dev(c, L))) return rc;
-    }
+    } else rc = project_last_dev(c, last_args(A, view, vo, nq, po, d_q, o));
+    if (rc) return rc;
     if (n_cur > 0) {
-        rc = search_proj_last_dev(c, A.dev<eorb_keypoint>(o_ck), n_cur, A.dev<uint8_t>(o_cd), cur_stride,
-                                  cur_is_orb ? A.dev<uint8_t>(o_co) : nullptr, d_q, nq, d_qo, A.dev<uint8_t>(o_va), A.dev<float>(o_rec),
-                                  A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob), dist_th, *gb, A.dev<int32_t>(o_mp), th, mode, checkOri,
-                                  A.dev<int32_t>(o_nm), cur_uright ? A.dev<float>(o_ur2) : nullptr, cur_uright ? A.dev<float>(o_x) : nullptr);
-        if (rc) return rc;
-    } else EORB_HIP(c, hipMemsetAsync(A.dev<int32_t>(o_nm), 0, sizeof(int32_t), c->stream));
+        const ProjLastArgs P{frame_dev(A, fr), grid_b(*gb), d_q, nq, po.has_orb ? A.dev<uint8_t>(po.orb) : nullptr, A.dev<uint8_t>(o.va),
+                             A.dev<float>(o.rec), A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob), cur_uright ? A.dev<float>(o.ur) : nullptr,
+                             th, mode, checkOri, dist_th, A.dev<int32_t>(r.slots), A.dev<int32_t>(r.nm)};
+        rc = search_proj_last_dev(c, P);
+    } else rc = result_no_matches(c, A, r);
+    if (rc) return rc;
     const char* h;
-    const bool proj_out = valid || uv || level;
-    if ((rc = A.download(o_nm, (proj_out ? o_end : o_mp + sizeof(int32_t) * (size_t)n_cur) - o_nm, &h))) return rc;
-    const int32_t* hs = (const int32_t*)(h + o_mp);
-    if (kf) { for (int i = 0; i < n_cur; i++) if (hs[i] >= 0) cur_mp[i] = hs[i]; }
-    else memcpy(cur_mp, hs, sizeof(int32_t) * (size_t)n_cur);
-    if (valid) memcpy(valid, h + o_va, m);
-    if (uv) memcpy(uv, h + o_uv, 8 * m);
-    if (level) memcpy(level, h + o_lv, 4 * m);
-    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
+    if ((rc = result_out(A, r, (valid || uv || level) ? o_end : r.end, cur_mp, nmatches, nullptr, &h))) return rc;
+    if (valid) memcpy(valid, h + o.va, m);
+    if (uv) memcpy(uv, h + o.uv, 8 * m);
+    if (level) memcpy(level, h + o.lv, 4 * m);
     return EORB_OK;
 }
 
@@ -2202,22 +2177,6 @@ int eorb_frame_fisheye(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRigh
     return EORB_OK;
 }
 
-// the searched two-camera frame's checks shared by the two projection matchers: sizes, octaves (the kernel keeps levels in 8 bits),
-// slot states (-3 .. nq - 1)
-static int twocam_frame_check(eorb_ctx* c, const char* who, const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride,
-                              const int32_t* slots, int nq)
-{
-    const int nT = nL + nR;
-    if (nL < 0 || nR < 0 || nq < 0 || stride < 32 || !slots || (nT > 0 && (!kps || !desc))) return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
-    if (nT > kTcMaxKpsHost) return set_err(c, EORB_E_CAPACITY, "%s: %d keypoints > %d", who, nT, kTcMaxKpsHost);
-    if (nq >= (1 << 24)) return set_err(c, EORB_E_CAPACITY, "%s: %d queries >= 2^24", who, nq);
-    for (int i = 0; i < nT; i++) {
-        if (kps[i].octave < 0 || kps[i].octave > 127) return set_err(c, EORB_E_ARG, "%s: keypoint %d has octave %d outside [0, 127]", who, i, kps[i].octave);
-        if (slots[i] < -3 || slots[i] >= nq) return set_err(c, EORB_E_ARG, "%s: slot %d holds %d", who, i, slots[i]);
-    }
-    return EORB_OK;
-}
-
 int eorb_search_by_projection_map_fisheye(eorb_ctx* c,
         const eorb_keypoint* kps, int nL, int nR, const uint8_t* desc, int stride, const int32_t* l2r, const int32_t* r2l,
         int M, const uint8_t* in_view, const float* proj_xy, const int32_t* level, const float* view_cos, const float* level_scale,
@@ -2232,15 +2191,12 @@ int eorb_search_by_projection_map_fisheye(eorb_ctx* c,
         (nL > 0 && !l2r) || (nR > 0 && !r2l))
         return set_err(c, EORB_E_ARG, "search_by_projection_map_fisheye: bad arguments");
     int rc;
-    if ((rc = twocam_frame_check(c, "search_by_projection_map_fisheye", kps, nL, nR, desc, stride, frame_mp, M))) return rc;
-    for (int i = 0; i < nL; i++) if (l2r[i] < -1 || l2r[i] >= nR) return set_err(c, EORB_E_ARG, "search_by_projection_map_fisheye: l2r[%d] = %d", i, l2r[i]);
-    for (int i = 0; i < nR; i++) if (r2l[i] < -1 || r2l[i] >= nL) return set_err(c, EORB_E_ARG, "search_by_projection_map_fisheye: r2l[%d] = %d", i, r2l[i]);
+    Arena A(c);
+    TcFrameOff fr;
+    if ((rc = twocam_frame_in(c, A, "search_by_projection_map_fisheye", kps, nL, nR, desc, stride, frame_mp, M, l2r, r2l, fr))) return rc;
     fe_enter(c);
     const int nT = nL + nR;
     if (M == 0 || nT == 0) return EORB_OK;
-    Arena A(c);
-    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)nT), o_d = A.in(desc, (size_t)stride * nT);
-    const size_t o_l2r = A.in(l2r, sizeof(int32_t) * (size_t)nL), o_r2l = A.in(r2l, sizeof(int32_t) * (size_t)nR);
     const size_t o_md = A.in(mp_desc, 32 * (size_t)M);
     // per map point and camera: proj x, proj y, view cos, level scale
     std::vector<float> f4(8 * (size_t)M);
@@ -2252,23 +2208,12 @@ int eorb_search_by_projection_map_fisheye(eorb_ctx* c,
     const size_t o_f4 = A.in(f4.data(), sizeof(float) * f4.size());
     const size_t o_lv = A.in(level, sizeof(int32_t) * (size_t)M), o_lvr = A.in(level_r, sizeof(int32_t) * (size_t)M);
     const size_t o_iv = A.in(in_view, M), o_ivr = A.in(in_view_r, M), o_ob = A.in(mp_obs, M);
-    const size_t o_nm = A.in(nullptr, 16);
-    const size_t o_fm = A.in(frame_mp, sizeof(int32_t) * (size_t)nT);
+    const ResultOff r = result_in(A, frame_mp, nT);
     if ((rc = A.upload())) return rc;
-    TcArgs T{};
-    T.kps = A.dev<eorb_keypoint>(o_k); T.nL = nL; T.nR = nR; T.desc = A.dev<uint8_t>(o_d); T.stride = stride;
-    T.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
-    T.nq = M; T.mp_desc = A.dev<uint8_t>(o_md); T.mp_obs = A.dev<uint8_t>(o_ob); T.th = th; T.nnratio = nnratio;
-    T.in_view = A.dev<uint8_t>(o_iv); T.qf = A.dev<float4>(o_f4); T.qlevel = A.dev<int32_t>(o_lv);
-    T.in_view_r = A.dev<uint8_t>(o_ivr); T.qf_r = A.dev<float4>(o_f4) + M; T.qlevel_r = A.dev<int32_t>(o_lvr);
-    T.l2r = A.dev<int32_t>(o_l2r); T.r2l = A.dev<int32_t>(o_r2l);
-    T.slots = A.dev<int32_t>(o_fm); T.nmatches = A.dev<int32_t>(o_nm);
-    if ((rc = twocam_walk_dev(c, 0, T))) return rc;
-    const char* h;
-    if ((rc = A.download(o_nm, o_fm + sizeof(int32_t) * (size_t)nT - o_nm, &h))) return rc;
-    memcpy(frame_mp, h + o_fm, sizeof(int32_t) * (size_t)nT);
-    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
-    return EORB_OK;
+    const CamQuery Q[2] = {{A.dev<uint8_t>(o_iv), A.dev<float4>(o_f4), A.dev<int32_t>(o_lv)},
+                           {A.dev<uint8_t>(o_ivr), A.dev<float4>(o_f4) + M, A.dev<int32_t>(o_lvr)}};
+    if ((rc = twocam_walk_dev(c, 0, twocam_args(A, fr, gb, M, o_md, o_ob, th, r, Q, nnratio)))) return rc;
+    return result_out(A, r, r.end, frame_mp, nmatches);
 }
 
 int eorb_search_by_projection_last_fisheye(eorb_ctx* c,
@@ -2283,12 +2228,12 @@ int eorb_search_by_projection_last_fisheye(eorb_ctx* c,
         (n_last > 0 && (!last_kps || !valid || !uv || !uv_r || !mp_desc || !mp_obs || !level_scale)))
         return set_err(c, EORB_E_ARG, "search_by_projection_last_fisheye: bad arguments");
     int rc;
-    if ((rc = twocam_frame_check(c, "search_by_projection_last_fisheye", cur_kps, nL, nR, cur_desc, cur_stride, cur_mp, n_last))) return rc;
+    Arena A(c);
+    TcFrameOff fr;
+    if ((rc = twocam_frame_in(c, A, "search_by_projection_last_fisheye", cur_kps, nL, nR, cur_desc, cur_stride, cur_mp, n_last, nullptr, nullptr, fr))) return rc;
     fe_enter(c);
     const int nT = nL + nR;
     if (n_last == 0 || nT == 0) return EORB_OK;
-    Arena A(c);
-    const size_t o_k = A.in(cur_kps, sizeof(eorb_keypoint) * (size_t)nT), o_d = A.in(cur_desc, (size_t)cur_stride * nT);
     const size_t o_lk = A.in(last_kps, sizeof(eorb_keypoint) * (size_t)n_last), o_md = A.in(mp_desc, 32 * (size_t)n_last);
     std::vector<float> f5(5 * (size_t)n_last);
     for (int i = 0; i < n_last; i++) {
@@ -2297,23 +2242,14 @@ int eorb_search_by_projection_last_fisheye(eorb_ctx* c,
     }
     const size_t o_f5 = A.in(f5.data(), sizeof(float) * f5.size());
     const size_t o_va = A.in(valid, n_last), o_ob = A.in(mp_obs, n_last);
-    const size_t o_nm = A.in(nullptr, 16);
-    const size_t o_mp = A.in(cur_mp, sizeof(int32_t) * (size_t)nT);
+    const ResultOff r = result_in(A, cur_mp, nT);
     const size_t o_rec = A.reserve(2 * sizeof(int32_t) * (size_t)n_last);
     if ((rc = A.upload())) return rc;
-    TcArgs T{};
-    T.kps = A.dev<eorb_keypoint>(o_k); T.nL = nL; T.nR = nR; T.desc = A.dev<uint8_t>(o_d); T.stride = cur_stride;
-    T.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
-    T.nq = n_last; T.mp_desc = A.dev<uint8_t>(o_md); T.mp_obs = A.dev<uint8_t>(o_ob); T.th = th;
+    TcArgs T = twocam_args(A, fr, gb, n_last, o_md, o_ob, th, r);
     T.valid = A.dev<uint8_t>(o_va); T.quv = A.dev<float>(o_f5); T.qkps = A.dev<eorb_keypoint>(o_lk); T.mode = mode; T.checkOri = checkOri;
     T.rec = A.dev<int32_t>(o_rec);
-    T.slots = A.dev<int32_t>(o_mp); T.nmatches = A.dev<int32_t>(o_nm);
     if ((rc = twocam_walk_dev(c, 1, T))) return rc;
-    const char* h;
-    if ((rc = A.download(o_nm, o_mp + sizeof(int32_t) * (size_t)nT - o_nm, &h))) return rc;
-    memcpy(cur_mp, h + o_mp, sizeof(int32_t) * (size_t)nT);
-    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
-    return EORB_OK;
+    return result_out(A, r, r.end, cur_mp, nmatches);
 }
 
 // the BoW-node walk of SearchForTriangulation (:975-1214) shared by both camera models: kb == nullptr runs the Pinhole test on
@@ -2475,7 +2411,7 @@ static int kf_radius_common(eorb_ctx* c,
     if ((rc = A.upload())) return rc;
     RadArgs R{};
     R.kps = A.dev<eorb_keypoint>(o_k); R.n = n; R.desc = A.dev<uint8_t>(o_d); R.stride = stride;
-    R.g = GridB{gb->minX, gb->minY, gb->invW, gb->invH};
+    R.g = grid_b(*gb);
     R.cell = A.dev<uint16_t>(o_cell);
     R.M = M; R.valid = A.dev<uint8_t>(o_va); R.uv = A.dev<float>(o_uv);
     R.radius = A.dev<float>(o_rad); R.level = A.dev<int32_t>(o_lv); R.q_desc = A.dev<uint8_t>(o_qd);

@@ -893,6 +893,17 @@ static size_t win_resolve_lds_rest(int cap2, int capq)
     return ((size_t)capq * (4 + 4 + 4 + 1 + 16) + (32 + 4) * 4 + (size_t)cap2 * (4 + 2 + 1 + 8 + 4) + 16 + 15) & ~(size_t)15;
 }
 
+// A kernel's dynamic LDS beyond 64 KB needs an opt-in, which holds per device: made once per context (a second context on another
+// GPU needs it too) and kernel; `bit` numbers the kernel in c->lds_optin
+enum { kOptWinCand = 0, kOptWinResolve = 3, kOptTwocam = 6, kOptKfRadius = 8, kOptBowAssemble = 9 };
+static int lds_optin(eorb_ctx* c, int bit, const void* kernel, int bytes)
+{
+    if (c->lds_optin & (1u << bit)) return EORB_OK;
+    EORB_HIP(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    c->lds_optin |= 1u << bit;
+    return EORB_OK;
+}
+
 // smallest d in [lo, 256] for which pred(d) holds, else 257 (= keep every candidate)
 template <typename F> static int first_dist(int lo, F pred) { for (int d = lo; d <= 256; d++) if (pred(d)) return d; return 257; }
 
@@ -934,12 +945,8 @@ static int launch_win(eorb_ctx* c, WinArgs& A, int npairs, int nq_max, const cha
     A.total = (uint32_t*)c->win_total.p;
     const size_t total_n = c->win_total_n;
     c->win_total_n = 0;                                 // (until both phases are known to have been launched)
-    // per device, not per process: a second context on another GPU needs the opt-in too -- once per context and kind
-    if (!(c->win_attr_done & (1u << KIND))) {
-        EORB_HIP(c, hipFuncSetAttribute((const void*)win_cand_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-        EORB_HIP(c, hipFuncSetAttribute((const void*)win_resolve_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-        c->win_attr_done |= 1u << KIND;
-    }
+    if ((rc = lds_optin(c, kOptWinCand + KIND, (const void*)win_cand_kernel<KIND>, 159 * 1024))) return rc;
+    if ((rc = lds_optin(c, kOptWinResolve + KIND, (const void*)win_resolve_kernel<KIND>, 159 * 1024))) return rc;
     ProfScope ps(c, name);
     // queries per phase-1 workgroup: a lone pair is spread over as many workgroups as it has queries per wavefront (one each: 0.091 ->
     // 0.085 ms per SearchForInitialization call against two each; every workgroup stages the searched frame, 57 KB, from the L2)
@@ -968,7 +975,7 @@ int search_init_dev(eorb_ctx* c, int npairs,
     A.nqp = n1; A.capq = cap1;
     A.kps1 = kps1; A.kp1_stride = kp1_stride; A.desc1 = desc1; A.dstride1 = dstride1; A.desc1_slice = desc1_slice; A.is_orb1 = is_orb1;
     A.prev_matched = prev_matched; A.windowSize = windowSize;
-    A.g = GridB{gb.minX, gb.minY, gb.invW, gb.invH}; A.nnratio = nnratio; A.checkOri = checkOri;
+    A.g = grid_b(gb); A.nnratio = nnratio; A.checkOri = checkOri;
     A.matches12 = matches12; A.nmatches = nmatches;
     // a second-best candidate only matters while "bestDist < bestDist2 * ratio" (:772) can fail for some bestDist <= TH_LOW: every
     // dist2 with TH_LOW < dist2 * ratio passes like INT_MAX does (float product monotone in dist2); best candidates need dist <= TH_LOW
@@ -976,39 +983,35 @@ int search_init_dev(eorb_ctx* c, int npairs,
     return launch_win<0>(c, A, npairs, cap1, "search_init");
 }
 
-int search_proj_last_dev(eorb_ctx* c, const eorb_keypoint* cur_kps, int n_cur, const uint8_t* cur_desc, int cur_stride,
-                         const uint8_t* cur_is_orb, const eorb_keypoint* last_kps, int n_last, const uint8_t* last_is_orb,
-                         const uint8_t* valid, const float* uvs, const uint8_t* mp_desc, const uint8_t* mp_obs,
-                         int dist_th, eorb_grid_bounds gb, int32_t* cur_mp, float th, int mode, int checkOri,
-                         int32_t* nmatches, const float* cur_uright, const float* q_ur)
+// a lone pair's searched frame
+static void win_frame(WinArgs& A, const FrameDev& f) { A.kps2 = f.kps; A.n2 = f.n; A.cap2 = std::max(f.n, 1); A.desc2 = f.desc; A.dstride2 = f.stride; A.is_orb2 = f.is_orb; A.uright2 = f.uright; }
+
+int search_proj_last_dev(eorb_ctx* c, const ProjLastArgs& P)
 {
     WinArgs A{};
-    A.dist_th = dist_th; A.uright2 = cur_uright; A.q_ur = q_ur;
-    A.kps2 = cur_kps; A.n2 = n_cur; A.cap2 = std::max(n_cur, 1); A.desc2 = cur_desc; A.dstride2 = cur_stride; A.is_orb2 = cur_is_orb;
-    A.nq = n_last; A.capq = std::max(n_last, 1); A.qkps = last_kps; A.q_is_orb = last_is_orb; A.valid = valid; A.qf = uvs;
-    A.mp_desc = mp_desc; A.mp_obs = mp_obs;
-    A.g = GridB{gb.minX, gb.minY, gb.invW, gb.invH};
-    A.slot_mp = cur_mp; A.th = th; A.mode = mode; A.checkOri = checkOri; A.nmatches = nmatches;
-    A.dmax = dist_th < 0 ? 0 : std::min(dist_th + 1, 256);          // best only: "if(bestDist<=TH_HIGH)" (:2140), bestDist starts at 256: every listed candidate
+    win_frame(A, P.f);
+    A.dist_th = P.dist_th; A.q_ur = P.q_ur;
+    A.nq = P.nq; A.capq = std::max(P.nq, 1); A.qkps = P.q_kps; A.q_is_orb = P.q_is_orb; A.valid = P.valid; A.qf = P.uvs;
+    A.mp_desc = P.mp_desc; A.mp_obs = P.mp_obs;
+    A.g = P.g;
+    A.slot_mp = P.slots; A.th = P.th; A.mode = P.mode; A.checkOri = P.checkOri; A.nmatches = P.nmatches;
+    A.dmax = P.dist_th < 0 ? 0 : std::min(P.dist_th + 1, 256);      // best only: "if(bestDist<=TH_HIGH)" (:2140), bestDist starts at 256: every listed candidate
                                                                     // passes both tests, which phase 2's fixed point relies on
-    return launch_win<1>(c, A, 1, n_last, "search_proj_last");
+    return launch_win<1>(c, A, 1, P.nq, "search_proj_last");
 }
 
-int search_proj_map_dev(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const uint8_t* is_orb,
-                        int M, const uint8_t* in_view, const float4* mp_f4, const int32_t* level, const uint8_t* mp_desc,
-                        const uint8_t* mp_obs, const uint8_t* mp_is_orb, eorb_grid_bounds gb, int32_t* frame_mp, float th,
-                        float nnratio, int32_t* nmatches, const float* uright, const float* q_ur)
+int search_proj_map_dev(eorb_ctx* c, const ProjMapArgs& P)
 {
     WinArgs A{};
-    A.uright2 = uright; A.q_ur = q_ur;
-    A.kps2 = kps; A.n2 = n; A.cap2 = std::max(n, 1); A.desc2 = desc; A.dstride2 = stride; A.is_orb2 = is_orb;
-    A.nq = M; A.capq = std::max(M, 1); A.valid = in_view; A.qf = (const float*)mp_f4; A.qlevel = level;
-    A.mp_desc = mp_desc; A.mp_obs = mp_obs; A.mp_is_orb = mp_is_orb;
-    A.g = GridB{gb.minX, gb.minY, gb.invW, gb.invH};
-    A.slot_mp = frame_mp; A.th = th; A.nnratio = nnratio; A.nmatches = nmatches;
+    win_frame(A, P.f);
+    A.q_ur = P.q_ur;
+    A.nq = P.M; A.capq = std::max(P.M, 1); A.valid = P.in_view; A.qf = (const float*)P.qf; A.qlevel = P.level;
+    A.mp_desc = P.mp_desc; A.mp_obs = P.mp_obs; A.mp_is_orb = P.mp_is_orb;
+    A.g = P.g;
+    A.slot_mp = P.slots; A.th = P.th; A.nnratio = P.nnratio; A.nmatches = P.nmatches;
     // the second best rejects only while "bestDist > ratio * bestDist2" (:134) can hold for some bestDist <= TH_HIGH
-    A.dmax = std::min(256, first_dist(TH_HIGH + 1, [&](int d) { return !((float)TH_HIGH > nnratio * (float)d); }));
-    return launch_win<2>(c, A, 1, M, "search_proj_map");
+    A.dmax = std::min(256, first_dist(TH_HIGH + 1, [&](int d) { return !((float)TH_HIGH > P.nnratio * (float)d); }));
+    return launch_win<2>(c, A, 1, P.M, "search_proj_map");
 }
 
 
@@ -1453,7 +1456,8 @@ int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell)
     if (A.taken) {
         const size_t lds = 64 + (((size_t)A.n + 15) & ~(size_t)15);
         if (lds > 160 * 1024) return set_err(c, EORB_E_CAPACITY, "kf_radius_match: %d keypoints exceed the LDS flags", A.n);
-        hipFuncSetAttribute((const void*)kf_radius_seq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        int rc;
+        if ((rc = lds_optin(c, kOptKfRadius, (const void*)kf_radius_seq_kernel, 160 * 1024))) return rc;
         kf_radius_seq_kernel<<<1, 256, lds, c->stream>>>(A);
     } else {
         kf_radius_kernel<<<std::min((A.M + 3) / 4, 4096), 256, 0, c->stream>>>(A);
@@ -1682,9 +1686,10 @@ int bow_transform_dev(eorb_ctx* c, const uint8_t* d_desc, int n, int stride, con
     int P = 64; while (P < n) P <<= 1;
     const size_t lds = (size_t)P * 20;
     if (lds > 150 * 1024) return set_err(c, EORB_E_CAPACITY, "bow_transform: %d features exceed the LDS sort", n);
+    int rc;
+    if ((rc = lds_optin(c, kOptBowAssemble, (const void*)bow_assemble_kernel, 150 * 1024))) return rc;
     ProfScope ps(c, "bow_transform");
     bow_descend_kernel<<<(n + 3) / 4, 256, 0, c->stream>>>(d_desc, n, stride, V, V.L - levelsup, d_word_of, d_w_of, d_node_of);
-    hipFuncSetAttribute((const void*)bow_assemble_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     bow_assemble_kernel<<<1, 1024, lds, c->stream>>>(d_word_of, d_w_of, d_node_of, n, P, weighting, norm, d_bow_word, d_bow_val,
                                                      d_fv_node, d_fv_off, d_fv_idx, d_counts);
     EORB_LAUNCH_CHECK(c, "bow_transform kernels");
@@ -1876,7 +1881,6 @@ int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR
 // | level + 1: the reference's candidate order (cell ix, cell iy, insertion index) rides in the key for the tie-breaks, as in
 // win_key.  Descriptors are read from global memory (only those of window candidates).
 constexpr int kTcCells = kGridCols * kGridRows;
-constexpr int kTcMaxKps = 8192;                  // nL + nR: 16 B of LDS each next to the 2 x 3072 cell starts
 constexpr int32_t kTcObs = 1 << 30;              // slot state bit: the slot's map point has Observations() > 0
 
 
@@ -2100,12 +2104,8 @@ int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A)
     const int nT = A.nL + A.nR;
     if (nT > kTcMaxKps) return set_err(c, EORB_E_CAPACITY, "two-camera matcher: %d keypoints > %d", nT, kTcMaxKps);
     const size_t lds = (((size_t)2 * kTcCells * 4 + 15) & ~(size_t)15) + (size_t)nT * 16;
-    static bool attr[2] = {false, false};
-    if (!attr[kind]) {
-        EORB_HIP(c, hipFuncSetAttribute(kind ? (const void*)twocam_walk_kernel<1> : (const void*)twocam_walk_kernel<0>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-        attr[kind] = true;
-    }
+    int rc;
+    if ((rc = lds_optin(c, kOptTwocam + kind, kind ? (const void*)twocam_walk_kernel<1> : (const void*)twocam_walk_kernel<0>, 160 * 1024 - 2048))) return rc;
     ProfScope ps(c, kind ? "twocam_last" : "twocam_map");
     if (kind) twocam_walk_kernel<1><<<1, 256, lds, c->stream>>>(A);
     else twocam_walk_kernel<0><<<1, 256, lds, c->stream>>>(A);

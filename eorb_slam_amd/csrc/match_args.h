@@ -1,11 +1,33 @@
-// Argument blocks of the KeyFrame-side matchers, shared by match.hip (kernels) and eorb_fe.hip (C ABI).
+// Argument blocks and launchers of the matchers, shared by match.hip (kernels) and eorb_fe.hip (C ABI).
 #pragma once
 #include <stdint.h>
-#include "../../include/eorb_fe.h"
+#include "eorb_ctx.h"
 
 namespace eorb {
 
 struct GridB { float minX, minY, invW, invH; };
+inline GridB grid_b(const eorb_grid_bounds& gb) { return GridB{gb.minX, gb.minY, gb.invW, gb.invH}; }
+
+// a searched frame on the device; is_orb, uright: NULL without AKAZE features / outside the rectified-stereo configurations
+struct FrameDev { const eorb_keypoint* kps; int n; const uint8_t* desc; int stride; const uint8_t* is_orb; const float* uright; };
+
+// SearchByProjection(CurrentFrame, LastFrame / pKF) (match.hip launch_win<1>): per query keypoint its record uvs = (u, v, levelScale);
+// q_ur (stereo, with f.uright): the queries' right coordinates
+struct ProjLastArgs {
+    FrameDev f; GridB g;
+    const eorb_keypoint* q_kps; int nq; const uint8_t* q_is_orb; const uint8_t* valid; const float* uvs;
+    const uint8_t* mp_desc; const uint8_t* mp_obs; const float* q_ur;
+    float th; int mode, checkOri, dist_th; int32_t* slots; int32_t* nmatches;
+};
+
+// SearchByProjection(Frame, map points) (match.hip launch_win<2>): per map point its record qf = (projX, projY, viewCos, levelScale);
+// q_ur (stereo, with f.uright): mTrackProjXR
+struct ProjMapArgs {
+    FrameDev f; GridB g;
+    int M; const uint8_t* in_view; const float4* qf; const int32_t* level;
+    const uint8_t* mp_desc; const uint8_t* mp_obs; const uint8_t* mp_is_orb; const float* q_ur;
+    float th, nnratio; int32_t* slots; int32_t* nmatches;
+};
 
 // DBoW2::FeatureVector as CSR, device resident: node ids ascending, off[nn + 1], feature indices
 struct FeatVec { const uint32_t* nodes; const int32_t* off; const int32_t* idx; int nn; };
@@ -39,11 +61,6 @@ struct TriKbArgs {
     const float* sigma2_1;
 };
 
-// launchers (match.hip); fisheye: the frame holds nL left features, then right ones; K: the KannalaBrandt8 walk (K->T is the block)
-int search_bow_dev(eorb_ctx* c, const BowArgs& A);
-int search_bow_fisheye_dev(eorb_ctx* c, const BowArgs& A, int nL);
-int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K = nullptr);
-
 struct RadArgs {
     const eorb_keypoint* kps; int n; const uint8_t* desc; int stride; GridB g;
     const uint16_t* cell;                           // n: ix*48+iy or 0xFFFF (Frame::PosInGrid), from kf_cells_kernel
@@ -61,6 +78,7 @@ struct BowVoc {
 };
 
 // two-camera tracking matchers (match.hip twocam_walk_kernel): the searched frame holds nL left keypoints, then nR right ones
+constexpr int kTcMaxKps = 8192;                  // nL + nR: 16 B of LDS each next to the 2 x 3072 cell starts
 struct TcArgs {
     const eorb_keypoint* kps; int nL, nR; const uint8_t* desc; int stride; GridB g;
     int nq; const uint8_t* mp_desc; const uint8_t* mp_obs; float th; float nnratio;
@@ -73,5 +91,34 @@ struct TcArgs {
     int32_t* rec;                                // KIND 1: (slot << 5 | bin) of every match in order, 2 * nq entries
     int32_t* slots; int32_t* nmatches;
 };
+
+// ---- the launchers of match.hip: window matchers, node walks, two-camera frames (kind: 0 map points, 1 last frame), the rest ----
+int search_init_dev(eorb_ctx* c, int npairs,
+                    const eorb_keypoint* kps1, const int32_t* n1, size_t kp1_stride, const uint8_t* desc1, int dstride1, size_t desc1_slice,
+                    const uint8_t* is_orb1,
+                    const eorb_keypoint* kps2, const int32_t* n2, size_t kp2_stride, const uint8_t* desc2, int dstride2, size_t desc2_slice,
+                    const uint8_t* is_orb2, int cap1, int cap2,
+                    eorb_grid_bounds gb, float* prev_matched, int32_t* matches12, int windowSize, float nnratio,
+                    int checkOri, int32_t* nmatches);
+int search_proj_last_dev(eorb_ctx* c, const ProjLastArgs& P);
+int search_proj_map_dev(eorb_ctx* c, const ProjMapArgs& P);
+// fisheye: the frame holds nL left features, then right ones; K: the KannalaBrandt8 walk (K->T is the block)
+int search_bow_dev(eorb_ctx* c, const BowArgs& A);
+int search_bow_fisheye_dev(eorb_ctx* c, const BowArgs& A, int nL);
+int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K = nullptr);
+int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const eorb_keypoint* kps1,
+                      const eorb_keypoint* kps2, int n, const float* sig1, const float* sig2, float* out);
+int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A);
+int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR, int cap, int32_t* d_lap, int32_t* d_idx2,
+                     int32_t* d_kdist2, int32_t* d_cand, int32_t* d_dist2);
+int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell);
+int bow_transform_dev(eorb_ctx* c, const uint8_t* d_desc, int n, int stride, const BowVoc& V, int levelsup, int weighting, int norm,
+                      uint32_t* d_word_of, double* d_w_of, uint32_t* d_node_of, uint32_t* d_bow_word, double* d_bow_val,
+                      uint32_t* d_fv_node, int32_t* d_fv_off, int32_t* d_fv_idx, int32_t* d_counts);
+int window_match_dev(eorb_ctx* c, const uint8_t* d_q, int nq, int q_stride, const uint8_t* d_t, int t_stride, const int32_t* d_off,
+                     const int32_t* d_cand, int32_t* d_out);
+int distinctive_dev(eorb_ctx* c, const uint8_t* d_desc, const int32_t* d_offsets, int M, int32_t* d_best);
+int sort_response_dev(eorb_ctx* c, const eorb_keypoint* d_kps, int n, int32_t* d_perm);
+int bf_knn2_dev(eorb_ctx* c, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int32_t* d_idx2, int32_t* d_dist2);
 
 }  // namespace eorb

@@ -456,3 +456,240 @@ def test_argument_errors_and_empty_calls(fe, ctx):
                                                C.byref(F.gb), p(fm), 10.0, 100, 1, None, None, None, C.byref(nm)) == E_ARG               # no min_dist
     assert L.eorb_search_by_projection_kf_pose(h, p(F.kps), 16, p(F.desc), 32, None, C.byref(v), p(kps), 0, None, None, None, None, None, None,
                                                C.byref(F.gb), p(fm), 10.0, 100, 1, None, None, None, C.byref(nm)) == 0
+
+
+# ---- the marshalling contract of the projection matchers: empty sides, optional outputs, relocalisation slots ------------------------
+M_T, N_T = 64, 48
+SENT = 0x5A5A5A5A
+
+
+@functools.lru_cache(None)
+def _tiny():
+    """64 map points in front of the 346x260 camera of synth.map_scene (facing it, every predicted level inside the pyramid), 64
+    last-frame / KeyFrame keypoints at those levels, and a frame of 48 keypoints planted on the projections"""
+    s = synth.map_scene(41, M_T)
+    rng = np.random.default_rng(42)
+    fx, fy, cx, cy = s["cam"]
+    u = rng.uniform(20, W - 20, M_T); v = rng.uniform(20, H - 20, M_T); z = rng.uniform(2, 6, M_T)
+    Pc = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1)
+    pos = np.ascontiguousarray(((Pc - s["t"]) @ s["R"].astype(np.float64)).astype(F32))
+    PO = pos.astype(np.float64) - s["Ow"]
+    dist = np.linalg.norm(PO, axis=1)
+    normal = np.ascontiguousarray((PO / dist[:, None]).astype(F32))
+    max_dist = (dist * 1.2 ** rng.uniform(0.5, 6.5, M_T)).astype(F32); min_dist = (max_dist / F32(1.2 ** 7)).astype(F32)
+    kw = _view_kw(s, mbf=35.0)
+    kwr, _ = _right_kw(_view_kw(s))
+    args = (pos, normal, min_dist, max_dist)
+    _, (r,) = proj_ref.frustum(proj_ref.view(**kw), *args, cos_limit=0.5)
+    assert int(r["in_view"].sum()) >= 56
+    mp_desc = synth.random_descriptors(M_T, seed=43)
+    kps, desc, src = synth.planted_frame(r["in_view"], r["proj_xy"], r["level"], mp_desc, N_T, W, H, seed=44)
+    q_kps = synth.random_keypoints(M_T, W, H, nlevels=8, seed=45)
+    q_kps["octave"] = np.clip(r["level"], 0, 7)
+    ur = np.where(src >= 0, r["proj_xr"][np.maximum(src, 0)] + rng.uniform(-1, 1, N_T), -1.0).astype(F32)
+    l2r = np.full(N_T // 2, -1, np.int32); r2l = np.full(N_T - N_T // 2, -1, np.int32)
+    l2r[:6] = np.arange(6); r2l[:6] = np.arange(6)
+    return dict(kw=kw, kwr=kwr, args=args, r=r, mp_desc=mp_desc, mp_obs=np.ones(M_T, np.uint8), kps=kps, desc=desc, q_kps=q_kps, uright=ur,
+                l2r=l2r, r2l=r2l)
+
+
+def _caller_projected(fe, ctx, sc, gb):
+    """name -> call(n, M, slots, nm) of the five matchers whose projections the caller supplies (here: the frustum record)"""
+    L, h, p = ctx.L, ctx.h, fe._p
+    r = sc["r"]
+    fr = lambda n: (p(sc["kps"]), n, p(sc["desc"]), 32, None)
+    last = lambda n, M: (h, *fr(n), p(sc["q_kps"]), M, None, p(r["in_view"]), p(r["proj_xy"]), p(sc["mp_desc"]), p(sc["mp_obs"]), p(r["level_scale"]),
+                         C.byref(gb))
+    map_ = lambda n, M: (h, *fr(n), M, p(r["in_view"]), p(r["proj_xy"]), p(r["level"]), p(r["view_cos"]), p(sc["mp_desc"]), p(sc["mp_obs"]), None,
+                         p(r["level_scale"]), C.byref(gb))
+    return {
+        "last": lambda n, M, s, nm: L.eorb_search_by_projection_last(*last(n, M), p(s), 7.0, 0, 1, C.byref(nm)),
+        "last_stereo": lambda n, M, s, nm: L.eorb_search_by_projection_last_stereo(*last(n, M), p(s), 7.0, 0, 1, p(sc["uright"]), p(r["proj_xr"]),
+                                                                                 C.byref(nm)),
+        "kf": lambda n, M, s, nm: L.eorb_search_by_projection_kf(h, *fr(n), p(sc["q_kps"]), M, None, p(r["in_view"]), p(r["proj_xy"]), p(r["level"]),
+                                                                 p(r["level_scale"]), p(sc["mp_desc"]), C.byref(gb), p(s), 10.0, 100, 1, C.byref(nm)),
+        "map": lambda n, M, s, nm: L.eorb_search_by_projection_map(*map_(n, M), p(s), 1.0, 0.8, C.byref(nm)),
+        "map_stereo": lambda n, M, s, nm: L.eorb_search_by_projection_map_stereo(*map_(n, M), p(s), 1.0, 0.8, p(sc["uright"]), p(r["proj_xr"]),
+                                                                               C.byref(nm)),
+    }
+
+
+@pytest.mark.parametrize("name", ["last", "last_stereo", "kf", "map", "map_stereo"])
+def test_empty_side_of_a_caller_projected_matcher(fe, ctx, name):
+    """either side empty: EORB_OK, *nmatches = 0, the slots untouched (kf with an empty frame: the entry's private copy of the slots is
+    empty too, and must not reach the NULL check in the caller's place)"""
+    sc = _tiny()
+    call = _caller_projected(fe, ctx, sc, fe.grid_bounds(W, H))[name]
+    for n, M in ((0, M_T), (N_T, 0), (0, 0)):
+        slots = np.full(N_T, SENT, np.int32); nm = C.c_int(-7)
+        assert call(n, M, slots, nm) == 0
+        assert nm.value == 0 and np.all(slots == SENT)
+    slots = np.full(N_T, -1, np.int32); nm = C.c_int(-7)                    # (and the full call finds the planted observations)
+    assert call(N_T, M_T, slots, nm) == 0 and nm.value >= 5 and nm.value == int((slots >= 0).sum())
+
+
+def _guarded(n, dt, k=1):
+    """an array of n x k between two 16-byte guards of 0xA5 -> (array view, check())"""
+    item = np.dtype(dt).itemsize * k
+    buf = np.full(32 + n * item, 0xA5, np.uint8)
+    a = buf[16:16 + n * item].view(dt)
+    a = a.reshape(n, k) if k > 1 else a
+
+    def intact():
+        return bool(np.all(buf[:16] == 0xA5) and np.all(buf[16 + n * item:] == 0xA5))
+    return a, intact
+
+
+def _fused(fe, ctx, sc, gb):
+    """name -> call(n, slots, want) of the four fused entries over all M_T points: want = the set of optional outputs to pass.
+    -> (rc, nmatches, n_in_view or None, dict of the guarded outputs, their guards)"""
+    L, h, p = ctx.L, ctx.h, fe._p
+    v = fe.view(**sc["kw"]); va, _ = fe._views([v, fe.view(**sc["kwr"])])
+    A = [p(a) for a in sc["args"]]
+    nL = N_T // 2
+
+    def frustum_recs(nviews, want):
+        recs = (fe._lib.FrustumOut * nviews)(); outs = []; guards = []
+        for i in range(nviews):
+            d = {}
+            for name, dt, k in fe._FRUSTUM_FIELDS:
+                if want is True or name in want:
+                    d[name], g = _guarded(M_T, dt, k); guards.append(g)
+                    setattr(recs[i], name, d[name].ctypes.data)
+            outs.append(d)
+        return recs, outs, guards
+
+    def local(n, slots, want):
+        recs, outs, guards = frustum_recs(1, want) if want else (None, [{}], [])
+        nm, nv = C.c_int(-7), C.c_int(-7)
+        rc = L.eorb_search_local_points(h, p(sc["kps"]), n, p(sc["desc"]), 32, None, C.byref(v), M_T, *A, None, None, 0.5, p(sc["mp_desc"]),
+                                        p(sc["mp_obs"]), C.byref(gb), p(slots), 1.0, 0.8, None, 0, 0.0, recs, C.byref(nv), C.byref(nm))
+        return rc, nm.value, nv.value, outs[0], guards
+
+    def local_fisheye(n, slots, want):
+        recs, outs, guards = frustum_recs(2, want) if want else (None, [{}, {}], [])
+        nm, nv = C.c_int(-7), C.c_int(-7)
+        l, r_ = (nL, n - nL) if n else (0, 0)
+        rc = L.eorb_search_local_points_fisheye(h, p(sc["kps"]), l, r_, p(sc["desc"]), 32, p(sc["l2r"]), p(sc["r2l"]), va, M_T, *A, None, 0.5,
+                                                p(sc["mp_desc"]), p(sc["mp_obs"]), C.byref(gb), p(slots), 1.0, 0.8, 0, 0.0, recs, C.byref(nv),
+                                                C.byref(nm))
+        return rc, nm.value, nv.value, {f"{k}{i}": a for i, d in enumerate(outs) for k, a in d.items()}, guards
+
+    def pose(kf):
+        def call(n, slots, want):
+            want = ("valid", "uv", "level")[:3 if kf else 2] if want is True else want
+            d = {}; guards = []
+            for name, dt, k in (("valid", np.uint8, 1), ("uv", F32, 2), ("level", np.int32, 1)):
+                if name in want:
+                    d[name], g = _guarded(M_T, dt, k); guards.append(g)
+            nm = C.c_int(-7)
+            head = (h, p(sc["kps"]), n, p(sc["desc"]), 32, None, C.byref(v), p(sc["q_kps"]), M_T, None, A[0])
+            if kf:
+                rc = L.eorb_search_by_projection_kf_pose(*head, A[2], A[3], None, p(sc["mp_desc"]), C.byref(gb), p(slots), 10.0, 100, 1,
+                                                         p(d.get("valid")), p(d.get("uv")), p(d.get("level")), C.byref(nm))
+            else:
+                rc = L.eorb_search_by_projection_last_pose(*head, None, p(sc["mp_desc"]), p(sc["mp_obs"]), C.byref(gb), p(slots), 7.0, 0, 1, None,
+                                                           p(d.get("valid")), p(d.get("uv")), C.byref(nm))
+            return rc, nm.value, None, d, guards
+        return call
+    return {"local": local, "local_fisheye": local_fisheye, "last_pose": pose(False), "kf_pose": pose(True)}
+
+
+def _projection_only(fe, ctx, sc, name):
+    """what the projector's own entry point gives for the fused entry `name`: (n_in_view or None, dict keyed like _fused's outputs)"""
+    v = fe.view(**sc["kw"])
+    if name == "local":
+        return fe.isInFrustum(v, *sc["args"], viewingCosLimit=0.5, ctx=ctx)
+    if name == "local_fisheye":
+        n, outs = fe.isInFrustum([v, fe.view(**sc["kwr"])], *sc["args"], viewingCosLimit=0.5, ctx=ctx)
+        return n, {f"{k}{i}": a for i, d in enumerate(outs) for k, a in d.items()}
+    if name == "last_pose":
+        return None, fe.ProjectLastFrame(v, sc["args"][0], sc["q_kps"], ctx=ctx)
+    return None, fe.ProjectKeyFramePoints(v, sc["args"][0], sc["args"][2], sc["args"][3], ctx=ctx)
+
+
+@pytest.mark.parametrize("name", ["local", "local_fisheye", "last_pose", "kf_pose"])
+def test_empty_side_of_a_fused_entry(fe, ctx, name):
+    sc = _tiny()
+    gb = fe.grid_bounds(W, H)
+    L, h, p = ctx.L, ctx.h, fe._p
+    # queries but an empty frame: the projection still runs and is delivered, nmatches = 0, the slots stay
+    slots = np.full(N_T, SENT if "fisheye" not in name else -3, np.int32)
+    rc, nm, nv, got, guards = _fused(fe, ctx, sc, gb)[name](0, slots, True)
+    wn, want = _projection_only(fe, ctx, sc, name)
+    assert rc == 0 and nm == 0 and nv == wn and np.all(slots == slots[0]) and all(g() for g in guards)
+    assert len(got) >= 2
+    for k, a in got.items():
+        assert a.tobytes() == want[k].tobytes(), k
+    assert wn is None or wn >= 56
+    # no queries: EORB_OK, counts 0, nothing written
+    v = fe.view(**sc["kw"]); va, _ = fe._views([v, fe.view(**sc["kwr"])])
+    sent = np.full(16, 77, np.uint8)
+    out = (fe._lib.FrustumOut * 2)()
+    for o in out:
+        o.in_view = sent.ctypes.data; o.reason = sent.ctypes.data
+    slots = np.full(N_T, SENT if "fisheye" not in name else -3, np.int32)
+    nmc, nvc = C.c_int(-7), C.c_int(-7)
+    fr = (p(sc["kps"]), N_T, p(sc["desc"]), 32, None)
+    if name == "local":
+        rc = L.eorb_search_local_points(h, *fr, C.byref(v), 0, None, None, None, None, None, None, 0.5, None, None, C.byref(gb), p(slots), 1.0, 0.8,
+                                        None, 0, 0.0, out, C.byref(nvc), C.byref(nmc))
+    elif name == "local_fisheye":
+        rc = L.eorb_search_local_points_fisheye(h, p(sc["kps"]), N_T // 2, N_T - N_T // 2, p(sc["desc"]), 32, p(sc["l2r"]), p(sc["r2l"]), va, 0,
+                                                None, None, None, None, None, 0.5, None, None, C.byref(gb), p(slots), 1.0, 0.8, 0, 0.0, out,
+                                                C.byref(nvc), C.byref(nmc))
+    elif name == "last_pose":
+        nvc.value = 0
+        rc = L.eorb_search_by_projection_last_pose(h, *fr, C.byref(v), None, 0, None, None, None, None, None, C.byref(gb), p(slots), 7.0, 0, 1, None,
+                                                   p(sent), p(sent), C.byref(nmc))
+    else:
+        nvc.value = 0
+        rc = L.eorb_search_by_projection_kf_pose(h, *fr, C.byref(v), None, 0, None, None, None, None, None, None, C.byref(gb), p(slots), 10.0, 100, 1,
+                                                 p(sent), p(sent), p(sent), C.byref(nmc))
+    assert rc == 0 and nmc.value == 0 and nvc.value == 0 and np.all(slots == slots[0]) and np.all(sent == 77)
+
+
+def _subsets(names):
+    return [tuple(n for i, n in enumerate(names) if m >> i & 1) for m in range(1 << len(names))]
+
+
+@pytest.mark.parametrize("name", ["local", "local_fisheye", "last_pose", "kf_pose"])
+def test_optional_outputs_of_a_fused_entry(fe, ctx, name):
+    """any subset of the optional outputs: the same slots and counts, the given arrays as in the all-outputs call, nothing beyond them"""
+    sc = _tiny()
+    call = _fused(fe, ctx, sc, fe.grid_bounds(W, H))[name]
+    init = np.full(N_T, -1, np.int32); init[::7] = -2
+    full_slots = init.copy()
+    rc, nm, nv, full, guards = call(N_T, full_slots, True)
+    assert rc == 0 and nm >= 5 and nm == int((full_slots >= 0).sum()) and all(g() for g in guards)
+    cases = {"local": [(), ("in_view", "level"), ("proj_xr",)], "local_fisheye": [(), ("in_view", "level"), ("reason",)],
+             "last_pose": _subsets(("valid", "uv"))[:-1], "kf_pose": _subsets(("valid", "uv", "level"))[:-1]}[name]
+    for want in cases:
+        slots = init.copy()
+        rc, nm2, nv2, got, guards = call(N_T, slots, want)
+        assert rc == 0 and (nm2, nv2) == (nm, nv) and np.array_equal(slots, full_slots), want
+        assert all(g() for g in guards) and len(got) == len(want) * (2 if name == "local_fisheye" else 1)
+        for k, a in got.items():
+            assert a.tobytes() == full[k].tobytes(), (want, k)
+
+
+def test_relocalisation_slots_of_both_keyframe_searches(fe, ctx, oracle):
+    """slots holding -3, -2, -1 and map-point indices on entry: _kf (the caller projects) and _kf_pose give the oracle's result and
+    leave every slot that was not -1 as it was"""
+    sc = _tiny()
+    v = fe.view(**sc["kw"])
+    pos, _, min_dist, max_dist = sc["args"]
+    cm = np.full(N_T, -1, np.int32)
+    cm[0::6] = -2; cm[1::6] = -3; cm[2::6] = np.arange(len(cm[2::6])) * 5 % M_T
+    held = cm != -1
+    Cur = fe.FrameView(sc["kps"], sc["desc"], W, H)
+    pr = fe.ProjectKeyFramePoints(v, pos, min_dist, max_dist, ctx=ctx)
+    for th in (10.0, 3.0):
+        on, ocm = oracle.search_by_projection_kf(oracle.Frame(sc["kps"], sc["desc"], W, H), sc["q_kps"], None, pr["valid"], pr["uv"], pr["level"],
+                                                 pr["level_scale"], sc["mp_desc"], cm, th, 100, True)
+        gn, gcm = fe.ORBmatcher(0.9, True, ctx).SearchByProjectionKF(Cur, sc["q_kps"], None, pr["valid"], pr["uv"], pr["level"], pr["level_scale"],
+                                                                     sc["mp_desc"], cm, th, 100)
+        fn, fcm, *_ = fe.SearchByProjectionKFPose(Cur, v, sc["q_kps"], pos, min_dist, max_dist, sc["mp_desc"], cm, th, 100, ctx=ctx)
+        assert gn == on == fn and np.array_equal(gcm, ocm) and np.array_equal(fcm, ocm)
+        assert np.array_equal(gcm[held], cm[held]) and gn == int((gcm[~held] >= 0).sum())
+    assert on >= 5 and {-3, -2}.issubset(set(cm.tolist())) and (cm >= 0).sum() >= 5

@@ -235,3 +235,70 @@ def test_matcher_errors(oracle, fe, ctx):
     rng = np.random.default_rng(1)
     fv = synth.feature_vector_of(rng.integers(0, 5, len(kps)), rng)
     assert code(fe.SearchByBoWFisheye, kps, desc, np.ones(len(kps), np.uint8), fv, kps, len(kps) + 1, desc, fv, 0.7, True, ctx) == E_ARG
+
+
+# ---- empty sides; a second device ------------------------------------------------------------------------------------------------
+def _synthetic_case(n, nL, M, seed):
+    """n random keypoints (nL of them left), M map points / last-frame points drawn from them; no stereo links"""
+    rng = np.random.default_rng(seed)
+    kps = synth.random_keypoints(n, W, H, nlevels=8, seed=seed + 1); desc = synth.random_descriptors(n, seed=seed + 2)
+    sf = synth.scale_tables(8, 1.2)[0]
+    left, right, mp_desc, mp_obs = synth.map_inputs(kps, nL, sf, rng, M, src=(kps, desc))
+    return dict(kps=kps, desc=desc, nL=nL, l2r=np.full(nL, -1, np.int32), r2l=np.full(n - nL, -1, np.int32), left=left, right=right,
+                mp_desc=mp_desc, mp_obs=mp_obs, sf=sf)
+
+
+def test_empty_sides_of_the_two_camera_matchers(fe, ctx):
+    """nL + nR == 0 or no queries: EORB_OK, *nmatches = 0, the slots untouched"""
+    import ctypes as C
+    n, nL, M = 32, 20, 16
+    sc = _synthetic_case(n, nL, M, 71)
+    L, h, p = ctx.L, ctx.h, fe._p
+    gb = fe.grid_bounds(W, H)
+    (a0, a1, a2, a3, a4), (b0, b1, b2, b3, b4) = sc["left"], sc["right"]
+    lk = sc["kps"][:M].copy(); z = np.zeros((M, 2), np.float32); ones = np.ones(M, np.uint8); ls = np.ones(M, np.float32)
+
+    def map_(l, r, m, slots, nm):
+        return L.eorb_search_by_projection_map_fisheye(h, p(sc["kps"]), l, r, p(sc["desc"]), 32, p(sc["l2r"]), p(sc["r2l"]), m, p(a0), p(a1), p(a2),
+                                                       p(a3), p(a4), p(b0), p(b1), p(b2), p(b3), p(b4), p(sc["mp_desc"]), p(sc["mp_obs"]),
+                                                       C.byref(gb), p(slots), 1.0, 0.8, C.byref(nm))
+
+    def last(l, r, m, slots, nm):
+        return L.eorb_search_by_projection_last_fisheye(h, p(sc["kps"]), l, r, p(sc["desc"]), 32, p(lk), m, p(ones), p(z), p(z), p(sc["mp_desc"]),
+                                                        p(ones), p(ls), C.byref(gb), p(slots), 7.0, 0, 1, C.byref(nm))
+    for call in (map_, last):
+        for l, r, m in ((0, 0, M), (nL, n - nL, 0), (0, 0, 0)):
+            slots = np.where(np.arange(n) % 2, -3, -2).astype(np.int32); before = slots.copy()     # (valid states: the slots are checked first)
+            nm = C.c_int(-7)
+            assert call(l, r, m, slots, nm) == 0
+            assert nm.value == 0 and np.array_equal(slots, before)
+        slots = np.full(n, M, np.int32); nm = C.c_int(-7)                    # validation still comes before the early return
+        assert call(nL, n - nL, 0, slots, nm) == E_ARG and nm.value == 0 and np.all(slots == M)
+
+
+def test_matchers_on_a_second_device(fe, ctx):
+    """a context on device 1 gives what device 0 gives: the two-camera walk with more than 64 KB of LDS (24 592 + 16 * 2600 bytes) and a
+    window matcher both need their dynamic-LDS opt-in on that device"""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("fewer than two visible devices")
+    c1 = fe.Context(device=1)
+    try:
+        n, nL, M = 2600, 1500, 64
+        sc = _synthetic_case(n, nL, M, 81)
+        gb = fe.grid_bounds(W, H)
+        fm = np.full(n, -1, np.int32); fm[::29] = -2
+        one = _synthetic_case(64, 64, M, 91)
+        F = fe.FrameView(one["kps"], one["desc"], W, H)
+        iv, pxy, lv, vc, ls = one["left"]
+        got = []
+        for c in (ctx, c1):
+            m = fe.ORBmatcher(0.8, True, c)
+            got.append((m.SearchByProjectionMapFisheye(sc["kps"], nL, sc["desc"], sc["l2r"], sc["r2l"], gb, sc["left"], sc["right"], sc["mp_desc"],
+                                                       sc["mp_obs"], fm, 3.0),
+                        m.SearchByProjectionMap(F, iv, pxy, lv, vc, one["mp_desc"], one["mp_obs"], np.full(64, -1, np.int32), 3.0, ls)))
+        for (n0, s0), (n1, s1) in zip(got[0], got[1]):
+            assert n0 == n1 and np.array_equal(s0, s1)
+        assert got[0][0][0] >= 10 and got[0][1][0] >= 10
+    finally:
+        c1.close()
