@@ -888,6 +888,85 @@ int eorb_normalize_minmax_u8(eorb_ctx* c, const float* img, int W, int H, uint8_
     return EORB_OK;
 }
 
+// ---- marshalling shared by the extraction entry points (eorb_orb_extract, eorb_frame_mono / _stereo / _fisheye, eorb_ev_slice_extract
+// and the tracked pair): check the image, queue it, reserve the result block, one download, copy out -----------------------------------
+// what every entry checks of its image (a pair passes NULL when either image is missing).  need_calib: eorb_frame_mono
+static int image_check(eorb_ctx* c, const char* who, const uint8_t* img, int W, int H, int stride, bool need_calib = false)
+{
+    if (!img || W <= 0 || H <= 0) return EORB_E_EMPTY;                 // _image.empty() -> -1 (:1096), trackedImage.empty() -> return (:1270, :1319)
+    const OrbState& o = c->orb;
+    if (!o.configured) return set_err(c, EORB_E_NOTCONF, "%s: eorb_orb_configure not called", who);
+    if (need_calib && !c->calib_set) return set_err(c, EORB_E_NOTCONF, "%s: eorb_set_calibration not called", who);
+    if (W != o.W || H != o.H) return set_err(c, EORB_E_ARG, "%s: image %dx%d does not match the configured %dx%d", who, W, H, o.W, o.H);
+    if (stride < W) return set_err(c, EORB_E_ARG, "%s: stride %d < width %d", who, stride, W);
+    return EORB_OK;
+}
+
+// the image -> arena, its rows packed.  allow_zero_copy (the one image of a call, up to 1 MiB): it is read once, by the pyramid's first
+// kernel, which then reads the pinned staging buffer itself (Arena::in_ptr): no upload in front of the launch
+static size_t image_in(Arena& A, const uint8_t* img, int W, int H, int stride, bool allow_zero_copy)
+{
+    static const int zc_env = [] { const char* e = getenv("EORB_IMAGE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
+    if (allow_zero_copy) A.host_inputs = zc_env != 0 && (size_t)W * H <= ((size_t)1 << 20);
+    return A.in2d(img, H, (size_t)W, (size_t)stride);
+}
+
+// the result block of an extraction of nimg images (one, or the two of a pair), contiguous:
+//   head | keypoints [nimg] | undistorted keypoints (eorb_frame_mono) | descriptors [nimg] | oob (one image)
+// every array holds max_out records per image; what a pair adds (matches, candidates) follows the block.  One head for all entries:
+// device code is handed &head->n[i] and so on
+struct ExtractHead {
+    int32_t n[2], mono[2];      // keypoints and monoIndex of each image
+    int32_t aux[2];             // [0]: eorb_frame_stereo's matches / eorb_frame_fisheye's candidates (fisheye_lowe_kernel reads n, mono, aux[0] as lap[0..4])
+    int32_t flag[2];            // internal capacity exceeded, one per extraction launch
+    float corners[8];           // eorb_frame_mono: the undistorted corners (0, 0), (W, 0), (0, H), (W, H)
+};
+struct ExtractOff { size_t head, kp, un, desc, oob, mo; int nimg; };
+static ExtractOff extract_reserve(Arena& A, int max_out, int nimg, bool undist = false)
+{
+    ExtractOff x{};
+    x.mo = (size_t)max_out; x.nimg = nimg;
+    x.head = A.reserve(sizeof(ExtractHead));
+    x.kp = A.reserve(sizeof(eorb_keypoint) * x.mo * nimg);
+    if (undist) x.un = A.reserve(sizeof(eorb_keypoint) * x.mo);
+    x.desc = A.reserve(32 * x.mo * nimg);
+    if (nimg == 1) x.oob = A.reserve(x.mo);
+    return x;
+}
+// end of the one download of a one-image call: the head always, the arrays up to the last one the caller takes and up to its capacity
+static size_t extract_end(const ExtractOff& x, int cap, bool kps, bool un, bool desc, bool oob)
+{
+    const size_t ncopy = std::min(x.mo, (size_t)std::max(cap, 0));
+    if (ncopy && oob) return x.oob + ncopy;
+    if (ncopy && desc) return x.desc + 32 * ncopy;
+    if (ncopy && un) return x.un + sizeof(eorb_keypoint) * ncopy;
+    if (ncopy && kps) return x.kp + sizeof(eorb_keypoint) * ncopy;
+    return x.head + sizeof(ExtractHead);
+}
+// after the download (h: its host view): a set flag (nflag: extraction launches of the call) and a count above cap are
+// EORB_E_CAPACITY and nothing is written; else every image's n records and its counters go to the caller (any pointer may be NULL)
+struct ExtractDst { eorb_keypoint* kps; uint8_t* desc; uint8_t* oob; int* n; int* mono; };
+static int extract_out(eorb_ctx* c, const char* who, const char* h, const ExtractOff& x, int cap, int nflag, const ExtractDst* dst, const ExtractHead** head = nullptr)
+{
+    const ExtractHead& hd = *(const ExtractHead*)(h + x.head);
+    if (head) *head = &hd;
+    // (reported here; the sticky word of the *_dev calls is not involved)
+    if (nflag == 1 && hd.flag[0]) return set_err(c, EORB_E_CAPACITY, "%s: internal capacity exceeded (flag %d)", who, hd.flag[0]);
+    if (nflag == 2 && (hd.flag[0] || hd.flag[1])) return set_err(c, EORB_E_CAPACITY, "%s: internal capacity exceeded (flags %d, %d)", who, hd.flag[0], hd.flag[1]);
+    if (x.nimg == 1 && hd.n[0] > cap) return set_err(c, EORB_E_CAPACITY, "%s: %d keypoints > caller capacity %d", who, hd.n[0], cap);
+    if (x.nimg == 2 && (hd.n[0] > cap || hd.n[1] > cap)) return set_err(c, EORB_E_CAPACITY, "%s: %d / %d keypoints > caller capacity %d", who, hd.n[0], hd.n[1], cap);
+    for (int i = 0; i < x.nimg; i++) {
+        const ExtractDst& d = dst[i];
+        const size_t n = (size_t)std::max(hd.n[i], 0);
+        if (d.kps && n) memcpy(d.kps, h + x.kp + sizeof(eorb_keypoint) * x.mo * i, sizeof(eorb_keypoint) * n);
+        if (d.desc && n) memcpy(d.desc, h + x.desc + 32 * x.mo * i, 32 * n);
+        if (d.oob && n) memcpy(d.oob, h + x.oob, n);
+        if (d.n) *d.n = hd.n[i];
+        if (d.mono) *d.mono = hd.mono[i];
+    }
+    return EORB_OK;
+}
+
 // ---- the L1 image builder's per-chunk path, one call per chunk (src/Event/EvImBuilder.cpp:1300-1515) ----------------------------
 // resolveMinMaxVals' start values (min 0, max -1e6: src/Event/EventConversion.cc:224-225) in the order-preserving encoding of the
 // gather kernels' atomics (enc_f32), uploaded with a call's events instead of being written by a kernel
@@ -925,25 +1004,26 @@ int eorb_ev_slice_extract(eorb_ctx* c, const eorb_event* ev, const eorb_raw_even
     if (!(sigma > 0.f)) return set_err(c, EORB_E_ARG, "ev_slice_extract: sigma must be > 0");
     fe_enter(c);
     const int W = o.W, H = o.H;
-    const size_t npix = (size_t)W * H, mo = (size_t)o.max_out;
+    const size_t npix = (size_t)W * H;
     int rc, is_raw = 0;
     Arena A(c);
     std::vector<eorb_event16> packed;
     size_t o_ev = 0;
     if ((rc = slice_events_in(c, A, ev, raw, n, packed, &o_ev, &is_raw, "ev_slice_extract"))) return rc;
     // the running extremes travel initialised with the events (no launch for them); device-only: float image; outputs, contiguous:
-    // u8 image | {n, mono, flag, pad} | keypoints | descriptors | oob
+    // u8 image | the extraction's result block
     // a live slice (the binning-free form reads every event once, in ev_pre_kernel): the events stay in pinned host memory and the
     // extremes are initialised by that kernel -- no copy in front of the first launch
     static const int zc_env = [] { const char* e = getenv("EORB_SLICE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
     const bool zc = zc_env != 0 && n > 0 && n <= 16384 && c->dbg_gather_form == 0;
     A.host_inputs = zc;
     const size_t o_mm = zc ? A.reserve(sizeof(kMinMaxPreset)) : A.in(kMinMaxPreset, sizeof(kMinMaxPreset)), o_f32 = A.reserve(sizeof(float) * npix);
-    const size_t o_u8 = A.reserve(npix), o_n = A.reserve(16), o_kp = A.reserve(sizeof(eorb_keypoint) * mo), o_desc = A.reserve(32 * mo), o_oob = A.reserve(mo);
+    const size_t o_u8 = A.reserve(npix);
+    const ExtractOff X = extract_reserve(A, o.max_out, 1);
     if ((rc = A.upload())) return rc;
     int64_t offs[2] = {0, (int64_t)n};
     uint8_t* d_u8 = A.dev<uint8_t>(o_u8);
-    int32_t* dn = A.dev<int32_t>(o_n);
+    ExtractHead* hd = A.dev<ExtractHead>(X.head);
     // EvImConverter::ev2im_gauss(l1Evs, W, H, sigma) :1345 (pol = false, normalized = true)
     // (the normalisation to u8 is left to the extraction's first kernel: one launch less)
     c->mm_preset = !zc;
@@ -951,34 +1031,26 @@ int eorb_ev_slice_extract(eorb_ctx* c, const eorb_event* ev, const eorb_raw_even
     A.inputs_done();
     // makeFrame :1348 -> EvFrame ctor -> ORBextractor::operator() (EventFrame.cpp:220)
     c->pyr0_f32 = A.dev<float>(o_f32); c->pyr0_mm = A.dev<uint32_t>(o_mm);
-    if ((rc = orb_extract_dev(c, d_u8, W, npix, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(o_kp), A.dev<uint8_t>(o_desc), A.dev<uint8_t>(o_oob),
-                              dn, dn + 1, dn + 2))) return rc;
-    if ((rc = ensure(c, c->l1_ref_img, npix)) || (rc = ensure(c, c->l1_ref_pts, sizeof(float) * 2 * mo))) return rc;
+    if ((rc = orb_extract_dev(c, d_u8, W, npix, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(X.kp), A.dev<uint8_t>(X.desc), A.dev<uint8_t>(X.oob),
+                              hd->n, hd->mono, hd->flag))) return rc;
+    if ((rc = ensure(c, c->l1_ref_img, npix)) || (rc = ensure(c, c->l1_ref_pts, sizeof(float) * 2 * X.mo))) return rc;
     c->l1_nref = -1; c->l1_W = W; c->l1_H = H; c->klt_ref_serial++;
     c->l1_img_off = o_u8; c->l1_img_gen = c->arena_gen;
-    const size_t ncopy = std::min<size_t>(mo, (size_t)std::max(cap, 0));
-    const size_t first = out_u8 ? o_u8 : o_n;
-    const size_t end = !ncopy ? o_n + 16 : (oob ? o_oob + ncopy : ((want_desc && desc) ? o_desc + 32 * ncopy : (kps ? o_kp + sizeof(eorb_keypoint) * ncopy : o_n + 16)));
+    const size_t first = out_u8 ? o_u8 : X.head;
     const char* h;
-    if ((rc = A.download_begin(first, end - first))) return rc;
+    if ((rc = A.download_begin(first, extract_end(X, cap, kps, false, want_desc && desc, oob) - first))) return rc;
     // ELK_Tracker::setRefImage(image, keypoints) (:1363 init -> KLT_Tracker.cpp:22-46): the image and its points stay on the device --
     // queued behind the download, which does not wait for them (the next call on the stream is ordered behind them)
     EORB_HIP(c, hipMemcpyAsync(c->l1_ref_img.p, d_u8, npix, hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = ev_kp_points_dev(c, A.dev<eorb_keypoint>(o_kp), dn, (int)mo, (float*)c->l1_ref_pts.p))) return rc;
+    if ((rc = ev_kp_points_dev(c, A.dev<eorb_keypoint>(X.kp), hd->n, (int)X.mo, (float*)c->l1_ref_pts.p))) return rc;
     if ((rc = A.download_wait(&h))) return rc;
-    const int32_t* hn = (const int32_t*)(h + o_n);
-    if (hn[2]) return set_err(c, EORB_E_CAPACITY, "ev_slice_extract: internal capacity exceeded (flag %d)", hn[2]);
-    c->l1_nref = hn[0];
-    if (out_u8) memcpy(out_u8, h + o_u8, npix);
-    if (hn[0] > cap) return set_err(c, EORB_E_CAPACITY, "ev_slice_extract: %d keypoints > caller capacity %d", hn[0], cap);
-    if (hn[0] > 0) {
-        if (kps) memcpy(kps, h + o_kp, sizeof(eorb_keypoint) * (size_t)hn[0]);
-        if (want_desc && desc) memcpy(desc, h + o_desc, 32 * (size_t)hn[0]);
-        if (oob) memcpy(oob, h + o_oob, (size_t)hn[0]);
+    const ExtractHead& got = *(const ExtractHead*)(h + X.head);
+    if (!got.flag[0]) {                                   // the reference frame and the image stand whatever the caller's capacity is
+        c->l1_nref = got.n[0];
+        if (out_u8) memcpy(out_u8, h + o_u8, npix);
     }
-    if (n_out) *n_out = hn[0];
-    if (mono_index) *mono_index = hn[1];
-    return EORB_OK;
+    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
+    return extract_out(c, "ev_slice_extract", h, X, cap, 1, &dst);
 }
 
 int eorb_ev_slice_track(eorb_ctx* c, const eorb_event* ev, const eorb_raw_event* raw, size_t n, float sigma, const eorb_klt_params* klt,
@@ -1198,44 +1270,22 @@ int eorb_orb_extract(eorb_ctx* c, const uint8_t* img, int W, int H, int stride, 
 {
     if (!c) return EORB_E_ARG;
     if (n_out) *n_out = 0;
-    if (!img || W <= 0 || H <= 0) return EORB_E_EMPTY;                 // _image.empty() -> -1 (:1096)
-    OrbState& o = c->orb;
-    if (!o.configured) return set_err(c, EORB_E_NOTCONF, "eorb_orb_extract: not configured");
-    if (W != o.W || H != o.H) return set_err(c, EORB_E_ARG, "image %dx%d does not match the configured %dx%d", W, H, o.W, o.H);
-    if (stride < W) return set_err(c, EORB_E_ARG, "stride < width");
-    fe_enter(c);
     int rc;
-    const size_t mo = (size_t)o.max_out;
+    if ((rc = image_check(c, "orb_extract", img, W, H, stride))) return rc;
+    fe_enter(c);
     Arena A(c);
-    // the image is read once, by the pyramid's first kernel: it reads the pinned staging buffer itself (no upload in front of the launch)
-    static const int zc_env = [] { const char* e = getenv("EORB_IMAGE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
-    A.host_inputs = zc_env != 0 && (size_t)W * H <= ((size_t)1 << 20);
-    const size_t o_img = A.in2d(img, H, (size_t)W, (size_t)stride);
-    // outputs, contiguous: {n, mono, flag, pad} | keypoints | descriptors | oob
-    const size_t o_n = A.reserve(16), o_kp = A.reserve(sizeof(eorb_keypoint) * mo), o_desc = A.reserve(32 * mo), o_oob = A.reserve(mo);
+    const size_t o_img = image_in(A, img, W, H, stride, true);
+    const ExtractOff X = extract_reserve(A, c->orb.max_out, 1);
     if ((rc = A.upload())) return rc;
-    int32_t* dn = A.dev<int32_t>(o_n);
-    rc = orb_extract_dev(c, A.in_ptr<uint8_t>(o_img), W, (size_t)W * H, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(o_kp),
-                         A.dev<uint8_t>(o_desc), A.dev<uint8_t>(o_oob), dn, dn + 1, dn + 2);
+    ExtractHead* hd = A.dev<ExtractHead>(X.head);
+    rc = orb_extract_dev(c, A.in_ptr<uint8_t>(o_img), W, (size_t)W * H, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(X.kp),
+                         A.dev<uint8_t>(X.desc), A.dev<uint8_t>(X.oob), hd->n, hd->mono, hd->flag);
     A.inputs_done();
     if (rc) return rc;
-    // one copy back: counters always, the rest up to the caller's capacity
-    const size_t ncopy = std::min<size_t>(mo, (size_t)std::max(cap, 0));
-    const size_t end = !ncopy ? o_n + 16 : (oob ? o_oob + ncopy : ((want_desc && desc) ? o_desc + 32 * ncopy : (kps ? o_kp + sizeof(eorb_keypoint) * ncopy : o_n + 16)));
     const char* h;
-    if ((rc = A.download(o_n, end - o_n, &h))) return rc;
-    const int32_t* hn = (const int32_t*)(h + o_n);
-    if (hn[2])                                    // (reported here; the sticky word of the *_dev calls is not involved)
-        return set_err(c, EORB_E_CAPACITY, "orb_extract: internal capacity exceeded (flag %d)", hn[2]);
-    if (hn[0] > cap) return set_err(c, EORB_E_CAPACITY, "orb_extract: %d keypoints > caller capacity %d", hn[0], cap);
-    if (hn[0] > 0) {
-        if (kps) memcpy(kps, h + o_kp, sizeof(eorb_keypoint) * (size_t)hn[0]);
-        if (want_desc && desc) memcpy(desc, h + o_desc, 32 * (size_t)hn[0]);
-        if (oob) memcpy(oob, h + o_oob, (size_t)hn[0]);
-    }
-    if (n_out) *n_out = hn[0];
-    if (mono_index) *mono_index = hn[1];
-    return EORB_OK;
+    if ((rc = A.download(X.head, extract_end(X, cap, kps, false, want_desc && desc, oob) - X.head, &h))) return rc;
+    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
+    return extract_out(c, "orb_extract", h, X, cap, 1, &dst);
 }
 
 // Frame::Frame(imGray, ...) (src/Frame.cc:229-266): eorb_orb_extract with undistKeyPoints (:246-252) and ComputeImageBounds (:840-867)
@@ -1246,56 +1296,35 @@ int eorb_frame_mono(eorb_ctx* c, const uint8_t* img, int W, int H, int stride, i
 {
     if (!c) return EORB_E_ARG;
     if (n_out) *n_out = 0;
-    if (!img || W <= 0 || H <= 0) return EORB_E_EMPTY;
-    OrbState& o = c->orb;
-    if (!o.configured) return set_err(c, EORB_E_NOTCONF, "eorb_frame_mono: not configured");
-    if (!c->calib_set) return set_err(c, EORB_E_NOTCONF, "eorb_frame_mono: eorb_set_calibration not called");
-    if (W != o.W || H != o.H) return set_err(c, EORB_E_ARG, "image %dx%d does not match the configured %dx%d", W, H, o.W, o.H);
-    if (stride < W) return set_err(c, EORB_E_ARG, "stride < width");
-    fe_enter(c);
     int rc;
-    const size_t mo = (size_t)o.max_out;
+    if ((rc = image_check(c, "eorb_frame_mono", img, W, H, stride, true))) return rc;
+    fe_enter(c);
     Arena A(c);
-    static const int zc_env = [] { const char* e = getenv("EORB_IMAGE_ZERO_COPY"); return e ? atoi(e) : 1; }();
-    A.host_inputs = zc_env != 0 && (size_t)W * H <= ((size_t)1 << 20);
-    const size_t o_img = A.in2d(img, H, (size_t)W, (size_t)stride);
-    // outputs, contiguous: {n, mono, flag, pad, corners[4][2]} | keypoints | undistorted keypoints | descriptors | oob
-    const size_t o_n = A.reserve(48), o_kp = A.reserve(sizeof(eorb_keypoint) * mo), o_un = A.reserve(sizeof(eorb_keypoint) * mo),
-                 o_desc = A.reserve(32 * mo), o_oob = A.reserve(mo);
+    const size_t o_img = image_in(A, img, W, H, stride, true);
+    const ExtractOff X = extract_reserve(A, c->orb.max_out, 1, true);
     if ((rc = A.upload())) return rc;
-    int32_t* dn = A.dev<int32_t>(o_n);
-    rc = orb_extract_dev(c, A.in_ptr<uint8_t>(o_img), W, (size_t)W * H, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(o_kp),
-                         A.dev<uint8_t>(o_desc), A.dev<uint8_t>(o_oob), dn, dn + 1, dn + 2);
+    ExtractHead* hd = A.dev<ExtractHead>(X.head);
+    rc = orb_extract_dev(c, A.in_ptr<uint8_t>(o_img), W, (size_t)W * H, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(X.kp),
+                         A.dev<uint8_t>(X.desc), A.dev<uint8_t>(X.oob), hd->n, hd->mono, hd->flag);
     A.inputs_done();
     if (rc) return rc;
     const bool gate = c->calib_dev.gate != 0;
-    if ((rc = calib_frame_dev(c, A.dev<eorb_keypoint>(o_kp), dn, (int)mo, A.dev<eorb_keypoint>(o_un), (float*)(dn + 4), W, H))) return rc;
-    const size_t ncopy = std::min<size_t>(mo, (size_t)std::max(cap, 0));
-    const size_t end = !ncopy ? o_n + 48 : (oob ? o_oob + ncopy : ((want_desc && desc) ? o_desc + 32 * ncopy :
-                       ((kps_un && gate) ? o_un + sizeof(eorb_keypoint) * ncopy : ((kps || kps_un) ? o_kp + sizeof(eorb_keypoint) * ncopy : o_n + 48))));
+    if ((rc = calib_frame_dev(c, A.dev<eorb_keypoint>(X.kp), hd->n, (int)X.mo, A.dev<eorb_keypoint>(X.un), hd->corners, W, H))) return rc;
     const char* h;
-    if ((rc = A.download(o_n, end - o_n, &h))) return rc;
-    const int32_t* hn = (const int32_t*)(h + o_n);
-    if (hn[2]) return set_err(c, EORB_E_CAPACITY, "eorb_frame_mono: internal capacity exceeded (flag %d)", hn[2]);
-    if (hn[0] > cap) return set_err(c, EORB_E_CAPACITY, "eorb_frame_mono: %d keypoints > caller capacity %d", hn[0], cap);
-    if (hn[0] > 0) {
-        if (kps) memcpy(kps, h + o_kp, sizeof(eorb_keypoint) * (size_t)hn[0]);
-        if (kps_un) memcpy(kps_un, h + (gate ? o_un : o_kp), sizeof(eorb_keypoint) * (size_t)hn[0]);      // gate closed: vUndistKPts = vDistKPts
-        if (want_desc && desc) memcpy(desc, h + o_desc, 32 * (size_t)hn[0]);
-        if (oob) memcpy(oob, h + o_oob, (size_t)hn[0]);
-    }
+    if ((rc = A.download(X.head, extract_end(X, cap, kps || kps_un, kps_un && gate, want_desc && desc, oob) - X.head, &h))) return rc;
+    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
+    const ExtractHead* got;
+    if ((rc = extract_out(c, "eorb_frame_mono", h, X, cap, 1, &dst, &got))) return rc;
+    if (kps_un && got->n[0] > 0) memcpy(kps_un, h + (gate ? X.un : X.kp), sizeof(eorb_keypoint) * (size_t)got->n[0]);      // gate closed: vUndistKPts = vDistKPts
     if (bounds) {
         if (c->calib_bounds.gate) {                           // Frame.cc:855-858: std::min(a, b) = b < a ? b : a, std::max(a, b) = a < b ? b : a
-            float q[8];
-            memcpy(q, hn + 4, sizeof q);                      // corners (0, 0), (W, 0), (0, H), (W, H)
+            const float* q = got->corners;
             bounds[0] = (q[4] < q[0]) ? q[4] : q[0];
             bounds[1] = (q[2] < q[6]) ? q[6] : q[2];
             bounds[2] = (q[3] < q[1]) ? q[3] : q[1];
             bounds[3] = (q[5] < q[7]) ? q[7] : q[5];
         } else { bounds[0] = 0.0f; bounds[1] = (float)W; bounds[2] = 0.0f; bounds[3] = (float)H; }
     }
-    if (n_out) *n_out = hn[0];
-    if (mono_index) *mono_index = hn[1];
     return EORB_OK;
 }
 
@@ -1307,43 +1336,29 @@ int eorb_frame_stereo(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRight
 {
     if (!c) return EORB_E_ARG;
     if (nL) *nL = 0; if (nR) *nR = 0; if (nmatches) *nmatches = 0;
-    if (!imLeft || !imRight || W <= 0 || H <= 0) return EORB_E_EMPTY;
-    OrbState& o = c->orb;
-    if (!o.configured) return set_err(c, EORB_E_NOTCONF, "eorb_frame_stereo: not configured");
-    if (W != o.W || H != o.H || stride < W) return set_err(c, EORB_E_ARG, "eorb_frame_stereo: the images do not match the configured %dx%d", o.W, o.H);
+    int rc;
+    if ((rc = image_check(c, "eorb_frame_stereo", imLeft && imRight ? imLeft : nullptr, W, H, stride))) return rc;
     if (!(mb > 0.f) || !(mbf > 0.f)) return set_err(c, EORB_E_ARG, "eorb_frame_stereo: baseline %.4f, bf %.4f", mb, mbf);
     fe_enter(c);
-    int rc;
-    const size_t mo = (size_t)o.max_out;
     Arena A(c);
-    const size_t o_imL = A.in2d(imLeft, H, (size_t)W, (size_t)stride), o_imR = A.in2d(imRight, H, (size_t)W, (size_t)stride);
-    // outputs, contiguous: {n[2], mono[2], flag, matches, pad} | keypoints [2] | descriptors [2] | uRight | depth | (norms)
-    const size_t o_n = A.reserve(32), o_kp = A.reserve(sizeof(eorb_keypoint) * mo * 2), o_desc = A.reserve(32 * mo * 2);
-    const size_t o_ur = A.reserve(sizeof(float) * mo), o_dp = A.reserve(sizeof(float) * mo), o_sad = A.reserve(sizeof(int32_t) * mo);
+    const size_t o_imL = image_in(A, imLeft, W, H, stride, false), o_imR = image_in(A, imRight, W, H, stride, false);
+    // outputs, contiguous: the result block of the pair | uRight | depth | (norms)
+    const ExtractOff X = extract_reserve(A, c->orb.max_out, 2);
+    const size_t o_ur = A.reserve(sizeof(float) * X.mo), o_dp = A.reserve(sizeof(float) * X.mo), o_sad = A.reserve(sizeof(int32_t) * X.mo);
     if ((rc = A.upload())) return rc;
-    int32_t* dn = A.dev<int32_t>(o_n);
-    rc = orb_extract_dev(c, A.dev<uint8_t>(o_imL), W, o_imR - o_imL, 2, 0, 0, 1, A.dev<eorb_keypoint>(o_kp), A.dev<uint8_t>(o_desc), nullptr, dn, dn + 2, dn + 4);
+    ExtractHead* hd = A.dev<ExtractHead>(X.head);
+    rc = orb_extract_dev(c, A.dev<uint8_t>(o_imL), W, o_imR - o_imL, 2, 0, 0, 1, A.dev<eorb_keypoint>(X.kp), A.dev<uint8_t>(X.desc), nullptr, hd->n, hd->mono, hd->flag);
     if (rc) return rc;
-    if ((rc = stereo_match_dev(c, A.dev<eorb_keypoint>(o_kp), A.dev<uint8_t>(o_desc), dn, mb, mbf, A.dev<float>(o_ur), A.dev<float>(o_dp),
-                               A.dev<int32_t>(o_sad), dn + 5))) return rc;
+    if ((rc = stereo_match_dev(c, A.dev<eorb_keypoint>(X.kp), A.dev<uint8_t>(X.desc), hd->n, mb, mbf, A.dev<float>(o_ur), A.dev<float>(o_dp),
+                               A.dev<int32_t>(o_sad), hd->aux))) return rc;
     const char* h;
-    if ((rc = A.download(o_n, o_sad - o_n, &h))) return rc;
-    const int32_t* hn = (const int32_t*)(h + o_n);
-    if (hn[4]) return set_err(c, EORB_E_CAPACITY, "eorb_frame_stereo: internal capacity exceeded (flag %d)", hn[4]);
-    if (hn[0] > cap || hn[1] > cap) return set_err(c, EORB_E_CAPACITY, "eorb_frame_stereo: %d / %d keypoints > caller capacity %d", hn[0], hn[1], cap);
-    if (hn[0] > 0) {
-        if (kpsL) memcpy(kpsL, h + o_kp, sizeof(eorb_keypoint) * (size_t)hn[0]);
-        if (descL) memcpy(descL, h + o_desc, 32 * (size_t)hn[0]);
-        if (uRight) memcpy(uRight, h + o_ur, sizeof(float) * (size_t)hn[0]);
-        if (depth) memcpy(depth, h + o_dp, sizeof(float) * (size_t)hn[0]);
-    }
-    if (hn[1] > 0) {
-        if (kpsR) memcpy(kpsR, h + o_kp + sizeof(eorb_keypoint) * mo, sizeof(eorb_keypoint) * (size_t)hn[1]);
-        if (descR) memcpy(descR, h + o_desc + 32 * mo, 32 * (size_t)hn[1]);
-    }
-    if (nL) *nL = hn[0];
-    if (nR) *nR = hn[1];
-    if (nmatches) *nmatches = hn[5];
+    if ((rc = A.download(X.head, o_sad - X.head, &h))) return rc;
+    const ExtractDst dst[2] = {{kpsL, descL, nullptr, nL, nullptr}, {kpsR, descR, nullptr, nR, nullptr}};
+    const ExtractHead* got;
+    if ((rc = extract_out(c, "eorb_frame_stereo", h, X, cap, 1, dst, &got))) return rc;      // (one launch for both images: one flag)
+    if (uRight && got->n[0] > 0) memcpy(uRight, h + o_ur, sizeof(float) * (size_t)got->n[0]);
+    if (depth && got->n[0] > 0) memcpy(depth, h + o_dp, sizeof(float) * (size_t)got->n[0]);
+    if (nmatches) *nmatches = got->aux[0];
     return EORB_OK;
 }
 
@@ -1351,15 +1366,13 @@ static int tracked_common(eorb_ctx* c, const uint8_t* img, int W, int H, int str
                           int n, int mode, const uint8_t* ref, uint8_t* desc, uint8_t* oob)
 {
     if (!c) return EORB_E_ARG;
-    if (!img || W <= 0 || H <= 0) return EORB_E_EMPTY;                 // trackedImage.empty() -> return (:1270, :1319)
-    OrbState& o = c->orb;
-    if (!o.configured) return set_err(c, EORB_E_NOTCONF, "tracked descriptors: not configured");
-    if (W != o.W || H != o.H || stride < W || n < 0) return set_err(c, EORB_E_ARG, "tracked descriptors: bad image/arguments");
+    int rc;
+    if ((rc = image_check(c, "tracked descriptors", img, W, H, stride))) return rc;
+    if (n < 0) return set_err(c, EORB_E_ARG, "tracked descriptors: %d keypoints", n);
     if (n == 0) return EORB_OK;
     fe_enter(c);
-    int rc;
     Arena A(c);
-    const size_t o_img = A.in2d(img, H, (size_t)W, (size_t)stride), o_ref = A.in(ref, ref ? 32 * (size_t)n : 0);
+    const size_t o_img = image_in(A, img, W, H, stride, false), o_ref = A.in(ref, ref ? 32 * (size_t)n : 0);
     // keypoints (in / out: mode 1 writes their octaves) | outputs of mode 0, contiguous: descriptors | oob
     const size_t o_kp = A.in(kps_in, sizeof(eorb_keypoint) * (size_t)n);
     const size_t o_desc = A.reserve(32 * (size_t)n), o_oob = A.reserve((size_t)n);
@@ -2127,53 +2140,38 @@ int eorb_frame_fisheye(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRigh
 {
     if (!c) return EORB_E_ARG;
     if (nL) *nL = 0; if (nR) *nR = 0; if (monoLeft) *monoLeft = 0; if (monoRight) *monoRight = 0; if (ncand) *ncand = 0;
-    if (!imLeft || !imRight || W <= 0 || H <= 0) return EORB_E_EMPTY;
-    OrbState& o = c->orb;
-    if (!o.configured) return set_err(c, EORB_E_NOTCONF, "eorb_frame_fisheye: not configured");
-    if (W != o.W || H != o.H || stride < W || cap < 0) return set_err(c, EORB_E_ARG, "eorb_frame_fisheye: the images do not match the configured %dx%d", o.W, o.H);
-    fe_enter(c);
     int rc;
-    const size_t mo = (size_t)o.max_out;
+    if ((rc = image_check(c, "eorb_frame_fisheye", imLeft && imRight ? imLeft : nullptr, W, H, stride))) return rc;
+    if (cap < 0) return set_err(c, EORB_E_ARG, "eorb_frame_fisheye: capacity %d", cap);
+    fe_enter(c);
     Arena A(c);
-    const size_t o_imL = A.in2d(imLeft, H, (size_t)W, (size_t)stride), o_imR = A.in2d(imRight, H, (size_t)W, (size_t)stride);
-    // outputs, contiguous: {n[2], mono[2], candidates, flags[2]} | keypoints [2] | descriptors [2] | candidates | distances; then the
-    // knn scratch
-    const size_t o_n = A.reserve(64), o_kp = A.reserve(sizeof(eorb_keypoint) * mo * 2), o_desc = A.reserve(32 * mo * 2);
+    const size_t o_imL = image_in(A, imLeft, W, H, stride, false), o_imR = image_in(A, imRight, W, H, stride, false);
+    // outputs, contiguous: the result block of the pair | candidates | distances; then the knn scratch
+    const ExtractOff X = extract_reserve(A, c->orb.max_out, 2);
+    const size_t mo = X.mo;
     const size_t o_cand = A.reserve(sizeof(int32_t) * mo), o_d2 = A.reserve(2 * sizeof(int32_t) * mo);
     const size_t o_end = A.reserve(0);
     const size_t o_idx = A.reserve(2 * sizeof(int32_t) * mo), o_kd = A.reserve(2 * sizeof(int32_t) * mo);
     if ((rc = A.upload())) return rc;
-    int32_t* dn = A.dev<int32_t>(o_n);
-    EORB_HIP(c, hipMemsetAsync(dn, 0, 64, c->stream));
+    ExtractHead* hd = A.dev<ExtractHead>(X.head);
+    EORB_HIP(c, hipMemsetAsync(hd, 0, sizeof(ExtractHead), c->stream));       // (the candidates are counted by atomics)
     // ExtractORB(0, imLeft, mvLappingArea of mpCamera) and ExtractORB(1, imRight, mvLappingArea of mpCamera2) (Frame.cc:1124-1129):
     // two launches, each with its own lapping area
-    rc = orb_extract_dev(c, A.dev<uint8_t>(o_imL), W, 0, 1, lapL0, lapL1, 1, A.dev<eorb_keypoint>(o_kp), A.dev<uint8_t>(o_desc), nullptr, dn, dn + 2, dn + 5);
+    rc = orb_extract_dev(c, A.dev<uint8_t>(o_imL), W, 0, 1, lapL0, lapL1, 1, A.dev<eorb_keypoint>(X.kp), A.dev<uint8_t>(X.desc), nullptr, hd->n, hd->mono, hd->flag);
     if (rc) return rc;
-    rc = orb_extract_dev(c, A.dev<uint8_t>(o_imR), W, 0, 1, lapR0, lapR1, 1, A.dev<eorb_keypoint>(o_kp) + mo, A.dev<uint8_t>(o_desc) + 32 * mo,
-                         nullptr, dn + 1, dn + 3, dn + 6);
+    rc = orb_extract_dev(c, A.dev<uint8_t>(o_imR), W, 0, 1, lapR0, lapR1, 1, A.dev<eorb_keypoint>(X.kp) + mo, A.dev<uint8_t>(X.desc) + 32 * mo,
+                         nullptr, hd->n + 1, hd->mono + 1, hd->flag + 1);
     if (rc) return rc;
-    if ((rc = fisheye_lowe_dev(c, A.dev<uint8_t>(o_desc), A.dev<uint8_t>(o_desc) + 32 * mo, (int)mo, dn, A.dev<int32_t>(o_idx), A.dev<int32_t>(o_kd),
+    if ((rc = fisheye_lowe_dev(c, A.dev<uint8_t>(X.desc), A.dev<uint8_t>(X.desc) + 32 * mo, (int)mo, hd->n, A.dev<int32_t>(o_idx), A.dev<int32_t>(o_kd),
                                A.dev<int32_t>(o_cand), A.dev<int32_t>(o_d2)))) return rc;
     const char* h;
-    if ((rc = A.download(o_n, o_end - o_n, &h))) return rc;
-    const int32_t* hn = (const int32_t*)(h + o_n);
-    if (hn[5] || hn[6]) return set_err(c, EORB_E_CAPACITY, "eorb_frame_fisheye: internal capacity exceeded (flags %d, %d)", hn[5], hn[6]);
-    if (hn[0] > cap || hn[1] > cap) return set_err(c, EORB_E_CAPACITY, "eorb_frame_fisheye: %d / %d keypoints > caller capacity %d", hn[0], hn[1], cap);
-    if (hn[0] > 0) {
-        if (kpsL) memcpy(kpsL, h + o_kp, sizeof(eorb_keypoint) * (size_t)hn[0]);
-        if (descL) memcpy(descL, h + o_desc, 32 * (size_t)hn[0]);
-        if (right_idx) memcpy(right_idx, h + o_cand, sizeof(int32_t) * (size_t)hn[0]);
-        if (dist2) memcpy(dist2, h + o_d2, 2 * sizeof(int32_t) * (size_t)hn[0]);
-    }
-    if (hn[1] > 0) {
-        if (kpsR) memcpy(kpsR, h + o_kp + sizeof(eorb_keypoint) * mo, sizeof(eorb_keypoint) * (size_t)hn[1]);
-        if (descR) memcpy(descR, h + o_desc + 32 * mo, 32 * (size_t)hn[1]);
-    }
-    if (nL) *nL = hn[0];
-    if (nR) *nR = hn[1];
-    if (monoLeft) *monoLeft = hn[2];
-    if (monoRight) *monoRight = hn[3];
-    if (ncand) *ncand = hn[4];
+    if ((rc = A.download(X.head, o_end - X.head, &h))) return rc;
+    const ExtractDst dst[2] = {{kpsL, descL, nullptr, nL, monoLeft}, {kpsR, descR, nullptr, nR, monoRight}};
+    const ExtractHead* got;
+    if ((rc = extract_out(c, "eorb_frame_fisheye", h, X, cap, 2, dst, &got))) return rc;
+    if (right_idx && got->n[0] > 0) memcpy(right_idx, h + o_cand, sizeof(int32_t) * (size_t)got->n[0]);
+    if (dist2 && got->n[0] > 0) memcpy(dist2, h + o_d2, 2 * sizeof(int32_t) * (size_t)got->n[0]);
+    if (ncand) *ncand = got->aux[0];
     return EORB_OK;
 }
 

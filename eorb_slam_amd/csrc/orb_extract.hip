@@ -15,12 +15,15 @@
 //   blur_kernel         GaussianBlur(5x5, sigma 2, REFLECT_101) 8u Q8 separable     (:1141-1142)
 //   brief_kernel        computeOrbDescriptor (:108-157): 32 lanes per keypoint, 16 taps each
 //   assemble_kernel     output ordering of operator() (:1150-1173): scale, lapping-area back-fill
+//   describe_kernel     orient + brief + assemble of a keypoint in one launch, for a lapping area that holds none or all of them
+//   tracked_desc_kernel ComputeTrackedKPtsDesc (:1316-1363) / AssignKPtLevelByBestDesc (:1267-1314) on given keypoints
 #include "eorb_ctx.h"
 #include "dev_math.h"
 #include "orb_pattern.h"
 #include <math.h>
 #include <algorithm>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace eorb {
@@ -1152,27 +1155,26 @@ __global__ __launch_bounds__(kOctThreads) void octree_kernel(const DevGeom* __re
 }
 
 // ---------------------------------------------------------------------------------------------------
-// orientation: IC_Angle :77-104.  32 lanes per keypoint: lane = column u of the disc (-15 .. 15, one lane idle), walking the row pairs
-// +-v: consecutive lanes read consecutive bytes of a row (with a lane per ROW every load instruction of a wave touched 64 different
-// image lines).  Integer moments: the order of the sums is free.
-__global__ __launch_bounds__(256) void orient_kernel(const DevGeom* __restrict__ G, const uint8_t* __restrict__ pyr,
-                                                     const uint32_t* __restrict__ lvl_kp, const int32_t* __restrict__ lvl_cnt,
-                                                     float* __restrict__ kp_angle)
+// from an octree slot to an output record, 32 lanes per keypoint: what orient / brief / assemble / describe / tracked_desc are written with
+// slot gid < kp_total of a slice's level arrays -> (level, i); the slot holds a keypoint when i < cnt[level].
+// *before (when asked for) = keypoints of the lower levels = the emission index of the level's first keypoint (:1150-1173)
+__device__ __forceinline__ void kp_slot(const DevGeom* __restrict__ G, const int32_t* __restrict__ cnt, int gid, int& level, int& i, int* before = nullptr)
 {
-    const int slice = blockIdx.y;
-    const int gid = blockIdx.x * 8 + (threadIdx.x >> 5);       // keypoint slot in the slice's level arrays
+    level = 0;
+    if (before) *before = 0;
+    while (level + 1 < G->nlevels && gid >= G->lv[level + 1].kp_off) { if (before) *before += cnt[level]; level++; }
+    i = gid - G->lv[level].kp_off;
+}
+
+// the octree's record x | y << 12 | score << 24 in level coordinates: candidate coords are relative to minBorder (:889-893)
+__device__ __forceinline__ void kp_level_xy(uint32_t p, const LevelGeom& L, int& cx, int& cy) { cx = (int)(p & 0xfff) + L.minBX; cy = (int)((p >> 12) & 0xfff) + L.minBY; }
+
+// orientation: IC_Angle :77-104.  Lane (of the 32) = column u of the disc (-15 .. 15, one lane idle), walking the row pairs +-v: consecutive
+// lanes read consecutive bytes of a row (with a lane per ROW every load instruction of a wave touched 64 different image lines).
+// Integer moments: the order of the sums is free.  Every lane of the 32-group holds the result.
+__device__ __forceinline__ float ic_angle32(const DevGeom* __restrict__ G, const uint8_t* __restrict__ center, int step)
+{
     const int u = (int)(threadIdx.x & 31) - 15;                // -15 .. 16 (16: no column)
-    if (gid >= G->kp_total) return;
-    int level = 0;
-    while (level + 1 < G->nlevels && gid >= G->lv[level + 1].kp_off) level++;
-    const LevelGeom& L = G->lv[level];
-    const int i = gid - L.kp_off;
-    if (i >= lvl_cnt[slice * G->nlevels + level]) return;     // whole 32-lane group exits together
-    const uint32_t p = lvl_kp[(size_t)slice * G->kp_total + gid];
-    // keypoint in level coordinates: candidate coords are relative to minBorder (:889-893)
-    const int cx = (int)(p & 0xfff) + L.minBX, cy = (int)((p >> 12) & 0xfff) + L.minBY;
-    const uint8_t* center = pyr + (size_t)slice * G->pyr_bytes + L.buf_off + (size_t)(cy + G->edge) * L.bw + (cx + G->edge);
-    const int step = L.bw;
     const int au = u < 0 ? -u : u;
     int m_01 = 0, m_10 = 0;
     if (au <= 15) m_10 = u * (int)center[u];
@@ -1189,7 +1191,45 @@ __global__ __launch_bounds__(256) void orient_kernel(const DevGeom* __restrict__
         m_01 += __shfl_xor(m_01, d, 64);
         m_10 += __shfl_xor(m_10, d, 64);
     }
-    if ((threadIdx.x & 31) == 0) kp_angle[(size_t)slice * G->kp_total + gid] = dev_fast_atan2((float)m_01, (float)m_10);
+    return dev_fast_atan2((float)m_01, (float)m_10);
+}
+
+// the output record of operator() :1150-1173
+__device__ __forceinline__ eorb_keypoint kp_record(uint32_t p, const LevelGeom& L, int level, float scale, float angle)
+{
+    eorb_keypoint kp{};
+    kp.x = (float)(int)(p & 0xfff) + (float)L.minBX;
+    kp.y = (float)(int)((p >> 12) & 0xfff) + (float)L.minBY;
+    if (level != 0) { kp.x = kp.x * scale; kp.y = kp.y * scale; }       // keypoint.pt *= scale
+    kp.size = (float)L.patch_size;
+    kp.angle = angle;
+    kp.response = (float)(p >> 24);
+    kp.octave = level; kp.class_id = -1;
+    return kp;
+}
+
+// any lane of this thread's 32-lane half of the wave has `flag` set (all 64 lanes arrive together)
+__device__ __forceinline__ bool group32_any(bool flag)
+{
+    const uint64_t any = __ballot(flag);
+    return (((threadIdx.x >> 5) & 1) ? (uint32_t)(any >> 32) : (uint32_t)any) != 0;
+}
+
+__global__ __launch_bounds__(256) void orient_kernel(const DevGeom* __restrict__ G, const uint8_t* __restrict__ pyr,
+                                                     const uint32_t* __restrict__ lvl_kp, const int32_t* __restrict__ lvl_cnt,
+                                                     float* __restrict__ kp_angle)
+{
+    const int slice = blockIdx.y;
+    const int gid = blockIdx.x * 8 + (threadIdx.x >> 5);       // keypoint slot in the slice's level arrays
+    if (gid >= G->kp_total) return;
+    int level, i, cx, cy;
+    kp_slot(G, lvl_cnt + slice * G->nlevels, gid, level, i);
+    if (i >= lvl_cnt[slice * G->nlevels + level]) return;     // whole 32-lane group exits together
+    const LevelGeom& L = G->lv[level];
+    kp_level_xy(lvl_kp[(size_t)slice * G->kp_total + gid], L, cx, cy);
+    const uint8_t* center = pyr + (size_t)slice * G->pyr_bytes + L.buf_off + (size_t)(cy + G->edge) * L.bw + (cx + G->edge);
+    const float angle = ic_angle32(G, center, L.bw);
+    if ((threadIdx.x & 31) == 0) kp_angle[(size_t)slice * G->kp_total + gid] = angle;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1283,23 +1323,17 @@ __global__ __launch_bounds__(256) void brief_kernel(const DevGeom* __restrict__ 
     const int gid = blockIdx.x * 8 + (threadIdx.x >> 5);
     const int b = threadIdx.x & 31;
     if (gid >= G->kp_total) return;
-    int level = 0;
-    while (level + 1 < G->nlevels && gid >= G->lv[level + 1].kp_off) level++;
+    int level, i, cx, cy;
+    kp_slot(G, lvl_cnt + slice * G->nlevels, gid, level, i);
+    if (i >= lvl_cnt[slice * G->nlevels + level]) return;     // whole 32-lane group exits together
     const LevelGeom& L = G->lv[level];
-    const int i = gid - L.kp_off;
-    if (i >= lvl_cnt[slice * G->nlevels + level]) return;
-    const uint32_t p = lvl_kp[(size_t)slice * G->kp_total + gid];
-    const int cx = (int)(p & 0xfff) + L.minBX, cy = (int)((p >> 12) & 0xfff) + L.minBY;
+    kp_level_xy(lvl_kp[(size_t)slice * G->kp_total + gid], L, cx, cy);
     const uint8_t* img = blur + (size_t)slice * G->roi_bytes + L.roi_off;
     int oob = 0;
     const int val = brief_byte(img, L.w, L.h, cx, cy, kp_angle[(size_t)slice * G->kp_total + gid], b, oob);
     lvl_desc[((size_t)slice * G->kp_total + gid) * 32 + b] = (uint8_t)val;
-    const uint64_t anyoob = __ballot(oob != 0);
-    if (b == 0) {
-        const int half = (threadIdx.x >> 5) & 1;
-        const uint32_t m = half ? (uint32_t)(anyoob >> 32) : (uint32_t)anyoob;
-        lvl_oob[(size_t)slice * G->kp_total + gid] = m ? 1 : 0;
-    }
+    const bool anyoob = group32_any(oob != 0);
+    if (b == 0) lvl_oob[(size_t)slice * G->kp_total + gid] = anyoob ? 1 : 0;
 }
 
 // ORBextractor::ComputeTrackedKPtsDesc (:1316-1363) [mode 0] and AssignKPtLevelByBestDesc (:1267-1314) [mode 1]:
@@ -1314,28 +1348,26 @@ __global__ __launch_bounds__(256) void tracked_desc_kernel(const DevGeom* __rest
     const int b = threadIdx.x & 31;
     if (i >= n) return;
     const eorb_keypoint kp = kps[i];
-    const int half = (threadIdx.x >> 5) & 1;
+    // descriptor byte b of the keypoint on `level`
+    auto byte_at = [&](int level, int& oob) {
+        const LevelGeom& L = G->lv[level];
+        const float scale = 1.0f / G->sf[level];                                      // mvInvScaleFactor[level] (:436)
+        const int cx = dev_cvround(kp.x * scale), cy = dev_cvround(kp.y * scale);
+        return brief_byte(blur + L.roi_off, L.w, L.h, cx, cy, kp.angle, b, oob);
+    };
     if (mode == 0) {
         const int level = kp.octave;
         int val = 0, oob = 0;
-        if (level >= 0 && level < G->nlevels) {
-            const LevelGeom& L = G->lv[level];
-            const float scale = 1.0f / G->sf[level];                                  // mvInvScaleFactor[level] (:436)
-            const int cx = dev_cvround(kp.x * scale), cy = dev_cvround(kp.y * scale);
-            val = brief_byte(blur + L.roi_off, L.w, L.h, cx, cy, kp.angle, b, oob);
-        }
+        if (level >= 0 && level < G->nlevels) val = byte_at(level, oob);
         desc[(size_t)i * 32 + b] = (uint8_t)val;
-        const uint64_t anyoob = __ballot(oob != 0);
-        if (b == 0 && oobf) oobf[i] = (half ? (uint32_t)(anyoob >> 32) : (uint32_t)anyoob) ? 1 : 0;
+        const bool anyoob = group32_any(oob != 0);
+        if (b == 0 && oobf) oobf[i] = anyoob ? 1 : 0;
     } else {
         const int refb = ref_desc[(size_t)i * 32 + b];
         int minDist = 0x7fffffff, best = kp.octave;
         for (int level = 0; level < G->nlevels; level++) {
-            const LevelGeom& L = G->lv[level];
-            const float scale = 1.0f / G->sf[level];
-            const int cx = dev_cvround(kp.x * scale), cy = dev_cvround(kp.y * scale);
             int oob = 0;
-            const int val = brief_byte(blur + L.roi_off, L.w, L.h, cx, cy, kp.angle, b, oob);
+            const int val = byte_at(level, oob);
             int d = __popc((unsigned)(val ^ refb));
 #pragma unroll
             for (int sft = 16; sft >= 1; sft >>= 1) d += __shfl_xor(d, sft, 64);   // sum over the 32 lanes of this keypoint
@@ -1363,7 +1395,6 @@ __global__ __launch_bounds__(256) void assemble_kernel(const DevGeom* __restrict
     for (int l = 0; l < G->nlevels; l++) nk += lvl_cnt[slice * G->nlevels + l];
     if (tid == 0) out_n[slice] = nk;
     int mono_run = 0, stereo_run = 0;      // counts of each class before the current pass
-    int e0 = 0;                            // emission index of the first keypoint of the current level
     for (int l = 0; l < G->nlevels; l++) {
         const LevelGeom& L = G->lv[l];
         const int nl = lvl_cnt[slice * G->nlevels + l];
@@ -1375,14 +1406,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(const DevGeom* __restrict
             size_t gi = 0;
             if (valid) {
                 gi = (size_t)slice * G->kp_total + L.kp_off + i;
-                const uint32_t p = lvl_kp[gi];
-                kp.x = (float)(int)(p & 0xfff) + (float)L.minBX;
-                kp.y = (float)(int)((p >> 12) & 0xfff) + (float)L.minBY;
-                if (l != 0) { kp.x = kp.x * scale; kp.y = kp.y * scale; }       // keypoint.pt *= scale
-                kp.size = (float)L.patch_size;
-                kp.angle = kp_angle[gi];
-                kp.response = (float)(p >> 24);
-                kp.octave = l; kp.class_id = -1;
+                kp = kp_record(lvl_kp[gi], L, l, scale, kp_angle[gi]);
                 st = kp.x >= (float)lap0 && kp.x <= (float)lap1;
             }
             const uint64_t bs = __ballot(valid && st), bm = __ballot(valid && !st);
@@ -1412,9 +1436,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(const DevGeom* __restrict
             stereo_run += ts; mono_run += tm;
             __syncthreads();
         }
-        e0 += nl;
     }
-    (void)e0;
     if (tid == 0 && out_mono) out_mono[slice] = mono_run;
 }
 
@@ -1443,55 +1465,23 @@ __global__ __launch_bounds__(256) void describe_kernel(const DevGeom* __restrict
         if (out_flag && slice == 0) *out_flag = *err_flag;      // (host entry point: the flag travels with the counters)
     }
     if (gid >= G->kp_total) return;
-    int level = 0, before = 0;
-    while (level + 1 < G->nlevels && gid >= G->lv[level + 1].kp_off) { before += cnt[level]; level++; }
-    const LevelGeom& L = G->lv[level];
-    const int i = gid - L.kp_off;
+    int level, i, before, cx, cy;
+    kp_slot(G, cnt, gid, level, i, &before);
     if (i >= cnt[level]) return;                               // whole 32-lane group exits together
+    const LevelGeom& L = G->lv[level];
     const uint32_t p = lvl_kp[(size_t)slice * G->kp_total + gid];
-    const int cx = (int)(p & 0xfff) + L.minBX, cy = (int)((p >> 12) & 0xfff) + L.minBY;
-    // ---- IC_Angle: lane = column u of the disc (-15 .. 15, one lane idle) ----
+    kp_level_xy(p, L, cx, cy);
     const uint8_t* center = pyr + (size_t)slice * G->pyr_bytes + L.buf_off + (size_t)(cy + G->edge) * L.bw + (cx + G->edge);
-    const int step = L.bw;
-    const int u = l32 - 15;
-    const int au = u < 0 ? -u : u;
-    int m_01 = 0, m_10 = 0;
-    if (au <= 15) m_10 = u * (int)center[u];
-#pragma unroll
-    for (int v = 1; v <= 15; ++v) {
-        if (au <= G->umax[v]) {
-            const int val_plus = center[u + v * step], val_minus = center[u - v * step];
-            m_01 += v * (val_plus - val_minus);
-            m_10 += u * (val_plus + val_minus);
-        }
-    }
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) {
-        m_01 += __shfl_xor(m_01, d, 64);
-        m_10 += __shfl_xor(m_10, d, 64);
-    }
-    const float angle = dev_fast_atan2((float)m_01, (float)m_10);          // (every lane of the group holds both sums)
+    const float angle = ic_angle32(G, center, L.bw);
     const int dst = all_stereo ? nk - 1 - (before + i) : before + i;
     int val = 0, oob = 0;
     if (DESC) val = brief_byte(blur + (size_t)slice * G->roi_bytes + L.roi_off, L.w, L.h, cx, cy, angle, l32, oob);
-    const uint64_t anyoob = __ballot(oob != 0);
+    const bool anyoob = group32_any(oob != 0);
     if (dst < 0 || dst >= out_cap) return;
     if (DESC && out_desc) out_desc[((size_t)slice * out_cap + dst) * 32 + l32] = (uint8_t)val;
     if (l32 == 0) {
-        eorb_keypoint kp{};
-        kp.x = (float)(int)(p & 0xfff) + (float)L.minBX;
-        kp.y = (float)(int)((p >> 12) & 0xfff) + (float)L.minBY;
-        const float scale = G->sf[level];
-        if (level != 0) { kp.x = kp.x * scale; kp.y = kp.y * scale; }       // keypoint.pt *= scale
-        kp.size = (float)L.patch_size;
-        kp.angle = angle;
-        kp.response = (float)(p >> 24);
-        kp.octave = level; kp.class_id = -1;
-        out_kp[(size_t)slice * out_cap + dst] = kp;
-        if (out_oob) {
-            const uint32_t m = ((threadIdx.x >> 5) & 1) ? (uint32_t)(anyoob >> 32) : (uint32_t)anyoob;
-            out_oob[(size_t)slice * out_cap + dst] = (DESC && m) ? 1 : 0;
-        }
+        out_kp[(size_t)slice * out_cap + dst] = kp_record(p, L, level, G->sf[level], angle);
+        if (out_oob) out_oob[(size_t)slice * out_cap + dst] = (DESC && anyoob) ? 1 : 0;
     }
 }
 
@@ -1691,6 +1681,33 @@ int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H)
     return EORB_OK;
 }
 
+// the pyramid of B images (or, when the caller left the normalisation of its float images to this kernel, of c->pyr0_f32: d_img is
+// then where the u8 images go) and the blurred levels of it; grid sizes as orb_extract_dev has always had them (the kernels are grid-stride)
+static void launch_pyramid(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t img_slice_bytes, int B, int32_t* err_flag)
+{
+    OrbState& o = c->orb;
+    const DevGeom* G = (const DevGeom*)o.geom.p;
+    uint8_t* pyr = (uint8_t*)c->pyr.p;
+    const dim3 grid0((o.lv[0].bw * o.lv[0].bh / 4 + 256) / 256, B);
+    if (c->pyr0_f32) {
+        pyr_level0_f32_kernel<<<grid0, 256, 0, c->stream>>>(c->pyr0_f32, c->pyr0_mm, const_cast<uint8_t*>(d_img), img_stride, img_slice_bytes, G, pyr, err_flag);
+        c->pyr0_f32 = nullptr; c->pyr0_mm = nullptr;
+    } else
+        pyr_level0_kernel<<<grid0, 256, 0, c->stream>>>(d_img, img_stride, img_slice_bytes, G, pyr, err_flag);
+    for (int l = 1; l < o.nlevels; l++) {
+        const int n = o.lv[l].bw * o.lv[l].bh;
+        pyr_resize_kernel<<<dim3(B >= 16 ? (n + 1023) / 1024 : (n + 255) / 256, B), 256, 0, c->stream>>>(l, G, (const short4*)o.tabs.p, pyr);
+    }
+}
+
+static void launch_blur(eorb_ctx* c, int B)
+{
+    OrbState& o = c->orb;
+    int tyt = 0, wmax = 0;
+    for (int l = 0; l < o.nlevels; l++) { tyt += (o.lv[l].h + kBlurTH - 1) / kBlurTH; wmax = std::max(wmax, o.lv[l].w); }
+    blur_kernel<<<dim3((wmax + kBlurTW - 1) / kBlurTW, tyt, B), 256, 0, c->stream>>>((const DevGeom*)o.geom.p, (const uint8_t*)c->pyr.p, (uint8_t*)c->blur.p);
+}
+
 int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t img_slice_bytes, int B, int lap0, int lap1,
                     int want_desc, eorb_keypoint* d_kps, uint8_t* d_desc, uint8_t* d_oob, int32_t* d_n, int32_t* d_mono,
                     int32_t* d_flag_out)
@@ -1717,17 +1734,7 @@ int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t im
     o.last_B = B; o.last_blur = want_desc != 0; o.last_cells = true;
     {
         ProfScope ps(c, "orb_pyr");
-        const int n0 = o.lv[0].bw * o.lv[0].bh;
-        if (c->pyr0_f32) {
-            // (the caller left the normalisation of its float images to this kernel; d_img is where the u8 images go)
-            pyr_level0_f32_kernel<<<dim3((n0 / 4 + 256) / 256, B), 256, 0, c->stream>>>(c->pyr0_f32, c->pyr0_mm, const_cast<uint8_t*>(d_img), img_stride, img_slice_bytes, G, pyr, err_flag);
-            c->pyr0_f32 = nullptr; c->pyr0_mm = nullptr;
-        } else
-        pyr_level0_kernel<<<dim3((n0 / 4 + 256) / 256, B), 256, 0, c->stream>>>(d_img, img_stride, img_slice_bytes, G, pyr, err_flag);
-        for (int l = 1; l < o.nlevels; l++) {
-            const int n = o.lv[l].bw * o.lv[l].bh;
-            pyr_resize_kernel<<<dim3(B >= 16 ? (n + 1023) / 1024 : (n + 255) / 256, B), 256, 0, c->stream>>>(l, G, (const short4*)o.tabs.p, pyr);
-        }
+        launch_pyramid(c, d_img, img_stride, img_slice_bytes, B, err_flag);
         EORB_LAUNCH_CHECK(c, "pyramid kernels");
     }
     {
@@ -1741,18 +1748,16 @@ int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t im
         // reports an earlier batch's overflow
         int32_t* sticky = d_flag_out ? nullptr : (int32_t*)c->status.p;
         int32_t* redo = err_flag + 16;                               // one flag per (slice, level), behind the error flag
-        if (o.oct_all_lds[placement])
-            octree_kernel<true><<<B * o.nlevels, kOctThreads, o.oct_lds[placement], c->stream>>>(G, (const int32_t*)c->cell_cnt.p, (const uint32_t*)c->cell_cand.p,
-                                                                    (unsigned char*)c->oct_scratch.p, (uint32_t*)c->lvl_kp.p, (int32_t*)c->lvl_cnt.p, err_flag, sticky, placement, nullptr);
+        auto octree = [&](auto lds_only, int lds_bytes, int32_t* redo_flags) {
+            octree_kernel<decltype(lds_only)::value><<<B * o.nlevels, kOctThreads, lds_bytes, c->stream>>>(G, (const int32_t*)c->cell_cnt.p, (const uint32_t*)c->cell_cand.p,
+                (unsigned char*)c->oct_scratch.p, (uint32_t*)c->lvl_kp.p, (int32_t*)c->lvl_cnt.p, err_flag, sticky, placement, redo_flags);
+        };
+        if (o.oct_all_lds[placement]) octree(std::true_type{}, o.oct_lds[placement], nullptr);
         else if (o.oct_dyn[placement]) {
             // levels whose candidates fit the LDS this time run there; the others are left to the mixed placement
-            octree_kernel<true><<<B * o.nlevels, kOctThreads, o.oct_dyn_lds[placement], c->stream>>>(G, (const int32_t*)c->cell_cnt.p, (const uint32_t*)c->cell_cand.p,
-                                                                    (unsigned char*)c->oct_scratch.p, (uint32_t*)c->lvl_kp.p, (int32_t*)c->lvl_cnt.p, err_flag, sticky, placement, redo);
-            octree_kernel<false><<<B * o.nlevels, kOctThreads, o.oct_lds[placement], c->stream>>>(G, (const int32_t*)c->cell_cnt.p, (const uint32_t*)c->cell_cand.p,
-                                                                    (unsigned char*)c->oct_scratch.p, (uint32_t*)c->lvl_kp.p, (int32_t*)c->lvl_cnt.p, err_flag, sticky, placement, redo);
-        } else
-            octree_kernel<false><<<B * o.nlevels, kOctThreads, o.oct_lds[placement], c->stream>>>(G, (const int32_t*)c->cell_cnt.p, (const uint32_t*)c->cell_cand.p,
-                                                                    (unsigned char*)c->oct_scratch.p, (uint32_t*)c->lvl_kp.p, (int32_t*)c->lvl_cnt.p, err_flag, sticky, placement, nullptr);
+            octree(std::true_type{}, o.oct_dyn_lds[placement], redo);
+            octree(std::false_type{}, o.oct_lds[placement], redo);
+        } else octree(std::false_type{}, o.oct_lds[placement], nullptr);
         EORB_LAUNCH_CHECK(c, "octree_kernel");
     }
     // a lapping area [lap0, lap1] that ends left of the first column a keypoint can have holds none of them, one that spans the image
@@ -1763,9 +1768,7 @@ int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t im
     const int all_stereo = !none_in && all_in;
     if (want_desc) {
         ProfScope ps(c, "orb_blur");
-        int tyt = 0, wmax = 0;
-        for (int l = 0; l < o.nlevels; l++) { tyt += (o.lv[l].h + kBlurTH - 1) / kBlurTH; wmax = std::max(wmax, o.lv[l].w); }
-        blur_kernel<<<dim3((wmax + kBlurTW - 1) / kBlurTW, tyt, B), 256, 0, c->stream>>>(G, pyr, (uint8_t*)c->blur.p);
+        launch_blur(c, B);
         EORB_LAUNCH_CHECK(c, "blur_kernel");
     }
     if (one_launch) {
@@ -1864,19 +1867,10 @@ int orb_pyramid_blur_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride)
     int rc;
     if ((rc = ensure(c, c->pyr, (size_t)o.pyr_bytes))) return rc;
     if ((rc = ensure(c, c->blur, (size_t)o.roi_bytes))) return rc;
-    const DevGeom* G = (const DevGeom*)o.geom.p;
-    uint8_t* pyr = (uint8_t*)c->pyr.p;
     o.last_B = 1; o.last_blur = true; o.last_cells = false;
     ProfScope ps(c, "orb_pyr_blur");
-    const int n0 = o.lv[0].bw * o.lv[0].bh;
-    pyr_level0_kernel<<<dim3((n0 + 255) / 256, 1), 256, 0, c->stream>>>(d_img, img_stride, 0, G, pyr, nullptr);
-    for (int l = 1; l < o.nlevels; l++) {
-        const int n = o.lv[l].bw * o.lv[l].bh;
-        pyr_resize_kernel<<<dim3((n + 255) / 256, 1), 256, 0, c->stream>>>(l, G, (const short4*)o.tabs.p, pyr);
-    }
-    int tyt = 0, wmax = 0;
-    for (int l = 0; l < o.nlevels; l++) { tyt += (o.lv[l].h + kBlurTH - 1) / kBlurTH; wmax = std::max(wmax, o.lv[l].w); }
-    blur_kernel<<<dim3((wmax + kBlurTW - 1) / kBlurTW, tyt, 1), 256, 0, c->stream>>>(G, pyr, (uint8_t*)c->blur.p);
+    launch_pyramid(c, d_img, img_stride, 0, 1, nullptr);
+    launch_blur(c, 1);
     EORB_LAUNCH_CHECK(c, "pyramid/blur kernels");
     return EORB_OK;
 }

@@ -331,6 +331,10 @@ class ORBextractor:
         self.ctx.check(self.ctx.L.eorb_orb_get_tables(self.ctx.h, _p(sf), _p(inv), _p(nf), C.byref(e)))
         self.mvScaleFactor, self.mvInvScaleFactor, self.mnFeaturesPerLevel, self.edge = sf, inv, nf, e.value
 
+    def _out(self, *records):
+        """one capacity-sized, zeroed caller array per record type (a dtype, or (dtype, columns))"""
+        return [np.zeros((self.cap,) + tuple(r[1:]), r[0]) if isinstance(r, tuple) else np.zeros(self.cap, r) for r in records]
+
     def stereo(self, imLeft, imRight, mb, mbf):
         """Frame::Frame(imLeft, imRight, ...) (src/Frame.cc:97-152): both extractions and Frame::ComputeStereoMatches (:869-1048) in one
         call.  Returns dict(kpsL, descL, kpsR, descR, uRight (mvuRight), depth (mvDepth), nmatches (before the median cut))."""
@@ -339,8 +343,7 @@ class ORBextractor:
         if imR.shape != imL.shape:
             raise ValueError("left and right image differ in size")
         cap = self.cap
-        kL = np.zeros(cap, KP_DTYPE); kR = np.zeros(cap, KP_DTYPE); dL = np.zeros((cap, 32), np.uint8); dR = np.zeros((cap, 32), np.uint8)
-        ur = np.zeros(cap, np.float32); dp = np.zeros(cap, np.float32)
+        kL, kR, dL, dR, ur, dp = self._out(KP_DTYPE, KP_DTYPE, (np.uint8, 32), (np.uint8, 32), np.float32, np.float32)
         nL, nR, nm = C.c_int(), C.c_int(), C.c_int()
         self.ctx.check(self.ctx.L.eorb_frame_stereo(self.ctx.h, _p(imL), _p(imR), W, H, imL.strides[0], float(mb), float(mbf), _p(kL), _p(dL), C.byref(nL),
                                                     _p(kR), _p(dR), C.byref(nR), cap, _p(ur), _p(dp), C.byref(nm)))
@@ -357,8 +360,7 @@ class ORBextractor:
         if imR.shape != imL.shape:
             raise ValueError("left and right image differ in size")
         cap = self.cap
-        kL = np.zeros(cap, KP_DTYPE); kR = np.zeros(cap, KP_DTYPE); dL = np.zeros((cap, 32), np.uint8); dR = np.zeros((cap, 32), np.uint8)
-        cand = np.zeros(cap, np.int32); d2 = np.zeros((cap, 2), np.int32)
+        kL, kR, dL, dR, cand, d2 = self._out(KP_DTYPE, KP_DTYPE, (np.uint8, 32), (np.uint8, 32), np.int32, (np.int32, 2))
         nL, nR, mL, mR, nc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
         self.ctx.check(self.ctx.L.eorb_frame_fisheye(self.ctx.h, _p(imL), _p(imR), W, H, imL.strides[0],
                                                      int(vLappingAreaLeft[0]), int(vLappingAreaLeft[1]), int(vLappingAreaRight[0]), int(vLappingAreaRight[1]),
@@ -374,8 +376,7 @@ class ORBextractor:
         desc, oob, bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY))."""
         image = np.ascontiguousarray(image, np.uint8)
         H, W = image.shape
-        kps = np.empty(self.cap, KP_DTYPE); un = np.empty(self.cap, KP_DTYPE)
-        desc = np.empty((self.cap, 32), np.uint8); oob = np.empty(self.cap, np.uint8); bounds = np.zeros(4, np.float32)
+        kps, un, desc, oob = self._out(KP_DTYPE, KP_DTYPE, (np.uint8, 32), np.uint8); bounds = np.zeros(4, np.float32)
         n = C.c_int(); mono = C.c_int()
         self.ctx.check(self.ctx.L.eorb_frame_mono(self.ctx.h, _p(image), W, H, image.strides[0], vLappingArea[0], vLappingArea[1], int(want_desc),
                                                   _p(kps), _p(un), _p(desc), _p(oob), self.cap, C.byref(n), C.byref(mono), _p(bounds)))
@@ -395,14 +396,13 @@ class ORBextractor:
             return -1, None, None, None
         image = np.ascontiguousarray(image, np.uint8)
         H, W = image.shape
-        kps = np.zeros(self.cap, KP_DTYPE); desc = np.zeros((self.cap, 32), np.uint8); oob = np.zeros(self.cap, np.uint8)
+        kps, desc, oob = self._out(KP_DTYPE, (np.uint8, 32), np.uint8)
         n = C.c_int(); mono = C.c_int()
         self.ctx.check(self.ctx.L.eorb_orb_extract(self.ctx.h, _p(image), W, H, image.strides[0], vLappingArea[0],
                                                    vLappingArea[1], int(want_desc), _p(kps), _p(desc), _p(oob),
                                                    self.cap, C.byref(n), C.byref(mono)))
         k = n.value
         return mono.value, kps[:k].copy(), (desc[:k].copy() if want_desc else None), oob[:k].copy()
-
 
     def ComputeTrackedKPtsDesc(self, trackedImage, trackedKPts):
         """src/ORBextractor.cc:1316-1363 -> (refDescs n x 32, oob flags)"""
