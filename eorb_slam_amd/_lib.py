@@ -23,6 +23,7 @@ EXPORTS = [
     "eorb_fe_configure", "eorb_fe_run_batch_dev", "eorb_fe_last_f32_dev",
     "eorb_ev_slice_extract", "eorb_ev_slice_track", "eorb_ev_slice_image", "eorb_ev_mc_contest",
     "eorb_project_frustum", "eorb_project_last_frame", "eorb_project_keyframe_points", "eorb_search_local_points", "eorb_search_local_points_fisheye", "eorb_search_by_projection_last_pose", "eorb_search_by_projection_kf_pose",
+    "eorb_project_keyframe_side", "eorb_fuse_pose", "eorb_search_by_projection_kf_scw", "eorb_search_by_sim3", "eorb_fuse_keyframes",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
 ]
@@ -66,6 +67,12 @@ class FrustumOut(C.Structure):
     """eorb_frustum_out: what isInFrustum leaves in a MapPoint, one array per member (any may be NULL)"""
     _fields_ = [("in_view", C.c_void_p), ("proj_xy", C.c_void_p), ("proj_xr", C.c_void_p), ("level", C.c_void_p),
                 ("view_cos", C.c_void_p), ("depth", C.c_void_p), ("level_scale", C.c_void_p), ("reason", C.c_void_p)]
+
+
+class KfSideOut(C.Structure):
+    """eorb_kfside_out: the KeyFrame-side projection per (keyframe, map point), one array per member (any may be NULL)"""
+    _fields_ = [("valid", C.c_void_p), ("uv", C.c_void_p), ("radius", C.c_void_p), ("level", C.c_void_p), ("q_ur", C.c_void_p),
+                ("dist3d", C.c_void_p), ("reason", C.c_void_p)]
 
 
 class Calib(C.Structure):
@@ -298,6 +305,18 @@ def lib():
     L.eorb_search_by_projection_kf_pose.restype = ci
     L.eorb_search_by_projection_kf_pose.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, C.POINTER(GridBounds), vp, cf, ci, ci,
                                                     vp, vp, vp, pi]
+    gbp = C.POINTER(GridBounds)
+    L.eorb_project_keyframe_side.restype = ci
+    L.eorb_project_keyframe_side.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, cf, vp]
+    L.eorb_fuse_pose.restype = ci
+    L.eorb_fuse_pose.argtypes = [vp, vp, ci, vp, ci, gbp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp]
+    L.eorb_search_by_projection_kf_scw.restype = ci
+    L.eorb_search_by_projection_kf_scw.argtypes = [vp, vp, ci, vp, ci, gbp, vp, ci, vp, vp, vp, vp, vp, vp, cf, vp, cf, vp, vp, vp]
+    L.eorb_search_by_sim3.restype = ci
+    L.eorb_search_by_sim3.argtypes = [vp, vp, ci, vp, ci, gbp, vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, gbp, vp, vp, vp, vp, vp, vp,
+                                      vp, vp, vp, vp, cf, ci, vp, pi, vp, vp]
+    L.eorb_fuse_keyframes.restype = ci
+    L.eorb_fuse_keyframes.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]
     L.eorb_selfcheck_math.restype = ci; L.eorb_selfcheck_math.argtypes = [vp, ci, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.eorb_pack_events.restype = None; L.eorb_pack_events.argtypes = [vp, C.c_size_t, vp]

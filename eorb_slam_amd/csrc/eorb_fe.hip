@@ -2443,6 +2443,325 @@ int eorb_kf_radius_match_stereo(eorb_ctx* c,
     return kf_radius_common(c, kps, n, desc, stride, gb, M, valid, uv, radius, level, q_desc, inv_sigma2, nlevels, nullptr, 0.f, best_idx, best_dist, uright, q_ur);
 }
 
+// ---- KeyFrame-side matchers: projection (project.hip modes D, E) and search behind one upload, one wait, one download ------------
+// Limits of one call: the arena holds 34 B per query and 64 B per keypoint
+static constexpr int64_t kKfSideMaxQueries = (int64_t)1 << 22;      // K * M
+static constexpr int64_t kKfSideMaxKps = (int64_t)1 << 22;          // keypoints of all keyframes together
+static constexpr int kKfSideMaxKfs = 1024;                          // K
+
+static KfPose kf_pose_of(const eorb_view& v)
+{
+    KfPose P{};
+    memcpy(P.R, v.R, sizeof(P.R)); memcpy(P.t, v.t, sizeof(P.t)); memcpy(P.Ow, v.Ow, sizeof(P.Ow));
+    P.cam = warp_cam_of(v.cam);
+    P.minX = v.minX; P.maxX = v.maxX; P.minY = v.minY; P.maxY = v.maxY; P.mbf = v.mbf;
+    return P;
+}
+
+// the arena regions of the projector's K * M outputs, in the order a call downloads them: reason first (eorb_fuse_keyframes wants
+// nothing else), then the members of eorb_kfside_out
+struct KfSideOff { size_t rs, va, uv, rad, lv, qur, d3, end_rs, end; };
+static KfSideOff kfside_reserve(Arena& A, size_t n)
+{
+    KfSideOff o;
+    o.rs = A.reserve(n); o.end_rs = A.total;
+    o.va = A.reserve(n); o.uv = A.reserve(8 * n); o.rad = A.reserve(4 * n); o.lv = A.reserve(4 * n); o.qur = A.reserve(4 * n);
+    o.d3 = A.reserve(4 * n); o.end = A.total;
+    return o;
+}
+static KfSideDev kfside_dev(const Arena& A, const KfSideOff& o)
+{
+    return KfSideDev{A.dev<uint8_t>(o.va), A.dev<float2>(o.uv), A.dev<int32_t>(o.lv), A.dev<float>(o.rad), A.dev<float>(o.qur),
+                     A.dev<float>(o.d3), A.dev<uint8_t>(o.rs)};
+}
+static bool kfside_wants_all(const eorb_kfside_out* out)
+{
+    return out && (out->valid || out->uv || out->radius || out->level || out->q_ur || out->dist3d);
+}
+static size_t kfside_end(const KfSideOff& o, const eorb_kfside_out* out, size_t without)
+{
+    return kfside_wants_all(out) ? o.end : (out && out->reason) ? o.end_rs : without;
+}
+static void kfside_copy_out(const char* h, const KfSideOff& o, size_t n, const eorb_kfside_out* out)
+{
+    if (!out) return;
+    if (out->reason) memcpy(out->reason, h + o.rs, n);
+    if (out->valid) memcpy(out->valid, h + o.va, n);
+    if (out->uv) memcpy(out->uv, h + o.uv, 8 * n);
+    if (out->radius) memcpy(out->radius, h + o.rad, 4 * n);
+    if (out->level) memcpy(out->level, h + o.lv, 4 * n);
+    if (out->q_ur) memcpy(out->q_ur, h + o.qur, 4 * n);
+    if (out->dist3d) memcpy(out->dist3d, h + o.d3, 4 * n);
+}
+
+// the map points of mode D and the views' shared table
+struct KfSideIn { size_t pos, nrm, mind, maxd, skip, sf, pose; std::vector<KfPose> poses; };
+static int kfside_check(eorb_ctx* c, const char* who, const eorb_view* views, int K, int M, const float* pos, const float* normal,
+                        const float* min_dist, const float* max_dist)
+{
+    if (K < 0 || M < 0 || (K > 0 && !views) || (K > 0 && M > 0 && (!pos || !normal || !min_dist || !max_dist)))
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
+    int rc;
+    for (int k = 0; k < K; k++) {
+        if ((rc = view_check(c, who, views + k, false))) return rc;
+        if (views[k].nlevels != views[0].nlevels || views[k].log_scale != views[0].log_scale)
+            return set_err(c, EORB_E_ARG, "%s: keyframe %d has another scale pyramid than keyframe 0 (one table serves the batch)", who, k);
+    }
+    return EORB_OK;
+}
+static void kfside_in(Arena& A, KfSideIn& I, const eorb_view* views, int K, int M, const float* pos, const float* normal,
+                      const float* min_dist, const float* max_dist, const uint8_t* skip)
+{
+    const size_t m = (size_t)M;
+    I.pos = A.in(pos, 12 * m); I.nrm = A.in(normal, 12 * m); I.mind = A.in(min_dist, 4 * m); I.maxd = A.in(max_dist, 4 * m);
+    I.skip = A.in(skip, skip ? (size_t)K * m : 0);
+    I.sf = A.in(views[0].scale_factors, sizeof(float) * (size_t)views[0].nlevels);
+    I.poses.resize(K);
+    for (int k = 0; k < K; k++) I.poses[k] = kf_pose_of(views[k]);
+    I.pose = A.in(I.poses.data(), sizeof(KfPose) * (size_t)K);
+}
+static KfSideArgs kfside_args(const Arena& A, const KfSideIn& I, const eorb_view* views, int K, int M, bool has_skip, float th, const KfSideOff& o)
+{
+    KfSideArgs P{};
+    P.V = A.dev<KfPose>(I.pose); P.K = K; P.M = M;
+    P.nlevels = views[0].nlevels; P.log_scale = views[0].log_scale; P.sf = A.dev<float>(I.sf); P.th = th;
+    P.pos = A.dev<float>(I.pos); P.normal = A.dev<float>(I.nrm); P.min_dist = A.dev<float>(I.mind); P.max_dist = A.dev<float>(I.maxd);
+    P.skip = has_skip ? A.dev<uint8_t>(I.skip) : nullptr;
+    P.O = kfside_dev(A, o);
+    return P;
+}
+
+int eorb_project_keyframe_side(eorb_ctx* c, const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                               const float* max_dist, const uint8_t* skip, float th, const eorb_kfside_out* out)
+{
+    if (!c) return EORB_E_ARG;
+    int rc;
+    if (!view) return set_err(c, EORB_E_ARG, "project_keyframe_side: null view");
+    if ((rc = kfside_check(c, "project_keyframe_side", view, 1, M, pos, normal, min_dist, max_dist))) return rc;
+    if (M > kKfSideMaxQueries) return set_err(c, EORB_E_CAPACITY, "project_keyframe_side: %d map points exceed %lld", M, (long long)kKfSideMaxQueries);
+    fe_enter(c);
+    if (M == 0) return EORB_OK;
+    Arena A(c);
+    KfSideIn I;
+    kfside_in(A, I, view, 1, M, pos, normal, min_dist, max_dist, skip);
+    const KfSideOff o = kfside_reserve(A, (size_t)M);
+    if ((rc = A.upload())) return rc;
+    if ((rc = project_kfside_dev(c, kfside_args(A, I, view, 1, M, skip != nullptr, th, o)))) return rc;
+    const char* h;
+    if ((rc = A.download(o.rs, o.end - o.rs, &h))) return rc;
+    kfside_copy_out(h, o, (size_t)M, out);
+    return EORB_OK;
+}
+
+// mode D over K keyframes, then the batched radius match; shared by eorb_fuse_pose (K = 1) and eorb_fuse_keyframes
+static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, const eorb_grid_bounds* gb, int K,
+                       const eorb_keypoint* kps, const uint8_t* desc, int stride, const float* uright, const int32_t* kf_off,
+                       int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* q_desc,
+                       const uint8_t* skip, const float* inv_sigma2, float th, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
+{
+    int rc;
+    if (K > kKfSideMaxKfs || (K > 0 && M > 0 && (int64_t)K * M > kKfSideMaxQueries))      // (sizes only: nothing is read before this)
+        return set_err(c, EORB_E_CAPACITY, "%s: %d keyframes x %d map points exceed %d keyframes or %lld queries", who, K, M, kKfSideMaxKfs,
+                       (long long)kKfSideMaxQueries);
+    if ((rc = kfside_check(c, who, views, K, M, pos, normal, min_dist, max_dist))) return rc;
+    if (stride < 32 || (K > 0 && (!gb || !kf_off)) || (K > 0 && M > 0 && (!q_desc || !best_idx || !best_dist)) || (uright && !inv_sigma2))
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
+    if (K == 0) return EORB_OK;
+    if (kf_off[0] != 0) return set_err(c, EORB_E_ARG, "%s: kf_off[0] = %d", who, kf_off[0]);
+    for (int k = 0; k < K; k++) if (kf_off[k + 1] < kf_off[k]) return set_err(c, EORB_E_ARG, "%s: kf_off decreases at keyframe %d", who, k);
+    const int ntotal = kf_off[K];
+    if (ntotal > kKfSideMaxKps) return set_err(c, EORB_E_CAPACITY, "%s: %d keypoints exceed %lld", who, ntotal, (long long)kKfSideMaxKps);
+    if (ntotal > 0 && (!kps || !desc)) return set_err(c, EORB_E_ARG, "%s: no keypoints", who);
+    if (inv_sigma2 && views[0].nlevels > 64) return set_err(c, EORB_E_ARG, "%s: the reprojection gate takes at most 64 levels", who);
+    fe_enter(c);
+    const size_t nq = (size_t)K * M;
+    for (size_t q = 0; q < nq; q++) { best_idx[q] = -1; best_dist[q] = 256; }
+    if (M == 0) return EORB_OK;
+    Arena A(c);
+    KfSideIn I;
+    kfside_in(A, I, views, K, M, pos, normal, min_dist, max_dist, skip);
+    std::vector<GridB> g(K);
+    for (int k = 0; k < K; k++) g[k] = grid_b(gb[k]);
+    const size_t o_g = A.in(g.data(), sizeof(GridB) * (size_t)K), o_off = A.in(kf_off, sizeof(int32_t) * ((size_t)K + 1));
+    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)ntotal), o_d = A.in(desc, (size_t)stride * ntotal);
+    const size_t o_ur = A.in(uright, uright ? sizeof(float) * (size_t)ntotal : 0);
+    const size_t o_qd = A.in(q_desc, 32 * (size_t)M);
+    const size_t o_is = A.in(inv_sigma2, inv_sigma2 ? sizeof(float) * (size_t)views[0].nlevels : 0);
+    // outputs, contiguous: best index | best distance | the projector's arrays; then the keypoints' cells
+    const size_t o_bi = A.reserve(4 * nq), o_bd = A.reserve(4 * nq), o_bend = A.total;
+    const KfSideOff o = kfside_reserve(A, nq);
+    const size_t o_cell = A.reserve(sizeof(uint16_t) * (size_t)ntotal);
+    if ((rc = A.upload())) return rc;
+    const KfSideArgs P = kfside_args(A, I, views, K, M, skip != nullptr, th, o);
+    if ((rc = project_kfside_dev(c, P))) return rc;
+    RadBatchArgs B{};
+    B.kps = A.dev<eorb_keypoint>(o_k); B.desc = A.dev<uint8_t>(o_d); B.stride = stride; B.cell = A.dev<uint16_t>(o_cell);
+    B.uright = uright ? A.dev<float>(o_ur) : nullptr;
+    B.kf_off = A.dev<int32_t>(o_off); B.g = A.dev<GridB>(o_g); B.K = K; B.M = M;
+    B.valid = P.O.valid; B.uv = (const float*)P.O.uv; B.radius = P.O.radius; B.level = P.O.level; B.q_ur = P.O.q_ur;
+    B.q_desc = A.dev<uint8_t>(o_qd); B.q_desc_kstride = 0;
+    B.inv_sigma2 = inv_sigma2 ? A.dev<float>(o_is) : nullptr; B.nlevels = views[0].nlevels;
+    B.best_idx = A.dev<int32_t>(o_bi); B.best_dist = A.dev<int32_t>(o_bd);
+    if ((rc = kf_radius_batch_dev(c, B, ntotal, A.dev<uint16_t>(o_cell)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_bi, kfside_end(o, out, o_bend) - o_bi, &h))) return rc;
+    memcpy(best_idx, h + o_bi, 4 * nq);
+    memcpy(best_dist, h + o_bd, 4 * nq);
+    kfside_copy_out(h, o, nq, out);
+    return EORB_OK;
+}
+
+int eorb_fuse_pose(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                   const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                   const uint8_t* skip, const uint8_t* q_desc, const float* inv_sigma2, const float* uright, float th,
+                   int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
+{
+    if (!c) return EORB_E_ARG;
+    if (n < 0 || !view || !gb) return set_err(c, EORB_E_ARG, "fuse_pose: bad arguments");
+    const int32_t off[2] = {0, n};
+    return fuse_common(c, "fuse_pose", view, gb, 1, kps, desc, stride, uright, off, M, pos, normal, min_dist, max_dist, q_desc, skip,
+                       inv_sigma2, th, best_idx, best_dist, out);
+}
+
+int eorb_fuse_keyframes(eorb_ctx* c, const eorb_view* views, const eorb_grid_bounds* gb, int K,
+                        const eorb_keypoint* kps, const uint8_t* desc, int stride, const float* uright, const int32_t* kf_off,
+                        int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* q_desc,
+                        const uint8_t* skip, const float* inv_sigma2, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reason)
+{
+    if (!c) return EORB_E_ARG;
+    eorb_kfside_out out{};
+    out.reason = reason;
+    return fuse_common(c, "fuse_keyframes", views, gb, K, kps, desc, stride, uright, kf_off, M, pos, normal, min_dist, max_dist, q_desc, skip,
+                       inv_sigma2, th, best_idx, best_dist, reason ? &out : nullptr);
+}
+
+int eorb_search_by_projection_kf_scw(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                                     const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                                     const float* max_dist, const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken,
+                                     float accept_thr, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
+{
+    if (!c) return EORB_E_ARG;
+    int rc;
+    if (n < 0 || !view || !gb || stride < 32 || (n > 0 && (!kps || !desc || !taken)) || (M > 0 && (!q_desc || !best_idx || !best_dist)))
+        return set_err(c, EORB_E_ARG, "search_by_projection_kf_scw: bad arguments");
+    if ((rc = kfside_check(c, "search_by_projection_kf_scw", view, 1, M, pos, normal, min_dist, max_dist))) return rc;
+    if (M > kKfSideMaxQueries) return set_err(c, EORB_E_CAPACITY, "search_by_projection_kf_scw: %d map points exceed %lld", M, (long long)kKfSideMaxQueries);
+    fe_enter(c);
+    for (int m = 0; m < M; m++) { best_idx[m] = -1; best_dist[m] = 256; }
+    if (M == 0) return EORB_OK;
+    const size_t nq = (size_t)M;
+    Arena A(c);
+    KfSideIn I;
+    kfside_in(A, I, view, 1, M, pos, normal, min_dist, max_dist, skip);
+    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)n), o_d = A.in(desc, (size_t)stride * n);
+    const size_t o_qd = A.in(q_desc, 32 * nq);
+    // outputs, contiguous: taken (in / out) | best index | best distance | the projector's arrays; then the keypoints' cells
+    const size_t o_tk = A.in(taken, (size_t)n);
+    const size_t o_bi = A.reserve(4 * nq), o_bd = A.reserve(4 * nq), o_bend = A.total;
+    const KfSideOff o = kfside_reserve(A, nq);
+    const size_t o_cell = A.reserve(sizeof(uint16_t) * (size_t)n);
+    if ((rc = A.upload())) return rc;
+    const KfSideArgs P = kfside_args(A, I, view, 1, M, skip != nullptr, th, o);
+    if ((rc = project_kfside_dev(c, P))) return rc;
+    RadArgs R{};
+    R.kps = A.dev<eorb_keypoint>(o_k); R.n = n; R.desc = A.dev<uint8_t>(o_d); R.stride = stride;
+    R.g = grid_b(*gb); R.cell = A.dev<uint16_t>(o_cell);
+    R.M = M; R.valid = P.O.valid; R.uv = (const float*)P.O.uv; R.radius = P.O.radius; R.level = P.O.level; R.q_desc = A.dev<uint8_t>(o_qd);
+    R.taken = A.dev<uint8_t>(o_tk); R.accept_thr = accept_thr;
+    R.best_idx = A.dev<int32_t>(o_bi); R.best_dist = A.dev<int32_t>(o_bd);
+    if ((rc = kf_radius_dev(c, R, A.dev<uint16_t>(o_cell)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_tk, kfside_end(o, out, o_bend) - o_tk, &h))) return rc;
+    memcpy(best_idx, h + o_bi, 4 * nq);
+    memcpy(best_dist, h + o_bd, 4 * nq);
+    if (n > 0) memcpy(taken, h + o_tk, (size_t)n);
+    kfside_copy_out(h, o, nq, out);
+    return EORB_OK;
+}
+
+int eorb_search_by_sim3(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const eorb_grid_bounds* gb1, const eorb_view* view1,
+        const float* pos1, const float* min_dist1, const float* max_dist1, const uint8_t* mp_desc1, const uint8_t* skip1,
+        const eorb_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const eorb_grid_bounds* gb2, const eorb_view* view2,
+        const float* pos2, const float* min_dist2, const float* max_dist2, const uint8_t* mp_desc2, const uint8_t* skip2,
+        const float* sR12, const float* t12, const float* sR21, const float* t21, float th, int th_high,
+        int32_t* match12, int* nfound, int32_t* vnMatch1, int32_t* vnMatch2)
+{
+    if (!c) return EORB_E_ARG;
+    if (nfound) *nfound = 0;
+    if (n1 < 0 || n2 < 0 || stride1 < 32 || stride2 < 32 || !gb1 || !gb2 || !sR12 || !t12 || !sR21 || !t21 || th_high < 0 || th_high > 255 ||
+        (n1 > 0 && (!kps1 || !desc1 || !pos1 || !min_dist1 || !max_dist1 || !mp_desc1 || !match12)) ||
+        (n2 > 0 && (!kps2 || !desc2 || !pos2 || !min_dist2 || !max_dist2 || !mp_desc2)))
+        return set_err(c, EORB_E_ARG, "search_by_sim3: bad arguments");
+    int rc;
+    if ((rc = view_check(c, "search_by_sim3", view1, false)) || (rc = view_check(c, "search_by_sim3", view2, false))) return rc;
+    if (view1->cam.model != 0 || view2->cam.model != 0)      // the reference hard-codes fx, fy, cx, cy (:1746-1749, :1811)
+        return set_err(c, EORB_E_CONFIG, "search_by_sim3: pinhole keyframes only");
+    if ((int64_t)n1 + n2 > kKfSideMaxKps) return set_err(c, EORB_E_CAPACITY, "search_by_sim3: %d + %d keypoints exceed %lld", n1, n2, (long long)kKfSideMaxKps);
+    fe_enter(c);
+    for (int i = 0; i < n1; i++) match12[i] = -1;
+    if (vnMatch1) for (int i = 0; i < n1; i++) vnMatch1[i] = -1;
+    if (vnMatch2) for (int i = 0; i < n2; i++) vnMatch2[i] = -1;
+    if (n1 == 0 || n2 == 0) return EORB_OK;
+    // a 2 x M batch: row 0 = KF1's points searched in KF2, row 1 = KF2's points searched in KF1; the searched keypoints in that order
+    const int M = std::max(n1, n2), ntotal = n1 + n2;
+    const size_t m = (size_t)M;
+    std::vector<eorb_keypoint> kcat((size_t)ntotal);
+    memcpy(kcat.data(), kps2, sizeof(eorb_keypoint) * (size_t)n2); memcpy(kcat.data() + n2, kps1, sizeof(eorb_keypoint) * (size_t)n1);
+    std::vector<uint8_t> dcat(32 * (size_t)ntotal), qd(64 * m, 0);
+    for (int i = 0; i < n2; i++) memcpy(&dcat[32 * (size_t)i], desc2 + (size_t)i * stride2, 32);
+    for (int i = 0; i < n1; i++) memcpy(&dcat[32 * ((size_t)n2 + i)], desc1 + (size_t)i * stride1, 32);
+    memcpy(qd.data(), mp_desc1, 32 * (size_t)n1); memcpy(qd.data() + 32 * m, mp_desc2, 32 * (size_t)n2);
+    const int32_t off[3] = {0, n2, ntotal};
+    const GridB g[2] = {grid_b(*gb2), grid_b(*gb1)};
+    Arena A(c);
+    const size_t o_k = A.in(kcat.data(), sizeof(eorb_keypoint) * (size_t)ntotal), o_d = A.in(dcat.data(), dcat.size()), o_qd = A.in(qd.data(), qd.size());
+    const size_t o_off = A.in(off, sizeof(off)), o_g = A.in(g, sizeof(g));
+    const size_t o_p1 = A.in(pos1, 12 * (size_t)n1), o_mn1 = A.in(min_dist1, 4 * (size_t)n1), o_mx1 = A.in(max_dist1, 4 * (size_t)n1);
+    const size_t o_p2 = A.in(pos2, 12 * (size_t)n2), o_mn2 = A.in(min_dist2, 4 * (size_t)n2), o_mx2 = A.in(max_dist2, 4 * (size_t)n2);
+    const size_t o_s1 = A.in(skip1, skip1 ? (size_t)n1 : 0), o_s2 = A.in(skip2, skip2 ? (size_t)n2 : 0);
+    const size_t o_sf1 = A.in(view1->scale_factors, sizeof(float) * (size_t)view1->nlevels);
+    const size_t o_sf2 = A.in(view2->scale_factors, sizeof(float) * (size_t)view2->nlevels);
+    // outputs, contiguous: nfound | match12 | vnMatch1 | vnMatch2; then what only the kernels read
+    const size_t o_nf = A.reserve(16), o_m12 = A.reserve(4 * (size_t)n1), o_v1 = A.reserve(4 * (size_t)n1), o_v2 = A.reserve(4 * (size_t)n2);
+    const size_t o_end = A.total;
+    const size_t o_bi = A.reserve(8 * m), o_bd = A.reserve(8 * m);
+    const KfSideOff o = kfside_reserve(A, 2 * m);
+    const size_t o_cell = A.reserve(sizeof(uint16_t) * (size_t)ntotal);
+    if ((rc = A.upload())) return rc;
+    Sim3Args S{};
+    S.M = M; S.th = th; S.O = kfside_dev(A, o);
+    for (int hf = 0; hf < 2; hf++) {
+        Sim3Half& H = S.H[hf];
+        const eorb_view* va = hf ? view2 : view1; const eorb_view* vb = hf ? view1 : view2;
+        memcpy(H.Ra, va->R, sizeof(H.Ra)); memcpy(H.ta, va->t, sizeof(H.ta));
+        memcpy(H.sRb, hf ? sR12 : sR21, sizeof(H.sRb)); memcpy(H.tb, hf ? t12 : t21, sizeof(H.tb));
+        H.fx = view1->cam.fx; H.fy = view1->cam.fy; H.cx = view1->cam.cx; H.cy = view1->cam.cy;
+        H.minX = vb->minX; H.maxX = vb->maxX; H.minY = vb->minY; H.maxY = vb->maxY;
+        H.nlevels = vb->nlevels; H.log_scale = vb->log_scale; H.sf = A.dev<float>(hf ? o_sf1 : o_sf2);
+        H.n = hf ? n2 : n1;
+        H.pos = A.dev<float>(hf ? o_p2 : o_p1); H.min_dist = A.dev<float>(hf ? o_mn2 : o_mn1); H.max_dist = A.dev<float>(hf ? o_mx2 : o_mx1);
+        H.skip = (hf ? skip2 : skip1) ? A.dev<uint8_t>(hf ? o_s2 : o_s1) : nullptr;
+    }
+    if ((rc = project_sim3_dev(c, S))) return rc;
+    RadBatchArgs B{};
+    B.kps = A.dev<eorb_keypoint>(o_k); B.desc = A.dev<uint8_t>(o_d); B.stride = 32; B.cell = A.dev<uint16_t>(o_cell);
+    B.kf_off = A.dev<int32_t>(o_off); B.g = A.dev<GridB>(o_g); B.K = 2; B.M = M;
+    B.valid = S.O.valid; B.uv = (const float*)S.O.uv; B.radius = S.O.radius; B.level = S.O.level; B.q_ur = S.O.q_ur;
+    B.q_desc = A.dev<uint8_t>(o_qd); B.q_desc_kstride = 32 * m;
+    B.best_idx = A.dev<int32_t>(o_bi); B.best_dist = A.dev<int32_t>(o_bd);
+    if ((rc = kf_radius_batch_dev(c, B, ntotal, A.dev<uint16_t>(o_cell)))) return rc;
+    if ((rc = sim3_agree_dev(c, B.best_idx, B.best_dist, M, n1, n2, th_high, A.dev<int32_t>(o_v1), A.dev<int32_t>(o_v2), A.dev<int32_t>(o_m12),
+                             A.dev<int32_t>(o_nf)))) return rc;
+    const char* h;
+    if ((rc = A.download(o_nf, ((vnMatch1 || vnMatch2) ? o_end : o_v1) - o_nf, &h))) return rc;
+    memcpy(match12, h + o_m12, 4 * (size_t)n1);
+    if (nfound) *nfound = *(const int32_t*)(h + o_nf);
+    if (vnMatch1) memcpy(vnMatch1, h + o_v1, 4 * (size_t)n1);
+    if (vnMatch2) memcpy(vnMatch2, h + o_v2, 4 * (size_t)n2);
+    return EORB_OK;
+}
+
 int eorb_bow_set_vocabulary(eorb_ctx* c, int nnodes, int L, const int32_t* child_off, const int32_t* child_ids,
                             const uint8_t* node_desc, const int32_t* word_id, const double* weight)
 {

@@ -1466,6 +1466,94 @@ int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell)
     return EORB_OK;
 }
 
+// The same search over K keyframes at once (eorb_fuse_keyframes, eorb_fuse_pose, eorb_search_by_sim3): the keyframes' keypoints are
+// concatenated (kf_off[K + 1]), query (k, m) is entry k * M + m of the projector's arrays.  One wavefront per query runs
+// radius_scan<false> over keyframe k's keypoint range with that keyframe's grid bounds; the queries are independent.
+__global__ void kf_cells_batch_kernel(const eorb_keypoint* __restrict__ kps, int ntotal, const int32_t* __restrict__ kf_off, int K,
+                                      const GridB* __restrict__ g, uint16_t* __restrict__ cell)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ntotal) return;
+    int lo = 0, hi = K - 1;                                     // the keyframe of keypoint i: the last k with kf_off[k] <= i
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (kf_off[mid] <= i) lo = mid; else hi = mid - 1; }
+    const GridB b = g[lo];
+    const int px = (int)roundf((kps[i].x - b.minX) * b.invW);
+    const int py = (int)roundf((kps[i].y - b.minY) * b.invH);
+    cell[i] = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? (uint16_t)0xFFFF : (uint16_t)(px * kGridRows + py);
+}
+
+__global__ __launch_bounds__(256) void kf_radius_batch_kernel(RadBatchArgs B)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t nq = (int64_t)B.K * B.M;
+    for (int64_t q = gw; q < nq; q += nw) {
+        const int k = (int)(q / B.M);
+        const int off = B.kf_off[k];
+        const size_t qo = (size_t)k * B.M;
+        RadArgs A{};
+        A.kps = B.kps + off; A.n = B.kf_off[k + 1] - off; A.desc = B.desc + (size_t)off * B.stride; A.stride = B.stride;
+        A.g = B.g[k]; A.cell = B.cell + off;
+        A.M = B.M; A.valid = B.valid + qo; A.uv = B.uv + 2 * qo; A.radius = B.radius + qo; A.level = B.level + qo;
+        A.q_desc = B.q_desc + (size_t)k * B.q_desc_kstride;
+        A.inv_sigma2 = B.inv_sigma2; A.nlevels = B.nlevels;
+        A.uright = B.uright ? B.uright + off : nullptr; A.q_ur = B.uright ? B.q_ur + qo : nullptr;
+        const int m = (int)(q - (int64_t)qo);
+        uint64_t k0 = ~0ull;
+        if (A.valid[m]) k0 = radius_scan<false>(A, m, lane, 64, nullptr);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k0, d, 64); k0 = o < k0 ? o : k0; }
+        if (lane == 0) {
+            const bool ok = k0 != ~0ull && (int)(k0 >> 44) < 256;
+            B.best_idx[q] = ok ? (int)(k0 & 0xffffffffu) : -1;
+            B.best_dist[q] = ok ? (int)(k0 >> 44) : 256;
+        }
+    }
+}
+
+// the agreement pass of SearchBySim3 (:1948-1964) over a 2 x M batch: row 0 = KF1's points searched in KF2, row 1 the reverse
+__global__ void sim3_agree_kernel(const int32_t* __restrict__ best_idx, const int32_t* __restrict__ best_dist, int M, int N1, int N2,
+                                  int th_high, int32_t* __restrict__ vn1, int32_t* __restrict__ vn2, int32_t* __restrict__ match12,
+                                  int32_t* __restrict__ nfound)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N2) vn2[i] = best_dist[M + i] <= th_high ? best_idx[M + i] : -1;
+    bool found = false;
+    if (i < N1) {
+        const int idx2 = best_dist[i] <= th_high ? best_idx[i] : -1;
+        vn1[i] = idx2;
+        if (idx2 >= 0 && idx2 < N2) {
+            const int idx1 = best_dist[M + idx2] <= th_high ? best_idx[M + idx2] : -1;
+            found = idx1 == i;
+        }
+        match12[i] = found ? idx2 : -1;
+    }
+    const unsigned long long b = __ballot(found);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(nfound, __popcll(b));
+}
+
+int kf_radius_batch_dev(eorb_ctx* c, const RadBatchArgs& B, int ntotal, uint16_t* d_cell)
+{
+    const int64_t nq = (int64_t)B.K * B.M;
+    if (nq <= 0) return EORB_OK;
+    ProfScope ps(c, "kf_radius_batch");
+    if (ntotal > 0) kf_cells_batch_kernel<<<(ntotal + 255) / 256, 256, 0, c->stream>>>(B.kps, ntotal, B.kf_off, B.K, B.g, d_cell);
+    kf_radius_batch_kernel<<<(unsigned)std::min<int64_t>((nq + 3) / 4, 8192), 256, 0, c->stream>>>(B);
+    EORB_LAUNCH_CHECK(c, "kf_radius_batch kernels");
+    return EORB_OK;
+}
+
+int sim3_agree_dev(eorb_ctx* c, const int32_t* best_idx, const int32_t* best_dist, int M, int N1, int N2, int th_high,
+                   int32_t* vn1, int32_t* vn2, int32_t* match12, int32_t* nfound)
+{
+    EORB_HIP(c, hipMemsetAsync(nfound, 0, sizeof(int32_t), c->stream));
+    const int n = std::max(N1, N2);
+    if (n <= 0) return EORB_OK;
+    sim3_agree_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(best_idx, best_dist, M, N1, N2, th_high, vn1, vn2, match12, nfound);
+    EORB_LAUNCH_CHECK(c, "sim3_agree_kernel");
+    return EORB_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // DBoW2 TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup)
 // (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1125-1250): the producer of the feature vectors the SearchByBoW kernels consume.

@@ -71,6 +71,18 @@ struct RadArgs {
     int32_t* best_idx; int32_t* best_dist;
 };
 
+// the radius match over K keyframes (match.hip kf_radius_batch_kernel): keypoints / descriptors / cells / uright of all keyframes
+// concatenated, keyframe k = rows kf_off[k] .. kf_off[k + 1] - 1 with grid bounds g[k]; the projector's arrays hold K * M queries,
+// (k, m) at k * M + m; the descriptor of query (k, m) is row m of q_desc + k * q_desc_kstride (0: all keyframes share the M rows)
+struct RadBatchArgs {
+    const eorb_keypoint* kps; const uint8_t* desc; int stride; const uint16_t* cell; const float* uright;
+    const int32_t* kf_off; const GridB* g; int K, M;
+    const uint8_t* valid; const float* uv; const float* radius; const int32_t* level; const float* q_ur;
+    const uint8_t* q_desc; size_t q_desc_kstride;
+    const float* inv_sigma2; int nlevels;
+    int32_t* best_idx; int32_t* best_dist;
+};
+
 // DBoW2 vocabulary tree, device resident (TemplatedVocabulary::m_nodes flattened; node 0 = root)
 struct BowVoc {
     int nnodes, L;
@@ -112,6 +124,9 @@ int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A);
 int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR, int cap, int32_t* d_lap, int32_t* d_idx2,
                      int32_t* d_kdist2, int32_t* d_cand, int32_t* d_dist2);
 int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell);
+int kf_radius_batch_dev(eorb_ctx* c, const RadBatchArgs& B, int ntotal, uint16_t* d_cell);
+int sim3_agree_dev(eorb_ctx* c, const int32_t* best_idx, const int32_t* best_dist, int M, int N1, int N2, int th_high,
+                   int32_t* vn1, int32_t* vn2, int32_t* match12, int32_t* nfound);
 int bow_transform_dev(eorb_ctx* c, const uint8_t* d_desc, int n, int stride, const BowVoc& V, int levelsup, int weighting, int norm,
                       uint32_t* d_word_of, double* d_w_of, uint32_t* d_node_of, uint32_t* d_bow_word, double* d_bow_val,
                       uint32_t* d_fv_node, int32_t* d_fv_off, int32_t* d_fv_idx, int32_t* d_counts);

@@ -1,6 +1,7 @@
 // project.hip -- map points projected on the device: Frame::isInFrustum / isInFrustumChecks (src/Frame.cc:548-637, :1252-1325),
 // MapPoint::PredictScale (src/MapPoint.cc:570-593) and the projection loops of ORBmatcher::SearchByProjection (src/ORBmatcher.cc
-// :1999-2022, :2092-2095, :2215-2239).  One thread per map point, float arithmetic in the reference's order with the double steps
+// :1999-2022, :2092-2095, :2215-2239), and the KeyFrame-side projections of Fuse, SearchByProjection(pKF, Scw, ...) and SearchBySim3
+// (:1463-1513, :1650-1690, :511-550, :1799-1830).  One thread per map point (and keyframe), float arithmetic in the reference's order with the double steps
 // of OpenCV 3.4.1 ("Parity choices of the projector"); the CPU restatement is tests/proj_ref/proj_ref.c.
 // The kernels write the caller-visible arrays and the packed records the matcher kernels read (match.hip), so a fused entry point
 // launches the matcher straight behind them.
@@ -187,6 +188,122 @@ __global__ __launch_bounds__(256) void project_kf_kernel(const KfArgs A)
         k.octave = level; k.class_id = level;                           // query level = nPredictedLevel (:2236)
         A.q_kps[i] = k;
     }
+}
+
+// ---- the KeyFrame-side modes -------------------------------------------------------------------------------------------------------
+// KeyFrame::IsInImage (src/KeyFrame.cc:919-922): the upper bounds are strict, and a NaN or an infinity fails by itself
+__device__ __forceinline__ bool kf_is_in_image(float x, float y, float minX, float maxX, float minY, float maxY)
+{
+    return x >= minX && x < maxX && y >= minY && y < maxY;
+}
+
+__device__ __forceinline__ void kfside_store(const KfSideDev& O, size_t i, bool valid, int reason, float u, float v, int level, float radius,
+                                             float q_ur, float dist)
+{
+    O.valid[i] = (uint8_t)(valid ? 1 : 0);
+    O.uv[i] = make_float2(u, v);
+    O.level[i] = level;
+    O.radius[i] = radius;
+    O.q_ur[i] = q_ur;
+    O.dist3d[i] = dist;
+    O.reason[i] = (uint8_t)reason;
+}
+
+// mode D: the projection of Fuse(pKF, vpMapPoints, th, bRight) (src/ORBmatcher.cc:1463-1513), Fuse(pKF, Scw, ...) (:1650-1690) and
+// SearchByProjection(pKF, Scw, ...) (:511-550, :595-), one thread per (keyframe, map point).  A rejected point keeps uv = (-1, -1)
+// and q_ur = 0 until IsInImage has passed, dist3d = 0 until it was computed, level = -1 and radius = 0 throughout.
+__global__ __launch_bounds__(256) void project_kfside_kernel(const KfSideArgs A)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)A.K * A.M) return;
+    const int k = (int)(i / A.M), m = (int)(i - (size_t)k * A.M);
+    bool valid = false;
+    int reason = 0, level = -1;
+    float u = -1.f, v = -1.f, radius = 0.f, q_ur = 0.f, dist3D = 0.f;
+    if (A.skip && A.skip[i]) reason = 1;
+    else {
+        const KfPose& V = A.V[k];
+        const float P[3] = {A.pos[3 * (size_t)m], A.pos[3 * (size_t)m + 1], A.pos[3 * (size_t)m + 2]};
+        float p3Dc[3];
+        cv_gemm3x1(V.R, P, V.t, 1.0, p3Dc);                             // Rcw*p3Dw + tcw
+        const float z = p3Dc[2];
+        float pu = -1.f, pv = -1.f;
+        if (!(z < 0.0f)) cam_project_f(V.cam, p3Dc, pu, pv);           // a zero depth goes on (:1467)
+        if (z < 0.0f) reason = 2;
+        else if (!kf_is_in_image(pu, pv, V.minX, V.maxX, V.minY, V.maxY)) reason = 3;
+        else {
+            u = pu; v = pv;
+            q_ur = pu - V.mbf * (1.0f / z);                             // ur = uv.x - bf*invz (:1473, :1487)
+            const float PO[3] = {P[0] - V.Ow[0], P[1] - V.Ow[1], P[2] - V.Ow[2]};
+            dist3D = (float)cv_norm3(PO);
+            const float minD = A.min_dist[m], maxD = A.max_dist[m];
+            const float Pn[3] = {A.normal[3 * (size_t)m], A.normal[3 * (size_t)m + 1], A.normal[3 * (size_t)m + 2]};
+            if (dist3D < 0.8f * minD || dist3D > 1.2f * maxD) reason = 5;
+            else if (cv_dot3(PO, Pn) < 0.5 * (double)dist3D) reason = 6;   // "PO.dot(Pn)<0.5*dist3D": a comparison of doubles (:1504)
+            else {
+                level = predict_scale(maxD, dist3D, A.nlevels, A.log_scale);
+                radius = A.th * A.sf[level];
+                valid = true;
+            }
+        }
+    }
+    kfside_store(A.O, i, valid, reason, u, v, level, radius, q_ur, dist3D);
+}
+
+// mode E: the two projections of SearchBySim3 (:1799-1830, :1879-1910), one thread per (direction, keypoint slot)
+__global__ __launch_bounds__(256) void project_sim3_kernel(const Sim3Args A)
+{
+    const int h = blockIdx.y, m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= A.M) return;
+    const Sim3Half& S = A.H[h];
+    bool valid = false;
+    int reason = 0, level = -1;
+    float u = -1.f, v = -1.f, radius = 0.f, dist3D = 0.f;
+    if (m >= S.n || (S.skip && S.skip[m])) reason = 1;
+    else {
+        const float P[3] = {S.pos[3 * (size_t)m], S.pos[3 * (size_t)m + 1], S.pos[3 * (size_t)m + 2]};
+        float pa[3], pb[3];
+        cv_gemm3x1(S.Ra, P, S.ta, 1.0, pa);                             // R1w*p3Dw + t1w
+        cv_gemm3x1(S.sRb, pa, S.tb, 1.0, pb);                           // sR21*p3Dc1 + t21
+        if (pb[2] < 0.0f) reason = 2;
+        else {
+            const float invz = (float)(1.0 / (double)pb[2]);
+            const float x = pb[0] * invz, y = pb[1] * invz;
+            const float pu = S.fx * x + S.cx, pv = S.fy * y + S.cy;
+            if (!kf_is_in_image(pu, pv, S.minX, S.maxX, S.minY, S.maxY)) reason = 3;
+            else {
+                u = pu; v = pv;
+                dist3D = (float)cv_norm3(pb);                           // cv::norm(p3Dc2): the camera-frame norm
+                const float minD = S.min_dist[m], maxD = S.max_dist[m];
+                if (dist3D < 0.8f * minD || dist3D > 1.2f * maxD) reason = 5;
+                else {
+                    level = predict_scale(maxD, dist3D, S.nlevels, S.log_scale);
+                    radius = A.th * S.sf[level];
+                    valid = true;
+                }
+            }
+        }
+    }
+    kfside_store(A.O, (size_t)h * A.M + m, valid, reason, u, v, level, radius, 0.f, dist3D);
+}
+
+int project_kfside_dev(eorb_ctx* c, const KfSideArgs& A)
+{
+    const size_t n = (size_t)A.K * A.M;
+    if (n == 0) return EORB_OK;
+    ProfScope ps(c, "project_kfside");
+    project_kfside_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(A);
+    EORB_LAUNCH_CHECK(c, "project_kfside_kernel");
+    return EORB_OK;
+}
+
+int project_sim3_dev(eorb_ctx* c, const Sim3Args& A)
+{
+    if (A.M <= 0) return EORB_OK;
+    ProfScope ps(c, "project_sim3");
+    project_sim3_kernel<<<dim3((A.M + 255) / 256, 2), 256, 0, c->stream>>>(A);
+    EORB_LAUNCH_CHECK(c, "project_sim3_kernel");
+    return EORB_OK;
 }
 
 int project_frustum_dev(eorb_ctx* c, const FrustumArgs& A)

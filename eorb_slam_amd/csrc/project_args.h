@@ -46,7 +46,42 @@ struct KfArgs {            // mode C: SearchByProjection(CurrentFrame, pKF, sAlr
     const eorb_keypoint* kf_kps; eorb_keypoint* q_kps;      // optional: the matcher's query keypoints, octave = class_id = level
 };
 
+// pose, camera and image bounds of one keyframe of the KeyFrame-side modes (an eorb_view without its tables: the batch shares one)
+struct KfPose {
+    float R[9], t[3], Ow[3];
+    WarpCam cam;
+    float minX, maxX, minY, maxY, mbf;
+};
+
+// per (keyframe, map point) outputs of modes D and E, K * M entries each: what kf_radius_batch_dev (match.hip) reads, plus the test aids
+struct KfSideDev {
+    uint8_t* valid; float2* uv; int32_t* level; float* radius; float* q_ur; float* dist3d; uint8_t* reason;
+};
+
+struct KfSideArgs {        // mode D: Fuse (both overloads), SearchByProjection(pKF, Scw, ...)
+    const KfPose* V; int K, M;                                  // V: device array of K poses
+    int nlevels; float log_scale; const float* sf; float th;
+    const float* pos; const float* normal; const float* min_dist; const float* max_dist;
+    const uint8_t* skip;                                        // K * M or NULL
+    KfSideDev O;
+};
+
+struct Sim3Half {          // mode E, one direction: p3Dc_b = sRba * (Raw * p3Dw + taw) + tba, searched in keyframe b
+    float Ra[9], ta[3], sRb[9], tb[3];
+    float fx, fy, cx, cy;                                       // pKF1's in both directions (:1746-1749)
+    float minX, maxX, minY, maxY;                               // keyframe b's IsInImage
+    int nlevels; float log_scale; const float* sf;              // keyframe b's tables
+    int n; const float* pos; const float* min_dist; const float* max_dist; const uint8_t* skip;
+};
+
+struct Sim3Args {          // both halves in one launch; outputs as a 2 x M batch (M >= both n, the tail of a half invalid)
+    Sim3Half H[2]; int M; float th;
+    KfSideDev O;
+};
+
 int project_frustum_dev(eorb_ctx* c, const FrustumArgs& A);
+int project_kfside_dev(eorb_ctx* c, const KfSideArgs& A);
+int project_sim3_dev(eorb_ctx* c, const Sim3Args& A);
 int project_last_dev(eorb_ctx* c, const LastArgs& A);
 int project_kf_dev(eorb_ctx* c, const KfArgs& A);
 

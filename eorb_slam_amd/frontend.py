@@ -937,6 +937,126 @@ def SearchBySim3(kf1, kf2, q1, q2, th=7.5, ctx=None):
     return int(ok.sum()), np.where(ok, vn1, -1).astype(np.int32)
 
 
+# ---- KeyFrame-side matchers with the projection on the device ------------------------------------------------------------------------
+_KFSIDE_FIELDS = (("valid", np.uint8, 1), ("uv", np.float32, 2), ("radius", np.float32, 1), ("level", np.int32, 1), ("q_ur", np.float32, 1),
+                  ("dist3d", np.float32, 1), ("reason", np.uint8, 1))
+
+
+def _kfside_out(n, want=True):
+    """-> (eorb_kfside_out or None, dict of the arrays behind it)"""
+    if not want:
+        return None, None
+    rec = _lib.KfSideOut()
+    d = {}
+    for name, dt, k in _KFSIDE_FIELDS:
+        d[name] = np.zeros((n, k) if k > 1 else n, dt)
+        setattr(rec, name, d[name].ctypes.data if n else None)
+    rec._keep = d
+    return rec, d
+
+
+def _kf(kps, desc):
+    kps = np.ascontiguousarray(kps, KP_DTYPE)
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(len(kps), -1) if len(kps) else np.zeros((0, 32), np.uint8)
+    return kps, desc, desc.shape[1]
+
+
+def ProjectKeyFrameSide(view_, pos, normal, min_dist, max_dist, th, skip=None, ctx=None):
+    """the projection of Fuse (src/ORBmatcher.cc:1463-1513, :1650-1690) and SearchByProjection(pKF, Scw, ...) (:511-550) for one view
+    -> dict(valid, uv, radius, level, q_ur, dist3d, reason): what KeyFrameRadiusMatch takes, plus the test aids"""
+    c = ctx or default_context()
+    pos, normal, min_dist, max_dist, skip, _ = _points(pos, normal, min_dist, max_dist, skip, None)
+    M = len(min_dist)
+    rec, d = _kfside_out(M)
+    c.check(c.L.eorb_project_keyframe_side(c.h, C.byref(view_), M, _p(pos), _p(normal), _p(min_dist), _p(max_dist), _p(skip), float(th), C.byref(rec)))
+    return d
+
+
+def FusePose(kps, desc, gb, view_, pos, normal, min_dist, max_dist, q_desc, inv_sigma2=None, th=3.0, skip=None, uright=None,
+             want_projection=False, ctx=None):
+    """ORBmatcher::Fuse(pKF, vpMapPoints, th) up to the map update (src/ORBmatcher.cc:1439-1578), projection included; inv_sigma2 None:
+    the Sim3 overload (:1642-1720).  uright = pKF->mvuRight selects the stereo gate.  -> (best_idx, best_dist[, projection dict]); the
+    caller thresholds with TH_LOW."""
+    c = ctx or default_context()
+    kps, desc, stride = _kf(kps, desc)
+    pos, normal, min_dist, max_dist, skip, _ = _points(pos, normal, min_dist, max_dist, skip, None)
+    q_desc = np.ascontiguousarray(q_desc, np.uint8)
+    isg = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+    ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+    M = len(min_dist)
+    bi = np.zeros(M, np.int32); bd = np.zeros(M, np.int32)
+    rec, d = _kfside_out(M, want_projection)
+    c.check(c.L.eorb_fuse_pose(c.h, _p(kps), len(kps), _p(desc), stride, C.byref(gb), C.byref(view_), M, _p(pos), _p(normal), _p(min_dist),
+                               _p(max_dist), _p(skip), _p(q_desc), _p(isg), _p(ur), float(th), _p(bi), _p(bd),
+                               None if rec is None else C.byref(rec)))
+    return (bi, bd, d) if want_projection else (bi, bd)
+
+
+def SearchByProjectionKFScw(kps, desc, gb, view_, pos, normal, min_dist, max_dist, q_desc, taken, th, ratioHamming=1.0, skip=None,
+                            want_projection=False, ctx=None):
+    """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (src/ORBmatcher.cc:487-590) up to the assignment
+    of vpMatched: queries in order, taken = the keypoints that hold a match.  -> (best_idx, best_dist, taken[, projection dict])"""
+    c = ctx or default_context()
+    kps, desc, stride = _kf(kps, desc)
+    pos, normal, min_dist, max_dist, skip, _ = _points(pos, normal, min_dist, max_dist, skip, None)
+    q_desc = np.ascontiguousarray(q_desc, np.uint8)
+    tk = np.array(taken, np.uint8)
+    M = len(min_dist)
+    bi = np.zeros(M, np.int32); bd = np.zeros(M, np.int32)
+    rec, d = _kfside_out(M, want_projection)
+    c.check(c.L.eorb_search_by_projection_kf_scw(c.h, _p(kps), len(kps), _p(desc), stride, C.byref(gb), C.byref(view_), M, _p(pos), _p(normal),
+                                                 _p(min_dist), _p(max_dist), _p(skip), _p(q_desc), float(th), _p(tk),
+                                                 float(np.float32(ORBmatcher.TH_LOW) * np.float32(ratioHamming)), _p(bi), _p(bd),
+                                                 None if rec is None else C.byref(rec)))
+    return (bi, bd, tk, d) if want_projection else (bi, bd, tk)
+
+
+def SearchBySim3Pose(kf1, kf2, sR12, t12, sR21, t21, th=7.5, th_high=ORBmatcher.TH_HIGH, ctx=None):
+    """ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1743-1967) in one call, projections included.  kf = dict(kps, desc, gb, view, pos,
+    min_dist, max_dist, mp_desc, skip): per keypoint slot the map point it holds, skip = no map point, bad or already matched
+    (:1773-1783); sR12 = s12*R12, sR21 = (1/s12)*R12.t(), t21 = -sR21*t12 (:1760-1762, the caller's).
+    -> (nFound, match12, vnMatch1, vnMatch2)"""
+    c = ctx or default_context()
+    a = []
+    for kf in (kf1, kf2):
+        kps, desc, stride = _kf(kf["kps"], kf["desc"])
+        n = len(kps)
+        f = lambda x, dt: np.ascontiguousarray(x, dt)
+        skip = None if kf.get("skip") is None else f(kf["skip"], np.uint8)
+        a.append((kps, n, desc, stride, kf["gb"], kf["view"], f(kf["pos"], np.float32), f(kf["min_dist"], np.float32), f(kf["max_dist"], np.float32),
+                  f(kf["mp_desc"], np.uint8), skip))
+    n1, n2 = a[0][1], a[1][1]
+    m12 = np.zeros(n1, np.int32); v1 = np.zeros(n1, np.int32); v2 = np.zeros(n2, np.int32)
+    nf = C.c_int(0)
+    mats = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in (sR12, t12, sR21, t21)]
+    side = lambda s: (_p(s[0]), s[1], _p(s[2]), s[3], C.byref(s[4]), C.byref(s[5]), _p(s[6]), _p(s[7]), _p(s[8]), _p(s[9]), _p(s[10]))
+    c.check(c.L.eorb_search_by_sim3(c.h, *side(a[0]), *side(a[1]), *[_p(x) for x in mats], float(th), int(th_high), _p(m12), C.byref(nf), _p(v1), _p(v2)))
+    return nf.value, m12, v1, v2
+
+
+def FuseKeyFrames(views, gbs, kps, desc, kf_off, pos, normal, min_dist, max_dist, q_desc, inv_sigma2=None, th=3.0, skip=None, uright=None,
+                  want_reason=False, ctx=None):
+    """Fuse of M shared map points into K keyframes in one call (LocalMapping::SearchInNeighbors, LoopClosing::SearchAndFuse): views /
+    gbs per keyframe, keypoints / descriptors / uright of all keyframes concatenated with kf_off[K + 1]; skip K x M.
+    -> (best_idx K x M relative to the keyframe, best_dist K x M[, reason K x M]).  The caller applies the rows in the reference's
+    keyframe order and re-tests isBad() / IsInKeyFrame(pKF_k) before each (include/eorb_fe.h)."""
+    c = ctx or default_context()
+    va, K = _views(views)
+    ga = (_lib.GridBounds * K)(*gbs)
+    kps, desc, stride = _kf(kps, desc)
+    off = np.ascontiguousarray(kf_off, np.int32)
+    pos, normal, min_dist, max_dist, skip, _ = _points(pos, normal, min_dist, max_dist, skip, None)
+    q_desc = np.ascontiguousarray(q_desc, np.uint8)
+    isg = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32)
+    ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+    M = len(min_dist)
+    bi = np.zeros((K, M), np.int32); bd = np.zeros((K, M), np.int32)
+    rs = np.zeros((K, M), np.uint8) if want_reason else None
+    c.check(c.L.eorb_fuse_keyframes(c.h, va, ga, K, _p(kps), _p(desc), stride, _p(ur), _p(off), M, _p(pos), _p(normal), _p(min_dist), _p(max_dist),
+                                    _p(q_desc), _p(skip), _p(isg), float(th), _p(bi), _p(bd), _p(rs)))
+    return (bi, bd, rs) if want_reason else (bi, bd)
+
+
 class ELK_Tracker:
     """EORB_SLAM::ELK_Tracker (src/Event/KLT_Tracker.cpp): pyramidal LK on the device + the reference's match bookkeeping."""
 

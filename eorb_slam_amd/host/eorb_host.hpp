@@ -760,6 +760,79 @@ public:
                                             uv.data(), radius.data(), level.data(), mpDesc.ptr(), invSigma2.data(), (int)invSigma2.size(),
                                             uright.data(), qUr.data(), bestIdx.data(), bestDist.data()));
     }
+    // ---- the KeyFrame-side matchers with the projection on the device (see include/eorb_fe.h) ----
+    // the map points handed to Fuse / SearchByProjection(pKF, Scw): GetWorldPos, GetNormal, mfMinDistance, mfMaxDistance, 3 / 3 / 1 / 1
+    // floats per point, and GetDescriptor; skip (optional): !pMP, isBad(), IsInKeyFrame(pKF) / spAlreadyFound
+    struct MapPoints { std::vector<float> pos, normal, minDist, maxDist; eorb_host::Mat8 desc; std::vector<uint8_t> skip;
+                       int size() const { return (int)minDist.size(); } };
+    // what the projection leaves per (keyframe, map point): eorb_kfside_out
+    struct SideProjection { std::vector<uint8_t> valid, reason; std::vector<float> uv, radius, qUr, dist3D; std::vector<int> level;
+        eorb_kfside_out bind(size_t n) {
+            valid.assign(n, 0); reason.assign(n, 0); uv.assign(2 * n, 0.f); radius.assign(n, 0.f); qUr.assign(n, 0.f); dist3D.assign(n, 0.f);
+            level.assign(n, 0);
+            return eorb_kfside_out{valid.data(), uv.data(), radius.data(), level.data(), qUr.data(), dist3D.data(), reason.data()};
+        } };
+    // the projection of Fuse / SearchByProjection(pKF, Scw) alone (:1463-1513, :1650-1690, :511-550)
+    void ProjectKeyFrameSide(const eorb_view& view, const MapPoints& P, float th, SideProjection& out) {
+        auto& c = eorb_host::thread_context();
+        const eorb_kfside_out o = out.bind((size_t)P.size());
+        c.check(eorb_project_keyframe_side(c.get(), &view, P.size(), P.pos.data(), P.normal.data(), P.minDist.data(), P.maxDist.data(),
+                                           P.skip.empty() ? nullptr : P.skip.data(), th, &o));
+    }
+    // Fuse(pKF, vpMapPoints, th) up to the map update (:1439-1578); invSigma2 == nullptr: Fuse(pKF, Scw, ...) (:1642-1720); uright =
+    // pKF->mvuRight or nullptr.  The caller thresholds bestDist with TH_LOW and performs Replace / AddObservation in order.
+    void Fuse(const FrameView& KF, const eorb_view& view, const MapPoints& P, const std::vector<float>* invSigma2,
+              const std::vector<float>* uright, float th, std::vector<int>& bestIdx, std::vector<int>& bestDist, SideProjection* proj = nullptr) {
+        auto& c = eorb_host::thread_context();
+        const int M = P.size();
+        bestIdx.assign(M, -1); bestDist.assign(M, 256);
+        eorb_kfside_out o{};
+        if (proj) o = proj->bind((size_t)M);
+        c.check(eorb_fuse_pose(c.get(), KF.kps->data(), KF.numAllKPts(), KF.desc->ptr(), KF.desc->cols ? KF.desc->cols : 32, &KF.gb, &view, M,
+                               P.pos.data(), P.normal.data(), P.minDist.data(), P.maxDist.data(), P.skip.empty() ? nullptr : P.skip.data(),
+                               P.desc.ptr(), invSigma2 ? invSigma2->data() : nullptr, uright ? uright->data() : nullptr, th, bestIdx.data(),
+                               bestDist.data(), proj ? &o : nullptr));
+    }
+    // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) up to the assignment of vpMatched (:487-590): taken in / out
+    void SearchByProjection(const FrameView& KF, const eorb_view& view, const MapPoints& P, std::vector<uint8_t>& taken, float th,
+                            float ratioHamming, std::vector<int>& bestIdx, std::vector<int>& bestDist) {
+        auto& c = eorb_host::thread_context();
+        const int M = P.size();
+        bestIdx.assign(M, -1); bestDist.assign(M, 256);
+        c.check(eorb_search_by_projection_kf_scw(c.get(), KF.kps->data(), KF.numAllKPts(), KF.desc->ptr(), KF.desc->cols ? KF.desc->cols : 32,
+                                                 &KF.gb, &view, M, P.pos.data(), P.normal.data(), P.minDist.data(), P.maxDist.data(),
+                                                 P.skip.empty() ? nullptr : P.skip.data(), P.desc.ptr(), th, taken.data(),
+                                                 (float)TH_LOW * ratioHamming, bestIdx.data(), bestDist.data(), nullptr));
+    }
+    // SearchBySim3 (:1743-1967) in one call: P1 / P2 = the map points of the keyframes' keypoint slots (skip: none, bad or already
+    // matched), sR12 / t12 / sR21 / t21 as at :1760-1762.  match12[i1] = index in KF2 or -1; returns nFound
+    int SearchBySim3(const FrameView& KF1, const eorb_view& view1, const MapPoints& P1, const FrameView& KF2, const eorb_view& view2,
+                     const MapPoints& P2, const float sR12[9], const float t12[3], const float sR21[9], const float t21[3], float th,
+                     std::vector<int>& match12) {
+        auto& c = eorb_host::thread_context();
+        match12.assign(KF1.numAllKPts(), -1); int nf = 0;
+        c.check(eorb_search_by_sim3(c.get(), KF1.kps->data(), KF1.numAllKPts(), KF1.desc->ptr(), KF1.desc->cols ? KF1.desc->cols : 32, &KF1.gb,
+                                    &view1, P1.pos.data(), P1.minDist.data(), P1.maxDist.data(), P1.desc.ptr(),
+                                    P1.skip.empty() ? nullptr : P1.skip.data(), KF2.kps->data(), KF2.numAllKPts(), KF2.desc->ptr(),
+                                    KF2.desc->cols ? KF2.desc->cols : 32, &KF2.gb, &view2, P2.pos.data(), P2.minDist.data(), P2.maxDist.data(),
+                                    P2.desc.ptr(), P2.skip.empty() ? nullptr : P2.skip.data(), sR12, t12, sR21, t21, th, TH_HIGH,
+                                    match12.data(), &nf, nullptr, nullptr));
+        return nf;
+    }
+    // Fuse of P into K keyframes at once (SearchInNeighbors, SearchAndFuse): KFs = the keyframes concatenated (keypoints, descriptors,
+    // kfOff[K + 1]), P.skip = K x M or empty.  bestIdx / bestDist: K x M, applied by the caller keyframe by keyframe with the re-tests
+    // that include/eorb_fe.h lists.
+    void FuseKeyFrames(const std::vector<eorb_view>& views, const std::vector<eorb_grid_bounds>& gbs, const std::vector<eorb_host::KeyPoint>& kps,
+                       const eorb_host::Mat8& desc, const std::vector<int32_t>& kfOff, const MapPoints& P, const std::vector<float>* invSigma2,
+                       const std::vector<float>* uright, float th, std::vector<int>& bestIdx, std::vector<int>& bestDist) {
+        auto& c = eorb_host::thread_context();
+        const int K = (int)views.size(), M = P.size();
+        bestIdx.assign((size_t)K * M, -1); bestDist.assign((size_t)K * M, 256);
+        c.check(eorb_fuse_keyframes(c.get(), views.data(), gbs.data(), K, kps.data(), desc.ptr(), desc.cols ? desc.cols : 32,
+                                    uright ? uright->data() : nullptr, kfOff.data(), M, P.pos.data(), P.normal.data(), P.minDist.data(),
+                                    P.maxDist.data(), P.desc.ptr(), P.skip.empty() ? nullptr : P.skip.data(),
+                                    invSigma2 ? invSigma2->data() : nullptr, th, bestIdx.data(), bestDist.data(), nullptr));
+    }
 protected:
     float mfNNratio; bool mbCheckOrientation;
 };

@@ -533,3 +533,130 @@ def planted_frame(valid, uv, level, q_desc, n, W, H, nlevels=8, seed=0, jitter=1
     src[:k] = pick
     perm = rng.permutation(n)
     return kps[perm], np.ascontiguousarray(desc[perm]), src[perm]
+
+
+# ---- KeyFrame-side matchers: a neighbourhood of keyframes around shared points, and a Sim3 pair -----------------------------------
+def _approx_side_projection(R, t, Ow, cam, bounds, P, nrm, dmin, dmax, nlevels, scaleFactor):
+    """float64 sketch of the KeyFrame-side projection, for planting keypoints only (the restatement decides every outcome)
+    -> (valid, uv, level, z)"""
+    P = P.astype(np.float64)
+    Pc = P @ R.astype(np.float64).T + t
+    z = Pc[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uv = project_np(cam, Pc)
+    PO = P - Ow
+    dist = np.linalg.norm(PO, axis=1)
+    ok = (z > 0) & (uv[:, 0] >= bounds[0]) & (uv[:, 0] < bounds[1]) & (uv[:, 1] >= bounds[2]) & (uv[:, 1] < bounds[3])
+    ok &= (dist >= 0.8 * dmin) & (dist <= 1.2 * dmax) & (np.sum(PO * nrm, axis=1) >= 0.5 * dist)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lv = np.ceil(np.log(dmax / np.maximum(dist, 1e-12)) / np.log(scaleFactor))
+    lv = np.clip(np.nan_to_num(lv), 0, nlevels - 1).astype(np.int32)
+    return ok.astype(np.uint8), np.nan_to_num(uv).astype(np.float32), lv, z
+
+
+def keyframe_neighbourhood(seed, K, M, n_kps=1000, W=346, H=260, nlevels=8, scaleFactor=1.2, mbf=35.0, cam=None, jitter=2.5):
+    """K keyframes around the M shared map points of map_scene(seed, M): keyframe k is the scene's camera moved a little, and holds
+    n_kps[k] keypoints (an int serves all; 0 gives an empty keyframe) planted by planted_frame on a float64 sketch of its projection.
+    uright: none (-1) for a third of the keypoints, near the point's predicted right coordinate for most of the rest, 2-6 px off for
+    some (the stereo gate's third term then decides).  -> dict(views = [keyword dicts for frontend.view / proj_ref.view], kps, desc,
+    src, uright = lists per keyframe, pos, normal, min_dist, max_dist, mp_desc, scale_factors, inv_sigma2)"""
+    s = map_scene(seed, M, W, H, nlevels=nlevels, scaleFactor=scaleFactor)
+    rng = np.random.default_rng(seed + 1000)
+    n_kps = [int(n_kps)] * K if np.isscalar(n_kps) else [int(n) for n in n_kps]
+    cam = tuple(cam) if cam is not None else s["cam"]
+    mp_desc = random_descriptors(M, seed=seed + 1)
+    sf = s["scale_factors"]
+    inv_sigma2 = (np.float32(1.0) / (sf * sf)).astype(np.float32)
+    views, kps, desc, src, uright = [], [], [], [], []
+    R0, t0 = s["R"].astype(np.float64), s["t"].astype(np.float64)
+    for k in range(K):
+        dR = rot(*(rng.uniform(-0.06, 0.06, 3) * (k > 0))).astype(np.float64)
+        R = (dR @ R0).astype(np.float32)
+        t = (dR @ t0 + rng.uniform(-0.4, 0.4, 3) * (k > 0)).astype(np.float32)
+        Ow = (-R.T.astype(np.float64) @ t).astype(np.float32)
+        views.append(dict(R=R, t=t, Ow=Ow, cam=cam, bounds=s["bounds"], nlevels=nlevels, log_scale=s["log_scale"], scale_factors=sf, mbf=mbf))
+        ok, uv, lv, z = _approx_side_projection(R, t, Ow, cam, s["bounds"], s["pos"], s["normal"], s["min_dist"], s["max_dist"], nlevels, scaleFactor)
+        kp, d, sr = planted_frame(ok, uv, lv, mp_desc, n_kps[k], W, H, nlevels=nlevels, seed=seed + 10 * k + 2, jitter=jitter)
+        n = n_kps[k]
+        qur = uv[:, 0] - mbf / np.where(z > 0, z, 1.0)
+        ur = np.where(sr >= 0, qur[np.maximum(sr, 0)] + rng.uniform(-1, 1, n), kp["x"] - rng.uniform(1, 30, n)).astype(np.float32)
+        off = rng.random(n) < 0.3
+        ur[off] += (rng.uniform(2, 6, n) * rng.choice([-1, 1], n)).astype(np.float32)[off]
+        ur[rng.random(n) < 0.33] = -1.0
+        kps.append(kp); desc.append(d); src.append(sr); uright.append(ur)
+    return dict(views=views, kps=kps, desc=desc, src=src, uright=uright, pos=s["pos"], normal=s["normal"], min_dist=s["min_dist"],
+                max_dist=s["max_dist"], mp_desc=mp_desc, scale_factors=sf, inv_sigma2=inv_sigma2, W=W, H=H)
+
+
+def sim3_pair(seed, n=1000, s12=1.0, W=346, H=260, f=280.0, nlevels=8, scaleFactor=1.2, n_both=220, n_one=120, n_cross=120):
+    """Two keyframes of n keypoint slots each and a similarity S12 between their cameras (p_c1 = s12*R12*p_c2 + t12), for
+    ORBmatcher::SearchBySim3.  Physical points seen by both cameras get a keypoint in each keyframe, with the point's descriptor:
+      - n_both of them hold consistent map points in both slots: the two searches agree;
+      - n_one have no map point in KF2's slot (skip2): found from KF1 only, removed by the agreement pass;
+      - n_cross hold in KF2's slot the map point of another pair (its position and descriptor): the two directions disagree.
+    The other slots hold map points from a box around the camera (behind it, outside the image, outside the distance range) or none.
+    -> dict(kf1, kf2 = dict(kps, desc, view = keyword dict, pos, min_dist, max_dist, mp_desc, skip), sR12, t12, sR21, t21, W, H)"""
+    rng = np.random.default_rng(seed)
+    sf, log_scale = scale_tables(nlevels, scaleFactor)
+    cam = (float(f), float(f), W / 2.0, H / 2.0)
+    bounds = (0.0, float(W), 0.0, float(H))
+    Rw = [rot(0.05, -0.1, 0.02), rot(-0.2, 0.15, 0.1)]                         # R1w, R2w
+    tw = [np.array([0.3, -0.2, 0.1], np.float32), np.array([-1.0, 0.4, 0.6], np.float32)]
+    R12 = rot(0.03, -0.05, 0.02).astype(np.float32)
+    t12 = np.array([0.25, -0.1, 0.15], np.float32)
+    # :1760-1762 in float, as cv::Mat evaluates them: scalar products, then a 3x3 by 3x1 product
+    sR12 = (np.float32(s12) * R12).astype(np.float32)
+    sR21 = (np.float64(1.0 / np.float32(s12)) * R12.T.astype(np.float64)).astype(np.float32)
+    t21 = (-(sR21.astype(np.float64) @ t12.astype(np.float64))).astype(np.float32)
+    S21 = lambda X: X @ sR21.astype(np.float64).T + t21
+    S12 = lambda X: X @ sR12.astype(np.float64).T + t12
+    world = lambda k, Xc: ((Xc - tw[k]) @ Rw[k].astype(np.float64)).astype(np.float32)          # R^T (Xc - t)
+    ng = n_both + n_one + n_cross
+    assert ng <= n
+    X1 = np.stack([rng.uniform(-2.0, 2.0, ng), rng.uniform(-1.5, 1.5, ng), rng.uniform(4.0, 9.0, ng)], 1)      # in camera 1
+    X2 = S21(X1)
+    L = rng.integers(0, nlevels, ng)
+    d = random_descriptors(ng, seed=seed + 1)
+    kf = []
+    for k, X in ((0, X1), (1, X2)):
+        kps = random_keypoints(n, W, H, nlevels=nlevels, seed=seed + 2 + k)
+        desc = random_descriptors(n, seed=seed + 4 + k)
+        uv = project_np(cam, X)
+        kps["x"][:ng] = uv[:, 0] + rng.uniform(-1.5, 1.5, ng); kps["y"][:ng] = uv[:, 1] + rng.uniform(-1.5, 1.5, ng)
+        kps["octave"][:ng] = np.clip(L + rng.choice([-1, 0], ng), 0, nlevels - 1)
+        for j in range(ng):
+            desc[j] = flip_bits(d[j], int(rng.integers(0, 25)), rng)
+        # the slots' own map points: the physical point for the planted slots, a box around the camera for the rest
+        Xc = np.stack([rng.uniform(-6, 6, n), rng.uniform(-5, 5, n), rng.uniform(-2, 12, n)], 1)
+        Xc[:ng] = X
+        dist_other = np.linalg.norm(S21(Xc) if k == 0 else S12(Xc), axis=1)                     # the norm the other camera's test reads
+        dmax = dist_other * scaleFactor ** rng.uniform(-3, nlevels + 2, n)
+        dmax[:ng] = dist_other[:ng] * scaleFactor ** (L - 0.5)
+        mp_desc = random_descriptors(n, seed=seed + 6 + k)
+        for j in range(ng):
+            mp_desc[j] = flip_bits(d[j], int(rng.integers(0, 25)), rng)
+        skip = (rng.random(n) < 0.15).astype(np.uint8)
+        skip[:ng] = 0
+        kf.append(dict(kps=kps, desc=desc, Xc=Xc, dmax=dmax, mp_desc=mp_desc, skip=skip))
+    # KF2's slots of the one-sided pairs hold no map point; those of the crossed pairs hold another pair's point
+    one = np.arange(n_both, n_both + n_one); cross = np.arange(n_both + n_one, ng)
+    kf[1]["skip"][one] = 1
+    other = np.roll(cross, 1)
+    kf[1]["Xc"][cross] = X2[other]
+    kf[1]["dmax"][cross] = np.linalg.norm(X1[other], axis=1) * scaleFactor ** (L[other] - 0.5)
+    for j, o in zip(cross, other):
+        kf[1]["mp_desc"][j] = flip_bits(d[o], int(rng.integers(0, 25)), rng)
+    out = {}
+    for k in (0, 1):
+        perm = rng.permutation(n)
+        g = kf[k]
+        dmax = g["dmax"].astype(np.float32)
+        out["kf%d" % (k + 1)] = dict(
+            kps=g["kps"][perm], desc=np.ascontiguousarray(g["desc"][perm]),
+            view=dict(R=Rw[k], t=tw[k], Ow=(-Rw[k].T.astype(np.float64) @ tw[k]).astype(np.float32), cam=cam, bounds=bounds, nlevels=nlevels,
+                      log_scale=log_scale, scale_factors=sf),
+            pos=np.ascontiguousarray(world(k, g["Xc"])[perm]), max_dist=dmax[perm],
+            min_dist=(dmax / np.float32(scaleFactor ** (nlevels - 1))).astype(np.float32)[perm],
+            mp_desc=np.ascontiguousarray(g["mp_desc"][perm]), skip=g["skip"][perm])
+    out.update(sR12=sR12, t12=t12, sR21=sR21, t21=t21, W=W, H=H)
+    return out

@@ -588,8 +588,9 @@ int eorb_kb8_triangulate_matches(eorb_ctx* ctx, const eorb_camera* cam1, const e
 /* replaces the search core shared by ORBmatcher::Fuse (src/ORBmatcher.cc:1512-1578 and :1700-1720), SearchBySim3
  * (:1829-1860, :1909-1940) and SearchByProjection(KeyFrame*, Scw, ...) (:548-588, :667-706): for every projected map point
  * m (valid[m], uv, radius = th*getORBScaleFactor(level), predicted level, descriptor) the best keypoint among
- * KeyFrame::GetFeaturesInArea(u, v, radius) (src/KeyFrame.cc:873-917) with octave in [level-1, level].  Projection and the
- * map update stay with the caller.
+ * KeyFrame::GetFeaturesInArea(u, v, radius) (src/KeyFrame.cc:873-917) with octave in [level-1, level].  This entry point takes
+ * projections the caller computed; eorb_fuse_pose, eorb_search_by_projection_kf_scw, eorb_search_by_sim3 and eorb_fuse_keyframes
+ * below project on the device in front of the same search.  The map update stays with the caller.
  *   inv_sigma2 != NULL : Fuse's mono reprojection gate e2*inv_sigma2[octave] > 5.99 (:1557-1564)
  *   taken != NULL      : n flags in/out, SearchByProjection(KF,Scw) semantics: queries in order, flagged keypoints skipped,
  *                        taken[best] = 1 when (float)best_dist <= accept_thr (= TH_LOW*ratioHamming, :582-586)
@@ -605,6 +606,96 @@ int eorb_kf_radius_match_stereo(eorb_ctx* ctx,
         const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
         int M, const uint8_t* valid, const float* uv, const float* radius, const int32_t* level, const uint8_t* q_desc,
         const float* inv_sigma2, int nlevels, const float* uright, const float* q_ur, int32_t* best_idx, int32_t* best_dist);
+
+/* ---- KeyFrame-side matchers with the projection on the device ----------------------------------------------------------------------
+ * The projection loops in front of that search core, one thread per (keyframe, map point), in the reference's operation order with
+ * its double steps, then the search behind the same upload, wait and download.  Only ORB map points:
+ * MixedMatcher's KeyFrame-side forms gate keypoint type against point type and read a per-keypoint sigma table
+ * (src/MixedMatcher.cpp:1707-1745); the search core has neither, so the views' AKAZE tables are ignored here.  The Sim3 decomposition
+ * (sRcw/scw, Ow = -Rcw.t()*tcw, :1628-1632) and the right camera's pose of bRight (:1400-1425) are 3 x 3 host algebra on cv::Mat
+ * expressions and stay with the caller, who hands the result in as an eorb_view.
+ *
+ * mode D, the sequence shared by Fuse(pKF, vpMapPoints, th, bRight) (src/ORBmatcher.cc:1463-1513), Fuse(pKF, Scw, ...) (:1650-1690)
+ * and both SearchByProjection(pKF, Scw, ...) (:511-550, :595-): p3Dc = Rcw*p3Dw + tcw; p3Dc.z < 0 rejected (a zero depth goes on);
+ * uv = camera.project(p3Dc); KeyFrame::IsInImage (src/KeyFrame.cc:919-922: x >= minX && x < maxX, the upper bound strict, unlike
+ * Frame's; a NaN or an infinity fails here by itself); dist3D = (float)cv::norm(p3Dw - Ow) inside [0.8f*min_dist, 1.2f*max_dist];
+ * PO.dot(Pn) < 0.5*dist3D rejected, a comparison of doubles; level = PredictScale(dist3D); radius = th * scale_factors[level];
+ * q_ur = uv.x - mbf * (1/z).
+ * Per point, any pointer may be NULL: valid, uv, radius, level, q_ur are what eorb_kf_radius_match[_stereo] takes.  A rejected point
+ * keeps uv = (-1, -1) and q_ur = 0 until IsInImage has passed, dist3d = 0 until it was computed, level = -1, radius = 0.
+ * reason: 0 accepted, 1 skipped by the caller, 2 negative depth, 3 outside the image, 5 distance, 6 viewing angle. */
+typedef struct eorb_kfside_out {
+    uint8_t* valid; float* uv; float* radius; int32_t* level; float* q_ur; float* dist3d; uint8_t* reason;
+} eorb_kfside_out;
+
+/* mode D alone for one view.  skip[m] != 0 (optional): no map point, isBad(), IsInKeyFrame(pKF) / spAlreadyFound (:1443-1460, :1647).
+ * M == 0: EORB_OK, nothing written. */
+int eorb_project_keyframe_side(eorb_ctx* ctx, const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                               const float* max_dist, const uint8_t* skip, float th, const eorb_kfside_out* out);
+
+/* replaces ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) up to the map update (:1439-1578): mode D, then the radius match of
+ * eorb_kf_radius_match (uright == NULL) or eorb_kf_radius_match_stereo (uright = pKF->mvuRight, q_ur from the projector) over its
+ * results; inv_sigma2[view->nlevels].  inv_sigma2 == NULL: the Sim3 overload Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)
+ * (:1642-1720), which has no reprojection gate.  best_idx / best_dist as eorb_kf_radius_match returns them: the caller thresholds
+ * with TH_LOW (:1581, :1723).  bRight: the caller passes the right camera's view, keypoints, descriptors and grid and adds
+ * numAllKPtsLeft() to the indices (:1567).  out (optional): the projection.  Returns exactly what eorb_project_keyframe_side and
+ * eorb_kf_radius_match[_stereo] in sequence return. */
+int eorb_fuse_pose(eorb_ctx* ctx, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                   const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                   const uint8_t* skip, const uint8_t* q_desc, const float* inv_sigma2, const float* uright, float th,
+                   int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out);
+
+/* replaces both ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, [vpPointsKFs,] vpMatched, th, ratioHamming) (:487-590, :592-706)
+ * up to the assignment of vpMatched: mode D, then the in-order form of eorb_kf_radius_match (taken[n] in / out = keypoints holding a
+ * vpMatched entry, accept_thr = TH_LOW*ratioHamming). */
+int eorb_search_by_projection_kf_scw(eorb_ctx* ctx, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                                     const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                                     const float* max_dist, const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken,
+                                     float accept_thr, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out);
+
+/* replaces ORBmatcher::SearchBySim3 (:1743-1967) in one call: both projections (mode E, :1799-1830 and :1879-1910: two chained
+ * products R1w*p + t1w, sR21*(.) + t21; z < 0 rejected; invz = (float)(1.0/z); u = fx*(X*invz) + cx; IsInImage of the searched
+ * keyframe; dist3D = (float)cv::norm(p3Dc2), the camera-frame norm, inside the invariance region; no camera centre and no viewing
+ * angle), both radius matches (:1832-1866, :1912-1946, bestDist <= th_high = TH_HIGH) and the agreement pass (:1948-1964).
+ * Per keyframe: keypoints, descriptors, grid bounds, the view (pose, IsInImage bounds, scale tables), and per keypoint slot i the
+ * map point's pos / min_dist / max_dist / descriptor with skip[i] != 0 for no map point, isBad() or vbAlreadyMatched (:1773-1783).
+ * sR12, t12, sR21, t21: the caller's (:1760-1762).  fx, fy, cx, cy are view1's in both directions, as the reference reads pKF1's
+ * (:1746-1749).  Pinhole only: a KannalaBrandt8 view returns EORB_E_CONFIG.  match12[n1] = index in KF2 or -1; vnMatch1[n1] /
+ * vnMatch2[n2] (optional): the two searches before the agreement pass.  An empty side: EORB_OK, every output -1, *nfound = 0. */
+int eorb_search_by_sim3(eorb_ctx* ctx,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const eorb_grid_bounds* gb1, const eorb_view* view1,
+        const float* pos1, const float* min_dist1, const float* max_dist1, const uint8_t* mp_desc1, const uint8_t* skip1,
+        const eorb_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const eorb_grid_bounds* gb2, const eorb_view* view2,
+        const float* pos2, const float* min_dist2, const float* max_dist2, const uint8_t* mp_desc2, const uint8_t* skip2,
+        const float* sR12, const float* t12, const float* sR21, const float* t21, float th, int th_high,
+        int32_t* match12, int* nfound, int32_t* vnMatch1, int32_t* vnMatch2);
+
+/* Fuse of M shared map points into K keyframes at once: LocalMapping::SearchInNeighbors (src/LocalMapping.cc:840-892) and
+ * LoopClosing::SearchAndFuse (src/LoopClosing.cc:2348-2420) up to the map update.  views[K], gb[K]; keypoints / descriptors /
+ * optional uright of all keyframes concatenated, keyframe k = rows kf_off[k] .. kf_off[k+1]-1 (the convention of
+ * eorb_distinctive_descriptors); one inv_sigma2[nlevels] / scale_factors table (views[0]'s; every view must name the same pyramid)
+ * serves all keyframes, inv_sigma2 == NULL = the Sim3 overload; skip[K*M] (optional) = isBad() and IsInKeyFrame(pKF_k) at call time.
+ * best_idx[K*M] (relative to the keyframe) / best_dist[K*M] / reason[K*M] (optional): entry k*M + m is what eorb_fuse_pose returns
+ * for keyframe k and point m.  Limits: K <= 1024, K*M <= 2^22, 2^22 keypoints in all; beyond them EORB_E_CAPACITY.
+ *
+ * Why the batch is exact: the search result of (k, m) depends only on geometry, descriptors and keyframe k's keypoints, and
+ * Replace / AddObservation / AddMapPoint change none of those within one SearchInNeighbors / SearchAndFuse pass.  What they do
+ * change is which points the reference skips, so the caller applies the results keyframe by keyframe in the reference's order and
+ * re-tests the skip conditions immediately before applying each:
+ *     eorb_fuse_keyframes(..., best_idx, best_dist, NULL);
+ *     for k in the reference's keyframe order:
+ *         for m in 0 .. M-1:
+ *             if (vpMapPoints[m]->isBad() || vpMapPoints[m]->IsInKeyFrame(pKF_k)) continue;   // Sim3 overload: spAlreadyFound of pKF_k
+ *             if (best_dist[k*M + m] <= TH_LOW) { Replace / AddObservation + AddMapPoint as at :1581-1600; nFused++; }
+ * One input can change inside a pass: pMPinKF->Replace(pMP) ends in pMP->ComputeDistinctiveDescriptors() (src/MapPoint.cc:317), so a
+ * shared point that absorbs another may come out with another descriptor.  So the caller also compares, before applying row
+ * (k, m), the point's descriptor with the one it uploaded; where it changed, that row is stale and the caller searches the point in
+ * pKF_k again with the new descriptor (eorb_fuse_pose, alone or grouped with the other changed points) and applies that result.
+ * tests/test_kfside_ref.py runs this adapter against the sequential loop on a model map. */
+int eorb_fuse_keyframes(eorb_ctx* ctx, const eorb_view* views, const eorb_grid_bounds* gb, int K,
+                        const eorb_keypoint* kps, const uint8_t* desc, int stride, const float* uright, const int32_t* kf_off,
+                        int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* q_desc,
+                        const uint8_t* skip, const float* inv_sigma2, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reason);
 
 /* replaces MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423; f3), batched over M map points: the
  * descriptors observed for map point m are rows offsets[m] .. offsets[m+1]-1 of desc (n x 32); best[m] = the row (relative

@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Per-call latency (through ctypes, each call ends in its own wait) of the KeyFrame-side matchers with the projection on the device,
+against the path callers have without them.  346 x 260, 1 000 keypoints per keyframe, M = 1 000 map points:
+
+  fuse K = 1, 8, 20
+    batched          eorb_fuse_keyframes, one call for the K keyframes
+    fused_per_kf     eorb_fuse_pose, K calls
+    cpu_path         per keyframe: the CPU restatement of the projection on one core of the same host (tests/kfside_ref, its timing
+                     build: -O3 -march=native), then eorb_kf_radius_match: what callers have without the projector
+  sim3 (one pair)
+    fused            eorb_search_by_sim3
+    cpu_path         the restatement of both projections, eorb_kf_radius_match twice, the agreement loop in numpy
+
+The calls of a shape take turns inside one loop, so that a drift of the clocks or of the shared host touches them alike.  Prints one
+JSON object (and writes it to --out)."""
+import argparse, json, os, sys, time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+W, H = 346, 260
+
+
+def _time(calls, n, np):
+    for _ in range(5):
+        for fn in calls.values():
+            fn()
+    ts = {k: [] for k in calls}
+    for _ in range(n):
+        for k, fn in calls.items():
+            t = time.perf_counter(); fn(); ts[k].append((time.perf_counter() - t) * 1e3)
+    return {k: {"p50_ms": float(np.percentile(x, 50)), "p95_ms": float(np.percentile(x, 95)), "calls": len(x)} for k, x in ts.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--M", type=int, default=1000)
+    ap.add_argument("--n", type=int, default=1000)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import numpy as np
+    from eorb_slam_amd import frontend as fe, synth
+    from twocam_latency import _sources_hash
+    import kfside_ref as ref
+    M, n = a.M, a.n
+    res = {"sources_hash": _sources_hash(), "M": M, "n": n, "size": [W, H], "fuse": {}, "sim3": {}}
+    ctx = fe.Context()
+    gb = fe.grid_bounds(W, H)
+    for K in (1, 8, 20):
+        sc = synth.keyframe_neighbourhood(200 + K, K, M, n_kps=n)
+        geom = (sc["pos"], sc["normal"], sc["min_dist"], sc["max_dist"])
+        views = [fe.view(**kw) for kw in sc["views"]]; rviews = [ref.view(**kw) for kw in sc["views"]]
+        kps = np.concatenate(sc["kps"]); desc = np.concatenate(sc["desc"])
+        off = (np.arange(K + 1) * n).astype(np.int32)
+        isg, qd = sc["inv_sigma2"], sc["mp_desc"]
+
+        def batched():
+            return fe.FuseKeyFrames(views, [gb] * K, kps, desc, off, *geom, qd, inv_sigma2=isg, th=3.0, ctx=ctx)
+
+        def per_kf():
+            return [fe.FusePose(sc["kps"][k], sc["desc"][k], gb, views[k], *geom, qd, inv_sigma2=isg, th=3.0, ctx=ctx) for k in range(K)]
+
+        def cpu_path():
+            out = []
+            for k in range(K):
+                p = ref.keyframe_side(rviews[k], *geom, 3.0, timing=True)
+                out.append(fe.KeyFrameRadiusMatch(sc["kps"][k], sc["desc"][k], gb, p["valid"], p["uv"], p["radius"], p["level"], qd, inv_sigma2=isg, ctx=ctx))
+            return out
+        b, f, c = batched(), per_kf(), cpu_path()
+        for k in range(K):
+            assert np.array_equal(b[0][k], f[k][0]) and np.array_equal(b[0][k], c[k][0]) and np.array_equal(b[1][k], c[k][1])
+        assert int((b[1] <= 50).sum()) >= 30 * K
+        e = _time({"batched": batched, "fused_per_kf": per_kf, "cpu_path": cpu_path}, a.calls, np)
+        e["batched_beats_cpu_path"] = bool(e["batched"]["p50_ms"] < e["cpu_path"]["p50_ms"])
+        e["fused_per_kf_beats_cpu_path"] = bool(e["fused_per_kf"]["p50_ms"] < e["cpu_path"]["p50_ms"])
+        res["fuse"]["K%d" % K] = e
+    # one Sim3 pair
+    sp = synth.sim3_pair(300, n=n, s12=0.9)
+    k1, k2 = sp["kf1"], sp["kf2"]
+    kf = [dict(k, gb=gb, view=fe.view(**k["view"])) for k in (k1, k2)]
+    rv1, rv2 = ref.view(**k1["view"]), ref.view(**k2["view"])
+    cam = k1["view"]["cam"]
+
+    def sim3_fused():
+        return fe.SearchBySim3Pose(kf[0], kf[1], sp["sR12"], sp["t12"], sp["sR21"], sp["t21"], th=7.5, ctx=ctx)
+
+    def sim3_cpu():
+        p12 = ref.sim3_half(rv1, sp["sR21"], sp["t21"], cam, rv2, k1["pos"], k1["min_dist"], k1["max_dist"], 7.5, skip=k1["skip"], timing=True)
+        p21 = ref.sim3_half(rv2, sp["sR12"], sp["t12"], cam, rv1, k2["pos"], k2["min_dist"], k2["max_dist"], 7.5, skip=k2["skip"], timing=True)
+        bi1, bd1 = fe.KeyFrameRadiusMatch(k2["kps"], k2["desc"], gb, p12["valid"], p12["uv"], p12["radius"], p12["level"], k1["mp_desc"], ctx=ctx)
+        bi2, bd2 = fe.KeyFrameRadiusMatch(k1["kps"], k1["desc"], gb, p21["valid"], p21["uv"], p21["radius"], p21["level"], k2["mp_desc"], ctx=ctx)
+        vn1 = np.where(bd1 <= 100, bi1, -1); vn2 = np.where(bd2 <= 100, bi2, -1)
+        ok = (vn1 >= 0) & (vn2[np.clip(vn1, 0, len(vn2) - 1)] == np.arange(len(vn1)))
+        return int(ok.sum()), np.where(ok, vn1, -1).astype(np.int32)
+    g, w = sim3_fused(), sim3_cpu()
+    assert g[0] == w[0] and np.array_equal(g[1], w[1]) and g[0] >= 30
+    e = _time({"fused": sim3_fused, "cpu_path": sim3_cpu}, a.calls, np)
+    e["fused_beats_cpu_path"] = bool(e["fused"]["p50_ms"] < e["cpu_path"]["p50_ms"])
+    res["sim3"] = e
+    ctx.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
