@@ -24,6 +24,8 @@ EXPORTS = [
     "eorb_ev_slice_extract", "eorb_ev_slice_track", "eorb_ev_slice_image", "eorb_ev_mc_contest",
     "eorb_project_frustum", "eorb_project_last_frame", "eorb_project_keyframe_points", "eorb_search_local_points", "eorb_search_local_points_fisheye", "eorb_search_by_projection_last_pose", "eorb_search_by_projection_kf_pose",
     "eorb_project_keyframe_side", "eorb_fuse_pose", "eorb_search_by_projection_kf_scw", "eorb_search_by_sim3", "eorb_fuse_keyframes",
+    "eorb_kf_radius_match_mixed", "eorb_project_keyframe_side_mixed", "eorb_fuse_pose_mixed", "eorb_search_by_projection_kf_scw_mixed",
+    "eorb_fuse_keyframes_mixed",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
 ]
@@ -317,6 +319,16 @@ def lib():
                                       vp, vp, vp, vp, cf, ci, vp, pi, vp, vp]
     L.eorb_fuse_keyframes.restype = ci
     L.eorb_fuse_keyframes.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp]
+    L.eorb_kf_radius_match_mixed.restype = ci
+    L.eorb_kf_radius_match_mixed.argtypes = [vp, vp, ci, vp, ci, gbp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp]
+    L.eorb_project_keyframe_side_mixed.restype = ci
+    L.eorb_project_keyframe_side_mixed.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, cf, vp]
+    L.eorb_fuse_pose_mixed.restype = ci
+    L.eorb_fuse_pose_mixed.argtypes = [vp, vp, ci, vp, ci, gbp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp]
+    L.eorb_search_by_projection_kf_scw_mixed.restype = ci
+    L.eorb_search_by_projection_kf_scw_mixed.argtypes = [vp, vp, ci, vp, ci, gbp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp, cf, vp, vp, vp]
+    L.eorb_fuse_keyframes_mixed.restype = ci
+    L.eorb_fuse_keyframes_mixed.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]
     L.eorb_selfcheck_math.restype = ci; L.eorb_selfcheck_math.argtypes = [vp, ci, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.eorb_pack_events.restype = None; L.eorb_pack_events.argtypes = [vp, C.c_size_t, vp]

@@ -2382,14 +2382,32 @@ int eorb_kb8_triangulate_matches(eorb_ctx* c, const eorb_camera* cam1, const eor
     return A.download_to(z1, o_z, sizeof(float) * (size_t)n);
 }
 
+// what the MixedMatcher forms take on top of the ORB ones (a NULL KfMixedIn* = an ORB entry point): kp_is_orb / kp_inv_sigma2 per
+// keypoint, mp_is_orb per map point, each optional
+struct KfMixedIn { const uint8_t* kp_is_orb; const float* kp_inv_sigma2; const uint8_t* mp_is_orb; };
+struct KfMixedOff { size_t kio, sig, mio; };
+static KfMixedOff kf_mixed_in(Arena& A, const KfMixedIn* mx, size_t n, size_t M)
+{
+    KfMixedOff o{};
+    if (!mx) return o;
+    o.kio = A.in(mx->kp_is_orb, mx->kp_is_orb ? n : 0);
+    o.sig = A.in(mx->kp_inv_sigma2, mx->kp_inv_sigma2 ? sizeof(float) * n : 0);
+    o.mio = A.in(mx->mp_is_orb, mx->mp_is_orb ? M : 0);
+    return o;
+}
+static const uint8_t* kf_mixed_kp(const Arena& A, const KfMixedIn* mx, const KfMixedOff& o) { return mx && mx->kp_is_orb ? A.dev<uint8_t>(o.kio) : nullptr; }
+static const float* kf_mixed_sigma(const Arena& A, const KfMixedIn* mx, const KfMixedOff& o) { return mx && mx->kp_inv_sigma2 ? A.dev<float>(o.sig) : nullptr; }
+static const uint8_t* kf_mixed_mp(const Arena& A, const KfMixedIn* mx, const KfMixedOff& o) { return mx && mx->mp_is_orb ? A.dev<uint8_t>(o.mio) : nullptr; }
+
 static int kf_radius_common(eorb_ctx* c,
         const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
         int M, const uint8_t* valid, const float* uv, const float* radius, const int32_t* level, const uint8_t* q_desc,
         const float* inv_sigma2, int nlevels, uint8_t* taken, float accept_thr, int32_t* best_idx, int32_t* best_dist,
-        const float* uright, const float* q_ur)
+        const float* uright, const float* q_ur, const KfMixedIn* mx = nullptr)
 {
     if (!c) return EORB_E_ARG;
-    if ((uright != nullptr) != (q_ur != nullptr) || (uright && !inv_sigma2)) return set_err(c, EORB_E_ARG, "kf_radius_match: the stereo gate needs uright, q_ur and inv_sigma2");
+    const float* sigma = mx ? mx->kp_inv_sigma2 : inv_sigma2;
+    if ((uright != nullptr) != (q_ur != nullptr) || (uright && !sigma)) return set_err(c, EORB_E_ARG, "kf_radius_match: the stereo gate needs uright, q_ur and inv_sigma2");
     if (n < 0 || M < 0 || stride < 32 || !gb || (M > 0 && (!valid || !uv || !radius || !level || !q_desc || !best_idx || !best_dist)) ||
         (inv_sigma2 && (nlevels <= 0 || nlevels > 64)))
         return set_err(c, EORB_E_ARG, "kf_radius_match: bad arguments");
@@ -2403,11 +2421,12 @@ static int kf_radius_common(eorb_ctx* c,
     const size_t o_va = A.in(valid, M), o_qd = A.in(q_desc, 32 * (size_t)M);
     const size_t o_is = A.in(inv_sigma2, inv_sigma2 ? sizeof(float) * nlevels : 0);
     const size_t o_ur = A.in(uright, uright ? sizeof(float) * n : 0), o_qur = A.in(q_ur, q_ur ? sizeof(float) * M : 0);
+    const KfMixedOff mo = kf_mixed_in(A, mx, (size_t)n, (size_t)M);
     // outputs, contiguous: taken (in / out) | best index | best distance; then the keypoints' cells
     const size_t o_tk = A.in(taken, taken ? (size_t)n : 0);
     const size_t o_bi = A.reserve(sizeof(int32_t) * M), o_bd = A.reserve(sizeof(int32_t) * M), o_cell = A.reserve(sizeof(uint16_t) * n);
     if ((rc = A.upload())) return rc;
-    RadArgs R{};
+    RadArgsMixed R{};
     R.kps = A.dev<eorb_keypoint>(o_k); R.n = n; R.desc = A.dev<uint8_t>(o_d); R.stride = stride;
     R.g = grid_b(*gb);
     R.cell = A.dev<uint16_t>(o_cell);
@@ -2417,7 +2436,8 @@ static int kf_radius_common(eorb_ctx* c,
     R.uright = uright ? A.dev<float>(o_ur) : nullptr; R.q_ur = uright ? A.dev<float>(o_qur) : nullptr;
     R.taken = taken ? A.dev<uint8_t>(o_tk) : nullptr; R.accept_thr = accept_thr;
     R.best_idx = A.dev<int32_t>(o_bi); R.best_dist = A.dev<int32_t>(o_bd);
-    if ((rc = kf_radius_dev(c, R, A.dev<uint16_t>(o_cell)))) return rc;
+    R.mp_is_orb = kf_mixed_mp(A, mx, mo); R.kp_inv_sigma2 = kf_mixed_sigma(A, mx, mo);
+    if ((rc = mx ? kf_radius_mixed_dev(c, R, A.dev<uint16_t>(o_cell), kf_mixed_kp(A, mx, mo)) : kf_radius_dev(c, R, A.dev<uint16_t>(o_cell)))) return rc;
     const size_t first = taken ? o_tk : o_bi;
     const char* h;
     if ((rc = A.download(first, o_bd + sizeof(int32_t) * M - first, &h))) return rc;
@@ -2441,6 +2461,17 @@ int eorb_kf_radius_match_stereo(eorb_ctx* c,
         const float* inv_sigma2, int nlevels, const float* uright, const float* q_ur, int32_t* best_idx, int32_t* best_dist)
 {
     return kf_radius_common(c, kps, n, desc, stride, gb, M, valid, uv, radius, level, q_desc, inv_sigma2, nlevels, nullptr, 0.f, best_idx, best_dist, uright, q_ur);
+}
+
+int eorb_kf_radius_match_mixed(eorb_ctx* c,
+        const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+        const uint8_t* kp_is_orb, const float* kp_inv_sigma2, const float* uright,
+        int M, const uint8_t* valid, const float* uv, const float* radius, const int32_t* level, const uint8_t* q_desc,
+        const uint8_t* mp_is_orb, const float* q_ur, uint8_t* taken, float accept_thr, int32_t* best_idx, int32_t* best_dist)
+{
+    const KfMixedIn mx{kp_is_orb, kp_inv_sigma2, mp_is_orb};
+    return kf_radius_common(c, kps, n, desc, stride, gb, M, valid, uv, radius, level, q_desc, nullptr, 0, taken, accept_thr, best_idx, best_dist,
+                            uright, q_ur, &mx);
 }
 
 // ---- KeyFrame-side matchers: projection (project.hip modes D, E) and search behind one upload, one wait, one download ------------
@@ -2495,9 +2526,9 @@ static void kfside_copy_out(const char* h, const KfSideOff& o, size_t n, const e
 }
 
 // the map points of mode D and the views' shared table
-struct KfSideIn { size_t pos, nrm, mind, maxd, skip, sf, pose; std::vector<KfPose> poses; };
+struct KfSideIn { size_t pos, nrm, mind, maxd, skip, sf, pose, ak; KfMixedOff mo; std::vector<KfPose> poses; };
 static int kfside_check(eorb_ctx* c, const char* who, const eorb_view* views, int K, int M, const float* pos, const float* normal,
-                        const float* min_dist, const float* max_dist)
+                        const float* min_dist, const float* max_dist, bool mixed = false)
 {
     if (K < 0 || M < 0 || (K > 0 && !views) || (K > 0 && M > 0 && (!pos || !normal || !min_dist || !max_dist)))
         return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
@@ -2506,65 +2537,91 @@ static int kfside_check(eorb_ctx* c, const char* who, const eorb_view* views, in
         if ((rc = view_check(c, who, views + k, false))) return rc;
         if (views[k].nlevels != views[0].nlevels || views[k].log_scale != views[0].log_scale)
             return set_err(c, EORB_E_ARG, "%s: keyframe %d has another scale pyramid than keyframe 0 (one table serves the batch)", who, k);
+        if (mixed && (views[k].ak_nlevels != views[0].ak_nlevels || views[k].ak_log_scale != views[0].ak_log_scale))
+            return set_err(c, EORB_E_ARG, "%s: keyframe %d has another AKAZE pyramid than keyframe 0 (one table serves the batch)", who, k);
     }
     return EORB_OK;
 }
 static void kfside_in(Arena& A, KfSideIn& I, const eorb_view* views, int K, int M, const float* pos, const float* normal,
-                      const float* min_dist, const float* max_dist, const uint8_t* skip)
+                      const float* min_dist, const float* max_dist, const uint8_t* skip, const KfMixedIn* mx = nullptr, size_t ntotal = 0)
 {
     const size_t m = (size_t)M;
     I.pos = A.in(pos, 12 * m); I.nrm = A.in(normal, 12 * m); I.mind = A.in(min_dist, 4 * m); I.maxd = A.in(max_dist, 4 * m);
     I.skip = A.in(skip, skip ? (size_t)K * m : 0);
     I.sf = A.in(views[0].scale_factors, sizeof(float) * (size_t)views[0].nlevels);
+    I.ak = mx ? A.in(views[0].ak_scale_factors, views[0].ak_nlevels > 0 ? sizeof(float) * (size_t)views[0].ak_nlevels : 0) : 0;
+    I.mo = kf_mixed_in(A, mx, ntotal, m);
     I.poses.resize(K);
     for (int k = 0; k < K; k++) I.poses[k] = kf_pose_of(views[k]);
     I.pose = A.in(I.poses.data(), sizeof(KfPose) * (size_t)K);
 }
-static KfSideArgs kfside_args(const Arena& A, const KfSideIn& I, const eorb_view* views, int K, int M, bool has_skip, float th, const KfSideOff& o)
+static KfSideArgsMixed kfside_args(const Arena& A, const KfSideIn& I, const eorb_view* views, int K, int M, bool has_skip, float th, const KfSideOff& o,
+                              const KfMixedIn* mx = nullptr)
 {
-    KfSideArgs P{};
+    KfSideArgsMixed P{};
     P.V = A.dev<KfPose>(I.pose); P.K = K; P.M = M;
     P.nlevels = views[0].nlevels; P.log_scale = views[0].log_scale; P.sf = A.dev<float>(I.sf); P.th = th;
     P.pos = A.dev<float>(I.pos); P.normal = A.dev<float>(I.nrm); P.min_dist = A.dev<float>(I.mind); P.max_dist = A.dev<float>(I.maxd);
     P.skip = has_skip ? A.dev<uint8_t>(I.skip) : nullptr;
     P.O = kfside_dev(A, o);
+    if (mx) {
+        P.mp_is_orb = kf_mixed_mp(A, mx, I.mo);
+        P.ak_nlevels = views[0].ak_nlevels; P.ak_log_scale = views[0].ak_log_scale; P.ak_sf = P.ak_nlevels > 0 ? A.dev<float>(I.ak) : nullptr;
+    }
     return P;
 }
 
-int eorb_project_keyframe_side(eorb_ctx* c, const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
-                               const float* max_dist, const uint8_t* skip, float th, const eorb_kfside_out* out)
+static int project_kfside_common(eorb_ctx* c, const char* who, const eorb_view* view, int M, const float* pos, const float* normal,
+                                 const float* min_dist, const float* max_dist, const uint8_t* skip, float th, const eorb_kfside_out* out,
+                                 const KfMixedIn* mx)
 {
     if (!c) return EORB_E_ARG;
     int rc;
-    if (!view) return set_err(c, EORB_E_ARG, "project_keyframe_side: null view");
-    if ((rc = kfside_check(c, "project_keyframe_side", view, 1, M, pos, normal, min_dist, max_dist))) return rc;
-    if (M > kKfSideMaxQueries) return set_err(c, EORB_E_CAPACITY, "project_keyframe_side: %d map points exceed %lld", M, (long long)kKfSideMaxQueries);
+    if (!view) return set_err(c, EORB_E_ARG, "%s: null view", who);
+    if ((rc = kfside_check(c, who, view, 1, M, pos, normal, min_dist, max_dist))) return rc;
+    if (M > kKfSideMaxQueries) return set_err(c, EORB_E_CAPACITY, "%s: %d map points exceed %lld", who, M, (long long)kKfSideMaxQueries);
     fe_enter(c);
     if (M == 0) return EORB_OK;
     Arena A(c);
     KfSideIn I;
-    kfside_in(A, I, view, 1, M, pos, normal, min_dist, max_dist, skip);
+    kfside_in(A, I, view, 1, M, pos, normal, min_dist, max_dist, skip, mx);
     const KfSideOff o = kfside_reserve(A, (size_t)M);
     if ((rc = A.upload())) return rc;
-    if ((rc = project_kfside_dev(c, kfside_args(A, I, view, 1, M, skip != nullptr, th, o)))) return rc;
+    const KfSideArgsMixed P = kfside_args(A, I, view, 1, M, skip != nullptr, th, o, mx);
+    if ((rc = mx ? project_kfside_mixed_dev(c, P) : project_kfside_dev(c, P))) return rc;
     const char* h;
     if ((rc = A.download(o.rs, o.end - o.rs, &h))) return rc;
     kfside_copy_out(h, o, (size_t)M, out);
     return EORB_OK;
 }
 
+int eorb_project_keyframe_side(eorb_ctx* c, const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                               const float* max_dist, const uint8_t* skip, float th, const eorb_kfside_out* out)
+{
+    return project_kfside_common(c, "project_keyframe_side", view, M, pos, normal, min_dist, max_dist, skip, th, out, nullptr);
+}
+
+int eorb_project_keyframe_side_mixed(eorb_ctx* c, const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                                     const float* max_dist, const uint8_t* mp_is_orb, const uint8_t* skip, float th, const eorb_kfside_out* out)
+{
+    const KfMixedIn mx{nullptr, nullptr, mp_is_orb};
+    return project_kfside_common(c, "project_keyframe_side_mixed", view, M, pos, normal, min_dist, max_dist, skip, th, out, &mx);
+}
+
 // mode D over K keyframes, then the batched radius match; shared by eorb_fuse_pose (K = 1) and eorb_fuse_keyframes
 static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, const eorb_grid_bounds* gb, int K,
                        const eorb_keypoint* kps, const uint8_t* desc, int stride, const float* uright, const int32_t* kf_off,
                        int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* q_desc,
-                       const uint8_t* skip, const float* inv_sigma2, float th, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
+                       const uint8_t* skip, const float* inv_sigma2, float th, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out,
+                       const KfMixedIn* mx = nullptr)
 {
     int rc;
     if (K > kKfSideMaxKfs || (K > 0 && M > 0 && (int64_t)K * M > kKfSideMaxQueries))      // (sizes only: nothing is read before this)
         return set_err(c, EORB_E_CAPACITY, "%s: %d keyframes x %d map points exceed %d keyframes or %lld queries", who, K, M, kKfSideMaxKfs,
                        (long long)kKfSideMaxQueries);
-    if ((rc = kfside_check(c, who, views, K, M, pos, normal, min_dist, max_dist))) return rc;
-    if (stride < 32 || (K > 0 && (!gb || !kf_off)) || (K > 0 && M > 0 && (!q_desc || !best_idx || !best_dist)) || (uright && !inv_sigma2))
+    if ((rc = kfside_check(c, who, views, K, M, pos, normal, min_dist, max_dist, mx != nullptr))) return rc;
+    if (stride < 32 || (K > 0 && (!gb || !kf_off)) || (K > 0 && M > 0 && (!q_desc || !best_idx || !best_dist)) ||
+        (uright && !(mx ? mx->kp_inv_sigma2 : inv_sigma2)))
         return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
     if (K == 0) return EORB_OK;
     if (kf_off[0] != 0) return set_err(c, EORB_E_ARG, "%s: kf_off[0] = %d", who, kf_off[0]);
@@ -2579,7 +2636,7 @@ static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, con
     if (M == 0) return EORB_OK;
     Arena A(c);
     KfSideIn I;
-    kfside_in(A, I, views, K, M, pos, normal, min_dist, max_dist, skip);
+    kfside_in(A, I, views, K, M, pos, normal, min_dist, max_dist, skip, mx, (size_t)ntotal);
     std::vector<GridB> g(K);
     for (int k = 0; k < K; k++) g[k] = grid_b(gb[k]);
     const size_t o_g = A.in(g.data(), sizeof(GridB) * (size_t)K), o_off = A.in(kf_off, sizeof(int32_t) * ((size_t)K + 1));
@@ -2592,9 +2649,9 @@ static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, con
     const KfSideOff o = kfside_reserve(A, nq);
     const size_t o_cell = A.reserve(sizeof(uint16_t) * (size_t)ntotal);
     if ((rc = A.upload())) return rc;
-    const KfSideArgs P = kfside_args(A, I, views, K, M, skip != nullptr, th, o);
-    if ((rc = project_kfside_dev(c, P))) return rc;
-    RadBatchArgs B{};
+    const KfSideArgsMixed P = kfside_args(A, I, views, K, M, skip != nullptr, th, o, mx);
+    if ((rc = mx ? project_kfside_mixed_dev(c, P) : project_kfside_dev(c, P))) return rc;
+    RadBatchArgsMixed B{};
     B.kps = A.dev<eorb_keypoint>(o_k); B.desc = A.dev<uint8_t>(o_d); B.stride = stride; B.cell = A.dev<uint16_t>(o_cell);
     B.uright = uright ? A.dev<float>(o_ur) : nullptr;
     B.kf_off = A.dev<int32_t>(o_off); B.g = A.dev<GridB>(o_g); B.K = K; B.M = M;
@@ -2602,7 +2659,9 @@ static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, con
     B.q_desc = A.dev<uint8_t>(o_qd); B.q_desc_kstride = 0;
     B.inv_sigma2 = inv_sigma2 ? A.dev<float>(o_is) : nullptr; B.nlevels = views[0].nlevels;
     B.best_idx = A.dev<int32_t>(o_bi); B.best_dist = A.dev<int32_t>(o_bd);
-    if ((rc = kf_radius_batch_dev(c, B, ntotal, A.dev<uint16_t>(o_cell)))) return rc;
+    B.mp_is_orb = P.mp_is_orb; B.kp_inv_sigma2 = kf_mixed_sigma(A, mx, I.mo);
+    if ((rc = mx ? kf_radius_batch_mixed_dev(c, B, ntotal, A.dev<uint16_t>(o_cell), kf_mixed_kp(A, mx, I.mo))
+                 : kf_radius_batch_dev(c, B, ntotal, A.dev<uint16_t>(o_cell)))) return rc;
     const char* h;
     if ((rc = A.download(o_bi, kfside_end(o, out, o_bend) - o_bi, &h))) return rc;
     memcpy(best_idx, h + o_bi, 4 * nq);
@@ -2635,24 +2694,52 @@ int eorb_fuse_keyframes(eorb_ctx* c, const eorb_view* views, const eorb_grid_bou
                        inv_sigma2, th, best_idx, best_dist, reason ? &out : nullptr);
 }
 
-int eorb_search_by_projection_kf_scw(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
-                                     const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
-                                     const float* max_dist, const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken,
-                                     float accept_thr, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
+int eorb_fuse_pose_mixed(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                         const uint8_t* kp_is_orb, const float* kp_inv_sigma2, const float* uright,
+                         const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                         const uint8_t* mp_is_orb, const uint8_t* skip, const uint8_t* q_desc, float th,
+                         int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
+{
+    if (!c) return EORB_E_ARG;
+    if (n < 0 || !view || !gb) return set_err(c, EORB_E_ARG, "fuse_pose_mixed: bad arguments");
+    const int32_t off[2] = {0, n};
+    const KfMixedIn mx{kp_is_orb, kp_inv_sigma2, mp_is_orb};
+    return fuse_common(c, "fuse_pose_mixed", view, gb, 1, kps, desc, stride, uright, off, M, pos, normal, min_dist, max_dist, q_desc, skip,
+                       nullptr, th, best_idx, best_dist, out, &mx);
+}
+
+int eorb_fuse_keyframes_mixed(eorb_ctx* c, const eorb_view* views, const eorb_grid_bounds* gb, int K,
+                              const eorb_keypoint* kps, const uint8_t* desc, int stride, const uint8_t* kp_is_orb, const float* kp_inv_sigma2,
+                              const float* uright, const int32_t* kf_off,
+                              int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_is_orb,
+                              const uint8_t* q_desc, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reason)
+{
+    if (!c) return EORB_E_ARG;
+    eorb_kfside_out out{};
+    out.reason = reason;
+    const KfMixedIn mx{kp_is_orb, kp_inv_sigma2, mp_is_orb};
+    return fuse_common(c, "fuse_keyframes_mixed", views, gb, K, kps, desc, stride, uright, kf_off, M, pos, normal, min_dist, max_dist, q_desc, skip,
+                       nullptr, th, best_idx, best_dist, reason ? &out : nullptr, &mx);
+}
+
+static int kf_scw_common(eorb_ctx* c, const char* who, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                         const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                         const float* max_dist, const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken,
+                         float accept_thr, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out, const KfMixedIn* mx)
 {
     if (!c) return EORB_E_ARG;
     int rc;
     if (n < 0 || !view || !gb || stride < 32 || (n > 0 && (!kps || !desc || !taken)) || (M > 0 && (!q_desc || !best_idx || !best_dist)))
-        return set_err(c, EORB_E_ARG, "search_by_projection_kf_scw: bad arguments");
-    if ((rc = kfside_check(c, "search_by_projection_kf_scw", view, 1, M, pos, normal, min_dist, max_dist))) return rc;
-    if (M > kKfSideMaxQueries) return set_err(c, EORB_E_CAPACITY, "search_by_projection_kf_scw: %d map points exceed %lld", M, (long long)kKfSideMaxQueries);
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
+    if ((rc = kfside_check(c, who, view, 1, M, pos, normal, min_dist, max_dist))) return rc;
+    if (M > kKfSideMaxQueries) return set_err(c, EORB_E_CAPACITY, "%s: %d map points exceed %lld", who, M, (long long)kKfSideMaxQueries);
     fe_enter(c);
     for (int m = 0; m < M; m++) { best_idx[m] = -1; best_dist[m] = 256; }
     if (M == 0) return EORB_OK;
     const size_t nq = (size_t)M;
     Arena A(c);
     KfSideIn I;
-    kfside_in(A, I, view, 1, M, pos, normal, min_dist, max_dist, skip);
+    kfside_in(A, I, view, 1, M, pos, normal, min_dist, max_dist, skip, mx, (size_t)n);
     const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)n), o_d = A.in(desc, (size_t)stride * n);
     const size_t o_qd = A.in(q_desc, 32 * nq);
     // outputs, contiguous: taken (in / out) | best index | best distance | the projector's arrays; then the keypoints' cells
@@ -2661,15 +2748,16 @@ int eorb_search_by_projection_kf_scw(eorb_ctx* c, const eorb_keypoint* kps, int 
     const KfSideOff o = kfside_reserve(A, nq);
     const size_t o_cell = A.reserve(sizeof(uint16_t) * (size_t)n);
     if ((rc = A.upload())) return rc;
-    const KfSideArgs P = kfside_args(A, I, view, 1, M, skip != nullptr, th, o);
-    if ((rc = project_kfside_dev(c, P))) return rc;
-    RadArgs R{};
+    const KfSideArgsMixed P = kfside_args(A, I, view, 1, M, skip != nullptr, th, o, mx);
+    if ((rc = mx ? project_kfside_mixed_dev(c, P) : project_kfside_dev(c, P))) return rc;
+    RadArgsMixed R{};
     R.kps = A.dev<eorb_keypoint>(o_k); R.n = n; R.desc = A.dev<uint8_t>(o_d); R.stride = stride;
     R.g = grid_b(*gb); R.cell = A.dev<uint16_t>(o_cell);
     R.M = M; R.valid = P.O.valid; R.uv = (const float*)P.O.uv; R.radius = P.O.radius; R.level = P.O.level; R.q_desc = A.dev<uint8_t>(o_qd);
     R.taken = A.dev<uint8_t>(o_tk); R.accept_thr = accept_thr;
     R.best_idx = A.dev<int32_t>(o_bi); R.best_dist = A.dev<int32_t>(o_bd);
-    if ((rc = kf_radius_dev(c, R, A.dev<uint16_t>(o_cell)))) return rc;
+    R.mp_is_orb = P.mp_is_orb;
+    if ((rc = mx ? kf_radius_mixed_dev(c, R, A.dev<uint16_t>(o_cell), kf_mixed_kp(A, mx, I.mo)) : kf_radius_dev(c, R, A.dev<uint16_t>(o_cell)))) return rc;
     const char* h;
     if ((rc = A.download(o_tk, kfside_end(o, out, o_bend) - o_tk, &h))) return rc;
     memcpy(best_idx, h + o_bi, 4 * nq);
@@ -2677,6 +2765,26 @@ int eorb_search_by_projection_kf_scw(eorb_ctx* c, const eorb_keypoint* kps, int 
     if (n > 0) memcpy(taken, h + o_tk, (size_t)n);
     kfside_copy_out(h, o, nq, out);
     return EORB_OK;
+}
+
+int eorb_search_by_projection_kf_scw(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                                     const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                                     const float* max_dist, const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken,
+                                     float accept_thr, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
+{
+    return kf_scw_common(c, "search_by_projection_kf_scw", kps, n, desc, stride, gb, view, M, pos, normal, min_dist, max_dist, skip, q_desc, th,
+                         taken, accept_thr, best_idx, best_dist, out, nullptr);
+}
+
+int eorb_search_by_projection_kf_scw_mixed(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride,
+                                           const eorb_grid_bounds* gb, const uint8_t* kp_is_orb, const eorb_view* view, int M, const float* pos,
+                                           const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_is_orb,
+                                           const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken, float accept_thr,
+                                           int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
+{
+    const KfMixedIn mx{kp_is_orb, nullptr, mp_is_orb};
+    return kf_scw_common(c, "search_by_projection_kf_scw_mixed", kps, n, desc, stride, gb, view, M, pos, normal, min_dist, max_dist, skip, q_desc,
+                         th, taken, accept_thr, best_idx, best_dist, out, &mx);
 }
 
 int eorb_search_by_sim3(eorb_ctx* c,

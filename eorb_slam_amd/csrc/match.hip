@@ -20,6 +20,7 @@
 #include "dev_math.h"
 #include "kb8_dev.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace eorb {
 
@@ -895,7 +896,7 @@ static size_t win_resolve_lds_rest(int cap2, int capq)
 
 // A kernel's dynamic LDS beyond 64 KB needs an opt-in, which holds per device: made once per context (a second context on another
 // GPU needs it too) and kernel; `bit` numbers the kernel in c->lds_optin
-enum { kOptWinCand = 0, kOptWinResolve = 3, kOptTwocam = 6, kOptKfRadius = 8, kOptBowAssemble = 9 };
+enum { kOptWinCand = 0, kOptWinResolve = 3, kOptTwocam = 6, kOptKfRadius = 8, kOptBowAssemble = 9, kOptKfRadiusMixed = 10 };
 static int lds_optin(eorb_ctx* c, int bit, const void* kernel, int bytes)
 {
     if (c->lds_optin & (1u << bit)) return EORB_OK;
@@ -1367,27 +1368,76 @@ __global__ void kf_cells_kernel(const eorb_keypoint* __restrict__ kps, int n, Gr
     cell[i] = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? (uint16_t)0xFFFF : (uint16_t)(px * kGridRows + py);
 }
 
-template <bool SEQ>
-__device__ __forceinline__ uint64_t radius_scan(const RadArgs& A, int m, int first, int step, const uint8_t* taken)
+// the mixed forms' cell word: Frame::PosInGrid as the 12-bit cell number ix*48+iy (64 x 48 = 3072 cells), 0xFFFF outside the grid, as
+// kf_cells_kernel writes it
+__device__ __forceinline__ uint16_t kf_cell_of(const eorb_keypoint& k, const GridB& g)
+{
+    const int px = (int)roundf((k.x - g.minX) * g.invW);
+    const int py = (int)roundf((k.y - g.minY) * g.invH);
+    return (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? (uint16_t)0xFFFF : (uint16_t)(px * kGridRows + py);
+}
+// the mixed forms carry the row's type in the cell word: bit 15 set = not an ORB row (!isORBDescValid(idx)); 0xFFFF stays "outside"
+constexpr int kCellNotOrb = 0x8000;
+__device__ __forceinline__ uint16_t kf_cell_mixed(const eorb_keypoint& k, const GridB& g, const uint8_t* __restrict__ kp_is_orb, int i)
+{
+    const uint16_t cell = kf_cell_of(k, g);
+    return (cell != 0xFFFF && kp_is_orb && !kp_is_orb[i]) ? (uint16_t)(cell | kCellNotOrb) : cell;
+}
+
+__global__ void kf_cells_mixed_kernel(const eorb_keypoint* __restrict__ kps, int n, GridB g, const uint8_t* __restrict__ kp_is_orb,
+                                      uint16_t* __restrict__ cell)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    cell[i] = kf_cell_mixed(kps[i], g, kp_is_orb, i);
+}
+
+// MIXED: the search loop of MixedMatcher::Fuse (src/MixedMatcher.cpp:1703-1758, :1891-1921) and MixedMatcher::SearchByProjection(pKF,
+// Scw, ...) (:1136-1170, :1266-1300): a candidate of another type than the map point is skipped (isORBMP != isORBDescValid(idx)), the
+// level is getKPtLevelMono(idx) (octave of an ORB row, class_id of an AKAZE row) and the reprojection gate reads getKPtInvLevelSigma2(idx)
+// per keypoint.  The type test comes first and costs no load (the cell word has the bit); kp_inv_sigma2[i] is read last.
+template <bool SEQ, bool MIXED, typename Args>             // Args: RadArgs, or RadArgsMixed where MIXED
+__device__ __forceinline__ uint64_t radius_scan(const Args& A, int m, int first, int step, const uint8_t* taken)
 {
     const float u = A.uv[2 * m], v = A.uv[2 * m + 1], r = A.radius[m];
     int cx0, cx1, cy0, cy1;
     uint64_t k0 = ~0ull;
     if (!cell_range(A.g, u, v, r, cx0, cx1, cy0, cy1)) return k0;
     const int L = A.level[m];
+    int mp_type = 0;
+    if constexpr (MIXED) mp_type = (A.mp_is_orb && !A.mp_is_orb[m]) ? kCellNotOrb : 0;
     uint64_t q0, q1, q2, q3;
     load_desc32(A.q_desc + (size_t)m * 32, q0, q1, q2, q3);
     for (int i = first; i < A.n; i += step) {
-        const int cell = A.cell[i];
+        int cell = A.cell[i];
         if (cell == 0xFFFF) continue;
+        if (MIXED) {
+            if ((cell & kCellNotOrb) != mp_type) continue;
+            cell &= kCellNotOrb - 1;
+        }
         const int cx = cell / kGridRows, cy = cell - cx * kGridRows;
         if (cx < cx0 || cx > cx1 || cy < cy0 || cy > cy1) continue;
         const eorb_keypoint k = A.kps[i];
         const float distx = k.x - u, disty = k.y - v;
         if (!(fabsf(distx) < r && fabsf(disty) < r)) continue;
         if (SEQ && taken[i]) continue;
-        if (k.octave < L - 1 || k.octave > L) continue;
-        if (A.inv_sigma2) {
+        const int kpLevel = (MIXED && mp_type) ? k.class_id : k.octave;
+        if (kpLevel < L - 1 || kpLevel > L) continue;
+        // (two gates in full rather than one with a selected sigma: the ORB instantiation keeps the code it had, instruction for instruction)
+        if constexpr (MIXED) {
+            if (A.kp_inv_sigma2) {
+                const float ex = u - k.x, ey = v - k.y;
+                const float kpr = A.uright ? A.uright[i] : -1.f;
+                if (kpr >= 0.f) {                                              // src/MixedMatcher.cpp:1721-1734
+                    const float er = A.q_ur[m] - kpr;
+                    const float e2 = ex * ex + ey * ey + er * er;
+                    if ((double)(e2 * A.kp_inv_sigma2[i]) > 7.8) continue;     // e2*pKF->getKPtInvLevelSigma2(idx)
+                } else {
+                    const float e2 = ex * ex + ey * ey;
+                    if ((double)(e2 * A.kp_inv_sigma2[i]) > 5.99) continue;
+                }
+            }
+        } else if (A.inv_sigma2) {
             if (k.octave < 0 || k.octave >= A.nlevels) continue;
             const float ex = u - k.x, ey = v - k.y;
             const float kpr = A.uright ? A.uright[i] : -1.f;
@@ -1409,13 +1459,17 @@ __device__ __forceinline__ uint64_t radius_scan(const RadArgs& A, int m, int fir
     return k0;
 }
 
-__global__ __launch_bounds__(256) void kf_radius_kernel(RadArgs A)
+template <bool MIXED> using RadArgsOf = std::conditional_t<MIXED, RadArgsMixed, RadArgs>;
+template <bool MIXED> using RadBatchArgsOf = std::conditional_t<MIXED, RadBatchArgsMixed, RadBatchArgs>;
+
+template <bool MIXED>
+__global__ __launch_bounds__(256) void kf_radius_kernel(RadArgsOf<MIXED> A)
 {
     const int lane = threadIdx.x & 63;
     const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
     for (int m = gw; m < A.M; m += nw) {
         uint64_t k0 = ~0ull;
-        if (A.valid[m]) k0 = radius_scan<false>(A, m, lane, 64, nullptr);
+        if (A.valid[m]) k0 = radius_scan<false, MIXED>(A, m, lane, 64, nullptr);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k0, d, 64); k0 = o < k0 ? o : k0; }
         if (lane == 0) {
@@ -1426,7 +1480,8 @@ __global__ __launch_bounds__(256) void kf_radius_kernel(RadArgs A)
     }
 }
 
-__global__ __launch_bounds__(256) void kf_radius_seq_kernel(RadArgs A)
+template <bool MIXED>
+__global__ __launch_bounds__(256) void kf_radius_seq_kernel(RadArgsOf<MIXED> A)
 {
     extern __shared__ unsigned char smem[];
     uint64_t* red = (uint64_t*)smem;
@@ -1435,7 +1490,7 @@ __global__ __launch_bounds__(256) void kf_radius_seq_kernel(RadArgs A)
     __syncthreads();
     for (int m = 0; m < A.M; m++) {
         uint64_t k0 = ~0ull, k1 = ~0ull;
-        if (A.valid[m]) k0 = radius_scan<true>(A, m, threadIdx.x, blockDim.x, taken);
+        if (A.valid[m]) k0 = radius_scan<true, MIXED>(A, m, threadIdx.x, blockDim.x, taken);
         block_top2(k0, k1, red);
         if (threadIdx.x == 0) {
             const bool ok = k0 != ~0ull && (int)(k0 >> 44) < 256;
@@ -1448,22 +1503,31 @@ __global__ __launch_bounds__(256) void kf_radius_seq_kernel(RadArgs A)
     for (int i = threadIdx.x; i < A.n; i += blockDim.x) A.taken[i] = taken[i];
 }
 
-int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell)
+template <bool MIXED, typename Args>
+static int kf_radius_launch(eorb_ctx* c, const Args& A, uint16_t* d_cell, const uint8_t* d_kp_is_orb)
 {
     if (A.M <= 0) return EORB_OK;
-    ProfScope ps(c, "kf_radius_match");
-    if (A.n > 0) kf_cells_kernel<<<(A.n + 255) / 256, 256, 0, c->stream>>>(A.kps, A.n, A.g, d_cell);
+    ProfScope ps(c, MIXED ? "kf_radius_match_mixed" : "kf_radius_match");
+    if (A.n > 0) {
+        if constexpr (MIXED) kf_cells_mixed_kernel<<<(A.n + 255) / 256, 256, 0, c->stream>>>(A.kps, A.n, A.g, d_kp_is_orb, d_cell);
+        else kf_cells_kernel<<<(A.n + 255) / 256, 256, 0, c->stream>>>(A.kps, A.n, A.g, d_cell);
+    }
     if (A.taken) {
         const size_t lds = 64 + (((size_t)A.n + 15) & ~(size_t)15);
         if (lds > 160 * 1024) return set_err(c, EORB_E_CAPACITY, "kf_radius_match: %d keypoints exceed the LDS flags", A.n);
         int rc;
-        if ((rc = lds_optin(c, kOptKfRadius, (const void*)kf_radius_seq_kernel, 160 * 1024))) return rc;
-        kf_radius_seq_kernel<<<1, 256, lds, c->stream>>>(A);
+        if ((rc = lds_optin(c, MIXED ? kOptKfRadiusMixed : kOptKfRadius, (const void*)kf_radius_seq_kernel<MIXED>, 160 * 1024))) return rc;
+        kf_radius_seq_kernel<MIXED><<<1, 256, lds, c->stream>>>(A);
     } else {
-        kf_radius_kernel<<<std::min((A.M + 3) / 4, 4096), 256, 0, c->stream>>>(A);
+        kf_radius_kernel<MIXED><<<std::min((A.M + 3) / 4, 4096), 256, 0, c->stream>>>(A);
     }
     EORB_LAUNCH_CHECK(c, "kf_radius_match kernels");
     return EORB_OK;
+}
+int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell) { return kf_radius_launch<false>(c, A, d_cell, nullptr); }
+int kf_radius_mixed_dev(eorb_ctx* c, const RadArgsMixed& A, uint16_t* d_cell, const uint8_t* d_kp_is_orb)
+{
+    return kf_radius_launch<true>(c, A, d_cell, d_kp_is_orb);
 }
 
 // The same search over K keyframes at once (eorb_fuse_keyframes, eorb_fuse_pose, eorb_search_by_sim3): the keyframes' keypoints are
@@ -1481,8 +1545,18 @@ __global__ void kf_cells_batch_kernel(const eorb_keypoint* __restrict__ kps, int
     const int py = (int)roundf((kps[i].y - b.minY) * b.invH);
     cell[i] = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? (uint16_t)0xFFFF : (uint16_t)(px * kGridRows + py);
 }
+__global__ void kf_cells_batch_mixed_kernel(const eorb_keypoint* __restrict__ kps, int ntotal, const int32_t* __restrict__ kf_off, int K,
+                                            const GridB* __restrict__ g, const uint8_t* __restrict__ kp_is_orb, uint16_t* __restrict__ cell)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ntotal) return;
+    int lo = 0, hi = K - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (kf_off[mid] <= i) lo = mid; else hi = mid - 1; }
+    cell[i] = kf_cell_mixed(kps[i], g[lo], kp_is_orb, i);
+}
 
-__global__ __launch_bounds__(256) void kf_radius_batch_kernel(RadBatchArgs B)
+template <bool MIXED>
+__global__ __launch_bounds__(256) void kf_radius_batch_kernel(RadBatchArgsOf<MIXED> B)
 {
     const int lane = threadIdx.x & 63;
     const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -1491,16 +1565,17 @@ __global__ __launch_bounds__(256) void kf_radius_batch_kernel(RadBatchArgs B)
         const int k = (int)(q / B.M);
         const int off = B.kf_off[k];
         const size_t qo = (size_t)k * B.M;
-        RadArgs A{};
+        RadArgsOf<MIXED> A{};
         A.kps = B.kps + off; A.n = B.kf_off[k + 1] - off; A.desc = B.desc + (size_t)off * B.stride; A.stride = B.stride;
         A.g = B.g[k]; A.cell = B.cell + off;
         A.M = B.M; A.valid = B.valid + qo; A.uv = B.uv + 2 * qo; A.radius = B.radius + qo; A.level = B.level + qo;
         A.q_desc = B.q_desc + (size_t)k * B.q_desc_kstride;
         A.inv_sigma2 = B.inv_sigma2; A.nlevels = B.nlevels;
         A.uright = B.uright ? B.uright + off : nullptr; A.q_ur = B.uright ? B.q_ur + qo : nullptr;
+        if constexpr (MIXED) { A.mp_is_orb = B.mp_is_orb; A.kp_inv_sigma2 = B.kp_inv_sigma2 ? B.kp_inv_sigma2 + off : nullptr; }
         const int m = (int)(q - (int64_t)qo);
         uint64_t k0 = ~0ull;
-        if (A.valid[m]) k0 = radius_scan<false>(A, m, lane, 64, nullptr);
+        if (A.valid[m]) k0 = radius_scan<false, MIXED>(A, m, lane, 64, nullptr);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k0, d, 64); k0 = o < k0 ? o : k0; }
         if (lane == 0) {
@@ -1538,8 +1613,19 @@ int kf_radius_batch_dev(eorb_ctx* c, const RadBatchArgs& B, int ntotal, uint16_t
     if (nq <= 0) return EORB_OK;
     ProfScope ps(c, "kf_radius_batch");
     if (ntotal > 0) kf_cells_batch_kernel<<<(ntotal + 255) / 256, 256, 0, c->stream>>>(B.kps, ntotal, B.kf_off, B.K, B.g, d_cell);
-    kf_radius_batch_kernel<<<(unsigned)std::min<int64_t>((nq + 3) / 4, 8192), 256, 0, c->stream>>>(B);
+    kf_radius_batch_kernel<false><<<(unsigned)std::min<int64_t>((nq + 3) / 4, 8192), 256, 0, c->stream>>>(B);
     EORB_LAUNCH_CHECK(c, "kf_radius_batch kernels");
+    return EORB_OK;
+}
+
+int kf_radius_batch_mixed_dev(eorb_ctx* c, const RadBatchArgsMixed& B, int ntotal, uint16_t* d_cell, const uint8_t* d_kp_is_orb)
+{
+    const int64_t nq = (int64_t)B.K * B.M;
+    if (nq <= 0) return EORB_OK;
+    ProfScope ps(c, "kf_radius_batch_mixed");
+    if (ntotal > 0) kf_cells_batch_mixed_kernel<<<(ntotal + 255) / 256, 256, 0, c->stream>>>(B.kps, ntotal, B.kf_off, B.K, B.g, d_kp_is_orb, d_cell);
+    kf_radius_batch_kernel<true><<<(unsigned)std::min<int64_t>((nq + 3) / 4, 8192), 256, 0, c->stream>>>(B);
+    EORB_LAUNCH_CHECK(c, "kf_radius_batch_mixed kernels");
     return EORB_OK;
 }
 

@@ -83,6 +83,12 @@ struct RadBatchArgs {
     int32_t* best_idx; int32_t* best_dist;
 };
 
+// the mixed kernels' arguments (MixedMatcher's KeyFrame-side forms): the ORB ones plus mp_is_orb[M] (NULL = every map point ORB; one
+// array for all keyframes of a batch) and kp_inv_sigma2 = getKPtInvLevelSigma2(idx) per keypoint (NULL = no reprojection gate; inv_sigma2
+// / nlevels are unused).  The keypoints' types are bit 15 of their cell words (kf_cells_mixed_kernel).
+struct RadArgsMixed : RadArgs { const uint8_t* mp_is_orb; const float* kp_inv_sigma2; };
+struct RadBatchArgsMixed : RadBatchArgs { const uint8_t* mp_is_orb; const float* kp_inv_sigma2; };
+
 // DBoW2 vocabulary tree, device resident (TemplatedVocabulary::m_nodes flattened; node 0 = root)
 struct BowVoc {
     int nnodes, L;
@@ -125,6 +131,8 @@ int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR
                      int32_t* d_kdist2, int32_t* d_cand, int32_t* d_dist2);
 int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell);
 int kf_radius_batch_dev(eorb_ctx* c, const RadBatchArgs& B, int ntotal, uint16_t* d_cell);
+int kf_radius_mixed_dev(eorb_ctx* c, const RadArgsMixed& A, uint16_t* d_cell, const uint8_t* d_kp_is_orb);
+int kf_radius_batch_mixed_dev(eorb_ctx* c, const RadBatchArgsMixed& B, int ntotal, uint16_t* d_cell, const uint8_t* d_kp_is_orb);
 int sim3_agree_dev(eorb_ctx* c, const int32_t* best_idx, const int32_t* best_dist, int M, int N1, int N2, int th_high,
                    int32_t* vn1, int32_t* vn2, int32_t* match12, int32_t* nfound);
 int bow_transform_dev(eorb_ctx* c, const uint8_t* d_desc, int n, int stride, const BowVoc& V, int levelsup, int weighting, int norm,

@@ -6,6 +6,7 @@
 // The kernels write the caller-visible arrays and the packed records the matcher kernels read (match.hip), so a fused entry point
 // launches the matcher straight behind them.
 #include "project_args.h"
+#include <type_traits>
 
 namespace eorb {
 
@@ -212,7 +213,11 @@ __device__ __forceinline__ void kfside_store(const KfSideDev& O, size_t i, bool 
 // mode D: the projection of Fuse(pKF, vpMapPoints, th, bRight) (src/ORBmatcher.cc:1463-1513), Fuse(pKF, Scw, ...) (:1650-1690) and
 // SearchByProjection(pKF, Scw, ...) (:511-550, :595-), one thread per (keyframe, map point).  A rejected point keeps uv = (-1, -1)
 // and q_ur = 0 until IsInImage has passed, dist3d = 0 until it was computed, level = -1 and radius = 0 throughout.
-__global__ __launch_bounds__(256) void project_kfside_kernel(const KfSideArgs A)
+// MIXED: MixedMatcher's forms (src/MixedMatcher.cpp:1632-1688, :1837-1876, :1098-1134, :1226-1262), which differ in the tables alone: a
+// non-ORB point of a keyframe with AKAZE tables takes its level from getAKAZENLevels / getAKAZELogScaleFactor (src/MapPoint.cc:545-568)
+// and its radius from getAKAZEScaleFactor(level); the rule of scale_tables() above.
+template <bool MIXED>
+__global__ __launch_bounds__(256) void project_kfside_kernel(const std::conditional_t<MIXED, KfSideArgsMixed, KfSideArgs> A)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)A.K * A.M) return;
@@ -241,8 +246,15 @@ __global__ __launch_bounds__(256) void project_kfside_kernel(const KfSideArgs A)
             if (dist3D < 0.8f * minD || dist3D > 1.2f * maxD) reason = 5;
             else if (cv_dot3(PO, Pn) < 0.5 * (double)dist3D) reason = 6;   // "PO.dot(Pn)<0.5*dist3D": a comparison of doubles (:1504)
             else {
-                level = predict_scale(maxD, dist3D, A.nlevels, A.log_scale);
-                radius = A.th * A.sf[level];
+                bool ak = false;                                                 // the rule of scale_tables()
+                if constexpr (MIXED) ak = A.ak_nlevels > 0 && A.mp_is_orb && !A.mp_is_orb[m];
+                if constexpr (MIXED) {
+                    level = predict_scale(maxD, dist3D, ak ? A.ak_nlevels : A.nlevels, ak ? A.ak_log_scale : A.log_scale);
+                    radius = A.th * (ak ? A.ak_sf : A.sf)[level];
+                } else {
+                    level = predict_scale(maxD, dist3D, A.nlevels, A.log_scale);
+                    radius = A.th * A.sf[level];
+                }
                 valid = true;
             }
         }
@@ -292,8 +304,18 @@ int project_kfside_dev(eorb_ctx* c, const KfSideArgs& A)
     const size_t n = (size_t)A.K * A.M;
     if (n == 0) return EORB_OK;
     ProfScope ps(c, "project_kfside");
-    project_kfside_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(A);
+    project_kfside_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(A);
     EORB_LAUNCH_CHECK(c, "project_kfside_kernel");
+    return EORB_OK;
+}
+
+int project_kfside_mixed_dev(eorb_ctx* c, const KfSideArgsMixed& A)
+{
+    const size_t n = (size_t)A.K * A.M;
+    if (n == 0) return EORB_OK;
+    ProfScope ps(c, "project_kfside_mixed");
+    project_kfside_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(A);
+    EORB_LAUNCH_CHECK(c, "project_kfside_mixed_kernel");
     return EORB_OK;
 }
 

@@ -66,6 +66,9 @@ struct KfSideArgs {        // mode D: Fuse (both overloads), SearchByProjection(
     KfSideDev O;
 };
 
+// mode D for MixedMatcher: M flags (NULL = every point ORB) and the batch's AKAZE tables (ak_nlevels == 0: none)
+struct KfSideArgsMixed : KfSideArgs { const uint8_t* mp_is_orb; int ak_nlevels; float ak_log_scale; const float* ak_sf; };
+
 struct Sim3Half {          // mode E, one direction: p3Dc_b = sRba * (Raw * p3Dw + taw) + tba, searched in keyframe b
     float Ra[9], ta[3], sRb[9], tb[3];
     float fx, fy, cx, cy;                                       // pKF1's in both directions (:1746-1749)
@@ -81,6 +84,7 @@ struct Sim3Args {          // both halves in one launch; outputs as a 2 x M batc
 
 int project_frustum_dev(eorb_ctx* c, const FrustumArgs& A);
 int project_kfside_dev(eorb_ctx* c, const KfSideArgs& A);
+int project_kfside_mixed_dev(eorb_ctx* c, const KfSideArgsMixed& A);
 int project_sim3_dev(eorb_ctx* c, const Sim3Args& A);
 int project_last_dev(eorb_ctx* c, const LastArgs& A);
 int project_kf_dev(eorb_ctx* c, const KfArgs& A);

@@ -1057,6 +1057,107 @@ def FuseKeyFrames(views, gbs, kps, desc, kf_off, pos, normal, min_dist, max_dist
     return (bi, bd, rs) if want_reason else (bi, bd)
 
 
+# ---- the same for mixed ORB + AKAZE keyframes (MixedMatcher on a MixedKeyFrame; the *_mixed entry points of include/eorb_fe.h) ----------
+def _u8(a):
+    return None if a is None else np.ascontiguousarray(a, np.uint8)
+
+
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, np.float32)
+
+
+def KeyFrameRadiusMatchMixed(kps, desc, gb, valid, uv, radius, level, q_desc, kp_is_orb=None, kp_inv_sigma2=None, mp_is_orb=None,
+                             uright=None, q_ur=None, taken=None, accept_thr=0.0, ctx=None):
+    """Search loop of MixedMatcher::Fuse / SearchByProjection(pKF, Scw, ...) (src/MixedMatcher.cpp:1703-1758, :1136-1170): the type gate
+    kp_is_orb[idx] == mp_is_orb[m], the level of getKPtLevelMono and kp_inv_sigma2 = getKPtInvLevelSigma2 per keypoint (None: no
+    reprojection gate).  Returns (best_idx, best_dist) or (best_idx, best_dist, taken) when `taken` is given."""
+    c = ctx or default_context()
+    kps, desc, stride = _kf(kps, desc)
+    valid = _u8(valid); uv = _f32(uv); radius = _f32(radius); level = np.ascontiguousarray(level, np.int32); q_desc = _u8(q_desc)
+    M = len(valid)
+    if (uright is None) != (q_ur is None):
+        raise ValueError("the stereo gate takes uright and q_ur")
+    kio, sig, mio, ur, qr = _u8(kp_is_orb), _f32(kp_inv_sigma2), _u8(mp_is_orb), _f32(uright), _f32(q_ur)
+    for a, n, what in ((kio, len(kps), "kp_is_orb"), (sig, len(kps), "kp_inv_sigma2"), (ur, len(kps), "uright"), (mio, M, "mp_is_orb"), (qr, M, "q_ur")):
+        if a is not None and len(a) != n:
+            raise ValueError("%s has %d entries, not %d" % (what, len(a), n))
+    bi = np.zeros(M, np.int32); bd = np.zeros(M, np.int32)
+    tk = None if taken is None else np.array(taken, np.uint8)
+    c.check(c.L.eorb_kf_radius_match_mixed(c.h, _p(kps), len(kps), _p(desc), stride, C.byref(gb), _p(kio), _p(sig), _p(ur), M, _p(valid), _p(uv),
+                                           _p(radius), _p(level), _p(q_desc), _p(mio), _p(qr), _p(tk), float(accept_thr), _p(bi), _p(bd)))
+    return (bi, bd) if tk is None else (bi, bd, tk)
+
+
+def ProjectKeyFrameSideMixed(view_, pos, normal, min_dist, max_dist, th, mp_is_orb=None, skip=None, ctx=None):
+    """ProjectKeyFrameSide with the scale tables picked per point: a point with mp_is_orb == 0 takes the view's AKAZE tables
+    (src/MixedMatcher.cpp:1632-1688, src/MapPoint.cc:545-568)"""
+    c = ctx or default_context()
+    pos, normal, min_dist, max_dist, skip, mio = _points(pos, normal, min_dist, max_dist, skip, mp_is_orb)
+    M = len(min_dist)
+    rec, d = _kfside_out(M)
+    c.check(c.L.eorb_project_keyframe_side_mixed(c.h, C.byref(view_), M, _p(pos), _p(normal), _p(min_dist), _p(max_dist), _p(mio), _p(skip),
+                                                 float(th), C.byref(rec)))
+    return d
+
+
+def FusePoseMixed(kps, desc, gb, view_, pos, normal, min_dist, max_dist, q_desc, kp_is_orb=None, kp_inv_sigma2=None, mp_is_orb=None, th=3.0,
+                  skip=None, uright=None, want_projection=False, ctx=None):
+    """MixedMatcher::Fuse(pKF, vpMapPoints, th, bRight) up to the map update (src/MixedMatcher.cpp:1575-1758), projection included;
+    kp_inv_sigma2 None: the Sim3 overload (:1799-1921).  -> (best_idx, best_dist[, projection dict]); the caller thresholds with TH_LOW."""
+    c = ctx or default_context()
+    kps, desc, stride = _kf(kps, desc)
+    pos, normal, min_dist, max_dist, skip, mio = _points(pos, normal, min_dist, max_dist, skip, mp_is_orb)
+    q_desc = _u8(q_desc)
+    kio, sig, ur = _u8(kp_is_orb), _f32(kp_inv_sigma2), _f32(uright)
+    M = len(min_dist)
+    bi = np.zeros(M, np.int32); bd = np.zeros(M, np.int32)
+    rec, d = _kfside_out(M, want_projection)
+    c.check(c.L.eorb_fuse_pose_mixed(c.h, _p(kps), len(kps), _p(desc), stride, C.byref(gb), _p(kio), _p(sig), _p(ur), C.byref(view_), M, _p(pos),
+                                     _p(normal), _p(min_dist), _p(max_dist), _p(mio), _p(skip), _p(q_desc), float(th), _p(bi), _p(bd),
+                                     None if rec is None else C.byref(rec)))
+    return (bi, bd, d) if want_projection else (bi, bd)
+
+
+def SearchByProjectionKFScwMixed(kps, desc, gb, view_, pos, normal, min_dist, max_dist, q_desc, taken, th, kp_is_orb=None, mp_is_orb=None,
+                                 ratioHamming=1.0, skip=None, want_projection=False, ctx=None):
+    """both MixedMatcher::SearchByProjection(pKF, Scw, ...) (src/MixedMatcher.cpp:1065-1189, :1191-1324) up to the assignment of
+    vpMatched.  -> (best_idx, best_dist, taken[, projection dict])"""
+    c = ctx or default_context()
+    kps, desc, stride = _kf(kps, desc)
+    pos, normal, min_dist, max_dist, skip, mio = _points(pos, normal, min_dist, max_dist, skip, mp_is_orb)
+    q_desc = _u8(q_desc); kio = _u8(kp_is_orb)
+    tk = np.array(taken, np.uint8)
+    M = len(min_dist)
+    bi = np.zeros(M, np.int32); bd = np.zeros(M, np.int32)
+    rec, d = _kfside_out(M, want_projection)
+    c.check(c.L.eorb_search_by_projection_kf_scw_mixed(c.h, _p(kps), len(kps), _p(desc), stride, C.byref(gb), _p(kio), C.byref(view_), M, _p(pos),
+                                                       _p(normal), _p(min_dist), _p(max_dist), _p(mio), _p(skip), _p(q_desc), float(th), _p(tk),
+                                                       float(np.float32(ORBmatcher.TH_LOW) * np.float32(ratioHamming)), _p(bi), _p(bd),
+                                                       None if rec is None else C.byref(rec)))
+    return (bi, bd, tk, d) if want_projection else (bi, bd, tk)
+
+
+def FuseKeyFramesMixed(views, gbs, kps, desc, kf_off, pos, normal, min_dist, max_dist, q_desc, kp_is_orb=None, kp_inv_sigma2=None,
+                       mp_is_orb=None, th=3.0, skip=None, uright=None, want_reason=False, ctx=None):
+    """MixedMatcher::Fuse of M shared map points into K MixedKeyFrames in one call: FuseKeyFrames with kp_is_orb / kp_inv_sigma2
+    concatenated like kps and one mp_is_orb for all keyframes.  -> (best_idx K x M, best_dist K x M[, reason K x M]); the caller's part
+    is FuseKeyFrames' (include/eorb_fe.h)."""
+    c = ctx or default_context()
+    va, K = _views(views)
+    ga = (_lib.GridBounds * K)(*gbs)
+    kps, desc, stride = _kf(kps, desc)
+    off = np.ascontiguousarray(kf_off, np.int32)
+    pos, normal, min_dist, max_dist, skip, mio = _points(pos, normal, min_dist, max_dist, skip, mp_is_orb)
+    q_desc = _u8(q_desc)
+    kio, sig, ur = _u8(kp_is_orb), _f32(kp_inv_sigma2), _f32(uright)
+    M = len(min_dist)
+    bi = np.zeros((K, M), np.int32); bd = np.zeros((K, M), np.int32)
+    rs = np.zeros((K, M), np.uint8) if want_reason else None
+    c.check(c.L.eorb_fuse_keyframes_mixed(c.h, va, ga, K, _p(kps), _p(desc), stride, _p(kio), _p(sig), _p(ur), _p(off), M, _p(pos), _p(normal),
+                                          _p(min_dist), _p(max_dist), _p(mio), _p(q_desc), _p(skip), float(th), _p(bi), _p(bd), _p(rs)))
+    return (bi, bd, rs) if want_reason else (bi, bd)
+
+
 class ELK_Tracker:
     """EORB_SLAM::ELK_Tracker (src/Event/KLT_Tracker.cpp): pyramidal LK on the device + the reference's match bookkeeping."""
 

@@ -833,6 +833,70 @@ public:
                                     P.maxDist.data(), P.desc.ptr(), P.skip.empty() ? nullptr : P.skip.data(),
                                     invSigma2 ? invSigma2->data() : nullptr, th, bestIdx.data(), bestDist.data(), nullptr));
     }
+    // ---- the same on a MixedKeyFrame: EORB_SLAM::MixedMatcher's KeyFrame-side forms (see the *_mixed entry points of include/eorb_fe.h) ----
+    // what a MixedKeyFrame adds: kpIsOrb[i] = pKF->isORBDescValid(i), kpInvSigma2[i] = pKF->getKPtInvLevelSigma2(i) (empty: no
+    // reprojection gate), mpIsOrb[m] = vpMapPoints[m]->isORBMapPoint(); an empty vector means "all ORB" on that side
+    struct MixedKinds { std::vector<uint8_t> kpIsOrb; std::vector<float> kpInvSigma2; std::vector<uint8_t> mpIsOrb;
+        const uint8_t* kp() const { return kpIsOrb.empty() ? nullptr : kpIsOrb.data(); }
+        const float* sigma() const { return kpInvSigma2.empty() ? nullptr : kpInvSigma2.data(); }
+        const uint8_t* mp() const { return mpIsOrb.empty() ? nullptr : mpIsOrb.data(); } };
+    // search loop of MixedMatcher::Fuse / SearchByProjection(pKF, Scw, ...): KeyFrameRadiusMatch and FuseStereoMatch in one
+    void KeyFrameRadiusMatchMixed(const FrameView& KF, const MixedKinds& kinds, const std::vector<uint8_t>& valid, const std::vector<float>& uv,
+                                  const std::vector<float>& radius, const std::vector<int>& level, const eorb_host::Mat8& mpDesc,
+                                  const std::vector<float>* uright, const std::vector<float>* qUr, std::vector<uint8_t>* taken, float acceptThr,
+                                  std::vector<int>& bestIdx, std::vector<int>& bestDist) {
+        auto& c = eorb_host::thread_context();
+        const int M = (int)valid.size();
+        bestIdx.assign(M, -1); bestDist.assign(M, 256);
+        c.check(eorb_kf_radius_match_mixed(c.get(), KF.kps->data(), KF.numAllKPts(), KF.desc->ptr(), KF.desc->cols ? KF.desc->cols : 32, &KF.gb,
+                                           kinds.kp(), kinds.sigma(), uright ? uright->data() : nullptr, M, valid.data(), uv.data(),
+                                           radius.data(), level.data(), mpDesc.ptr(), kinds.mp(), qUr ? qUr->data() : nullptr,
+                                           taken ? taken->data() : nullptr, acceptThr, bestIdx.data(), bestDist.data()));
+    }
+    void ProjectKeyFrameSideMixed(const eorb_view& view, const MapPoints& P, const MixedKinds& kinds, float th, SideProjection& out) {
+        auto& c = eorb_host::thread_context();
+        const eorb_kfside_out o = out.bind((size_t)P.size());
+        c.check(eorb_project_keyframe_side_mixed(c.get(), &view, P.size(), P.pos.data(), P.normal.data(), P.minDist.data(), P.maxDist.data(),
+                                                 kinds.mp(), P.skip.empty() ? nullptr : P.skip.data(), th, &o));
+    }
+    // MixedMatcher::Fuse(pKF, vpMapPoints, th, bRight) up to the map update (src/MixedMatcher.cpp:1575-1758); kinds.kpInvSigma2 empty:
+    // MixedMatcher::Fuse(pKF, Scw, ...) (:1799-1921)
+    void FuseMixed(const FrameView& KF, const eorb_view& view, const MapPoints& P, const MixedKinds& kinds, const std::vector<float>* uright,
+                   float th, std::vector<int>& bestIdx, std::vector<int>& bestDist, SideProjection* proj = nullptr) {
+        auto& c = eorb_host::thread_context();
+        const int M = P.size();
+        bestIdx.assign(M, -1); bestDist.assign(M, 256);
+        eorb_kfside_out o{};
+        if (proj) o = proj->bind((size_t)M);
+        c.check(eorb_fuse_pose_mixed(c.get(), KF.kps->data(), KF.numAllKPts(), KF.desc->ptr(), KF.desc->cols ? KF.desc->cols : 32, &KF.gb,
+                                     kinds.kp(), kinds.sigma(), uright ? uright->data() : nullptr, &view, M, P.pos.data(), P.normal.data(),
+                                     P.minDist.data(), P.maxDist.data(), kinds.mp(), P.skip.empty() ? nullptr : P.skip.data(), P.desc.ptr(), th,
+                                     bestIdx.data(), bestDist.data(), proj ? &o : nullptr));
+    }
+    // both MixedMatcher::SearchByProjection(pKF, Scw, ...) up to the assignment of vpMatched (:1065-1189, :1191-1324): taken in / out
+    void SearchByProjectionMixed(const FrameView& KF, const eorb_view& view, const MapPoints& P, const MixedKinds& kinds,
+                                 std::vector<uint8_t>& taken, float th, float ratioHamming, std::vector<int>& bestIdx, std::vector<int>& bestDist) {
+        auto& c = eorb_host::thread_context();
+        const int M = P.size();
+        bestIdx.assign(M, -1); bestDist.assign(M, 256);
+        c.check(eorb_search_by_projection_kf_scw_mixed(c.get(), KF.kps->data(), KF.numAllKPts(), KF.desc->ptr(), KF.desc->cols ? KF.desc->cols : 32,
+                                                       &KF.gb, kinds.kp(), &view, M, P.pos.data(), P.normal.data(), P.minDist.data(),
+                                                       P.maxDist.data(), kinds.mp(), P.skip.empty() ? nullptr : P.skip.data(), P.desc.ptr(), th,
+                                                       taken.data(), (float)TH_LOW * ratioHamming, bestIdx.data(), bestDist.data(), nullptr));
+    }
+    // MixedMatcher::Fuse of P into K MixedKeyFrames at once: FuseKeyFrames with kinds.kpIsOrb / kpInvSigma2 concatenated like kps
+    void FuseKeyFramesMixed(const std::vector<eorb_view>& views, const std::vector<eorb_grid_bounds>& gbs,
+                            const std::vector<eorb_host::KeyPoint>& kps, const eorb_host::Mat8& desc, const std::vector<int32_t>& kfOff,
+                            const MapPoints& P, const MixedKinds& kinds, const std::vector<float>* uright, float th, std::vector<int>& bestIdx,
+                            std::vector<int>& bestDist) {
+        auto& c = eorb_host::thread_context();
+        const int K = (int)views.size(), M = P.size();
+        bestIdx.assign((size_t)K * M, -1); bestDist.assign((size_t)K * M, 256);
+        c.check(eorb_fuse_keyframes_mixed(c.get(), views.data(), gbs.data(), K, kps.data(), desc.ptr(), desc.cols ? desc.cols : 32, kinds.kp(),
+                                          kinds.sigma(), uright ? uright->data() : nullptr, kfOff.data(), M, P.pos.data(), P.normal.data(),
+                                          P.minDist.data(), P.maxDist.data(), kinds.mp(), P.desc.ptr(), P.skip.empty() ? nullptr : P.skip.data(),
+                                          th, bestIdx.data(), bestDist.data(), nullptr));
+    }
 protected:
     float mfNNratio; bool mbCheckOrientation;
 };

@@ -588,6 +588,60 @@ def keyframe_neighbourhood(seed, K, M, n_kps=1000, W=346, H=260, nlevels=8, scal
                 max_dist=s["max_dist"], mp_desc=mp_desc, scale_factors=sf, inv_sigma2=inv_sigma2, W=W, H=H)
 
 
+def akaze_tables(n_octaves=4, n_layers=4):
+    """the AKAZE pyramid of a MixedFrame, one entry per level = octave * n_layers + layer: scale 2^(level / n_layers)
+    -> (scale factors, log scale factor)"""
+    sf = np.array([2.0 ** (l / n_layers) for l in range(n_octaves * n_layers)], np.float32)
+    return sf, np.float32(np.log(np.float32(2.0 ** (1.0 / n_layers))))
+
+
+def mixed_keyframe_neighbourhood(seed, K, M, n_kps=1000, kinds=None, ak_frac=1.0 / 3.0, cross_frac=0.3, jitter=3.0, **kw):
+    """keyframe_neighbourhood(seed, K, M, n_kps) turned into K MixedKeyFrames: about ak_frac of the map points and of each keyframe's
+    rows are AKAZE.  The AKAZE pyramid has 16 levels at 2^(1/4) (4 octaves x 4 layers) against the ORB one's 8 at 1.2.  An AKAZE row
+    carries class_id = level and octave = class_id / 4 (a reader of octave gets the wrong level); an ORB row keeps octave = level,
+    class_id = -1.  A planted row is of its point's type except for cross_frac of them, which are of the other type, sit at a level
+    inside the point's window and carry the closer descriptor: only the type gate keeps them out.  kp_inv_sigma2 is the ORB table at
+    octave for an ORB row and the AKAZE table at class_id for an AKAZE row (not the ORB table's entry at that row's octave).
+    kinds[k] in ("mixed", "orb", "akaze") fixes keyframe k's row types.
+    -> keyframe_neighbourhood's dict (views with the AKAZE tables) plus mp_is_orb, kp_is_orb / kp_inv_sigma2 = lists per keyframe,
+    ak_scale_factors, ak_inv_sigma2"""
+    sc = keyframe_neighbourhood(seed, K, M, n_kps=n_kps, jitter=jitter, **kw)
+    rng = np.random.default_rng(seed + 2000)
+    ak_sf, ak_log = akaze_tables()
+    nA, nO = len(ak_sf), len(sc["scale_factors"])
+    ak_is2 = (np.float32(1.0) / (ak_sf * ak_sf)).astype(np.float32)
+    mp_is_orb = (rng.random(M) >= ak_frac).astype(np.uint8)
+    kinds = ["mixed"] * K if kinds is None else list(kinds)
+    kp_is_orb, kp_is2 = [], []
+    for k in range(K):
+        v = sc["views"][k]
+        v.update(ak_nlevels=nA, ak_log_scale=ak_log, ak_scale_factors=ak_sf)
+        kp, src, d = sc["kps"][k], sc["src"][k], sc["desc"][k]
+        n = len(kp)
+        planted = src >= 0
+        pt_orb = mp_is_orb[np.maximum(src, 0)]
+        if kinds[k] == "mixed":
+            cross = rng.random(n) < cross_frac
+            io = np.where(planted, np.where(cross, 1 - pt_orb, pt_orb), rng.random(n) >= ak_frac).astype(np.uint8)
+        else:
+            io = np.full(n, kinds[k] == "orb", np.uint8)
+        # the planted rows' levels: the point's predicted level in the point's own pyramid, minus 0 or 1
+        _, _, lvA, _ = _approx_side_projection(v["R"], v["t"], v["Ow"], v["cam"], v["bounds"], sc["pos"], sc["normal"], sc["min_dist"],
+                                               sc["max_dist"], nA, 2.0 ** 0.25)
+        lvl = np.where(pt_orb == 1, kp["octave"], lvA[np.maximum(src, 0)] - rng.integers(0, 2, n))
+        lvl = np.where(planted, lvl, np.where(io == 1, kp["octave"], rng.integers(0, nA, n)))
+        lvl = np.clip(lvl, 0, np.where(io == 1, nO - 1, nA - 1)).astype(np.int32)
+        kp["octave"] = np.where(io == 1, lvl, lvl // 4)
+        kp["class_id"] = np.where(io == 1, -1, lvl)
+        # a planted row of the other type is the closer one: at most 3 flipped bits
+        for i in np.flatnonzero(planted & (io != pt_orb)):
+            d[i] = flip_bits(sc["mp_desc"][src[i]], int(rng.integers(0, 4)), rng)
+        kp_is_orb.append(io)
+        kp_is2.append(np.where(io == 1, sc["inv_sigma2"][np.clip(kp["octave"], 0, nO - 1)], ak_is2[np.clip(lvl, 0, nA - 1)]).astype(np.float32))
+    sc.update(mp_is_orb=mp_is_orb, kp_is_orb=kp_is_orb, kp_inv_sigma2=kp_is2, ak_scale_factors=ak_sf, ak_inv_sigma2=ak_is2)
+    return sc
+
+
 def sim3_pair(seed, n=1000, s12=1.0, W=346, H=260, f=280.0, nlevels=8, scaleFactor=1.2, n_both=220, n_one=120, n_cross=120):
     """Two keyframes of n keypoint slots each and a similarity S12 between their cameras (p_c1 = s12*R12*p_c2 + t12), for
     ORBmatcher::SearchBySim3.  Physical points seen by both cameras get a keypoint in each keyframe, with the point's descriptor:

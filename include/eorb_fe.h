@@ -609,9 +609,9 @@ int eorb_kf_radius_match_stereo(eorb_ctx* ctx,
 
 /* ---- KeyFrame-side matchers with the projection on the device ----------------------------------------------------------------------
  * The projection loops in front of that search core, one thread per (keyframe, map point), in the reference's operation order with
- * its double steps, then the search behind the same upload, wait and download.  Only ORB map points:
- * MixedMatcher's KeyFrame-side forms gate keypoint type against point type and read a per-keypoint sigma table
- * (src/MixedMatcher.cpp:1707-1745); the search core has neither, so the views' AKAZE tables are ignored here.  The Sim3 decomposition
+ * its double steps, then the search behind the same upload, wait and download.  These five serve ORB keyframes
+ * and ignore the views' AKAZE tables; MixedMatcher's forms on a MixedKeyFrame (type gate, per-keypoint level and sigma, AKAZE tables)
+ * are the *_mixed entry points further down.  The Sim3 decomposition
  * (sRcw/scw, Ow = -Rcw.t()*tcw, :1628-1632) and the right camera's pose of bRight (:1400-1425) are 3 x 3 host algebra on cv::Mat
  * expressions and stay with the caller, who hands the result in as an eorb_view.
  *
@@ -696,6 +696,64 @@ int eorb_fuse_keyframes(eorb_ctx* ctx, const eorb_view* views, const eorb_grid_b
                         const eorb_keypoint* kps, const uint8_t* desc, int stride, const float* uright, const int32_t* kf_off,
                         int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* q_desc,
                         const uint8_t* skip, const float* inv_sigma2, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reason);
+
+/* ---- the same for mixed ORB + AKAZE keyframes: MixedMatcher on a MixedKeyFrame --------------------------------------------------------
+ * MixedMatcher::Fuse(pKF, vpMapPoints, th, bRight) (src/MixedMatcher.cpp:1575-1797), Fuse(pKF, Scw, ...) (:1799-1933) and both
+ * SearchByProjection(pKF, Scw, ...) (:1065-1189, :1191-1324) differ from the ORBmatcher forms above in four places, and in nothing else:
+ *   tables   a map point with mp_is_orb[m] == 0 (!pMP->isORBMapPoint()) takes its level from the view's AKAZE pyramid (ak_nlevels,
+ *            ak_log_scale: MapPoint::PredictScale(dist, pKF), src/MapPoint.cc:545-568) and radius = th * ak_scale_factors[level]
+ *            (getAKAZEScaleFactor, :1684-1688); on a view with ak_nlevels == 0 it falls back to the ORB tables, as in
+ *            eorb_project_frustum
+ *   type     a candidate with kp_is_orb[idx] != mp_is_orb[m] is skipped (isORBMP != pKF->isORBDescValid(idx), :1707-1710)
+ *   level    getKPtLevelMono(idx): octave of an ORB row, class_id of an AKAZE row (src/MixedFrame.cpp:438-446), in [level-1, level]
+ *   sigma    the reprojection gate of the first Fuse overload multiplies by kp_inv_sigma2[idx] = pKF->getKPtInvLevelSigma2(idx)
+ *            (:1732, :1743; the ORB table at octave for an ORB row, mvInvLevelSigma2AK[octave][layer of class_id] for an AKAZE row,
+ *            src/MixedFrame.cpp:486-497): a float product compared with the double 5.99, or 7.8 where uright[idx] >= 0
+ * kp_is_orb[n] / mp_is_orb[M]: 1 = ORB, NULL = all ORB on that side.  kp_inv_sigma2[n]: NULL = no reprojection gate (the Sim3
+ * overload and SearchByProjection have none); NULL with uright given is EORB_E_ARG.  AKAZE rows are compared on the first 32 bytes of
+ * their descriptor row at the caller's stride.  bRight, limits and error codes as the ORB forms.  With every flag NULL and
+ * kp_inv_sigma2[i] = inv_sigma2[octave of i], each function returns what its ORB counterpart returns. */
+
+/* eorb_kf_radius_match and eorb_kf_radius_match_stereo in one, with the type gate, the keypoint level and the per-keypoint sigma of
+ * the MixedMatcher search loops (:1703-1758, :1891-1921, :1136-1170, :1266-1300).  uright[n] / q_ur[M] (both or neither): the stereo
+ * gate; taken[n] / accept_thr (optional): the in-order form of SearchByProjection. */
+int eorb_kf_radius_match_mixed(eorb_ctx* ctx,
+        const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+        const uint8_t* kp_is_orb, const float* kp_inv_sigma2, const float* uright,
+        int M, const uint8_t* valid, const float* uv, const float* radius, const int32_t* level, const uint8_t* q_desc,
+        const uint8_t* mp_is_orb, const float* q_ur, uint8_t* taken, float accept_thr, int32_t* best_idx, int32_t* best_dist);
+
+/* mode D with the tables picked per point (:1632-1688, :1837-1876, :1098-1134, :1226-1262): eorb_project_keyframe_side otherwise */
+int eorb_project_keyframe_side_mixed(eorb_ctx* ctx, const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
+                                     const float* max_dist, const uint8_t* mp_is_orb, const uint8_t* skip, float th, const eorb_kfside_out* out);
+
+/* replaces MixedMatcher::Fuse(pKF, vpMapPoints, th, bRight) up to the map update (:1575-1758) and, with kp_inv_sigma2 == NULL,
+ * MixedMatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1799-1921): one upload, one wait, one download.  Returns exactly what
+ * eorb_project_keyframe_side_mixed followed by eorb_kf_radius_match_mixed returns. */
+int eorb_fuse_pose_mixed(eorb_ctx* ctx, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                         const uint8_t* kp_is_orb, const float* kp_inv_sigma2, const float* uright,
+                         const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist,
+                         const uint8_t* mp_is_orb, const uint8_t* skip, const uint8_t* q_desc, float th,
+                         int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out);
+
+/* replaces both MixedMatcher::SearchByProjection(pKF, Scw, vpPoints, [vpPointsKFs,] vpMatched, th, ratioHamming) (:1065-1189,
+ * :1191-1324) up to the assignment of vpMatched: eorb_search_by_projection_kf_scw with the tables, type gate and level above. */
+int eorb_search_by_projection_kf_scw_mixed(eorb_ctx* ctx, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride,
+                                           const eorb_grid_bounds* gb, const uint8_t* kp_is_orb, const eorb_view* view, int M, const float* pos,
+                                           const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_is_orb,
+                                           const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken, float accept_thr,
+                                           int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out);
+
+/* MixedMatcher::Fuse of M shared map points into K MixedKeyFrames at once (LocalMapping::SearchInNeighbors, LoopClosing::SearchAndFuse):
+ * eorb_fuse_keyframes with kp_is_orb / kp_inv_sigma2 concatenated like kps and one mp_is_orb[M] for all keyframes.  Every view must
+ * name the same ORB pyramid and the same AKAZE pyramid (ak_nlevels, ak_log_scale; the tables are views[0]'s), otherwise EORB_E_ARG.
+ * Entry k*M + m is what eorb_fuse_pose_mixed returns for keyframe k and point m.  The caller-side recipe above eorb_fuse_keyframes
+ * (apply in the reference's keyframe order, re-test the skip conditions, search stale descriptors again) applies word for word. */
+int eorb_fuse_keyframes_mixed(eorb_ctx* ctx, const eorb_view* views, const eorb_grid_bounds* gb, int K,
+                              const eorb_keypoint* kps, const uint8_t* desc, int stride, const uint8_t* kp_is_orb, const float* kp_inv_sigma2,
+                              const float* uright, const int32_t* kf_off,
+                              int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_is_orb,
+                              const uint8_t* q_desc, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reason);
 
 /* replaces MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423; f3), batched over M map points: the
  * descriptors observed for map point m are rows offsets[m] .. offsets[m+1]-1 of desc (n x 32); best[m] = the row (relative

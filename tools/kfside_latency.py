@@ -11,6 +11,13 @@ against the path callers have without them.  346 x 260, 1 000 keypoints per keyf
     fused            eorb_search_by_sim3
     cpu_path         the restatement of both projections, eorb_kf_radius_match twice, the agreement loop in numpy
 
+--mixed: the same shape on mixed ORB + AKAZE keyframes (synth.mixed_keyframe_neighbourhood), fuse K = 1, 8, 20
+    mixed_batched    eorb_fuse_keyframes_mixed, one call for the K keyframes
+    mixed_per_kf     eorb_fuse_pose_mixed, K calls
+    cpu_restatement  per keyframe: the CPU restatement of MixedMatcher's projection and search on one core of the same host
+                     (tests/kfside_mixed_ref, timing build)
+    orb_batched      eorb_fuse_keyframes on the same keypoints and points read as ORB ones: the ORB-only kernels in the same build
+
 The calls of a shape take turns inside one loop, so that a drift of the clocks or of the shared host touches them alike.  Prints one
 JSON object (and writes it to --out)."""
 import argparse, json, os, sys, time
@@ -37,12 +44,15 @@ def main():
     ap.add_argument("--M", type=int, default=1000)
     ap.add_argument("--n", type=int, default=1000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mixed", action="store_true", help="time the *_mixed entry points instead (profiles/kfside_mixed_latency.json)")
     a = ap.parse_args()
     import numpy as np
     from eorb_slam_amd import frontend as fe, synth
     from twocam_latency import _sources_hash
     import kfside_ref as ref
     M, n = a.M, a.n
+    if a.mixed:
+        return _mixed(a, np, fe, synth, _sources_hash())
     res = {"sources_hash": _sources_hash(), "M": M, "n": n, "size": [W, H], "fuse": {}, "sim3": {}}
     ctx = fe.Context()
     gb = fe.grid_bounds(W, H)
@@ -98,11 +108,63 @@ def main():
     e["fused_beats_cpu_path"] = bool(e["fused"]["p50_ms"] < e["cpu_path"]["p50_ms"])
     res["sim3"] = e
     ctx.close()
+    _emit(res, a.out)
+
+
+def _emit(res, out):
     line = json.dumps(res)
     print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        open(a.out, "w").write(line + "\n")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        open(out, "w").write(line + "\n")
+
+
+def _mixed(a, np, fe, synth, sources_hash):
+    import kfside_mixed_ref as mref
+    from oracle import oracle_py as oracle
+    oracle.build()
+    mref.use_oracle(oracle)
+    M, n = a.M, a.n
+    res = {"sources_hash": sources_hash, "M": M, "n": n, "size": [W, H], "mixed_fuse": {}}
+    ctx = fe.Context()
+    gb = fe.grid_bounds(W, H)
+    for K in (1, 8, 20):
+        sc = synth.mixed_keyframe_neighbourhood(200 + K, K, M, n_kps=n)
+        geom = (sc["pos"], sc["normal"], sc["min_dist"], sc["max_dist"])
+        views = [fe.view(**kw) for kw in sc["views"]]; rviews = [mref.view(**kw) for kw in sc["views"]]
+        frames = [oracle.Frame(sc["kps"][k], sc["desc"][k], W, H) for k in range(K)]
+        kps = np.concatenate(sc["kps"]); desc = np.concatenate(sc["desc"])
+        kio = np.concatenate(sc["kp_is_orb"]); sig = np.concatenate(sc["kp_inv_sigma2"]); mio = sc["mp_is_orb"]
+        off = (np.arange(K + 1) * n).astype(np.int32)
+        isg, qd = sc["inv_sigma2"], sc["mp_desc"]
+
+        def mixed_batched():
+            return fe.FuseKeyFramesMixed(views, [gb] * K, kps, desc, off, *geom, qd, kp_is_orb=kio, kp_inv_sigma2=sig, mp_is_orb=mio, th=3.0, ctx=ctx)
+
+        def mixed_per_kf():
+            return [fe.FusePoseMixed(sc["kps"][k], sc["desc"][k], gb, views[k], *geom, qd, kp_is_orb=sc["kp_is_orb"][k],
+                                     kp_inv_sigma2=sc["kp_inv_sigma2"][k], mp_is_orb=mio, th=3.0, ctx=ctx) for k in range(K)]
+
+        def cpu_restatement():
+            out = []
+            for k in range(K):
+                p = mref.keyframe_side(rviews[k], *geom, 3.0, mp_is_orb=mio, timing=True)
+                out.append(mref.search(frames[k], p, qd, kp_is_orb=sc["kp_is_orb"][k], kp_inv_sigma2=sc["kp_inv_sigma2"][k], mp_is_orb=mio, timing=True))
+            return out
+
+        def orb_batched():
+            return fe.FuseKeyFrames(views, [gb] * K, kps, desc, off, *geom, qd, inv_sigma2=isg, th=3.0, ctx=ctx)
+        b, f, c = mixed_batched(), mixed_per_kf(), cpu_restatement()
+        for k in range(K):
+            assert np.array_equal(b[0][k], f[k][0]) and np.array_equal(b[0][k], c[k][0]) and np.array_equal(b[1][k], c[k][1])
+        assert int((b[1] <= 50).sum()) >= 30 * K
+        e = _time({"mixed_batched": mixed_batched, "mixed_per_kf": mixed_per_kf, "cpu_restatement": cpu_restatement, "orb_batched": orb_batched},
+                  a.calls, np)
+        e["mixed_over_orb_batched"] = e["mixed_batched"]["p50_ms"] / e["orb_batched"]["p50_ms"]
+        e["accepted"] = {"mixed": int((b[1] <= 50).sum()), "orb_only": int((orb_batched()[1] <= 50).sum())}
+        res["mixed_fuse"]["K%d" % K] = e
+    ctx.close()
+    _emit(res, a.out)
 
 
 if __name__ == "__main__":
