@@ -26,6 +26,8 @@ EXPORTS = [
     "eorb_project_keyframe_side", "eorb_fuse_pose", "eorb_search_by_projection_kf_scw", "eorb_search_by_sim3", "eorb_fuse_keyframes",
     "eorb_kf_radius_match_mixed", "eorb_project_keyframe_side_mixed", "eorb_fuse_pose_mixed", "eorb_search_by_projection_kf_scw_mixed",
     "eorb_fuse_keyframes_mixed",
+    "eorb_search_for_triangulation_keyframes", "eorb_search_for_triangulation_kb8_keyframes", "eorb_search_by_bow_keyframes",
+    "eorb_search_by_bow_kf_keyframes",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
 ]
@@ -75,6 +77,12 @@ class KfSideOut(C.Structure):
     """eorb_kfside_out: the KeyFrame-side projection per (keyframe, map point), one array per member (any may be NULL)"""
     _fields_ = [("valid", C.c_void_p), ("uv", C.c_void_p), ("radius", C.c_void_p), ("level", C.c_void_p), ("q_ur", C.c_void_p),
                 ("dist3d", C.c_void_p), ("reason", C.c_void_p)]
+
+
+class KfSet(C.Structure):
+    """eorb_kf_set: K keyframes concatenated (rows and feature vectors; the arrays are host pointers: keep them alive)"""
+    _fields_ = [("K", C.c_int), ("kps", C.c_void_p), ("desc", C.c_void_p), ("stride", C.c_int), ("flag", C.c_void_p), ("kf_off", C.c_void_p),
+                ("nodes", C.c_void_p), ("node_off", C.c_void_p), ("feat_off", C.c_void_p), ("idx", C.c_void_p)]
 
 
 class Calib(C.Structure):
@@ -329,6 +337,16 @@ def lib():
     L.eorb_search_by_projection_kf_scw_mixed.argtypes = [vp, vp, ci, vp, ci, gbp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp, cf, vp, vp, vp]
     L.eorb_fuse_keyframes_mixed.restype = ci
     L.eorb_fuse_keyframes_mixed.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp]
+    ksp = C.POINTER(KfSet)
+    L.eorb_search_for_triangulation_keyframes.restype = ci
+    L.eorb_search_for_triangulation_keyframes.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, ci, ksp, vp, vp, vp, vp, ci, ci, ci, vp, vp]
+    L.eorb_search_for_triangulation_kb8_keyframes.restype = ci
+    L.eorb_search_for_triangulation_kb8_keyframes.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, ci, ksp, vp, vp, vp, vp, vp, vp, vp, vp, ci,
+                                                              ci, ci, vp, vp]
+    L.eorb_search_by_bow_keyframes.restype = ci
+    L.eorb_search_by_bow_keyframes.argtypes = [vp, ksp, vp, ci, vp, vp, vp, vp, ci, vp, cf, ci, vp]
+    L.eorb_search_by_bow_kf_keyframes.restype = ci
+    L.eorb_search_by_bow_kf_keyframes.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, ci, ksp, vp, cf, ci, vp]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]
     L.eorb_selfcheck_math.restype = ci; L.eorb_selfcheck_math.argtypes = [vp, ci, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.eorb_pack_events.restype = None; L.eorb_pack_events.argtypes = [vp, C.c_size_t, vp]

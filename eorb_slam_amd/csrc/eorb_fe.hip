@@ -2356,6 +2356,293 @@ int eorb_search_for_triangulation_kb8(eorb_ctx* c,
                              nlevels, bCoarse, checkOri, &K, match12, nmatches);
 }
 
+// ---- the node walks over K keyframes per call (eorb_kf_set of include/eorb_fe.h) ----------------------------------------------------
+static constexpr int kKfBatchMaxKfs = 1024;                             // K
+static constexpr int64_t kKfBatchMaxOut = (int64_t)1 << 22;             // K * the length of one output row
+static constexpr int64_t kKfBatchMaxRows = (int64_t)1 << 22;            // rows of all keyframes together; feature indices likewise
+
+// FvPair::queue's checks for one feature vector, plus its offsets; k >= 0 names the keyframe of a set
+static int fv_check(eorb_ctx* c, const char* what, const char* name, int k, const int32_t* off, const int32_t* idx, int nn, int n_features)
+{
+    char who[48];
+    if (k >= 0) snprintf(who, sizeof(who), "keyframe %d", k); else snprintf(who, sizeof(who), "%s", name);
+    if (nn == 0) return EORB_OK;
+    if (off[0] != 0) return set_err(c, EORB_E_ARG, "%s: %s: node offsets start at %d", what, who, off[0]);
+    for (int a = 0; a < nn; a++) if (off[a + 1] < off[a]) return set_err(c, EORB_E_ARG, "%s: %s: node offsets decrease at node %d", what, who, a);
+    if (off[nn] > kKfBatchMaxRows) return set_err(c, EORB_E_CAPACITY, "%s: %s: %d feature indices exceed %lld", what, who, off[nn], (long long)kKfBatchMaxRows);
+    for (int i = 0; i < off[nn]; i++)
+        if (idx[i] < 0 || idx[i] >= n_features) return set_err(c, EORB_E_ARG, "%s: %s: feature index out of range", what, who);
+    return EORB_OK;
+}
+
+// the set as a call's input: check() decides the limits from the sizes, then reads the offsets, then every index; queue() lays the
+// slice table and the concatenated arrays out in the arena (pack32: descriptor rows cut to their first 32 bytes, the BoW walk's row)
+struct KfSetIn {
+    std::vector<KfSlice> sl; int K = 0, ntotal = 0, nnodes = 0, nidx = 0, max_nn = 0, dstride = 0;
+    size_t o_sl = 0, o_kps = 0, o_desc = 0, o_flag = 0, o_nodes = 0, o_off = 0, o_idx = 0;
+    int check(eorb_ctx* c, const char* what, const eorb_kf_set* S, int n_out)
+    {
+        if (!S || S->K < 0 || n_out < 0) return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+        K = S->K;
+        if (K > kKfBatchMaxKfs || (int64_t)K * n_out > kKfBatchMaxOut)                 // (sizes only: nothing is read before this)
+            return set_err(c, EORB_E_CAPACITY, "%s: %d keyframes x %d outputs exceed %d keyframes or %lld outputs", what, K, n_out, kKfBatchMaxKfs,
+                           (long long)kKfBatchMaxOut);
+        if (K == 0) return EORB_OK;
+        if (S->stride < 32 || !S->kf_off || !S->node_off) return set_err(c, EORB_E_ARG, "%s: bad keyframe set", what);
+        if (S->kf_off[0] != 0 || S->node_off[0] != 0) return set_err(c, EORB_E_ARG, "%s: kf_off[0] = %d, node_off[0] = %d", what, S->kf_off[0], S->node_off[0]);
+        for (int k = 0; k < K; k++)
+            if (S->kf_off[k + 1] < S->kf_off[k] || S->node_off[k + 1] < S->node_off[k])
+                return set_err(c, EORB_E_ARG, "%s: kf_off or node_off decreases at keyframe %d", what, k);
+        ntotal = S->kf_off[K]; nnodes = S->node_off[K];
+        if (ntotal > kKfBatchMaxRows || nnodes > kKfBatchMaxRows)
+            return set_err(c, EORB_E_CAPACITY, "%s: %d rows, %d nodes exceed %lld", what, ntotal, nnodes, (long long)kKfBatchMaxRows);
+        if ((ntotal > 0 && (!S->kps || !S->desc || !S->flag)) || (nnodes > 0 && (!S->nodes || !S->feat_off || !S->idx)))
+            return set_err(c, EORB_E_ARG, "%s: keyframe set without arrays", what);
+        sl.resize(K);
+        int64_t idx0 = 0;
+        for (int k = 0; k < K; k++) {
+            KfSlice& s = sl[k];
+            s.row0 = S->kf_off[k]; s.nrows = S->kf_off[k + 1] - s.row0;
+            s.node0 = S->node_off[k]; s.nn = S->node_off[k + 1] - s.node0;
+            s.off0 = s.node0 + k; s.idx0 = (int32_t)idx0;
+            int rc;
+            if ((rc = fv_check(c, what, nullptr, k, S->feat_off + s.off0, S->idx + idx0, s.nn, s.nrows))) return rc;
+            if (s.nn > 0) idx0 += S->feat_off[s.off0 + s.nn];
+            if (idx0 > kKfBatchMaxRows) return set_err(c, EORB_E_CAPACITY, "%s: feature indices exceed %lld at keyframe %d", what, (long long)kKfBatchMaxRows, k);
+            max_nn = std::max(max_nn, s.nn);
+        }
+        nidx = (int)idx0;
+        return EORB_OK;
+    }
+    void queue(Arena& A, const eorb_kf_set* S, bool pack32)
+    {
+        o_sl = A.in(sl.data(), sizeof(KfSlice) * (size_t)K);
+        o_kps = A.in(S->kps, sizeof(eorb_keypoint) * (size_t)ntotal);
+        dstride = pack32 ? 32 : S->stride;
+        o_desc = pack32 ? A.in2d(S->desc, ntotal, 32, (size_t)S->stride) : A.in(S->desc, (size_t)S->stride * ntotal);
+        o_flag = A.in(S->flag, (size_t)ntotal);
+        o_nodes = A.in(S->nodes, sizeof(int32_t) * (size_t)nnodes);
+        o_off = A.in(S->feat_off, sizeof(int32_t) * ((size_t)nnodes + K));
+        o_idx = A.in(S->idx, sizeof(int32_t) * (size_t)nidx);
+    }
+    FeatVec fv(const Arena& A) const { return FeatVec{A.dev<uint32_t>(o_nodes), A.dev<int32_t>(o_off), A.dev<int32_t>(o_idx), 0}; }
+};
+
+// the shared side's feature vector, straight from the caller's arrays
+struct FvIn {
+    size_t o_nodes = 0, o_off = 0, o_idx = 0; int nn = 0;
+    void queue(Arena& A, const uint32_t* nodes, const int32_t* off, const int32_t* idx, int n)
+    {
+        nn = n;
+        o_nodes = A.in(nodes, sizeof(int32_t) * (size_t)nn); o_off = A.in(off, sizeof(int32_t) * ((size_t)nn + 1));
+        o_idx = A.in(idx, sizeof(int32_t) * (size_t)off[nn]);
+    }
+    FeatVec fv(const Arena& A) const { return FeatVec{A.dev<uint32_t>(o_nodes), A.dev<int32_t>(o_off), A.dev<int32_t>(o_idx), nn}; }
+};
+
+// K rows of n outputs: every slot -1, every count 0 (what a call returns where nothing can match)
+static void kfbatch_clear(int K, int n, int32_t* out, int32_t* nmatches)
+{
+    for (size_t i = 0; i < (size_t)K * n; i++) out[i] = -1;
+    if (nmatches) for (int k = 0; k < K; k++) nmatches[k] = 0;
+}
+
+// outputs of a batched walk, contiguous: [K x (32 histogram bins + nmatches) | K x n matches]; then the rotation bins
+struct KfBatchOut { size_t o_hist, o_m, o_bin; };
+static KfBatchOut kfbatch_reserve(Arena& A, int K, int n)
+{
+    KfBatchOut o;
+    o.o_hist = A.reserve(sizeof(int32_t) * kPairHist * (size_t)K); o.o_m = A.reserve(sizeof(int32_t) * (size_t)K * n); o.o_bin = A.reserve((size_t)K * n);
+    return o;
+}
+static int kfbatch_out(Arena& A, const KfBatchOut& o, int K, int n, int32_t* out, int32_t* nmatches)
+{
+    const char* h;
+    int rc;
+    if ((rc = A.download(o.o_hist, o.o_m + sizeof(int32_t) * (size_t)K * n - o.o_hist, &h))) return rc;
+    memcpy(out, h + o.o_m, sizeof(int32_t) * (size_t)K * n);
+    if (nmatches) for (int k = 0; k < K; k++) memcpy(nmatches + k, h + o.o_hist + sizeof(int32_t) * ((size_t)k * kPairHist + 32), 4);
+    return EORB_OK;
+}
+
+// search_tri_common over the K keyframes of a set: pKF1 and the level tables are uploaded once, the pairs' values go into device tables
+static int search_tri_batch_common(eorb_ctx* c, const char* what,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1, const eorb_kf_set* S, KfSetIn& J,
+        const float* ep, const float* F12, const float* scale2, const float* sigma2_2, const float* sigma2_1, int nlevels,
+        int bCoarse, int checkOri, TriKbArgs* kb, const int32_t* nleft2, const float* Rt, int32_t* match12, int32_t* nmatches)
+{
+    const int K = J.K;
+    fe_enter(c);
+    kfbatch_clear(K, n1, match12, nmatches);
+    if (K == 0 || n1 == 0 || nn1 == 0 || J.ntotal == 0 || J.max_nn == 0) return EORB_OK;
+    int rc;
+    if ((rc = fv_check(c, what, "pKF1", -1, node_off1, idx1, nn1, n1))) return rc;
+    for (int k = 0; k < K; k++) {
+        const KfSlice& s = J.sl[k];
+        if (s.nn == 0) continue;
+        for (int i = s.row0; i < s.row0 + s.nrows; i++)
+            if (S->flag[i] && (S->kps[i].octave < 0 || S->kps[i].octave >= nlevels))
+                return set_err(c, EORB_E_ARG, "%s: keyframe %d: keypoint %d has octave %d outside [0,%d)", what, k, i - s.row0, S->kps[i].octave, nlevels);
+    }
+    if (kb)
+        for (int i = 0; i < n1; i++)
+            if ((elig1[i] & 1) && (kps1[i].octave < 0 || kps1[i].octave >= nlevels))
+                return set_err(c, EORB_E_ARG, "%s: pKF1 keypoint %d has octave %d outside [0,%d)", what, i, kps1[i].octave, nlevels);
+    std::vector<TriPair> P(K);
+    std::vector<TriKbPair> Q(kb ? K : 0);
+    const int nrt = kb && kb->nleft1 >= 0 ? 48 : 12;
+    for (int k = 0; k < K; k++) {
+        P[k] = TriPair{};
+        P[k].epx = ep[2 * k]; P[k].epy = ep[2 * k + 1];
+        if (F12) for (int i = 0; i < 9; i++) P[k].F[i] = F12[9 * k + i];
+        if (kb) {
+            Q[k] = TriKbPair{};
+            Q[k].nleft2 = nleft2[k];
+            for (int i = 0; i < nrt; i++) Q[k].Rt[i] = Rt[(size_t)nrt * k + i];
+        }
+    }
+    Arena A(c);
+    FvIn f1;
+    f1.queue(A, nodes1, node_off1, idx1, nn1);
+    const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * n1), o_d1 = A.in(desc1, (size_t)stride1 * n1), o_e1 = A.in(elig1, n1);
+    const size_t o_sc = A.in(scale2, sizeof(float) * nlevels), o_sg = A.in(sigma2_2, sizeof(float) * nlevels);
+    const size_t o_s1 = kb ? A.in(sigma2_1, sizeof(float) * nlevels) : 0;
+    J.queue(A, S, false);
+    const size_t o_p = A.in(P.data(), sizeof(TriPair) * (size_t)K), o_q = kb ? A.in(Q.data(), sizeof(TriKbPair) * (size_t)K) : 0;
+    const KfBatchOut o = kfbatch_reserve(A, K, n1);
+    if ((rc = A.upload())) return rc;
+    TriBatchArgs B{};
+    TriArgs& T = B.T;
+    T.kps1 = A.dev<eorb_keypoint>(o_k1); T.n1 = n1; T.desc1 = A.dev<uint8_t>(o_d1); T.stride1 = stride1;
+    T.elig1 = A.dev<uint8_t>(o_e1); T.fv1 = f1.fv(A);
+    T.kps2 = A.dev<eorb_keypoint>(J.o_kps); T.n2 = 0; T.desc2 = A.dev<uint8_t>(J.o_desc); T.stride2 = J.dstride;
+    T.elig2 = A.dev<uint8_t>(J.o_flag); T.fv2 = J.fv(A);
+    T.scale2 = A.dev<float>(o_sc); T.sigma2_2 = A.dev<float>(o_sg); T.nlevels = nlevels;
+    T.bCoarse = bCoarse; T.checkOri = checkOri;
+    T.match12 = A.dev<int32_t>(o.o_m); T.bin1 = A.dev<int8_t>(o.o_bin); T.histo = A.dev<int32_t>(o.o_hist); T.nmatches = T.histo + 32;
+    B.kf = A.dev<KfSlice>(J.o_sl); B.pair = A.dev<TriPair>(o_p); B.K = K;
+    TriKbBatchArgs KB{};
+    if (kb) {
+        kb->T = T; kb->sigma2_1 = A.dev<float>(o_s1);
+        KB.K = *kb; KB.kf = B.kf; KB.pair = B.pair; KB.kb = A.dev<TriKbPair>(o_q); KB.nk = K;
+    }
+    if ((rc = search_tri_batch_dev(c, B, kb ? &KB : nullptr))) return rc;
+    return kfbatch_out(A, o, K, n1, match12, nmatches);
+}
+
+int eorb_search_for_triangulation_keyframes(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "search_for_triangulation_keyframes";
+    KfSetIn I;
+    int rc;
+    if ((rc = I.check(c, what, set, n1))) return rc;
+    if (nn1 < 0 || stride1 < 32 || !scale2 || !sigma2_2 || nlevels <= 0 || nlevels > 64 ||
+        (I.K > 0 && (!ep || !F12 || (n1 > 0 && (!match12 || !kps1 || !desc1 || !elig1)) || (nn1 > 0 && (!nodes1 || !node_off1 || !idx1)))))
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    return search_tri_batch_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, F12, scale2, sigma2_2,
+                                   nullptr, nlevels, bCoarse, checkOri, nullptr, nullptr, nullptr, match12, nmatches);
+}
+
+int eorb_search_for_triangulation_kb8_keyframes(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, const int32_t* nleft2,
+        const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
+        const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "search_for_triangulation_kb8_keyframes";
+    KfSetIn I;
+    int rc;
+    if ((rc = I.check(c, what, set, n1))) return rc;
+    if (nn1 < 0 || stride1 < 32 || !cam1 || !cam2 || !scale2 || !sigma2_1 || !sigma2_2 || nlevels <= 0 || nlevels > 64 || nleft1 < -1 || nleft1 > n1 ||
+        (I.K > 0 && (!ep || !Rt || !nleft2 || (n1 > 0 && (!match12 || !kps1 || !desc1 || !elig1)) || (nn1 > 0 && (!nodes1 || !node_off1 || !idx1)))))
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    for (int k = 0; k < I.K; k++)
+        if (nleft2[k] < -1 || nleft2[k] > I.sl[k].nrows) return set_err(c, EORB_E_ARG, "%s: keyframe %d: nleft2 %d", what, k, nleft2[k]);
+    fe_enter(c);
+    kfbatch_clear(I.K, n1, match12, nmatches);
+    const bool twocam = nleft1 >= 0;
+    for (int k = 0; k < I.K; k++)
+        if (twocam != (nleft2[k] >= 0))       // the reference leaves R12 an empty cv::Mat (:1000-1014)
+            return set_err(c, EORB_E_CONFIG, "%s: keyframe %d: one keyframe of the pair has two cameras and the other one", what, k);
+    const int nc1 = twocam ? 2 : 1;
+    for (int k = 0; k < nc1; k++)
+        if (cam1[k].model != 1)
+            return set_err(c, EORB_E_CONFIG, "%s: pKF1's camera %d is not KannalaBrandt8 (Pinhole pCamera1: eorb_search_for_triangulation_keyframes)", what, k);
+    for (int k = 0; k < nc1; k++)
+        if (cam2[k].model != 0 && cam2[k].model != 1) return set_err(c, EORB_E_ARG, "%s: the neighbours' camera %d has model %d", what, k, cam2[k].model);
+    TriKbArgs KA{};
+    KA.nleft1 = nleft1; KA.nleft2 = -1;
+    for (int k = 0; k < 2; k++) { KA.cam1[k] = cam1[k < nc1 ? k : 0]; KA.cam2[k] = cam2[k < nc1 ? k : 0]; }
+    return search_tri_batch_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, nullptr, scale2, sigma2_2,
+                                   sigma2_1, nlevels, bCoarse, checkOri, &KA, nleft2, Rt, match12, nmatches);
+}
+
+// bow_common over the K keyframes of a set.  kf_kf = 0: the set is the KeyFrame side, `one` the frame (flag1 unused);
+// kf_kf = 1: `one` is pKF1 with flag1 = has_mp1, the set is side 2.  Row k has n1 entries either way.
+static int bow_batch_common(eorb_ctx* c, const char* what, int kf_kf, const eorb_kf_set* S,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, const uint8_t* flag1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        int32_t* out, float nnratio, int checkOri, int32_t* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    KfSetIn I;
+    int rc;
+    if ((rc = I.check(c, what, S, n1))) return rc;
+    const int K = I.K;
+    if (nn1 < 0 || (K > 0 && ((n1 > 0 && (!out || !kps1 || !desc1 || (kf_kf && !flag1))) || (nn1 > 0 && (!nodes1 || !node_off1 || !idx1)))))
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    fe_enter(c);
+    kfbatch_clear(K, n1, out, nmatches);
+    if (K == 0 || n1 == 0 || nn1 == 0 || I.ntotal == 0 || I.max_nn == 0) return EORB_OK;
+    if ((rc = fv_check(c, what, kf_kf ? "pKF1" : "frame", -1, node_off1, idx1, nn1, n1))) return rc;
+    Arena A(c);
+    FvIn f1;
+    f1.queue(A, nodes1, node_off1, idx1, nn1);
+    const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * n1), o_d1 = A.in(desc1, 32 * (size_t)n1);
+    const size_t o_f1 = kf_kf ? A.in(flag1, n1) : 0;
+    I.queue(A, S, true);
+    const KfBatchOut o = kfbatch_reserve(A, K, n1);
+    const int nscratch = kf_kf ? I.ntotal : 0;                          // vbMatched2 of every pair
+    const size_t o_scr = A.reserve(sizeof(int32_t) * (size_t)nscratch);
+    if ((rc = A.upload())) return rc;
+    const eorb_keypoint* sk = A.dev<eorb_keypoint>(I.o_kps); const uint8_t* sd = A.dev<uint8_t>(I.o_desc); const uint8_t* sf = A.dev<uint8_t>(I.o_flag);
+    const eorb_keypoint* k1 = A.dev<eorb_keypoint>(o_k1); const uint8_t* d1 = A.dev<uint8_t>(o_d1);
+    int32_t* hist = A.dev<int32_t>(o.o_hist); int32_t* m = A.dev<int32_t>(o.o_m); int32_t* scr = A.dev<int32_t>(o_scr);
+    BowBatchArgs B{};
+    if (kf_kf) B.A = BowArgs{k1, d1, A.dev<uint8_t>(o_f1), f1.fv(A), sk, 0, sd, I.fv(A), scr, A.dev<int8_t>(o.o_bin), hist, hist + 32, nnratio, checkOri, 1, sf, m, n1};
+    else B.A = BowArgs{sk, sd, sf, I.fv(A), k1, n1, d1, f1.fv(A), m, A.dev<int8_t>(o.o_bin), hist, hist + 32, nnratio, checkOri, 0, sf, nullptr, 0};
+    B.kf = A.dev<KfSlice>(I.o_sl); B.K = K; B.n_out = n1; B.max_nn = kf_kf ? nn1 : I.max_nn;
+    if ((rc = search_bow_batch_dev(c, B, kf_kf ? scr : nullptr, nscratch))) return rc;
+    return kfbatch_out(A, o, K, n1, out, nmatches);
+}
+
+int eorb_search_by_bow_keyframes(eorb_ctx* c, const eorb_kf_set* set,
+        const eorb_keypoint* f_kps, int n_f, const uint8_t* f_desc,
+        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
+        int32_t* match_f, float nnratio, int checkOri, int32_t* nmatches)
+{
+    return bow_batch_common(c, "search_by_bow_keyframes", 0, set, f_kps, n_f, f_desc, nullptr, f_nodes, f_node_off, f_idx, f_nn, match_f, nnratio,
+                            checkOri, nmatches);
+}
+
+int eorb_search_by_bow_kf_keyframes(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, const uint8_t* has_mp1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, int32_t* match12, float nnratio, int checkOri, int32_t* nmatches)
+{
+    return bow_batch_common(c, "search_by_bow_kf_keyframes", 1, set, kps1, n1, desc1, has_mp1, nodes1, node_off1, idx1, nn1, match12, nnratio,
+                            checkOri, nmatches);
+}
+
 int eorb_kb8_triangulate_matches(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt,
         const eorb_keypoint* kps1, const eorb_keypoint* kps2, int n, const float* sigma2_1, const float* sigma2_2, int nlevels,
         float* z1)

@@ -1087,90 +1087,150 @@ __device__ __forceinline__ bool bow_accept(const BowArgs& A, uint64_t k0, uint64
     return (A.kf_kf ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW) && (float)bestDist1 < A.nnratio * (float)bestDist2;
 }
 
-__global__ __launch_bounds__(256) void search_bow_kernel(BowArgs A)
+// node a of the KeyFrame side, one wavefront
+__device__ __forceinline__ void bow_node(const BowArgs& A, int a, int lane)
 {
-    const int lane = threadIdx.x & 63;
-    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    for (int a = gw; a < A.kf_fv.nn; a += nw) {
-        const int lo = find_node(A.f_fv, A.kf_fv.nodes[a], lane);
-        if (lo < 0) continue;
-        const int f0 = A.f_fv.off[lo], f1 = A.f_fv.off[lo + 1];
-        const int k0n = A.kf_fv.off[a], k1n = A.kf_fv.off[a + 1];
-        if (f1 - f0 <= 64 && k1n - k0n <= 64) {
-            // The usual node (about ten features on either side): everything it touches is loaded once -- lane = frame feature for the
-            // candidates, lane = KeyFrame feature for the queries, handed round by shuffles.  A frame feature belongs to this node
-            // only, so "already matched" (vpMapPointMatches[realIdxF] / vbMatched2) is a lane-local flag: no memory round trip between
-            // the KeyFrame features of the node (the walk below took three dependent global loads per feature).
-            const int nF = f1 - f0, nK = k1n - k0n;
-            int idxF = -1; bool availF = false; uint64_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-            if (lane < nF) {
-                idxF = A.f_fv.idx[f0 + lane];
-                availF = A.match_f[idxF] < 0 && !(A.kf_kf && !A.f_has_mp[idxF]);
-                const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)idxF * 32);
-                t0 = tp[0]; t1 = tp[1]; t2 = tp[2]; t3 = tp[3];
-            }
-            int idxK = -1; bool hasK = false; uint64_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-            if (lane < nK) {
-                idxK = A.kf_fv.idx[k0n + lane];
-                hasK = A.kf_has_mp[idxK] != 0;
-                const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)idxK * 32);
-                q0 = dq[0]; q1 = dq[1]; q2 = dq[2]; q3 = dq[3];
-            }
-            for (int i = 0; i < nK; i++) {
-                if (!__shfl((int)hasK, i, 64)) continue;
-                const uint64_t b0 = __shfl(q0, i, 64), b1 = __shfl(q1, i, 64), b2 = __shfl(q2, i, 64), b3 = __shfl(q3, i, 64);
-                const int realIdxKF = __shfl(idxK, i, 64);
-                uint64_t k0 = ~0ull, k1 = ~0ull;
-                if (availF) {
-                    const int dist = __popcll(b0 ^ t0) + __popcll(b1 ^ t1) + __popcll(b2 ^ t2) + __popcll(b3 ^ t3);
-                    k0 = ((uint64_t)dist << 32) | (uint32_t)lane;          // candidate order = vector order = lane order
-                }
-                shfl_top2(k0, k1);
-                if (bow_accept(A, k0, k1)) {
-                    const int win = (int)(k0 & 63u);
-                    const int bestIdxF = __shfl(idxF, win, 64);
-                    if (lane == win) availF = false;
-                    if (lane == 0) bow_commit<false>(A, realIdxKF, bestIdxF, A.kf_kf ? realIdxKF : bestIdxF);
-                }
-            }
-            continue;
+    const int lo = find_node(A.f_fv, A.kf_fv.nodes[a], lane);
+    if (lo < 0) return;
+    const int f0 = A.f_fv.off[lo], f1 = A.f_fv.off[lo + 1];
+    const int k0n = A.kf_fv.off[a], k1n = A.kf_fv.off[a + 1];
+    if (f1 - f0 <= 64 && k1n - k0n <= 64) {
+        // The usual node (about ten features on either side): everything it touches is loaded once -- lane = frame feature for the
+        // candidates, lane = KeyFrame feature for the queries, handed round by shuffles.  A frame feature belongs to this node
+        // only, so "already matched" (vpMapPointMatches[realIdxF] / vbMatched2) is a lane-local flag: no memory round trip between
+        // the KeyFrame features of the node (the walk below took three dependent global loads per feature).
+        const int nF = f1 - f0, nK = k1n - k0n;
+        int idxF = -1; bool availF = false; uint64_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+        if (lane < nF) {
+            idxF = A.f_fv.idx[f0 + lane];
+            availF = A.match_f[idxF] < 0 && !(A.kf_kf && !A.f_has_mp[idxF]);
+            const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)idxF * 32);
+            t0 = tp[0]; t1 = tp[1]; t2 = tp[2]; t3 = tp[3];
         }
-        for (int iKF = k0n; iKF < k1n; iKF++) {
-            const int realIdxKF = A.kf_fv.idx[iKF];
-            if (!A.kf_has_mp[realIdxKF]) continue;
-            const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)realIdxKF * 32);
-            const uint64_t q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3];
-            // candidate order = vector order (iF): key = dist << 32 | iF keeps the reference's first-wins tie rule
+        int idxK = -1; bool hasK = false; uint64_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+        if (lane < nK) {
+            idxK = A.kf_fv.idx[k0n + lane];
+            hasK = A.kf_has_mp[idxK] != 0;
+            const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)idxK * 32);
+            q0 = dq[0]; q1 = dq[1]; q2 = dq[2]; q3 = dq[3];
+        }
+        for (int i = 0; i < nK; i++) {
+            if (!__shfl((int)hasK, i, 64)) continue;
+            const uint64_t b0 = __shfl(q0, i, 64), b1 = __shfl(q1, i, 64), b2 = __shfl(q2, i, 64), b3 = __shfl(q3, i, 64);
+            const int realIdxKF = __shfl(idxK, i, 64);
             uint64_t k0 = ~0ull, k1 = ~0ull;
-            for (int iF = f0 + lane; iF < f1; iF += 64) {
-                const int realIdxF = A.f_fv.idx[iF];
-                if (__hip_atomic_load(&A.match_f[realIdxF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) continue;   // vpMapPointMatches[realIdxF] / vbMatched2
-                if (A.kf_kf && !A.f_has_mp[realIdxF]) continue;                      // !pMP2 || pMP2->isBad()
-                const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)realIdxF * 32);
-                const int dist = __popcll(q0 ^ tp[0]) + __popcll(q1 ^ tp[1]) + __popcll(q2 ^ tp[2]) + __popcll(q3 ^ tp[3]);
-                top2_insert(((uint64_t)dist << 32) | (uint32_t)iF, k0, k1);
+            if (availF) {
+                const int dist = __popcll(b0 ^ t0) + __popcll(b1 ^ t1) + __popcll(b2 ^ t2) + __popcll(b3 ^ t3);
+                k0 = ((uint64_t)dist << 32) | (uint32_t)lane;          // candidate order = vector order = lane order
             }
             shfl_top2(k0, k1);
             if (bow_accept(A, k0, k1)) {
-                if (lane == 0) {
-                    const int bestIdxF = A.f_fv.idx[(int)(k0 & 0xffffffffu)];
-                    bow_commit<true>(A, realIdxKF, bestIdxF, A.kf_kf ? realIdxKF : bestIdxF);
-                }
-                __threadfence();          // the next KeyFrame feature of this node must see match_f
+                const int win = (int)(k0 & 63u);
+                const int bestIdxF = __shfl(idxF, win, 64);
+                if (lane == win) availF = false;
+                if (lane == 0) bow_commit<false>(A, realIdxKF, bestIdxF, A.kf_kf ? realIdxKF : bestIdxF);
             }
+        }
+        return;
+    }
+    for (int iKF = k0n; iKF < k1n; iKF++) {
+        const int realIdxKF = A.kf_fv.idx[iKF];
+        if (!A.kf_has_mp[realIdxKF]) continue;
+        const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)realIdxKF * 32);
+        const uint64_t q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3];
+        // candidate order = vector order (iF): key = dist << 32 | iF keeps the reference's first-wins tie rule
+        uint64_t k0 = ~0ull, k1 = ~0ull;
+        for (int iF = f0 + lane; iF < f1; iF += 64) {
+            const int realIdxF = A.f_fv.idx[iF];
+            if (__hip_atomic_load(&A.match_f[realIdxF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) continue;   // vpMapPointMatches[realIdxF] / vbMatched2
+            if (A.kf_kf && !A.f_has_mp[realIdxF]) continue;                      // !pMP2 || pMP2->isBad()
+            const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)realIdxF * 32);
+            const int dist = __popcll(q0 ^ tp[0]) + __popcll(q1 ^ tp[1]) + __popcll(q2 ^ tp[2]) + __popcll(q3 ^ tp[3]);
+            top2_insert(((uint64_t)dist << 32) | (uint32_t)iF, k0, k1);
+        }
+        shfl_top2(k0, k1);
+        if (bow_accept(A, k0, k1)) {
+            if (lane == 0) {
+                const int bestIdxF = A.f_fv.idx[(int)(k0 & 0xffffffffu)];
+                bow_commit<true>(A, realIdxKF, bestIdxF, A.kf_kf ? realIdxKF : bestIdxF);
+            }
+            __threadfence();          // the next KeyFrame feature of this node must see match_f
         }
     }
 }
 
+__global__ __launch_bounds__(256) void search_bow_kernel(BowArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+    for (int a = gw; a < A.kf_fv.nn; a += nw) bow_node(A, a, lane);
+}
+
+// ---- K pairs per launch: blockIdx.y = the pair, so the pair index and everything read with it is wave-uniform ----
+__device__ __forceinline__ FeatVec fv_slice(const FeatVec& all, const KfSlice& s)
+{
+    return FeatVec{all.nodes + s.node0, all.off + s.off0, all.idx + s.idx0, s.nn};
+}
+
+// the single walk's block for pair k.  SearchByBoW(pKF_k, F): the set is the KeyFrame side and pair k owns match_f / bin_f slice k.
+// SearchByBoW(pKF1, pKF2_k): the set is side 2 (the "frame" side of the walk); pair k owns match12 / bin_f slice k, and its vbMatched2
+// flags (match_f) are the set's rows row0 .. of the scratch array.  Either way a wavefront orders match_f accesses only against its
+// own earlier ones: a node of pair k touches only pair k's slice, at the features of that node.
+__device__ __forceinline__ BowArgs bow_pair(const BowBatchArgs& B, int k)
+{
+    const KfSlice s = B.kf[k];
+    BowArgs A = B.A;
+    const size_t o = (size_t)k * B.n_out;
+    // (offsets chosen by selects, one set of pointer additions: pointers assigned under a branch end up in scratch memory)
+    const bool kk = A.kf_kf != 0;
+    const int r1 = kk ? 0 : s.row0, r2 = kk ? s.row0 : 0;
+    A.kf_kps += r1; A.kf_desc += (size_t)r1 * 32; A.kf_has_mp += r1;
+    A.f_kps += r2; A.f_desc += (size_t)r2 * 32; A.f_has_mp += r2;
+    A.kf_fv = FeatVec{A.kf_fv.nodes + (kk ? 0 : s.node0), A.kf_fv.off + (kk ? 0 : s.off0), A.kf_fv.idx + (kk ? 0 : s.idx0), kk ? A.kf_fv.nn : s.nn};
+    A.f_fv = FeatVec{A.f_fv.nodes + (kk ? s.node0 : 0), A.f_fv.off + (kk ? s.off0 : 0), A.f_fv.idx + (kk ? s.idx0 : 0), kk ? s.nn : A.f_fv.nn};
+    A.n_kf = kk ? A.n_kf : s.nrows; A.n_f = kk ? s.nrows : A.n_f;
+    A.match_f += kk ? (size_t)s.row0 : o; A.match12 += kk ? o : 0;
+    A.bin_f += o;
+    A.histo += k * kPairHist; A.nmatches = A.histo + 32;
+    return A;
+}
+
+__global__ __launch_bounds__(256) void search_bow_batch_kernel(BowBatchArgs B)
+{
+    const BowArgs A = bow_pair(B, blockIdx.y);
+    const int lane = threadIdx.x & 63;
+    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+    for (int a = gw; a < A.kf_fv.nn; a += nw) bow_node(A, a, lane);
+}
+
+// three_maxima one bin at a time (the running state after bin i, then the 10 % rule) for rot_finish, whose loop over the bins is not
+// unrolled.  The window matchers and the fisheye walk keep three_maxima itself, the form their generated code was measured with.
+struct Maxima3 { int max1 = 0, max2 = 0, max3 = 0, a = -1, b = -1, c = -1; };
+__device__ __forceinline__ void maxima3_step(Maxima3& m, int s, int i)
+{
+    const bool g1 = s > m.max1, g2 = s > m.max2, g3 = s > m.max3;      // (max1 >= max2 >= max3: g1 implies g2 implies g3)
+    m.c = g2 ? m.b : (g3 ? i : m.c); m.max3 = g2 ? m.max2 : (g3 ? s : m.max3);
+    m.b = g1 ? m.a : (g2 ? i : m.b); m.max2 = g1 ? m.max1 : (g2 ? s : m.max2);
+    m.a = g1 ? i : m.a;              m.max1 = g1 ? s : m.max1;
+}
+__device__ __forceinline__ void maxima3_end(Maxima3 m, int& ind1, int& ind2, int& ind3)
+{
+    if ((float)m.max2 < 0.1f * (float)m.max1) { m.b = -1; m.c = -1; }
+    else if ((float)m.max3 < 0.1f * (float)m.max1) { m.c = -1; }
+    ind1 = m.a; ind2 = m.b; ind3 = m.c;
+}
+
 // the rotation check's end (ComputeThreeMaxima + the erase loop) over the n slots of out whose bins were recorded
-__global__ void search_bow_finish_kernel(int32_t* out, const int8_t* bin, int n, int32_t* histo, int32_t* nmatches)
+__device__ __forceinline__ void rot_finish(int32_t* out, const int8_t* bin, int n, int32_t* histo, int32_t* nmatches)
 {
     __shared__ int keep;
     if (threadIdx.x == 0) {
-        int h[HISTO_LENGTH];
-        for (int i = 0; i < HISTO_LENGTH; i++) h[i] = histo[i];
+        // (one bin at a time: unrolled, the 30 scalar loads and the compare masks of all steps are live at once and 55 SGPRs spill)
+        Maxima3 m;
+#pragma unroll 1
+        for (int i = 0; i < HISTO_LENGTH; i++) maxima3_step(m, histo[i], i);
         int i1, i2, i3;
-        three_maxima(h, HISTO_LENGTH, i1, i2, i3);
+        maxima3_end(m, i1, i2, i3);
         int k = 0;
         if (i1 >= 0) k |= 1 << i1; if (i2 >= 0) k |= 1 << i2; if (i3 >= 0) k |= 1 << i3;
         keep = k;
@@ -1182,6 +1242,28 @@ __global__ void search_bow_finish_kernel(int32_t* out, const int8_t* bin, int n,
         if (b >= 0 && !(keep & (1 << b)) && out[i] >= 0) { out[i] = -1; dec++; }
     }
     if (dec) atomicSub(nmatches, dec);
+}
+
+__global__ void search_bow_finish_kernel(int32_t* out, const int8_t* bin, int n, int32_t* histo, int32_t* nmatches)
+{
+    rot_finish(out, bin, n, histo, nmatches);
+}
+
+// one block per pair
+__global__ void search_finish_batch_kernel(int32_t* out, const int8_t* bin, int n, int32_t* histo)
+{
+    const size_t o = (size_t)blockIdx.x * n;
+    int32_t* h = histo + blockIdx.x * kPairHist;
+    rot_finish(out + o, bin + o, n, h, h + 32);
+}
+
+// K pairs: every output slot and bin -1, histograms and counters 0, the keyframe-to-keyframe form's vbMatched2 flags -1
+__global__ void search_init_batch_kernel(int32_t* out, int8_t* bin, int nout, int32_t* histo, int nhist, int32_t* scratch, int nscratch)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nout) { out[i] = -1; bin[i] = -1; }
+    if (i < nhist) histo[i] = 0;
+    if (i < nscratch) scratch[i] = -1;
 }
 
 __global__ void bow_init_kernel(int32_t* match_f, int8_t* bin_f, int n_f, int32_t* histo, int32_t* nmatches, int32_t* match12, int n_kf)
@@ -1206,6 +1288,26 @@ int search_bow_dev(eorb_ctx* c, const BowArgs& A)
                                                                            A.histo, A.nmatches);
     }
     EORB_LAUNCH_CHECK(c, "search_bow kernels");
+    return EORB_OK;
+}
+
+static void search_init_batch(eorb_ctx* c, int32_t* out, int8_t* bin, int K, int n_out, int32_t* histo, int32_t* scratch, int nscratch)
+{
+    const int nout = K * n_out, nhist = K * kPairHist;          // (K * n_out <= 2^22: the entry points' limit)
+    search_init_batch_kernel<<<(std::max(std::max(nout, nhist), nscratch) + 255) / 256, 256, 0, c->stream>>>(out, bin, nout, histo, nhist, scratch, nscratch);
+}
+
+// three launches for any K: init, walk (one wavefront per pair and KeyFrame-side node), rotation finish (one block per pair)
+int search_bow_batch_dev(eorb_ctx* c, const BowBatchArgs& B, int32_t* scratch, int nscratch)
+{
+    ProfScope ps(c, B.A.kf_kf ? "search_by_bow_kf_keyframes" : "search_by_bow_keyframes");
+    int32_t* out = B.A.kf_kf ? B.A.match12 : B.A.match_f;
+    search_init_batch(c, out, B.A.bin_f, B.K, B.n_out, B.A.histo, scratch, nscratch);
+    if (B.max_nn > 0) {
+        search_bow_batch_kernel<<<dim3(std::min((B.max_nn + 3) / 4, 1024), B.K), 256, 0, c->stream>>>(B);
+        if (B.A.checkOri) search_finish_batch_kernel<<<B.K, 256, 0, c->stream>>>(out, B.A.bin_f, B.n_out, B.A.histo);
+    }
+    EORB_LAUNCH_CHECK(c, "search_bow batch kernels");
     return EORB_OK;
 }
 
@@ -1234,58 +1336,63 @@ __device__ __forceinline__ bool epipolar_ok(float x1, float y1, float x2, float 
     return dsqr < 3.84f * unc;
 }
 
+// entry p of fv1, one wavefront
+template <class G, class Args>
+__device__ __forceinline__ void tri_entry(const TriArgs& A, const Args& GA, int p, int lane)
+{
+    const int id1 = A.fv1.idx[p];
+    const uint8_t e1 = A.elig1[id1];                // bit 0: eligible; bit 1: rectified-stereo keypoint (mvuRight >= 0, bStereo1 :1051)
+    if (!(e1 & 1)) return;
+    int lo = 0, hi = A.fv1.nn;                      // node a with off1[a] <= p < off1[a+1]
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.fv1.off[mid] <= p) lo = mid; else hi = mid; }
+    const uint32_t node = A.fv1.nodes[lo];
+    int l2 = 0, h2 = A.fv2.nn;
+    while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (A.fv2.nodes[mid] < node) l2 = mid + 1; else h2 = mid; }
+    if (l2 >= A.fv2.nn || A.fv2.nodes[l2] != node) return;
+    const eorb_keypoint kp1 = A.kps1[id1];
+    const G g(GA, id1, e1, kp1);
+    uint64_t q0, q1, q2, q3;
+    load_desc32(A.desc1 + (size_t)id1 * A.stride1, q0, q1, q2, q3);
+    uint64_t k0 = ~0ull;
+    for (int i2 = A.fv2.off[l2] + lane; i2 < A.fv2.off[l2 + 1]; i2 += 64) {
+        const int id2 = A.fv2.idx[i2];
+        const uint8_t e2 = A.elig2[id2];
+        if (!(e2 & 1)) continue;
+        uint64_t t0, t1, t2, t3;
+        load_desc32(A.desc2 + (size_t)id2 * A.stride2, t0, t1, t2, t3);
+        const int dist = __popcll(q0 ^ t0) + __popcll(q1 ^ t1) + __popcll(q2 ^ t2) + __popcll(q3 ^ t3);
+        if (dist > TH_LOW) continue;
+        const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)(~(uint32_t)i2);
+        if (key >= k0) continue;                                           // cannot change this lane's answer
+        const eorb_keypoint kp2 = A.kps2[id2];
+        if (kp2.octave < 0 || kp2.octave >= A.nlevels) continue;            // rejected on the host already
+        if (g.epipole_gate(e2)) {
+            const float distex = A.epx - kp2.x, distey = A.epy - kp2.y;
+            if (distex * distex + distey * distey < 100 * A.scale2[kp2.octave]) continue;
+        }
+        if (!(A.bCoarse || g.ok(id2, kp2))) continue;
+        k0 = key;
+    }
+    k0 = shfl_min(k0);
+    if (lane == 0 && k0 != ~0ull) {
+        const int bestIdx2 = A.fv2.idx[(int)(~(uint32_t)(k0 & 0xffffffffu))];
+        A.match12[id1] = bestIdx2;
+        atomicAdd(A.nmatches, 1);
+        if (A.checkOri) {
+            const int bin = rot_bin(kp1.angle, A.kps2[bestIdx2].angle);
+            A.bin1[id1] = (int8_t)bin;
+            atomicAdd(&A.histo[bin], 1);
+        }
+    }
+}
+
 template <class G, class Args>
 __device__ __forceinline__ void tri_walk(const TriArgs& A, const Args& GA)
 {
     const int lane = threadIdx.x & 63;
     const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
     const int total = A.fv1.off[A.fv1.nn];
-    for (int p = gw; p < total; p += nw) {
-        const int id1 = A.fv1.idx[p];
-        const uint8_t e1 = A.elig1[id1];                // bit 0: eligible; bit 1: rectified-stereo keypoint (mvuRight >= 0, bStereo1 :1051)
-        if (!(e1 & 1)) continue;
-        int lo = 0, hi = A.fv1.nn;                      // node a with off1[a] <= p < off1[a+1]
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.fv1.off[mid] <= p) lo = mid; else hi = mid; }
-        const uint32_t node = A.fv1.nodes[lo];
-        int l2 = 0, h2 = A.fv2.nn;
-        while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (A.fv2.nodes[mid] < node) l2 = mid + 1; else h2 = mid; }
-        if (l2 >= A.fv2.nn || A.fv2.nodes[l2] != node) continue;
-        const eorb_keypoint kp1 = A.kps1[id1];
-        const G g(GA, id1, e1, kp1);
-        uint64_t q0, q1, q2, q3;
-        load_desc32(A.desc1 + (size_t)id1 * A.stride1, q0, q1, q2, q3);
-        uint64_t k0 = ~0ull;
-        for (int i2 = A.fv2.off[l2] + lane; i2 < A.fv2.off[l2 + 1]; i2 += 64) {
-            const int id2 = A.fv2.idx[i2];
-            const uint8_t e2 = A.elig2[id2];
-            if (!(e2 & 1)) continue;
-            uint64_t t0, t1, t2, t3;
-            load_desc32(A.desc2 + (size_t)id2 * A.stride2, t0, t1, t2, t3);
-            const int dist = __popcll(q0 ^ t0) + __popcll(q1 ^ t1) + __popcll(q2 ^ t2) + __popcll(q3 ^ t3);
-            if (dist > TH_LOW) continue;
-            const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)(~(uint32_t)i2);
-            if (key >= k0) continue;                                           // cannot change this lane's answer
-            const eorb_keypoint kp2 = A.kps2[id2];
-            if (kp2.octave < 0 || kp2.octave >= A.nlevels) continue;            // rejected on the host already
-            if (g.epipole_gate(e2)) {
-                const float distex = A.epx - kp2.x, distey = A.epy - kp2.y;
-                if (distex * distex + distey * distey < 100 * A.scale2[kp2.octave]) continue;
-            }
-            if (!(A.bCoarse || g.ok(id2, kp2))) continue;
-            k0 = key;
-        }
-        k0 = shfl_min(k0);
-        if (lane == 0 && k0 != ~0ull) {
-            const int bestIdx2 = A.fv2.idx[(int)(~(uint32_t)(k0 & 0xffffffffu))];
-            A.match12[id1] = bestIdx2;
-            atomicAdd(A.nmatches, 1);
-            if (A.checkOri) {
-                const int bin = rot_bin(kp1.angle, A.kps2[bestIdx2].angle);
-                A.bin1[id1] = (int8_t)bin;
-                atomicAdd(&A.histo[bin], 1);
-            }
-        }
-    }
+    for (int p = gw; p < total; p += nw) tri_entry<G>(A, GA, p, lane);
 }
 
 struct TriPinhole {                  // pCamera1 = Pinhole: the test on F12
@@ -1298,19 +1405,23 @@ struct TriPinhole {                  // pCamera1 = Pinhole: the test on F12
 // pCamera1 = KannalaBrandt8: epipolarConstrain = TriangulateMatches(...) > KB8_DEF_TH_EPC (KannalaBrandt8.cpp:315-320, :416-486).
 // Two-camera keyframes (nleft >= 0) pick one of four poses and cameras per (left/right, left/right) pair (:1107-1137) and skip
 // the epipole test; bStereo is false for them (:1051, :1079).
+struct TriKbPairView { const TriKbArgs& K; const float* Rt; int nleft2; };       // pair k of a batch: K's own Rt / nleft2 are unused
 struct TriKb8 {
-    const TriKbArgs& K; const int bRight1; const bool bStereo1; const float x1, y1, sig1;
-    __device__ __forceinline__ TriKb8(const TriKbArgs& k, int id1, uint8_t e1, const eorb_keypoint& kp1)
-        : K(k), bRight1(k.nleft1 >= 0 && id1 >= k.nleft1), bStereo1(k.nleft1 < 0 && (e1 & 2)), x1(kp1.x), y1(kp1.y), sig1(k.sigma2_1[kp1.octave]) {}
+    const TriKbArgs& K; const float* const Rt; const int nleft2; const int bRight1; const bool bStereo1; const float x1, y1, sig1;
+    __device__ __forceinline__ TriKb8(const TriKbArgs& k, const float* rt, int nl2, int id1, uint8_t e1, const eorb_keypoint& kp1)
+        : K(k), Rt(rt), nleft2(nl2), bRight1(k.nleft1 >= 0 && id1 >= k.nleft1), bStereo1(k.nleft1 < 0 && (e1 & 2)), x1(kp1.x), y1(kp1.y),
+          sig1(k.sigma2_1[kp1.octave]) {}
+    __device__ __forceinline__ TriKb8(const TriKbArgs& k, int id1, uint8_t e1, const eorb_keypoint& kp1) : TriKb8(k, k.Rt, k.nleft2, id1, e1, kp1) {}
+    __device__ __forceinline__ TriKb8(const TriKbPairView& v, int id1, uint8_t e1, const eorb_keypoint& kp1) : TriKb8(v.K, v.Rt, v.nleft2, id1, e1, kp1) {}
     __device__ __forceinline__ bool twocam() const { return K.nleft1 >= 0; }
     __device__ __forceinline__ bool epipole_gate(uint8_t e2) const { return !twocam() && !bStereo1 && !(e2 & 2); }      // :1097-1105
     __device__ __forceinline__ bool ok(int id2, const eorb_keypoint& kp2) const
     {
-        const int bRight2 = twocam() && id2 >= K.nleft2;
+        const int bRight2 = twocam() && id2 >= nleft2;
         const int pose = twocam() ? (bRight1 << 1 | bRight2) : 0;       // ll, lr, rl, rr
         const WarpCam c1 = warp_cam_of(K.cam1[twocam() ? bRight1 : 0]);
         const WarpCam c2 = warp_cam_of(K.cam2[twocam() ? bRight2 : 0]);
-        return kb8_triangulate_matches(c1, c2, x1, y1, kp2.x, kp2.y, K.Rt + 12 * pose, K.Rt + 12 * pose + 9, sig1,
+        return kb8_triangulate_matches(c1, c2, x1, y1, kp2.x, kp2.y, Rt + 12 * pose, Rt + 12 * pose + 9, sig1,
                                        K.T.sigma2_2[kp2.octave]) > 0.0001f;       // KB8_DEF_TH_EPC
     }
 };
@@ -1318,6 +1429,33 @@ struct TriKb8 {
 // two entry points, not one with a run-time camera switch: the Pinhole walk needs a third of the KannalaBrandt8 one's registers
 __global__ __launch_bounds__(256) void search_tri_kernel(TriArgs A) { tri_walk<TriPinhole>(A, A); }
 __global__ __launch_bounds__(256) void search_tri_kb8_kernel(TriKbArgs K) { tri_walk<TriKb8>(K.T, K); }
+
+// K pairs per launch (blockIdx.y = the pair): pKF1 and the level tables stay as in T; pKF2_k, its epipole and F12 come from the tables
+__device__ __forceinline__ TriArgs tri_pair(const TriArgs& T, const KfSlice* kf, const TriPair* pair, int k, bool pinhole)
+{
+    const KfSlice s = kf[k];
+    TriArgs A = T;
+    A.kps2 += s.row0; A.n2 = s.nrows; A.desc2 += (size_t)s.row0 * A.stride2; A.elig2 += s.row0; A.fv2 = fv_slice(A.fv2, s);
+    A.epx = pair[k].epx; A.epy = pair[k].epy;
+    if (pinhole) for (int i = 0; i < 9; i++) A.F[i] = pair[k].F[i];
+    const size_t o = (size_t)k * A.n1;
+    A.match12 += o; A.bin1 += o;
+    A.histo += k * kPairHist; A.nmatches = A.histo + 32;
+    return A;
+}
+
+__global__ __launch_bounds__(256) void search_tri_batch_kernel(TriBatchArgs B)
+{
+    const TriArgs A = tri_pair(B.T, B.kf, B.pair, blockIdx.y, true);
+    tri_walk<TriPinhole>(A, A);
+}
+
+__global__ __launch_bounds__(256) void search_tri_kb8_batch_kernel(TriKbBatchArgs B)
+{
+    const TriArgs A = tri_pair(B.K.T, B.kf, B.pair, blockIdx.y, false);
+    const TriKbPair* kb = B.kb + blockIdx.y;
+    tri_walk<TriKb8>(A, TriKbPairView{B.K, kb->Rt, kb->nleft2});
+}
 
 int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K)
 {
@@ -1328,6 +1466,20 @@ int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K)
     else search_tri_kernel<<<blocks, 256, 0, c->stream>>>(A);
     if (A.checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A.match12, A.bin1, A.n1, A.histo, A.nmatches);
     EORB_LAUNCH_CHECK(c, K ? "search_for_triangulation_kb8 kernels" : "search_for_triangulation kernels");
+    return EORB_OK;
+}
+
+// init, walk (one wavefront per pair and entry of fv1), rotation finish (one block per pair)
+int search_tri_batch_dev(eorb_ctx* c, const TriBatchArgs& B, const TriKbBatchArgs* K)
+{
+    ProfScope ps(c, K ? "search_for_triangulation_kb8_keyframes" : "search_for_triangulation_keyframes");
+    const TriArgs& T = B.T;
+    search_init_batch(c, T.match12, T.bin1, B.K, T.n1, T.histo, nullptr, 0);
+    const dim3 grid(std::min((T.n1 + 3) / 4 + 1, 2048), B.K);
+    if (K) search_tri_kb8_batch_kernel<<<grid, 256, 0, c->stream>>>(*K);
+    else search_tri_batch_kernel<<<grid, 256, 0, c->stream>>>(B);
+    if (T.checkOri) search_finish_batch_kernel<<<B.K, 256, 0, c->stream>>>(T.match12, T.bin1, T.n1, T.histo);
+    EORB_LAUNCH_CHECK(c, K ? "search_for_triangulation_kb8 batch kernels" : "search_for_triangulation batch kernels");
     return EORB_OK;
 }
 

@@ -61,6 +61,21 @@ struct TriKbArgs {
     const float* sigma2_1;
 };
 
+// ---- the node walks over K keyframes per call (match.hip search_bow_batch_kernel, search_tri_batch_kernel, search_tri_kb8_batch_kernel) ----
+// Keyframe k of the set: rows row0 .. row0 + nrows - 1 of the concatenated keypoints / descriptors / flags, nodes node0 .. node0 + nn - 1
+// of the concatenated node ids, its nn + 1 offsets from off0 and its feature indices from idx0 (offsets and indices relative to the
+// keyframe).  One record per pair in a device table that the kernels read with the wave-uniform pair index.
+struct KfSlice { int32_t row0, nrows, node0, nn, off0, idx0; };
+struct TriPair { float epx, epy, F[9]; };           // F unused by the KannalaBrandt8 walk
+struct TriKbPair { int32_t nleft2; float Rt[48]; };
+constexpr int kPairHist = 33;                       // per pair: 32 rotation bins, then nmatches
+
+// A = the block of the single walk with the shared side filled in and, on the set's side, the bases of the concatenated arrays;
+// match_f / match12 / bin_f hold K slices of n_out entries, histo K * kPairHist
+struct BowBatchArgs { BowArgs A; const KfSlice* kf; int K, n_out, max_nn; };
+struct TriBatchArgs { TriArgs T; const KfSlice* kf; const TriPair* pair; int K; };
+struct TriKbBatchArgs { TriKbArgs K; const KfSlice* kf; const TriPair* pair; const TriKbPair* kb; int nk; };
+
 struct RadArgs {
     const eorb_keypoint* kps; int n; const uint8_t* desc; int stride; GridB g;
     const uint16_t* cell;                           // n: ix*48+iy or 0xFFFF (Frame::PosInGrid), from kf_cells_kernel
@@ -124,6 +139,9 @@ int search_proj_map_dev(eorb_ctx* c, const ProjMapArgs& P);
 int search_bow_dev(eorb_ctx* c, const BowArgs& A);
 int search_bow_fisheye_dev(eorb_ctx* c, const BowArgs& A, int nL);
 int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K = nullptr);
+// the same walks over K pairs; scratch (keyframe-to-keyframe form): the vbMatched2 flags, one per row of the set
+int search_bow_batch_dev(eorb_ctx* c, const BowBatchArgs& B, int32_t* scratch, int nscratch);
+int search_tri_batch_dev(eorb_ctx* c, const TriBatchArgs& B, const TriKbBatchArgs* K = nullptr);
 int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const eorb_keypoint* kps1,
                       const eorb_keypoint* kps2, int n, const float* sig1, const float* sig2, float* out);
 int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A);

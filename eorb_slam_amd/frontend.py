@@ -856,6 +856,101 @@ def SearchForTriangulationKB8(kps1, nleft1, desc1, elig1, fv1, kps2, nleft2, des
     return nm.value, np.stack([k, m[k]], axis=1).astype(np.int32)
 
 
+# ---- the node-walk matchers over K keyframes per call (eorb_kf_set and the *_keyframes entry points of include/eorb_fe.h) ----
+class KeyFrameSet:
+    """K keyframes as one eorb_kf_set: keyframes = [(kps, desc, flag, fv), ...], flag = elig2 / kf_has_mp / has_mp2 of the single form,
+    fv = the CSR triple.  Rows and feature vectors are concatenated; .kf_off / .node_off are the ranges per keyframe."""
+
+    def __init__(self, keyframes):
+        K = len(keyframes)
+        self.K = K
+        descs = [np.ascontiguousarray(d, np.uint8) for _, d, _, _ in keyframes]
+        descs = [d.reshape(len(k), -1) if len(k) else np.zeros((0, 32), np.uint8) for (k, _, _, _), d in zip(keyframes, descs)]
+        strides = {d.shape[1] for d in descs if len(d)}
+        assert len(strides) <= 1, "the keyframes of a set share one descriptor stride"
+        self.stride = strides.pop() if strides else 32
+        self.kps = np.concatenate([np.ascontiguousarray(k, KP_DTYPE) for k, _, _, _ in keyframes] + [np.zeros(0, KP_DTYPE)])
+        self.desc = np.ascontiguousarray(np.concatenate([d for d in descs if len(d)] + [np.zeros((0, self.stride), np.uint8)]))
+        self.flag = np.concatenate([np.ascontiguousarray(f, np.uint8) for _, _, f, _ in keyframes] + [np.zeros(0, np.uint8)])
+        fvs = [_fv(fv) for _, _, _, fv in keyframes]
+        self.kf_off = np.cumsum([0] + [len(k) for k, _, _, _ in keyframes]).astype(np.int32)
+        self.node_off = np.cumsum([0] + [len(n) for n, _, _ in fvs]).astype(np.int32)
+        self.nodes = np.concatenate([n for n, _, _ in fvs] + [np.zeros(0, np.uint32)])
+        self.feat_off = np.concatenate([o if len(o) else np.zeros(1, np.int32) for _, o, _ in fvs] + [np.zeros(0, np.int32)])
+        self.idx = np.concatenate([i for _, _, i in fvs] + [np.zeros(0, np.int32)])
+        self.c = _lib.KfSet(K, _p(self.kps), _p(self.desc), int(self.stride), _p(self.flag), _p(self.kf_off), _p(self.nodes), _p(self.node_off),
+                            _p(self.feat_off), _p(self.idx))
+
+
+def _kf_set(kfs):
+    return kfs if isinstance(kfs, KeyFrameSet) else KeyFrameSet(kfs)
+
+
+def SearchForTriangulationKeyFrames(kps1, desc1, elig1, fv1, kfs, ep, F12, scale2, sigma2_2, bCoarse=False, checkOri=False, ctx=None):
+    """SearchForTriangulation(pKF1, pKF2_k, F12_k) over the K neighbours of kfs (a KeyFrameSet or its list; flag = elig2) in one call:
+    LocalMapping::CreateNewMapPoints.  ep (K, 2), F12 (K, 3, 3).  -> (nmatches[K], match12 K x n1); the caller applies the rows in the
+    reference's order and drops a pair whose idx1 got a map point meanwhile (include/eorb_fe.h)."""
+    c = ctx or default_context()
+    S = _kf_set(kfs)
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); desc1 = np.ascontiguousarray(desc1, np.uint8); e1 = np.ascontiguousarray(elig1, np.uint8)
+    n1, o1, i1 = _fv(fv1)
+    ep = np.ascontiguousarray(ep, np.float32).reshape(-1); F = np.ascontiguousarray(F12, np.float32).reshape(-1)
+    assert len(ep) == 2 * S.K and len(F) == 9 * S.K
+    sc = np.ascontiguousarray(scale2, np.float32); sg = np.ascontiguousarray(sigma2_2, np.float32)
+    m = np.full((S.K, len(kps1)), -1, np.int32); nm = np.zeros(S.K, np.int32)
+    c.check(c.L.eorb_search_for_triangulation_keyframes(c.h, _p(kps1), len(kps1), _p(desc1), desc1.shape[1], _p(e1), _p(n1), _p(o1), _p(i1), len(n1),
+                                                        C.byref(S.c), _p(ep), _p(F), _p(sc), _p(sg), len(sc), int(bCoarse), int(checkOri), _p(m), _p(nm)))
+    return nm, m
+
+
+def SearchForTriangulationKB8KeyFrames(kps1, nleft1, desc1, elig1, fv1, kfs, nleft2, cams1, cams2, Rt, ep, scale2, sigma2_1, sigma2_2,
+                                       bCoarse=False, checkOri=False, ctx=None):
+    """The same with a KannalaBrandt8 pCamera1 (SearchForTriangulationKB8 per neighbour): nleft2[K]; Rt (K, 12) for monocular keyframes,
+    (K, 48) for two-camera ones; the cameras and level tables are shared.  -> (nmatches[K], match12 K x n1)."""
+    c = ctx or default_context()
+    S = _kf_set(kfs)
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); desc1 = np.ascontiguousarray(desc1, np.uint8); e1 = np.ascontiguousarray(elig1, np.uint8)
+    n1, o1, i1 = _fv(fv1)
+    nl2 = np.ascontiguousarray(nleft2, np.int32)
+    rt = np.ascontiguousarray(Rt, np.float32).reshape(-1)
+    ep = np.ascontiguousarray(ep, np.float32).reshape(-1)
+    assert len(nl2) == S.K and len(ep) == 2 * S.K and len(rt) == (48 if nleft1 >= 0 else 12) * S.K
+    sc = np.ascontiguousarray(scale2, np.float32)
+    s1 = np.ascontiguousarray(sigma2_1, np.float32); s2 = np.ascontiguousarray(sigma2_2, np.float32)
+    m = np.full((S.K, len(kps1)), -1, np.int32); nm = np.zeros(S.K, np.int32)
+    c1, c2 = _cams(cams1), _cams(cams2)
+    c.check(c.L.eorb_search_for_triangulation_kb8_keyframes(c.h, _p(kps1), len(kps1), int(nleft1), _p(desc1), desc1.shape[1], _p(e1), _p(n1), _p(o1),
+                                                            _p(i1), len(n1), C.byref(S.c), _p(nl2), C.byref(c1), C.byref(c2), _p(rt), _p(ep), _p(sc),
+                                                            _p(s1), _p(s2), len(s2), int(bCoarse), int(checkOri), _p(m), _p(nm)))
+    return nm, m
+
+
+def SearchByBoWKeyFrames(kfs, f_kps, f_desc, f_fv, nnratio=0.7, checkOri=True, ctx=None):
+    """SearchByBoW(pKF_k, F) over the K candidates of kfs (flag = kf_has_mp) against one frame in one call: Tracking::Relocalization.
+    -> (nmatches[K], match_f K x n_f, indices relative to keyframe k)."""
+    c = ctx or default_context()
+    S = _kf_set(kfs)
+    f_kps = np.ascontiguousarray(f_kps, KP_DTYPE); f_desc = np.ascontiguousarray(f_desc, np.uint8)
+    fn, fo, fi = _fv(f_fv)
+    m = np.full((S.K, len(f_kps)), -1, np.int32); nm = np.zeros(S.K, np.int32)
+    c.check(c.L.eorb_search_by_bow_keyframes(c.h, C.byref(S.c), _p(f_kps), len(f_kps), _p(f_desc), _p(fn), _p(fo), _p(fi), len(fn), _p(m),
+                                             float(nnratio), int(checkOri), _p(nm)))
+    return nm, m
+
+
+def SearchByBoW_KF_KeyFrames(kps1, desc1, has_mp1, fv1, kfs, nnratio=0.8, checkOri=True, ctx=None):
+    """SearchByBoW(pKF1, pKF2_k) over the K keyframes of kfs (flag = has_mp2) in one call: LoopClosing::DetectCommonRegionsFromBoW.
+    -> (nmatches[K], match12 K x n1)."""
+    c = ctx or default_context()
+    S = _kf_set(kfs)
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); desc1 = np.ascontiguousarray(desc1, np.uint8); h1 = np.ascontiguousarray(has_mp1, np.uint8)
+    n1, o1, i1 = _fv(fv1)
+    m = np.full((S.K, len(kps1)), -1, np.int32); nm = np.zeros(S.K, np.int32)
+    c.check(c.L.eorb_search_by_bow_kf_keyframes(c.h, _p(kps1), len(kps1), _p(desc1), _p(h1), _p(n1), _p(o1), _p(i1), len(n1), C.byref(S.c), _p(m),
+                                                float(nnratio), int(checkOri), _p(nm)))
+    return nm, m
+
+
 def KB8TriangulateMatches(cam1, cam2, Rt, kps1, kps2, sigma2_1, sigma2_2, ctx=None):
     """KannalaBrandt8::TriangulateMatches (src/CameraModels/KannalaBrandt8.cpp:416-486) for each pair (kps1[i], kps2[i]); Rt = R12 | t12
     (12 floats).  Returns z1 per pair (float32), -1 where the reference returns -1."""

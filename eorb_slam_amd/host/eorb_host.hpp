@@ -724,6 +724,106 @@ public:
         for (size_t i = 0; i < m12.size(); i++) if (m12[i] >= 0) vMatchedPairs.emplace_back(i, (size_t)m12[i]);     // :1203-1211
         return nm;
     }
+    // ---- the same matchers over K keyframes per call (eorb_kf_set and the *_keyframes entry points of include/eorb_fe.h) ----
+    // row k of a K x n1 match table -> vMatchedPairs of keyframe k (:1203-1211)
+    static void PairsPerKeyFrame(const std::vector<int>& m12, int K, size_t n1, std::vector<std::vector<std::pair<size_t, size_t>>>& vv) {
+        vv.assign(K, std::vector<std::pair<size_t, size_t>>());
+        for (int k = 0; k < K; k++)
+            for (size_t i = 0; i < n1; i++) if (m12[k * n1 + i] >= 0) vv[k].emplace_back(i, (size_t)m12[k * n1 + i]);
+    }
+    // one keyframe of the list: its view, the flag byte per feature (elig2 / kfHasMP / hasMP2 of the single overloads) and its FeatureVector
+    struct KeyFrameNodes { const FrameView* KF; const std::vector<uint8_t>* flag; const FeatureVector* FV; };
+    // the list packed into the concatenated arrays an eorb_kf_set points at
+    struct KeyFrameSet {
+        std::vector<eorb_host::KeyPoint> kps; std::vector<uint8_t> desc, flag; std::vector<int32_t> kfOff{0}, nodeOff{0}, featOff, idx;
+        std::vector<uint32_t> nodes; eorb_kf_set set{};
+        explicit KeyFrameSet(const std::vector<KeyFrameNodes>& kfs) {
+            int stride = 32;
+            for (const auto& k : kfs) if (k.KF->numAllKPts() > 0) stride = k.KF->desc->cols;
+            for (const auto& k : kfs) {
+                const int n = k.KF->numAllKPts();
+                if (n > 0 && k.KF->desc->cols != stride) throw eorb_host::Error(EORB_E_ARG, "KeyFrameSet: the keyframes of a set share one descriptor stride");
+                kps.insert(kps.end(), k.KF->kps->begin(), k.KF->kps->end());
+                if (n > 0) desc.insert(desc.end(), k.KF->desc->ptr(), k.KF->desc->ptr() + (size_t)n * stride);
+                flag.insert(flag.end(), k.flag->begin(), k.flag->end());
+                kfOff.push_back((int32_t)kps.size());
+                nodes.insert(nodes.end(), k.FV->nodes.begin(), k.FV->nodes.end());
+                nodeOff.push_back((int32_t)nodes.size());
+                if (k.FV->off.empty()) featOff.push_back(0); else featOff.insert(featOff.end(), k.FV->off.begin(), k.FV->off.end());
+                idx.insert(idx.end(), k.FV->idx.begin(), k.FV->idx.end());
+            }
+            set.K = (int)kfs.size(); set.kps = kps.data(); set.desc = desc.data(); set.stride = stride; set.flag = flag.data();
+            set.kf_off = kfOff.data(); set.nodes = nodes.data(); set.node_off = nodeOff.data(); set.feat_off = featOff.data(); set.idx = idx.data();
+        }
+        KeyFrameSet(const KeyFrameSet&) = delete;
+        KeyFrameSet& operator=(const KeyFrameSet&) = delete;
+    };
+    // SearchForTriangulation(pKF1, pKF2_k, F12_k, ...) over the neighbours of LocalMapping::CreateNewMapPoints (LocalMapping.cc:467-511):
+    // ep[2K], F12[9K]; vvMatchedPairs[k] = the pairs of neighbour k, searched with elig1 as it stands before the loop.  The caller walks k
+    // in the reference's order and drops a pair whose idx1 got a map point from an earlier neighbour (the recipe in include/eorb_fe.h).
+    std::vector<int> SearchForTriangulation(const FrameView& KF1, const std::vector<uint8_t>& elig1, const FeatureVector& FV1,
+                                            const std::vector<KeyFrameNodes>& KFs, const std::vector<float>& ep, const std::vector<float>& F12,
+                                            const std::vector<float>& scale2, const std::vector<float>& sigma2_2,
+                                            std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs, bool bCoarse = false) {
+        auto& c = eorb_host::thread_context();
+        const KeyFrameSet S(KFs);
+        const size_t n1 = (size_t)KF1.numAllKPts();
+        std::vector<int> m12(S.set.K * n1, -1), nm(S.set.K, 0);
+        if (ep.size() != 2 * (size_t)S.set.K || F12.size() != 9 * (size_t)S.set.K) throw eorb_host::Error(EORB_E_ARG, "SearchForTriangulation: ep / F12 per keyframe");
+        c.check(eorb_search_for_triangulation_keyframes(c.get(), KF1.kps->data(), (int)n1, KF1.desc->ptr(), KF1.desc->cols, elig1.data(),
+                                                        FV1.nodes.data(), FV1.off.data(), FV1.idx.data(), (int)FV1.nodes.size(), &S.set, ep.data(),
+                                                        F12.data(), scale2.data(), sigma2_2.data(), (int)scale2.size(), bCoarse,
+                                                        mbCheckOrientation, m12.data(), nm.data()));
+        PairsPerKeyFrame(m12, S.set.K, n1, vvMatchedPairs);
+        return nm;
+    }
+    // the same with a KannalaBrandt8 pCamera1: nLeft2[K]; Rt = 12 floats (monocular) or 48 (two cameras) per neighbour
+    std::vector<int> SearchForTriangulation(const FrameView& KF1, int nLeft1, const std::vector<uint8_t>& elig1, const FeatureVector& FV1,
+                                            const std::vector<KeyFrameNodes>& KFs, const std::vector<int>& nLeft2, const eorb_camera cams1[2],
+                                            const eorb_camera cams2[2], const std::vector<float>& Rt, const std::vector<float>& ep,
+                                            const std::vector<float>& scale2, const std::vector<float>& sigma2_1, const std::vector<float>& sigma2_2,
+                                            std::vector<std::vector<std::pair<size_t, size_t>>>& vvMatchedPairs, bool bCoarse = false) {
+        auto& c = eorb_host::thread_context();
+        const KeyFrameSet S(KFs);
+        const size_t n1 = (size_t)KF1.numAllKPts(), K = (size_t)S.set.K;
+        std::vector<int> m12(K * n1, -1), nm(K, 0);
+        if (nLeft2.size() != K || ep.size() != 2 * K || Rt.size() != (nLeft1 >= 0 ? 48 : 12) * K)
+            throw eorb_host::Error(EORB_E_ARG, "SearchForTriangulation: nLeft2 / ep / Rt per keyframe");
+        c.check(eorb_search_for_triangulation_kb8_keyframes(c.get(), KF1.kps->data(), (int)n1, nLeft1, KF1.desc->ptr(), KF1.desc->cols, elig1.data(),
+                                                            FV1.nodes.data(), FV1.off.data(), FV1.idx.data(), (int)FV1.nodes.size(), &S.set,
+                                                            nLeft2.data(), cams1, cams2, Rt.data(), ep.data(), scale2.data(), sigma2_1.data(),
+                                                            sigma2_2.data(), (int)sigma2_2.size(), bCoarse, mbCheckOrientation, m12.data(), nm.data()));
+        PairsPerKeyFrame(m12, S.set.K, n1, vvMatchedPairs);
+        return nm;
+    }
+    // SearchByBoW(pKF_k, F, vvpMapPointMatches[k]) over the candidates of Tracking::Relocalization (Tracking.cc:2674-2689):
+    // vvMatchF[k][j] = feature of keyframe k whose map point goes to F's j, or -1
+    std::vector<int> SearchByBoW(const std::vector<KeyFrameNodes>& KFs, const FrameView& F, const FeatureVector& fFV,
+                                 std::vector<std::vector<int>>& vvMatchF) {
+        auto& c = eorb_host::thread_context();
+        const KeyFrameSet S(KFs);
+        const size_t n = (size_t)F.numAllKPts();
+        std::vector<int> m(S.set.K * n, -1), nm(S.set.K, 0);
+        c.check(eorb_search_by_bow_keyframes(c.get(), &S.set, F.kps->data(), (int)n, F.desc->ptr(), fFV.nodes.data(), fFV.off.data(), fFV.idx.data(),
+                                             (int)fFV.nodes.size(), m.data(), mfNNratio, mbCheckOrientation, nm.data()));
+        vvMatchF.assign(S.set.K, std::vector<int>());
+        for (int k = 0; k < S.set.K; k++) vvMatchF[k].assign(m.begin() + k * n, m.begin() + (k + 1) * n);
+        return nm;
+    }
+    // SearchByBoW(pKF1, pKF2_k, vvpMatchedMPs[k]) over a candidate and its covisibles (LoopClosing.cc:628-648): vvMatches12[k][i] = index in
+    // keyframe k, or -1
+    std::vector<int> SearchByBoW(const FrameView& KF1, const std::vector<uint8_t>& hasMP1, const FeatureVector& FV1,
+                                 const std::vector<KeyFrameNodes>& KFs, std::vector<std::vector<int>>& vvMatches12) {
+        auto& c = eorb_host::thread_context();
+        const KeyFrameSet S(KFs);
+        const size_t n = (size_t)KF1.numAllKPts();
+        std::vector<int> m(S.set.K * n, -1), nm(S.set.K, 0);
+        c.check(eorb_search_by_bow_kf_keyframes(c.get(), KF1.kps->data(), (int)n, KF1.desc->ptr(), hasMP1.data(), FV1.nodes.data(), FV1.off.data(),
+                                                FV1.idx.data(), (int)FV1.nodes.size(), &S.set, m.data(), mfNNratio, mbCheckOrientation, nm.data()));
+        vvMatches12.assign(S.set.K, std::vector<int>());
+        for (int k = 0; k < S.set.K; k++) vvMatches12[k].assign(m.begin() + k * n, m.begin() + (k + 1) * n);
+        return nm;
+    }
     // Fuse(pKF, vpMapPoints, th, bRight = true) (:1407-1578) on a two-camera KeyFrame: the search core over the right block.
     // KFRight = the right keypoints and descriptors (desc + Nleft * stride) with the right grid's bounds; uv / radius / level from
     // the map points projected by mpCamera2 (:1463-1513).  The returned indices are right-camera indices plus nLeft (:1567).

@@ -326,6 +326,66 @@ def project_np(c, P):
     return np.stack([c[0] * r * np.cos(psi) + c[2], c[1] * r * np.sin(psi) + c[3]], axis=1)
 
 
+def _scene(rng, npts, nnodes):
+    """3D points in front of the first camera with a descriptor, a vocabulary node and an orientation each"""
+    z = rng.uniform(1.5, 9.0, npts)
+    X = np.stack([rng.uniform(-1.1, 1.1, npts) * z, rng.uniform(-0.9, 0.9, npts) * z, z], axis=1)
+    base = rng.integers(0, 256, (npts, 32), dtype=np.uint8)
+    node = rng.integers(0, nnodes, npts) * 7 + 3
+    ang = rng.uniform(0, 360, npts)
+    return X, base, node, ang
+
+
+def _observe(rng, scene, poses, cams, W, H, ndistract, nties, stride, second, angle_offset=0.0):
+    """One keyframe's view of a scene: per camera (poses[cidx] = (R, t), cams[cidx]) the visible points with near-duplicate
+    descriptors and distractors, shuffled; then elig, nodes and the feature vector.  second: the keyframe searched in (pKF2) -- nties
+    exact-descriptor ties and noise on the orientations.  Two cameras: bit 1 of elig stays clear."""
+    X, base, node, ang = scene
+    npts, ncam, twocam = len(X), len(poses), len(poses) == 2
+    blocks = []
+    for cidx in range(ncam):
+        R, t = poses[cidx]
+        Pc = X @ R.T.astype(np.float64) + t
+        uv = project_np(cams[cidx], Pc)
+        vis = (Pc[:, 2] > 0.2) & (uv[:, 0] >= 0) & (uv[:, 0] < W) & (uv[:, 1] >= 0) & (uv[:, 1] < H)
+        vis &= rng.uniform(size=npts) < 0.9
+        pid = np.nonzero(vis)[0]
+        rows = []
+        for p in pid:
+            rows.append((uv[p, 0] + rng.normal(0, 0.4), uv[p, 1] + rng.normal(0, 0.4), p, flip_bits(base[p], rng.integers(0, 11), rng)))
+        for _ in range(ndistract // ncam):
+            p = rng.integers(npts)
+            rows.append((rng.uniform(0, W), rng.uniform(0, H), p, flip_bits(base[p], rng.integers(12, 31), rng)))
+        if second:
+            for j in rng.choice(len(pid), min(nties // ncam, len(pid)), replace=False):
+                x, y, p, d = rows[j]
+                rows.append((x + rng.uniform(-1.5, 1.5), y + rng.uniform(-1.5, 1.5), p, d.copy()))
+        order = rng.permutation(len(rows))
+        blocks.append([rows[i] for i in order])
+    allrows = [r for b in blocks for r in b]
+    n = len(allrows)
+    kps = np.zeros(n, KP_DTYPE)
+    kps["x"] = np.array([r[0] for r in allrows], np.float32); kps["y"] = np.array([r[1] for r in allrows], np.float32)
+    kps["octave"] = rng.integers(0, 4, n); kps["size"] = 31.0; kps["class_id"] = -1
+    pids = np.array([r[2] for r in allrows], np.int64)
+    a = ang[pids] + (rng.normal(0, 4, n) if second else 0) + np.where(rng.uniform(size=n) < 0.1, rng.uniform(0, 360, n), 0)
+    kps["angle"] = np.mod(a + angle_offset, 360).astype(np.float32)
+    desc = np.zeros((n, stride), np.uint8)
+    if n:
+        desc[:, :32] = np.stack([r[3] for r in allrows])
+    if stride > 32:
+        desc[:, 32:] = rng.integers(0, 256, (n, stride - 32), dtype=np.uint8)
+    elig = (rng.uniform(size=n) < 0.85).astype(np.uint8)
+    if stride > 32:
+        elig[rng.uniform(size=n) < 0.15] = 0                         # non-ORB rows of a Mixed keyframe
+    if not twocam:
+        elig |= ((rng.uniform(size=n) < 0.1) << 1).astype(np.uint8) & (elig << 1)
+    nodes = node[pids].copy()
+    nodes[rng.uniform(size=n) < 0.05] = 1                              # a node the other keyframe may lack
+    fv = feature_vector_of(nodes, rng)
+    return dict(kps=kps, nleft=len(blocks[0]) if twocam else -1, desc=desc, elig=elig, fv=fv)
+
+
 def keyframe_pair(seed=0, twocam=False, npts=600, ndistract=150, nties=30, stride=32, nnodes=60, size=None, ep_near=True):
     """A keyframe pair seeing one 3D scene.  Returns a dict of the matcher's inputs (kps / nleft / desc / elig / fv per keyframe,
     cams, Rt, ep, scale2, sigma2).  True observations carry near-duplicate descriptors (<= 10 flipped bits); distractors copy a
@@ -347,55 +407,9 @@ def keyframe_pair(seed=0, twocam=False, npts=600, ndistract=150, nties=30, strid
     if twocam:
         poses[(0, 1)] = ((Rrl.astype(np.float64) @ R1).astype(np.float32), (Rrl.astype(np.float64) @ t1 + trl).astype(np.float32))
         poses[(1, 1)] = ((Rrl.astype(np.float64) @ R2).astype(np.float32), (Rrl.astype(np.float64) @ t2 + trl).astype(np.float32))
-    z = rng.uniform(1.5, 9.0, npts)
-    X = np.stack([rng.uniform(-1.1, 1.1, npts) * z, rng.uniform(-0.9, 0.9, npts) * z, z], axis=1)
-    base = rng.integers(0, 256, (npts, 32), dtype=np.uint8)
-    node = rng.integers(0, nnodes, npts) * 7 + 3
-    ang = rng.uniform(0, 360, npts)
-    ncam = 2 if twocam else 1
-    kf = []
-    for k in range(2):
-        blocks = []
-        for cidx in range(ncam):
-            R, t = poses[(k, cidx)]
-            Pc = X @ R.T.astype(np.float64) + t
-            uv = project_np(cams[cidx], Pc)
-            vis = (Pc[:, 2] > 0.2) & (uv[:, 0] >= 0) & (uv[:, 0] < W) & (uv[:, 1] >= 0) & (uv[:, 1] < H)
-            vis &= rng.uniform(size=npts) < 0.9
-            pid = np.nonzero(vis)[0]
-            rows = []
-            for p in pid:
-                rows.append((uv[p, 0] + rng.normal(0, 0.4), uv[p, 1] + rng.normal(0, 0.4), p, flip_bits(base[p], rng.integers(0, 11), rng)))
-            for _ in range(ndistract // ncam):
-                p = rng.integers(npts)
-                rows.append((rng.uniform(0, W), rng.uniform(0, H), p, flip_bits(base[p], rng.integers(12, 31), rng)))
-            if k == 1:
-                for j in rng.choice(len(pid), min(nties // ncam, len(pid)), replace=False):
-                    x, y, p, d = rows[j]
-                    rows.append((x + rng.uniform(-1.5, 1.5), y + rng.uniform(-1.5, 1.5), p, d.copy()))
-            order = rng.permutation(len(rows))
-            blocks.append([rows[i] for i in order])
-        allrows = [r for b in blocks for r in b]
-        n = len(allrows)
-        kps = np.zeros(n, KP_DTYPE)
-        kps["x"] = np.array([r[0] for r in allrows], np.float32); kps["y"] = np.array([r[1] for r in allrows], np.float32)
-        kps["octave"] = rng.integers(0, 4, n); kps["size"] = 31.0; kps["class_id"] = -1
-        pids = np.array([r[2] for r in allrows])
-        a = ang[pids] + (rng.normal(0, 4, n) if k else 0) + np.where(rng.uniform(size=n) < 0.1, rng.uniform(0, 360, n), 0)
-        kps["angle"] = np.mod(a, 360).astype(np.float32)
-        desc = np.zeros((n, stride), np.uint8)
-        desc[:, :32] = np.stack([r[3] for r in allrows])
-        if stride > 32:
-            desc[:, 32:] = rng.integers(0, 256, (n, stride - 32), dtype=np.uint8)
-        elig = (rng.uniform(size=n) < 0.85).astype(np.uint8)
-        if stride > 32:
-            elig[rng.uniform(size=n) < 0.15] = 0                         # non-ORB rows of a Mixed keyframe
-        if not twocam:
-            elig |= ((rng.uniform(size=n) < 0.1) << 1).astype(np.uint8) & (elig << 1)
-        nodes = node[pids].copy()
-        nodes[rng.uniform(size=n) < 0.05] = 1                              # a node the other keyframe may lack
-        fv = feature_vector_of(nodes, rng)
-        kf.append(dict(kps=kps, nleft=len(blocks[0]) if twocam else -1, desc=desc, elig=elig, fv=fv))
+    scene = _scene(rng, npts, nnodes)
+    kf = [_observe(rng, scene, [poses[(k, cidx)] for cidx in range(2 if twocam else 1)], cams, W, H, ndistract, nties, stride,
+                   second=bool(k)) for k in range(2)]
     if twocam:
         Rt = np.concatenate([rel_pose(*poses[(0, a)], *poses[(1, b)]) for a, b in ((0, 0), (0, 1), (1, 0), (1, 1))])
     else:
@@ -406,6 +420,100 @@ def keyframe_pair(seed=0, twocam=False, npts=600, ndistract=150, nties=30, strid
     return dict(kps1=kf[0]["kps"], nleft1=kf[0]["nleft"], desc1=kf[0]["desc"], elig1=kf[0]["elig"], fv1=kf[0]["fv"],
                 kps2=kf[1]["kps"], nleft2=kf[1]["nleft"], desc2=kf[1]["desc"], elig2=kf[1]["elig"], fv2=kf[1]["fv"],
                 cams1=camsp, cams2=camsp, Rt=Rt, ep=np.array(ep, np.float32), scale2=scale, sigma2_1=sigma2, sigma2_2=sigma2)
+
+
+def cap_nodes(fv, caps, x):
+    """fv with node a cut to its caps[a] leftmost features by x (None or missing: all), vector order kept; the rest appear in no node,
+    which is legal input"""
+    nodes, off, idx = fv
+    keep = []
+    for a in range(len(nodes)):
+        m = idx[off[a]:off[a + 1]]
+        cap = caps[a] if a < len(caps) else None
+        keep.append(m if cap is None else m[np.sort(np.argsort(x[m], kind="stable")[:cap])])
+    return nodes, np.cumsum([0] + [len(k) for k in keep]).astype(np.int32), np.concatenate(keep + [np.zeros(0, np.int32)]).astype(np.int32)
+
+
+def _skew(t):
+    return np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]], np.float64)
+
+
+def neighbour_pose(k):
+    """pose k of a neighbourhood: a few degrees of rotation and a baseline that differ for every k (five patterns, nudged every fifth
+    keyframe), part of the baseline along the optical axis so that the epipole of a Pinhole pair lies in or near the image"""
+    a, b = k % 5, k // 5
+    R = rot(0.03 - 0.011 * a + 0.004 * b, -0.08 + 0.027 * a - 0.006 * b, 0.02 * (1 - a) + 0.003 * b)
+    t = np.array([-0.35 + 0.16 * a + 0.03 * b, 0.04 - 0.03 * a + 0.01 * b, 0.06 + 0.09 * (a % 3) + 0.02 * b], np.float32)
+    return R, t
+
+
+def triangulation_neighbourhood(seed, K, twocam=False, pinhole=False, npts=250, ndistract=60, nties=12, stride=32, nnodes=10, size=None,
+                                angle_step=50.0):
+    """One current keyframe (pKF1) and K neighbours at different poses over one scene, built like keyframe_pair: the inputs of
+    LocalMapping::CreateNewMapPoints' SearchForTriangulation loop.  Returns pKF1's arrays (kps1, nleft1, desc1, elig1, fv1), the list
+    kfs of neighbours (dicts kps, nleft, desc, elig, fv), cams1 / cams2, the level tables and per neighbour Rt[k] (12 or 48 floats) and
+    ep[k].  pinhole: both cameras are the Pinhole part of CAM_MONO, ep[k] = the true epipole project(R2w * Cw + t2w) and F12[k] =
+    K1^-T [t12]x R12 K2^-1 in float.  Otherwise KannalaBrandt8 as in keyframe_pair, ep[k] near a keypoint of the neighbour.  The
+    neighbours' orientations are offset by k * angle_step degrees, so every pair keeps other bins of the rotation histogram."""
+    assert not (twocam and pinhole)
+    rng = np.random.default_rng(seed)
+    scale, sigma2 = level_tables()
+    if twocam:
+        W = H = 512 if size is None else size
+        cams = (CAM_L, CAM_R)
+        Rrl, trl = rot(0.002, -0.01, 0.003), np.array([-0.11, 0.001, 0.002], np.float32)
+    else:
+        W, H = (346, 260) if size is None else size
+        cams = (CAM_MONO[:4],) if pinhole else (CAM_MONO,)
+
+    def rig(R, t):
+        if not twocam:
+            return [(R, t)]
+        return [(R, t), ((Rrl.astype(np.float64) @ R).astype(np.float32), (Rrl.astype(np.float64) @ t + trl).astype(np.float32))]
+
+    R1, t1 = np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
+    scene = _scene(rng, npts, nnodes)
+    kf1 = _observe(rng, scene, rig(R1, t1), cams, W, H, ndistract, nties, stride, second=False)
+    kfs, Rts, eps, Fs = [], [], [], []
+    for k in range(K):
+        R2, t2 = neighbour_pose(k)
+        kf = _observe(rng, scene, rig(R2, t2), cams, W, H, ndistract, nties, stride, second=True, angle_offset=angle_step * k)
+        kfs.append(kf)
+        if twocam:
+            Rts.append(np.concatenate([rel_pose(*rig(R1, t1)[a], *rig(R2, t2)[b]) for a, b in ((0, 0), (0, 1), (1, 0), (1, 1))]))
+        else:
+            Rts.append(rel_pose(R1, t1, R2, t2))
+        if pinhole:
+            fx, fy, cx, cy = cams[0]
+            Kinv = np.linalg.inv(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float64))
+            R12 = Rts[-1][:9].reshape(3, 3).astype(np.float64); t12 = Rts[-1][9:].astype(np.float64)
+            Fs.append((Kinv.T @ _skew(t12) @ R12 @ Kinv).astype(np.float32))
+            C2 = R2.astype(np.float64) @ (-(R1.T.astype(np.float64) @ t1)) + t2           # pKF1's centre in camera 2
+            eps.append(project_np(cams[0], C2[None])[0].astype(np.float32))
+        else:
+            k2 = kf["kps"]
+            eps.append(np.array((k2["x"][0] + 4.0, k2["y"][0]) if len(k2) else (-1000.0, -1000.0), np.float32))
+    camsp = cams if twocam else cams[0]
+    out = dict(kps1=kf1["kps"], nleft1=kf1["nleft"], desc1=kf1["desc"], elig1=kf1["elig"], fv1=kf1["fv"], kfs=kfs, cams1=camsp, cams2=camsp,
+               Rt=np.stack(Rts).astype(np.float32) if K else np.zeros((0, 12), np.float32),
+               ep=np.stack(eps).astype(np.float32) if K else np.zeros((0, 2), np.float32), scale2=scale, sigma2_1=sigma2, sigma2_2=sigma2)
+    if pinhole:
+        out["F12"] = np.stack(Fs) if K else np.zeros((0, 3, 3), np.float32)
+    return out
+
+
+def bow_neighbourhood(seed, K, npts=250, ndistract=60, nties=12, nnodes=10, caps=None, p_mp=0.8, angle_step=50.0):
+    """One frame (or current keyframe) and K keyframes over one scene for the SearchByBoW loops of Tracking::Relocalization and
+    LoopClosing::DetectCommonRegionsFromBoW: a point's observations share its vocabulary node, so matching features mostly share a
+    node.  caps[k] (optional) = per-node caps of keyframe k's feature vector (cap_nodes by image x: a keyframe's nodes can sit on
+    either side of a kernel's per-node limit).  Returns the frame's kps / desc / fv / has_mp and kfs (dicts kps, desc, fv, has_mp)."""
+    s = triangulation_neighbourhood(seed, K, npts=npts, ndistract=ndistract, nties=nties, nnodes=nnodes, angle_step=angle_step)
+    rng = np.random.default_rng(seed + 7919)
+    kfs = []
+    for k, kf in enumerate(s["kfs"]):
+        fv = kf["fv"] if not caps or caps[k] is None else cap_nodes(kf["fv"], caps[k], kf["kps"]["x"])
+        kfs.append(dict(kps=kf["kps"], desc=kf["desc"], fv=fv, has_mp=(rng.uniform(size=len(kf["kps"])) < p_mp).astype(np.uint8)))
+    return dict(kps=s["kps1"], desc=s["desc1"], fv=s["fv1"], has_mp=(rng.uniform(size=len(s["kps1"])) < p_mp).astype(np.uint8), kfs=kfs)
 
 
 # ---- camera calibrations (eorb_calib of include/eorb_fe.h): model 0 = Pinhole / cv::undistortPoints, 1 = KannalaBrandt8 /

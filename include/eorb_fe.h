@@ -755,6 +755,85 @@ int eorb_fuse_keyframes_mixed(eorb_ctx* ctx, const eorb_view* views, const eorb_
                               int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* mp_is_orb,
                               const uint8_t* q_desc, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reason);
 
+/* ---- the node-walk matchers over K keyframes per call ----------------------------------------------------------------------------------
+ * Three loops of the reference call a node-walk matcher once per keyframe of a list: LocalMapping::CreateNewMapPoints
+ * (src/LocalMapping.cc:467-511; the same loop at src/Tracking.cc:3212-3215) runs SearchForTriangulation(mpCurrentKeyFrame, pKF2_k, ...)
+ * over the neighbours, Tracking::Relocalization (src/Tracking.cc:2674-2689) SearchByBoW(pKF_k, CurrentFrame, ...) over the candidates,
+ * LoopClosing::DetectCommonRegionsFromBoW (src/LoopClosing.cc:628-648) SearchByBoW(mpCurrentKF, vpCovKFi[j], ...) over a candidate and
+ * its covisibles.  The four entry points below take the K keyframes of such a loop in one eorb_kf_set and return K rows; row k is what
+ * the single entry point returns for pair k, bit for bit.  One upload (the shared side once), one wait, one download; three kernel
+ * launches for any K.
+ *
+ * eorb_kf_set: keypoints, descriptors (one stride >= 32) and the flag byte of all keyframes concatenated, keyframe k = rows
+ * kf_off[k] .. kf_off[k+1]-1 (the convention of eorb_fuse_keyframes and eorb_distinctive_descriptors).  flag = what the single form
+ * takes per feature of that side: elig2 (SearchForTriangulation), kf_has_mp (eorb_search_by_bow), has_mp2 (eorb_search_by_bow_kf).
+ * The K DBoW2 feature vectors are concatenated the same way: keyframe k owns node ids nodes[node_off[k] .. node_off[k+1]-1]
+ * (ascending within the keyframe); its nn_k + 1 per-node offsets are feat_off[node_off[k] + k ..] (the first is 0, relative to the
+ * keyframe), so feat_off holds node_off[K] + K entries; its feature indices (relative to the keyframe's first row) follow those of
+ * keyframe k-1 in idx.  A keyframe with no rows or no nodes is legal: its row is all -1 and its count 0, the others are unaffected.
+ * Every check of the single forms is made per keyframe and the message names k.  Limits, decided from the sizes before any array is
+ * read: K <= 1024, K * n (n = the length of one output row) <= 2^22, then 2^22 rows in all; beyond them EORB_E_CAPACITY.  kf_off /
+ * node_off that do not start at 0 or decrease: EORB_E_ARG. */
+typedef struct eorb_kf_set {
+    int K;
+    const eorb_keypoint* kps; const uint8_t* desc; int stride; const uint8_t* flag; const int32_t* kf_off;
+    const uint32_t* nodes; const int32_t* node_off; const int32_t* feat_off; const int32_t* idx;
+} eorb_kf_set;
+
+/* SearchForTriangulation(pKF1, pKF2_k, F12_k, ...) for the K neighbours in `set` (flag = elig2): pKF1 as in
+ * eorb_search_for_triangulation; ep[2K] and F12[9K] per neighbour; one scale2 / sigma2_2[nlevels] table serves all keyframes (they
+ * share one pyramid, as in eorb_fuse_keyframes); bCoarse and checkOri are shared.  match12[K*n1], nmatches[K] (optional).
+ *
+ * Why the batch is exact, and the caller's recipe for CreateNewMapPoints.  The reference never writes vbMatched2, so the result for a
+ * pKF1 feature depends on that feature, pKF2_k and F12_k only; what changes between neighbours is which pKF1 features are eligible:
+ * AddMapPoint(pMP, idx1) (src/LocalMapping.cc:775) takes idx1 out of the later neighbours' searches, pKF2->AddMapPoint (:776) touches
+ * only that neighbour.  So the caller batches the neighbours that pass the baseline tests (:477-494), computes each F12_k, passes
+ * elig1 as it stands before the loop, and applies the rows in the reference's order:
+ *     eorb_search_for_triangulation_keyframes(..., match12, NULL);
+ *     for k in the reference's neighbour order:
+ *         for idx1 with match12[k*n1 + idx1] >= 0:
+ *             if (mpCurrentKeyFrame->GetMapPoint(idx1)) continue;        // set by an earlier neighbour of this pass
+ *             triangulate (idx1, match12[k*n1 + idx1]) as at :530-780
+ * This reproduces the sequential loop exactly while checkOri is false, and both callers construct the matcher that way
+ * (src/LocalMapping.cc:443, src/Tracking.cc:3152).  With checkOri set a row equals the single call with the same elig1, which is not
+ * the reference's sequence once elig1 has changed: the rotation histogram of a later neighbour would have been built without the
+ * features taken meanwhile.  The reference may leave the loop early (CheckNewKeyFrames(), :469); the batch has then computed the
+ * remaining rows for nothing.  tests/test_kfbatch_recipe.py runs this recipe against the sequential loop on a model map. */
+int eorb_search_for_triangulation_keyframes(eorb_ctx* ctx,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches);
+
+/* the same with the KannalaBrandt8 test of eorb_search_for_triangulation_kb8: Rt[12K] (monocular keyframes) or Rt[48K] (two-camera
+ * keyframes: ll, lr, rl, rr per neighbour); cam1[2] / cam2[2] and the level tables are shared; nleft1 once, nleft2[K] per neighbour,
+ * all -1 or all >= 0 like nleft1 (EORB_E_CONFIG otherwise, as every EORB_E_CONFIG rule of the single form).  A Pinhole pCamera2 is
+ * allowed.  The recipe above applies word for word. */
+int eorb_search_for_triangulation_kb8_keyframes(eorb_ctx* ctx,
+        const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, const int32_t* nleft2,
+        const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
+        const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches);
+
+/* SearchByBoW(pKF_k, F, vvpMapPointMatches[k]) for the K candidates in `set` (the pKF side; flag = kf_has_mp) against one frame
+ * (f_desc n_f x 32): Tracking::Relocalization.  match_f[K*n_f] = KeyFrame feature index relative to keyframe k, or -1; nmatches[K]
+ * (optional).  Exact without a recipe: each k writes a fresh vector and the K searches share no state.  isBad() keyframes are left
+ * out by the caller (:2677).  The first 32 bytes of each descriptor row of the set are read. */
+int eorb_search_by_bow_keyframes(eorb_ctx* ctx, const eorb_kf_set* set,
+        const eorb_keypoint* f_kps, int n_f, const uint8_t* f_desc,
+        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
+        int32_t* match_f, float nnratio, int checkOri, int32_t* nmatches);
+
+/* SearchByBoW(pKF1, pKF2_k, vvpMatchedMPs[k]) for the K keyframes in `set` (side 2; flag = has_mp2, required) against one keyframe
+ * (side 1, desc1 n1 x 32): LoopClosing::DetectCommonRegionsFromBoW.  match12[K*n1] = index in keyframe k, or -1; nmatches[K]
+ * (optional).  Exact without a recipe, as above; isBad() keyframes are left out by the caller. */
+int eorb_search_by_bow_kf_keyframes(eorb_ctx* ctx,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, const uint8_t* has_mp1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, int32_t* match12, float nnratio, int checkOri, int32_t* nmatches);
+
 /* replaces MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423; f3), batched over M map points: the
  * descriptors observed for map point m are rows offsets[m] .. offsets[m+1]-1 of desc (n x 32); best[m] = the row (relative
  * to offsets[m]) with the least median Hamming distance to the others, -1 when there is none. */
