@@ -2023,114 +2023,6 @@ int eorb_search_by_projection_kf_pose(eorb_ctx* c,
                             nullptr, valid, uv, level, nmatches);
 }
 
-// The two feature vectors of a node walk (SearchByBoW, SearchForTriangulation) as the caller holds them.  queue() checks every
-// index against its side's feature count and lays [nodes | off | idx] of both sides out as one input of the arena; after
-// A.upload(), dev(A, side) is that side with device pointers.
-struct HostFv { const uint32_t* nodes; const int32_t* off; const int32_t* idx; int nn, n_features; const char* name; };
-struct FvPair {
-    std::vector<int32_t> blk; size_t o_blk = 0, base[2] = {0, 0}; int nn[2] = {0, 0};
-    int queue(eorb_ctx* c, Arena& A, const char* what, const HostFv& s0, const HostFv& s1)
-    {
-        const HostFv* side[2] = {&s0, &s1};
-        for (int k = 0; k < 2; k++) {
-            const HostFv& s = *side[k];
-            const int ni = s.off[s.nn];
-            for (int i = 0; i < ni; i++) if (s.idx[i] < 0 || s.idx[i] >= s.n_features) return set_err(c, EORB_E_ARG, "%s: %s index out of range", what, s.name);
-            base[k] = blk.size(); nn[k] = s.nn;
-            blk.insert(blk.end(), (const int32_t*)s.nodes, (const int32_t*)s.nodes + s.nn);
-            blk.insert(blk.end(), s.off, s.off + s.nn + 1);
-            blk.insert(blk.end(), s.idx, s.idx + ni);
-        }
-        o_blk = A.in(blk.data(), sizeof(int32_t) * blk.size());
-        return EORB_OK;
-    }
-    FeatVec dev(const Arena& A, int k) const
-    {
-        const int32_t* B = A.dev<int32_t>(o_blk) + base[k];
-        return FeatVec{(const uint32_t*)B, B + nn[k], B + nn[k] + nn[k] + 1, nn[k]};
-    }
-};
-
-static int bow_common(eorb_ctx* c, int kf_kf,
-        const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
-        const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
-        const eorb_keypoint* f_kps, int n_f, const uint8_t* f_desc, const uint8_t* f_has_mp,
-        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
-        int32_t* match_out, float nnratio, int checkOri, int* nmatches, int fisheye_nL = -1)
-{
-    if (!c) return EORB_E_ARG;
-    if (n_kf < 0 || n_f < 0 || kf_nn < 0 || f_nn < 0 || !match_out) return set_err(c, EORB_E_ARG, "search_by_bow: bad arguments");
-    if (fisheye_nL > n_f) return set_err(c, EORB_E_ARG, "search_by_bow_fisheye: nL %d > %d frame features", fisheye_nL, n_f);
-    fe_enter(c);
-    if (nmatches) *nmatches = 0;
-    const int nout = kf_kf ? n_kf : n_f;
-    for (int i = 0; i < nout; i++) match_out[i] = -1;
-    if (n_kf == 0 || n_f == 0 || kf_nn == 0 || f_nn == 0) return EORB_OK;
-    int rc;
-    Arena A(c);
-    FvPair fv;
-    if ((rc = fv.queue(c, A, "search_by_bow", {kf_nodes, kf_node_off, kf_idx, kf_nn, n_kf, "KeyFrame"}, {f_nodes, f_node_off, f_idx, f_nn, n_f, "frame"})))
-        return rc;
-    const size_t o_kk = A.in(kf_kps, sizeof(eorb_keypoint) * n_kf), o_kd = A.in(kf_desc, 32 * (size_t)n_kf);
-    const size_t o_fk = A.in(f_kps, sizeof(eorb_keypoint) * n_f), o_fd = A.in(f_desc, 32 * (size_t)n_f);
-    std::vector<uint8_t> flags((size_t)n_kf + n_f, 1);
-    memcpy(flags.data(), kf_has_mp, n_kf);
-    if (f_has_mp) memcpy(flags.data() + n_kf, f_has_mp, n_f);
-    const size_t o_fl = A.in(flags.data(), flags.size());
-    // outputs, contiguous: histogram (nmatches at [32]) | frame matches | KeyFrame matches; then the rotation bins
-    const size_t o_hist = A.reserve(sizeof(int32_t) * 40), o_mf = A.reserve(sizeof(int32_t) * n_f), o_m12 = A.reserve(sizeof(int32_t) * n_kf);
-    const size_t o_bin = A.reserve((size_t)std::max(n_f, n_kf));
-    if ((rc = A.upload())) return rc;
-    int32_t* hist = A.dev<int32_t>(o_hist);
-    const uint8_t* fl = A.dev<uint8_t>(o_fl);
-    const BowArgs B{A.dev<eorb_keypoint>(o_kk), A.dev<uint8_t>(o_kd), fl, fv.dev(A, 0),
-                    A.dev<eorb_keypoint>(o_fk), n_f, A.dev<uint8_t>(o_fd), fv.dev(A, 1),
-                    A.dev<int32_t>(o_mf), A.dev<int8_t>(o_bin), hist, hist + 32, nnratio, checkOri, kf_kf,
-                    fl + n_kf, A.dev<int32_t>(o_m12), n_kf};
-    if ((rc = fisheye_nL >= 0 ? search_bow_fisheye_dev(c, B, fisheye_nL) : search_bow_dev(c, B))) return rc;
-    const size_t o_out = kf_kf ? o_m12 : o_mf;
-    const char* h;
-    if ((rc = A.download(o_hist, o_out + sizeof(int32_t) * nout - o_hist, &h))) return rc;
-    memcpy(match_out, h + o_out, sizeof(int32_t) * nout);
-    if (nmatches) memcpy(nmatches, h + o_hist + sizeof(int32_t) * 32, 4);
-    return EORB_OK;
-}
-
-int eorb_search_by_bow(eorb_ctx* c,
-        const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
-        const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
-        const eorb_keypoint* f_kps, int n_f, const uint8_t* f_desc,
-        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
-        int32_t* match_f, float nnratio, int checkOri, int* nmatches)
-{
-    return bow_common(c, 0, kf_kps, n_kf, kf_desc, kf_has_mp, kf_nodes, kf_node_off, kf_idx, kf_nn, f_kps, n_f, f_desc, nullptr,
-                      f_nodes, f_node_off, f_idx, f_nn, match_f, nnratio, checkOri, nmatches);
-}
-
-int eorb_search_by_bow_kf(eorb_ctx* c,
-        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, const uint8_t* has_mp1,
-        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
-        const eorb_keypoint* kps2, int n2, const uint8_t* desc2, const uint8_t* has_mp2,
-        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
-        int32_t* match12, float nnratio, int checkOri, int* nmatches)
-{
-    if (c && !has_mp2 && n2 > 0) return set_err(c, EORB_E_ARG, "search_by_bow_kf: has_mp2 is required");
-    return bow_common(c, 1, kps1, n1, desc1, has_mp1, nodes1, node_off1, idx1, nn1, kps2, n2, desc2, has_mp2,
-                      nodes2, node_off2, idx2, nn2, match12, nnratio, checkOri, nmatches);
-}
-
-int eorb_search_by_bow_fisheye(eorb_ctx* c,
-        const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
-        const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
-        const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc,
-        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
-        int32_t* match_f, float nnratio, int checkOri, int* nmatches)
-{
-    if (c && nL < 0) return set_err(c, EORB_E_ARG, "search_by_bow_fisheye: nL %d", nL);
-    return bow_common(c, 0, kf_kps, n_kf, kf_desc, kf_has_mp, kf_nodes, kf_node_off, kf_idx, kf_nn, f_kps, n_f, f_desc, nullptr,
-                      f_nodes, f_node_off, f_idx, f_nn, match_f, nnratio, checkOri, nmatches, nL);
-}
-
 // ---- two-camera frames: the frame seam and the tracking matchers ------------------------------------------------------------
 int eorb_frame_fisheye(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRight, int W, int H, int stride,
                        int lapL0, int lapL1, int lapR0, int lapR1,
@@ -2250,118 +2142,14 @@ int eorb_search_by_projection_last_fisheye(eorb_ctx* c,
     return result_out(A, r, r.end, cur_mp, nmatches);
 }
 
-// the BoW-node walk of SearchForTriangulation (:975-1214) shared by both camera models: kb == nullptr runs the Pinhole test on
-// F12, otherwise KannalaBrandt8::epipolarConstrain with kb's cameras and poses.  One upload, one wait, one download.
-static int search_tri_common(eorb_ctx* c, const char* what,
-        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
-        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
-        const eorb_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
-        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
-        const float* ep, const float* F12, const float* scale2, const float* sigma2_2, const float* sigma2_1, int nlevels,
-        int bCoarse, int checkOri, TriKbArgs* kb, int32_t* match12, int* nmatches)
-{
-    fe_enter(c);
-    if (nmatches) *nmatches = 0;
-    for (int i = 0; i < n1; i++) match12[i] = -1;
-    if (n1 == 0 || n2 == 0 || nn1 == 0 || nn2 == 0) return EORB_OK;
-    int rc;
-    Arena A(c);
-    FvPair fv;
-    if ((rc = fv.queue(c, A, what, {nodes1, node_off1, idx1, nn1, n1, "pKF1"}, {nodes2, node_off2, idx2, nn2, n2, "pKF2"}))) return rc;
-    for (int i = 0; i < n2; i++)
-        if (elig2[i] && (kps2[i].octave < 0 || kps2[i].octave >= nlevels))
-            return set_err(c, EORB_E_ARG, "%s: pKF2 keypoint %d has octave %d outside [0,%d)", what, i, kps2[i].octave, nlevels);
-    if (kb)
-        for (int i = 0; i < n1; i++)
-            if ((elig1[i] & 1) && (kps1[i].octave < 0 || kps1[i].octave >= nlevels))
-                return set_err(c, EORB_E_ARG, "%s: pKF1 keypoint %d has octave %d outside [0,%d)", what, i, kps1[i].octave, nlevels);
-    const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * n1), o_d1 = A.in(desc1, (size_t)stride1 * n1);
-    const size_t o_k2 = A.in(kps2, sizeof(eorb_keypoint) * n2), o_d2 = A.in(desc2, (size_t)stride2 * n2);
-    const size_t o_e1 = A.in(elig1, n1), o_e2 = A.in(elig2, n2);
-    const size_t o_sc = A.in(scale2, sizeof(float) * nlevels), o_sg = A.in(sigma2_2, sizeof(float) * nlevels);
-    const size_t o_s1 = kb ? A.in(sigma2_1, sizeof(float) * nlevels) : 0;
-    // outputs, contiguous: histogram (nmatches at [32]) | matches; then the rotation bins
-    const size_t o_hist = A.reserve(sizeof(int32_t) * 40), o_m12 = A.reserve(sizeof(int32_t) * (size_t)n1), o_bin = A.reserve((size_t)n1);
-    if ((rc = A.upload())) return rc;
-    int32_t* hist = A.dev<int32_t>(o_hist);
-    TriArgs T{};
-    T.kps1 = A.dev<eorb_keypoint>(o_k1); T.n1 = n1; T.desc1 = A.dev<uint8_t>(o_d1); T.stride1 = stride1;
-    T.elig1 = A.dev<uint8_t>(o_e1); T.fv1 = fv.dev(A, 0);
-    T.kps2 = A.dev<eorb_keypoint>(o_k2); T.n2 = n2; T.desc2 = A.dev<uint8_t>(o_d2); T.stride2 = stride2;
-    T.elig2 = A.dev<uint8_t>(o_e2); T.fv2 = fv.dev(A, 1);
-    T.epx = ep[0]; T.epy = ep[1];
-    if (F12) for (int i = 0; i < 9; i++) T.F[i] = F12[i];
-    T.scale2 = A.dev<float>(o_sc); T.sigma2_2 = A.dev<float>(o_sg); T.nlevels = nlevels;
-    T.bCoarse = bCoarse; T.checkOri = checkOri;
-    T.match12 = A.dev<int32_t>(o_m12); T.bin1 = A.dev<int8_t>(o_bin); T.histo = hist; T.nmatches = hist + 32;
-    if (kb) { kb->T = T; kb->sigma2_1 = A.dev<float>(o_s1); }
-    if ((rc = search_tri_dev(c, T, kb))) return rc;
-    const char* h;
-    if ((rc = A.download(o_hist, o_m12 + sizeof(int32_t) * (size_t)n1 - o_hist, &h))) return rc;
-    memcpy(match12, h + o_m12, sizeof(int32_t) * (size_t)n1);
-    if (nmatches) memcpy(nmatches, h + o_hist + sizeof(int32_t) * 32, 4);
-    return EORB_OK;
-}
-
-int eorb_search_for_triangulation(eorb_ctx* c,
-        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
-        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
-        const eorb_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
-        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
-        const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
-        int bCoarse, int checkOri, int32_t* match12, int* nmatches)
-{
-    if (!c) return EORB_E_ARG;
-    if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !match12 || stride1 < 32 || stride2 < 32 || !ep || !F12 || !scale2 || !sigma2_2 ||
-        nlevels <= 0 || nlevels > 64)
-        return set_err(c, EORB_E_ARG, "search_for_triangulation: bad arguments");
-    return search_tri_common(c, "search_for_triangulation", kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1,
-                             kps2, n2, desc2, stride2, elig2, nodes2, node_off2, idx2, nn2, ep, F12, scale2, sigma2_2, nullptr,
-                             nlevels, bCoarse, checkOri, nullptr, match12, nmatches);
-}
-
-int eorb_search_for_triangulation_kb8(eorb_ctx* c,
-        const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
-        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
-        const eorb_keypoint* kps2, int n2, int nleft2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
-        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
-        const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
-        const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
-        int bCoarse, int checkOri, int32_t* match12, int* nmatches)
-{
-    if (!c) return EORB_E_ARG;
-    if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !match12 || stride1 < 32 || stride2 < 32 || !cam1 || !cam2 || !Rt || !ep ||
-        !scale2 || !sigma2_1 || !sigma2_2 || nlevels <= 0 || nlevels > 64 || nleft1 < -1 || nleft2 < -1 || nleft1 > n1 || nleft2 > n2)
-        return set_err(c, EORB_E_ARG, "search_for_triangulation_kb8: bad arguments");
-    fe_enter(c);
-    if (nmatches) *nmatches = 0;
-    for (int i = 0; i < n1; i++) match12[i] = -1;
-    const bool twocam = nleft1 >= 0;
-    if ((nleft1 < 0) != (nleft2 < 0))      // the reference leaves R12 an empty cv::Mat (:1000-1014)
-        return set_err(c, EORB_E_CONFIG, "search_for_triangulation_kb8: one keyframe has two cameras and the other one");
-    const int nc1 = twocam ? 2 : 1;
-    for (int k = 0; k < nc1; k++)
-        if (cam1[k].model != 1)
-            return set_err(c, EORB_E_CONFIG, "search_for_triangulation_kb8: pKF1's camera %d is not KannalaBrandt8 "
-                                             "(Pinhole pCamera1: eorb_search_for_triangulation)", k);
-    for (int k = 0; k < nc1; k++)
-        if (cam2[k].model != 0 && cam2[k].model != 1)
-            return set_err(c, EORB_E_ARG, "search_for_triangulation_kb8: pKF2's camera %d has model %d", k, cam2[k].model);
-    TriKbArgs K{};
-    K.nleft1 = nleft1; K.nleft2 = nleft2;
-    for (int k = 0; k < 2; k++) { K.cam1[k] = cam1[k < nc1 ? k : 0]; K.cam2[k] = cam2[k < nc1 ? k : 0]; }
-    for (int i = 0; i < (twocam ? 48 : 12); i++) K.Rt[i] = Rt[i];
-    return search_tri_common(c, "search_for_triangulation_kb8", kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1,
-                             kps2, n2, desc2, stride2, elig2, nodes2, node_off2, idx2, nn2, ep, nullptr, scale2, sigma2_2, sigma2_1,
-                             nlevels, bCoarse, checkOri, &K, match12, nmatches);
-}
-
-// ---- the node walks over K keyframes per call (eorb_kf_set of include/eorb_fe.h) ----------------------------------------------------
+// ---- the node walks (SearchByBoW, SearchForTriangulation) over K keyframes per call (eorb_kf_set of include/eorb_fe.h); the single-pair
+// entry points are the same code with a set of one ----------------------------------------------------------------------------------
 static constexpr int kKfBatchMaxKfs = 1024;                             // K
 static constexpr int64_t kKfBatchMaxOut = (int64_t)1 << 22;             // K * the length of one output row
 static constexpr int64_t kKfBatchMaxRows = (int64_t)1 << 22;            // rows of all keyframes together; feature indices likewise
 
-// FvPair::queue's checks for one feature vector, plus its offsets; k >= 0 names the keyframe of a set
+// one feature vector as the device walks need it (tri_entry bisects the offsets, bow_node reads off[a + 1]): offsets from 0 that never
+// decrease, every index inside the side's features; k >= 0 names the keyframe of a set
 static int fv_check(eorb_ctx* c, const char* what, const char* name, int k, const int32_t* off, const int32_t* idx, int nn, int n_features)
 {
     char who[48];
@@ -2428,6 +2216,15 @@ struct KfSetIn {
     FeatVec fv(const Arena& A) const { return FeatVec{A.dev<uint32_t>(o_nodes), A.dev<int32_t>(o_off), A.dev<int32_t>(o_idx), 0}; }
 };
 
+// one keyframe as a set of one: a view of the caller's arrays, nothing copied (node_off[nn + 1] is the set's feat_off at K = 1)
+struct KfSetOne {
+    int32_t kf_off[2], node_off[2]; eorb_kf_set S;
+    KfSetOne(const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const uint8_t* flag,
+             const uint32_t* nodes, const int32_t* off, const int32_t* idx, int nn)
+        : kf_off{0, n}, node_off{0, nn}, S{1, kps, desc, stride, flag, kf_off, nodes, node_off, off, idx} {}
+    KfSetOne(const KfSetOne&) = delete;
+};
+
 // the shared side's feature vector, straight from the caller's arrays
 struct FvIn {
     size_t o_nodes = 0, o_off = 0, o_idx = 0; int nn = 0;
@@ -2465,8 +2262,10 @@ static int kfbatch_out(Arena& A, const KfBatchOut& o, int K, int n, int32_t* out
     return EORB_OK;
 }
 
-// search_tri_common over the K keyframes of a set: pKF1 and the level tables are uploaded once, the pairs' values go into device tables
-static int search_tri_batch_common(eorb_ctx* c, const char* what,
+// the BoW-node walk of SearchForTriangulation (:975-1214) over the K keyframes of a set, shared by both camera models: kb == nullptr runs
+// the Pinhole test on F12, otherwise KannalaBrandt8::epipolarConstrain with kb's cameras and the pairs' poses.  pKF1 and the level tables
+// are uploaded once, the pairs' values go into device tables.  what: the entry point, in messages and as the profile scope
+static int search_tri_common(eorb_ctx* c, const char* what,
         const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1, const eorb_kf_set* S, KfSetIn& J,
         const float* ep, const float* F12, const float* scale2, const float* sigma2_2, const float* sigma2_1, int nlevels,
@@ -2527,8 +2326,22 @@ static int search_tri_batch_common(eorb_ctx* c, const char* what,
         kb->T = T; kb->sigma2_1 = A.dev<float>(o_s1);
         KB.K = *kb; KB.kf = B.kf; KB.pair = B.pair; KB.kb = A.dev<TriKbPair>(o_q); KB.nk = K;
     }
-    if ((rc = search_tri_batch_dev(c, B, kb ? &KB : nullptr))) return rc;
+    if ((rc = search_tri_batch_dev(c, what, B, kb ? &KB : nullptr))) return rc;
     return kfbatch_out(A, o, K, n1, match12, nmatches);
+}
+
+// the cameras of a KannalaBrandt8 walk into its block: pKF1's must be KannalaBrandt8, the other side's Pinhole or KannalaBrandt8
+static int kb8_cameras(eorb_ctx* c, const char* what, int nleft1, const eorb_camera* cam1, const eorb_camera* cam2, TriKbArgs& KA)
+{
+    const int nc1 = nleft1 >= 0 ? 2 : 1;
+    for (int k = 0; k < nc1; k++)
+        if (cam1[k].model != 1)
+            return set_err(c, EORB_E_CONFIG, "%s: pKF1's camera %d is not KannalaBrandt8 (Pinhole pCamera1: the entry point without kb8)", what, k);
+    for (int k = 0; k < nc1; k++)
+        if (cam2[k].model != 0 && cam2[k].model != 1) return set_err(c, EORB_E_ARG, "%s: pKF2's camera %d has model %d", what, k, cam2[k].model);
+    KA.nleft1 = nleft1;
+    for (int k = 0; k < 2; k++) { KA.cam1[k] = cam1[k < nc1 ? k : 0]; KA.cam2[k] = cam2[k < nc1 ? k : 0]; }
+    return EORB_OK;
 }
 
 int eorb_search_for_triangulation_keyframes(eorb_ctx* c,
@@ -2545,7 +2358,7 @@ int eorb_search_for_triangulation_keyframes(eorb_ctx* c,
     if (nn1 < 0 || stride1 < 32 || !scale2 || !sigma2_2 || nlevels <= 0 || nlevels > 64 ||
         (I.K > 0 && (!ep || !F12 || (n1 > 0 && (!match12 || !kps1 || !desc1 || !elig1)) || (nn1 > 0 && (!nodes1 || !node_off1 || !idx1)))))
         return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
-    return search_tri_batch_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, F12, scale2, sigma2_2,
+    return search_tri_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, F12, scale2, sigma2_2,
                                    nullptr, nlevels, bCoarse, checkOri, nullptr, nullptr, nullptr, match12, nmatches);
 }
 
@@ -2573,25 +2386,19 @@ int eorb_search_for_triangulation_kb8_keyframes(eorb_ctx* c,
     for (int k = 0; k < I.K; k++)
         if (twocam != (nleft2[k] >= 0))       // the reference leaves R12 an empty cv::Mat (:1000-1014)
             return set_err(c, EORB_E_CONFIG, "%s: keyframe %d: one keyframe of the pair has two cameras and the other one", what, k);
-    const int nc1 = twocam ? 2 : 1;
-    for (int k = 0; k < nc1; k++)
-        if (cam1[k].model != 1)
-            return set_err(c, EORB_E_CONFIG, "%s: pKF1's camera %d is not KannalaBrandt8 (Pinhole pCamera1: eorb_search_for_triangulation_keyframes)", what, k);
-    for (int k = 0; k < nc1; k++)
-        if (cam2[k].model != 0 && cam2[k].model != 1) return set_err(c, EORB_E_ARG, "%s: the neighbours' camera %d has model %d", what, k, cam2[k].model);
     TriKbArgs KA{};
-    KA.nleft1 = nleft1; KA.nleft2 = -1;
-    for (int k = 0; k < 2; k++) { KA.cam1[k] = cam1[k < nc1 ? k : 0]; KA.cam2[k] = cam2[k < nc1 ? k : 0]; }
-    return search_tri_batch_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, nullptr, scale2, sigma2_2,
+    if ((rc = kb8_cameras(c, what, nleft1, cam1, cam2, KA))) return rc;
+    return search_tri_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, nullptr, scale2, sigma2_2,
                                    sigma2_1, nlevels, bCoarse, checkOri, &KA, nleft2, Rt, match12, nmatches);
 }
 
-// bow_common over the K keyframes of a set.  kf_kf = 0: the set is the KeyFrame side, `one` the frame (flag1 unused);
-// kf_kf = 1: `one` is pKF1 with flag1 = has_mp1, the set is side 2.  Row k has n1 entries either way.
-static int bow_batch_common(eorb_ctx* c, const char* what, int kf_kf, const eorb_kf_set* S,
+// SearchByBoW over the K keyframes of a set.  kf_kf = 0: the set is the KeyFrame side, `one` the frame (flag1 unused; nL >= 0: a
+// two-camera frame of nL left features, then right ones); kf_kf = 1: `one` is pKF1 with flag1 = has_mp1, the set is side 2.  Row k has
+// n1 entries either way.  what: the entry point in messages, prof: its profile scope
+static int bow_common(eorb_ctx* c, const char* what, const char* prof, int kf_kf, const eorb_kf_set* S,
         const eorb_keypoint* kps1, int n1, const uint8_t* desc1, const uint8_t* flag1,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
-        int32_t* out, float nnratio, int checkOri, int32_t* nmatches)
+        int32_t* out, float nnratio, int checkOri, int32_t* nmatches, int nL = -1)
 {
     if (!c) return EORB_E_ARG;
     KfSetIn I;
@@ -2621,7 +2428,7 @@ static int bow_batch_common(eorb_ctx* c, const char* what, int kf_kf, const eorb
     if (kf_kf) B.A = BowArgs{k1, d1, A.dev<uint8_t>(o_f1), f1.fv(A), sk, 0, sd, I.fv(A), scr, A.dev<int8_t>(o.o_bin), hist, hist + 32, nnratio, checkOri, 1, sf, m, n1};
     else B.A = BowArgs{sk, sd, sf, I.fv(A), k1, n1, d1, f1.fv(A), m, A.dev<int8_t>(o.o_bin), hist, hist + 32, nnratio, checkOri, 0, sf, nullptr, 0};
     B.kf = A.dev<KfSlice>(I.o_sl); B.K = K; B.n_out = n1; B.max_nn = kf_kf ? nn1 : I.max_nn;
-    if ((rc = search_bow_batch_dev(c, B, kf_kf ? scr : nullptr, nscratch))) return rc;
+    if ((rc = search_bow_batch_dev(c, prof, B, kf_kf ? scr : nullptr, nscratch, nL))) return rc;
     return kfbatch_out(A, o, K, n1, out, nmatches);
 }
 
@@ -2630,7 +2437,7 @@ int eorb_search_by_bow_keyframes(eorb_ctx* c, const eorb_kf_set* set,
         const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
         int32_t* match_f, float nnratio, int checkOri, int32_t* nmatches)
 {
-    return bow_batch_common(c, "search_by_bow_keyframes", 0, set, f_kps, n_f, f_desc, nullptr, f_nodes, f_node_off, f_idx, f_nn, match_f, nnratio,
+    return bow_common(c, "search_by_bow_keyframes", "search_by_bow_keyframes", 0, set, f_kps, n_f, f_desc, nullptr, f_nodes, f_node_off, f_idx, f_nn, match_f, nnratio,
                             checkOri, nmatches);
 }
 
@@ -2639,8 +2446,108 @@ int eorb_search_by_bow_kf_keyframes(eorb_ctx* c,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
         const eorb_kf_set* set, int32_t* match12, float nnratio, int checkOri, int32_t* nmatches)
 {
-    return bow_batch_common(c, "search_by_bow_kf_keyframes", 1, set, kps1, n1, desc1, has_mp1, nodes1, node_off1, idx1, nn1, match12, nnratio,
+    return bow_common(c, "search_by_bow_kf_keyframes", "search_by_bow_kf_keyframes", 1, set, kps1, n1, desc1, has_mp1, nodes1, node_off1, idx1, nn1, match12, nnratio,
                             checkOri, nmatches);
+}
+
+// ---- the single-pair forms: the other keyframe (or the KeyFrame of SearchByBoW(pKF, F)) as a set of one ----
+int eorb_search_for_triangulation(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_keypoint* kps2, int n2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
+        const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "search_for_triangulation";
+    if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !match12 || stride1 < 32 || stride2 < 32 || !ep || !F12 || !scale2 || !sigma2_2 ||
+        nlevels <= 0 || nlevels > 64)
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    kfbatch_clear(1, n1, match12, nmatches);          // before any error that depends on what the arrays hold
+    const KfSetOne two(kps2, n2, desc2, stride2, elig2, nodes2, node_off2, idx2, nn2);
+    KfSetIn I;
+    int rc;
+    if ((rc = I.check(c, what, &two.S, n1))) return rc;
+    return search_tri_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, &two.S, I, ep, F12, scale2, sigma2_2,
+                             nullptr, nlevels, bCoarse, checkOri, nullptr, nullptr, nullptr, match12, nmatches);
+}
+
+int eorb_search_for_triangulation_kb8(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_keypoint* kps2, int n2, int nleft2, const uint8_t* desc2, int stride2, const uint8_t* elig2,
+        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
+        const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
+        const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int* nmatches)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "search_for_triangulation_kb8";
+    if (n1 < 0 || n2 < 0 || nn1 < 0 || nn2 < 0 || !match12 || stride1 < 32 || stride2 < 32 || !cam1 || !cam2 || !Rt || !ep ||
+        !scale2 || !sigma2_1 || !sigma2_2 || nlevels <= 0 || nlevels > 64 || nleft1 < -1 || nleft2 < -1 || nleft1 > n1 || nleft2 > n2)
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    kfbatch_clear(1, n1, match12, nmatches);
+    if ((nleft1 < 0) != (nleft2 < 0))      // the reference leaves R12 an empty cv::Mat (:1000-1014)
+        return set_err(c, EORB_E_CONFIG, "%s: one keyframe has two cameras and the other one", what);
+    TriKbArgs KA{};
+    int rc;
+    if ((rc = kb8_cameras(c, what, nleft1, cam1, cam2, KA))) return rc;
+    const KfSetOne two(kps2, n2, desc2, stride2, elig2, nodes2, node_off2, idx2, nn2);
+    KfSetIn I;
+    if ((rc = I.check(c, what, &two.S, n1))) return rc;
+    return search_tri_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, &two.S, I, ep, nullptr, scale2, sigma2_2,
+                             sigma2_1, nlevels, bCoarse, checkOri, &KA, &nleft2, Rt, match12, nmatches);
+}
+
+// SearchByBoW(pKF, F) (kf_kf = 0: the set is the KeyFrame) and SearchByBoW(pKF1, pKF2) (kf_kf = 1: the set is pKF2)
+static int bow_single(eorb_ctx* c, const char* what, const char* prof, int kf_kf,
+        const eorb_keypoint* s_kps, int s_n, const uint8_t* s_desc, const uint8_t* s_flag,
+        const uint32_t* s_nodes, const int32_t* s_node_off, const int32_t* s_idx, int s_nn,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, const uint8_t* flag1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        int32_t* out, float nnratio, int checkOri, int* nmatches, int nL = -1)
+{
+    if (!c) return EORB_E_ARG;
+    if (s_n < 0 || n1 < 0 || s_nn < 0 || nn1 < 0 || !out) return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    kfbatch_clear(1, n1, out, nmatches);              // before any error that depends on what the arrays hold
+    const KfSetOne one(s_kps, s_n, s_desc, 32, s_flag, s_nodes, s_node_off, s_idx, s_nn);
+    return bow_common(c, what, prof, kf_kf, &one.S, kps1, n1, desc1, flag1, nodes1, node_off1, idx1, nn1, out, nnratio, checkOri, nmatches, nL);
+}
+
+int eorb_search_by_bow(eorb_ctx* c,
+        const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
+        const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
+        const eorb_keypoint* f_kps, int n_f, const uint8_t* f_desc,
+        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
+        int32_t* match_f, float nnratio, int checkOri, int* nmatches)
+{
+    return bow_single(c, "search_by_bow", "search_bow", 0, kf_kps, n_kf, kf_desc, kf_has_mp, kf_nodes, kf_node_off, kf_idx, kf_nn,
+                      f_kps, n_f, f_desc, nullptr, f_nodes, f_node_off, f_idx, f_nn, match_f, nnratio, checkOri, nmatches);
+}
+
+int eorb_search_by_bow_kf(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, const uint8_t* has_mp1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_keypoint* kps2, int n2, const uint8_t* desc2, const uint8_t* has_mp2,
+        const uint32_t* nodes2, const int32_t* node_off2, const int32_t* idx2, int nn2,
+        int32_t* match12, float nnratio, int checkOri, int* nmatches)
+{
+    if (c && !has_mp2 && n2 > 0) return set_err(c, EORB_E_ARG, "search_by_bow_kf: has_mp2 is required");
+    return bow_single(c, "search_by_bow_kf", "search_bow", 1, kps2, n2, desc2, has_mp2, nodes2, node_off2, idx2, nn2,
+                      kps1, n1, desc1, has_mp1, nodes1, node_off1, idx1, nn1, match12, nnratio, checkOri, nmatches);
+}
+
+int eorb_search_by_bow_fisheye(eorb_ctx* c,
+        const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
+        const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
+        const eorb_keypoint* f_kps, int n_f, int nL, const uint8_t* f_desc,
+        const uint32_t* f_nodes, const int32_t* f_node_off, const int32_t* f_idx, int f_nn,
+        int32_t* match_f, float nnratio, int checkOri, int* nmatches)
+{
+    if (c && (nL < 0 || nL > n_f)) return set_err(c, EORB_E_ARG, "search_by_bow_fisheye: nL %d of %d frame features", nL, n_f);
+    return bow_single(c, "search_by_bow_fisheye", "search_bow_fisheye", 0, kf_kps, n_kf, kf_desc, kf_has_mp, kf_nodes, kf_node_off, kf_idx, kf_nn,
+                      f_kps, n_f, f_desc, nullptr, f_nodes, f_node_off, f_idx, f_nn, match_f, nnratio, checkOri, nmatches, nL);
 }
 
 int eorb_kb8_triangulate_matches(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt,

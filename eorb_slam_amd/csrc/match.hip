@@ -1159,20 +1159,13 @@ __device__ __forceinline__ void bow_node(const BowArgs& A, int a, int lane)
     }
 }
 
-__global__ __launch_bounds__(256) void search_bow_kernel(BowArgs A)
-{
-    const int lane = threadIdx.x & 63;
-    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    for (int a = gw; a < A.kf_fv.nn; a += nw) bow_node(A, a, lane);
-}
-
 // ---- K pairs per launch: blockIdx.y = the pair, so the pair index and everything read with it is wave-uniform ----
 __device__ __forceinline__ FeatVec fv_slice(const FeatVec& all, const KfSlice& s)
 {
     return FeatVec{all.nodes + s.node0, all.off + s.off0, all.idx + s.idx0, s.nn};
 }
 
-// the single walk's block for pair k.  SearchByBoW(pKF_k, F): the set is the KeyFrame side and pair k owns match_f / bin_f slice k.
+// bow_node's block for pair k.  SearchByBoW(pKF_k, F): the set is the KeyFrame side and pair k owns match_f / bin_f slice k.
 // SearchByBoW(pKF1, pKF2_k): the set is side 2 (the "frame" side of the walk); pair k owns match12 / bin_f slice k, and its vbMatched2
 // flags (match_f) are the set's rows row0 .. of the scratch array.  Either way a wavefront orders match_f accesses only against its
 // own earlier ones: a node of pair k touches only pair k's slice, at the features of that node.
@@ -1201,6 +1194,55 @@ __global__ __launch_bounds__(256) void search_bow_batch_kernel(BowBatchArgs B)
     const int lane = threadIdx.x & 63;
     const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
     for (int a = gw; a < A.kf_fv.nn; a += nw) bow_node(A, a, lane);
+}
+
+// SearchByBoW(KeyFrame*, Frame&) on a two-camera frame (ORBmatcher.cc:276-478): per KeyFrame feature two best / second-best pairs,
+// one over the frame's left features (index < nL) and one over its right ones (:357-377); the right best is taken only inside
+// "if(bestDist1 <= TH_LOW)" (:410) and its ratio test is "... || true" (:412).  A frame feature belongs to one vocabulary node, so
+// nodes run concurrently as in search_bow_batch_kernel: one wavefront per node, KeyFrame features in order, lanes over the node's frame
+// features.  The rotation check reuses search_finish_batch_kernel (every frame slot is matched at most once).
+__global__ __launch_bounds__(256) void search_bow_fisheye_kernel(BowBatchArgs B, int nL)
+{
+    const BowArgs A = bow_pair(B, blockIdx.y);
+    const int lane = threadIdx.x & 63;
+    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+    for (int a = gw; a < A.kf_fv.nn; a += nw) {
+        const int lo = find_node(A.f_fv, A.kf_fv.nodes[a], lane);
+        if (lo < 0) continue;
+        const int f0 = A.f_fv.off[lo], f1 = A.f_fv.off[lo + 1];
+        for (int iKF = A.kf_fv.off[a]; iKF < A.kf_fv.off[a + 1]; iKF++) {
+            const int realIdxKF = A.kf_fv.idx[iKF];
+            if (!A.kf_has_mp[realIdxKF]) continue;
+            const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)realIdxKF * 32);
+            const uint64_t q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3];
+            uint64_t l0 = ~0ull, l1 = ~0ull, r0 = ~0ull, r1 = ~0ull;         // key = dist << 32 | iF (vector order breaks ties)
+            for (int iF = f0 + lane; iF < f1; iF += 64) {
+                const int realIdxF = A.f_fv.idx[iF];
+                if (__hip_atomic_load(&A.match_f[realIdxF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) continue;
+                const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)realIdxF * 32);
+                const int dist = __popcll(q0 ^ tp[0]) + __popcll(q1 ^ tp[1]) + __popcll(q2 ^ tp[2]) + __popcll(q3 ^ tp[3]);
+                if (dist >= 256) continue;
+                const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)iF;
+                if (realIdxF < nL) top2_insert(key, l0, l1); else top2_insert(key, r0, r1);
+            }
+            shfl_top2(l0, l1);
+            shfl_top2(r0, r1);
+            const int bestDist1 = l0 == ~0ull ? 256 : (int)(l0 >> 32);
+            if (bestDist1 > TH_LOW) continue;
+            const int bestDist2 = l1 == ~0ull ? 256 : (int)(l1 >> 32);
+            if (lane == 0) {
+                if ((float)bestDist1 < A.nnratio * (float)bestDist2) {
+                    const int bestIdxF = A.f_fv.idx[(int)(l0 & 0xffffffffu)];
+                    bow_commit<true>(A, realIdxKF, bestIdxF, bestIdxF);
+                }
+                if (r0 != ~0ull && (int)(r0 >> 32) <= TH_LOW) {                  // ratio "|| true" (:412)
+                    const int bestIdxFR = A.f_fv.idx[(int)(r0 & 0xffffffffu)];
+                    bow_commit<true>(A, realIdxKF, bestIdxFR, bestIdxFR);
+                }
+            }
+            __threadfence();          // the next KeyFrame feature of this node must see match_f
+        }
+    }
 }
 
 // three_maxima one bin at a time (the running state after bin i, then the 10 % rule) for rot_finish, whose loop over the bins is not
@@ -1244,11 +1286,6 @@ __device__ __forceinline__ void rot_finish(int32_t* out, const int8_t* bin, int 
     if (dec) atomicSub(nmatches, dec);
 }
 
-__global__ void search_bow_finish_kernel(int32_t* out, const int8_t* bin, int n, int32_t* histo, int32_t* nmatches)
-{
-    rot_finish(out, bin, n, histo, nmatches);
-}
-
 // one block per pair
 __global__ void search_finish_batch_kernel(int32_t* out, const int8_t* bin, int n, int32_t* histo)
 {
@@ -1266,48 +1303,26 @@ __global__ void search_init_batch_kernel(int32_t* out, int8_t* bin, int nout, in
     if (i < nscratch) scratch[i] = -1;
 }
 
-__global__ void bow_init_kernel(int32_t* match_f, int8_t* bin_f, int n_f, int32_t* histo, int32_t* nmatches, int32_t* match12, int n_kf)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_f) match_f[i] = -1;
-    if (i < max(n_f, n_kf)) bin_f[i] = -1;
-    if (match12 && i < n_kf) match12[i] = -1;
-    if (i < 32) histo[i] = 0;
-    if (i == 0) *nmatches = 0;
-}
-
-int search_bow_dev(eorb_ctx* c, const BowArgs& A)
-{
-    ProfScope ps(c, "search_bow");
-    bow_init_kernel<<<(std::max(std::max(A.n_f, A.n_kf), 32) + 255) / 256, 256, 0, c->stream>>>(A.match_f, A.bin_f, A.n_f, A.histo, A.nmatches,
-                                                                                              A.kf_kf ? A.match12 : nullptr, A.n_kf);
-    if (A.kf_fv.nn > 0 && A.f_fv.nn > 0) {
-        const int blocks = std::min((A.kf_fv.nn + 3) / 4, 1024);
-        search_bow_kernel<<<blocks, 256, 0, c->stream>>>(A);
-        if (A.checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A.kf_kf ? A.match12 : A.match_f, A.bin_f, A.kf_kf ? A.n_kf : A.n_f,
-                                                                           A.histo, A.nmatches);
-    }
-    EORB_LAUNCH_CHECK(c, "search_bow kernels");
-    return EORB_OK;
-}
-
 static void search_init_batch(eorb_ctx* c, int32_t* out, int8_t* bin, int K, int n_out, int32_t* histo, int32_t* scratch, int nscratch)
 {
     const int nout = K * n_out, nhist = K * kPairHist;          // (K * n_out <= 2^22: the entry points' limit)
     search_init_batch_kernel<<<(std::max(std::max(nout, nhist), nscratch) + 255) / 256, 256, 0, c->stream>>>(out, bin, nout, histo, nhist, scratch, nscratch);
 }
 
-// three launches for any K: init, walk (one wavefront per pair and KeyFrame-side node), rotation finish (one block per pair)
-int search_bow_batch_dev(eorb_ctx* c, const BowBatchArgs& B, int32_t* scratch, int nscratch)
+// three launches for any K: init, walk (one wavefront per pair and KeyFrame-side node), rotation finish (one block per pair).  name: the
+// entry point's profile scope; nL >= 0: the walk of a two-camera frame (nL left features, then right ones)
+int search_bow_batch_dev(eorb_ctx* c, const char* name, const BowBatchArgs& B, int32_t* scratch, int nscratch, int nL)
 {
-    ProfScope ps(c, B.A.kf_kf ? "search_by_bow_kf_keyframes" : "search_by_bow_keyframes");
+    ProfScope ps(c, name);
     int32_t* out = B.A.kf_kf ? B.A.match12 : B.A.match_f;
     search_init_batch(c, out, B.A.bin_f, B.K, B.n_out, B.A.histo, scratch, nscratch);
     if (B.max_nn > 0) {
-        search_bow_batch_kernel<<<dim3(std::min((B.max_nn + 3) / 4, 1024), B.K), 256, 0, c->stream>>>(B);
+        const dim3 grid(std::min((B.max_nn + 3) / 4, 1024), B.K);
+        if (nL >= 0) search_bow_fisheye_kernel<<<grid, 256, 0, c->stream>>>(B, nL);
+        else search_bow_batch_kernel<<<grid, 256, 0, c->stream>>>(B);
         if (B.A.checkOri) search_finish_batch_kernel<<<B.K, 256, 0, c->stream>>>(out, B.A.bin_f, B.n_out, B.A.histo);
     }
-    EORB_LAUNCH_CHECK(c, "search_bow batch kernels");
+    EORB_LAUNCH_CHECK(c, name);
     return EORB_OK;
 }
 
@@ -1405,14 +1420,12 @@ struct TriPinhole {                  // pCamera1 = Pinhole: the test on F12
 // pCamera1 = KannalaBrandt8: epipolarConstrain = TriangulateMatches(...) > KB8_DEF_TH_EPC (KannalaBrandt8.cpp:315-320, :416-486).
 // Two-camera keyframes (nleft >= 0) pick one of four poses and cameras per (left/right, left/right) pair (:1107-1137) and skip
 // the epipole test; bStereo is false for them (:1051, :1079).
-struct TriKbPairView { const TriKbArgs& K; const float* Rt; int nleft2; };       // pair k of a batch: K's own Rt / nleft2 are unused
+struct TriKbPairView { const TriKbArgs& K; const float* Rt; int nleft2; };       // pair k: the block, its poses (ll, lr, rl, rr) and pKF2_k's nleft
 struct TriKb8 {
     const TriKbArgs& K; const float* const Rt; const int nleft2; const int bRight1; const bool bStereo1; const float x1, y1, sig1;
-    __device__ __forceinline__ TriKb8(const TriKbArgs& k, const float* rt, int nl2, int id1, uint8_t e1, const eorb_keypoint& kp1)
-        : K(k), Rt(rt), nleft2(nl2), bRight1(k.nleft1 >= 0 && id1 >= k.nleft1), bStereo1(k.nleft1 < 0 && (e1 & 2)), x1(kp1.x), y1(kp1.y),
-          sig1(k.sigma2_1[kp1.octave]) {}
-    __device__ __forceinline__ TriKb8(const TriKbArgs& k, int id1, uint8_t e1, const eorb_keypoint& kp1) : TriKb8(k, k.Rt, k.nleft2, id1, e1, kp1) {}
-    __device__ __forceinline__ TriKb8(const TriKbPairView& v, int id1, uint8_t e1, const eorb_keypoint& kp1) : TriKb8(v.K, v.Rt, v.nleft2, id1, e1, kp1) {}
+    __device__ __forceinline__ TriKb8(const TriKbPairView& v, int id1, uint8_t e1, const eorb_keypoint& kp1)
+        : K(v.K), Rt(v.Rt), nleft2(v.nleft2), bRight1(v.K.nleft1 >= 0 && id1 >= v.K.nleft1), bStereo1(v.K.nleft1 < 0 && (e1 & 2)), x1(kp1.x), y1(kp1.y),
+          sig1(v.K.sigma2_1[kp1.octave]) {}
     __device__ __forceinline__ bool twocam() const { return K.nleft1 >= 0; }
     __device__ __forceinline__ bool epipole_gate(uint8_t e2) const { return !twocam() && !bStereo1 && !(e2 & 2); }      // :1097-1105
     __device__ __forceinline__ bool ok(int id2, const eorb_keypoint& kp2) const
@@ -1425,10 +1438,6 @@ struct TriKb8 {
                                        K.T.sigma2_2[kp2.octave]) > 0.0001f;       // KB8_DEF_TH_EPC
     }
 };
-
-// two entry points, not one with a run-time camera switch: the Pinhole walk needs a third of the KannalaBrandt8 one's registers
-__global__ __launch_bounds__(256) void search_tri_kernel(TriArgs A) { tri_walk<TriPinhole>(A, A); }
-__global__ __launch_bounds__(256) void search_tri_kb8_kernel(TriKbArgs K) { tri_walk<TriKb8>(K.T, K); }
 
 // K pairs per launch (blockIdx.y = the pair): pKF1 and the level tables stay as in T; pKF2_k, its epipole and F12 come from the tables
 __device__ __forceinline__ TriArgs tri_pair(const TriArgs& T, const KfSlice* kf, const TriPair* pair, int k, bool pinhole)
@@ -1444,6 +1453,7 @@ __device__ __forceinline__ TriArgs tri_pair(const TriArgs& T, const KfSlice* kf,
     return A;
 }
 
+// two kernels, not one with a run-time camera switch: the Pinhole walk needs a third of the KannalaBrandt8 one's registers
 __global__ __launch_bounds__(256) void search_tri_batch_kernel(TriBatchArgs B)
 {
     const TriArgs A = tri_pair(B.T, B.kf, B.pair, blockIdx.y, true);
@@ -1457,29 +1467,17 @@ __global__ __launch_bounds__(256) void search_tri_kb8_batch_kernel(TriKbBatchArg
     tri_walk<TriKb8>(A, TriKbPairView{B.K, kb->Rt, kb->nleft2});
 }
 
-int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K)
+// init, walk (one wavefront per pair and entry of fv1), rotation finish (one block per pair); name: the entry point's profile scope
+int search_tri_batch_dev(eorb_ctx* c, const char* name, const TriBatchArgs& B, const TriKbBatchArgs* K)
 {
-    ProfScope ps(c, K ? "search_for_triangulation_kb8" : "search_for_triangulation");
-    const int blocks = std::min((A.n1 + 3) / 4 + 1, 2048);
-    bow_init_kernel<<<(std::max(A.n1, 32) + 255) / 256, 256, 0, c->stream>>>(A.match12, A.bin1, A.n1, A.histo, A.nmatches, nullptr, 0);
-    if (K) search_tri_kb8_kernel<<<blocks, 256, 0, c->stream>>>(*K);
-    else search_tri_kernel<<<blocks, 256, 0, c->stream>>>(A);
-    if (A.checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A.match12, A.bin1, A.n1, A.histo, A.nmatches);
-    EORB_LAUNCH_CHECK(c, K ? "search_for_triangulation_kb8 kernels" : "search_for_triangulation kernels");
-    return EORB_OK;
-}
-
-// init, walk (one wavefront per pair and entry of fv1), rotation finish (one block per pair)
-int search_tri_batch_dev(eorb_ctx* c, const TriBatchArgs& B, const TriKbBatchArgs* K)
-{
-    ProfScope ps(c, K ? "search_for_triangulation_kb8_keyframes" : "search_for_triangulation_keyframes");
+    ProfScope ps(c, name);
     const TriArgs& T = B.T;
     search_init_batch(c, T.match12, T.bin1, B.K, T.n1, T.histo, nullptr, 0);
     const dim3 grid(std::min((T.n1 + 3) / 4 + 1, 2048), B.K);
     if (K) search_tri_kb8_batch_kernel<<<grid, 256, 0, c->stream>>>(*K);
     else search_tri_batch_kernel<<<grid, 256, 0, c->stream>>>(B);
     if (T.checkOri) search_finish_batch_kernel<<<B.K, 256, 0, c->stream>>>(T.match12, T.bin1, T.n1, T.histo);
-    EORB_LAUNCH_CHECK(c, K ? "search_for_triangulation_kb8 batch kernels" : "search_for_triangulation batch kernels");
+    EORB_LAUNCH_CHECK(c, name);
     return EORB_OK;
 }
 
@@ -2436,67 +2434,6 @@ int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A)
     if (kind) twocam_walk_kernel<1><<<1, 256, lds, c->stream>>>(A);
     else twocam_walk_kernel<0><<<1, 256, lds, c->stream>>>(A);
     EORB_LAUNCH_CHECK(c, "twocam_walk_kernel");
-    return EORB_OK;
-}
-
-// SearchByBoW(KeyFrame*, Frame&) on a two-camera frame (ORBmatcher.cc:276-478): per KeyFrame feature two best / second-best pairs,
-// one over the frame's left features (index < nL) and one over its right ones (:357-377); the right best is taken only inside
-// "if(bestDist1 <= TH_LOW)" (:410) and its ratio test is "... || true" (:412).  A frame feature belongs to one vocabulary node, so
-// nodes run concurrently as in search_bow_kernel: one wavefront per node, KeyFrame features in order, lanes over the node's frame
-// features.  The rotation check reuses search_bow_finish_kernel (every frame slot is matched at most once).
-__global__ __launch_bounds__(256) void search_bow_fisheye_kernel(BowArgs A, int nL)
-{
-    const int lane = threadIdx.x & 63;
-    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    for (int a = gw; a < A.kf_fv.nn; a += nw) {
-        const int lo = find_node(A.f_fv, A.kf_fv.nodes[a], lane);
-        if (lo < 0) continue;
-        const int f0 = A.f_fv.off[lo], f1 = A.f_fv.off[lo + 1];
-        for (int iKF = A.kf_fv.off[a]; iKF < A.kf_fv.off[a + 1]; iKF++) {
-            const int realIdxKF = A.kf_fv.idx[iKF];
-            if (!A.kf_has_mp[realIdxKF]) continue;
-            const uint64_t* dq = (const uint64_t*)(A.kf_desc + (size_t)realIdxKF * 32);
-            const uint64_t q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3];
-            uint64_t l0 = ~0ull, l1 = ~0ull, r0 = ~0ull, r1 = ~0ull;         // key = dist << 32 | iF (vector order breaks ties)
-            for (int iF = f0 + lane; iF < f1; iF += 64) {
-                const int realIdxF = A.f_fv.idx[iF];
-                if (__hip_atomic_load(&A.match_f[realIdxF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) continue;
-                const uint64_t* tp = (const uint64_t*)(A.f_desc + (size_t)realIdxF * 32);
-                const int dist = __popcll(q0 ^ tp[0]) + __popcll(q1 ^ tp[1]) + __popcll(q2 ^ tp[2]) + __popcll(q3 ^ tp[3]);
-                if (dist >= 256) continue;
-                const uint64_t key = ((uint64_t)dist << 32) | (uint32_t)iF;
-                if (realIdxF < nL) top2_insert(key, l0, l1); else top2_insert(key, r0, r1);
-            }
-            shfl_top2(l0, l1);
-            shfl_top2(r0, r1);
-            const int bestDist1 = l0 == ~0ull ? 256 : (int)(l0 >> 32);
-            if (bestDist1 > TH_LOW) continue;
-            const int bestDist2 = l1 == ~0ull ? 256 : (int)(l1 >> 32);
-            if (lane == 0) {
-                if ((float)bestDist1 < A.nnratio * (float)bestDist2) {
-                    const int bestIdxF = A.f_fv.idx[(int)(l0 & 0xffffffffu)];
-                    bow_commit<true>(A, realIdxKF, bestIdxF, bestIdxF);
-                }
-                if (r0 != ~0ull && (int)(r0 >> 32) <= TH_LOW) {                  // ratio "|| true" (:412)
-                    const int bestIdxFR = A.f_fv.idx[(int)(r0 & 0xffffffffu)];
-                    bow_commit<true>(A, realIdxKF, bestIdxFR, bestIdxFR);
-                }
-            }
-            __threadfence();          // the next KeyFrame feature of this node must see match_f
-        }
-    }
-}
-
-int search_bow_fisheye_dev(eorb_ctx* c, const BowArgs& A, int nL)
-{
-    ProfScope ps(c, "search_bow_fisheye");
-    bow_init_kernel<<<(std::max(A.n_f, 32) + 255) / 256, 256, 0, c->stream>>>(A.match_f, A.bin_f, A.n_f, A.histo, A.nmatches, nullptr, 0);
-    if (A.kf_fv.nn > 0 && A.f_fv.nn > 0) {
-        const int blocks = std::min((A.kf_fv.nn + 3) / 4, 1024);
-        search_bow_fisheye_kernel<<<blocks, 256, 0, c->stream>>>(A, nL);
-        if (A.checkOri) search_bow_finish_kernel<<<1, 256, 0, c->stream>>>(A.match_f, A.bin_f, A.n_f, A.histo, A.nmatches);
-    }
-    EORB_LAUNCH_CHECK(c, "search_bow_fisheye kernels");
     return EORB_OK;
 }
 

@@ -32,7 +32,7 @@ struct ProjMapArgs {
 // DBoW2::FeatureVector as CSR, device resident: node ids ascending, off[nn + 1], feature indices
 struct FeatVec { const uint32_t* nodes; const int32_t* off; const int32_t* idx; int nn; };
 
-// SearchByBoW (match.hip search_bow_kernel, search_bow_fisheye_kernel)
+// SearchByBoW: the block of one pair (match.hip bow_node; bow_pair makes it from BowBatchArgs)
 struct BowArgs {
     const eorb_keypoint* kf_kps; const uint8_t* kf_desc; const uint8_t* kf_has_mp; FeatVec kf_fv;
     const eorb_keypoint* f_kps; int n_f; const uint8_t* f_desc; FeatVec f_fv;
@@ -50,27 +50,27 @@ struct TriArgs {
     int32_t* match12; int8_t* bin1; int32_t* histo; int32_t* nmatches;
 };
 
-// SearchForTriangulation with KannalaBrandt8::epipolarConstrain (match.hip search_tri_kb8_kernel); T.F is unused
+// SearchForTriangulation with KannalaBrandt8::epipolarConstrain (match.hip search_tri_kb8_batch_kernel); T.F is unused
 struct Pose12 { float v[12]; };              // R row-major, t
 
 struct TriKbArgs {
     TriArgs T;
-    int nleft1, nleft2;                             // numAllKPtsLeft(): both -1 (monocular) or both >= 0 (two cameras)
+    int nleft1;                                     // numAllKPtsLeft() of pKF1: -1 (monocular) or >= 0 (two cameras); pKF2_k's is TriKbPair::nleft2
     eorb_camera cam1[2], cam2[2];                   // mpCamera, mpCamera2 of pKF1 / pKF2
-    float Rt[48];                                   // ll, lr, rl, rr: R12 row-major then t12 (monocular: Rt[0..11])
     const float* sigma2_1;
 };
 
-// ---- the node walks over K keyframes per call (match.hip search_bow_batch_kernel, search_tri_batch_kernel, search_tri_kb8_batch_kernel) ----
+// ---- the node walks over K keyframes per call, a single pair being K = 1 (match.hip search_bow_batch_kernel, search_bow_fisheye_kernel,
+// search_tri_batch_kernel, search_tri_kb8_batch_kernel) ----
 // Keyframe k of the set: rows row0 .. row0 + nrows - 1 of the concatenated keypoints / descriptors / flags, nodes node0 .. node0 + nn - 1
 // of the concatenated node ids, its nn + 1 offsets from off0 and its feature indices from idx0 (offsets and indices relative to the
 // keyframe).  One record per pair in a device table that the kernels read with the wave-uniform pair index.
 struct KfSlice { int32_t row0, nrows, node0, nn, off0, idx0; };
 struct TriPair { float epx, epy, F[9]; };           // F unused by the KannalaBrandt8 walk
-struct TriKbPair { int32_t nleft2; float Rt[48]; };
+struct TriKbPair { int32_t nleft2; float Rt[48]; };   // ll, lr, rl, rr: R12 row-major then t12 (monocular: Rt[0..11])
 constexpr int kPairHist = 33;                       // per pair: 32 rotation bins, then nmatches
 
-// A = the block of the single walk with the shared side filled in and, on the set's side, the bases of the concatenated arrays;
+// A = the block of one pair with the shared side filled in and, on the set's side, the bases of the concatenated arrays;
 // match_f / match12 / bin_f hold K slices of n_out entries, histo K * kPairHist
 struct BowBatchArgs { BowArgs A; const KfSlice* kf; int K, n_out, max_nn; };
 struct TriBatchArgs { TriArgs T; const KfSlice* kf; const TriPair* pair; int K; };
@@ -135,13 +135,10 @@ int search_init_dev(eorb_ctx* c, int npairs,
                     int checkOri, int32_t* nmatches);
 int search_proj_last_dev(eorb_ctx* c, const ProjLastArgs& P);
 int search_proj_map_dev(eorb_ctx* c, const ProjMapArgs& P);
-// fisheye: the frame holds nL left features, then right ones; K: the KannalaBrandt8 walk (K->T is the block)
-int search_bow_dev(eorb_ctx* c, const BowArgs& A);
-int search_bow_fisheye_dev(eorb_ctx* c, const BowArgs& A, int nL);
-int search_tri_dev(eorb_ctx* c, const TriArgs& A, const TriKbArgs* K = nullptr);
-// the same walks over K pairs; scratch (keyframe-to-keyframe form): the vbMatched2 flags, one per row of the set
-int search_bow_batch_dev(eorb_ctx* c, const BowBatchArgs& B, int32_t* scratch, int nscratch);
-int search_tri_batch_dev(eorb_ctx* c, const TriBatchArgs& B, const TriKbBatchArgs* K = nullptr);
+// the node walks over K pairs; name: the profile scope of the entry point.  scratch (keyframe-to-keyframe form): the vbMatched2 flags, one
+// per row of the set; nL >= 0: the frame holds nL left features, then right ones; K: the KannalaBrandt8 walk (K->K.T is the block)
+int search_bow_batch_dev(eorb_ctx* c, const char* name, const BowBatchArgs& B, int32_t* scratch, int nscratch, int nL = -1);
+int search_tri_batch_dev(eorb_ctx* c, const char* name, const TriBatchArgs& B, const TriKbBatchArgs* K = nullptr);
 int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const eorb_keypoint* kps1,
                       const eorb_keypoint* kps2, int n, const float* sig1, const float* sig2, float* out);
 int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A);

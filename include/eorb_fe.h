@@ -412,7 +412,8 @@ int eorb_search_by_projection_last_fisheye(eorb_ctx* ctx,
 /* replaces the two-camera path of ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBmatcher.cc:276-478):
  * inputs as eorb_search_by_bow, frame features = nL left then the right ones (n_f in all).  Two best / second-best pairs, over
  * frame indices below nL and over the rest (:357-377); the right best is taken only inside "if(bestDist1 <= TH_LOW)" (:410) and
- * its ratio test always passes ("|| true", :412).  kf_kps in the KeyFrame's index order (its right keypoints after its left ones). */
+ * its ratio test always passes ("|| true", :412).  kf_kps in the KeyFrame's index order (its right keypoints after its left ones).
+ * The KeyFrame goes through the set form's path as a set of one (eorb_kf_set below): its checks and limits apply, as at eorb_search_by_bow. */
 int eorb_search_by_bow_fisheye(eorb_ctx* ctx,
         const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
         const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
@@ -522,7 +523,10 @@ int eorb_search_by_projection_kf_pose(eorb_ctx* ctx,
 
 /* replaces the mono branch of ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBmatcher.cc:276-478;
  * MixedMatcher.cpp:148-356).  DBoW2::FeatureVector as CSR (node ids ascending, offsets, feature indices in vector
- * order).  kf_has_mp[i] = map point present and !isBad().  match_f[n_f] out = KeyFrame feature index or -1. */
+ * order).  kf_has_mp[i] = map point present and !isBad().  match_f[n_f] out = KeyFrame feature index or -1.
+ * This is eorb_search_by_bow_keyframes with K = 1 (the KeyFrame as a set of one, a view of these arrays) and inherits its checks and
+ * limits: on either side node offsets start at 0 and never decrease and every feature index lies inside the side (EORB_E_ARG, match_f
+ * all -1 and *nmatches 0); 2^22 rows, outputs and feature indices (EORB_E_CAPACITY). */
 int eorb_search_by_bow(eorb_ctx* ctx,
         const eorb_keypoint* kf_kps, int n_kf, const uint8_t* kf_desc, const uint8_t* kf_has_mp,
         const uint32_t* kf_nodes, const int32_t* kf_node_off, const int32_t* kf_idx, int kf_nn,
@@ -531,7 +535,8 @@ int eorb_search_by_bow(eorb_ctx* ctx,
         int32_t* match_f, float nnratio, int checkOri, int* nmatches);
 
 /* replaces the mono branch of ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (src/ORBmatcher.cc:833-973; loop
- * closing / place recognition).  match12[n1] out = index of the pKF2 feature, or -1. */
+ * closing / place recognition).  match12[n1] out = index of the pKF2 feature, or -1.  This is
+ * eorb_search_by_bow_kf_keyframes with K = 1 (pKF2 as a set of one) and inherits its checks and limits, as eorb_search_by_bow does. */
 int eorb_search_by_bow_kf(eorb_ctx* ctx,
         const eorb_keypoint* kps1, int n1, const uint8_t* desc1, const uint8_t* has_mp1,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
@@ -546,7 +551,9 @@ int eorb_search_by_bow_kf(eorb_ctx* ctx,
  * Pinhole::epipolarConstrain rebuilds for every candidate (Pinhole.cpp:137-140).  scale2[l] = pKF2->getORBScaleFactor(l),
  * sigma2_2[l] = pKF2->getORBLevelSigma2(l).  match12[n1] out = vMatches12 (the caller forms vMatchedPairs, :1203-1211).
  * Rectified stereo: bit 1 of elig1[i] / elig2[i] set = the keypoint has a right coordinate (bStereo1 / bStereo2: mvuRight >= 0, :1051,
- * :1079): the epipole-distance test (:1093-1100) is skipped for a pair with such a keypoint; bOnlyStereo = clear bit 0 of the others. */
+ * :1079): the epipole-distance test (:1093-1100) is skipped for a pair with such a keypoint; bOnlyStereo = clear bit 0 of the others.
+ * This is eorb_search_for_triangulation_keyframes with K = 1 (pKF2 as a set of one, a view of these arrays with stride2 its stride) and
+ * inherits its checks and limits, as eorb_search_by_bow does. */
 int eorb_search_for_triangulation(eorb_ctx* ctx,
         const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
@@ -568,7 +575,8 @@ int eorb_search_for_triangulation(eorb_ctx* ctx,
  * two cameras) must be model 1, else EORB_E_CONFIG: a Pinhole pCamera1 is eorb_search_for_triangulation.  pCamera2 may be
  * either model.  sigma2_1 / sigma2_2 = getORBLevelSigma2 of pKF1 / pKF2 (both keyframes share nlevels); eligible keypoints of
  * both keyframes need an octave in [0, nlevels).  Outputs as eorb_search_for_triangulation: ties go to the last passing
- * candidate, the rotation histogram keeps its three maxima.  One upload, one wait, one download. */
+ * candidate, the rotation histogram keeps its three maxima.  One upload, one wait, one download.  This is
+ * eorb_search_for_triangulation_kb8_keyframes with K = 1 and inherits its checks and limits, as eorb_search_by_bow does. */
 int eorb_search_for_triangulation_kb8(eorb_ctx* ctx,
         const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
@@ -771,7 +779,9 @@ int eorb_fuse_keyframes_mixed(eorb_ctx* ctx, const eorb_view* views, const eorb_
  * (ascending within the keyframe); its nn_k + 1 per-node offsets are feat_off[node_off[k] + k ..] (the first is 0, relative to the
  * keyframe), so feat_off holds node_off[K] + K entries; its feature indices (relative to the keyframe's first row) follow those of
  * keyframe k-1 in idx.  A keyframe with no rows or no nodes is legal: its row is all -1 and its count 0, the others are unaffected.
- * Every check of the single forms is made per keyframe and the message names k.  Limits, decided from the sizes before any array is
+ * Every keyframe's feature vector is checked (offsets from 0 that never decrease, indices inside the keyframe's rows; eligible keypoints'
+ * octaves where they index a table) and the message names k; the single entry points are these with K = 1 and have no checks of the
+ * feature vectors of their own.  Limits, decided from the sizes before any array is
  * read: K <= 1024, K * n (n = the length of one output row) <= 2^22, then 2^22 rows in all; beyond them EORB_E_CAPACITY.  kf_off /
  * node_off that do not start at 0 or decrease: EORB_E_ARG. */
 typedef struct eorb_kf_set {

@@ -1,6 +1,7 @@
 """GPU parity of the node-walk matchers over K keyframes per call (eorb_search_for_triangulation_keyframes, its KannalaBrandt8 form,
 eorb_search_by_bow_keyframes, eorb_search_by_bow_kf_keyframes): row k of a batch is the oracle's single-pair function on pair k, as
-integers, with no tolerance.  Cases and oracle rows: tests/kfbatch_cases.py."""
+integers, with no tolerance.  Cases and oracle rows: tests/kfbatch_cases.py.  The single-pair entry points are the same path with K = 1:
+their checks, empty sides, strides and profile scopes are tested at the end."""
 import ctypes as C
 import os
 import sys
@@ -261,3 +262,155 @@ def test_errors_come_back_as_codes(fe, ctx):
     gn, gm = _tri_batch(fe, ctx, s, kfs, [0, 1, 2], False, False)
     on, om = kc.tri_rows("pinhole", 4, False, False)
     assert np.array_equal(gn, on[:3]) and np.array_equal(gm, om[:3])
+
+
+# ---- the single-pair entry points: the set form with K = 1 -------------------------------------------------------------------------
+def _fisheye_scene():
+    """the 32-keypoint two-camera frame (nL = 20) of test_gpu_twocam.py's empty-sides case against a KeyFrame made of its own rows with a
+    few bits flipped; four vocabulary nodes"""
+    rng = np.random.default_rng(71)
+    kps = synth.random_keypoints(32, 512, 512, nlevels=8, seed=72); desc = synth.random_descriptors(32, seed=73)
+    perm = rng.permutation(32)
+    kd = np.stack([synth.flip_bits(desc[i], 6, rng) for i in perm])
+    node = np.arange(32) % 4
+    return dict(kf=(kps[perm], kd, (rng.uniform(size=32) < 0.8).astype(np.uint8), synth.feature_vector_of(node[perm], rng)),
+                f=(kps, desc, np.ones(32, np.uint8), synth.feature_vector_of(node, rng)), nL=20)
+
+
+class _Single:
+    """One single-pair entry point on one small scene as a raw call: a side is (kps, desc, flag, fv); `set` is the side the entry point
+    wraps into a set of one (pKF2, or the KeyFrame of SearchByBoW(pKF, F)), `shared` the other, which owns the output row.  call()
+    -> (code, count, row) with the row prefilled with 7 and the count with -7."""
+
+    def __init__(self, name, oracle):
+        self.name = name
+        if name == "tri":
+            s = kc.tri_scene("pinhole_small")
+            self.expect = [r[0] for r in kc.tri_rows("pinhole_small", 4, False, True)]
+        elif name in ("tri_kb8", "tri_twocam"):
+            s = kc.tri_scene(name[4:], 3)
+            self.expect = [r[0] for r in kc.tri_rows(name[4:], 3, False, True)]
+        if name.startswith("tri"):
+            self.s = s
+            self.set, self.shared = kc.tri_set(s, [0])[0], (s["kps1"], s["desc1"], s["elig1"], s["fv1"])
+            self.nleft = (s["kfs"][0]["nleft"], s["nleft1"]) if "F12" not in s else None
+        elif name in ("bow", "bow_kf"):
+            s = kc.bow_scene("small")
+            self.set, self.shared = kc.bow_set(s, [0])[0], (s["kps"], s["desc"], s["has_mp"], s["fv"])
+            self.ratio = 0.8 if name == "bow_kf" else 0.7
+            self.expect = [r[0] for r in kc.bow_rows("small", 4, name == "bow_kf", self.ratio, True)]
+        else:
+            s = _fisheye_scene()
+            self.set, self.shared, self.nL = s["kf"], s["f"], s["nL"]
+            self.expect = oracle.search_by_bow_fisheye(*self.set, self.shared[0], self.nL, self.shared[1], self.shared[3], 0.7, True)
+
+    def call(self, fe, ctx, set_side, shared):
+        L, h, p = ctx.L, ctx.h, fe._p
+        keep = []                                           # the arrays the pointers refer to
+
+        def side(sd, with_stride):
+            kps, desc, flag, fv = sd
+            a = [np.ascontiguousarray(kps, synth.KP_DTYPE), np.ascontiguousarray(desc, np.uint8), np.ascontiguousarray(flag, np.uint8)] + fe._fv(fv)
+            keep.append(a)
+            k, d, f, n, o, i = a
+            stride = (int(d.shape[1]),) if with_stride else ()
+            return (p(k), len(k)), (p(d),) + stride + (p(f),), (p(n), p(o), p(i), len(n))
+        tri = self.name.startswith("tri")
+        (k2, d2, v2), (k1, d1, v1) = side(set_side, tri), side(shared, tri)
+        row = np.full(len(shared[0]), 7, np.int32); nm = C.c_int(-7)
+        tail = (p(row), C.byref(nm))
+        if tri:
+            s = self.s
+            f32 = lambda a: np.ascontiguousarray(a, np.float32)
+            ep, sc, sg = f32(s["ep"][0]), f32(s["scale2"]), f32(s["sigma2_2"])
+            if self.nleft is None:
+                F = f32(s["F12"][0]).reshape(9)
+                rc = L.eorb_search_for_triangulation(h, *k1, *d1, *v1, *k2, *d2, *v2, p(ep), p(F), p(sc), p(sg), len(sc), 0, 1, *tail)
+            else:
+                nl2, nl1 = (min(nl, len(sd[0])) for nl, sd in zip(self.nleft, (set_side, shared)))
+                rt = np.zeros(48, np.float32); r = f32(s["Rt"][0]).reshape(-1); rt[:len(r)] = r
+                c1, c2, s1 = fe._cams(s["cams1"]), fe._cams(s["cams2"]), f32(s["sigma2_1"])
+                rc = L.eorb_search_for_triangulation_kb8(h, *k1, nl1, *d1, *v1, *k2, nl2, *d2, *v2, C.byref(c1), C.byref(c2), p(rt), p(ep), p(sc),
+                                                         p(s1), p(sg), len(sg), 0, 1, *tail)
+        elif self.name == "bow":
+            rc = L.eorb_search_by_bow(h, *k2, *d2, *v2, *k1, d1[0], *v1, *tail[:1], self.ratio, 1, tail[1])
+        elif self.name == "bow_kf":
+            rc = L.eorb_search_by_bow_kf(h, *k1, *d1, *v1, *k2, *d2, *v2, *tail[:1], self.ratio, 1, tail[1])
+        else:
+            rc = L.eorb_search_by_bow_fisheye(h, *k2, *d2, *v2, *k1, min(self.nL, len(shared[0])), d1[0], *v1, *tail[:1], 0.7, 1, tail[1])
+        return rc, nm.value, row
+
+
+_SINGLES = ["tri", "tri_kb8", "tri_twocam", "bow", "bow_kf", "bow_fisheye"]
+
+
+def _broken_fvs(sd):
+    """the side with its feature vector broken in three ways: offsets that start at 1, an offset below its predecessor, an index equal to
+    the side's feature count"""
+    kps, desc, flag, (nodes, off, idx) = sd
+    assert len(nodes) >= 2 and off[1] >= 1
+    a = off.copy(); a[0] = 1
+    b = off.copy(); b[2] = off[1] - 1
+    c = idx.copy(); c[len(c) // 2] = len(kps)
+    return [(kps, desc, flag, fv) for fv in ((nodes, a, idx), (nodes, b, idx), (nodes, off, c))]
+
+
+@pytest.mark.parametrize("name", _SINGLES)
+def test_single_forms_refuse_malformed_feature_vectors(oracle, fe, ctx, name):
+    """offsets that do not start at 0 or decrease and an index past the side's features, on either side of each of the five single-pair
+    entry points (the KannalaBrandt8 one on monocular and on two-camera keyframes): EORB_E_ARG with the row all -1 and the count 0, and
+    the context then gives the oracle's result for the intact scene"""
+    e = _Single(name, oracle)
+    for bad in _broken_fvs(e.set):
+        rc, n, row = e.call(fe, ctx, bad, e.shared)
+        assert rc == E_ARG and n == 0 and (row == -1).all(), (rc, n)
+    for bad in _broken_fvs(e.shared):
+        rc, n, row = e.call(fe, ctx, e.set, bad)
+        assert rc == E_ARG and n == 0 and (row == -1).all(), (rc, n)
+    rc, n, row = e.call(fe, ctx, e.set, e.shared)
+    print(name, "oracle", e.expect[0], "gpu", n)
+    assert rc == 0 and n == e.expect[0] and np.array_equal(row, e.expect[1])
+
+
+@pytest.mark.parametrize("name", _SINGLES)
+def test_single_forms_on_empty_sides(oracle, fe, ctx, name):
+    """no rows on the set's side, rows without nodes there, no rows on the shared side: EORB_OK, count 0, every slot -1"""
+    e = _Single(name, oracle)
+    stride = e.set[1].shape[1]
+    for set_side, shared in ((_empty_kf(stride), e.shared), (e.set[:3] + (_EMPTY_FV,), e.shared), (e.set, _empty_kf(stride))):
+        rc, n, row = e.call(fe, ctx, set_side, shared)
+        assert rc == 0 and n == 0 and len(row) == len(shared[0]) and (row == -1).all(), (rc, n)
+
+
+def test_triangulation_pair_with_unequal_strides(oracle, fe, ctx):
+    """stride1 = 32 against stride2 = 61 and the reverse (padding: random bytes): the set carries pKF2's stride and pKF1 its own"""
+    s = kc.tri_scene("pinhole_small")
+    kf = s["kfs"][0]
+    on, om = (r[0] for r in kc.tri_rows("pinhole_small", 4, False, True))
+    assert on >= 20
+    rng = np.random.default_rng(9)
+    pad = lambda d: np.concatenate([d, rng.integers(0, 256, (len(d), 29), dtype=np.uint8)], axis=1)
+    for d1, d2 in ((s["desc1"], pad(kf["desc"])), (pad(s["desc1"]), kf["desc"])):
+        assert {d1.shape[1], d2.shape[1]} == {32, 61}
+        gn, pairs = fe.SearchForTriangulation(s["kps1"], d1, s["elig1"], s["fv1"], kf["kps"], d2, kf["elig"], kf["fv"], s["ep"][0], s["F12"][0],
+                                              s["scale2"], s["sigma2_2"], False, True, ctx=ctx)
+        ok = np.nonzero(om >= 0)[0]
+        assert gn == on and np.array_equal(pairs, np.stack([ok, om[ok]], axis=1))
+
+
+def test_profile_scopes_keep_the_entry_points_names(oracle, fe, ctx):
+    """one call of each single-pair entry point and one set call, profiled: the single calls are recorded under their own scopes (both
+    SearchByBoW forms under search_bow), the set call under its own, each once per call"""
+    ctx.prof_enable(True)
+    try:
+        ctx.prof_reset()
+        for name in ("tri", "tri_kb8", "bow", "bow_kf", "bow_fisheye"):
+            e = _Single(name, oracle)
+            assert e.call(fe, ctx, e.set, e.shared)[0] == 0
+        b = kc.bow_scene("small")
+        fe.SearchByBoWKeyFrames(kc.bow_set(b), b["kps"], b["desc"], b["fv"], 0.7, True, ctx=ctx)
+        got = {k: v[1] for k, v in ctx.prof_results().items()}
+    finally:
+        ctx.prof_enable(False)
+    assert got == {"search_for_triangulation": 1, "search_for_triangulation_kb8": 1, "search_bow": 2, "search_bow_fisheye": 1,
+                   "search_by_bow_keyframes": 1}, got

@@ -703,7 +703,7 @@ def _node_of(fv, n):
 
 @pytest.mark.parametrize("ori", [True, False])
 def test_search_by_bow_node_sizes(oracle, fe, ctx, ori):
-    """Both paths of search_bow_kernel: a node with at most 64 features on either side is matched in registers, any other one
+    """Both paths of the BoW walk (bow_node): a node with at most 64 features on either side is matched in registers, any other one
     through match_f in global memory.  Seven nodes, capped (KeyFrame side, frame side) to sit on both sides of that limit."""
     k1, d1, k2, d2 = _two_frames(oracle, seed=41, shift=2)
     rng = np.random.default_rng(5)

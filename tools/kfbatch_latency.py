@@ -8,14 +8,17 @@ K single calls they replace.  346 x 260, about 1 000 rows per keyframe, K = 1, 8
   bow_kf    eorb_search_by_bow_kf_keyframes              vs K x eorb_search_by_bow_kf               (LoopClosing::DetectCommonRegionsFromBoW)
 
     batched        the one call for the K keyframes
-    single_loop    K single calls on this library
+    single_loop    K single calls on this library.  A single call is the set form with K = 1 (one marshalling path, one kernel per walk), so
+                   at K = 1 batched and single_loop time the same code and differ by the Python wrappers only
     oracle_1core   K calls of the oracle's timing build (-O3 -march=native) on one core of the same host
     parent_loop    K single calls on the parent commit, measured by a child process of this tool in the same visit: --parent-root names a
                    checkout of the parent with its library built (git worktree add DIR HEAD~1 && make -C DIR/eorb_slam_amd/csrc); the
                    child imports the package from there and the scenes from this tree.  The yardstick for the batch.
     alone_loop     K single calls on this library, alone in a child process like parent_loop.  The children run in the order parent, this
                    tree, parent, this tree (parent_loop, alone_loop, parent_loop_2, alone_loop_2): whether the single entry points moved
-                   is read off these four, not off single_loop, which shares its process and its loop with the batch.
+                   is read off these four, not off single_loop, which shares its process and its loop with the batch.  single_vs_parent
+                   states the comparison: the better p50 of the two alone runs against the worse p50 of the two parent runs plus the
+                   margin, the larger of the two differences between the runs of one library.
 
 batched and single_loop take turns inside one loop, so that a drift of the clocks or of the shared host touches them alike.  Prints one JSON
 object (and writes it to --out)."""
@@ -186,6 +189,9 @@ def main():
         runs = [child(r) for r in (a.parent_root, ROOT, a.parent_root, ROOT)]
         for key, e in res["shapes"].items():
             e["parent_loop"], e["alone_loop"], e["parent_loop_2"], e["alone_loop_2"] = [r[key]["single_loop"] for r in runs]
+            pp, aa = [e[k]["p50_ms"] for k in ("parent_loop", "parent_loop_2")], [e[k]["p50_ms"] for k in ("alone_loop", "alone_loop_2")]
+            margin = max(abs(pp[0] - pp[1]), abs(aa[0] - aa[1]))
+            e["single_vs_parent"] = {"alone_best_ms": min(aa), "parent_worst_ms": max(pp), "margin_ms": margin, "no_slower": bool(min(aa) <= max(pp) + margin)}
             e["batched_beats_parent_loop"] = bool(e["batched"]["p50_ms"] < min(e["parent_loop"]["p50_ms"], e["parent_loop_2"]["p50_ms"]))
     line = json.dumps(res)
     print(line)
