@@ -2593,6 +2593,42 @@ static const uint8_t* kf_mixed_kp(const Arena& A, const KfMixedIn* mx, const KfM
 static const float* kf_mixed_sigma(const Arena& A, const KfMixedIn* mx, const KfMixedOff& o) { return mx && mx->kp_inv_sigma2 ? A.dev<float>(o.sig) : nullptr; }
 static const uint8_t* kf_mixed_mp(const Arena& A, const KfMixedIn* mx, const KfMixedOff& o) { return mx && mx->mp_is_orb ? A.dev<uint8_t>(o.mio) : nullptr; }
 
+// ---- the searched side of the KeyFrame-side radius search (match.hip kf_radius_dev): the keypoints of K keyframes concatenated, keyframe k
+// = rows kf_off[k] .. kf_off[k + 1] - 1 with grid bounds gb[k]; one keyframe is K = 1 with kf_off = {0, n} ----
+struct KfSearched { size_t k, d, ur, off, g, tk, cell; int K, ntotal, stride; bool has_ur, has_tk; std::vector<GridB> gv; };
+// its inputs; taken (the in-order form, in / out) comes last, so that a call's outputs can follow it.  kf_off stays the caller's until upload()
+static void kf_searched_in(Arena& A, KfSearched& S, int K, const eorb_keypoint* kps, const uint8_t* desc, int stride, const float* uright,
+                           const int32_t* kf_off, const eorb_grid_bounds* gb, const uint8_t* taken)
+{
+    const size_t n = (size_t)kf_off[K];
+    S.K = K; S.ntotal = kf_off[K]; S.stride = stride; S.has_ur = uright != nullptr; S.has_tk = taken != nullptr;
+    S.gv.resize(K);
+    for (int k = 0; k < K; k++) S.gv[k] = grid_b(gb[k]);
+    S.g = A.in(S.gv.data(), sizeof(GridB) * (size_t)K); S.off = A.in(kf_off, sizeof(int32_t) * ((size_t)K + 1));
+    S.k = A.in(kps, sizeof(eorb_keypoint) * n); S.d = A.in(desc, (size_t)stride * n);
+    S.ur = A.in(uright, uright ? sizeof(float) * n : 0);
+    S.tk = A.in(taken, taken ? n : 0);
+}
+// the keypoints' cells: device only, behind the call's outputs
+static void kf_searched_cells(Arena& A, KfSearched& S) { S.cell = A.reserve(sizeof(uint16_t) * (size_t)S.ntotal); }
+// the block of the search: the searched side, the K * M queries Q (the projector's arrays or uploaded ones) and their descriptors
+static RadBatchArgsMixed kf_searched_args(const Arena& A, const KfSearched& S, int M, const KfSideDev& Q, const uint8_t* d_q_desc, size_t q_desc_kstride,
+                                          const float* d_inv_sigma2, int nlevels, float accept_thr, int32_t* d_best_idx, int32_t* d_best_dist,
+                                          const KfMixedIn* mx, const KfMixedOff& mo)
+{
+    RadBatchArgsMixed B{};
+    B.kps = A.dev<eorb_keypoint>(S.k); B.desc = A.dev<uint8_t>(S.d); B.stride = S.stride; B.cell = A.dev<uint16_t>(S.cell);
+    B.uright = S.has_ur ? A.dev<float>(S.ur) : nullptr;
+    B.kf_off = A.dev<int32_t>(S.off); B.g = A.dev<GridB>(S.g); B.K = S.K; B.M = M;
+    B.valid = Q.valid; B.uv = (const float*)Q.uv; B.radius = Q.radius; B.level = Q.level; B.q_ur = Q.q_ur;
+    B.q_desc = d_q_desc; B.q_desc_kstride = q_desc_kstride;
+    B.inv_sigma2 = d_inv_sigma2; B.nlevels = nlevels;
+    B.taken = S.has_tk ? A.dev<uint8_t>(S.tk) : nullptr; B.accept_thr = accept_thr;
+    B.best_idx = d_best_idx; B.best_dist = d_best_dist;
+    B.mp_is_orb = kf_mixed_mp(A, mx, mo); B.kp_inv_sigma2 = kf_mixed_sigma(A, mx, mo);
+    return B;
+}
+
 static int kf_radius_common(eorb_ctx* c,
         const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
         int M, const uint8_t* valid, const float* uv, const float* radius, const int32_t* level, const uint8_t* q_desc,
@@ -2610,28 +2646,21 @@ static int kf_radius_common(eorb_ctx* c,
     if (M == 0 || n == 0) return EORB_OK;
     int rc;
     Arena A(c);
-    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * n), o_d = A.in(desc, (size_t)stride * n);
+    const int32_t off[2] = {0, n};
     const size_t o_uv = A.in(uv, sizeof(float) * 2 * (size_t)M), o_rad = A.in(radius, sizeof(float) * M), o_lv = A.in(level, sizeof(int32_t) * M);
     const size_t o_va = A.in(valid, M), o_qd = A.in(q_desc, 32 * (size_t)M);
-    const size_t o_is = A.in(inv_sigma2, inv_sigma2 ? sizeof(float) * nlevels : 0);
-    const size_t o_ur = A.in(uright, uright ? sizeof(float) * n : 0), o_qur = A.in(q_ur, q_ur ? sizeof(float) * M : 0);
+    const size_t o_is = A.in(inv_sigma2, inv_sigma2 ? sizeof(float) * nlevels : 0), o_qur = A.in(q_ur, q_ur ? sizeof(float) * M : 0);
     const KfMixedOff mo = kf_mixed_in(A, mx, (size_t)n, (size_t)M);
+    KfSearched S;
+    kf_searched_in(A, S, 1, kps, desc, stride, uright, off, gb, taken);
     // outputs, contiguous: taken (in / out) | best index | best distance; then the keypoints' cells
-    const size_t o_tk = A.in(taken, taken ? (size_t)n : 0);
-    const size_t o_bi = A.reserve(sizeof(int32_t) * M), o_bd = A.reserve(sizeof(int32_t) * M), o_cell = A.reserve(sizeof(uint16_t) * n);
+    const size_t o_tk = S.tk, o_bi = A.reserve(sizeof(int32_t) * M), o_bd = A.reserve(sizeof(int32_t) * M);
+    kf_searched_cells(A, S);
     if ((rc = A.upload())) return rc;
-    RadArgsMixed R{};
-    R.kps = A.dev<eorb_keypoint>(o_k); R.n = n; R.desc = A.dev<uint8_t>(o_d); R.stride = stride;
-    R.g = grid_b(*gb);
-    R.cell = A.dev<uint16_t>(o_cell);
-    R.M = M; R.valid = A.dev<uint8_t>(o_va); R.uv = A.dev<float>(o_uv);
-    R.radius = A.dev<float>(o_rad); R.level = A.dev<int32_t>(o_lv); R.q_desc = A.dev<uint8_t>(o_qd);
-    R.inv_sigma2 = inv_sigma2 ? A.dev<float>(o_is) : nullptr; R.nlevels = nlevels;
-    R.uright = uright ? A.dev<float>(o_ur) : nullptr; R.q_ur = uright ? A.dev<float>(o_qur) : nullptr;
-    R.taken = taken ? A.dev<uint8_t>(o_tk) : nullptr; R.accept_thr = accept_thr;
-    R.best_idx = A.dev<int32_t>(o_bi); R.best_dist = A.dev<int32_t>(o_bd);
-    R.mp_is_orb = kf_mixed_mp(A, mx, mo); R.kp_inv_sigma2 = kf_mixed_sigma(A, mx, mo);
-    if ((rc = mx ? kf_radius_mixed_dev(c, R, A.dev<uint16_t>(o_cell), kf_mixed_kp(A, mx, mo)) : kf_radius_dev(c, R, A.dev<uint16_t>(o_cell)))) return rc;
+    const KfSideDev Q{A.dev<uint8_t>(o_va), A.dev<float2>(o_uv), A.dev<int32_t>(o_lv), A.dev<float>(o_rad), A.dev<float>(o_qur), nullptr, nullptr};
+    const RadBatchArgsMixed B = kf_searched_args(A, S, M, Q, A.dev<uint8_t>(o_qd), 0, inv_sigma2 ? A.dev<float>(o_is) : nullptr, nlevels, accept_thr,
+                                                 A.dev<int32_t>(o_bi), A.dev<int32_t>(o_bd), mx, mo);
+    if ((rc = kf_radius_dev(c, mx ? "kf_radius_match_mixed" : "kf_radius_match", mx != nullptr, B, n, kf_mixed_kp(A, mx, mo)))) return rc;
     const size_t first = taken ? o_tk : o_bi;
     const char* h;
     if ((rc = A.download(first, o_bd + sizeof(int32_t) * M - first, &h))) return rc;
@@ -2802,12 +2831,14 @@ int eorb_project_keyframe_side_mixed(eorb_ctx* c, const eorb_view* view, int M, 
     return project_kfside_common(c, "project_keyframe_side_mixed", view, M, pos, normal, min_dist, max_dist, skip, th, out, &mx);
 }
 
-// mode D over K keyframes, then the batched radius match; shared by eorb_fuse_pose (K = 1) and eorb_fuse_keyframes
+// mode D over K keyframes, then the radius search; shared by eorb_fuse_pose (K = 1), eorb_fuse_keyframes and, with seq, by
+// eorb_search_by_projection_kf_scw (K = 1: the queries in order, vpMatched = taken in and out, no reprojection gate)
+struct KfInOrder { uint8_t* taken; float accept_thr; };
 static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, const eorb_grid_bounds* gb, int K,
                        const eorb_keypoint* kps, const uint8_t* desc, int stride, const float* uright, const int32_t* kf_off,
                        int M, const float* pos, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* q_desc,
                        const uint8_t* skip, const float* inv_sigma2, float th, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out,
-                       const KfMixedIn* mx = nullptr)
+                       const KfMixedIn* mx = nullptr, const KfInOrder* seq = nullptr)
 {
     int rc;
     if (K > kKfSideMaxKfs || (K > 0 && M > 0 && (int64_t)K * M > kKfSideMaxQueries))      // (sizes only: nothing is read before this)
@@ -2831,35 +2862,28 @@ static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, con
     Arena A(c);
     KfSideIn I;
     kfside_in(A, I, views, K, M, pos, normal, min_dist, max_dist, skip, mx, (size_t)ntotal);
-    std::vector<GridB> g(K);
-    for (int k = 0; k < K; k++) g[k] = grid_b(gb[k]);
-    const size_t o_g = A.in(g.data(), sizeof(GridB) * (size_t)K), o_off = A.in(kf_off, sizeof(int32_t) * ((size_t)K + 1));
-    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)ntotal), o_d = A.in(desc, (size_t)stride * ntotal);
-    const size_t o_ur = A.in(uright, uright ? sizeof(float) * (size_t)ntotal : 0);
     const size_t o_qd = A.in(q_desc, 32 * (size_t)M);
     const size_t o_is = A.in(inv_sigma2, inv_sigma2 ? sizeof(float) * (size_t)views[0].nlevels : 0);
-    // outputs, contiguous: best index | best distance | the projector's arrays; then the keypoints' cells
+    uint8_t* taken = seq ? seq->taken : nullptr;
+    KfSearched S;
+    kf_searched_in(A, S, K, kps, desc, stride, uright, kf_off, gb, taken);
+    // outputs, contiguous: taken (in / out, the in-order form) | best index | best distance | the projector's arrays; then the keypoints' cells
     const size_t o_bi = A.reserve(4 * nq), o_bd = A.reserve(4 * nq), o_bend = A.total;
     const KfSideOff o = kfside_reserve(A, nq);
-    const size_t o_cell = A.reserve(sizeof(uint16_t) * (size_t)ntotal);
+    kf_searched_cells(A, S);
     if ((rc = A.upload())) return rc;
     const KfSideArgsMixed P = kfside_args(A, I, views, K, M, skip != nullptr, th, o, mx);
     if ((rc = mx ? project_kfside_mixed_dev(c, P) : project_kfside_dev(c, P))) return rc;
-    RadBatchArgsMixed B{};
-    B.kps = A.dev<eorb_keypoint>(o_k); B.desc = A.dev<uint8_t>(o_d); B.stride = stride; B.cell = A.dev<uint16_t>(o_cell);
-    B.uright = uright ? A.dev<float>(o_ur) : nullptr;
-    B.kf_off = A.dev<int32_t>(o_off); B.g = A.dev<GridB>(o_g); B.K = K; B.M = M;
-    B.valid = P.O.valid; B.uv = (const float*)P.O.uv; B.radius = P.O.radius; B.level = P.O.level; B.q_ur = P.O.q_ur;
-    B.q_desc = A.dev<uint8_t>(o_qd); B.q_desc_kstride = 0;
-    B.inv_sigma2 = inv_sigma2 ? A.dev<float>(o_is) : nullptr; B.nlevels = views[0].nlevels;
-    B.best_idx = A.dev<int32_t>(o_bi); B.best_dist = A.dev<int32_t>(o_bd);
-    B.mp_is_orb = P.mp_is_orb; B.kp_inv_sigma2 = kf_mixed_sigma(A, mx, I.mo);
-    if ((rc = mx ? kf_radius_batch_mixed_dev(c, B, ntotal, A.dev<uint16_t>(o_cell), kf_mixed_kp(A, mx, I.mo))
-                 : kf_radius_batch_dev(c, B, ntotal, A.dev<uint16_t>(o_cell)))) return rc;
+    const RadBatchArgsMixed B = kf_searched_args(A, S, M, P.O, A.dev<uint8_t>(o_qd), 0, inv_sigma2 ? A.dev<float>(o_is) : nullptr, views[0].nlevels,
+                                                 seq ? seq->accept_thr : 0.f, A.dev<int32_t>(o_bi), A.dev<int32_t>(o_bd), mx, I.mo);
+    const char* scope = seq ? (mx ? "kf_radius_match_mixed" : "kf_radius_match") : (mx ? "kf_radius_batch_mixed" : "kf_radius_batch");
+    if ((rc = kf_radius_dev(c, scope, mx != nullptr, B, ntotal, kf_mixed_kp(A, mx, I.mo)))) return rc;
+    const size_t first = taken ? S.tk : o_bi;
     const char* h;
-    if ((rc = A.download(o_bi, kfside_end(o, out, o_bend) - o_bi, &h))) return rc;
+    if ((rc = A.download(first, kfside_end(o, out, o_bend) - first, &h))) return rc;
     memcpy(best_idx, h + o_bi, 4 * nq);
     memcpy(best_dist, h + o_bd, 4 * nq);
+    if (taken) memcpy(taken, h + S.tk, (size_t)ntotal);
     kfside_copy_out(h, o, nq, out);
     return EORB_OK;
 }
@@ -2916,48 +2940,12 @@ int eorb_fuse_keyframes_mixed(eorb_ctx* c, const eorb_view* views, const eorb_gr
                        nullptr, th, best_idx, best_dist, reason ? &out : nullptr, &mx);
 }
 
-static int kf_scw_common(eorb_ctx* c, const char* who, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
-                         const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
-                         const float* max_dist, const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken,
-                         float accept_thr, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out, const KfMixedIn* mx)
+// SearchByProjection(pKF, Scw): fuse_common at K = 1 in order; the entry points' own checks come first (no inv_sigma2, no uright)
+static int kf_scw_check(eorb_ctx* c, const char* who, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
+                        const eorb_view* view, int M, const uint8_t* q_desc, const uint8_t* taken, const int32_t* best_idx, const int32_t* best_dist)
 {
-    if (!c) return EORB_E_ARG;
-    int rc;
     if (n < 0 || !view || !gb || stride < 32 || (n > 0 && (!kps || !desc || !taken)) || (M > 0 && (!q_desc || !best_idx || !best_dist)))
         return set_err(c, EORB_E_ARG, "%s: bad arguments", who);
-    if ((rc = kfside_check(c, who, view, 1, M, pos, normal, min_dist, max_dist))) return rc;
-    if (M > kKfSideMaxQueries) return set_err(c, EORB_E_CAPACITY, "%s: %d map points exceed %lld", who, M, (long long)kKfSideMaxQueries);
-    fe_enter(c);
-    for (int m = 0; m < M; m++) { best_idx[m] = -1; best_dist[m] = 256; }
-    if (M == 0) return EORB_OK;
-    const size_t nq = (size_t)M;
-    Arena A(c);
-    KfSideIn I;
-    kfside_in(A, I, view, 1, M, pos, normal, min_dist, max_dist, skip, mx, (size_t)n);
-    const size_t o_k = A.in(kps, sizeof(eorb_keypoint) * (size_t)n), o_d = A.in(desc, (size_t)stride * n);
-    const size_t o_qd = A.in(q_desc, 32 * nq);
-    // outputs, contiguous: taken (in / out) | best index | best distance | the projector's arrays; then the keypoints' cells
-    const size_t o_tk = A.in(taken, (size_t)n);
-    const size_t o_bi = A.reserve(4 * nq), o_bd = A.reserve(4 * nq), o_bend = A.total;
-    const KfSideOff o = kfside_reserve(A, nq);
-    const size_t o_cell = A.reserve(sizeof(uint16_t) * (size_t)n);
-    if ((rc = A.upload())) return rc;
-    const KfSideArgsMixed P = kfside_args(A, I, view, 1, M, skip != nullptr, th, o, mx);
-    if ((rc = mx ? project_kfside_mixed_dev(c, P) : project_kfside_dev(c, P))) return rc;
-    RadArgsMixed R{};
-    R.kps = A.dev<eorb_keypoint>(o_k); R.n = n; R.desc = A.dev<uint8_t>(o_d); R.stride = stride;
-    R.g = grid_b(*gb); R.cell = A.dev<uint16_t>(o_cell);
-    R.M = M; R.valid = P.O.valid; R.uv = (const float*)P.O.uv; R.radius = P.O.radius; R.level = P.O.level; R.q_desc = A.dev<uint8_t>(o_qd);
-    R.taken = A.dev<uint8_t>(o_tk); R.accept_thr = accept_thr;
-    R.best_idx = A.dev<int32_t>(o_bi); R.best_dist = A.dev<int32_t>(o_bd);
-    R.mp_is_orb = P.mp_is_orb;
-    if ((rc = mx ? kf_radius_mixed_dev(c, R, A.dev<uint16_t>(o_cell), kf_mixed_kp(A, mx, I.mo)) : kf_radius_dev(c, R, A.dev<uint16_t>(o_cell)))) return rc;
-    const char* h;
-    if ((rc = A.download(o_tk, kfside_end(o, out, o_bend) - o_tk, &h))) return rc;
-    memcpy(best_idx, h + o_bi, 4 * nq);
-    memcpy(best_dist, h + o_bd, 4 * nq);
-    if (n > 0) memcpy(taken, h + o_tk, (size_t)n);
-    kfside_copy_out(h, o, nq, out);
     return EORB_OK;
 }
 
@@ -2966,8 +2954,14 @@ int eorb_search_by_projection_kf_scw(eorb_ctx* c, const eorb_keypoint* kps, int 
                                      const float* max_dist, const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken,
                                      float accept_thr, int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
 {
-    return kf_scw_common(c, "search_by_projection_kf_scw", kps, n, desc, stride, gb, view, M, pos, normal, min_dist, max_dist, skip, q_desc, th,
-                         taken, accept_thr, best_idx, best_dist, out, nullptr);
+    if (!c) return EORB_E_ARG;
+    const char* who = "search_by_projection_kf_scw";
+    int rc;
+    if ((rc = kf_scw_check(c, who, kps, n, desc, stride, gb, view, M, q_desc, taken, best_idx, best_dist))) return rc;
+    const int32_t off[2] = {0, n};
+    const KfInOrder seq{taken, accept_thr};
+    return fuse_common(c, who, view, gb, 1, kps, desc, stride, nullptr, off, M, pos, normal, min_dist, max_dist, q_desc, skip, nullptr, th,
+                       best_idx, best_dist, out, nullptr, &seq);
 }
 
 int eorb_search_by_projection_kf_scw_mixed(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride,
@@ -2976,9 +2970,15 @@ int eorb_search_by_projection_kf_scw_mixed(eorb_ctx* c, const eorb_keypoint* kps
                                            const uint8_t* skip, const uint8_t* q_desc, float th, uint8_t* taken, float accept_thr,
                                            int32_t* best_idx, int32_t* best_dist, const eorb_kfside_out* out)
 {
+    if (!c) return EORB_E_ARG;
+    const char* who = "search_by_projection_kf_scw_mixed";
+    int rc;
+    if ((rc = kf_scw_check(c, who, kps, n, desc, stride, gb, view, M, q_desc, taken, best_idx, best_dist))) return rc;
+    const int32_t off[2] = {0, n};
     const KfMixedIn mx{kp_is_orb, nullptr, mp_is_orb};
-    return kf_scw_common(c, "search_by_projection_kf_scw_mixed", kps, n, desc, stride, gb, view, M, pos, normal, min_dist, max_dist, skip, q_desc,
-                         th, taken, accept_thr, best_idx, best_dist, out, &mx);
+    const KfInOrder seq{taken, accept_thr};
+    return fuse_common(c, who, view, gb, 1, kps, desc, stride, nullptr, off, M, pos, normal, min_dist, max_dist, q_desc, skip, nullptr, th,
+                       best_idx, best_dist, out, &mx, &seq);
 }
 
 int eorb_search_by_sim3(eorb_ctx* c,
@@ -3015,10 +3015,11 @@ int eorb_search_by_sim3(eorb_ctx* c,
     for (int i = 0; i < n1; i++) memcpy(&dcat[32 * ((size_t)n2 + i)], desc1 + (size_t)i * stride1, 32);
     memcpy(qd.data(), mp_desc1, 32 * (size_t)n1); memcpy(qd.data() + 32 * m, mp_desc2, 32 * (size_t)n2);
     const int32_t off[3] = {0, n2, ntotal};
-    const GridB g[2] = {grid_b(*gb2), grid_b(*gb1)};
+    const eorb_grid_bounds gb[2] = {*gb2, *gb1};
     Arena A(c);
-    const size_t o_k = A.in(kcat.data(), sizeof(eorb_keypoint) * (size_t)ntotal), o_d = A.in(dcat.data(), dcat.size()), o_qd = A.in(qd.data(), qd.size());
-    const size_t o_off = A.in(off, sizeof(off)), o_g = A.in(g, sizeof(g));
+    KfSearched R;
+    kf_searched_in(A, R, 2, kcat.data(), dcat.data(), 32, nullptr, off, gb, nullptr);
+    const size_t o_qd = A.in(qd.data(), qd.size());
     const size_t o_p1 = A.in(pos1, 12 * (size_t)n1), o_mn1 = A.in(min_dist1, 4 * (size_t)n1), o_mx1 = A.in(max_dist1, 4 * (size_t)n1);
     const size_t o_p2 = A.in(pos2, 12 * (size_t)n2), o_mn2 = A.in(min_dist2, 4 * (size_t)n2), o_mx2 = A.in(max_dist2, 4 * (size_t)n2);
     const size_t o_s1 = A.in(skip1, skip1 ? (size_t)n1 : 0), o_s2 = A.in(skip2, skip2 ? (size_t)n2 : 0);
@@ -3029,7 +3030,7 @@ int eorb_search_by_sim3(eorb_ctx* c,
     const size_t o_end = A.total;
     const size_t o_bi = A.reserve(8 * m), o_bd = A.reserve(8 * m);
     const KfSideOff o = kfside_reserve(A, 2 * m);
-    const size_t o_cell = A.reserve(sizeof(uint16_t) * (size_t)ntotal);
+    kf_searched_cells(A, R);
     if ((rc = A.upload())) return rc;
     Sim3Args S{};
     S.M = M; S.th = th; S.O = kfside_dev(A, o);
@@ -3046,13 +3047,9 @@ int eorb_search_by_sim3(eorb_ctx* c,
         H.skip = (hf ? skip2 : skip1) ? A.dev<uint8_t>(hf ? o_s2 : o_s1) : nullptr;
     }
     if ((rc = project_sim3_dev(c, S))) return rc;
-    RadBatchArgs B{};
-    B.kps = A.dev<eorb_keypoint>(o_k); B.desc = A.dev<uint8_t>(o_d); B.stride = 32; B.cell = A.dev<uint16_t>(o_cell);
-    B.kf_off = A.dev<int32_t>(o_off); B.g = A.dev<GridB>(o_g); B.K = 2; B.M = M;
-    B.valid = S.O.valid; B.uv = (const float*)S.O.uv; B.radius = S.O.radius; B.level = S.O.level; B.q_ur = S.O.q_ur;
-    B.q_desc = A.dev<uint8_t>(o_qd); B.q_desc_kstride = 32 * m;
-    B.best_idx = A.dev<int32_t>(o_bi); B.best_dist = A.dev<int32_t>(o_bd);
-    if ((rc = kf_radius_batch_dev(c, B, ntotal, A.dev<uint16_t>(o_cell)))) return rc;
+    const RadBatchArgsMixed B = kf_searched_args(A, R, M, S.O, A.dev<uint8_t>(o_qd), 32 * m, nullptr, 0, 0.f, A.dev<int32_t>(o_bi), A.dev<int32_t>(o_bd),
+                                                 nullptr, KfMixedOff{});
+    if ((rc = kf_radius_dev(c, "kf_radius_batch", false, B, ntotal, nullptr))) return rc;
     if ((rc = sim3_agree_dev(c, B.best_idx, B.best_dist, M, n1, n2, th_high, A.dev<int32_t>(o_v1), A.dev<int32_t>(o_v2), A.dev<int32_t>(o_m12),
                              A.dev<int32_t>(o_nf)))) return rc;
     const char* h;

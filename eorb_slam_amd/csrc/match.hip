@@ -1507,19 +1507,10 @@ int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* c
 // search core of ORBmatcher::Fuse (:1512-1578, :1700-1720), SearchBySim3 (:1829-1860, :1909-1940) and
 // SearchByProjection(KeyFrame*, Scw, ...) (:548-588): best keypoint (least distance, first in GetFeaturesInArea order) with
 // octave in [L-1, L] inside the radius.  SEQ = false: queries independent, one wave each.  SEQ = true (vpMatched feeds later
-// queries): one workgroup walks the queries in order.
+// queries): one workgroup walks the queries in order.  Both read RadBatchArgs: the keyframes' keypoints concatenated (kf_off[K + 1]),
+// query (k, m) at entry k * M + m of the query arrays; a single keyframe is K = 1.
 
-__global__ void kf_cells_kernel(const eorb_keypoint* __restrict__ kps, int n, GridB g, uint16_t* __restrict__ cell)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int px = (int)roundf((kps[i].x - g.minX) * g.invW);
-    const int py = (int)roundf((kps[i].y - g.minY) * g.invH);
-    cell[i] = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? (uint16_t)0xFFFF : (uint16_t)(px * kGridRows + py);
-}
-
-// the mixed forms' cell word: Frame::PosInGrid as the 12-bit cell number ix*48+iy (64 x 48 = 3072 cells), 0xFFFF outside the grid, as
-// kf_cells_kernel writes it
+// the cell word: Frame::PosInGrid as the 12-bit cell number ix*48+iy (64 x 48 = 3072 cells), 0xFFFF outside the grid
 __device__ __forceinline__ uint16_t kf_cell_of(const eorb_keypoint& k, const GridB& g)
 {
     const int px = (int)roundf((k.x - g.minX) * g.invW);
@@ -1534,12 +1525,16 @@ __device__ __forceinline__ uint16_t kf_cell_mixed(const eorb_keypoint& k, const 
     return (cell != 0xFFFF && kp_is_orb && !kp_is_orb[i]) ? (uint16_t)(cell | kCellNotOrb) : cell;
 }
 
-__global__ void kf_cells_mixed_kernel(const eorb_keypoint* __restrict__ kps, int n, GridB g, const uint8_t* __restrict__ kp_is_orb,
-                                      uint16_t* __restrict__ cell)
+// the cells of every keyframe's keypoints in one launch
+template <bool MIXED>
+__global__ void kf_cells_batch_kernel(const eorb_keypoint* __restrict__ kps, int ntotal, const int32_t* __restrict__ kf_off, int K,
+                                      const GridB* __restrict__ g, const uint8_t* __restrict__ kp_is_orb, uint16_t* __restrict__ cell)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    cell[i] = kf_cell_mixed(kps[i], g, kp_is_orb, i);
+    if (i >= ntotal) return;
+    int lo = 0, hi = K - 1;                                     // the keyframe of keypoint i: the last k with kf_off[k] <= i
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (kf_off[mid] <= i) lo = mid; else hi = mid - 1; }
+    cell[i] = MIXED ? kf_cell_mixed(kps[i], g[lo], kp_is_orb, i) : kf_cell_of(kps[i], g[lo]);
 }
 
 // MIXED: the search loop of MixedMatcher::Fuse (src/MixedMatcher.cpp:1703-1758, :1891-1921) and MixedMatcher::SearchByProjection(pKF,
@@ -1612,27 +1607,54 @@ __device__ __forceinline__ uint64_t radius_scan(const Args& A, int m, int first,
 template <bool MIXED> using RadArgsOf = std::conditional_t<MIXED, RadArgsMixed, RadArgs>;
 template <bool MIXED> using RadBatchArgsOf = std::conditional_t<MIXED, RadBatchArgsMixed, RadBatchArgs>;
 
+// keyframe k of the block as radius_scan reads it: its keypoint range with its grid bounds, its M queries.  (B by value: through a
+// reference to the kernel's argument the ORB batch kernel takes two more SGPRs.)
 template <bool MIXED>
-__global__ __launch_bounds__(256) void kf_radius_kernel(RadArgsOf<MIXED> A)
+__device__ __forceinline__ RadArgsOf<MIXED> rad_pair(const RadBatchArgsOf<MIXED> B, int k)
+{
+    const int off = B.kf_off[k];
+    const size_t qo = (size_t)k * B.M;
+    RadArgsOf<MIXED> A{};
+    A.kps = B.kps + off; A.n = B.kf_off[k + 1] - off; A.desc = B.desc + (size_t)off * B.stride; A.stride = B.stride;
+    A.g = B.g[k]; A.cell = B.cell + off;
+    A.M = B.M; A.valid = B.valid + qo; A.uv = B.uv + 2 * qo; A.radius = B.radius + qo; A.level = B.level + qo;
+    A.q_desc = B.q_desc + (size_t)k * B.q_desc_kstride;
+    A.inv_sigma2 = B.inv_sigma2; A.nlevels = B.nlevels;
+    A.uright = B.uright ? B.uright + off : nullptr; A.q_ur = B.uright ? B.q_ur + qo : nullptr;
+    A.taken = B.taken; A.accept_thr = B.accept_thr;
+    A.best_idx = B.best_idx + qo; A.best_dist = B.best_dist + qo;
+    if constexpr (MIXED) { A.mp_is_orb = B.mp_is_orb; A.kp_inv_sigma2 = B.kp_inv_sigma2 ? B.kp_inv_sigma2 + off : nullptr; }
+    return A;
+}
+
+// One wavefront per query runs radius_scan<false> over keyframe k's keypoint range; the queries are independent.
+template <bool MIXED>
+__global__ __launch_bounds__(256) void kf_radius_batch_kernel(RadBatchArgsOf<MIXED> B)
 {
     const int lane = threadIdx.x & 63;
-    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
-    for (int m = gw; m < A.M; m += nw) {
+    const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t nq = (int64_t)B.K * B.M;
+    for (int64_t q = gw; q < nq; q += nw) {
+        const int k = (int)(q / B.M);
+        const RadArgsOf<MIXED> A = rad_pair<MIXED>(B, k);
+        const int m = (int)(q - (int64_t)k * B.M);
         uint64_t k0 = ~0ull;
         if (A.valid[m]) k0 = radius_scan<false, MIXED>(A, m, lane, 64, nullptr);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k0, d, 64); k0 = o < k0 ? o : k0; }
         if (lane == 0) {
             const bool ok = k0 != ~0ull && (int)(k0 >> 44) < 256;
-            A.best_idx[m] = ok ? (int)(k0 & 0xffffffffu) : -1;
-            A.best_dist[m] = ok ? (int)(k0 >> 44) : 256;
+            B.best_idx[q] = ok ? (int)(k0 & 0xffffffffu) : -1;
+            B.best_dist[q] = ok ? (int)(k0 >> 44) : 256;
         }
     }
 }
 
+// The in-order form (K = 1): one workgroup, the vpMatched flags in LDS, the queries one after another.
 template <bool MIXED>
-__global__ __launch_bounds__(256) void kf_radius_seq_kernel(RadArgsOf<MIXED> A)
+__global__ __launch_bounds__(256) void kf_radius_seq_kernel(RadBatchArgsOf<MIXED> B)
 {
+    const RadArgsOf<MIXED> A = rad_pair<MIXED>(B, 0);
     extern __shared__ unsigned char smem[];
     uint64_t* red = (uint64_t*)smem;
     uint8_t* taken = (uint8_t*)(red + 8);
@@ -1651,89 +1673,6 @@ __global__ __launch_bounds__(256) void kf_radius_seq_kernel(RadArgsOf<MIXED> A)
         __syncthreads();
     }
     for (int i = threadIdx.x; i < A.n; i += blockDim.x) A.taken[i] = taken[i];
-}
-
-template <bool MIXED, typename Args>
-static int kf_radius_launch(eorb_ctx* c, const Args& A, uint16_t* d_cell, const uint8_t* d_kp_is_orb)
-{
-    if (A.M <= 0) return EORB_OK;
-    ProfScope ps(c, MIXED ? "kf_radius_match_mixed" : "kf_radius_match");
-    if (A.n > 0) {
-        if constexpr (MIXED) kf_cells_mixed_kernel<<<(A.n + 255) / 256, 256, 0, c->stream>>>(A.kps, A.n, A.g, d_kp_is_orb, d_cell);
-        else kf_cells_kernel<<<(A.n + 255) / 256, 256, 0, c->stream>>>(A.kps, A.n, A.g, d_cell);
-    }
-    if (A.taken) {
-        const size_t lds = 64 + (((size_t)A.n + 15) & ~(size_t)15);
-        if (lds > 160 * 1024) return set_err(c, EORB_E_CAPACITY, "kf_radius_match: %d keypoints exceed the LDS flags", A.n);
-        int rc;
-        if ((rc = lds_optin(c, MIXED ? kOptKfRadiusMixed : kOptKfRadius, (const void*)kf_radius_seq_kernel<MIXED>, 160 * 1024))) return rc;
-        kf_radius_seq_kernel<MIXED><<<1, 256, lds, c->stream>>>(A);
-    } else {
-        kf_radius_kernel<MIXED><<<std::min((A.M + 3) / 4, 4096), 256, 0, c->stream>>>(A);
-    }
-    EORB_LAUNCH_CHECK(c, "kf_radius_match kernels");
-    return EORB_OK;
-}
-int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell) { return kf_radius_launch<false>(c, A, d_cell, nullptr); }
-int kf_radius_mixed_dev(eorb_ctx* c, const RadArgsMixed& A, uint16_t* d_cell, const uint8_t* d_kp_is_orb)
-{
-    return kf_radius_launch<true>(c, A, d_cell, d_kp_is_orb);
-}
-
-// The same search over K keyframes at once (eorb_fuse_keyframes, eorb_fuse_pose, eorb_search_by_sim3): the keyframes' keypoints are
-// concatenated (kf_off[K + 1]), query (k, m) is entry k * M + m of the projector's arrays.  One wavefront per query runs
-// radius_scan<false> over keyframe k's keypoint range with that keyframe's grid bounds; the queries are independent.
-__global__ void kf_cells_batch_kernel(const eorb_keypoint* __restrict__ kps, int ntotal, const int32_t* __restrict__ kf_off, int K,
-                                      const GridB* __restrict__ g, uint16_t* __restrict__ cell)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ntotal) return;
-    int lo = 0, hi = K - 1;                                     // the keyframe of keypoint i: the last k with kf_off[k] <= i
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (kf_off[mid] <= i) lo = mid; else hi = mid - 1; }
-    const GridB b = g[lo];
-    const int px = (int)roundf((kps[i].x - b.minX) * b.invW);
-    const int py = (int)roundf((kps[i].y - b.minY) * b.invH);
-    cell[i] = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? (uint16_t)0xFFFF : (uint16_t)(px * kGridRows + py);
-}
-__global__ void kf_cells_batch_mixed_kernel(const eorb_keypoint* __restrict__ kps, int ntotal, const int32_t* __restrict__ kf_off, int K,
-                                            const GridB* __restrict__ g, const uint8_t* __restrict__ kp_is_orb, uint16_t* __restrict__ cell)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ntotal) return;
-    int lo = 0, hi = K - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (kf_off[mid] <= i) lo = mid; else hi = mid - 1; }
-    cell[i] = kf_cell_mixed(kps[i], g[lo], kp_is_orb, i);
-}
-
-template <bool MIXED>
-__global__ __launch_bounds__(256) void kf_radius_batch_kernel(RadBatchArgsOf<MIXED> B)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const int64_t nq = (int64_t)B.K * B.M;
-    for (int64_t q = gw; q < nq; q += nw) {
-        const int k = (int)(q / B.M);
-        const int off = B.kf_off[k];
-        const size_t qo = (size_t)k * B.M;
-        RadArgsOf<MIXED> A{};
-        A.kps = B.kps + off; A.n = B.kf_off[k + 1] - off; A.desc = B.desc + (size_t)off * B.stride; A.stride = B.stride;
-        A.g = B.g[k]; A.cell = B.cell + off;
-        A.M = B.M; A.valid = B.valid + qo; A.uv = B.uv + 2 * qo; A.radius = B.radius + qo; A.level = B.level + qo;
-        A.q_desc = B.q_desc + (size_t)k * B.q_desc_kstride;
-        A.inv_sigma2 = B.inv_sigma2; A.nlevels = B.nlevels;
-        A.uright = B.uright ? B.uright + off : nullptr; A.q_ur = B.uright ? B.q_ur + qo : nullptr;
-        if constexpr (MIXED) { A.mp_is_orb = B.mp_is_orb; A.kp_inv_sigma2 = B.kp_inv_sigma2 ? B.kp_inv_sigma2 + off : nullptr; }
-        const int m = (int)(q - (int64_t)qo);
-        uint64_t k0 = ~0ull;
-        if (A.valid[m]) k0 = radius_scan<false, MIXED>(A, m, lane, 64, nullptr);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(k0, d, 64); k0 = o < k0 ? o : k0; }
-        if (lane == 0) {
-            const bool ok = k0 != ~0ull && (int)(k0 >> 44) < 256;
-            B.best_idx[q] = ok ? (int)(k0 & 0xffffffffu) : -1;
-            B.best_dist[q] = ok ? (int)(k0 >> 44) : 256;
-        }
-    }
 }
 
 // the agreement pass of SearchBySim3 (:1948-1964) over a 2 x M batch: row 0 = KF1's points searched in KF2, row 1 the reverse
@@ -1757,26 +1696,30 @@ __global__ void sim3_agree_kernel(const int32_t* __restrict__ best_idx, const in
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(nfound, __popcll(b));
 }
 
-int kf_radius_batch_dev(eorb_ctx* c, const RadBatchArgs& B, int ntotal, uint16_t* d_cell)
+template <bool MIXED>
+static int kf_radius_launch(eorb_ctx* c, const char* name, const RadBatchArgsOf<MIXED>& B, int ntotal, const uint8_t* d_kp_is_orb)
 {
     const int64_t nq = (int64_t)B.K * B.M;
     if (nq <= 0) return EORB_OK;
-    ProfScope ps(c, "kf_radius_batch");
-    if (ntotal > 0) kf_cells_batch_kernel<<<(ntotal + 255) / 256, 256, 0, c->stream>>>(B.kps, ntotal, B.kf_off, B.K, B.g, d_cell);
-    kf_radius_batch_kernel<false><<<(unsigned)std::min<int64_t>((nq + 3) / 4, 8192), 256, 0, c->stream>>>(B);
-    EORB_LAUNCH_CHECK(c, "kf_radius_batch kernels");
+    if (B.taken && B.K != 1) return set_err(c, EORB_E_ARG, "%s: the in-order search takes one keyframe", name);
+    ProfScope ps(c, name);
+    if (ntotal > 0)
+        kf_cells_batch_kernel<MIXED><<<(ntotal + 255) / 256, 256, 0, c->stream>>>(B.kps, ntotal, B.kf_off, B.K, B.g, d_kp_is_orb, B.cell);
+    if (B.taken) {
+        const size_t lds = 64 + (((size_t)ntotal + 15) & ~(size_t)15);
+        if (lds > 160 * 1024) return set_err(c, EORB_E_CAPACITY, "kf_radius_match: %d keypoints exceed the LDS flags", ntotal);
+        int rc;
+        if ((rc = lds_optin(c, MIXED ? kOptKfRadiusMixed : kOptKfRadius, (const void*)kf_radius_seq_kernel<MIXED>, 160 * 1024))) return rc;
+        kf_radius_seq_kernel<MIXED><<<1, 256, lds, c->stream>>>(B);
+    } else {
+        kf_radius_batch_kernel<MIXED><<<(unsigned)std::min<int64_t>((nq + 3) / 4, 8192), 256, 0, c->stream>>>(B);
+    }
+    EORB_LAUNCH_CHECK(c, name);
     return EORB_OK;
 }
-
-int kf_radius_batch_mixed_dev(eorb_ctx* c, const RadBatchArgsMixed& B, int ntotal, uint16_t* d_cell, const uint8_t* d_kp_is_orb)
+int kf_radius_dev(eorb_ctx* c, const char* name, bool mixed, const RadBatchArgsMixed& B, int ntotal, const uint8_t* d_kp_is_orb)
 {
-    const int64_t nq = (int64_t)B.K * B.M;
-    if (nq <= 0) return EORB_OK;
-    ProfScope ps(c, "kf_radius_batch_mixed");
-    if (ntotal > 0) kf_cells_batch_mixed_kernel<<<(ntotal + 255) / 256, 256, 0, c->stream>>>(B.kps, ntotal, B.kf_off, B.K, B.g, d_kp_is_orb, d_cell);
-    kf_radius_batch_kernel<true><<<(unsigned)std::min<int64_t>((nq + 3) / 4, 8192), 256, 0, c->stream>>>(B);
-    EORB_LAUNCH_CHECK(c, "kf_radius_batch_mixed kernels");
-    return EORB_OK;
+    return mixed ? kf_radius_launch<true>(c, name, B, ntotal, d_kp_is_orb) : kf_radius_launch<false>(c, name, B, ntotal, nullptr);
 }
 
 int sim3_agree_dev(eorb_ctx* c, const int32_t* best_idx, const int32_t* best_dist, int M, int N1, int N2, int th_high,

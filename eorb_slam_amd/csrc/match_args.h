@@ -76,31 +76,35 @@ struct BowBatchArgs { BowArgs A; const KfSlice* kf; int K, n_out, max_nn; };
 struct TriBatchArgs { TriArgs T; const KfSlice* kf; const TriPair* pair; int K; };
 struct TriKbBatchArgs { TriKbArgs K; const KfSlice* kf; const TriPair* pair; const TriKbPair* kb; int nk; };
 
-struct RadArgs {
-    const eorb_keypoint* kps; int n; const uint8_t* desc; int stride; GridB g;
-    const uint16_t* cell;                           // n: ix*48+iy or 0xFFFF (Frame::PosInGrid), from kf_cells_kernel
-    int M; const uint8_t* valid; const float* uv; const float* radius; const int32_t* level; const uint8_t* q_desc;
-    const float* inv_sigma2; int nlevels;
-    const float* uright; const float* q_ur;       // Fuse, rectified stereo: mvuRight per keypoint (>= 0: has one), the map points' predicted right coordinates
-    uint8_t* taken; float accept_thr;
-    int32_t* best_idx; int32_t* best_dist;
-};
-
-// the radius match over K keyframes (match.hip kf_radius_batch_kernel): keypoints / descriptors / cells / uright of all keyframes
-// concatenated, keyframe k = rows kf_off[k] .. kf_off[k + 1] - 1 with grid bounds g[k]; the projector's arrays hold K * M queries,
-// (k, m) at k * M + m; the descriptor of query (k, m) is row m of q_desc + k * q_desc_kstride (0: all keyframes share the M rows)
+// the KeyFrame-side radius search (match.hip kf_radius_batch_kernel, kf_radius_seq_kernel) over K keyframes, a single keyframe being
+// K = 1: keypoints / descriptors / cells / uright of all keyframes concatenated, keyframe k = rows kf_off[k] .. kf_off[k + 1] - 1 with
+// grid bounds g[k]; the query arrays hold K * M queries, (k, m) at k * M + m; the descriptor of query (k, m) is row m of
+// q_desc + k * q_desc_kstride (0: all keyframes share the M rows).  taken (K = 1 only): the in-order form, vpMatched in and out
 struct RadBatchArgs {
-    const eorb_keypoint* kps; const uint8_t* desc; int stride; const uint16_t* cell; const float* uright;
+    const eorb_keypoint* kps; const uint8_t* desc; int stride;
+    uint16_t* cell;                                 // per keypoint: ix*48+iy or 0xFFFF (Frame::PosInGrid); the launcher fills it (kf_cells_batch_kernel)
+    const float* uright;                            // Fuse, rectified stereo: mvuRight per keypoint (>= 0: has one); q_ur: the map points' predicted right coordinates
     const int32_t* kf_off; const GridB* g; int K, M;
     const uint8_t* valid; const float* uv; const float* radius; const int32_t* level; const float* q_ur;
     const uint8_t* q_desc; size_t q_desc_kstride;
     const float* inv_sigma2; int nlevels;
     int32_t* best_idx; int32_t* best_dist;
+    uint8_t* taken; float accept_thr;
+};
+
+// one keyframe of it as radius_scan reads it: the device-side view that rad_pair (match.hip) makes from the block and a keyframe index
+struct RadArgs {
+    const eorb_keypoint* kps; int n; const uint8_t* desc; int stride; GridB g; const uint16_t* cell;
+    int M; const uint8_t* valid; const float* uv; const float* radius; const int32_t* level; const uint8_t* q_desc;
+    const float* inv_sigma2; int nlevels;
+    const float* uright; const float* q_ur;
+    uint8_t* taken; float accept_thr;
+    int32_t* best_idx; int32_t* best_dist;
 };
 
 // the mixed kernels' arguments (MixedMatcher's KeyFrame-side forms): the ORB ones plus mp_is_orb[M] (NULL = every map point ORB; one
 // array for all keyframes of a batch) and kp_inv_sigma2 = getKPtInvLevelSigma2(idx) per keypoint (NULL = no reprojection gate; inv_sigma2
-// / nlevels are unused).  The keypoints' types are bit 15 of their cell words (kf_cells_mixed_kernel).
+// / nlevels are unused).  The keypoints' types are bit 15 of their cell words (kf_cells_batch_kernel<true>).
 struct RadArgsMixed : RadArgs { const uint8_t* mp_is_orb; const float* kp_inv_sigma2; };
 struct RadBatchArgsMixed : RadBatchArgs { const uint8_t* mp_is_orb; const float* kp_inv_sigma2; };
 
@@ -144,10 +148,9 @@ int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* c
 int twocam_walk_dev(eorb_ctx* c, int kind, const TcArgs& A);
 int fisheye_lowe_dev(eorb_ctx* c, const uint8_t* d_descL, const uint8_t* d_descR, int cap, int32_t* d_lap, int32_t* d_idx2,
                      int32_t* d_kdist2, int32_t* d_cand, int32_t* d_dist2);
-int kf_radius_dev(eorb_ctx* c, const RadArgs& A, uint16_t* d_cell);
-int kf_radius_batch_dev(eorb_ctx* c, const RadBatchArgs& B, int ntotal, uint16_t* d_cell);
-int kf_radius_mixed_dev(eorb_ctx* c, const RadArgsMixed& A, uint16_t* d_cell, const uint8_t* d_kp_is_orb);
-int kf_radius_batch_mixed_dev(eorb_ctx* c, const RadBatchArgsMixed& B, int ntotal, uint16_t* d_cell, const uint8_t* d_kp_is_orb);
+// the radius search of B (its cells first); name: the profile scope of the entry point; mixed: the MixedMatcher kernels (the ORB ones
+// take B's base); B.taken chooses the in-order kernel; d_kp_is_orb: the keypoints' types for the cell words (mixed, may be NULL)
+int kf_radius_dev(eorb_ctx* c, const char* name, bool mixed, const RadBatchArgsMixed& B, int ntotal, const uint8_t* d_kp_is_orb);
 int sim3_agree_dev(eorb_ctx* c, const int32_t* best_idx, const int32_t* best_dist, int M, int N1, int N2, int th_high,
                    int32_t* vn1, int32_t* vn2, int32_t* match12, int32_t* nfound);
 int bow_transform_dev(eorb_ctx* c, const uint8_t* d_desc, int n, int stride, const BowVoc& V, int levelsup, int weighting, int norm,

@@ -53,7 +53,7 @@ struct KfPose {
     float minX, maxX, minY, maxY, mbf;
 };
 
-// per (keyframe, map point) outputs of modes D and E, K * M entries each: what kf_radius_batch_dev (match.hip) reads, plus the test aids
+// per (keyframe, map point) outputs of modes D and E, K * M entries each: what kf_radius_dev (match.hip) reads, plus the test aids
 struct KfSideDev {
     uint8_t* valid; float2* uv; int32_t* level; float* radius; float* q_ur; float* dist3d; uint8_t* reason;
 };

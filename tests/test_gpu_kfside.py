@@ -331,3 +331,236 @@ def test_argument_errors_empty_sides_and_limits(fe, ctx):
     assert L.eorb_fuse_pose(h, p(kps), n, p(desc), 32, C.byref(gb), C.byref(v), M, p(pos), p(nrm), p(mn), p(mx), None, p(qd), None, None, 3.0,
                             p(bi), p(bd), None) == 0
     assert (bd <= TH_LOW).sum() >= 30
+
+
+# ---- a single keyframe is K = 1 of the batch: the shapes at which the shared path can go wrong ----------------------------------------
+SCALE = (1.2 ** np.arange(8)).astype(F32)
+INV_SIGMA2 = (F32(1.0) / (SCALE * SCALE)).astype(F32)
+
+
+@functools.lru_cache(None)
+def _radius_case(n, M, seed, contend=False):
+    """n random keypoints and M queries aimed at picked ones: the keypoint's position and descriptor with noise (half of the queries a few
+    flipped bits, half about 43 of 256, around TH_LOW and 0.8 TH_LOW), the level at or one above its octave.  Query 0 is an exact copy of
+    keypoint 0 (a hit under every gate); every fourth query asks for a level no keypoint near it has, a tenth are invalid, a few lie
+    outside the grid.  contend: query 1 is query 0 again, so that in order it loses keypoint 0.  uright: none for 40 % of the keypoints."""
+    rng = np.random.default_rng(seed)
+    kps = synth.random_keypoints(n, W, H, nlevels=6, seed=seed + 1)
+    desc = synth.random_descriptors(n, seed=seed + 2)
+    pick = rng.integers(0, n, M); pick[0] = 0
+    if contend and M > 1:
+        pick[1] = 0
+    noise = rng.normal(0, 1.5, (M, 2)); noise[0] = 0
+    if contend and M > 1:
+        noise[1] = 0.25
+    uv = (np.stack([kps["x"][pick], kps["y"][pick]], 1) + noise).astype(F32)
+    level = (kps["octave"][pick] + rng.integers(0, 2, M)).astype(np.int32); level[0] = kps["octave"][0]
+    miss = np.arange(M) % 4 == (3 if contend else 1)
+    level[miss] += 3
+    out = rng.random(M) < 0.03; out[:2] = False
+    uv[out] = rng.uniform(-40, 0, (int(out.sum()), 2)).astype(F32)
+    p = np.where(rng.random(M) < 0.5, 0.02, 0.17); p[0] = 0
+    qd = desc[pick] ^ np.packbits(rng.random((M, 256)) < p[:, None], axis=1)
+    valid = (rng.random(M) < 0.9).astype(np.uint8); valid[:2] = 1
+    uright = np.where(rng.random(n) < 0.6, kps["x"] - rng.uniform(2, 30, n), -1).astype(F32)
+    q_ur = (np.where(uright[pick] >= 0, uright[pick], 0) + rng.normal(0, 1.5, M)).astype(F32); q_ur[0] = max(uright[0], 0)
+    radius = (F32(3.0) * SCALE[np.minimum(level, 7)]).astype(F32)
+    d = dict(kps=kps, desc=desc, valid=valid, uv=uv, radius=radius, level=level, qd=qd, uright=uright, q_ur=q_ur)
+    for a in d.values():
+        a.setflags(write=False)
+    return d
+
+
+def _gate_kw(s, gate):
+    kw = {} if gate == "plain" else dict(inv_sigma2=INV_SIGMA2)
+    if gate == "stereo":
+        kw.update(uright=s["uright"], q_ur=s["q_ur"])
+    return kw
+
+
+def _q(s):
+    return s["valid"], s["uv"], s["radius"], s["level"], s["qd"]
+
+
+def _both(bi):
+    return bool((bi >= 0).any()) and bool((bi < 0).any())
+
+
+@pytest.mark.parametrize("gate", ["plain", "sigma", "stereo"])
+@pytest.mark.parametrize("n", [1, 63, 64, 65])
+def test_independent_radius_search_lane_and_wave_edges(fe, ctx, oracle, n, gate):
+    """eorb_kf_radius_match / _stereo: the lanes stride the keypoints by 64, four waves share a workgroup"""
+    gb = fe.grid_bounds(W, H)
+    hits = misses = 0
+    for M in (1, 3, 4, 5, 257):
+        s = _radius_case(n, M, 100 + n)
+        want = oracle.kf_radius_match(oracle.Frame(s["kps"], s["desc"], W, H), *_q(s), **_gate_kw(s, gate))
+        got = fe.KeyFrameRadiusMatch(s["kps"], s["desc"], gb, *_q(s), ctx=ctx, **_gate_kw(s, gate))
+        assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes(), M
+        assert want[0][0] == 0 and want[1][0] == 0 and (M == 1 or _both(want[0])), M      # (one query cannot both hit and miss)
+        hits += int((want[0] >= 0).sum()); misses += int((want[0] < 0).sum())
+    print("independent", n, gate, "hits", hits, "misses", misses)
+    assert hits >= 50 and misses >= 50
+
+
+def test_independent_radius_search_goes_round_the_grid_stride_loop(fe, ctx, oracle):
+    """K = 1 with more queries than the 8192 workgroups of four waves take in one round"""
+    n, M = 65, 4 * 8192 + 5
+    s = _radius_case(n, M, 7)
+    Fr = oracle.Frame(s["kps"], s["desc"], W, H)
+    gb = fe.grid_bounds(W, H)
+    for gate in ("plain", "sigma", "stereo"):
+        want = oracle.kf_radius_match(Fr, *_q(s), **_gate_kw(s, gate))
+        got = fe.KeyFrameRadiusMatch(s["kps"], s["desc"], gb, *_q(s), ctx=ctx, **_gate_kw(s, gate))
+        assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes(), gate
+        assert _both(want[0]) and _both(want[0][4 * 8192:]), gate                          # the second round has both as well
+
+
+def _taken(n, seed):
+    tk = (np.random.default_rng(seed).random(n) < 0.2).astype(np.uint8)
+    tk[0] = 0                                                                              # (keypoint 0 is what queries 0 and 1 want)
+    return tk
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 300])
+def test_in_order_radius_search(fe, ctx, oracle, n):
+    """eorb_kf_radius_match(taken, accept_thr): one workgroup, the flags in LDS"""
+    gb = fe.grid_bounds(W, H)
+    taken = _taken(n, 3)
+    newly = 0
+    for M in (1, 2, 65):
+        s = _radius_case(n, M, 200 + n, contend=True)
+        Fr = oracle.Frame(s["kps"], s["desc"], W, H)
+        free = oracle.kf_radius_match(Fr, *_q(s))
+        for thr in (float(TH_LOW), float(F32(0.8) * F32(TH_LOW))):
+            want = oracle.kf_radius_match(Fr, *_q(s), taken=taken, accept_thr=thr)
+            got = fe.KeyFrameRadiusMatch(s["kps"], s["desc"], gb, *_q(s), taken=taken, accept_thr=thr, ctx=ctx)
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(got, want)), (M, thr)
+            assert want[0][0] == 0 and want[2][0] == 1 and np.all(want[2][taken == 1] == 1)
+            if M > 1:
+                assert free[0][1] == 0 and want[0][1] != 0                                 # query 1 loses keypoint 0 to query 0
+                assert not np.array_equal(want[0], free[0])
+            if M == 65:
+                assert _both(want[0])
+                newly += int(want[2].sum()) - int(taken.sum())
+        if M == 65 and n > 1:                                                              # the threshold decides who keeps a keypoint
+            a, b = (oracle.kf_radius_match(Fr, *_q(s), taken=taken, accept_thr=t)[2] for t in (50.0, 40.0))
+            print("in order", n, "taken at TH_LOW", int(a.sum()), "at 0.8 TH_LOW", int(b.sum()))
+            assert a.sum() > b.sum()
+    assert newly >= 2
+
+
+@functools.lru_cache(None)
+def _scw_case(n, M, th=4.0):
+    """n keypoints of the 1 000-keypoint scene, most of them planted on map points that project validly, and M map points chosen among
+    the planted ones; the second half of the points repeats the first, so that in order the repeats lose their keypoints"""
+    sc = _nbh(45, 1, 1000, (1000,))
+    p = kfside_ref.keyframe_side(kfside_ref.view(**sc["views"][0]), *_geom(sc), th)
+    src = sc["src"][0]
+    good = np.flatnonzero((src >= 0) & (p["valid"][np.maximum(src, 0)] == 1))
+    other = np.flatnonzero(src < 0)
+    rows = np.concatenate([good[:max(1, (3 * n) // 4)], other])[:n]
+    pts = src[rows[src[rows] >= 0]]
+    pts = np.concatenate([pts, np.setdiff1d(np.arange(1000), pts)])[:(M + 1) // 2]         # (points nobody was planted on: mostly misses)
+    pts = np.concatenate([pts, pts])[:M]
+    g = tuple(np.ascontiguousarray(a[pts]) for a in _geom(sc))
+    return dict(kps=sc["kps"][0][rows], desc=sc["desc"][0][rows], geom=g, mp_desc=np.ascontiguousarray(sc["mp_desc"][pts]), view=sc["views"][0])
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 300])
+def test_in_order_search_by_projection_kf_scw(fe, ctx, ref, oracle, n):
+    """eorb_search_by_projection_kf_scw: mode D, then the in-order kernel, as fuse_common's K = 1"""
+    gb = fe.grid_bounds(W, H)
+    taken = _taken(n, 5)
+    for M in (1, 2, 65):
+        s = _scw_case(n, M)
+        p = ref.keyframe_side(ref.view(**s["view"]), *s["geom"], 4.0)
+        Fr = oracle.Frame(s["kps"], s["desc"], W, H)
+        q = (p["valid"], p["uv"], p["radius"], p["level"], s["mp_desc"])
+        free = oracle.kf_radius_match(Fr, *q)
+        for ratio in (1.0, 0.8):
+            thr = float(F32(TH_LOW) * F32(ratio))
+            want = oracle.kf_radius_match(Fr, *q, taken=taken, accept_thr=thr)
+            bi, bd, tk, g = fe.SearchByProjectionKFScw(s["kps"], s["desc"], gb, fe.view(**s["view"]), *s["geom"], s["mp_desc"], taken, 4.0,
+                                                       ratioHamming=ratio, want_projection=True, ctx=ctx)
+            _eq(g, p, PROJ)
+            assert bi.tobytes() == want[0].tobytes() and bd.tobytes() == want[1].tobytes() and tk.tobytes() == want[2].tobytes(), (M, ratio)
+            assert want[0][0] >= 0 and np.all(want[2][taken == 1] == 1)
+            if M > 1:
+                r = (M + 1) // 2                                                           # the first repeat: point 0 again
+                assert free[0][r] == free[0][0] and want[0][r] != want[0][0]               # in order it loses its keypoint
+                assert _both(want[0])
+
+
+@pytest.mark.parametrize("n1,n2", [(65, 300), (300, 65), (1, 300), (300, 1)])
+def test_search_by_sim3_with_unequal_sides(fe, ctx, ref, oracle, n1, n2):
+    """row 1 of the 2 x M batch: its query offset M = max(n1, n2) and its descriptors' stride differ from its keypoint count"""
+    sp = synth.sim3_pair(47, n=300, n_both=80, n_one=40, n_cross=40)
+    cut = lambda kf, a, n: {k: (v[a:a + n] if isinstance(v, np.ndarray) else v) for k, v in kf.items()}
+    full = _sim3_ref(ref, oracle, sp, 7.5)[4]
+    i1 = int(np.flatnonzero(full >= 0)[0])                                                 # a side of one keeps a slot of an agreed pair
+    sp = dict(sp, kf1=cut(sp["kf1"], i1 if n1 == 1 else 0, n1), kf2=cut(sp["kf2"], int(full[i1]) if n2 == 1 else 0, n2))
+    th = 7.5
+    p12, p21, vn1, vn2, m12 = _sim3_ref(ref, oracle, sp, th)
+    gb = fe.grid_bounds(W, H)
+    kf = [dict(k, gb=gb, view=fe.view(**k["view"])) for k in (sp["kf1"], sp["kf2"])]
+    nf, g12, g1, g2 = fe.SearchBySim3Pose(kf[0], kf[1], sp["sR12"], sp["t12"], sp["sR21"], sp["t21"], th=th, ctx=ctx)
+    assert g1.tobytes() == vn1.tobytes() and g2.tobytes() == vn2.tobytes()
+    assert g12.tobytes() == m12.tobytes() and nf == int((m12 >= 0).sum())
+    print("sim3", n1, n2, "found", int((vn1 >= 0).sum()), int((vn2 >= 0).sum()), "agreed", nf)
+    assert (vn1 >= 0).any() and (vn2 >= 0).any() and _both(vn1 if n1 > 1 else vn2) and nf >= (5 if min(n1, n2) > 1 else 1)
+
+
+def test_radius_search_profile_scopes_keep_the_entry_points_names(fe, ctx, ref):
+    """one call of each entry point, profiled: the single-keyframe calls under kf_radius_match, the fused ones under kf_radius_batch"""
+    s = _radius_case(65, 65, 9)
+    c = _scw_case(65, 65)
+    sc = _nbh(49, 2, 65, NKPS[2])
+    kps, desc, ur, off = _cat(sc)
+    sp = synth.sim3_pair(47, n=300, n_both=80, n_one=40, n_cross=40)
+    gb = fe.grid_bounds(W, H)
+    kf = [dict(k, gb=gb, view=fe.view(**k["view"])) for k in (sp["kf1"], sp["kf2"])]
+    calls = [("kf_radius_match", lambda: fe.KeyFrameRadiusMatch(s["kps"], s["desc"], gb, *_q(s), ctx=ctx)),
+             ("kf_radius_match", lambda: fe.KeyFrameRadiusMatch(s["kps"], s["desc"], gb, *_q(s), ctx=ctx, **_gate_kw(s, "stereo"))),
+             ("kf_radius_match", lambda: fe.KeyFrameRadiusMatch(s["kps"], s["desc"], gb, *_q(s), taken=_taken(65, 3), accept_thr=50.0, ctx=ctx)),
+             ("kf_radius_match", lambda: fe.SearchByProjectionKFScw(c["kps"], c["desc"], gb, fe.view(**c["view"]), *c["geom"], c["mp_desc"],
+                                                                    _taken(65, 5), 4.0, ctx=ctx)),
+             ("kf_radius_batch", lambda: fe.FusePose(c["kps"], c["desc"], gb, fe.view(**c["view"]), *c["geom"], c["mp_desc"], ctx=ctx)),
+             ("kf_radius_batch", lambda: fe.FuseKeyFrames([fe.view(**kw) for kw in sc["views"]], [gb] * 2, kps, desc, off, *_geom(sc), sc["mp_desc"],
+                                                          ctx=ctx)),
+             ("kf_radius_batch", lambda: fe.SearchBySim3Pose(kf[0], kf[1], sp["sR12"], sp["t12"], sp["sR21"], sp["t21"], ctx=ctx))]
+    ctx.prof_enable(True)
+    try:
+        for name, call in calls:
+            ctx.prof_reset()
+            call()
+            got = {k: v[1] for k, v in ctx.prof_results().items() if k.startswith("kf_radius")}
+            assert got == {name: 1}, (name, got)
+    finally:
+        ctx.prof_enable(False)
+
+
+def test_one_keyframe_without_keypoints(fe, ctx):
+    """K = 1 with kf_off = {0, 0}: EORB_OK, -1 / 256 everywhere, no keypoint read (every keypoint pointer is NULL)"""
+    c = _scw_case(65, 65)
+    s = _radius_case(65, 65, 9)
+    L, h = ctx.L, ctx.h
+    v = fe.view(**c["view"]); gb = fe.grid_bounds(W, H)
+    p = lambda a: None if a is None else np.ascontiguousarray(a).ctypes.data_as(C.c_void_p)
+    pos, nrm, mn, mx = [np.ascontiguousarray(a) for a in c["geom"]]
+    qd = np.ascontiguousarray(c["mp_desc"])
+    M = 65
+    va, uv, rad, lv, sqd = [np.ascontiguousarray(a) for a in _q(s)]
+    out = lambda: (np.full(M, 7, np.int32), np.full(M, 7, np.int32))
+    bi, bd = out()
+    assert L.eorb_kf_radius_match(h, None, 0, None, 32, C.byref(gb), M, p(va), p(uv), p(rad), p(lv), p(sqd), None, 0, None, 0.0, p(bi), p(bd)) == 0
+    assert np.all(bi == -1) and np.all(bd == 256)
+    bi, bd = out()
+    assert L.eorb_fuse_pose(h, None, 0, None, 32, C.byref(gb), C.byref(v), M, p(pos), p(nrm), p(mn), p(mx), None, p(qd), None, None, 3.0,
+                            p(bi), p(bd), None) == 0
+    assert np.all(bi == -1) and np.all(bd == 256)
+    for tk in (None, np.zeros(1, np.uint8)):                                               # no flags, or flags of no keypoint
+        bi, bd = out()
+        assert L.eorb_search_by_projection_kf_scw(h, None, 0, None, 32, C.byref(gb), C.byref(v), M, p(pos), p(nrm), p(mn), p(mx), None, p(qd),
+                                                  4.0, p(tk), 50.0, p(bi), p(bd), None) == 0
+        assert np.all(bi == -1) and np.all(bd == 256) and (tk is None or tk[0] == 0)

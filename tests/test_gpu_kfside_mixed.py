@@ -340,3 +340,169 @@ def test_mixed_argument_errors_empty_sides_and_limits(fe, ctx):
     assert L.eorb_kf_radius_match_mixed(h, p(zk), big, p(zd), 32, C.byref(gb), None, None, None, *args, p(tk), 50.0, p(bi), p(bd)) == E_CAPACITY
     assert L.eorb_kf_radius_match_mixed(h, p(zk), big - 1, p(zd), 32, C.byref(gb), None, None, None, *args, p(tk), 50.0, p(bi), p(bd)) == 0
     fuse_ok()
+
+
+# ---- a single keyframe is K = 1 of the batch: the shapes at which the shared path can go wrong ----------------------------------------
+def _both(bi):
+    return bool((bi >= 0).any()) and bool((bi < 0).any())
+
+
+_CASES = {}
+
+
+def _sub_case(oracle, n, M, th=4.0):
+    """n rows and M points of the 1 000 x 1 000 mixed scene.  Row 0 is the keypoint that point 0 finds in the whole keyframe under every
+    gate, so it finds it among fewer rows too; three quarters of the rows are such winners, the rest carry no point.  The points are
+    the winners' own in turns with points nobody wins; the second half of the points repeats the first (in order the repeats lose
+    their keypoints; beyond 1 000 points the first 128 repeat).  -> the sub-scene, its geometry and the restatement's projection of it"""
+    if (n, M) in _CASES:
+        return _CASES[n, M]
+    sc = cases.scene()
+    p = cases.projection(th)[0]
+    src = sc["src"][0]
+    wins = np.ones(cases.N, bool)
+    for gate in cases.GATES:
+        bi = cases.search(oracle, sc, 0, p, gate)[0]
+        wins &= (src >= 0) & (bi[np.maximum(src, 0)] == np.arange(cases.N))
+    rows = np.concatenate([np.flatnonzero(wins)[:max(1, (3 * n) // 4)], np.flatnonzero(src < 0)])[:n]
+    won = src[rows[src[rows] >= 0]]
+    rest = np.setdiff1d(np.arange(cases.M), won)
+    pts = np.concatenate([np.stack([won, rest[:len(won)]], 1).reshape(-1), rest[len(won):]])      # won and not won take turns
+    pts = np.resize(pts[:(M + 1) // 2 if M <= cases.M else 128], M)
+    c = np.ascontiguousarray
+    s = dict(kps=sc["kps"][0][rows], desc=c(sc["desc"][0][rows]), uright=sc["uright"][0][rows], kp_is_orb=sc["kp_is_orb"][0][rows],
+             kp_inv_sigma2=sc["kp_inv_sigma2"][0][rows], mp_is_orb=sc["mp_is_orb"][pts], mp_desc=c(sc["mp_desc"][pts]),
+             geom=tuple(c(a[pts]) for a in cases.geom(sc)), view=sc["views"][0])
+    s["p"] = mref.keyframe_side(mref.view(**s["view"]), *s["geom"], th, mp_is_orb=s["mp_is_orb"])
+    _CASES[n, M] = s
+    return s
+
+
+def _sub_kw(s, gate):
+    kw = dict(kp_is_orb=s["kp_is_orb"], mp_is_orb=s["mp_is_orb"])
+    if gate != "none":
+        kw["kp_inv_sigma2"] = s["kp_inv_sigma2"]
+    if gate == "stereo":
+        kw["uright"] = s["uright"]
+    return kw
+
+
+def _sub_q(s):
+    p = s["p"]
+    return p["valid"], p["uv"], p["radius"], p["level"], s["mp_desc"]
+
+
+def _sub_ref(oracle, s, gate, **extra):
+    return mref.search(oracle.Frame(s["kps"], s["desc"], W, H), s["p"], s["mp_desc"], **_sub_kw(s, gate), **extra)
+
+
+def _taken(n, seed):
+    tk = (np.random.default_rng(seed).random(n) < 0.2).astype(np.uint8)
+    tk[0] = 0                                                                              # (row 0 is what point 0 and its repeat want)
+    return tk
+
+
+@pytest.mark.parametrize("gate", cases.GATES)
+@pytest.mark.parametrize("n", [1, 63, 64, 65])
+def test_mixed_independent_radius_search_lane_and_wave_edges(fe, ctx, ref, oracle, n, gate):
+    """eorb_kf_radius_match_mixed: the lanes stride the keypoints by 64, four waves share a workgroup"""
+    gb = fe.grid_bounds(W, H)
+    hits = misses = 0
+    for M in (1, 3, 4, 5, 257):
+        s = _sub_case(oracle, n, M)
+        want = _sub_ref(oracle, s, gate)
+        got = fe.KeyFrameRadiusMatchMixed(s["kps"], s["desc"], gb, *_sub_q(s), q_ur=s["p"]["q_ur"] if gate == "stereo" else None, ctx=ctx,
+                                          **_sub_kw(s, gate))
+        _same(got, want)
+        assert want[0][0] == 0 and (M < 257 or _both(want[0])), M
+        hits += int((want[0] >= 0).sum()); misses += int((want[0] < 0).sum())
+    print("mixed independent", n, gate, "hits", hits, "misses", misses)
+    assert hits >= 5 and misses >= 50
+
+
+def test_mixed_independent_radius_search_goes_round_the_grid_stride_loop(fe, ctx, ref, oracle):
+    """K = 1 with more queries than the 8192 workgroups of four waves take in one round"""
+    n, M = 65, 4 * 8192 + 5
+    s = _sub_case(oracle, n, M)
+    gb = fe.grid_bounds(W, H)
+    for gate in cases.GATES:
+        want = _sub_ref(oracle, s, gate)
+        got = fe.KeyFrameRadiusMatchMixed(s["kps"], s["desc"], gb, *_sub_q(s), q_ur=s["p"]["q_ur"] if gate == "stereo" else None, ctx=ctx,
+                                          **_sub_kw(s, gate))
+        _same(got, want)
+        assert _both(want[0]) and _both(want[0][4 * 8192:]), gate
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 300])
+def test_mixed_in_order_searches(fe, ctx, ref, oracle, n):
+    """eorb_kf_radius_match_mixed(taken, accept_thr) and eorb_search_by_projection_kf_scw_mixed on the same sub-scenes"""
+    gb = fe.grid_bounds(W, H)
+    taken = _taken(n, 3)
+    for M in (1, 2, 65):
+        s = _sub_case(oracle, n, M)
+        free = _sub_ref(oracle, s, "none")
+        v = fe.view(**s["view"])
+        flags = dict(kp_is_orb=s["kp_is_orb"], mp_is_orb=s["mp_is_orb"])
+        for ratio in (1.0, 0.8):
+            thr = float(F32(TH_LOW) * F32(ratio))
+            want = _sub_ref(oracle, s, "none", taken=taken, accept_thr=thr)
+            _same(fe.KeyFrameRadiusMatchMixed(s["kps"], s["desc"], gb, *_sub_q(s), taken=taken, accept_thr=thr, ctx=ctx, **flags), want)
+            bi, bd, tk, g = fe.SearchByProjectionKFScwMixed(s["kps"], s["desc"], gb, v, *s["geom"], s["mp_desc"], taken, 4.0, ratioHamming=ratio,
+                                                            want_projection=True, ctx=ctx, **flags)
+            _eq(g, s["p"])
+            _same((bi, bd, tk), want)
+            assert want[0][0] == 0 and want[2][0] == 1 and np.all(want[2][taken == 1] == 1)
+            if M > 1:
+                r = (M + 1) // 2                                                           # the first repeat: point 0 again
+                assert free[0][r] == 0 and want[0][r] != 0                                 # in order it loses keypoint 0
+            assert M < 65 or _both(want[0])                                                # (at M = 2 the repeat may find a second best)
+
+
+def test_mixed_radius_search_profile_scopes_keep_the_entry_points_names(fe, ctx, ref, oracle):
+    s = _sub_case(oracle, 65, 65)
+    gb = fe.grid_bounds(W, H)
+    v = fe.view(**s["view"])
+    flags = dict(kp_is_orb=s["kp_is_orb"], mp_is_orb=s["mp_is_orb"])
+    off = np.array([0, 65], np.int32)
+    calls = [("kf_radius_match_mixed", lambda: fe.KeyFrameRadiusMatchMixed(s["kps"], s["desc"], gb, *_sub_q(s), ctx=ctx, **flags)),
+             ("kf_radius_match_mixed", lambda: fe.KeyFrameRadiusMatchMixed(s["kps"], s["desc"], gb, *_sub_q(s), taken=_taken(65, 3), accept_thr=50.0,
+                                                                           ctx=ctx, **flags)),
+             ("kf_radius_match_mixed", lambda: fe.SearchByProjectionKFScwMixed(s["kps"], s["desc"], gb, v, *s["geom"], s["mp_desc"], _taken(65, 3), 4.0,
+                                                                               ctx=ctx, **flags)),
+             ("kf_radius_batch_mixed", lambda: fe.FusePoseMixed(s["kps"], s["desc"], gb, v, *s["geom"], s["mp_desc"], ctx=ctx, **flags)),
+             ("kf_radius_batch_mixed", lambda: fe.FuseKeyFramesMixed([v], [gb], s["kps"], s["desc"], off, *s["geom"], s["mp_desc"], ctx=ctx, **flags))]
+    ctx.prof_enable(True)
+    try:
+        for name, call in calls:
+            ctx.prof_reset()
+            call()
+            got = {k: c[1] for k, c in ctx.prof_results().items() if k.startswith("kf_radius")}
+            assert got == {name: 1}, (name, got)
+    finally:
+        ctx.prof_enable(False)
+
+
+def test_mixed_one_keyframe_without_keypoints(fe, ctx, ref, oracle):
+    """K = 1 with kf_off = {0, 0}: EORB_OK, -1 / 256 everywhere, no keypoint read (every keypoint pointer is NULL)"""
+    s = _sub_case(oracle, 65, 65)
+    L, h = ctx.L, ctx.h
+    v = fe.view(**s["view"]); gb = fe.grid_bounds(W, H)
+    p = lambda a: None if a is None else np.ascontiguousarray(a).ctypes.data_as(C.c_void_p)
+    pos, nrm, mn, mx = s["geom"]
+    qd, mio = s["mp_desc"], np.ascontiguousarray(s["mp_is_orb"])
+    M = 65
+    va, uv, rad, lv = [np.ascontiguousarray(s["p"][k]) for k in ("valid", "uv", "radius", "level")]
+    out = lambda: (np.full(M, 7, np.int32), np.full(M, 7, np.int32))
+    bi, bd = out()
+    assert L.eorb_kf_radius_match_mixed(h, None, 0, None, 32, C.byref(gb), None, None, None, M, p(va), p(uv), p(rad), p(lv), p(qd), p(mio), None,
+                                        None, 0.0, p(bi), p(bd)) == 0
+    assert np.all(bi == -1) and np.all(bd == 256)
+    bi, bd = out()
+    assert L.eorb_fuse_pose_mixed(h, None, 0, None, 32, C.byref(gb), None, None, None, C.byref(v), M, p(pos), p(nrm), p(mn), p(mx), p(mio), None,
+                                  p(qd), 3.0, p(bi), p(bd), None) == 0
+    assert np.all(bi == -1) and np.all(bd == 256)
+    for tk in (None, np.zeros(1, np.uint8)):                                               # no flags, or flags of no keypoint
+        bi, bd = out()
+        assert L.eorb_search_by_projection_kf_scw_mixed(h, None, 0, None, 32, C.byref(gb), None, C.byref(v), M, p(pos), p(nrm), p(mn), p(mx),
+                                                        p(mio), None, p(qd), 4.0, p(tk), 50.0, p(bi), p(bd), None) == 0
+        assert np.all(bi == -1) and np.all(bd == 256) and (tk is None or tk[0] == 0)
