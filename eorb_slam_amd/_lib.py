@@ -28,6 +28,7 @@ EXPORTS = [
     "eorb_fuse_keyframes_mixed",
     "eorb_search_for_triangulation_keyframes", "eorb_search_for_triangulation_kb8_keyframes", "eorb_search_by_bow_keyframes",
     "eorb_search_by_bow_kf_keyframes",
+    "eorb_kfdb_clear", "eorb_kfdb_add", "eorb_kfdb_erase", "eorb_kfdb_info", "eorb_kfdb_get_scores", "eorb_kfdb_detect_reloc", "eorb_kfdb_detect_nbest",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
 ]
@@ -347,6 +348,15 @@ def lib():
     L.eorb_search_by_bow_keyframes.argtypes = [vp, ksp, vp, ci, vp, vp, vp, vp, ci, vp, cf, ci, vp]
     L.eorb_search_by_bow_kf_keyframes.restype = ci
     L.eorb_search_by_bow_kf_keyframes.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, ci, ksp, vp, cf, ci, vp]
+    L.eorb_kfdb_clear.restype = ci; L.eorb_kfdb_clear.argtypes = [vp]
+    L.eorb_kfdb_add.restype = ci; L.eorb_kfdb_add.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.eorb_kfdb_erase.restype = ci; L.eorb_kfdb_erase.argtypes = [vp, ci]
+    L.eorb_kfdb_info.restype = ci; L.eorb_kfdb_info.argtypes = [vp, pi, pi]
+    L.eorb_kfdb_get_scores.restype = ci; L.eorb_kfdb_get_scores.argtypes = [vp, ci, vp]
+    L.eorb_kfdb_detect_reloc.restype = ci
+    L.eorb_kfdb_detect_reloc.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, pi, pi, pi, C.POINTER(cf)]
+    L.eorb_kfdb_detect_nbest.restype = ci
+    L.eorb_kfdb_detect_nbest.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, pi, pi, pi, C.POINTER(cf)]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]
     L.eorb_selfcheck_math.restype = ci; L.eorb_selfcheck_math.argtypes = [vp, ci, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.eorb_pack_events.restype = None; L.eorb_pack_events.argtypes = [vp, C.c_size_t, vp]

@@ -89,6 +89,19 @@ struct CalibDev {
     double RR[9];
 };
 
+// KeyFrameDatabase on the device (kfdb.hip): no inverted file -- every list of the reference's holds its keyframes in the order of their
+// latest add(), so a live keyframe's BowVector and an add sequence number say the same
+struct KfdbSlot { uint32_t off; int32_t n; uint32_t seq, pad; };      // words [off, off + n) of the pools; n < 0: the slot is free
+struct KfdbState {
+    DevBuf tab, words, vals, score[2];          // KfdbSlot per slot | word ids | values | stored score per slot and query family
+    int slot_cap = 0; int64_t word_cap = 0, word_used = 0, word_live = 0;
+    int n_slots = 0, n_live = 0; uint32_t next_seq = 0;
+    std::vector<KfdbSlot> h_tab;                // the host's copy of tab
+    std::vector<int> free_slots;                // min-heap: the lowest free slot is reused first
+    int dbg_initial_slots = 0;                  // test hook "kfdb_initial_slots": first capacity in slots (and 64 words per slot); 0: default
+    int dbg_finish_lds = 0;                     // test hook "kfdb_finish_lds_entries": scored entries sorted in LDS (0: as many as fit), to force the sort in global memory
+};
+
 }  // namespace eorb
 
 struct eorb_ctx {
@@ -162,6 +175,7 @@ struct eorb_ctx {
     // DBoW2 vocabulary (device copy) for eorb_bow_transform
     eorb::DevBuf voc;
     int voc_nnodes = 0, voc_L = 0; size_t voc_off[5] = {0, 0, 0, 0, 0};
+    eorb::KfdbState kfdb;
     // batched front end
     bool fe_configured = false;
     eorb_fe_config fe{};

@@ -3,10 +3,12 @@
 #include "eorb_ctx.h"
 #include "match_args.h"
 #include "project_args.h"
+#include "kfdb.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 namespace eorb {
@@ -332,6 +334,7 @@ void eorb_destroy(eorb_ctx* c)
                       &c->fe_matches12, &c->fe_nmatches,
                       &c->orb.tabs, &c->orb.geom, &c->status, &c->win_ws, &c->win_total, &c->arena, &c->l1_ref_img, &c->l1_ref_pts, &c->ev_info, &c->ev_stamps, &c->pd_hash, &c->pd_lut, &c->pd_src_info, &c->pd_sl_tab, &c->pd_sl_tile, &c->pd_sl_rows, &c->pd_cnt};
     for (DevBuf* b : bufs) free_buf(*b);
+    kfdb_free(c);
     for (auto& s : c->pinned) { if (s.ev) hipEventDestroy(s.ev); if (s.p) hipHostFree(s.p); }
     for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
     if (c->dl_pinned) hipHostFree(c->dl_pinned);
@@ -384,6 +387,8 @@ int eorb_debug_option(eorb_ctx* c, const char* name, int value)
     if (!strcmp(name, "position_dict")) { c->dbg_pd = value; if (!value) { c->pd_valid = 0; c->dd_keep = 0; } return EORB_OK; }
     if (!strcmp(name, "slot_hot_waves")) { c->dbg_slot_hot_waves = value; return EORB_OK; }
     if (!strcmp(name, "slot_prerank")) { c->dbg_slot_prerank = value; return EORB_OK; }
+    if (!strcmp(name, "kfdb_initial_slots")) { c->kfdb.dbg_initial_slots = value; return EORB_OK; }
+    if (!strcmp(name, "kfdb_finish_lds_entries")) { c->kfdb.dbg_finish_lds = value; return EORB_OK; }
     return set_err(c, EORB_E_ARG, "debug option '%s' unknown", name);
 }
 
@@ -404,6 +409,8 @@ long long eorb_debug_counter(eorb_ctx* c, const char* name)
     if (!strcmp(name, "dict_positions")) return c->pd_valid ? c->pd_K : 0;
     if (!strcmp(name, "slot_scatter_form")) return c->sl_last_rank;       // the scatter of the last slot-form call: 1 rank form, 0 ballot form
     if (!strcmp(name, "slot_chunk")) return c->sl_last_chunk;
+    if (!strcmp(name, "kfdb_slot_cap")) return c->kfdb.slot_cap;          // KeyFrameDatabase pools: slots / words they hold room for
+    if (!strcmp(name, "kfdb_word_cap")) return c->kfdb.word_cap;
     if (!strcmp(name, "slot_parts")) return c->sl_last_parts;              // 2: the last slot-form call ran its batch as two halves
     if (!strcmp(name, "slot_hot_overflow")) {           // lists the last slot-form call handed back to the LDS gather because their length bucket was full (synchronises)
         long long n = 0;
@@ -3151,6 +3158,168 @@ int eorb_bow_transform(eorb_ctx* c, const uint8_t* desc, int n, int stride, int 
     if (word_of) memcpy(word_of, h + o_wo, 4 * N);
     if (node_of) memcpy(node_of, h + o_no, 4 * N);
     return EORB_OK;
+}
+
+// ---- KeyFrameDatabase (kfdb.hip) ------------------------------------------------------------------------------------------------
+int eorb_kfdb_clear(eorb_ctx* c)
+{
+    if (!c) return EORB_E_ARG;
+    KfdbState& s = c->kfdb;
+    s.n_slots = 0; s.n_live = 0; s.word_used = 0; s.word_live = 0; s.next_seq = 0;          // (the pools keep their size)
+    s.h_tab.clear(); s.free_slots.clear();
+    return EORB_OK;
+}
+
+int eorb_kfdb_info(eorb_ctx* c, int* n_live, int* n_slots)
+{
+    if (!c) return EORB_E_ARG;
+    if (n_live) *n_live = c->kfdb.n_live;
+    if (n_slots) *n_slots = c->kfdb.n_slots;
+    return EORB_OK;
+}
+
+int eorb_kfdb_add(eorb_ctx* c, int K, const int32_t* off, const uint32_t* word, const double* val, int32_t* slots_out)
+{
+    if (!c) return EORB_E_ARG;
+    if (K < 0 || (K > 0 && (!off || !slots_out))) return set_err(c, EORB_E_ARG, "kfdb_add: bad arguments");
+    if (K == 0) return EORB_OK;
+    KfdbState& s = c->kfdb;
+    // limits first, from the sizes alone
+    const int fresh = std::max(0, K - (int)s.free_slots.size());
+    if (s.n_slots + fresh > kKfdbMaxSlots) return set_err(c, EORB_E_CAPACITY, "kfdb_add: %d slots, limit %d", s.n_slots + fresh, kKfdbMaxSlots);
+    if ((uint64_t)s.next_seq + (uint64_t)K >= 0xffffffffull) return set_err(c, EORB_E_CAPACITY, "kfdb_add: add sequence numbers exhausted");
+    if (off[0] != 0) return set_err(c, EORB_E_ARG, "kfdb_add: off[0] = %d", off[0]);
+    for (int k = 0; k < K; k++) if (off[k + 1] < off[k]) return set_err(c, EORB_E_ARG, "kfdb_add: offsets not monotone at keyframe %d", k);
+    const int64_t total = off[K];
+    if (total > 0 && (!word || !val)) return set_err(c, EORB_E_ARG, "kfdb_add: bad arguments");
+    if (s.word_live + total >= ((int64_t)1 << 30)) return set_err(c, EORB_E_CAPACITY, "kfdb_add: %lld words in the database, limit 2^30", (long long)(s.word_live + total));
+    for (int k = 0; k < K; k++)
+        for (int i = off[k] + 1; i < off[k + 1]; i++)
+            if (word[i] <= word[i - 1]) return set_err(c, EORB_E_ARG, "kfdb_add: the word ids of keyframe %d do not ascend strictly (entry %d)", k, i - off[k]);
+    fe_enter(c);
+    int rc;
+    if ((rc = kfdb_reserve(c, fresh, total))) return rc;
+    std::vector<int32_t> slot(K);
+    std::vector<KfdbSlot> rec(K);
+    for (int k = 0; k < K; k++) {
+        int sl;
+        if (!s.free_slots.empty()) { std::pop_heap(s.free_slots.begin(), s.free_slots.end(), std::greater<int>()); sl = s.free_slots.back(); s.free_slots.pop_back(); }
+        else { sl = s.n_slots++; s.h_tab.push_back(KfdbSlot{0u, -1, 0u, 0u}); }
+        const int n = off[k + 1] - off[k];
+        rec[k] = KfdbSlot{(uint32_t)s.word_used, n, s.next_seq++, 0u};
+        s.word_used += n; s.word_live += n; s.n_live++;
+        s.h_tab[sl] = rec[k];
+        slot[k] = sl; slots_out[k] = sl;
+    }
+    Arena A(c);
+    const size_t o_slot = A.in(slot.data(), sizeof(int32_t) * (size_t)K), o_rec = A.in(rec.data(), sizeof(KfdbSlot) * (size_t)K);
+    const size_t o_src = A.in(off, sizeof(int32_t) * (size_t)K), o_w = A.in(word, sizeof(uint32_t) * (size_t)total), o_v = A.in(val, sizeof(double) * (size_t)total);
+    if ((rc = A.upload())) return rc;
+    if ((rc = kfdb_add_dev(c, K, A.dev<int32_t>(o_slot), A.dev<KfdbSlot>(o_rec), A.dev<int32_t>(o_src), A.dev<uint32_t>(o_w), A.dev<double>(o_v)))) return rc;
+    EORB_HIP(c, fe_stream_sync(c));              // (slot, rec and the staging slot are free again)
+    return EORB_OK;
+}
+
+int eorb_kfdb_erase(eorb_ctx* c, int slot)
+{
+    if (!c) return EORB_E_ARG;
+    KfdbState& s = c->kfdb;
+    if (slot < 0 || slot >= s.n_slots || s.h_tab[slot].n < 0) return set_err(c, EORB_E_ARG, "kfdb_erase: slot %d holds no keyframe", slot);
+    fe_enter(c);
+    int rc;
+    if ((rc = kfdb_erase_dev(c, slot))) return rc;
+    s.word_live -= s.h_tab[slot].n; s.n_live--;
+    s.h_tab[slot] = KfdbSlot{0u, -1, 0u, 0u};
+    s.free_slots.push_back(slot); std::push_heap(s.free_slots.begin(), s.free_slots.end(), std::greater<int>());
+    return EORB_OK;
+}
+
+int eorb_kfdb_get_scores(eorb_ctx* c, int family, float* scores)
+{
+    if (!c) return EORB_E_ARG;
+    if (family < 0 || family > 1 || !scores) return set_err(c, EORB_E_ARG, "kfdb_get_scores: bad arguments");
+    KfdbState& s = c->kfdb;
+    if (!s.n_slots) return EORB_OK;
+    fe_enter(c);
+    EORB_HIP(c, hipMemcpyAsync(scores, s.score[family].p, sizeof(float) * (size_t)s.n_slots, hipMemcpyDeviceToHost, c->stream));
+    EORB_HIP(c, fe_stream_sync(c));
+    return EORB_OK;
+}
+
+// both queries: one upload (the query, exclude, covis and the zeroed counters), three kernels, one download (counters and results)
+static int kfdb_detect(eorb_ctx* c, const char* what, int nbest, int n_words, const uint32_t* word, const double* val, const uint8_t* exclude,
+                       const int32_t* covis, int cap, int32_t* slot, float* si, int32_t* words, float* acc, int32_t* best_slot, uint8_t* keep,
+                       float* sorted_acc, int32_t* sorted_best_slot, int* n_listed, int* n_scored, int* max_common_words, float* best_acc)
+{
+    if (!c) return EORB_E_ARG;
+    if (n_words < 0 || cap < 0 || !n_listed || !n_scored || !max_common_words || !best_acc || (n_words > 0 && (!word || !val)) ||
+        (cap > 0 && (!slot || !si || !words)) || (cap > 0 && covis && (!acc || !best_slot || (nbest ? (!sorted_acc || !sorted_best_slot) : !keep))))
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    KfdbState& s = c->kfdb;
+    if (n_words > kKfdbMaxQueryWords) return set_err(c, EORB_E_CAPACITY, "%s: %d query words, limit %d", what, n_words, kKfdbMaxQueryWords);
+    for (int i = 1; i < n_words; i++) if (word[i] <= word[i - 1]) return set_err(c, EORB_E_ARG, "%s: the query's word ids do not ascend strictly (entry %d)", what, i);
+    *n_listed = 0; *n_scored = 0; *max_common_words = 0; *best_acc = 0.f;
+    if (!n_words || !s.n_live) return EORB_OK;
+    fe_enter(c);
+    const size_t NS = (size_t)s.n_slots, CAP = (size_t)cap;
+    int npad = 1;
+    while (npad < s.n_slots) npad <<= 1;
+    static const int32_t zero_hdr[4] = {0, 0, 0, 0};
+    Arena A(c);
+    KfdbQuery q{};
+    q.n_slots = s.n_slots; q.nq = n_words; q.family = nbest ? EORB_KFDB_PLACE : EORB_KFDB_RELOC; q.cap = cap; q.nbest = nbest; q.npad = npad;
+    q.lds_cap = s.dbg_finish_lds > 0 ? s.dbg_finish_lds : kKfdbMaxSlots;
+    const size_t o_qw = A.in(word, sizeof(uint32_t) * (size_t)n_words), o_qv = A.in(val, sizeof(double) * (size_t)n_words);
+    const size_t o_ex = exclude ? A.in(exclude, NS) : 0, o_cv = covis ? A.in(covis, sizeof(int32_t) * kKfdbCovis * NS) : 0;
+    // outputs, contiguous: counters | slot | si | words | acc | best_slot | keep | sorted_acc | sorted_best_slot
+    const size_t o_hdr = A.in(zero_hdr, sizeof(zero_hdr));
+    const size_t o_slot = A.reserve(4 * CAP), o_si = A.reserve(4 * CAP), o_words = A.reserve(4 * CAP);
+    const size_t o_acc = covis ? A.reserve(4 * CAP) : 0, o_best = covis ? A.reserve(4 * CAP) : 0, o_keep = covis && !nbest ? A.reserve(CAP) : 0;
+    const size_t o_sacc = covis && nbest ? A.reserve(4 * CAP) : 0, o_sbest = covis && nbest ? A.reserve(4 * CAP) : 0;
+    const size_t o_end = A.reserve(0);
+    const size_t o_cnt = A.reserve(4 * NS), o_first = A.reserve(4 * NS), o_listed = A.reserve(NS), o_sis = A.reserve(4 * NS);
+    const size_t o_key = A.reserve(8 * (size_t)npad), o_kslot = A.reserve(4 * (size_t)npad);
+    int rc;
+    if ((rc = A.upload())) return rc;
+    q.q_word = A.dev<uint32_t>(o_qw); q.q_val = A.dev<double>(o_qv);
+    q.exclude = exclude ? A.dev<uint8_t>(o_ex) : nullptr; q.covis = covis ? A.dev<int32_t>(o_cv) : nullptr;
+    q.hdr = A.dev<int32_t>(o_hdr);
+    q.cnt = A.dev<int32_t>(o_cnt); q.first = A.dev<uint32_t>(o_first); q.listed = A.dev<uint8_t>(o_listed); q.si_slot = A.dev<float>(o_sis);
+    q.key = A.dev<uint64_t>(o_key); q.kslot = A.dev<uint32_t>(o_kslot);
+    q.o_slot = A.dev<int32_t>(o_slot); q.o_si = A.dev<float>(o_si); q.o_words = A.dev<int32_t>(o_words);
+    q.o_acc = A.dev<float>(o_acc); q.o_best = A.dev<int32_t>(o_best); q.o_keep = A.dev<uint8_t>(o_keep);
+    q.o_sacc = A.dev<float>(o_sacc); q.o_sbest = A.dev<int32_t>(o_sbest);
+    if ((rc = kfdb_query_dev(c, q))) return rc;
+    const char* h;
+    if ((rc = A.download(o_hdr, o_end - o_hdr, &h))) return rc;
+    int32_t hdr[4];
+    memcpy(hdr, h + o_hdr, sizeof(hdr));
+    *n_listed = hdr[0]; *n_scored = hdr[1]; *max_common_words = hdr[2]; memcpy(best_acc, &hdr[3], sizeof(float));
+    if (hdr[1] > cap) return set_err(c, EORB_E_CAPACITY, "%s: %d keyframes scored, cap %d", what, hdr[1], cap);
+    const size_t S = (size_t)hdr[1];
+    memcpy(slot, h + o_slot, 4 * S); memcpy(si, h + o_si, 4 * S); memcpy(words, h + o_words, 4 * S);
+    if (covis) {
+        memcpy(acc, h + o_acc, 4 * S); memcpy(best_slot, h + o_best, 4 * S);
+        if (nbest) { memcpy(sorted_acc, h + o_sacc, 4 * S); memcpy(sorted_best_slot, h + o_sbest, 4 * S); }
+        else memcpy(keep, h + o_keep, S);
+    }
+    return EORB_OK;
+}
+
+int eorb_kfdb_detect_reloc(eorb_ctx* c, int n_words, const uint32_t* word, const double* val, const int32_t* covis, int cap,
+                           int32_t* slot, float* si, int32_t* words, float* acc, int32_t* best_slot, uint8_t* keep,
+                           int* n_listed, int* n_scored, int* max_common_words, float* best_acc)
+{
+    return kfdb_detect(c, "kfdb_detect_reloc", 0, n_words, word, val, nullptr, covis, cap, slot, si, words, acc, best_slot, keep, nullptr, nullptr,
+                       n_listed, n_scored, max_common_words, best_acc);
+}
+
+int eorb_kfdb_detect_nbest(eorb_ctx* c, int n_words, const uint32_t* word, const double* val, const uint8_t* exclude, const int32_t* covis,
+                           int cap, int32_t* slot, float* si, int32_t* words, float* acc, int32_t* best_slot, float* sorted_acc,
+                           int32_t* sorted_best_slot, int* n_listed, int* n_scored, int* max_common_words, float* best_acc)
+{
+    return kfdb_detect(c, "kfdb_detect_nbest", 1, n_words, word, val, exclude, covis, cap, slot, si, words, acc, best_slot, nullptr, sorted_acc,
+                       sorted_best_slot, n_listed, n_scored, max_common_words, best_acc);
 }
 
 int eorb_calc_optical_flow_pyr_lk(eorb_ctx* c, const uint8_t* prev, const uint8_t* next, int W, int H, int stride,

@@ -1549,6 +1549,108 @@ class ORBVocabulary:
         return bw[:nw.value].copy(), bv[:nw.value].copy(), fv
 
 
+class KeyFrameDatabase:
+    """KeyFrameDatabase (src/KeyFrameDatabase.cc) resident on the device: one per context.  Keyframes are named by the slots add()
+    returns; mapping slots to keyframes, the map test, isBad(), the already-added set and the nNumCandidates cut stay with the caller
+    (eorb_slam_amd/host/eorb_host.hpp does them).  Queries return dicts of numpy arrays in lScoreAndMatch order."""
+    RELOC, PLACE = 0, 1
+    MAX_QUERY_WORDS = 4096
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+
+    def info(self):
+        """(live keyframes, n_slots)"""
+        c = self.ctx
+        nl, ns = C.c_int(0), C.c_int(0)
+        c.check(c.L.eorb_kfdb_info(c.h, C.byref(nl), C.byref(ns)))
+        return nl.value, ns.value
+
+    @property
+    def n_slots(self):
+        return self.info()[1]
+
+    def add(self, word, val):
+        """add(pKF) :39-45 for one BowVector (word ids ascending) -> its slot"""
+        return int(self.add_many([(word, val)])[0])
+
+    def add_many(self, vectors):
+        """K keyframes in order, [(word, val)] -> their slots"""
+        c = self.ctx
+        K = len(vectors)
+        off = np.zeros(K + 1, np.int32)
+        off[1:] = np.cumsum([len(w) for w, _ in vectors])
+        word = np.ascontiguousarray(np.concatenate([np.asarray(w, np.uint32) for w, _ in vectors]) if K else np.zeros(0), np.uint32)
+        val = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64) for _, v in vectors]) if K else np.zeros(0), np.float64)
+        slots = np.zeros(max(K, 1), np.int32)
+        c.check(c.L.eorb_kfdb_add(c.h, K, _p(off), _p(word), _p(val), _p(slots)))
+        return slots[:K]
+
+    def erase(self, slot):
+        c = self.ctx
+        c.check(c.L.eorb_kfdb_erase(c.h, int(slot)))
+
+    def clear(self):
+        c = self.ctx
+        c.check(c.L.eorb_kfdb_clear(c.h))
+
+    def scores(self, family):
+        """mRelocScore (RELOC) / mPlaceRecognitionScore (PLACE) per slot"""
+        c = self.ctx
+        out = np.zeros(self.n_slots, np.float32)
+        c.check(c.L.eorb_kfdb_get_scores(c.h, int(family), _p(out)))
+        return out
+
+    def _detect(self, nbest, word, val, exclude, covis, cap):
+        c = self.ctx
+        word = np.ascontiguousarray(word, np.uint32); val = np.ascontiguousarray(val, np.float64)
+        ns = self.n_slots
+        cap = ns if cap is None else int(cap)
+        if covis is not None:
+            covis = np.ascontiguousarray(covis, np.int32)
+            if covis.shape != (ns, 10):
+                raise ValueError("covis must be (n_slots, 10)")
+        if exclude is not None:
+            exclude = np.ascontiguousarray(exclude, np.uint8)
+            if exclude.shape != (ns,):
+                raise ValueError("exclude must be (n_slots,)")
+        m = max(cap, 1)
+        o = dict(slot=np.zeros(m, np.int32), si=np.zeros(m, np.float32), words=np.zeros(m, np.int32), acc=np.zeros(m, np.float32),
+                 best_slot=np.zeros(m, np.int32))
+        if nbest:
+            o["sorted_acc"] = np.zeros(m, np.float32); o["sorted_best_slot"] = np.zeros(m, np.int32)
+        else:
+            o["keep"] = np.zeros(m, np.uint8)
+        nl, nsc, mc, ba = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0)
+        tail = (C.byref(nl), C.byref(nsc), C.byref(mc), C.byref(ba))
+        if nbest:
+            rc = c.L.eorb_kfdb_detect_nbest(c.h, len(word), _p(word), _p(val), _p(exclude), _p(covis), cap, _p(o["slot"]), _p(o["si"]),
+                                            _p(o["words"]), _p(o["acc"]), _p(o["best_slot"]), _p(o["sorted_acc"]), _p(o["sorted_best_slot"]), *tail)
+        else:
+            rc = c.L.eorb_kfdb_detect_reloc(c.h, len(word), _p(word), _p(val), _p(covis), cap, _p(o["slot"]), _p(o["si"]), _p(o["words"]),
+                                            _p(o["acc"]), _p(o["best_slot"]), _p(o["keep"]), *tail)
+        if rc != 0:
+            e = EorbError(rc, c.L.eorb_last_error(c.h).decode())
+            e.n_scored = nsc.value
+            raise e
+        res = {k: v[:nsc.value].copy() for k, v in o.items()}
+        if covis is None:
+            for k in ("acc", "best_slot", "keep", "sorted_acc", "sorted_best_slot"):
+                res.pop(k, None)
+        res.update(n_listed=nl.value, n_scored=nsc.value, max_common_words=mc.value, best_acc=np.float32(ba.value))
+        return res
+
+    def detect_relocalization_candidates(self, word, val, covis=None, cap=None):
+        """DetectRelocalizationCandidates :783-895 up to the map test: slot, si, words[, acc, best_slot, keep] + the counts.  covis:
+        (n_slots, 10) slot ids, -1 = none; None: no accumulation.  cap: length of the result arrays (default n_slots)."""
+        return self._detect(0, word, val, None, covis, cap)
+
+    def detect_nbest_candidates(self, word, val, exclude=None, covis=None, cap=None):
+        """DetectNBestCandidates :612-780 up to the loop at :731: the scored list, acc / best_slot, and sorted_acc / sorted_best_slot
+        = lAccScoreAndMatch after sort(compFirst).  exclude: (n_slots,) bytes, the connected keyframes."""
+        return self._detect(1, word, val, exclude, covis, cap)
+
+
 def HammingWindowMatch(q_desc, t_desc, cand_offsets, cand_idx, ctx=None):
     """Best / second-best candidate per query in candidate order (the loop body of the windowed matchers, ORBmatcher.cc:754-774).
     Returns (best_idx, best_dist, second_idx, second_dist)."""

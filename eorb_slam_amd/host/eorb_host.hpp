@@ -1030,6 +1030,128 @@ private:
     int weighting_, norm_;
 };
 
+// KeyFrameDatabase (src/KeyFrameDatabase.cc) resident on the device.  Keyframes are named by the slots add() returns; the adapter keeps a
+// `slot` member per KeyFrame and a vector<KeyFrame*> by slot.  What needs the KeyFrame itself is mirrored per slot here
+// and kept current by the adapter: its map (GetMap, an id), isBad(), Map::IsBad() per map id and GetBestCovisibilityKeyFrames(10) as
+// slots.  The object owns one context (the database lives in it) and a mutex in the place of mMutex: any thread may call it.
+class KeyFrameDatabase {
+public:
+    typedef std::vector<std::pair<uint32_t, double>> BowVector;      // DBoW2::BowVector in map order: word ids ascending
+
+    explicit KeyFrameDatabase(int device = 0) : ctx_(device) {}
+
+    // add(pKF) :39-45 -> the keyframe's slot (the lowest free one)
+    int add(const BowVector& bow, long mapId) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        std::vector<uint32_t> w; std::vector<double> v;
+        split(bow, w, v);
+        const int32_t off[2] = {0, (int32_t)w.size()};
+        int32_t slot = -1;
+        ctx_.check(eorb_kfdb_add(ctx_.get(), 1, off, w.data(), v.data(), &slot));
+        if ((size_t)slot >= map_.size()) { map_.resize(slot + 1, -1); bad_.resize(slot + 1, 0); covis_.resize((size_t)(slot + 1) * EORB_KFDB_COVIS, -1); }
+        map_[slot] = mapId; bad_[slot] = 0;
+        std::fill(covis_.begin() + (size_t)slot * EORB_KFDB_COVIS, covis_.begin() + (size_t)(slot + 1) * EORB_KFDB_COVIS, -1);
+        return slot;
+    }
+    // erase(pKF) :47-66; the slot also leaves every covisibility row
+    void erase(int slot) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        erase_locked(slot);
+    }
+    // clear() :68-72
+    void clear() {
+        std::lock_guard<std::mutex> lock(mMutex);
+        ctx_.check(eorb_kfdb_clear(ctx_.get()));
+        map_.clear(); bad_.clear(); covis_.clear();
+    }
+    // clearMap(pMap) :74-98: every keyframe of that map leaves the lists
+    void clearMap(long mapId) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        for (size_t s = 0; s < map_.size(); s++) if (map_[s] == mapId) erase_locked((int)s);
+    }
+    void SetBadFlag(int slot, bool bad = true) { std::lock_guard<std::mutex> lock(mMutex); bad_.at(slot) = bad ? 1 : 0; }      // KeyFrame::isBad()
+    void SetMapBad(long mapId, bool bad = true) {                                                                            // Map::IsBad()
+        std::lock_guard<std::mutex> lock(mMutex);
+        auto it = std::find(badMaps_.begin(), badMaps_.end(), mapId);
+        if (bad && it == badMaps_.end()) badMaps_.push_back(mapId);
+        if (!bad && it != badMaps_.end()) badMaps_.erase(it);
+    }
+    // GetBestCovisibilityKeyFrames(10) of the keyframe in `slot`, as slots in their order (keyframes outside the database: left out or -1)
+    void SetBestCovisibility(int slot, const std::vector<int>& neighbours) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        for (int j = 0; j < EORB_KFDB_COVIS; j++) covis_.at((size_t)slot * EORB_KFDB_COVIS + j) = j < (int)neighbours.size() ? neighbours[j] : -1;
+    }
+
+    // DetectRelocalizationCandidates(F, pMap) :783-895 -> the slots of vpRelocCandidates
+    std::vector<int> DetectRelocalizationCandidates(const BowVector& bow, long mapId) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        std::vector<uint32_t> w; std::vector<double> v;
+        split(bow, w, v);
+        const int cap = (int)map_.size(), m = cap ? cap : 1;
+        std::vector<int32_t> slot(m), words(m), best(m); std::vector<float> si(m), acc(m); std::vector<uint8_t> keep(m);
+        int nl = 0, ns = 0, mc = 0; float ba = 0.f;
+        ctx_.check(eorb_kfdb_detect_reloc(ctx_.get(), (int)w.size(), w.data(), v.data(), covis_.data(), cap, slot.data(), si.data(), words.data(),
+                                          acc.data(), best.data(), keep.data(), &nl, &ns, &mc, &ba));
+        std::vector<int> vpRelocCandidates;
+        std::vector<uint8_t> spAlreadyAddedKF(map_.size(), 0);
+        for (int i = 0; i < ns; i++) {                           // :878-892
+            if (!keep[i]) continue;
+            const int pKFi = best[i];
+            if (map_[pKFi] != mapId) continue;
+            if (!spAlreadyAddedKF[pKFi]) { vpRelocCandidates.push_back(pKFi); spAlreadyAddedKF[pKFi] = 1; }
+        }
+        return vpRelocCandidates;
+    }
+
+    // DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates) :612-780; connected = pKF->GetConnectedKeyFrames() as slots,
+    // mapId = pKF->GetMap()
+    void DetectNBestCandidates(const BowVector& bow, long mapId, const std::vector<int>& connected, std::vector<int>& vpLoopCand,
+                               std::vector<int>& vpMergeCand, int nNumCandidates) {
+        std::lock_guard<std::mutex> lock(mMutex);
+        std::vector<uint32_t> w; std::vector<double> v;
+        split(bow, w, v);
+        const int cap = (int)map_.size(), m = cap ? cap : 1;
+        std::vector<uint8_t> exclude(m, 0);
+        for (int s : connected) if (s >= 0 && s < cap) exclude[s] = 1;
+        std::vector<int32_t> slot(m), words(m), best(m), sbest(m); std::vector<float> si(m), acc(m), sacc(m);
+        int nl = 0, ns = 0, mc = 0; float ba = 0.f;
+        ctx_.check(eorb_kfdb_detect_nbest(ctx_.get(), (int)w.size(), w.data(), v.data(), exclude.data(), covis_.data(), cap, slot.data(), si.data(),
+                                          words.data(), acc.data(), best.data(), sacc.data(), sbest.data(), &nl, &ns, &mc, &ba));
+        vpLoopCand.clear(); vpMergeCand.clear();
+        std::vector<uint8_t> spAlreadyAddedKF(map_.size(), 0);
+        // :731-752.  The reference's while loop `continue`s on a bad keyframe without advancing its iterator and never ends; this mirror
+        // skips the bad keyframe and advances.
+        for (int i = 0; i < ns && ((int)vpLoopCand.size() < nNumCandidates || (int)vpMergeCand.size() < nNumCandidates); i++) {
+            const int pKFi = sbest[i];
+            if (bad_[pKFi]) continue;
+            if (!spAlreadyAddedKF[pKFi]) {
+                if (mapId == map_[pKFi] && (int)vpLoopCand.size() < nNumCandidates) vpLoopCand.push_back(pKFi);
+                else if (mapId != map_[pKFi] && (int)vpMergeCand.size() < nNumCandidates &&
+                         std::find(badMaps_.begin(), badMaps_.end(), map_[pKFi]) == badMaps_.end()) vpMergeCand.push_back(pKFi);
+                spAlreadyAddedKF[pKFi] = 1;
+            }
+        }
+    }
+
+private:
+    static void split(const BowVector& bow, std::vector<uint32_t>& w, std::vector<double>& v) {
+        w.resize(bow.size()); v.resize(bow.size());
+        for (size_t i = 0; i < bow.size(); i++) { w[i] = bow[i].first; v[i] = bow[i].second; }
+    }
+    void erase_locked(int slot) {
+        ctx_.check(eorb_kfdb_erase(ctx_.get(), slot));
+        map_[slot] = -1; bad_[slot] = 0;
+        for (auto& s : covis_) if (s == slot) s = -1;
+        std::fill(covis_.begin() + (size_t)slot * EORB_KFDB_COVIS, covis_.begin() + (size_t)(slot + 1) * EORB_KFDB_COVIS, -1);
+    }
+    eorb_host::Context ctx_;
+    std::mutex mMutex;
+    std::vector<long> map_;            // per slot: the keyframe's map id (-1: free slot)
+    std::vector<uint8_t> bad_;         // per slot: isBad()
+    std::vector<int32_t> covis_;       // per slot: ten neighbours as slots
+    std::vector<long> badMaps_;
+};
+
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423) for a batch of map points (CSR offsets into desc rows)
 inline std::vector<int> ComputeDistinctiveDescriptors(const eorb_host::Mat8& desc, const std::vector<int32_t>& offsets) {
     auto& c = eorb_host::thread_context();

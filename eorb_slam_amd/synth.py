@@ -822,3 +822,60 @@ def sim3_pair(seed, n=1000, s12=1.0, W=346, H=260, f=280.0, nlevels=8, scaleFact
             mp_desc=np.ascontiguousarray(g["mp_desc"][perm]), skip=g["skip"][perm])
     out.update(sR12=sR12, t12=t12, sR21=sR21, t21=t21, W=W, H=H)
     return out
+
+
+# ---- bag-of-words database (KeyFrameDatabase queries): keyframes of a "place" share most of their words
+def _bow_vector(rng, pool, vocab_words, n, p_place):
+    """n distinct word ids, a share p_place of them from `pool`, with positive L1-normalised weights (TF-IDF + L1_NORM)"""
+    n = int(min(n, vocab_words))
+    n_in = int(min(len(pool), round(n * p_place)))
+    w_in = rng.choice(pool, size=n_in, replace=False)
+    if vocab_words <= 20000:
+        rest = rng.choice(np.setdiff1d(np.arange(vocab_words, dtype=np.int64), w_in), size=n - n_in, replace=False)
+    else:                                              # a large vocabulary (the latency tool's): draw and reject instead of listing the rest
+        rest = np.zeros(0, np.int64)
+        while len(rest) < n - n_in:
+            c = rng.integers(vocab_words, size=2 * (n - n_in) + 16)
+            c = c[np.sort(np.unique(c, return_index=True)[1])]
+            rest = np.concatenate([rest, c[~np.isin(c, w_in) & ~np.isin(c, rest)]])
+        rest = rest[:n - n_in]
+    w = np.sort(np.concatenate([w_in, rest])).astype(np.uint32)
+    v = rng.uniform(0.2, 1.0, size=n)
+    if n:
+        v = v / v.sum()
+    return w, v.astype(np.float64)
+
+
+def bow_database(seed, K, vocab_words=2000, words_per_kf=120, nplaces=4, nqueries=3, p_place=0.85, kf_words=None, query_words=None):
+    """K keyframes over `nplaces` places for the KeyFrameDatabase queries (src/KeyFrameDatabase.cc:612-895).  A place owns a subset of the
+    vocabulary; a keyframe draws a share of its words (between 0.45 and p_place, so that the 0.8 rule splits the keyframes of a place) from
+    its place's subset and the rest from anywhere, with L1-normalised positive weights.  kf_words (optional, K ints): the length of each
+    keyframe's vector instead of about words_per_kf; query_words: the length of each query's.
+    Returns dict(vocab_words, place (K), kfs = [(word, val)], covis (K, 10) int32: up to ten neighbours in order, a mix of same-place and
+    other-place keyframes and -1, queries = [dict(word, val, place)])."""
+    rng = np.random.default_rng(seed)
+    nplaces = max(1, min(nplaces, max(K, 1)))
+    sub = int(max(min(vocab_words // nplaces, 2 * words_per_kf), 1))
+    pools = [np.arange(p * sub, (p + 1) * sub, dtype=np.int64) % vocab_words for p in range(nplaces)]
+    place = (np.arange(K) % nplaces).astype(np.int32)
+    rng.shuffle(place)
+    kfs = []
+    for k in range(K):
+        n = int(kf_words[k]) if kf_words is not None else int(rng.integers(max(words_per_kf * 3 // 4, 1), words_per_kf * 5 // 4 + 1))
+        kfs.append(_bow_vector(rng, pools[place[k]], vocab_words, n, rng.uniform(0.45, p_place)))
+    covis = np.full((K, 10), -1, np.int32)
+    for k in range(K):
+        same = np.flatnonzero((place == place[k]) & (np.arange(K) != k)); other = np.flatnonzero(place != place[k])
+        for j in range(10):
+            u = rng.uniform()
+            if u < 0.6 and len(same):
+                covis[k, j] = rng.choice(same)
+            elif u < 0.8 and len(other):
+                covis[k, j] = rng.choice(other)
+    queries = []
+    for i in range(nqueries):
+        p = int(rng.integers(nplaces))
+        n = int(query_words[i]) if query_words is not None else words_per_kf
+        w, v = _bow_vector(rng, pools[p], vocab_words, n, p_place)
+        queries.append(dict(word=w, val=v, place=p))
+    return dict(vocab_words=vocab_words, place=place, kfs=kfs, covis=covis, queries=queries)

@@ -111,11 +111,15 @@ int         eorb_sync(eorb_ctx* ctx);
  * stamp: 0 = choose the gather kernel by the batch's shape, 1 = the pipelined workgroup per tile, 2 = the wave per tile, 3 = no
  * binning, every tile's wave reads all events of its slice (calls with at most 4 slices), 4 = two-byte slot lists whatever the
  * batch's shape (falls back to 1 where they do not apply: polarity, sigma > 4/3, a tile with more than 254 slots)), "dedupe_min_events" (float events:
- * number of events per call from which their distinct positions are tabulated, default 2^20) */
+ * number of events per call from which their distinct positions are tabulated, default 2^20), "kfdb_initial_slots" (KeyFrameDatabase:
+ * the capacity in slots, and 64 pool words per slot, that the first eorb_kfdb_add allocates, to cross a pool growth with a handful of adds),
+ * "kfdb_finish_lds_entries" (KeyFrameDatabase queries: scored keyframes up to which the last kernel sorts in LDS, 0 = as many as fit (4096),
+ * to force its sort in global memory) */
 int         eorb_debug_option(eorb_ctx* ctx, const char* name, int value);
 /* test hook: counters a test can read to see which path served its calls.  "slot_calls": accumulation calls that took the slot
  * lists (gather_form 0 on dense batches, or 4); "slot_flags": sticky device flags of that path (0 = fine; synchronises); "slot_hot_items": lists the last such call handed to
- * the register-row kernel (synchronises); "slot_rank_ok": 1 when the scatter takes its ranks from LDS atomics.
+ * the register-row kernel (synchronises); "slot_rank_ok": 1 when the scatter takes its ranks from LDS atomics; "kfdb_slot_cap" /
+ * "kfdb_word_cap": slots / words the KeyFrameDatabase pools hold room for.
  * Returns the value, or -1 for an unknown name. */
 long long   eorb_debug_counter(eorb_ctx* ctx, const char* name);
 /* test hook, not part of the reference's interface: the intermediate images of the extractor, for stage-by-stage comparison with
@@ -878,6 +882,69 @@ int eorb_bow_set_vocabulary(eorb_ctx* ctx, int nnodes, int L, const int32_t* chi
 int eorb_bow_transform(eorb_ctx* ctx, const uint8_t* desc, int n, int stride, int levelsup, int weighting, int norm,
                        uint32_t* bow_word, double* bow_val, int* n_words, uint32_t* fv_node, int32_t* fv_off, int32_t* fv_idx,
                        int* n_fvnodes, int32_t* word_of, int32_t* node_of);
+
+/* ---- KeyFrameDatabase: the place-recognition queries (src/KeyFrameDatabase.cc) -------------------------------------------------
+ * The consumer of eorb_bow_transform's BowVector and the producer of the keyframe lists eorb_search_by_bow_keyframes /
+ * eorb_search_by_bow_kf_keyframes take.  The database belongs to the context and lives on the device.  There is no inverted file:
+ * add() (:39-45) appends a keyframe to the list of each of its words in one call, so every list holds its keyframes in the order of
+ * their latest add; the database keeps each live keyframe's BowVector (word ids strictly ascending, double values) and an add
+ * sequence number, and lKFsSharingWords (first-encounter order of the walk at :791-806 / :624-653) is the listed keyframes ordered by
+ * (smallest word shared with the query, add sequence).  Keyframes are named by slots: eorb_kfdb_add returns them, the lowest free slot
+ * first, so the slot of an erased keyframe is reused.  What stays with the caller (pointers and mutexes): the slot <-> KeyFrame* table,
+ * the map test (GetMap), isBad(), the already-added set and the nNumCandidates cut (eorb_slam_amd/host/eorb_host.hpp performs them).
+ *
+ * Stored scores: one float per slot and query family, EORB_KFDB_RELOC = mRelocScore, EORB_KFDB_PLACE = mPlaceRecognitionScore.  A query
+ * writes it for every keyframe it scores; the covisibility accumulation (:846-871 / :693-718) adds the stored score of every LISTED
+ * neighbour, which is the one an earlier query left when the neighbour shares a word but is under the threshold this time -- as the
+ * reference does.  Both are 0 at add (the reference initialises mPlaceRecognitionScore to 0 and leaves mRelocScore uninitialised:
+ * here both are defined as 0).
+ *
+ * Limits, decided from the sizes before any array is read: EORB_KFDB_MAX_SLOTS slots; EORB_KFDB_MAX_QUERY_WORDS words in a query (its
+ * word ids are staged in LDS); fewer than 2^30 words in the live vectors and 2^32 adds since the last clear; beyond them EORB_E_CAPACITY.  Values must be finite. */
+#define EORB_KFDB_MAX_SLOTS        65536
+#define EORB_KFDB_MAX_QUERY_WORDS  4096
+#define EORB_KFDB_COVIS            10      /* GetBestCovisibilityKeyFrames(10) */
+#define EORB_KFDB_RELOC            0
+#define EORB_KFDB_PLACE            1
+
+/* clear() :68-72: empties the database; the next slot returned is 0 again */
+int eorb_kfdb_clear(eorb_ctx* ctx);
+
+/* add(pKF) :39-45 for K keyframes in order (K = 1: one add; K > 1: PostLoad, tests): keyframe k's BowVector is (word, val)[off[k] ..
+ * off[k + 1]), off[0] = 0; a vector without words is legal.  Word ids that do not ascend strictly: EORB_E_ARG, naming k; nothing is
+ * added then.  slots_out[k]: the slot of keyframe k.  Only the new vectors are uploaded; a pool that has to grow is copied on the device. */
+int eorb_kfdb_add(eorb_ctx* ctx, int K, const int32_t* off, const uint32_t* word, const double* val, int32_t* slots_out);
+
+/* erase(pKF) :47-66.  A slot that holds no keyframe: EORB_E_ARG. */
+int eorb_kfdb_erase(eorb_ctx* ctx, int slot);
+
+/* *n_live keyframes in the database; *n_slots = one more than the highest slot returned since the last clear (the length of the per-slot
+ * arrays below) */
+int eorb_kfdb_info(eorb_ctx* ctx, int* n_live, int* n_slots);
+
+/* the stored scores of one family (EORB_KFDB_RELOC / EORB_KFDB_PLACE), n_slots floats; free slots read 0 or what their last keyframe left */
+int eorb_kfdb_get_scores(eorb_ctx* ctx, int family, float* scores);
+
+/* DetectRelocalizationCandidates(F, pMap) :783-895 for the query BowVector (word, val)[n_words] (F->mBowVec, ascending).
+ * covis: n_slots * EORB_KFDB_COVIS slot ids, row s = GetBestCovisibilityKeyFrames(10) of slot s in their order, -1 = none / not in the
+ * database (ids outside [0, n_slots) and free slots count as none); NULL: no accumulation, only the scored list is returned.
+ * Outputs, cap entries each, in lScoreAndMatch order (:826-837: listed keyframes with words > minCommonWords, minCommonWords =
+ * (int)(maxCommonWords * 0.8f), :819): slot, si (L1Scoring::score as a float, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68: the sum over
+ * the common words in ascending word order in double, -score / 2.0; the sign of a -0.0 is kept), words (mnRelocWords); with covis also acc
+ * (accScore), best_slot (pBestKF) and keep (1: accScore > 0.75f * bestAccScore, :873-882).  *n_listed = lKFsSharingWords.size(),
+ * *n_scored = lScoreAndMatch.size(), *max_common_words, *best_acc (0 without covis).  *n_scored > cap: EORB_E_CAPACITY with the needed
+ * count in *n_scored (the family's stored scores are this query's all the same).  Nothing listed: zero counts, EORB_OK. */
+int eorb_kfdb_detect_reloc(eorb_ctx* ctx, int n_words, const uint32_t* word, const double* val, const int32_t* covis, int cap,
+                           int32_t* slot, float* si, int32_t* words, float* acc, int32_t* best_slot, uint8_t* keep,
+                           int* n_listed, int* n_scored, int* max_common_words, float* best_acc);
+
+/* DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, n) :612-780 for pKF->mBowVec.  exclude: n_slots bytes, non-zero = the keyframe is in
+ * spConnectedKF: never listed, and never counted as a covisible neighbour (its query id is not set, :635-645); NULL = none.  The scored
+ * list and acc / best_slot as above; sorted_acc / sorted_best_slot: lAccScoreAndMatch after sort(compFirst) (:606-609, :722), a stable sort
+ * by descending accScore -- what the loop at :731-752 walks. */
+int eorb_kfdb_detect_nbest(eorb_ctx* ctx, int n_words, const uint32_t* word, const double* val, const uint8_t* exclude, const int32_t* covis,
+                           int cap, int32_t* slot, float* si, int32_t* words, float* acc, int32_t* best_slot, float* sorted_acc,
+                           int32_t* sorted_best_slot, int* n_listed, int* n_scored, int* max_common_words, float* best_acc);
 
 /* The loop body every windowed matcher of src/ORBmatcher.cc shares (e.g. :754-774, :95-130, :2050-2070): for query q the
  * candidates cand_idx[cand_offsets[q] .. cand_offsets[q+1]) (what GetFeaturesInArea returned, after the caller's gates) are
