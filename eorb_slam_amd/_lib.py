@@ -29,6 +29,7 @@ EXPORTS = [
     "eorb_search_for_triangulation_keyframes", "eorb_search_for_triangulation_kb8_keyframes", "eorb_search_by_bow_keyframes",
     "eorb_search_by_bow_kf_keyframes",
     "eorb_kfdb_clear", "eorb_kfdb_add", "eorb_kfdb_erase", "eorb_kfdb_info", "eorb_kfdb_get_scores", "eorb_kfdb_detect_reloc", "eorb_kfdb_detect_nbest",
+    "eorb_two_view_ransac", "eorb_two_view_check_rt",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
 ]
@@ -116,6 +117,14 @@ def calib(model, K, dist, R=None, P=None):
         for i in range(min(len(P), 12)):
             q.P[i] = float(P[i])
     return q
+
+
+class TvrParams(C.Structure):
+    """eorb_tvr_params: mSigma, mThChiSqScore, mThChiSqF"""
+    _fields_ = [("sigma", C.c_float), ("th_score", C.c_float), ("th_f", C.c_float)]
+
+
+TVR_MAX_ITERS, TVR_MAX_MATCHES, TVR_MAX_KEYS, TVR_MAX_POSES = 1024, 16384, 1048576, 64
 
 
 class KltParams(C.Structure):
@@ -357,6 +366,11 @@ def lib():
     L.eorb_kfdb_detect_reloc.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, pi, pi, pi, C.POINTER(cf)]
     L.eorb_kfdb_detect_nbest.restype = ci
     L.eorb_kfdb_detect_nbest.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, pi, pi, pi, C.POINTER(cf)]
+    L.eorb_two_view_ransac.restype = ci
+    L.eorb_two_view_ransac.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, C.POINTER(TvrParams), vp, C.POINTER(cf), pi, vp, vp, C.POINTER(cf), pi, vp,
+                                       vp, vp, vp, vp]
+    L.eorb_two_view_check_rt.restype = ci
+    L.eorb_two_view_check_rt.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, cf, cf, ci, vp, ci, vp, vp, vp, vp, vp]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]
     L.eorb_selfcheck_math.restype = ci; L.eorb_selfcheck_math.argtypes = [vp, ci, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.eorb_pack_events.restype = None; L.eorb_pack_events.argtypes = [vp, C.c_size_t, vp]

@@ -4,6 +4,7 @@
 #include "match_args.h"
 #include "project_args.h"
 #include "kfdb.h"
+#include "twoview.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -2581,6 +2582,126 @@ int eorb_kb8_triangulate_matches(eorb_ctx* c, const eorb_camera* cam1, const eor
                                 A.dev<float>(o_s2), A.dev<float>(o_z))))
         return rc;
     return A.download_to(z1, o_z, sizeof(float) * (size_t)n);
+}
+
+// the (x, y) of n keypoints, packed for the arena
+static std::vector<float> tv_points(const eorb_keypoint* kps, int n)
+{
+    std::vector<float> p(2 * (size_t)n);
+    for (int i = 0; i < n; i++) { p[2 * (size_t)i] = kps[i].x; p[2 * (size_t)i + 1] = kps[i].y; }
+    return p;
+}
+// sizes first (nothing is read), then the match indices against the key arrays
+static int tv_check_sizes(eorb_ctx* c, const char* what, int n1, int n2, int N)
+{
+    if (n1 > EORB_TVR_MAX_KEYS || n2 > EORB_TVR_MAX_KEYS) return set_err(c, EORB_E_CAPACITY, "%s: %d / %d keys, at most EORB_TVR_MAX_KEYS = %d", what, n1, n2, EORB_TVR_MAX_KEYS);
+    if (N > EORB_TVR_MAX_MATCHES) return set_err(c, EORB_E_CAPACITY, "%s: %d matches, at most EORB_TVR_MAX_MATCHES = %d", what, N, EORB_TVR_MAX_MATCHES);
+    return EORB_OK;
+}
+static int tv_check_matches(eorb_ctx* c, const char* what, const int32_t* match12, int N, int n1, int n2)
+{
+    for (int i = 0; i < N; i++)
+        if (match12[2 * i] < 0 || match12[2 * i] >= n1 || match12[2 * i + 1] < 0 || match12[2 * i + 1] >= n2)
+            return set_err(c, EORB_E_ARG, "%s: match %d = (%d, %d) is outside the %d / %d keys", what, i, match12[2 * i], match12[2 * i + 1], n1, n2);
+    return EORB_OK;
+}
+
+int eorb_two_view_ransac(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2, const int32_t* match12, int N,
+        const int32_t* sets, int iters, const eorb_tvr_params* params,
+        float* H21, float* SH, int32_t* best_it_h, uint8_t* inliers_h, float* F21, float* SF, int32_t* best_it_f, uint8_t* inliers_f,
+        float* it_score_h, float* it_score_f, float* it_H, float* it_F)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "two_view_ransac";
+    if (!kps1 || !kps2 || !match12 || !sets || !params || n1 < 0 || n2 < 0 || !H21 || !SH || !best_it_h || !inliers_h || !F21 || !SF ||
+        !best_it_f || !inliers_f)
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    if (N < 8 || iters < 1) return set_err(c, EORB_E_ARG, "%s: %d matches (at least 8), %d iterations (at least 1)", what, N, iters);
+    int rc;
+    if ((rc = tv_check_sizes(c, what, n1, n2, N))) return rc;
+    if (iters > EORB_TVR_MAX_ITERS) return set_err(c, EORB_E_CAPACITY, "%s: %d iterations, at most EORB_TVR_MAX_ITERS = %d", what, iters, EORB_TVR_MAX_ITERS);
+    if ((rc = tv_check_matches(c, what, match12, N, n1, n2))) return rc;
+    for (int i = 0; i < 8 * iters; i++)
+        if (sets[i] < 0 || sets[i] >= N) return set_err(c, EORB_E_ARG, "%s: set %d holds the index %d of %d matches", what, i / 8, sets[i], N);
+    fe_enter(c);
+    const std::vector<float> p1 = tv_points(kps1, n1), p2 = tv_points(kps2, n2);
+    const size_t sN = (size_t)N, sI = (size_t)iters;
+    Arena A(c);
+    const size_t o_p1 = A.in(p1.data(), sizeof(float) * p1.size()), o_p2 = A.in(p2.data(), sizeof(float) * p2.size());
+    const size_t o_m = A.in(match12, sizeof(int32_t) * 2 * sN), o_s = A.in(sets, sizeof(int32_t) * 8 * sI);
+    const size_t o_n1 = A.reserve(sizeof(float) * p1.size()), o_n2 = A.reserve(sizeof(float) * p2.size());
+    const size_t o_hdr = A.reserve(sizeof(float) * kTvHdrFloats), o_hyp = A.reserve(sizeof(float) * kTvHypFloats * 2 * sI), o_inl = A.reserve(2 * sI * sN);
+    // results, contiguous: the 22 words | inliers_h | inliers_f | the per-iteration aids
+    const size_t o_res = A.reserve(sizeof(float) * 22), o_ih = A.reserve(sN), o_if = A.reserve(sN);
+    const size_t o_sh = A.reserve(sizeof(float) * sI), o_sf = A.reserve(sizeof(float) * sI);
+    const size_t o_ith = A.reserve(sizeof(float) * 9 * sI), o_itf = A.reserve(sizeof(float) * 9 * sI);
+    if ((rc = A.upload())) return rc;
+    TvRansacArgs T{};
+    T.pts1 = A.dev<float2>(o_p1); T.pts2 = A.dev<float2>(o_p2); T.n1 = n1; T.n2 = n2;
+    T.match12 = A.dev<int32_t>(o_m); T.N = N; T.sets = A.dev<int32_t>(o_s); T.iters = iters;
+    T.sigma = params->sigma; T.th_score = params->th_score; T.th_f = params->th_f;
+    T.pn1 = A.dev<float2>(o_n1); T.pn2 = A.dev<float2>(o_n2); T.hdr = A.dev<float>(o_hdr); T.hyp = A.dev<float>(o_hyp); T.inl = A.dev<uint8_t>(o_inl);
+    T.res = A.dev<float>(o_res); T.inliers_h = A.dev<uint8_t>(o_ih); T.inliers_f = A.dev<uint8_t>(o_if);
+    T.it_score_h = A.dev<float>(o_sh); T.it_score_f = A.dev<float>(o_sf); T.it_H = A.dev<float>(o_ith); T.it_F = A.dev<float>(o_itf);
+    if ((rc = twoview_ransac_dev(c, T))) return rc;
+    const bool aids = it_score_h || it_score_f || it_H || it_F;
+    const char* h;
+    if ((rc = A.download(o_res, (aids ? o_itf + sizeof(float) * 9 * sI : o_if + sN) - o_res, &h))) return rc;
+    const float* r = (const float*)(h + o_res);
+    *SH = r[0]; *SF = r[1];
+    memcpy(best_it_h, r + 2, sizeof(int32_t)); memcpy(best_it_f, r + 3, sizeof(int32_t));
+    memcpy(H21, r + 4, sizeof(float) * 9); memcpy(F21, r + 13, sizeof(float) * 9);
+    memcpy(inliers_h, h + o_ih, sN); memcpy(inliers_f, h + o_if, sN);
+    if (it_score_h) memcpy(it_score_h, h + o_sh, sizeof(float) * sI);
+    if (it_score_f) memcpy(it_score_f, h + o_sf, sizeof(float) * sI);
+    if (it_H) memcpy(it_H, h + o_ith, sizeof(float) * 9 * sI);
+    if (it_F) memcpy(it_F, h + o_itf, sizeof(float) * 9 * sI);
+    return EORB_OK;
+}
+
+int eorb_two_view_check_rt(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2, const int32_t* match12, int N,
+        const uint8_t* inliers, const float* K, float th2, float min_parallax_crt, int min_triangulated,
+        const eorb_tvr_pose* poses, int Kp, int32_t* n_good, uint8_t* good, float* p3d, float* cos_sel, float* cos_all)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "two_view_check_rt";
+    if (!kps1 || !kps2 || !match12 || !inliers || !K || !poses || n1 < 1 || n2 < 1 || N < 1 || Kp < 1 || min_triangulated < 0 || !n_good || !good ||
+        !p3d || !cos_sel)
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    int rc;
+    if ((rc = tv_check_sizes(c, what, n1, n2, N))) return rc;
+    if (Kp > EORB_TVR_MAX_POSES) return set_err(c, EORB_E_CAPACITY, "%s: %d poses, at most EORB_TVR_MAX_POSES = %d", what, Kp, EORB_TVR_MAX_POSES);
+    if ((rc = tv_check_matches(c, what, match12, N, n1, n2))) return rc;
+    {   // vP3D / vbGood are indexed by `first`: with one first index in two matches their values would depend on the order of the writes
+        std::vector<uint8_t> seen((size_t)n1, 0);
+        for (int i = 0; i < N; i++) {
+            if (seen[match12[2 * i]]) return set_err(c, EORB_E_ARG, "%s: two matches have the first index %d", what, match12[2 * i]);
+            seen[match12[2 * i]] = 1;
+        }
+    }
+    fe_enter(c);
+    const std::vector<float> p1 = tv_points(kps1, n1), p2 = tv_points(kps2, n2);
+    const size_t sN = (size_t)N, sK = (size_t)Kp, s1 = (size_t)n1;
+    Arena A(c);
+    const size_t o_p1 = A.in(p1.data(), sizeof(float) * p1.size()), o_p2 = A.in(p2.data(), sizeof(float) * p2.size());
+    const size_t o_m = A.in(match12, sizeof(int32_t) * 2 * sN), o_in = A.in(inliers, sN), o_po = A.in(poses, sizeof(eorb_tvr_pose) * sK);
+    // results, contiguous: n_good | cos_sel | good | p3d | cos_all
+    const size_t o_ng = A.reserve(sizeof(int32_t) * sK), o_cs = A.reserve(sizeof(float) * sK), o_g = A.reserve(sK * s1);
+    const size_t o_p3 = A.reserve(sizeof(float) * 3 * sK * s1), o_ca = A.reserve(sizeof(float) * sK * sN);
+    if ((rc = A.upload())) return rc;
+    EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_g), 0, o_ca - o_g, c->stream));
+    TvCheckRtArgs T{};
+    T.pts1 = A.dev<float2>(o_p1); T.pts2 = A.dev<float2>(o_p2); T.n1 = n1; T.match12 = A.dev<int32_t>(o_m); T.N = N; T.inliers = A.dev<uint8_t>(o_in);
+    memcpy(T.K, K, sizeof T.K); T.th2 = th2; T.min_parallax_crt = min_parallax_crt; T.min_triangulated = min_triangulated;
+    T.poses = A.dev<float>(o_po); T.Kp = Kp;
+    T.n_good = A.dev<int32_t>(o_ng); T.cos_sel = A.dev<float>(o_cs); T.good = A.dev<uint8_t>(o_g); T.p3d = A.dev<float>(o_p3); T.cos_all = A.dev<float>(o_ca);
+    if ((rc = twoview_check_rt_dev(c, T))) return rc;
+    const char* h;
+    if ((rc = A.download(o_ng, (cos_all ? o_ca + sizeof(float) * sK * sN : o_p3 + sizeof(float) * 3 * sK * s1) - o_ng, &h))) return rc;
+    memcpy(n_good, h + o_ng, sizeof(int32_t) * sK); memcpy(cos_sel, h + o_cs, sizeof(float) * sK);
+    memcpy(good, h + o_g, sK * s1); memcpy(p3d, h + o_p3, sizeof(float) * 3 * sK * s1);
+    if (cos_all) memcpy(cos_all, h + o_ca, sizeof(float) * sK * sN);
+    return EORB_OK;
 }
 
 // what the MixedMatcher forms take on top of the ORB ones (a NULL KfMixedIn* = an ORB entry point): kp_is_orb / kp_inv_sigma2 per

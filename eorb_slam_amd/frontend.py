@@ -1253,6 +1253,87 @@ def FuseKeyFramesMixed(views, gbs, kps, desc, kf_off, pos, normal, min_dist, max
     return (bi, bd, rs) if want_reason else (bi, bd)
 
 
+def make_sets(N, iterations, seed=0):
+    """`iterations` sets of 8 distinct indices into N matches (int32 [iterations, 8]).  A stand-in for the draw of
+    src/TwoViewReconstruction.cc:107-124, for tests and tools: it does not reproduce DUtils::Random."""
+    assert N >= 8
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.permutation(N)[:8] for _ in range(iterations)]).astype(np.int32)
+
+
+def tvr_poses(K, Rs, ts):
+    """the pose hypotheses of CheckRT as an [Kp, 27] float32 array (eorb_tvr_pose: R, t, P2 = K*[R|t], O2 = -R.t()*t).  P2 and O2 are the
+    caller's 3x3 algebra; this helper forms them in float32 with numpy, which is not the reference's cv::gemm to the last bit."""
+    K = np.asarray(K, np.float32).reshape(3, 3)
+    out = np.zeros((len(Rs), 27), np.float32)
+    for h, (R, t) in enumerate(zip(Rs, ts)):
+        R = np.asarray(R, np.float32).reshape(3, 3); t = np.asarray(t, np.float32).reshape(3)
+        out[h, :9] = R.reshape(9); out[h, 9:12] = t
+        out[h, 12:24] = (K @ np.concatenate([R, t[:, None]], axis=1)).astype(np.float32).reshape(12)
+        out[h, 24:27] = (-(R.T @ t)).astype(np.float32)
+    return out
+
+
+class TwoViewReconstruction:
+    """The two stages of TwoViewReconstruction (src/TwoViewReconstruction.cc) whose cost grows with the match count:
+    find_homography_fundamental = the FindHomography / FindFundamental threads of Reconstruct (:131-136), check_rt = CheckRT (:1242-1352)
+    for all pose hypotheses of ReconstructF / ReconstructH in one call.  The set draw, the H/F choice, K.t()*F21*K, DecomposeE, the
+    decomposition of H, resolveReconstStat* and the acos of the parallax stay with the caller."""
+
+    def __init__(self, K, sigma=1.0, iterations=200, th_score=5.991, th_f=3.841, min_parallax_crt=0.99998, min_triangulated=50, ctx=None):
+        self.K = np.ascontiguousarray(np.asarray(K, np.float32).reshape(3, 3))
+        self.sigma, self.iterations = float(sigma), int(iterations)
+        self.params = _lib.TvrParams(float(sigma), float(th_score), float(th_f))
+        self.min_parallax_crt, self.min_triangulated = float(np.float32(min_parallax_crt)), int(min_triangulated)
+        self.ctx = ctx or default_context()
+
+    @staticmethod
+    def _in(kps1, kps2, matches12):
+        kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
+        m = np.ascontiguousarray(matches12, np.int32)
+        assert m.ndim == 2 and m.shape[1] == 2
+        return kps1, kps2, m
+
+    def find_homography_fundamental(self, kps1, kps2, matches12, sets, aids=False):
+        """kps1 / kps2: ALL keys of the two frames; matches12 [N, 2] = mvMatches12; sets [iterations, 8] indices into matches12.
+        Returns dict(H21, SH, best_it_h, inliers_h, F21, SF, best_it_f, inliers_f) and with aids the per-iteration it_score_h, it_score_f,
+        it_H, it_F."""
+        c = self.ctx
+        kps1, kps2, m = self._in(kps1, kps2, matches12)
+        sets = np.ascontiguousarray(sets, np.int32)
+        assert sets.ndim == 2 and sets.shape[1] == 8
+        N, it = len(m), len(sets)
+        o = dict(H21=np.zeros((3, 3), np.float32), F21=np.zeros((3, 3), np.float32), inliers_h=np.zeros(N, np.uint8), inliers_f=np.zeros(N, np.uint8))
+        a = dict(it_score_h=np.zeros(it, np.float32), it_score_f=np.zeros(it, np.float32), it_H=np.zeros((it, 3, 3), np.float32),
+                 it_F=np.zeros((it, 3, 3), np.float32)) if aids else {}
+        SH, SF, bh, bf = C.c_float(0), C.c_float(0), C.c_int(-1), C.c_int(-1)
+        c.check(c.L.eorb_two_view_ransac(c.h, _p(kps1), len(kps1), _p(kps2), len(kps2), _p(m), N, _p(sets), it, C.byref(self.params),
+                                         _p(o["H21"]), C.byref(SH), C.byref(bh), _p(o["inliers_h"]), _p(o["F21"]), C.byref(SF), C.byref(bf),
+                                         _p(o["inliers_f"]), _p(a.get("it_score_h")), _p(a.get("it_score_f")), _p(a.get("it_H")), _p(a.get("it_F"))))
+        o.update(SH=np.float32(SH.value), SF=np.float32(SF.value), best_it_h=bh.value, best_it_f=bf.value)
+        o.update(a)
+        return o
+
+    def check_rt(self, kps1, kps2, matches12, inliers, poses, th2=None, min_parallax_crt=None, min_triangulated=None, want_cos_all=False):
+        """poses: [Kp, 27] float32 (tvr_poses).  th2 defaults to 4*sigma^2 (:621).  Returns dict(n_good [Kp], good [Kp, n1], p3d [Kp, n1, 3],
+        cos_sel [Kp]) and cos_all [Kp, N] when asked; parallax = degrees(acos(cos_sel)) in double is the caller's."""
+        c = self.ctx
+        kps1, kps2, m = self._in(kps1, kps2, matches12)
+        inl = np.ascontiguousarray(inliers, np.uint8); poses = np.ascontiguousarray(poses, np.float32)
+        assert inl.shape == (len(m),) and poses.ndim == 2 and poses.shape[1] == 27
+        Kp, n1, N = len(poses), len(kps1), len(m)
+        th2 = 4.0 * self.sigma * self.sigma if th2 is None else th2
+        mp = self.min_parallax_crt if min_parallax_crt is None else float(np.float32(min_parallax_crt))
+        mt = self.min_triangulated if min_triangulated is None else int(min_triangulated)
+        o = dict(n_good=np.zeros(Kp, np.int32), good=np.zeros((Kp, n1), np.uint8), p3d=np.zeros((Kp, n1, 3), np.float32), cos_sel=np.zeros(Kp, np.float32))
+        ca = np.zeros((Kp, N), np.float32) if want_cos_all else None
+        c.check(c.L.eorb_two_view_check_rt(c.h, _p(kps1), n1, _p(kps2), len(kps2), _p(m), N, _p(inl), _p(self.K), float(th2), mp, mt, _p(poses), Kp,
+                                           _p(o["n_good"]), _p(o["good"]), _p(o["p3d"]), _p(o["cos_sel"]), _p(ca)))
+        if want_cos_all:
+            o["cos_all"] = ca
+        return o
+
+
 class ELK_Tracker:
     """EORB_SLAM::ELK_Tracker (src/Event/KLT_Tracker.cpp): pyramidal LK on the device + the reference's match bookkeeping."""
 
@@ -1318,7 +1399,8 @@ class EvImBuilder:
     (resolveEvWinSize :209-232) and, on a dispatch, the four-way reconstruction contest with the L2 detection of the winner
     (generateMCImage :1146-1247, isMcImageGood :260-267).  What stays with the caller, as in the reference: the optimisers that
     produce the poses of the motion-compensated reconstructions (`mci_poses`), the two-view RANSAC refinement of step() (:600-668,
-    `reconstruct`), the IMU and the L2 tracker's queue."""
+    `reconstruct`: a callback; its N-proportional stages are TwoViewReconstruction.find_homography_fundamental / check_rt), the IMU
+    and the L2 tracker's queue."""
     IDLE, INIT, TRACKING = 0, 1, 2
     DEF_TH_MIN_KPTS, DEF_TH_MIN_MATCHES = 100, 50                     # include/Event/EventData.h:24-26
 

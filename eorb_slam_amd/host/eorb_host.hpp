@@ -285,7 +285,8 @@ private:
 // l1ChunkSize events the event image and its frame -- INIT: detect-only ORBextractor + ELK_Tracker::setRefImage (init :568-592);
 // TRACKING: ELK_Tracker::trackAndMatchCurrImage (KLT_Tracker.cpp:215-234) + refineTrackedPts (:104-151) -- the window-size rule
 // (resolveEvWinSize :209-232) and, on a dispatch, generateMCImage (:1146-1247) + isMcImageGood (:260-267).  The optimisers that hand
-// generateMCImage its poses, step()'s two-view refinement, the IMU and the L2 queue stay with the caller, as in the reference.
+// generateMCImage its poses, step()'s two-view refinement (its RANSAC and CheckRT stages: ORB_SLAM3::TwoViewReconstruction below), the
+// IMU and the L2 queue stay with the caller, as in the reference.
 // (Python twin with the same members: eorb_slam_amd/frontend.py::EvImBuilder; tests/test_gpu_chain.py checks that one against the
 // oracle's chain chunk by chunk, tests/test_host_cpp.py checks this one against the separate seams.)
 class EvImBuilder {
@@ -1150,6 +1151,67 @@ private:
     std::vector<uint8_t> bad_;         // per slot: isBad()
     std::vector<int32_t> covis_;       // per slot: ten neighbours as slots
     std::vector<long> badMaps_;
+};
+
+// The two stages of TwoViewReconstruction (src/TwoViewReconstruction.cc) whose cost grows with the match count, on the calling thread's
+// context.  FindHomographyFundamental = the two threads of Reconstruct (:131-136 / :228-233) in one call; CheckRT = :1242-1352 for every
+// pose hypothesis of ReconstructF (4) / ReconstructH (8) in one call.  The set draw (mvSets), SH/(SH+SF) and the H/F choice, K.t()*F21*K,
+// DecomposeE, the Faugeras decomposition, resolveReconstStat* and acos stay with the adapter.
+class TwoViewReconstruction {
+public:
+    typedef std::pair<int, int> Match;
+    struct HF {                            // what FindHomography / FindFundamental leave; best_it < 0: no iteration scored above 0
+        float H21[9], F21[9], SH = 0.f, SF = 0.f; int32_t best_it_h = -1, best_it_f = -1;
+        std::vector<uint8_t> vbMatchesInliersH, vbMatchesInliersF;
+        std::vector<float> it_score_h, it_score_f, it_H, it_F;      // filled when asked for (test aids)
+    };
+    struct RT {                            // CheckRT per pose: nGood, vbGood / vP3D by first index, vCosParallax[min(mMinTriangulated, size - 1)]
+        std::vector<int32_t> nGood; std::vector<uint8_t> vbGood; std::vector<float> vP3D, cosParallax, cosAll;
+        double parallax(int pose) const { return nGood[pose] > 0 ? std::acos((double)cosParallax[pose]) * 180 / 3.14159265358979323846 : 0.0; }      // :1346
+    };
+
+    explicit TwoViewReconstruction(const float K[9], float sigma = 1.0f, int iterations = 200) : mSigma(sigma), mMaxIterations(iterations) {
+        for (int i = 0; i < 9; i++) mK[i] = K[i];
+    }
+    eorb_tvr_params params{1.0f, 5.991f, 3.841f};        // sigma is set from mSigma at each call
+    float mMinParallaxCRT = 0.99998f; int mMinTriangulated = 50;
+
+    // vKeys1 / vKeys2: ALL keys of the two frames; vMatches12: mvMatches12; vSets: mMaxIterations x 8 indices into vMatches12
+    HF FindHomographyFundamental(const std::vector<eorb_keypoint>& vKeys1, const std::vector<eorb_keypoint>& vKeys2, const std::vector<Match>& vMatches12,
+                                 const std::vector<int32_t>& vSets, bool aids = false) const {
+        auto& c = eorb_host::thread_context();
+        const int N = (int)vMatches12.size(), it = (int)(vSets.size() / 8);
+        const std::vector<int32_t> m = flat(vMatches12);
+        HF o;
+        o.vbMatchesInliersH.assign(N, 0); o.vbMatchesInliersF.assign(N, 0);
+        if (aids) { o.it_score_h.assign(it, 0.f); o.it_score_f.assign(it, 0.f); o.it_H.assign((size_t)it * 9, 0.f); o.it_F.assign((size_t)it * 9, 0.f); }
+        eorb_tvr_params p = params; p.sigma = mSigma;
+        c.check(eorb_two_view_ransac(c.get(), vKeys1.data(), (int)vKeys1.size(), vKeys2.data(), (int)vKeys2.size(), m.data(), N, vSets.data(), it, &p,
+                                     o.H21, &o.SH, &o.best_it_h, o.vbMatchesInliersH.data(), o.F21, &o.SF, &o.best_it_f, o.vbMatchesInliersF.data(),
+                                     aids ? o.it_score_h.data() : nullptr, aids ? o.it_score_f.data() : nullptr, aids ? o.it_H.data() : nullptr,
+                                     aids ? o.it_F.data() : nullptr));
+        return o;
+    }
+    RT CheckRT(const std::vector<eorb_keypoint>& vKeys1, const std::vector<eorb_keypoint>& vKeys2, const std::vector<Match>& vMatches12,
+               const std::vector<uint8_t>& vbMatchesInliers, const std::vector<eorb_tvr_pose>& poses, float th2, bool cosAll = false) const {
+        auto& c = eorb_host::thread_context();
+        const size_t N = vMatches12.size(), Kp = poses.size(), n1 = vKeys1.size();
+        const std::vector<int32_t> m = flat(vMatches12);
+        RT o;
+        o.nGood.assign(Kp, 0); o.vbGood.assign(Kp * n1, 0); o.vP3D.assign(Kp * n1 * 3, 0.f); o.cosParallax.assign(Kp, 0.f);
+        if (cosAll) o.cosAll.assign(Kp * N, 0.f);
+        c.check(eorb_two_view_check_rt(c.get(), vKeys1.data(), (int)n1, vKeys2.data(), (int)vKeys2.size(), m.data(), (int)N, vbMatchesInliers.data(), mK,
+                                       th2, mMinParallaxCRT, mMinTriangulated, poses.data(), (int)Kp, o.nGood.data(), o.vbGood.data(), o.vP3D.data(),
+                                       o.cosParallax.data(), cosAll ? o.cosAll.data() : nullptr));
+        return o;
+    }
+private:
+    static std::vector<int32_t> flat(const std::vector<Match>& v) {
+        std::vector<int32_t> m(2 * v.size());
+        for (size_t i = 0; i < v.size(); i++) { m[2 * i] = v[i].first; m[2 * i + 1] = v[i].second; }
+        return m;
+    }
+    float mK[9]; float mSigma; int mMaxIterations;
 };
 
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423) for a batch of map points (CSR offsets into desc rows)

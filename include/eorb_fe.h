@@ -597,6 +597,55 @@ int eorb_kb8_triangulate_matches(eorb_ctx* ctx, const eorb_camera* cam1, const e
         const eorb_keypoint* kps1, const eorb_keypoint* kps2, int n, const float* sigma2_1, const float* sigma2_2, int nlevels,
         float* z1);
 
+/* ---- TwoViewReconstruction (src/TwoViewReconstruction.cc): the two stages whose cost grows with the match count ----------------------
+ * The call after SearchForInitialization in Tracking::MonocularInitialization (src/Tracking.cc:3559) and after the KLT match of the
+ * event trackers (EvImBuilder.cpp:622, EvAsynchTracker.cpp:1044, ...).  What stays with the caller is 3x3 algebra and decisions: the
+ * set draw (DUtils::Random, :107-124), SH/(SH+SF) and the H/F choice, K.t()*F21*K, DecomposeE, the Faugeras decomposition of
+ * ReconstructH, resolveReconstStat*, and the acos of the parallax.
+ *
+ * Limits, decided from the sizes before any array is read (EORB_E_CAPACITY): */
+#define EORB_TVR_MAX_ITERS    1024
+#define EORB_TVR_MAX_MATCHES  16384
+#define EORB_TVR_MAX_KEYS     1048576
+#define EORB_TVR_MAX_POSES    64
+typedef struct eorb_tvr_params {
+    float sigma;        /* mSigma */
+    float th_score;     /* mParams2VR.mThChiSqScore, 5.991f */
+    float th_f;         /* mParams2VR.mThChiSqF, 3.841f */
+} eorb_tvr_params;
+/* one pose hypothesis of CheckRT: R, t, and the caller's 3x3 algebra P2 = K*[R|t] (3x4 row-major) and O2 = -R.t()*t */
+typedef struct eorb_tvr_pose { float R[9]; float t[3]; float P2[12]; float O2[3]; } eorb_tvr_pose;
+
+/* replaces the two threads of Reconstruct (:131-136 / :228-233): FindHomography (:264-312) and FindFundamental (:315-363) with Normalize
+ * (:1193-1239), ComputeH21 (:366-406), ComputeF21 (:408-443), CheckHomography (:445-528) and CheckFundamental (:530-608).
+ * kps1[n1] / kps2[n2]: ALL keys of the two frames (only x, y are read; Normalize runs over every key, matched or not, in index order);
+ * match12[N][2]: the mvMatches12 pairs (first, second) in order; sets[iters][8]: indices into match12, drawn by the caller.
+ * Results: H21[9] / F21[9] row-major, SH / SF, best_it_h / best_it_f, inliers_h[N] / inliers_f[N] (0 / 1).  The winner is the first
+ * iteration whose score is > the running best, which starts at 0.0f (:305, :356): equal scores keep the earlier iteration and a NaN
+ * score never wins.  When no iteration scores above 0: best_it = -1, the matrix is zeros and the flags are zeros; the reference leaves
+ * H21 / F21 empty cv::Mats there, and FindFundamental's inlier vector has length 0, because it takes N from the size of its output
+ * argument (:318) -- which is also why a caller that passes a non-empty vector gets N flags.
+ * Test aids, NULL to skip: it_score_h[iters], it_score_f[iters], it_H[iters*9], it_F[iters*9] (every iteration's score, H21i, F21i).
+ * EORB_E_ARG: N < 8, iters < 1, a set index outside [0, N), a match index outside the key arrays.  The OpenCV 3.4.1 arithmetic
+ * (JacobiSVDImpl_<float> with its cv::RNG completion, gemm's small-matrix branch, Mat::inv 3x3) is restated on its scalar paths:
+ * DESIGN.md section 2. */
+int eorb_two_view_ransac(eorb_ctx* ctx, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2, const int32_t* match12, int N,
+        const int32_t* sets, int iters, const eorb_tvr_params* params,
+        float* H21, float* SH, int32_t* best_it_h, uint8_t* inliers_h, float* F21, float* SF, int32_t* best_it_f, uint8_t* inliers_f,
+        float* it_score_h, float* it_score_f, float* it_H, float* it_F);
+
+/* CheckRT (:1242-1352) with Triangulate (:1177-1191) for Kp pose hypotheses (the 4 of ReconstructF :633-636, the 8 of ReconstructH).
+ * inliers[N]: vbMatchesInliers; K: 3x3 row-major (fx, fy, cx, cy and P1 = K[I|0] are copies); min_parallax_crt: mMinParallaxCRT as the
+ * float the reference narrows 0.99998 into.  Per pose h: n_good[h]; good[h*n1 + first] = vbGood; p3d[(h*n1 + first)*3 ..] = vP3D, zeros
+ * where not written -- written for every counted match, not only the good ones (:1334); cos_sel[h] = vCosParallax[min(min_triangulated,
+ * size - 1)] after the ascending sort, or 0 when n_good == 0: parallax = acos(cos_sel)*180/CV_PI in double stays with the caller.  The
+ * sort orders -0 before +0 and every NaN last (returned as the canonical NaN); std::sort in the reference is undefined with a NaN.
+ * cos_all (NULL to skip): Kp*N, the cosParallax of each counted match, -2 for a match that was not counted.
+ * EORB_E_ARG: a match index outside the key arrays, two matches with the same first index (mvMatches12 has none), min_triangulated < 0. */
+int eorb_two_view_check_rt(eorb_ctx* ctx, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2, const int32_t* match12, int N,
+        const uint8_t* inliers, const float* K, float th2, float min_parallax_crt, int min_triangulated,
+        const eorb_tvr_pose* poses, int Kp, int32_t* n_good, uint8_t* good, float* p3d, float* cos_sel, float* cos_all);
+
 /* replaces the search core shared by ORBmatcher::Fuse (src/ORBmatcher.cc:1512-1578 and :1700-1720), SearchBySim3
  * (:1829-1860, :1909-1940) and SearchByProjection(KeyFrame*, Scw, ...) (:548-588, :667-706): for every projected map point
  * m (valid[m], uv, radius = th*getORBScaleFactor(level), predicted level, descriptor) the best keypoint among
