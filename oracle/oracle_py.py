@@ -126,6 +126,9 @@ def lib(fast=False):
     L.orc_mci_warp_se3.restype = None
     L.orc_mci_warp_se3.argtypes = [vp, C.c_size_t, C.POINTER(Pinhole), cd, vp, vp, cf, vp, vp]
     L.orc_mci_warp_se2.restype = None; L.orc_mci_warp_se2.argtypes = [vp, C.c_size_t, C.POINTER(Pinhole), vp, ci, vp]
+    L.orc_mci_warp_se3_cam.restype = None
+    L.orc_mci_warp_se3_cam.argtypes = [vp, C.c_size_t, C.POINTER(Camera), cd, vp, vp, cf, vp, vp]
+    L.orc_mci_warp_se2_cam.restype = None; L.orc_mci_warp_se2_cam.argtypes = [vp, C.c_size_t, C.POINTER(Camera), vp, ci, vp]
     L.orc_ev2mci_se3.restype = ci
     L.orc_ev2mci_se3.argtypes = [vp, C.c_size_t, C.POINTER(Pinhole), cd, vp, vp, cf, vp, ci, ci, cf, ci, ci, vp, vp, vp]
     L.orc_ev2mci_se2.restype = ci
@@ -529,6 +532,27 @@ def ev2mci_se2(ev, cam, params2D, W, H, sigma=1.0, pol=False, normalized=False):
     r = lib().orc_ev2mci_se2_cam(_p(ev), len(ev), C.byref(pc), _p(pr), len(pr), W, H, float(sigma), int(pol), int(normalized),
                              _p(f32), _p(u8), _p(mm))
     return f32, (u8 if r else None), mm
+
+
+def mci_warp_se3(ev, cam, angle, axis, tt, medDepth, depth=None):
+    """the warped positions (n, 2) f32 that ev2mci_se3 accumulates"""
+    ev = np.ascontiguousarray(ev, EVENT_DTYPE)
+    ax = np.ascontiguousarray(axis, np.float64); t = np.ascontiguousarray(tt, np.float64)
+    dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+    uv = np.zeros((len(ev), 2), np.float32)
+    pc = _camera(cam)
+    lib().orc_mci_warp_se3_cam(_p(ev), len(ev), C.byref(pc), float(angle), _p(ax), _p(t), float(medDepth), _p(dp), _p(uv))
+    return uv
+
+
+def mci_warp_se2(ev, cam, params2D):
+    """the warped positions (n, 2) f32 that ev2mci_se2 accumulates"""
+    ev = np.ascontiguousarray(ev, EVENT_DTYPE)
+    pr = np.ascontiguousarray(params2D, np.float32)
+    uv = np.zeros((len(ev), 2), np.float32)
+    pc = _camera(cam)
+    lib().orc_mci_warp_se2_cam(_p(ev), len(ev), C.byref(pc), _p(pr), len(pr), _p(uv))
+    return uv
 
 
 def measure_image_focus(img):
