@@ -333,6 +333,26 @@ __device__ __forceinline__ float dev_logf(float x)
 
 __device__ __forceinline__ int dev_cvround(float v) { return __float2int_rn(v); }
 
+// (int)floorf(v) as the reference's x86 executes it (cvttss2si): INT_MIN for NaN, +-inf and every value outside int32, where the
+// bare v_cvt_i32_f32 saturates and turns NaN into 0.  For an index whose range test must reject what the reference rejects.
+__device__ __forceinline__ int dev_floor_index(float v)
+{
+    const float f = floorf(v);
+    return (f >= -2147483648.f && f < 2147483648.f) ? (int)f : (int)0x80000000u;
+}
+// cvRound(v) under the same rule (nearest-even), where an index is formed from a caller's coordinate
+__device__ __forceinline__ int dev_cvround_index(float v)
+{
+    const float f = rintf(v);
+    return (f >= -2147483648.f && f < 2147483648.f) ? (int)f : (int)0x80000000u;
+}
+// (int)roundf(v) under the same rule (Frame::PosInGrid, roundFloatCoord)
+__device__ __forceinline__ int dev_round_index(float v)
+{
+    const float f = roundf(v);
+    return (f >= -2147483648.f && f < 2147483648.f) ? (int)f : (int)0x80000000u;
+}
+
 // popcount of a 256-bit XOR: ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:2360-2378)
 __device__ __forceinline__ int dev_hamming256(const uint64_t a[4], const uint64_t b[4])
 {

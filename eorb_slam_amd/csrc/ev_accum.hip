@@ -47,8 +47,9 @@ constexpr uint32_t kHashDropped = 0x7fffffffu;
 __device__ __forceinline__ bool ev_tile_range(const eorb_event16& e, const BinParams& P, int& tx0, int& tx1, int& ty0, int& ty1)
 {
     const float x = e.x, y = e.y;
-    if (!(x == x && y == y)) return false;          // NaN coordinates (e.g. a one-event MCI window: 0 * inf) convert to
-                                                    // INT_MIN on the reference's x86: never in the image
+    // NaN coordinates (e.g. a one-event MCI window: 0 * inf), +-inf and everything outside int32 convert to INT_MIN on the
+    // reference's x86: never in the image.  Rejected here, in float, so that xi +- h below cannot overflow either
+    if (!(x > -2147483648.f && x < 2147483648.f && y > -2147483648.f && y < 2147483648.f)) return false;
     const int xi = P.mode_count ? (int)roundf(x) : (int)floorf(x);
     const int yi = P.mode_count ? (int)roundf(y) : (int)floorf(y);
     tx0 = max((xi - P.h) >> 3, 0); tx1 = min((xi + P.h) >> 3, P.TX - 1);

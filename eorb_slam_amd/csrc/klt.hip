@@ -148,7 +148,7 @@ __global__ __launch_bounds__(64) void klt_track_kernel(KltArgs A)
         } else { nextx = outx * 2.f; nexty = outy * 2.f; }
         outx = nextx; outy = nexty;
         prevx -= halfWin; prevy -= halfWin;
-        const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
+        const int ipx = dev_floor_index(prevx), ipy = dev_floor_index(prevy);      // (a NaN point fails the test below, as on x86)
         if (ipx < -win || ipx >= L.w || ipy < -win || ipy >= L.h) {
             if (level == 0) { st = false; errv = 0.f; }
             continue;
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(64) void klt_track_kernel(KltArgs A)
         uint32_t j00[T], j01[T], j10[T], j11[T];
         int held_x = 0x7fffffff, held_y = 0x7fffffff;
         for (int j = 0; j < A.maxCount; j++) {
-            const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
+            const int inx = dev_floor_index(nextx), iny = dev_floor_index(nexty);
             if (inx < -win || inx >= L.w || iny < -win || iny >= L.h) {
                 if (level == 0) st = false;
                 break;
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(64) void klt_track_kernel(KltArgs A)
         }
         if (st && level == 0 && !(A.flags & 8)) {
             const float npx = outx - halfWin, npy = outy - halfWin;
-            const int inx = (int)floorf(npx), iny = (int)floorf(npy);
+            const int inx = dev_floor_index(npx), iny = dev_floor_index(npy);
             if (inx < -win || inx >= L.w || iny < -win || iny >= L.h) { st = false; continue; }
             const float aa = npx - (float)inx, bb = npy - (float)iny;
             iw00 = dev_cvround((1.f - aa) * (1.f - bb) * (1 << W_BITS));

@@ -124,14 +124,21 @@ __device__ __forceinline__ int rot_bin(float a1, float a2)
 // Frame::GetFeaturesInArea cell range (src/Frame.cc:722-745); returns false when the reference returns empty
 __device__ __forceinline__ bool cell_range(const GridB& g, float x, float y, float r, int& cx0, int& cx1, int& cy0, int& cy1)
 {
+    // the reference's x86 converts NaN and every value outside int32 to INT_MIN: an upper cell index of 2^31 or more (an infinite or
+    // huge radius) is negative there and the area empty, where the bare conversion saturates and would search the whole grid
+    // Only the upper indices need the test.  With r >= 0 a lower index that passes 2^31 is followed by an upper one that does, and
+    // both machines return "empty".  With r < 0 the lower one can pass 2^31 alone: x86 then makes cx0 = 0 and walks cells where this
+    // returns "empty" -- but |dx| < r is false for every keypoint when r <= 0, so the reference's walk finds nothing either.
     cx0 = max(0, (int)floorf((x - g.minX - r) * g.invW));
     if (cx0 >= kGridCols) return false;
-    cx1 = min(kGridCols - 1, (int)ceilf((x - g.minX + r) * g.invW));
-    if (cx1 < 0) return false;
+    const float fx1 = ceilf((x - g.minX + r) * g.invW);
+    if (!(fx1 >= 0.f && fx1 < 2147483648.f)) return false;
+    cx1 = min(kGridCols - 1, (int)fx1);
     cy0 = max(0, (int)floorf((y - g.minY - r) * g.invH));
     if (cy0 >= kGridRows) return false;
-    cy1 = min(kGridRows - 1, (int)ceilf((y - g.minY + r) * g.invH));
-    if (cy1 < 0) return false;
+    const float fy1 = ceilf((y - g.minY + r) * g.invH);
+    if (!(fy1 >= 0.f && fy1 < 2147483648.f)) return false;
+    cy1 = min(kGridRows - 1, (int)fy1);
     return true;
 }
 
@@ -240,8 +247,8 @@ struct WinQuery {              // wave-uniform description of one query
 __device__ __forceinline__ uint32_t f2_info(const eorb_keypoint& k, bool isorb, const GridB& g)
 {
     // Frame::PosInGrid (Frame.cc:783-793)
-    const int px = (int)roundf((k.x - g.minX) * g.invW);
-    const int py = (int)roundf((k.y - g.minY) * g.invH);
+    const int px = dev_round_index((k.x - g.minX) * g.invW);       // (a NaN keypoint is outside the grid, as on x86)
+    const int py = dev_round_index((k.y - g.minY) * g.invH);
     const uint32_t cell = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? 0xFFFFu : (uint32_t)(px * kGridRows + py);
     return cell | ((uint32_t)(kp_level(k, isorb) & 0xff) << 16) | ((uint32_t)isorb << 24);
 }
@@ -1513,8 +1520,8 @@ int kb8_tri_batch_dev(eorb_ctx* c, const eorb_camera* cam1, const eorb_camera* c
 // the cell word: Frame::PosInGrid as the 12-bit cell number ix*48+iy (64 x 48 = 3072 cells), 0xFFFF outside the grid
 __device__ __forceinline__ uint16_t kf_cell_of(const eorb_keypoint& k, const GridB& g)
 {
-    const int px = (int)roundf((k.x - g.minX) * g.invW);
-    const int py = (int)roundf((k.y - g.minY) * g.invH);
+    const int px = dev_round_index((k.x - g.minX) * g.invW);
+    const int py = dev_round_index((k.y - g.minY) * g.invH);
     return (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? (uint16_t)0xFFFF : (uint16_t)(px * kGridRows + py);
 }
 // the mixed forms carry the row's type in the cell word: bit 15 set = not an ORB row (!isORBDescValid(idx)); 0xFFFF stays "outside"
@@ -2238,7 +2245,7 @@ __global__ __launch_bounds__(256) void twocam_walk_kernel(TcArgs A)
         int32_t v = A.slots[gi];
         if (v >= 0 && A.mp_obs[v]) v |= kTcObs;
         S.slot[gi] = v;
-        const int px = (int)roundf((k.x - A.g.minX) * A.g.invW), py = (int)roundf((k.y - A.g.minY) * A.g.invH);   // PosInGrid :783-793
+        const int px = dev_round_index((k.x - A.g.minX) * A.g.invW), py = dev_round_index((k.y - A.g.minY) * A.g.invH);   // PosInGrid :783-793
         if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) atomicAdd(&S.cst[cam * kTcCells + px * kGridRows + py], 1u);
     }
     __syncthreads();
@@ -2261,7 +2268,7 @@ __global__ __launch_bounds__(256) void twocam_walk_kernel(TcArgs A)
     __syncthreads();
     for (int gi = tid; gi < nT; gi += blockDim.x) {
         const float2 P = S.pos[gi];
-        const int px = (int)roundf((P.x - A.g.minX) * A.g.invW), py = (int)roundf((P.y - A.g.minY) * A.g.invH);
+        const int px = dev_round_index((P.x - A.g.minX) * A.g.invW), py = dev_round_index((P.y - A.g.minY) * A.g.invH);
         if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows)
             S.item[atomicAdd(&S.cst[(gi >= nL) * kTcCells + px * kGridRows + py], 1u)] = (uint16_t)gi;   // (order inside a cell: the key's index)
     }

@@ -1283,6 +1283,9 @@ __global__ __launch_bounds__(256) void blur_kernel(const DevGeom* __restrict__ G
 // ---------------------------------------------------------------------------------------------------
 // rBRIEF: 32 lanes per keypoint, lane b computes descriptor byte b (16 taps)
 // computeOrbDescriptor (:108-157) for one descriptor byte; img = blurred level (w x h, step = w, no border)
+// IDX: the type of the linear tap index.  int for the extractor's own keypoints (inside their level); long long for a caller's
+// keypoints, whose position may be anywhere in int32 (the reference's index is a pointer offset: it does not wrap at 32 bits)
+template <typename IDX = int>
 __device__ __forceinline__ int brief_byte(const uint8_t* __restrict__ img, int w, int h, int cx, int cy, float angle_deg, int b, int& oob)
 {
     const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
@@ -1291,8 +1294,8 @@ __device__ __forceinline__ int brief_byte(const uint8_t* __restrict__ img, int w
     dev_sincosf(angle, &sb, &ca);
     const float a = ca, bb = sb;
     const int step = w;
-    const int base = cy * step + cx;
-    const int total = w * h;
+    const IDX base = (IDX)cy * step + cx;
+    const IDX total = (IDX)w * h;
     const signed char* pat = c_pattern + b * 32;
     int val = 0;
 #pragma unroll
@@ -1305,7 +1308,7 @@ __device__ __forceinline__ int brief_byte(const uint8_t* __restrict__ img, int w
             const float c0 = px * a, c1 = py * bb;
             const int dy = dev_cvround(r0 + r1);
             const int dx = dev_cvround(c0 - c1);
-            const int idx = base + dy * step + dx;
+            const IDX idx = base + (IDX)dy * step + dx;
             if (idx < 0 || idx >= total) { oob = 1; t[s] = 0; }
             else t[s] = img[idx];
         }
@@ -1352,8 +1355,9 @@ __global__ __launch_bounds__(256) void tracked_desc_kernel(const DevGeom* __rest
     auto byte_at = [&](int level, int& oob) {
         const LevelGeom& L = G->lv[level];
         const float scale = 1.0f / G->sf[level];                                      // mvInvScaleFactor[level] (:436)
-        const int cx = dev_cvround(kp.x * scale), cy = dev_cvround(kp.y * scale);
-        return brief_byte(blur + L.roi_off, L.w, L.h, cx, cy, kp.angle, b, oob);
+        // (cvRound of NaN or of a value beyond int32 is INT_MIN on the reference's x86: no tap inside the level)
+        const int cx = dev_cvround_index(kp.x * scale), cy = dev_cvround_index(kp.y * scale);
+        return brief_byte<long long>(blur + L.roi_off, L.w, L.h, cx, cy, kp.angle, b, oob);
     };
     if (mode == 0) {
         const int level = kp.octave;

@@ -70,6 +70,7 @@ float orc_atanf(float x);           /* glibc atanf / atan2f (fdlibm float)      
 float orc_atan2f(float y, float x);
 float orc_fast_atan2(float y, float x);   /* OpenCV 3.4 cv::fastAtan2 polynomial, degrees     */
 int   orc_cvround(double v);              /* cvRound: round-half-to-even                        */
+int   orc_to_index(double r);             /* integral double -> int32, INT_MIN outside it (x86)  */
 /* order-independent 64-bit hash of f over every float whose bit pattern is in [lo_bits, hi_bits] (which: 0 expf(-x),
  * 1 sinf(x), 2 cosf(x), 3 tanf(x), 4 atanf(x)); the device computes the same hash of its own functions (eorb_selfcheck_math). */
 uint64_t orc_math_hash(int which, uint32_t lo_bits, uint32_t hi_bits);

@@ -30,7 +30,11 @@ static inline uint64_t asu64(double d) { uint64_t u; memcpy(&u, &d, 8); return u
 static inline double   asf64(uint64_t u) { double d; memcpy(&d, &u, 8); return d; }
 static inline uint32_t asu32(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 
-int orc_cvround(double v) { return (int)lrint(v); }   /* default rounding mode: nearest-even */
+/* An integral double as the int32 that cvtsd2si / cvttss2si make of it: INT_MIN for NaN, +-inf and everything outside int32.  C leaves
+ * that cast undefined; the reference's x86 is the specification (README.md, "Pinning status"). */
+int orc_to_index(double r) { return (r >= -2147483648.0 && r < 2147483648.0) ? (int)r : (int)(-2147483647 - 1); }
+/* cvRound: nearest-even (the default rounding mode).  (int)lrint(v) kept the low 32 bits of a 64-bit conversion: 0 for NaN and 1e30. */
+int orc_cvround(double v) { return orc_to_index(rint(v)); }
 
 /* tab[i] = bits(2^(i/32)) - (i << 47) */
 static const uint64_t k_exp2_tab[32] = {

@@ -169,6 +169,11 @@ def warp_se3(ev, cam, angle, axis, t, depth, wrong=None):
     angle rate about the unit `axis` (Rodrigues: cos a I + sin a [axis]x + (1 - cos a) axis axis^T), P = unproject(x_k, y_k),
     uv = project(d R P + t rate), d = `depth` (one median depth, or one depth per event).  Returns (n, 2) float64.
     wrong: "rate" measures the rate from the first event, (t_k - t_first) / (t_last - t_first)."""
+    return project(cam, warp_se3_points(ev, cam, angle, axis, t, depth, wrong))
+
+
+def warp_se3_points(ev, cam, angle, axis, t, depth, wrong=None):
+    """the 3-D points d R P + t rate that warp_se3 projects, (n, 3) float64"""
     rate = _rate(ev["ts"], wrong)
     a = np.asarray(axis, F64); t = np.asarray(t, F64)
     P = unproject(cam, ev["x"].astype(F64), ev["y"].astype(F64))
@@ -176,7 +181,7 @@ def warp_se3(ev, cam, angle, axis, t, depth, wrong=None):
     c, s = np.cos(ang)[:, None], np.sin(ang)[:, None]
     RP = c * P + s * np.cross(a[None, :], P) + (1.0 - c) * (P @ a)[:, None] * a[None, :]
     d = np.broadcast_to(np.asarray(depth, F64), rate.shape)
-    return project(cam, d[:, None] * RP + t[None, :] * rate[:, None])
+    return d[:, None] * RP + t[None, :] * rate[:, None]
 
 
 def warp_se2(ev, cam, params, wrong=None):
