@@ -102,6 +102,18 @@ struct KfdbState {
     int dbg_finish_lds = 0;                     // test hook "kfdb_finish_lds_entries": scored entries sorted in LDS (0: as many as fit), to force the sort in global memory
 };
 
+// A set of positions and the device tables derived from it.  The context holds three (eorb_ctx: maps, dd, pd); every function that builds
+// or reads the tables receives the set it works on.
+struct PosTables {
+    DevBuf lut, src_info, stamps;                // float2 per position | its integer position (ev_src_info_kernel) | its stamp (ev_stamp_kernel)
+    DevBuf sl_tab, sl_tile, sl_rows;             // slot form (ev_slots.hip): per position its tiles / slot numbers, per tile its rows; valid when sl_ok
+    int w = 0, h = 0, check = 1;                 // the positions as a (w x h) sensor; check: checkInImage of the maps
+    int key_W = -1, key_H = -1, key_mode = -1; float key_sigma = -1.f;      // what the derived tables were built for (-1: nothing)
+    int sl_ok = 0, sl_null = 0; size_t sl_info_off = 0;
+    int sl_launched = 0;                         // assignment kernels launched, their info on its way to the read-back buffer (ev_slots_prepare_launch / _finish)
+    int src_info_done = 0;                       // src_info launched ahead of ev_raw_tables (float bulk path)
+};
+
 }  // namespace eorb
 
 struct eorb_ctx {
@@ -117,10 +129,9 @@ struct eorb_ctx {
     // accumulation workspaces
     eorb::DevBuf ev16, chunks, segoff, entries, img_f32, img_u8, minmax, tile_order, order_hist;
     // raw sensor events: undistortion maps (float2 per sensor pixel) and the tables derived from them
-    eorb::DevBuf lut, src_info, stamps;
+    eorb::PosTables maps;
     eorb::DevBuf ev_info, ev_stamps;              // float events of the per-slice calls: the same tables per EVENT (ev_direct_slices_dev)
-    // slot form of the raw accumulation (ev_slots.hip): per sensor pixel its tiles / slot numbers, per tile its rows; valid when sl_ok
-    eorb::DevBuf sl_tab, sl_tile, sl_rows, sl_trace; long long sl_trace_n = 0;
+    eorb::DevBuf sl_trace; long long sl_trace_n = 0;
     // per-batch workspaces of the slot form, one set per part of a batch (a batch of 64 slices or more runs as two halves)
     struct SlotWS { eorb::DevBuf chunks, segoff, entries, tile_order, plan, hot, rec16; };
     SlotWS sl_ws[2];
@@ -129,27 +140,26 @@ struct eorb_ctx {
     static constexpr int kSlotEvents = 10;
     hipStream_t sl_side = nullptr, sl_pstream = nullptr, sl_gstream = nullptr; hipEvent_t sl_ev[kSlotEvents] = {};
     int sl_last_parts = 0, sl_last_nb[2] = {0, 0};      // the last slot-form call: its parts, (slices x tiles) of each
-    int sl_ok = 0, sl_null = 0, sl_rank_ok = -1;
+    int sl_rank_ok = -1;
     int ncu = 0;                                 // compute units of c->device (per context: a second context may sit on another GPU)
     unsigned sl_attr = 0;                        // bit per kernel instantiation whose dynamic-LDS opt-in was made on c->device
     int sl_last_rank = -1, sl_last_chunk = 0;    // the scatter the last slot-form call ran (1 rank form, 0 ballot form), its chunk size
     int* rb_pinned = nullptr;                   // 64 ints of pinned host memory: the landing place of small read-backs (position count, slot info)
-    int sl_launched = 0; int sl_hinfo[6] = {0, 0, 0, 0, 0, 0};      // assignment kernels launched, their read-back (ev_slots_prepare_launch / _finish)
-    int dd_src_info_done = 0;                   // float bulk path: src_info of the per-call table already launched
-    long long sl_calls = 0; size_t sl_info_off = 0;     // test hook counters (eorb_debug_counter)
-    // float events in bulk: the distinct positions of a call become the rows of a per-call stamp table (ev_accumulate_dev)
-    eorb::DevBuf dd_tab, dd_src_info, dd_stamps, dd_ev, dd_cnt, dd_sl_tab, dd_sl_tile, dd_sl_rows;
-    int dd_sl_ok = 0, dd_sl_null = 0; size_t dd_sl_info_off = 0;
+    long long sl_calls = 0;                      // test hook counter (eorb_debug_counter)
+    // float events in bulk: the distinct positions of a call are tabulated in a hash table (dd.lut, 8 bytes per row: the positions as a
+    // 65 536-wide sensor) and the raw path runs on the tables of that per-call set (ev_accumulate_dev)
+    eorb::PosTables dd;
+    eorb::DevBuf dd_ev, dd_cnt;
     // ... and across calls: once a call's positions are known, the next calls of the context look theirs up in a frozen dictionary
-    // (compact hash -> dense id < 65 536, tables per id) and only fall back to the per-call tabulation when a new position turns up
-    eorb::DevBuf pd_hash, pd_lut, pd_src_info, pd_sl_tab, pd_sl_tile, pd_sl_rows, pd_cnt;
-    int pd_valid = 0, pd_K = 0, pd_W = 0, pd_H = 0, pd_sl_null = 0, pd_cooldown = 0; float pd_sigma = 0.f; size_t pd_sl_info_off = 0;
+    // (compact hash -> dense id < 65 536; pd: the positions per id as a (pd_K x 1) sensor, their tables) and only fall back to the
+    // per-call tabulation when a new position turns up
+    eorb::PosTables pd;
+    eorb::DevBuf pd_hash, pd_cnt;
+    int pd_valid = 0, pd_K = 0, pd_W = 0, pd_H = 0, pd_cooldown = 0; float pd_sigma = 0.f;
     int dd_keep = 0;                             // the per-call position table holds an earlier call's positions and is extended, not cleared
     long long pd_hits = 0, pd_misses = 0;        // calls served by the dictionary / calls that found a new position (eorb_debug_counter)
     eorb::DevBuf focus_sd;                       // measureImageFocus: per-patch deviations
     int64_t dbg_dd_min = (int64_t)1 << 20;       // events from which the positions are deduplicated (test hook: "dedupe_min_events")
-    int lut_w = 0, lut_h = 0, lut_check = 1;
-    int lut_key_W = -1, lut_key_H = -1, lut_key_mode = -1; float lut_key_sigma = -1.f;
     // extractor workspaces
     eorb::OrbState orb;
     eorb::DevBuf pyr, score, blur, cell_cnt, cell_cand, lvl_cnt, lvl_kp, kp_angle, out_kp, out_desc, out_oob,
@@ -162,7 +172,6 @@ struct eorb_ctx {
     eorb::DevBuf arena;                  // host-buffer entry points: all inputs / outputs of one call, one H2D and one D2H copy
     void* dl_pinned = nullptr; size_t dl_cap = 0;      // pinned landing buffer of the D2H copy (the call synchronises before reading it)
     hipEvent_t dl_event = nullptr;                     // recorded behind that copy: what the call waits for
-    bool mm_preset = false;                            // the next ev_accumulate_dev finds its running extremes initialised (per-slice calls)
     // pyramidal LK workspaces; klt_ref_key: the reference frame whose pyramid and derivatives the buffers hold (0 = none)
     eorb::DevBuf klt_pyr, klt_der, klt_scratch;
     unsigned long long klt_ref_key = 0, klt_ref_geo = 0, klt_ref_serial = 0;
@@ -192,9 +201,6 @@ struct eorb_ctx {
     // read back by eorb_sync / eorb_fe_status
     eorb::DevBuf status;
     // test hooks (eorb_debug_option): shrink the octree node pool to force an overflow; force the octree's global-memory layout
-    // set by a caller whose float event images (and running extremes) are still to be normalised: orb_extract_dev's first kernel does
-    // it while it builds level 0 (and writes the u8 images to its d_img argument); cleared by that call
-    const float* pyr0_f32 = nullptr; const uint32_t* pyr0_mm = nullptr;
     int dbg_pool_shrink = 0, dbg_force_global = 0, dbg_oct_list = 0;      // (dbg_oct_list: the octree's list algorithm for every pass; applies at the next eorb_orb_configure)
     int dbg_gather_form = 0;                     // raw Gaussian accumulation: 0 by batch shape, 1 K2r, 2 K2s, 3 K2d (<= 4 slices), 4 slot lists (K2p)
     int dbg_orb_three_launches = 0;              // extraction: orientation, descriptors and output order as three kernels (the path of a lapping area) for every call
@@ -232,7 +238,8 @@ struct ProfScope {
 // ev_accum.hip
 int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
                       float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized,
-                      uint32_t* d_minmax_enc);
+                      uint32_t* d_minmax_enc, bool mm_preset = false);
+// mm_preset: the caller has initialised the running extremes (the per-slice calls; only the binning-free form takes its word for it)
 int ev_direct_slices_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* beg, const int64_t* end, int B, int W, int H,
                          float sigma, int pol, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, bool mm_preset = false);
 int ev_undistort_dev(eorb_ctx* c, const eorb_raw_event* d_raw, size_t n, int W, int H, double tsFactor, eorb_event* d_out, uint32_t* d_blk);
@@ -253,14 +260,14 @@ int ev_contest_select_dev(eorb_ctx* c, const float* d_focus_img, const int img_o
                           float* d_focus_out, int* d_winner, uint8_t* d_out);
 int ev_kp_points_dev(eorb_ctx* c, const eorb_keypoint* d_kps, const int32_t* d_n, int cap, float* d_pts);
 // ev_slots.hip
-int ev_slots_prepare_launch(eorb_ctx* c, int W, int H, int h, int TX, int TY);
-int ev_slots_prepare(eorb_ctx* c, int W, int H, int h, int TX, int TY, const float* d_stamps /* nullptr: taps from c->lut */, int stamp_stride, int SWP,
+int ev_slots_prepare_launch(eorb_ctx* c, PosTables& T, int W, int H, int h, int TX, int TY);
+int ev_slots_prepare(eorb_ctx* c, PosTables& T, int W, int H, int h, int TX, int TY, const float* d_stamps /* nullptr: taps from T.lut */, int stamp_stride, int SWP,
                       float two_sig2, float norm);
 struct SlotDict {              // float events looked up in the context's position dictionary by the count pass (ev_slots.hip)
     const uint4* hash; uint32_t mask; uint32_t* rec; int* miss;
     int rec2;                  // the dictionary holds fewer than 65 535 positions: rec is written as 2-byte records (0xffff = none), else 4-byte
 };
-int ev_slots_accumulate(eorb_ctx* c, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H, int TX, int TY,
+int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H, int TX, int TY,
                         float* d_f32, uint32_t* d_minmax_enc, const SlotDict* dict = nullptr);
 int ev_slots_trace_read(eorb_ctx* c, unsigned long long* out, long long max_records);
 // klt.hip
@@ -273,7 +280,10 @@ int stereo_match_dev(eorb_ctx* c, const eorb_keypoint* d_kps, const uint8_t* d_d
                      float* d_uright, float* d_depth, int32_t* d_sad, int32_t* d_nmatch);
 int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t img_slice_bytes, int B, int lap0, int lap1,
                     int want_desc, eorb_keypoint* d_kps, uint8_t* d_desc, uint8_t* d_oob, int32_t* d_n, int32_t* d_mono,
-                    int32_t* d_flag_out = nullptr);      // d_flag_out: receives the overflow flag of this extraction (host entry point)
+                    int32_t* d_flag_out = nullptr,       // d_flag_out: receives the overflow flag of this extraction (host entry point)
+                    const float* d_level0_f32 = nullptr, const uint32_t* d_level0_mm = nullptr);
+// d_level0_f32: the float event images (and their running extremes d_level0_mm) are still to be normalised: the first kernel does it while
+// it builds level 0, and writes the u8 images to d_img
 int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H);
 int orb_err_flag(eorb_ctx* c, int B, int* flag);
 int orb_err_flag_to(eorb_ctx* c, int B, int32_t* d_dst);

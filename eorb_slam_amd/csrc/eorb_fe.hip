@@ -329,12 +329,14 @@ void eorb_destroy(eorb_ctx* c)
     fe_enter(c);
     hipStreamSynchronize(c->stream);
     prof_collect(c);
-    DevBuf* bufs[] = {&c->ev16, &c->chunks, &c->segoff, &c->entries, &c->img_f32, &c->img_u8, &c->minmax, &c->tile_order, &c->order_hist, &c->lut, &c->src_info, &c->stamps, &c->sl_tab, &c->sl_tile, &c->sl_rows, &c->sl_trace, &c->dd_tab, &c->dd_src_info, &c->dd_stamps, &c->dd_sl_tab, &c->dd_sl_tile, &c->dd_sl_rows, &c->dd_ev, &c->dd_cnt, &c->focus_sd, &c->voc, &c->klt_pyr, &c->klt_der, &c->klt_scratch, &c->pyr, &c->score,
+    DevBuf* bufs[] = {&c->ev16, &c->chunks, &c->segoff, &c->entries, &c->img_f32, &c->img_u8, &c->minmax, &c->tile_order, &c->order_hist, &c->sl_trace, &c->dd_ev, &c->dd_cnt, &c->focus_sd, &c->voc, &c->klt_pyr, &c->klt_der, &c->klt_scratch, &c->pyr, &c->score,
                       &c->blur, &c->cell_cnt, &c->cell_cand, &c->lvl_cnt, &c->lvl_kp, &c->kp_angle, &c->out_kp, &c->out_desc,
                       &c->out_oob, &c->out_n, &c->oct_scratch, &c->fe_prev_kp, &c->fe_prev_desc, &c->fe_prev_n, &c->fe_pm,
                       &c->fe_matches12, &c->fe_nmatches,
-                      &c->orb.tabs, &c->orb.geom, &c->status, &c->win_ws, &c->win_total, &c->arena, &c->l1_ref_img, &c->l1_ref_pts, &c->ev_info, &c->ev_stamps, &c->pd_hash, &c->pd_lut, &c->pd_src_info, &c->pd_sl_tab, &c->pd_sl_tile, &c->pd_sl_rows, &c->pd_cnt};
+                      &c->orb.tabs, &c->orb.geom, &c->status, &c->win_ws, &c->win_total, &c->arena, &c->l1_ref_img, &c->l1_ref_pts, &c->ev_info, &c->ev_stamps, &c->pd_hash, &c->pd_cnt};
     for (DevBuf* b : bufs) free_buf(*b);
+    for (PosTables* t : {&c->maps, &c->dd, &c->pd})
+        for (DevBuf* b : {&t->lut, &t->src_info, &t->stamps, &t->sl_tab, &t->sl_tile, &t->sl_rows}) free_buf(*b);
     kfdb_free(c);
     for (auto& s : c->pinned) { if (s.ev) hipEventDestroy(s.ev); if (s.p) hipHostFree(s.p); }
     for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
@@ -474,9 +476,10 @@ long long eorb_debug_counter(eorb_ctx* c, const char* name)
         return n;
     }
     if (!strcmp(name, "slot_flags")) {
-        if (!c->sl_tile.p || !c->sl_info_off) return 0;
+        const PosTables& T = c->maps;                         // (the maps' slot tables, whatever the float calls built)
+        if (!T.sl_tile.p || !T.sl_info_off) return 0;
         int flags = 0;
-        if (hipMemcpyAsync(&flags, (char*)c->sl_tile.p + c->sl_info_off + 3 * sizeof(int), sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
+        if (hipMemcpyAsync(&flags, (char*)T.sl_tile.p + T.sl_info_off + 3 * sizeof(int), sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
         if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
         return flags;
     }
@@ -553,7 +556,7 @@ static int ev_host_common(eorb_ctx* c, const eorb_event* ev, size_t n, int W, in
 {
     if (!c) return EORB_E_ARG;
     const int raw = rawev != nullptr;
-    if (raw && !c->lut_w) return set_err(c, EORB_E_NOTCONF, "ev2im_raw: eorb_set_undistort_maps not called");
+    if (raw && !c->maps.w) return set_err(c, EORB_E_NOTCONF, "ev2im_raw: eorb_set_undistort_maps not called");
     if (raw) ev = nullptr;
     if (W <= 0 || H <= 0 || (n && !ev && !raw)) return set_err(c, EORB_E_ARG, "ev2im: bad arguments");
     fe_enter(c);
@@ -563,9 +566,9 @@ static int ev_host_common(eorb_ctx* c, const eorb_event* ev, size_t n, int W, in
     std::vector<eorb_event16> packed;
     if (n && raw) {
         for (size_t i = 0; i < n; i++)
-            if ((int)rawev[i].x >= c->lut_w || (int)rawev[i].y >= c->lut_h)       // the reference asserts (MyCalibrator.cpp:176)
+            if ((int)rawev[i].x >= c->maps.w || (int)rawev[i].y >= c->maps.h)       // the reference asserts (MyCalibrator.cpp:176)
                 return set_err(c, EORB_E_ARG, "ev2im_raw: event %zu at (%u,%u) lies outside the %dx%d maps", i, rawev[i].x, rawev[i].y,
-                               c->lut_w, c->lut_h);
+                               c->maps.w, c->maps.h);
     } else if (n) {
         packed.resize(n);
         eorb_pack_events(ev, n, packed.data());
@@ -626,11 +629,12 @@ int eorb_ev2im_gauss(eorb_ctx* c, const eorb_event* ev, size_t n, int W, int H, 
 }
 
 // ---- raw sensor events + undistortion maps ----------------------------------------------------------
-// the maps are in c->lut (uploaded, or written there by calib_maps_dev): everything derived from them is stale
+// the maps are in c->maps.lut (uploaded, or written there by calib_maps_dev): everything derived from them is stale
 static int install_maps(eorb_ctx* c, int LW, int LH, int checkInImage)
 {
-    c->lut_w = LW; c->lut_h = LH; c->lut_check = checkInImage != 0;
-    c->lut_key_W = c->lut_key_H = c->lut_key_mode = -1; c->lut_key_sigma = -1.f;      // derived tables are stale
+    PosTables& T = c->maps;
+    T.w = LW; T.h = LH; T.check = checkInImage != 0;
+    T.key_W = T.key_H = T.key_mode = -1; T.key_sigma = -1.f;      // derived tables are stale
     return EORB_OK;
 }
 
@@ -642,14 +646,14 @@ int eorb_set_undistort_maps(eorb_ctx* c, const float* mapX, const float* mapY, i
     fe_enter(c);
     const size_t n = (size_t)LW * LH;
     int rc;
-    if ((rc = upload_persistent(c, c->lut, sizeof(float) * 2 * n, [&](char* hp) {
+    if ((rc = upload_persistent(c, c->maps.lut, sizeof(float) * 2 * n, [&](char* hp) {
             float* xy = (float*)hp;
             for (size_t i = 0; i < n; i++) { xy[2 * i] = mapX[i]; xy[2 * i + 1] = mapY[i]; }
         }))) return rc;
     return install_maps(c, LW, LH, checkInImage);
 }
 
-// MyCalibrator::generateUndistMaps (src/Utils/MyCalibrator.cpp:52-102) on the device: the kernel writes c->lut, install_maps does the rest
+// MyCalibrator::generateUndistMaps (src/Utils/MyCalibrator.cpp:52-102) on the device: the kernel writes c->maps.lut, install_maps does the rest
 int eorb_generate_undistort_maps(eorb_ctx* c, int LW, int LH, int checkInImage, float* mapX, float* mapY)
 {
     if (!c) return EORB_E_ARG;
@@ -659,11 +663,11 @@ int eorb_generate_undistort_maps(eorb_ctx* c, int LW, int LH, int checkInImage, 
     fe_enter(c);
     const size_t n = (size_t)LW * LH;
     int rc;
-    if ((rc = ensure(c, c->lut, sizeof(float) * 2 * n))) return rc;
+    if ((rc = ensure(c, c->maps.lut, sizeof(float) * 2 * n))) return rc;
     Arena A(c);
     const size_t o_x = A.reserve(mapX ? sizeof(float) * n : 0), o_y = A.reserve(mapX ? sizeof(float) * n : 0);
     if ((rc = A.upload())) return rc;
-    if ((rc = calib_maps_dev(c, LW, LH, (float*)c->lut.p, mapX ? A.dev<float>(o_x) : nullptr, mapX ? A.dev<float>(o_y) : nullptr))) return rc;
+    if ((rc = calib_maps_dev(c, LW, LH, (float*)c->maps.lut.p, mapX ? A.dev<float>(o_x) : nullptr, mapX ? A.dev<float>(o_y) : nullptr))) return rc;
     if (mapX) {
         const char* h;
         if ((rc = A.download(o_x, o_y + sizeof(float) * n - o_x, &h))) return rc;
@@ -705,15 +709,15 @@ int eorb_undistort_points(eorb_ctx* c, const float* xy, int n, float* xy_out)
 int eorb_undistort_events(eorb_ctx* c, const eorb_raw_event* raw, size_t n, int W, int H, double tsFactor, eorb_event* out, size_t* n_out)
 {
     if (!c) return EORB_E_ARG;
-    if (!c->lut_w) return set_err(c, EORB_E_NOTCONF, "undistort_events: eorb_set_undistort_maps not called");
+    if (!c->maps.w) return set_err(c, EORB_E_NOTCONF, "undistort_events: eorb_set_undistort_maps not called");
     if ((n && (!raw || !out)) || !n_out || W <= 0 || H <= 0) return set_err(c, EORB_E_ARG, "undistort_events: bad arguments");
     fe_enter(c);
     *n_out = 0;
     if (!n) return EORB_OK;
     for (size_t i = 0; i < n; i++)
-        if ((int)raw[i].x >= c->lut_w || (int)raw[i].y >= c->lut_h)
+        if ((int)raw[i].x >= c->maps.w || (int)raw[i].y >= c->maps.h)
             return set_err(c, EORB_E_ARG, "undistort_events: event %zu at (%u,%u) lies outside the %dx%d maps", i, raw[i].x, raw[i].y,
-                           c->lut_w, c->lut_h);
+                           c->maps.w, c->maps.h);
     int rc;
     const int nblk = (int)((n + 1023) / 1024);
     Arena A(c);
@@ -988,10 +992,10 @@ static int slice_events_in(eorb_ctx* c, Arena& A, const eorb_event* ev, const eo
     if (ev && raw) return set_err(c, EORB_E_ARG, "%s: float events OR raw sensor events", who);
     *is_raw = raw != nullptr;
     if (raw) {
-        if (!c->lut_w) return set_err(c, EORB_E_NOTCONF, "%s: raw events need eorb_set_undistort_maps first", who);
+        if (!c->maps.w) return set_err(c, EORB_E_NOTCONF, "%s: raw events need eorb_set_undistort_maps first", who);
         for (size_t i = 0; i < n; i++)
-            if ((int)raw[i].x >= c->lut_w || (int)raw[i].y >= c->lut_h)       // the reference asserts (MyCalibrator.cpp:176)
-                return set_err(c, EORB_E_ARG, "%s: event %zu at (%u,%u) lies outside the %dx%d maps", who, i, raw[i].x, raw[i].y, c->lut_w, c->lut_h);
+            if ((int)raw[i].x >= c->maps.w || (int)raw[i].y >= c->maps.h)       // the reference asserts (MyCalibrator.cpp:176)
+                return set_err(c, EORB_E_ARG, "%s: event %zu at (%u,%u) lies outside the %dx%d maps", who, i, raw[i].x, raw[i].y, c->maps.w, c->maps.h);
         *o_ev = A.in(raw, sizeof(eorb_raw_event) * n);
     } else {
         packed.resize(n);
@@ -1034,13 +1038,11 @@ int eorb_ev_slice_extract(eorb_ctx* c, const eorb_event* ev, const eorb_raw_even
     ExtractHead* hd = A.dev<ExtractHead>(X.head);
     // EvImConverter::ev2im_gauss(l1Evs, W, H, sigma) :1345 (pol = false, normalized = true)
     // (the normalisation to u8 is left to the extraction's first kernel: one launch less)
-    c->mm_preset = !zc;
-    if ((rc = ev_accumulate_dev(c, A.in_ptr<void>(o_ev), is_raw, offs, 1, W, H, sigma, 0, 0, A.dev<float>(o_f32), d_u8, 0, A.dev<uint32_t>(o_mm)))) return rc;
+    if ((rc = ev_accumulate_dev(c, A.in_ptr<void>(o_ev), is_raw, offs, 1, W, H, sigma, 0, 0, A.dev<float>(o_f32), d_u8, 0, A.dev<uint32_t>(o_mm), !zc))) return rc;
     A.inputs_done();
     // makeFrame :1348 -> EvFrame ctor -> ORBextractor::operator() (EventFrame.cpp:220)
-    c->pyr0_f32 = A.dev<float>(o_f32); c->pyr0_mm = A.dev<uint32_t>(o_mm);
     if ((rc = orb_extract_dev(c, d_u8, W, npix, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(X.kp), A.dev<uint8_t>(X.desc), A.dev<uint8_t>(X.oob),
-                              hd->n, hd->mono, hd->flag))) return rc;
+                              hd->n, hd->mono, hd->flag, A.dev<float>(o_f32), A.dev<uint32_t>(o_mm)))) return rc;
     if ((rc = ensure(c, c->l1_ref_img, npix)) || (rc = ensure(c, c->l1_ref_pts, sizeof(float) * 2 * X.mo))) return rc;
     c->l1_nref = -1; c->l1_W = W; c->l1_H = H; c->klt_ref_serial++;
     c->l1_img_off = o_u8; c->l1_img_gen = c->arena_gen;
@@ -1086,8 +1088,7 @@ int eorb_ev_slice_track(eorb_ctx* c, const eorb_event* ev, const eorb_raw_event*
     if ((rc = A.upload())) return rc;
     int64_t offs[2] = {0, (int64_t)n};
     uint8_t* d_u8 = A.dev<uint8_t>(o_u8);
-    c->mm_preset = true;
-    if ((rc = ev_accumulate_dev(c, A.dev<void>(o_ev), is_raw, offs, 1, W, H, sigma, 0, 0, A.dev<float>(o_f32), d_u8, 1, A.dev<uint32_t>(o_mm)))) return rc;
+    if ((rc = ev_accumulate_dev(c, A.dev<void>(o_ev), is_raw, offs, 1, W, H, sigma, 0, 0, A.dev<float>(o_f32), d_u8, 1, A.dev<uint32_t>(o_mm), true))) return rc;
     c->l1_img_off = o_u8; c->l1_img_gen = c->arena_gen;
     // ELK_Tracker::trackCurrImage (KLT_Tracker.cpp:49-74): calcOpticalFlowPyrLK(mRefFrame, currImage, mRefPoints, kpts, ..., OPTFLOW_USE_INITIAL_FLOW)
     if (nref && (rc = klt_track_dev(c, (const uint8_t*)c->l1_ref_img.p, d_u8, W, H, W, (const float*)c->l1_ref_pts.p, A.dev<float>(o_pts), nref, klt->win,
@@ -3637,9 +3638,8 @@ static int fe_run_batch_common(eorb_ctx* c, const void* d_events, int raw, const
     int rc = from_images ? EORB_OK : ev_accumulate_dev(c, d_events, raw, h_offsets, B, f.W, f.H, f.sigma, f.pol, 0, (float*)c->img_f32.p, img, 0,
                                                        (uint32_t*)c->minmax.p);
     if (rc) return rc;
-    if (!from_images) { c->pyr0_f32 = (const float*)c->img_f32.p; c->pyr0_mm = (const uint32_t*)c->minmax.p; }
     rc = orb_extract_dev(c, img, f.W, npix, B, f.lap0, f.lap1, f.want_desc, wk + cap, wd + 32 * cap, nullptr, wn + 1,
-                         wn + 1 + f.max_batch + 1);
+                         wn + 1 + f.max_batch + 1, nullptr, from_images ? nullptr : (const float*)c->img_f32.p, from_images ? nullptr : (const uint32_t*)c->minmax.p);
     if (rc) return rc;
     if (f.match && f.want_desc) {
         eorb_grid_bounds gb;
@@ -3678,7 +3678,7 @@ int eorb_fe_run_batch_raw4_dev(eorb_ctx* c, const eorb_raw_event4* d_events, con
                                uint8_t* d_images, eorb_keypoint* d_kps, uint8_t* d_desc, int32_t* d_nkps,
                                int32_t* d_matches12, int32_t* d_nmatches)
 {
-    if (c && !c->lut_w) return set_err(c, EORB_E_NOTCONF, "fe_run_batch_raw4: eorb_set_undistort_maps not called");
+    if (c && !c->maps.w) return set_err(c, EORB_E_NOTCONF, "fe_run_batch_raw4: eorb_set_undistort_maps not called");
     return fe_run_batch_common(c, d_events, 3, h_offsets, B, d_images, d_kps, d_desc, d_nkps, d_matches12, d_nmatches);
 }
 
@@ -3686,7 +3686,7 @@ int eorb_fe_run_batch_raw2_dev(eorb_ctx* c, const eorb_raw_event2* d_events, con
                                uint8_t* d_images, eorb_keypoint* d_kps, uint8_t* d_desc, int32_t* d_nkps,
                                int32_t* d_matches12, int32_t* d_nmatches)
 {
-    if (c && !c->lut_w) return set_err(c, EORB_E_NOTCONF, "fe_run_batch_raw2: eorb_set_undistort_maps not called");
+    if (c && !c->maps.w) return set_err(c, EORB_E_NOTCONF, "fe_run_batch_raw2: eorb_set_undistort_maps not called");
     if (c && c->fe_configured && c->fe.pol) return set_err(c, EORB_E_ARG, "fe_run_batch_raw2: the 2-byte record carries no polarity");
     return fe_run_batch_common(c, d_events, 4, h_offsets, B, d_images, d_kps, d_desc, d_nkps, d_matches12, d_nmatches);
 }
@@ -3702,7 +3702,7 @@ int eorb_fe_run_batch_raw_dev(eorb_ctx* c, const eorb_raw_event* d_events, const
                               uint8_t* d_images, eorb_keypoint* d_kps, uint8_t* d_desc, int32_t* d_nkps,
                               int32_t* d_matches12, int32_t* d_nmatches)
 {
-    if (c && !c->lut_w) return set_err(c, EORB_E_NOTCONF, "fe_run_batch_raw: eorb_set_undistort_maps not called");
+    if (c && !c->maps.w) return set_err(c, EORB_E_NOTCONF, "fe_run_batch_raw: eorb_set_undistort_maps not called");
     return fe_run_batch_common(c, d_events, 1, h_offsets, B, d_images, d_kps, d_desc, d_nkps, d_matches12, d_nmatches);
 }
 

@@ -1739,9 +1739,9 @@ int ev_undistort_dev(eorb_ctx* c, const eorb_raw_event* d_raw, size_t n, int W, 
 {
     const int nblk = (int)((n + 1023) / 1024);
     ProfScope ps(c, "ev_undistort");
-    ev_undistort_count_kernel<<<nblk, 1024, 0, c->stream>>>(d_raw, n, (const float2*)c->lut.p, c->lut_w, W, H, c->lut_check, d_blk);
+    ev_undistort_count_kernel<<<nblk, 1024, 0, c->stream>>>(d_raw, n, (const float2*)c->maps.lut.p, c->maps.w, W, H, c->maps.check, d_blk);
     ev_undistort_scan_kernel<<<1, 1, 0, c->stream>>>(d_blk, nblk);
-    ev_undistort_write_kernel<<<nblk, 1024, 0, c->stream>>>(d_raw, n, (const float2*)c->lut.p, c->lut_w, W, H, c->lut_check, tsFactor, d_blk, d_out);
+    ev_undistort_write_kernel<<<nblk, 1024, 0, c->stream>>>(d_raw, n, (const float2*)c->maps.lut.p, c->maps.w, W, H, c->maps.check, tsFactor, d_blk, d_out);
     EORB_LAUNCH_CHECK(c, "ev_undistort kernels");
     return EORB_OK;
 }
@@ -1975,48 +1975,48 @@ static GatherParams ev_gather_params(int W, int H, int h, int TX, int TY, int NT
     return G;
 }
 
-// raw events: the tables derived from the maps (integer position of every sensor pixel, its stamp); rebuilt only when (image size,
-// sigma, mode) change
-static int ev_raw_tables(eorb_ctx* c, int W, int H, int h, float sigma, int mode_count, GatherParams& G, bool hashed = false, bool want_slots = false)
+// raw events: the tables derived from the positions of the set T (integer position of every sensor pixel, its stamp, the slot tables);
+// rebuilt only when (image size, sigma, mode) differ from T's key.  T is the maps, or (hashed) the per-call set of the float bulk path,
+// whose key the caller resets for every call and whose src_info / slot assignment it may have launched ahead.
+static int ev_raw_tables(eorb_ctx* c, PosTables& T, int W, int H, int h, float sigma, int mode_count, GatherParams& G, bool hashed = false, bool want_slots = false)
 {
     int rc;
-    // tables derived from the maps; rebuilt only when (image size, sigma, mode) change
-    const int nsrc = c->lut_w * c->lut_h;
+    const int nsrc = T.w * T.h;
     const int SW = 2 * h + 1, SWP = (SW + 3) & ~3;
     G.stamp_stride = SW * SWP; G.stamp_colstride = SWP;
-    if (c->lut_key_W != W || c->lut_key_H != H || c->lut_key_sigma != sigma || c->lut_key_mode != mode_count) {
+    if (T.key_W != W || T.key_H != H || T.key_sigma != sigma || T.key_mode != mode_count) {
         ProfScope ps(c, "ev_stamp_tables");
         const int TXs = (W + kTile - 1) / kTile, TYs = (H + kTile - 1) / kTile;
-        if (!(hashed && c->dd_src_info_done)) {
-            if ((rc = ensure(c, c->src_info, sizeof(uint32_t) * (size_t)nsrc))) return rc;
-            ev_src_info_kernel<<<(nsrc + 255) / 256, 256, 0, c->stream>>>((const float2*)c->lut.p, nsrc, W, H, c->lut_check, mode_count,
-                                                                            (uint32_t*)c->src_info.p);
+        if (!T.src_info_done) {
+            if ((rc = ensure(c, T.src_info, sizeof(uint32_t) * (size_t)nsrc))) return rc;
+            ev_src_info_kernel<<<(nsrc + 255) / 256, 256, 0, c->stream>>>((const float2*)T.lut.p, nsrc, W, H, T.check, mode_count,
+                                                                            (uint32_t*)T.src_info.p);
             EORB_LAUNCH_CHECK(c, "ev_src_info_kernel");
-            c->sl_launched = 0;
+            T.sl_launched = 0;
         }
-        c->dd_src_info_done = 0;
-        if (!(hashed && want_slots)) c->sl_launched = 0;      // (an assignment launched ahead by the float bulk path serves that call only)
-        c->sl_ok = 0;
+        T.src_info_done = 0;
+        if (!(hashed && want_slots)) T.sl_launched = 0;      // (an assignment launched ahead by the float bulk path serves that call only)
+        T.sl_ok = 0;
         bool need_stamps = !mode_count;
         if (!mode_count && hashed && want_slots) {
             // the per-call positions of float events (2^20 table rows, most of them empty): the slot form computes its rows from the
             // positions, so the 235 MB stamp table is only built when that form cannot serve the call
-            if ((rc = ev_slots_prepare(c, W, H, h, TXs, TYs, nullptr, G.stamp_stride, G.stamp_colstride, G.two_sig2, G.norm))) return rc;
-            if (c->sl_ok) need_stamps = false;
+            if ((rc = ev_slots_prepare(c, T, W, H, h, TXs, TYs, nullptr, G.stamp_stride, G.stamp_colstride, G.two_sig2, G.norm))) return rc;
+            if (T.sl_ok) need_stamps = false;
         }
         if (need_stamps) {
             if ((size_t)nsrc * SW * SWP * 4 + 256 >= ((size_t)1 << 32)) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: stamp table of %d sensor pixels x %d taps is too large", nsrc, SW * SWP);
-            if ((rc = ensure(c, c->stamps, sizeof(float) * ((size_t)nsrc * SW * SWP + 2 * kStampPad)))) return rc;
-            EORB_HIP(c, hipMemsetAsync(c->stamps.p, 0, sizeof(float) * kStampPad, c->stream));
-            EORB_HIP(c, hipMemsetAsync((float*)c->stamps.p + kStampPad + (size_t)nsrc * SW * SWP, 0, sizeof(float) * kStampPad, c->stream));
-            ev_stamp_kernel<<<2048, 256, 0, c->stream>>>((const float2*)c->lut.p, (const uint32_t*)c->src_info.p, nsrc, G,
-                                                         (float*)c->stamps.p + kStampPad);
+            if ((rc = ensure(c, T.stamps, sizeof(float) * ((size_t)nsrc * SW * SWP + 2 * kStampPad)))) return rc;
+            EORB_HIP(c, hipMemsetAsync(T.stamps.p, 0, sizeof(float) * kStampPad, c->stream));
+            EORB_HIP(c, hipMemsetAsync((float*)T.stamps.p + kStampPad + (size_t)nsrc * SW * SWP, 0, sizeof(float) * kStampPad, c->stream));
+            ev_stamp_kernel<<<2048, 256, 0, c->stream>>>((const float2*)T.lut.p, (const uint32_t*)T.src_info.p, nsrc, G,
+                                                         (float*)T.stamps.p + kStampPad);
             EORB_LAUNCH_CHECK(c, "ev_stamp_kernel");
-            if (!hashed && (rc = ev_slots_prepare(c, W, H, h, TXs, TYs, (const float*)c->stamps.p + kStampPad, G.stamp_stride, G.stamp_colstride, G.two_sig2, G.norm))) return rc;
+            if (!hashed && (rc = ev_slots_prepare(c, T, W, H, h, TXs, TYs, (const float*)T.stamps.p + kStampPad, G.stamp_stride, G.stamp_colstride, G.two_sig2, G.norm))) return rc;
         }
-        c->lut_key_W = W; c->lut_key_H = H; c->lut_key_sigma = sigma; c->lut_key_mode = mode_count;
+        T.key_W = W; T.key_H = H; T.key_sigma = sigma; T.key_mode = mode_count;
     }
-    G.stamps = (const float*)c->stamps.p + kStampPad;     // K2r reads up to 7 floats before / behind a column
+    G.stamps = (const float*)T.stamps.p + kStampPad;     // K2r reads up to 7 floats before / behind a column
     return EORB_OK;
 }
 
@@ -2052,7 +2052,7 @@ int ev_direct_slices_dev(eorb_ctx* c, const void* d_events, int raw, const int64
     }
     int rc;
     GatherParams G = ev_gather_params(W, H, h, TX, TY, NT, 0, B * NT, sigma);
-    if (raw && (rc = ev_raw_tables(c, W, H, h, sigma, 0, G))) return rc;
+    if (raw && (rc = ev_raw_tables(c, c->maps, W, H, h, sigma, 0, G))) return rc;
     // every event of the call resolved once into its list entry (ev_pre_kernel), over the span of the slices
     int64_t lo = S.beg[0], hi = S.end[0];
     for (int b = 1; b < B; b++) { lo = std::min(lo, S.beg[b]); hi = std::max(hi, S.end[b]); }
@@ -2079,7 +2079,7 @@ int ev_direct_slices_dev(eorb_ctx* c, const void* d_events, int raw, const int64
         G.stamps = (const float*)c->ev_stamps.p;
     } else if (span) {
         ProfScope ps(c, "ev_stamp_tables");
-        ev_pre_kernel<false><<<(int)((span + 255) / 256), 256, 0, c->stream>>>(d_first, (int)span, W, H, c->lut_w, c->lut_h, (const uint32_t*)c->src_info.p, 0u, d_pre, mm_in_pre ? d_minmax_enc : nullptr, B);
+        ev_pre_kernel<false><<<(int)((span + 255) / 256), 256, 0, c->stream>>>(d_first, (int)span, W, H, c->maps.w, c->maps.h, (const uint32_t*)c->maps.src_info.p, 0u, d_pre, mm_in_pre ? d_minmax_enc : nullptr, B);
         EORB_LAUNCH_CHECK(c, "ev_pre_kernel");
     }
     if (!mm_preset && !mm_in_pre) {
@@ -2115,8 +2115,11 @@ __global__ void ev_unpack2_kernel(const uint16_t* __restrict__ in, int64_t n, in
 // ---- float events in bulk, across calls: the position dictionary -----------------------------------------------------------------
 // A loader's maps do not change between calls, so the positions of one call's events are those of the next.  After a call whose
 // positions were tabulated (dd_insert_kernel) and number at most 65 535, they are frozen into a DICTIONARY: a compact open-addressing
-// table { x bits, y bits, dense id } (2^17 entries: L2-resident) and, per dense id, what the maps' tables hold per sensor pixel (position,
-// integer position, slot tables, rows).  The following calls run the slot form straight on the float events: its count pass looks
+// table { x bits, y bits, dense id } (2^17 entries: L2-resident, c->pd_hash) and, per dense id, what the maps' tables hold per sensor
+// pixel (position, integer position, slot tables, rows): the set c->pd, its positions a (K x 1) sensor.  The context so holds three sets
+// of position tables: c->maps (built by ev_raw_tables for the raw calls), c->dd (the per-call set: filled and built anew by every
+// tabulating call) and c->pd (built by pd_freeze from c->dd's positions, read by pd_accumulate until a call misses it).  Each builder and
+// reader is handed its set; none touches another.  The following calls run the slot form straight on the float events: its count pass looks
 // every position up (sl_count_lds_kernel<16, true>) and writes the dense id as the hashed record -- one pass over the events where the
 // per-call tabulation makes two, no table to clear and rebuild.  A position the dictionary does not hold is counted; the call then
 // falls back to the per-call tabulation (whose table becomes the next dictionary).
@@ -2141,41 +2144,29 @@ __global__ void pd_build_kernel(const unsigned long long* __restrict__ tab, int 
     }
 }
 
-// the tables of the call's positions (the context's dd_* set, valid right after a per-call tabulation) -> the frozen dictionary
+// the call's positions (c->dd.lut, valid right after a per-call tabulation) -> the frozen dictionary and its set of tables c->pd
 static int pd_freeze(eorb_ctx* c, int W, int H, int h, float sigma, int TX, int TY, int npos)
 {
     c->pd_valid = 0;
     if (npos < 1 || npos > 65535) return EORB_OK;                      // (dense ids travel as hashed records below 65 536 rows: the LDS count pass)
     const size_t cap = (size_t)1 << kDdLog, hcap = (size_t)1 << kPdLog;
+    PosTables& T = c->pd;
     int rc;
-    if ((rc = ensure(c, c->pd_hash, sizeof(uint4) * hcap)) || (rc = ensure(c, c->pd_lut, sizeof(float2) * 65536)) || (rc = ensure(c, c->pd_cnt, 64))) return rc;
+    if ((rc = ensure(c, c->pd_hash, sizeof(uint4) * hcap)) || (rc = ensure(c, T.lut, sizeof(float2) * 65536)) || (rc = ensure(c, c->pd_cnt, 64))) return rc;
     EORB_HIP(c, hipMemsetAsync(c->pd_hash.p, 0xff, sizeof(uint4) * hcap, c->stream));
     EORB_HIP(c, hipMemsetAsync(c->pd_cnt.p, 0, 64, c->stream));
-    pd_build_kernel<<<(int)((cap + 255) / 256), 256, 0, c->stream>>>((const unsigned long long*)c->dd_tab.p, (int)cap, 65535, (int*)c->pd_cnt.p, (float2*)c->pd_lut.p, (uint4*)c->pd_hash.p);
+    pd_build_kernel<<<(int)((cap + 255) / 256), 256, 0, c->stream>>>((const unsigned long long*)c->dd.lut.p, (int)cap, 65535, (int*)c->pd_cnt.p, (float2*)T.lut.p, (uint4*)c->pd_hash.p);
     EORB_LAUNCH_CHECK(c, "pd_build_kernel");
     // the per-id tables: the raw path's own builders on the dictionary's positions as a (K x 1) "sensor"
-    auto swap_tables = [&]() {
-        std::swap(c->lut, c->pd_lut); std::swap(c->src_info, c->pd_src_info);
-        std::swap(c->sl_tab, c->pd_sl_tab); std::swap(c->sl_tile, c->pd_sl_tile); std::swap(c->sl_rows, c->pd_sl_rows);
-        std::swap(c->sl_null, c->pd_sl_null); std::swap(c->sl_info_off, c->pd_sl_info_off);
-    };
-    swap_tables();
-    const int sw = c->lut_w, sh = c->lut_h, sc = c->lut_check, sok = c->sl_ok, sl0 = c->sl_launched;
-    c->lut_w = npos; c->lut_h = 1; c->lut_check = 0; c->sl_launched = 0;
-    rc = ensure(c, c->src_info, sizeof(uint32_t) * (size_t)npos);
-    if (!rc) {
-        ev_src_info_kernel<<<(npos + 255) / 256, 256, 0, c->stream>>>((const float2*)c->lut.p, npos, W, H, 0, 0, (uint32_t*)c->src_info.p);
-        const float sig2 = sigma * sigma;
-        rc = ev_slots_prepare(c, W, H, h, TX, TY, nullptr, 0, 0, 2.0f * sig2, 2.0f * (float)3.1415926535897932384626433832795 * sig2);
-    }
-    const int ok = c->sl_ok;
-    c->lut_w = sw; c->lut_h = sh; c->lut_check = sc; c->sl_ok = sok; c->sl_launched = sl0;
-    swap_tables();
-    if (rc) return rc;
+    T.w = npos; T.h = 1; T.check = 0; T.sl_launched = 0;
+    if ((rc = ensure(c, T.src_info, sizeof(uint32_t) * (size_t)npos))) return rc;
+    ev_src_info_kernel<<<(npos + 255) / 256, 256, 0, c->stream>>>((const float2*)T.lut.p, npos, W, H, 0, 0, (uint32_t*)T.src_info.p);
+    const float sig2 = sigma * sigma;
+    if ((rc = ev_slots_prepare(c, T, W, H, h, TX, TY, nullptr, 0, 0, 2.0f * sig2, 2.0f * (float)3.1415926535897932384626433832795 * sig2))) return rc;
     // the count pass keeps the dense ids' tile ranges and its per-wavefront counters in LDS (ev_slots.hip, sl_count_lds_kernel)
     const int NTp = (TX * TY + 1) & ~1;
     const bool lds_ok = TX <= 127 && TY <= 127 && 4 * (((size_t)npos + 2) / 2) + (size_t)16 * NTp * 2 <= 159 * 1024;
-    if (ok && lds_ok) { c->pd_valid = 1; c->pd_K = npos; c->pd_W = W; c->pd_H = H; c->pd_sigma = sigma; }
+    if (T.sl_ok && lds_ok) { c->pd_valid = 1; c->pd_K = npos; c->pd_W = W; c->pd_H = H; c->pd_sigma = sigma; }
     return EORB_OK;
 }
 
@@ -2186,22 +2177,12 @@ static int pd_accumulate(eorb_ctx* c, const eorb_event16* d_src, const int64_t* 
     int rc;
     if ((rc = ensure(c, c->dd_ev, 4 * (size_t)std::max<int64_t>(n0, 1)))) return rc;
     EORB_HIP(c, hipMemsetAsync(c->pd_cnt.p, 0, 64, c->stream));
-    auto swap_tables = [&]() {
-        std::swap(c->lut, c->pd_lut); std::swap(c->src_info, c->pd_src_info);
-        std::swap(c->sl_tab, c->pd_sl_tab); std::swap(c->sl_tile, c->pd_sl_tile); std::swap(c->sl_rows, c->pd_sl_rows);
-        std::swap(c->sl_null, c->pd_sl_null); std::swap(c->sl_info_off, c->pd_sl_info_off);
-    };
-    swap_tables();
-    const int sw = c->lut_w, sh = c->lut_h, sok = c->sl_ok;
-    c->lut_w = c->pd_K; c->lut_h = 1; c->sl_ok = 1;
     {
         ProfScope ps(c, "ev_minmax_init");
         ev_minmax_init_kernel<<<(B + 63) / 64, 64, 0, c->stream>>>(d_minmax_enc, B);
     }
     SlotDict D{(const uint4*)c->pd_hash.p, (1u << kPdLog) - 1u, (uint32_t*)c->dd_ev.p, (int*)c->pd_cnt.p, c->pd_K < 65535 ? 1 : 0};
-    rc = ev_slots_accumulate(c, d_src, 16, off, B, W, H, TX, TY, d_f32, d_minmax_enc, &D);
-    c->lut_w = sw; c->lut_h = sh; c->sl_ok = sok;
-    swap_tables();
+    rc = ev_slots_accumulate(c, c->pd, d_src, 16, off, B, W, H, TX, TY, d_f32, d_minmax_enc, &D);      // (pd_valid: c->pd is pd_K x 1, its slot tables ok)
     if (rc < 0) return rc;
     if (rc > 0) { *missed = 1; return EORB_OK; }                        // the batch's shape does not fit the slot form: the per-call path decides
     if (normalized && d_u8) {
@@ -2220,15 +2201,15 @@ static int pd_accumulate(eorb_ctx* c, const eorb_event16* d_src, const int64_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------
+static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
+                                float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc);
+
 int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
                       float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized,
-                      uint32_t* d_minmax_enc)
+                      uint32_t* d_minmax_enc, bool mm_preset)
 {
-    const bool mm_preset = c->mm_preset;                 // (only the binning-free form takes the caller's word for it; the others initialise the extremes themselves)
-    c->mm_preset = false;
     if (B <= 0 || W <= 0 || H <= 0) return set_err(c, EORB_E_ARG, "ev_accumulate: bad size");
-    if (raw && !c->lut_w) return set_err(c, EORB_E_NOTCONF, "ev_accumulate: raw events need eorb_set_undistort_maps first");
-    const eorb_event16* d_ev = (const eorb_event16*)d_events;          // eorb_raw_event has the same 16-byte stride
+    if (raw && !c->maps.w) return set_err(c, EORB_E_NOTCONF, "ev_accumulate: raw events need eorb_set_undistort_maps first");
     const int h = mode_count ? 0 : (int)ceil((double)sigma * 3.0);     // lenHalfWin :222
     if (h > 8) return set_err(c, EORB_E_CONFIG, "ev_accumulate: sigma %.3f gives half window %d > 8", sigma, h);
     // exp(-d^2 / 2 sigma^2) underflows to 0 inside the window below sigma ~ 0.197 (d^2 up to 8 at h = 1): with polarity the
@@ -2236,12 +2217,7 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
     if (pol && !mode_count && sigma < 0.2f) return set_err(c, EORB_E_CONFIG, "ev_accumulate: polarity images need sigma >= 0.2 (got %.3f)", sigma);
     const int R = (2 * h <= kTile) ? ((h == 0) ? 1 : 2) : 3;            // max tiles an event spans per axis
     const int TX = (W + kTile - 1) / kTile, TY = (H + kTile - 1) / kTile, NT = TX * TY;
-    int nbits = 1; while ((1 << nbits) < NT) nbits++;
-    const int dup = R * R;
-    const bool hashed = raw == 2;                        // (recursion of the block below: d_events are 4-byte hashed records)
-    const bool packed4 = raw == 3;                       // 4-byte sensor records (eorb_raw_event4)
-    const bool packed2 = raw == 4;                       // 2-byte sensor records (eorb_raw_event2: y * LW + x)
-    if (packed2 && (int64_t)c->lut_w * c->lut_h > 65535) return set_err(c, EORB_E_ARG, "ev_accumulate: 2-byte records need a sensor of at most 65 535 pixels (the maps are %dx%d)", c->lut_w, c->lut_h);
+    if (raw == 4 && (int64_t)c->maps.w * c->maps.h > 65535) return set_err(c, EORB_E_ARG, "ev_accumulate: 2-byte records need a sensor of at most 65 535 pixels (the maps are %dx%d)", c->maps.w, c->maps.h);
     if (!raw && !mode_count && c->dbg_gather_form != 1 && h_offsets[B] - h_offsets[0] >= c->dbg_dd_min && c->dbg_dd_min > 0) {
         // float events in bulk: tabulate their distinct positions, continue on the raw path (see dd_insert_kernel)
         const int64_t n0 = h_offsets[B] - h_offsets[0];
@@ -2267,7 +2243,9 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
         }
         if (c->pd_cooldown > 0) c->pd_cooldown--;
         if (fits) {
-            if ((rc = ensure(c, c->dd_tab, 8 * cap)) || (rc = ensure(c, c->dd_cnt, 64)) || (rc = ensure(c, c->dd_ev, 4 * (size_t)n0))) return rc;
+            PosTables& T = c->dd;
+            if ((rc = ensure(c, T.lut, 8 * cap)) || (rc = ensure(c, c->dd_cnt, 64)) || (rc = ensure(c, c->dd_ev, 4 * (size_t)n0))) return rc;
+            T.w = 65536; T.h = (int)(cap / 65536); T.check = 0;          // the hash table as a sensor's maps: row = sensor pixel
             const eorb_event16* src = (const eorb_event16*)d_events + h_offsets[0];
             int hc[2] = {0, 0};
             {
@@ -2276,11 +2254,11 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
                 // not see every sensor pixel: the table accumulates them over the calls); otherwise it starts empty
                 const bool keep = c->dd_keep && slot_shape && c->dbg_pd != 0;
                 if (!keep) {
-                    EORB_HIP(c, hipMemsetAsync(c->dd_tab.p, 0xff, 8 * cap, c->stream));
+                    EORB_HIP(c, hipMemsetAsync(T.lut.p, 0xff, 8 * cap, c->stream));
                     EORB_HIP(c, hipMemsetAsync(c->dd_cnt.p, 0, 64, c->stream));
                 } else EORB_HIP(c, hipMemsetAsync((int*)c->dd_cnt.p + 1, 0, 4, c->stream));      // (the crowding flag is per call)
                 c->dd_keep = 0;
-                dd_insert_kernel<<<4096, 256, 0, c->stream>>>(src, n0, (unsigned long long*)c->dd_tab.p, (int*)c->dd_cnt.p, (uint32_t*)c->dd_ev.p);
+                dd_insert_kernel<<<4096, 256, 0, c->stream>>>(src, n0, (unsigned long long*)T.lut.p, (int*)c->dd_cnt.p, (uint32_t*)c->dd_ev.p);
                 EORB_LAUNCH_CHECK(c, "dd_insert_kernel");
                 int* rb = readback_buf(c);
                 if (!rb) return set_err(c, EORB_E_HIP, "pinned alloc failed");
@@ -2288,43 +2266,21 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
                 // in front of the wait: the integer positions of the table rows and the slot assignment (what the slot form's host
                 // side needs read back), so that the call waits for the stream once
                 if (!pol && !mode_count && (c->dbg_gather_form == 0 || c->dbg_gather_form == 2 || c->dbg_gather_form == 4) && h >= 1 && h <= 4) {
-                    std::swap(c->lut, c->dd_tab); std::swap(c->src_info, c->dd_src_info);
-                    std::swap(c->sl_tab, c->dd_sl_tab); std::swap(c->sl_tile, c->dd_sl_tile); std::swap(c->sl_info_off, c->dd_sl_info_off);
-                    const int sw0 = c->lut_w, sh0 = c->lut_h, sok0 = c->sl_ok;
-                    c->lut_w = 65536; c->lut_h = (int)(cap / 65536);
-                    int rc2 = ensure(c, c->src_info, sizeof(uint32_t) * cap);
-                    if (!rc2) {
-                        ev_src_info_kernel<<<(int)((cap + 255) / 256), 256, 0, c->stream>>>((const float2*)c->lut.p, (int)cap, W, H, 0, mode_count, (uint32_t*)c->src_info.p);
-                        rc2 = ev_slots_prepare_launch(c, W, H, h, TX, TY);
-                    }
-                    c->sl_ok = sok0;
-                    c->lut_w = sw0; c->lut_h = sh0;
-                    std::swap(c->lut, c->dd_tab); std::swap(c->src_info, c->dd_src_info);
-                    std::swap(c->sl_tab, c->dd_sl_tab); std::swap(c->sl_tile, c->dd_sl_tile); std::swap(c->sl_info_off, c->dd_sl_info_off);
-                    if (rc2) return rc2;
-                    c->dd_src_info_done = 1;
+                    if ((rc = ensure(c, T.src_info, sizeof(uint32_t) * cap))) return rc;
+                    ev_src_info_kernel<<<(int)((cap + 255) / 256), 256, 0, c->stream>>>((const float2*)T.lut.p, (int)cap, W, H, 0, mode_count, (uint32_t*)T.src_info.p);
+                    if ((rc = ev_slots_prepare_launch(c, T, W, H, h, TX, TY))) return rc;
+                    T.src_info_done = 1;
                 }
                 EORB_HIP(c, hipStreamSynchronize(c->stream));
                 hc[0] = rb[0]; hc[1] = rb[1];
             }
-            if (!(!hc[1] && hc[0] <= max_ids)) { c->dd_src_info_done = 0; c->sl_launched = 0; }
+            if (!(!hc[1] && hc[0] <= max_ids)) { T.src_info_done = 0; T.sl_launched = 0; }
             if (!hc[1] && hc[0] <= max_ids) {
-                // the raw path on the per-call tables: the context's map state is swapped for the duration of the call
-                auto swap_tables = [&]() {
-                    std::swap(c->lut, c->dd_tab); std::swap(c->src_info, c->dd_src_info); std::swap(c->stamps, c->dd_stamps);
-                    std::swap(c->sl_tab, c->dd_sl_tab); std::swap(c->sl_tile, c->dd_sl_tile); std::swap(c->sl_rows, c->dd_sl_rows);
-                    std::swap(c->sl_ok, c->dd_sl_ok); std::swap(c->sl_null, c->dd_sl_null); std::swap(c->sl_info_off, c->dd_sl_info_off);
-                };
-                swap_tables();
-                const int sw = c->lut_w, sh = c->lut_h, sc = c->lut_check, kW = c->lut_key_W, kH = c->lut_key_H, kM = c->lut_key_mode;
-                const float kS = c->lut_key_sigma;
-                c->lut_w = 65536; c->lut_h = (int)(cap / 65536); c->lut_check = 0;       // the hash table as the call's maps: slot = sensor pixel
-                c->lut_key_W = c->lut_key_H = c->lut_key_mode = -1; c->lut_key_sigma = -1.f;
+                // the raw path on the per-call set (records: row numbers of its table), whose tables are this call's: nothing built is current
+                T.key_W = T.key_H = T.key_mode = -1; T.key_sigma = -1.f;
                 std::vector<int64_t> off(B + 1);
                 for (int b = 0; b <= B; b++) off[b] = h_offsets[b] - h_offsets[0];
-                rc = ev_accumulate_dev(c, c->dd_ev.p, 2, off.data(), B, W, H, sigma, pol, mode_count, d_f32, d_u8, normalized, d_minmax_enc);
-                swap_tables();
-                c->lut_w = sw; c->lut_h = sh; c->lut_check = sc; c->lut_key_W = kW; c->lut_key_H = kH; c->lut_key_mode = kM; c->lut_key_sigma = kS;
+                rc = ev_accumulate_tables(c, T, c->dd_ev.p, 2, off.data(), B, W, H, sigma, pol, mode_count, d_f32, d_u8, normalized, d_minmax_enc);
                 // these positions serve the next calls (a call that just missed the dictionary with MANY new positions -- events that are not
                 // map-valued -- does not try again for a while)
                 if (!rc && slot_shape && c->dbg_pd != 0) {
@@ -2338,7 +2294,7 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
     {
         // one or a few small slices of raw events (the live per-slice call): no binning at all, K2d
         const int64_t nev0 = h_offsets[B] - h_offsets[0];
-        if (!hashed && !packed4 && !packed2 && !mode_count && B <= 4 && (c->dbg_gather_form == 3 || (c->dbg_gather_form == 0 && nev0 <= 16384))) {
+        if (!(raw >= 2 && raw <= 4) && !mode_count && B <= 4 && (c->dbg_gather_form == 3 || (c->dbg_gather_form == 0 && nev0 <= 16384))) {
             int64_t beg[kDirectSlices], end[kDirectSlices];
             for (int b = 0; b < B; b++) {
                 if (h_offsets[b + 1] < h_offsets[b]) return set_err(c, EORB_E_ARG, "ev_accumulate: offsets not monotone");
@@ -2347,6 +2303,24 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
             return ev_direct_slices_dev(c, d_events, raw, beg, end, B, W, H, sigma, pol, d_f32, d_u8, normalized, d_minmax_enc, mm_preset);
         }
     }
+    return ev_accumulate_tables(c, c->maps, d_events, raw, h_offsets, B, W, H, sigma, pol, mode_count, d_f32, d_u8, normalized, d_minmax_enc);
+}
+
+// The forms that bin: the slot form, else the batch pipeline (count, scan, scatter, gather).  Raw events (raw 1, 3, 4: 16-, 4-, 2-byte
+// records) are looked up in the tables of the set T; raw 2: 4-byte records that are row numbers of T, the per-call set.  The arguments
+// have passed ev_accumulate_dev's checks.
+static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
+                                float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc)
+{
+    const eorb_event16* d_ev = (const eorb_event16*)d_events;          // eorb_raw_event has the same 16-byte stride
+    const int h = mode_count ? 0 : (int)ceil((double)sigma * 3.0);
+    const int R = (2 * h <= kTile) ? ((h == 0) ? 1 : 2) : 3;            // max tiles an event spans per axis
+    const int TX = (W + kTile - 1) / kTile, TY = (H + kTile - 1) / kTile, NT = TX * TY;
+    int nbits = 1; while ((1 << nbits) < NT) nbits++;
+    const int dup = R * R;
+    const bool hashed = raw == 2;                        // 4-byte hashed records (the float bulk path)
+    const bool packed4 = raw == 3;                       // 4-byte sensor records (eorb_raw_event4)
+    const bool packed2 = raw == 4;                       // 2-byte sensor records (eorb_raw_event2: y * LW + x)
     // dense batches of raw events without polarity: two-byte slot lists, a tile position's rows in LDS (ev_slots.hip)
     if (raw && !mode_count && !pol && (c->dbg_gather_form == 0 || c->dbg_gather_form == 4 || (hashed && c->dbg_gather_form == 2))) {
         const int64_t nev0 = h_offsets[B] - h_offsets[0];
@@ -2354,15 +2328,15 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
         if (c->dbg_gather_form == 4 || !sparse0) {
             int rc;
             GatherParams G = ev_gather_params(W, H, h, TX, TY, NT, mode_count, B * NT, sigma);
-            if ((rc = ev_raw_tables(c, W, H, h, sigma, mode_count, G, hashed, true))) return rc;
-            if (c->sl_ok) {
+            if ((rc = ev_raw_tables(c, T, W, H, h, sigma, mode_count, G, hashed, true))) return rc;
+            if (T.sl_ok) {
                 {
                     ProfScope ps(c, "ev_minmax_init");
                     ev_minmax_init_kernel<<<(B + 63) / 64, 64, 0, c->stream>>>(d_minmax_enc, B);
                 }
                 // > 0: the batch's shape does not fit the slot form (tile grids beyond the scatter's LDS, e.g. VGA-class sensors; more than
                 // 2 048 slices) and nothing was launched: the batch pipeline below serves it
-                if ((rc = ev_slots_accumulate(c, d_events, hashed ? -4 : (packed4 ? 4 : (packed2 ? 2 : 16)), h_offsets, B, W, H, TX, TY, d_f32, d_minmax_enc)) < 0) return rc;
+                if ((rc = ev_slots_accumulate(c, T, d_events, hashed ? -4 : (packed4 ? 4 : (packed2 ? 2 : 16)), h_offsets, B, W, H, TX, TY, d_f32, d_minmax_enc)) < 0) return rc;
                 if (rc == 0) {
                     if (normalized && d_u8) {
                         ProfScope ps(c, "ev_normalize");
@@ -2376,11 +2350,11 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
         }
     }
     if (packed4 || packed2) {
-        // the other forms read 16-byte records: widen the batch's events once and go on with those
+        // the other forms read 16-byte records: widen the batch's events once and go on with those (sensor records: T is the maps)
         const int64_t n0 = h_offsets[B] - h_offsets[0];
         int rc;
         if ((rc = ensure(c, c->ev16, sizeof(eorb_raw_event) * (size_t)std::max<int64_t>(n0, 1)))) return rc;
-        if (n0 > 0 && packed2) ev_unpack2_kernel<<<(int)std::min<int64_t>((n0 + 255) / 256, 65536), 256, 0, c->stream>>>((const uint16_t*)d_events + h_offsets[0], n0, c->lut_w, (eorb_raw_event*)c->ev16.p);
+        if (n0 > 0 && packed2) ev_unpack2_kernel<<<(int)std::min<int64_t>((n0 + 255) / 256, 65536), 256, 0, c->stream>>>((const uint16_t*)d_events + h_offsets[0], n0, T.w, (eorb_raw_event*)c->ev16.p);
         else if (n0 > 0) ev_unpack4_kernel<<<(int)std::min<int64_t>((n0 + 255) / 256, 65536), 256, 0, c->stream>>>((const uint32_t*)d_events + h_offsets[0], n0, (eorb_raw_event*)c->ev16.p);
         EORB_LAUNCH_CHECK(c, "ev_unpack4_kernel");
         std::vector<int64_t> off(B + 1);
@@ -2442,7 +2416,7 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
     int32_t* d_order = (int32_t*)(d_tile_cnt + 2 * (size_t)nb);
 
     GatherParams G = ev_gather_params(W, H, h, TX, TY, NT, mode_count, nb, sigma);
-    if (raw && (rc = ev_raw_tables(c, W, H, h, sigma, mode_count, G, hashed))) return rc;
+    if (raw && (rc = ev_raw_tables(c, T, W, H, h, sigma, mode_count, G, hashed))) return rc;
     {
         ProfScope ps(c, "ev_minmax_init");
         ev_minmax_init_kernel<<<(B + 63) / 64, 64, 0, c->stream>>>(d_minmax_enc, B);
@@ -2450,7 +2424,7 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
     // nearly empty tiles (fewer than one 64-entry batch per tile on average) of raw events with a Gaussian stamp: K2s, a wave per tile
     const bool sparse = raw && !mode_count && (c->dbg_gather_form == 2 || (c->dbg_gather_form == 0 && nev * dup < (int64_t)nb * 64));
     {
-        BinParams P{W, H, h, TX, TY, NT, nbits, dup, mode_count, pol, raw ? 1 : 0, c->lut_w, c->lut_h, (const uint32_t*)c->src_info.p,
+        BinParams P{W, H, h, TX, TY, NT, nbits, dup, mode_count, pol, raw ? 1 : 0, T.w, T.h, (const uint32_t*)T.src_info.p,
                     hashed ? 1 : 0};
         const size_t lds = sizeof(uint32_t) * (size_t)NT;
         if (lds > 64 * 1024) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: %d tiles exceed the binning LDS", NT);

@@ -1161,25 +1161,25 @@ __global__ __launch_bounds__(64) void sl_hot_kernel(const uint32_t* __restrict__
 
 // ---- host ----
 // Two halves, so that a caller that synchronises anyway (the float bulk path waits for its position count) can put the slot
-// assignment in front of ITS wait: launch = assignment + row bases (+ the once-per-context rank check), info read back into
-// c->sl_hinfo by an asynchronous copy; finish = after the stream was waited for: the rows, sl_ok.
-int ev_slots_prepare_launch(eorb_ctx* c, int W, int H, int h, int TX, int TY)
+// assignment in front of ITS wait: launch = assignment + row bases (+ the once-per-context rank check), info on its way to
+// the read-back buffer by an asynchronous copy; finish = after the stream was waited for: the rows, T.sl_ok.
+int ev_slots_prepare_launch(eorb_ctx* c, PosTables& T, int W, int H, int h, int TX, int TY)
 {
-    c->sl_ok = 0; c->sl_launched = 0;
+    T.sl_ok = 0; T.sl_launched = 0;
     if (h < 1 || h > 4 || TX >= 256 || TY >= 256) return EORB_OK;
-    const int nsrc = c->lut_w * c->lut_h, NT = TX * TY;
+    const int nsrc = T.w * T.h, NT = TX * TY;
     int rc;
     const size_t geo_off = sizeof(uint2) * (size_t)nsrc;                // slot_tab | slot_geo (16 bits per sensor pixel, + pad)
-    if ((rc = ensure(c, c->sl_tab, geo_off + sizeof(uint16_t) * ((size_t)nsrc + 2)))) return rc;
+    if ((rc = ensure(c, T.sl_tab, geo_off + sizeof(uint16_t) * ((size_t)nsrc + 2)))) return rc;
     // nslots | rowbase | tile_w | ctr | (spare) (NT each) | info (4 ints) | rank check (u64)
-    if ((rc = ensure(c, c->sl_tile, sizeof(uint32_t) * (5 * (size_t)NT + 8)))) return rc;
-    uint32_t* d_nslots = (uint32_t*)c->sl_tile.p;
+    if ((rc = ensure(c, T.sl_tile, sizeof(uint32_t) * (5 * (size_t)NT + 8)))) return rc;
+    uint32_t* d_nslots = (uint32_t*)T.sl_tile.p;
     uint32_t* d_rowbase = d_nslots + NT;
     int* d_info = (int*)(d_nslots + 5 * (size_t)NT);
-    c->sl_info_off = sizeof(uint32_t) * 5 * (size_t)NT;
-    EORB_HIP(c, hipMemsetAsync(c->sl_tile.p, 0, sizeof(uint32_t) * (5 * (size_t)NT + 8), c->stream));
-    sl_assign_kernel<<<(nsrc + 256) / 256, 256, 0, c->stream>>>((const uint32_t*)c->src_info.p, nsrc, W, H, h, TX, d_nslots, (uint2*)c->sl_tab.p,
-                                                                (uint16_t*)((char*)c->sl_tab.p + geo_off), d_info);
+    T.sl_info_off = sizeof(uint32_t) * 5 * (size_t)NT;
+    EORB_HIP(c, hipMemsetAsync(T.sl_tile.p, 0, sizeof(uint32_t) * (5 * (size_t)NT + 8), c->stream));
+    sl_assign_kernel<<<(nsrc + 256) / 256, 256, 0, c->stream>>>((const uint32_t*)T.src_info.p, nsrc, W, H, h, TX, d_nslots, (uint2*)T.sl_tab.p,
+                                                                (uint16_t*)((char*)T.sl_tab.p + geo_off), d_info);
     sl_rowbase_kernel<<<1, 1024, 0, c->stream>>>(d_nslots, NT, d_rowbase, d_info);
     EORB_LAUNCH_CHECK(c, "slot table kernels");
     if (c->sl_rank_ok < 0) {
@@ -1190,41 +1190,41 @@ int ev_slots_prepare_launch(eorb_ctx* c, int W, int H, int h, int TX, int TY)
     }
     int* rb = readback_buf(c);
     if (!rb) return set_err(c, EORB_E_HIP, "pinned alloc failed");
-    EORB_HIP(c, hipMemcpyAsync(rb + 8, d_info, sizeof(c->sl_hinfo), hipMemcpyDeviceToHost, c->stream));
-    c->sl_launched = 1;
+    EORB_HIP(c, hipMemcpyAsync(rb + 8, d_info, sizeof(int) * 6, hipMemcpyDeviceToHost, c->stream));
+    T.sl_launched = 1;
     return EORB_OK;
 }
 
-int ev_slots_prepare_finish(eorb_ctx* c, int W, int H, int h, int TX, int TY, const float* d_stamps, int stamp_stride, int SWP, float two_sig2, float norm)
+int ev_slots_prepare_finish(eorb_ctx* c, PosTables& T, int W, int H, int h, int TX, int TY, const float* d_stamps, int stamp_stride, int SWP, float two_sig2, float norm)
 {
-    if (!c->sl_launched) return EORB_OK;
-    c->sl_launched = 0;
-    const int nsrc = c->lut_w * c->lut_h, NT = TX * TY;
-    memcpy(c->sl_hinfo, readback_buf(c) + 8, sizeof(c->sl_hinfo));
-    const int* hinfo = c->sl_hinfo;
+    if (!T.sl_launched) return EORB_OK;
+    T.sl_launched = 0;
+    const int nsrc = T.w * T.h, NT = TX * TY;
+    int hinfo[6];
+    memcpy(hinfo, readback_buf(c) + 8, sizeof(hinfo));
     int rc;
     if (c->sl_rank_ok < 0) c->sl_rank_ok = (hinfo[4] == 0 && hinfo[5] == 0) ? 1 : 0;
     if (hinfo[2] || hinfo[1] >= (int)kNoSlot || hinfo[0] <= 0) return EORB_OK;      // a tile with more than 254 slots: the batch pipeline serves these maps
-    if ((rc = ensure(c, c->sl_rows, sizeof(float) * 64 * (size_t)hinfo[0] + 4096 + 256 * 256))) return rc;      // + slack: sl_hot_kernel loads 240 rows whatever the tile holds
-    const uint32_t* d_rowbase = (const uint32_t*)c->sl_tile.p + NT;
-    sl_rows_kernel<<<(nsrc + 3) / 4, 256, 0, c->stream>>>((const uint32_t*)c->src_info.p, (const uint2*)c->sl_tab.p, nsrc, W, H, h, TX, d_stamps,
-                                                            stamp_stride, SWP, (const float2*)c->lut.p, two_sig2, norm, d_rowbase, (float*)c->sl_rows.p);
+    if ((rc = ensure(c, T.sl_rows, sizeof(float) * 64 * (size_t)hinfo[0] + 4096 + 256 * 256))) return rc;      // + slack: sl_hot_kernel loads 240 rows whatever the tile holds
+    const uint32_t* d_rowbase = (const uint32_t*)T.sl_tile.p + NT;
+    sl_rows_kernel<<<(nsrc + 3) / 4, 256, 0, c->stream>>>((const uint32_t*)T.src_info.p, (const uint2*)T.sl_tab.p, nsrc, W, H, h, TX, d_stamps,
+                                                            stamp_stride, SWP, (const float2*)T.lut.p, two_sig2, norm, d_rowbase, (float*)T.sl_rows.p);
     EORB_LAUNCH_CHECK(c, "sl_rows_kernel");
-    c->sl_null = hinfo[1];
-    c->sl_ok = 1;
+    T.sl_null = hinfo[1];
+    T.sl_ok = 1;
     return EORB_OK;
 }
 
-// tables of the current maps / sigma (called from ev_raw_tables when they change); c->sl_ok = 1 when the slot form can run
-int ev_slots_prepare(eorb_ctx* c, int W, int H, int h, int TX, int TY, const float* d_stamps, int stamp_stride, int SWP, float two_sig2, float norm)
+// slot tables of the set T for an image size / sigma (called from ev_raw_tables when they change); T.sl_ok = 1 when the slot form can run
+int ev_slots_prepare(eorb_ctx* c, PosTables& T, int W, int H, int h, int TX, int TY, const float* d_stamps, int stamp_stride, int SWP, float two_sig2, float norm)
 {
     int rc;
-    if (!c->sl_launched) {
-        if ((rc = ev_slots_prepare_launch(c, W, H, h, TX, TY))) return rc;
-        if (!c->sl_launched) return EORB_OK;
+    if (!T.sl_launched) {
+        if ((rc = ev_slots_prepare_launch(c, T, W, H, h, TX, TY))) return rc;
+        if (!T.sl_launched) return EORB_OK;
         EORB_HIP(c, hipStreamSynchronize(c->stream));
     }
-    return ev_slots_prepare_finish(c, W, H, h, TX, TY, d_stamps, stamp_stride, SWP, two_sig2, norm);
+    return ev_slots_prepare_finish(c, T, W, H, h, TX, TY, d_stamps, stamp_stride, SWP, two_sig2, norm);
 }
 
 // dynamic-LDS opt-in of one kernel instantiation, once per CONTEXT (= per device: a second context may sit on another GPU)
@@ -1304,7 +1304,7 @@ static int sl_streams(eorb_ctx* c)
 // count -> scan -> scatter -> plan -> gather for the B slices of one PART of a batch (the whole batch, or one of its halves), on the
 // part's own workspaces.  Streams: binning on the context's stream; the plan on P; the long lists on H; the LDS gather on G when the
 // batch runs in halves (so that the next half's binning, HBM- and LDS-atomic-bound, runs under it), else on the context's stream.
-static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, const void* d_events, int stride_in, const int64_t* h_offsets, int B,
+static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int part, int nparts, const void* d_events, int stride_in, const int64_t* h_offsets, int B,
                       int W, int H, int TX, int TY, float* d_f32, uint32_t* d_minmax_enc, const SlotScatterChoice& sc, const SlotDict* dict)
 {
     // with a position dictionary the count pass reads the float events and writes the hashed records every later pass reads
@@ -1368,17 +1368,17 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
     uint32_t* d_segbase = (uint32_t*)((char*)ws.segoff.p + cnt_bytes);
     uint32_t* d_tile_cnt = (uint32_t*)ws.tile_order.p;
     uint32_t* d_tile_base = d_tile_cnt + nb;
-    uint32_t* d_nslots = (uint32_t*)c->sl_tile.p;
+    uint32_t* d_nslots = (uint32_t*)T.sl_tile.p;
     uint32_t* d_rowbase = d_nslots + NT;
     int* d_info = (int*)(d_nslots + 5 * (size_t)NT);
     const eorb_raw_event* d_ev = dict ? (const eorb_raw_event*)dict->rec : (const eorb_raw_event*)d_events;
     int scat_stride = stride;
     bool prerank = false;                             // the count pass left ranked 8-byte records: sl_scatter_pre_kernel
-    const uint2* d_tab = (const uint2*)c->sl_tab.p;
+    const uint2* d_tab = (const uint2*)T.sl_tab.p;
     const int ncu = sl_ncu(c);
     const int NTp = (NT + 1) & ~1;
     // ---- the gather's plan: sizes first (its buffers are allocated before anything of the part is launched) ----
-    const size_t lds_g = (size_t)(c->sl_null + 1) * 256;
+    const size_t lds_g = (size_t)(T.sl_null + 1) * 256;
     const int wg_per_cu = std::max(1, (int)((160 * 1024) / lds_g));
     static const int nw_env = [] { const char* e = getenv("EORB_SLOT_WAVES"); return e ? atoi(e) : 0; }();
     static const int ns_env = [] { const char* e = getenv("EORB_SLOT_ROUNDS"); return e ? atoi(e) : 0; }();
@@ -1404,10 +1404,10 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
     // cycles per entry instead of 29, which shortens the launch's longest chains AND moves more entries per second; shorter lists
     // would not repay the 240 row loads per list (measured at 128 x 1 Mev: threshold 4 096 ... 8 192 1.40-1.45 ms, 16 384 1.53, none 2.44)
     static const long long hot_env = [] { const char* e = getenv("EORB_SLOT_HOT_MIN"); return e ? atoll(e) : -1ll; }();
-    uint32_t hot_min = c->sl_null <= SL_HOT_NROWS ? (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, nev * nparts / 16000), 0x7fffffff) : 0u;
+    uint32_t hot_min = T.sl_null <= SL_HOT_NROWS ? (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, nev * nparts / 16000), 0x7fffffff) : 0u;
     const long long hot_over = c->dbg_slot_hot_min >= 0 ? c->dbg_slot_hot_min : hot_env;
     // (never below 64: the register-row kernel's tail load reads the 64 bytes that END at the list's end; 0 = that kernel off)
-    if (hot_over >= 0) hot_min = (c->sl_null <= SL_HOT_NROWS && hot_over > 0) ? (uint32_t)std::min<long long>(std::max<long long>(hot_over, 64), 0x7fffffff) : 0u;
+    if (hot_over >= 0) hot_min = (T.sl_null <= SL_HOT_NROWS && hot_over > 0) ? (uint32_t)std::min<long long>(std::max<long long>(hot_over, 64), 0x7fffffff) : 0u;
     const uint32_t hot_cap = c->dbg_slot_hot_cap > 0 ? (uint32_t)std::min(c->dbg_slot_hot_cap, kHotCap) : (uint32_t)kHotCap;
     if ((rc = ensure(c, ws.hot, sizeof(HotDesc) * (size_t)kHotBuckets * kHotCap + 256))) return rc;
     uint32_t* d_hot_cnt = (uint32_t*)ws.hot.p;                           // 16 bucket counts | ticket (at word 32) | overflow count (33) | descriptors (from byte 256)
@@ -1416,12 +1416,12 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
         std::unique_ptr<ProfScope> ps(new ProfScope(c, "ev_count"));      // (one scope per kernel of the binning: count, scan, scatter)
         const size_t lds = sizeof(uint32_t) * (size_t)NT;
         // the tile ranges of all sensor pixels + one set of counters per wavefront in the LDS of one workgroup per CU?
-        const size_t nsrc = (size_t)c->lut_w * (size_t)c->lut_h;
+        const size_t nsrc = (size_t)T.w * (size_t)T.h;
         const size_t lds_c = 4 * ((nsrc + 2) / 2) + (size_t)kCountWaves * NTp * 2;
         static const int cl_env = [] { const char* e = getenv("EORB_SLOT_COUNT_LDS"); return e ? atoi(e) : 1; }();
         if (dict && !(TX <= 127 && TY <= 127 && lds_c <= 159 * 1024)) return set_err(c, EORB_E_CAPACITY, "slot form: the position dictionary needs the LDS count pass");
         if (nchunks && dict) {
-            const uint16_t* d_geo = (const uint16_t*)((const char*)c->sl_tab.p + sizeof(uint2) * nsrc);
+            const uint16_t* d_geo = (const uint16_t*)((const char*)T.sl_tab.p + sizeof(uint2) * nsrc);
             const int g = std::min(ncu, (nchunks + kCountWaves - 1) / kCountWaves);
             static const int pre_env_d = [] { const char* e = getenv("EORB_SLOT_PRERANK"); return e ? atoi(e) : 1; }();
             const int pre_on_d = c->dbg_slot_prerank >= 0 ? c->dbg_slot_prerank : pre_env_d;
@@ -1430,14 +1430,14 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
                 if ((rc = ensure(c, ws.rec16, sizeof(uint64_t) * (size_t)std::max<int64_t>(h_offsets[B], 1)))) return rc;
                 prerank = true;
                 if ((rc = sl_optin(c, 21, (const void*)sl_count_lds_kernel<16, true, true>, 159 * 1024))) return rc;
-                sl_count_lds_kernel<16, true, true><<<g, 64 * kCountWaves, lds_c, M>>>((const eorb_raw_event*)d_events, d_chunks, nchunks, d_geo, c->lut_w, c->lut_h, TX, NT, d_segcnt, *dict, (uint16_t*)ws.rec16.p);
+                sl_count_lds_kernel<16, true, true><<<g, 64 * kCountWaves, lds_c, M>>>((const eorb_raw_event*)d_events, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, *dict, (uint16_t*)ws.rec16.p);
             } else {
             if ((rc = sl_optin(c, 13, (const void*)sl_count_lds_kernel<16, true>, 159 * 1024))) return rc;
-            sl_count_lds_kernel<16, true><<<g, 64 * kCountWaves, lds_c, M>>>((const eorb_raw_event*)d_events, d_chunks, nchunks, d_geo, c->lut_w, c->lut_h, TX, NT, d_segcnt, *dict);
+            sl_count_lds_kernel<16, true><<<g, 64 * kCountWaves, lds_c, M>>>((const eorb_raw_event*)d_events, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, *dict);
             }
         }
         else if (nchunks && cl_env && TX <= 127 && TY <= 127 && lds_c <= 159 * 1024) {
-            const uint16_t* d_geo = (const uint16_t*)((const char*)c->sl_tab.p + sizeof(uint2) * nsrc);
+            const uint16_t* d_geo = (const uint16_t*)((const char*)T.sl_tab.p + sizeof(uint2) * nsrc);
             const int g = std::min(ncu, (nchunks + kCountWaves - 1) / kCountWaves);
             // 16-byte records on a sensor of at most 65 535 pixels: the pass leaves a 2-byte record per event for the scatter
             static const int tc_env = [] { const char* e = getenv("EORB_SLOT_TRANSCODE"); return e ? atoi(e) : 1; }();
@@ -1451,7 +1451,7 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
                 d_rec16 = (uint16_t*)ws.rec16.p;
                 prerank = true;
 #define SL_COUNTR(ST, BIT) do { if ((rc = sl_optin(c, BIT, (const void*)sl_count_lds_kernel<ST, false, true>, 159 * 1024))) return rc; \
-                sl_count_lds_kernel<ST, false, true><<<g, 64 * kCountWaves, lds_c, M>>>(d_ev, d_chunks, nchunks, d_geo, c->lut_w, c->lut_h, TX, NT, d_segcnt, SlotDict{nullptr, 0u, nullptr, nullptr, 0}, d_rec16); } while (0)
+                sl_count_lds_kernel<ST, false, true><<<g, 64 * kCountWaves, lds_c, M>>>(d_ev, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, SlotDict{nullptr, 0u, nullptr, nullptr, 0}, d_rec16); } while (0)
                 if (stride == 16) SL_COUNTR(16, 18); else if (stride == 4) SL_COUNTR(4, 19); else SL_COUNTR(2, 20);
 #undef SL_COUNTR
             }
@@ -1461,17 +1461,17 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
                 d_rec16 = (uint16_t*)ws.rec16.p;
             }
 #define SL_COUNT(ST, BIT) do { if ((rc = sl_optin(c, BIT, (const void*)sl_count_lds_kernel<ST>, 159 * 1024))) return rc; \
-                sl_count_lds_kernel<ST><<<g, 64 * kCountWaves, lds_c, M>>>(d_ev, d_chunks, nchunks, d_geo, c->lut_w, c->lut_h, TX, NT, d_segcnt, SlotDict{nullptr, 0u, nullptr, nullptr}, d_rec16); } while (0)
+                sl_count_lds_kernel<ST><<<g, 64 * kCountWaves, lds_c, M>>>(d_ev, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, SlotDict{nullptr, 0u, nullptr, nullptr}, d_rec16); } while (0)
             if (stride == 16) SL_COUNT(16, 0); else if (stride == 4) SL_COUNT(4, 1); else if (stride == 2) SL_COUNT(2, 10); else SL_COUNT(-4, 2);
 #undef SL_COUNT
             if (d_rec16) { d_ev = (const eorb_raw_event*)d_rec16; scat_stride = 2; }
             }
         }
         else if (nchunks) {
-            if (stride == 16) sl_count_kernel<16><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, c->lut_w, c->lut_h, TX, NT, d_segcnt);
-            else if (stride == 4) sl_count_kernel<4><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, c->lut_w, c->lut_h, TX, NT, d_segcnt);
-            else if (stride == 2) sl_count_kernel<2><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, c->lut_w, c->lut_h, TX, NT, d_segcnt);
-            else sl_count_kernel<-4><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, c->lut_w, c->lut_h, TX, NT, d_segcnt);
+            if (stride == 16) sl_count_kernel<16><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, d_segcnt);
+            else if (stride == 4) sl_count_kernel<4><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, d_segcnt);
+            else if (stride == 2) sl_count_kernel<2><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, d_segcnt);
+            else sl_count_kernel<-4><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, d_segcnt);
         }
         ps.reset(); ps.reset(new ProfScope(c, "ev_scan"));
         sl_scan_kernel<<<B, 1024, 0, M>>>(d_slice_c0, d_segcnt, NT, d_segbase, d_tile_cnt, d_tile_base);
@@ -1493,29 +1493,29 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
             const uint16_t* d_segcnt_c = d_segcnt;
             if (sc.waves == 16) {
                 if ((rc = sl_optin(c, 16, (const void*)sl_scatter_pre_kernel<16>, 159 * 1024))) return rc;
-                sl_scatter_pre_kernel<16><<<nchunks, 64 * 16, lds_p, M>>>((const uint64_t*)ws.rec16.p, d_chunks, d_tab, c->lut_w * c->lut_h, TX, NT, chunk, d_slice_eb, d_segcnt_c, d_segbase, d_tile_base, (slot_entry*)ws.entries.p);
+                sl_scatter_pre_kernel<16><<<nchunks, 64 * 16, lds_p, M>>>((const uint64_t*)ws.rec16.p, d_chunks, d_tab, T.w * T.h, TX, NT, chunk, d_slice_eb, d_segcnt_c, d_segbase, d_tile_base, (slot_entry*)ws.entries.p);
             } else {
                 if ((rc = sl_optin(c, 17, (const void*)sl_scatter_pre_kernel<8>, 159 * 1024))) return rc;
-                sl_scatter_pre_kernel<8><<<nchunks, 64 * 8, lds_p, M>>>((const uint64_t*)ws.rec16.p, d_chunks, d_tab, c->lut_w * c->lut_h, TX, NT, chunk, d_slice_eb, d_segcnt_c, d_segbase, d_tile_base, (slot_entry*)ws.entries.p);
+                sl_scatter_pre_kernel<8><<<nchunks, 64 * 8, lds_p, M>>>((const uint64_t*)ws.rec16.p, d_chunks, d_tab, T.w * T.h, TX, NT, chunk, d_slice_eb, d_segcnt_c, d_segbase, d_tile_base, (slot_entry*)ws.entries.p);
             }
         }
         else if (nchunks && sc.rank) {
 #define SL_SCAT(ST, NW, BIT) do { if ((rc = sl_optin(c, BIT, (const void*)sl_scatter_rank_kernel<ST, NW>, 159 * 1024))) return rc; \
-                sl_scatter_rank_kernel<ST, NW><<<nchunks, 64 * NW, sc.lds, M>>>(d_ev, d_chunks, d_tab, c->lut_w, c->lut_h, TX, NT, chunk, \
+                sl_scatter_rank_kernel<ST, NW><<<nchunks, 64 * NW, sc.lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, chunk, \
                                                                                    d_slice_eb, d_segbase, d_tile_base, (slot_entry*)ws.entries.p); } while (0)
             if (sc.waves == 16) { if (stride == 16) SL_SCAT(16, 16, 3); else if (stride == 4) SL_SCAT(4, 16, 4); else if (stride == 2) SL_SCAT(2, 16, 11); else SL_SCAT(-4, 16, 5); }
             else { if (stride == 16) SL_SCAT(16, 8, 6); else if (stride == 4) SL_SCAT(4, 8, 7); else if (stride == 2) SL_SCAT(2, 8, 12); else SL_SCAT(-4, 8, 8); }
 #undef SL_SCAT
         }
         else if (nchunks)
-            sl_scatter_kernel<<<nchunks, 64 * kSlotScatWaves, sc.lds, M>>>(d_ev, d_chunks, d_tab, stride, c->lut_w, c->lut_h, TX, TY, NT, chunk,
+            sl_scatter_kernel<<<nchunks, 64 * kSlotScatWaves, sc.lds, M>>>(d_ev, d_chunks, d_tab, stride, T.w, T.h, TX, TY, NT, chunk,
                                                                                  d_slice_eb, d_segbase, d_tile_base, (slot_entry*)ws.entries.p);
         EORB_LAUNCH_CHECK(c, "ev_bin (slot) kernels");
     }
     EORB_HIP(c, hipEventRecord(E[2], M));                                // the part's entries are in place
     {
-        SlotGather Pg{d_task, d_items, (const uint8_t*)ws.entries.p, d_nslots, d_rowbase, (const float*)c->sl_rows.p,
-                      d_tile_w, d_ctr, d_f32, d_minmax_enc, d_info, (int*)c->status.p, B, W, H, TX, NT, c->sl_null, prio_ref, nullptr};
+        SlotGather Pg{d_task, d_items, (const uint8_t*)ws.entries.p, d_nslots, d_rowbase, (const float*)T.sl_rows.p,
+                      d_tile_w, d_ctr, d_f32, d_minmax_enc, d_info, (int*)c->status.p, B, W, H, TX, NT, T.sl_null, prio_ref, nullptr};
 #ifdef EORB_SLOT_TRACE
         if ((rc = ensure(c, c->sl_trace, sizeof(unsigned long long) * 6 * 16 * (size_t)Gt + 64))) return rc;
         EORB_HIP(c, hipMemsetAsync(c->sl_trace.p, 0, sizeof(unsigned long long) * 6 * 16 * (size_t)Gt + 64, M));
@@ -1529,7 +1529,7 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
             const int hw = c->dbg_slot_hot_waves > 0 ? c->dbg_slot_hot_waves : (hw_env > 0 ? hw_env : 8 * ncu);     // two per SIMD: all of its registers
             EORB_HIP(c, hipStreamWaitEvent(Hs, E[2], 0));
             EORB_HIP(c, hipStreamWaitEvent(Hs, E[1], 0));
-            sl_hot_kernel<<<hw, 64, 0, Hs>>>(d_hot_cnt, d_hot_cnt + 32, d_hot_items, kHotCap, (const float*)c->sl_rows.p, (const slot_entry*)ws.entries.p,
+            sl_hot_kernel<<<hw, 64, 0, Hs>>>(d_hot_cnt, d_hot_cnt + 32, d_hot_items, kHotCap, (const float*)T.sl_rows.p, (const slot_entry*)ws.entries.p,
                                              d_f32, d_minmax_enc, W, H);
         }
         EORB_HIP(c, hipEventRecord(E[3], Hs));
@@ -1549,7 +1549,7 @@ static int slots_part(eorb_ctx* c, eorb_ctx::SlotWS& ws, int part, int nparts, c
 // the register-row kernel of the first half (vector-ALU / LDS-read / scalar-ALU bound) beside the count and scatter passes of the
 // second (HBM- and LDS-atomic bound).  Returns kSlotDeclined (> 0, nothing launched) when the batch's shape does not
 // fit: the caller goes on with the batch pipeline.
-int ev_slots_accumulate(eorb_ctx* c, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H, int TX, int TY,
+int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H, int TX, int TY,
                         float* d_f32, uint32_t* d_minmax_enc, const SlotDict* dict)
 {
     const int NT = TX * TY;
@@ -1580,7 +1580,7 @@ int ev_slots_accumulate(eorb_ctx* c, const void* d_events, int stride, const int
     const int B0 = nparts == 2 ? B / 2 : B;
     for (int part = 0; part < nparts; part++) {
         const int b0 = part ? B0 : 0, nb_ = part ? B - B0 : B0;
-        if ((rc = slots_part(c, c->sl_ws[part], part, nparts, d_events, stride, h_offsets + b0, nb_, W, H, TX, TY,
+        if ((rc = slots_part(c, T, c->sl_ws[part], part, nparts, d_events, stride, h_offsets + b0, nb_, W, H, TX, TY,
                              d_f32 + (size_t)b0 * W * H, d_minmax_enc + 2 * (size_t)b0, sc, dict))) return rc;
     }
     // whatever the other streams did is done before the images are read (streams are in order: the last part's events cover the first's)

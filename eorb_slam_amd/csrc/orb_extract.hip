@@ -1685,18 +1685,18 @@ int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H)
     return EORB_OK;
 }
 
-// the pyramid of B images (or, when the caller left the normalisation of its float images to this kernel, of c->pyr0_f32: d_img is
+// the pyramid of B images (or, when the caller left the normalisation of its float images to this kernel, of d_f32 and their running extremes d_mm: d_img is
 // then where the u8 images go) and the blurred levels of it; grid sizes as orb_extract_dev has always had them (the kernels are grid-stride)
-static void launch_pyramid(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t img_slice_bytes, int B, int32_t* err_flag)
+static void launch_pyramid(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t img_slice_bytes, int B, int32_t* err_flag,
+                           const float* d_f32 = nullptr, const uint32_t* d_mm = nullptr)
 {
     OrbState& o = c->orb;
     const DevGeom* G = (const DevGeom*)o.geom.p;
     uint8_t* pyr = (uint8_t*)c->pyr.p;
     const dim3 grid0((o.lv[0].bw * o.lv[0].bh / 4 + 256) / 256, B);
-    if (c->pyr0_f32) {
-        pyr_level0_f32_kernel<<<grid0, 256, 0, c->stream>>>(c->pyr0_f32, c->pyr0_mm, const_cast<uint8_t*>(d_img), img_stride, img_slice_bytes, G, pyr, err_flag);
-        c->pyr0_f32 = nullptr; c->pyr0_mm = nullptr;
-    } else
+    if (d_f32)
+        pyr_level0_f32_kernel<<<grid0, 256, 0, c->stream>>>(d_f32, d_mm, const_cast<uint8_t*>(d_img), img_stride, img_slice_bytes, G, pyr, err_flag);
+    else
         pyr_level0_kernel<<<grid0, 256, 0, c->stream>>>(d_img, img_stride, img_slice_bytes, G, pyr, err_flag);
     for (int l = 1; l < o.nlevels; l++) {
         const int n = o.lv[l].bw * o.lv[l].bh;
@@ -1714,7 +1714,7 @@ static void launch_blur(eorb_ctx* c, int B)
 
 int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t img_slice_bytes, int B, int lap0, int lap1,
                     int want_desc, eorb_keypoint* d_kps, uint8_t* d_desc, uint8_t* d_oob, int32_t* d_n, int32_t* d_mono,
-                    int32_t* d_flag_out)
+                    int32_t* d_flag_out, const float* d_level0_f32, const uint32_t* d_level0_mm)
 {
     OrbState& o = c->orb;
     if (!o.configured) return set_err(c, EORB_E_NOTCONF, "orb_extract: eorb_orb_configure not called");
@@ -1738,7 +1738,7 @@ int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t im
     o.last_B = B; o.last_blur = want_desc != 0; o.last_cells = true;
     {
         ProfScope ps(c, "orb_pyr");
-        launch_pyramid(c, d_img, img_stride, img_slice_bytes, B, err_flag);
+        launch_pyramid(c, d_img, img_stride, img_slice_bytes, B, err_flag, d_level0_f32, d_level0_mm);
         EORB_LAUNCH_CHECK(c, "pyramid kernels");
     }
     {

@@ -139,6 +139,77 @@ def test_float_bulk_position_dictionary(oracle, fe):
     cc.dev_free(d_ev); cc.dev_free(d_img); cc.close()
 
 
+def test_raw_and_float_bulk_calls_share_a_context(oracle, fe):
+    """Raw calls (the maps' tables), float bulk calls (the per-call position tables) and dictionary calls interleaved on ONE context: each
+    keeps to its own set of tables.  Every image against the oracle; a raw call behind a float call rebuilds nothing (the launch count of
+    the ev_stamp_tables scope stands, the maps' slot tables keep their flags), a change of sigma rebuilds once.  Then a float slice
+    through eorb_ev_slice_extract (whose extraction builds level 0 from the float image) followed by eorb_orb_extract of a u8 image."""
+    import ctypes as C
+    W, H = 64, 48
+    mx, my = _maps(W, H)
+    c = fe.Context()
+    fe.EvImConverter.set_undistort_maps(mx, my, True, ctx=c)
+    c.prof_enable(True)
+    c.debug_option("gather_form", 4); c.debug_option("dedupe_min_events", 1)
+    raws = [synth.random_raw_events(6000, W, H, seed=60 + k) for k in range(4)]
+    fl = oracle.undistort_events(synth.random_raw_events(6000, W, H, seed=70), mx, my, W, H, True, 1.0)
+    moved = fl.copy(); moved["x"][777] += np.float32(0.125)
+    builds = lambda: c.prof_results().get("ev_stamp_tables", (0.0, 0))[1]
+    cnt = lambda: (c.debug_counter("dict_hits"), c.debug_counter("dict_misses"))
+
+    def raw_call(raw, sigma=1.0):
+        ev = oracle.undistort_events(raw, mx, my, W, H, True, 1.0)
+        of, ou, omm = oracle.ev2im_gauss(ev, W, H, sigma, False, True, fast=True)
+        gf, gu, gmm = fe.EvImConverter.ev2im_gauss_raw(raw, W, H, sigma, False, True, ctx=c, return_all=True)
+        assert _same_bits(of, gf) and np.array_equal(ou, gu) and _same_bits(np.asarray(omm, np.float32), gmm), ("raw", len(raw), sigma)
+
+    def float_call(ev):
+        of, ou, omm = oracle.ev2im_gauss(ev, W, H, 1.0, False, True, fast=True)
+        gf, gu, gmm = fe.EvImConverter.ev2im_gauss(ev, W, H, 1.0, False, True, ctx=c, return_all=True)
+        assert _same_bits(of, gf) and np.array_equal(ou, gu) and _same_bits(np.asarray(omm, np.float32), gmm), ("float", len(ev))
+
+    def raw_call_rebuilds_nothing(raw):
+        b = builds()
+        raw_call(raw)
+        assert builds() == b and c.debug_counter("slot_flags") == flags0
+
+    raw_call(raws[0])                                                   # 1
+    b1, flags0, calls1 = builds(), c.debug_counter("slot_flags"), c.debug_counter("slot_calls")
+    assert b1 == 1 and calls1 == 1
+    float_call(fl)                                                      # 2: tabulates, freezes
+    assert c.debug_counter("dict_positions") > 0 and cnt() == (0, 0)
+    raw_call_rebuilds_nothing(raws[0])                                  # 3
+    float_call(fl); assert cnt() == (1, 0)                              # 4: served by the dictionary
+    raw_call_rebuilds_nothing(raws[1])                                  # 5
+    float_call(moved); assert cnt() == (1, 1)                           # 6: a position the dictionary does not hold
+    raw_call_rebuilds_nothing(raws[2])                                  # 7
+    # 8: the binning-free form (one slice of at most 16 384 events) on the maps' src_info -- its own pass over the events is the one
+    # launch of the scope -- and, with the bulk path off, on per-event tables; with it on, the float events still find their dictionary
+    c.debug_option("gather_form", 0)
+    b = builds(); raw_call(raws[3]); assert builds() == b + 1 and c.debug_counter("slot_flags") == flags0
+    h = cnt()[0]; float_call(moved); assert cnt() == (h + 1, 1)
+    c.debug_option("dedupe_min_events", 1 << 20)
+    float_call(fl); assert cnt() == (h + 1, 1)
+    c.debug_option("gather_form", 4)
+    for sigma in (0.7, 1.0):                                            # 9: another sigma: the maps' tables are built again, once
+        b = builds(); raw_call(raws[0], sigma); assert builds() == b + 1
+    raw_call_rebuilds_nothing(raws[1])
+    # a float slice whose extraction normalises the float image itself, then a u8 image on the same context
+    c.debug_option("gather_form", 0)
+    W2, H2 = 240, 180
+    ge = fe.ORBextractor(1000, 1.2, 4, 10, 0, 19, imSize=(W2, H2), ctx=c)
+    oe = oracle.OrbExtractor(1000, 1.2, 4, 10, 0, edgeTh=19, imWidth=W2, fast=True)
+    evs = [np.ascontiguousarray(synth.shapes_events(2000, W2, H2, seed=80 + k, motion=0.5, undistort=True)) for k in range(2)]
+    imgs = [oracle.ev2im_gauss(e, W2, H2, 1.0, False, True, fast=True)[1] for e in evs]
+    kps = np.zeros(ge.cap, synth.KP_DTYPE); desc = np.zeros((ge.cap, 32), np.uint8); oob = np.zeros(ge.cap, np.uint8)
+    n = C.c_int(0); mono = C.c_int(0)
+    c.check(c.L.eorb_ev_slice_extract(c.h, fe._p(evs[0]), None, len(evs[0]), 1.0, 0, 1000, 1, fe._p(kps), fe._p(desc), fe._p(oob), ge.cap, C.byref(n), C.byref(mono), None))
+    for img, (gk, gd) in ((imgs[0], (kps[:n.value], desc[:n.value])), (imgs[1], ge(imgs[1])[1:3])):
+        _, ok, od, _ = oe.extract(img)
+        assert len(ok) == len(gk) and np.array_equal(ok.view(np.uint8), gk.view(np.uint8)) and np.array_equal(od, gd)
+    c.close()
+
+
 def test_ev2im_gauss_shapes_lut(oracle, fe, ctx):
     """C1 stand-in: LUT-undistorted shapes events, L1 chunk (2000) and L2 window (6000)."""
     for n in (2000, 6000, 50000):
