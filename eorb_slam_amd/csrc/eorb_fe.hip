@@ -3508,6 +3508,11 @@ int eorb_distinctive_descriptors(eorb_ctx* c, const uint8_t* desc, const int32_t
     if (M < 0 || (M > 0 && (!offsets || !best))) return set_err(c, EORB_E_ARG, "distinctive_descriptors: bad arguments");
     if (M == 0) return EORB_OK;
     for (int m = 0; m < M; m++) if (offsets[m + 1] < offsets[m]) return set_err(c, EORB_E_ARG, "distinctive_descriptors: offsets not monotone");
+    // (distinctive_kernel counts a row's distances in 16-bit bins, two to a 32-bit word: see there)
+    if (offsets[0] < 0) return set_err(c, EORB_E_ARG, "distinctive_descriptors: negative offset");
+    for (int m = 0; m < M; m++)
+        if ((long long)offsets[m + 1] - offsets[m] > 65535)
+            return set_err(c, EORB_E_CAPACITY, "distinctive_descriptors: map point %d has %d rows, more than the 65535 a 16-bit bin counts", m, (int)(offsets[m + 1] - offsets[m]));
     fe_enter(c);
     const int n = offsets[M];
     int rc;

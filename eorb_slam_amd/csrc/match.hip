@@ -2047,6 +2047,9 @@ int sort_response_dev(eorb_ctx* c, const eorb_keypoint* d_kps, int n, int32_t* d
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423), batched over map points: one workgroup per map point,
 // thread i owns row i of the N x N distance matrix; its median is read off a 257-bin counting histogram (distances are
 // integers in [0, 256]); the first row with the smallest median wins.
+// The bins are 16 bits wide and bins d and d ^ 1 share the 32-bit word that the atomic adds to, so a row may hold at most 65 535
+// equal distances: one more carries out of the low bin into its neighbour (or out of the word).  A row has N distances, so
+// eorb_distinctive_descriptors refuses a map point with N > 65 535 (EORB_E_CAPACITY) before anything is launched.
 __global__ __launch_bounds__(256) void distinctive_kernel(const uint8_t* __restrict__ desc, const int32_t* __restrict__ offsets,
                                                           int32_t* __restrict__ best)
 {

@@ -899,7 +899,8 @@ int eorb_search_by_bow_kf_keyframes(eorb_ctx* ctx,
 
 /* replaces MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423; f3), batched over M map points: the
  * descriptors observed for map point m are rows offsets[m] .. offsets[m+1]-1 of desc (n x 32); best[m] = the row (relative
- * to offsets[m]) with the least median Hamming distance to the others, -1 when there is none. */
+ * to offsets[m]) with the least median Hamming distance to the others, -1 when there is none.  At most 65 535 rows per map point
+ * (EORB_E_CAPACITY beyond, decided from the offsets before desc is read); offsets[0] >= 0 (EORB_E_ARG). */
 int eorb_distinctive_descriptors(eorb_ctx* ctx, const uint8_t* desc, const int32_t* offsets, int M, int32_t* best);
 
 /* ---- KLT tracker ----------------------------------------------------------------------------------

@@ -389,8 +389,10 @@ def test_projection_stereo_gate_known_answers(oracle):
 def test_compute_stereo_matches_known_answers(oracle):
     """Frame::ComputeStereoMatches (src/Frame.cc:869-1048) on a pair whose answer is known: the right image is the left one moved by
     exactly 6 pixels, so every accepted match has its best shift at the keypoint itself (a zero L1 norm, a symmetric parabola unless
-    the neighbours differ) and a disparity within a pixel of 6; the median cut keeps the zero norms; no right keypoints -> no match;
-    a baseline that forbids the disparity (maxD = mbf / mb < 6) -> no match."""
+    the neighbours differ) and a disparity within a pixel of 6; the median cut keeps the zero norms HERE, because more than half of
+    the 866 accepted matches lie on the levels >= 1, where the resized images differ: the median norm is 122 and thDist 256.2.  (With a
+    median of 0 the cut takes back every match, zero norms included, since `0 < 0` is false: tests/helper_scenes.py, pairs "identical" and
+    "moved_maxd_6".)  No right keypoints -> no match; a baseline that forbids the disparity (maxD = mbf / mb < 6) -> no match."""
     left = synth.texture_image(346 + 16, 260, seed=4)
     right = np.ascontiguousarray(left[:, 6:6 + 346]); left = np.ascontiguousarray(left[:, :346])
     eL = oracle.OrbExtractor(1000, 1.2, 8, 20, 7, edgeTh=19, imWidth=346); eR = oracle.OrbExtractor(1000, 1.2, 8, 20, 7, edgeTh=19, imWidth=346)
