@@ -44,7 +44,7 @@ struct LevelGeom {
     int cand_cap;        // candidate capacity of the level
     int cand_off;        // offset (entries) of the level's candidate array inside a slice block
     int nfeat;           // mnFeaturesPerLevel
-    int kp_cap;          // nfeat + slack
+    int kp_cap;          // max(nfeat + slack, 4 * octree roots)
     int kp_off;          // offset (entries) of the level's keypoint array inside a slice block
     int xtab_off, ytab_off;   // resize coefficient tables (int offsets into the table buffer)
     int xmax;            // first dx whose source column is clamped (HResize)

@@ -1559,13 +1559,18 @@ int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H)
         L.cell_off = cells; cells += L.nCols * L.nRows;
         cell_cap = std::max(cell_cap, ((L.wCell + 1) / 2) * ((L.hCell + 1) / 2));
         L.nfeat = o.nfeat[l];
-        L.kp_cap = L.nfeat + 8;
+        // The octree's first pass over nIni roots yields up to 4 * nIni nodes before the list is compared with the quota N for the
+        // first time (:688), and the reference returns them all.  From then on a full pass is only run while size + 3 * nToExpand <= N
+        // (the list stays <= N), and a cut-off division adds at most 3 nodes and the walk stops at the first size >= N (:749):
+        // <= N + 2.  So a level returns at most max(N + 2, 4 * nIni); N + 8 is the slack it has always had (node_cap below
+        // already holds the 4 * nIni first-pass nodes).
+        L.kp_cap = std::max(L.nfeat + 8, 4 * nIni);
         L.kp_off = kp_total; kp_total += L.kp_cap;
         L.scale = o.sf[l];
         L.patch_size = (int)(31.0f * o.sf[l]);
         L.node_cap = L.nfeat + 4 * nIni + 24;
         node_cap_max = std::max(node_cap_max, L.node_cap);
-        vsp_cap_max = std::max(vsp_cap_max, 2 * (L.nfeat + 16));
+        vsp_cap_max = std::max(vsp_cap_max, std::max(2 * (L.nfeat + 16), 4 * nIni));      // (the first pass may note every one of its 4 * nIni children)
         // resize tables (cv::resize INTER_LINEAR 8u, SURVEY App.B H5)
         L.xtab_off = (int)tabs.size() / 4;
         L.xmax = L.w;

@@ -167,7 +167,8 @@ const float* orc_orb_scale_factors(const orc_orb* e);      /* nlevels */
 const float* orc_orb_inv_scale_factors(const orc_orb* e);
 const int*   orc_orb_features_per_level(const orc_orb* e);
 const int*   orc_orb_umax(const orc_orb* e);               /* 16 entries */
-int          orc_orb_max_keypoints(const orc_orb* e);      /* safe output capacity */
+int          orc_orb_max_keypoints(const orc_orb* e);      /* safe output capacity when no level has more than 2 octree roots */
+int          orc_orb_max_keypoints_for(const orc_orb* e, int W, int H);   /* for W x H images: per level max(N + 8, 4 * nIni) */
 
 /* ORBextractor::operator() (:1092-1176 with descriptors, :1178-1238 detect only).
  * kps: capacity cap; desc: cap*32 (may be NULL if !want_desc); oob: cap bytes or NULL, set to 1

@@ -149,6 +149,7 @@ def lib(fast=False):
     for f in ("orc_orb_features_per_level", "orc_orb_umax"):
         getattr(L, f).restype = C.POINTER(ci); getattr(L, f).argtypes = [vp]
     L.orc_orb_max_keypoints.restype = ci; L.orc_orb_max_keypoints.argtypes = [vp]
+    L.orc_orb_max_keypoints_for.restype = ci; L.orc_orb_max_keypoints_for.argtypes = [vp, ci, ci]
     L.orc_orb_extract.restype = ci
     L.orc_orb_extract.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, C.POINTER(ci)]
     L.orc_orb_level_size.restype = ci; L.orc_orb_level_size.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci)]
@@ -296,10 +297,11 @@ class OrbExtractor:
     def extract(self, img, lap=(0, 1000), want_desc=True):
         img = np.ascontiguousarray(img, np.uint8)
         H, W = img.shape
-        kps = np.zeros(self.cap, KP_DTYPE); desc = np.zeros((self.cap, 32), np.uint8)
-        oob = np.zeros(self.cap, np.uint8); n = C.c_int(0)
+        cap = max(self.cap, self.L.orc_orb_max_keypoints_for(self.h, W, H))      # (a wide frame's first pass may exceed the quota)
+        kps = np.zeros(cap, KP_DTYPE); desc = np.zeros((cap, 32), np.uint8)
+        oob = np.zeros(cap, np.uint8); n = C.c_int(0)
         mono = self.L.orc_orb_extract(self.h, _p(img), W, H, W, lap[0], lap[1], int(want_desc),
-                                      _p(kps), _p(desc), _p(oob), self.cap, C.byref(n))
+                                      _p(kps), _p(desc), _p(oob), cap, C.byref(n))
         if mono < 0:
             return mono, None, None, None
         return mono, kps[:n.value].copy(), (desc[:n.value].copy() if want_desc else None), oob[:n.value].copy()
@@ -385,11 +387,11 @@ def fast9_16(img, threshold):
     return out[:n].copy()
 
 
-def distribute_octree(cands, minX, maxX, minY, maxY, N):
+def distribute_octree(cands, minX, maxX, minY, maxY, N, fast=False):
     cands = np.ascontiguousarray(cands, KP_DTYPE)
-    cap = max(N + 64, 64)
+    cap = max(N + 64, 64, 4 * (maxX - minX) // max(maxY - minY, 1) + 8)      # (the first pass: up to 4 nodes per root)
     out = np.zeros(cap, KP_DTYPE)
-    n = lib().orc_distribute_octree(_p(cands), len(cands), minX, maxX, minY, maxY, N, _p(out), cap)
+    n = lib(fast).orc_distribute_octree(_p(cands), len(cands), minX, maxX, minY, maxY, N, _p(out), cap)
     assert 0 <= n <= cap, n
     return out[:n].copy()
 

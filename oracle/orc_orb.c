@@ -101,6 +101,29 @@ const int* orc_orb_features_per_level(const orc_orb* e) { return e->nfeat_level;
 const int* orc_orb_umax(const orc_orb* e) { return e->umax; }
 int orc_orb_max_keypoints(const orc_orb* e) { return e->p.nfeatures + 8 * e->p.nlevels; }
 
+/* The most keypoints one level can return.  DistributeOctTree's first pass over nIni roots yields up to 4 * nIni nodes before the
+ * list is compared with the quota N for the first time (:688), and the reference returns them all.  From then on a full pass is
+ * only run while size + 3 * nToExpand <= N, so the list stays <= N after it, and a cut-off division adds at most 3 nodes and the
+ * walk stops at the first size >= N (:749): <= N - 1 + 3 = N + 2.  Hence max(N + 2, 4 * nIni); N + 8 keeps the slack the extractor
+ * has always had. */
+static int level_capacity(int nfeat, int w, int h, int E)
+{
+    const int width = (w - E + 3) - (E - 3), height = (h - E + 3) - (E - 3);
+    int nIni = (width > 0 && height > 0) ? (int)roundf((float)width / (float)height) : 0;
+    if (nIni < 0) nIni = 0;
+    return nfeat + 8 > 4 * nIni ? nfeat + 8 : 4 * nIni;
+}
+
+int orc_orb_max_keypoints_for(const orc_orb* e, int W, int H)
+{
+    int total = 0;
+    for (int l = 0; l < e->p.nlevels; l++) {
+        const float scale = e->inv_sf[l];
+        total += level_capacity(e->nfeat_level[l], orc_cvround((double)((float)W * scale)), orc_cvround((double)((float)H * scale)), e->edge);
+    }
+    return total;
+}
+
 /* ---- OpenCV: borderInterpolate(REFLECT_101) -------------------------------------------------- */
 static inline int reflect101(int p, int len)
 {
@@ -635,7 +658,7 @@ static int compute_keypoints(orc_orb* e)
         }
         free(xys);
         e->cand[level] = cand; e->ncand[level] = nc;
-        int capk = e->nfeat_level[level] + 64;                     /* result never exceeds N+2 (N>=4) */
+        int capk = level_capacity(e->nfeat_level[level], cols, rows, E) + 56;   /* max(N + 2, 4 * nIni) and slack */
         orc_keypoint* kps = (orc_keypoint*)malloc(sizeof(orc_keypoint) * (capk > 0 ? capk : 1));
         int nk = 0;
         if (nc > 0) {

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from eorb_slam_amd import synth
+from fast_ref import fast_np as _fast_np
 
 
 def _noise(W, H, seed):
@@ -125,33 +126,7 @@ def test_pyramid_levels_chain_and_border(oracle, W, H):
 
 # ---------------------------------------------------------------------------------------------------
 # FAST
-_RING = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1),
-         (-2, 2), (-1, 3)]
-
-
-def _fast_np(img, threshold):
-    """cv::FAST(TYPE_9_16, nonmax suppression) by brute force: score = the largest t for which 9 contiguous ring pixels are all
-    brighter than centre + t or all darker than centre - t = max over the 16 arcs of min(d) - 1 and min(-d) - 1; corner iff
-    score >= threshold; kept iff strictly above its 8 neighbours' scores (non-corners count 0); 3-px margin."""
-    h, w = img.shape
-    s = img.astype(np.int64)
-    d = np.stack([s[3 + dy:h - 3 + dy, 3 + dx:w - 3 + dx] - s[3:h - 3, 3:w - 3] for dx, dy in _RING])      # ring - centre
-    best = np.full(d.shape[1:], -(1 << 20), np.int64)
-    for k in range(16):
-        arc = d[[(k + i) % 16 for i in range(9)]]
-        best = np.maximum(best, np.maximum(arc.min(axis=0) - 1, (-arc).min(axis=0) - 1))
-    score = np.zeros((h, w), np.int64)
-    score[3:h - 3, 3:w - 3] = np.where(best >= threshold, best, 0)
-    out = []
-    for y in range(3, h - 3):
-        for x in range(3, w - 3):
-            v = score[y, x]
-            if v >= max(threshold, 1):
-                nb = score[y - 1:y + 2, x - 1:x + 2].copy()
-                nb[1, 1] = -1
-                if v > nb.max():
-                    out.append((x, y, v))
-    return np.array(out, np.int32).reshape(-1, 3)
+# (the brute-force detector lives in tests/fast_ref.py: tests/octree_model.py runs it on every cell window)
 
 
 @pytest.mark.parametrize("name,threshold", [("noise", 10), ("noise", 40), ("texture", 10), ("texture", 40)])
