@@ -5,12 +5,11 @@
 #include <string>
 #include <vector>
 #include "../../include/eorb_fe.h"
+#include "ev_plan.h"
 
 namespace eorb {
 
 constexpr int kMaxLevels = 16;
-constexpr int kTile = 8;            // accumulation tile edge (one wavefront = 8x8 pixels)
-constexpr int kChunk = 4096;        // events per binning chunk (one wavefront bins one chunk)
 constexpr int kGridCols = 64;       // FRAME_GRID_COLS include/Frame.h:46
 constexpr int kGridRows = 48;       // FRAME_GRID_ROWS include/Frame.h:45
 
@@ -146,6 +145,7 @@ struct eorb_ctx {
     int sl_last_rank = -1, sl_last_chunk = 0;    // the scatter the last slot-form call ran (1 rank form, 0 ballot form), its chunk size
     int* rb_pinned = nullptr;                   // 64 ints of pinned host memory: the landing place of small read-backs (position count, slot info)
     long long sl_calls = 0;                      // test hook counter (eorb_debug_counter)
+    int accum_route = 0;                         // what served the last ev_accumulate_dev call (ev_plan.h: form | position set | sparse | widened)
     // float events in bulk: the distinct positions of a call are tabulated in a hash table (dd.lut, 8 bytes per row: the positions as a
     // 65 536-wide sensor) and the raw path runs on the tables of that per-call set (ev_accumulate_dev)
     eorb::PosTables dd;
@@ -236,11 +236,12 @@ struct ProfScope {
 #define EORB_LAUNCH_CHECK(c, what) do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return eorb::hip_check((c), e__, what); } while (0)
 
 // ev_accum.hip
+AccumKnobs accum_knobs(const eorb_ctx* c);      // the knobs of the accumulation forms: test hooks of the context over the environment (one table, there)
 int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
                       float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized,
                       uint32_t* d_minmax_enc, bool mm_preset = false);
 // mm_preset: the caller has initialised the running extremes (the per-slice calls; only the binning-free form takes its word for it)
-int ev_direct_slices_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* beg, const int64_t* end, int B, int W, int H,
+int ev_direct_slices_dev(eorb_ctx* c, const AccumShape& S, const void* d_events, int raw, const int64_t* beg, const int64_t* end, int B, int W, int H,
                          float sigma, int pol, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, bool mm_preset = false);
 int ev_undistort_dev(eorb_ctx* c, const eorb_raw_event* d_raw, size_t n, int W, int H, double tsFactor, eorb_event* d_out, uint32_t* d_blk);
 int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, uint64_t* d_lineend, eorb_raw_event* d_ev, uint8_t* d_status,
@@ -267,7 +268,7 @@ struct SlotDict {              // float events looked up in the context's positi
     const uint4* hash; uint32_t mask; uint32_t* rec; int* miss;
     int rec2;                  // the dictionary holds fewer than 65 535 positions: rec is written as 2-byte records (0xffff = none), else 4-byte
 };
-int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H, int TX, int TY,
+int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const AccumShape& S, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H,
                         float* d_f32, uint32_t* d_minmax_enc, const SlotDict* dict = nullptr);
 int ev_slots_trace_read(eorb_ctx* c, unsigned long long* out, long long max_records);
 // klt.hip

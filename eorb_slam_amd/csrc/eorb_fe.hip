@@ -406,6 +406,7 @@ long long eorb_debug_counter(eorb_ctx* c, const char* name)
 {
     if (!c || !name) return -1;
     if (!strcmp(name, "slot_calls")) return c->sl_calls;
+    if (!strcmp(name, "accum_route")) return c->accum_route;
     if (!strcmp(name, "slot_rank_ok")) return c->sl_rank_ok;
     if (!strcmp(name, "dict_hits")) return c->pd_hits;                    // bulk float calls served by the frozen position dictionary
     if (!strcmp(name, "dict_misses")) return c->pd_misses;                // ... that found a new position and tabulated afresh
@@ -576,7 +577,7 @@ static int ev_host_common(eorb_ctx* c, const eorb_event* ev, size_t n, int W, in
     Arena A(c);
     // (a live slice goes to the binning-free form, which reads every event once: in place, from the pinned staging buffer)
     static const int zc_env = [] { const char* e = getenv("EORB_SLICE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
-    A.host_inputs = zc_env != 0 && !mode_count && n > 0 && n <= 16384 && c->dbg_gather_form == 0;
+    A.host_inputs = zc_env != 0 && plan_host_events(accum_shape(W, H, sigma, mode_count, 1, (int64_t)n), AccumRequest{raw, pol, mode_count, 1}, accum_knobs(c));
     const size_t o_ev = A.in(raw ? (const void*)rawev : (const void*)packed.data(), sizeof(eorb_event16) * n);
     // outputs, contiguous: min/max (encoded | decoded) | u8 image | f32 image
     const size_t o_mm = A.reserve(64), o_u8 = A.reserve(npix), o_f32 = A.reserve(sizeof(float) * npix);
@@ -586,13 +587,12 @@ static int ev_host_common(eorb_ctx* c, const eorb_event* ev, size_t n, int W, in
     uint8_t* d_u8 = A.dev<uint8_t>(o_u8);
     float* d_f32 = A.dev<float>(o_f32);
     if (out_u8 && mode_count) EORB_HIP(c, hipMemsetAsync(d_u8, 0, npix, c->stream));     // count images stay empty when max == min
-    const long long slot_calls0 = c->sl_calls;
     rc = ev_accumulate_dev(c, A.in_ptr<void>(o_ev), raw, offs, 1, W, H, sigma, pol, mode_count, d_f32, d_u8, normalized, mm);
     A.inputs_done();
     if (rc) return rc;
     // the slot form reports an internal fault (its gather found no rows at LDS offset 0 and wrote no image) through the sticky status
     // word: this call's copy of it travels with the outputs (word 2 of the min/max block)
-    const bool slot_ran = c->sl_calls != slot_calls0;
+    const bool slot_ran = (c->accum_route & kRouteFormMask) == kFormSlots;
     if (slot_ran) EORB_HIP(c, hipMemcpyAsync(mm + 2, c->status.p, 4, hipMemcpyDeviceToDevice, c->stream));
     const size_t end = out_f32 ? o_f32 + sizeof(float) * npix : (out_u8 ? o_u8 + npix : o_mm + 64);
     const char* h;
@@ -1027,7 +1027,7 @@ int eorb_ev_slice_extract(eorb_ctx* c, const eorb_event* ev, const eorb_raw_even
     // a live slice (the binning-free form reads every event once, in ev_pre_kernel): the events stay in pinned host memory and the
     // extremes are initialised by that kernel -- no copy in front of the first launch
     static const int zc_env = [] { const char* e = getenv("EORB_SLICE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
-    const bool zc = zc_env != 0 && n > 0 && n <= 16384 && c->dbg_gather_form == 0;
+    const bool zc = zc_env != 0 && plan_host_events(accum_shape(W, H, sigma, 0, 1, (int64_t)n), AccumRequest{is_raw, 0, 0, 1}, accum_knobs(c));
     A.host_inputs = zc;
     const size_t o_mm = zc ? A.reserve(sizeof(kMinMaxPreset)) : A.in(kMinMaxPreset, sizeof(kMinMaxPreset)), o_f32 = A.reserve(sizeof(float) * npix);
     const size_t o_u8 = A.reserve(npix);
@@ -1178,7 +1178,7 @@ int eorb_ev_mc_contest(eorb_ctx* c, const eorb_event* ev, size_t n, const eorb_c
     if ((long)n <= direct_max) {
         // every reconstruction of the window in ONE launch of the binning-free kernel (float events, normalized = false).  (Beyond
         // the single-slice limit of 16 384 events too: five binned passes of 60 us each are what the alternative costs here.)
-        if ((rc = ev_direct_slices_dev(c, d_ev, 0, beg, end, nimg, W, H, sigma, 0, d_f32, nullptr, 0, d_mm))) return rc;
+        if ((rc = ev_direct_slices_dev(c, accum_shape(W, H, sigma, 0, nimg, (int64_t)n), d_ev, 0, beg, end, nimg, W, H, sigma, 0, d_f32, nullptr, 0, d_mm))) return rc;
     } else {
         const int64_t dd_saved = c->dbg_dd_min; c->dbg_dd_min = 0;     // (warped events: no two share a position)
         for (int j = 0; j < nimg && !rc; j++) {

@@ -251,7 +251,6 @@ __global__ __launch_bounds__(64) void ev_scatter_kernel(const eorb_event16* __re
 //      counters are private to the wave: no barrier inside this phase.
 //   D  slot p of the sorted order -> (event, tile) -> the entry is rebuilt from the event (L2) and stored at the tile's run base +
 //      (p - loff[tile]): consecutive threads write consecutive entries of a run.
-constexpr int kScatWaves = 8;
 template <int R>
 __global__ __launch_bounds__(64 * kScatWaves) void ev_scatter2_kernel(const eorb_event16* __restrict__ ev, const ChunkDesc* __restrict__ chunks,
                                                           BinParams P, int chunk_cap, const int64_t* __restrict__ slice_ebase,
@@ -1124,7 +1123,6 @@ __global__ __launch_bounds__(64 * kSparseWaves) void ev_gather_sparse_kernel(con
 // and a descriptor upload there; instead every tile's wave reads ALL events of its slice (690 waves x 2 000 events: nothing),
 // keeps those whose stamp reaches the tile -- in event order, ballot-compacted into a small LDS list -- and adds them as K2s does.
 // Same entries in the same order as the binned lists, hence the same image.
-constexpr int kDirectSlices = 8;
 struct DirectSlices { int64_t beg[kDirectSlices], end[kDirectSlices]; int64_t tab_base; };      // the slices' event ranges (they may overlap: the contest's later-half histogram)
 constexpr int kDirectList = 2048;                   // entries of the LDS list (flushed when the next batch of loads might not fit)
 #ifndef EORB_DIRECT_G
@@ -1909,7 +1907,6 @@ int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, uint64_t* 
 // (ev_src_info_kernel / ev_stamp_kernel evaluate the same arithmetic K2's value waves do); the events become 4-byte records naming
 // their slot, and the raw path (K2r: table reads instead of 49 f64 expf per event) does the rest.  Falls back to K2 when the
 // positions do not repeat (motion-compensated events).
-constexpr int kDdLog = 20;                                         // table slots = 2^20; at most half may fill
 constexpr uint64_t kDdEmpty = ~0ull;                               // (NaN, NaN): never a position that is looked up (NaN events are dropped)
 __device__ __forceinline__ uint32_t dd_hash(uint64_t k)
 {
@@ -1978,15 +1975,15 @@ static GatherParams ev_gather_params(int W, int H, int h, int TX, int TY, int NT
 // raw events: the tables derived from the positions of the set T (integer position of every sensor pixel, its stamp, the slot tables);
 // rebuilt only when (image size, sigma, mode) differ from T's key.  T is the maps, or (hashed) the per-call set of the float bulk path,
 // whose key the caller resets for every call and whose src_info / slot assignment it may have launched ahead.
-static int ev_raw_tables(eorb_ctx* c, PosTables& T, int W, int H, int h, float sigma, int mode_count, GatherParams& G, bool hashed = false, bool want_slots = false)
+static int ev_raw_tables(eorb_ctx* c, PosTables& T, const AccumShape& S, int W, int H, float sigma, int mode_count, GatherParams& G, bool hashed = false, bool want_slots = false)
 {
     int rc;
+    const int h = S.h;
     const int nsrc = T.w * T.h;
     const int SW = 2 * h + 1, SWP = (SW + 3) & ~3;
     G.stamp_stride = SW * SWP; G.stamp_colstride = SWP;
     if (T.key_W != W || T.key_H != H || T.key_sigma != sigma || T.key_mode != mode_count) {
         ProfScope ps(c, "ev_stamp_tables");
-        const int TXs = (W + kTile - 1) / kTile, TYs = (H + kTile - 1) / kTile;
         if (!T.src_info_done) {
             if ((rc = ensure(c, T.src_info, sizeof(uint32_t) * (size_t)nsrc))) return rc;
             ev_src_info_kernel<<<(nsrc + 255) / 256, 256, 0, c->stream>>>((const float2*)T.lut.p, nsrc, W, H, T.check, mode_count,
@@ -2001,7 +1998,7 @@ static int ev_raw_tables(eorb_ctx* c, PosTables& T, int W, int H, int h, float s
         if (!mode_count && hashed && want_slots) {
             // the per-call positions of float events (2^20 table rows, most of them empty): the slot form computes its rows from the
             // positions, so the 235 MB stamp table is only built when that form cannot serve the call
-            if ((rc = ev_slots_prepare(c, T, W, H, h, TXs, TYs, nullptr, G.stamp_stride, G.stamp_colstride, G.two_sig2, G.norm))) return rc;
+            if ((rc = ev_slots_prepare(c, T, W, H, h, S.TX, S.TY, nullptr, G.stamp_stride, G.stamp_colstride, G.two_sig2, G.norm))) return rc;
             if (T.sl_ok) need_stamps = false;
         }
         if (need_stamps) {
@@ -2012,12 +2009,89 @@ static int ev_raw_tables(eorb_ctx* c, PosTables& T, int W, int H, int h, float s
             ev_stamp_kernel<<<2048, 256, 0, c->stream>>>((const float2*)T.lut.p, (const uint32_t*)T.src_info.p, nsrc, G,
                                                          (float*)T.stamps.p + kStampPad);
             EORB_LAUNCH_CHECK(c, "ev_stamp_kernel");
-            if (!hashed && (rc = ev_slots_prepare(c, T, W, H, h, TXs, TYs, (const float*)T.stamps.p + kStampPad, G.stamp_stride, G.stamp_colstride, G.two_sig2, G.norm))) return rc;
+            if (!hashed && (rc = ev_slots_prepare(c, T, W, H, h, S.TX, S.TY, (const float*)T.stamps.p + kStampPad, G.stamp_stride, G.stamp_colstride, G.two_sig2, G.norm))) return rc;
         }
         T.key_W = W; T.key_H = H; T.key_sigma = sigma; T.key_mode = mode_count;
     }
     G.stamps = (const float*)T.stamps.p + kStampPad;     // K2r reads up to 7 floats before / behind a column
     return EORB_OK;
+}
+
+// ---- the knobs ---------------------------------------------------------------------------------------------------------------------
+// Every switch of the accumulation forms, from its two sources: a test hook of the context (eorb_debug_option) and the environment
+// (read once per process; meant for A/B runs of one build).  Which wins, per knob:
+//
+//   knob             option (context field)             environment            rule
+//   gather_form      "gather_form"                      --                     option
+//   dd_min           "dedupe_min_events"                --                     option
+//   pd               "position_dict"                    --                     option
+//   scatter          --                                 EORB_SCATTER (2)       environment; 1: the pipeline's first scatter form
+//   gather_threads   --                                 EORB_GATHER_THREADS    environment if 192..1024 and a multiple of 64, else the build's
+//   gather_nc        --                                 EORB_GATHER_NC (0)     environment; 2 / 4, anything else: by the launch's size
+//   slot_chunk       --                                 EORB_SLOT_CHUNK (0)    environment if 256 / 1024 / 2048 / 4096, else by the slices' length
+//   slot_waves       --                                 EORB_SLOT_WAVES (0)    environment if 1..16
+//   slot_rounds      --                                 EORB_SLOT_ROUNDS (0)   environment if >= 1, else 4
+//   slot_count_lds   --                                 EORB_SLOT_COUNT_LDS (1) environment
+//   slot_transcode   --                                 EORB_SLOT_TRANSCODE (1) environment
+//   slot_rank        "slot_rank" (-1)                   EORB_SLOT_RANK (1)     option if >= 0, else environment; non-zero: allowed
+//   slot_hot_min     "slot_hot_min" (-1)                EORB_SLOT_HOT_MIN (-1) option if >= 0, else environment; < 0: by the batch's size
+//   slot_hot_cap     "slot_hot_cap" (0)                 --                     option; <= 0: kHotCap
+//   slot_hot_waves   "slot_hot_waves" (0)               EORB_SLOT_HOT_WAVES (0) option if > 0, else environment if > 0, else 8 per CU
+//   slot_prerank     "slot_prerank" (-1)                EORB_SLOT_PRERANK (1)  option if >= 0, else environment
+//   slot_halves      "slot_halves" (-1)                 EORB_SLOT_HALVES (-1)  option if >= 0, else environment; > 0: two halves
+AccumKnobs accum_knobs(const eorb_ctx* c)
+{
+    static const AccumKnobs env = [] {
+        auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
+        AccumKnobs k;
+        k.scatter = (int)num("EORB_SCATTER", 2);
+        const int gt = (int)num("EORB_GATHER_THREADS", kGatherThreads);
+        k.gather_threads = (gt >= 192 && gt <= 1024 && gt % 64 == 0) ? gt : kGatherThreads;
+        k.gather_nc = (int)num("EORB_GATHER_NC", 0);
+        const int sc = (int)num("EORB_SLOT_CHUNK", 0);
+        k.slot_chunk = (sc == 256 || sc == 1024 || sc == 2048 || sc == 4096) ? sc : 0;
+        k.slot_waves = (int)num("EORB_SLOT_WAVES", 0);
+        k.slot_rounds = (int)num("EORB_SLOT_ROUNDS", 0);
+        k.slot_count_lds = (int)num("EORB_SLOT_COUNT_LDS", 1);
+        k.slot_transcode = (int)num("EORB_SLOT_TRANSCODE", 1);
+        k.slot_rank = num("EORB_SLOT_RANK", 1) != 0;
+        k.slot_hot_min = num("EORB_SLOT_HOT_MIN", -1);
+        k.slot_hot_waves = std::max((int)num("EORB_SLOT_HOT_WAVES", 0), 0);
+        k.slot_prerank = (int)num("EORB_SLOT_PRERANK", 1);
+        k.slot_halves = (int)num("EORB_SLOT_HALVES", -1);
+        return k;
+    }();
+    AccumKnobs k = env;
+    k.gather_form = c->dbg_gather_form; k.dd_min = c->dbg_dd_min; k.pd = c->dbg_pd;
+    if (c->dbg_slot_rank >= 0) k.slot_rank = c->dbg_slot_rank != 0;
+    if (c->dbg_slot_hot_min >= 0) k.slot_hot_min = c->dbg_slot_hot_min;
+    k.slot_hot_cap = c->dbg_slot_hot_cap;
+    if (c->dbg_slot_hot_waves > 0) k.slot_hot_waves = c->dbg_slot_hot_waves;
+    if (c->dbg_slot_prerank >= 0) k.slot_prerank = c->dbg_slot_prerank;
+    if (c->dbg_slot_halves >= 0) k.slot_halves = c->dbg_slot_halves;
+    return k;
+}
+
+// ---- the launches every form shares ----------------------------------------------------------------------------------------------
+static void ev_minmax_init(eorb_ctx* c, uint32_t* d_minmax_enc, int B)
+{
+    ProfScope ps(c, "ev_minmax_init");
+    ev_minmax_init_kernel<<<(B + 63) / 64, 64, 0, c->stream>>>(d_minmax_enc, B);
+}
+static int ev_normalize(eorb_ctx* c, const float* d_f32, const uint32_t* d_minmax_enc, uint8_t* d_u8, int npix, int B, int mode_count)
+{
+    ProfScope ps(c, "ev_normalize");
+    dim3 grid((npix + 255) / 256 > 64 ? 64 : (npix + 255) / 256, B);
+    ev_normalize_kernel<<<grid, 256, 0, c->stream>>>(d_f32, d_minmax_enc, d_u8, npix, mode_count);
+    EORB_LAUNCH_CHECK(c, "ev_normalize_kernel");
+    return EORB_OK;
+}
+// the slices' offsets counted from the call's first event
+static std::vector<int64_t> rebased(const int64_t* h_offsets, int B)
+{
+    std::vector<int64_t> off(B + 1);
+    for (int b = 0; b <= B; b++) off[b] = h_offsets[b] - h_offsets[0];
+    return off;
 }
 
 // eorb_raw_event4 (x | p << 15 | y << 16: the 4-byte wire record of a sensor event for the images, which never read the time
@@ -2034,16 +2108,12 @@ __global__ void ev_unpack4_kernel(const uint32_t* __restrict__ in, int64_t n, eo
 // K2d on its own: up to 8 slices given by their event ranges [beg, end) inside one array (the ranges may overlap), float or raw events,
 // Gaussian stamp.  ev_accumulate_dev takes this path for the live per-slice calls; the motion-compensation contest
 // (eorb_ev_mc_contest) hands it the reconstructions of one window in one launch.
-int ev_direct_slices_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* beg, const int64_t* end, int B, int W, int H,
+int ev_direct_slices_dev(eorb_ctx* c, const AccumShape& A, const void* d_events, int raw, const int64_t* beg, const int64_t* end, int B, int W, int H,
                          float sigma, int pol, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, bool mm_preset)
 {
     if (B < 1 || B > kDirectSlices) return set_err(c, EORB_E_ARG, "direct slices: %d slices", B);
-    const int h = (int)ceil((double)sigma * 3.0);
+    const int h = A.h, TX = A.TX, TY = A.TY, NT = A.NT, dup = A.dup;
     if (h > 8) return set_err(c, EORB_E_CONFIG, "ev_accumulate: sigma %.3f gives half window %d > 8", sigma, h);
-    const int R = (2 * h <= kTile) ? ((h == 0) ? 1 : 2) : 3;
-    const int TX = (W + kTile - 1) / kTile, TY = (H + kTile - 1) / kTile, NT = TX * TY;
-    int nbits = 1; while ((1 << nbits) < NT) nbits++;
-    const int dup = R * R;
     DirectSlices S{};
     for (int b = 0; b < B; b++) {
         if (end[b] < beg[b]) return set_err(c, EORB_E_ARG, "ev_accumulate: offsets not monotone");
@@ -2052,7 +2122,7 @@ int ev_direct_slices_dev(eorb_ctx* c, const void* d_events, int raw, const int64
     }
     int rc;
     GatherParams G = ev_gather_params(W, H, h, TX, TY, NT, 0, B * NT, sigma);
-    if (raw && (rc = ev_raw_tables(c, c->maps, W, H, h, sigma, 0, G))) return rc;
+    if (raw && (rc = ev_raw_tables(c, c->maps, A, W, H, sigma, 0, G))) return rc;
     // every event of the call resolved once into its list entry (ev_pre_kernel), over the span of the slices
     int64_t lo = S.beg[0], hi = S.end[0];
     for (int b = 1; b < B; b++) { lo = std::min(lo, S.beg[b]); hi = std::max(hi, S.end[b]); }
@@ -2082,22 +2152,14 @@ int ev_direct_slices_dev(eorb_ctx* c, const void* d_events, int raw, const int64
         ev_pre_kernel<false><<<(int)((span + 255) / 256), 256, 0, c->stream>>>(d_first, (int)span, W, H, c->maps.w, c->maps.h, (const uint32_t*)c->maps.src_info.p, 0u, d_pre, mm_in_pre ? d_minmax_enc : nullptr, B);
         EORB_LAUNCH_CHECK(c, "ev_pre_kernel");
     }
-    if (!mm_preset && !mm_in_pre) {
-        ProfScope ps(c, "ev_minmax_init");
-        ev_minmax_init_kernel<<<(B + 63) / 64, 64, 0, c->stream>>>(d_minmax_enc, B);
-    }
+    if (!mm_preset && !mm_in_pre) ev_minmax_init(c, d_minmax_enc, B);
     {
         ProfScope ps(c, "ev_gather");
         if (pol) ev_gather_direct_kernel<true><<<B * NT, 64, 0, c->stream>>>(d_pre, S, G, d_f32, d_minmax_enc);
         else ev_gather_direct_kernel<false><<<B * NT, 64, 0, c->stream>>>(d_pre, S, G, d_f32, d_minmax_enc);
         EORB_LAUNCH_CHECK(c, "ev_gather_direct_kernel");
     }
-    if (normalized && d_u8) {
-        ProfScope ps(c, "ev_normalize");
-        dim3 grid((W * H + 255) / 256 > 64 ? 64 : (W * H + 255) / 256, B);
-        ev_normalize_kernel<<<grid, 256, 0, c->stream>>>(d_f32, d_minmax_enc, d_u8, W * H, 0);
-        EORB_LAUNCH_CHECK(c, "ev_normalize_kernel");
-    }
+    if (normalized && d_u8) return ev_normalize(c, d_f32, d_minmax_enc, d_u8, W * H, B, 0);
     return EORB_OK;
 }
 
@@ -2145,7 +2207,7 @@ __global__ void pd_build_kernel(const unsigned long long* __restrict__ tab, int 
 }
 
 // the call's positions (c->dd.lut, valid right after a per-call tabulation) -> the frozen dictionary and its set of tables c->pd
-static int pd_freeze(eorb_ctx* c, int W, int H, int h, float sigma, int TX, int TY, int npos)
+static int pd_freeze(eorb_ctx* c, const AccumShape& S, int W, int H, float sigma, int npos)
 {
     c->pd_valid = 0;
     if (npos < 1 || npos > 65535) return EORB_OK;                      // (dense ids travel as hashed records below 65 536 rows: the LDS count pass)
@@ -2162,35 +2224,26 @@ static int pd_freeze(eorb_ctx* c, int W, int H, int h, float sigma, int TX, int 
     if ((rc = ensure(c, T.src_info, sizeof(uint32_t) * (size_t)npos))) return rc;
     ev_src_info_kernel<<<(npos + 255) / 256, 256, 0, c->stream>>>((const float2*)T.lut.p, npos, W, H, 0, 0, (uint32_t*)T.src_info.p);
     const float sig2 = sigma * sigma;
-    if ((rc = ev_slots_prepare(c, T, W, H, h, TX, TY, nullptr, 0, 0, 2.0f * sig2, 2.0f * (float)3.1415926535897932384626433832795 * sig2))) return rc;
+    if ((rc = ev_slots_prepare(c, T, W, H, S.h, S.TX, S.TY, nullptr, 0, 0, 2.0f * sig2, 2.0f * (float)3.1415926535897932384626433832795 * sig2))) return rc;
     // the count pass keeps the dense ids' tile ranges and its per-wavefront counters in LDS (ev_slots.hip, sl_count_lds_kernel)
-    const int NTp = (TX * TY + 1) & ~1;
-    const bool lds_ok = TX <= 127 && TY <= 127 && 4 * (((size_t)npos + 2) / 2) + (size_t)16 * NTp * 2 <= 159 * 1024;
+    const bool lds_ok = S.TX <= 127 && S.TY <= 127 && 4 * (((size_t)npos + 2) / 2) + (size_t)16 * S.NTp * 2 <= 159 * 1024;
     if (T.sl_ok && lds_ok) { c->pd_valid = 1; c->pd_K = npos; c->pd_W = W; c->pd_H = H; c->pd_sigma = sigma; }
     return EORB_OK;
 }
 
 // a call served by the dictionary; *missed = 1 when a position was not in it (the images are then incomplete: the caller redoes the call)
-static int pd_accumulate(eorb_ctx* c, const eorb_event16* d_src, const int64_t* off, int B, int W, int H, int TX, int TY, float sigma,
-                         float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, int64_t n0, int* missed)
+static int pd_accumulate(eorb_ctx* c, const AccumShape& S, const eorb_event16* d_src, const int64_t* off, int B, int W, int H,
+                         float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, int* missed)
 {
     int rc;
-    if ((rc = ensure(c, c->dd_ev, 4 * (size_t)std::max<int64_t>(n0, 1)))) return rc;
+    if ((rc = ensure(c, c->dd_ev, 4 * (size_t)std::max<int64_t>(S.nev, 1)))) return rc;
     EORB_HIP(c, hipMemsetAsync(c->pd_cnt.p, 0, 64, c->stream));
-    {
-        ProfScope ps(c, "ev_minmax_init");
-        ev_minmax_init_kernel<<<(B + 63) / 64, 64, 0, c->stream>>>(d_minmax_enc, B);
-    }
+    ev_minmax_init(c, d_minmax_enc, B);
     SlotDict D{(const uint4*)c->pd_hash.p, (1u << kPdLog) - 1u, (uint32_t*)c->dd_ev.p, (int*)c->pd_cnt.p, c->pd_K < 65535 ? 1 : 0};
-    rc = ev_slots_accumulate(c, c->pd, d_src, 16, off, B, W, H, TX, TY, d_f32, d_minmax_enc, &D);      // (pd_valid: c->pd is pd_K x 1, its slot tables ok)
+    rc = ev_slots_accumulate(c, c->pd, S, d_src, 16, off, B, W, H, d_f32, d_minmax_enc, &D);      // (pd_valid: c->pd is pd_K x 1, its slot tables ok)
     if (rc < 0) return rc;
-    if (rc > 0) { *missed = 1; return EORB_OK; }                        // the batch's shape does not fit the slot form: the per-call path decides
-    if (normalized && d_u8) {
-        ProfScope ps(c, "ev_normalize");
-        dim3 grid((W * H + 255) / 256 > 64 ? 64 : (W * H + 255) / 256, B);
-        ev_normalize_kernel<<<grid, 256, 0, c->stream>>>(d_f32, d_minmax_enc, d_u8, W * H, 0);
-        EORB_LAUNCH_CHECK(c, "ev_normalize_kernel");
-    }
+    if (rc > 0) { *missed = 1; return EORB_OK; }                        // kSlotDeclined: the batch's shape does not fit the slot form, the per-call path decides
+    if (normalized && d_u8 && (rc = ev_normalize(c, d_f32, d_minmax_enc, d_u8, W * H, B, 0))) return rc;
     // the call's one wait: did every position have its entry?
     int* rb = readback_buf(c);
     if (!rb) return set_err(c, EORB_E_HIP, "pinned alloc failed");
@@ -2200,9 +2253,92 @@ static int pd_accumulate(eorb_ctx* c, const eorb_event16* d_src, const int64_t* 
     return EORB_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------
-static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
-                                float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc);
+// ---- the dispatcher --------------------------------------------------------------------------------------------------------------
+// Which form serves a call is decided by the rules of ev_plan.h, asked here in one order: float events in bulk (the dictionary, else
+// the per-call tabulation), the binning-free form, then the forms that bin (the slot form, else the list pipeline).  A call leaves its
+// first-choice form only where a comment below says "declined"; what served it is recorded in c->accum_route.
+static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, int set, const AccumShape& S, AccumRequest Q, const AccumKnobs& K, const void* d_events,
+                                const int64_t* h_offsets, int W, int H, float sigma, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc);
+
+// the binning-free form on the slices of a call
+static int ev_direct(eorb_ctx* c, const AccumShape& S, const AccumRequest& Q, const void* d_events, const int64_t* h_offsets, int W, int H, float sigma,
+                     float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, bool mm_preset)
+{
+    int64_t beg[kDirectSlices], end[kDirectSlices];
+    for (int b = 0; b < Q.B; b++) {
+        if (h_offsets[b + 1] < h_offsets[b]) return set_err(c, EORB_E_ARG, "ev_accumulate: offsets not monotone");
+        beg[b] = h_offsets[b]; end[b] = h_offsets[b + 1];
+    }
+    return ev_direct_slices_dev(c, S, d_events, Q.raw, beg, end, Q.B, W, H, sigma, Q.pol, d_f32, d_u8, normalized, d_minmax_enc, mm_preset);
+}
+
+// Float events in bulk (plan_bulk_eligible): the dictionary of an earlier call, else this call's positions tabulated (see
+// dd_insert_kernel) and the forms that bin on the per-call set.  *served = false: nothing of the call is done, the caller goes on with
+// the float events as they are.
+static int ev_bulk_float(eorb_ctx* c, const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K, const void* d_events, const int64_t* h_offsets,
+                         int W, int H, float sigma, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, bool* served)
+{
+    const int B = Q.B;
+    const bool slot_shape = plan_slot_shaped(S, Q, K);
+    const size_t cap = (size_t)1 << kDdLog;
+    const int max_ids = (int)(cap / 2);
+    const eorb_event16* src = (const eorb_event16*)d_events + h_offsets[0];
+    const std::vector<int64_t> off = rebased(h_offsets, B);
+    int rc;
+    if (plan_dict_usable(S, Q, K, DictState{c->pd_valid, c->pd_W, c->pd_H, c->pd_cooldown, c->pd_sigma}, W, H, sigma)) {
+        // the positions of an earlier call, frozen: one pass over the events (see pd_accumulate)
+        int missed = 0;
+        if ((rc = pd_accumulate(c, S, src, off.data(), B, W, H, d_f32, d_u8, normalized, d_minmax_enc, &missed))) return rc;
+        if (!missed) { c->pd_hits++; c->accum_route = kFormSlots | kSetDict; *served = true; return EORB_OK; }
+        // declined: a dictionary miss (new positions, or a batch the slot form does not take) -- tabulate this call's afresh, freeze those
+        c->pd_misses++; c->pd_valid = 0;
+    }
+    if (c->pd_cooldown > 0) c->pd_cooldown--;
+    if (!plan_bulk_fits(S, K)) return EORB_OK;                          // (the list pipeline could not read row numbers as records)
+    PosTables& T = c->dd;
+    if ((rc = ensure(c, T.lut, 8 * cap)) || (rc = ensure(c, c->dd_cnt, 64)) || (rc = ensure(c, c->dd_ev, 4 * (size_t)S.nev))) return rc;
+    T.w = 65536; T.h = (int)(cap / 65536); T.check = 0;                 // the hash table as a sensor's maps: row = sensor pixel
+    int hc[2] = {0, 0};
+    {
+        ProfScope ps(c, "ev_dedupe");
+        // the table of an earlier call is kept while the positions seen so far can still become a dictionary (a sparse call does
+        // not see every sensor pixel: the table accumulates them over the calls); otherwise it starts empty
+        const bool keep = c->dd_keep && slot_shape && K.pd != 0;
+        if (!keep) {
+            EORB_HIP(c, hipMemsetAsync(T.lut.p, 0xff, 8 * cap, c->stream));
+            EORB_HIP(c, hipMemsetAsync(c->dd_cnt.p, 0, 64, c->stream));
+        } else EORB_HIP(c, hipMemsetAsync((int*)c->dd_cnt.p + 1, 0, 4, c->stream));      // (the crowding flag is per call)
+        c->dd_keep = 0;
+        dd_insert_kernel<<<4096, 256, 0, c->stream>>>(src, S.nev, (unsigned long long*)T.lut.p, (int*)c->dd_cnt.p, (uint32_t*)c->dd_ev.p);
+        EORB_LAUNCH_CHECK(c, "dd_insert_kernel");
+        int* rb = readback_buf(c);
+        if (!rb) return set_err(c, EORB_E_HIP, "pinned alloc failed");
+        EORB_HIP(c, hipMemcpyAsync(rb, c->dd_cnt.p, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+        // in front of the wait: the integer positions of the table rows and the slot assignment (what the slot form's host
+        // side needs read back), so that the call waits for the stream once
+        if (plan_tables_ahead(S, Q, K)) {
+            if ((rc = ensure(c, T.src_info, sizeof(uint32_t) * cap))) return rc;
+            ev_src_info_kernel<<<(int)((cap + 255) / 256), 256, 0, c->stream>>>((const float2*)T.lut.p, (int)cap, W, H, 0, Q.mode_count, (uint32_t*)T.src_info.p);
+            if ((rc = ev_slots_prepare_launch(c, T, W, H, S.h, S.TX, S.TY))) return rc;
+            T.src_info_done = 1;
+        }
+        EORB_HIP(c, hipStreamSynchronize(c->stream));
+        hc[0] = rb[0]; hc[1] = rb[1];
+    }
+    // declined: a crowded or over-full position table (the positions do not repeat) -- on with the float events
+    if (hc[1] || hc[0] > max_ids) { T.src_info_done = 0; T.sl_launched = 0; return EORB_OK; }
+    // the forms that bin, on the per-call set (records: row numbers of its table), whose tables are this call's: nothing built is current
+    T.key_W = T.key_H = T.key_mode = -1; T.key_sigma = -1.f;
+    *served = true;
+    rc = ev_accumulate_tables(c, T, kSetPerCall, S, AccumRequest{2, Q.pol, Q.mode_count, B}, K, c->dd_ev.p, off.data(), W, H, sigma, d_f32, d_u8, normalized, d_minmax_enc);
+    // these positions serve the next calls (a call that just missed the dictionary with MANY new positions -- events that are not
+    // map-valued -- does not try again for a while)
+    if (!rc && slot_shape && K.pd != 0) {
+        if (hc[0] <= 65535) { const int rc3 = pd_freeze(c, S, W, H, sigma, hc[0]); if (rc3) return rc3; c->dd_keep = 1; }
+        else c->pd_cooldown = 16;
+    }
+    return rc;
+}
 
 int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
                       float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized,
@@ -2210,165 +2346,76 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
 {
     if (B <= 0 || W <= 0 || H <= 0) return set_err(c, EORB_E_ARG, "ev_accumulate: bad size");
     if (raw && !c->maps.w) return set_err(c, EORB_E_NOTCONF, "ev_accumulate: raw events need eorb_set_undistort_maps first");
-    const int h = mode_count ? 0 : (int)ceil((double)sigma * 3.0);     // lenHalfWin :222
-    if (h > 8) return set_err(c, EORB_E_CONFIG, "ev_accumulate: sigma %.3f gives half window %d > 8", sigma, h);
+    const AccumShape S = accum_shape(W, H, sigma, mode_count, B, h_offsets[B] - h_offsets[0]);
+    if (S.h > 8) return set_err(c, EORB_E_CONFIG, "ev_accumulate: sigma %.3f gives half window %d > 8", sigma, S.h);
     // exp(-d^2 / 2 sigma^2) underflows to 0 inside the window below sigma ~ 0.197 (d^2 up to 8 at h = 1): with polarity the
     // reference's running maximum then depends on visits that add nothing (see the gather kernels)
     if (pol && !mode_count && sigma < 0.2f) return set_err(c, EORB_E_CONFIG, "ev_accumulate: polarity images need sigma >= 0.2 (got %.3f)", sigma);
-    const int R = (2 * h <= kTile) ? ((h == 0) ? 1 : 2) : 3;            // max tiles an event spans per axis
-    const int TX = (W + kTile - 1) / kTile, TY = (H + kTile - 1) / kTile, NT = TX * TY;
     if (raw == 4 && (int64_t)c->maps.w * c->maps.h > 65535) return set_err(c, EORB_E_ARG, "ev_accumulate: 2-byte records need a sensor of at most 65 535 pixels (the maps are %dx%d)", c->maps.w, c->maps.h);
-    if (!raw && !mode_count && c->dbg_gather_form != 1 && h_offsets[B] - h_offsets[0] >= c->dbg_dd_min && c->dbg_dd_min > 0) {
-        // float events in bulk: tabulate their distinct positions, continue on the raw path (see dd_insert_kernel)
-        const int64_t n0 = h_offsets[B] - h_offsets[0];
-        const int64_t ps0 = n0 / B;
-        const int chunk0 = ps0 >= (int64_t)1 << 17 ? 2048 : (ps0 >= (int64_t)1 << 14 ? 1024 : 256);
-        const int NTp0 = (NT + 1) & ~1;
-        static const int scat_env = [] { const char* e = getenv("EORB_SCATTER"); return e ? atoi(e) : 2; }();
-        // the hashed records are only read by the count kernel and the second form of the scatter
-        const bool fits = scat_env != 1 && TX < 256 && TY < 256 &&
-            (((size_t)chunk0 * 8 + (size_t)chunk0 * 2 + (size_t)chunk0 * R * R * 2 + (size_t)kScatWaves * NTp0 * 2 + (size_t)(NTp0 + 2) * 2 + (size_t)NT * 4 + 15) & ~(size_t)15) <= 64 * 1024;
-        const size_t cap = (size_t)1 << kDdLog;
-        const int max_ids = (int)(cap / 2);
-        int rc;
-        const bool slot_shape = !pol && !mode_count && (c->dbg_gather_form == 0 || c->dbg_gather_form == 4) && h >= 1 && h <= 4;
-        if (fits && slot_shape && c->pd_valid && c->pd_W == W && c->pd_H == H && c->pd_sigma == sigma && c->pd_cooldown == 0 && c->dbg_pd != 0) {
-            // the positions of an earlier call, frozen: one pass over the events (see pd_accumulate)
-            std::vector<int64_t> off(B + 1);
-            for (int b = 0; b <= B; b++) off[b] = h_offsets[b] - h_offsets[0];
-            int missed = 0;
-            if ((rc = pd_accumulate(c, (const eorb_event16*)d_events + h_offsets[0], off.data(), B, W, H, TX, TY, sigma, d_f32, d_u8, normalized, d_minmax_enc, n0, &missed))) return rc;
-            if (!missed) { c->pd_hits++; return EORB_OK; }
-            c->pd_misses++; c->pd_valid = 0;                            // new positions: tabulate this call's afresh (below), freeze those
-        }
-        if (c->pd_cooldown > 0) c->pd_cooldown--;
-        if (fits) {
-            PosTables& T = c->dd;
-            if ((rc = ensure(c, T.lut, 8 * cap)) || (rc = ensure(c, c->dd_cnt, 64)) || (rc = ensure(c, c->dd_ev, 4 * (size_t)n0))) return rc;
-            T.w = 65536; T.h = (int)(cap / 65536); T.check = 0;          // the hash table as a sensor's maps: row = sensor pixel
-            const eorb_event16* src = (const eorb_event16*)d_events + h_offsets[0];
-            int hc[2] = {0, 0};
-            {
-                ProfScope ps(c, "ev_dedupe");
-                // the table of an earlier call is kept while the positions seen so far can still become a dictionary (a sparse call does
-                // not see every sensor pixel: the table accumulates them over the calls); otherwise it starts empty
-                const bool keep = c->dd_keep && slot_shape && c->dbg_pd != 0;
-                if (!keep) {
-                    EORB_HIP(c, hipMemsetAsync(T.lut.p, 0xff, 8 * cap, c->stream));
-                    EORB_HIP(c, hipMemsetAsync(c->dd_cnt.p, 0, 64, c->stream));
-                } else EORB_HIP(c, hipMemsetAsync((int*)c->dd_cnt.p + 1, 0, 4, c->stream));      // (the crowding flag is per call)
-                c->dd_keep = 0;
-                dd_insert_kernel<<<4096, 256, 0, c->stream>>>(src, n0, (unsigned long long*)T.lut.p, (int*)c->dd_cnt.p, (uint32_t*)c->dd_ev.p);
-                EORB_LAUNCH_CHECK(c, "dd_insert_kernel");
-                int* rb = readback_buf(c);
-                if (!rb) return set_err(c, EORB_E_HIP, "pinned alloc failed");
-                EORB_HIP(c, hipMemcpyAsync(rb, c->dd_cnt.p, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-                // in front of the wait: the integer positions of the table rows and the slot assignment (what the slot form's host
-                // side needs read back), so that the call waits for the stream once
-                if (!pol && !mode_count && (c->dbg_gather_form == 0 || c->dbg_gather_form == 2 || c->dbg_gather_form == 4) && h >= 1 && h <= 4) {
-                    if ((rc = ensure(c, T.src_info, sizeof(uint32_t) * cap))) return rc;
-                    ev_src_info_kernel<<<(int)((cap + 255) / 256), 256, 0, c->stream>>>((const float2*)T.lut.p, (int)cap, W, H, 0, mode_count, (uint32_t*)T.src_info.p);
-                    if ((rc = ev_slots_prepare_launch(c, T, W, H, h, TX, TY))) return rc;
-                    T.src_info_done = 1;
-                }
-                EORB_HIP(c, hipStreamSynchronize(c->stream));
-                hc[0] = rb[0]; hc[1] = rb[1];
-            }
-            if (!(!hc[1] && hc[0] <= max_ids)) { T.src_info_done = 0; T.sl_launched = 0; }
-            if (!hc[1] && hc[0] <= max_ids) {
-                // the raw path on the per-call set (records: row numbers of its table), whose tables are this call's: nothing built is current
-                T.key_W = T.key_H = T.key_mode = -1; T.key_sigma = -1.f;
-                std::vector<int64_t> off(B + 1);
-                for (int b = 0; b <= B; b++) off[b] = h_offsets[b] - h_offsets[0];
-                rc = ev_accumulate_tables(c, T, c->dd_ev.p, 2, off.data(), B, W, H, sigma, pol, mode_count, d_f32, d_u8, normalized, d_minmax_enc);
-                // these positions serve the next calls (a call that just missed the dictionary with MANY new positions -- events that are not
-                // map-valued -- does not try again for a while)
-                if (!rc && slot_shape && c->dbg_pd != 0) {
-                    if (hc[0] <= 65535) { const int rc3 = pd_freeze(c, W, H, h, sigma, TX, TY, hc[0]); if (rc3) return rc3; c->dd_keep = 1; }
-                    else c->pd_cooldown = 16;
-                }
-                return rc;
-            }
-        }
+    const AccumKnobs K = accum_knobs(c);
+    const AccumRequest Q{raw, pol, mode_count, B};
+    if (plan_bulk_eligible(S, Q, K)) {
+        bool served = false;
+        const int rc = ev_bulk_float(c, S, Q, K, d_events, h_offsets, W, H, sigma, d_f32, d_u8, normalized, d_minmax_enc, &served);
+        if (rc || served) return rc;
     }
-    {
-        // one or a few small slices of raw events (the live per-slice call): no binning at all, K2d
-        const int64_t nev0 = h_offsets[B] - h_offsets[0];
-        if (!(raw >= 2 && raw <= 4) && !mode_count && B <= 4 && (c->dbg_gather_form == 3 || (c->dbg_gather_form == 0 && nev0 <= 16384))) {
-            int64_t beg[kDirectSlices], end[kDirectSlices];
-            for (int b = 0; b < B; b++) {
-                if (h_offsets[b + 1] < h_offsets[b]) return set_err(c, EORB_E_ARG, "ev_accumulate: offsets not monotone");
-                beg[b] = h_offsets[b]; end[b] = h_offsets[b + 1];
-            }
-            return ev_direct_slices_dev(c, d_events, raw, beg, end, B, W, H, sigma, pol, d_f32, d_u8, normalized, d_minmax_enc, mm_preset);
-        }
+    const int set = raw ? kSetMaps : kSetNone;
+    if (plan_direct(S, Q, K)) {
+        // one or a few small slices (the live per-slice call): no binning at all, K2d
+        c->accum_route = kFormDirect | set;
+        return ev_direct(c, S, Q, d_events, h_offsets, W, H, sigma, d_f32, d_u8, normalized, d_minmax_enc, mm_preset);
     }
-    return ev_accumulate_tables(c, c->maps, d_events, raw, h_offsets, B, W, H, sigma, pol, mode_count, d_f32, d_u8, normalized, d_minmax_enc);
+    return ev_accumulate_tables(c, c->maps, set, S, Q, K, d_events, h_offsets, W, H, sigma, d_f32, d_u8, normalized, d_minmax_enc);
 }
 
-// The forms that bin: the slot form, else the batch pipeline (count, scan, scatter, gather).  Raw events (raw 1, 3, 4: 16-, 4-, 2-byte
-// records) are looked up in the tables of the set T; raw 2: 4-byte records that are row numbers of T, the per-call set.  The arguments
-// have passed ev_accumulate_dev's checks.
-static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
-                                float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc)
+// The forms that bin: the slot form; else, short records widened, the binning-free form or the list pipeline (count, scan, scatter,
+// gather).  Sensor records (raw 1, 3, 4: 16-, 4-, 2-byte) are looked up in the tables of the set T; raw 2: 4-byte records that are row
+// numbers of T, the per-call set; raw 0: float events, T unused.  The arguments have passed ev_accumulate_dev's checks.
+static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, int set, const AccumShape& S, AccumRequest Q, const AccumKnobs& K, const void* d_events,
+                                const int64_t* h_offsets, int W, int H, float sigma, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc)
 {
-    const eorb_event16* d_ev = (const eorb_event16*)d_events;          // eorb_raw_event has the same 16-byte stride
-    const int h = mode_count ? 0 : (int)ceil((double)sigma * 3.0);
-    const int R = (2 * h <= kTile) ? ((h == 0) ? 1 : 2) : 3;            // max tiles an event spans per axis
-    const int TX = (W + kTile - 1) / kTile, TY = (H + kTile - 1) / kTile, NT = TX * TY;
-    int nbits = 1; while ((1 << nbits) < NT) nbits++;
-    const int dup = R * R;
-    const bool hashed = raw == 2;                        // 4-byte hashed records (the float bulk path)
-    const bool packed4 = raw == 3;                       // 4-byte sensor records (eorb_raw_event4)
-    const bool packed2 = raw == 4;                       // 2-byte sensor records (eorb_raw_event2: y * LW + x)
+    const int B = Q.B, pol = Q.pol, mode_count = Q.mode_count;
+    const int NT = S.NT, dup = S.dup;
+    const bool hashed = Q.raw == 2;                      // 4-byte hashed records (the float bulk path)
+    int rc, wide = 0;
     // dense batches of raw events without polarity: two-byte slot lists, a tile position's rows in LDS (ev_slots.hip)
-    if (raw && !mode_count && !pol && (c->dbg_gather_form == 0 || c->dbg_gather_form == 4 || (hashed && c->dbg_gather_form == 2))) {
-        const int64_t nev0 = h_offsets[B] - h_offsets[0];
-        const bool sparse0 = nev0 * dup < (int64_t)B * NT * 64;          // (fewer than one 64-entry batch per tile on average: K2s)
-        if (c->dbg_gather_form == 4 || !sparse0) {
-            int rc;
-            GatherParams G = ev_gather_params(W, H, h, TX, TY, NT, mode_count, B * NT, sigma);
-            if ((rc = ev_raw_tables(c, T, W, H, h, sigma, mode_count, G, hashed, true))) return rc;
-            if (T.sl_ok) {
-                {
-                    ProfScope ps(c, "ev_minmax_init");
-                    ev_minmax_init_kernel<<<(B + 63) / 64, 64, 0, c->stream>>>(d_minmax_enc, B);
-                }
-                // > 0: the batch's shape does not fit the slot form (tile grids beyond the scatter's LDS, e.g. VGA-class sensors; more than
-                // 2 048 slices) and nothing was launched: the batch pipeline below serves it
-                if ((rc = ev_slots_accumulate(c, T, d_events, hashed ? -4 : (packed4 ? 4 : (packed2 ? 2 : 16)), h_offsets, B, W, H, TX, TY, d_f32, d_minmax_enc)) < 0) return rc;
-                if (rc == 0) {
-                    if (normalized && d_u8) {
-                        ProfScope ps(c, "ev_normalize");
-                        dim3 grid((W * H + 255) / 256 > 64 ? 64 : (W * H + 255) / 256, B);
-                        ev_normalize_kernel<<<grid, 256, 0, c->stream>>>(d_f32, d_minmax_enc, d_u8, W * H, mode_count);
-                        EORB_LAUNCH_CHECK(c, "ev_normalize_kernel");
-                    }
-                    return EORB_OK;
-                }
+    if (plan_slot_eligible(S, Q, K)) {
+        GatherParams G = ev_gather_params(W, H, S.h, S.TX, S.TY, NT, mode_count, B * NT, sigma);
+        if ((rc = ev_raw_tables(c, T, S, W, H, sigma, mode_count, G, hashed, true))) return rc;
+        if (T.sl_ok) {
+            ev_minmax_init(c, d_minmax_enc, B);
+            if ((rc = ev_slots_accumulate(c, T, S, d_events, hashed ? -4 : (Q.raw == 3 ? 4 : (Q.raw == 4 ? 2 : 16)), h_offsets, B, W, H, d_f32, d_minmax_enc)) < 0) return rc;
+            if (rc == 0) {
+                c->accum_route = kFormSlots | set;
+                if (normalized && d_u8) return ev_normalize(c, d_f32, d_minmax_enc, d_u8, W * H, B, mode_count);
+                return EORB_OK;
             }
+            // declined: kSlotDeclined -- the batch's shape does not fit the slot form (plan_slot_shape: tile grids beyond the scatter's
+            // LDS, e.g. VGA-class sensors; more than 2 048 slices) and nothing was launched
+        }
+        // declined: T.sl_ok == 0 -- a tile of these positions holds more than 254 slots
+    }
+    std::vector<int64_t> off;
+    if (Q.raw == 3 || Q.raw == 4) {
+        // the other forms read 16-byte records: widen the batch's events once and go on with those (sensor records: T is the maps)
+        if ((rc = ensure(c, c->ev16, sizeof(eorb_raw_event) * (size_t)std::max<int64_t>(S.nev, 1)))) return rc;
+        const int grid = (int)std::min<int64_t>((S.nev + 255) / 256, 65536);
+        if (S.nev > 0 && Q.raw == 4) ev_unpack2_kernel<<<grid, 256, 0, c->stream>>>((const uint16_t*)d_events + h_offsets[0], S.nev, T.w, (eorb_raw_event*)c->ev16.p);
+        else if (S.nev > 0) ev_unpack4_kernel<<<grid, 256, 0, c->stream>>>((const uint32_t*)d_events + h_offsets[0], S.nev, (eorb_raw_event*)c->ev16.p);
+        EORB_LAUNCH_CHECK(c, "ev_unpack4_kernel");
+        off = rebased(h_offsets, B);
+        d_events = c->ev16.p; h_offsets = off.data(); Q.raw = 1; wide = kRouteWidened;
+        if (plan_direct(S, Q, K)) {
+            c->accum_route = kFormDirect | set | wide;
+            return ev_direct(c, S, Q, d_events, h_offsets, W, H, sigma, d_f32, d_u8, normalized, d_minmax_enc, false);
         }
     }
-    if (packed4 || packed2) {
-        // the other forms read 16-byte records: widen the batch's events once and go on with those (sensor records: T is the maps)
-        const int64_t n0 = h_offsets[B] - h_offsets[0];
-        int rc;
-        if ((rc = ensure(c, c->ev16, sizeof(eorb_raw_event) * (size_t)std::max<int64_t>(n0, 1)))) return rc;
-        if (n0 > 0 && packed2) ev_unpack2_kernel<<<(int)std::min<int64_t>((n0 + 255) / 256, 65536), 256, 0, c->stream>>>((const uint16_t*)d_events + h_offsets[0], n0, T.w, (eorb_raw_event*)c->ev16.p);
-        else if (n0 > 0) ev_unpack4_kernel<<<(int)std::min<int64_t>((n0 + 255) / 256, 65536), 256, 0, c->stream>>>((const uint32_t*)d_events + h_offsets[0], n0, (eorb_raw_event*)c->ev16.p);
-        EORB_LAUNCH_CHECK(c, "ev_unpack4_kernel");
-        std::vector<int64_t> off(B + 1);
-        for (int b = 0; b <= B; b++) off[b] = h_offsets[b] - h_offsets[0];
-        return ev_accumulate_dev(c, c->ev16.p, 1, off.data(), B, W, H, sigma, pol, mode_count, d_f32, d_u8, normalized, d_minmax_enc);
-    }
-    // chunk list (host) -> device.  A chunk is binned by ONE wavefront, 64 events at a time: large inputs take kChunk events per
-    // chunk (fewer segment tables), small ones shorter chunks so that a single 2 000-event slice is not one 32-iteration serial
-    // loop (72 us on MI355X) but eight waves side by side
-    const int64_t nev_all = h_offsets[B] - h_offsets[0];
-    const int64_t per_slice = nev_all / B;
-    static const int scat_form = [] { const char* e = getenv("EORB_SCATTER"); return e ? atoi(e) : 2; }();      // 1: first form (A/B runs)
-    const int chunk_big = scat_form == 1 ? kChunk : 2048;
-    const int chunk = per_slice >= (int64_t)1 << 17 ? chunk_big : (per_slice >= (int64_t)1 << 14 ? 1024 : 256);
+    // ---- the list pipeline ----
+    const int raw = Q.raw;
+    const eorb_event16* d_ev = (const eorb_event16*)d_events;          // eorb_raw_event has the same 16-byte stride
+    // chunk list (host) -> device.  A chunk is binned by ONE workgroup: large inputs take long chunks (fewer segment tables), small
+    // ones shorter chunks so that a single 2 000-event slice is not one serial loop (72 us on MI355X) but eight waves side by side
+    const int chunk = plan_pipeline_chunk(S, K);
     std::vector<ChunkDesc> cds;
     std::vector<int> slice_c0(B + 1);
     std::vector<int64_t> slice_eb(B);
@@ -2385,18 +2432,16 @@ static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events,
     }
     slice_c0[B] = (int)cds.size();
     const int nchunks = (int)cds.size();
-    const int64_t nev = h_offsets[B] - h_offsets[0];
     const size_t cd_bytes = sizeof(ChunkDesc) * (size_t)std::max(nchunks, 1);
     const size_t sc_bytes = (sizeof(int) * (size_t)(B + 1) + 7) & ~(size_t)7;
     const size_t eb_bytes = sizeof(int64_t) * (size_t)B;
     const int nb = B * NT;
-    int rc;
     if ((rc = ensure(c, c->chunks, cd_bytes + sc_bytes + eb_bytes))) return rc;
     // segcnt u16 [nchunks][NT] | segbase u32 [nchunks][NT]
     const size_t cnt_bytes = (sizeof(uint16_t) * (size_t)std::max(nchunks, 1) * NT + 15) & ~(size_t)15;
     if ((rc = ensure(c, c->segoff, cnt_bytes + sizeof(uint32_t) * (size_t)std::max(nchunks, 1) * NT))) return rc;
     const int esz = pol ? 4 : 2;
-    if ((rc = ensure(c, c->entries, sizeof(float) * esz * (size_t)std::max<int64_t>(nev, 1) * dup + 64))) return rc;   // + slack: K2r reads entry 0 of an empty list
+    if ((rc = ensure(c, c->entries, sizeof(float) * esz * (size_t)std::max<int64_t>(S.nev, 1) * dup + 64))) return rc;   // + slack: K2r reads entry 0 of an empty list
     // tile_cnt | tile_base | order
     if ((rc = ensure(c, c->tile_order, sizeof(uint32_t) * 3 * (size_t)nb))) return rc;
     char* hp = (char*)pinned(c, cd_bytes + sc_bytes + eb_bytes);
@@ -2415,16 +2460,15 @@ static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events,
     uint32_t* d_tile_base = d_tile_cnt + nb;
     int32_t* d_order = (int32_t*)(d_tile_cnt + 2 * (size_t)nb);
 
-    GatherParams G = ev_gather_params(W, H, h, TX, TY, NT, mode_count, nb, sigma);
-    if (raw && (rc = ev_raw_tables(c, T, W, H, h, sigma, mode_count, G, hashed))) return rc;
+    GatherParams G = ev_gather_params(W, H, S.h, S.TX, S.TY, NT, mode_count, nb, sigma);
+    if (raw && (rc = ev_raw_tables(c, T, S, W, H, sigma, mode_count, G, hashed))) return rc;
+    ev_minmax_init(c, d_minmax_enc, B);
+    // nearly empty tiles of raw events with a Gaussian stamp: K2s, a wave per tile
+    const GatherPlan gp = plan_gather(S, Q, K);
+    const bool sparse = gp.kind == kGatherSparse;
+    c->accum_route = kFormLists | set | (sparse ? kRouteSparse : 0) | wide;
     {
-        ProfScope ps(c, "ev_minmax_init");
-        ev_minmax_init_kernel<<<(B + 63) / 64, 64, 0, c->stream>>>(d_minmax_enc, B);
-    }
-    // nearly empty tiles (fewer than one 64-entry batch per tile on average) of raw events with a Gaussian stamp: K2s, a wave per tile
-    const bool sparse = raw && !mode_count && (c->dbg_gather_form == 2 || (c->dbg_gather_form == 0 && nev * dup < (int64_t)nb * 64));
-    {
-        BinParams P{W, H, h, TX, TY, NT, nbits, dup, mode_count, pol, raw ? 1 : 0, T.w, T.h, (const uint32_t*)T.src_info.p,
+        BinParams P{W, H, S.h, S.TX, S.TY, NT, S.nbits, dup, mode_count, pol, raw ? 1 : 0, T.w, T.h, (const uint32_t*)T.src_info.p,
                     hashed ? 1 : 0};
         const size_t lds = sizeof(uint32_t) * (size_t)NT;
         if (lds > 64 * 1024) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: %d tiles exceed the binning LDS", NT);
@@ -2433,17 +2477,15 @@ static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events,
         if (nchunks) ev_count_kernel<<<nchunks, 256, lds, c->stream>>>(d_ev, d_chunks, P, d_segcnt);
         ev_scan_kernel<<<B, 1024, 0, c->stream>>>(d_slice_c0, d_segcnt, NT, d_segbase, d_tile_cnt, d_tile_base);
         if (nchunks) {
-            const int NTp = (NT + 1) & ~1;
-            const size_t lds2 = ((size_t)chunk * 8 + (size_t)chunk * 2 + (size_t)chunk * R * R * 2 + (size_t)kScatWaves * NTp * 2 + (size_t)(NTp + 2) * 2 + (size_t)NT * 4 + 15) & ~(size_t)15;
-            // (float events with polarity carry 16-byte entries: first form)
-            const bool form2 = scat_form != 1 && !(pol && !raw) && lds2 <= 64 * 1024 && TX < 256 && TY < 256;
+            const size_t lds2 = plan_scatter2_lds(S, chunk);
+            const bool form2 = plan_scatter2(S, Q, K);
             if (hashed && !form2) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: hashed records need the second form of the scatter");
 #define LAUNCH_BIN(RR, PP) do { if (form2) ev_scatter2_kernel<RR><<<nchunks, 64 * kScatWaves, lds2, c->stream>>>(d_ev, d_chunks, P, chunk, d_slice_eb, d_segbase, d_tile_base, (uint2*)en); \
                                 else ev_scatter_kernel<RR, PP><<<nchunks, 64, lds, c->stream>>>(d_ev, d_chunks, P, d_slice_eb, d_segbase, d_tile_base, en); } while (0)
-            const bool wide = pol && !raw;                       // raw entries keep the polarity in the sensor-pixel word
-            if (R == 1) { if (wide) LAUNCH_BIN(1, true); else LAUNCH_BIN(1, false); }
-            else if (R == 2) { if (wide) LAUNCH_BIN(2, true); else LAUNCH_BIN(2, false); }
-            else { if (wide) LAUNCH_BIN(3, true); else LAUNCH_BIN(3, false); }
+            const bool wide_entries = pol && !raw;               // raw entries keep the polarity in the sensor-pixel word
+            if (S.R == 1) { if (wide_entries) LAUNCH_BIN(1, true); else LAUNCH_BIN(1, false); }
+            else if (S.R == 2) { if (wide_entries) LAUNCH_BIN(2, true); else LAUNCH_BIN(2, false); }
+            else { if (wide_entries) LAUNCH_BIN(3, true); else LAUNCH_BIN(3, false); }
 #undef LAUNCH_BIN
         }
         if (!sparse) {
@@ -2456,30 +2498,18 @@ static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events,
     }
     {
         ProfScope ps(c, "ev_gather");
-        static const int gthreads = [] { const char* e = getenv("EORB_GATHER_THREADS"); int v = e ? atoi(e) : kGatherThreads;
-                                         return (v >= 192 && v <= 1024 && v % 64 == 0) ? v : kGatherThreads; }();
         const int mode = mode_count ? 2 : ((G.div_is_pow2 && G.fast_norm) ? 1 : 0);
         const float* en = (const float*)c->entries.p;
-#define LAUNCH_G(PP, MM, RR) ev_gather_kernel<PP, MM, RR><<<nb, gthreads, 0, c->stream>>>(d_slice_eb, d_order, G, d_tile_cnt, d_tile_base, en, d_f32, d_minmax_enc)
+        const uint2* en2 = (const uint2*)c->entries.p;
+#define LAUNCH_G(PP, MM, RR) ev_gather_kernel<PP, MM, RR><<<nb, gp.threads, 0, c->stream>>>(d_slice_eb, d_order, G, d_tile_cnt, d_tile_base, en, d_f32, d_minmax_enc)
         if (sparse) {
-            const uint2* en2 = (const uint2*)c->entries.p;
-            // large launches: 8 consecutive work items per wave (a wave per item leaves the launch bound by workgroup dispatch)
-            const int per_wave = nb >= 65536 ? 16 : 1;
-            const int grid = (nb + kSparseWaves * per_wave - 1) / (kSparseWaves * per_wave);
-            if (pol) ev_gather_sparse_kernel<true><<<grid, 64 * kSparseWaves, 0, c->stream>>>(d_slice_eb, G, per_wave, d_tile_cnt, d_tile_base, en2, d_f32, d_minmax_enc);
-            else ev_gather_sparse_kernel<false><<<grid, 64 * kSparseWaves, 0, c->stream>>>(d_slice_eb, G, per_wave, d_tile_cnt, d_tile_base, en2, d_f32, d_minmax_enc);
-        } else if (raw && mode != 2) {
-            // the add wave + four value waves with two tile columns each (shortest chain per batch), or -- when the launch has
-            // enough tiles to keep every SIMD busy anyway -- two value waves with four columns each (the rectangle arithmetic is
-            // done once per four columns: fewest instructions per batch)
-            static const int nc_env = [] { const char* e = getenv("EORB_GATHER_NC"); return e ? atoi(e) : 0; }();
-            const int NC = nc_env == 2 || nc_env == 4 ? nc_env : (nb >= 32768 ? 4 : 2);
-            const int rthreads = 64 * (1 + 8 / NC);
-            const uint2* en2 = (const uint2*)c->entries.p;
-            const int ngrid = nb;
-#define LAUNCH_R(PP, CC) ev_gather_raw_kernel<PP, CC><<<ngrid, rthreads, 0, c->stream>>>(d_slice_eb, d_order, G, d_tile_cnt, d_tile_base, en2, d_f32, d_minmax_enc)
-            if (pol) { if (NC == 4) LAUNCH_R(true, 4); else LAUNCH_R(true, 2); }
-            else { if (NC == 4) LAUNCH_R(false, 4); else LAUNCH_R(false, 2); }
+            const int grid = (nb + kSparseWaves * gp.per_wave - 1) / (kSparseWaves * gp.per_wave);
+            if (pol) ev_gather_sparse_kernel<true><<<grid, 64 * kSparseWaves, 0, c->stream>>>(d_slice_eb, G, gp.per_wave, d_tile_cnt, d_tile_base, en2, d_f32, d_minmax_enc);
+            else ev_gather_sparse_kernel<false><<<grid, 64 * kSparseWaves, 0, c->stream>>>(d_slice_eb, G, gp.per_wave, d_tile_cnt, d_tile_base, en2, d_f32, d_minmax_enc);
+        } else if (gp.kind == kGatherRawRows) {
+#define LAUNCH_R(PP, CC) ev_gather_raw_kernel<PP, CC><<<nb, gp.threads, 0, c->stream>>>(d_slice_eb, d_order, G, d_tile_cnt, d_tile_base, en2, d_f32, d_minmax_enc)
+            if (pol) { if (gp.NC == 4) LAUNCH_R(true, 4); else LAUNCH_R(true, 2); }
+            else { if (gp.NC == 4) LAUNCH_R(false, 4); else LAUNCH_R(false, 2); }
 #undef LAUNCH_R
         } else if (raw) {                                  // count image of raw events
             if (pol) LAUNCH_G(true, 2, true); else LAUNCH_G(false, 2, true);
@@ -2488,12 +2518,7 @@ static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, const void* d_events,
 #undef LAUNCH_G
         EORB_LAUNCH_CHECK(c, "ev_gather_kernel");
     }
-    if (normalized && d_u8) {
-        ProfScope ps(c, "ev_normalize");
-        dim3 grid((W * H + 255) / 256 > 64 ? 64 : (W * H + 255) / 256, B);
-        ev_normalize_kernel<<<grid, 256, 0, c->stream>>>(d_f32, d_minmax_enc, d_u8, W * H, mode_count);
-        EORB_LAUNCH_CHECK(c, "ev_normalize_kernel");
-    }
+    if (normalized && d_u8) return ev_normalize(c, d_f32, d_minmax_enc, d_u8, W * H, B, mode_count);
     return EORB_OK;
 }
 

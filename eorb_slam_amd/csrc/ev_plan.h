@@ -1,0 +1,238 @@
+// ev_plan.h -- which form an event-accumulation call takes: the call's derived geometry (AccumShape), the knobs that can steer it
+// (AccumKnobs, filled by accum_knobs() in ev_accum.hip) and the rules, each a named function with one home.  Host-only: no HIP
+// header, no eorb_ctx, so that a plain C++ compiler can build a caller of the rules (tests/host/accum_plan_check.cpp).
+//
+// The dispatcher (ev_accum.hip: ev_accumulate_dev, ev_accumulate_tables) asks the rules in this order:
+//   plan_bulk_eligible -> plan_bulk_fits -> plan_dict_usable -> (plan_slot_shaped, plan_tables_ahead while tabulating)
+//   -> plan_direct -> plan_slot_eligible -> plan_slot_shape -> (widen short records) -> plan_direct again -> plan_pipeline_chunk,
+//   plan_scatter2, plan_sparse_gather, plan_gather.
+// plan_first_route() is the same sequence without a device: the form a call takes when nothing declines at run time.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace eorb {
+
+constexpr int kTile = 8;            // accumulation tile edge (one wavefront = 8x8 pixels)
+constexpr int kChunk = 4096;        // events per binning chunk of the first scatter form (one wavefront bins one chunk)
+constexpr int kScatWaves = 8;       // wavefronts of ev_scatter2_kernel
+constexpr int kSlotScatWaves = 8;   // wavefronts of sl_scatter_kernel and of the 2 048-event rank scatter
+constexpr int kDdLog = 20;          // float events in bulk: the per-call position table has 2^20 rows; at most half may fill
+constexpr int kDirectSlices = 8;    // slices one launch of the binning-free form takes (the dispatcher sends it at most 4)
+constexpr int64_t kDirectMaxEvents = 16384;      // a call of up to this many events takes the binning-free form by its shape
+
+// ---- the shape: everything derived from (W, H, sigma, mode_count, B, nev), made once per call ----------------------------------
+struct AccumShape {
+    int h;                  // half window of the stamp, lenHalfWin (0 for count images)
+    int R, dup;             // tiles an event spans per axis at most; list entries an event yields at most (R * R)
+    int TX, TY, NT, NTp;    // the tile grid; NT rounded up to even (16-bit counter rows are cleared as 32-bit words)
+    int nbits;              // bits of a tile number
+    int64_t nev, per_slice; // events of the call; per slice on average (what the chunk sizes go by)
+};
+inline AccumShape accum_shape(int W, int H, float sigma, int mode_count, int B, int64_t nev)
+{
+    AccumShape S;
+    S.h = mode_count ? 0 : (int)ceil((double)sigma * 3.0);              // lenHalfWin :222
+    S.R = (2 * S.h <= kTile) ? ((S.h == 0) ? 1 : 2) : 3;
+    S.dup = S.R * S.R;
+    S.TX = (W + kTile - 1) / kTile; S.TY = (H + kTile - 1) / kTile; S.NT = S.TX * S.TY; S.NTp = (S.NT + 1) & ~1;
+    S.nbits = 1; while ((1 << S.nbits) < S.NT) S.nbits++;
+    S.nev = nev; S.per_slice = B > 0 ? nev / B : 0;
+    return S;
+}
+
+// what the caller asks for.  raw: 0 float events, 1 16-byte sensor records, 2 row numbers of the per-call position table (the float
+// bulk path's own records), 3 eorb_raw_event4, 4 eorb_raw_event2
+struct AccumRequest { int raw, pol, mode_count, B; };
+
+// ---- the knobs (see the table at accum_knobs, ev_accum.hip, for where each comes from) -------------------------------------------
+struct AccumKnobs {
+    int gather_form = 0;                     // 0 by the rules below, 1 list pipeline / dense gather, 2 sparse gather, 3 binning-free, 4 slot lists
+    int64_t dd_min = (int64_t)1 << 20;       // float events from which a call's positions are tabulated (<= 0: never)
+    int pd = 1;                              // 0: no position dictionary
+    int scatter = 2;                         // 1: the list pipeline's first scatter form only
+    int gather_threads = 512, gather_nc = 0; // ev_gather_kernel's workgroup; tile columns per value wave of ev_gather_raw_kernel (0: by size)
+    int slot_chunk = 0, slot_waves = 0, slot_rounds = 0, slot_count_lds = 1, slot_transcode = 1;
+    bool slot_rank = true;                   // the rank scatter may run (if the device check passed too)
+    long long slot_hot_min = -1;             // -1: by the batch's size
+    int slot_hot_cap = 0, slot_hot_waves = 0, slot_prerank = 1, slot_halves = -1;
+};
+
+// ---- the route a call took (eorb_debug_counter "accum_route"; 0: no call yet) ----------------------------------------------------
+enum { kFormDirect = 1, kFormSlots = 2, kFormLists = 3, kRouteFormMask = 3 };
+enum { kSetNone = 0 << 2, kSetMaps = 1 << 2, kSetPerCall = 2 << 2, kSetDict = 3 << 2 };
+enum { kRouteSparse = 1 << 4, kRouteWidened = 1 << 5 };
+
+// ---- the rules -------------------------------------------------------------------------------------------------------------------
+// Float events in bulk: their distinct positions are tabulated and the call goes on with row numbers as records (raw 2).
+// gather_form 1 asks for the list pipeline on the events as they are; every other forced form is still tabulated first -- so float
+// events with gather_form 3 and dd_min lowered do NOT take the binning-free form.  (Why 3 is not excluded like 1: unknown.)
+inline bool plan_bulk_eligible(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    return !Q.raw && !Q.mode_count && K.gather_form != 1 && S.nev >= K.dd_min && K.dd_min > 0;
+}
+
+// events per chunk of the list pipeline (a chunk is binned by one workgroup; short slices take short chunks so that a single
+// 2 000-event slice is eight waves side by side, not one serial loop)
+inline int plan_pipeline_chunk(const AccumShape& S, const AccumKnobs& K)
+{
+    return S.per_slice >= (int64_t)1 << 17 ? (K.scatter == 1 ? kChunk : 2048) : (S.per_slice >= (int64_t)1 << 14 ? 1024 : 256);
+}
+
+// dynamic LDS of ev_scatter2_kernel for chunks of `chunk` events: records, tile numbers, entry indices, per-wave counts, offsets, bases
+inline size_t plan_scatter2_lds(const AccumShape& S, int chunk)
+{
+    return ((size_t)chunk * 8 + (size_t)chunk * 2 + (size_t)chunk * S.dup * 2 + (size_t)kScatWaves * S.NTp * 2 + (size_t)(S.NTp + 2) * 2 + (size_t)S.NT * 4 + 15) & ~(size_t)15;
+}
+
+// The pipeline's second scatter form (the only one that reads row-number records).  wide: float events with polarity carry 16-byte
+// entries, which only the first form writes.
+inline bool plan_scatter2(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    return K.scatter != 1 && !(Q.pol && !Q.raw) && plan_scatter2_lds(S, plan_pipeline_chunk(S, K)) <= 64 * 1024 && S.TX < 256 && S.TY < 256;
+}
+
+// May the bulk path hand row-number records on?  = plan_scatter2 for those records (raw 2, so the polarity clause is moot), asked
+// before anything is tabulated.
+inline bool plan_bulk_fits(const AccumShape& S, const AccumKnobs& K)
+{
+    return plan_scatter2(S, AccumRequest{2, 0, 0, 1}, K);
+}
+
+// Could the slot form serve these float events (by request, not by load)?  Governs freezing the positions into the dictionary and
+// keeping the position table across calls.  gather_form 2 is NOT slot-shaped although plan_slot_eligible admits it for row-number
+// records: a forced sparse call tabulates, may still run the slot form, but never freezes.  (On purpose or not: unknown.)
+inline bool plan_slot_shaped(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    return !Q.pol && !Q.mode_count && (K.gather_form == 0 || K.gather_form == 4) && S.h >= 1 && S.h <= 4;
+}
+
+// The per-call set's integer positions and slot assignment are launched ahead of the tabulation's wait (one wait per call).  Wider
+// than plan_slot_shaped by gather_form 2, matching plan_slot_eligible for row-number records.
+inline bool plan_tables_ahead(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    return !Q.pol && !Q.mode_count && (K.gather_form == 0 || K.gather_form == 2 || K.gather_form == 4) && S.h >= 1 && S.h <= 4;
+}
+
+// the frozen dictionary's key, as the context holds it
+struct DictState { int valid, W, H, cooldown; float sigma; };
+// a bulk call is served by the dictionary of an earlier call (no sparse test: one pass over the events beats the list pipeline's two)
+inline bool plan_dict_usable(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K, const DictState& D, int W, int H, float sigma)
+{
+    return plan_bulk_fits(S, K) && plan_slot_shaped(S, Q, K) && D.valid && D.W == W && D.H == H && D.sigma == sigma && D.cooldown == 0 && K.pd != 0;
+}
+
+// The binning-free form: one or a few small slices of float or 16-byte sensor events with a Gaussian stamp.  Short records are
+// widened first (the dispatcher asks again with raw 1).
+inline bool plan_direct(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    return !(Q.raw >= 2 && Q.raw <= 4) && !Q.mode_count && Q.B <= 4 && (K.gather_form == 3 || (K.gather_form == 0 && S.nev <= kDirectMaxEvents));
+}
+
+// A host-buffer entry point leaves a slice's events in pinned host memory when the binning-free form, which reads every event once,
+// is what plan_direct gives by the call's shape (a forced form is a test's business: those upload).  Float events that
+// plan_bulk_eligible sends to the tabulation first (dd_min lowered to the slice's size) stay in host memory as well, although the
+// tabulation and the forms behind it read them several times: kept as it was, slower but correct.
+inline bool plan_host_events(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    return S.nev > 0 && K.gather_form == 0 && plan_direct(S, Q, K);
+}
+
+// fewer than one 64-entry batch per tile on average
+inline bool plan_sparse_load(const AccumShape& S, int B) { return S.nev * S.dup < (int64_t)B * S.NT * 64; }
+
+// The slot form: sensor or row-number records, Gaussian stamp, no polarity; by load, or forced (4).  gather_form 2 on row-number
+// records still passes the first clause and then the load test -- the "forced sparse" of a float bulk call is decided by its load.
+// gather_form 4 on a count or polarity image is not eligible and runs the list pipeline.
+inline bool plan_slot_eligible(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    return Q.raw && !Q.mode_count && !Q.pol && (K.gather_form == 0 || K.gather_form == 4 || (Q.raw == 2 && K.gather_form == 2)) &&
+           (K.gather_form == 4 || !plan_sparse_load(S, Q.B));
+}
+
+// the list pipeline's sparse gather (a wave per tile): forced, or by load; gather_form 4 that fell through gathers densely
+inline bool plan_sparse_gather(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    return Q.raw && !Q.mode_count && (K.gather_form == 2 || (K.gather_form == 0 && plan_sparse_load(S, Q.B)));
+}
+
+// the list pipeline's gather kernel
+enum { kGatherSparse, kGatherRawRows, kGatherGeneric };
+struct GatherPlan { int kind, NC, threads, per_wave; };
+inline GatherPlan plan_gather(const AccumShape& S, const AccumRequest& Q, const AccumKnobs& K)
+{
+    const int nb = Q.B * S.NT;
+    // sparse, large launches: 16 consecutive work items per wave (a wave per item leaves the launch bound by workgroup dispatch)
+    if (plan_sparse_gather(S, Q, K)) return GatherPlan{kGatherSparse, 0, 0, nb >= 65536 ? 16 : 1};
+    if (Q.raw && !Q.mode_count) {
+        // the add wave + four value waves with two tile columns each (shortest chain per batch), or -- when the launch has enough
+        // tiles to keep every SIMD busy anyway -- two value waves with four columns each (fewest instructions per batch)
+        const int NC = K.gather_nc == 2 || K.gather_nc == 4 ? K.gather_nc : (nb >= 32768 ? 4 : 2);
+        return GatherPlan{kGatherRawRows, NC, 64 * (1 + 8 / NC), 0};
+    }
+    return GatherPlan{kGatherGeneric, 0, K.gather_threads, 0};
+}
+
+// ---- the slot form's own shape test ----------------------------------------------------------------------------------------------
+struct SlotScatterChoice { int chunk, waves; bool rank; size_t lds; };
+inline size_t plan_slot_lds_rank(int NT, int chunk, int waves) { const int NTp = (NT + 1) & ~1; return ((size_t)NT * 4 + (size_t)chunk * 4 * 2 + (size_t)waves * NTp * 2 + (size_t)(NTp + 2) * 2 + (size_t)chunk * 4 + 15) & ~(size_t)15; }
+inline size_t plan_slot_lds_pre(int NT, int chunk) { const int NTp = (NT + 1) & ~1; return ((size_t)NT * 4 + (size_t)chunk * 4 * 2 + (size_t)(NTp + 2) * 2 + (size_t)chunk * 4 + 15) & ~(size_t)15; }
+inline size_t plan_slot_lds_ballot(int NT, int chunk) { const int NTp = (NT + 1) & ~1; return ((size_t)chunk * 4 + (size_t)chunk * 2 + (size_t)chunk * 4 * 2 + (size_t)kSlotScatWaves * NTp * 2 + (size_t)(NTp + 2) * 2 + (size_t)NT * 4 + 15) & ~(size_t)15; }
+
+// The scatter a batch will run -- decided before anything is launched: the preferred chunk size first, then shorter chunks; for each
+// the rank form (its own LDS footprint, <= 160 KB with the opt-in) where the device check allows it, else the ballot form (64 KB).
+// false: no form fits (e.g. VGA-class sensors without the rank scatter: 4 800 tiles x 8 per-wave counter rows alone are 77 KB).
+inline bool plan_slot_scatter(const AccumShape& S, const AccumKnobs& K, bool rank_ok, SlotScatterChoice* out)
+{
+    // chunks of 4 096 events (16 wavefronts per scatter workgroup) where the rank scatter runs and the slices are long: per-chunk work
+    // (the tiles' list bases, the prefix over the waves, the count rows) is shared by twice the events
+    // (128 x 1 Mev: binning 1.46-1.51 ms with 2 048, 1.41-1.44 with 4 096)
+    const int pref = K.slot_chunk ? K.slot_chunk : (S.per_slice >= (int64_t)1 << 18 ? 4096 : (S.per_slice >= (int64_t)1 << 17 ? 2048 : (S.per_slice >= (int64_t)1 << 14 ? 1024 : 256)));
+    const bool rank_allowed = rank_ok && K.slot_rank;
+    static const int sizes[4] = {4096, 2048, 1024, 256};
+    for (int i = 0; i < 4; i++) {
+        const int chunk = sizes[i];
+        if (chunk > pref) continue;
+        if (rank_allowed) {
+            const int waves = chunk == 4096 ? 16 : kSlotScatWaves;
+            const size_t l = plan_slot_lds_rank(S.NT, chunk, waves);
+            // (two or more workgroups per CU: the phases of different chunks overlap; one 130 KB workgroup per CU still beats falling back)
+            if (l <= (size_t)(chunk == 4096 ? 79 : 158) * 1024) { *out = SlotScatterChoice{chunk, waves, true, l}; return true; }
+        }
+        if (chunk <= 2048) {
+            const size_t l = plan_slot_lds_ballot(S.NT, chunk);
+            if (l <= 64 * 1024) { *out = SlotScatterChoice{chunk, kSlotScatWaves, false, l}; return true; }
+        }
+    }
+    return false;
+}
+
+// sl_plan_kernel keeps two words per slice in LDS and ranks a position's lists by an O(B^2) loop, sl_scan_kernel is one workgroup
+// per slice: batches of more than 2 048 slices take the list pipeline; so do tile grids whose count rows do not fit the LDS
+inline bool plan_slot_shape(const AccumShape& S, int B, const AccumKnobs& K, bool rank_ok, SlotScatterChoice* out)
+{
+    return !(B > 2048 || (size_t)S.NT * 4 > 64 * 1024 || !plan_slot_scatter(S, K, rank_ok, out));
+}
+
+// ---- the whole sequence, without a device: the route of a call that nothing declines at run time ----------------------------------
+// (the dictionary holds every position, the position table does not crowd; slots_usable: the positions' slot tables are, sl_ok)
+inline int plan_first_route(const AccumShape& S, AccumRequest Q, const AccumKnobs& K, const DictState& D, int W, int H, float sigma, bool rank_ok,
+                            bool slots_usable = true)
+{
+    SlotScatterChoice sc;
+    int set = Q.raw ? kSetMaps : kSetNone, wide = 0;
+    if (plan_bulk_eligible(S, Q, K) && plan_bulk_fits(S, K)) {
+        if (plan_dict_usable(S, Q, K, D, W, H, sigma) && plan_slot_shape(S, Q.B, K, rank_ok, &sc)) return kFormSlots | kSetDict;
+        Q.raw = 2; set = kSetPerCall;
+    }
+    else if (plan_direct(S, Q, K)) return kFormDirect | set;
+    if (plan_slot_eligible(S, Q, K) && slots_usable && plan_slot_shape(S, Q.B, K, rank_ok, &sc)) return kFormSlots | set;
+    if (Q.raw == 3 || Q.raw == 4) {
+        Q.raw = 1; wide = kRouteWidened;
+        if (plan_direct(S, Q, K)) return kFormDirect | set | wide;
+    }
+    return kFormLists | set | (plan_sparse_gather(S, Q, K) ? kRouteSparse : 0) | wide;
+}
+
+}  // namespace eorb

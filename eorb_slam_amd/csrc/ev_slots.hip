@@ -45,7 +45,6 @@ constexpr uint32_t kNoSlot = 0xffu;
 // sl_hot_kernel (SRC0 relative), so that kernel moves an entry to M0 with one scalar instruction; sl_gather_kernel reads the slot byte.
 typedef uint16_t slot_entry;
 constexpr uint32_t kEntryTag = 0x1000u;
-constexpr int kSlotScatWaves = 8;
 constexpr uint16_t kNoGeo = 0xffffu;           // (tile 127,127 with a second tile: never a valid range, TX and TY <= 127 there)
 constexpr int kCountWaves = 16;
 
@@ -1243,40 +1242,6 @@ static int sl_ncu(eorb_ctx* c)
 
 constexpr int kSlotDeclined = 1;       // ev_slots_accumulate: the batch's shape does not fit this form, nothing was launched
 
-// The scatter a batch will run -- decided before anything is launched: the preferred chunk size first, then shorter chunks; for each
-// the rank form (its own LDS footprint, <= 160 KB with the opt-in) where the device check allows it, else the ballot form (64 KB).
-// false: no form fits (e.g. VGA-class sensors: 4 800 tiles x 8 per-wave counter rows alone are 77 KB) and the caller falls back to
-// the batch pipeline, whose first scatter form needs 4 bytes of LDS per tile only.
-struct SlotScatterChoice { int chunk, waves; bool rank; size_t lds; };
-static size_t sl_lds_rank(int NT, int chunk, int waves) { const int NTp = (NT + 1) & ~1; return ((size_t)NT * 4 + (size_t)chunk * 4 * 2 + (size_t)waves * NTp * 2 + (size_t)(NTp + 2) * 2 + (size_t)chunk * 4 + 15) & ~(size_t)15; }
-static size_t sl_lds_pre(int NT, int chunk) { const int NTp = (NT + 1) & ~1; return ((size_t)NT * 4 + (size_t)chunk * 4 * 2 + (size_t)(NTp + 2) * 2 + (size_t)chunk * 4 + 15) & ~(size_t)15; }
-static size_t sl_lds_ballot(int NT, int chunk) { const int NTp = (NT + 1) & ~1; return ((size_t)chunk * 4 + (size_t)chunk * 2 + (size_t)chunk * 4 * 2 + (size_t)kSlotScatWaves * NTp * 2 + (size_t)(NTp + 2) * 2 + (size_t)NT * 4 + 15) & ~(size_t)15; }
-static bool sl_choose_scatter(const eorb_ctx* c, int NT, int64_t per_slice, bool rank_allowed, SlotScatterChoice* out)
-{
-    static const int chunk_env = [] { const char* e = getenv("EORB_SLOT_CHUNK"); const int v = e ? atoi(e) : 0; return (v == 256 || v == 1024 || v == 2048 || v == 4096) ? v : 0; }();
-    // chunks of 4 096 events (16 wavefronts per scatter workgroup) where the rank scatter runs and the slices are long: per-chunk work
-    // (the tiles' list bases, the prefix over the waves, the count rows) is shared by twice the events
-    // (128 x 1 Mev: binning 1.46-1.51 ms with 2 048, 1.41-1.44 with 4 096)
-    const int pref = chunk_env ? chunk_env : (per_slice >= (int64_t)1 << 18 ? 4096 : (per_slice >= (int64_t)1 << 17 ? 2048 : (per_slice >= (int64_t)1 << 14 ? 1024 : 256)));
-    static const int sizes[4] = {4096, 2048, 1024, 256};
-    for (int i = 0; i < 4; i++) {
-        const int chunk = sizes[i];
-        if (chunk > pref) continue;
-        if (rank_allowed) {
-            const int waves = chunk == 4096 ? 16 : kSlotScatWaves;
-            const size_t l = sl_lds_rank(NT, chunk, waves);
-            // (two or more workgroups per CU: the phases of different chunks overlap; one 130 KB workgroup per CU still beats falling back)
-            if (l <= (size_t)(chunk == 4096 ? 79 : 158) * 1024) { *out = {chunk, waves, true, l}; return true; }
-        }
-        if (chunk <= 2048) {
-            const size_t l = sl_lds_ballot(NT, chunk);
-            if (l <= 64 * 1024) { *out = {chunk, kSlotScatWaves, false, l}; return true; }
-        }
-    }
-    (void)c;
-    return false;
-}
-
 // The streams and events of the slot form, made once per context, all or nothing: P = the gather's plan (single-block kernels beside
 // the scatter), H = the register-row kernel (high priority: its lists are the launch's longest chains), G = the LDS gather of a
 // half batch while the main stream bins the next half.
@@ -1305,7 +1270,7 @@ static int sl_streams(eorb_ctx* c)
 // part's own workspaces.  Streams: binning on the context's stream; the plan on P; the long lists on H; the LDS gather on G when the
 // batch runs in halves (so that the next half's binning, HBM- and LDS-atomic-bound, runs under it), else on the context's stream.
 static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int part, int nparts, const void* d_events, int stride_in, const int64_t* h_offsets, int B,
-                      int W, int H, int TX, int TY, float* d_f32, uint32_t* d_minmax_enc, const SlotScatterChoice& sc, const SlotDict* dict)
+                      int W, int H, int TX, int TY, float* d_f32, uint32_t* d_minmax_enc, const SlotScatterChoice& sc, const SlotDict* dict, const AccumKnobs& K)
 {
     // with a position dictionary the count pass reads the float events and writes the hashed records every later pass reads
     const int stride = dict ? (dict->rec2 ? 2 : -4) : stride_in;
@@ -1380,15 +1345,13 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
     // ---- the gather's plan: sizes first (its buffers are allocated before anything of the part is launched) ----
     const size_t lds_g = (size_t)(T.sl_null + 1) * 256;
     const int wg_per_cu = std::max(1, (int)((160 * 1024) / lds_g));
-    static const int nw_env = [] { const char* e = getenv("EORB_SLOT_WAVES"); return e ? atoi(e) : 0; }();
-    static const int ns_env = [] { const char* e = getenv("EORB_SLOT_ROUNDS"); return e ? atoi(e) : 0; }();
     // four wavefronts per SIMD saturate the vector ALUs and leave every list about full single-wave speed (measured: 8 per SIMD
     // process the same entries per second, each list at half the pace)
     int nw = std::min(16, std::max(1, 16 / wg_per_cu));
-    if (nw_env >= 1 && nw_env <= 16) nw = nw_env;
+    if (K.slot_waves >= 1 && K.slot_waves <= 16) nw = K.slot_waves;
     nw = std::min(nw, std::max(1, B));
     // one task per tile position plus a few rounds of spare ones shared out by weight; a position never gets more wavefronts than slices
-    const int rounds = ns_env >= 1 ? ns_env : 4;
+    const int rounds = K.slot_rounds >= 1 ? K.slot_rounds : 4;
     const int Gt = NT + rounds * ncu * wg_per_cu;
     const int max_per_tile = (B + nw - 1) / nw;
     // items | task table | longest lists | scratch (2 NT) | tile weights | tickets
@@ -1403,12 +1366,11 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
     // lists of a few thousand entries or more go to the register-row kernel (when every tile's rows fit its 240 registers): 13
     // cycles per entry instead of 29, which shortens the launch's longest chains AND moves more entries per second; shorter lists
     // would not repay the 240 row loads per list (measured at 128 x 1 Mev: threshold 4 096 ... 8 192 1.40-1.45 ms, 16 384 1.53, none 2.44)
-    static const long long hot_env = [] { const char* e = getenv("EORB_SLOT_HOT_MIN"); return e ? atoll(e) : -1ll; }();
     uint32_t hot_min = T.sl_null <= SL_HOT_NROWS ? (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, nev * nparts / 16000), 0x7fffffff) : 0u;
-    const long long hot_over = c->dbg_slot_hot_min >= 0 ? c->dbg_slot_hot_min : hot_env;
+    const long long hot_over = K.slot_hot_min;
     // (never below 64: the register-row kernel's tail load reads the 64 bytes that END at the list's end; 0 = that kernel off)
     if (hot_over >= 0) hot_min = (T.sl_null <= SL_HOT_NROWS && hot_over > 0) ? (uint32_t)std::min<long long>(std::max<long long>(hot_over, 64), 0x7fffffff) : 0u;
-    const uint32_t hot_cap = c->dbg_slot_hot_cap > 0 ? (uint32_t)std::min(c->dbg_slot_hot_cap, kHotCap) : (uint32_t)kHotCap;
+    const uint32_t hot_cap = K.slot_hot_cap > 0 ? (uint32_t)std::min(K.slot_hot_cap, kHotCap) : (uint32_t)kHotCap;
     if ((rc = ensure(c, ws.hot, sizeof(HotDesc) * (size_t)kHotBuckets * kHotCap + 256))) return rc;
     uint32_t* d_hot_cnt = (uint32_t*)ws.hot.p;                           // 16 bucket counts | ticket (at word 32) | overflow count (33) | descriptors (from byte 256)
     HotDesc* d_hot_items = (HotDesc*)((char*)ws.hot.p + 256);
@@ -1418,14 +1380,11 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
         // the tile ranges of all sensor pixels + one set of counters per wavefront in the LDS of one workgroup per CU?
         const size_t nsrc = (size_t)T.w * (size_t)T.h;
         const size_t lds_c = 4 * ((nsrc + 2) / 2) + (size_t)kCountWaves * NTp * 2;
-        static const int cl_env = [] { const char* e = getenv("EORB_SLOT_COUNT_LDS"); return e ? atoi(e) : 1; }();
         if (dict && !(TX <= 127 && TY <= 127 && lds_c <= 159 * 1024)) return set_err(c, EORB_E_CAPACITY, "slot form: the position dictionary needs the LDS count pass");
         if (nchunks && dict) {
             const uint16_t* d_geo = (const uint16_t*)((const char*)T.sl_tab.p + sizeof(uint2) * nsrc);
             const int g = std::min(ncu, (nchunks + kCountWaves - 1) / kCountWaves);
-            static const int pre_env_d = [] { const char* e = getenv("EORB_SLOT_PRERANK"); return e ? atoi(e) : 1; }();
-            const int pre_on_d = c->dbg_slot_prerank >= 0 ? c->dbg_slot_prerank : pre_env_d;
-            if (pre_on_d && dict->rec2 && sc.rank && sl_lds_pre(NT, chunk) <= 158 * 1024) {
+            if (K.slot_prerank && dict->rec2 && sc.rank && plan_slot_lds_pre(NT, chunk) <= 158 * 1024) {
                 // (the dense ids are 16-bit: the ranked 8-byte record serves the dictionary path too)
                 if ((rc = ensure(c, ws.rec16, sizeof(uint64_t) * (size_t)std::max<int64_t>(h_offsets[B], 1)))) return rc;
                 prerank = true;
@@ -1436,17 +1395,14 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
             sl_count_lds_kernel<16, true><<<g, 64 * kCountWaves, lds_c, M>>>((const eorb_raw_event*)d_events, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, *dict);
             }
         }
-        else if (nchunks && cl_env && TX <= 127 && TY <= 127 && lds_c <= 159 * 1024) {
+        else if (nchunks && K.slot_count_lds && TX <= 127 && TY <= 127 && lds_c <= 159 * 1024) {
             const uint16_t* d_geo = (const uint16_t*)((const char*)T.sl_tab.p + sizeof(uint2) * nsrc);
             const int g = std::min(ncu, (nchunks + kCountWaves - 1) / kCountWaves);
             // 16-byte records on a sensor of at most 65 535 pixels: the pass leaves a 2-byte record per event for the scatter
-            static const int tc_env = [] { const char* e = getenv("EORB_SLOT_TRANSCODE"); return e ? atoi(e) : 1; }();
             uint16_t* d_rec16 = nullptr;
             // ... or, where the rank scatter would run: an 8-byte record that also carries the ranks of the event's entries in the
             // chunk's runs (the values the counting atomics return), so that the scatter neither counts nor ranks (sl_scatter_pre_kernel)
-            static const int pre_env = [] { const char* e = getenv("EORB_SLOT_PRERANK"); return e ? atoi(e) : 1; }();
-            const int pre_on = c->dbg_slot_prerank >= 0 ? c->dbg_slot_prerank : pre_env;
-            if (pre_on && (stride == 16 || stride == 4 || stride == 2) && nsrc <= 65535 && sc.rank && sl_lds_pre(NT, chunk) <= 158 * 1024) {
+            if (K.slot_prerank && (stride == 16 || stride == 4 || stride == 2) && nsrc <= 65535 && sc.rank && plan_slot_lds_pre(NT, chunk) <= 158 * 1024) {
                 if ((rc = ensure(c, ws.rec16, sizeof(uint64_t) * (size_t)std::max<int64_t>(h_offsets[B], 1)))) return rc;
                 d_rec16 = (uint16_t*)ws.rec16.p;
                 prerank = true;
@@ -1456,7 +1412,7 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
 #undef SL_COUNTR
             }
             else {
-            if (tc_env && stride == 16 && nsrc <= 65535 && sc.rank) {
+            if (K.slot_transcode && stride == 16 && nsrc <= 65535 && sc.rank) {
                 if ((rc = ensure(c, ws.rec16, sizeof(uint16_t) * (size_t)std::max<int64_t>(h_offsets[B], 1)))) return rc;
                 d_rec16 = (uint16_t*)ws.rec16.p;
             }
@@ -1485,11 +1441,11 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
                                                                                d_items, d_tile_w, d_tile_m, d_ctr, d_hot_cnt, d_hot_items, hot_cap);
         sl_tasks_kernel<<<1, 1024, sizeof(uint32_t) * (size_t)NT, P>>>(d_tile_w, d_tile_m, NT, Gt, max_per_tile, d_scr, d_task, d_hot_cnt, hot_cap);
         EORB_HIP(c, hipEventRecord(E[1], P));
-        // ---- the scatter (form and chunk size chosen up front: sl_choose_scatter) ----
+        // ---- the scatter (form and chunk size chosen up front: plan_slot_scatter, ev_plan.h) ----
         ProfScope ps2(c, "ev_scatter");
         const int stride = scat_stride;                                   // (what the count pass left for the scatter)
         if (nchunks && prerank) {
-            const size_t lds_p = sl_lds_pre(NT, chunk);
+            const size_t lds_p = plan_slot_lds_pre(NT, chunk);
             const uint16_t* d_segcnt_c = d_segcnt;
             if (sc.waves == 16) {
                 if ((rc = sl_optin(c, 16, (const void*)sl_scatter_pre_kernel<16>, 159 * 1024))) return rc;
@@ -1525,8 +1481,7 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
         if ((rc = sl_optin(c, 9, (const void*)sl_gather_kernel, 160 * 1024))) return rc;
         if (hot_min) {
             // the long lists on the high-priority stream beside the gather: they need the scatter's entries and the plan's descriptors
-            static const int hw_env = [] { const char* e = getenv("EORB_SLOT_HOT_WAVES"); return e ? atoi(e) : 0; }();
-            const int hw = c->dbg_slot_hot_waves > 0 ? c->dbg_slot_hot_waves : (hw_env > 0 ? hw_env : 8 * ncu);     // two per SIMD: all of its registers
+            const int hw = K.slot_hot_waves > 0 ? K.slot_hot_waves : 8 * ncu;     // two per SIMD: all of its registers
             EORB_HIP(c, hipStreamWaitEvent(Hs, E[2], 0));
             EORB_HIP(c, hipStreamWaitEvent(Hs, E[1], 0));
             sl_hot_kernel<<<hw, 64, 0, Hs>>>(d_hot_cnt, d_hot_cnt + 32, d_hot_items, kHotCap, (const float*)T.sl_rows.p, (const slot_entry*)ws.entries.p,
@@ -1549,25 +1504,18 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
 // the register-row kernel of the first half (vector-ALU / LDS-read / scalar-ALU bound) beside the count and scatter passes of the
 // second (HBM- and LDS-atomic bound).  Returns kSlotDeclined (> 0, nothing launched) when the batch's shape does not
 // fit: the caller goes on with the batch pipeline.
-int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H, int TX, int TY,
+int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const AccumShape& S, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H,
                         float* d_f32, uint32_t* d_minmax_enc, const SlotDict* dict)
 {
-    const int NT = TX * TY;
-    const int64_t nev = h_offsets[B] - h_offsets[0];
-    static const int rank_env0 = [] { const char* e = getenv("EORB_SLOT_RANK"); return e ? atoi(e) : 1; }();
-    const bool rank_allowed = c->sl_rank_ok == 1 && (c->dbg_slot_rank < 0 ? rank_env0 != 0 : c->dbg_slot_rank != 0);
-    static const int halves_env = [] { const char* e = getenv("EORB_SLOT_HALVES"); return e ? atoi(e) : -1; }();
-    const int halves_opt = c->dbg_slot_halves >= 0 ? c->dbg_slot_halves : halves_env;
+    const int TX = S.TX, TY = S.TY, NT = S.NT;
+    const AccumKnobs K = accum_knobs(c);
     // Off by default.  Measured at 128 x 1 Mev: 3.94 ms per step in halves against 3.34 in one part -- each half's gather phase is bounded
     // from below by the serial chain of its own longest list (200 000 entries x 13 cycles = 1.1 ms on the register-row kernel's
     // wavefront), so two halves pay that chain twice; the overlap of the second half's binning with the first half's gather does not
     // buy it back.  The parts machinery stays (test hook "slot_halves", EORB_SLOT_HALVES=1) for batches without such chains.
-    const int nparts = (halves_opt > 0 && B >= 2) ? 2 : 1;
-    const int64_t per_slice = nev / B;
+    const int nparts = (K.slot_halves > 0 && B >= 2) ? 2 : 1;
     SlotScatterChoice sc;
-    // sl_plan_kernel keeps two words per slice in LDS and ranks a position's lists by an O(B^2) loop, sl_scan_kernel is one workgroup
-    // per slice: batches of more than 2 048 slices take the batch pipeline; so do tile grids whose count rows do not fit the LDS
-    if (B > 2048 || (size_t)NT * 4 > 64 * 1024 || !sl_choose_scatter(c, NT, per_slice, rank_allowed, &sc)) return kSlotDeclined;
+    if (!plan_slot_shape(S, B, K, c->sl_rank_ok == 1, &sc)) return kSlotDeclined;
     for (int b = 0; b < B; b++) {
         const int64_t s = h_offsets[b], e = h_offsets[b + 1];
         if (e < s) return set_err(c, EORB_E_ARG, "ev_accumulate: offsets not monotone");
@@ -1581,7 +1529,7 @@ int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const void* d_events, i
     for (int part = 0; part < nparts; part++) {
         const int b0 = part ? B0 : 0, nb_ = part ? B - B0 : B0;
         if ((rc = slots_part(c, T, c->sl_ws[part], part, nparts, d_events, stride, h_offsets + b0, nb_, W, H, TX, TY,
-                             d_f32 + (size_t)b0 * W * H, d_minmax_enc + 2 * (size_t)b0, sc, dict))) return rc;
+                             d_f32 + (size_t)b0 * W * H, d_minmax_enc + 2 * (size_t)b0, sc, dict, K))) return rc;
     }
     // whatever the other streams did is done before the images are read (streams are in order: the last part's events cover the first's)
     hipEvent_t* E = c->sl_ev + 5 * (nparts - 1);

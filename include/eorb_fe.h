@@ -107,10 +107,13 @@ void        eorb_destroy(eorb_ctx* ctx);
 int         eorb_sync(eorb_ctx* ctx);
 /* test hooks, not part of the reference's interface: "octree_pool_shrink" (n > 0: shrink the octree node pool by n at the
  * next configure, to force the overflow path), "octree_force_global" (1: keep the whole octree working set in global memory), "orb_three_launches" (1: orientation, descriptors and output order as the three kernels of a call with a lapping area), "win_lds_entries" (window matchers: entries of a pair that the second phase stages in LDS; default: as many as fit), "win_list_cap" / "win_pool_cap" (window matchers:
- * candidate list capacity per query / pool per pair, to force the full-scan path), "gather_form" (raw events with a Gaussian
- * stamp: 0 = choose the gather kernel by the batch's shape, 1 = the pipelined workgroup per tile, 2 = the wave per tile, 3 = no
- * binning, every tile's wave reads all events of its slice (calls with at most 4 slices), 4 = two-byte slot lists whatever the
- * batch's shape (falls back to 1 where they do not apply: polarity, sigma > 4/3, a tile with more than 254 slots)), "dedupe_min_events" (float events:
+ * candidate list capacity per query / pool per pair, to force the full-scan path), "gather_form" (event images with a Gaussian
+ * stamp; the rules are csrc/ev_plan.h: 0 = choose the form by the call's shape; 1 = the list pipeline with its dense gather, float events
+ * are not tabulated; 2 = the list pipeline with the wave per tile (float events: only those the bulk path tabulates, and their slot
+ * lists still run when the batch is dense); 3 = no binning, every tile's wave reads all events of its slice (float or 16-byte sensor
+ * records, at most 4 slices; float events the bulk path tabulates are not served this way); 4 = two-byte slot lists whatever the
+ * batch's load (sensor records and tabulated float events; a count image, polarity, sigma > 4/3, a tile with more than 254 slots or
+ * more than 2 048 slices run the list pipeline with its dense gather)), "dedupe_min_events" (float events:
  * number of events per call from which their distinct positions are tabulated, default 2^20), "kfdb_initial_slots" (KeyFrameDatabase:
  * the capacity in slots, and 64 pool words per slot, that the first eorb_kfdb_add allocates, to cross a pool growth with a handful of adds),
  * "kfdb_finish_lds_entries" (KeyFrameDatabase queries: scored keyframes up to which the last kernel sorts in LDS, 0 = as many as fit (4096),
@@ -119,7 +122,10 @@ int         eorb_debug_option(eorb_ctx* ctx, const char* name, int value);
 /* test hook: counters a test can read to see which path served its calls.  "slot_calls": accumulation calls that took the slot
  * lists (gather_form 0 on dense batches, or 4); "slot_flags": sticky device flags of that path (0 = fine; synchronises); "slot_hot_items": lists the last such call handed to
  * the register-row kernel (synchronises); "slot_rank_ok": 1 when the scatter takes its ranks from LDS atomics; "kfdb_slot_cap" /
- * "kfdb_word_cap": slots / words the KeyFrameDatabase pools hold room for.
+ * "kfdb_word_cap": slots / words the KeyFrameDatabase pools hold room for; "accum_route": what served the context's last accumulation
+ * call (0: none yet) = form (1 binning-free, 2 slot lists, 3 list pipeline) | position set << 2 (0 none: float events as they are,
+ * 1 the undistortion maps, 2 the call's own tabulated positions, 3 the position dictionary) | 16 if the pipeline's sparse gather ran
+ * | 32 if short records (eorb_raw_event4 / eorb_raw_event2) were widened first.
  * Returns the value, or -1 for an unknown name. */
 long long   eorb_debug_counter(eorb_ctx* ctx, const char* name);
 /* test hook, not part of the reference's interface: the intermediate images of the extractor, for stage-by-stage comparison with

@@ -4,13 +4,16 @@ with the oracle on the same inputs.  A NaN in an output equals any NaN; every ot
 import numpy as np
 import pytest
 
+import accum_routes as ar
 import edge_inputs as ei
 import plain_ref as pr
 
 pytestmark = pytest.mark.gpu
 
 # gather forms of ev2im_gauss: by size (0), the list pipeline (1), the binning-free kernel (3), bulk (2 with dedupe_min_events 1),
-# slot lists (4 with dedupe_min_events 1)
+# slot lists (4 with dedupe_min_events 1).  The labels name what is asked for, not always what runs: count images take the list
+# pipeline under every label; "slots" and "bulk" with polarity or a half window beyond 4 run the list pipeline on the tabulated
+# positions; "bulk" (the sparse gather forced) still runs the slot lists when the call is dense.  Each test reads the route back.
 FORMS = {"auto": (0, 1 << 20), "lists": (1, 1 << 20), "direct": (3, 1 << 20), "bulk": (2, 1), "slots": (4, 1)}
 
 
@@ -46,8 +49,14 @@ def test_ev2im_gauss_edges(oracle, fe, W, H, sigma, pol, form):
     what = "%dx%d sigma %.1f pol %d %s" % (W, H, sigma, pol, form)
     c = fe.Context()                                                       # (its own: the bulk forms keep positions between calls)
     try:
+        opts = (("gather_form", FORMS[form][0]), ("dedupe_min_events", FORMS[form][1]))
         c.debug_option("gather_form", FORMS[form][0]); c.debug_option("dedupe_min_events", FORMS[form][1])
         got = fe.EvImConverter.ev2im_gauss(ev, W, H, sigma, pol, True, ctx=c, return_all=True)
+        route = ar.assert_route(c, what, "gauss", [len(ev)], pol, opts, dict_valid=False, W=W, H=H, sigma=sigma)
+        if form in ("auto", "lists", "direct"):
+            assert route == ((ar.LISTS if form == "lists" else ar.DIRECT) | ar.NONE), (what, ar.describe(route))
+        elif pol:
+            assert route & ~ar.SPARSE == ar.LISTS | ar.PER_CALL, (what, ar.describe(route))
         _equal_oracle(what, got, oracle.ev2im_gauss(ev, W, H, sigma, pol, True))
         ei.check_acc_rule(what, got, oracle, ev, W, H, sigma, pol)
         got = fe.EvImConverter.ev2im_gauss(blank, W, H, sigma, pol, True, ctx=c, return_all=True)
@@ -95,7 +104,11 @@ def test_ev2im_count_ties_and_edges(oracle, fe, W, H, form):
     c = fe.Context()
     try:
         c.debug_option("gather_form", FORMS[form][0]); c.debug_option("dedupe_min_events", FORMS[form][1])
-        run = lambda ev, pol: fe.EvImConverter.ev2im(ev, W, H, pol, True, ctx=c, return_all=True)
+
+        def run(ev, pol):
+            res = fe.EvImConverter.ev2im(ev, W, H, pol, True, ctx=c, return_all=True)
+            assert c.debug_counter("accum_route") == ar.LISTS | ar.NONE == ar.planned_route("count", [len(ev)], pol, (("gather_form", FORMS[form][0]), ("dedupe_min_events", FORMS[form][1])), W=W, H=H)
+            return res
         what = "%dx%d %s" % (W, H, form)
         ei.check_count_rule(what, run, oracle, W, H)
         ev = ei.count_events(W, H)
@@ -173,13 +186,17 @@ def test_raw_path_edges(oracle, fe, sigma, check):
         assert ei.same_events(got, oev) and ei.same_events(got, want), "undistort_events keeps %d events, the oracle %d, by hand %d" % (len(got), len(oev), len(want))
         for form in sorted(FORMS):
             c.debug_option("gather_form", FORMS[form][0]); c.debug_option("dedupe_min_events", FORMS[form][1])
+            opts = (("gather_form", FORMS[form][0]), ("dedupe_min_events", FORMS[form][1]))
             for pol in (False, True):
                 what = "raw sigma %.1f check %d pol %d %s" % (sigma, check, pol, form)
                 res = fe.EvImConverter.ev2im_gauss_raw(raw, W, H, sigma, pol, True, ctx=c, return_all=True)
+                route = ar.assert_route(c, what, "gauss_raw", [len(raw)], pol, opts, W=W, H=H, sigma=sigma)
+                assert route & ar.MAPS and (ar.forms_of(route) != ar.SLOTS or (not pol and form in ("auto", "slots"))), (what, ar.describe(route))
                 _equal_oracle(what, res, oracle.ev2im_gauss(oev, W, H, sigma, pol, True))
                 ei.check_acc_rule(what, res, oracle, want, W, H, sigma, pol)
             for pol in (False, True):                                        # the count form under the same settings
                 res = fe.EvImConverter.ev2im_raw(raw, W, H, pol, True, ctx=c, return_all=True)
+                assert c.debug_counter("accum_route") == ar.LISTS | ar.MAPS == ar.planned_route("count_raw", [len(raw)], pol, opts, W=W, H=H)
                 _equal_oracle("raw count check %d pol %d %s" % (check, pol, form), res, oracle.ev2im(oev, W, H, pol, True))
                 sub, _ = ei.acc_expected_events(want, W, H, 0, count=True)
                 _equal_oracle("raw count check %d pol %d %s, rule" % (check, pol, form), res, oracle.ev2im(sub, W, H, pol, True))

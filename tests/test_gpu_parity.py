@@ -1,11 +1,15 @@
 """Parity tests proper: the HIP path (through the C ABI) against the CPU oracle, bit-exact.
 Run on the GPU box with `pytest -m gpu`."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from eorb_slam_amd import synth
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accum_routes as ar                           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -41,18 +45,25 @@ def _same_bits(a, b):
 ])
 def test_ev2im_gauss_bit_exact(oracle, fe, ctx, case):
     """form: the accumulation kernels -- chosen by the call's size (0: up to 16 384 events take the binning-free kernel), the
-    binned list pipeline whatever the size (1), the binning-free kernel whatever the size (3)."""
+    binned list pipeline whatever the size (1), the binning-free kernel whatever the size (3).  What served each call is read back and
+    held to the dispatcher's rules (-1 and -4 with polarity or sigma > 4/3 run the list pipeline on the tabulated positions)."""
     W, H = case.get("W", 240), case.get("H", 180)
     ev = synth.random_events(case["n"], W, H, seed=11 + case["n"], frac=case["frac"])
     try:
         for form in (0, 1, 3, -1, -4):
             # -1: the bulk form of the float path at test size (the distinct positions of the call tabulated, then the raw kernels);
             # -4: the same with the slot lists (rows computed from the call's positions)
-            ctx.debug_option("gather_form", (2 if form == -1 else 4) if form < 0 else form)
-            ctx.debug_option("dedupe_min_events", 1 if form < 0 else 1 << 20)
+            opts = (("gather_form", (2 if form == -1 else 4) if form < 0 else form), ("dedupe_min_events", 1 if form < 0 else 1 << 20))
+            for k, v in opts:
+                ctx.debug_option(k, v)
             for normalized in (True, False):
                 of, ou, omm = oracle.ev2im_gauss(ev, W, H, case["sigma"], case["pol"], normalized)
                 gf, gu, gmm = fe.EvImConverter.ev2im_gauss(ev, W, H, case["sigma"], case["pol"], normalized, ctx=ctx, return_all=True)
+                route = ar.assert_route(ctx, (form, case), "gauss", [len(ev)], case["pol"], opts, W=W, H=H, sigma=case["sigma"])
+                if form in (1, 3) or (form == 0 and len(ev) > 16384):
+                    assert route == ((ar.DIRECT if form == 3 else ar.LISTS) | ar.NONE), (form, ar.describe(route))
+                elif len(ev):
+                    assert (route & ar.PER_CALL or route & ar.DICT == ar.DICT) if form < 0 else route == ar.DIRECT | ar.NONE, (form, ar.describe(route))
                 assert _same_bits(of, gf), "form %d: f32 image differs: %d px" % (form, int((of.view(np.uint32) != gf.view(np.uint32)).sum()))
                 assert _same_bits(omm, gmm), form
                 if normalized:
@@ -231,6 +242,7 @@ def test_ev2im_gauss_hot_pixel_order(oracle, fe, ctx):
             for pol in (False, True):
                 of, ou, omm = oracle.ev2im_gauss(ev, 240, 180, 1.0, pol, True)
                 gf, gu, gmm = fe.EvImConverter.ev2im_gauss(ev, 240, 180, 1.0, pol, True, ctx=ctx, return_all=True)
+                assert ar.assert_route(ctx, form, "gauss", [n], pol, (("gather_form", form),)) == ((ar.DIRECT if form == 3 else ar.LISTS) | ar.NONE)
                 assert _same_bits(of, gf) and np.array_equal(ou, gu) and _same_bits(omm, gmm), form
     finally:
         ctx.debug_option("gather_form", 0)
@@ -1459,9 +1471,9 @@ def test_register_row_kernel_list_tails(oracle, fe):
     ctx.close()
 
 
-def _raw_batch(fe, raws, W, H, mx, my, opts=(), check=True, sigma=1.0):
-    """One eorb_fe_run_batch_raw_dev call over the slices `raws` (detect-only extraction, no matching): u8 images, the float images
-    behind them (eorb_fe_last_f32_dev), the running extremes and the slot form's test-hook counters."""
+def _raw_batch(fe, raws, W, H, mx, my, opts=(), check=True, sigma=1.0, fmt=True):
+    """One eorb_fe_run_batch_raw_dev call over the slices `raws` (detect-only extraction, no matching; fmt=4: as eorb_raw_event4 records):
+    u8 images, the float images behind them (eorb_fe_last_f32_dev), the running extremes and the accumulation's test-hook counters."""
     B = len(raws)
     sizes = [len(r) for r in raws]
     fb = fe.FrontEndBatch(W, H, sigma, False, 400, 1.2, 1, 10, 0, 9, max_batch=B, max_events=max(max(sizes), 1), want_desc=False, match=False)
@@ -1469,16 +1481,16 @@ def _raw_batch(fe, raws, W, H, mx, my, opts=(), check=True, sigma=1.0):
     for k, v in opts:
         c.debug_option(k, v)
     fe.EvImConverter.set_undistort_maps(mx, my, check, ctx=c)
-    blob = np.concatenate(raws)
+    blob = np.concatenate(raws) if fmt is True else np.concatenate([fe.pack_raw_events4(r) for r in raws])
     d_ev = c.dev_alloc(max(blob.nbytes, 16)); c.upload(d_ev, blob)
     d_img = c.dev_alloc(B * W * H); d_kp = c.dev_alloc(B * cap * 28); d_n = c.dev_alloc(B * 4)
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    fb.run_dev(d_ev, off, d_img, d_kp, None, d_n, None, None, raw=True)
+    fb.run_dev(d_ev, off, d_img, d_kp, None, d_n, None, None, raw=fmt)
     c.sync()
     imgs = np.zeros((B, H, W), np.uint8); c.download(imgs, d_img)
     p32, mm = fb.last_f32(B)
     f32 = np.zeros((B, H, W), np.float32); c.download(f32, p32)
-    cnt = {k: c.debug_counter(k) for k in ("slot_calls", "slot_flags", "slot_hot_items", "slot_hot_overflow", "slot_scatter_form", "slot_chunk", "slot_rank_ok", "slot_parts")}
+    cnt = {k: c.debug_counter(k) for k in ("slot_calls", "slot_flags", "slot_hot_items", "slot_hot_overflow", "slot_scatter_form", "slot_chunk", "slot_rank_ok", "slot_parts", "accum_route")}
     for p_ in (d_ev, d_img, d_kp, d_n):
         c.dev_free(p_)
     c.close()

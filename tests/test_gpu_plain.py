@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from eorb_slam_amd import synth
+import accum_routes as ar
 import plain_ref as pr
 import test_oracle_plain as op
 
@@ -38,16 +39,23 @@ def _same_bits(a, b):
 # ---- accumulation -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("W,H,sigma,pol", op.ACC_CASES)
 def test_ev2im_gauss_every_gather_form_against_plain(oracle, fe, ctx, W, H, sigma, pol):
-    """the forms of test_ev2im_gauss_bit_exact: by size (0), the list pipeline (1), the binning-free kernel (3), the two bulk forms"""
+    """the forms of test_ev2im_gauss_bit_exact: by size (0), the list pipeline (1), the binning-free kernel (3), the two bulk forms
+    (which run the list pipeline on the tabulated positions with polarity or a half window beyond 4); the route is read back"""
     ev = op.acc_events(W, H)
     ref = op.acc_plain(W, H, sigma, pol)
     of, ou, omm = oracle.ev2im_gauss(ev, W, H, sigma, pol, True)
     try:
         for form in (0, 1, 3, -1, -4):
-            ctx.debug_option("gather_form", (2 if form == -1 else 4) if form < 0 else form)
-            ctx.debug_option("dedupe_min_events", 1 if form < 0 else 1 << 20)
+            opts = (("gather_form", (2 if form == -1 else 4) if form < 0 else form), ("dedupe_min_events", 1 if form < 0 else 1 << 20))
+            for k, v in opts:
+                ctx.debug_option(k, v)
             gf, gu, gmm = fe.EvImConverter.ev2im_gauss(ev, W, H, sigma, pol, True, ctx=ctx, return_all=True)
             what = "%dx%d sigma %.1f pol %d form %d" % (W, H, sigma, pol, form)
+            route = ar.assert_route(ctx, what, "gauss", [len(ev)], pol, opts, W=W, H=H, sigma=sigma)
+            if form >= 0:
+                assert route == ((ar.LISTS if form == 1 else ar.DIRECT) | ar.NONE), (what, ar.describe(route))
+            elif pol or sigma > 4.0 / 3.0:
+                assert ar.forms_of(route) == ar.LISTS and route & ar.PER_CALL, (what, ar.describe(route))
             op.check_accumulation(what, gf, gmm, gu, ref)
             assert _same_bits(of, gf), "%s: f32 image differs from the oracle in %d px" % (what, int((of.view(np.uint32) != gf.view(np.uint32)).sum()))
             assert _same_bits(omm, gmm) and np.array_equal(ou, gu), what

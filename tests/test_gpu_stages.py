@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from eorb_slam_amd import synth
+import accum_routes as ar
 import test_gpu_parity as parity
 
 pytestmark = pytest.mark.gpu
@@ -252,13 +253,19 @@ def test_float_accumulation_off_sizes(oracle, fe, ctx, W, H):
     ev = synth.random_events(5000, W, H, seed=11 + W, frac=True)
     try:
         for form in (0, 1, 3, -1, -4):
-            ctx.debug_option("gather_form", (2 if form == -1 else 4) if form < 0 else form)
-            ctx.debug_option("dedupe_min_events", 1 if form < 0 else 1 << 20)
+            opts = (("gather_form", (2 if form == -1 else 4) if form < 0 else form), ("dedupe_min_events", 1 if form < 0 else 1 << 20))
+            for k, v in opts:
+                ctx.debug_option(k, v)
             for sigma, pol in ((1.0, False), (1.5, True), (0.5, False)):
                 for normalized in (True, False):
                     of, ou, omm = oracle.ev2im_gauss(ev, W, H, sigma, pol, normalized)
                     gf, gu, gmm = fe.EvImConverter.ev2im_gauss(ev, W, H, sigma, pol, normalized, ctx=ctx, return_all=True)
                     what = (form, sigma, pol, normalized)
+                    route = ar.assert_route(ctx, what, "gauss", [len(ev)], pol, opts, W=W, H=H, sigma=sigma)
+                    if form >= 0:
+                        assert route == ((ar.LISTS if form == 1 else ar.DIRECT) | ar.NONE), (what, ar.describe(route))
+                    elif pol:                       # (the bulk forms with polarity: the list pipeline on the tabulated positions)
+                        assert ar.forms_of(route) == ar.LISTS and route & ar.PER_CALL, (what, ar.describe(route))
                     assert _same_bits(of, gf), "%s: f32 image differs: %d px" % (what, int((of.view(np.uint32) != gf.view(np.uint32)).sum()))
                     assert _same_bits(omm, gmm), what
                     if normalized:

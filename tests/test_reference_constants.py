@@ -92,4 +92,5 @@ def test_event_record_and_stamp_constants_equal_reference():
     orc = _read(ROOT, "oracle/orc_events.c")
     assert re.search(r"ceil\(\(double\)sigma \* 3\.0\)", orc) and "0.001f" in orc
     prod = _read(ROOT, "eorb_slam_amd/csrc/ev_accum.hip")
-    assert re.search(r"ceil\(\(double\)sigma \* 3\.0\)", prod) and "0.001f" in prod
+    plan = _read(ROOT, "eorb_slam_amd/csrc/ev_plan.h")                          # (the half window is computed in one place: accum_shape)
+    assert len(re.findall(r"ceil\(\(double\)sigma \* 3\.0\)", plan)) == 1 and "0.001f" in prod
