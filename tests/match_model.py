@@ -127,8 +127,9 @@ class _Hist:
 
 
 # ---------------------------------------------------------------------------------------------------
-def candidates(fr, x, y, r, min_level, max_level, wrong=None):
-    """Frame::GetFeaturesInArea :710-781 by brute force, in its order"""
+def candidates(fr, x, y, r, min_level, max_level, wrong=None, levels=None):
+    """Frame::GetFeaturesInArea :710-781 by brute force, in its order.  levels: what getKPtLevelMono(vCell[j]) (:763) gives for the
+    keypoints of this grid where that is not the keypoint's own level (the right grid of a two-camera frame, tests/twocam_model.py)"""
     x, y, r = F(x), F(y), F(r)
     cr = ei.cell_range_rule(x, y, r, fr.gb)
     if cr is None:
@@ -147,7 +148,7 @@ def candidates(fr, x, y, r, min_level, max_level, wrong=None):
         if c is None or not (cr[0] <= c[0] <= cr[1] and cr[2] <= c[1] <= cr[3]):
             continue
         if check:
-            lv = level_of(fr, i)
+            lv = level_of(fr, i) if levels is None else levels[i]
             if lv < min_level or (max_level >= 0 and lv > max_level):
                 continue
         if inside(F(fr.kps["x"][i]) - x) and inside(F(fr.kps["y"][i]) - y):
