@@ -131,7 +131,7 @@ struct eorb_ctx {
     eorb::PosTables maps;
     eorb::DevBuf ev_info, ev_stamps;              // float events of the per-slice calls: the same tables per EVENT (ev_direct_slices_dev)
     eorb::DevBuf sl_trace; long long sl_trace_n = 0;
-    // per-batch workspaces of the slot form, one set per part of a batch (a batch of 64 slices or more runs as two halves)
+    // per-batch workspaces of the slot form, one set per part of a batch (a batch runs as two halves only on request: "slot_halves")
     struct SlotWS { eorb::DevBuf chunks, segoff, entries, tile_order, plan, hot, rec16; };
     SlotWS sl_ws[2];
     // its streams (made together, ev_slots.hip sl_streams): sl_side = the register-row kernel (high priority), sl_pstream = the plan,
@@ -141,8 +141,9 @@ struct eorb_ctx {
     int sl_last_parts = 0, sl_last_nb[2] = {0, 0};      // the last slot-form call: its parts, (slices x tiles) of each
     int sl_rank_ok = -1;
     int ncu = 0;                                 // compute units of c->device (per context: a second context may sit on another GPU)
-    unsigned sl_attr = 0;                        // bit per kernel instantiation whose dynamic-LDS opt-in was made on c->device
+    std::vector<const void*> sl_optins;          // kernel instantiations whose dynamic-LDS opt-in was made on c->device (ev_slots.hip sl_optin)
     int sl_last_rank = -1, sl_last_chunk = 0;    // the scatter the last slot-form call ran (1 rank form, 0 ballot form), its chunk size
+    int sl_last_binning = -1;                    // ... and its whole SlotBinPlan (ev_plan.h slot_binning_code)
     int* rb_pinned = nullptr;                   // 64 ints of pinned host memory: the landing place of small read-backs (position count, slot info)
     long long sl_calls = 0;                      // test hook counter (eorb_debug_counter)
     int accum_route = 0;                         // what served the last ev_accumulate_dev call (ev_plan.h: form | position set | sparse | widened)

@@ -413,6 +413,7 @@ long long eorb_debug_counter(eorb_ctx* c, const char* name)
     if (!strcmp(name, "dict_positions")) return c->pd_valid ? c->pd_K : 0;
     if (!strcmp(name, "slot_scatter_form")) return c->sl_last_rank;       // the scatter of the last slot-form call: 1 rank form, 0 ballot form
     if (!strcmp(name, "slot_chunk")) return c->sl_last_chunk;
+    if (!strcmp(name, "slot_binning")) return c->sl_last_binning;         // count | record << 2 | scatter << 4 of the last slot-form call (ev_plan.h SlotBinPlan)
     if (!strcmp(name, "kfdb_slot_cap")) return c->kfdb.slot_cap;          // KeyFrameDatabase pools: slots / words they hold room for
     if (!strcmp(name, "kfdb_word_cap")) return c->kfdb.word_cap;
     if (!strcmp(name, "slot_parts")) return c->sl_last_parts;              // 2: the last slot-form call ran its batch as two halves

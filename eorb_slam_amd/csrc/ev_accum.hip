@@ -2031,8 +2031,6 @@ static int ev_raw_tables(eorb_ctx* c, PosTables& T, const AccumShape& S, int W, 
 //   slot_chunk       --                                 EORB_SLOT_CHUNK (0)    environment if 256 / 1024 / 2048 / 4096, else by the slices' length
 //   slot_waves       --                                 EORB_SLOT_WAVES (0)    environment if 1..16
 //   slot_rounds      --                                 EORB_SLOT_ROUNDS (0)   environment if >= 1, else 4
-//   slot_count_lds   --                                 EORB_SLOT_COUNT_LDS (1) environment
-//   slot_transcode   --                                 EORB_SLOT_TRANSCODE (1) environment
 //   slot_rank        "slot_rank" (-1)                   EORB_SLOT_RANK (1)     option if >= 0, else environment; non-zero: allowed
 //   slot_hot_min     "slot_hot_min" (-1)                EORB_SLOT_HOT_MIN (-1) option if >= 0, else environment; < 0: by the batch's size
 //   slot_hot_cap     "slot_hot_cap" (0)                 --                     option; <= 0: kHotCap
@@ -2052,8 +2050,6 @@ AccumKnobs accum_knobs(const eorb_ctx* c)
         k.slot_chunk = (sc == 256 || sc == 1024 || sc == 2048 || sc == 4096) ? sc : 0;
         k.slot_waves = (int)num("EORB_SLOT_WAVES", 0);
         k.slot_rounds = (int)num("EORB_SLOT_ROUNDS", 0);
-        k.slot_count_lds = (int)num("EORB_SLOT_COUNT_LDS", 1);
-        k.slot_transcode = (int)num("EORB_SLOT_TRANSCODE", 1);
         k.slot_rank = num("EORB_SLOT_RANK", 1) != 0;
         k.slot_hot_min = num("EORB_SLOT_HOT_MIN", -1);
         k.slot_hot_waves = std::max((int)num("EORB_SLOT_HOT_WAVES", 0), 0);
@@ -2416,48 +2412,30 @@ static int ev_accumulate_tables(eorb_ctx* c, PosTables& T, int set, const AccumS
     // chunk list (host) -> device.  A chunk is binned by ONE workgroup: large inputs take long chunks (fewer segment tables), small
     // ones shorter chunks so that a single 2 000-event slice is not one serial loop (72 us on MI355X) but eight waves side by side
     const int chunk = plan_pipeline_chunk(S, K);
-    std::vector<ChunkDesc> cds;
-    std::vector<int> slice_c0(B + 1);
-    std::vector<int64_t> slice_eb(B);
     for (int b = 0; b < B; b++) {
-        slice_c0[b] = (int)cds.size();
         const int64_t s = h_offsets[b], e = h_offsets[b + 1];
         if (e < s) return set_err(c, EORB_E_ARG, "ev_accumulate: offsets not monotone");
         if ((e - s) * dup >= (int64_t)1 << 31) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: %lld events in one slice", (long long)(e - s));
-        slice_eb[b] = (s - h_offsets[0]) * dup;                 // every event yields at most dup entries
-        for (int64_t k = s; k < e; k += chunk) {
-            ChunkDesc cd; cd.start = k; cd.n = (int32_t)std::min<int64_t>(chunk, e - k); cd.slice = b;
-            cds.push_back(cd);
-        }
     }
-    slice_c0[B] = (int)cds.size();
-    const int nchunks = (int)cds.size();
-    const size_t cd_bytes = sizeof(ChunkDesc) * (size_t)std::max(nchunks, 1);
-    const size_t sc_bytes = (sizeof(int) * (size_t)(B + 1) + 7) & ~(size_t)7;
-    const size_t eb_bytes = sizeof(int64_t) * (size_t)B;
-    const int nb = B * NT;
-    if ((rc = ensure(c, c->chunks, cd_bytes + sc_bytes + eb_bytes))) return rc;
-    // segcnt u16 [nchunks][NT] | segbase u32 [nchunks][NT]
-    const size_t cnt_bytes = (sizeof(uint16_t) * (size_t)std::max(nchunks, 1) * NT + 15) & ~(size_t)15;
-    if ((rc = ensure(c, c->segoff, cnt_bytes + sizeof(uint32_t) * (size_t)std::max(nchunks, 1) * NT))) return rc;
+    const HostBins hb = bin_chunks_host(h_offsets, B, chunk, EntryBaseRule{dup, 0, 1});      // every event yields at most dup entries
+    const int nchunks = (int)hb.nchunks;
+    BinLayout L(B, nchunks, NT);
+    const int nb = L.nb;
+    if ((rc = ensure(c, c->chunks, L.chunks_bytes()))) return rc;
+    if ((rc = ensure(c, c->segoff, L.segoff_bytes()))) return rc;
     const int esz = pol ? 4 : 2;
     if ((rc = ensure(c, c->entries, sizeof(float) * esz * (size_t)std::max<int64_t>(S.nev, 1) * dup + 64))) return rc;   // + slack: K2r reads entry 0 of an empty list
     // tile_cnt | tile_base | order
     if ((rc = ensure(c, c->tile_order, sizeof(uint32_t) * 3 * (size_t)nb))) return rc;
-    char* hp = (char*)pinned(c, cd_bytes + sc_bytes + eb_bytes);
-    if (!hp) return set_err(c, EORB_E_HIP, "pinned alloc failed");
-    if (nchunks) memcpy(hp, cds.data(), sizeof(ChunkDesc) * nchunks);
-    memcpy(hp + cd_bytes, slice_c0.data(), sizeof(int) * (size_t)(B + 1));
-    memcpy(hp + cd_bytes + sc_bytes, slice_eb.data(), eb_bytes);
-    EORB_HIP(c, hipMemcpyAsync(c->chunks.p, hp, cd_bytes + sc_bytes + eb_bytes, hipMemcpyHostToDevice, c->stream));
-    pinned_commit(c);
-    const ChunkDesc* d_chunks = (const ChunkDesc*)c->chunks.p;
-    const int* d_slice_c0 = (const int*)((char*)c->chunks.p + cd_bytes);
-    const int64_t* d_slice_eb = (const int64_t*)((char*)c->chunks.p + cd_bytes + sc_bytes);
-    uint16_t* d_segcnt = (uint16_t*)c->segoff.p;
-    uint32_t* d_segbase = (uint32_t*)((char*)c->segoff.p + cnt_bytes);
-    uint32_t* d_tile_cnt = (uint32_t*)c->tile_order.p;
-    uint32_t* d_tile_base = d_tile_cnt + nb;
+    if ((rc = bin_chunks_upload(c, L, hb, c->chunks.p, c->stream))) return rc;
+    L.view(c->chunks.p, c->segoff.p, c->tile_order.p);
+    const ChunkDesc* d_chunks = L.d_chunks;
+    const int* d_slice_c0 = L.d_slice_c0;
+    const int64_t* d_slice_eb = L.d_slice_eb;
+    uint16_t* d_segcnt = L.d_segcnt;
+    uint32_t* d_segbase = L.d_segbase;
+    uint32_t* d_tile_cnt = L.d_tile_cnt;
+    uint32_t* d_tile_base = L.d_tile_base;
     int32_t* d_order = (int32_t*)(d_tile_cnt + 2 * (size_t)nb);
 
     GatherParams G = ev_gather_params(W, H, S.h, S.TX, S.TY, NT, mode_count, nb, sigma);

@@ -6,11 +6,13 @@
 //   plan_bulk_eligible -> plan_bulk_fits -> plan_dict_usable -> (plan_slot_shaped, plan_tables_ahead while tabulating)
 //   -> plan_direct -> plan_slot_eligible -> plan_slot_shape -> (widen short records) -> plan_direct again -> plan_pipeline_chunk,
 //   plan_scatter2, plan_sparse_gather, plan_gather.
+// The slot form (ev_slots.hip) then asks plan_slot_binning once per call and plan_slot_gather once per part of the batch.
 // plan_first_route() is the same sequence without a device: the form a call takes when nothing declines at run time.
 #pragma once
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
 
 namespace eorb {
 
@@ -18,6 +20,9 @@ constexpr int kTile = 8;            // accumulation tile edge (one wavefront = 8
 constexpr int kChunk = 4096;        // events per binning chunk of the first scatter form (one wavefront bins one chunk)
 constexpr int kScatWaves = 8;       // wavefronts of ev_scatter2_kernel
 constexpr int kSlotScatWaves = 8;   // wavefronts of sl_scatter_kernel and of the 2 048-event rank scatter
+constexpr int kSlotCountWaves = 16; // wavefronts of sl_count_lds_kernel: one chunk each, one row of 16-bit tile counters each in LDS
+constexpr int kHotCap = 8192;       // lists per length bucket of sl_hot_kernel's work list
+constexpr int kHotRows = 240;       // rows sl_hot_kernel holds in registers: tile positions with more slots never go to it
 constexpr int kDdLog = 20;          // float events in bulk: the per-call position table has 2^20 rows; at most half may fill
 constexpr int kDirectSlices = 8;    // slices one launch of the binning-free form takes (the dispatcher sends it at most 4)
 constexpr int64_t kDirectMaxEvents = 16384;      // a call of up to this many events takes the binning-free form by its shape
@@ -53,7 +58,7 @@ struct AccumKnobs {
     int pd = 1;                              // 0: no position dictionary
     int scatter = 2;                         // 1: the list pipeline's first scatter form only
     int gather_threads = 512, gather_nc = 0; // ev_gather_kernel's workgroup; tile columns per value wave of ev_gather_raw_kernel (0: by size)
-    int slot_chunk = 0, slot_waves = 0, slot_rounds = 0, slot_count_lds = 1, slot_transcode = 1;
+    int slot_chunk = 0, slot_waves = 0, slot_rounds = 0;
     bool slot_rank = true;                   // the rank scatter may run (if the device check passed too)
     long long slot_hot_min = -1;             // -1: by the batch's size
     int slot_hot_cap = 0, slot_hot_waves = 0, slot_prerank = 1, slot_halves = -1;
@@ -213,6 +218,87 @@ inline bool plan_slot_scatter(const AccumShape& S, const AccumKnobs& K, bool ran
 inline bool plan_slot_shape(const AccumShape& S, int B, const AccumKnobs& K, bool rank_ok, SlotScatterChoice* out)
 {
     return !(B > 2048 || (size_t)S.NT * 4 > 64 * 1024 || !plan_slot_scatter(S, K, rank_ok, out));
+}
+
+// ---- the slot form's binning: which count pass runs, what it leaves for the scatter, which scatter reads it -----------------------
+enum { kCountGlobal, kCountLds, kCountLdsKeyed };      // sl_count_kernel | sl_count_lds_kernel<ST> | sl_count_lds_kernel<16, KEYED>
+enum { kRecAsIs, kRecShort2, kRecRanked8 };            // what the scatter reads: the count pass's own input records (with a dictionary: the
+                                                       // records it writes), a 2-byte sensor index per event, an 8-byte index + ranks per event
+enum { kScatBallot, kScatRank, kScatPre };             // sl_scatter_kernel | sl_scatter_rank_kernel<ST, NW> | sl_scatter_pre_kernel<NW>
+struct SlotBinPlan {
+    int count, record, scatter;
+    int stride, scat_stride;            // record stride the count pass / the rank and ballot scatters read (-4: 4-byte row numbers, else bytes)
+    size_t lds_count, lds_scatter;      // dynamic LDS of the two launches
+};
+// eorb_debug_counter "slot_binning"
+inline int slot_binning_code(const SlotBinPlan& p) { return p.count | p.record << 2 | p.scatter << 4; }
+
+// stride_in: 16 / 4 / 2-byte sensor records or -4 (row numbers of the per-call table); nsrc: positions of the set (the sensor's pixels);
+// dict: 0 none, 1 the count pass looks float events up in the position dictionary and writes 4-byte rows, 2: 2-byte ids.
+// false: a dictionary call whose tile-range table does not fit the LDS -- only the LDS count pass has the lookup.
+// The asymmetries, kept as they were:
+//  - ranked records are made for 16 / 4 / 2-byte sensor records and for 2-byte dictionary ids, never for 4-byte rows (stride -4 from
+//    either source): a ranked record holds a 16-bit position.
+//  - 2-byte transcoding is for 16-byte records only: 4- and 2-byte records are short already.  It is tied to sc.rank although the
+//    ballot scatter reads stride 2 as well (the ballot form is the fallback of a failed device check, left as plain as possible).
+//  - `nsrc <= 65535` is implied by lds_fits where the sensor is the image (8x8 tiles: NT >= nsrc / 64, so lds_c >= 2.5 nsrc and
+//    159 KiB hold 65 126 positions at most) and by dict == 2 (fewer than 65 535 ids).  It is kept: a sensor may be larger than the
+//    image, and a 16-bit index is what both record formats rest on.
+//  - the global count pass never leaves records: VGA-class sensors run count and scatter on the events as they came.
+//  - scat_stride is what the rank / ballot scatter reads; the pre-ranked scatter has one record format and ignores it (it keeps `stride`).
+inline bool plan_slot_binning(const AccumShape& S, int stride_in, int64_t nsrc, int dict, const SlotScatterChoice& sc, const AccumKnobs& K, SlotBinPlan* out)
+{
+    const int stride = dict ? (dict == 2 ? 2 : -4) : stride_in;
+    // the tile ranges of all positions (16 bits each, copied as dwords) + one row of counters per wavefront in the LDS of one workgroup per CU?
+    const size_t lds_c = 4 * (((size_t)nsrc + 2) / 2) + (size_t)kSlotCountWaves * S.NTp * 2;
+    const bool lds_fits = S.TX <= 127 && S.TY <= 127 && lds_c <= 159 * 1024;
+    const size_t lds_p = plan_slot_lds_pre(S.NT, sc.chunk);
+    const bool pre_fits = K.slot_prerank && sc.rank && lds_p <= 158 * 1024;
+    const int scat = sc.rank ? kScatRank : kScatBallot;
+    SlotBinPlan p{kCountLds, kRecAsIs, scat, stride, stride, lds_c, sc.lds};
+    if (dict) {
+        if (!lds_fits) return false;
+        p.count = kCountLdsKeyed;
+        if (pre_fits && dict == 2) { p.record = kRecRanked8; p.scatter = kScatPre; p.lds_scatter = lds_p; }
+    }
+    else if (!lds_fits) { p.count = kCountGlobal; p.lds_count = sizeof(uint32_t) * (size_t)S.NT; }
+    else if (pre_fits && (stride == 16 || stride == 4 || stride == 2) && nsrc <= 65535) { p.record = kRecRanked8; p.scatter = kScatPre; p.lds_scatter = lds_p; }
+    else if (stride == 16 && nsrc <= 65535 && sc.rank) { p.record = kRecShort2; p.scat_stride = 2; }
+    *out = p;
+    return true;
+}
+
+// ---- the slot form's gather: workgroup shape, task count, which lists go to the register-row kernel --------------------------------
+struct SlotGatherPlan {
+    size_t lds; int wg_per_cu, nw, rounds, Gt, max_per_tile;      // sl_gather_kernel: LDS, workgroups per CU, wavefronts, spare rounds, tasks, wavefronts a position gets at most
+    uint32_t prio_ref, hot_min, hot_cap; int hot_waves;          // lists this long go first | to sl_hot_kernel (0: that kernel is off) | per bucket; its wavefronts
+};
+// B, nev: slices and events of the PART (the batch, or a half of it); sl_null: most slots of a tile of these positions; ncu: compute units
+inline SlotGatherPlan plan_slot_gather(const AccumShape& S, int B, int64_t nev, int nparts, int sl_null, int ncu, const AccumKnobs& K)
+{
+    SlotGatherPlan g;
+    g.lds = (size_t)(sl_null + 1) * 256;
+    g.wg_per_cu = std::max(1, (int)((160 * 1024) / g.lds));
+    // four wavefronts per SIMD saturate the vector ALUs and leave every list about full single-wave speed (measured: 8 per SIMD
+    // process the same entries per second, each list at half the pace)
+    g.nw = std::min(16, std::max(1, 16 / g.wg_per_cu));
+    if (K.slot_waves >= 1 && K.slot_waves <= 16) g.nw = K.slot_waves;
+    g.nw = std::min(g.nw, std::max(1, B));
+    // one task per tile position plus a few rounds of spare ones shared out by weight; a position never gets more wavefronts than slices
+    g.rounds = K.slot_rounds >= 1 ? K.slot_rounds : 4;
+    g.Gt = S.NT + g.rounds * ncu * g.wg_per_cu;
+    g.max_per_tile = (B + g.nw - 1) / g.nw;
+    g.prio_ref = (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, nev / 2000), 0x7fffffff);   // lists this long go first at the issue arbiter
+    // lists of a few thousand entries or more go to the register-row kernel (when every tile's rows fit its 240 registers): 13
+    // cycles per entry instead of 29, which shortens the launch's longest chains AND moves more entries per second; shorter lists
+    // would not repay the 240 row loads per list (measured at 128 x 1 Mev: threshold 4 096 ... 8 192 1.40-1.45 ms, 16 384 1.53, none 2.44)
+    g.hot_min = sl_null <= kHotRows ? (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, nev * nparts / 16000), 0x7fffffff) : 0u;
+    const long long hot_over = K.slot_hot_min;
+    // (never below 64: the register-row kernel's tail load reads the 64 bytes that END at the list's end; 0 = that kernel off)
+    if (hot_over >= 0) g.hot_min = (sl_null <= kHotRows && hot_over > 0) ? (uint32_t)std::min<long long>(std::max<long long>(hot_over, 64), 0x7fffffff) : 0u;
+    g.hot_cap = K.slot_hot_cap > 0 ? (uint32_t)std::min(K.slot_hot_cap, kHotCap) : (uint32_t)kHotCap;
+    g.hot_waves = K.slot_hot_waves > 0 ? K.slot_hot_waves : 8 * ncu;     // two per SIMD: all of its registers
+    return g;
 }
 
 // ---- the whole sequence, without a device: the route of a call that nothing declines at run time ----------------------------------

@@ -33,7 +33,6 @@
 #include "dev_math.h"
 #include "sl_hot_asm.h"
 #include <algorithm>
-#include <memory>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -46,7 +45,6 @@ constexpr uint32_t kNoSlot = 0xffu;
 typedef uint16_t slot_entry;
 constexpr uint32_t kEntryTag = 0x1000u;
 constexpr uint16_t kNoGeo = 0xffffu;           // (tile 127,127 with a second tile: never a valid range, TX and TY <= 127 there)
-constexpr int kCountWaves = 16;
 
 // ---- tables ---------------------------------------------------------------------------------------------------------------------
 // Tile range of a sensor pixel = tiles that hold an IN-IMAGE pixel of its stamp (:250 `if (isInImage)`): every entry of a list
@@ -151,7 +149,8 @@ __global__ __launch_bounds__(256) void sl_rows_kernel(const uint32_t* __restrict
 }
 
 // ---- K0: the chunk descriptors, the slices' first chunks and entry bases, from the slice offsets (a kernel argument: no staging
-// buffer, no host-to-device copy in front of the count pass).  Same arithmetic as the host loop of ev_slots_accumulate. ----
+// buffer, no host-to-device copy in front of the count pass).  Same arithmetic as bin_chunks_host (ev_common.h) with the slot
+// form's entry-base rule. ----
 constexpr int kOffsetsInArg = 256;
 struct SliceOffsets { int64_t off[kOffsetsInArg + 1]; };
 __global__ __launch_bounds__(256) void sl_chunks_kernel(SliceOffsets S, int B, int chunk_shift /* chunks are 2^shift events */, int NT, int nchunks,
@@ -264,7 +263,7 @@ __device__ __forceinline__ uint32_t sl_dict_hash(uint64_t k)
 // the chunk's (tile) run.  It goes out with the sensor index as one 8-byte record { index : 16, rank of the event's tile of class j :
 // 12 bits each }: the scatter (sl_scatter_pre_kernel) then neither counts nor ranks again -- its two most expensive phases.
 template <int stride, bool KEYED = false, bool RANKS = false>
-__global__ __launch_bounds__(64 * kCountWaves) void sl_count_lds_kernel(const eorb_raw_event* __restrict__ ev, const ChunkDesc* __restrict__ chunks,
+__global__ __launch_bounds__(64 * kSlotCountWaves) void sl_count_lds_kernel(const eorb_raw_event* __restrict__ ev, const ChunkDesc* __restrict__ chunks,
                                                                        int nchunks, const uint16_t* __restrict__ slot_geo, int LW, int LH,
                                                                        int TX, int NT, uint16_t* __restrict__ segcnt, SlotDict D = SlotDict{nullptr, 0u, nullptr, nullptr, 0},
                                                                        uint16_t* __restrict__ rec16 = nullptr)
@@ -272,14 +271,14 @@ __global__ __launch_bounds__(64 * kCountWaves) void sl_count_lds_kernel(const eo
     extern __shared__ uint32_t smc[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ntab = (LW * LH + 2) >> 1, NTp = (NT + 1) & ~1;
-    for (int i = tid; i < ntab; i += 64 * kCountWaves) smc[i] = ((const uint32_t*)slot_geo)[i];
+    for (int i = tid; i < ntab; i += 64 * kSlotCountWaves) smc[i] = ((const uint32_t*)slot_geo)[i];
     const uint16_t* tab = (const uint16_t*)smc;
     uint32_t* cnt = smc + ntab + wave * (NTp >> 1);
     __syncthreads();
     constexpr int astride = stride < 0 ? -stride : stride;
     const uint32_t xmask = stride == 4 ? 0x7fffu : 0xffffu;
     constexpr int U = 8;
-    for (int ch = blockIdx.x * kCountWaves + wave; ch < nchunks; ch += gridDim.x * kCountWaves) {
+    for (int ch = blockIdx.x * kSlotCountWaves + wave; ch < nchunks; ch += gridDim.x * kSlotCountWaves) {
         const ChunkDesc cd = chunks[ch];
         for (int i = lane; i < (NTp >> 1); i += 64) cnt[i] = 0u;
         const unsigned char* e = (const unsigned char*)ev + (size_t)cd.start * (size_t)astride;
@@ -844,7 +843,8 @@ __global__ __launch_bounds__(1024) void sl_rankcheck_kernel(unsigned long long* 
 // { slice, tile, entries, list offset (2), tile x0, tile y0, byte offset of the tile's rows } lands in one of 16 buckets by length
 // (bucket 0 = longest: the hot kernel takes them in that order), and the position's own list carries it with the top bit of the slice
 // set, for the gather to skip.
-constexpr int kHotBuckets = 16, kHotCap = 8192;
+constexpr int kHotBuckets = 16;
+static_assert(kHotRows == SL_HOT_NROWS, "plan_slot_gather (ev_plan.h) and sl_hot_kernel's register rows");
 struct HotDesc { uint32_t slice, tile, cnt, off_lo, off_hi, tx0, ty0, rows_off; };
 __global__ __launch_bounds__(256) void sl_plan_kernel(const uint32_t* __restrict__ tile_cnt, const uint32_t* __restrict__ tile_base,
                                                       const int64_t* __restrict__ slice_ebase, int B, int NT, int TX, uint32_t hot_min,
@@ -1226,12 +1226,13 @@ int ev_slots_prepare(eorb_ctx* c, PosTables& T, int W, int H, int h, int TX, int
     return ev_slots_prepare_finish(c, T, W, H, h, TX, TY, d_stamps, stamp_stride, SWP, two_sig2, norm);
 }
 
-// dynamic-LDS opt-in of one kernel instantiation, once per CONTEXT (= per device: a second context may sit on another GPU)
-static int sl_optin(eorb_ctx* c, int bit, const void* fn, int bytes)
+// dynamic-LDS opt-in of one kernel instantiation, keyed by the kernel's address, once per CONTEXT (= per device: a second context may
+// sit on another GPU)
+static int sl_optin(eorb_ctx* c, const void* fn, int bytes)
 {
-    if (c->sl_attr & (1u << bit)) return EORB_OK;
+    if (std::find(c->sl_optins.begin(), c->sl_optins.end(), fn) != c->sl_optins.end()) return EORB_OK;
     EORB_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    c->sl_attr |= 1u << bit;
+    c->sl_optins.push_back(fn);
     return EORB_OK;
 }
 static int sl_ncu(eorb_ctx* c)
@@ -1266,237 +1267,216 @@ static int sl_streams(eorb_ctx* c)
     return EORB_OK;
 }
 
-// count -> scan -> scatter -> plan -> gather for the B slices of one PART of a batch (the whole batch, or one of its halves), on the
-// part's own workspaces.  Streams: binning on the context's stream; the plan on P; the long lists on H; the LDS gather on G when the
-// batch runs in halves (so that the next half's binning, HBM- and LDS-atomic-bound, runs under it), else on the context's stream.
-static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int part, int nparts, const void* d_events, int stride_in, const int64_t* h_offsets, int B,
-                      int W, int H, int TX, int TY, float* d_f32, uint32_t* d_minmax_enc, const SlotScatterChoice& sc, const SlotDict* dict, const AccumKnobs& K)
+// ---- which instantiation serves a stage: (variant, record stride[, wavefronts]) -> kernel ----
+using SlCountLdsFn = decltype(&sl_count_lds_kernel<16>);
+using SlCountFn = decltype(&sl_count_kernel<16>);
+using SlScatPreFn = decltype(&sl_scatter_pre_kernel<16>);
+using SlScatRankFn = decltype(&sl_scatter_rank_kernel<16, 16>);
+// (if-chains, one return per instantiation: the order of first mention is the order of the kernels in the code object)
+static SlCountLdsFn sl_count_lds_fn(const SlotBinPlan& bp)
 {
-    // with a position dictionary the count pass reads the float events and writes the hashed records every later pass reads
-    const int stride = dict ? (dict->rec2 ? 2 : -4) : stride_in;
-    const int NT = TX * TY;
-    const int64_t nev = h_offsets[B] - h_offsets[0];
-    const int chunk = sc.chunk;
-    hipStream_t M = c->stream, P = c->sl_pstream, Hs = c->sl_side, G = nparts > 1 ? c->sl_gstream : c->stream;
-    hipEvent_t* E = c->sl_ev + 5 * part;             // fork (scan done), plan, scat, hot done, gather done
-    // up to 256 slices: the descriptors are made on the device from the offsets (sl_chunks_kernel); more: on the host, one copy
-    const bool on_dev = B <= kOffsetsInArg;
-    std::vector<ChunkDesc> cds;
-    std::vector<int> slice_c0(on_dev ? 0 : B + 1);
-    std::vector<int64_t> slice_eb(on_dev ? 0 : B + 1);
-    int64_t eb = 0, nch = 0;
-    for (int b = 0; b < B; b++) {
-        if (!on_dev) slice_c0[b] = (int)nch;
-        const int64_t s = h_offsets[b], e = h_offsets[b + 1];
-        if (!on_dev) slice_eb[b] = eb;
-        eb = (eb + (e - s) * 4 + (int64_t)NT * 16 + 15) & ~(int64_t)15;   // <= 4 entries per event, every list rounded up to 16
-        nch += (e - s + chunk - 1) / chunk;
-        if (!on_dev)
-            for (int64_t k = s; k < e; k += chunk) {
-                ChunkDesc cd; cd.start = k; cd.n = (int32_t)std::min<int64_t>(chunk, e - k); cd.slice = b;
-                cds.push_back(cd);
-            }
+    const bool ranks = bp.record == kRecRanked8;
+    if (bp.count == kCountLdsKeyed) {                // (reads the float events: 16 bytes)
+        if (ranks) return sl_count_lds_kernel<16, true, true>;
+        return sl_count_lds_kernel<16, true>;
     }
-    if (nch >= (int64_t)1 << 31) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: too many chunks");
-    if (!on_dev) { slice_c0[B] = (int)nch; slice_eb[B] = eb; }
-    const int nchunks = (int)nch;
-    const size_t cd_bytes = sizeof(ChunkDesc) * (size_t)std::max(nchunks, 1);
-    const size_t sc_bytes = (sizeof(int) * (size_t)(B + 1) + 7) & ~(size_t)7;
-    const size_t eb_bytes = sizeof(int64_t) * (size_t)B;
-    const int nb = B * NT;
-    c->sl_last_nb[part] = nb;
+    if (ranks) {
+        if (bp.stride == 16) return sl_count_lds_kernel<16, false, true>;
+        if (bp.stride == 4) return sl_count_lds_kernel<4, false, true>;
+        return sl_count_lds_kernel<2, false, true>;
+    }
+    if (bp.stride == 16) return sl_count_lds_kernel<16>;
+    if (bp.stride == 4) return sl_count_lds_kernel<4>;
+    if (bp.stride == 2) return sl_count_lds_kernel<2>;
+    return sl_count_lds_kernel<-4>;
+}
+static SlCountFn sl_count_fn(int stride)
+{
+    if (stride == 16) return sl_count_kernel<16>;
+    if (stride == 4) return sl_count_kernel<4>;
+    if (stride == 2) return sl_count_kernel<2>;
+    return sl_count_kernel<-4>;
+}
+static SlScatPreFn sl_scatter_pre_fn(int waves)
+{
+    if (waves == 16) return sl_scatter_pre_kernel<16>;
+    return sl_scatter_pre_kernel<8>;
+}
+static SlScatRankFn sl_scatter_rank_fn(int stride, int waves)
+{
+    if (waves == 16) {
+        if (stride == 16) return sl_scatter_rank_kernel<16, 16>;
+        if (stride == 4) return sl_scatter_rank_kernel<4, 16>;
+        if (stride == 2) return sl_scatter_rank_kernel<2, 16>;
+        return sl_scatter_rank_kernel<-4, 16>;
+    }
+    if (stride == 16) return sl_scatter_rank_kernel<16, 8>;
+    if (stride == 4) return sl_scatter_rank_kernel<4, 8>;
+    if (stride == 2) return sl_scatter_rank_kernel<2, 8>;
+    return sl_scatter_rank_kernel<-4, 8>;
+}
+
+// One PART of a batch (the whole batch, or one of its halves): its B slices on the part's own workspaces.  Streams: binning on the
+// context's stream M; the gather's plan on P; the long lists on H; the LDS gather on G when the batch runs in halves (so that the next
+// half's binning, HBM- and LDS-atomic-bound, runs under it), else on M.  Events: fork (scan done), plan, scat, hot done, gather done.
+struct SlotPart {
+    eorb_ctx* c; const PosTables& T; eorb_ctx::SlotWS& ws;
+    const void* d_events; const SlotDict* dict; const int64_t* h_offsets; int B, W, H, TX, TY, NT, ncu;
+    float* d_f32; uint32_t* d_minmax_enc;
+    SlotScatterChoice sc; SlotBinPlan bp; SlotGatherPlan gp; BinLayout L;
+    hipStream_t M, P, Hs, G; hipEvent_t* E;
+    // the tables of the positions
+    const uint2* d_tab() const { return (const uint2*)T.sl_tab.p; }
+    const uint16_t* d_geo() const { return (const uint16_t*)((const char*)T.sl_tab.p + sizeof(uint2) * (size_t)T.w * (size_t)T.h); }
+    uint32_t* d_nslots() const { return (uint32_t*)T.sl_tile.p; }
+    uint32_t* d_rowbase() const { return d_nslots() + NT; }
+    int* d_info() const { return (int*)(d_nslots() + 5 * (size_t)NT); }
+    // ws.plan: items | task table | longest lists | scratch (2 NT) | tile weights | tickets
+    size_t plan_bytes() const { return sizeof(uint4) * (size_t)L.nb + sizeof(uint32_t) * ((size_t)gp.Gt + 5 * (size_t)NT); }
+    uint4* d_items() const { return (uint4*)ws.plan.p; }
+    uint32_t* d_task() const { return (uint32_t*)(d_items() + L.nb); }
+    uint32_t* d_tile_m() const { return d_task() + gp.Gt; }
+    uint32_t* d_scr() const { return d_tile_m() + NT; }
+    uint32_t* d_tile_w() const { return d_scr() + 2 * (size_t)NT; }
+    uint32_t* d_ctr() const { return d_tile_w() + NT; }
+    // ws.hot: 16 bucket counts | ticket (at word 32) | overflow count (33) | descriptors (from byte 256)
+    uint32_t* d_hot_cnt() const { return (uint32_t*)ws.hot.p; }
+    HotDesc* d_hot_items() const { return (HotDesc*)((char*)ws.hot.p + 256); }
+    slot_entry* d_entries() const { return (slot_entry*)ws.entries.p; }
+};
+
+// ---- stage 1, the layout: every buffer of the part is sized and allocated before anything of the part is launched; then the chunk
+// descriptors -- up to 256 slices: made on the device from the offsets (sl_chunks_kernel); more: on the host, one copy ----
+static int slots_layout(SlotPart& p)
+{
+    eorb_ctx* c = p.c; eorb_ctx::SlotWS& ws = p.ws;
+    const int B = p.B, NT = p.NT, chunk = p.sc.chunk;
+    const bool on_dev = B <= kOffsetsInArg;
+    const HostBins hb = bin_chunks_host(p.h_offsets, B, chunk, EntryBaseRule{4, (int64_t)NT * 16, 16}, !on_dev);   // <= 4 entries per event, every list rounded up to 16
+    if (hb.nchunks >= (int64_t)1 << 31) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: too many chunks");
+    p.L = BinLayout(B, (int)hb.nchunks, NT);
+    const BinLayout& L = p.L;
     int rc;
-    if ((rc = ensure(c, ws.chunks, cd_bytes + sc_bytes + eb_bytes))) return rc;
-    const size_t cnt_bytes = (sizeof(uint16_t) * (size_t)std::max(nchunks, 1) * NT + 15) & ~(size_t)15;
-    if ((rc = ensure(c, ws.segoff, cnt_bytes + sizeof(uint32_t) * (size_t)std::max(nchunks, 1) * NT))) return rc;
-    if ((rc = ensure(c, ws.entries, sizeof(slot_entry) * (size_t)eb + 8192))) return rc;      // + slack: the gather requests blocks past a list's end
-    if ((rc = ensure(c, ws.tile_order, sizeof(uint32_t) * 2 * (size_t)nb))) return rc;
+    if ((rc = ensure(c, ws.chunks, L.chunks_bytes()))) return rc;
+    if ((rc = ensure(c, ws.segoff, L.segoff_bytes()))) return rc;
+    if ((rc = ensure(c, ws.entries, sizeof(slot_entry) * (size_t)hb.entries + 8192))) return rc;      // + slack: the gather requests blocks past a list's end
+    if ((rc = ensure(c, ws.tile_order, sizeof(uint32_t) * 2 * (size_t)L.nb))) return rc;
+    if ((rc = ensure(c, ws.plan, p.plan_bytes()))) return rc;
+    if ((rc = ensure(c, ws.hot, sizeof(HotDesc) * (size_t)kHotBuckets * kHotCap + 256))) return rc;
+    // the record per event the count pass leaves for the scatter (indexed like the events: from the batch's first)
+    if (p.bp.record != kRecAsIs && (rc = ensure(c, ws.rec16, (p.bp.record == kRecRanked8 ? sizeof(uint64_t) : sizeof(uint16_t)) * (size_t)std::max<int64_t>(p.h_offsets[B], 1)))) return rc;
+#ifdef EORB_SLOT_TRACE
+    if ((rc = ensure(c, c->sl_trace, sizeof(unsigned long long) * 6 * 16 * (size_t)p.gp.Gt + 64))) return rc;
+#endif
     if (on_dev) {
         SliceOffsets so;
-        for (int b = 0; b <= B; b++) so.off[b] = h_offsets[b];
-        sl_chunks_kernel<<<std::max(1, (nchunks + 255) / 256), 256, 0, M>>>(so, B, chunk == 4096 ? 12 : (chunk == 2048 ? 11 : (chunk == 1024 ? 10 : 8)), NT, nchunks, (ChunkDesc*)ws.chunks.p, (int*)((char*)ws.chunks.p + cd_bytes),
-                                                                                  (int64_t*)((char*)ws.chunks.p + cd_bytes + sc_bytes));
+        for (int b = 0; b <= B; b++) so.off[b] = p.h_offsets[b];
+        sl_chunks_kernel<<<std::max(1, (L.nchunks + 255) / 256), 256, 0, p.M>>>(so, B, chunk == 4096 ? 12 : (chunk == 2048 ? 11 : (chunk == 1024 ? 10 : 8)), NT, L.nchunks, (ChunkDesc*)ws.chunks.p,
+                                                                                 (int*)((char*)ws.chunks.p + L.cd), (int64_t*)((char*)ws.chunks.p + L.cd + L.sc));
     }
-    else {
-        char* hp = (char*)pinned(c, cd_bytes + sc_bytes + eb_bytes);
-        if (!hp) return set_err(c, EORB_E_HIP, "pinned alloc failed");
-        if (nchunks) memcpy(hp, cds.data(), sizeof(ChunkDesc) * nchunks);
-        memcpy(hp + cd_bytes, slice_c0.data(), sizeof(int) * (size_t)(B + 1));
-        memcpy(hp + cd_bytes + sc_bytes, slice_eb.data(), eb_bytes);
-        EORB_HIP(c, hipMemcpyAsync(ws.chunks.p, hp, cd_bytes + sc_bytes + eb_bytes, hipMemcpyHostToDevice, M));
-        pinned_commit(c);
-    }
-    const ChunkDesc* d_chunks = (const ChunkDesc*)ws.chunks.p;
-    const int* d_slice_c0 = (const int*)((char*)ws.chunks.p + cd_bytes);
-    const int64_t* d_slice_eb = (const int64_t*)((char*)ws.chunks.p + cd_bytes + sc_bytes);
-    uint16_t* d_segcnt = (uint16_t*)ws.segoff.p;
-    uint32_t* d_segbase = (uint32_t*)((char*)ws.segoff.p + cnt_bytes);
-    uint32_t* d_tile_cnt = (uint32_t*)ws.tile_order.p;
-    uint32_t* d_tile_base = d_tile_cnt + nb;
-    uint32_t* d_nslots = (uint32_t*)T.sl_tile.p;
-    uint32_t* d_rowbase = d_nslots + NT;
-    int* d_info = (int*)(d_nslots + 5 * (size_t)NT);
-    const eorb_raw_event* d_ev = dict ? (const eorb_raw_event*)dict->rec : (const eorb_raw_event*)d_events;
-    int scat_stride = stride;
-    bool prerank = false;                             // the count pass left ranked 8-byte records: sl_scatter_pre_kernel
-    const uint2* d_tab = (const uint2*)T.sl_tab.p;
-    const int ncu = sl_ncu(c);
-    const int NTp = (NT + 1) & ~1;
-    // ---- the gather's plan: sizes first (its buffers are allocated before anything of the part is launched) ----
-    const size_t lds_g = (size_t)(T.sl_null + 1) * 256;
-    const int wg_per_cu = std::max(1, (int)((160 * 1024) / lds_g));
-    // four wavefronts per SIMD saturate the vector ALUs and leave every list about full single-wave speed (measured: 8 per SIMD
-    // process the same entries per second, each list at half the pace)
-    int nw = std::min(16, std::max(1, 16 / wg_per_cu));
-    if (K.slot_waves >= 1 && K.slot_waves <= 16) nw = K.slot_waves;
-    nw = std::min(nw, std::max(1, B));
-    // one task per tile position plus a few rounds of spare ones shared out by weight; a position never gets more wavefronts than slices
-    const int rounds = K.slot_rounds >= 1 ? K.slot_rounds : 4;
-    const int Gt = NT + rounds * ncu * wg_per_cu;
-    const int max_per_tile = (B + nw - 1) / nw;
-    // items | task table | longest lists | scratch (2 NT) | tile weights | tickets
-    if ((rc = ensure(c, ws.plan, sizeof(uint4) * (size_t)nb + sizeof(uint32_t) * ((size_t)Gt + 5 * (size_t)NT)))) return rc;
-    uint4* d_items = (uint4*)ws.plan.p;
-    uint32_t* d_task = (uint32_t*)(d_items + nb);
-    uint32_t* d_tile_m = d_task + Gt;
-    uint32_t* d_scr = d_tile_m + NT;
-    uint32_t* d_tile_w = d_scr + 2 * (size_t)NT;
-    uint32_t* d_ctr = d_tile_w + NT;
-    const uint32_t prio_ref = (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, nev / 2000), 0x7fffffff);   // lists this long go first at the issue arbiter
-    // lists of a few thousand entries or more go to the register-row kernel (when every tile's rows fit its 240 registers): 13
-    // cycles per entry instead of 29, which shortens the launch's longest chains AND moves more entries per second; shorter lists
-    // would not repay the 240 row loads per list (measured at 128 x 1 Mev: threshold 4 096 ... 8 192 1.40-1.45 ms, 16 384 1.53, none 2.44)
-    uint32_t hot_min = T.sl_null <= SL_HOT_NROWS ? (uint32_t)std::min<int64_t>(std::max<int64_t>(4096, nev * nparts / 16000), 0x7fffffff) : 0u;
-    const long long hot_over = K.slot_hot_min;
-    // (never below 64: the register-row kernel's tail load reads the 64 bytes that END at the list's end; 0 = that kernel off)
-    if (hot_over >= 0) hot_min = (T.sl_null <= SL_HOT_NROWS && hot_over > 0) ? (uint32_t)std::min<long long>(std::max<long long>(hot_over, 64), 0x7fffffff) : 0u;
-    const uint32_t hot_cap = K.slot_hot_cap > 0 ? (uint32_t)std::min(K.slot_hot_cap, kHotCap) : (uint32_t)kHotCap;
-    if ((rc = ensure(c, ws.hot, sizeof(HotDesc) * (size_t)kHotBuckets * kHotCap + 256))) return rc;
-    uint32_t* d_hot_cnt = (uint32_t*)ws.hot.p;                           // 16 bucket counts | ticket (at word 32) | overflow count (33) | descriptors (from byte 256)
-    HotDesc* d_hot_items = (HotDesc*)((char*)ws.hot.p + 256);
+    else if ((rc = bin_chunks_upload(c, L, hb, ws.chunks.p, p.M))) return rc;
+    p.L.view(ws.chunks.p, ws.segoff.p, ws.tile_order.p);
+    return EORB_OK;
+}
+
+// ---- stage 2, the binning, from the SlotBinPlan: count -> scan (one profile scope per kernel), then -- behind the fork of the
+// gather's plan, slots_fork_plan -- the scatter ----
+static int slots_count_scan(const SlotPart& p)
+{
+    eorb_ctx* c = p.c; const PosTables& T = p.T; const BinLayout& L = p.L; const SlotBinPlan& bp = p.bp;
+    int rc;
     {
-        std::unique_ptr<ProfScope> ps(new ProfScope(c, "ev_count"));      // (one scope per kernel of the binning: count, scan, scatter)
-        const size_t lds = sizeof(uint32_t) * (size_t)NT;
-        // the tile ranges of all sensor pixels + one set of counters per wavefront in the LDS of one workgroup per CU?
-        const size_t nsrc = (size_t)T.w * (size_t)T.h;
-        const size_t lds_c = 4 * ((nsrc + 2) / 2) + (size_t)kCountWaves * NTp * 2;
-        if (dict && !(TX <= 127 && TY <= 127 && lds_c <= 159 * 1024)) return set_err(c, EORB_E_CAPACITY, "slot form: the position dictionary needs the LDS count pass");
-        if (nchunks && dict) {
-            const uint16_t* d_geo = (const uint16_t*)((const char*)T.sl_tab.p + sizeof(uint2) * nsrc);
-            const int g = std::min(ncu, (nchunks + kCountWaves - 1) / kCountWaves);
-            if (K.slot_prerank && dict->rec2 && sc.rank && plan_slot_lds_pre(NT, chunk) <= 158 * 1024) {
-                // (the dense ids are 16-bit: the ranked 8-byte record serves the dictionary path too)
-                if ((rc = ensure(c, ws.rec16, sizeof(uint64_t) * (size_t)std::max<int64_t>(h_offsets[B], 1)))) return rc;
-                prerank = true;
-                if ((rc = sl_optin(c, 21, (const void*)sl_count_lds_kernel<16, true, true>, 159 * 1024))) return rc;
-                sl_count_lds_kernel<16, true, true><<<g, 64 * kCountWaves, lds_c, M>>>((const eorb_raw_event*)d_events, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, *dict, (uint16_t*)ws.rec16.p);
-            } else {
-            if ((rc = sl_optin(c, 13, (const void*)sl_count_lds_kernel<16, true>, 159 * 1024))) return rc;
-            sl_count_lds_kernel<16, true><<<g, 64 * kCountWaves, lds_c, M>>>((const eorb_raw_event*)d_events, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, *dict);
-            }
+        ProfScope ps(c, "ev_count");
+        if (L.nchunks && bp.count == kCountGlobal) {
+            const SlCountFn fn = sl_count_fn(bp.stride);
+            fn<<<L.nchunks, 256, bp.lds_count, p.M>>>((const eorb_raw_event*)p.d_events, L.d_chunks, p.d_tab(), T.w, T.h, p.TX, p.NT, L.d_segcnt);
         }
-        else if (nchunks && K.slot_count_lds && TX <= 127 && TY <= 127 && lds_c <= 159 * 1024) {
-            const uint16_t* d_geo = (const uint16_t*)((const char*)T.sl_tab.p + sizeof(uint2) * nsrc);
-            const int g = std::min(ncu, (nchunks + kCountWaves - 1) / kCountWaves);
-            // 16-byte records on a sensor of at most 65 535 pixels: the pass leaves a 2-byte record per event for the scatter
-            uint16_t* d_rec16 = nullptr;
-            // ... or, where the rank scatter would run: an 8-byte record that also carries the ranks of the event's entries in the
-            // chunk's runs (the values the counting atomics return), so that the scatter neither counts nor ranks (sl_scatter_pre_kernel)
-            if (K.slot_prerank && (stride == 16 || stride == 4 || stride == 2) && nsrc <= 65535 && sc.rank && plan_slot_lds_pre(NT, chunk) <= 158 * 1024) {
-                if ((rc = ensure(c, ws.rec16, sizeof(uint64_t) * (size_t)std::max<int64_t>(h_offsets[B], 1)))) return rc;
-                d_rec16 = (uint16_t*)ws.rec16.p;
-                prerank = true;
-#define SL_COUNTR(ST, BIT) do { if ((rc = sl_optin(c, BIT, (const void*)sl_count_lds_kernel<ST, false, true>, 159 * 1024))) return rc; \
-                sl_count_lds_kernel<ST, false, true><<<g, 64 * kCountWaves, lds_c, M>>>(d_ev, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, SlotDict{nullptr, 0u, nullptr, nullptr, 0}, d_rec16); } while (0)
-                if (stride == 16) SL_COUNTR(16, 18); else if (stride == 4) SL_COUNTR(4, 19); else SL_COUNTR(2, 20);
-#undef SL_COUNTR
-            }
-            else {
-            if (K.slot_transcode && stride == 16 && nsrc <= 65535 && sc.rank) {
-                if ((rc = ensure(c, ws.rec16, sizeof(uint16_t) * (size_t)std::max<int64_t>(h_offsets[B], 1)))) return rc;
-                d_rec16 = (uint16_t*)ws.rec16.p;
-            }
-#define SL_COUNT(ST, BIT) do { if ((rc = sl_optin(c, BIT, (const void*)sl_count_lds_kernel<ST>, 159 * 1024))) return rc; \
-                sl_count_lds_kernel<ST><<<g, 64 * kCountWaves, lds_c, M>>>(d_ev, d_chunks, nchunks, d_geo, T.w, T.h, TX, NT, d_segcnt, SlotDict{nullptr, 0u, nullptr, nullptr}, d_rec16); } while (0)
-            if (stride == 16) SL_COUNT(16, 0); else if (stride == 4) SL_COUNT(4, 1); else if (stride == 2) SL_COUNT(2, 10); else SL_COUNT(-4, 2);
-#undef SL_COUNT
-            if (d_rec16) { d_ev = (const eorb_raw_event*)d_rec16; scat_stride = 2; }
-            }
+        else if (L.nchunks) {
+            // the tile ranges of all positions + one set of counters per wavefront in the LDS of one workgroup per CU; with a dictionary
+            // the pass reads the float events and writes the records every later pass reads
+            const SlCountLdsFn fn = sl_count_lds_fn(bp);
+            if ((rc = sl_optin(c, (const void*)fn, 159 * 1024))) return rc;
+            fn<<<std::min(p.ncu, (L.nchunks + kSlotCountWaves - 1) / kSlotCountWaves), 64 * kSlotCountWaves, bp.lds_count, p.M>>>(
+                (const eorb_raw_event*)p.d_events, L.d_chunks, L.nchunks, p.d_geo(), T.w, T.h, p.TX, p.NT, L.d_segcnt,
+                p.dict ? *p.dict : SlotDict{nullptr, 0u, nullptr, nullptr, 0}, bp.record != kRecAsIs ? (uint16_t*)p.ws.rec16.p : nullptr);
         }
-        else if (nchunks) {
-            if (stride == 16) sl_count_kernel<16><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, d_segcnt);
-            else if (stride == 4) sl_count_kernel<4><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, d_segcnt);
-            else if (stride == 2) sl_count_kernel<2><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, d_segcnt);
-            else sl_count_kernel<-4><<<nchunks, 256, lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, d_segcnt);
+    }
+    ProfScope ps(c, "ev_scan");
+    sl_scan_kernel<<<p.B, 1024, 0, p.M>>>(L.d_slice_c0, L.d_segcnt, p.NT, L.d_segbase, L.d_tile_cnt, L.d_tile_base);
+    return EORB_OK;
+}
+
+static int slots_scatter(const SlotPart& p)
+{
+    eorb_ctx* c = p.c; const PosTables& T = p.T; const BinLayout& L = p.L; const SlotBinPlan& bp = p.bp;
+    const int chunk = p.sc.chunk, waves = p.sc.waves;
+    // what the count pass left: the dictionary's records, the 2-byte transcoded records, or the events as they came
+    const eorb_raw_event* d_ev = p.dict ? (const eorb_raw_event*)p.dict->rec : (const eorb_raw_event*)(bp.record == kRecShort2 ? p.ws.rec16.p : p.d_events);
+    int rc;
+    {
+        ProfScope ps(c, "ev_scatter");
+        if (L.nchunks && bp.scatter == kScatPre) {
+            const SlScatPreFn fn = sl_scatter_pre_fn(waves);
+            if ((rc = sl_optin(c, (const void*)fn, 159 * 1024))) return rc;
+            fn<<<L.nchunks, 64 * waves, bp.lds_scatter, p.M>>>((const uint64_t*)p.ws.rec16.p, L.d_chunks, p.d_tab(), T.w * T.h, p.TX, p.NT, chunk, L.d_slice_eb, L.d_segcnt, L.d_segbase,
+                                                               L.d_tile_base, p.d_entries());
         }
-        ps.reset(); ps.reset(new ProfScope(c, "ev_scan"));
-        sl_scan_kernel<<<B, 1024, 0, M>>>(d_slice_c0, d_segcnt, NT, d_segbase, d_tile_cnt, d_tile_base);
-        ps.reset();
-        // ---- the gather's plan needs the scan's counts only: it runs on its own stream BESIDE the scatter (50 us of single-block
-        //      kernels off the critical path) ----
-        EORB_HIP(c, hipEventRecord(E[0], M));
-        EORB_HIP(c, hipStreamWaitEvent(P, E[0], 0));
-        EORB_HIP(c, hipMemsetAsync(ws.hot.p, 0, 256, P));
-        sl_plan_kernel<<<NT, 256, sizeof(uint32_t) * 2 * (size_t)B, P>>>(d_tile_cnt, d_tile_base, d_slice_eb, B, NT, TX, hot_min, d_nslots, d_rowbase,
-                                                                               d_items, d_tile_w, d_tile_m, d_ctr, d_hot_cnt, d_hot_items, hot_cap);
-        sl_tasks_kernel<<<1, 1024, sizeof(uint32_t) * (size_t)NT, P>>>(d_tile_w, d_tile_m, NT, Gt, max_per_tile, d_scr, d_task, d_hot_cnt, hot_cap);
-        EORB_HIP(c, hipEventRecord(E[1], P));
-        // ---- the scatter (form and chunk size chosen up front: plan_slot_scatter, ev_plan.h) ----
-        ProfScope ps2(c, "ev_scatter");
-        const int stride = scat_stride;                                   // (what the count pass left for the scatter)
-        if (nchunks && prerank) {
-            const size_t lds_p = plan_slot_lds_pre(NT, chunk);
-            const uint16_t* d_segcnt_c = d_segcnt;
-            if (sc.waves == 16) {
-                if ((rc = sl_optin(c, 16, (const void*)sl_scatter_pre_kernel<16>, 159 * 1024))) return rc;
-                sl_scatter_pre_kernel<16><<<nchunks, 64 * 16, lds_p, M>>>((const uint64_t*)ws.rec16.p, d_chunks, d_tab, T.w * T.h, TX, NT, chunk, d_slice_eb, d_segcnt_c, d_segbase, d_tile_base, (slot_entry*)ws.entries.p);
-            } else {
-                if ((rc = sl_optin(c, 17, (const void*)sl_scatter_pre_kernel<8>, 159 * 1024))) return rc;
-                sl_scatter_pre_kernel<8><<<nchunks, 64 * 8, lds_p, M>>>((const uint64_t*)ws.rec16.p, d_chunks, d_tab, T.w * T.h, TX, NT, chunk, d_slice_eb, d_segcnt_c, d_segbase, d_tile_base, (slot_entry*)ws.entries.p);
-            }
+        else if (L.nchunks && bp.scatter == kScatRank) {
+            const SlScatRankFn fn = sl_scatter_rank_fn(bp.scat_stride, waves);
+            if ((rc = sl_optin(c, (const void*)fn, 159 * 1024))) return rc;
+            fn<<<L.nchunks, 64 * waves, bp.lds_scatter, p.M>>>(d_ev, L.d_chunks, p.d_tab(), T.w, T.h, p.TX, p.NT, chunk, L.d_slice_eb, L.d_segbase, L.d_tile_base, p.d_entries());
         }
-        else if (nchunks && sc.rank) {
-#define SL_SCAT(ST, NW, BIT) do { if ((rc = sl_optin(c, BIT, (const void*)sl_scatter_rank_kernel<ST, NW>, 159 * 1024))) return rc; \
-                sl_scatter_rank_kernel<ST, NW><<<nchunks, 64 * NW, sc.lds, M>>>(d_ev, d_chunks, d_tab, T.w, T.h, TX, NT, chunk, \
-                                                                                   d_slice_eb, d_segbase, d_tile_base, (slot_entry*)ws.entries.p); } while (0)
-            if (sc.waves == 16) { if (stride == 16) SL_SCAT(16, 16, 3); else if (stride == 4) SL_SCAT(4, 16, 4); else if (stride == 2) SL_SCAT(2, 16, 11); else SL_SCAT(-4, 16, 5); }
-            else { if (stride == 16) SL_SCAT(16, 8, 6); else if (stride == 4) SL_SCAT(4, 8, 7); else if (stride == 2) SL_SCAT(2, 8, 12); else SL_SCAT(-4, 8, 8); }
-#undef SL_SCAT
-        }
-        else if (nchunks)
-            sl_scatter_kernel<<<nchunks, 64 * kSlotScatWaves, sc.lds, M>>>(d_ev, d_chunks, d_tab, stride, T.w, T.h, TX, TY, NT, chunk,
-                                                                                 d_slice_eb, d_segbase, d_tile_base, (slot_entry*)ws.entries.p);
+        else if (L.nchunks)
+            sl_scatter_kernel<<<L.nchunks, 64 * kSlotScatWaves, bp.lds_scatter, p.M>>>(d_ev, L.d_chunks, p.d_tab(), bp.scat_stride, T.w, T.h, p.TX, p.TY, p.NT, chunk, L.d_slice_eb, L.d_segbase,
+                                                                                         L.d_tile_base, p.d_entries());
         EORB_LAUNCH_CHECK(c, "ev_bin (slot) kernels");
     }
-    EORB_HIP(c, hipEventRecord(E[2], M));                                // the part's entries are in place
-    {
-        SlotGather Pg{d_task, d_items, (const uint8_t*)ws.entries.p, d_nslots, d_rowbase, (const float*)T.sl_rows.p,
-                      d_tile_w, d_ctr, d_f32, d_minmax_enc, d_info, (int*)c->status.p, B, W, H, TX, NT, T.sl_null, prio_ref, nullptr};
+    EORB_HIP(c, hipEventRecord(p.E[2], p.M));                            // the part's entries are in place
+    return EORB_OK;
+}
+
+// ---- stage 3, the gather, from the SlotGatherPlan.  Its plan needs the scan's counts only: it is forked between scan and scatter and
+// runs on its own stream BESIDE the scatter (50 us of single-block kernels off the critical path) ----
+static int slots_fork_plan(const SlotPart& p)
+{
+    eorb_ctx* c = p.c; const BinLayout& L = p.L; const SlotGatherPlan& g = p.gp;
+    EORB_HIP(c, hipEventRecord(p.E[0], p.M));
+    EORB_HIP(c, hipStreamWaitEvent(p.P, p.E[0], 0));
+    EORB_HIP(c, hipMemsetAsync(p.ws.hot.p, 0, 256, p.P));
+    sl_plan_kernel<<<p.NT, 256, sizeof(uint32_t) * 2 * (size_t)p.B, p.P>>>(L.d_tile_cnt, L.d_tile_base, L.d_slice_eb, p.B, p.NT, p.TX, g.hot_min, p.d_nslots(), p.d_rowbase(),
+                                                                             p.d_items(), p.d_tile_w(), p.d_tile_m(), p.d_ctr(), p.d_hot_cnt(), p.d_hot_items(), g.hot_cap);
+    sl_tasks_kernel<<<1, 1024, sizeof(uint32_t) * (size_t)p.NT, p.P>>>(p.d_tile_w(), p.d_tile_m(), p.NT, g.Gt, g.max_per_tile, p.d_scr(), p.d_task(), p.d_hot_cnt(), g.hot_cap);
+    EORB_HIP(c, hipEventRecord(p.E[1], p.P));
+    return EORB_OK;
+}
+
+static int slots_gather(const SlotPart& p)
+{
+    eorb_ctx* c = p.c; const PosTables& T = p.T; const SlotGatherPlan& g = p.gp;
+    int rc;
+    SlotGather Pg{p.d_task(), p.d_items(), (const uint8_t*)p.ws.entries.p, p.d_nslots(), p.d_rowbase(), (const float*)T.sl_rows.p,
+                  p.d_tile_w(), p.d_ctr(), p.d_f32, p.d_minmax_enc, p.d_info(), (int*)c->status.p, p.B, p.W, p.H, p.TX, p.NT, T.sl_null, g.prio_ref, nullptr};
 #ifdef EORB_SLOT_TRACE
-        if ((rc = ensure(c, c->sl_trace, sizeof(unsigned long long) * 6 * 16 * (size_t)Gt + 64))) return rc;
-        EORB_HIP(c, hipMemsetAsync(c->sl_trace.p, 0, sizeof(unsigned long long) * 6 * 16 * (size_t)Gt + 64, M));
-        Pg.trace = (unsigned long long*)c->sl_trace.p + 8;
-        c->sl_trace_n = (long long)Gt * 16;
+    EORB_HIP(c, hipMemsetAsync(c->sl_trace.p, 0, sizeof(unsigned long long) * 6 * 16 * (size_t)g.Gt + 64, p.M));
+    Pg.trace = (unsigned long long*)c->sl_trace.p + 8;
+    c->sl_trace_n = (long long)g.Gt * 16;
 #endif
-        if ((rc = sl_optin(c, 9, (const void*)sl_gather_kernel, 160 * 1024))) return rc;
-        if (hot_min) {
-            // the long lists on the high-priority stream beside the gather: they need the scatter's entries and the plan's descriptors
-            const int hw = K.slot_hot_waves > 0 ? K.slot_hot_waves : 8 * ncu;     // two per SIMD: all of its registers
-            EORB_HIP(c, hipStreamWaitEvent(Hs, E[2], 0));
-            EORB_HIP(c, hipStreamWaitEvent(Hs, E[1], 0));
-            sl_hot_kernel<<<hw, 64, 0, Hs>>>(d_hot_cnt, d_hot_cnt + 32, d_hot_items, kHotCap, (const float*)T.sl_rows.p, (const slot_entry*)ws.entries.p,
-                                             d_f32, d_minmax_enc, W, H);
-        }
-        EORB_HIP(c, hipEventRecord(E[3], Hs));
-        if (G != M) EORB_HIP(c, hipStreamWaitEvent(G, E[2], 0));
-        EORB_HIP(c, hipStreamWaitEvent(G, E[1], 0));                       // the plan and the task table
-        {
-            ProfScope ps(c, "ev_gather", G);
-            sl_gather_kernel<<<Gt, 64 * nw, lds_g, G>>>(Pg);
-        }
-        EORB_HIP(c, hipEventRecord(E[4], G));
-        EORB_LAUNCH_CHECK(c, "sl_gather_kernel");
+    if ((rc = sl_optin(c, (const void*)sl_gather_kernel, 160 * 1024))) return rc;
+    if (g.hot_min) {
+        // the long lists on the high-priority stream beside the gather: they need the scatter's entries and the plan's descriptors
+        EORB_HIP(c, hipStreamWaitEvent(p.Hs, p.E[2], 0));
+        EORB_HIP(c, hipStreamWaitEvent(p.Hs, p.E[1], 0));
+        sl_hot_kernel<<<g.hot_waves, 64, 0, p.Hs>>>(p.d_hot_cnt(), p.d_hot_cnt() + 32, p.d_hot_items(), kHotCap, (const float*)T.sl_rows.p, p.d_entries(), p.d_f32, p.d_minmax_enc, p.W, p.H);
     }
+    EORB_HIP(c, hipEventRecord(p.E[3], p.Hs));
+    if (p.G != p.M) EORB_HIP(c, hipStreamWaitEvent(p.G, p.E[2], 0));
+    EORB_HIP(c, hipStreamWaitEvent(p.G, p.E[1], 0));                       // the plan and the task table
+    {
+        ProfScope ps(c, "ev_gather", p.G);
+        sl_gather_kernel<<<g.Gt, 64 * g.nw, g.lds, p.G>>>(Pg);
+    }
+    EORB_HIP(c, hipEventRecord(p.E[4], p.G));
+    EORB_LAUNCH_CHECK(c, "sl_gather_kernel");
     return EORB_OK;
 }
 
@@ -1507,7 +1487,6 @@ static int slots_part(eorb_ctx* c, const PosTables& T, eorb_ctx::SlotWS& ws, int
 int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const AccumShape& S, const void* d_events, int stride, const int64_t* h_offsets, int B, int W, int H,
                         float* d_f32, uint32_t* d_minmax_enc, const SlotDict* dict)
 {
-    const int TX = S.TX, TY = S.TY, NT = S.NT;
     const AccumKnobs K = accum_knobs(c);
     // Off by default.  Measured at 128 x 1 Mev: 3.94 ms per step in halves against 3.34 in one part -- each half's gather phase is bounded
     // from below by the serial chain of its own longest list (200 000 entries x 13 cycles = 1.1 ms on the register-row kernel's
@@ -1519,17 +1498,24 @@ int ev_slots_accumulate(eorb_ctx* c, const PosTables& T, const AccumShape& S, co
     for (int b = 0; b < B; b++) {
         const int64_t s = h_offsets[b], e = h_offsets[b + 1];
         if (e < s) return set_err(c, EORB_E_ARG, "ev_accumulate: offsets not monotone");
-        if ((e - s) * 4 + (int64_t)NT * 16 >= (int64_t)1 << 31) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: %lld events in one slice", (long long)(e - s));
+        if ((e - s) * 4 + (int64_t)S.NT * 16 >= (int64_t)1 << 31) return set_err(c, EORB_E_CAPACITY, "ev_accumulate: %lld events in one slice", (long long)(e - s));
     }
     int rc;
     if ((rc = sl_streams(c))) return rc;
     c->sl_calls++;
-    c->sl_last_rank = sc.rank ? 1 : 0; c->sl_last_chunk = sc.chunk; c->sl_last_parts = nparts;
+    SlotBinPlan bp;
+    if (!plan_slot_binning(S, stride, (int64_t)T.w * T.h, dict ? (dict->rec2 ? 2 : 1) : 0, sc, K, &bp))
+        return set_err(c, EORB_E_CAPACITY, "slot form: the position dictionary needs the LDS count pass");
+    c->sl_last_rank = bp.scatter != kScatBallot ? 1 : 0; c->sl_last_chunk = sc.chunk; c->sl_last_parts = nparts; c->sl_last_binning = slot_binning_code(bp);
     const int B0 = nparts == 2 ? B / 2 : B;
     for (int part = 0; part < nparts; part++) {
         const int b0 = part ? B0 : 0, nb_ = part ? B - B0 : B0;
-        if ((rc = slots_part(c, T, c->sl_ws[part], part, nparts, d_events, stride, h_offsets + b0, nb_, W, H, TX, TY,
-                             d_f32 + (size_t)b0 * W * H, d_minmax_enc + 2 * (size_t)b0, sc, dict, K))) return rc;
+        const int64_t* off = h_offsets + b0;
+        SlotPart p{c, T, c->sl_ws[part], d_events, dict, off, nb_, W, H, S.TX, S.TY, S.NT, sl_ncu(c), d_f32 + (size_t)b0 * W * H, d_minmax_enc + 2 * (size_t)b0,
+                   sc, bp, plan_slot_gather(S, nb_, off[nb_] - off[0], nparts, T.sl_null, sl_ncu(c), K), BinLayout(),
+                   c->stream, c->sl_pstream, c->sl_side, nparts > 1 ? c->sl_gstream : c->stream, c->sl_ev + 5 * part};
+        c->sl_last_nb[part] = nb_ * S.NT;
+        if ((rc = slots_layout(p)) || (rc = slots_count_scan(p)) || (rc = slots_fork_plan(p)) || (rc = slots_scatter(p)) || (rc = slots_gather(p))) return rc;
     }
     // whatever the other streams did is done before the images are read (streams are in order: the last part's events cover the first's)
     hipEvent_t* E = c->sl_ev + 5 * (nparts - 1);

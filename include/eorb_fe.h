@@ -125,7 +125,10 @@ int         eorb_debug_option(eorb_ctx* ctx, const char* name, int value);
  * "kfdb_word_cap": slots / words the KeyFrameDatabase pools hold room for; "accum_route": what served the context's last accumulation
  * call (0: none yet) = form (1 binning-free, 2 slot lists, 3 list pipeline) | position set << 2 (0 none: float events as they are,
  * 1 the undistortion maps, 2 the call's own tabulated positions, 3 the position dictionary) | 16 if the pipeline's sparse gather ran
- * | 32 if short records (eorb_raw_event4 / eorb_raw_event2) were widened first.
+ * | 32 if short records (eorb_raw_event4 / eorb_raw_event2) were widened first; "slot_scatter_form" (1 rank or pre-ranked scatter, 0 ballot),
+ * "slot_chunk" (events per binning chunk) and "slot_binning" of the last call that took the slot lists (-1: none yet) = count pass (0 global
+ * counters, 1 tile ranges in LDS, 2 the same with the position dictionary's lookup) | record the scatter reads << 2 (0 the events as they
+ * are, 1 2-byte sensor indices, 2 8-byte ranked records) | scatter << 4 (0 ballot, 1 rank, 2 pre-ranked).
  * Returns the value, or -1 for an unknown name. */
 long long   eorb_debug_counter(eorb_ctx* ctx, const char* name);
 /* test hook, not part of the reference's interface: the intermediate images of the extractor, for stage-by-stage comparison with

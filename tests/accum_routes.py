@@ -15,6 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIRECT, SLOTS, LISTS = 1, 2, 3                       # include/eorb_fe.h, "accum_route"
 NONE, MAPS, PER_CALL, DICT = 0 << 2, 1 << 2, 2 << 2, 3 << 2
 SPARSE, WIDENED = 1 << 4, 1 << 5
+# the slot form's binning (csrc/ev_plan.h SlotBinPlan, "slot_binning" = count | record << 2 | scatter << 4)
+COUNT_GLOBAL, COUNT_LDS, COUNT_LDS_KEYED = 0, 1, 2
+REC_AS_IS, REC_SHORT2, REC_RANKED8 = 0, 1, 2
+SCAT_BALLOT, SCAT_RANK, SCAT_PRE = 0, 1, 2
 
 W, H, SIGMA = 240, 180, 1.0
 BULK = (("dedupe_min_events", 1),)                   # the float bulk path at test size
@@ -29,8 +33,19 @@ def describe(route):
     return "%s / %s%s%s" % (form, pset, ", sparse" if route & SPARSE else "", ", widened" if route & WIDENED else "")
 
 
-def _row(name, entry, sizes, want, pol=False, opts=(), events="random", dict_valid=False):
-    return dict(name=name, entry=entry, sizes=list(sizes), want=want, pol=pol, opts=tuple(opts), events=events, dict_valid=dict_valid)
+def binning(count, record, scatter):
+    return count | record << 2 | scatter << 4
+
+
+def describe_binning(code):
+    return "%s / %s / %s" % (("global", "lds", "lds-keyed", "?")[code & 3], ("as-is", "short2", "ranked8", "?")[(code >> 2) & 3],
+                             ("ballot", "rank", "pre", "?")[(code >> 4) & 3])
+
+
+def _row(name, entry, sizes, want, pol=False, opts=(), events="random", dict_valid=False, want_count=None):
+    """want_count: the count pass a SLOTS row must record in "slot_binning" (None: not asserted)"""
+    return dict(name=name, entry=entry, sizes=list(sizes), want=want, pol=pol, opts=tuple(opts), events=events, dict_valid=dict_valid,
+                want_count=want_count)
 
 
 # A row is a list of calls on ONE context, in order (only the dictionary row has more than one).
@@ -47,9 +62,9 @@ ROWS = [
     [_row("float bulk 11040, no dictionary", "gauss", [11040], SLOTS | PER_CALL, opts=BULK + (("position_dict", 0),), events="mapped")],
     [_row("float bulk 11039, no dictionary", "gauss", [11039], LISTS | PER_CALL | SPARSE, opts=BULK + (("position_dict", 0),), events="mapped")],
     [_row("float bulk 11040, first call", "gauss", [11040], SLOTS | PER_CALL, opts=BULK, events="mapped"),
-     _row("float bulk 11040, same events again", "gauss", [11040], SLOTS | DICT, opts=BULK, events="same", dict_valid=True),
+     _row("float bulk 11040, same events again", "gauss", [11040], SLOTS | DICT, opts=BULK, events="same", dict_valid=True, want_count=COUNT_LDS_KEYED),
      # (the dictionary path has no load test)
-     _row("float bulk 5000, third call", "gauss", [5000], SLOTS | DICT, opts=BULK, events="same", dict_valid=True)],
+     _row("float bulk 5000, third call", "gauss", [5000], SLOTS | DICT, opts=BULK, events="same", dict_valid=True, want_count=COUNT_LDS_KEYED)],
     [_row("raw batch 5 x 11040", "batch_raw", [11040] * 5, SLOTS | MAPS)],
     [_row("raw batch 5, sum 55199", "batch_raw", [11040] * 4 + [11039], LISTS | MAPS | SPARSE)],
     [_row("raw batch 4 x 4096", "batch_raw", [4096] * 4, DIRECT | MAPS)],
@@ -84,11 +99,15 @@ def plan_exe():
 
 def plan(queries):
     """queries: dicts with any of W H sigma mode_count B nev raw pol gather_form dedupe_min_events position_dict slot_rank rank_ok
-    dict_valid scatter slots_usable -> per query a dict(route, pipeline_chunk, slot_ok, slot_chunk, slot_scatter_rank, bulk_fits, host_events)."""
+    dict_valid scatter slots_usable, and for the slot form's own plans stride sensor_w sensor_h (0: the image) dict (0 none, 1 4-byte rows,
+    2 2-byte ids) slot_prerank ncu sl_null slot_hot_min nparts -> per query a dict(route, pipeline_chunk, slot_ok, slot_chunk,
+    slot_scatter_rank, bulk_fits, host_events; slot_waves, bin_ok, count, record, scatter, bin_stride, scat_stride, lds_count, lds_scatter,
+    slot_binning; g_lds ... g_hot_waves: the SlotGatherPlan of the whole batch as one part)."""
     keys = ("W", "H", "sigma", "mode_count", "B", "nev", "raw", "pol", "gather_form", "dedupe_min_events", "position_dict", "slot_rank", "rank_ok",
-            "dict_valid", "scatter", "slots_usable")
+            "dict_valid", "scatter", "slots_usable", "stride", "sensor_w", "sensor_h", "dict", "slot_prerank", "ncu", "sl_null", "slot_hot_min", "nparts")
     dflt = dict(W=W, H=H, sigma=SIGMA, mode_count=0, B=1, nev=0, raw=0, pol=0, gather_form=0, dedupe_min_events=1 << 20, position_dict=1, slot_rank=-1,
-                rank_ok=1, dict_valid=0, scatter=2, slots_usable=1)
+                rank_ok=1, dict_valid=0, scatter=2, slots_usable=1, stride=16, sensor_w=0, sensor_h=0, dict=0, slot_prerank=-1, ncu=256, sl_null=240,
+                slot_hot_min=-1, nparts=1)
     lines = []
     for q in queries:
         assert set(q) <= set(keys), q
@@ -96,7 +115,9 @@ def plan(queries):
         lines.append(" ".join(repr(float(v[k])) if k == "sigma" else str(int(v[k])) for k in keys))
     out = subprocess.run([plan_exe()], input="\n".join(lines) + "\n", capture_output=True, text=True)
     assert out.returncode == 0, out.stderr
-    names = ("route", "pipeline_chunk", "slot_ok", "slot_chunk", "slot_scatter_rank", "bulk_fits", "host_events")
+    names = ("route", "pipeline_chunk", "slot_ok", "slot_chunk", "slot_scatter_rank", "bulk_fits", "host_events",
+             "slot_waves", "bin_ok", "count", "record", "scatter", "bin_stride", "scat_stride", "lds_count", "lds_scatter", "slot_binning",
+             "g_lds", "g_wg_per_cu", "g_nw", "g_rounds", "g_tasks", "g_max_per_tile", "g_prio_ref", "g_hot_min", "g_hot_cap", "g_hot_waves")
     res = [dict(zip(names, (int(x) for x in ln.split()))) for ln in out.stdout.strip().split("\n")]
     assert len(res) == len(lines), out.stdout
     return res

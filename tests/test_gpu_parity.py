@@ -1490,7 +1490,7 @@ def _raw_batch(fe, raws, W, H, mx, my, opts=(), check=True, sigma=1.0, fmt=True)
     imgs = np.zeros((B, H, W), np.uint8); c.download(imgs, d_img)
     p32, mm = fb.last_f32(B)
     f32 = np.zeros((B, H, W), np.float32); c.download(f32, p32)
-    cnt = {k: c.debug_counter(k) for k in ("slot_calls", "slot_flags", "slot_hot_items", "slot_hot_overflow", "slot_scatter_form", "slot_chunk", "slot_rank_ok", "slot_parts", "accum_route")}
+    cnt = {k: c.debug_counter(k) for k in ("slot_calls", "slot_flags", "slot_hot_items", "slot_hot_overflow", "slot_scatter_form", "slot_chunk", "slot_binning", "slot_rank_ok", "slot_parts", "accum_route")}
     for p_ in (d_ev, d_img, d_kp, d_n):
         c.dev_free(p_)
     c.close()
@@ -1569,11 +1569,16 @@ def test_slot_scatter_ballot_form_equals_rank_form(oracle, fe):
     # (form 1 twice: with the ranks the count pass keeps -- sl_scatter_pre_kernel, the default -- and with the scatter ranking by itself,
     #  sl_scatter_rank_kernel, which sensors of more than 65 535 pixels still take)
     for name, raws in batches.items():
-        for form, pre in ((1, 1), (1, 0), (0, 0)):
-            got = _raw_batch(fe, raws, W, H, mx, my, (("gather_form", 4), ("slot_rank", form), ("slot_prerank", pre)))
+        for form, pre, binning in ((1, 1, ar.binning(ar.COUNT_LDS, ar.REC_RANKED8, ar.SCAT_PRE)), (1, 0, ar.binning(ar.COUNT_LDS, ar.REC_SHORT2, ar.SCAT_RANK)),
+                                   (0, 0, ar.binning(ar.COUNT_LDS, ar.REC_AS_IS, ar.SCAT_BALLOT))):
+            opts = (("gather_form", 4), ("slot_rank", form), ("slot_prerank", pre))
+            got = _raw_batch(fe, raws, W, H, mx, my, opts)
             cnt = got[3]
             assert cnt["slot_calls"] == 1 and cnt["slot_flags"] == 0 and cnt["slot_rank_ok"] == 1, (name, form, cnt)
             assert cnt["slot_scatter_form"] == form, (name, form, cnt)
+            planned = ar.plan([dict(raw=1, B=len(raws), nev=sum(len(r) for r in raws), stride=16, **dict(opts))])[0]
+            assert cnt["slot_binning"] == binning == planned["slot_binning"], (name, form, pre, ar.describe_binning(cnt["slot_binning"]), planned)
+            assert cnt["slot_chunk"] == planned["slot_chunk"], (name, cnt, planned)
             if name == "2 x 300k":
                 assert cnt["slot_chunk"] == (4096 if form else 2048), cnt
             _check_raw_batch(oracle, raws, W, H, mx, my, got, (name, form, pre))
@@ -1597,6 +1602,9 @@ def test_raw_dense_batch_on_vga_class_sensors(oracle, fe):
         for form, slot_rank, slot_calls in ((0, 1, 1), (4, 1, 1), (0, 0, 0), (4, 0, 0)):
             got = _raw_batch(fe, raws, W, H, mx, my, (("gather_form", form), ("slot_rank", slot_rank)))
             assert got[3]["slot_calls"] == slot_calls and got[3]["slot_flags"] == 0, (W, H, form, slot_rank, got[3])
+            if slot_calls:      # the sensor pixels' tile ranges do not fit the LDS: the global count pass, the events as they are
+                planned = ar.plan([dict(raw=1, B=2, nev=sum(len(r) for r in raws), W=W, H=H, stride=16, gather_form=form, slot_rank=slot_rank)])[0]
+                assert got[3]["slot_binning"] == ar.binning(ar.COUNT_GLOBAL, ar.REC_AS_IS, ar.SCAT_RANK) == planned["slot_binning"], (W, H, form, got[3], planned)
             _check_raw_batch(oracle, raws, W, H, mx, my, got, (W, H, form, slot_rank))
 
 
@@ -1618,6 +1626,10 @@ def test_packed_wire_records_equal_raw_records(oracle, fe):
             d_img = c.dev_alloc(B * W * H); d_kp = c.dev_alloc(B * cap * 28); d_desc = c.dev_alloc(B * cap * 32); d_n = c.dev_alloc(B * 4)
             fb.run_dev(d_ev, np.arange(B + 1, dtype=np.int64) * n, d_img, d_kp, d_desc, d_n, raw=fmt)
             c.sync()
+            if n == 60000:      # the dense batch: slot lists, whose count pass ranks records of every width
+                planned = ar.plan([dict(raw=1 if fmt is True else (3 if fmt == 4 else 4), B=B, nev=n * B, stride=16 if fmt is True else fmt)])[0]
+                assert planned["route"] & 3 == ar.SLOTS and c.debug_counter("accum_route") & 3 == ar.SLOTS, (fmt, planned)
+                assert c.debug_counter("slot_binning") == ar.binning(ar.COUNT_LDS, ar.REC_RANKED8, ar.SCAT_PRE) == planned["slot_binning"], (fmt, planned)
             imgs = np.zeros((B, H, W), np.uint8); c.download(imgs, d_img)
             nk = np.zeros(B, np.int32); c.download(nk, d_n)
             kps = np.zeros((B, cap), synth.KP_DTYPE); c.download(kps, d_kp)

@@ -76,6 +76,10 @@ def test_route_and_images_of_every_table_row(oracle, fe, row):
                     got = fe.EvImConverter.ev2im_gauss_raw(ev[0], W, H, sigma, pol, True, ctx=c, return_all=True)
             route = c.debug_counter("accum_route")
             assert route == call["want"], (what, ar.describe(route), ar.describe(call["want"]))
+            if call["want_count"] is not None:      # (the dictionary's positions: at most one per event, 2-byte ids)
+                planned = ar.plan([dict(ar.query_of(call), stride=16, dict=2, sensor_w=call["sizes"][0], sensor_h=1)])[0]
+                got_bin = c.debug_counter("slot_binning")
+                assert got_bin & 3 == call["want_count"] == planned["count"], (what, ar.describe_binning(got_bin), planned)
             _equal_oracle(want, got, what)
     finally:
         if c is not None:
