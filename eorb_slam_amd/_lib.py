@@ -30,6 +30,7 @@ EXPORTS = [
     "eorb_search_by_bow_kf_keyframes",
     "eorb_kfdb_clear", "eorb_kfdb_add", "eorb_kfdb_erase", "eorb_kfdb_info", "eorb_kfdb_get_scores", "eorb_kfdb_detect_reloc", "eorb_kfdb_detect_nbest",
     "eorb_two_view_ransac", "eorb_two_view_check_rt",
+    "eorb_sim3_ransac",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
 ]
@@ -125,6 +126,21 @@ class TvrParams(C.Structure):
 
 
 TVR_MAX_ITERS, TVR_MAX_MATCHES, TVR_MAX_KEYS, TVR_MAX_POSES = 1024, 16384, 1048576, 64
+
+
+class Sim3Problem(C.Structure):
+    """eorb_sim3_problem: one Sim3Solver (its correspondences and sets follow those of the problems before it in the flat arrays)"""
+    _fields_ = [("N", C.c_int32), ("iters", C.c_int32), ("fix_scale", C.c_int32), ("min_inliers", C.c_int32),
+                ("Rt1", C.c_float * 12), ("Rt2", C.c_float * 12), ("cam1", Camera), ("cam2", Camera)]
+
+
+class Sim3Result(C.Structure):
+    """eorb_sim3_result: bConverge, the winning iteration, its count, mnIterations, mBestT12 / Rotation / Translation / Scale"""
+    _fields_ = [("converged", C.c_int32), ("best_it", C.c_int32), ("n_inliers", C.c_int32), ("iterations_used", C.c_int32),
+                ("T12", C.c_float * 16), ("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float)]
+
+
+S3_MAX_ITERS, S3_MAX_CORR, S3_MAX_PROBLEMS = 1024, 16384, 64
 
 
 class KltParams(C.Structure):
@@ -369,6 +385,8 @@ def lib():
     L.eorb_two_view_ransac.restype = ci
     L.eorb_two_view_ransac.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, C.POINTER(TvrParams), vp, C.POINTER(cf), pi, vp, vp, C.POINTER(cf), pi, vp,
                                        vp, vp, vp, vp]
+    L.eorb_sim3_ransac.restype = ci
+    L.eorb_sim3_ransac.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.eorb_two_view_check_rt.restype = ci
     L.eorb_two_view_check_rt.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, cf, cf, ci, vp, ci, vp, vp, vp, vp, vp]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]

@@ -175,6 +175,74 @@ __device__ __forceinline__ void dev_dsincos(double x, double* sn, double* cs)
     }
 }
 
+// double-precision atan2 for the rotation angle of Sim3Solver::ComputeSim3 (src/Sim3Solver.cc:368): fdlibm's e_atan2.c over s_atan.c,
+// the same text as the CPU restatement (tests/sim3_ref/sim3_ref.c), which is held to 1 ulp of the host's atan2 (tests/test_sim3_ref.py).
+__device__ __forceinline__ double dev_datan(double x)
+{
+    const double atanhi[4] = {4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01, 1.57079632679489655800e+00};
+    const double atanlo[4] = {2.26987774529616870924e-17, 3.06161699786838301793e-17, 1.39033110312309984516e-17, 6.12323399573676603587e-17};
+    const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01, aT2 = 1.42857142725034663711e-01,
+                 aT3 = -1.11111104054623557880e-01, aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
+                 aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02, aT8 = 4.97687799461593236017e-02,
+                 aT9 = -3.65315727442169155270e-02, aT10 = 1.62858201153657823623e-02;
+    const int hx = __double2hiint(x), ix = hx & 0x7fffffff;
+    double hi = 0., lo = 0.;
+    int id;
+    if (ix >= 0x44100000) {
+        if (ix > 0x7ff00000 || (ix == 0x7ff00000 && __double2loint(x) != 0)) return x + x;
+        return hx > 0 ? atanhi[3] + atanlo[3] : -atanhi[3] - atanlo[3];
+    }
+    if (ix < 0x3fdc0000) {
+        if (ix < 0x3e200000) return x;
+        id = -1;
+    } else {
+        x = fabs(x);
+        if (ix < 0x3ff30000) {
+            if (ix < 0x3fe60000) { id = 0; hi = atanhi[0]; lo = atanlo[0]; x = (2.0 * x - 1.0) / (2.0 + x); }
+            else { id = 1; hi = atanhi[1]; lo = atanlo[1]; x = (x - 1.0) / (x + 1.0); }
+        } else {
+            if (ix < 0x40038000) { id = 2; hi = atanhi[2]; lo = atanlo[2]; x = (x - 1.5) / (1.0 + 1.5 * x); }
+            else { id = 3; hi = atanhi[3]; lo = atanlo[3]; x = -1.0 / x; }
+        }
+    }
+    double z = x * x;
+    const double w = z * z;
+    const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
+    const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
+    if (id < 0) return x - x * (s1 + s2);
+    z = hi - ((x * (s1 + s2) - lo) - x);
+    return hx < 0 ? -z : z;
+}
+__device__ __forceinline__ double dev_datan2(double y, double x)
+{
+    const double tiny = 1.0e-300, pi_o_4 = 7.8539816339744827900E-01, pi_o_2 = 1.5707963267948965580E+00, pi = 3.1415926535897931160E+00,
+                 pi_lo = 1.2246467991473531772E-16;
+    const int hx = __double2hiint(x), ix = hx & 0x7fffffff, hy = __double2hiint(y), iy = hy & 0x7fffffff;
+    const unsigned lx = (unsigned)__double2loint(x), ly = (unsigned)__double2loint(y);
+    if (((unsigned)ix | ((lx | (0u - lx)) >> 31)) > 0x7ff00000u || ((unsigned)iy | ((ly | (0u - ly)) >> 31)) > 0x7ff00000u) return x + y;
+    if ((((unsigned)hx - 0x3ff00000u) | lx) == 0) return dev_datan(y);
+    const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);
+    if (((unsigned)iy | ly) == 0) {
+        if (m < 2) return y;
+        return m == 2 ? pi + tiny : -pi - tiny;
+    }
+    if (((unsigned)ix | lx) == 0) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    if (ix == 0x7ff00000) {
+        if (iy == 0x7ff00000) return m == 0 ? pi_o_4 + tiny : m == 1 ? -pi_o_4 - tiny : m == 2 ? 3.0 * pi_o_4 + tiny : -3.0 * pi_o_4 - tiny;
+        return m == 0 ? 0.0 : m == 1 ? -0.0 : m == 2 ? pi + tiny : -pi - tiny;
+    }
+    if (iy == 0x7ff00000) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    const int k = (iy - ix) >> 20;
+    double z;
+    if (k > 60) z = pi_o_2 + 0.5 * pi_lo;
+    else if (hx < 0 && k < -60) z = 0.0;
+    else z = dev_datan(fabs(y / x));
+    if (m == 0) return z;
+    if (m == 1) return -z;
+    if (m == 2) return pi - (z - pi_lo);
+    return (z - pi_lo) - pi;
+}
+
 // ---- tanf / atanf / atan2f: glibc's float algorithms (s_tanf.c + k_tanf.c with the sincosf.h double reduction; s_atanf.c;
 // e_atan2f.c), the operation sequences of oracle/orc_math.c written independently here; needed by KannalaBrandt8::unproject /
 // project (src/CameraModels/KannalaBrandt8.cpp:87-190).  Checked against the oracle over their whole domains by

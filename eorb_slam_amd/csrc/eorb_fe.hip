@@ -5,6 +5,7 @@
 #include "project_args.h"
 #include "kfdb.h"
 #include "twoview.h"
+#include "sim3.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -2703,6 +2704,84 @@ int eorb_two_view_check_rt(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const
     memcpy(n_good, h + o_ng, sizeof(int32_t) * sK); memcpy(cos_sel, h + o_cs, sizeof(float) * sK);
     memcpy(good, h + o_g, sK * s1); memcpy(p3d, h + o_p3, sizeof(float) * 3 * sK * s1);
     if (cos_all) memcpy(cos_all, h + o_ca, sizeof(float) * sK * sN);
+    return EORB_OK;
+}
+
+int eorb_sim3_ransac(eorb_ctx* c, const eorb_sim3_problem* problems, int K, const float* Xw1, const float* Xw2,
+        const float* sigma2_1, const float* sigma2_2, const int32_t* sets,
+        eorb_sim3_result* results, uint8_t* inliers, int32_t* it_inliers, float* it_T12, float* it_T21, float* it_scale)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "sim3_ransac";
+    if (!problems || !Xw1 || !Xw2 || !sigma2_1 || !sigma2_2 || !sets || !results || !inliers) return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    if (K < 1) return set_err(c, EORB_E_ARG, "%s: %d problems (at least 1)", what, K);
+    if (K > EORB_S3_MAX_PROBLEMS) return set_err(c, EORB_E_CAPACITY, "%s: %d problems, at most EORB_S3_MAX_PROBLEMS = %d", what, K, EORB_S3_MAX_PROBLEMS);
+    // sizes first (no array is read), then the cameras, then the sets and the sigmas
+    std::vector<S3Prob> pv((size_t)K);
+    size_t tN = 0, tI = 0;
+    int max_N = 0, max_iters = 0;
+    for (int k = 0; k < K; k++) {
+        const eorb_sim3_problem& p = problems[k];
+        if (p.N < 3 || p.iters < 1 || p.min_inliers < 0)
+            return set_err(c, EORB_E_ARG, "%s: problem %d has %d correspondences (at least 3), %d iterations (at least 1), min_inliers %d (at least 0)", what, k,
+                           p.N, p.iters, p.min_inliers);
+        if (p.N > EORB_S3_MAX_CORR) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d correspondences, at most EORB_S3_MAX_CORR = %d", what, k, p.N, EORB_S3_MAX_CORR);
+        if (p.iters > EORB_S3_MAX_ITERS) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d iterations, at most EORB_S3_MAX_ITERS = %d", what, k, p.iters, EORB_S3_MAX_ITERS);
+        S3Prob& d = pv[k];
+        d.N = p.N; d.iters = p.iters; d.corr_off = (int)tN; d.set_off = (int)tI; d.fix_scale = p.fix_scale != 0; d.min_inliers = p.min_inliers;
+        memcpy(d.Rt1, p.Rt1, sizeof d.Rt1); memcpy(d.Rt2, p.Rt2, sizeof d.Rt2);
+        d.cam1 = warp_cam_of(p.cam1); d.cam2 = warp_cam_of(p.cam2);
+        tN += (size_t)p.N; tI += (size_t)p.iters;
+        max_N = std::max(max_N, p.N); max_iters = std::max(max_iters, p.iters);
+    }
+    for (int k = 0; k < K; k++)
+        if ((problems[k].cam1.model != 0 && problems[k].cam1.model != 1) || (problems[k].cam2.model != 0 && problems[k].cam2.model != 1))
+            return set_err(c, EORB_E_CONFIG, "%s: problem %d has a camera model other than Pinhole (0) / KannalaBrandt8 (1)", what, k);
+    for (int k = 0; k < K; k++) {
+        const S3Prob& d = pv[k];
+        for (int i = 0; i < 3 * d.iters; i++) {
+            const int32_t s = sets[3 * (size_t)d.set_off + i];
+            if (s < 0 || s >= d.N) return set_err(c, EORB_E_ARG, "%s: problem %d, set %d holds the index %d of %d correspondences", what, k, i / 3, s, d.N);
+        }
+        for (int i = 0; i < d.N; i++) {
+            const float s1 = sigma2_1[(size_t)d.corr_off + i], s2 = sigma2_2[(size_t)d.corr_off + i];
+            if (!(s1 >= 0.f && s1 < 1e15f) || !(s2 >= 0.f && s2 < 1e15f))
+                return set_err(c, EORB_E_ARG, "%s: problem %d, correspondence %d has sigma2 = (%g, %g), outside [0, 1e15)", what, k, i, (double)s1, (double)s2);
+        }
+    }
+    fe_enter(c);
+    int rc;
+    Arena A(c);
+    const size_t o_pr = A.in(pv.data(), sizeof(S3Prob) * (size_t)K);
+    const size_t o_x1 = A.in(Xw1, sizeof(float) * 3 * tN), o_x2 = A.in(Xw2, sizeof(float) * 3 * tN);
+    const size_t o_s1 = A.in(sigma2_1, sizeof(float) * tN), o_s2 = A.in(sigma2_2, sizeof(float) * tN), o_st = A.in(sets, sizeof(int32_t) * 3 * tI);
+    const size_t o_c1 = A.reserve(sizeof(float) * 3 * tN), o_c2 = A.reserve(sizeof(float) * 3 * tN);
+    const size_t o_p1 = A.reserve(sizeof(float) * 2 * tN), o_p2 = A.reserve(sizeof(float) * 2 * tN);
+    const size_t o_b1 = A.reserve(sizeof(float) * tN), o_b2 = A.reserve(sizeof(float) * tN), o_hyp = A.reserve(sizeof(float) * kS3HypFloats * tI);
+    // results, contiguous and zero on entry: the K records | inliers | the per-iteration aids
+    const size_t o_res = A.reserve(sizeof(int32_t) * kS3ResWords * (size_t)K), o_inl = A.reserve(tN);
+    const size_t o_cnt = A.reserve(sizeof(int32_t) * tI), o_sc = A.reserve(sizeof(float) * tI);
+    const size_t o_t12 = A.reserve(sizeof(float) * 16 * tI), o_t21 = A.reserve(sizeof(float) * 16 * tI), o_end = A.reserve(0);
+    if ((rc = A.upload())) return rc;
+    EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_res), 0, o_end - o_res, c->stream));
+    S3Args T{};
+    T.prob = A.dev<S3Prob>(o_pr); T.K = K; T.max_N = max_N; T.max_iters = max_iters;
+    T.Xw1 = A.dev<float>(o_x1); T.Xw2 = A.dev<float>(o_x2); T.sigma2_1 = A.dev<float>(o_s1); T.sigma2_2 = A.dev<float>(o_s2); T.sets = A.dev<int32_t>(o_st);
+    T.X1 = A.dev<float>(o_c1); T.X2 = A.dev<float>(o_c2); T.p1 = A.dev<float2>(o_p1); T.p2 = A.dev<float2>(o_p2);
+    T.b1 = A.dev<float>(o_b1); T.b2 = A.dev<float>(o_b2); T.hyp = A.dev<float>(o_hyp);
+    T.res = A.dev<int32_t>(o_res); T.inliers = A.dev<uint8_t>(o_inl); T.it_inliers = A.dev<int32_t>(o_cnt); T.it_scale = A.dev<float>(o_sc);
+    T.it_T12 = A.dev<float>(o_t12); T.it_T21 = A.dev<float>(o_t21);
+    if ((rc = sim3_ransac_dev(c, T))) return rc;
+    const bool aids = it_inliers || it_T12 || it_T21 || it_scale;
+    const char* h;
+    if ((rc = A.download(o_res, (aids ? o_end : o_cnt) - o_res, &h))) return rc;
+    static_assert(sizeof(eorb_sim3_result) == sizeof(int32_t) * kS3ResWords, "eorb_sim3_result is kS3ResWords words");
+    memcpy(results, h + o_res, sizeof(eorb_sim3_result) * (size_t)K);
+    memcpy(inliers, h + o_inl, tN);
+    if (it_inliers) memcpy(it_inliers, h + o_cnt, sizeof(int32_t) * tI);
+    if (it_scale) memcpy(it_scale, h + o_sc, sizeof(float) * tI);
+    if (it_T12) memcpy(it_T12, h + o_t12, sizeof(float) * 16 * tI);
+    if (it_T21) memcpy(it_T21, h + o_t21, sizeof(float) * 16 * tI);
     return EORB_OK;
 }
 

@@ -1334,6 +1334,104 @@ class TwoViewReconstruction:
         return o
 
 
+def sim3_ransac_iterations(N, probability, min_inliers, max_iterations):
+    """mRansacMaxIts of Sim3Solver::SetRansacParameters (src/Sim3Solver.cc:137-147): epsilon in float, pow / log / ceil in double.
+    `int nIterations = ceil(...)` of a value no int holds converts as the reference's x86 build does (cvttsd2si: INT_MIN), which
+    max(1, min(...)) turns into 1: min_inliers = 0 and N < min_inliers end there."""
+    epsilon = float(np.float32(min_inliers) / np.float32(N))
+    if min_inliers == N:
+        n = 1
+    else:
+        with np.errstate(all="ignore"):
+            v = np.ceil(np.log(np.float64(1 - probability)) / np.log(np.float64(1) - np.float64(epsilon) ** 3))
+        n = int(v) if np.isfinite(v) and -2147483648.0 <= v < 2147483648.0 else -2147483648
+    return max(1, min(n, int(max_iterations)))
+
+
+def sim3_draw_sets(N, iterations, seed):
+    """the minimal sets of Sim3Solver::iterate (:178-189) on a numpy generator (the reference draws from DUtils::Random): three draws
+    without replacement, the drawn slot refilled with the back of vAvailableIndices.  -> [iterations, 3] int32"""
+    rng = np.random.default_rng(seed)
+    sets = np.zeros((iterations, 3), np.int32)
+    for it in range(iterations):
+        moved = {}
+        for i in range(3):
+            size = N - i
+            randi = int(rng.integers(0, size))
+            sets[it, i] = moved.get(randi, randi)
+            moved[randi] = moved.get(size - 1, size - 1)
+    return sets
+
+
+class Sim3Solver:
+    """Sim3Solver (src/Sim3Solver.cc) over correspondences the caller has compacted (the constructor's filter :71-91 and the mvnIndices1
+    map stay with the caller): Xw1 / Xw2 [N, 3] GetWorldPos() of both sides, Rt1 / Rt2 [12] Rcw then tcw of pKF1 / pKF2, cam1 / cam2 as
+    (fx, fy, cx, cy[, k1..k4[, precision]]), sigma2_1 / sigma2_2 getKPtLevelSigma2 per correspondence (or one value).  find() runs
+    iterate to its end on the device; solve_candidates() runs one solver per BoW candidate in one call."""
+
+    def __init__(self, Xw1, Xw2, Rt1, Rt2, cam1, cam2, sigma2_1, sigma2_2, fix_scale=True, ctx=None):
+        self.Xw1 = np.ascontiguousarray(Xw1, np.float32).reshape(-1, 3); self.Xw2 = np.ascontiguousarray(Xw2, np.float32).reshape(-1, 3)
+        self.N = len(self.Xw1)
+        assert len(self.Xw2) == self.N
+        self.Rt1 = np.ascontiguousarray(Rt1, np.float32).reshape(12); self.Rt2 = np.ascontiguousarray(Rt2, np.float32).reshape(12)
+        self.cam1, self.cam2 = _lib.camera(cam1), _lib.camera(cam2)
+        self.sigma2_1 = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma2_1, np.float32), (self.N,)))
+        self.sigma2_2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma2_2, np.float32), (self.N,)))
+        self.fix_scale = bool(fix_scale)
+        self.ctx = ctx or default_context()
+        self.set_ransac_parameters()
+
+    def set_ransac_parameters(self, probability=0.99, min_inliers=6, max_iterations=300):
+        """SetRansacParameters (:126-150) -> the iteration count"""
+        self.probability, self.min_inliers = float(probability), int(min_inliers)
+        self.iters = sim3_ransac_iterations(self.N, probability, min_inliers, max_iterations)
+        return self.iters
+
+    def draw_sets(self, seed):
+        return sim3_draw_sets(self.N, self.iters, seed)
+
+    def problem(self, iters):
+        p = _lib.Sim3Problem()
+        p.N, p.iters, p.fix_scale, p.min_inliers = self.N, int(iters), int(self.fix_scale), self.min_inliers
+        p.Rt1[:] = self.Rt1.tolist(); p.Rt2[:] = self.Rt2.tolist()
+        p.cam1, p.cam2 = self.cam1, self.cam2
+        return p
+
+    def find(self, sets, aids=False):
+        """sets [iterations, 3]: indices into the correspondences.  Returns dict(converged, best_it, n_inliers, iterations_used, T12 [4, 4],
+        R12 [3, 3], t12 [3], s12, inliers [N]) and with aids the per-iteration it_inliers, it_T12, it_T21, it_scale."""
+        return Sim3Solver.solve_candidates([self], [sets], aids=aids, ctx=self.ctx)[0]
+
+    @staticmethod
+    def solve_candidates(solvers, sets_list, aids=False, ctx=None):
+        """one eorb_sim3_ransac call for K solvers (LoopClosing builds one per BoW candidate) -> a list of find()'s dicts"""
+        c = ctx or solvers[0].ctx
+        K = len(solvers)
+        sets_list = [np.ascontiguousarray(s, np.int32) for s in sets_list]
+        assert len(sets_list) == K and all(s.ndim == 2 and s.shape[1] == 3 for s in sets_list)
+        probs = (_lib.Sim3Problem * K)(*[s.problem(len(st)) for s, st in zip(solvers, sets_list)])
+        Xw1 = np.concatenate([s.Xw1 for s in solvers]); Xw2 = np.concatenate([s.Xw2 for s in solvers])
+        sg1 = np.concatenate([s.sigma2_1 for s in solvers]); sg2 = np.concatenate([s.sigma2_2 for s in solvers])
+        sets = np.concatenate(sets_list)
+        tN, tI = len(Xw1), len(sets)
+        res = (_lib.Sim3Result * K)()
+        inl = np.zeros(tN, np.uint8)
+        a = dict(it_inliers=np.zeros(tI, np.int32), it_T12=np.zeros((tI, 4, 4), np.float32), it_T21=np.zeros((tI, 4, 4), np.float32),
+                 it_scale=np.zeros(tI, np.float32)) if aids else {}
+        c.check(c.L.eorb_sim3_ransac(c.h, probs, K, _p(Xw1), _p(Xw2), _p(sg1), _p(sg2), _p(sets), res, _p(inl), _p(a.get("it_inliers")),
+                                     _p(a.get("it_T12")), _p(a.get("it_T21")), _p(a.get("it_scale"))))
+        out, n0, i0 = [], 0, 0
+        for k, (s, st) in enumerate(zip(solvers, sets_list)):
+            r = res[k]
+            o = dict(inliers=inl[n0:n0 + s.N].copy(), converged=int(r.converged), best_it=int(r.best_it), n_inliers=int(r.n_inliers),
+                     iterations_used=int(r.iterations_used), T12=np.array(r.T12, np.float32).reshape(4, 4),
+                     R12=np.array(r.R12, np.float32).reshape(3, 3), t12=np.array(r.t12, np.float32), s12=np.float32(r.s12))
+            o.update({key: v[i0:i0 + len(st)].copy() for key, v in a.items()})
+            out.append(o)
+            n0 += s.N; i0 += len(st)
+        return out
+
+
 class ELK_Tracker:
     """EORB_SLAM::ELK_Tracker (src/Event/KLT_Tracker.cpp): pyramidal LK on the device + the reference's match bookkeeping."""
 

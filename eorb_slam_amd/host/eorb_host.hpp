@@ -1214,6 +1214,117 @@ private:
     float mK[9]; float mSigma; int mMaxIterations;
 };
 
+// Sim3Solver (src/Sim3Solver.cc) on the calling thread's context, over correspondences the adapter has compacted: the constructor's filter
+// (:71-91: null, isBad, index < 0) stays with it, and so do the set draw and the g2o::Sim3 composition.  The first
+// iterate() / find() makes ONE device call for all mRansacMaxIts iterations; iterate(n, ...) then replays its chunk of the loop from the
+// per-iteration counts and transforms, so "while(!bConverge && !bNoMore) iterate(20, ...)" (LoopClosing.cc:698-701) returns what the
+// reference returns, chunk by chunk.  GetEstimated* give the state that loop ends in (the reference's mBest* once it has ended).
+class Sim3Solver {
+public:
+    typedef std::vector<float> Mat;        // a 4x4 / 3x3 / 3x1 float matrix, row-major; empty = cv::Mat()
+
+    // Xw1 / Xw2: 3 floats per correspondence (GetWorldPos of both sides); Rt1 / Rt2: Rcw row-major then tcw of pKF1 / pKF2;
+    // sigma2_1 / sigma2_2: getKPtLevelSigma2 per correspondence.  vnIndices1 / N1 (optional): mvnIndices1 and mN1, for vbInliers.
+    Sim3Solver(const std::vector<float>& Xw1, const std::vector<float>& Xw2, const float Rt1[12], const float Rt2[12], const eorb_camera& cam1,
+               const eorb_camera& cam2, const std::vector<float>& sigma2_1, const std::vector<float>& sigma2_2, bool bFixScale = true,
+               const std::vector<int>& vnIndices1 = std::vector<int>(), int N1 = -1)
+        : mXw1(Xw1), mXw2(Xw2), mSigma1(sigma2_1), mSigma2(sigma2_2), mvnIndices1(vnIndices1), N((int)(Xw1.size() / 3)), mbFixScale(bFixScale) {
+        for (int i = 0; i < 12; i++) { mProblem.Rt1[i] = Rt1[i]; mProblem.Rt2[i] = Rt2[i]; }
+        mProblem.cam1 = cam1; mProblem.cam2 = cam2;
+        if (mvnIndices1.empty()) for (int i = 0; i < N; i++) mvnIndices1.push_back(i);
+        mN1 = N1 < 0 ? N : N1;
+        SetRansacParameters();
+    }
+    // :126-150.  "int nIterations = ceil(...)" of a value no int holds converts as the reference's x86 build does (INT_MIN -> 1 iteration)
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacMaxIts = maxIterations;
+        const float epsilon = (float)mRansacMinInliers / N;
+        int nIterations;
+        if (mRansacMinInliers == N) nIterations = 1;
+        else {
+            const double v = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow((double)epsilon, 3)));
+            nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
+        }
+        mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+        mnIterations = 0; mnBestInliers = 0; mSolved = false;
+    }
+    int GetMaxIterations() const { return mRansacMaxIts; }
+    // the minimal sets of :178-189 from the adapter's generator: randomInt(min, max) = DUtils::Random::RandomInt
+    template <class RandomInt> void DrawSets(RandomInt&& randomInt) {
+        mvSets.clear();
+        std::vector<int32_t> all((size_t)N), avail;
+        for (int i = 0; i < N; i++) all[i] = i;
+        for (int it = 0; it < mRansacMaxIts; it++) {
+            avail = all;
+            for (int i = 0; i < 3; i++) {
+                const int randi = randomInt(0, (int)avail.size() - 1);
+                mvSets.push_back(avail[randi]);
+                avail[randi] = avail.back(); avail.pop_back();
+            }
+        }
+        mSolved = false;
+    }
+    void SetSets(const std::vector<int32_t>& vSets) { mvSets = vSets; mSolved = false; }      // mRansacMaxIts x 3 indices
+
+    Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, bool& bConverge) {      // :221-297
+        bNoMore = false; bConverge = false;
+        vbInliers = std::vector<bool>(mN1, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers) { bNoMore = true; return Mat(); }
+        solve();
+        int nCurrentIterations = 0;
+        Mat bestSim3;
+        while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+            const int it = mnIterations;
+            nCurrentIterations++; mnIterations++;
+            if (mItInliers[it] >= mnBestInliers) {
+                mnBestInliers = mItInliers[it];
+                const Mat T12(mItT12.begin() + 16 * (size_t)it, mItT12.begin() + 16 * (size_t)it + 16);
+                if (mItInliers[it] > mRansacMinInliers) {        // (the device's winner: its flags are this iteration's)
+                    nInliers = mItInliers[it];
+                    for (int i = 0; i < N; i++) if (mvbBestInliers[i]) vbInliers[mvnIndices1[i]] = true;
+                    bConverge = true;
+                    return T12;
+                }
+                bestSim3 = T12;
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return bestSim3;
+    }
+    Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {                      // :152-219
+        bool bConverge;
+        const Mat T = iterate(nIterations, bNoMore, vbInliers, nInliers, bConverge);
+        return bConverge ? T : Mat();
+    }
+    Mat find(std::vector<bool>& vbInliers12, int& nInliers) { bool bFlag; return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers); }      // :299-303
+    Mat GetEstimatedRotation() const { return Mat(mResult.R12, mResult.R12 + 9); }
+    Mat GetEstimatedTranslation() const { return Mat(mResult.t12, mResult.t12 + 3); }
+    float GetEstimatedScale() const { return mResult.s12; }
+    const eorb_sim3_result& result() { solve(); return mResult; }
+    const std::vector<int32_t>& it_inliers() { solve(); return mItInliers; }
+    int mnIterations = 0;
+private:
+    void solve() {
+        if (mSolved) return;
+        auto& c = eorb_host::thread_context();
+        mProblem.N = N; mProblem.iters = (int)(mvSets.size() / 3); mProblem.fix_scale = mbFixScale; mProblem.min_inliers = mRansacMinInliers;
+        if (mProblem.iters != mRansacMaxIts) throw eorb_host::Error(EORB_E_ARG, "Sim3Solver: the sets do not cover mRansacMaxIts iterations (DrawSets / SetSets)");
+        mvbBestInliers.assign((size_t)N, 0); mItInliers.assign((size_t)mProblem.iters, 0); mItT12.assign((size_t)mProblem.iters * 16, 0.f);
+        c.check(eorb_sim3_ransac(c.get(), &mProblem, 1, mXw1.data(), mXw2.data(), mSigma1.data(), mSigma2.data(), mvSets.data(), &mResult,
+                                 mvbBestInliers.data(), mItInliers.data(), mItT12.data(), nullptr, nullptr));
+        mSolved = true;
+    }
+    std::vector<float> mXw1, mXw2, mSigma1, mSigma2;
+    std::vector<int> mvnIndices1;
+    std::vector<int32_t> mvSets, mItInliers;
+    std::vector<float> mItT12;
+    std::vector<uint8_t> mvbBestInliers;
+    eorb_sim3_problem mProblem{}; eorb_sim3_result mResult{};
+    int N, mN1 = 0; bool mbFixScale;
+    double mRansacProb = 0.99; int mRansacMinInliers = 6, mRansacMaxIts = 300, mnBestInliers = 0; bool mSolved = false;
+};
+
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423) for a batch of map points (CSR offsets into desc rows)
 inline std::vector<int> ComputeDistinctiveDescriptors(const eorb_host::Mat8& desc, const std::vector<int32_t>& offsets) {
     auto& c = eorb_host::thread_context();

@@ -655,6 +655,57 @@ int eorb_two_view_check_rt(eorb_ctx* ctx, const eorb_keypoint* kps1, int n1, con
         const uint8_t* inliers, const float* K, float th2, float min_parallax_crt, int min_triangulated,
         const eorb_tvr_pose* poses, int Kp, int32_t* n_good, uint8_t* good, float* p3d, float* cos_sel, float* cos_all);
 
+/* ---- Sim3Solver (src/Sim3Solver.cc): Horn's closed form and its RANSAC loop ------------------------------------------------------------
+ * The stage between SearchByBoW(KF, KF) and SearchByProjection(KF, Scw) in LoopClosing::DetectCommonRegionsFromBoW
+ * (src/LoopClosing.cc:690-701): one solver per BoW candidate, so one call solves K independent problems; a single solver is K = 1.
+ * What stays with the caller: the constructor's filter (:71-91: null, isBad, index < 0) and the mvnIndices1 map, the iteration count of
+ * SetRansacParameters (:137-147), the set draw (DUtils::Random, :178-189), and the g2o::Sim3 composition after the solver.
+ *
+ * Limits, decided from the sizes before any array is read (EORB_E_CAPACITY): */
+#define EORB_S3_MAX_ITERS     1024
+#define EORB_S3_MAX_CORR      16384   /* per problem */
+#define EORB_S3_MAX_PROBLEMS  64
+/* One problem.  The per-correspondence and per-set arrays of a call are flat: problem k owns the N correspondences after those of the
+ * problems before it (rows sum(N[0..k)) ...), and the iters sets after theirs; the outputs inliers and it_* are laid out the same way. */
+typedef struct eorb_sim3_problem {
+    int32_t N;              /* correspondences the caller has already compacted (>= 3) */
+    int32_t iters;          /* mRansacMaxIts after SetRansacParameters (>= 1): the sets drawn for this problem */
+    int32_t fix_scale;      /* mbFixScale */
+    int32_t min_inliers;    /* mRansacMinInliers */
+    float Rt1[12], Rt2[12]; /* Rcw row-major then tcw of pKF1 / pKF2: the device computes mvX3Dc = Rcw*Xw + tcw (:107, :110) */
+    eorb_camera cam1, cam2; /* pCamera1 / pCamera2, either model */
+} eorb_sim3_problem;
+typedef struct eorb_sim3_result {
+    int32_t converged;        /* bConverge */
+    int32_t best_it;          /* the iteration the results come from, -1 when N < min_inliers */
+    int32_t n_inliers;        /* its count */
+    int32_t iterations_used;  /* mnIterations when "while(!bConverge && !bNoMore) iterate(20, ...)" ends */
+    float T12[16], R12[9], t12[3], s12;      /* mBestT12, mBestRotation, mBestTranslation, mBestScale */
+} eorb_sim3_result;
+
+/* Sim3Solver::iterate (:221-297) run to its end for K problems: ComputeSim3 (:316-427) and CheckInliers (:430-454) of every set, then the
+ * state the loop of LoopClosing.cc:698-701 is left in.
+ * Xw1 / Xw2 [sum N][3]: GetWorldPos() of both sides; sigma2_1 / sigma2_2 [sum N]: getKPtLevelSigma2 per correspondence (a mixed keyframe
+ * passes its AKAZE sigmas the same way); sets [sum iters][3]: indices into the problem's own N correspondences, drawn by the caller
+ * (repeated indices inside a set are accepted: the arithmetic is defined).
+ * The inlier bound is the reference's: mvnMaxError is a vector<size_t> (include/Sim3Solver.h:78-79), so 9.210*sigma2 is truncated to an
+ * integer and err < bound compares the float error with that integer (:446): 9 at sigma2 = 1, and 0 -- no inlier ever -- at 0.1.
+ * The result rule (:268-290): the running best starts at 0 and is replaced on >=, so among equal counts the later iteration wins; the
+ * first iteration whose count is > min_inliers ends the search (any earlier best was <= min_inliers); a count equal to min_inliers does
+ * not converge.  N < min_inliers (:228-232): converged = 0, best_it = -1, iterations_used = 0, everything else zero.  When nothing
+ * converges the running best is returned anyway, with converged = 0 and iterations_used = iters; the reference hands back only what the
+ * last chunk of 20 improved, and its caller ignores that unless bConverge.
+ * results[K]; inliers[sum N] (0 / 1, in compacted order).  Test aids, NULL to skip, with which a caller can replay any chunking of
+ * iterate: it_inliers[sum iters], it_T12[sum iters * 16], it_T21[sum iters * 16], it_scale[sum iters] (zeros for a problem with
+ * N < min_inliers).  Identical point triples give an all-NaN transform with 0 inliers (:370, 0/0), as in the reference.
+ * EORB_E_ARG: K < 1, N < 3, iters < 1, min_inliers < 0, a set index outside [0, N), a sigma2 that is negative, NaN or >= 1e15 (its
+ * conversion to size_t is undefined in the source).  EORB_E_CONFIG: a camera model other than 0 / 1.  No output is written on an error.
+ * The OpenCV 3.4.1 arithmetic (reduce, gemm, JacobiImpl_<float> of cv::eigen, Rodrigues, the MatExpr folds) is restated on its scalar
+ * paths: DESIGN.md section 2. */
+int eorb_sim3_ransac(eorb_ctx* ctx, const eorb_sim3_problem* problems, int K, const float* Xw1, const float* Xw2,
+        const float* sigma2_1, const float* sigma2_2, const int32_t* sets,
+        eorb_sim3_result* results, uint8_t* inliers, int32_t* it_inliers, float* it_T12, float* it_T21, float* it_scale);
+
 /* replaces the search core shared by ORBmatcher::Fuse (src/ORBmatcher.cc:1512-1578 and :1700-1720), SearchBySim3
  * (:1829-1860, :1909-1940) and SearchByProjection(KeyFrame*, Scw, ...) (:548-588, :667-706): for every projected map point
  * m (valid[m], uv, radius = th*getORBScaleFactor(level), predicted level, descriptor) the best keypoint among
