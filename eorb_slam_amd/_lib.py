@@ -30,7 +30,7 @@ EXPORTS = [
     "eorb_search_by_bow_kf_keyframes",
     "eorb_kfdb_clear", "eorb_kfdb_add", "eorb_kfdb_erase", "eorb_kfdb_info", "eorb_kfdb_get_scores", "eorb_kfdb_detect_reloc", "eorb_kfdb_detect_nbest",
     "eorb_two_view_ransac", "eorb_two_view_check_rt",
-    "eorb_sim3_ransac",
+    "eorb_sim3_ransac", "eorb_mlpnp_ransac",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
 ]
@@ -141,6 +141,21 @@ class Sim3Result(C.Structure):
 
 
 S3_MAX_ITERS, S3_MAX_CORR, S3_MAX_PROBLEMS = 1024, 16384, 64
+
+
+class MlpnpProblem(C.Structure):
+    """eorb_mlpnp_problem: one MLPnPsolver (its correspondences and sets follow those of the problems before it in the flat arrays)"""
+    _fields_ = [("N", C.c_int32), ("iters", C.c_int32), ("min_inliers", C.c_int32), ("th2", C.c_float), ("cam", Camera),
+                ("first_it", C.c_int32), ("best_it", C.c_int32)]
+
+
+class MlpnpResult(C.Structure):
+    """eorb_mlpnp_result: where Refine returned true, mnIterations, the running best, mRefinedTcw or mBestTcw and its count"""
+    _fields_ = [("stop_it", C.c_int32), ("iterations_used", C.c_int32), ("best_it", C.c_int32), ("n_best", C.c_int32),
+                ("refined", C.c_int32), ("n_inliers", C.c_int32), ("Tcw", C.c_float * 16)]
+
+
+PNP_MAX_ITERS, PNP_MAX_CORR, PNP_MAX_PROBLEMS = 1024, 4096, 64
 
 
 class KltParams(C.Structure):
@@ -387,6 +402,8 @@ def lib():
                                        vp, vp, vp, vp]
     L.eorb_sim3_ransac.restype = ci
     L.eorb_sim3_ransac.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.eorb_mlpnp_ransac.restype = ci
+    L.eorb_mlpnp_ransac.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.eorb_two_view_check_rt.restype = ci
     L.eorb_two_view_check_rt.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, cf, cf, ci, vp, ci, vp, vp, vp, vp, vp]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]

@@ -6,6 +6,7 @@
 #include "kfdb.h"
 #include "twoview.h"
 #include "sim3.h"
+#include "mlpnp.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -2782,6 +2783,76 @@ int eorb_sim3_ransac(eorb_ctx* c, const eorb_sim3_problem* problems, int K, cons
     if (it_scale) memcpy(it_scale, h + o_sc, sizeof(float) * tI);
     if (it_T12) memcpy(it_T12, h + o_t12, sizeof(float) * 16 * tI);
     if (it_T21) memcpy(it_T21, h + o_t21, sizeof(float) * 16 * tI);
+    return EORB_OK;
+}
+
+int eorb_mlpnp_ransac(eorb_ctx* c, const eorb_mlpnp_problem* problems, int K, const float* p2d, const float* Xw, const float* sigma2,
+        const int32_t* sets, eorb_mlpnp_result* results, uint8_t* inliers, int32_t* it_inliers, double* it_Rt, int32_t* it_refine_inliers)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "mlpnp_ransac";
+    if (!problems || !p2d || !Xw || !sigma2 || !sets || !results || !inliers) return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    if (K < 1) return set_err(c, EORB_E_ARG, "%s: %d problems (at least 1)", what, K);
+    if (K > EORB_PNP_MAX_PROBLEMS) return set_err(c, EORB_E_CAPACITY, "%s: %d problems, at most EORB_PNP_MAX_PROBLEMS = %d", what, K, EORB_PNP_MAX_PROBLEMS);
+    // sizes first (no array is read), then the cameras, then the sets
+    std::vector<PnpProb> pv((size_t)K);
+    size_t tN = 0, tI = 0;
+    int max_N = 0, max_iters = 0;
+    for (int k = 0; k < K; k++) {
+        const eorb_mlpnp_problem& p = problems[k];
+        if (p.N < 6 || p.iters < 1 || p.min_inliers < 6)
+            return set_err(c, EORB_E_ARG, "%s: problem %d has %d correspondences (at least 6), %d iterations (at least 1), min_inliers %d (at least 6)", what, k,
+                           p.N, p.iters, p.min_inliers);
+        if (p.N > EORB_PNP_MAX_CORR) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d correspondences, at most EORB_PNP_MAX_CORR = %d", what, k, p.N, EORB_PNP_MAX_CORR);
+        if (p.iters > EORB_PNP_MAX_ITERS) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d iterations, at most EORB_PNP_MAX_ITERS = %d", what, k, p.iters, EORB_PNP_MAX_ITERS);
+        if (p.first_it < 0 || p.first_it >= p.iters || p.best_it < -1 || p.best_it >= p.first_it)
+            return set_err(c, EORB_E_ARG, "%s: problem %d resumes at iteration %d of %d with the best %d (first_it in [0, iters), best_it in [-1, first_it))", what, k,
+                           p.first_it, p.iters, p.best_it);
+        PnpProb& d = pv[k];
+        d.N = p.N; d.iters = p.iters; d.corr_off = (int)tN; d.set_off = (int)tI; d.min_inliers = p.min_inliers; d.first_it = p.first_it; d.best_it = p.best_it;
+        d.th2 = p.th2; d.cam = warp_cam_of(p.cam);
+        tN += (size_t)p.N; tI += (size_t)p.iters;
+        max_N = std::max(max_N, p.N); max_iters = std::max(max_iters, p.iters);
+    }
+    for (int k = 0; k < K; k++)
+        if (problems[k].cam.model != 0 && problems[k].cam.model != 1)
+            return set_err(c, EORB_E_CONFIG, "%s: problem %d has a camera model other than Pinhole (0) / KannalaBrandt8 (1)", what, k);
+    for (int k = 0; k < K; k++) {
+        const PnpProb& d = pv[k];
+        for (int i = 0; i < 6 * d.iters; i++) {
+            const int32_t s = sets[6 * (size_t)d.set_off + i];
+            if (s < 0 || s >= d.N) return set_err(c, EORB_E_ARG, "%s: problem %d, set %d holds the index %d of %d correspondences", what, k, i / 6, s, d.N);
+        }
+    }
+    fe_enter(c);
+    int rc;
+    Arena A(c);
+    const size_t o_pr = A.in(pv.data(), sizeof(PnpProb) * (size_t)K);
+    const size_t o_p2 = A.in(p2d, sizeof(float) * 2 * tN), o_xw = A.in(Xw, sizeof(float) * 3 * tN), o_sg = A.in(sigma2, sizeof(float) * tN);
+    const size_t o_st = A.in(sets, sizeof(int32_t) * 6 * tI);
+    const size_t o_f = A.reserve(sizeof(double) * 3 * tN), o_ns = A.reserve(sizeof(double) * 6 * tN), o_x = A.reserve(sizeof(double) * 3 * tN);
+    const size_t o_bd = A.reserve(sizeof(float) * tN);
+    // results, contiguous and zero on entry: the K records | inliers | the per-iteration aids
+    const size_t o_res = A.reserve(sizeof(int32_t) * kPnpResWords * (size_t)K), o_inl = A.reserve(tN);
+    const size_t o_cnt = A.reserve(sizeof(int32_t) * tI), o_rfn = A.reserve(sizeof(int32_t) * tI), o_rt = A.reserve(sizeof(double) * 12 * tI), o_end = A.reserve(0);
+    if ((rc = A.upload())) return rc;
+    EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_res), 0, o_end - o_res, c->stream));
+    PnpArgs T{};
+    T.prob = A.dev<PnpProb>(o_pr); T.K = K; T.max_N = max_N; T.max_iters = max_iters;
+    T.p2d = A.dev<float>(o_p2); T.Xw = A.dev<float>(o_xw); T.sigma2 = A.dev<float>(o_sg); T.sets = A.dev<int32_t>(o_st);
+    T.f = A.dev<double>(o_f); T.ns = A.dev<double>(o_ns); T.X = A.dev<double>(o_x); T.bound = A.dev<float>(o_bd);
+    T.res = A.dev<int32_t>(o_res); T.inliers = A.dev<uint8_t>(o_inl); T.it_inliers = A.dev<int32_t>(o_cnt); T.it_refine = A.dev<int32_t>(o_rfn);
+    T.it_Rt = A.dev<double>(o_rt);
+    if ((rc = mlpnp_ransac_dev(c, T))) return rc;
+    const bool aids = it_inliers || it_Rt || it_refine_inliers;
+    const char* h;
+    if ((rc = A.download(o_res, (aids ? o_end : o_cnt) - o_res, &h))) return rc;
+    static_assert(sizeof(eorb_mlpnp_result) == sizeof(int32_t) * kPnpResWords, "eorb_mlpnp_result is kPnpResWords words");
+    memcpy(results, h + o_res, sizeof(eorb_mlpnp_result) * (size_t)K);
+    memcpy(inliers, h + o_inl, tN);
+    if (it_inliers) memcpy(it_inliers, h + o_cnt, sizeof(int32_t) * tI);
+    if (it_refine_inliers) memcpy(it_refine_inliers, h + o_rfn, sizeof(int32_t) * tI);
+    if (it_Rt) memcpy(it_Rt, h + o_rt, sizeof(double) * 12 * tI);
     return EORB_OK;
 }
 

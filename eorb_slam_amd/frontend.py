@@ -1432,6 +1432,122 @@ class Sim3Solver:
         return out
 
 
+def mlpnp_ransac_parameters(N, probability=0.99, min_inliers=10, max_iterations=300, min_set=6, epsilon=0.5):
+    """MLPnPsolver::SetRansacParameters (src/MLPnPsolver.cpp:268-298) -> (mRansacMinInliers, mRansacMaxIts).  mRansacEpsilon is a float:
+    int(N*epsilon) is a float product truncated, and epsilon is raised to minInliers/N in float; pow / log / ceil in double.
+    `int nIterations = ceil(...)` of a value no int holds converts as the reference's x86 build does (cvttsd2si: INT_MIN), which
+    max(1, min(...)) turns into 1."""
+    eps = np.float32(epsilon)
+    n_min = max(int(np.float32(N) * eps), int(min_inliers), int(min_set))
+    if eps < np.float32(n_min) / np.float32(N):
+        eps = np.float32(n_min) / np.float32(N)
+    if n_min == N:
+        n = 1
+    else:
+        with np.errstate(all="ignore"):
+            v = np.ceil(np.log(np.float64(1 - probability)) / np.log(np.float64(1) - np.float64(eps) ** 3))
+        n = int(v) if np.isfinite(v) and -2147483648.0 <= v < 2147483648.0 else -2147483648
+    return n_min, max(1, min(n, int(max_iterations)))
+
+
+def mlpnp_draw_sets(N, iterations, seed):
+    """the minimal sets of MLPnPsolver::iterate (:176-188) on a numpy generator (the reference draws from DUtils::Random): six draws
+    without replacement, the drawn slot refilled with the back of vAvailableIndices.  -> [iterations, 6] int32"""
+    rng = np.random.default_rng(seed)
+    sets = np.zeros((iterations, 6), np.int32)
+    for it in range(iterations):
+        moved = {}
+        for i in range(6):
+            size = N - i
+            randi = int(rng.integers(0, size))
+            sets[it, i] = moved.get(randi, randi)
+            moved[randi] = moved.get(size - 1, size - 1)
+    return sets
+
+
+class MLPnPsolver:
+    """MLPnPsolver (src/MLPnPsolver.cpp) over correspondences the caller has compacted (the constructor's filter :67-96 and
+    mvKeyPointIndices stay with the caller): p2d [N, 2] the undistorted keypoints, Xw [N, 3] GetWorldPos(), sigma2 getKPtLevelSigma2 per
+    correspondence (or one value), cam as (fx, fy, cx, cy[, k1..k4[, precision]]).  find() runs iterate to its end on the device;
+    solve_candidates() runs one solver per relocalisation candidate in one call; iterate() is the reference's chunked loop."""
+
+    def __init__(self, p2d, Xw, sigma2, cam, ctx=None):
+        self.p2d = np.ascontiguousarray(p2d, np.float32).reshape(-1, 2); self.Xw = np.ascontiguousarray(Xw, np.float32).reshape(-1, 3)
+        self.N = len(self.p2d)
+        assert len(self.Xw) == self.N
+        self.sigma2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma2, np.float32), (self.N,)))
+        self.cam = _lib.camera(cam)
+        self.ctx = ctx or default_context()
+        self.set_ransac_parameters()
+
+    def set_ransac_parameters(self, probability=0.99, min_inliers=10, max_iterations=300, min_set=6, epsilon=0.5, th2=5.991):
+        """SetRansacParameters (:268-303) -> the iteration count; resets the loop state of iterate()"""
+        self.th2 = float(th2)
+        self.min_inliers, self.iters = mlpnp_ransac_parameters(self.N, probability, min_inliers, max_iterations, min_set, epsilon)
+        self.mnIterations, self._best_it, self._sets = 0, -1, None
+        return self.iters
+
+    def draw_sets(self, seed, iterations=None):
+        return mlpnp_draw_sets(self.N, self.iters if iterations is None else iterations, seed)
+
+    def problem(self, iters, first_it=0, best_it=-1):
+        p = _lib.MlpnpProblem()
+        p.N, p.iters, p.min_inliers, p.th2, p.cam, p.first_it, p.best_it = self.N, int(iters), self.min_inliers, self.th2, self.cam, int(first_it), int(best_it)
+        return p
+
+    def find(self, sets, aids=False, first_it=0, best_it=-1):
+        """sets [iterations, 6]: indices into the correspondences.  Returns dict(stop_it, iterations_used, best_it, n_best, refined,
+        n_inliers, Tcw [4, 4], inliers [N]) and with aids the per-iteration it_inliers, it_Rt, it_refine_inliers.  refined: Tcw and inliers
+        are those of the hypothesis stop_it, the first with more than min_inliers inliers, which is what the reference's Refine returns
+        (it never stores the pose it computes: include/eorb_fe.h)."""
+        return MLPnPsolver.solve_candidates([self], [sets], aids, [first_it], [best_it], ctx=self.ctx)[0]
+
+    @staticmethod
+    def solve_candidates(solvers, sets_list, aids=False, first_its=None, best_its=None, ctx=None):
+        """one eorb_mlpnp_ransac call for K solvers (Relocalization builds one per candidate keyframe) -> a list of find()'s dicts"""
+        c = ctx or solvers[0].ctx
+        K = len(solvers)
+        sets_list = [np.ascontiguousarray(s, np.int32) for s in sets_list]
+        assert len(sets_list) == K and all(s.ndim == 2 and s.shape[1] == 6 for s in sets_list)
+        first_its = first_its or [0] * K; best_its = best_its or [-1] * K
+        probs = (_lib.MlpnpProblem * K)(*[s.problem(len(st), f, b) for s, st, f, b in zip(solvers, sets_list, first_its, best_its)])
+        p2d = np.concatenate([s.p2d for s in solvers]); Xw = np.concatenate([s.Xw for s in solvers]); sg = np.concatenate([s.sigma2 for s in solvers])
+        sets = np.concatenate(sets_list)
+        tN, tI = len(p2d), len(sets)
+        res = (_lib.MlpnpResult * K)()
+        inl = np.zeros(tN, np.uint8)
+        a = dict(it_inliers=np.zeros(tI, np.int32), it_Rt=np.zeros((tI, 12), np.float64), it_refine_inliers=np.zeros(tI, np.int32)) if aids else {}
+        c.check(c.L.eorb_mlpnp_ransac(c.h, probs, K, _p(p2d), _p(Xw), _p(sg), _p(sets), res, _p(inl), _p(a.get("it_inliers")), _p(a.get("it_Rt")),
+                                      _p(a.get("it_refine_inliers"))))
+        out, n0, i0 = [], 0, 0
+        for k, (s, st) in enumerate(zip(solvers, sets_list)):
+            r = res[k]
+            o = dict(inliers=inl[n0:n0 + s.N].copy(), stop_it=int(r.stop_it), iterations_used=int(r.iterations_used), best_it=int(r.best_it),
+                     n_best=int(r.n_best), refined=int(r.refined), n_inliers=int(r.n_inliers), Tcw=np.array(r.Tcw, np.float32).reshape(4, 4))
+            o.update({key: v[i0:i0 + len(st)].copy() for key, v in a.items()})
+            out.append(o)
+            n0 += s.N; i0 += len(st)
+        return out
+
+    def iterate(self, nIterations, sets):
+        """iterate(nIterations, bNoMore, vbInliers, nInliers) (:149-266) on the sets drawn so far -> (Tcw or None, bNoMore, inliers,
+        nInliers).  The loop condition is mnIterations < mRansacMaxIts || nCurrentIterations < nIterations: the first call runs to the
+        maximum unless Refine returns, every later call runs nIterations more.  sets [>= the iterations this call can reach, 6]: the
+        same array on every call, longer if need be; iteration i always uses sets[i]."""
+        if self.N < self.min_inliers:
+            return None, True, np.zeros(self.N, np.uint8), 0
+        sets = np.ascontiguousarray(sets, np.int32)
+        end = max(self.iters, self.mnIterations + int(nIterations))
+        assert len(sets) >= end, "iterate: %d sets, the call can reach iteration %d" % (len(sets), end)
+        o = self.find(sets[:end], first_it=self.mnIterations, best_it=self._best_it)
+        self.mnIterations, self._best_it = o["iterations_used"], o["best_it"]
+        if o["refined"]:
+            return o["Tcw"], False, o["inliers"], o["n_inliers"]
+        if o["n_best"] >= self.min_inliers:
+            return o["Tcw"], True, o["inliers"], o["n_inliers"]
+        return None, True, o["inliers"], 0
+
+
 class ELK_Tracker:
     """EORB_SLAM::ELK_Tracker (src/Event/KLT_Tracker.cpp): pyramidal LK on the device + the reference's match bookkeeping."""
 

@@ -1325,6 +1325,94 @@ private:
     double mRansacProb = 0.99; int mRansacMinInliers = 6, mRansacMaxIts = 300, mnBestInliers = 0; bool mSolved = false;
 };
 
+// ORB_SLAM3::MLPnPsolver (src/MLPnPsolver.cpp) over correspondences the adapter has compacted (the constructor's filter :67-96 stays with
+// it; vKeyPointIndices / nKeyPoints carry mvKeyPointIndices and mvpMapPointMatches.size() for vbInliers).  Every iterate(n, ...) is one
+// device call that walks the iterations this call of the reference's loop covers, resumed from the running best of the calls before it
+// (first_it / best_it of eorb_mlpnp_problem), so "iterate(5, ...)" of Tracking.cc:2716-2729 returns what the reference returns, call by call.
+class MLPnPsolver {
+public:
+    typedef std::vector<float> Mat;        // a 4x4 float matrix, row-major; empty = cv::Mat()
+
+    // p2d: 2 floats per correspondence (the undistorted keypoint); Xw: 3 floats (GetWorldPos); sigma2: getKPtLevelSigma2
+    MLPnPsolver(const std::vector<float>& p2d, const std::vector<float>& Xw, const std::vector<float>& sigma2, const eorb_camera& cam,
+                const std::vector<int>& vKeyPointIndices = std::vector<int>(), int nKeyPoints = -1)
+        : mP2D(p2d), mXw(Xw), mSigma2(sigma2), mvKeyPointIndices(vKeyPointIndices), N((int)(Xw.size() / 3)) {
+        mProblem.cam = cam;
+        if (mvKeyPointIndices.empty()) for (int i = 0; i < N; i++) mvKeyPointIndices.push_back(i);
+        mnKeyPoints = nKeyPoints < 0 ? N : nKeyPoints;
+        SetRansacParameters();
+    }
+    // :268-303.  mRansacEpsilon is a float; "int nIterations = ceil(...)" of a value no int holds converts as the reference's x86 build
+    // does (INT_MIN -> 1 iteration)
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 6, float epsilon = 0.4f,
+                             float th2 = 5.991f) {
+        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacMaxIts = maxIterations; mRansacEpsilon = epsilon; mRansacMinSet = minSet;
+        int nMinInliers = (int)(N * mRansacEpsilon);
+        if (nMinInliers < mRansacMinInliers) nMinInliers = mRansacMinInliers;
+        if (nMinInliers < minSet) nMinInliers = minSet;
+        mRansacMinInliers = nMinInliers;
+        if (mRansacEpsilon < (float)mRansacMinInliers / N) mRansacEpsilon = (float)mRansacMinInliers / N;
+        int nIterations;
+        if (mRansacMinInliers == N) nIterations = 1;
+        else {
+            const double v = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow((double)mRansacEpsilon, 3)));
+            nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
+        }
+        mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+        mTh2 = th2;
+        mnIterations = 0; mnBestIt = -1;
+    }
+    int GetMaxIterations() const { return mRansacMaxIts; }
+    int GetMinInliers() const { return mRansacMinInliers; }
+    // the minimal sets of :176-188 from the adapter's generator, for nSets iterations (at least what the calls of iterate will reach):
+    // randomInt(min, max) = DUtils::Random::RandomInt.  Sets already drawn stay; more are appended.
+    template <class RandomInt> void DrawSets(RandomInt&& randomInt, int nSets) {
+        std::vector<int32_t> all((size_t)N), avail;
+        for (int i = 0; i < N; i++) all[i] = i;
+        for (int it = (int)(mvSets.size() / 6); it < nSets; it++) {
+            avail = all;
+            for (int i = 0; i < 6; i++) {
+                const int randi = randomInt(0, (int)avail.size() - 1);
+                mvSets.push_back(avail[randi]);
+                avail[randi] = avail.back(); avail.pop_back();
+            }
+        }
+    }
+    void SetSets(const std::vector<int32_t>& vSets) { mvSets = vSets; }      // 6 indices per iteration
+    const std::vector<int32_t>& sets() const { return mvSets; }
+
+    Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {      // :149-266
+        bNoMore = false; vbInliers.clear(); nInliers = 0;
+        if (N < mRansacMinInliers) { bNoMore = true; return Mat(); }
+        // while (mnIterations < mRansacMaxIts || nCurrentIterations < nIterations): the first call runs to the maximum, later ones n more
+        const int end = std::max(mRansacMaxIts, mnIterations + nIterations);
+        if ((int)(mvSets.size() / 6) < end) throw eorb_host::Error(EORB_E_ARG, "MLPnPsolver: the sets do not cover the iterations of this call (DrawSets / SetSets)");
+        auto& c = eorb_host::thread_context();
+        mProblem.N = N; mProblem.iters = end; mProblem.min_inliers = mRansacMinInliers; mProblem.th2 = mTh2;
+        mProblem.first_it = mnIterations; mProblem.best_it = mnBestIt;
+        std::vector<uint8_t> flags((size_t)N, 0);
+        c.check(eorb_mlpnp_ransac(c.get(), &mProblem, 1, mP2D.data(), mXw.data(), mSigma2.data(), mvSets.data(), &mResult, flags.data(),
+                                  nullptr, nullptr, nullptr));
+        mnIterations = mResult.iterations_used; mnBestIt = mResult.best_it;
+        const bool best = !mResult.refined && mResult.n_best >= mRansacMinInliers;
+        if (!mResult.refined) bNoMore = true;      // (the walk ran to its end, which is at or beyond mRansacMaxIts)
+        if (!mResult.refined && !best) return Mat();
+        nInliers = mResult.n_inliers;
+        vbInliers = std::vector<bool>((size_t)mnKeyPoints, false);
+        for (int i = 0; i < N; i++) if (flags[i]) vbInliers[mvKeyPointIndices[i]] = true;
+        return Mat(mResult.Tcw, mResult.Tcw + 16);
+    }
+    const eorb_mlpnp_result& result() const { return mResult; }
+    int mnIterations = 0;
+private:
+    std::vector<float> mP2D, mXw, mSigma2;
+    std::vector<int> mvKeyPointIndices;
+    std::vector<int32_t> mvSets;
+    eorb_mlpnp_problem mProblem{}; eorb_mlpnp_result mResult{};
+    int N, mnKeyPoints = 0, mnBestIt = -1;
+    double mRansacProb = 0.99; int mRansacMinInliers = 8, mRansacMaxIts = 300, mRansacMinSet = 6; float mRansacEpsilon = 0.4f, mTh2 = 5.991f;
+};
+
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423) for a batch of map points (CSR offsets into desc rows)
 inline std::vector<int> ComputeDistinctiveDescriptors(const eorb_host::Mat8& desc, const std::vector<int32_t>& offsets) {
     auto& c = eorb_host::thread_context();

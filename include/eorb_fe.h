@@ -706,6 +706,65 @@ int eorb_sim3_ransac(eorb_ctx* ctx, const eorb_sim3_problem* problems, int K, co
         const float* sigma2_1, const float* sigma2_2, const int32_t* sets,
         eorb_sim3_result* results, uint8_t* inliers, int32_t* it_inliers, float* it_T12, float* it_T21, float* it_scale);
 
+/* ---- MLPnPsolver (src/MLPnPsolver.cpp): the pose RANSAC of Tracking::Relocalization ---------------------------------------------------
+ * The stage between SearchByBoW(KF, F) and PoseOptimization in Tracking::Relocalization (src/Tracking.cc:2697-2729): one solver per
+ * candidate keyframe, so one call solves K independent problems; a single solver is K = 1.
+ * What stays with the caller: the constructor's filter (:67-96: null, isBad) and mvKeyPointIndices, the iteration count and the minimum
+ * inliers of SetRansacParameters (:268-298), the set draw (DUtils::Random, :176-188), and everything after the solver.
+ * What the device computes: the bearing vectors (unproject of the undistorted keypoint, then /= z, in float, either camera model,
+ * :80-82), mvMaxError[i] = sigma2[i]*th2 as a float product (:302), computePose (:395-701) with mlpnp_gn (:737-802) and
+ * mlpnp_residuals_and_jacs (:804-851), CheckInliers (:305-336), and what Refine (:338-392) returns (below).
+ *
+ * Limits, decided from the sizes before any array is read (EORB_E_CAPACITY).  The correspondence limit is a choice: a frame's BoW
+ * matches with one keyframe do not approach it. */
+#define EORB_PNP_MAX_ITERS     1024
+#define EORB_PNP_MAX_CORR      4096    /* per problem */
+#define EORB_PNP_MAX_PROBLEMS  64
+/* One problem; the flat layout of eorb_sim3_problem: problem k's correspondences and sets follow those of the problems before it. */
+typedef struct eorb_mlpnp_problem {
+    int32_t N;              /* correspondences the caller has already compacted (>= 6) */
+    int32_t iters;          /* the sets passed for this problem (>= 1): iterations [0, iters) of this solver */
+    int32_t min_inliers;    /* mRansacMinInliers after the clamps of :280-285 (>= 6: the reference's Refine calls computePose on that many points) */
+    float th2;              /* SetRansacParameters' th2 (5.991) */
+    eorb_camera cam;        /* F.mpCamera, either model */
+    int32_t first_it;       /* the iteration the walk starts at: 0 for a fresh solver */
+    int32_t best_it;        /* the running best carried in, an index into the same sets below first_it, or -1: a fresh solver */
+} eorb_mlpnp_problem;
+typedef struct eorb_mlpnp_result {
+    int32_t stop_it;          /* the iteration at which Refine returned true, else -1 */
+    int32_t iterations_used;  /* mnIterations when the walk ends: stop_it + 1, else iters; 0 when N < min_inliers */
+    int32_t best_it, n_best;  /* the running best the loop is left with (mvbBestInliers / mnBestInliers): -1, 0 when there is none */
+    int32_t refined;          /* 1: Tcw is mRefinedTcw and inliers are mvbRefinedInliers: the pose and flags of iteration stop_it */
+    int32_t n_inliers;        /* mnRefinedInliers (the count of iteration stop_it), else n_best when n_best >= min_inliers, else 0 */
+    float Tcw[16];            /* mRefinedTcw when refined, else mBestTcw when n_best >= min_inliers, else zeros */
+} eorb_mlpnp_result;
+
+/* MLPnPsolver::iterate (:149-266) run to its end for K problems.
+ * p2d [sum N][2]: the undistorted keypoints; Xw [sum N][3]: GetWorldPos(); sigma2 [sum N]: getKPtLevelSigma2; sets [sum iters][6]:
+ * indices into the problem's own N correspondences, drawn by the caller (repeated indices inside a set are accepted: the arithmetic is
+ * defined, and a set of fewer than six distinct points gives a rank-deficient system, a NaN or a poor pose, and few inliers).
+ * The result rule (:163-265).  The running best starts at 0 and is replaced on > only (:220), so among equal counts the earlier
+ * iteration stays.  An iteration whose count is >= min_inliers (:217) invokes Refine.  Refine (:338-392) runs computePose on the running
+ * best's inliers into a local `result` that it never stores (:367-371): mRi / mti are written only at :200-212, so its CheckInliers
+ * (:374) counts the current hypothesis again.  Hence mnRefinedInliers is this iteration's count, Refine returns true exactly when that
+ * is > min_inliers (:379, strict, unlike the trigger), and mRefinedTcw / mvbRefinedInliers are this iteration's pose and flags.  The
+ * pose Refine computes affects nothing that is returned, and the device does not compute it; this reproduces the reference, it does not
+ * repair it.  The call ends at the first iteration whose count is > min_inliers; a count equal to min_inliers becomes the running best
+ * and the walk goes on.  N < min_inliers (:154-158): stop_it = best_it = -1, iterations_used = 0, everything else zero.  When no Refine
+ * succeeds the running best is returned as :249-262 do.
+ * Resuming (Relocalization calls iterate(5, ...) again on a solver whose pose failed PoseOptimization) needs no device state: first_it
+ * is where the walk starts, best_it the running best carried in; the device computes that one hypothesis and its flags again.
+ * results[K]; inliers[sum N] (0 / 1, in compacted order).  Test aids, NULL to skip: it_inliers[sum iters]; it_Rt[sum iters][12] as
+ * double, mRi row-major then mti of every hypothesis; it_refine_inliers[sum iters]: mnRefinedInliers at every iteration the rule
+ * invoked Refine at (the iteration's own count again, up to and including stop_it), -1 elsewhere.  Iterations
+ * below first_it other than best_it are not computed: their aids are zero (it_refine_inliers -1).
+ * A NaN coordinate gives NaN errors, which fail their <.  EORB_E_ARG: K < 1, N < 6, iters < 1, min_inliers < 6, first_it outside
+ * [0, iters), best_it outside [-1, first_it), a set index outside [0, N).  EORB_E_CONFIG: a camera model other than 0 / 1.  No output is
+ * written on an error.  Eigen 3.3's algorithms (JacobiSVD, FullPivHouseholderQR, SelfAdjointEigenSolver, LDLT, the small products)
+ * are restated on their scalar paths: DESIGN.md section 2. */
+int eorb_mlpnp_ransac(eorb_ctx* ctx, const eorb_mlpnp_problem* problems, int K, const float* p2d, const float* Xw, const float* sigma2,
+        const int32_t* sets, eorb_mlpnp_result* results, uint8_t* inliers, int32_t* it_inliers, double* it_Rt, int32_t* it_refine_inliers);
+
 /* replaces the search core shared by ORBmatcher::Fuse (src/ORBmatcher.cc:1512-1578 and :1700-1720), SearchBySim3
  * (:1829-1860, :1909-1940) and SearchByProjection(KeyFrame*, Scw, ...) (:548-588, :667-706): for every projected map point
  * m (valid[m], uv, radius = th*getORBScaleFactor(level), predicted level, descriptor) the best keypoint among
