@@ -28,6 +28,7 @@ EXPORTS = [
     "eorb_fuse_keyframes_mixed",
     "eorb_search_for_triangulation_keyframes", "eorb_search_for_triangulation_kb8_keyframes", "eorb_search_by_bow_keyframes",
     "eorb_search_by_bow_kf_keyframes",
+    "eorb_new_map_points", "eorb_create_new_map_points", "eorb_create_new_map_points_kb8",
     "eorb_kfdb_clear", "eorb_kfdb_add", "eorb_kfdb_erase", "eorb_kfdb_info", "eorb_kfdb_get_scores", "eorb_kfdb_detect_reloc", "eorb_kfdb_detect_nbest",
     "eorb_two_view_ransac", "eorb_two_view_check_rt",
     "eorb_sim3_ransac", "eorb_mlpnp_ransac",
@@ -156,6 +157,30 @@ class MlpnpResult(C.Structure):
 
 
 PNP_MAX_ITERS, PNP_MAX_CORR, PNP_MAX_PROBLEMS = 1024, 4096, 64
+
+
+class NewptsSide(C.Structure):
+    """eorb_newpts_side: the per-keypoint arrays of one side of CreateNewMapPoints (host pointers, any may be NULL)"""
+    _fields_ = [("kp_sigma2", C.c_void_p), ("kp_scale", C.c_void_p), ("kp_is_orb", C.c_void_p), ("uright", C.c_void_p), ("depth", C.c_void_p),
+                ("raw_xy", C.c_void_p)]
+
+
+class NewptsParams(C.Structure):
+    """eorb_newpts_params"""
+    _fields_ = [("form", C.c_int), ("views1", C.c_void_p), ("nleft1", C.c_int), ("mb1", C.c_float),
+                ("views2", C.c_void_p), ("nleft2", C.c_void_p), ("mb2", C.c_void_p), ("side1", NewptsSide), ("side2", NewptsSide),
+                ("level_scale", C.c_void_p), ("level_sigma2", C.c_void_p), ("nlevels", C.c_int),
+                ("ratio_factor_orb", C.c_float), ("ratio_factor_ak", C.c_float), ("far_points", C.c_int), ("th_far_points", C.c_float)]
+
+
+class NewptsOut(C.Structure):
+    """eorb_newpts_out: dense K x n1 arrays (x3d, branch, cos_parallax may be NULL)"""
+    _fields_ = [("status", C.c_void_p), ("x3d", C.c_void_p), ("branch", C.c_void_p), ("cos_parallax", C.c_void_p), ("n_new", C.c_void_p)]
+
+
+NEWPTS_LOCAL_MAPPING, NEWPTS_TRACKING = 0, 1
+NP_STATUS = ("new", "no_match", "claimed", "type", "parallax", "w_zero", "empty_stereo", "z1", "z2", "reproj1", "reproj2", "zero_dist", "far",
+             "scale", "nonfinite")          # EORB_NP_*: the value is the index
 
 
 class KltParams(C.Structure):
@@ -388,6 +413,12 @@ def lib():
     L.eorb_search_by_bow_keyframes.argtypes = [vp, ksp, vp, ci, vp, vp, vp, vp, ci, vp, cf, ci, vp]
     L.eorb_search_by_bow_kf_keyframes.restype = ci
     L.eorb_search_by_bow_kf_keyframes.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, ci, ksp, vp, cf, ci, vp]
+    npp, npo = C.POINTER(NewptsParams), C.POINTER(NewptsOut)
+    L.eorb_new_map_points.restype = ci; L.eorb_new_map_points.argtypes = [vp, vp, ci, vp, vp, ci, vp, npp, npo]
+    L.eorb_create_new_map_points.restype = ci
+    L.eorb_create_new_map_points.argtypes = L.eorb_search_for_triangulation_keyframes.argtypes + [npp, npo]
+    L.eorb_create_new_map_points_kb8.restype = ci
+    L.eorb_create_new_map_points_kb8.argtypes = L.eorb_search_for_triangulation_kb8_keyframes.argtypes + [npp, npo]
     L.eorb_kfdb_clear.restype = ci; L.eorb_kfdb_clear.argtypes = [vp]
     L.eorb_kfdb_add.restype = ci; L.eorb_kfdb_add.argtypes = [vp, ci, vp, vp, vp, vp]
     L.eorb_kfdb_erase.restype = ci; L.eorb_kfdb_erase.argtypes = [vp, ci]

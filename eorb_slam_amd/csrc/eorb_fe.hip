@@ -7,6 +7,7 @@
 #include "twoview.h"
 #include "sim3.h"
 #include "mlpnp.h"
+#include "newpts.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -2256,6 +2257,141 @@ static void kfbatch_clear(int K, int n, int32_t* out, int32_t* nmatches)
     if (nmatches) for (int k = 0; k < K; k++) nmatches[k] = 0;
 }
 
+// ---- CreateNewMapPoints (newpts.hip): the stage as a part of a call.  check() reads the arguments, queue() / reserve() lay its inputs and
+// its results out in the call's arena (the results right behind whatever the call reserved before: one download covers both), launch()
+// enqueues the kernels on a match12 that is already on the device, copy_out() hands the landing buffer to the caller's arrays ----
+static void np_clear(int K, int n1, const eorb_newpts_out* O)
+{
+    const size_t n = (size_t)K * n1;
+    if (!O) return;
+    if (O->status) memset(O->status, EORB_NP_NO_MATCH, n);
+    if (O->x3d) memset(O->x3d, 0, sizeof(float) * 3 * n);
+    if (O->branch) memset(O->branch, 0, n);
+    if (O->cos_parallax) memset(O->cos_parallax, 0, sizeof(float) * n);
+    if (O->n_new) memset(O->n_new, 0, sizeof(int32_t) * (size_t)K);
+}
+
+struct NpJob {
+    const eorb_newpts_params* P = nullptr; const eorb_newpts_out* O = nullptr;
+    int K = 0, n1 = 0, ntotal = 0;
+    std::vector<NpKf> kf; NpView v1[2];
+    size_t o_v1 = 0, o_kf = 0, o_in[2][6] = {}, o_ls = 0, o_lg = 0;
+    size_t o_st = 0, o_x = 0, o_br = 0, o_cs = 0, o_nn = 0, o_end = 0, o_tmp = 0, o_ps = 0;
+
+    static NpView view_of(const eorb_view& v)
+    {
+        NpView o{};
+        memcpy(o.R, v.R, sizeof o.R); memcpy(o.t, v.t, sizeof o.t); memcpy(o.Ow, v.Ow, sizeof o.Ow);
+        o.cam = warp_cam_of(v.cam); o.mbf = v.mbf;
+        return o;
+    }
+    // kps2 / kf_off: the neighbours' keypoints concatenated.  Sizes were decided by the caller (KfSetIn::check or the stage's own limits)
+    int check(eorb_ctx* c, const char* what, const eorb_keypoint* kps1, int n1_, const eorb_keypoint* kps2, const int32_t* kf_off, int K_,
+              const eorb_newpts_params* P_, const eorb_newpts_out* O_)
+    {
+        P = P_; O = O_; K = K_; n1 = n1_;
+        if (!P || !O || (K > 0 && (!O->n_new || (n1 > 0 && !O->status)))) return set_err(c, EORB_E_ARG, "%s: params, out, out->status and out->n_new are required", what);
+        if (P->form != EORB_NEWPTS_LOCAL_MAPPING && P->form != EORB_NEWPTS_TRACKING) return set_err(c, EORB_E_ARG, "%s: form %d", what, P->form);
+        if (K == 0) return EORB_OK;
+        ntotal = kf_off[K];
+        if (!P->views1 || !P->views2 || (n1 > 0 && !kps1) || (ntotal > 0 && !kps2)) return set_err(c, EORB_E_ARG, "%s: views and keypoints are required", what);
+        if (P->nleft1 < -1 || P->nleft1 > n1) return set_err(c, EORB_E_ARG, "%s: nleft1 %d", what, P->nleft1);
+        const bool twocam = P->nleft1 >= 0;
+        if (twocam && P->form == EORB_NEWPTS_TRACKING) return set_err(c, EORB_E_ARG, "%s: the Tracking form has no two-camera branch (nleft1 %d)", what, P->nleft1);
+        if (twocam && !P->nleft2) return set_err(c, EORB_E_ARG, "%s: nleft2 is required with nleft1 >= 0", what);
+        if (!(P->mb1 >= 0.f) || !(P->mb1 <= 3.40282347e+38f)) return set_err(c, EORB_E_ARG, "%s: mb1 is negative or not finite", what);
+        const int nv = twocam ? 2 : 1;
+        kf.assign((size_t)K, NpKf{});
+        for (int k = 0; k < K; k++) {
+            NpKf& d = kf[k];
+            d.row0 = kf_off[k]; d.nrows = kf_off[k + 1] - kf_off[k];
+            d.nleft2 = P->nleft2 ? P->nleft2[k] : -1;
+            if (d.nleft2 < -1 || d.nleft2 > d.nrows) return set_err(c, EORB_E_ARG, "%s: keyframe %d: nleft2 %d", what, k, d.nleft2);
+            if (twocam != (d.nleft2 >= 0))
+                return set_err(c, P->form == EORB_NEWPTS_TRACKING ? EORB_E_ARG : EORB_E_CONFIG, "%s: keyframe %d: one keyframe of the pair has two cameras and the other one", what, k);
+            d.mb = P->mb2 ? P->mb2[k] : 0.f;
+            if (!(d.mb >= 0.f) || !(d.mb <= 3.40282347e+38f)) return set_err(c, EORB_E_ARG, "%s: keyframe %d: mb is negative or not finite", what, k);
+        }
+        for (int v = 0; v < nv; v++)
+            if (P->views1[v].cam.model != 0 && P->views1[v].cam.model != 1)
+                return set_err(c, EORB_E_CONFIG, "%s: pKF1's camera %d has a model other than Pinhole (0) / KannalaBrandt8 (1)", what, v);
+        for (int k = 0; k < K; k++)
+            for (int v = 0; v < nv; v++)
+                if (P->views2[(size_t)nv * k + v].cam.model != 0 && P->views2[(size_t)nv * k + v].cam.model != 1)
+                    return set_err(c, EORB_E_CONFIG, "%s: keyframe %d: camera %d has a model other than Pinhole (0) / KannalaBrandt8 (1)", what, k, v);
+        for (int v = 0; v < 2; v++) v1[v] = view_of(P->views1[v < nv ? v : 0]);
+        for (int k = 0; k < K; k++)
+            for (int v = 0; v < 2; v++) kf[k].v[v] = view_of(P->views2[(size_t)nv * k + (v < nv ? v : 0)]);
+        const eorb_newpts_side* S[2] = {&P->side1, &P->side2};
+        const eorb_keypoint* kp[2] = {kps1, kps2};
+        const int n[2] = {n1, ntotal};
+        for (int s = 0; s < 2; s++) {
+            if (S[s]->uright && !S[s]->depth) return set_err(c, EORB_E_ARG, "%s: side %d: uright without depth", what, s + 1);
+            if (!S[s]->kp_sigma2 || !S[s]->kp_scale) {
+                if (!P->level_scale || !P->level_sigma2 || P->nlevels <= 0 || P->nlevels > 64)
+                    return set_err(c, EORB_E_ARG, "%s: side %d has no kp_sigma2 / kp_scale and the call no level tables", what, s + 1);
+                for (int i = 0; i < n[s]; i++)
+                    if (kp[s][i].octave < 0 || kp[s][i].octave >= P->nlevels)
+                        return set_err(c, EORB_E_ARG, "%s: side %d: keypoint %d has octave %d outside [0,%d)", what, s + 1, i, kp[s][i].octave, P->nlevels);
+            }
+            if (S[s]->uright)
+                for (int i = 0; i < n[s]; i++)
+                    if (S[s]->uright[i] >= 0 && !(fabsf(S[s]->depth[i]) <= 3.40282347e+38f))
+                        return set_err(c, EORB_E_ARG, "%s: side %d: keypoint %d has a right coordinate and a depth that is not finite", what, s + 1, i);
+        }
+        return EORB_OK;
+    }
+    void queue(Arena& A)
+    {
+        o_v1 = A.in(v1, sizeof v1); o_kf = A.in(kf.data(), sizeof(NpKf) * (size_t)K);
+        const eorb_newpts_side* S[2] = {&P->side1, &P->side2};
+        const size_t n[2] = {(size_t)n1, (size_t)ntotal};
+        for (int s = 0; s < 2; s++) {
+            o_in[s][0] = A.in(S[s]->kp_sigma2, S[s]->kp_sigma2 ? 4 * n[s] : 0); o_in[s][1] = A.in(S[s]->kp_scale, S[s]->kp_scale ? 4 * n[s] : 0);
+            o_in[s][2] = A.in(S[s]->kp_is_orb, S[s]->kp_is_orb ? n[s] : 0); o_in[s][3] = A.in(S[s]->uright, S[s]->uright ? 4 * n[s] : 0);
+            o_in[s][4] = A.in(S[s]->depth, S[s]->depth ? 4 * n[s] : 0); o_in[s][5] = A.in(S[s]->raw_xy, S[s]->raw_xy ? 8 * n[s] : 0);
+        }
+        const size_t nl = P->level_scale && P->level_sigma2 && P->nlevels > 0 ? (size_t)P->nlevels : 0;
+        o_ls = A.in(P->level_scale, 4 * nl); o_lg = A.in(P->level_sigma2, 4 * nl);
+    }
+    // results, contiguous and zero on entry: status | x3d | branch | cos_parallax | n_new; then the scratch
+    void reserve(Arena& A)
+    {
+        const size_t n = (size_t)K * n1;
+        o_st = A.reserve(n); o_x = A.reserve(12 * n); o_br = A.reserve(n); o_cs = A.reserve(4 * n); o_nn = A.reserve(4 * (size_t)K); o_end = A.reserve(0);
+        o_tmp = A.reserve(2 * n); o_ps = A.reserve(4);
+    }
+    int launch(eorb_ctx* c, const Arena& A, const eorb_keypoint* d_kps1, const eorb_keypoint* d_kps2, const int32_t* d_match12)
+    {
+        EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_st), 0, o_end - o_st, c->stream));
+        EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_ps), 0x7f, 4, c->stream));
+        NpArgs T{};
+        T.kps1 = d_kps1; T.kps2 = d_kps2; T.n1 = n1; T.K = K; T.nleft1 = P->nleft1; T.form = P->form;
+        T.v1 = A.dev<NpView>(o_v1); T.mb1 = P->mb1; T.kf = A.dev<NpKf>(o_kf);
+        const eorb_newpts_side* S[2] = {&P->side1, &P->side2};
+        NpSide* D[2] = {&T.s1, &T.s2};
+        for (int s = 0; s < 2; s++) {
+            D[s]->sigma2 = S[s]->kp_sigma2 ? A.dev<float>(o_in[s][0]) : nullptr; D[s]->scale = S[s]->kp_scale ? A.dev<float>(o_in[s][1]) : nullptr;
+            D[s]->is_orb = S[s]->kp_is_orb ? A.dev<uint8_t>(o_in[s][2]) : nullptr; D[s]->uright = S[s]->uright ? A.dev<float>(o_in[s][3]) : nullptr;
+            D[s]->depth = S[s]->depth ? A.dev<float>(o_in[s][4]) : nullptr; D[s]->raw_xy = S[s]->raw_xy ? A.dev<float>(o_in[s][5]) : nullptr;
+        }
+        T.level_scale = A.dev<float>(o_ls); T.level_sigma2 = A.dev<float>(o_lg); T.nlevels = P->nlevels;
+        T.rf_orb = P->ratio_factor_orb; T.rf_ak = P->ratio_factor_ak; T.far_points = P->far_points; T.th_far = P->th_far_points;
+        T.match12 = d_match12; T.tmp = A.dev<uint8_t>(o_tmp); T.pstar = A.dev<int32_t>(o_ps);
+        T.status = A.dev<uint8_t>(o_st); T.x3d = A.dev<float>(o_x); T.branch = A.dev<uint8_t>(o_br); T.cosp = A.dev<float>(o_cs); T.n_new = A.dev<int32_t>(o_nn);
+        return new_map_points_dev(c, T);
+    }
+    void copy_out(const char* h) const
+    {
+        const size_t n = (size_t)K * n1;
+        memcpy(O->status, h + o_st, n);
+        if (O->x3d) memcpy(O->x3d, h + o_x, 12 * n);
+        if (O->branch) memcpy(O->branch, h + o_br, n);
+        if (O->cos_parallax) memcpy(O->cos_parallax, h + o_cs, 4 * n);
+        memcpy(O->n_new, h + o_nn, 4 * (size_t)K);
+    }
+};
+
 // outputs of a batched walk, contiguous: [K x (32 histogram bins + nmatches) | K x n matches]; then the rotation bins
 struct KfBatchOut { size_t o_hist, o_m, o_bin; };
 static KfBatchOut kfbatch_reserve(Arena& A, int K, int n)
@@ -2264,13 +2400,15 @@ static KfBatchOut kfbatch_reserve(Arena& A, int K, int n)
     o.o_hist = A.reserve(sizeof(int32_t) * kPairHist * (size_t)K); o.o_m = A.reserve(sizeof(int32_t) * (size_t)K * n); o.o_bin = A.reserve((size_t)K * n);
     return o;
 }
-static int kfbatch_out(Arena& A, const KfBatchOut& o, int K, int n, int32_t* out, int32_t* nmatches)
+// np: the call went on with the triangulation stage, whose results lie behind these (NpJob::reserve)
+static int kfbatch_out(Arena& A, const KfBatchOut& o, int K, int n, int32_t* out, int32_t* nmatches, const NpJob* np = nullptr)
 {
     const char* h;
     int rc;
-    if ((rc = A.download(o.o_hist, o.o_m + sizeof(int32_t) * (size_t)K * n - o.o_hist, &h))) return rc;
+    if ((rc = A.download(o.o_hist, (np ? np->o_end : o.o_m + sizeof(int32_t) * (size_t)K * n) - o.o_hist, &h))) return rc;
     memcpy(out, h + o.o_m, sizeof(int32_t) * (size_t)K * n);
     if (nmatches) for (int k = 0; k < K; k++) memcpy(nmatches + k, h + o.o_hist + sizeof(int32_t) * ((size_t)k * kPairHist + 32), 4);
+    if (np) np->copy_out(h);
     return EORB_OK;
 }
 
@@ -2281,11 +2419,13 @@ static int search_tri_common(eorb_ctx* c, const char* what,
         const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1, const eorb_kf_set* S, KfSetIn& J,
         const float* ep, const float* F12, const float* scale2, const float* sigma2_2, const float* sigma2_1, int nlevels,
-        int bCoarse, int checkOri, TriKbArgs* kb, const int32_t* nleft2, const float* Rt, int32_t* match12, int32_t* nmatches)
+        int bCoarse, int checkOri, TriKbArgs* kb, const int32_t* nleft2, const float* Rt, int32_t* match12, int32_t* nmatches,
+        NpJob* np = nullptr)
 {
     const int K = J.K;
     fe_enter(c);
     kfbatch_clear(K, n1, match12, nmatches);
+    if (np) np_clear(K, n1, np->O);
     if (K == 0 || n1 == 0 || nn1 == 0 || J.ntotal == 0 || J.max_nn == 0) return EORB_OK;
     int rc;
     if ((rc = fv_check(c, what, "pKF1", -1, node_off1, idx1, nn1, n1))) return rc;
@@ -2321,7 +2461,9 @@ static int search_tri_common(eorb_ctx* c, const char* what,
     const size_t o_s1 = kb ? A.in(sigma2_1, sizeof(float) * nlevels) : 0;
     J.queue(A, S, false);
     const size_t o_p = A.in(P.data(), sizeof(TriPair) * (size_t)K), o_q = kb ? A.in(Q.data(), sizeof(TriKbPair) * (size_t)K) : 0;
+    if (np) np->queue(A);
     const KfBatchOut o = kfbatch_reserve(A, K, n1);
+    if (np) np->reserve(A);
     if ((rc = A.upload())) return rc;
     TriBatchArgs B{};
     TriArgs& T = B.T;
@@ -2339,7 +2481,10 @@ static int search_tri_common(eorb_ctx* c, const char* what,
         KB.K = *kb; KB.kf = B.kf; KB.pair = B.pair; KB.kb = A.dev<TriKbPair>(o_q); KB.nk = K;
     }
     if ((rc = search_tri_batch_dev(c, what, B, kb ? &KB : nullptr))) return rc;
-    return kfbatch_out(A, o, K, n1, match12, nmatches);
+    if (!np) return kfbatch_out(A, o, K, n1, match12, nmatches);
+    // the stage on the rows where they are; one copy brings both halves' results back
+    if ((rc = np->launch(c, A, T.kps1, T.kps2, T.match12))) return rc;
+    return kfbatch_out(A, o, K, n1, match12, nmatches, np);
 }
 
 // the cameras of a KannalaBrandt8 walk into its block: pKF1's must be KannalaBrandt8, the other side's Pinhole or KannalaBrandt8
@@ -2402,6 +2547,103 @@ int eorb_search_for_triangulation_kb8_keyframes(eorb_ctx* c,
     if ((rc = kb8_cameras(c, what, nleft1, cam1, cam2, KA))) return rc;
     return search_tri_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, nullptr, scale2, sigma2_2,
                                    sigma2_1, nlevels, bCoarse, checkOri, &KA, nleft2, Rt, match12, nmatches);
+}
+
+// ---- CreateNewMapPoints: the stage alone, and behind either K-keyframe search ----
+int eorb_new_map_points(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, const int32_t* kf_off, int K,
+                        const int32_t* match12, const eorb_newpts_params* params, const eorb_newpts_out* out)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "new_map_points";
+    if (K < 0 || n1 < 0 || (K > 0 && !kf_off)) return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    if (K > kKfBatchMaxKfs || (int64_t)K * n1 > kKfBatchMaxOut)                          // (sizes only: nothing is read before this)
+        return set_err(c, EORB_E_CAPACITY, "%s: %d keyframes x %d outputs exceed %d keyframes or %lld outputs", what, K, n1, kKfBatchMaxKfs, (long long)kKfBatchMaxOut);
+    if (K > 0) {
+        if (kf_off[0] != 0) return set_err(c, EORB_E_ARG, "%s: kf_off[0] = %d", what, kf_off[0]);
+        for (int k = 0; k < K; k++) if (kf_off[k + 1] < kf_off[k]) return set_err(c, EORB_E_ARG, "%s: kf_off decreases at keyframe %d", what, k);
+        if (kf_off[K] > kKfBatchMaxRows) return set_err(c, EORB_E_CAPACITY, "%s: %d rows exceed %lld", what, kf_off[K], (long long)kKfBatchMaxRows);
+    }
+    NpJob J;
+    int rc;
+    if ((rc = J.check(c, what, kps1, n1, kps2, kf_off, K, params, out))) return rc;
+    if (K > 0 && n1 > 0 && !match12) return set_err(c, EORB_E_ARG, "%s: match12 is required", what);
+    for (int k = 0; k < K; k++)
+        for (int i = 0; i < n1; i++) {
+            const int32_t m = match12[(size_t)k * n1 + i];
+            if (m < -1 || m >= J.kf[k].nrows) return set_err(c, EORB_E_ARG, "%s: keyframe %d: match12[%d] = %d outside [-1, %d)", what, k, i, m, J.kf[k].nrows);
+        }
+    fe_enter(c);
+    np_clear(K, n1, out);
+    if (K == 0 || n1 == 0) return EORB_OK;
+    Arena A(c);
+    const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * (size_t)n1), o_k2 = A.in(kps2, sizeof(eorb_keypoint) * (size_t)J.ntotal);
+    const size_t o_m = A.in(match12, sizeof(int32_t) * (size_t)K * n1);
+    J.queue(A);
+    J.reserve(A);
+    if ((rc = A.upload())) return rc;
+    if ((rc = J.launch(c, A, A.dev<eorb_keypoint>(o_k1), A.dev<eorb_keypoint>(o_k2), A.dev<int32_t>(o_m)))) return rc;
+    const char* h;
+    if ((rc = A.download(J.o_st, J.o_end - J.o_st, &h))) return rc;
+    J.copy_out(h);
+    return EORB_OK;
+}
+
+int eorb_create_new_map_points(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches,
+        const eorb_newpts_params* params, const eorb_newpts_out* out)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "create_new_map_points";
+    KfSetIn I;
+    int rc;
+    if ((rc = I.check(c, what, set, n1))) return rc;
+    if (nn1 < 0 || stride1 < 32 || !scale2 || !sigma2_2 || nlevels <= 0 || nlevels > 64 ||
+        (I.K > 0 && (!ep || !F12 || (n1 > 0 && (!match12 || !kps1 || !desc1 || !elig1)) || (nn1 > 0 && (!nodes1 || !node_off1 || !idx1)))))
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    NpJob J;
+    if ((rc = J.check(c, what, kps1, n1, set->kps, set->kf_off, I.K, params, out))) return rc;
+    return search_tri_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, F12, scale2, sigma2_2,
+                             nullptr, nlevels, bCoarse, checkOri, nullptr, nullptr, nullptr, match12, nmatches, &J);
+}
+
+int eorb_create_new_map_points_kb8(eorb_ctx* c,
+        const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, const int32_t* nleft2,
+        const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
+        const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches,
+        const eorb_newpts_params* params, const eorb_newpts_out* out)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "create_new_map_points_kb8";
+    KfSetIn I;
+    int rc;
+    if ((rc = I.check(c, what, set, n1))) return rc;
+    if (nn1 < 0 || stride1 < 32 || !cam1 || !cam2 || !scale2 || !sigma2_1 || !sigma2_2 || nlevels <= 0 || nlevels > 64 || nleft1 < -1 || nleft1 > n1 ||
+        (I.K > 0 && (!ep || !Rt || !nleft2 || (n1 > 0 && (!match12 || !kps1 || !desc1 || !elig1)) || (nn1 > 0 && (!nodes1 || !node_off1 || !idx1)))))
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    for (int k = 0; k < I.K; k++)
+        if (nleft2[k] < -1 || nleft2[k] > I.sl[k].nrows) return set_err(c, EORB_E_ARG, "%s: keyframe %d: nleft2 %d", what, k, nleft2[k]);
+    fe_enter(c);
+    kfbatch_clear(I.K, n1, match12, nmatches);
+    np_clear(I.K, n1, out);
+    const bool twocam = nleft1 >= 0;
+    for (int k = 0; k < I.K; k++)
+        if (twocam != (nleft2[k] >= 0))       // the reference leaves R12 an empty cv::Mat (:1000-1014)
+            return set_err(c, EORB_E_CONFIG, "%s: keyframe %d: one keyframe of the pair has two cameras and the other one", what, k);
+    TriKbArgs KA{};
+    if ((rc = kb8_cameras(c, what, nleft1, cam1, cam2, KA))) return rc;
+    NpJob J;
+    if ((rc = J.check(c, what, kps1, n1, set->kps, set->kf_off, I.K, params, out))) return rc;
+    if (params->nleft1 != nleft1) return set_err(c, EORB_E_ARG, "%s: params->nleft1 %d is not the search's %d", what, params->nleft1, nleft1);
+    for (int k = 0; k < I.K; k++)
+        if (J.kf[k].nleft2 != nleft2[k]) return set_err(c, EORB_E_ARG, "%s: keyframe %d: params->nleft2 %d is not the search's %d", what, k, J.kf[k].nleft2, nleft2[k]);
+    return search_tri_common(c, what, kps1, n1, desc1, stride1, elig1, nodes1, node_off1, idx1, nn1, set, I, ep, nullptr, scale2, sigma2_2,
+                             sigma2_1, nlevels, bCoarse, checkOri, &KA, nleft2, Rt, match12, nmatches, &J);
 }
 
 // SearchByBoW over the K keyframes of a set.  kf_kf = 0: the set is the KeyFrame side, `one` the frame (flag1 unused; nL >= 0: a

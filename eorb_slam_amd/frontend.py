@@ -925,6 +925,107 @@ def SearchForTriangulationKB8KeyFrames(kps1, nleft1, desc1, elig1, fv1, kfs, nle
     return nm, m
 
 
+# ---- CreateNewMapPoints: triangulation and its checks (eorb_new_map_points and the two fused forms of include/eorb_fe.h) ----
+_NP_SIDE = (("kp_sigma2", np.float32), ("kp_scale", np.float32), ("kp_is_orb", np.uint8), ("uright", np.float32), ("depth", np.float32),
+            ("raw_xy", np.float32))
+
+
+class NewPointsArgs:
+    """eorb_newpts_params and eorb_newpts_out over numpy arrays it keeps alive.  views1: one eorb_view (frontend.view) or (left, right);
+    views2: one per neighbour, or (left, right) per neighbour; side1 / side2: dicts of the per-keypoint arrays of eorb_newpts_side
+    (side2's concatenated like the neighbours' keypoints); the rest as the header names it.  out() -> the result arrays as a dict."""
+
+    def __init__(self, K, n1, views1, views2, form=_lib.NEWPTS_LOCAL_MAPPING, nleft1=-1, nleft2=None, mb1=0.0, mb2=None, side1=None, side2=None,
+                 level_scale=None, level_sigma2=None, ratio_factor_orb=1.8, ratio_factor_ak=1.8, far_points=False, th_far_points=0.0, aids=True):
+        P = _lib.NewptsParams()
+        self.keep = []
+        P.form = int(form); P.nleft1 = int(nleft1); P.mb1 = float(mb1)
+        self.v1, _ = _views(views1)
+        flat = []
+        for v in views2:
+            flat += [v] if isinstance(v, _lib.View) else list(v)
+        self.v2 = (_lib.View * max(len(flat), 1))(*flat)
+        P.views1 = C.cast(self.v1, C.c_void_p); P.views2 = C.cast(self.v2, C.c_void_p)
+        self.keep += [flat, views1]
+
+        def arr(a, t):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, t)
+            self.keep.append(a)
+            return a.ctypes.data
+        P.nleft2 = arr(nleft2, np.int32); P.mb2 = arr(mb2, np.float32)
+        for dst, src in ((P.side1, side1 or {}), (P.side2, side2 or {})):
+            for name, t in _NP_SIDE:
+                setattr(dst, name, arr(src.get(name), t))
+        P.level_scale = arr(level_scale, np.float32); P.level_sigma2 = arr(level_sigma2, np.float32)
+        P.nlevels = 0 if level_scale is None else len(level_scale)
+        P.ratio_factor_orb = float(ratio_factor_orb); P.ratio_factor_ak = float(ratio_factor_ak)
+        P.far_points = int(bool(far_points)); P.th_far_points = float(th_far_points)
+        self.P = P
+        self.status = np.zeros((K, n1), np.uint8); self.x3d = np.zeros((K, n1, 3), np.float32); self.n_new = np.zeros(K, np.int32)
+        self.branch = np.zeros((K, n1), np.uint8) if aids else None
+        self.cos_parallax = np.zeros((K, n1), np.float32) if aids else None
+        self.O = _lib.NewptsOut(_p(self.status), _p(self.x3d), _p(self.branch), _p(self.cos_parallax), _p(self.n_new))
+
+    def out(self):
+        return dict(status=self.status, x3d=self.x3d, branch=self.branch, cos_parallax=self.cos_parallax, n_new=self.n_new)
+
+
+def NewMapPoints(kps1, kps2, kf_off, match12, views1, views2, ctx=None, **kw):
+    """The per-match half of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:527-784; form=_lib.NEWPTS_TRACKING:
+    src/Tracking.cc:3232-3408) over the K neighbours whose keypoints are concatenated in kps2 (kf_off[K + 1]), on match12 (K, n1) as
+    SearchForTriangulationKeyFrames returned it.  kw: NewPointsArgs.  -> dict(status (K, n1) of _lib.NP_STATUS indices, x3d (K, n1, 3),
+    branch, cos_parallax, n_new[K]); the claim by an earlier neighbour and the ratioFactor rule of mixed keyframes are resolved."""
+    c = ctx or default_context()
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
+    kf_off = np.ascontiguousarray(kf_off, np.int32); K = len(kf_off) - 1
+    m = np.ascontiguousarray(match12, np.int32).reshape(K, len(kps1))
+    A = NewPointsArgs(K, len(kps1), views1, views2, **kw)
+    c.check(c.L.eorb_new_map_points(c.h, _p(kps1), len(kps1), _p(kps2), _p(kf_off), K, _p(m), C.byref(A.P), C.byref(A.O)))
+    return A.out()
+
+
+def CreateNewMapPoints(kps1, desc1, elig1, fv1, kfs, ep, F12, scale2, sigma2_2, views1, views2, bCoarse=False, checkOri=False, ctx=None, **kw):
+    """SearchForTriangulationKeyFrames and NewMapPoints in one call: match12 stays on the device.  -> (nmatches[K], match12 K x n1,
+    the dict of NewMapPoints); equal to the two calls in sequence."""
+    c = ctx or default_context()
+    S = _kf_set(kfs)
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); desc1 = np.ascontiguousarray(desc1, np.uint8); e1 = np.ascontiguousarray(elig1, np.uint8)
+    n1, o1, i1 = _fv(fv1)
+    ep = np.ascontiguousarray(ep, np.float32).reshape(-1); F = np.ascontiguousarray(F12, np.float32).reshape(-1)
+    assert len(ep) == 2 * S.K and len(F) == 9 * S.K
+    sc = np.ascontiguousarray(scale2, np.float32); sg = np.ascontiguousarray(sigma2_2, np.float32)
+    m = np.full((S.K, len(kps1)), -1, np.int32); nm = np.zeros(S.K, np.int32)
+    A = NewPointsArgs(S.K, len(kps1), views1, views2, **kw)
+    c.check(c.L.eorb_create_new_map_points(c.h, _p(kps1), len(kps1), _p(desc1), desc1.shape[1], _p(e1), _p(n1), _p(o1), _p(i1), len(n1),
+                                           C.byref(S.c), _p(ep), _p(F), _p(sc), _p(sg), len(sc), int(bCoarse), int(checkOri), _p(m), _p(nm),
+                                           C.byref(A.P), C.byref(A.O)))
+    return nm, m, A.out()
+
+
+def CreateNewMapPointsKB8(kps1, nleft1, desc1, elig1, fv1, kfs, nleft2, cams1, cams2, Rt, ep, scale2, sigma2_1, sigma2_2, views1, views2,
+                          bCoarse=False, checkOri=False, ctx=None, **kw):
+    """The same over SearchForTriangulationKB8KeyFrames (nleft1 / nleft2 are handed to both halves)."""
+    c = ctx or default_context()
+    S = _kf_set(kfs)
+    kps1 = np.ascontiguousarray(kps1, KP_DTYPE); desc1 = np.ascontiguousarray(desc1, np.uint8); e1 = np.ascontiguousarray(elig1, np.uint8)
+    n1, o1, i1 = _fv(fv1)
+    nl2 = np.ascontiguousarray(nleft2, np.int32)
+    rt = np.ascontiguousarray(Rt, np.float32).reshape(-1)
+    ep = np.ascontiguousarray(ep, np.float32).reshape(-1)
+    assert len(nl2) == S.K and len(ep) == 2 * S.K and len(rt) == (48 if nleft1 >= 0 else 12) * S.K
+    sc = np.ascontiguousarray(scale2, np.float32)
+    s1 = np.ascontiguousarray(sigma2_1, np.float32); s2 = np.ascontiguousarray(sigma2_2, np.float32)
+    m = np.full((S.K, len(kps1)), -1, np.int32); nm = np.zeros(S.K, np.int32)
+    c1, c2 = _cams(cams1), _cams(cams2)
+    A = NewPointsArgs(S.K, len(kps1), views1, views2, nleft1=nleft1, nleft2=nl2, **kw)
+    c.check(c.L.eorb_create_new_map_points_kb8(c.h, _p(kps1), len(kps1), int(nleft1), _p(desc1), desc1.shape[1], _p(e1), _p(n1), _p(o1),
+                                               _p(i1), len(n1), C.byref(S.c), _p(nl2), C.byref(c1), C.byref(c2), _p(rt), _p(ep), _p(sc),
+                                               _p(s1), _p(s2), len(s2), int(bCoarse), int(checkOri), _p(m), _p(nm), C.byref(A.P), C.byref(A.O)))
+    return nm, m, A.out()
+
+
 def SearchByBoWKeyFrames(kfs, f_kps, f_desc, f_fv, nnratio=0.7, checkOri=True, ctx=None):
     """SearchByBoW(pKF_k, F) over the K candidates of kfs (flag = kf_has_mp) against one frame in one call: Tracking::Relocalization.
     -> (nmatches[K], match_f K x n_f, indices relative to keyframe k)."""

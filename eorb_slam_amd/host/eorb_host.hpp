@@ -1413,6 +1413,30 @@ private:
     double mRansacProb = 0.99; int mRansacMinInliers = 8, mRansacMaxIts = 300, mRansacMinSet = 6; float mRansacEpsilon = 0.4f, mTh2 = 5.991f;
 };
 
+// LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:527-784; params.form = EORB_NEWPTS_TRACKING: Tracking::CreateNewMapPoints,
+// src/Tracking.cc:3232-3408): the per-match half for the K neighbours whose keypoints are concatenated in kps2 (kfOff[K + 1]), on
+// vMatches12 (K * n1) as SearchForTriangulation returned it for every neighbour with the initial eligibility.  The claim of idx1 by an
+// earlier neighbour (:775) and the ratioFactor rule of mixed keyframes (:464, :545-546) are resolved in the call.  The adapter then walks
+// status in the reference's order and, per EORB_NP_NEW entry, does :770-783 (new MapPoint(x3D), the observations, the two AddMapPoint,
+// ComputeDistinctiveDescriptors, UpdateNormalAndDepth, Atlas::AddMapPoint).  params as include/eorb_fe.h documents eorb_newpts_params.
+struct NewMapPoints {
+    std::vector<uint8_t> status, branch;       // K * n1: EORB_NP_*, EORB_NP_BRANCH_*
+    std::vector<float> x3D, cosParallax;       // 3 per entry (zero unless status is EORB_NP_NEW); cosParallaxRays
+    std::vector<int32_t> nNew;                 // per neighbour
+};
+inline NewMapPoints CreateNewMapPoints(const std::vector<eorb_host::KeyPoint>& kps1, const std::vector<eorb_host::KeyPoint>& kps2,
+                                       const std::vector<int32_t>& kfOff, const std::vector<int32_t>& vMatches12, const eorb_newpts_params& params) {
+    auto& c = eorb_host::thread_context();
+    const int K = kfOff.empty() ? 0 : (int)kfOff.size() - 1;
+    const size_t n = (size_t)K * kps1.size();
+    if (vMatches12.size() != n) throw eorb_host::Error(EORB_E_ARG, "CreateNewMapPoints: vMatches12 holds K * n1 entries");
+    NewMapPoints r;
+    r.status.resize(n); r.branch.resize(n); r.x3D.resize(3 * n); r.cosParallax.resize(n); r.nNew.resize((size_t)K);
+    const eorb_newpts_out out{r.status.data(), r.x3D.data(), r.branch.data(), r.cosParallax.data(), r.nNew.data()};
+    c.check(eorb_new_map_points(c.get(), kps1.data(), (int)kps1.size(), kps2.data(), kfOff.data(), K, vMatches12.data(), &params, &out));
+    return r;
+}
+
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:349-423) for a batch of map points (CSR offsets into desc rows)
 inline std::vector<int> ComputeDistinctiveDescriptors(const eorb_host::Mat8& desc, const std::vector<int32_t>& offsets) {
     auto& c = eorb_host::thread_context();

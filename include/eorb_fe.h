@@ -970,17 +970,19 @@ typedef struct eorb_kf_set {
  * pKF1 feature depends on that feature, pKF2_k and F12_k only; what changes between neighbours is which pKF1 features are eligible:
  * AddMapPoint(pMP, idx1) (src/LocalMapping.cc:775) takes idx1 out of the later neighbours' searches, pKF2->AddMapPoint (:776) touches
  * only that neighbour.  So the caller batches the neighbours that pass the baseline tests (:477-494), computes each F12_k, passes
- * elig1 as it stands before the loop, and applies the rows in the reference's order:
- *     eorb_search_for_triangulation_keyframes(..., match12, NULL);
+ * elig1 as it stands before the loop, and hands the rows to the triangulation stage, which applies them in the reference's order
+ * and resolves "set by an earlier neighbour of this pass" itself (eorb_new_map_points below; eorb_create_new_map_points is this
+ * search and that stage in one call):
+ *     eorb_create_new_map_points(..., match12, NULL, &params, &out);
  *     for k in the reference's neighbour order:
- *         for idx1 with match12[k*n1 + idx1] >= 0:
- *             if (mpCurrentKeyFrame->GetMapPoint(idx1)) continue;        // set by an earlier neighbour of this pass
- *             triangulate (idx1, match12[k*n1 + idx1]) as at :530-780
+ *         for idx1 with out.status[k*n1 + idx1] == EORB_NP_NEW:
+ *             new MapPoint(out.x3d + 3*(k*n1 + idx1)), observations, AddMapPoint(idx1), AddMapPoint(match12[k*n1 + idx1]) (:770-783)
  * This reproduces the sequential loop exactly while checkOri is false, and both callers construct the matcher that way
  * (src/LocalMapping.cc:443, src/Tracking.cc:3152).  With checkOri set a row equals the single call with the same elig1, which is not
  * the reference's sequence once elig1 has changed: the rotation histogram of a later neighbour would have been built without the
  * features taken meanwhile.  The reference may leave the loop early (CheckNewKeyFrames(), :469); the batch has then computed the
- * remaining rows for nothing.  tests/test_kfbatch_recipe.py runs this recipe against the sequential loop on a model map. */
+ * remaining rows for nothing.  tests/test_kfbatch_recipe.py runs this recipe against the sequential loop on a model map with a made-up
+ * triangulation rule, tests/test_newpts_recipe.py with the real stage. */
 int eorb_search_for_triangulation_keyframes(eorb_ctx* ctx,
         const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
         const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
@@ -998,6 +1000,106 @@ int eorb_search_for_triangulation_kb8_keyframes(eorb_ctx* ctx,
         const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
         const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
         int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches);
+
+/* ---- CreateNewMapPoints on the device: triangulation and its checks -----------------------------------------------------------
+ * replaces the per-match half of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:527-784) and of its copy
+ * Tracking::CreateNewMapPoints (src/Tracking.cc:3232-3408) for the K neighbours of one keyframe: per pair (idx1, idx2 =
+ * match12[k*n1 + idx1]) the type gate (:542), the pose / camera choice (:563-628), unprojectMat and the ray parallax (:631-636), the
+ * stereo parallax (:642-647), linear triangulation through cv::SVD::compute or UnprojectStereo (:650-683; src/KeyFrame.cc:924-940),
+ * the two depth signs (:689-695), the two chi-square reprojection gates (:698-748), the far-point test (:760) and the scale
+ * consistency test (:763-767), in the reference's operation order on OpenCV 3.4.1's scalar paths ("Parity
+ * choices of CreateNewMapPoints").  The two sequential rules of the loop are resolved in the call:
+ *   the claim: AddMapPoint(pMP, idx1) (:775) takes idx1 out of the later neighbours, so the pair that counts for idx1 is the first k,
+ *     in neighbour order, whose pair is accepted; its later matches get EORB_NP_CLAIMED.  Two idx1 on one idx2 of a neighbour are both
+ *     reported (the reference creates both points and pKF2->AddMapPoint overwrites; that stays with the caller);
+ *   ratioFactor (:464): overwritten with the AKAZE factor at the first AKAZE-AKAZE pair the loop reaches (:545-546) and never set back;
+ *     pairs are visited k-major, idx1 ascending (src/ORBmatcher.cc:1206-1211), a claimed idx1 is not visited.
+ * After the call the caller still does, per EORB_NP_NEW entry in the reference's order: new MapPoint(x3d), the two AddObservation,
+ * the two AddMapPoint, ComputeDistinctiveDescriptors (eorb_distinctive_descriptors), UpdateNormalAndDepth, Atlas::AddMapPoint.
+ * The baseline tests that leave a neighbour out (:477-494) stay with the caller, as in eorb_search_for_triangulation_keyframes.
+ * EvLocalMapping's variants are not covered. */
+#define EORB_NEWPTS_LOCAL_MAPPING 0   /* src/LocalMapping.cc:527-784 */
+#define EORB_NEWPTS_TRACKING      1   /* src/Tracking.cc:3232-3408: xn = ((u-cx)*invfx, (v-cy)*invfy, 1), fx*x*invz+cx in the non-stereo
+                                         gate too, no two-camera branch, no far-point test, bStereo = uRight >= 0 */
+/* status, one value per exit of the loop body */
+#define EORB_NP_NEW           0   /* triangulation is successful (:769) */
+#define EORB_NP_NO_MATCH      1   /* match12 < 0 */
+#define EORB_NP_CLAIMED       2   /* idx1 got its map point from an earlier neighbour of this call (:775) */
+#define EORB_NP_TYPE          3   /* isORBKPt1 != isORBKPt2 (:542) */
+#define EORB_NP_PARALLAX      4   /* no stereo and very low parallax (:680-683) */
+#define EORB_NP_W_ZERO        5   /* x3D.at<float>(3) == 0 (:665) */
+#define EORB_NP_EMPTY_STEREO  6   /* UnprojectStereo returned an empty Mat: depth <= 0 (:687; Tracking.cc would fault there) */
+#define EORB_NP_Z1            7   /* z1 <= 0 (:690) */
+#define EORB_NP_Z2            8   /* z2 <= 0 (:694) */
+#define EORB_NP_REPROJ1       9   /* chi-square gate in keyframe 1 (:709, :721) */
+#define EORB_NP_REPROJ2      10   /* chi-square gate in keyframe 2 (:735, :746) */
+#define EORB_NP_ZERO_DIST    11   /* dist1 == 0 || dist2 == 0 (:757) */
+#define EORB_NP_FAR          12   /* mbFarPoints && (dist1 >= mThFarPoints || dist2 >= mThFarPoints) (:760) */
+#define EORB_NP_SCALE        13   /* ratioDist*ratioFactor < ratioOctave || ratioDist > ratioOctave*ratioFactor (:766) */
+#define EORB_NP_NONFINITE    14   /* x3D, z, the reprojection error or a distance is not finite: this library's rule, as reason 7 of
+                                     eorb_project_frustum (the reference goes on with a NaN there: every comparison is false) */
+/* branch (test aid): how x3D was formed */
+#define EORB_NP_BRANCH_NONE    0
+#define EORB_NP_BRANCH_DLT     1
+#define EORB_NP_BRANCH_STEREO1 2
+#define EORB_NP_BRANCH_STEREO2 3
+
+/* per-keypoint arrays of one side: pKF1 (n1 entries) or the K neighbours concatenated like their keypoints (kf_off) */
+typedef struct eorb_newpts_side {
+    const float*   kp_sigma2;   /* getKPtLevelSigma2(i); NULL: level_sigma2[octave] (the convention of kp_inv_sigma2 in the mixed forms) */
+    const float*   kp_scale;    /* getKPtScaleFactor(i); NULL: level_scale[octave] */
+    const uint8_t* kp_is_orb;   /* isORBDescValid(i); NULL: all ORB */
+    const float*   uright;      /* mvuRight; NULL: no rectified right image (bStereo false) */
+    const float*   depth;       /* mvDepth; NULL with uright given is EORB_E_ARG; finite wherever uright >= 0 */
+    const float*   raw_xy;      /* mvKeys[i].pt, 2 per keypoint: what UnprojectStereo reads (KeyFrame.cc:929-930); NULL: the same as kps */
+} eorb_newpts_side;
+
+/* views1: pKF1's eorb_view (R, t, Ow, cam and mbf are read), two of them (left, right as eorb_view documents) when nleft1 >= 0;
+ * views2: one per neighbour, or two per neighbour (2k, 2k+1) when nleft1 >= 0.  nleft1 / nleft2[K] = numAllKPtsLeft() as in
+ * eorb_search_for_triangulation_kb8 (nleft2 NULL = all -1); one side with two cameras and the other with one: EORB_E_CONFIG.  With two
+ * cameras kps = the distorted left keypoints then the right ones, otherwise the undistorted ones (:548-557).  mpCamera2 != NULL is
+ * taken to be nleft >= 0.  fx, fy, cx, cy of the stereo gates and of UnprojectStereo are views[0].cam's, invfx = 1.0f/fx.
+ * mb1 / mb2[K] = KeyFrame::mb (finite, >= 0; mb2 NULL = 0).  The form EORB_NEWPTS_TRACKING takes nleft1 = -1 only. */
+typedef struct eorb_newpts_params {
+    int form;
+    const eorb_view* views1; int nleft1; float mb1;
+    const eorb_view* views2; const int32_t* nleft2; const float* mb2;
+    eorb_newpts_side side1, side2;
+    const float* level_scale; const float* level_sigma2; int nlevels;   /* read where kp_scale / kp_sigma2 is NULL */
+    float ratio_factor_orb, ratio_factor_ak;   /* 1.5f*getORBScaleFactor(), 1.5f*getAKAZEScaleFactor() */
+    int far_points; float th_far_points;       /* mbFarPoints, mThFarPoints */
+} eorb_newpts_params;
+
+/* dense like eorb_fuse_keyframes: entry k*n1 + idx1.  status and n_new[K] are required; x3d (3 per entry: the new point, zero unless
+ * status is EORB_NP_NEW), branch and cos_parallax (test aids: zero where the loop did not get that far) may be NULL */
+typedef struct eorb_newpts_out { uint8_t* status; float* x3d; uint8_t* branch; float* cos_parallax; int32_t* n_new; } eorb_newpts_out;
+
+/* the stage alone: match12[K*n1] from the host (what eorb_search_for_triangulation_keyframes returned), kps2 / kf_off[K + 1] the
+ * neighbours' keypoints concatenated as in eorb_kf_set.  A match12 entry outside [-1, rows of keyframe k): EORB_E_ARG.  Limits as the
+ * K-keyframe search: K <= 1024, K*n1 <= 2^22, 2^22 rows in all (EORB_E_CAPACITY).  Camera models other than 0 / 1: EORB_E_CONFIG.
+ * K == 0 and an all -1 match12: EORB_OK.  One upload, one wait, one download; two launches. */
+int eorb_new_map_points(eorb_ctx* ctx, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, const int32_t* kf_off, int K,
+                        const int32_t* match12, const eorb_newpts_params* params, const eorb_newpts_out* out);
+
+/* eorb_search_for_triangulation_keyframes followed by the stage: match12 stays on the device between the two halves; one upload,
+ * one wait, one download.  Returns exactly what the two calls in sequence return, match12 / nmatches included.  The arguments of both
+ * halves are checked before anything runs; the stage reads kps1 and set->kps. */
+int eorb_create_new_map_points(eorb_ctx* ctx,
+        const eorb_keypoint* kps1, int n1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, const float* ep, const float* F12, const float* scale2, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches,
+        const eorb_newpts_params* params, const eorb_newpts_out* out);
+
+/* the same over eorb_search_for_triangulation_kb8_keyframes; nleft1 / nleft2 are the search's, params->nleft1 / nleft2 must agree */
+int eorb_create_new_map_points_kb8(eorb_ctx* ctx,
+        const eorb_keypoint* kps1, int n1, int nleft1, const uint8_t* desc1, int stride1, const uint8_t* elig1,
+        const uint32_t* nodes1, const int32_t* node_off1, const int32_t* idx1, int nn1,
+        const eorb_kf_set* set, const int32_t* nleft2,
+        const eorb_camera* cam1, const eorb_camera* cam2, const float* Rt, const float* ep,
+        const float* scale2, const float* sigma2_1, const float* sigma2_2, int nlevels,
+        int bCoarse, int checkOri, int32_t* match12, int32_t* nmatches,
+        const eorb_newpts_params* params, const eorb_newpts_out* out);
 
 /* SearchByBoW(pKF_k, F, vvpMapPointMatches[k]) for the K candidates in `set` (the pKF side; flag = kf_has_mp) against one frame
  * (f_desc n_f x 32): Tracking::Relocalization.  match_f[K*n_f] = KeyFrame feature index relative to keyframe k, or -1; nmatches[K]
