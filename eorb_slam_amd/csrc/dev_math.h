@@ -174,6 +174,12 @@ __device__ __forceinline__ void dev_dsincos(double x, double* sn, double* cs)
         default: *sn = -kc; *cs = ks; break;
     }
 }
+// dev_dsincos, with a NaN handed through (its quadrant would come from the conversion of a NaN)
+__device__ __forceinline__ void dev_dsincos_nan(double x, double* sn, double* cs)
+{
+    if (x != x) { *sn = x; *cs = x; return; }
+    dev_dsincos(x, sn, cs);
+}
 
 // double-precision atan2 for the rotation angle of Sim3Solver::ComputeSim3 (src/Sim3Solver.cc:368): fdlibm's e_atan2.c over s_atan.c,
 // the same text as the CPU restatement (tests/sim3_ref/sim3_ref.c), which is held to 1 ulp of the host's atan2 (tests/test_sim3_ref.py).

@@ -1533,6 +1533,79 @@ static TcArgs twocam_args(const Arena& A, const TcFrameOff& f, const eorb_grid_b
     return T;
 }
 
+// ---- marshalling shared by the RANSAC set solvers (ransac_set.h: eorb_sim3_ransac, eorb_mlpnp_ransac): K problems, each with N
+// correspondences and `iters` caller-drawn sets of set_size indices, concatenated ----
+struct RansacLimit { int max; const char* name; };
+#define RANSAC_LIMIT(m) RansacLimit{m, #m}
+// what: the entry point's name in messages; the least N and min_inliers of a problem; the capacities
+struct RansacDesc { const char* what; int set_size, min_N, min_min_inliers; RansacLimit problems, corr, iters; };
+// a call's totals and its result region, contiguous and zero when the kernels start: the K records | inliers | the per-iteration aids in
+// the order given.  upload(): the call's last reservations, then A.upload(); download(): one copy, up to the aids or (when the caller
+// takes one) past them
+struct RansacAid { void* host; size_t bytes, off; };      // host: the caller's array or NULL; off: set by RansacCall::upload
+struct RansacCall {
+    size_t tN = 0, tI = 0; int max_N = 0, max_iters = 0;
+    size_t res = 0, inl = 0, end = 0, res_bytes = 0;
+    int upload(Arena& A, size_t record_bytes, RansacAid* aid, int n_aid)
+    {
+        res_bytes = record_bytes;
+        res = A.reserve(res_bytes); inl = A.reserve(tN);
+        for (int i = 0; i < n_aid; i++) aid[i].off = A.reserve(aid[i].bytes);
+        end = A.reserve(0);
+        if (const int rc = A.upload()) return rc;
+        EORB_HIP(A.c, hipMemsetAsync(A.dev<char>(res), 0, end - res, A.c->stream));
+        return EORB_OK;
+    }
+    int download(Arena& A, void* results, uint8_t* inliers, const RansacAid* aid, int n_aid) const
+    {
+        bool aids = false;
+        for (int i = 0; i < n_aid; i++) aids = aids || aid[i].host;
+        const char* h;
+        if (const int rc = A.download(res, (aids ? end : aid[0].off) - res, &h)) return rc;
+        memcpy(results, h + res, res_bytes); memcpy(inliers, h + inl, tN);
+        for (int i = 0; i < n_aid; i++) if (aid[i].host) memcpy(aid[i].host, h + aid[i].off, aid[i].bytes);
+        return EORB_OK;
+    }
+};
+static bool cam_model_ok(const eorb_camera& cam) { return cam.model == 0 || cam.model == 1; }
+// The checks in their order: K, then per problem the sizes and capacities (no array is read), then the camera models, then per problem
+// the set indices.  own(k, problem, pv[k]) is the solver's part of the size pass (its checks, its fields of pv[k]), arrays(k, head) its
+// checks of its own arrays after problem k's sets.  Fills the heads of pv and the totals.
+extern "C++" template <class Pub, class Dev, class Own, class CamOk, class Arrays>
+static int ransac_problems_in(eorb_ctx* c, const RansacDesc& D, const Pub* problems, int K, const int32_t* sets, std::vector<Dev>& pv, RansacCall& R,
+                              Own own, CamOk cam_ok, Arrays arrays)
+{
+    const char* what = D.what;
+    int rc;
+    if (K < 1) return set_err(c, EORB_E_ARG, "%s: %d problems (at least 1)", what, K);
+    if (K > D.problems.max) return set_err(c, EORB_E_CAPACITY, "%s: %d problems, at most %s = %d", what, K, D.problems.name, D.problems.max);
+    pv.assign((size_t)K, Dev{});
+    for (int k = 0; k < K; k++) {
+        const Pub& p = problems[k];
+        if (p.N < D.min_N || p.iters < 1 || p.min_inliers < D.min_min_inliers)
+            return set_err(c, EORB_E_ARG, "%s: problem %d has %d correspondences (at least %d), %d iterations (at least 1), min_inliers %d (at least %d)", what, k,
+                           p.N, D.min_N, p.iters, p.min_inliers, D.min_min_inliers);
+        if (p.N > D.corr.max) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d correspondences, at most %s = %d", what, k, p.N, D.corr.name, D.corr.max);
+        if (p.iters > D.iters.max) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d iterations, at most %s = %d", what, k, p.iters, D.iters.name, D.iters.max);
+        if ((rc = own(k, p, pv[k]))) return rc;
+        RansacProb& d = pv[k];
+        d.N = p.N; d.iters = p.iters; d.corr_off = (int)R.tN; d.set_off = (int)R.tI; d.min_inliers = p.min_inliers;
+        R.tN += (size_t)p.N; R.tI += (size_t)p.iters;
+        R.max_N = std::max(R.max_N, p.N); R.max_iters = std::max(R.max_iters, p.iters);
+    }
+    for (int k = 0; k < K; k++)
+        if (!cam_ok(problems[k])) return set_err(c, EORB_E_CONFIG, "%s: problem %d has a camera model other than Pinhole (0) / KannalaBrandt8 (1)", what, k);
+    for (int k = 0; k < K; k++) {
+        const RansacProb& d = pv[k];
+        for (int i = 0; i < D.set_size * d.iters; i++) {
+            const int32_t s = sets[D.set_size * (size_t)d.set_off + i];
+            if (s < 0 || s >= d.N)
+                return set_err(c, EORB_E_ARG, "%s: problem %d, set %d holds the index %d of %d correspondences", what, k, i / D.set_size, s, d.N);
+        }
+        if ((rc = arrays(k, d))) return rc;
+    }
+    return EORB_OK;
+}
 // ---- matchers, projections given by the caller -----------------------------------------------------------------------------------
 // reloc: the slot semantics of eorb_search_by_projection_kf (result_in)
 static int proj_last_common(eorb_ctx* c,
@@ -2955,45 +3028,29 @@ int eorb_sim3_ransac(eorb_ctx* c, const eorb_sim3_problem* problems, int K, cons
         eorb_sim3_result* results, uint8_t* inliers, int32_t* it_inliers, float* it_T12, float* it_T21, float* it_scale)
 {
     if (!c) return EORB_E_ARG;
-    const char* what = "sim3_ransac";
-    if (!problems || !Xw1 || !Xw2 || !sigma2_1 || !sigma2_2 || !sets || !results || !inliers) return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
-    if (K < 1) return set_err(c, EORB_E_ARG, "%s: %d problems (at least 1)", what, K);
-    if (K > EORB_S3_MAX_PROBLEMS) return set_err(c, EORB_E_CAPACITY, "%s: %d problems, at most EORB_S3_MAX_PROBLEMS = %d", what, K, EORB_S3_MAX_PROBLEMS);
-    // sizes first (no array is read), then the cameras, then the sets and the sigmas
-    std::vector<S3Prob> pv((size_t)K);
-    size_t tN = 0, tI = 0;
-    int max_N = 0, max_iters = 0;
-    for (int k = 0; k < K; k++) {
-        const eorb_sim3_problem& p = problems[k];
-        if (p.N < 3 || p.iters < 1 || p.min_inliers < 0)
-            return set_err(c, EORB_E_ARG, "%s: problem %d has %d correspondences (at least 3), %d iterations (at least 1), min_inliers %d (at least 0)", what, k,
-                           p.N, p.iters, p.min_inliers);
-        if (p.N > EORB_S3_MAX_CORR) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d correspondences, at most EORB_S3_MAX_CORR = %d", what, k, p.N, EORB_S3_MAX_CORR);
-        if (p.iters > EORB_S3_MAX_ITERS) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d iterations, at most EORB_S3_MAX_ITERS = %d", what, k, p.iters, EORB_S3_MAX_ITERS);
-        S3Prob& d = pv[k];
-        d.N = p.N; d.iters = p.iters; d.corr_off = (int)tN; d.set_off = (int)tI; d.fix_scale = p.fix_scale != 0; d.min_inliers = p.min_inliers;
-        memcpy(d.Rt1, p.Rt1, sizeof d.Rt1); memcpy(d.Rt2, p.Rt2, sizeof d.Rt2);
-        d.cam1 = warp_cam_of(p.cam1); d.cam2 = warp_cam_of(p.cam2);
-        tN += (size_t)p.N; tI += (size_t)p.iters;
-        max_N = std::max(max_N, p.N); max_iters = std::max(max_iters, p.iters);
-    }
-    for (int k = 0; k < K; k++)
-        if ((problems[k].cam1.model != 0 && problems[k].cam1.model != 1) || (problems[k].cam2.model != 0 && problems[k].cam2.model != 1))
-            return set_err(c, EORB_E_CONFIG, "%s: problem %d has a camera model other than Pinhole (0) / KannalaBrandt8 (1)", what, k);
-    for (int k = 0; k < K; k++) {
-        const S3Prob& d = pv[k];
-        for (int i = 0; i < 3 * d.iters; i++) {
-            const int32_t s = sets[3 * (size_t)d.set_off + i];
-            if (s < 0 || s >= d.N) return set_err(c, EORB_E_ARG, "%s: problem %d, set %d holds the index %d of %d correspondences", what, k, i / 3, s, d.N);
-        }
-        for (int i = 0; i < d.N; i++) {
-            const float s1 = sigma2_1[(size_t)d.corr_off + i], s2 = sigma2_2[(size_t)d.corr_off + i];
-            if (!(s1 >= 0.f && s1 < 1e15f) || !(s2 >= 0.f && s2 < 1e15f))
-                return set_err(c, EORB_E_ARG, "%s: problem %d, correspondence %d has sigma2 = (%g, %g), outside [0, 1e15)", what, k, i, (double)s1, (double)s2);
-        }
-    }
+    static const RansacDesc D{"sim3_ransac", 3, 3, 0, RANSAC_LIMIT(EORB_S3_MAX_PROBLEMS), RANSAC_LIMIT(EORB_S3_MAX_CORR), RANSAC_LIMIT(EORB_S3_MAX_ITERS)};
+    if (!problems || !Xw1 || !Xw2 || !sigma2_1 || !sigma2_2 || !sets || !results || !inliers) return set_err(c, EORB_E_ARG, "%s: bad arguments", D.what);
+    std::vector<S3Prob> pv;
+    RansacCall R;
+    int rc = ransac_problems_in(c, D, problems, K, sets, pv, R,
+        [](int, const eorb_sim3_problem& p, S3Prob& d) {
+            d.fix_scale = p.fix_scale != 0;
+            memcpy(d.Rt1, p.Rt1, sizeof d.Rt1); memcpy(d.Rt2, p.Rt2, sizeof d.Rt2);
+            d.cam1 = warp_cam_of(p.cam1); d.cam2 = warp_cam_of(p.cam2);
+            return EORB_OK;
+        },
+        [](const eorb_sim3_problem& p) { return cam_model_ok(p.cam1) && cam_model_ok(p.cam2); },
+        [&](int k, const RansacProb& d) {
+            for (int i = 0; i < d.N; i++) {
+                const float s1 = sigma2_1[(size_t)d.corr_off + i], s2 = sigma2_2[(size_t)d.corr_off + i];
+                if (!(s1 >= 0.f && s1 < 1e15f) || !(s2 >= 0.f && s2 < 1e15f))
+                    return set_err(c, EORB_E_ARG, "%s: problem %d, correspondence %d has sigma2 = (%g, %g), outside [0, 1e15)", D.what, k, i, (double)s1, (double)s2);
+            }
+            return EORB_OK;
+        });
+    if (rc) return rc;
     fe_enter(c);
-    int rc;
+    const size_t tN = R.tN, tI = R.tI;
     Arena A(c);
     const size_t o_pr = A.in(pv.data(), sizeof(S3Prob) * (size_t)K);
     const size_t o_x1 = A.in(Xw1, sizeof(float) * 3 * tN), o_x2 = A.in(Xw2, sizeof(float) * 3 * tN);
@@ -3001,101 +3058,57 @@ int eorb_sim3_ransac(eorb_ctx* c, const eorb_sim3_problem* problems, int K, cons
     const size_t o_c1 = A.reserve(sizeof(float) * 3 * tN), o_c2 = A.reserve(sizeof(float) * 3 * tN);
     const size_t o_p1 = A.reserve(sizeof(float) * 2 * tN), o_p2 = A.reserve(sizeof(float) * 2 * tN);
     const size_t o_b1 = A.reserve(sizeof(float) * tN), o_b2 = A.reserve(sizeof(float) * tN), o_hyp = A.reserve(sizeof(float) * kS3HypFloats * tI);
-    // results, contiguous and zero on entry: the K records | inliers | the per-iteration aids
-    const size_t o_res = A.reserve(sizeof(int32_t) * kS3ResWords * (size_t)K), o_inl = A.reserve(tN);
-    const size_t o_cnt = A.reserve(sizeof(int32_t) * tI), o_sc = A.reserve(sizeof(float) * tI);
-    const size_t o_t12 = A.reserve(sizeof(float) * 16 * tI), o_t21 = A.reserve(sizeof(float) * 16 * tI), o_end = A.reserve(0);
-    if ((rc = A.upload())) return rc;
-    EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_res), 0, o_end - o_res, c->stream));
+    static_assert(sizeof(eorb_sim3_result) == sizeof(int32_t) * kS3ResWords, "eorb_sim3_result is kS3ResWords words");
+    RansacAid aid[4] = {{it_inliers, sizeof(int32_t) * tI}, {it_scale, sizeof(float) * tI}, {it_T12, sizeof(float) * 16 * tI}, {it_T21, sizeof(float) * 16 * tI}};
+    if ((rc = R.upload(A, sizeof(eorb_sim3_result) * (size_t)K, aid, 4))) return rc;
     S3Args T{};
-    T.prob = A.dev<S3Prob>(o_pr); T.K = K; T.max_N = max_N; T.max_iters = max_iters;
+    T.prob = A.dev<S3Prob>(o_pr); T.K = K; T.max_N = R.max_N; T.max_iters = R.max_iters;
     T.Xw1 = A.dev<float>(o_x1); T.Xw2 = A.dev<float>(o_x2); T.sigma2_1 = A.dev<float>(o_s1); T.sigma2_2 = A.dev<float>(o_s2); T.sets = A.dev<int32_t>(o_st);
     T.X1 = A.dev<float>(o_c1); T.X2 = A.dev<float>(o_c2); T.p1 = A.dev<float2>(o_p1); T.p2 = A.dev<float2>(o_p2);
     T.b1 = A.dev<float>(o_b1); T.b2 = A.dev<float>(o_b2); T.hyp = A.dev<float>(o_hyp);
-    T.res = A.dev<int32_t>(o_res); T.inliers = A.dev<uint8_t>(o_inl); T.it_inliers = A.dev<int32_t>(o_cnt); T.it_scale = A.dev<float>(o_sc);
-    T.it_T12 = A.dev<float>(o_t12); T.it_T21 = A.dev<float>(o_t21);
+    T.res = A.dev<int32_t>(R.res); T.inliers = A.dev<uint8_t>(R.inl); T.it_inliers = A.dev<int32_t>(aid[0].off); T.it_scale = A.dev<float>(aid[1].off);
+    T.it_T12 = A.dev<float>(aid[2].off); T.it_T21 = A.dev<float>(aid[3].off);
     if ((rc = sim3_ransac_dev(c, T))) return rc;
-    const bool aids = it_inliers || it_T12 || it_T21 || it_scale;
-    const char* h;
-    if ((rc = A.download(o_res, (aids ? o_end : o_cnt) - o_res, &h))) return rc;
-    static_assert(sizeof(eorb_sim3_result) == sizeof(int32_t) * kS3ResWords, "eorb_sim3_result is kS3ResWords words");
-    memcpy(results, h + o_res, sizeof(eorb_sim3_result) * (size_t)K);
-    memcpy(inliers, h + o_inl, tN);
-    if (it_inliers) memcpy(it_inliers, h + o_cnt, sizeof(int32_t) * tI);
-    if (it_scale) memcpy(it_scale, h + o_sc, sizeof(float) * tI);
-    if (it_T12) memcpy(it_T12, h + o_t12, sizeof(float) * 16 * tI);
-    if (it_T21) memcpy(it_T21, h + o_t21, sizeof(float) * 16 * tI);
-    return EORB_OK;
+    return R.download(A, results, inliers, aid, 4);
 }
 
 int eorb_mlpnp_ransac(eorb_ctx* c, const eorb_mlpnp_problem* problems, int K, const float* p2d, const float* Xw, const float* sigma2,
         const int32_t* sets, eorb_mlpnp_result* results, uint8_t* inliers, int32_t* it_inliers, double* it_Rt, int32_t* it_refine_inliers)
 {
     if (!c) return EORB_E_ARG;
-    const char* what = "mlpnp_ransac";
-    if (!problems || !p2d || !Xw || !sigma2 || !sets || !results || !inliers) return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
-    if (K < 1) return set_err(c, EORB_E_ARG, "%s: %d problems (at least 1)", what, K);
-    if (K > EORB_PNP_MAX_PROBLEMS) return set_err(c, EORB_E_CAPACITY, "%s: %d problems, at most EORB_PNP_MAX_PROBLEMS = %d", what, K, EORB_PNP_MAX_PROBLEMS);
-    // sizes first (no array is read), then the cameras, then the sets
-    std::vector<PnpProb> pv((size_t)K);
-    size_t tN = 0, tI = 0;
-    int max_N = 0, max_iters = 0;
-    for (int k = 0; k < K; k++) {
-        const eorb_mlpnp_problem& p = problems[k];
-        if (p.N < 6 || p.iters < 1 || p.min_inliers < 6)
-            return set_err(c, EORB_E_ARG, "%s: problem %d has %d correspondences (at least 6), %d iterations (at least 1), min_inliers %d (at least 6)", what, k,
-                           p.N, p.iters, p.min_inliers);
-        if (p.N > EORB_PNP_MAX_CORR) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d correspondences, at most EORB_PNP_MAX_CORR = %d", what, k, p.N, EORB_PNP_MAX_CORR);
-        if (p.iters > EORB_PNP_MAX_ITERS) return set_err(c, EORB_E_CAPACITY, "%s: problem %d has %d iterations, at most EORB_PNP_MAX_ITERS = %d", what, k, p.iters, EORB_PNP_MAX_ITERS);
-        if (p.first_it < 0 || p.first_it >= p.iters || p.best_it < -1 || p.best_it >= p.first_it)
-            return set_err(c, EORB_E_ARG, "%s: problem %d resumes at iteration %d of %d with the best %d (first_it in [0, iters), best_it in [-1, first_it))", what, k,
-                           p.first_it, p.iters, p.best_it);
-        PnpProb& d = pv[k];
-        d.N = p.N; d.iters = p.iters; d.corr_off = (int)tN; d.set_off = (int)tI; d.min_inliers = p.min_inliers; d.first_it = p.first_it; d.best_it = p.best_it;
-        d.th2 = p.th2; d.cam = warp_cam_of(p.cam);
-        tN += (size_t)p.N; tI += (size_t)p.iters;
-        max_N = std::max(max_N, p.N); max_iters = std::max(max_iters, p.iters);
-    }
-    for (int k = 0; k < K; k++)
-        if (problems[k].cam.model != 0 && problems[k].cam.model != 1)
-            return set_err(c, EORB_E_CONFIG, "%s: problem %d has a camera model other than Pinhole (0) / KannalaBrandt8 (1)", what, k);
-    for (int k = 0; k < K; k++) {
-        const PnpProb& d = pv[k];
-        for (int i = 0; i < 6 * d.iters; i++) {
-            const int32_t s = sets[6 * (size_t)d.set_off + i];
-            if (s < 0 || s >= d.N) return set_err(c, EORB_E_ARG, "%s: problem %d, set %d holds the index %d of %d correspondences", what, k, i / 6, s, d.N);
-        }
-    }
+    static const RansacDesc D{"mlpnp_ransac", 6, 6, 6, RANSAC_LIMIT(EORB_PNP_MAX_PROBLEMS), RANSAC_LIMIT(EORB_PNP_MAX_CORR), RANSAC_LIMIT(EORB_PNP_MAX_ITERS)};
+    if (!problems || !p2d || !Xw || !sigma2 || !sets || !results || !inliers) return set_err(c, EORB_E_ARG, "%s: bad arguments", D.what);
+    std::vector<PnpProb> pv;
+    RansacCall R;
+    int rc = ransac_problems_in(c, D, problems, K, sets, pv, R,
+        [&](int k, const eorb_mlpnp_problem& p, PnpProb& d) {
+            if (p.first_it < 0 || p.first_it >= p.iters || p.best_it < -1 || p.best_it >= p.first_it)
+                return set_err(c, EORB_E_ARG, "%s: problem %d resumes at iteration %d of %d with the best %d (first_it in [0, iters), best_it in [-1, first_it))", D.what, k,
+                               p.first_it, p.iters, p.best_it);
+            d.first_it = p.first_it; d.best_it = p.best_it; d.th2 = p.th2; d.cam = warp_cam_of(p.cam);
+            return EORB_OK;
+        },
+        [](const eorb_mlpnp_problem& p) { return cam_model_ok(p.cam); }, [](int, const RansacProb&) { return EORB_OK; });
+    if (rc) return rc;
     fe_enter(c);
-    int rc;
+    const size_t tN = R.tN, tI = R.tI;
     Arena A(c);
     const size_t o_pr = A.in(pv.data(), sizeof(PnpProb) * (size_t)K);
     const size_t o_p2 = A.in(p2d, sizeof(float) * 2 * tN), o_xw = A.in(Xw, sizeof(float) * 3 * tN), o_sg = A.in(sigma2, sizeof(float) * tN);
     const size_t o_st = A.in(sets, sizeof(int32_t) * 6 * tI);
     const size_t o_f = A.reserve(sizeof(double) * 3 * tN), o_ns = A.reserve(sizeof(double) * 6 * tN), o_x = A.reserve(sizeof(double) * 3 * tN);
     const size_t o_bd = A.reserve(sizeof(float) * tN);
-    // results, contiguous and zero on entry: the K records | inliers | the per-iteration aids
-    const size_t o_res = A.reserve(sizeof(int32_t) * kPnpResWords * (size_t)K), o_inl = A.reserve(tN);
-    const size_t o_cnt = A.reserve(sizeof(int32_t) * tI), o_rfn = A.reserve(sizeof(int32_t) * tI), o_rt = A.reserve(sizeof(double) * 12 * tI), o_end = A.reserve(0);
-    if ((rc = A.upload())) return rc;
-    EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_res), 0, o_end - o_res, c->stream));
+    static_assert(sizeof(eorb_mlpnp_result) == sizeof(int32_t) * kPnpResWords, "eorb_mlpnp_result is kPnpResWords words");
+    RansacAid aid[3] = {{it_inliers, sizeof(int32_t) * tI}, {it_refine_inliers, sizeof(int32_t) * tI}, {it_Rt, sizeof(double) * 12 * tI}};
+    if ((rc = R.upload(A, sizeof(eorb_mlpnp_result) * (size_t)K, aid, 3))) return rc;
     PnpArgs T{};
-    T.prob = A.dev<PnpProb>(o_pr); T.K = K; T.max_N = max_N; T.max_iters = max_iters;
+    T.prob = A.dev<PnpProb>(o_pr); T.K = K; T.max_N = R.max_N; T.max_iters = R.max_iters;
     T.p2d = A.dev<float>(o_p2); T.Xw = A.dev<float>(o_xw); T.sigma2 = A.dev<float>(o_sg); T.sets = A.dev<int32_t>(o_st);
     T.f = A.dev<double>(o_f); T.ns = A.dev<double>(o_ns); T.X = A.dev<double>(o_x); T.bound = A.dev<float>(o_bd);
-    T.res = A.dev<int32_t>(o_res); T.inliers = A.dev<uint8_t>(o_inl); T.it_inliers = A.dev<int32_t>(o_cnt); T.it_refine = A.dev<int32_t>(o_rfn);
-    T.it_Rt = A.dev<double>(o_rt);
+    T.res = A.dev<int32_t>(R.res); T.inliers = A.dev<uint8_t>(R.inl); T.it_inliers = A.dev<int32_t>(aid[0].off); T.it_refine = A.dev<int32_t>(aid[1].off);
+    T.it_Rt = A.dev<double>(aid[2].off);
     if ((rc = mlpnp_ransac_dev(c, T))) return rc;
-    const bool aids = it_inliers || it_Rt || it_refine_inliers;
-    const char* h;
-    if ((rc = A.download(o_res, (aids ? o_end : o_cnt) - o_res, &h))) return rc;
-    static_assert(sizeof(eorb_mlpnp_result) == sizeof(int32_t) * kPnpResWords, "eorb_mlpnp_result is kPnpResWords words");
-    memcpy(results, h + o_res, sizeof(eorb_mlpnp_result) * (size_t)K);
-    memcpy(inliers, h + o_inl, tN);
-    if (it_inliers) memcpy(it_inliers, h + o_cnt, sizeof(int32_t) * tI);
-    if (it_refine_inliers) memcpy(it_refine_inliers, h + o_rfn, sizeof(int32_t) * tI);
-    if (it_Rt) memcpy(it_Rt, h + o_rt, sizeof(double) * 12 * tI);
-    return EORB_OK;
+    return R.download(A, results, inliers, aid, 3);
 }
 
 // what the MixedMatcher forms take on top of the ORB ones (a NULL KfMixedIn* = an ORB entry point): kp_is_orb / kp_inv_sigma2 per

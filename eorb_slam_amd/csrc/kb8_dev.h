@@ -71,6 +71,21 @@ __device__ __forceinline__ void cv_gemm3x1(const float* R, const float* x, const
         out[i] = (float)((double)t * alpha + (c ? (double)c[i] * 1.0 : 0.0 * 0.0));
     }
 }
+// cv::gemm, small-matrix branch (len = 3, 3x3 by 3x3, no C): float products summed in float, then (float)(t*alpha + c*beta) in double;
+// d may be a or b
+__device__ __forceinline__ void cv_gemm33(const float* a, const float* b, float* d)
+{
+    float r[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const float t = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+            r[3 * i + j] = (float)((double)t * 1.0 + 0.0 * 0.0);
+        }
+#pragma unroll
+    for (int i = 0; i < 9; i++) d[i] = r[i];
+}
 // Mat::dot (dotProd_32f, len 3: the double accumulation of dotProd_, returned as 0.0 + result)
 __device__ __forceinline__ double cv_dot3(const float* a, const float* b)
 {

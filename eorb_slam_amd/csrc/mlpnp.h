@@ -3,12 +3,13 @@
 #include <stdint.h>
 #include "eorb_ctx.h"
 #include "kb8_dev.h"
+#include "ransac_set.h"
 
 namespace eorb {
 
-// one problem as the kernels read it; corr_off / set_off: where its correspondences / sets begin in the flat arrays
-struct PnpProb {
-    int N, iters, corr_off, set_off, min_inliers, first_it, best_it;
+// one problem as the kernels read it
+struct PnpProb : RansacProb {
+    int first_it, best_it;
     float th2;
     WarpCam cam;
 };
@@ -18,8 +19,7 @@ constexpr int kPnpResWords = 22;
 constexpr int kPnpRowDoubles = 14;
 
 // eorb_mlpnp_ransac; every pointer is device memory
-struct PnpArgs {
-    const PnpProb* prob; int K, max_N, max_iters;
+struct PnpArgs : RansacSet<PnpProb> {
     const float* p2d; const float* Xw; const float* sigma2;          // per correspondence
     const int32_t* sets;                                             // 6 per hypothesis
     double* f; double* ns; double* X; float* bound;                  // pnp_prepare_kernel: bearing vector, nullspace (3x2), point, mvMaxError

@@ -20,13 +20,8 @@
 
 namespace eorb {
 
-__device__ __forceinline__ void pnp_dsincos(double x, double* sn, double* cs)
-{
-    if (x != x) { *sn = x; *cs = x; return; }
-    dev_dsincos(x, sn, cs);      // |x| < 100: see mlp_rodrigues2rot
-}
 #define MLP_FN __device__ __forceinline__
-#define MLP_SINCOS(x, ps, pc) pnp_dsincos((x), (ps), (pc))
+#define MLP_SINCOS(x, ps, pc) dev_dsincos_nan((x), (ps), (pc))      // |x| < 100: see mlp_rodrigues2rot
 #define MLP_HI(x) ((int32_t)__double2hiint(x))
 #define MLP_LO(x) ((uint32_t)__double2loint(x))
 #define MLP_MK(hi, lo) __hiloint2double((int)(hi), (int)(lo))
@@ -218,16 +213,11 @@ __global__ __launch_bounds__(64) void pnp_hyp_kernel(PnpArgs a)
     __shared__ PnpLds L;
     const PnpProb& P = a.prob[blockIdx.y];
     const int lane = threadIdx.x, it = blockIdx.x;
-    if (it >= P.iters || P.N < P.min_inliers || (it < P.first_it && it != P.best_it)) return;
+    if (it >= P.iters || ransac_skips(P) || (it < P.first_it && it != P.best_it)) return;
     const size_t h = (size_t)P.set_off + it;
     pnp_compute_pose(a, P, a.sets + 6 * h, 6, L, L.rows6);
     if (lane < 12) a.it_Rt[12 * h + lane] = L.Rt[lane];
-    int n = 0;
-    for (int base = 0; base < P.N; base += 64) {
-        const int i = base + lane;
-        const bool in = i < P.N && pnp_is_inlier(a, P, L.Rt, (size_t)P.corr_off + i);
-        n += __popcll(__ballot(in));
-    }
+    const int n = ransac_count_inliers(P.N, [&](int i) { return pnp_is_inlier(a, P, L.Rt, (size_t)P.corr_off + i); });
     if (lane == 0) a.it_inliers[h] = n;
 }
 
@@ -242,7 +232,7 @@ __global__ __launch_bounds__(256) void pnp_finish_kernel(PnpArgs a)
     int32_t* res = a.res + kPnpResWords * blockIdx.x;
     int32_t* refine = a.it_refine + P.set_off;
     for (int it = tid; it < P.iters; it += 256) refine[it] = -1;
-    if (P.N < P.min_inliers) { if (tid == 0) { res[0] = -1; res[2] = -1; } return; }      // (:154-158; everything else stays zero)
+    if (ransac_skips(P)) { if (tid == 0) { res[0] = -1; res[2] = -1; } return; }      // (:154-158; everything else stays zero)
     __syncthreads();
     const int32_t* cnt = a.it_inliers + P.set_off;
     const size_t g0 = (size_t)P.corr_off;

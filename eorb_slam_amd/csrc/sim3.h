@@ -3,12 +3,13 @@
 #include <stdint.h>
 #include "eorb_ctx.h"
 #include "kb8_dev.h"
+#include "ransac_set.h"
 
 namespace eorb {
 
-// one problem as the kernels read it; corr_off / set_off: where its correspondences / sets begin in the flat arrays
-struct S3Prob {
-    int N, iters, corr_off, set_off, fix_scale, min_inliers;
+// one problem as the kernels read it
+struct S3Prob : RansacProb {
+    int fix_scale;
     float Rt1[12], Rt2[12];
     WarpCam cam1, cam2;
 };
@@ -18,8 +19,7 @@ constexpr int kS3HypFloats = 13;
 constexpr int kS3ResWords = 33;
 
 // eorb_sim3_ransac; every pointer is device memory
-struct S3Args {
-    const S3Prob* prob; int K, max_N, max_iters;
+struct S3Args : RansacSet<S3Prob> {
     const float* Xw1; const float* Xw2; const float* sigma2_1; const float* sigma2_2;      // per correspondence
     const int32_t* sets;                                                                   // 3 per hypothesis
     float* X1; float* X2; float2* p1; float2* p2; float* b1; float* b2;                    // s3_prepare_kernel: mvX3Dc, mvP?im?, the bounds

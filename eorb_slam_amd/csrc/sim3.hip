@@ -27,17 +27,6 @@ __device__ __forceinline__ void s3_scale(const float* src, double alpha, float* 
 #pragma unroll
     for (int i = 0; i < N; i++) dst[i] = copy ? src[i] : src[i] * a + 0.0f;
 }
-// gemm, small-matrix branch, 3x3 by 3x3 (twoview.hip tv_gemm33)
-__device__ __forceinline__ void s3_gemm33(const float* a, const float* b, float* d)
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const float t = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-            d[3 * i + j] = (float)((double)t * 1.0 + 0.0 * 0.0);
-        }
-}
 // the templated hypot of lapack.cpp, float
 __device__ __forceinline__ float s3_hypotf(float a, float b)
 {
@@ -45,12 +34,6 @@ __device__ __forceinline__ float s3_hypotf(float a, float b)
     if (a > b) { b /= a; return a * sqrtf(1 + b * b); }
     if (b > 0) { a /= b; return b * sqrtf(1 + a * a); }
     return 0;
-}
-// dev_dsincos, with a NaN handed through (its quadrant would come from the conversion of a NaN)
-__device__ __forceinline__ void s3_dsincos(double x, double* sn, double* cs)
-{
-    if (x != x) { *sn = x; *cs = x; return; }
-    dev_dsincos(x, sn, cs);
 }
 
 // ComputeCentroid (:305-314): reduceC_'s two accumulators give (p0 + p2) + p1; C/3 is a MatExpr scale by 1./3
@@ -164,7 +147,7 @@ __global__ __launch_bounds__(kS3Lanes) void s3_hyp_kernel(S3Args a)
     __shared__ float smem[kS3HypWords * kS3Lanes];
     const S3Prob& P = a.prob[blockIdx.y];
     const int lane = threadIdx.x, it = blockIdx.x * kS3Lanes + lane;
-    if (it >= P.iters || P.N < P.min_inliers) return;      // (no barrier below: every lane works on its own LDS column)
+    if (it >= P.iters || ransac_skips(P)) return;      // (no barrier below: every lane works on its own LDS column)
     const size_t h = (size_t)P.set_off + it;
     float P1[9], P2[9], Pr1[9], Pr2[9], O1[3], O2[3], M[9];
 #pragma unroll
@@ -216,7 +199,7 @@ __global__ __launch_bounds__(kS3Lanes) void s3_hyp_kernel(S3Args a)
             for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.f : 0.f;
         } else {
             double sn, c;
-            s3_dsincos(theta, &sn, &c);
+            dev_dsincos_nan(theta, &sn, &c);
             const double c1 = 1. - c, itheta = theta ? 1. / theta : 0.;
             rx *= itheta; ry *= itheta; rz *= itheta;
             const double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};
@@ -226,7 +209,7 @@ __global__ __launch_bounds__(kS3Lanes) void s3_hyp_kernel(S3Args a)
         }
     }
     float P3[9], s12;
-    s3_gemm33(R, Pr2, P3);
+    cv_gemm33(R, Pr2, P3);
     if (!P.fix_scale) {
         // Mat::dot, len 9, unrolled by four; cv::pow(P3, 2) is a float product, den a double sum of floats
         double nom = 0;
@@ -321,15 +304,10 @@ __global__ __launch_bounds__(64) void s3_inlier_kernel(S3Args a)
 {
     const S3Prob& P = a.prob[blockIdx.y];
     const int lane = threadIdx.x, it = blockIdx.x;
-    if (it >= P.iters || P.N < P.min_inliers) return;
+    if (it >= P.iters || ransac_skips(P)) return;
     const size_t h = (size_t)P.set_off + it;
     const S3Pose T12 = s3_pose_of(a.it_T12 + 16 * h), T21 = s3_pose_of(a.it_T21 + 16 * h);
-    int n = 0;
-    for (int base = 0; base < P.N; base += 64) {
-        const int i = base + lane;
-        const bool in = i < P.N && s3_is_inlier(a, P, T12, T21, (size_t)P.corr_off + i);
-        n += __popcll(__ballot(in));
-    }
+    const int n = ransac_count_inliers(P.N, [&](int i) { return s3_is_inlier(a, P, T12, T21, (size_t)P.corr_off + i); });
     if (lane == 0) a.it_inliers[h] = n;
 }
 
@@ -341,7 +319,7 @@ __global__ __launch_bounds__(256) void s3_finish_kernel(S3Args a)
     const S3Prob& P = a.prob[blockIdx.x];
     const int tid = threadIdx.x;
     int32_t* res = a.res + kS3ResWords * blockIdx.x;
-    if (P.N < P.min_inliers) { if (tid == 0) res[1] = -1; return; }      // (:228-232; everything else stays zero)
+    if (ransac_skips(P)) { if (tid == 0) res[1] = -1; return; }      // (:228-232; everything else stays zero)
     if (tid == 0) { s_first = INT_MAX; s_key = -1; }
     __syncthreads();
     const int32_t* cnt = a.it_inliers + P.set_off;

@@ -21,21 +21,6 @@ constexpr int kTvHypLds = (9 * 16 + 9 * 9) * 4 + 9 * 8;      // bytes per lane: 
 
 __device__ __forceinline__ float tv_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
-// cv::gemm, small-matrix branch (len = 3, 3x3, no C): float products summed in float, then (float)(t*alpha + c*beta) in double
-__device__ __forceinline__ void tv_gemm33(const float* a, const float* b, float* d)
-{
-    float r[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const float t = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-            r[3 * i + j] = (float)((double)t * 1.0 + 0.0 * 0.0);
-        }
-#pragma unroll
-    for (int i = 0; i < 9; i++) d[i] = r[i];
-}
-
 // Mat::inv() 3x3: cv::invert DECOMP_LU, n == 3 closed form; determinant and cofactors in double, d = 1./d, d == 0 -> zeros
 __device__ __forceinline__ void tv_inv33(const float* S, float* D)
 {
@@ -254,7 +239,7 @@ __global__ __launch_bounds__(kTvLanes) void tv_hyp_kernel(TvRansacArgs a, int hb
         float T2inv[9], X12[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) T2inv[k] = a.hdr[18 + k];
-        tv_gemm33(T2inv, Xn, tmp); tv_gemm33(tmp, T1, X21);      // H21i = T2inv*Hn*T1
+        cv_gemm33(T2inv, Xn, tmp); cv_gemm33(tmp, T1, X21);      // H21i = T2inv*Hn*T1
         tv_inv33(X21, X12);                                      // H12i = H21i.inv()
 #pragma unroll
         for (int k = 0; k < 9; k++) { out[k] = X21[k]; out[9 + k] = X12[k]; }
@@ -297,12 +282,12 @@ __global__ __launch_bounds__(kTvLanes) void tv_hyp_kernel(TvRansacArgs a, int hb
 #pragma unroll
             for (int k = 0; k < 3; k++) { u[3 * i + k] = TV_A(k, i); vt[3 * i + k] = TV_V(i, k); }
         d[0] = (float)TV_W(0); d[4] = (float)TV_W(1); d[8] = 0.f;
-        tv_gemm33(u, d, tmp); tv_gemm33(tmp, vt, Xn);
+        cv_gemm33(u, d, tmp); cv_gemm33(tmp, vt, Xn);
     }
     float T2t[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) T2t[k] = a.hdr[27 + k];
-    tv_gemm33(T2t, Xn, tmp); tv_gemm33(tmp, T1, X21);            // F21i = T2t*Fn*T1
+    cv_gemm33(T2t, Xn, tmp); cv_gemm33(tmp, T1, X21);            // F21i = T2t*Fn*T1
 #pragma unroll
     for (int k = 0; k < 9; k++) { out[k] = X21[k]; out[9 + k] = 0.f; }
 }

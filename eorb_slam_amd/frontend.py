@@ -1435,33 +1435,64 @@ class TwoViewReconstruction:
         return o
 
 
-def sim3_ransac_iterations(N, probability, min_inliers, max_iterations):
-    """mRansacMaxIts of Sim3Solver::SetRansacParameters (src/Sim3Solver.cc:137-147): epsilon in float, pow / log / ceil in double.
-    `int nIterations = ceil(...)` of a value no int holds converts as the reference's x86 build does (cvttsd2si: INT_MIN), which
-    max(1, min(...)) turns into 1: min_inliers = 0 and N < min_inliers end there."""
-    epsilon = float(np.float32(min_inliers) / np.float32(N))
-    if min_inliers == N:
+def _ransac_max_iterations(probability, epsilon32, exact, max_iterations):
+    """the tail of both SetRansacParameters: 1 when min_inliers == N (exact), else ceil(log(1 - p) / log(1 - epsilon^3)) with pow / log /
+    ceil in double, then max(1, min(n, max_iterations)).  `int nIterations = ceil(...)` of a value no int holds converts as the
+    reference's x86 build does (cvttsd2si: INT_MIN), which max(1, min(...)) turns into 1."""
+    if exact:
         n = 1
     else:
         with np.errstate(all="ignore"):
-            v = np.ceil(np.log(np.float64(1 - probability)) / np.log(np.float64(1) - np.float64(epsilon) ** 3))
+            v = np.ceil(np.log(np.float64(1 - probability)) / np.log(np.float64(1) - np.float64(epsilon32) ** 3))
         n = int(v) if np.isfinite(v) and -2147483648.0 <= v < 2147483648.0 else -2147483648
     return max(1, min(n, int(max_iterations)))
 
 
-def sim3_draw_sets(N, iterations, seed):
-    """the minimal sets of Sim3Solver::iterate (:178-189) on a numpy generator (the reference draws from DUtils::Random): three draws
-    without replacement, the drawn slot refilled with the back of vAvailableIndices.  -> [iterations, 3] int32"""
+def _draw_minimal_sets(N, iterations, k, seed):
+    """k draws without replacement per iteration on a numpy generator (the reference draws from DUtils::Random), the drawn slot refilled
+    with the back of vAvailableIndices.  -> [iterations, k] int32"""
     rng = np.random.default_rng(seed)
-    sets = np.zeros((iterations, 3), np.int32)
+    sets = np.zeros((iterations, k), np.int32)
     for it in range(iterations):
         moved = {}
-        for i in range(3):
+        for i in range(k):
             size = N - i
             randi = int(rng.integers(0, size))
             sets[it, i] = moved.get(randi, randi)
             moved[randi] = moved.get(size - 1, size - 1)
     return sets
+
+
+def _solve_problem_set(c, call, solvers, sets_list, k, problems, arrays, records, aid_spec, aids):
+    """the scaffolding of both solve_candidates: one call(h, probs, K, *arrays, sets, res, inliers, *aids) for K solvers.  problems: the
+    ctypes problem of every solver; arrays: the solvers' per-correspondence attributes, concatenated in this order; records: the ctypes
+    result type; aid_spec: {name: (dtype, shape per iteration)} in the call's order -> [(record, inliers, {aid: rows})] per solver"""
+    K = len(solvers)
+    assert len(sets_list) == K and all(s.ndim == 2 and s.shape[1] == k for s in sets_list)
+    ins = [np.concatenate([getattr(s, name) for s in solvers]) for name in arrays]
+    sets = np.concatenate(sets_list)
+    tN, tI = len(ins[0]), len(sets)
+    res = (records * K)()
+    inl = np.zeros(tN, np.uint8)
+    a = {name: np.zeros((tI,) + shape, dtype) for name, (dtype, shape) in aid_spec.items()} if aids else {}
+    c.check(call(c.h, (type(problems[0]) * K)(*problems), K, *[_p(x) for x in ins], _p(sets), res, _p(inl), *[_p(a.get(name)) for name in aid_spec]))
+    out, n0, i0 = [], 0, 0
+    for r, s, st in zip(res, solvers, sets_list):
+        out.append((r, inl[n0:n0 + s.N].copy(), {key: v[i0:i0 + len(st)].copy() for key, v in a.items()}))
+        n0 += s.N; i0 += len(st)
+    return out
+
+
+def sim3_ransac_iterations(N, probability, min_inliers, max_iterations):
+    """mRansacMaxIts of Sim3Solver::SetRansacParameters (src/Sim3Solver.cc:137-147): epsilon in float; min_inliers = 0 and
+    N < min_inliers end at 1 (_ransac_max_iterations)."""
+    epsilon = float(np.float32(min_inliers) / np.float32(N))
+    return _ransac_max_iterations(probability, epsilon, min_inliers == N, max_iterations)
+
+
+def sim3_draw_sets(N, iterations, seed):
+    """the minimal sets of Sim3Solver::iterate (:178-189): three draws without replacement.  -> [iterations, 3] int32"""
+    return _draw_minimal_sets(N, iterations, 3, seed)
 
 
 class Sim3Solver:
@@ -1507,63 +1538,32 @@ class Sim3Solver:
     def solve_candidates(solvers, sets_list, aids=False, ctx=None):
         """one eorb_sim3_ransac call for K solvers (LoopClosing builds one per BoW candidate) -> a list of find()'s dicts"""
         c = ctx or solvers[0].ctx
-        K = len(solvers)
         sets_list = [np.ascontiguousarray(s, np.int32) for s in sets_list]
-        assert len(sets_list) == K and all(s.ndim == 2 and s.shape[1] == 3 for s in sets_list)
-        probs = (_lib.Sim3Problem * K)(*[s.problem(len(st)) for s, st in zip(solvers, sets_list)])
-        Xw1 = np.concatenate([s.Xw1 for s in solvers]); Xw2 = np.concatenate([s.Xw2 for s in solvers])
-        sg1 = np.concatenate([s.sigma2_1 for s in solvers]); sg2 = np.concatenate([s.sigma2_2 for s in solvers])
-        sets = np.concatenate(sets_list)
-        tN, tI = len(Xw1), len(sets)
-        res = (_lib.Sim3Result * K)()
-        inl = np.zeros(tN, np.uint8)
-        a = dict(it_inliers=np.zeros(tI, np.int32), it_T12=np.zeros((tI, 4, 4), np.float32), it_T21=np.zeros((tI, 4, 4), np.float32),
-                 it_scale=np.zeros(tI, np.float32)) if aids else {}
-        c.check(c.L.eorb_sim3_ransac(c.h, probs, K, _p(Xw1), _p(Xw2), _p(sg1), _p(sg2), _p(sets), res, _p(inl), _p(a.get("it_inliers")),
-                                     _p(a.get("it_T12")), _p(a.get("it_T21")), _p(a.get("it_scale"))))
-        out, n0, i0 = [], 0, 0
-        for k, (s, st) in enumerate(zip(solvers, sets_list)):
-            r = res[k]
-            o = dict(inliers=inl[n0:n0 + s.N].copy(), converged=int(r.converged), best_it=int(r.best_it), n_inliers=int(r.n_inliers),
+        spec = dict(it_inliers=(np.int32, ()), it_T12=(np.float32, (4, 4)), it_T21=(np.float32, (4, 4)), it_scale=(np.float32, ()))
+        out = []
+        for r, inl, a in _solve_problem_set(c, c.L.eorb_sim3_ransac, solvers, sets_list, 3, [s.problem(len(st)) for s, st in zip(solvers, sets_list)],
+                                            ("Xw1", "Xw2", "sigma2_1", "sigma2_2"), _lib.Sim3Result, spec, aids):
+            o = dict(inliers=inl, converged=int(r.converged), best_it=int(r.best_it), n_inliers=int(r.n_inliers),
                      iterations_used=int(r.iterations_used), T12=np.array(r.T12, np.float32).reshape(4, 4),
                      R12=np.array(r.R12, np.float32).reshape(3, 3), t12=np.array(r.t12, np.float32), s12=np.float32(r.s12))
-            o.update({key: v[i0:i0 + len(st)].copy() for key, v in a.items()})
+            o.update(a)
             out.append(o)
-            n0 += s.N; i0 += len(st)
         return out
 
 
 def mlpnp_ransac_parameters(N, probability=0.99, min_inliers=10, max_iterations=300, min_set=6, epsilon=0.5):
     """MLPnPsolver::SetRansacParameters (src/MLPnPsolver.cpp:268-298) -> (mRansacMinInliers, mRansacMaxIts).  mRansacEpsilon is a float:
-    int(N*epsilon) is a float product truncated, and epsilon is raised to minInliers/N in float; pow / log / ceil in double.
-    `int nIterations = ceil(...)` of a value no int holds converts as the reference's x86 build does (cvttsd2si: INT_MIN), which
-    max(1, min(...)) turns into 1."""
+    int(N*epsilon) is a float product truncated, and epsilon is raised to minInliers/N in float (_ransac_max_iterations has the rest)."""
     eps = np.float32(epsilon)
     n_min = max(int(np.float32(N) * eps), int(min_inliers), int(min_set))
     if eps < np.float32(n_min) / np.float32(N):
         eps = np.float32(n_min) / np.float32(N)
-    if n_min == N:
-        n = 1
-    else:
-        with np.errstate(all="ignore"):
-            v = np.ceil(np.log(np.float64(1 - probability)) / np.log(np.float64(1) - np.float64(eps) ** 3))
-        n = int(v) if np.isfinite(v) and -2147483648.0 <= v < 2147483648.0 else -2147483648
-    return n_min, max(1, min(n, int(max_iterations)))
+    return n_min, _ransac_max_iterations(probability, eps, n_min == N, max_iterations)
 
 
 def mlpnp_draw_sets(N, iterations, seed):
-    """the minimal sets of MLPnPsolver::iterate (:176-188) on a numpy generator (the reference draws from DUtils::Random): six draws
-    without replacement, the drawn slot refilled with the back of vAvailableIndices.  -> [iterations, 6] int32"""
-    rng = np.random.default_rng(seed)
-    sets = np.zeros((iterations, 6), np.int32)
-    for it in range(iterations):
-        moved = {}
-        for i in range(6):
-            size = N - i
-            randi = int(rng.integers(0, size))
-            sets[it, i] = moved.get(randi, randi)
-            moved[randi] = moved.get(size - 1, size - 1)
-    return sets
+    """the minimal sets of MLPnPsolver::iterate (:176-188): six draws without replacement.  -> [iterations, 6] int32"""
+    return _draw_minimal_sets(N, iterations, 6, seed)
 
 
 class MLPnPsolver:
@@ -1609,25 +1609,16 @@ class MLPnPsolver:
         c = ctx or solvers[0].ctx
         K = len(solvers)
         sets_list = [np.ascontiguousarray(s, np.int32) for s in sets_list]
-        assert len(sets_list) == K and all(s.ndim == 2 and s.shape[1] == 6 for s in sets_list)
         first_its = first_its or [0] * K; best_its = best_its or [-1] * K
-        probs = (_lib.MlpnpProblem * K)(*[s.problem(len(st), f, b) for s, st, f, b in zip(solvers, sets_list, first_its, best_its)])
-        p2d = np.concatenate([s.p2d for s in solvers]); Xw = np.concatenate([s.Xw for s in solvers]); sg = np.concatenate([s.sigma2 for s in solvers])
-        sets = np.concatenate(sets_list)
-        tN, tI = len(p2d), len(sets)
-        res = (_lib.MlpnpResult * K)()
-        inl = np.zeros(tN, np.uint8)
-        a = dict(it_inliers=np.zeros(tI, np.int32), it_Rt=np.zeros((tI, 12), np.float64), it_refine_inliers=np.zeros(tI, np.int32)) if aids else {}
-        c.check(c.L.eorb_mlpnp_ransac(c.h, probs, K, _p(p2d), _p(Xw), _p(sg), _p(sets), res, _p(inl), _p(a.get("it_inliers")), _p(a.get("it_Rt")),
-                                      _p(a.get("it_refine_inliers"))))
-        out, n0, i0 = [], 0, 0
-        for k, (s, st) in enumerate(zip(solvers, sets_list)):
-            r = res[k]
-            o = dict(inliers=inl[n0:n0 + s.N].copy(), stop_it=int(r.stop_it), iterations_used=int(r.iterations_used), best_it=int(r.best_it),
+        spec = dict(it_inliers=(np.int32, ()), it_Rt=(np.float64, (12,)), it_refine_inliers=(np.int32, ()))
+        out = []
+        for r, inl, a in _solve_problem_set(c, c.L.eorb_mlpnp_ransac, solvers, sets_list, 6,
+                                            [s.problem(len(st), f, b) for s, st, f, b in zip(solvers, sets_list, first_its, best_its)],
+                                            ("p2d", "Xw", "sigma2"), _lib.MlpnpResult, spec, aids):
+            o = dict(inliers=inl, stop_it=int(r.stop_it), iterations_used=int(r.iterations_used), best_it=int(r.best_it),
                      n_best=int(r.n_best), refined=int(r.refined), n_inliers=int(r.n_inliers), Tcw=np.array(r.Tcw, np.float32).reshape(4, 4))
-            o.update({key: v[i0:i0 + len(st)].copy() for key, v in a.items()})
+            o.update(a)
             out.append(o)
-            n0 += s.N; i0 += len(st)
         return out
 
     def iterate(self, nIterations, sets):

@@ -1214,6 +1214,34 @@ private:
     float mK[9]; float mSigma; int mMaxIterations;
 };
 
+namespace detail {
+// the tail of both SetRansacParameters: 1 when minInliers == N (exact), else ceil(log(1 - p) / log(1 - epsilon^3)), then
+// max(1, min(n, maxIterations)).  "int nIterations = ceil(...)" of a value no int holds converts as the reference's x86 build does
+// (INT_MIN -> 1 iteration)
+inline int ransac_max_iterations(double probability, float epsilon, bool exact, int maxIterations) {
+    int nIterations = 1;
+    if (!exact) {
+        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3)));
+        nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
+    }
+    return std::max(1, std::min(nIterations, maxIterations));
+}
+// the minimal sets of iterations [from_set, to_set), K draws without replacement each, appended to out:
+// randomInt(min, max) = DUtils::Random::RandomInt
+template <int K, class RandomInt> void draw_minimal_sets(int N, int from_set, int to_set, RandomInt&& randomInt, std::vector<int32_t>& out) {
+    std::vector<int32_t> all((size_t)N), avail;
+    for (int i = 0; i < N; i++) all[i] = i;
+    for (int it = from_set; it < to_set; it++) {
+        avail = all;
+        for (int i = 0; i < K; i++) {
+            const int randi = randomInt(0, (int)avail.size() - 1);
+            out.push_back(avail[randi]);
+            avail[randi] = avail.back(); avail.pop_back();
+        }
+    }
+}
+}  // namespace detail
+
 // Sim3Solver (src/Sim3Solver.cc) on the calling thread's context, over correspondences the adapter has compacted: the constructor's filter
 // (:71-91: null, isBad, index < 0) stays with it, and so do the set draw and the g2o::Sim3 composition.  The first
 // iterate() / find() makes ONE device call for all mRansacMaxIts iterations; iterate(n, ...) then replays its chunk of the loop from the
@@ -1235,33 +1263,17 @@ public:
         mN1 = N1 < 0 ? N : N1;
         SetRansacParameters();
     }
-    // :126-150.  "int nIterations = ceil(...)" of a value no int holds converts as the reference's x86 build does (INT_MIN -> 1 iteration)
+    // :126-150
     void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
-        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacMaxIts = maxIterations;
-        const float epsilon = (float)mRansacMinInliers / N;
-        int nIterations;
-        if (mRansacMinInliers == N) nIterations = 1;
-        else {
-            const double v = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow((double)epsilon, 3)));
-            nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
-        }
-        mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+        mRansacProb = probability; mRansacMinInliers = minInliers;
+        mRansacMaxIts = detail::ransac_max_iterations(mRansacProb, (float)mRansacMinInliers / N, mRansacMinInliers == N, maxIterations);
         mnIterations = 0; mnBestInliers = 0; mSolved = false;
     }
     int GetMaxIterations() const { return mRansacMaxIts; }
     // the minimal sets of :178-189 from the adapter's generator: randomInt(min, max) = DUtils::Random::RandomInt
     template <class RandomInt> void DrawSets(RandomInt&& randomInt) {
         mvSets.clear();
-        std::vector<int32_t> all((size_t)N), avail;
-        for (int i = 0; i < N; i++) all[i] = i;
-        for (int it = 0; it < mRansacMaxIts; it++) {
-            avail = all;
-            for (int i = 0; i < 3; i++) {
-                const int randi = randomInt(0, (int)avail.size() - 1);
-                mvSets.push_back(avail[randi]);
-                avail[randi] = avail.back(); avail.pop_back();
-            }
-        }
+        detail::draw_minimal_sets<3>(N, 0, mRansacMaxIts, randomInt, mvSets);
         mSolved = false;
     }
     void SetSets(const std::vector<int32_t>& vSets) { mvSets = vSets; mSolved = false; }      // mRansacMaxIts x 3 indices
@@ -1342,23 +1354,16 @@ public:
         mnKeyPoints = nKeyPoints < 0 ? N : nKeyPoints;
         SetRansacParameters();
     }
-    // :268-303.  mRansacEpsilon is a float; "int nIterations = ceil(...)" of a value no int holds converts as the reference's x86 build
-    // does (INT_MIN -> 1 iteration)
+    // :268-303.  mRansacEpsilon is a float
     void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 6, float epsilon = 0.4f,
                              float th2 = 5.991f) {
-        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacMaxIts = maxIterations; mRansacEpsilon = epsilon; mRansacMinSet = minSet;
+        mRansacProb = probability; mRansacMinInliers = minInliers; mRansacEpsilon = epsilon; mRansacMinSet = minSet;
         int nMinInliers = (int)(N * mRansacEpsilon);
         if (nMinInliers < mRansacMinInliers) nMinInliers = mRansacMinInliers;
         if (nMinInliers < minSet) nMinInliers = minSet;
         mRansacMinInliers = nMinInliers;
         if (mRansacEpsilon < (float)mRansacMinInliers / N) mRansacEpsilon = (float)mRansacMinInliers / N;
-        int nIterations;
-        if (mRansacMinInliers == N) nIterations = 1;
-        else {
-            const double v = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow((double)mRansacEpsilon, 3)));
-            nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
-        }
-        mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+        mRansacMaxIts = detail::ransac_max_iterations(mRansacProb, mRansacEpsilon, mRansacMinInliers == N, maxIterations);
         mTh2 = th2;
         mnIterations = 0; mnBestIt = -1;
     }
@@ -1367,16 +1372,7 @@ public:
     // the minimal sets of :176-188 from the adapter's generator, for nSets iterations (at least what the calls of iterate will reach):
     // randomInt(min, max) = DUtils::Random::RandomInt.  Sets already drawn stay; more are appended.
     template <class RandomInt> void DrawSets(RandomInt&& randomInt, int nSets) {
-        std::vector<int32_t> all((size_t)N), avail;
-        for (int i = 0; i < N; i++) all[i] = i;
-        for (int it = (int)(mvSets.size() / 6); it < nSets; it++) {
-            avail = all;
-            for (int i = 0; i < 6; i++) {
-                const int randi = randomInt(0, (int)avail.size() - 1);
-                mvSets.push_back(avail[randi]);
-                avail[randi] = avail.back(); avail.pop_back();
-            }
-        }
+        detail::draw_minimal_sets<6>(N, (int)(mvSets.size() / 6), nSets, randomInt, mvSets);
     }
     void SetSets(const std::vector<int32_t>& vSets) { mvSets = vSets; }      // 6 indices per iteration
     const std::vector<int32_t>& sets() const { return mvSets; }

@@ -117,6 +117,23 @@ def test_k3_equals_three_k1_calls_and_a_short_problem_stays_zero(fe, ctx):
     assert (short["it_refine_inliers"] == -1).all()
 
 
+def test_short_problem_between_two_live_ones(fe, ctx):
+    """K = 3 with N = 65 / 8 / 63 and 65 / 1 / 1 iterations: the middle problem has N < min_inliers, so every kernel's skip path runs between
+    two live problems whose sizes leave a tail in the count's 64-wide loop and in the hypothesis grid, at offsets that are no multiple of 64"""
+    pbs = [scenes.scene(65, seed=71, cam="k", iters=65), scenes.scene(8, seed=72, cam="p", iters=1, min_inliers=10),
+           scenes.scene(63, seed=73, cam="p", wrong=1.0, planar=True, iters=1)]
+    assert [(len(pb["p2d"]), len(pb["sets"])) for pb in pbs] == [(65, 65), (8, 1), (63, 1)]
+    out = _solve_k(fe, ctx, pbs)
+    refs = mr.MLPnPsolver.solve_candidates([scenes.solver(mr, pb) for pb in pbs], [pb["sets"] for pb in pbs], aids=True)
+    for k in (0, 2):
+        _same(out[k], refs[k], KEYS, "K=3 problem %d" % k)
+        _same(out[k], scenes.find(fe, pbs[k], aids=True, ctx=ctx), KEYS, "K=3 against K=1, problem %d" % k)
+    s = out[1]                                                             # (:154-158)
+    assert (s["stop_it"], s["best_it"], s["iterations_used"], s["n_best"], s["refined"], s["n_inliers"]) == (-1, -1, 0, 0, 0, 0)
+    assert not any(np.frombuffer(np.asarray(s[k]).tobytes(), np.uint8).any() for k in ("Tcw", "inliers", "it_inliers", "it_Rt"))
+    assert (s["it_refine_inliers"] == -1).all()                           # Refine was invoked at no iteration
+
+
 # ---- the result rule, resuming, odd inputs -----------------------------------------------------------------------------------------------
 def test_more_than_one_record_before_the_successful_refine(fe, ctx):
     pb = scenes.records_scene()

@@ -124,6 +124,22 @@ def test_k5_of_different_shapes(fe, ctx):
     assert out[3]["converged"] == 1 and out[3]["n_inliers"] == 3
 
 
+def test_short_problem_between_two_live_ones(fe, ctx):
+    """K = 3 with N = 65 / 6 / 63 and 65 / 1 / 1 iterations: the middle problem has N < min_inliers, so every kernel's skip path runs between
+    two live problems whose sizes leave a tail in the count's 64-wide loop and in the hypothesis grid, at offsets that are no multiple of 64"""
+    short = scenes.two_groups(3, 3, 7, "AB")                               # N = 6 < min_inliers = 7
+    short["sets"] = short["sets"][:1]
+    pbs = [scenes.scene(65, seed=71, pair="pk", iters=65), short, scenes.scene(63, seed=72, pair="kp", wrong=1.0, fix_scale=True, iters=1)]
+    assert [(len(pb["Xw1"]), len(pb["sets"])) for pb in pbs] == [(65, 65), (6, 1), (63, 1)]
+    out = _solve_k(fe, ctx, pbs)
+    for k in (0, 2):
+        _same(out[k], _ref(("short between", k), pbs[k]), KEYS, "K=3 problem %d" % k)
+        _same(out[k], scenes.find(fe, pbs[k], aids=True, ctx=ctx), KEYS, "K=3 against K=1, problem %d" % k)
+    s = out[1]                                                             # (:228-232)
+    assert (s["converged"], s["best_it"], s["n_inliers"], s["iterations_used"]) == (0, -1, 0, 0)
+    assert not any(np.frombuffer(np.asarray(s[k]).tobytes(), np.uint8).any() for k in ("T12", "R12", "t12", "s12", "inliers") + AIDS)
+
+
 def test_winners_without_the_aids_equal_those_with_them(fe, ctx):
     pbs = [scenes.scene(64, seed=51, pair="pk", iters=65), scenes.scene(65, seed=52, pair="kk", wrong=1.0, iters=63)]
     with_aids, without = _solve_k(fe, ctx, pbs, aids=True), _solve_k(fe, ctx, pbs, aids=False)
