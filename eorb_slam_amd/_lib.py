@@ -30,7 +30,7 @@ EXPORTS = [
     "eorb_search_by_bow_kf_keyframes",
     "eorb_new_map_points", "eorb_create_new_map_points", "eorb_create_new_map_points_kb8",
     "eorb_kfdb_clear", "eorb_kfdb_add", "eorb_kfdb_erase", "eorb_kfdb_info", "eorb_kfdb_get_scores", "eorb_kfdb_detect_reloc", "eorb_kfdb_detect_nbest",
-    "eorb_two_view_ransac", "eorb_two_view_check_rt",
+    "eorb_two_view_ransac", "eorb_two_view_check_rt", "eorb_two_view_reconstruct",
     "eorb_sim3_ransac", "eorb_mlpnp_ransac",
     "eorb_selfcheck_division", "eorb_selfcheck_math",
     "eorb_pack_events", "eorb_dev_alloc", "eorb_dev_free", "eorb_dev_upload", "eorb_dev_download",
@@ -127,6 +127,23 @@ class TvrParams(C.Structure):
 
 
 TVR_MAX_ITERS, TVR_MAX_MATCHES, TVR_MAX_KEYS, TVR_MAX_POSES = 1024, 16384, 1048576, 64
+TVR_FORM_STOCK, TVR_FORM_INFO = 0, 1
+
+
+class TvrReconParams(C.Structure):
+    """eorb_tvr_recon_params: Params2VR as eorb_two_view_reconstruct takes it"""
+    _fields_ = [("sigma", C.c_float), ("th_score", C.c_float), ("th_f", C.c_float), ("th_hf_ratio", C.c_float), ("min_parallax", C.c_float),
+                ("min_parallax_crt", C.c_float), ("min_triangulated", C.c_int), ("th_min_good_r", C.c_float), ("th_max_good_r_f", C.c_float),
+                ("th_max_good_r_h", C.c_float), ("th_rd_homo", C.c_float), ("form", C.c_int)]
+
+
+class TvrReconResult(C.Structure):
+    """eorb_tvr_recon_result"""
+    _fields_ = [("ok", C.c_int32), ("stage", C.c_int32), ("is_homography", C.c_int32), ("SH", C.c_float), ("SF", C.c_float), ("RH", C.c_float),
+                ("best_it_h", C.c_int32), ("best_it_f", C.c_int32), ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("n_inliers", C.c_int32),
+                ("n_min_good", C.c_int32), ("n_similar", C.c_int32), ("n_hyp", C.c_int32), ("hyp_good", C.c_int32 * 8),
+                ("hyp_parallax", C.c_float * 8), ("info_good", C.c_int32 * 8), ("hyp_best", C.c_int32), ("hyp_second", C.c_int32),
+                ("best_good", C.c_int32), ("second_good", C.c_int32), ("best_parallax", C.c_float), ("second_parallax", C.c_float)]
 
 
 class Sim3Problem(C.Structure):
@@ -437,6 +454,9 @@ def lib():
     L.eorb_mlpnp_ransac.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.eorb_two_view_check_rt.restype = ci
     L.eorb_two_view_check_rt.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp, cf, cf, ci, vp, ci, vp, vp, vp, vp, vp]
+    L.eorb_two_view_reconstruct.restype = ci
+    L.eorb_two_view_reconstruct.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, C.POINTER(TvrReconParams), C.POINTER(TvrReconResult),
+                                            vp, vp, vp, vp, vp, vp]
     L.eorb_selfcheck_division.restype = ci; L.eorb_selfcheck_division.argtypes = [vp, cf, cf, cf, C.POINTER(C.c_uint64)]
     L.eorb_selfcheck_math.restype = ci; L.eorb_selfcheck_math.argtypes = [vp, ci, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.eorb_pack_events.restype = None; L.eorb_pack_events.argtypes = [vp, C.c_size_t, vp]

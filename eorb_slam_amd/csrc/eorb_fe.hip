@@ -3023,6 +3023,81 @@ int eorb_two_view_check_rt(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const
     return EORB_OK;
 }
 
+int eorb_two_view_reconstruct(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2,
+        const int32_t* match12, int N, const int32_t* sets, int iters, const float* K, const eorb_tvr_recon_params* p,
+        eorb_tvr_recon_result* res, float* R21, float* t21, float* p3d, uint8_t* triangulated, uint8_t* trans_inliers, eorb_tvr_pose* hyp_poses)
+{
+    if (!c) return EORB_E_ARG;
+    const char* what = "two_view_reconstruct";
+    if (!kps1 || !kps2 || !match12 || !sets || !K || !p || n1 < 1 || n2 < 1 || !res || !R21 || !t21 || !p3d || !triangulated || !trans_inliers)
+        return set_err(c, EORB_E_ARG, "%s: bad arguments", what);
+    if (N < 8 || iters < 1) return set_err(c, EORB_E_ARG, "%s: %d matches (at least 8), %d iterations (at least 1)", what, N, iters);
+    if (p->min_triangulated < 0 || (p->form != EORB_TVR_FORM_STOCK && p->form != EORB_TVR_FORM_INFO))
+        return set_err(c, EORB_E_ARG, "%s: min_triangulated %d, form %d", what, p->min_triangulated, p->form);
+    int rc;
+    if ((rc = tv_check_sizes(c, what, n1, n2, N))) return rc;
+    if (iters > EORB_TVR_MAX_ITERS) return set_err(c, EORB_E_CAPACITY, "%s: %d iterations, at most EORB_TVR_MAX_ITERS = %d", what, iters, EORB_TVR_MAX_ITERS);
+    if ((rc = tv_check_matches(c, what, match12, N, n1, n2))) return rc;
+    for (int i = 0; i < 8 * iters; i++)
+        if (sets[i] < 0 || sets[i] >= N) return set_err(c, EORB_E_ARG, "%s: set %d holds the index %d of %d matches", what, i / 8, sets[i], N);
+    {   // vP3D / vbTriangulated are indexed by `first` (eorb_two_view_check_rt)
+        std::vector<uint8_t> seen((size_t)n1, 0);
+        for (int i = 0; i < N; i++) {
+            if (seen[match12[2 * i]]) return set_err(c, EORB_E_ARG, "%s: two matches have the first index %d", what, match12[2 * i]);
+            seen[match12[2 * i]] = 1;
+        }
+    }
+    fe_enter(c);
+    const std::vector<float> p1 = tv_points(kps1, n1), p2 = tv_points(kps2, n2);
+    const size_t sN = (size_t)N, sI = (size_t)iters, s1 = (size_t)n1;
+    constexpr size_t kH = 8;                                       // CheckRT's launch: the 8 hypotheses of ReconstructH
+    Arena A(c);
+    const size_t o_p1 = A.in(p1.data(), sizeof(float) * p1.size()), o_p2 = A.in(p2.data(), sizeof(float) * p2.size());
+    const size_t o_m = A.in(match12, sizeof(int32_t) * 2 * sN), o_s = A.in(sets, sizeof(int32_t) * 8 * sI);
+    // the RANSAC's own space and results, as in eorb_two_view_ransac
+    const size_t o_n1 = A.reserve(sizeof(float) * p1.size()), o_n2 = A.reserve(sizeof(float) * p2.size());
+    const size_t o_hdr = A.reserve(sizeof(float) * kTvHdrFloats), o_hyp = A.reserve(sizeof(float) * kTvHypFloats * 2 * sI), o_inl = A.reserve(2 * sI * sN);
+    const size_t o_rr = A.reserve(sizeof(float) * 22), o_ih = A.reserve(sN), o_if = A.reserve(sN);
+    const size_t o_sh = A.reserve(sizeof(float) * sI), o_sf = A.reserve(sizeof(float) * sI);
+    const size_t o_ith = A.reserve(sizeof(float) * 9 * sI), o_itf = A.reserve(sizeof(float) * 9 * sI);
+    const size_t o_sel = A.reserve(sN), o_ca = A.reserve(sizeof(float) * kH * sN);
+    // zeroed, contiguous: the results that travel (res | R21 | t21 | trans_inliers | triangulated | p3d | hyp_poses), then CheckRT's for 8 poses
+    const size_t o_res = A.reserve(sizeof(eorb_tvr_recon_result)), o_R = A.reserve(sizeof(float) * 18), o_t = A.reserve(sizeof(float) * 6);
+    const size_t o_ti = A.reserve(sN), o_tri = A.reserve(2 * s1), o_p3 = A.reserve(sizeof(float) * 6 * s1);
+    const size_t o_po = A.reserve(sizeof(eorb_tvr_pose) * kH), o_nh = A.reserve(sizeof(int32_t));
+    const size_t o_ng = A.reserve(sizeof(int32_t) * kH), o_cs = A.reserve(sizeof(float) * kH), o_g = A.reserve(kH * s1);
+    const size_t o_p8 = A.reserve(sizeof(float) * 3 * kH * s1), o_end = A.reserve(1);
+    if ((rc = A.upload())) return rc;
+    EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_res), 0, o_end - o_res, c->stream));
+    TvRansacArgs T{};
+    T.pts1 = A.dev<float2>(o_p1); T.pts2 = A.dev<float2>(o_p2); T.n1 = n1; T.n2 = n2;
+    T.match12 = A.dev<int32_t>(o_m); T.N = N; T.sets = A.dev<int32_t>(o_s); T.iters = iters;
+    T.sigma = p->sigma; T.th_score = p->th_score; T.th_f = p->th_f;
+    T.pn1 = A.dev<float2>(o_n1); T.pn2 = A.dev<float2>(o_n2); T.hdr = A.dev<float>(o_hdr); T.hyp = A.dev<float>(o_hyp); T.inl = A.dev<uint8_t>(o_inl);
+    T.res = A.dev<float>(o_rr); T.inliers_h = A.dev<uint8_t>(o_ih); T.inliers_f = A.dev<uint8_t>(o_if);
+    T.it_score_h = A.dev<float>(o_sh); T.it_score_f = A.dev<float>(o_sf); T.it_H = A.dev<float>(o_ith); T.it_F = A.dev<float>(o_itf);
+    TvReconArgs D{};
+    D.rres = T.res; D.inliers_h = T.inliers_h; D.inliers_f = T.inliers_f; D.N = N; D.n1 = n1;
+    memcpy(D.K, K, sizeof D.K); D.p = *p;
+    D.res = A.dev<eorb_tvr_recon_result>(o_res); D.poses = A.dev<float>(o_po); D.n_hyp = A.dev<int32_t>(o_nh);
+    D.sel_inl = A.dev<uint8_t>(o_sel); D.trans_inl = A.dev<uint8_t>(o_ti);
+    D.n_good = A.dev<int32_t>(o_ng); D.cos_sel = A.dev<float>(o_cs); D.good8 = A.dev<uint8_t>(o_g); D.p3d8 = A.dev<float>(o_p8);
+    D.R21 = A.dev<float>(o_R); D.t21 = A.dev<float>(o_t); D.tri = A.dev<uint8_t>(o_tri); D.p3d = A.dev<float>(o_p3);
+    TvCheckRtArgs Q{};
+    Q.pts1 = T.pts1; Q.pts2 = T.pts2; Q.n1 = n1; Q.match12 = T.match12; Q.N = N; Q.inliers = D.sel_inl;
+    memcpy(Q.K, K, sizeof Q.K); Q.th2 = 4.0f * (p->sigma * p->sigma); Q.min_parallax_crt = p->min_parallax_crt; Q.min_triangulated = p->min_triangulated;
+    Q.poses = D.poses; Q.Kp = (int)kH; Q.Kp_dev = D.n_hyp;
+    Q.n_good = A.dev<int32_t>(o_ng); Q.cos_sel = A.dev<float>(o_cs); Q.good = A.dev<uint8_t>(o_g); Q.p3d = A.dev<float>(o_p8); Q.cos_all = A.dev<float>(o_ca);
+    if ((rc = twoview_reconstruct_dev(c, T, D, Q))) return rc;
+    const char* h;
+    if ((rc = A.download(o_res, (hyp_poses ? o_po + sizeof(eorb_tvr_pose) * kH : o_p3 + sizeof(float) * 6 * s1) - o_res, &h))) return rc;
+    memcpy(res, h + o_res, sizeof *res);
+    memcpy(R21, h + o_R, sizeof(float) * 18); memcpy(t21, h + o_t, sizeof(float) * 6);
+    memcpy(trans_inliers, h + o_ti, sN); memcpy(triangulated, h + o_tri, 2 * s1); memcpy(p3d, h + o_p3, sizeof(float) * 6 * s1);
+    if (hyp_poses) memcpy(hyp_poses, h + o_po, sizeof(eorb_tvr_pose) * kH);
+    return EORB_OK;
+}
+
 int eorb_sim3_ransac(eorb_ctx* c, const eorb_sim3_problem* problems, int K, const float* Xw1, const float* Xw2,
         const float* sigma2_1, const float* sigma2_2, const int32_t* sets,
         eorb_sim3_result* results, uint8_t* inliers, int32_t* it_inliers, float* it_T12, float* it_T21, float* it_scale)

@@ -34,7 +34,25 @@ struct TvCheckRtArgs {
     const float* poses; int Kp;
     int32_t* n_good; float* cos_sel; uint8_t* good; float* p3d;      // good | p3d are contiguous and zero on entry
     float* cos_all;                                                     // Kp * N: cosParallax of a counted match, -2 otherwise
+    const int32_t* Kp_dev = nullptr;    // eorb_two_view_reconstruct: the hypothesis count tv_decide_kernel left (0, 4 or 8 <= Kp); null: Kp
 };
 int twoview_check_rt_dev(eorb_ctx* c, const TvCheckRtArgs& a);
+
+// eorb_two_view_reconstruct: what tv_decide_kernel and tv_resolve_kernel add around the two stages above; every pointer is device memory
+struct TvReconArgs {
+    const float* rres; const uint8_t* inliers_h; const uint8_t* inliers_f;      // what tv_finish_kernel left (TvRansacArgs::res, ...)
+    int N, n1;
+    float K[9]; eorb_tvr_recon_params p;
+    eorb_tvr_recon_result* res;         // zero on entry, as every output below
+    float* poses;                       // 8 * kTvPoseFloats: the hypotheses, zeros past the count
+    int32_t* n_hyp;                     // the device-side hypothesis count for CheckRT
+    uint8_t* sel_inl;                   // N: the flags of the chosen model, CheckRT's vbMatchesInliers
+    uint8_t* trans_inl;                 // N: vbTransInliers (INFO form)
+    const int32_t* n_good; const float* cos_sel; const uint8_t* good8; const float* p3d8;      // CheckRT's results for 8 poses
+    float* R21; float* t21; uint8_t* tri; float* p3d;                                          // the two result slots
+};
+// the RANSAC, tv_decide_kernel, CheckRT on its hypotheses, tv_resolve_kernel; R.res / inliers_* must be A.rres / inliers_*, and
+// T.poses / inliers / Kp_dev must be A.poses / sel_inl / n_hyp with T.Kp = 8
+int twoview_reconstruct_dev(eorb_ctx* c, const TvRansacArgs& R, const TvReconArgs& A, const TvCheckRtArgs& T);
 
 }  // namespace eorb

@@ -11,6 +11,11 @@
 //   tv_finish_kernel     the first-wins scan over the iterations' scores and the copy of the winners
 // eorb_two_view_check_rt is two: tv_check_rt_kernel (one thread per (pose, match)) and tv_select_kernel (one workgroup per pose: nGood
 // and the element of the sorted vCosParallax by a radix select, no sort).
+// eorb_two_view_reconstruct is those six with two more on one stream and no host step between them:
+//   tv_decide_kernel     after tv_finish_kernel: the SH+SF == 0 exit, RH and the H/F choice, the inlier count, DecomposeE or the Faugeras
+//                        decomposition on one lane (twoview_core.h), the 4 or 8 eorb_tvr_pose records and their count in device memory
+//   tv_resolve_kernel    after tv_select_kernel: the parallax (fdlibm acos), the decision rule of the form, the one or two result slots
+// CheckRT is launched for 8 poses and reads the count and the chosen flags from device memory.
 #include "twoview.h"
 #include "kb8_dev.h"
 
@@ -291,6 +296,28 @@ __global__ __launch_bounds__(kTvLanes) void tv_hyp_kernel(TvRansacArgs a, int hb
 #pragma unroll
     for (int k = 0; k < 9; k++) { out[k] = X21[k]; out[9 + k] = 0.f; }
 }
+
+// cv::SVD::compute of a 3x3 (with or without FULL_UV: one computation on a square matrix) for one lane of a workgroup, in an LDS
+// column as SVDecomp(Fpre) above: At = A^T, u = At^T after the normalisation, w = (float)W
+__device__ __noinline__ void tv_svd33(const float* A, float* w, float* u, float* vt)
+{
+    constexpr int M = 3, N = 3;
+    __shared__ double smem[(3 * 8 + 2 * 9 * 4) * kTvLanes / 8];      // tv_jacobi's column layout; the one calling lane uses column 0
+    double* W = smem;
+    float* At = (float*)(smem + N * kTvLanes);
+    float* Vt = At + N * M * kTvLanes;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) TV_A(i, k) = A[3 * k + i];
+    tv_jacobi<M, N, N, true, true>(At, Vt, W);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { u[3 * i + k] = TV_A(k, i); vt[3 * i + k] = TV_V(i, k); }
+        w[i] = (float)TV_W(i);
+    }
+}
 #undef TV_A
 #undef TV_V
 #undef TV_W
@@ -410,7 +437,8 @@ __device__ __forceinline__ uint32_t tv_cos_key(float f)
 __global__ __launch_bounds__(256) void tv_check_rt_kernel(TvCheckRtArgs a)
 {
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (id >= (long long)a.Kp * a.N) return;
+    const int Kp = a.Kp_dev ? min(*a.Kp_dev, a.Kp) : a.Kp;      // (the launch is sized for a.Kp: workgroups past a device-side count leave)
+    if (id >= (long long)Kp * a.N) return;
     const int h = (int)(id / a.N), i = (int)(id % a.N);
     float* cosv = a.cos_all + (size_t)h * a.N + i;
     *cosv = -2.f;
@@ -469,6 +497,7 @@ __global__ __launch_bounds__(256) void tv_select_kernel(TvCheckRtArgs a)
     __shared__ uint32_t s_prefix;
     __shared__ int s_k, s_total;
     const int tid = threadIdx.x, h = blockIdx.x;
+    if (a.Kp_dev && h >= *a.Kp_dev) return;            // (uniform over the workgroup, before any barrier)
     const float* cosv = a.cos_all + (size_t)h * a.N;
     uint32_t prefix = 0, mask = 0;
     int k = 0;
@@ -515,6 +544,119 @@ int twoview_check_rt_dev(eorb_ctx* c, const TvCheckRtArgs& a)
     { ProfScope ps(c, "tv_select");
       tv_select_kernel<<<a.Kp, 256, 0, c->stream>>>(a);
       EORB_LAUNCH_CHECK(c, "tv_select_kernel"); }
+    return EORB_OK;
+}
+
+// ---- Reconstruct (:67-262): what stands between and after the two stages ----------------------------------------------------------------
+#define TVC_FN __device__ static inline
+#define TVC_HI(x) ((int32_t)__double2hiint(x))
+#define TVC_LO(x) ((uint32_t)__double2loint(x))
+#define TVC_MK(hi, lo) __hiloint2double((int)(hi), (int)(lo))
+#define TVC_SVD33(A, w, u, vt) tv_svd33((A), (w), (u), (vt))
+#define TVC_UNROLL _Pragma("unroll")
+#include "twoview_core.h"
+
+// :139-157 / :236-261 and the heads of ReconstructF / ReconstructH: the SH+SF == 0 exit, RH and the H/F choice; every lane copies the
+// chosen model's flags and the wavefronts count them (integers: no order); lane 0 then forms the 4 or 8 hypotheses with their P2 and O2
+__global__ __launch_bounds__(256) void tv_decide_kernel(TvReconArgs a)
+{
+    __shared__ int s_stage, s_isH, s_N;
+    const int tid = threadIdx.x;
+    eorb_tvr_recon_result* r = a.res;
+    if (tid == 0) {
+        const float SH = a.rres[0], SF = a.rres[1];
+        r->SH = SH; r->SF = SF;
+        r->best_it_h = ((const int32_t*)a.rres)[2]; r->best_it_f = ((const int32_t*)a.rres)[3];
+#pragma unroll
+        for (int k = 0; k < 9; k++) { r->H21[k] = a.rres[4 + k]; r->F21[k] = a.rres[13 + k]; }
+        int stage = 2, isH = 0;
+        if (SH + SF == 0.f) stage = 0;
+        else {
+            const float RH = SH / (SH + SF);
+            r->RH = RH;
+            isH = RH > a.p.th_hf_ratio;
+        }
+        r->is_homography = isH;
+        s_stage = stage; s_isH = isH; s_N = 0;
+    }
+    __syncthreads();
+    int stage = s_stage;
+    const int isH = s_isH;
+    const uint8_t* src = (stage == 0 || !isH) ? a.inliers_f : a.inliers_h;
+    int cnt = 0;
+    for (int base = 0; base < a.N; base += 256) {
+        const int i = base + tid;
+        const uint8_t f = i < a.N ? src[i] : 0;
+        if (i < a.N) {
+            a.sel_inl[i] = f;
+            if (a.p.form == EORB_TVR_FORM_INFO) a.trans_inl[i] = f;
+        }
+        cnt += __popcll(__ballot(f != 0));
+    }
+    if ((tid & 63) == 0 && stage != 0) atomicAdd(&s_N, cnt);
+    __syncthreads();
+    if (tid != 0) return;
+    int n_hyp = 0;
+    if (stage != 0) {
+        r->n_inliers = s_N;
+        if (!isH) { tvc_hypotheses_f(a.K, r->F21, a.poses); n_hyp = 4; }
+        else if (tvc_hypotheses_h(a.K, r->H21, a.p.th_rd_homo, a.poses)) n_hyp = 8;
+        else stage = 1;
+    }
+    r->stage = stage; r->n_hyp = n_hyp;
+    *a.n_hyp = n_hyp;
+}
+
+// after CheckRT: the parallax of every hypothesis, the decision rule of the form, and the copy of the one or two chosen hypotheses into
+// the result slots (R, t by lane 0; the n1 rows of vP3D and vbTriangulated by every lane)
+__global__ __launch_bounds__(256) void tv_resolve_kernel(TvReconArgs a)
+{
+    __shared__ int s_slot[2];
+    const int tid = threadIdx.x;
+    eorb_tvr_recon_result* r = a.res;
+    if (tid == 0) {
+        s_slot[0] = s_slot[1] = -1;
+        r->hyp_best = r->hyp_second = -1;
+        if (r->stage == 2) {
+            int32_t ng[8]; float par[8];
+#pragma unroll
+            for (int h = 0; h < 8; h++) {
+                ng[h] = h < r->n_hyp ? a.n_good[h] : 0;
+                par[h] = h < r->n_hyp ? tvc_parallax(ng[h], a.cos_sel[h]) : 0.f;
+            }
+            tvc_resolve(&a.p, r->n_inliers, ng, par, r);
+            s_slot[0] = r->hyp_best; s_slot[1] = r->hyp_second;
+            for (int s = 0; s < 2; s++) {
+                const int h = s_slot[s];
+                if (h < 0) continue;
+                const float* pose = a.poses + kTvPoseFloats * h;
+                for (int k = 0; k < 9; k++) a.R21[9 * s + k] = pose[k];
+                for (int k = 0; k < 3; k++) a.t21[3 * s + k] = pose[9 + k];
+            }
+        }
+    }
+    __syncthreads();
+    for (int s = 0; s < 2; s++) {
+        const int h = s_slot[s];
+        if (h < 0) continue;
+        const uint8_t* g = a.good8 + (size_t)h * a.n1;
+        const float* p = a.p3d8 + (size_t)h * a.n1 * 3;
+        for (int i = tid; i < a.n1; i += 256) a.tri[(size_t)s * a.n1 + i] = g[i];
+        for (int i = tid; i < 3 * a.n1; i += 256) a.p3d[(size_t)s * a.n1 * 3 + i] = p[i];
+    }
+}
+
+int twoview_reconstruct_dev(eorb_ctx* c, const TvRansacArgs& R, const TvReconArgs& A, const TvCheckRtArgs& T)
+{
+    int rc;
+    if ((rc = twoview_ransac_dev(c, R))) return rc;
+    { ProfScope ps(c, "tv_decide");
+      tv_decide_kernel<<<1, 256, 0, c->stream>>>(A);
+      EORB_LAUNCH_CHECK(c, "tv_decide_kernel"); }
+    if ((rc = twoview_check_rt_dev(c, T))) return rc;
+    { ProfScope ps(c, "tv_resolve");
+      tv_resolve_kernel<<<1, 256, 0, c->stream>>>(A);
+      EORB_LAUNCH_CHECK(c, "tv_resolve_kernel"); }
     return EORB_OK;
 }
 

@@ -1379,7 +1379,8 @@ class TwoViewReconstruction:
     """The two stages of TwoViewReconstruction (src/TwoViewReconstruction.cc) whose cost grows with the match count:
     find_homography_fundamental = the FindHomography / FindFundamental threads of Reconstruct (:131-136), check_rt = CheckRT (:1242-1352)
     for all pose hypotheses of ReconstructF / ReconstructH in one call.  The set draw, the H/F choice, K.t()*F21*K, DecomposeE, the
-    decomposition of H, resolveReconstStat* and the acos of the parallax stay with the caller."""
+    decomposition of H, resolveReconstStat* and the acos of the parallax stay with the caller of these two; reconstruct is Reconstruct
+    whole in one device call, and only the set draw stays with its caller."""
 
     def __init__(self, K, sigma=1.0, iterations=200, th_score=5.991, th_f=3.841, min_parallax_crt=0.99998, min_triangulated=50, ctx=None):
         self.K = np.ascontiguousarray(np.asarray(K, np.float32).reshape(3, 3))
@@ -1432,6 +1433,45 @@ class TwoViewReconstruction:
                                            _p(o["n_good"]), _p(o["good"]), _p(o["p3d"]), _p(o["cos_sel"]), _p(ca)))
         if want_cos_all:
             o["cos_all"] = ca
+        return o
+
+    def recon_params(self, form=_lib.TVR_FORM_STOCK, th_hf_ratio=0.45, min_parallax=1.0, th_min_good_r=0.9, th_max_good_r_f=0.7,
+                     th_max_good_r_h=0.75, th_rd_homo=1.00001, min_parallax_crt=None, min_triangulated=None):
+        """eorb_tvr_recon_params: this object's sigma, thresholds and CheckRT settings with Params2VR's defaults for the rest"""
+        mp = self.min_parallax_crt if min_parallax_crt is None else float(np.float32(min_parallax_crt))
+        mt = self.min_triangulated if min_triangulated is None else int(min_triangulated)
+        return _lib.TvrReconParams(self.params.sigma, self.params.th_score, self.params.th_f, th_hf_ratio, min_parallax, mp, mt, th_min_good_r,
+                                   th_max_good_r_f, th_max_good_r_h, float(np.float32(th_rd_homo)), int(form))
+
+    def reconstruct(self, kps1, kps2, matches12, sets, form=_lib.TVR_FORM_STOCK, params=None, want_poses=False, **overrides):
+        """TwoViewReconstruction::Reconstruct as one device call (eorb_two_view_reconstruct): the RANSAC, the H/F choice, DecomposeE or the
+        Faugeras decomposition, CheckRT for the 4 or 8 hypotheses, the parallax and the decision of the form (TVR_FORM_STOCK: :67-158,
+        TVR_FORM_INFO: :162-262 with its ReconstInfo).  params: an eorb_tvr_recon_params, or built by recon_params(form, **overrides).
+        Returns a dict of every field of eorb_tvr_recon_result (ok, stage, is_homography, SH, SF, RH, ..., best_parallax,
+        second_parallax) and R21 [2, 3, 3], t21 [2, 3], p3d [2, n1, 3], triangulated [2, n1], trans_inliers [N]; with want_poses also
+        hyp_poses [8, 27].  include/eorb_fe.h states which slot holds what in each form."""
+        c = self.ctx
+        kps1, kps2, m = self._in(kps1, kps2, matches12)
+        sets = np.ascontiguousarray(sets, np.int32)
+        assert sets.ndim == 2 and sets.shape[1] == 8
+        par = params if params is not None else self.recon_params(form, **overrides)
+        N, n1 = len(m), len(kps1)
+        r = _lib.TvrReconResult()
+        o = dict(R21=np.zeros((2, 3, 3), np.float32), t21=np.zeros((2, 3), np.float32), p3d=np.zeros((2, n1, 3), np.float32),
+                 triangulated=np.zeros((2, n1), np.uint8), trans_inliers=np.zeros(N, np.uint8))
+        po = np.zeros((8, 27), np.float32) if want_poses else None
+        c.check(c.L.eorb_two_view_reconstruct(c.h, _p(kps1), n1, _p(kps2), len(kps2), _p(m), N, _p(sets), len(sets), _p(self.K), C.byref(par),
+                                              C.byref(r), _p(o["R21"]), _p(o["t21"]), _p(o["p3d"]), _p(o["triangulated"]), _p(o["trans_inliers"]),
+                                              _p(po)))
+        for name, typ in r._fields_:
+            v = getattr(r, name)
+            if hasattr(v, "__len__"):
+                o[name] = np.array(v[:], np.float32 if typ._type_ is C.c_float else np.int32)
+            else:
+                o[name] = np.float32(v) if typ is C.c_float else int(v)
+        o["H21"] = o["H21"].reshape(3, 3); o["F21"] = o["F21"].reshape(3, 3)
+        if want_poses:
+            o["hyp_poses"] = po
         return o
 
 

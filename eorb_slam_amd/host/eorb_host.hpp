@@ -1156,7 +1156,8 @@ private:
 // The two stages of TwoViewReconstruction (src/TwoViewReconstruction.cc) whose cost grows with the match count, on the calling thread's
 // context.  FindHomographyFundamental = the two threads of Reconstruct (:131-136 / :228-233) in one call; CheckRT = :1242-1352 for every
 // pose hypothesis of ReconstructF (4) / ReconstructH (8) in one call.  The set draw (mvSets), SH/(SH+SF) and the H/F choice, K.t()*F21*K,
-// DecomposeE, the Faugeras decomposition, resolveReconstStat* and acos stay with the adapter.
+// DecomposeE, the Faugeras decomposition, resolveReconstStat* and acos stay with an adapter that uses these two; Reconstruct below is the
+// whole function in one device call, and only the set draw (mvSets) stays with the adapter.
 class TwoViewReconstruction {
 public:
     typedef std::pair<int, int> Match;
@@ -1205,7 +1206,78 @@ public:
                                        o.cosParallax.data(), cosAll ? o.cosAll.data() : nullptr));
         return o;
     }
+
+    // ---- Reconstruct as one device call (eorb_two_view_reconstruct), in the reference's two overload shapes with OpenCV-free types:
+    // a 3x3 / 3x1 cv::Mat is a Mat33 / Vec3 (row-major), a cv::Point3f a Vec3.  vMatches12 is the reference's argument (per key of frame 1
+    // the index of its match in frame 2, or -1; mvMatches12 is built from it as :81-90 does); vSets, the draw of :107-124, is the
+    // caller's (mMaxIterations x 8 indices into mvMatches12).  `last` keeps every field of the call's eorb_tvr_recon_result.
+    struct Vec3 { float v[3]; };
+    struct Mat33 { float m[9]; };
+    struct ReconstInfo {                   // include/TwoViewReconstruction.h:62-80, with its initial values
+        int mnBestGood = 0, mnMinGood = 0, mnSecondBest = 0; float mBestParallax = -1.f, mSecondBestPar = -1.f; bool isHomography = true;
+        float mHScore = 0.f, mFScore = 0.f, mHFRatio = 0.f; unsigned char mnSimilar = 0; std::vector<int> mvnGood = std::vector<int>(8, 0);
+    };
+    struct Params2VR {                     // the members of Params2VR the decision reads (mThChiSq*, mMinParallaxCRT, mMinTriangulated: above)
+        float mThHFRatio = 0.45f, mDefMinParallax = 1.0f, mThMinGoodR = 0.9f, mThMaxGoodR_F = 0.7f, mThMaxGoodR_H = 0.75f, mThRDHomo = (float)1.00001;
+    } mParams2VR;
+    mutable eorb_tvr_recon_result last{};
+
+    // :67-158.  R21 / t21 / vP3D / vbTriangulated are written when the call returns true; R21 is left empty by the reference otherwise,
+    // and here the arguments are left as they were.
+    bool Reconstruct(const std::vector<eorb_keypoint>& vKeys1, const std::vector<eorb_keypoint>& vKeys2, const std::vector<int>& vMatches12,
+                     const std::vector<int32_t>& vSets, Mat33& R21, Vec3& t21, std::vector<Vec3>& vP3D, std::vector<bool>& vbTriangulated) const {
+        Out o = call(vKeys1, vKeys2, vMatches12, vSets, EORB_TVR_FORM_STOCK);
+        if (!last.ok) return false;
+        const size_t n1 = vKeys1.size();
+        std::memcpy(R21.m, o.R21.data(), sizeof R21.m); std::memcpy(t21.v, o.t21.data(), sizeof t21.v);
+        vP3D.resize(n1); vbTriangulated.assign(n1, false);
+        for (size_t i = 0; i < n1; i++) { std::memcpy(vP3D[i].v, &o.p3d[3 * i], sizeof vP3D[i].v); vbTriangulated[i] = o.tri[i] != 0; }
+        return true;
+    }
+    // :162-262.  The vectors get two entries (best, second best); at the SH+SF == 0 exit only vbTransInliers is written (:237), at the d test
+    // of ReconstructH vbTransInliers and the three scores, as the reference does.  Where the reference would read vR[-1] (ReconstructH with
+    // fewer than two hypotheses that triangulate anything) the entry is zeros.
+    bool Reconstruct(const std::vector<eorb_keypoint>& vKeys1, const std::vector<eorb_keypoint>& vKeys2, const std::vector<int>& vMatches12,
+                     const std::vector<int32_t>& vSets, std::vector<Mat33>& R21, std::vector<Vec3>& t21, std::vector<std::vector<Vec3>>& vP3D,
+                     std::vector<std::vector<bool>>& vbTriangulated, std::vector<bool>& vbTransInliers, ReconstInfo& reconstInfo) const {
+        Out o = call(vKeys1, vKeys2, vMatches12, vSets, EORB_TVR_FORM_INFO);
+        vbTransInliers.assign(o.trans.size(), false);
+        for (size_t i = 0; i < o.trans.size(); i++) vbTransInliers[i] = o.trans[i] != 0;
+        if (last.stage == 0) return false;
+        reconstInfo.mHScore = last.SH; reconstInfo.mFScore = last.SF; reconstInfo.mHFRatio = last.RH;
+        if (last.stage == 1) return false;
+        const size_t n1 = vKeys1.size();
+        R21.assign(2, Mat33{}); t21.assign(2, Vec3{}); vP3D.assign(2, std::vector<Vec3>(n1)); vbTriangulated.assign(2, std::vector<bool>(n1, false));
+        for (int s = 0; s < 2; s++) {
+            std::memcpy(R21[s].m, &o.R21[9 * s], sizeof R21[s].m); std::memcpy(t21[s].v, &o.t21[3 * s], sizeof t21[s].v);
+            for (size_t i = 0; i < n1; i++) { std::memcpy(vP3D[s][i].v, &o.p3d[3 * (s * n1 + i)], sizeof vP3D[s][i].v); vbTriangulated[s][i] = o.tri[s * n1 + i] != 0; }
+        }
+        reconstInfo.mnBestGood = last.best_good; reconstInfo.mBestParallax = last.best_parallax;
+        reconstInfo.mnSecondBest = last.second_good; reconstInfo.mSecondBestPar = last.second_parallax;
+        if (!last.is_homography) {         // (:972-976, resolveReconstStatF; ReconstructH writes neither isHomography nor these two)
+            for (int i = 0; i < 4; i++) reconstInfo.mvnGood[i] = last.info_good[i];
+            reconstInfo.isHomography = false;
+            reconstInfo.mnMinGood = last.n_min_good; reconstInfo.mnSimilar = (unsigned char)last.n_similar;
+        } else
+            for (int i = 0; i < 8; i++) reconstInfo.mvnGood[i] = last.info_good[i];
+        return last.ok != 0;
+    }
 private:
+    struct Out { std::vector<float> R21, t21, p3d; std::vector<uint8_t> tri, trans; };
+    Out call(const std::vector<eorb_keypoint>& vKeys1, const std::vector<eorb_keypoint>& vKeys2, const std::vector<int>& vMatches12,
+             const std::vector<int32_t>& vSets, int form) const {
+        auto& c = eorb_host::thread_context();
+        std::vector<int32_t> m;
+        for (size_t i = 0; i < vMatches12.size(); i++) if (vMatches12[i] >= 0) { m.push_back((int32_t)i); m.push_back(vMatches12[i]); }
+        const int N = (int)(m.size() / 2), n1 = (int)vKeys1.size();
+        eorb_tvr_recon_params p{mSigma, params.th_score, params.th_f, mParams2VR.mThHFRatio, mParams2VR.mDefMinParallax, mMinParallaxCRT,
+                                mMinTriangulated, mParams2VR.mThMinGoodR, mParams2VR.mThMaxGoodR_F, mParams2VR.mThMaxGoodR_H, mParams2VR.mThRDHomo, form};
+        Out o;
+        o.R21.assign(18, 0.f); o.t21.assign(6, 0.f); o.p3d.assign((size_t)6 * n1, 0.f); o.tri.assign((size_t)2 * n1, 0); o.trans.assign((size_t)N, 0);
+        c.check(eorb_two_view_reconstruct(c.get(), vKeys1.data(), n1, vKeys2.data(), (int)vKeys2.size(), m.data(), N, vSets.data(), (int)(vSets.size() / 8),
+                                          mK, &p, &last, o.R21.data(), o.t21.data(), o.p3d.data(), o.tri.data(), o.trans.data(), nullptr));
+        return o;
+    }
     static std::vector<int32_t> flat(const std::vector<Match>& v) {
         std::vector<int32_t> m(2 * v.size());
         for (size_t i = 0; i < v.size(); i++) { m[2 * i] = v[i].first; m[2 * i + 1] = v[i].second; }

@@ -608,9 +608,9 @@ int eorb_kb8_triangulate_matches(eorb_ctx* ctx, const eorb_camera* cam1, const e
 
 /* ---- TwoViewReconstruction (src/TwoViewReconstruction.cc): the two stages whose cost grows with the match count ----------------------
  * The call after SearchForInitialization in Tracking::MonocularInitialization (src/Tracking.cc:3559) and after the KLT match of the
- * event trackers (EvImBuilder.cpp:622, EvAsynchTracker.cpp:1044, ...).  What stays with the caller is 3x3 algebra and decisions: the
- * set draw (DUtils::Random, :107-124), SH/(SH+SF) and the H/F choice, K.t()*F21*K, DecomposeE, the Faugeras decomposition of
- * ReconstructH, resolveReconstStat*, and the acos of the parallax.
+ * event trackers (EvImBuilder.cpp:622, EvAsynchTracker.cpp:1044, ...).  What stays with the caller of these two is 3x3 algebra and
+ * decisions: the set draw (DUtils::Random, :107-124), SH/(SH+SF) and the H/F choice, K.t()*F21*K, DecomposeE, the Faugeras decomposition
+ * of ReconstructH, resolveReconstStat*, and the acos of the parallax.  eorb_two_view_reconstruct, after them, is Reconstruct whole.
  *
  * Limits, decided from the sizes before any array is read (EORB_E_CAPACITY): */
 #define EORB_TVR_MAX_ITERS    1024
@@ -654,6 +654,70 @@ int eorb_two_view_ransac(eorb_ctx* ctx, const eorb_keypoint* kps1, int n1, const
 int eorb_two_view_check_rt(eorb_ctx* ctx, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2, const int32_t* match12, int N,
         const uint8_t* inliers, const float* K, float th2, float min_parallax_crt, int min_triangulated,
         const eorb_tvr_pose* poses, int Kp, int32_t* n_good, uint8_t* good, float* p3d, float* cos_sel, float* cos_all);
+
+/* TwoViewReconstruction::Reconstruct as one call: the two stages above and everything the reference does between and after them -- the
+ * SH+SF == 0 exit, RH = SH/(SH+SF) and the H/F choice, K.t()*F21*K and DecomposeE (:1354-1375) or the Faugeras decomposition of
+ * ReconstructH, P2 = K*[R|t] and O2 = -R.t()*t of CheckRT (:1258-1270), CheckRT for the 4 or 8 hypotheses, the acos of the parallax, and
+ * the decision.  One upload, one wait, one download; nothing returns to the host between the stages.  What stays with the caller: the
+ * set draw (DUtils::Random, :107-124) and KannalaBrandt8's un-distortion of the keys before the call.
+ * Keys, matches and sets mean what they mean in eorb_two_view_ransac, with its limits (EORB_TVR_MAX_*, EORB_E_CAPACITY from the sizes,
+ * before any array is read) and errors; EORB_E_ARG besides for N < 8, a match or set index out of range, two matches with one `first`
+ * index (as eorb_two_view_check_rt), min_triangulated < 0, or a form that is neither of the two. */
+#define EORB_TVR_FORM_STOCK 0   /* Reconstruct :67-158 with ReconstructF :610-710, ReconstructH :712-873 */
+#define EORB_TVR_FORM_INFO  1   /* Reconstruct :162-262 with ReconstructF :902-979, ReconstructH :991-1175 */
+typedef struct eorb_tvr_recon_params {
+    float sigma, th_score, th_f;             /* as eorb_tvr_params */
+    float th_hf_ratio;                       /* mThHFRatio 0.45f */
+    float min_parallax;                      /* mDefMinParallax 1.0f */
+    float min_parallax_crt;                  /* (float)0.99998 */
+    int   min_triangulated;                  /* 50 */
+    float th_min_good_r, th_max_good_r_f, th_max_good_r_h;   /* 0.9f 0.7f 0.75f */
+    float th_rd_homo;                        /* (float)1.00001 */
+    int   form;
+} eorb_tvr_recon_params;
+typedef struct eorb_tvr_recon_result {
+    int32_t ok;              /* what Reconstruct returns */
+    int32_t stage;           /* 0: SH+SF == 0;  1: ReconstructH left at the d1/d2, d2/d3 test;  2: hypotheses checked */
+    int32_t is_homography;   /* RH > th_hf_ratio */
+    float   SH, SF, RH;  int32_t best_it_h, best_it_f;  float H21[9], F21[9];
+    int32_t n_inliers;       /* N of ReconstructF / ReconstructH */
+    int32_t n_min_good, n_similar;           /* F forms; 0 in the H forms */
+    int32_t n_hyp;           /* 4 or 8; 0 when stage < 2 */
+    int32_t hyp_good[8]; float hyp_parallax[8];   /* per hypothesis in hypothesis order (R1t1, R2t1, R1t2, R2t2 / vR[0..7]) */
+    int32_t info_good[8];    /* ReconstInfo::mvnGood as the reference writes it: F sorted descending in [0..3], H in hypothesis order */
+    int32_t hyp_best, hyp_second;            /* hypothesis index of slot 0 / slot 1, -1: none */
+    int32_t best_good, second_good; float best_parallax, second_parallax;
+} eorb_tvr_recon_result;
+/* Outputs: R21[2][9], t21[2][3], p3d[2][n1][3] (vP3D, indexed by `first`), triangulated[2][n1] (vbTriangulated), trans_inliers[N],
+ * hyp_poses[8] (test aid, NULL to skip: the hypotheses as CheckRT takes them, zeros past n_hyp).  A slot that is not written is zeros.
+ * - stage 0 (SH+SF == 0.f): ok = 0, RH = 0, is_homography = 0, n_inliers = 0, everything after F21 in the result is zero (hyp_best =
+ *   hyp_second = -1).  stage 1: is_homography = 1, n_inliers is counted, n_hyp = 0, the rest as at stage 0.  At either, every output array
+ *   is zero apart from trans_inliers below.
+ * - STOCK form.  Slot 0 is written only when ok == 1, and hyp_best is then its hypothesis (else -1); the reference leaves R21 empty
+ *   otherwise.  Slot 1, hyp_second (-1), second_parallax, info_good (the form has no ReconstInfo) and trans_inliers are always zero.
+ *   F: best_good = maxGood, best_parallax = the parallax of the first hypothesis whose count equals maxGood (the one the if / else-if
+ *   chain :663-707 looks at), second_good = 0.  H: best_good / second_good / best_parallax as the walk :837-858 leaves them
+ *   (best_parallax = -1 when no hypothesis has nGood > 0).
+ * - INFO form, F.  Slots 0 and 1 are the first two entries of the multimap<int, ..., greater<int>> (:937-971): descending nGood, equal
+ *   counts in insertion order 1, 2, 3, 4 (C++11 inserts an equal key at the upper bound).  info_good[0..3] is that sorted order and
+ *   [4..7] are 0 -- a reused ReconstInfo would keep stale values there, which resolveReconstStatF then counts: the caller's business.
+ *   ok = resolveReconstStatF (:876-900); n_similar is its unsigned char.
+ * - INFO form, H.  Slots 0 and 1 follow the best / second walk of :1118-1148 (strict >: the earlier hypothesis keeps a tie; a new best
+ *   hands the old best down to second).  The reference reads vR[-1] (:1160, :1167) when no hypothesis, or only one, has nGood > 0:
+ *   undefined behaviour.  Here such a slot is zeros with index -1 (its parallax field keeps the walk's initial -1); ok still follows
+ *   resolveReconstStatH (:981-989), which is false then.  info_good is nGood in hypothesis order.
+ * - trans_inliers (vbTransInliers; INFO only, zeros in STOCK): at stage 0 inliers_f (:237), otherwise the chosen model's flags (:906,
+ *   :995), also at stage 1.
+ * - Comparisons keep the reference's types: nGood > thMaxGoodR*maxGood compares floats (an int against a float product in the STOCK
+ *   form, (float)nGood > thMaxGoodR*float(maxGood) in the INFO form); nMinGood = max(static_cast<int>(mThMinGoodR*N), minTriangulated)
+ *   with the product in float; d1/d2 < thRDH and d2/d3 < thRDH in float; th2 = 4.0f*(sigma*sigma); RH > th_hf_ratio and SH+SF == 0.f in
+ *   float; parallax = (float)(acos((double)cos)*180/CV_PI), 0 when nGood == 0, with acos as fdlibm's e_acos.c on both sides.
+ * - NaN.  A NaN anywhere makes its comparison false as IEEE has it; nothing is special-cased.
+ * The OpenCV 3.4.1 arithmetic is restated on its scalar paths and pinned to nothing outside this repository. */
+int eorb_two_view_reconstruct(eorb_ctx* ctx, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2,
+        const int32_t* match12, int N, const int32_t* sets, int iters, const float* K, const eorb_tvr_recon_params* p,
+        eorb_tvr_recon_result* res, float* R21 /*[2][9]*/, float* t21 /*[2][3]*/, float* p3d /*[2][n1][3]*/,
+        uint8_t* triangulated /*[2][n1]*/, uint8_t* trans_inliers /*[N]*/, eorb_tvr_pose* hyp_poses /*[8], test aid, NULL to skip*/);
 
 /* ---- Sim3Solver (src/Sim3Solver.cc): Horn's closed form and its RANSAC loop ------------------------------------------------------------
  * The stage between SearchByBoW(KF, KF) and SearchByProjection(KF, Scw) in LoopClosing::DetectCommonRegionsFromBoW
