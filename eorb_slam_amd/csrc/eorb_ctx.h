@@ -214,6 +214,7 @@ struct eorb_ctx {
     int dbg_slot_prerank = -1;                   // slot form: ranks kept by the count pass, sl_scatter_pre_kernel (-1: default / EORB_SLOT_PRERANK, 0 / 1: test hook)
     int dbg_pd = 1;                              // float events in bulk: 0 = never freeze / use the position dictionary (test hook "position_dict")
     int dbg_slot_halves = -1;                    // slot form: -1 by the batch's shape / EORB_SLOT_HALVES, 0 one part, 1 two halves whatever the shape
+    int dbg_dirty_fill = -1;                     // "dirty_fill": -1 off; 0..255 the byte that new allocations (ensure), the call arena and its staging slot (Arena::upload) and the landing buffer (download_begin) are filled with before use
 };
 
 namespace eorb {

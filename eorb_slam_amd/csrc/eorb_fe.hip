@@ -39,6 +39,10 @@ int ensure(eorb_ctx* c, DevBuf& b, size_t bytes)
     hipError_t e = hipMalloc(&b.p, want);
     if (e != hipSuccess) { b.p = nullptr; return hip_check(c, e, "hipMalloc"); }
     b.cap = want;
+    // test hook "dirty_fill": the allocation starts out as the byte, whole, before anyone (on any stream) can use it
+    if (c && c->dbg_dirty_fill >= 0) {
+        if ((e = hipMemset(b.p, c->dbg_dirty_fill, want)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) return hip_check(c, e, "hipMemset (dirty_fill)");
+    }
     return EORB_OK;
 }
 
@@ -177,9 +181,12 @@ struct Arena {
         int rc = ensure(c, c->arena, total);
         if (rc) return rc;
         c->arena_gen++;                              // (whatever an earlier call left in the arena is gone)
+        const int dirty = c->dbg_dirty_fill;         // test hook "dirty_fill": the whole arena and the staging slot hold the byte before any input goes in
+        if (dirty >= 0) EORB_HIP(c, hipMemsetAsync(c->arena.p, dirty, c->arena.cap, c->stream));
         if (!in_end) return EORB_OK;
         char* hp = (char*)pinned(c, in_end);
         if (!hp) return set_err(c, EORB_E_HIP, "pinned alloc failed");
+        if (dirty >= 0) memset(hp, dirty, in_end);
         static const long kmax = [] { const char* e = getenv("EORB_UPLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }();      // (bytes; 0: always the copy engine)
         // the copy engine takes the staging buffer in pieces of kPiece as it fills: tens of MB are copied in while the host packs the rest;
         // an array of kPiece or more goes straight from the caller's buffer (the runtime copies pageable memory of that size in place,
@@ -232,6 +239,7 @@ struct Arena {
     {
         int rc = landing(bytes);
         if (rc) return rc;
+        if (c->dbg_dirty_fill >= 0) memset(c->dl_pinned, c->dbg_dirty_fill, c->dl_cap);      // (test hook: a host read outside the downloaded range sees the byte)
         // (the way back like the way in: up to a few hundred KB a kernel writes the pinned buffer; offsets of the arena are multiples of
         // 256 and both buffers longer than the rounded size)
         if ((long)bytes <= download_kmax() && !(off & 15)) {
@@ -395,6 +403,10 @@ int eorb_debug_option(eorb_ctx* c, const char* name, int value)
     if (!strcmp(name, "slot_prerank")) { c->dbg_slot_prerank = value; return EORB_OK; }
     if (!strcmp(name, "kfdb_initial_slots")) { c->kfdb.dbg_initial_slots = value; return EORB_OK; }
     if (!strcmp(name, "kfdb_finish_lds_entries")) { c->kfdb.dbg_finish_lds = value; return EORB_OK; }
+    if (!strcmp(name, "dirty_fill")) {
+        if (value < -1 || value > 255) return set_err(c, EORB_E_ARG, "dirty_fill: -1 (off) or a byte 0..255, not %d", value);
+        c->dbg_dirty_fill = value; return EORB_OK;
+    }
     return set_err(c, EORB_E_ARG, "debug option '%s' unknown", name);
 }
 
@@ -429,6 +441,14 @@ long long eorb_debug_counter(eorb_ctx* c, const char* name)
             n += h;
         }
         return n;
+    }
+    if (!strcmp(name, "win_total_nonzero")) {           // window matchers: pairs whose entry counter is not back at zero (synchronises)
+        const size_t n = c->win_total.p ? c->win_total.cap / sizeof(uint32_t) : 0;
+        if (!n) return 0;
+        std::vector<uint32_t> t(n);
+        if (hipMemcpyAsync(t.data(), c->win_total.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+        long long nz = 0; for (uint32_t v : t) nz += v != 0;
+        return nz;
     }
     if (!strcmp(name, "oct_lds_only")) return c->orb.oct_all_lds[0] | (c->orb.oct_all_lds[1] << 1);      // octree working set entirely in LDS: single frames | batches
     if (!strcmp(name, "oct_lds_bytes")) return c->orb.oct_lds[0];

@@ -1752,7 +1752,7 @@ class EvImBuilder:
 
     def __init__(self, W=240, H=180, l1ChunkSize=2000, l1NumLoop=3, l1FixedWinSz=False, continTracking=True, maxPixelDisp=3.0,
                  l1WinOverlap=0.5, minEvGenRate=1.0, l1ImSigma=1.0, maxNumPts=400, fastTh=0, imMargin=9, klt=(23, 1, 10, 0.03),
-                 cam=None, raw_events=False, keep_images=True):
+                 cam=None, raw_events=False, keep_images=True, ctx=None, ctx_l2=None):
         self.W, self.H, self.sigma = W, H, float(l1ImSigma)
         self.mbContTracking, self.mbFixedWinSize = bool(continTracking), bool(l1FixedWinSz)
         self.mL1EvWinSize = self.mInitL1EvWinSize = int(l1ChunkSize)
@@ -1761,7 +1761,9 @@ class EvImBuilder:
         self.cam, self.raw, self.keep_images = cam, bool(raw_events), keep_images
         # the L1 builder's own extractor (FAST = ORB with one level, :49-54 + EvBaseTracker.cpp:150-164) and the L2 tracker's
         # (2 x maxNumPts, src/Event/EvAsynchTracker.cpp:51,59-62), one context each as the reference has one extractor object each
-        self.ctx = Context(); self.ctx_l2 = Context()
+        # (ctx / ctx_l2: contexts of the caller's, which close() then leaves open)
+        self._own = (ctx is None, ctx_l2 is None)
+        self.ctx = ctx or Context(); self.ctx_l2 = ctx_l2 or Context()
         self.l1 = ORBextractor(maxNumPts, 1.0, 1, fastTh, 0, imMargin, imSize=(W, H), ctx=self.ctx)
         self.l2 = ORBextractor(2 * maxNumPts, 1.0, 1, fastTh, 0, imMargin, imSize=(W, H), ctx=self.ctx_l2)
         self.klt = _lib.KltParams(int(klt[0]), int(klt[1]), int(klt[2]), float(klt[3]), 1e-4)
@@ -1769,7 +1771,8 @@ class EvImBuilder:
         self.reset()
 
     def close(self):
-        self.ctx.close(); self.ctx_l2.close()
+        if self._own[0]: self.ctx.close()
+        if self._own[1]: self.ctx_l2.close()
 
     def set_undistort_maps(self, mapX, mapY, checkInImage=True):
         EvImConverter.set_undistort_maps(mapX, mapY, checkInImage, ctx=self.ctx)

@@ -117,7 +117,10 @@ int         eorb_sync(eorb_ctx* ctx);
  * number of events per call from which their distinct positions are tabulated, default 2^20), "kfdb_initial_slots" (KeyFrameDatabase:
  * the capacity in slots, and 64 pool words per slot, that the first eorb_kfdb_add allocates, to cross a pool growth with a handful of adds),
  * "kfdb_finish_lds_entries" (KeyFrameDatabase queries: scored keyframes up to which the last kernel sorts in LDS, 0 = as many as fit (4096),
- * to force its sort in global memory) */
+ * to force its sort in global memory), "dirty_fill" (-1, the default: off; 0 .. 255: every device allocation of the context is filled with
+ * that byte when it is made, the call arena is filled whole in front of every host-buffer call, and so are the pinned staging slot the
+ * call's inputs are packed into and the pinned buffer its results land in -- what a call reads without having written it is then that
+ * byte and not the zero of fresh memory or the previous call's values; tests/test_gpu_dirty.py) */
 int         eorb_debug_option(eorb_ctx* ctx, const char* name, int value);
 /* test hook: counters a test can read to see which path served its calls.  "slot_calls": accumulation calls that took the slot
  * lists (gather_form 0 on dense batches, or 4); "slot_flags": sticky device flags of that path (0 = fine; synchronises); "slot_hot_items": lists the last such call handed to
@@ -128,7 +131,8 @@ int         eorb_debug_option(eorb_ctx* ctx, const char* name, int value);
  * | 32 if short records (eorb_raw_event4 / eorb_raw_event2) were widened first; "slot_scatter_form" (1 rank or pre-ranked scatter, 0 ballot),
  * "slot_chunk" (events per binning chunk) and "slot_binning" of the last call that took the slot lists (-1: none yet) = count pass (0 global
  * counters, 1 tile ranges in LDS, 2 the same with the position dictionary's lookup) | record the scatter reads << 2 (0 the events as they
- * are, 1 2-byte sensor indices, 2 8-byte ranked records) | scatter << 4 (0 ballot, 1 rank, 2 pre-ranked).
+ * are, 1 2-byte sensor indices, 2 8-byte ranked records) | scatter << 4 (0 ballot, 1 rank, 2 pre-ranked); "win_total_nonzero": pairs of the
+ * window matchers whose entry counter is not back at zero after the last call (0 = fine; synchronises).
  * Returns the value, or -1 for an unknown name. */
 long long   eorb_debug_counter(eorb_ctx* ctx, const char* name);
 /* test hook, not part of the reference's interface: the intermediate images of the extractor, for stage-by-stage comparison with
