@@ -246,8 +246,7 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
 int ev_direct_slices_dev(eorb_ctx* c, const AccumShape& S, const void* d_events, int raw, const int64_t* beg, const int64_t* end, int B, int W, int H,
                          float sigma, int pol, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, bool mm_preset = false);
 int ev_undistort_dev(eorb_ctx* c, const eorb_raw_event* d_raw, size_t n, int W, int H, double tsFactor, eorb_event* d_out, uint32_t* d_blk);
-int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, uint64_t* d_lineend, eorb_raw_event* d_ev, uint8_t* d_status,
-                      eorb_raw_event* d_out, uint32_t* d_blk, size_t max_lines, uint32_t h_res[3]);
+int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, eorb_raw_event* d_out, size_t max_out, uint32_t h_res[3]);
 int ev_decode_minmax(eorb_ctx* c, const uint32_t* d_enc, float* d_out, int B);
 int ev_divcheck(eorb_ctx* c, float lo, float hi, float sigma, unsigned long long* bad_out);
 int ev_diag_read(unsigned long long* out16);

@@ -767,27 +767,22 @@ int eorb_parse_events_text(eorb_ctx* c, const char* text, size_t nbytes, eorb_ra
     fe_enter(c);
     *n_out = 0; if (bad_line) *bad_line = -1;
     if (!nbytes) return EORB_OK;
-    // every line of the accepted grammar is at least 8 bytes ("0 0 0 0\n"); shorter ones are comments / blanks or errors, so
-    // the line capacity is bounded by the caller's event capacity plus what the text could hold otherwise
-    const size_t max_lines = nbytes / 2 + 2;
+    // an event line takes at least 7 bytes (four tokens of one digit each and a byte between two of them: "0 0 0 0") and,
+    // but for the last line of the buffer, its '\n': at most (nbytes + 1) / 8 events.  Lines may be as many as bytes (blank ones); the
+    // workspaces per line are sized from the counted lines (ev_parse_text_dev)
+    const size_t max_events = (nbytes + 1) / 8;
     int rc;
-    const size_t nblk = (nbytes + 1023) / 1024;
     Arena A(c);
-    const size_t o_text = A.in(text, nbytes), o_out = A.reserve(sizeof(eorb_raw_event) * max_lines);
+    const size_t o_text = A.in(text, nbytes), o_out = A.reserve(sizeof(eorb_raw_event) * max_events);
     if ((rc = A.upload())) return rc;
-    // workspaces: lineend u64 | parsed events | status | block sums
-    if ((rc = ensure(c, c->entries, sizeof(uint64_t) * max_lines))) return rc;
-    if ((rc = ensure(c, c->ev16, sizeof(eorb_raw_event) * max_lines))) return rc;
-    if ((rc = ensure(c, c->segoff, max_lines + 64))) return rc;
-    if ((rc = ensure(c, c->tile_order, sizeof(uint32_t) * (std::max(nblk, (max_lines + 1023) / 1024) + 8)))) return rc;
     uint32_t res[3];
-    if ((rc = ev_parse_text_dev(c, A.dev<char>(o_text), nbytes, (uint64_t*)c->entries.p, (eorb_raw_event*)c->ev16.p,
-                                (uint8_t*)c->segoff.p, A.dev<eorb_raw_event>(o_out), (uint32_t*)c->tile_order.p, max_lines, res))) return rc;
+    if ((rc = ev_parse_text_dev(c, A.dev<char>(o_text), nbytes, A.dev<eorb_raw_event>(o_out), max_events, res))) return rc;
     pinned_release_lazy(c);                              // (ev_parse_text_dev has waited for the stream)
     if (res[2] != 0xffffffffu) {
         if (bad_line) *bad_line = (int64_t)res[2];
         return set_err(c, EORB_E_ARG, "parse_events_text: line %u is outside the accepted \"ts x y p\" grammar", res[2]);
     }
+    if (res[1] > max_events) return set_err(c, EORB_E_HIP, "parse_events_text: %u events counted in %zu bytes", res[1], nbytes);
     if (res[1] > cap) return set_err(c, EORB_E_CAPACITY, "parse_events_text: %u events, room for %zu", res[1], cap);
     if (res[1] && (rc = A.download_to(out, o_out, sizeof(eorb_raw_event) * (size_t)res[1]))) return rc;
     *n_out = res[1];

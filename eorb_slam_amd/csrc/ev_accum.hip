@@ -1779,12 +1779,13 @@ __global__ __launch_bounds__(1024) void txt_lineend_kernel(const char* __restric
     if (e) lineend[blk[blockIdx.x] + wbase[wave] + (uint32_t)__popcll(m & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))))] = i;
 }
 
-// one decimal token: digits [ '.' digits ].  Returns false when malformed.  mant = the digits without leading zeros (up to 19
-// significant), frac = number of digits after the point, big = more than 19 significant digits.
-__device__ __forceinline__ bool txt_number(const char* t, size_t& p, size_t end, uint64_t& mant, int& frac, bool& big)
+// one number token of the grammar (include/eorb_fe.h): \d+\.?\d* or \.\d+, taken greedily.  Returns false when there is no digit.
+// mant = the digits without leading zeros (up to 19 significant), frac = number of digits after the point, point = the token has
+// one, big = more than 19 significant digits.
+__device__ __forceinline__ bool txt_number(const char* t, size_t& p, size_t end, uint64_t& mant, int& frac, bool& point, bool& big)
 {
-    mant = 0; frac = 0; big = false;
-    int nd = 0, sig = 0; bool point = false;
+    mant = 0; frac = 0; big = false; point = false;
+    int nd = 0, sig = 0;
     while (p < end) {
         const char ch = t[p];
         if (ch >= '0' && ch <= '9') {
@@ -1812,19 +1813,19 @@ __global__ void txt_parse_kernel(const char* __restrict__ t, size_t nbytes, cons
     eorb_raw_event e{};
     if (p < end && t[p] != '#') {
         st = 2;
-        uint64_t m[4]; int fr[4]; bool big[4]; bool ok = true;
-        for (int k = 0; k < 4 && ok; k++) { ok = txt_number(t, p, end, m[k], fr[k], big[k]); txt_blanks(t, p, end); }
+        uint64_t m[4]; int fr[4]; bool pt[4], big[4]; bool ok = true;
+        for (int k = 0; k < 4 && ok; k++) { ok = txt_number(t, p, end, m[k], fr[k], pt[k], big[k]); txt_blanks(t, p, end); }
         ok = ok && p == end;
         // ts: Clinger's exact case -- integer mantissa < 2^53 and 10^frac exact in double: one correctly rounded division
         if (ok && (big[0] || m[0] >= (1ull << 53) || fr[0] > 22)) ok = false;
-        // x, y: integer-valued, 0..65535;  p: 0 or 1
+        // x, y: integer-valued, 0..65535;  p: 0 or 1 without a point
         for (int k = 1; k <= 2 && ok; k++) {
             uint64_t v = m[k];
             for (int d = 0; d < fr[k] && ok; d++) { if (v % 10) ok = false; v /= 10; }
             if (ok && (big[k] || v > 65535)) ok = false;
             m[k] = v;
         }
-        if (ok && (big[3] || fr[3] != 0 || m[3] > 1)) ok = false;
+        if (ok && (big[3] || pt[3] || m[3] > 1)) ok = false;
         if (ok) {
             double p10 = 1.0;
             for (int d = 0; d < fr[0]; d++) p10 *= 10.0;          // exact up to 1e22
@@ -1851,7 +1852,8 @@ __global__ __launch_bounds__(1024) void txt_keep_count_kernel(const uint8_t* __r
     if (threadIdx.x == 0) blk[blockIdx.x] = cnt;
 }
 __global__ __launch_bounds__(1024) void txt_keep_write_kernel(const uint8_t* __restrict__ status, const eorb_raw_event* __restrict__ ev,
-                                                              uint32_t nlines, const uint32_t* __restrict__ blk, eorb_raw_event* __restrict__ out)
+                                                              uint32_t nlines, const uint32_t* __restrict__ blk, eorb_raw_event* __restrict__ out,
+                                                              uint32_t max_out)
 {
     __shared__ uint32_t wbase[17];
     const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
@@ -1862,16 +1864,22 @@ __global__ __launch_bounds__(1024) void txt_keep_write_kernel(const uint8_t* __r
     __syncthreads();
     if (threadIdx.x == 0) { wbase[0] = 0; for (int w = 1; w <= 16; w++) wbase[w] += wbase[w - 1]; }
     __syncthreads();
-    if (keep) out[blk[blockIdx.x] + wbase[wave] + (uint32_t)__popcll(m & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))))] = ev[i];
+    if (keep) {
+        const uint32_t pos = blk[blockIdx.x] + wbase[wave] + (uint32_t)__popcll(m & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
+        if (pos < max_out) out[pos] = ev[i];                      // (max_out is the grammar's bound; the host checks the count against it)
+    }
 }
 __global__ void txt_set_u32_kernel(uint32_t* p, uint32_t v) { *p = v; }
 
-// d_text: nbytes of text; d_lineend / d_ev / d_status / d_out sized for max_lines; d_blk: (nbytes + 1023) / 1024 + 4 words.
+// d_text: nbytes of text; d_out: room for max_out events.  The line workspaces (line ends u64 | parsed events | status) are sized from
+// the counted lines, which the call waits for anyway; the block sums need (nbytes + 1023) / 1024 + 8 words, and lines <= nbytes.
 // h_res[0] = lines, h_res[1] = events kept, h_res[2] = first malformed line (0xffffffff = none)
-int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, uint64_t* d_lineend, eorb_raw_event* d_ev, uint8_t* d_status,
-                      eorb_raw_event* d_out, uint32_t* d_blk, size_t max_lines, uint32_t h_res[3])
+int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, eorb_raw_event* d_out, size_t max_out, uint32_t h_res[3])
 {
     const int nblk = (int)((nbytes + 1023) / 1024);
+    int rc;
+    if ((rc = ensure(c, c->tile_order, sizeof(uint32_t) * ((size_t)nblk + 8)))) return rc;
+    uint32_t* d_blk = (uint32_t*)c->tile_order.p;
     ProfScope ps(c, "ev_parse_text");
     txt_count_kernel<<<nblk, 1024, 0, c->stream>>>(d_text, nbytes, d_blk);
     ev_undistort_scan_kernel<<<1, 1, 0, c->stream>>>(d_blk, nblk);
@@ -1880,7 +1888,11 @@ int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, uint64_t* 
     EORB_HIP(c, hipStreamSynchronize(c->stream));
     h_res[0] = nlines; h_res[1] = 0; h_res[2] = 0xffffffffu;
     if (nlines == 0) return EORB_OK;
-    if (nlines > max_lines) return set_err(c, EORB_E_CAPACITY, "parse_events_text: %u lines, room for %zu", nlines, max_lines);
+    if (nlines > nbytes) return set_err(c, EORB_E_HIP, "parse_events_text: %u lines counted in %zu bytes", nlines, nbytes);
+    if ((rc = ensure(c, c->entries, sizeof(uint64_t) * (size_t)nlines))) return rc;
+    if ((rc = ensure(c, c->ev16, sizeof(eorb_raw_event) * (size_t)nlines))) return rc;
+    if ((rc = ensure(c, c->segoff, (size_t)nlines + 64))) return rc;
+    uint64_t* d_lineend = (uint64_t*)c->entries.p; eorb_raw_event* d_ev = (eorb_raw_event*)c->ev16.p; uint8_t* d_status = (uint8_t*)c->segoff.p;
     txt_lineend_kernel<<<nblk, 1024, 0, c->stream>>>(d_text, nbytes, d_blk, d_lineend);
     txt_parse_kernel<<<(nlines + 255) / 256, 256, 0, c->stream>>>(d_text, nbytes, d_lineend, nlines, d_ev, d_status);
     const int nb2 = (int)((nlines + 1023) / 1024);
@@ -1889,7 +1901,7 @@ int ev_parse_text_dev(eorb_ctx* c, const char* d_text, size_t nbytes, uint64_t* 
     txt_set_u32_kernel<<<1, 1, 0, c->stream>>>(d_bad, 0xffffffffu);
     txt_keep_count_kernel<<<nb2, 1024, 0, c->stream>>>(d_status, nlines, d_blk2, d_bad);
     ev_undistort_scan_kernel<<<1, 1, 0, c->stream>>>(d_blk2, nb2);
-    txt_keep_write_kernel<<<nb2, 1024, 0, c->stream>>>(d_status, d_ev, nlines, d_blk2, d_out);
+    txt_keep_write_kernel<<<nb2, 1024, 0, c->stream>>>(d_status, d_ev, nlines, d_blk2, d_out, (uint32_t)max_out);
     EORB_LAUNCH_CHECK(c, "ev_parse_text kernels");
     uint32_t two[2] = {0, 0};
     EORB_HIP(c, hipMemcpyAsync(&two[0], d_blk2 + nb2, 4, hipMemcpyDeviceToHost, c->stream));

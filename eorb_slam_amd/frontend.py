@@ -20,9 +20,10 @@ EV16_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("t", "<f8")])
 
 
 class EorbError(RuntimeError):
-    def __init__(self, code, msg):
+    def __init__(self, code, msg, bad_line=None):
         super().__init__("eorb_fe error %d: %s" % (code, msg))
         self.code = code
+        self.bad_line = bad_line                # parse_events_text: the 0-based index of the first malformed line
 
 
 def _p(a):
@@ -188,11 +189,14 @@ class EvImConverter:
 
     @staticmethod
     def parse_events_text(text, ctx=None):
-        """The text half of the loader (EventLoader.cpp:80-92): bytes of "ts x y p" lines -> RAW_DTYPE events."""
+        """The text half of the loader (EventLoader.cpp:80-92): bytes of "ts x y p" lines -> RAW_DTYPE events.  A line outside the
+        grammar of include/eorb_fe.h raises EorbError with .bad_line = the 0-based index of the first such line."""
         ctx = ctx or default_context()
         cap = text.count(b"\n") + 1
         out = np.zeros(cap, RAW_DTYPE); k = C.c_size_t(0); bad = C.c_int64(-1)
-        ctx.check(ctx.L.eorb_parse_events_text(ctx.h, text, len(text), _p(out), cap, C.byref(k), C.byref(bad)))
+        rc = ctx.L.eorb_parse_events_text(ctx.h, text, len(text), _p(out), cap, C.byref(k), C.byref(bad))
+        if rc != 0:
+            raise EorbError(rc, ctx.L.eorb_last_error(ctx.h).decode(), bad.value if bad.value >= 0 else None)
         return out[:k.value].copy()
 
     @staticmethod

@@ -186,11 +186,23 @@ int eorb_undistort_events(eorb_ctx* ctx, const eorb_raw_event* raw, size_t n, in
 
 /* replaces the text half of the loader: getline + EventDataStore::parseLine ("stream >> ts >> x >> y >> p",
  * src/Event/EventLoader.cpp:80-92) + BaseLoader::isComment (Utils/DataStore.cpp:111-114) over a whole buffer of the dataset's
- * events.txt.  Accepted grammar per line: `ts x y p` as plain decimals (no exponent) separated by blanks / tabs, optional '\r';
- * ts with at most 19 significant digits, value < 2^53 / 10^frac and at most 22 fractional digits (then one IEEE division gives
- * strtod's result); x, y integer-valued in 0..65535 (the reference truncates them, MyCalibrator.cpp:172-173); p in {0, 1}.
- * '#' lines and blank lines are skipped.  Any other line: EORB_E_ARG with *bad_line = its 0-based index (the caller falls back
- * to its own parser for that file).  out has room for cap events. */
+ * events.txt.  The accepted grammar (the kernel, the oracle and tests/loader_model.py follow this text):
+ *   lines     a line ends at '\n', or at the last byte of a buffer that does not end in '\n'; one trailing '\r' is dropped.  There is
+ *             no limit on a line's length.
+ *   skipped   a line that, after its leading blanks (' ' and '\t'), is empty or starts with '#', whatever bytes follow.
+ *   tokens    a number token is \d+\.?\d* or \.\d+ : no sign, no exponent, no other byte.  Tokens are taken greedily; blanks and tabs
+ *             between them are optional separators, as "stream >> ts >> x >> y >> p" reads them: `1.0.0 3 1` is (1.0, 0, 3, 1).  An
+ *             event line holds exactly four tokens, and only blanks may follow the fourth.
+ *   digits    a token of more than 19 significant digits is outside the grammar; significant digits count from the first non-zero
+ *             digit on, zeros of the fraction included (`1.0000000000000000000` has 20).  This holds for all four tokens.
+ *   ts        mantissa (the digits read as one integer) below 2^53 and at most 22 fraction digits: the value is the double nearest
+ *             to mantissa / 10^frac (one IEEE division of two exact doubles gives it, and so does a correct strtod).
+ *   x, y      every fraction digit is 0 and the value lies in 0..65535 (the reference truncates them, MyCalibrator.cpp:172-173).
+ *   p         no point, value 0 or 1 (`01` is 1; `1.` and `0.` are malformed).
+ * Any other line is malformed: EORB_E_ARG with *bad_line = the smallest 0-based index of a malformed line, comment and blank lines
+ * counted (the caller falls back to its own parser for that file); *n_out = 0 and out is not written.  This takes precedence over
+ * EORB_E_CAPACITY, which is returned when the text holds more than cap events (*n_out = 0, out not written, *bad_line = -1).
+ * out has room for cap events; bad_line may be NULL. */
 int eorb_parse_events_text(eorb_ctx* ctx, const char* text, size_t nbytes, eorb_raw_event* out, size_t cap, size_t* n_out,
                            int64_t* bad_line);
 

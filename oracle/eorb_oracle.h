@@ -109,9 +109,11 @@ size_t orc_undistort_events(const orc_raw_event* raw, size_t n, const float* map
 
 /* Text half of EventDataStore::getEventChunkRectified / getTxtData (src/Event/EventLoader.cpp:80-92, :264-305): one event per
  * line "ts x y p"; lines whose first non-blank character is '#' are comments (BaseLoader::isComment, Utils/DataStore.cpp:111-114).
- * ts: strtod (istringstream >> double); x, y: strtof then static_cast<int> (MyCalibrator.cpp:172-173); p: 0 / 1.
- * Accepted grammar (anything else -> returns -(line number) - 1, 0-based): decimal numbers without exponent, separated by
- * blanks / tabs, optional trailing '\r'; x and y integer-valued, 0..65535.  Blank lines are skipped.  Returns the number of events. */
+ * ts: strtod (istringstream >> double); x, y: integer-valued by their digits (the reference truncates, MyCalibrator.cpp:172-173);
+ * p: strtol, 0 / 1.  The accepted grammar is the one include/eorb_fe.h states for eorb_parse_events_text; no limit on a line's length.
+ * Returns the number of events; -(line number) - 1, 0-based, for the first line outside the grammar; ORC_PARSE_CAPACITY when every line
+ * is inside it and there are more than cap events. */
+#define ORC_PARSE_CAPACITY (-9223372036854775807L - 1)
 long orc_parse_events_text(const char* text, size_t nbytes, orc_raw_event* out, size_t cap);
 
 typedef struct { float fx, fy, cx, cy; } orc_pinhole;          /* Pinhole::mvParameters (float), CameraModels/Pinhole.cpp */

@@ -687,13 +687,17 @@ def bow_transform(voc, desc, levelsup=4, weighting=0, norm=1):
     return bw[:nw.value].copy(), bv[:nw.value].copy(), (fn[:nn.value].copy(), fo[:nn.value + 1].copy(), fi[:fo[nn.value]].copy()), wo[:n], no[:n]
 
 
-def parse_events_text(text):
-    """text: bytes. Returns RAW_DTYPE events, or raises ValueError(line) for a line outside the accepted grammar."""
+def parse_events_text(text, cap=None):
+    """text: bytes. Returns RAW_DTYPE events, or raises ValueError(line) for the first line outside the accepted grammar; with a cap
+    smaller than the number of events of a well-formed text, OverflowError."""
     L = lib(); L.orc_parse_events_text.restype = C.c_long
     L.orc_parse_events_text.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
-    cap = text.count(b"\n") + 1
-    out = np.zeros(cap, RAW_DTYPE)
+    if cap is None:
+        cap = text.count(b"\n") + 1
+    out = np.zeros(max(cap, 1), RAW_DTYPE)
     r = L.orc_parse_events_text(text, len(text), _p(out), cap)
+    if r == -2 ** 63:
+        raise OverflowError("more than %d events" % cap)
     if r < 0:
         raise ValueError(-r - 1)
     return out[:r].copy()

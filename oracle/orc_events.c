@@ -346,48 +346,78 @@ size_t orc_undistort_events(const orc_raw_event* raw, size_t n, const float* map
     return k;
 }
 
-/* EventLoader.cpp:80-92 "stream >> ts >> x >> y >> p" over the lines of a text buffer */
+/* EventLoader.cpp:80-92 "stream >> ts >> x >> y >> p" over the lines of a text buffer, by the grammar of include/eorb_fe.h
+ * (eorb_parse_events_text).  The tokens are cut by hand; ts then goes through strtod and p through strtol, each of which has to end where
+ * the token ends.  Returns the number of events, -(line + 1) for the first malformed line, or ORC_PARSE_CAPACITY when the text is well
+ * formed and holds more than cap events (a malformed line anywhere takes precedence). */
+typedef struct { size_t beg, end; int sig, frac, point; unsigned long long mant; } orc_tok;
+static int parse_token(const char* t, size_t* p, size_t end, orc_tok* k)
+{
+    int nd = 0;
+    k->beg = *p; k->sig = 0; k->frac = 0; k->point = 0; k->mant = 0;
+    for (; *p < end; (*p)++) {
+        const char ch = t[*p];
+        if (ch >= '0' && ch <= '9') {
+            if (k->sig > 0 || ch != '0') { if (k->sig < 19) k->mant = k->mant * 10 + (unsigned)(ch - '0'); k->sig++; }
+            nd++; if (k->point) k->frac++;
+        } else if (ch == '.' && !k->point) k->point = 1;
+        else break;
+    }
+    k->end = *p;
+    return nd > 0 && k->sig <= 19;                                         /* at least one digit, at most 19 significant */
+}
+/* every fraction digit 0, value 0..65535 */
+static int token_coord(const orc_tok* k, unsigned* v)
+{
+    unsigned long long m = k->mant;
+    for (int d = 0; d < k->frac; d++) { if (m % 10) return 0; m /= 10; }
+    if (m > 65535) return 0;
+    *v = (unsigned)m;
+    return 1;
+}
 long orc_parse_events_text(const char* text, size_t nbytes, orc_raw_event* out, size_t cap)
 {
-    size_t pos = 0; long line = 0; size_t n = 0;
-    char buf[256];
+    size_t pos = 0; long line = 0; size_t n = 0; int over = 0;
+    char small[64]; char* num = small; size_t num_cap = sizeof(small);
+    long ret = 0;
     while (pos < nbytes) {
         size_t end = pos;
         while (end < nbytes && text[end] != '\n') end++;
-        size_t len = end - pos;
-        if (len > 0 && text[pos + len - 1] == '\r') len--;
-        size_t i = 0;
-        while (i < len && (text[pos + i] == ' ' || text[pos + i] == '\t')) i++;
-        if (i < len && text[pos + i] != '#') {                           /* isComment / blank */
-            if (len >= sizeof(buf)) return -line - 1;
-            memcpy(buf, text + pos, len); buf[len] = 0;
-            for (size_t k = 0; k < len; k++) {                            /* grammar: digits, '.', blanks only */
-                const char ch = buf[k];
-                if (!((ch >= '0' && ch <= '9') || ch == '.' || ch == ' ' || ch == '\t')) return -line - 1;
+        size_t stop = end;
+        if (stop > pos && text[stop - 1] == '\r') stop--;
+        size_t i = pos;
+        while (i < stop && (text[i] == ' ' || text[i] == '\t')) i++;
+        if (i < stop && text[i] != '#') {                                 /* isComment / blank */
+            orc_tok k[4]; int ok = 1;
+            for (int j = 0; j < 4 && ok; j++) {
+                ok = parse_token(text, &i, stop, &k[j]);
+                while (i < stop && (text[i] == ' ' || text[i] == '\t')) i++;
             }
-            char* q = buf; char* e;
-            {   /* ts restricted to the exactly convertible case: <= 19 significant digits, mantissa < 2^53, <= 22 fraction digits */
-                const char* d = buf + i; unsigned long long mant = 0; int sig = 0, frac = 0, point = 0, big = 0;
-                for (; (*d >= '0' && *d <= '9') || (*d == '.' && !point); d++) {
-                    if (*d == '.') { point = 1; continue; }
-                    if (mant != 0 || *d != '0') { if (sig < 19) { mant = mant * 10 + (unsigned)(*d - '0'); sig++; } else big = 1; }
-                    if (point) frac++;
-                }
-                if (big || mant >= (1ull << 53) || frac > 22) return -line - 1;
+            unsigned x = 0, y = 0; double ts = 0; long pp = 0;
+            ok = ok && i == stop;
+            ok = ok && k[0].mant < (1ull << 53) && k[0].frac <= 22;
+            ok = ok && token_coord(&k[1], &x) && token_coord(&k[2], &y);
+            ok = ok && !k[3].point;
+            if (ok) {
+                const size_t l0 = k[0].end - k[0].beg, l3 = k[3].end - k[3].beg, need = (l0 > l3 ? l0 : l3) + 1;
+                if (need > num_cap) { if (num != small) free(num); num = (char*)malloc(need); num_cap = need; }
+                char* e;
+                memcpy(num, text + k[0].beg, l0); num[l0] = 0;
+                ts = strtod(num, &e); ok = e == num + l0;
+                memcpy(num, text + k[3].beg, l3); num[l3] = 0;
+                pp = strtol(num, &e, 10); ok = ok && e == num + l3 && (pp == 0 || pp == 1);
             }
-            const double ts = strtod(q, &e); if (e == q) return -line - 1; q = e;
-            const float x = strtof(q, &e); if (e == q) return -line - 1; q = e;
-            const float y = strtof(q, &e); if (e == q) return -line - 1; q = e;
-            const long pp = strtol(q, &e, 10); if (e == q) return -line - 1; q = e;
-            while (*q == ' ' || *q == '\t') q++;
-            if (*q != 0 || (pp != 0 && pp != 1)) return -line - 1;
-            if (x != (float)(int)x || y != (float)(int)y || x < 0 || x > 65535 || y < 0 || y > 65535) return -line - 1;
-            if (n >= cap) return -line - 1;
-            memset(&out[n], 0, sizeof(orc_raw_event));
-            out[n].x = (uint16_t)(int)x; out[n].y = (uint16_t)(int)y; out[n].p = (uint32_t)pp; out[n].t = ts;
+            if (!ok) { ret = -line - 1; goto done; }
+            if (n < cap) {
+                memset(&out[n], 0, sizeof(orc_raw_event));
+                out[n].x = (uint16_t)x; out[n].y = (uint16_t)y; out[n].p = (uint32_t)pp; out[n].t = ts;
+            } else over = 1;
             n++;
         }
         pos = end + 1; line++;
     }
-    return (long)n;
+    ret = over ? ORC_PARSE_CAPACITY : (long)n;
+done:
+    if (num != small) free(num);
+    return ret;
 }
