@@ -173,6 +173,8 @@ struct eorb_ctx {
     eorb::DevBuf arena;                  // host-buffer entry points: all inputs / outputs of one call, one H2D and one D2H copy
     void* dl_pinned = nullptr; size_t dl_cap = 0;      // pinned landing buffer of the D2H copy (the call synchronises before reading it)
     hipEvent_t dl_event = nullptr;                     // recorded behind that copy: what the call waits for
+    // cumulative over the context's life (eorb_debug_counter "arena_*"): calls, their arena and input bytes; downloads, their bytes and first offsets
+    long long arena_calls = 0, arena_bytes = 0, arena_in_bytes = 0, arena_downloads = 0, arena_download_bytes = 0, arena_download_first = 0;
     // pyramidal LK workspaces; klt_ref_key: the reference frame whose pyramid and derivatives the buffers hold (0 = none)
     eorb::DevBuf klt_pyr, klt_der, klt_scratch;
     unsigned long long klt_ref_key = 0, klt_ref_geo = 0, klt_ref_serial = 0;

@@ -152,7 +152,7 @@ struct Arena {
     std::vector<Part> parts;
     explicit Arena(eorb_ctx* cc) : c(cc) {}
     size_t take(size_t bytes) { const size_t o = total; total = (total + std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return o; }
-    // inputs first (they form the prefix that is uploaded), then reserve() for device-only / output regions
+    // inputs first (they form the prefix that is uploaded), then out() for the outputs (below) and reserve() for device-only regions
     size_t in(const void* h, size_t bytes) { const size_t o = take(bytes); if (h && bytes) parts.push_back({h, o, bytes, 0, 0, 0}); in_end = total; return o; }
     // float events, packed to the 16-byte record (eorb_pack_events) straight into the staging buffer
     size_t in_events(const eorb_event* ev, size_t n)
@@ -181,6 +181,7 @@ struct Arena {
         int rc = ensure(c, c->arena, total);
         if (rc) return rc;
         c->arena_gen++;                              // (whatever an earlier call left in the arena is gone)
+        c->arena_calls++; c->arena_bytes += (long long)total; c->arena_in_bytes += (long long)in_end;
         const int dirty = c->dbg_dirty_fill;         // test hook "dirty_fill": the whole arena and the staging slot hold the byte before any input goes in
         if (dirty >= 0) EORB_HIP(c, hipMemsetAsync(c->arena.p, dirty, c->arena.cap, c->stream));
         if (!in_end) return EORB_OK;
@@ -225,6 +226,7 @@ struct Arena {
     // download_begin / download_wait: the same in two halves -- what the caller launches in between (work the results do not depend on:
     // the LK reference kept for the next call) runs after the copy and is not waited for.
     size_t dl_off = 0;
+    void count_download(size_t off, size_t bytes) { c->arena_downloads++; c->arena_download_bytes += (long long)bytes; c->arena_download_first += (long long)off; }
     static long download_kmax() { static const long k = [] { const char* e = getenv("EORB_DOWNLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }(); return k; }      // (bytes; 0: always the copy engine)
     int landing(size_t bytes)
     {
@@ -239,6 +241,7 @@ struct Arena {
     {
         int rc = landing(bytes);
         if (rc) return rc;
+        count_download(off, bytes);
         if (c->dbg_dirty_fill >= 0) memset(c->dl_pinned, c->dbg_dirty_fill, c->dl_cap);      // (test hook: a host read outside the downloaded range sees the byte)
         // (the way back like the way in: up to a few hundred KB a kernel writes the pinned buffer; offsets of the arena are multiples of
         // 256 and both buffers longer than the rounded size)
@@ -276,6 +279,45 @@ struct Arena {
         // (profiling: the scopes' events are collected when the stream is idle -- eorb_prof_* synchronise before they read)
         return EORB_OK;
     }
+    // The outputs are declared like the inputs, and registration order is layout order:
+    //   out(dst, bytes)        reserves a region that fetch() copies to dst; dst == NULL: the region exists, the kernels write it, nobody takes it
+    //   inout(dst, off, bytes) the same for a region that exists already (an input that comes back)
+    //   want(off, bytes)       only extends the fetched span over a region: nothing is copied, the caller reads it through fetch()'s host
+    //                          view (count words, and records whose number is known only after the download)
+    // fetch(): ONE download of arena[first wanted offset, end of the last wanted region), the wait, then the copies.  fetch_begin() /
+    // fetch_wait(): its two halves (download_begin / download_wait).  Nothing wanted: fetch() only waits for the call's kernels.
+    struct Out { void* dst; size_t off, bytes; };
+    static constexpr int kMaxOuts = 32;                    // (a fixed array: no allocation on the one-call paths)
+    Out outs[kMaxOuts]; int nouts = 0; bool outs_full = false;
+    size_t want_lo = ~(size_t)0, want_hi = 0;
+    void want(size_t off, size_t bytes) { if (bytes) { want_lo = std::min(want_lo, off); want_hi = std::max(want_hi, off + bytes); } }
+    void inout(void* dst, size_t off, size_t bytes)
+    {
+        if (!dst || !bytes) return;
+        if (nouts == kMaxOuts) { outs_full = true; return; }
+        want(off, bytes); outs[nouts++] = Out{dst, off, bytes};
+    }
+    size_t out(void* dst, size_t bytes) { const size_t o = take(bytes); inout(dst, o, bytes); return o; }
+    void copy_out(const char* h) const { for (int i = 0; i < nouts; i++) memcpy(outs[i].dst, h + outs[i].off, outs[i].bytes); }
+    int fetch_begin()
+    {
+        if (outs_full) return set_err(c, EORB_E_HIP, "internal error: a call registered more than %d outputs", kMaxOuts);
+        return download_begin(want_lo, want_hi - want_lo);
+    }
+    int fetch_wait(const char** host = nullptr)
+    {
+        const char* h;
+        if (const int rc = download_wait(&h)) return rc;
+        copy_out(h);
+        if (host) *host = h;
+        return EORB_OK;
+    }
+    int fetch(const char** host = nullptr)
+    {
+        if (!want_hi) { EORB_HIP(c, fe_stream_sync(c)); return EORB_OK; }
+        if (const int rc = fetch_begin()) return rc;
+        return fetch_wait(host);
+    }
     // download() + memcpy(dst, ...) for one result; from kPiece on the copy engine writes the caller's buffer itself (as for the inputs)
     int download_to(void* dst, size_t off, size_t bytes)
     {
@@ -286,6 +328,7 @@ struct Arena {
             memcpy(dst, h + off, bytes);
             return EORB_OK;
         }
+        count_download(off, bytes);
         EORB_HIP(c, hipMemcpyAsync(dst, (char*)c->arena.p + off, bytes, hipMemcpyDeviceToHost, c->stream));
         EORB_HIP(c, fe_stream_sync(c));
         return EORB_OK;
@@ -431,6 +474,14 @@ long long eorb_debug_counter(eorb_ctx* c, const char* name)
     if (!strcmp(name, "slot_binning")) return c->sl_last_binning;         // count | record << 2 | scatter << 4 of the last slot-form call (ev_plan.h SlotBinPlan)
     if (!strcmp(name, "kfdb_slot_cap")) return c->kfdb.slot_cap;          // KeyFrameDatabase pools: slots / words they hold room for
     if (!strcmp(name, "kfdb_word_cap")) return c->kfdb.word_cap;
+    // host-buffer calls, cumulative over the context's life: arenas laid out and their bytes (all / the uploaded prefix); downloads, their
+    // bytes and the sum of their first offsets
+    if (!strcmp(name, "arena_calls")) return c->arena_calls;
+    if (!strcmp(name, "arena_bytes")) return c->arena_bytes;
+    if (!strcmp(name, "arena_in_bytes")) return c->arena_in_bytes;
+    if (!strcmp(name, "arena_downloads")) return c->arena_downloads;
+    if (!strcmp(name, "arena_download_bytes")) return c->arena_download_bytes;
+    if (!strcmp(name, "arena_download_first")) return c->arena_download_first;
     if (!strcmp(name, "slot_parts")) return c->sl_last_parts;              // 2: the last slot-form call ran its batch as two halves
     if (!strcmp(name, "slot_hot_overflow")) {           // lists the last slot-form call handed back to the LDS gather because their length bucket was full (synchronises)
         long long n = 0;
@@ -603,8 +654,9 @@ static int ev_host_common(eorb_ctx* c, const eorb_event* ev, size_t n, int W, in
     static const int zc_env = [] { const char* e = getenv("EORB_SLICE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
     A.host_inputs = zc_env != 0 && plan_host_events(accum_shape(W, H, sigma, mode_count, 1, (int64_t)n), AccumRequest{raw, pol, mode_count, 1}, accum_knobs(c));
     const size_t o_ev = A.in(raw ? (const void*)rawev : (const void*)packed.data(), sizeof(eorb_event16) * n);
-    // outputs, contiguous: min/max (encoded | decoded) | u8 image | f32 image
-    const size_t o_mm = A.reserve(64), o_u8 = A.reserve(npix), o_f32 = A.reserve(sizeof(float) * npix);
+    // outputs: min/max (encoded | decoded; read through the host view) | u8 image | f32 image
+    const size_t o_mm = A.out(nullptr, 64), o_u8 = A.out(out_u8, npix), o_f32 = A.out(out_f32, sizeof(float) * npix);
+    A.want(o_mm, 64);
     if ((rc = A.upload())) return rc;
     int64_t offs[2] = {0, (int64_t)n};
     uint32_t* mm = A.dev<uint32_t>(o_mm);
@@ -618,13 +670,13 @@ static int ev_host_common(eorb_ctx* c, const eorb_event* ev, size_t n, int W, in
     // word: this call's copy of it travels with the outputs (word 2 of the min/max block)
     const bool slot_ran = (c->accum_route & kRouteFormMask) == kFormSlots;
     if (slot_ran) EORB_HIP(c, hipMemcpyAsync(mm + 2, c->status.p, 4, hipMemcpyDeviceToDevice, c->stream));
-    const size_t end = out_f32 ? o_f32 + sizeof(float) * npix : (out_u8 ? o_u8 + npix : o_mm + 64);
     const char* h;
-    if ((rc = A.download(o_mm, end - o_mm, &h))) return rc;
-    if (slot_ran) {
+    if ((rc = A.fetch_begin()) || (rc = A.download_wait(&h))) return rc;
+    if (slot_ran) {                                      // (checked before anything reaches the caller's buffers)
         int32_t st; memcpy(&st, h + o_mm + 8, 4);
         if (st & 256) return set_err(c, EORB_E_HIP, "internal error: the slot gather found its LDS rows at a non-zero base; no image was written");
     }
+    A.copy_out(h);
     // the running extremes come back in their order-preserving integer encoding (enc_f32 of the gather kernels): decoded here
     float hmm[2];
     for (int k = 0; k < 2; k++) {
@@ -632,8 +684,6 @@ static int ev_host_common(eorb_ctx* c, const eorb_event* ev, size_t n, int W, in
         const uint32_t u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
         memcpy(&hmm[k], &u, 4);
     }
-    if (out_f32) memcpy(out_f32, h + o_f32, sizeof(float) * npix);
-    if (out_u8) memcpy(out_u8, h + o_u8, npix);
     if (minmax) { minmax[0] = hmm[0]; minmax[1] = hmm[1]; }
     if (is_u8) *is_u8 = mode_count ? (normalized && hmm[1] > hmm[0]) : (normalized != 0);
     return EORB_OK;
@@ -689,16 +739,10 @@ int eorb_generate_undistort_maps(eorb_ctx* c, int LW, int LH, int checkInImage, 
     int rc;
     if ((rc = ensure(c, c->maps.lut, sizeof(float) * 2 * n))) return rc;
     Arena A(c);
-    const size_t o_x = A.reserve(mapX ? sizeof(float) * n : 0), o_y = A.reserve(mapX ? sizeof(float) * n : 0);
+    const size_t o_x = A.out(mapX, mapX ? sizeof(float) * n : 0), o_y = A.out(mapY, mapX ? sizeof(float) * n : 0);
     if ((rc = A.upload())) return rc;
     if ((rc = calib_maps_dev(c, LW, LH, (float*)c->maps.lut.p, mapX ? A.dev<float>(o_x) : nullptr, mapX ? A.dev<float>(o_y) : nullptr))) return rc;
-    if (mapX) {
-        const char* h;
-        if ((rc = A.download(o_x, o_y + sizeof(float) * n - o_x, &h))) return rc;
-        memcpy(mapX, h + o_x, sizeof(float) * n);
-        memcpy(mapY, h + o_y, sizeof(float) * n);
-    } else
-        EORB_HIP(c, fe_stream_sync(c));
+    if ((rc = A.fetch())) return rc;                          // (no maps taken: the wait alone)
     return install_maps(c, LW, LH, checkInImage);
 }
 
@@ -827,8 +871,9 @@ static int mci_common(eorb_ctx* c, const eorb_event* ev, size_t n, const eorb_ca
     Arena A(c);
     const size_t o_ev = A.in_events(ev, n), o_depth = A.in(depth, depth ? sizeof(float) * n : 0);
     const size_t o_warp = A.reserve(sizeof(eorb_event16) * n);
-    // outputs, contiguous: min/max (encoded | decoded) | u8 image | f32 image
-    const size_t o_mm = A.reserve(64), o_u8 = A.reserve(npix), o_f32 = A.reserve(sizeof(float) * npix);
+    // outputs: min/max (encoded | decoded: the block is fetched whole) | u8 image (written when normalized) | f32 image
+    const size_t o_mm = A.out(nullptr, 64), o_u8 = A.out(normalized ? out_u8 : nullptr, npix), o_f32 = A.out(out_f32, sizeof(float) * npix);
+    A.want(o_mm, 64); A.inout(minmax, o_mm + 16, 8);
     if ((rc = A.upload())) return rc;
     const float* d_depth = depth ? A.dev<float>(o_depth) : nullptr;
     eorb_event16* d_warp = A.dev<eorb_event16>(o_warp);
@@ -844,13 +889,7 @@ static int mci_common(eorb_ctx* c, const eorb_event* ev, size_t n, const eorb_ca
     c->dbg_dd_min = dd_saved;
     if (rc) return rc;
     if ((rc = ev_decode_minmax(c, mm, mmf, 1))) return rc;
-    const size_t end = out_f32 ? o_f32 + sizeof(float) * npix : ((out_u8 && normalized) ? o_u8 + npix : o_mm + 64);
-    const char* h;
-    if ((rc = A.download(o_mm, end - o_mm, &h))) return rc;
-    if (out_f32) memcpy(out_f32, h + o_f32, sizeof(float) * npix);
-    if (out_u8 && normalized) memcpy(out_u8, h + o_u8, npix);
-    if (minmax) memcpy(minmax, h + o_mm + 16, 8);
-    return EORB_OK;
+    return A.fetch();
 }
 
 static eorb_camera pinhole_cam(const eorb_pinhole* p) { eorb_camera c{}; if (p) { c.fx = p->fx; c.fy = p->fy; c.cx = p->cx; c.cy = p->cy; } return c; }
@@ -892,13 +931,10 @@ int eorb_measure_image_focus_n(eorb_ctx* c, const float* imgs, int n, int W, int
     fe_enter(c);
     int rc;
     Arena A(c);
-    const size_t o_img = A.in(imgs, sizeof(float) * (size_t)W * H * n), o_focus = A.reserve(sizeof(float) * n);
+    const size_t o_img = A.in(imgs, sizeof(float) * (size_t)W * H * n), o_focus = A.out(focus, sizeof(float) * n);
     if ((rc = A.upload())) return rc;
     if ((rc = ev_focus_dev(c, A.dev<float>(o_img), n, W, H, A.dev<float>(o_focus)))) return rc;
-    const char* h;
-    if ((rc = A.download(o_focus, sizeof(float) * n, &h))) return rc;
-    memcpy(focus, h + o_focus, sizeof(float) * n);
-    return EORB_OK;
+    return A.fetch();
 }
 int eorb_measure_image_focus(eorb_ctx* c, const float* img, int W, int H, float* focus) { return eorb_measure_image_focus_n(c, img, 1, W, H, focus); }
 
@@ -910,13 +946,10 @@ int eorb_normalize_minmax_u8(eorb_ctx* c, const float* img, int W, int H, uint8_
     const size_t npix = (size_t)W * H;
     int rc;
     Arena A(c);
-    const size_t o_img = A.in(img, sizeof(float) * npix), o_mm = A.reserve(64), o_u8 = A.reserve(npix);
+    const size_t o_img = A.in(img, sizeof(float) * npix), o_mm = A.reserve(64), o_u8 = A.out(out, npix);
     if ((rc = A.upload())) return rc;
     if ((rc = ev_cvnormalize_dev(c, A.dev<float>(o_img), (int)npix, A.dev<uint32_t>(o_mm), A.dev<uint8_t>(o_u8)))) return rc;
-    const char* h;
-    if ((rc = A.download(o_u8, npix, &h))) return rc;
-    memcpy(out, h + o_u8, npix);
-    return EORB_OK;
+    return A.fetch();
 }
 
 // ---- marshalling shared by the extraction entry points (eorb_orb_extract, eorb_frame_mono / _stereo / _fisheye, eorb_ev_slice_extract
@@ -952,31 +985,30 @@ struct ExtractHead {
     int32_t flag[2];            // internal capacity exceeded, one per extraction launch
     float corners[8];           // eorb_frame_mono: the undistorted corners (0, 0), (W, 0), (0, H), (W, H)
 };
-struct ExtractOff { size_t head, kp, un, desc, oob, mo; int nimg; };
-static ExtractOff extract_reserve(Arena& A, int max_out, int nimg, bool undist = false)
+// where a call's records go (one entry per image; any pointer may be NULL)
+struct ExtractDst { eorb_keypoint* kps; uint8_t* desc; uint8_t* oob; int* n; int* mono; };
+struct ExtractOff { size_t head, kp, un, desc, oob, mo, ncopy; int nimg; };      // ncopy: the records a caller of this capacity can be handed
+// The number of records is known only after the download, so nothing is registered for copying: the fetched span covers the head and, of
+// every array the caller takes, the first ncopy records; extract_out copies n of them after its checks
+static ExtractOff extract_reserve(Arena& A, int max_out, int nimg, int cap, const ExtractDst* dst, bool undist = false)
 {
     ExtractOff x{};
-    x.mo = (size_t)max_out; x.nimg = nimg;
-    x.head = A.reserve(sizeof(ExtractHead));
-    x.kp = A.reserve(sizeof(eorb_keypoint) * x.mo * nimg);
-    if (undist) x.un = A.reserve(sizeof(eorb_keypoint) * x.mo);
-    x.desc = A.reserve(32 * x.mo * nimg);
-    if (nimg == 1) x.oob = A.reserve(x.mo);
+    x.mo = (size_t)max_out; x.nimg = nimg; x.ncopy = std::min(x.mo, (size_t)std::max(cap, 0));
+    x.head = A.out(nullptr, sizeof(ExtractHead));
+    x.kp = A.out(nullptr, sizeof(eorb_keypoint) * x.mo * nimg);
+    if (undist) x.un = A.out(nullptr, sizeof(eorb_keypoint) * x.mo);
+    x.desc = A.out(nullptr, 32 * x.mo * nimg);
+    if (nimg == 1) x.oob = A.out(nullptr, x.mo);
+    A.want(x.head, sizeof(ExtractHead));
+    for (int i = 0; i < nimg; i++) {
+        if (dst[i].kps) A.want(x.kp + sizeof(eorb_keypoint) * x.mo * i, sizeof(eorb_keypoint) * x.ncopy);
+        if (dst[i].desc) A.want(x.desc + 32 * x.mo * i, 32 * x.ncopy);
+        if (dst[i].oob) A.want(x.oob, x.ncopy);
+    }
     return x;
 }
-// end of the one download of a one-image call: the head always, the arrays up to the last one the caller takes and up to its capacity
-static size_t extract_end(const ExtractOff& x, int cap, bool kps, bool un, bool desc, bool oob)
-{
-    const size_t ncopy = std::min(x.mo, (size_t)std::max(cap, 0));
-    if (ncopy && oob) return x.oob + ncopy;
-    if (ncopy && desc) return x.desc + 32 * ncopy;
-    if (ncopy && un) return x.un + sizeof(eorb_keypoint) * ncopy;
-    if (ncopy && kps) return x.kp + sizeof(eorb_keypoint) * ncopy;
-    return x.head + sizeof(ExtractHead);
-}
-// after the download (h: its host view): a set flag (nflag: extraction launches of the call) and a count above cap are
-// EORB_E_CAPACITY and nothing is written; else every image's n records and its counters go to the caller (any pointer may be NULL)
-struct ExtractDst { eorb_keypoint* kps; uint8_t* desc; uint8_t* oob; int* n; int* mono; };
+// after the fetch (h: its host view): a set flag (nflag: extraction launches of the call) and a count above cap are
+// EORB_E_CAPACITY and nothing is written; else every image's n records and its counters go to the caller
 static int extract_out(eorb_ctx* c, const char* who, const char* h, const ExtractOff& x, int cap, int nflag, const ExtractDst* dst, const ExtractHead** head = nullptr)
 {
     const ExtractHead& hd = *(const ExtractHead*)(h + x.head);
@@ -1049,8 +1081,10 @@ int eorb_ev_slice_extract(eorb_ctx* c, const eorb_event* ev, const eorb_raw_even
     const bool zc = zc_env != 0 && plan_host_events(accum_shape(W, H, sigma, 0, 1, (int64_t)n), AccumRequest{is_raw, 0, 0, 1}, accum_knobs(c));
     A.host_inputs = zc;
     const size_t o_mm = zc ? A.reserve(sizeof(kMinMaxPreset)) : A.in(kMinMaxPreset, sizeof(kMinMaxPreset)), o_f32 = A.reserve(sizeof(float) * npix);
-    const size_t o_u8 = A.reserve(npix);
-    const ExtractOff X = extract_reserve(A, o.max_out, 1);
+    const size_t o_u8 = A.out(nullptr, npix);
+    if (out_u8) A.want(o_u8, npix);                       // (copied below, unless the extraction's flag is set)
+    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
+    const ExtractOff X = extract_reserve(A, o.max_out, 1, cap, &dst);
     if ((rc = A.upload())) return rc;
     int64_t offs[2] = {0, (int64_t)n};
     uint8_t* d_u8 = A.dev<uint8_t>(o_u8);
@@ -1065,20 +1099,18 @@ int eorb_ev_slice_extract(eorb_ctx* c, const eorb_event* ev, const eorb_raw_even
     if ((rc = ensure(c, c->l1_ref_img, npix)) || (rc = ensure(c, c->l1_ref_pts, sizeof(float) * 2 * X.mo))) return rc;
     c->l1_nref = -1; c->l1_W = W; c->l1_H = H; c->klt_ref_serial++;
     c->l1_img_off = o_u8; c->l1_img_gen = c->arena_gen;
-    const size_t first = out_u8 ? o_u8 : X.head;
     const char* h;
-    if ((rc = A.download_begin(first, extract_end(X, cap, kps, false, want_desc && desc, oob) - first))) return rc;
+    if ((rc = A.fetch_begin())) return rc;
     // ELK_Tracker::setRefImage(image, keypoints) (:1363 init -> KLT_Tracker.cpp:22-46): the image and its points stay on the device --
     // queued behind the download, which does not wait for them (the next call on the stream is ordered behind them)
     EORB_HIP(c, hipMemcpyAsync(c->l1_ref_img.p, d_u8, npix, hipMemcpyDeviceToDevice, c->stream));
     if ((rc = ev_kp_points_dev(c, A.dev<eorb_keypoint>(X.kp), hd->n, (int)X.mo, (float*)c->l1_ref_pts.p))) return rc;
-    if ((rc = A.download_wait(&h))) return rc;
+    if ((rc = A.fetch_wait(&h))) return rc;
     const ExtractHead& got = *(const ExtractHead*)(h + X.head);
     if (!got.flag[0]) {                                   // the reference frame and the image stand whatever the caller's capacity is
         c->l1_nref = got.n[0];
         if (out_u8) memcpy(out_u8, h + o_u8, npix);
     }
-    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
     return extract_out(c, "ev_slice_extract", h, X, cap, 1, &dst);
 }
 
@@ -1102,7 +1134,9 @@ int eorb_ev_slice_track(eorb_ctx* c, const eorb_event* ev, const eorb_raw_event*
     // status | err | u8 image; then device-only
     const size_t o_mm = A.in(kMinMaxPreset, sizeof(kMinMaxPreset));
     const size_t o_pts = A.in(pts, sizeof(float) * 2 * (size_t)nref);
-    const size_t o_st = A.reserve((size_t)nref + 16), o_err = A.reserve(sizeof(float) * (size_t)nref), o_u8 = A.reserve(npix);
+    A.inout(pts, o_pts, sizeof(float) * 2 * (size_t)nref);
+    const size_t o_st = A.out(nullptr, (size_t)nref + 16), o_err = A.out(err, sizeof(float) * (size_t)nref), o_u8 = A.out(out_u8, npix);
+    A.inout(status, o_st, (size_t)nref);
     const size_t o_f32 = A.reserve(sizeof(float) * npix);
     if ((rc = A.upload())) return rc;
     int64_t offs[2] = {0, (int64_t)n};
@@ -1113,16 +1147,7 @@ int eorb_ev_slice_track(eorb_ctx* c, const eorb_event* ev, const eorb_raw_event*
     if (nref && (rc = klt_track_dev(c, (const uint8_t*)c->l1_ref_img.p, d_u8, W, H, W, (const float*)c->l1_ref_pts.p, A.dev<float>(o_pts), nref, klt->win,
                                     klt->maxLevel, klt->maxCount, klt->epsilon, 4 /* OPTFLOW_USE_INITIAL_FLOW */, klt->minEigThreshold,
                                     A.dev<uint8_t>(o_st), A.dev<float>(o_err), c->klt_ref_serial))) return rc;
-    const size_t end = out_u8 ? o_u8 + npix : o_err + sizeof(float) * (size_t)nref;
-    const char* h;
-    if ((rc = A.download(o_pts, end - o_pts, &h))) return rc;
-    if (nref) {
-        memcpy(pts, h + o_pts, sizeof(float) * 2 * (size_t)nref);
-        memcpy(status, h + o_st, (size_t)nref);
-        memcpy(err, h + o_err, sizeof(float) * (size_t)nref);
-    }
-    if (out_u8) memcpy(out_u8, h + o_u8, npix);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_ev_slice_image(eorb_ctx* c, uint8_t* out_u8)
@@ -1171,8 +1196,11 @@ int eorb_ev_mc_contest(eorb_ctx* c, const eorb_event* ev, size_t n, const eorb_c
     const size_t o_mm = A.reserve(256), o_f32 = A.reserve(sizeof(float) * npix * (size_t)nimg), o_u8s = A.reserve(npix * (size_t)nimg);
     const size_t o_fimg = A.reserve(64);
     const size_t mo = l2 ? (size_t)l2->orb.max_out : 0;
-    // outputs, contiguous: focus[5] + winner | the winner's u8 image | {n, mono, flag} | keypoints
-    const size_t o_res = A.reserve(64), o_win = A.reserve(npix), o_n = A.reserve(16), o_kp = A.reserve(sizeof(eorb_keypoint) * std::max<size_t>(mo, 1));
+    // outputs: focus[5] + winner | the winner's u8 image | {n, mono, flag} | keypoints (the L2 extraction's: n of them, copied after its checks)
+    const size_t ncopy = l2 ? std::min<size_t>(mo, (size_t)std::max(cap, 0)) : 0;
+    const size_t o_res = A.out(nullptr, 64), o_win = A.out(out_u8, npix), o_n = A.out(nullptr, 16), o_kp = A.out(nullptr, sizeof(eorb_keypoint) * std::max<size_t>(mo, 1));
+    A.want(o_res, 64);
+    if (l2) { A.want(o_n, 16); if (kps) A.want(o_kp, sizeof(eorb_keypoint) * ncopy); }
     if ((rc = A.upload())) return rc;
     const eorb_event16* d_ev = A.dev<eorb_event16>(o_ev);
     eorb_event16* d_warp = A.dev<eorb_event16>(o_warp);
@@ -1222,14 +1250,11 @@ int eorb_ev_mc_contest(eorb_ctx* c, const eorb_event* ev, size_t n, const eorb_c
         l2->stream = saved;
         if (rc) { if (l2 != c) c->err = l2->err; return rc; }
     }
-    const size_t ncopy = l2 ? std::min<size_t>(mo, (size_t)std::max(cap, 0)) : 0;
-    const size_t end_off = l2 ? (ncopy && kps ? o_kp + sizeof(eorb_keypoint) * ncopy : o_n + 16) : (out_u8 ? o_win + npix : o_res + 64);
     const char* h;
-    if ((rc = A.download(o_res, end_off - o_res, &h))) return rc;
+    if ((rc = A.fetch(&h))) return rc;
     memcpy(focus, h + o_res, sizeof(float) * 5);
     int32_t w; memcpy(&w, h + o_res + 32, 4);
     *winner = w;
-    if (out_u8) memcpy(out_u8, h + o_win, npix);
     if (l2) {
         const int32_t* hn = (const int32_t*)(h + o_n);
         if (hn[2]) return set_err(c, EORB_E_CAPACITY, "ev_mc_contest: the L2 extraction exceeded an internal capacity (flag %d)", hn[2]);
@@ -1303,7 +1328,8 @@ int eorb_orb_extract(eorb_ctx* c, const uint8_t* img, int W, int H, int stride, 
     fe_enter(c);
     Arena A(c);
     const size_t o_img = image_in(A, img, W, H, stride, true);
-    const ExtractOff X = extract_reserve(A, c->orb.max_out, 1);
+    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
+    const ExtractOff X = extract_reserve(A, c->orb.max_out, 1, cap, &dst);
     if ((rc = A.upload())) return rc;
     ExtractHead* hd = A.dev<ExtractHead>(X.head);
     rc = orb_extract_dev(c, A.in_ptr<uint8_t>(o_img), W, (size_t)W * H, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(X.kp),
@@ -1311,8 +1337,7 @@ int eorb_orb_extract(eorb_ctx* c, const uint8_t* img, int W, int H, int stride, 
     A.inputs_done();
     if (rc) return rc;
     const char* h;
-    if ((rc = A.download(X.head, extract_end(X, cap, kps, false, want_desc && desc, oob) - X.head, &h))) return rc;
-    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
+    if ((rc = A.fetch(&h))) return rc;
     return extract_out(c, "orb_extract", h, X, cap, 1, &dst);
 }
 
@@ -1329,18 +1354,19 @@ int eorb_frame_mono(eorb_ctx* c, const uint8_t* img, int W, int H, int stride, i
     fe_enter(c);
     Arena A(c);
     const size_t o_img = image_in(A, img, W, H, stride, true);
-    const ExtractOff X = extract_reserve(A, c->orb.max_out, 1, true);
+    const bool gate = c->calib_dev.gate != 0;
+    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
+    const ExtractOff X = extract_reserve(A, c->orb.max_out, 1, cap, &dst, true);
+    if (kps_un) A.want(gate ? X.un : X.kp, sizeof(eorb_keypoint) * X.ncopy);      // gate closed: vUndistKPts = vDistKPts
     if ((rc = A.upload())) return rc;
     ExtractHead* hd = A.dev<ExtractHead>(X.head);
     rc = orb_extract_dev(c, A.in_ptr<uint8_t>(o_img), W, (size_t)W * H, 1, lap0, lap1, want_desc, A.dev<eorb_keypoint>(X.kp),
                          A.dev<uint8_t>(X.desc), A.dev<uint8_t>(X.oob), hd->n, hd->mono, hd->flag);
     A.inputs_done();
     if (rc) return rc;
-    const bool gate = c->calib_dev.gate != 0;
     if ((rc = calib_frame_dev(c, A.dev<eorb_keypoint>(X.kp), hd->n, (int)X.mo, A.dev<eorb_keypoint>(X.un), hd->corners, W, H))) return rc;
     const char* h;
-    if ((rc = A.download(X.head, extract_end(X, cap, kps || kps_un, kps_un && gate, want_desc && desc, oob) - X.head, &h))) return rc;
-    const ExtractDst dst{kps, want_desc ? desc : nullptr, oob, n_out, mono_index};
+    if ((rc = A.fetch(&h))) return rc;
     const ExtractHead* got;
     if ((rc = extract_out(c, "eorb_frame_mono", h, X, cap, 1, &dst, &got))) return rc;
     if (kps_un && got->n[0] > 0) memcpy(kps_un, h + (gate ? X.un : X.kp), sizeof(eorb_keypoint) * (size_t)got->n[0]);      // gate closed: vUndistKPts = vDistKPts
@@ -1370,9 +1396,12 @@ int eorb_frame_stereo(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRight
     fe_enter(c);
     Arena A(c);
     const size_t o_imL = image_in(A, imLeft, W, H, stride, false), o_imR = image_in(A, imRight, W, H, stride, false);
-    // outputs, contiguous: the result block of the pair | uRight | depth | (norms)
-    const ExtractOff X = extract_reserve(A, c->orb.max_out, 2);
-    const size_t o_ur = A.reserve(sizeof(float) * X.mo), o_dp = A.reserve(sizeof(float) * X.mo), o_sad = A.reserve(sizeof(int32_t) * X.mo);
+    // outputs: the result block of the pair | uRight | depth (n[0] of each, copied after the checks) | (norms)
+    const ExtractDst dst[2] = {{kpsL, descL, nullptr, nL, nullptr}, {kpsR, descR, nullptr, nR, nullptr}};
+    const ExtractOff X = extract_reserve(A, c->orb.max_out, 2, cap, dst);
+    const size_t o_ur = A.out(nullptr, sizeof(float) * X.mo), o_dp = A.out(nullptr, sizeof(float) * X.mo), o_sad = A.reserve(sizeof(int32_t) * X.mo);
+    if (uRight) A.want(o_ur, sizeof(float) * X.ncopy);
+    if (depth) A.want(o_dp, sizeof(float) * X.ncopy);
     if ((rc = A.upload())) return rc;
     ExtractHead* hd = A.dev<ExtractHead>(X.head);
     rc = orb_extract_dev(c, A.dev<uint8_t>(o_imL), W, o_imR - o_imL, 2, 0, 0, 1, A.dev<eorb_keypoint>(X.kp), A.dev<uint8_t>(X.desc), nullptr, hd->n, hd->mono, hd->flag);
@@ -1380,8 +1409,7 @@ int eorb_frame_stereo(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRight
     if ((rc = stereo_match_dev(c, A.dev<eorb_keypoint>(X.kp), A.dev<uint8_t>(X.desc), hd->n, mb, mbf, A.dev<float>(o_ur), A.dev<float>(o_dp),
                                A.dev<int32_t>(o_sad), hd->aux))) return rc;
     const char* h;
-    if ((rc = A.download(X.head, o_sad - X.head, &h))) return rc;
-    const ExtractDst dst[2] = {{kpsL, descL, nullptr, nL, nullptr}, {kpsR, descR, nullptr, nR, nullptr}};
+    if ((rc = A.fetch(&h))) return rc;
     const ExtractHead* got;
     if ((rc = extract_out(c, "eorb_frame_stereo", h, X, cap, 1, dst, &got))) return rc;      // (one launch for both images: one flag)
     if (uRight && got->n[0] > 0) memcpy(uRight, h + o_ur, sizeof(float) * (size_t)got->n[0]);
@@ -1401,22 +1429,14 @@ static int tracked_common(eorb_ctx* c, const uint8_t* img, int W, int H, int str
     fe_enter(c);
     Arena A(c);
     const size_t o_img = image_in(A, img, W, H, stride, false), o_ref = A.in(ref, ref ? 32 * (size_t)n : 0);
-    // keypoints (in / out: mode 1 writes their octaves) | outputs of mode 0, contiguous: descriptors | oob
+    // keypoints (in / out: mode 1 writes their octaves and takes them, kps_io) | outputs of mode 0 (desc, oob): descriptors | oob
     const size_t o_kp = A.in(kps_in, sizeof(eorb_keypoint) * (size_t)n);
-    const size_t o_desc = A.reserve(32 * (size_t)n), o_oob = A.reserve((size_t)n);
+    A.inout(kps_io, o_kp, sizeof(eorb_keypoint) * (size_t)n);
+    const size_t o_desc = A.out(desc, 32 * (size_t)n), o_oob = A.out(oob, (size_t)n);
     if ((rc = A.upload())) return rc;
     if ((rc = orb_pyramid_blur_dev(c, A.dev<uint8_t>(o_img), W))) return rc;
     if ((rc = orb_tracked_dev(c, A.dev<eorb_keypoint>(o_kp), n, mode, A.dev<uint8_t>(o_ref), A.dev<uint8_t>(o_desc), A.dev<uint8_t>(o_oob)))) return rc;
-    const char* h;
-    if (mode == 0) {
-        if ((rc = A.download(o_desc, (oob ? o_oob + n : o_desc + 32 * (size_t)n) - o_desc, &h))) return rc;
-        memcpy(desc, h + o_desc, 32 * (size_t)n);
-        if (oob) memcpy(oob, h + o_oob, (size_t)n);
-    } else {
-        if ((rc = A.download(o_kp, sizeof(eorb_keypoint) * (size_t)n, &h))) return rc;
-        memcpy(kps_io, h + o_kp, sizeof(eorb_keypoint) * (size_t)n);
-    }
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_orb_tracked_descriptors(eorb_ctx* c, const uint8_t* img, int W, int H, int stride, const eorb_keypoint* kps, int n,
@@ -1457,6 +1477,7 @@ int eorb_search_for_initialization(eorb_ctx* c,
     const size_t o_nm = A.in(nullptr, 16);
     const size_t o_m = A.in(nullptr, sizeof(int32_t) * (size_t)c1);
     const size_t o_pm = A.in(prev_matched, prev_matched ? sizeof(float) * 2 * (size_t)n1 : 0);
+    A.inout(nmatches, o_nm, sizeof(int32_t)); A.inout(matches12, o_m, sizeof(int32_t) * (size_t)n1); A.inout(prev_matched, o_pm, sizeof(float) * 2 * (size_t)n1);
     if ((rc = A.upload())) return rc;
     const int32_t* dn = A.dev<int32_t>(o_n);
     rc = search_init_dev(c, 1, A.dev<eorb_keypoint>(o_k1), dn, 0, A.dev<uint8_t>(o_d1), stride1, 0, is_orb1 ? A.dev<uint8_t>(o_o1) : nullptr,
@@ -1464,13 +1485,7 @@ int eorb_search_for_initialization(eorb_ctx* c,
                          c1, c2, *gb, prev_matched ? A.dev<float>(o_pm) : nullptr, A.dev<int32_t>(o_m), windowSize, nnratio, checkOri,
                          A.dev<int32_t>(o_nm));
     if (rc) return rc;
-    const size_t end = prev_matched ? o_pm + sizeof(float) * 2 * (size_t)n1 : o_m + sizeof(int32_t) * (size_t)n1;
-    const char* h;
-    if ((rc = A.download(o_nm, end - o_nm, &h))) return rc;
-    memcpy(matches12, h + o_m, sizeof(int32_t) * (size_t)n1);
-    if (prev_matched) memcpy(prev_matched, h + o_pm, sizeof(float) * 2 * (size_t)n1);
-    if (nmatches) *nmatches = *(const int32_t*)(h + o_nm);
-    return EORB_OK;
+    return A.fetch();
 }
 
 // ---- marshalling shared by the projection matchers: "queue into the arena, then (after A.upload()) the device view" ---------------
@@ -1488,26 +1503,26 @@ static FrameDev frame_dev(const Arena& A, const FrameOff& o)
 
 // the result region {nmatches, n_in_view | slots (in/out)}: the head of a call's contiguous outputs.  reloc: relocalisation
 // (SearchByProjection(CurrentFrame, pKF, sAlreadyFound)) -- every occupied slot is skipped (:2255-2256), only new matches are written back
-struct ResultOff { size_t nm, slots, end; std::vector<int32_t> masked; };
-static ResultOff result_in(Arena& A, const int32_t* slots, int n, bool reloc = false)
+struct ResultOff { size_t nm, slots; std::vector<int32_t> masked; };
+static ResultOff result_in(Arena& A, int32_t* slots, int n, bool reloc = false)
 {
     ResultOff o;
     if (reloc) { o.masked.assign(slots, slots + n); for (int32_t& s : o.masked) if (s != -1) s = -2; }
-    o.nm = A.in(nullptr, 16); o.slots = A.in(reloc ? o.masked.data() : slots, sizeof(int32_t) * (size_t)n); o.end = o.slots + sizeof(int32_t) * (size_t)n;
+    o.nm = A.in(nullptr, 16); o.slots = A.in(reloc ? o.masked.data() : slots, sizeof(int32_t) * (size_t)n);
+    A.want(o.nm, 16);
+    if (reloc) A.want(o.slots, sizeof(int32_t) * (size_t)n);      // (merged into the caller's slots by result_out)
+    else A.inout(slots, o.slots, sizeof(int32_t) * (size_t)n);
     return o;
 }
-// the call's one download, arena[o.nm, end): the counts and the slots; host: for what the caller copies out of the rest
-static int result_out(Arena& A, const ResultOff& o, size_t end, int32_t* slots, int* nmatches, int* n_in_view = nullptr, const char** host = nullptr)
+// the call's fetch: the counts and the slots, and whatever else the call registered
+static int result_out(Arena& A, const ResultOff& o, int32_t* slots, int* nmatches, int* n_in_view = nullptr)
 {
     const char* h;
-    const int rc = A.download(o.nm, end - o.nm, &h);
-    if (rc) return rc;
+    if (const int rc = A.fetch(&h)) return rc;
     const int32_t* cnt = (const int32_t*)(h + o.nm); const int32_t* got = (const int32_t*)(h + o.slots);
-    if (o.masked.empty()) memcpy(slots, got, o.end - o.slots);
-    else for (size_t i = 0; i < o.masked.size(); i++) if (got[i] >= 0) slots[i] = got[i];
+    for (size_t i = 0; i < o.masked.size(); i++) if (got[i] >= 0) slots[i] = got[i];
     if (nmatches) *nmatches = cnt[0];
     if (n_in_view) *n_in_view = cnt[1];
-    if (host) *host = h;
     return EORB_OK;
 }
 // a fused call on an empty frame: the projection ran, no matcher did
@@ -1554,31 +1569,17 @@ struct RansacLimit { int max; const char* name; };
 #define RANSAC_LIMIT(m) RansacLimit{m, #m}
 // what: the entry point's name in messages; the least N and min_inliers of a problem; the capacities
 struct RansacDesc { const char* what; int set_size, min_N, min_min_inliers; RansacLimit problems, corr, iters; };
-// a call's totals and its result region, contiguous and zero when the kernels start: the K records | inliers | the per-iteration aids in
-// the order given.  upload(): the call's last reservations, then A.upload(); download(): one copy, up to the aids or (when the caller
-// takes one) past them
-struct RansacAid { void* host; size_t bytes, off; };      // host: the caller's array or NULL; off: set by RansacCall::upload
+// a call's totals and its result region, contiguous and zero when the kernels start: the K records | inliers | the per-iteration aids,
+// which the entry point declares (A.out) between results() and upload().  upload(): the region's end, A.upload(), the memset
 struct RansacCall {
     size_t tN = 0, tI = 0; int max_N = 0, max_iters = 0;
-    size_t res = 0, inl = 0, end = 0, res_bytes = 0;
-    int upload(Arena& A, size_t record_bytes, RansacAid* aid, int n_aid)
+    size_t res = 0, inl = 0;
+    void results(Arena& A, void* records, size_t record_bytes, uint8_t* inliers) { res = A.out(records, record_bytes); inl = A.out(inliers, tN); }
+    int upload(Arena& A) const
     {
-        res_bytes = record_bytes;
-        res = A.reserve(res_bytes); inl = A.reserve(tN);
-        for (int i = 0; i < n_aid; i++) aid[i].off = A.reserve(aid[i].bytes);
-        end = A.reserve(0);
+        const size_t end = A.reserve(0);
         if (const int rc = A.upload()) return rc;
         EORB_HIP(A.c, hipMemsetAsync(A.dev<char>(res), 0, end - res, A.c->stream));
-        return EORB_OK;
-    }
-    int download(Arena& A, void* results, uint8_t* inliers, const RansacAid* aid, int n_aid) const
-    {
-        bool aids = false;
-        for (int i = 0; i < n_aid; i++) aids = aids || aid[i].host;
-        const char* h;
-        if (const int rc = A.download(res, (aids ? end : aid[0].off) - res, &h)) return rc;
-        memcpy(results, h + res, res_bytes); memcpy(inliers, h + inl, tN);
-        for (int i = 0; i < n_aid; i++) if (aid[i].host) memcpy(aid[i].host, h + aid[i].off, aid[i].bytes);
         return EORB_OK;
     }
 };
@@ -1652,7 +1653,7 @@ static int proj_last_common(eorb_ctx* c,
                          A.dev<uint8_t>(o_va), A.dev<float>(o_f3), A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob),
                          q_ur ? A.dev<float>(o_qur) : nullptr, th, mode, checkOri, dist_th, A.dev<int32_t>(r.slots), A.dev<int32_t>(r.nm)};
     if ((rc = search_proj_last_dev(c, P))) return rc;
-    return result_out(A, r, r.end, cur_mp, nmatches);
+    return result_out(A, r, cur_mp, nmatches);
 }
 
 int eorb_search_by_projection_last(eorb_ctx* c,
@@ -1722,7 +1723,7 @@ static int proj_map_common(eorb_ctx* c,
                         A.dev<uint8_t>(o_md), A.dev<uint8_t>(o_ob), mp_is_orb ? A.dev<uint8_t>(o_mo) : nullptr,
                         proj_xr ? A.dev<float>(o_qur) : nullptr, th, nnratio, A.dev<int32_t>(r.slots), A.dev<int32_t>(r.nm)};
     if ((rc = search_proj_map_dev(c, P))) return rc;
-    return result_out(A, r, r.end, frame_mp, nmatches);
+    return result_out(A, r, frame_mp, nmatches);
 }
 
 int eorb_search_by_projection_map(eorb_ctx* c,
@@ -1778,14 +1779,14 @@ static ProjView view_dev(const Arena& A, const eorb_view* v, const ViewOff& o)  
 }
 
 // the arena regions of one view's eorb_frustum_out, contiguous in the struct's order; then the matcher's records
-struct FrustumOff { size_t iv, xy, xr, lv, vc, dp, ls, rs, end, rec, srch; };
-static FrustumOff frustum_reserve(Arena& A, int M)
+struct FrustumOff { size_t iv, xy, xr, lv, vc, dp, ls, rs, rec, srch; };
+static FrustumOff frustum_reserve(Arena& A, int M, const eorb_frustum_out* out)      // out: the view's record, or NULL (nothing of it is taken)
 {
     const size_t m = (size_t)M;
+    const eorb_frustum_out d = out ? *out : eorb_frustum_out{};
     FrustumOff o;
-    o.iv = A.reserve(m); o.xy = A.reserve(8 * m); o.xr = A.reserve(4 * m); o.lv = A.reserve(4 * m); o.vc = A.reserve(4 * m);
-    o.dp = A.reserve(4 * m); o.ls = A.reserve(4 * m); o.rs = A.reserve(m);
-    o.end = A.total;
+    o.iv = A.out(d.in_view, m); o.xy = A.out(d.proj_xy, 8 * m); o.xr = A.out(d.proj_xr, 4 * m); o.lv = A.out(d.level, 4 * m); o.vc = A.out(d.view_cos, 4 * m);
+    o.dp = A.out(d.depth, 4 * m); o.ls = A.out(d.level_scale, 4 * m); o.rs = A.out(d.reason, m);
     return o;
 }
 static void frustum_reserve_recs(Arena& A, int M, FrustumOff& o) { o.rec = A.reserve(16 * (size_t)M); o.srch = A.reserve((size_t)M); }
@@ -1793,18 +1794,6 @@ static FrustumDev frustum_dev(const Arena& A, const FrustumOff& o)
 {
     return FrustumDev{A.dev<uint8_t>(o.iv), A.dev<float2>(o.xy), A.dev<float>(o.xr), A.dev<int32_t>(o.lv), A.dev<float>(o.vc),
                       A.dev<float>(o.dp), A.dev<float>(o.ls), A.dev<uint8_t>(o.rs), A.dev<float4>(o.rec), A.dev<uint8_t>(o.srch)};
-}
-static void frustum_copy_out(const char* h, const FrustumOff& o, int M, const eorb_frustum_out& out)
-{
-    const size_t m = (size_t)M;
-    if (out.in_view) memcpy(out.in_view, h + o.iv, m);
-    if (out.proj_xy) memcpy(out.proj_xy, h + o.xy, 8 * m);
-    if (out.proj_xr) memcpy(out.proj_xr, h + o.xr, 4 * m);
-    if (out.level) memcpy(out.level, h + o.lv, 4 * m);
-    if (out.view_cos) memcpy(out.view_cos, h + o.vc, 4 * m);
-    if (out.depth) memcpy(out.depth, h + o.dp, 4 * m);
-    if (out.level_scale) memcpy(out.level_scale, h + o.ls, 4 * m);
-    if (out.reason) memcpy(out.reason, h + o.rs, m);
 }
 
 // the points of modes A, B and C and their arena offsets (is_orb: per map point, or per query keypoint in mode B)
@@ -1869,18 +1858,15 @@ int eorb_project_frustum(eorb_ctx* c, const eorb_view* views, int nviews, int M,
     Arena A(c);
     const PointsOff po = points_in(A, M, pos, normal, min_dist, max_dist, skip, mp_is_orb);
     ViewOff vo[2] = {view_in(A, views), nviews > 1 ? view_in(A, views + 1) : ViewOff{0, 0}};
-    // outputs, contiguous: n_in_view | view 0 | view 1; then the matcher records (not downloaded)
-    const size_t o_n = A.reserve(16);
+    // outputs: n_in_view | view 0 | view 1; then the matcher records (device only)
+    const size_t o_n = A.out(nullptr, 16);
+    A.inout(n_in_view, o_n, sizeof(int32_t));
     FrustumOff fo[2];
-    for (int v = 0; v < nviews; v++) fo[v] = frustum_reserve(A, M);
+    for (int v = 0; v < nviews; v++) fo[v] = frustum_reserve(A, M, out ? out + v : nullptr);
     for (int v = 0; v < nviews; v++) frustum_reserve_recs(A, M, fo[v]);
     if ((rc = A.upload())) return rc;
     if ((rc = project_frustum_dev(c, frustum_args(A, views, nviews, vo, fo, M, po, cos_limit, 0, 0.f, A.dev<int32_t>(o_n))))) return rc;
-    const char* h;
-    if ((rc = A.download(o_n, fo[nviews - 1].end - o_n, &h))) return rc;
-    if (out) for (int v = 0; v < nviews; v++) frustum_copy_out(h, fo[v], M, out[v]);
-    if (n_in_view) *n_in_view = *(const int32_t*)(h + o_n);
-    return EORB_OK;
+    return A.fetch();
 }
 
 static int last_octave_check(eorb_ctx* c, const char* who, const eorb_view* v, const eorb_keypoint* kps, const uint8_t* is_orb, int n)
@@ -1910,24 +1896,16 @@ int eorb_project_last_frame(eorb_ctx* c, const eorb_view* view, const eorb_camer
     const PointsOff po = points_in(A, n, pos, nullptr, nullptr, nullptr, skip, last_is_orb);
     const size_t o_k = A.in(last_kps, sizeof(eorb_keypoint) * m);
     const ViewOff vo = view_in(A, view);
-    // outputs, contiguous: valid | uv | proj_ur | level_scale | uv_r; then the matcher's record
+    // outputs: valid | uv | proj_ur | level_scale | uv_r; then the matcher's record
     PoseOff o{};
-    o.va = A.reserve(m); o.uv = A.reserve(8 * m); o.ur = A.reserve(4 * m); o.ls = A.reserve(4 * m); o.uvr = A.reserve(8 * m);
-    const size_t o_end = A.total;
+    o.va = A.out(valid, m); o.uv = A.out(uv, 8 * m); o.ur = A.out(proj_ur, 4 * m); o.ls = A.out(level_scale, 4 * m); o.uvr = A.out(uv_r, 8 * m);
     o.rec = A.reserve(12 * m);
     if ((rc = A.upload())) return rc;
     LastArgs L = last_args(A, view, vo, n, po, A.dev<eorb_keypoint>(o_k), o);
     L.has_r = Trl ? 1 : 0;
     if (Trl) { L.cam_r = warp_cam_of(*cam_r); memcpy(L.Trl, Trl, sizeof(L.Trl)); }
     if ((rc = project_last_dev(c, L))) return rc;
-    const char* h;
-    if ((rc = A.download(o.va, o_end - o.va, &h))) return rc;
-    if (valid) memcpy(valid, h + o.va, m);
-    if (uv) memcpy(uv, h + o.uv, 8 * m);
-    if (proj_ur) memcpy(proj_ur, h + o.ur, 4 * m);
-    if (level_scale) memcpy(level_scale, h + o.ls, 4 * m);
-    if (uv_r) memcpy(uv_r, h + o.uvr, 8 * m);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_project_keyframe_points(eorb_ctx* c, const eorb_view* view, int n, const float* pos, const float* min_dist,
@@ -1944,21 +1922,13 @@ int eorb_project_keyframe_points(eorb_ctx* c, const eorb_view* view, int n, cons
     Arena A(c);
     const PointsOff po = points_in(A, n, pos, nullptr, min_dist, max_dist, skip, mp_is_orb);
     const ViewOff vo = view_in(A, view);
-    // outputs, contiguous: valid | uv | level | level_scale | dist3d; then the matcher's record
+    // outputs: valid | uv | level | level_scale | dist3d; then the matcher's record
     PoseOff o{};
-    o.va = A.reserve(m); o.uv = A.reserve(8 * m); o.lv = A.reserve(4 * m); o.ls = A.reserve(4 * m); o.d3 = A.reserve(4 * m);
-    const size_t o_end = A.total;
+    o.va = A.out(valid, m); o.uv = A.out(uv, 8 * m); o.lv = A.out(level, 4 * m); o.ls = A.out(level_scale, 4 * m); o.d3 = A.out(dist3d, 4 * m);
     o.rec = A.reserve(12 * m);
     if ((rc = A.upload())) return rc;
     if ((rc = project_kf_dev(c, kf_args(A, view, vo, n, po, o)))) return rc;
-    const char* h;
-    if ((rc = A.download(o.va, o_end - o.va, &h))) return rc;
-    if (valid) memcpy(valid, h + o.va, m);
-    if (uv) memcpy(uv, h + o.uv, 8 * m);
-    if (level) memcpy(level, h + o.lv, 4 * m);
-    if (level_scale) memcpy(level_scale, h + o.ls, 4 * m);
-    if (dist3d) memcpy(dist3d, h + o.d3, 4 * m);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_search_local_points(eorb_ctx* c,
@@ -1984,9 +1954,9 @@ int eorb_search_local_points(eorb_ctx* c,
     const size_t o_md = A.in(mp_desc, 32 * (size_t)M), o_ob = A.in(mp_obs, M);
     const PointsOff po = points_in(A, M, pos, normal, min_dist, max_dist, skip, mp_is_orb);
     const ViewOff vo = view_in(A, view);
-    // outputs, contiguous: {nmatches, n_in_view} | slots (in/out) | the projection arrays
+    // outputs: {nmatches, n_in_view} | slots (in/out) | the projection arrays
     const ResultOff r = result_in(A, frame_mp, n);
-    FrustumOff fo = frustum_reserve(A, M);
+    FrustumOff fo = frustum_reserve(A, M, out);
     frustum_reserve_recs(A, M, fo);
     if ((rc = A.upload())) return rc;
     const FrustumArgs F = frustum_args(A, view, 1, &vo, &fo, M, po, cos_limit, bFarPoints != 0, thFarPoints, A.dev<int32_t>(r.nm) + 1);
@@ -1997,10 +1967,7 @@ int eorb_search_local_points(eorb_ctx* c,
         rc = search_proj_map_dev(c, P);
     } else rc = result_no_matches(c, A, r);
     if (rc) return rc;
-    const char* h;
-    if ((rc = result_out(A, r, out ? fo.end : r.end, frame_mp, nmatches, n_in_view, &h))) return rc;
-    if (out) frustum_copy_out(h, fo, M, *out);
-    return EORB_OK;
+    return result_out(A, r, frame_mp, nmatches, n_in_view);
 }
 
 int eorb_search_local_points_fisheye(eorb_ctx* c,
@@ -2029,17 +1996,14 @@ int eorb_search_local_points_fisheye(eorb_ctx* c,
     const ViewOff vo[2] = {view_in(A, views), view_in(A, views + 1)};
     const ResultOff r = result_in(A, frame_mp, nT);
     FrustumOff fo[2];
-    for (int v = 0; v < 2; v++) fo[v] = frustum_reserve(A, M);
+    for (int v = 0; v < 2; v++) fo[v] = frustum_reserve(A, M, out ? out + v : nullptr);
     for (int v = 0; v < 2; v++) frustum_reserve_recs(A, M, fo[v]);
     if ((rc = A.upload())) return rc;
     const FrustumArgs F = frustum_args(A, views, 2, vo, fo, M, po, cos_limit, bFarPoints != 0, thFarPoints, A.dev<int32_t>(r.nm) + 1);
     if ((rc = project_frustum_dev(c, F))) return rc;
     const CamQuery Q[2] = {{F.O[0].search, F.O[0].rec, F.O[0].level}, {F.O[1].search, F.O[1].rec, F.O[1].level}};
     if ((rc = nT > 0 ? twocam_walk_dev(c, 0, twocam_args(A, fr, gb, M, o_md, o_ob, th, r, Q, nnratio)) : result_no_matches(c, A, r))) return rc;
-    const char* h;
-    if ((rc = result_out(A, r, out ? fo[1].end : r.end, frame_mp, nmatches, n_in_view, &h))) return rc;
-    if (out) for (int v = 0; v < 2; v++) frustum_copy_out(h, fo[v], M, out[v]);
-    return EORB_OK;
+    return result_out(A, r, frame_mp, nmatches, n_in_view);
 }
 
 // modes B and C in front of the last-frame matcher.  kf: the semantics of eorb_search_by_projection_kf (query level = the predicted
@@ -2069,11 +2033,10 @@ static int proj_pose_common(eorb_ctx* c, const char* who, bool kf,
     const size_t o_md = A.in(mp_desc, 32 * m), o_ob = A.in(kf ? obs.data() : mp_obs, m);
     const PointsOff po = points_in(A, nq, pos, nullptr, min_dist, max_dist, skip, q_is_orb);
     const ViewOff vo = view_in(A, view);
-    // outputs, contiguous: nmatches | slots (in/out) | valid | uv | level; then what only the matcher reads
+    // outputs: nmatches | slots (in/out) | valid | uv | level; then what only the matcher reads
     const ResultOff r = result_in(A, cur_mp, n_cur, kf);
     PoseOff o{};
-    o.va = A.reserve(m); o.uv = A.reserve(8 * m); o.lv = A.reserve(4 * m);
-    const size_t o_end = A.total;
+    o.va = A.out(valid, m); o.uv = A.out(uv, 8 * m); o.lv = A.out(level, 4 * m);
     o.ls = A.reserve(4 * m); o.ur = o.d3 = A.reserve(4 * m); o.uvr = A.reserve(8 * m); o.rec = A.reserve(12 * m);      // (ur, d3: one region, by mode)
     const size_t o_q2 = A.reserve(sizeof(eorb_keypoint) * m);
     if ((rc = A.upload())) return rc;
@@ -2092,12 +2055,7 @@ static int proj_pose_common(eorb_ctx* c, const char* who, bool kf,
         rc = search_proj_last_dev(c, P);
     } else rc = result_no_matches(c, A, r);
     if (rc) return rc;
-    const char* h;
-    if ((rc = result_out(A, r, (valid || uv || level) ? o_end : r.end, cur_mp, nmatches, nullptr, &h))) return rc;
-    if (valid) memcpy(valid, h + o.va, m);
-    if (uv) memcpy(uv, h + o.uv, 8 * m);
-    if (level) memcpy(level, h + o.lv, 4 * m);
-    return EORB_OK;
+    return result_out(A, r, cur_mp, nmatches);
 }
 
 int eorb_search_by_projection_last_pose(eorb_ctx* c,
@@ -2139,11 +2097,14 @@ int eorb_frame_fisheye(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRigh
     fe_enter(c);
     Arena A(c);
     const size_t o_imL = image_in(A, imLeft, W, H, stride, false), o_imR = image_in(A, imRight, W, H, stride, false);
-    // outputs, contiguous: the result block of the pair | candidates | distances; then the knn scratch
-    const ExtractOff X = extract_reserve(A, c->orb.max_out, 2);
+    // outputs: the result block of the pair | candidates | distances (n[0] of each, copied after the checks); then the knn scratch
+    const ExtractDst dst[2] = {{kpsL, descL, nullptr, nL, monoLeft}, {kpsR, descR, nullptr, nR, monoRight}};
+    const ExtractOff X = extract_reserve(A, c->orb.max_out, 2, cap, dst);
     const size_t mo = X.mo;
-    const size_t o_cand = A.reserve(sizeof(int32_t) * mo), o_d2 = A.reserve(2 * sizeof(int32_t) * mo);
-    const size_t o_end = A.reserve(0);
+    const size_t o_cand = A.out(nullptr, sizeof(int32_t) * mo), o_d2 = A.out(nullptr, 2 * sizeof(int32_t) * mo);
+    if (right_idx) A.want(o_cand, sizeof(int32_t) * X.ncopy);
+    if (dist2) A.want(o_d2, 2 * sizeof(int32_t) * X.ncopy);
+    A.reserve(0);                                        // (an empty region; tests/golden/arena_layout.json pins the layout)
     const size_t o_idx = A.reserve(2 * sizeof(int32_t) * mo), o_kd = A.reserve(2 * sizeof(int32_t) * mo);
     if ((rc = A.upload())) return rc;
     ExtractHead* hd = A.dev<ExtractHead>(X.head);
@@ -2158,8 +2119,7 @@ int eorb_frame_fisheye(eorb_ctx* c, const uint8_t* imLeft, const uint8_t* imRigh
     if ((rc = fisheye_lowe_dev(c, A.dev<uint8_t>(X.desc), A.dev<uint8_t>(X.desc) + 32 * mo, (int)mo, hd->n, A.dev<int32_t>(o_idx), A.dev<int32_t>(o_kd),
                                A.dev<int32_t>(o_cand), A.dev<int32_t>(o_d2)))) return rc;
     const char* h;
-    if ((rc = A.download(X.head, o_end - X.head, &h))) return rc;
-    const ExtractDst dst[2] = {{kpsL, descL, nullptr, nL, monoLeft}, {kpsR, descR, nullptr, nR, monoRight}};
+    if ((rc = A.fetch(&h))) return rc;
     const ExtractHead* got;
     if ((rc = extract_out(c, "eorb_frame_fisheye", h, X, cap, 2, dst, &got))) return rc;
     if (right_idx && got->n[0] > 0) memcpy(right_idx, h + o_cand, sizeof(int32_t) * (size_t)got->n[0]);
@@ -2204,7 +2164,7 @@ int eorb_search_by_projection_map_fisheye(eorb_ctx* c,
     const CamQuery Q[2] = {{A.dev<uint8_t>(o_iv), A.dev<float4>(o_f4), A.dev<int32_t>(o_lv)},
                            {A.dev<uint8_t>(o_ivr), A.dev<float4>(o_f4) + M, A.dev<int32_t>(o_lvr)}};
     if ((rc = twocam_walk_dev(c, 0, twocam_args(A, fr, gb, M, o_md, o_ob, th, r, Q, nnratio)))) return rc;
-    return result_out(A, r, r.end, frame_mp, nmatches);
+    return result_out(A, r, frame_mp, nmatches);
 }
 
 int eorb_search_by_projection_last_fisheye(eorb_ctx* c,
@@ -2240,7 +2200,7 @@ int eorb_search_by_projection_last_fisheye(eorb_ctx* c,
     T.valid = A.dev<uint8_t>(o_va); T.quv = A.dev<float>(o_f5); T.qkps = A.dev<eorb_keypoint>(o_lk); T.mode = mode; T.checkOri = checkOri;
     T.rec = A.dev<int32_t>(o_rec);
     if ((rc = twocam_walk_dev(c, 1, T))) return rc;
-    return result_out(A, r, r.end, cur_mp, nmatches);
+    return result_out(A, r, cur_mp, nmatches);
 }
 
 // ---- the node walks (SearchByBoW, SearchForTriangulation) over K keyframes per call (eorb_kf_set of include/eorb_fe.h); the single-pair
@@ -2346,8 +2306,8 @@ static void kfbatch_clear(int K, int n, int32_t* out, int32_t* nmatches)
 }
 
 // ---- CreateNewMapPoints (newpts.hip): the stage as a part of a call.  check() reads the arguments, queue() / reserve() lay its inputs and
-// its results out in the call's arena (the results right behind whatever the call reserved before: one download covers both), launch()
-// enqueues the kernels on a match12 that is already on the device, copy_out() hands the landing buffer to the caller's arrays ----
+// its results out in the call's arena (the results right behind whatever the call declared before: the call's one fetch covers both),
+// launch() enqueues the kernels on a match12 that is already on the device ----
 static void np_clear(int K, int n1, const eorb_newpts_out* O)
 {
     const size_t n = (size_t)K * n1;
@@ -2446,7 +2406,8 @@ struct NpJob {
     void reserve(Arena& A)
     {
         const size_t n = (size_t)K * n1;
-        o_st = A.reserve(n); o_x = A.reserve(12 * n); o_br = A.reserve(n); o_cs = A.reserve(4 * n); o_nn = A.reserve(4 * (size_t)K); o_end = A.reserve(0);
+        o_st = A.out(O->status, n); o_x = A.out(O->x3d, 12 * n); o_br = A.out(O->branch, n); o_cs = A.out(O->cos_parallax, 4 * n); o_nn = A.out(O->n_new, 4 * (size_t)K);
+        o_end = A.reserve(0);
         o_tmp = A.reserve(2 * n); o_ps = A.reserve(4);
     }
     int launch(eorb_ctx* c, const Arena& A, const eorb_keypoint* d_kps1, const eorb_keypoint* d_kps2, const int32_t* d_match12)
@@ -2469,34 +2430,24 @@ struct NpJob {
         T.status = A.dev<uint8_t>(o_st); T.x3d = A.dev<float>(o_x); T.branch = A.dev<uint8_t>(o_br); T.cosp = A.dev<float>(o_cs); T.n_new = A.dev<int32_t>(o_nn);
         return new_map_points_dev(c, T);
     }
-    void copy_out(const char* h) const
-    {
-        const size_t n = (size_t)K * n1;
-        memcpy(O->status, h + o_st, n);
-        if (O->x3d) memcpy(O->x3d, h + o_x, 12 * n);
-        if (O->branch) memcpy(O->branch, h + o_br, n);
-        if (O->cos_parallax) memcpy(O->cos_parallax, h + o_cs, 4 * n);
-        memcpy(O->n_new, h + o_nn, 4 * (size_t)K);
-    }
 };
 
-// outputs of a batched walk, contiguous: [K x (32 histogram bins + nmatches) | K x n matches]; then the rotation bins
+// outputs of a batched walk: [K x (32 histogram bins + nmatches) | K x n matches]; then the rotation bins.  The counts sit one to a
+// histogram row: kfbatch_out picks them out of the host view
 struct KfBatchOut { size_t o_hist, o_m, o_bin; };
-static KfBatchOut kfbatch_reserve(Arena& A, int K, int n)
+static KfBatchOut kfbatch_reserve(Arena& A, int K, int n, int32_t* out, const int32_t* nmatches)
 {
     KfBatchOut o;
-    o.o_hist = A.reserve(sizeof(int32_t) * kPairHist * (size_t)K); o.o_m = A.reserve(sizeof(int32_t) * (size_t)K * n); o.o_bin = A.reserve((size_t)K * n);
+    o.o_hist = A.out(nullptr, sizeof(int32_t) * kPairHist * (size_t)K); o.o_m = A.out(out, sizeof(int32_t) * (size_t)K * n); o.o_bin = A.reserve((size_t)K * n);
+    if (nmatches) A.want(o.o_hist, sizeof(int32_t) * kPairHist * (size_t)K);
     return o;
 }
-// np: the call went on with the triangulation stage, whose results lie behind these (NpJob::reserve)
-static int kfbatch_out(Arena& A, const KfBatchOut& o, int K, int n, int32_t* out, int32_t* nmatches, const NpJob* np = nullptr)
+// the call's fetch (a triangulation stage behind the walk has registered its results: NpJob::reserve)
+static int kfbatch_out(Arena& A, const KfBatchOut& o, int K, int32_t* nmatches)
 {
     const char* h;
-    int rc;
-    if ((rc = A.download(o.o_hist, (np ? np->o_end : o.o_m + sizeof(int32_t) * (size_t)K * n) - o.o_hist, &h))) return rc;
-    memcpy(out, h + o.o_m, sizeof(int32_t) * (size_t)K * n);
+    if (const int rc = A.fetch(&h)) return rc;
     if (nmatches) for (int k = 0; k < K; k++) memcpy(nmatches + k, h + o.o_hist + sizeof(int32_t) * ((size_t)k * kPairHist + 32), 4);
-    if (np) np->copy_out(h);
     return EORB_OK;
 }
 
@@ -2550,7 +2501,7 @@ static int search_tri_common(eorb_ctx* c, const char* what,
     J.queue(A, S, false);
     const size_t o_p = A.in(P.data(), sizeof(TriPair) * (size_t)K), o_q = kb ? A.in(Q.data(), sizeof(TriKbPair) * (size_t)K) : 0;
     if (np) np->queue(A);
-    const KfBatchOut o = kfbatch_reserve(A, K, n1);
+    const KfBatchOut o = kfbatch_reserve(A, K, n1, match12, nmatches);
     if (np) np->reserve(A);
     if ((rc = A.upload())) return rc;
     TriBatchArgs B{};
@@ -2569,10 +2520,9 @@ static int search_tri_common(eorb_ctx* c, const char* what,
         KB.K = *kb; KB.kf = B.kf; KB.pair = B.pair; KB.kb = A.dev<TriKbPair>(o_q); KB.nk = K;
     }
     if ((rc = search_tri_batch_dev(c, what, B, kb ? &KB : nullptr))) return rc;
-    if (!np) return kfbatch_out(A, o, K, n1, match12, nmatches);
     // the stage on the rows where they are; one copy brings both halves' results back
-    if ((rc = np->launch(c, A, T.kps1, T.kps2, T.match12))) return rc;
-    return kfbatch_out(A, o, K, n1, match12, nmatches, np);
+    if (np && (rc = np->launch(c, A, T.kps1, T.kps2, T.match12))) return rc;
+    return kfbatch_out(A, o, K, nmatches);
 }
 
 // the cameras of a KannalaBrandt8 walk into its block: pKF1's must be KannalaBrandt8, the other side's Pinhole or KannalaBrandt8
@@ -2670,10 +2620,7 @@ int eorb_new_map_points(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const eo
     J.reserve(A);
     if ((rc = A.upload())) return rc;
     if ((rc = J.launch(c, A, A.dev<eorb_keypoint>(o_k1), A.dev<eorb_keypoint>(o_k2), A.dev<int32_t>(o_m)))) return rc;
-    const char* h;
-    if ((rc = A.download(J.o_st, J.o_end - J.o_st, &h))) return rc;
-    J.copy_out(h);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_create_new_map_points(eorb_ctx* c,
@@ -2759,7 +2706,7 @@ static int bow_common(eorb_ctx* c, const char* what, const char* prof, int kf_kf
     const size_t o_k1 = A.in(kps1, sizeof(eorb_keypoint) * n1), o_d1 = A.in(desc1, 32 * (size_t)n1);
     const size_t o_f1 = kf_kf ? A.in(flag1, n1) : 0;
     I.queue(A, S, true);
-    const KfBatchOut o = kfbatch_reserve(A, K, n1);
+    const KfBatchOut o = kfbatch_reserve(A, K, n1, out, nmatches);
     const int nscratch = kf_kf ? I.ntotal : 0;                          // vbMatched2 of every pair
     const size_t o_scr = A.reserve(sizeof(int32_t) * (size_t)nscratch);
     if ((rc = A.upload())) return rc;
@@ -2771,7 +2718,7 @@ static int bow_common(eorb_ctx* c, const char* what, const char* prof, int kf_kf
     else B.A = BowArgs{sk, sd, sf, I.fv(A), k1, n1, d1, f1.fv(A), m, A.dev<int8_t>(o.o_bin), hist, hist + 32, nnratio, checkOri, 0, sf, nullptr, 0};
     B.kf = A.dev<KfSlice>(I.o_sl); B.K = K; B.n_out = n1; B.max_nn = kf_kf ? nn1 : I.max_nn;
     if ((rc = search_bow_batch_dev(c, prof, B, kf_kf ? scr : nullptr, nscratch, nL))) return rc;
-    return kfbatch_out(A, o, K, n1, out, nmatches);
+    return kfbatch_out(A, o, K, nmatches);
 }
 
 int eorb_search_by_bow_keyframes(eorb_ctx* c, const eorb_kf_set* set,
@@ -2939,6 +2886,54 @@ static int tv_check_matches(eorb_ctx* c, const char* what, const int32_t* match1
             return set_err(c, EORB_E_ARG, "%s: match %d = (%d, %d) is outside the %d / %d keys", what, i, match12[2 * i], match12[2 * i + 1], n1, n2);
     return EORB_OK;
 }
+static int tv_check_sets(eorb_ctx* c, const char* what, const int32_t* sets, int iters, int N)
+{
+    for (int i = 0; i < 8 * iters; i++)
+        if (sets[i] < 0 || sets[i] >= N) return set_err(c, EORB_E_ARG, "%s: set %d holds the index %d of %d matches", what, i / 8, sets[i], N);
+    return EORB_OK;
+}
+// vP3D / vbGood / vbTriangulated are indexed by `first`: with one first index in two matches their values would depend on the order of the writes
+static int tv_check_first_once(eorb_ctx* c, const char* what, const int32_t* match12, int N, int n1)
+{
+    std::vector<uint8_t> seen((size_t)n1, 0);
+    for (int i = 0; i < N; i++) {
+        if (seen[match12[2 * i]]) return set_err(c, EORB_E_ARG, "%s: two matches have the first index %d", what, match12[2 * i]);
+        seen[match12[2 * i]] = 1;
+    }
+    return EORB_OK;
+}
+
+// the H / F RANSAC as a part of a call (eorb_two_view_ransac, and the first stage of eorb_two_view_reconstruct): its inputs, its own space
+// and its results: the 22 words | inliers_h | inliers_f | the per-iteration aids.  dst: who takes the arrays (any may be NULL); the 22
+// words are read through the host view (tv_ransac_reserve's want: only when the caller takes them)
+struct TvRansacDst { uint8_t* inliers_h; uint8_t* inliers_f; float* it_score_h; float* it_score_f; float* it_H; float* it_F; };
+struct TvRansacOff { size_t p1, p2, m, s, n1, n2, hdr, hyp, inl, res, ih, inf, sh, sf, ith, itf; };
+static TvRansacOff tv_ransac_reserve(Arena& A, const std::vector<float>& p1, const std::vector<float>& p2, const int32_t* match12, int N, const int32_t* sets,
+                                     int iters, bool words, const TvRansacDst& d)
+{
+    const size_t sN = (size_t)N, sI = (size_t)iters;
+    TvRansacOff o;
+    o.p1 = A.in(p1.data(), sizeof(float) * p1.size()); o.p2 = A.in(p2.data(), sizeof(float) * p2.size());
+    o.m = A.in(match12, sizeof(int32_t) * 2 * sN); o.s = A.in(sets, sizeof(int32_t) * 8 * sI);
+    o.n1 = A.reserve(sizeof(float) * p1.size()); o.n2 = A.reserve(sizeof(float) * p2.size());
+    o.hdr = A.reserve(sizeof(float) * kTvHdrFloats); o.hyp = A.reserve(sizeof(float) * kTvHypFloats * 2 * sI); o.inl = A.reserve(2 * sI * sN);
+    o.res = A.out(nullptr, sizeof(float) * 22); o.ih = A.out(d.inliers_h, sN); o.inf = A.out(d.inliers_f, sN);
+    o.sh = A.out(d.it_score_h, sizeof(float) * sI); o.sf = A.out(d.it_score_f, sizeof(float) * sI);
+    o.ith = A.out(d.it_H, sizeof(float) * 9 * sI); o.itf = A.out(d.it_F, sizeof(float) * 9 * sI);
+    if (words) A.want(o.res, sizeof(float) * 22);
+    return o;
+}
+static TvRansacArgs tv_ransac_args(const Arena& A, const TvRansacOff& o, int n1, int n2, int N, int iters, float sigma, float th_score, float th_f)
+{
+    TvRansacArgs T{};
+    T.pts1 = A.dev<float2>(o.p1); T.pts2 = A.dev<float2>(o.p2); T.n1 = n1; T.n2 = n2;
+    T.match12 = A.dev<int32_t>(o.m); T.N = N; T.sets = A.dev<int32_t>(o.s); T.iters = iters;
+    T.sigma = sigma; T.th_score = th_score; T.th_f = th_f;
+    T.pn1 = A.dev<float2>(o.n1); T.pn2 = A.dev<float2>(o.n2); T.hdr = A.dev<float>(o.hdr); T.hyp = A.dev<float>(o.hyp); T.inl = A.dev<uint8_t>(o.inl);
+    T.res = A.dev<float>(o.res); T.inliers_h = A.dev<uint8_t>(o.ih); T.inliers_f = A.dev<uint8_t>(o.inf);
+    T.it_score_h = A.dev<float>(o.sh); T.it_score_f = A.dev<float>(o.sf); T.it_H = A.dev<float>(o.ith); T.it_F = A.dev<float>(o.itf);
+    return T;
+}
 
 int eorb_two_view_ransac(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2, const int32_t* match12, int N,
         const int32_t* sets, int iters, const eorb_tvr_params* params,
@@ -2955,41 +2950,19 @@ int eorb_two_view_ransac(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const e
     if ((rc = tv_check_sizes(c, what, n1, n2, N))) return rc;
     if (iters > EORB_TVR_MAX_ITERS) return set_err(c, EORB_E_CAPACITY, "%s: %d iterations, at most EORB_TVR_MAX_ITERS = %d", what, iters, EORB_TVR_MAX_ITERS);
     if ((rc = tv_check_matches(c, what, match12, N, n1, n2))) return rc;
-    for (int i = 0; i < 8 * iters; i++)
-        if (sets[i] < 0 || sets[i] >= N) return set_err(c, EORB_E_ARG, "%s: set %d holds the index %d of %d matches", what, i / 8, sets[i], N);
+    if ((rc = tv_check_sets(c, what, sets, iters, N))) return rc;
     fe_enter(c);
     const std::vector<float> p1 = tv_points(kps1, n1), p2 = tv_points(kps2, n2);
-    const size_t sN = (size_t)N, sI = (size_t)iters;
     Arena A(c);
-    const size_t o_p1 = A.in(p1.data(), sizeof(float) * p1.size()), o_p2 = A.in(p2.data(), sizeof(float) * p2.size());
-    const size_t o_m = A.in(match12, sizeof(int32_t) * 2 * sN), o_s = A.in(sets, sizeof(int32_t) * 8 * sI);
-    const size_t o_n1 = A.reserve(sizeof(float) * p1.size()), o_n2 = A.reserve(sizeof(float) * p2.size());
-    const size_t o_hdr = A.reserve(sizeof(float) * kTvHdrFloats), o_hyp = A.reserve(sizeof(float) * kTvHypFloats * 2 * sI), o_inl = A.reserve(2 * sI * sN);
-    // results, contiguous: the 22 words | inliers_h | inliers_f | the per-iteration aids
-    const size_t o_res = A.reserve(sizeof(float) * 22), o_ih = A.reserve(sN), o_if = A.reserve(sN);
-    const size_t o_sh = A.reserve(sizeof(float) * sI), o_sf = A.reserve(sizeof(float) * sI);
-    const size_t o_ith = A.reserve(sizeof(float) * 9 * sI), o_itf = A.reserve(sizeof(float) * 9 * sI);
+    const TvRansacOff o = tv_ransac_reserve(A, p1, p2, match12, N, sets, iters, true, TvRansacDst{inliers_h, inliers_f, it_score_h, it_score_f, it_H, it_F});
     if ((rc = A.upload())) return rc;
-    TvRansacArgs T{};
-    T.pts1 = A.dev<float2>(o_p1); T.pts2 = A.dev<float2>(o_p2); T.n1 = n1; T.n2 = n2;
-    T.match12 = A.dev<int32_t>(o_m); T.N = N; T.sets = A.dev<int32_t>(o_s); T.iters = iters;
-    T.sigma = params->sigma; T.th_score = params->th_score; T.th_f = params->th_f;
-    T.pn1 = A.dev<float2>(o_n1); T.pn2 = A.dev<float2>(o_n2); T.hdr = A.dev<float>(o_hdr); T.hyp = A.dev<float>(o_hyp); T.inl = A.dev<uint8_t>(o_inl);
-    T.res = A.dev<float>(o_res); T.inliers_h = A.dev<uint8_t>(o_ih); T.inliers_f = A.dev<uint8_t>(o_if);
-    T.it_score_h = A.dev<float>(o_sh); T.it_score_f = A.dev<float>(o_sf); T.it_H = A.dev<float>(o_ith); T.it_F = A.dev<float>(o_itf);
-    if ((rc = twoview_ransac_dev(c, T))) return rc;
-    const bool aids = it_score_h || it_score_f || it_H || it_F;
+    if ((rc = twoview_ransac_dev(c, tv_ransac_args(A, o, n1, n2, N, iters, params->sigma, params->th_score, params->th_f)))) return rc;
     const char* h;
-    if ((rc = A.download(o_res, (aids ? o_itf + sizeof(float) * 9 * sI : o_if + sN) - o_res, &h))) return rc;
-    const float* r = (const float*)(h + o_res);
+    if ((rc = A.fetch(&h))) return rc;
+    const float* r = (const float*)(h + o.res);
     *SH = r[0]; *SF = r[1];
     memcpy(best_it_h, r + 2, sizeof(int32_t)); memcpy(best_it_f, r + 3, sizeof(int32_t));
     memcpy(H21, r + 4, sizeof(float) * 9); memcpy(F21, r + 13, sizeof(float) * 9);
-    memcpy(inliers_h, h + o_ih, sN); memcpy(inliers_f, h + o_if, sN);
-    if (it_score_h) memcpy(it_score_h, h + o_sh, sizeof(float) * sI);
-    if (it_score_f) memcpy(it_score_f, h + o_sf, sizeof(float) * sI);
-    if (it_H) memcpy(it_H, h + o_ith, sizeof(float) * 9 * sI);
-    if (it_F) memcpy(it_F, h + o_itf, sizeof(float) * 9 * sI);
     return EORB_OK;
 }
 
@@ -3006,22 +2979,16 @@ int eorb_two_view_check_rt(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const
     if ((rc = tv_check_sizes(c, what, n1, n2, N))) return rc;
     if (Kp > EORB_TVR_MAX_POSES) return set_err(c, EORB_E_CAPACITY, "%s: %d poses, at most EORB_TVR_MAX_POSES = %d", what, Kp, EORB_TVR_MAX_POSES);
     if ((rc = tv_check_matches(c, what, match12, N, n1, n2))) return rc;
-    {   // vP3D / vbGood are indexed by `first`: with one first index in two matches their values would depend on the order of the writes
-        std::vector<uint8_t> seen((size_t)n1, 0);
-        for (int i = 0; i < N; i++) {
-            if (seen[match12[2 * i]]) return set_err(c, EORB_E_ARG, "%s: two matches have the first index %d", what, match12[2 * i]);
-            seen[match12[2 * i]] = 1;
-        }
-    }
+    if ((rc = tv_check_first_once(c, what, match12, N, n1))) return rc;
     fe_enter(c);
     const std::vector<float> p1 = tv_points(kps1, n1), p2 = tv_points(kps2, n2);
     const size_t sN = (size_t)N, sK = (size_t)Kp, s1 = (size_t)n1;
     Arena A(c);
     const size_t o_p1 = A.in(p1.data(), sizeof(float) * p1.size()), o_p2 = A.in(p2.data(), sizeof(float) * p2.size());
     const size_t o_m = A.in(match12, sizeof(int32_t) * 2 * sN), o_in = A.in(inliers, sN), o_po = A.in(poses, sizeof(eorb_tvr_pose) * sK);
-    // results, contiguous: n_good | cos_sel | good | p3d | cos_all
-    const size_t o_ng = A.reserve(sizeof(int32_t) * sK), o_cs = A.reserve(sizeof(float) * sK), o_g = A.reserve(sK * s1);
-    const size_t o_p3 = A.reserve(sizeof(float) * 3 * sK * s1), o_ca = A.reserve(sizeof(float) * sK * sN);
+    // results: n_good | cos_sel | good | p3d | cos_all
+    const size_t o_ng = A.out(n_good, sizeof(int32_t) * sK), o_cs = A.out(cos_sel, sizeof(float) * sK), o_g = A.out(good, sK * s1);
+    const size_t o_p3 = A.out(p3d, sizeof(float) * 3 * sK * s1), o_ca = A.out(cos_all, sizeof(float) * sK * sN);
     if ((rc = A.upload())) return rc;
     EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_g), 0, o_ca - o_g, c->stream));
     TvCheckRtArgs T{};
@@ -3030,12 +2997,7 @@ int eorb_two_view_check_rt(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const
     T.poses = A.dev<float>(o_po); T.Kp = Kp;
     T.n_good = A.dev<int32_t>(o_ng); T.cos_sel = A.dev<float>(o_cs); T.good = A.dev<uint8_t>(o_g); T.p3d = A.dev<float>(o_p3); T.cos_all = A.dev<float>(o_ca);
     if ((rc = twoview_check_rt_dev(c, T))) return rc;
-    const char* h;
-    if ((rc = A.download(o_ng, (cos_all ? o_ca + sizeof(float) * sK * sN : o_p3 + sizeof(float) * 3 * sK * s1) - o_ng, &h))) return rc;
-    memcpy(n_good, h + o_ng, sizeof(int32_t) * sK); memcpy(cos_sel, h + o_cs, sizeof(float) * sK);
-    memcpy(good, h + o_g, sK * s1); memcpy(p3d, h + o_p3, sizeof(float) * 3 * sK * s1);
-    if (cos_all) memcpy(cos_all, h + o_ca, sizeof(float) * sK * sN);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_two_view_reconstruct(eorb_ctx* c, const eorb_keypoint* kps1, int n1, const eorb_keypoint* kps2, int n2,
@@ -3053,44 +3015,24 @@ int eorb_two_view_reconstruct(eorb_ctx* c, const eorb_keypoint* kps1, int n1, co
     if ((rc = tv_check_sizes(c, what, n1, n2, N))) return rc;
     if (iters > EORB_TVR_MAX_ITERS) return set_err(c, EORB_E_CAPACITY, "%s: %d iterations, at most EORB_TVR_MAX_ITERS = %d", what, iters, EORB_TVR_MAX_ITERS);
     if ((rc = tv_check_matches(c, what, match12, N, n1, n2))) return rc;
-    for (int i = 0; i < 8 * iters; i++)
-        if (sets[i] < 0 || sets[i] >= N) return set_err(c, EORB_E_ARG, "%s: set %d holds the index %d of %d matches", what, i / 8, sets[i], N);
-    {   // vP3D / vbTriangulated are indexed by `first` (eorb_two_view_check_rt)
-        std::vector<uint8_t> seen((size_t)n1, 0);
-        for (int i = 0; i < N; i++) {
-            if (seen[match12[2 * i]]) return set_err(c, EORB_E_ARG, "%s: two matches have the first index %d", what, match12[2 * i]);
-            seen[match12[2 * i]] = 1;
-        }
-    }
+    if ((rc = tv_check_sets(c, what, sets, iters, N))) return rc;
+    if ((rc = tv_check_first_once(c, what, match12, N, n1))) return rc;
     fe_enter(c);
     const std::vector<float> p1 = tv_points(kps1, n1), p2 = tv_points(kps2, n2);
-    const size_t sN = (size_t)N, sI = (size_t)iters, s1 = (size_t)n1;
+    const size_t sN = (size_t)N, s1 = (size_t)n1;
     constexpr size_t kH = 8;                                       // CheckRT's launch: the 8 hypotheses of ReconstructH
     Arena A(c);
-    const size_t o_p1 = A.in(p1.data(), sizeof(float) * p1.size()), o_p2 = A.in(p2.data(), sizeof(float) * p2.size());
-    const size_t o_m = A.in(match12, sizeof(int32_t) * 2 * sN), o_s = A.in(sets, sizeof(int32_t) * 8 * sI);
-    // the RANSAC's own space and results, as in eorb_two_view_ransac
-    const size_t o_n1 = A.reserve(sizeof(float) * p1.size()), o_n2 = A.reserve(sizeof(float) * p2.size());
-    const size_t o_hdr = A.reserve(sizeof(float) * kTvHdrFloats), o_hyp = A.reserve(sizeof(float) * kTvHypFloats * 2 * sI), o_inl = A.reserve(2 * sI * sN);
-    const size_t o_rr = A.reserve(sizeof(float) * 22), o_ih = A.reserve(sN), o_if = A.reserve(sN);
-    const size_t o_sh = A.reserve(sizeof(float) * sI), o_sf = A.reserve(sizeof(float) * sI);
-    const size_t o_ith = A.reserve(sizeof(float) * 9 * sI), o_itf = A.reserve(sizeof(float) * 9 * sI);
+    const TvRansacOff o = tv_ransac_reserve(A, p1, p2, match12, N, sets, iters, false, TvRansacDst{});      // (its results stay on the device)
     const size_t o_sel = A.reserve(sN), o_ca = A.reserve(sizeof(float) * kH * sN);
     // zeroed, contiguous: the results that travel (res | R21 | t21 | trans_inliers | triangulated | p3d | hyp_poses), then CheckRT's for 8 poses
-    const size_t o_res = A.reserve(sizeof(eorb_tvr_recon_result)), o_R = A.reserve(sizeof(float) * 18), o_t = A.reserve(sizeof(float) * 6);
-    const size_t o_ti = A.reserve(sN), o_tri = A.reserve(2 * s1), o_p3 = A.reserve(sizeof(float) * 6 * s1);
-    const size_t o_po = A.reserve(sizeof(eorb_tvr_pose) * kH), o_nh = A.reserve(sizeof(int32_t));
+    const size_t o_res = A.out(res, sizeof(eorb_tvr_recon_result)), o_R = A.out(R21, sizeof(float) * 18), o_t = A.out(t21, sizeof(float) * 6);
+    const size_t o_ti = A.out(trans_inliers, sN), o_tri = A.out(triangulated, 2 * s1), o_p3 = A.out(p3d, sizeof(float) * 6 * s1);
+    const size_t o_po = A.out(hyp_poses, sizeof(eorb_tvr_pose) * kH), o_nh = A.reserve(sizeof(int32_t));
     const size_t o_ng = A.reserve(sizeof(int32_t) * kH), o_cs = A.reserve(sizeof(float) * kH), o_g = A.reserve(kH * s1);
     const size_t o_p8 = A.reserve(sizeof(float) * 3 * kH * s1), o_end = A.reserve(1);
     if ((rc = A.upload())) return rc;
     EORB_HIP(c, hipMemsetAsync(A.dev<char>(o_res), 0, o_end - o_res, c->stream));
-    TvRansacArgs T{};
-    T.pts1 = A.dev<float2>(o_p1); T.pts2 = A.dev<float2>(o_p2); T.n1 = n1; T.n2 = n2;
-    T.match12 = A.dev<int32_t>(o_m); T.N = N; T.sets = A.dev<int32_t>(o_s); T.iters = iters;
-    T.sigma = p->sigma; T.th_score = p->th_score; T.th_f = p->th_f;
-    T.pn1 = A.dev<float2>(o_n1); T.pn2 = A.dev<float2>(o_n2); T.hdr = A.dev<float>(o_hdr); T.hyp = A.dev<float>(o_hyp); T.inl = A.dev<uint8_t>(o_inl);
-    T.res = A.dev<float>(o_rr); T.inliers_h = A.dev<uint8_t>(o_ih); T.inliers_f = A.dev<uint8_t>(o_if);
-    T.it_score_h = A.dev<float>(o_sh); T.it_score_f = A.dev<float>(o_sf); T.it_H = A.dev<float>(o_ith); T.it_F = A.dev<float>(o_itf);
+    const TvRansacArgs T = tv_ransac_args(A, o, n1, n2, N, iters, p->sigma, p->th_score, p->th_f);
     TvReconArgs D{};
     D.rres = T.res; D.inliers_h = T.inliers_h; D.inliers_f = T.inliers_f; D.N = N; D.n1 = n1;
     memcpy(D.K, K, sizeof D.K); D.p = *p;
@@ -3104,13 +3046,7 @@ int eorb_two_view_reconstruct(eorb_ctx* c, const eorb_keypoint* kps1, int n1, co
     Q.poses = D.poses; Q.Kp = (int)kH; Q.Kp_dev = D.n_hyp;
     Q.n_good = A.dev<int32_t>(o_ng); Q.cos_sel = A.dev<float>(o_cs); Q.good = A.dev<uint8_t>(o_g); Q.p3d = A.dev<float>(o_p8); Q.cos_all = A.dev<float>(o_ca);
     if ((rc = twoview_reconstruct_dev(c, T, D, Q))) return rc;
-    const char* h;
-    if ((rc = A.download(o_res, (hyp_poses ? o_po + sizeof(eorb_tvr_pose) * kH : o_p3 + sizeof(float) * 6 * s1) - o_res, &h))) return rc;
-    memcpy(res, h + o_res, sizeof *res);
-    memcpy(R21, h + o_R, sizeof(float) * 18); memcpy(t21, h + o_t, sizeof(float) * 6);
-    memcpy(trans_inliers, h + o_ti, sN); memcpy(triangulated, h + o_tri, 2 * s1); memcpy(p3d, h + o_p3, sizeof(float) * 6 * s1);
-    if (hyp_poses) memcpy(hyp_poses, h + o_po, sizeof(eorb_tvr_pose) * kH);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_sim3_ransac(eorb_ctx* c, const eorb_sim3_problem* problems, int K, const float* Xw1, const float* Xw2,
@@ -3149,17 +3085,19 @@ int eorb_sim3_ransac(eorb_ctx* c, const eorb_sim3_problem* problems, int K, cons
     const size_t o_p1 = A.reserve(sizeof(float) * 2 * tN), o_p2 = A.reserve(sizeof(float) * 2 * tN);
     const size_t o_b1 = A.reserve(sizeof(float) * tN), o_b2 = A.reserve(sizeof(float) * tN), o_hyp = A.reserve(sizeof(float) * kS3HypFloats * tI);
     static_assert(sizeof(eorb_sim3_result) == sizeof(int32_t) * kS3ResWords, "eorb_sim3_result is kS3ResWords words");
-    RansacAid aid[4] = {{it_inliers, sizeof(int32_t) * tI}, {it_scale, sizeof(float) * tI}, {it_T12, sizeof(float) * 16 * tI}, {it_T21, sizeof(float) * 16 * tI}};
-    if ((rc = R.upload(A, sizeof(eorb_sim3_result) * (size_t)K, aid, 4))) return rc;
+    R.results(A, results, sizeof(eorb_sim3_result) * (size_t)K, inliers);
+    const size_t o_ii = A.out(it_inliers, sizeof(int32_t) * tI), o_is = A.out(it_scale, sizeof(float) * tI);
+    const size_t o_t12 = A.out(it_T12, sizeof(float) * 16 * tI), o_t21 = A.out(it_T21, sizeof(float) * 16 * tI);
+    if ((rc = R.upload(A))) return rc;
     S3Args T{};
     T.prob = A.dev<S3Prob>(o_pr); T.K = K; T.max_N = R.max_N; T.max_iters = R.max_iters;
     T.Xw1 = A.dev<float>(o_x1); T.Xw2 = A.dev<float>(o_x2); T.sigma2_1 = A.dev<float>(o_s1); T.sigma2_2 = A.dev<float>(o_s2); T.sets = A.dev<int32_t>(o_st);
     T.X1 = A.dev<float>(o_c1); T.X2 = A.dev<float>(o_c2); T.p1 = A.dev<float2>(o_p1); T.p2 = A.dev<float2>(o_p2);
     T.b1 = A.dev<float>(o_b1); T.b2 = A.dev<float>(o_b2); T.hyp = A.dev<float>(o_hyp);
-    T.res = A.dev<int32_t>(R.res); T.inliers = A.dev<uint8_t>(R.inl); T.it_inliers = A.dev<int32_t>(aid[0].off); T.it_scale = A.dev<float>(aid[1].off);
-    T.it_T12 = A.dev<float>(aid[2].off); T.it_T21 = A.dev<float>(aid[3].off);
+    T.res = A.dev<int32_t>(R.res); T.inliers = A.dev<uint8_t>(R.inl); T.it_inliers = A.dev<int32_t>(o_ii); T.it_scale = A.dev<float>(o_is);
+    T.it_T12 = A.dev<float>(o_t12); T.it_T21 = A.dev<float>(o_t21);
     if ((rc = sim3_ransac_dev(c, T))) return rc;
-    return R.download(A, results, inliers, aid, 4);
+    return A.fetch();
 }
 
 int eorb_mlpnp_ransac(eorb_ctx* c, const eorb_mlpnp_problem* problems, int K, const float* p2d, const float* Xw, const float* sigma2,
@@ -3189,16 +3127,17 @@ int eorb_mlpnp_ransac(eorb_ctx* c, const eorb_mlpnp_problem* problems, int K, co
     const size_t o_f = A.reserve(sizeof(double) * 3 * tN), o_ns = A.reserve(sizeof(double) * 6 * tN), o_x = A.reserve(sizeof(double) * 3 * tN);
     const size_t o_bd = A.reserve(sizeof(float) * tN);
     static_assert(sizeof(eorb_mlpnp_result) == sizeof(int32_t) * kPnpResWords, "eorb_mlpnp_result is kPnpResWords words");
-    RansacAid aid[3] = {{it_inliers, sizeof(int32_t) * tI}, {it_refine_inliers, sizeof(int32_t) * tI}, {it_Rt, sizeof(double) * 12 * tI}};
-    if ((rc = R.upload(A, sizeof(eorb_mlpnp_result) * (size_t)K, aid, 3))) return rc;
+    R.results(A, results, sizeof(eorb_mlpnp_result) * (size_t)K, inliers);
+    const size_t o_ii = A.out(it_inliers, sizeof(int32_t) * tI), o_ir = A.out(it_refine_inliers, sizeof(int32_t) * tI), o_rt = A.out(it_Rt, sizeof(double) * 12 * tI);
+    if ((rc = R.upload(A))) return rc;
     PnpArgs T{};
     T.prob = A.dev<PnpProb>(o_pr); T.K = K; T.max_N = R.max_N; T.max_iters = R.max_iters;
     T.p2d = A.dev<float>(o_p2); T.Xw = A.dev<float>(o_xw); T.sigma2 = A.dev<float>(o_sg); T.sets = A.dev<int32_t>(o_st);
     T.f = A.dev<double>(o_f); T.ns = A.dev<double>(o_ns); T.X = A.dev<double>(o_x); T.bound = A.dev<float>(o_bd);
-    T.res = A.dev<int32_t>(R.res); T.inliers = A.dev<uint8_t>(R.inl); T.it_inliers = A.dev<int32_t>(aid[0].off); T.it_refine = A.dev<int32_t>(aid[1].off);
-    T.it_Rt = A.dev<double>(aid[2].off);
+    T.res = A.dev<int32_t>(R.res); T.inliers = A.dev<uint8_t>(R.inl); T.it_inliers = A.dev<int32_t>(o_ii); T.it_refine = A.dev<int32_t>(o_ir);
+    T.it_Rt = A.dev<double>(o_rt);
     if ((rc = mlpnp_ransac_dev(c, T))) return rc;
-    return R.download(A, results, inliers, aid, 3);
+    return A.fetch();
 }
 
 // what the MixedMatcher forms take on top of the ORB ones (a NULL KfMixedIn* = an ORB entry point): kp_is_orb / kp_inv_sigma2 per
@@ -3278,21 +3217,16 @@ static int kf_radius_common(eorb_ctx* c,
     const KfMixedOff mo = kf_mixed_in(A, mx, (size_t)n, (size_t)M);
     KfSearched S;
     kf_searched_in(A, S, 1, kps, desc, stride, uright, off, gb, taken);
-    // outputs, contiguous: taken (in / out) | best index | best distance; then the keypoints' cells
-    const size_t o_tk = S.tk, o_bi = A.reserve(sizeof(int32_t) * M), o_bd = A.reserve(sizeof(int32_t) * M);
+    // outputs: taken (in / out) | best index | best distance; then the keypoints' cells
+    A.inout(taken, S.tk, (size_t)n);
+    const size_t o_bi = A.out(best_idx, sizeof(int32_t) * M), o_bd = A.out(best_dist, sizeof(int32_t) * M);
     kf_searched_cells(A, S);
     if ((rc = A.upload())) return rc;
     const KfSideDev Q{A.dev<uint8_t>(o_va), A.dev<float2>(o_uv), A.dev<int32_t>(o_lv), A.dev<float>(o_rad), A.dev<float>(o_qur), nullptr, nullptr};
     const RadBatchArgsMixed B = kf_searched_args(A, S, M, Q, A.dev<uint8_t>(o_qd), 0, inv_sigma2 ? A.dev<float>(o_is) : nullptr, nlevels, accept_thr,
                                                  A.dev<int32_t>(o_bi), A.dev<int32_t>(o_bd), mx, mo);
     if ((rc = kf_radius_dev(c, mx ? "kf_radius_match_mixed" : "kf_radius_match", mx != nullptr, B, n, kf_mixed_kp(A, mx, mo)))) return rc;
-    const size_t first = taken ? o_tk : o_bi;
-    const char* h;
-    if ((rc = A.download(first, o_bd + sizeof(int32_t) * M - first, &h))) return rc;
-    memcpy(best_idx, h + o_bi, sizeof(int32_t) * M);
-    memcpy(best_dist, h + o_bd, sizeof(int32_t) * M);
-    if (taken) memcpy(taken, h + o_tk, (size_t)n);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_kf_radius_match(eorb_ctx* c,
@@ -3337,40 +3271,22 @@ static KfPose kf_pose_of(const eorb_view& v)
     return P;
 }
 
-// the arena regions of the projector's K * M outputs, in the order a call downloads them: reason first (eorb_fuse_keyframes wants
-// nothing else), then the members of eorb_kfside_out
-struct KfSideOff { size_t rs, va, uv, rad, lv, qur, d3, end_rs, end; };
-static KfSideOff kfside_reserve(Arena& A, size_t n)
+// the arena regions of the projector's K * M outputs: reason first (eorb_fuse_keyframes wants nothing else), then the members of
+// eorb_kfside_out.  out: the caller's record, or NULL (nothing of it is taken)
+struct KfSideOff { size_t rs, va, uv, rad, lv, qur, d3; };
+static KfSideOff kfside_reserve(Arena& A, size_t n, const eorb_kfside_out* out)
 {
+    const eorb_kfside_out d = out ? *out : eorb_kfside_out{};
     KfSideOff o;
-    o.rs = A.reserve(n); o.end_rs = A.total;
-    o.va = A.reserve(n); o.uv = A.reserve(8 * n); o.rad = A.reserve(4 * n); o.lv = A.reserve(4 * n); o.qur = A.reserve(4 * n);
-    o.d3 = A.reserve(4 * n); o.end = A.total;
+    o.rs = A.out(d.reason, n);
+    o.va = A.out(d.valid, n); o.uv = A.out(d.uv, 8 * n); o.rad = A.out(d.radius, 4 * n); o.lv = A.out(d.level, 4 * n); o.qur = A.out(d.q_ur, 4 * n);
+    o.d3 = A.out(d.dist3d, 4 * n);
     return o;
 }
 static KfSideDev kfside_dev(const Arena& A, const KfSideOff& o)
 {
     return KfSideDev{A.dev<uint8_t>(o.va), A.dev<float2>(o.uv), A.dev<int32_t>(o.lv), A.dev<float>(o.rad), A.dev<float>(o.qur),
                      A.dev<float>(o.d3), A.dev<uint8_t>(o.rs)};
-}
-static bool kfside_wants_all(const eorb_kfside_out* out)
-{
-    return out && (out->valid || out->uv || out->radius || out->level || out->q_ur || out->dist3d);
-}
-static size_t kfside_end(const KfSideOff& o, const eorb_kfside_out* out, size_t without)
-{
-    return kfside_wants_all(out) ? o.end : (out && out->reason) ? o.end_rs : without;
-}
-static void kfside_copy_out(const char* h, const KfSideOff& o, size_t n, const eorb_kfside_out* out)
-{
-    if (!out) return;
-    if (out->reason) memcpy(out->reason, h + o.rs, n);
-    if (out->valid) memcpy(out->valid, h + o.va, n);
-    if (out->uv) memcpy(out->uv, h + o.uv, 8 * n);
-    if (out->radius) memcpy(out->radius, h + o.rad, 4 * n);
-    if (out->level) memcpy(out->level, h + o.lv, 4 * n);
-    if (out->q_ur) memcpy(out->q_ur, h + o.qur, 4 * n);
-    if (out->dist3d) memcpy(out->dist3d, h + o.d3, 4 * n);
 }
 
 // the map points of mode D and the views' shared table
@@ -3433,14 +3349,11 @@ static int project_kfside_common(eorb_ctx* c, const char* who, const eorb_view* 
     Arena A(c);
     KfSideIn I;
     kfside_in(A, I, view, 1, M, pos, normal, min_dist, max_dist, skip, mx);
-    const KfSideOff o = kfside_reserve(A, (size_t)M);
+    const KfSideOff o = kfside_reserve(A, (size_t)M, out);
     if ((rc = A.upload())) return rc;
     const KfSideArgsMixed P = kfside_args(A, I, view, 1, M, skip != nullptr, th, o, mx);
     if ((rc = mx ? project_kfside_mixed_dev(c, P) : project_kfside_dev(c, P))) return rc;
-    const char* h;
-    if ((rc = A.download(o.rs, o.end - o.rs, &h))) return rc;
-    kfside_copy_out(h, o, (size_t)M, out);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_project_keyframe_side(eorb_ctx* c, const eorb_view* view, int M, const float* pos, const float* normal, const float* min_dist,
@@ -3492,9 +3405,10 @@ static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, con
     uint8_t* taken = seq ? seq->taken : nullptr;
     KfSearched S;
     kf_searched_in(A, S, K, kps, desc, stride, uright, kf_off, gb, taken);
-    // outputs, contiguous: taken (in / out, the in-order form) | best index | best distance | the projector's arrays; then the keypoints' cells
-    const size_t o_bi = A.reserve(4 * nq), o_bd = A.reserve(4 * nq), o_bend = A.total;
-    const KfSideOff o = kfside_reserve(A, nq);
+    // outputs: taken (in / out, the in-order form) | best index | best distance | the projector's arrays; then the keypoints' cells
+    A.inout(taken, S.tk, (size_t)ntotal);
+    const size_t o_bi = A.out(best_idx, 4 * nq), o_bd = A.out(best_dist, 4 * nq);
+    const KfSideOff o = kfside_reserve(A, nq, out);
     kf_searched_cells(A, S);
     if ((rc = A.upload())) return rc;
     const KfSideArgsMixed P = kfside_args(A, I, views, K, M, skip != nullptr, th, o, mx);
@@ -3503,14 +3417,7 @@ static int fuse_common(eorb_ctx* c, const char* who, const eorb_view* views, con
                                                  seq ? seq->accept_thr : 0.f, A.dev<int32_t>(o_bi), A.dev<int32_t>(o_bd), mx, I.mo);
     const char* scope = seq ? (mx ? "kf_radius_match_mixed" : "kf_radius_match") : (mx ? "kf_radius_batch_mixed" : "kf_radius_batch");
     if ((rc = kf_radius_dev(c, scope, mx != nullptr, B, ntotal, kf_mixed_kp(A, mx, I.mo)))) return rc;
-    const size_t first = taken ? S.tk : o_bi;
-    const char* h;
-    if ((rc = A.download(first, kfside_end(o, out, o_bend) - first, &h))) return rc;
-    memcpy(best_idx, h + o_bi, 4 * nq);
-    memcpy(best_dist, h + o_bd, 4 * nq);
-    if (taken) memcpy(taken, h + S.tk, (size_t)ntotal);
-    kfside_copy_out(h, o, nq, out);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_fuse_pose(eorb_ctx* c, const eorb_keypoint* kps, int n, const uint8_t* desc, int stride, const eorb_grid_bounds* gb,
@@ -3650,11 +3557,11 @@ int eorb_search_by_sim3(eorb_ctx* c,
     const size_t o_s1 = A.in(skip1, skip1 ? (size_t)n1 : 0), o_s2 = A.in(skip2, skip2 ? (size_t)n2 : 0);
     const size_t o_sf1 = A.in(view1->scale_factors, sizeof(float) * (size_t)view1->nlevels);
     const size_t o_sf2 = A.in(view2->scale_factors, sizeof(float) * (size_t)view2->nlevels);
-    // outputs, contiguous: nfound | match12 | vnMatch1 | vnMatch2; then what only the kernels read
-    const size_t o_nf = A.reserve(16), o_m12 = A.reserve(4 * (size_t)n1), o_v1 = A.reserve(4 * (size_t)n1), o_v2 = A.reserve(4 * (size_t)n2);
-    const size_t o_end = A.total;
+    // outputs: nfound | match12 | vnMatch1 | vnMatch2; then what only the kernels read
+    const size_t o_nf = A.out(nullptr, 16), o_m12 = A.out(match12, 4 * (size_t)n1), o_v1 = A.out(vnMatch1, 4 * (size_t)n1), o_v2 = A.out(vnMatch2, 4 * (size_t)n2);
+    A.inout(nfound, o_nf, sizeof(int32_t));
     const size_t o_bi = A.reserve(8 * m), o_bd = A.reserve(8 * m);
-    const KfSideOff o = kfside_reserve(A, 2 * m);
+    const KfSideOff o = kfside_reserve(A, 2 * m, nullptr);
     kf_searched_cells(A, R);
     if ((rc = A.upload())) return rc;
     Sim3Args S{};
@@ -3677,13 +3584,7 @@ int eorb_search_by_sim3(eorb_ctx* c,
     if ((rc = kf_radius_dev(c, "kf_radius_batch", false, B, ntotal, nullptr))) return rc;
     if ((rc = sim3_agree_dev(c, B.best_idx, B.best_dist, M, n1, n2, th_high, A.dev<int32_t>(o_v1), A.dev<int32_t>(o_v2), A.dev<int32_t>(o_m12),
                              A.dev<int32_t>(o_nf)))) return rc;
-    const char* h;
-    if ((rc = A.download(o_nf, ((vnMatch1 || vnMatch2) ? o_end : o_v1) - o_nf, &h))) return rc;
-    memcpy(match12, h + o_m12, 4 * (size_t)n1);
-    if (nfound) *nfound = *(const int32_t*)(h + o_nf);
-    if (vnMatch1) memcpy(vnMatch1, h + o_v1, 4 * (size_t)n1);
-    if (vnMatch2) memcpy(vnMatch2, h + o_v2, 4 * (size_t)n2);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_bow_set_vocabulary(eorb_ctx* c, int nnodes, int L, const int32_t* child_off, const int32_t* child_ids,
@@ -3765,16 +3666,14 @@ int eorb_bow_transform(eorb_ctx* c, const uint8_t* desc, int n, int stride, int 
     int32_t cnt[2];
     memcpy(cnt, h + o_cnt, 8);
     *n_words = cnt[0]; *n_fvnodes = cnt[1];
-    // the second range ends with the last array asked for: node_of, word_of or the feature vector's indices
-    const size_t end = node_of ? o_no + 4 * N : (word_of ? o_wo + 4 * N : o_fi + 4 * (N + 2));
-    if ((rc = A.download(o_bw, end - o_bw, &h))) return rc;
-    memcpy(bow_word, h + o_bw, 4 * (size_t)cnt[0]);
-    memcpy(bow_val, h + o_bv, 8 * (size_t)cnt[0]);
-    memcpy(fv_off, h + o_fo, 4 * ((size_t)cnt[1] + 1));
-    memcpy(fv_node, h + o_fn, 4 * (size_t)cnt[1]);
+    // the second fetch: the arrays at the sizes the counts give; the feature vector's indices are as many as fv_off says, which arrives
+    // with them (their region is fetched whole)
+    A.inout(bow_word, o_bw, 4 * (size_t)cnt[0]); A.inout(bow_val, o_bv, 8 * (size_t)cnt[0]);
+    A.inout(fv_off, o_fo, 4 * ((size_t)cnt[1] + 1)); A.inout(fv_node, o_fn, 4 * (size_t)cnt[1]);
+    A.want(o_fi, 4 * (N + 2));
+    A.inout(word_of, o_wo, 4 * N); A.inout(node_of, o_no, 4 * N);
+    if ((rc = A.fetch(&h))) return rc;
     memcpy(fv_idx, h + o_fi, 4 * (size_t)fv_off[cnt[1]]);
-    if (word_of) memcpy(word_of, h + o_wo, 4 * N);
-    if (node_of) memcpy(node_of, h + o_no, 4 * N);
     return EORB_OK;
 }
 
@@ -3889,12 +3788,15 @@ static int kfdb_detect(eorb_ctx* c, const char* what, int nbest, int n_words, co
     q.lds_cap = s.dbg_finish_lds > 0 ? s.dbg_finish_lds : kKfdbMaxSlots;
     const size_t o_qw = A.in(word, sizeof(uint32_t) * (size_t)n_words), o_qv = A.in(val, sizeof(double) * (size_t)n_words);
     const size_t o_ex = exclude ? A.in(exclude, NS) : 0, o_cv = covis ? A.in(covis, sizeof(int32_t) * kKfdbCovis * NS) : 0;
-    // outputs, contiguous: counters | slot | si | words | acc | best_slot | keep | sorted_acc | sorted_best_slot
+    // outputs: counters | slot | si | words | acc | best_slot | keep | sorted_acc | sorted_best_slot.  The arrays hold n_scored records, known
+    // after the download: the span covers their cap records, the copies follow the capacity check
     const size_t o_hdr = A.in(zero_hdr, sizeof(zero_hdr));
-    const size_t o_slot = A.reserve(4 * CAP), o_si = A.reserve(4 * CAP), o_words = A.reserve(4 * CAP);
-    const size_t o_acc = covis ? A.reserve(4 * CAP) : 0, o_best = covis ? A.reserve(4 * CAP) : 0, o_keep = covis && !nbest ? A.reserve(CAP) : 0;
-    const size_t o_sacc = covis && nbest ? A.reserve(4 * CAP) : 0, o_sbest = covis && nbest ? A.reserve(4 * CAP) : 0;
-    const size_t o_end = A.reserve(0);
+    A.want(o_hdr, sizeof(zero_hdr));
+    auto records = [&](size_t bytes) { const size_t o = A.out(nullptr, bytes); A.want(o, bytes); return o; };
+    const size_t o_slot = records(4 * CAP), o_si = records(4 * CAP), o_words = records(4 * CAP);
+    const size_t o_acc = covis ? records(4 * CAP) : 0, o_best = covis ? records(4 * CAP) : 0, o_keep = covis && !nbest ? records(CAP) : 0;
+    const size_t o_sacc = covis && nbest ? records(4 * CAP) : 0, o_sbest = covis && nbest ? records(4 * CAP) : 0;
+    A.reserve(0);                                        // (an empty region; tests/golden/arena_layout.json pins the layout)
     const size_t o_cnt = A.reserve(4 * NS), o_first = A.reserve(4 * NS), o_listed = A.reserve(NS), o_sis = A.reserve(4 * NS);
     const size_t o_key = A.reserve(8 * (size_t)npad), o_kslot = A.reserve(4 * (size_t)npad);
     int rc;
@@ -3909,7 +3811,7 @@ static int kfdb_detect(eorb_ctx* c, const char* what, int nbest, int n_words, co
     q.o_sacc = A.dev<float>(o_sacc); q.o_sbest = A.dev<int32_t>(o_sbest);
     if ((rc = kfdb_query_dev(c, q))) return rc;
     const char* h;
-    if ((rc = A.download(o_hdr, o_end - o_hdr, &h))) return rc;
+    if ((rc = A.fetch(&h))) return rc;
     int32_t hdr[4];
     memcpy(hdr, h + o_hdr, sizeof(hdr));
     *n_listed = hdr[0]; *n_scored = hdr[1]; *max_common_words = hdr[2]; memcpy(best_acc, &hdr[3], sizeof(float));
@@ -3954,18 +3856,15 @@ int eorb_calc_optical_flow_pyr_lk(eorb_ctx* c, const uint8_t* prev, const uint8_
     const size_t ib = (size_t)stride * H;
     Arena A(c);
     const size_t o_prev = A.in(prev, ib), o_next = A.in(next, ib), o_pp = A.in(prev_pts, sizeof(float) * 2 * (size_t)n);
-    // outputs, contiguous: next points (in / out) | status | err
+    // outputs: next points (in / out) | status | err
     const size_t o_np = A.in(next_pts, sizeof(float) * 2 * (size_t)n);
-    const size_t o_st = A.reserve((size_t)n + 16), o_err = A.reserve(sizeof(float) * (size_t)n);
+    A.inout(next_pts, o_np, sizeof(float) * 2 * (size_t)n);
+    const size_t o_st = A.out(nullptr, (size_t)n + 16), o_err = A.out(err, sizeof(float) * (size_t)n);
+    A.inout(status, o_st, (size_t)n);
     if ((rc = A.upload())) return rc;
     if ((rc = klt_track_dev(c, A.dev<uint8_t>(o_prev), A.dev<uint8_t>(o_next), W, H, stride, A.dev<float>(o_pp), A.dev<float>(o_np), n, win,
                             maxLevel, maxCount, epsilon, flags, minEigThreshold, A.dev<uint8_t>(o_st), A.dev<float>(o_err)))) return rc;
-    const char* h;
-    if ((rc = A.download(o_np, o_err + sizeof(float) * (size_t)n - o_np, &h))) return rc;
-    memcpy(next_pts, h + o_np, sizeof(float) * 2 * (size_t)n);
-    memcpy(status, h + o_st, (size_t)n);
-    memcpy(err, h + o_err, sizeof(float) * (size_t)n);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_hamming_window_match(eorb_ctx* c, const uint8_t* q_desc, int nq, int q_stride, const uint8_t* t_desc, int nt, int t_stride,
@@ -3984,18 +3883,13 @@ int eorb_hamming_window_match(eorb_ctx* c, const uint8_t* q_desc, int nq, int q_
     Arena A(c);
     const size_t o_q = A.in(q_desc, (size_t)q_stride * nq), o_t = A.in(t_desc, (size_t)t_stride * nt);
     const size_t o_off = A.in(cand_offsets, sizeof(int32_t) * ((size_t)nq + 1)), o_cand = A.in(cand_idx, sizeof(int32_t) * (size_t)ncand);
-    const size_t o_out = A.reserve(sizeof(int32_t) * 4 * (size_t)nq);      // best index | best distance | second index | second distance
+    const size_t q4 = sizeof(int32_t) * (size_t)nq;
+    const size_t o_out = A.out(nullptr, 4 * q4);      // best index | best distance | second index | second distance
+    A.inout(best_idx, o_out, q4); A.inout(best_d, o_out + q4, q4); A.inout(second_idx, o_out + 2 * q4, q4); A.inout(second_d, o_out + 3 * q4, q4);
     if ((rc = A.upload())) return rc;
     if ((rc = window_match_dev(c, A.dev<uint8_t>(o_q), nq, q_stride, A.dev<uint8_t>(o_t), t_stride, A.dev<int32_t>(o_off),
                                A.dev<int32_t>(o_cand), A.dev<int32_t>(o_out)))) return rc;
-    const char* h;
-    if ((rc = A.download(o_out, sizeof(int32_t) * 4 * (size_t)nq, &h))) return rc;
-    const int32_t* o = (const int32_t*)(h + o_out);
-    memcpy(best_idx, o, 4 * (size_t)nq);
-    memcpy(best_d, o + nq, 4 * (size_t)nq);
-    memcpy(second_idx, o + 2 * (size_t)nq, 4 * (size_t)nq);
-    memcpy(second_d, o + 3 * (size_t)nq, 4 * (size_t)nq);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_distinctive_descriptors(eorb_ctx* c, const uint8_t* desc, const int32_t* offsets, int M, int32_t* best)
@@ -4014,13 +3908,10 @@ int eorb_distinctive_descriptors(eorb_ctx* c, const uint8_t* desc, const int32_t
     int rc;
     Arena A(c);
     const size_t o_desc = A.in(desc, 32 * (size_t)n), o_off = A.in(offsets, sizeof(int32_t) * (size_t)(M + 1));
-    const size_t o_best = A.reserve(sizeof(int32_t) * (size_t)M);
+    const size_t o_best = A.out(best, sizeof(int32_t) * (size_t)M);
     if ((rc = A.upload())) return rc;
     if ((rc = distinctive_dev(c, A.dev<uint8_t>(o_desc), A.dev<int32_t>(o_off), M, A.dev<int32_t>(o_best)))) return rc;
-    const char* h;
-    if ((rc = A.download(o_best, sizeof(int32_t) * (size_t)M, &h))) return rc;
-    memcpy(best, h + o_best, sizeof(int32_t) * (size_t)M);
-    return EORB_OK;
+    return A.fetch();
 }
 
 int eorb_sort_by_response(eorb_ctx* c, const eorb_keypoint* kps, int n, int32_t* perm)
@@ -4031,13 +3922,10 @@ int eorb_sort_by_response(eorb_ctx* c, const eorb_keypoint* kps, int n, int32_t*
     fe_enter(c);
     int rc;
     Arena A(c);
-    const size_t o_kp = A.in(kps, sizeof(eorb_keypoint) * n), o_perm = A.reserve(sizeof(int32_t) * n);
+    const size_t o_kp = A.in(kps, sizeof(eorb_keypoint) * n), o_perm = A.out(perm, sizeof(int32_t) * n);
     if ((rc = A.upload())) return rc;
     if ((rc = sort_response_dev(c, A.dev<eorb_keypoint>(o_kp), n, A.dev<int32_t>(o_perm)))) return rc;
-    const char* h;
-    if ((rc = A.download(o_perm, sizeof(int32_t) * n, &h))) return rc;
-    memcpy(perm, h + o_perm, sizeof(int32_t) * n);
-    return EORB_OK;
+    return A.fetch();
 }
 
 void eorb_resolve_num_mixed(int nDetectedORB, int nDetectedAK, int nDesired, int nDesiredAK, int* nORB, int* nAK)
@@ -4061,15 +3949,11 @@ int eorb_hamming_bf_knn2(eorb_ctx* c, const uint8_t* q, int nq, const uint8_t* t
     int rc;
     Arena A(c);
     const size_t o_q = A.in(q, 32 * (size_t)nq), o_t = A.in(t, 32 * (size_t)nt);
-    const size_t o_idx = A.reserve(sizeof(int32_t) * 2 * (size_t)nq), o_dist = A.reserve(sizeof(int32_t) * 2 * (size_t)nq);
+    const size_t o_idx = A.out(idx2, sizeof(int32_t) * 2 * (size_t)nq), o_dist = A.out(dist2, sizeof(int32_t) * 2 * (size_t)nq);
     if ((rc = A.upload())) return rc;
     rc = bf_knn2_dev(c, A.dev<uint8_t>(o_q), nq, A.dev<uint8_t>(o_t), nt, A.dev<int32_t>(o_idx), A.dev<int32_t>(o_dist));
     if (rc) return rc;
-    const char* h;
-    if ((rc = A.download(o_idx, o_dist + sizeof(int32_t) * 2 * (size_t)nq - o_idx, &h))) return rc;
-    memcpy(idx2, h + o_idx, sizeof(int32_t) * 2 * (size_t)nq);
-    memcpy(dist2, h + o_dist, sizeof(int32_t) * 2 * (size_t)nq);
-    return EORB_OK;
+    return A.fetch();
 }
 
 // ---- batched HBM-resident front end --------------------------------------------------------------------

@@ -133,6 +133,9 @@ int         eorb_debug_option(eorb_ctx* ctx, const char* name, int value);
  * counters, 1 tile ranges in LDS, 2 the same with the position dictionary's lookup) | record the scatter reads << 2 (0 the events as they
  * are, 1 2-byte sensor indices, 2 8-byte ranked records) | scatter << 4 (0 ballot, 1 rank, 2 pre-ranked); "win_total_nonzero": pairs of the
  * window matchers whose entry counter is not back at zero after the last call (0 = fine; synchronises).
+ * The host-buffer calls' arena, cumulative over the context's life (a test reads them before and after a call): "arena_calls" (arenas laid
+ * out), "arena_bytes" (their sizes), "arena_in_bytes" (their uploaded prefixes), "arena_downloads", "arena_download_bytes" and
+ * "arena_download_first" (the sum of the downloads' first arena offsets); tests/test_gpu_arena_layout.py.
  * Returns the value, or -1 for an unknown name. */
 long long   eorb_debug_counter(eorb_ctx* ctx, const char* name);
 /* test hook, not part of the reference's interface: the intermediate images of the extractor, for stage-by-stage comparison with
