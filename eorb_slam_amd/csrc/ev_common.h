@@ -12,7 +12,8 @@ namespace eorb {
 
 // ---- the bins of a batch: its chunk list and the workspaces count -> scan -> scatter share, one layout for the list pipeline and the
 // slot form.  chunks buffer: ChunkDesc [nchunks] | the slices' first chunks, int [B + 1] (padded to 8 bytes) | their entry bases,
-// int64 [B]; segoff buffer: segcnt u16 [nchunks][NT] (padded to 16 bytes) | segbase u32 [nchunks][NT]; tile_order buffer: tile_cnt
+// int64 [B]; segoff buffer: segcnt u16 [nchunks][NT] (padded to 16 bytes) | segbase u32 [nchunks][NT] (the list pipeline; the slot
+// form: loff | gbase, below); tile_order buffer: tile_cnt
 // u32 [B * NT] | tile_base u32 [B * NT] (| what the pipeline adds behind them) ----
 struct BinLayout {
     int B, nchunks, NT, nb;
@@ -26,7 +27,13 @@ struct BinLayout {
         sc = (sizeof(int) * (size_t)(B + 1) + 7) & ~(size_t)7;
         eb = sizeof(int64_t) * (size_t)B;
         cnt = (sizeof(uint16_t) * (size_t)std::max(nchunks, 1) * NT + 15) & ~(size_t)15;
+        rows = plan_slot_rows(nchunks, NT); lp = rows.lp; gp = rows.gp;
     }
+    // the slot form keeps other rows in its segoff buffer (ev_plan.h, plan_slot_rows): loff u16 [nchunks][lp] | gbase u32 [nchunks][gp]
+    int lp = 0, gp = 0; SlotRows rows{0, 0, 0, 0};
+    uint16_t* d_loff = nullptr; uint32_t* d_gbase = nullptr;
+    size_t slot_rows_bytes() const { return rows.bytes; }
+    void view_slot_rows(void* segoff) { d_loff = (uint16_t*)segoff; d_gbase = (uint32_t*)((char*)segoff + rows.loff_bytes); }
     size_t chunks_bytes() const { return cd + sc + eb; }
     size_t segoff_bytes() const { return cnt + sizeof(uint32_t) * (size_t)std::max(nchunks, 1) * NT; }
     void view(void* chunks, void* segoff, void* tile_order)      // (after the buffers' ensure())

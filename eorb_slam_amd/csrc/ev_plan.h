@@ -181,9 +181,37 @@ inline GatherPlan plan_gather(const AccumShape& S, const AccumRequest& Q, const 
 
 // ---- the slot form's own shape test ----------------------------------------------------------------------------------------------
 struct SlotScatterChoice { int chunk, waves; bool rank; size_t lds; };
+// the scatters' whole LDS.  Pre-ranked: the chunk's gbase row (NT words) | tile of every sorted slot | its loff row (NT + 1 halves, padded
+// to NTp + 2 >= plan_slot_loff_pitch) | the sorted entry bytes -- two row copies, no scan scratch.  The rank and ballot forms add their
+// per-wave count rows (and a few words of static scan scratch that these sums leave out).
 inline size_t plan_slot_lds_rank(int NT, int chunk, int waves) { const int NTp = (NT + 1) & ~1; return ((size_t)NT * 4 + (size_t)chunk * 4 * 2 + (size_t)waves * NTp * 2 + (size_t)(NTp + 2) * 2 + (size_t)chunk * 4 + 15) & ~(size_t)15; }
 inline size_t plan_slot_lds_pre(int NT, int chunk) { const int NTp = (NT + 1) & ~1; return ((size_t)NT * 4 + (size_t)chunk * 4 * 2 + (size_t)(NTp + 2) * 2 + (size_t)chunk * 4 + 15) & ~(size_t)15; }
 inline size_t plan_slot_lds_ballot(int NT, int chunk) { const int NTp = (NT + 1) & ~1; return ((size_t)chunk * 4 + (size_t)chunk * 2 + (size_t)chunk * 4 * 2 + (size_t)kSlotScatWaves * NTp * 2 + (size_t)(NTp + 2) * 2 + (size_t)NT * 4 + 15) & ~(size_t)15; }
+
+// ---- the rows the slot form's count pass and scan leave for its scatters (BinLayout, ev_common.h) -----------------------------------
+// loff[chunk][0 .. NT]: the exclusive prefix of the chunk's entries over the tiles, loff[NT] = all of them, as 16-bit words: a chunk
+// has at most kSlotChunkMax events of at most 4 entries each.  gbase[chunk][0 .. NT): where tile t's run of the chunk starts in the
+// slice's lists, minus loff[t] (mod 2^32).
+constexpr int kSlotChunkMax = 4096;
+static_assert(4 * kSlotChunkMax <= 0xffff, "a chunk's entry count, loff[NT], is a 16-bit word");
+inline int plan_slot_loff_pitch(int NT) { return (NT + 2) & ~1; }      // 16-bit words per row: NT + 1 rounded up to even (rows are copied as dwords)
+inline int plan_slot_gbase_pitch(int NT) { return (NT + 3) & ~3; }     // 32-bit words per row: sl_scan_kernel stores 16 bytes at a time
+// the one allocation rule of the two: loff u16 [nchunks][lp] (padded to 16 bytes) | gbase u32 [nchunks][gp]
+struct SlotRows { int lp, gp; size_t loff_bytes, bytes; };
+inline SlotRows plan_slot_rows(int nchunks, int NT)
+{
+    SlotRows r;
+    const size_t n = (size_t)std::max(nchunks, 1);
+    r.lp = plan_slot_loff_pitch(NT); r.gp = plan_slot_gbase_pitch(NT);
+    r.loff_bytes = (sizeof(uint16_t) * n * r.lp + 15) & ~(size_t)15;
+    r.bytes = r.loff_bytes + sizeof(uint32_t) * n * r.gp;
+    return r;
+}
+// sl_scan_kernel: a thread takes kSlotScanTiles consecutive tiles; the wavefronts that cover the tile grid once are one SEGMENT of the
+// slice's chunks, and the workgroup's 16 wavefronts make as many segments as fit (690 tiles: 87 threads = 2 wavefronts, 8 segments)
+constexpr int kSlotScanTiles = 8;
+inline int plan_slot_scan_waves(int NT) { return std::min(16, ((NT + kSlotScanTiles - 1) / kSlotScanTiles + 63) / 64); }
+inline int plan_slot_scan_segments(int NT) { return 16 / plan_slot_scan_waves(NT); }
 
 // The scatter a batch will run -- decided before anything is launched: the preferred chunk size first, then shorter chunks; for each
 // the rank form (its own LDS footprint, <= 160 KB with the opt-in) where the device check allows it, else the ballot form (64 KB).
@@ -195,7 +223,7 @@ inline bool plan_slot_scatter(const AccumShape& S, const AccumKnobs& K, bool ran
     // (128 x 1 Mev: binning 1.46-1.51 ms with 2 048, 1.41-1.44 with 4 096)
     const int pref = K.slot_chunk ? K.slot_chunk : (S.per_slice >= (int64_t)1 << 18 ? 4096 : (S.per_slice >= (int64_t)1 << 17 ? 2048 : (S.per_slice >= (int64_t)1 << 14 ? 1024 : 256)));
     const bool rank_allowed = rank_ok && K.slot_rank;
-    static const int sizes[4] = {4096, 2048, 1024, 256};
+    static const int sizes[4] = {kSlotChunkMax, 2048, 1024, 256};
     for (int i = 0; i < 4; i++) {
         const int chunk = sizes[i];
         if (chunk > pref) continue;

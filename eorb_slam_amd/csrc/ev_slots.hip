@@ -9,8 +9,10 @@
 // Per batch ("Round 3: a different decomposition"):
 //   K0  sl_chunks_kernel       chunk descriptors, the slices' first chunks and entry bases from the slice offsets (a kernel argument)
 //   K1a sl_count_lds_kernel    entries of every (chunk, tile): the sensor pixels' tile ranges as a 16-bit table in LDS, one wavefront per
-//                              chunk (sl_count_kernel where that table does not fit)
-//   K1b sl_scan_kernel         one contiguous event-ordered list per (slice, tile); per-tile weights
+//                              chunk (sl_count_kernel where that table does not fit); it leaves the counts' exclusive prefix over the
+//                              tiles, loff[chunk][0 .. NT] -- the chunk's tile offsets, made once, where the counts are at hand
+//   K1b sl_scan_kernel         one contiguous event-ordered list per (slice, tile); per-tile weights; gbase[chunk][tile], the word a
+//                              scatter adds an entry's place in its chunk's tile-sorted order to
 //       (RANKS form, the default for sensors of <= 65 535 pixels: the values the counting atomics return are the entries' ranks in the
 //                              chunk's runs; they go out with the sensor index as an 8-byte record per event, and the scatter below
 //                              -- sl_scatter_pre_kernel -- neither counts nor ranks again)
@@ -200,9 +202,10 @@ __device__ __forceinline__ uint32_t sl_load_rec(const unsigned char* e, int k)
 template <int stride>
 __global__ __launch_bounds__(256) void sl_count_kernel(const eorb_raw_event* __restrict__ ev, const ChunkDesc* __restrict__ chunks,
                                                        const uint2* __restrict__ slot_tab, int LW, int LH, int TX, int NT,
-                                                       uint16_t* __restrict__ segcnt)
+                                                       int LP, uint16_t* __restrict__ loff)
 {
     extern __shared__ uint32_t cnt[];               // NT
+    __shared__ uint32_t s_wsum[4];
     const ChunkDesc cd = chunks[blockIdx.x];
     for (int i = threadIdx.x; i < NT; i += blockDim.x) cnt[i] = 0;
     __syncthreads();
@@ -236,8 +239,22 @@ __global__ __launch_bounds__(256) void sl_count_kernel(const eorb_raw_event* __r
         }
     }
     __syncthreads();
-    uint16_t* sc = segcnt + (size_t)blockIdx.x * NT;
-    for (int i = threadIdx.x; i < NT; i += blockDim.x) sc[i] = (uint16_t)cnt[i];
+    // the chunk's tile offsets: the counts' exclusive prefix over the tiles, in place (consecutive tiles per thread, one step over the waves)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int per = (NT + 255) / 256;
+    const int t0 = min((int)threadIdx.x * per, NT), t1 = min(t0 + per, NT);
+    uint32_t mine = 0;
+    for (int t = t0; t < t1; t++) mine += cnt[t];
+    const uint32_t incl = (uint32_t)wave_incl_scan((int)mine);
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = incl - mine;
+    for (int w = 0; w < wave; w++) before += s_wsum[w];
+    for (int t = t0; t < t1; t++) { const uint32_t v = cnt[t]; cnt[t] = before; before += v; }
+    __syncthreads();
+    uint16_t* lo = loff + (size_t)blockIdx.x * LP;
+    for (int i = threadIdx.x; i < NT; i += 256) lo[i] = (uint16_t)cnt[i];
+    if (threadIdx.x == 255) { lo[NT] = (uint16_t)before; if (NT + 1 < LP) lo[NT + 1] = 0; }      // (the last thread's `before` is the chunk's total)
 }
 
 // K1a with the tile ranges in LDS.  The count pass is a streaming read of the events plus ONE table lookup per event; with the table
@@ -265,7 +282,7 @@ __device__ __forceinline__ uint32_t sl_dict_hash(uint64_t k)
 template <int stride, bool KEYED = false, bool RANKS = false>
 __global__ __launch_bounds__(64 * kSlotCountWaves) void sl_count_lds_kernel(const eorb_raw_event* __restrict__ ev, const ChunkDesc* __restrict__ chunks,
                                                                        int nchunks, const uint16_t* __restrict__ slot_geo, int LW, int LH,
-                                                                       int TX, int NT, uint16_t* __restrict__ segcnt, SlotDict D = SlotDict{nullptr, 0u, nullptr, nullptr, 0},
+                                                                       int TX, int NT, int LP, uint16_t* __restrict__ loff, SlotDict D = SlotDict{nullptr, 0u, nullptr, nullptr, 0},
                                                                        uint16_t* __restrict__ rec16 = nullptr)
 {
     extern __shared__ uint32_t smc[];
@@ -376,51 +393,135 @@ __global__ __launch_bounds__(64 * kSlotCountWaves) void sl_count_lds_kernel(cons
         }
         // (one wavefront: its LDS instructions execute in order, nothing to wait for but the compiler must keep that order)
         __builtin_amdgcn_wave_barrier();
-        uint16_t* sc = segcnt + (size_t)ch * NT;
-        const uint16_t* c16 = (const uint16_t*)cnt;
-        for (int i = lane; i < NT; i += 64) sc[i] = c16[i];
+        // The chunk's tile offsets: the row of counts becomes its exclusive prefix over the tiles, in place -- consecutive counter pairs
+        // per lane, one wave scan, no workgroup barrier (the row is the wave's own).  Offsets are at most 4 x 4 096: 16 bits hold them.
+        const int nd = NTp >> 1, per = (nd + 63) >> 6;
+        const int d0 = min(lane * per, nd), d1 = min(d0 + per, nd);
+        uint32_t mine = 0;
+        for (int d = d0; d < d1; d++) { const uint32_t w = cnt[d]; mine += (w & 0xffffu) + (w >> 16); }
+        const uint32_t incl = (uint32_t)wave_incl_scan((int)mine);
+        uint32_t before = incl - mine;
+        for (int d = d0; d < d1; d++) { const uint32_t w = cnt[d]; const uint32_t lo = before; before += w & 0xffffu; cnt[d] = lo | (before << 16); before += w >> 16; }
+        __builtin_amdgcn_wave_barrier();
+        uint32_t* so = (uint32_t*)(loff + (size_t)ch * LP);
+        for (int i = lane; i < nd; i += 64) so[i] = cnt[i];
+        // loff[NT], the chunk's entries: lane 63's inclusive sum.  (NT odd: the row's pad counter IS tile NT and its prefix went out above.)
+        if (!(NT & 1) && lane == 63) so[nd] = incl;
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-// ---- K1b: one workgroup per slice.  Per tile: exclusive scan of its counts over the slice's chunks (segbase), the total (tile_cnt);
-// exclusive scan over the tiles of the totals rounded up to 16 entries (tile_base: every list starts on a 16-byte boundary) ----
-__global__ __launch_bounds__(1024) void sl_scan_kernel(const int* __restrict__ slice_chunk0, const uint16_t* __restrict__ segcnt, int NT,
-                                                       uint32_t* __restrict__ segbase, uint32_t* __restrict__ tile_cnt,
+// ---- K1b: one workgroup per slice.  Per tile: its entries in the slice (tile_cnt; a chunk's count is loff[t + 1] - loff[t]); exclusive
+// scan over the tiles of the totals rounded up to 16 entries (tile_base: every list starts on a 16-byte boundary); per (chunk, tile)
+// the word the scatters add a sorted position to: gbase = tile_base + entries of the slice's earlier chunks - loff (mod 2^32).
+// The walk over the chunks is split: a thread owns kSlotScanTiles consecutive tiles of ONE segment of the slice's chunks -- the
+// segments' totals meet in LDS, then every segment walks its chunks again (they are in the L2) with its base in hand.  128 x 1 Mev:
+// 8 segments of 31 chunks, 8 chunk rows requested at a time (4 in the second walk), against one chain of 245 before.  One workgroup per slice as before: the
+// slices are independent, nothing waits on another workgroup.  Measured: 74 us against the 51 of the serial walk that left segbase
+// (the second walk is new work: the bases used to be summed by every scatter workgroup) -- the scatter it serves went from 734 to 605. ----
+__global__ __launch_bounds__(1024) void sl_scan_kernel(const int* __restrict__ slice_chunk0, const uint16_t* __restrict__ loff, int NT, int LP, int GP,
+                                                       uint32_t* __restrict__ gbase, uint32_t* __restrict__ tile_cnt,
                                                        uint32_t* __restrict__ tile_base)
 {
+    constexpr int T = kSlotScanTiles, ND = T / 2 + 1, U1 = 8, U2 = 4;      // (chunk rows in flight per thread: pass 1, pass 2 -- which also holds the words it stores)
+    __shared__ uint32_t segtot[16 * 64 * T];         // [segment][tile of the thread][thread of the segment]
     __shared__ uint32_t wsum[16];
-    __shared__ uint32_t carry;
     const int slice = blockIdx.x;
     const int c0 = slice_chunk0[slice], c1 = slice_chunk0[slice + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < NT; t0 += blockDim.x) {
-        const int tile = t0 + threadIdx.x;
-        uint32_t run = 0;
-        if (tile < NT) {
-            int c = c0;
-            for (; c + 8 <= c1; c += 8) {
-                uint32_t v[8];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (uniform: a segment's chunk rows are scalar addresses)
+    const int NG = (NT + T - 1) / T;                  // threads that cover the tiles once
+    const int GW = min(16, (NG + 63) >> 6), GT = GW * 64;      // ... as wavefronts = one segment (plan_slot_scan_waves)
+    const int NS = 16 / GW;                           // segments (plan_slot_scan_segments); wavefronts beyond NS * GW idle
+    const int seg = wave / GW, gl = (wave - seg * GW) * 64 + lane;
+    const bool act = seg < NS;
+    const int nper = (c1 - c0 + NS - 1) / NS;         // chunks per segment
+    const int cs = act ? min(c0 + seg * nper, c1) : c1, ce = min(cs + nper, c1);
+    const int LPd = LP >> 1;
+    // the T + 1 offsets of chunk c from tile t0 on, as dwords (those past the row's end repeat its last one: their tiles are masked below)
+    // (Rows start on dwords only.  The five dwords out of the two ALIGNED 16-byte loads that hold them, selected by the row's
+    // misalignment, were measured: 89 us for 128 x 1 Mev against 74 with the five dword loads below.)
+    auto load_row = [&](int c, int t0, uint32_t (&w)[ND]) {
+        const uint32_t* row = (const uint32_t*)(loff + (size_t)c * LP);
 #pragma unroll
-                for (int u = 0; u < 8; u++) v[u] = segcnt[(size_t)(c + u) * NT + tile];
+        for (int k = 0; k < ND; k++) w[k] = row[min((t0 >> 1) + k, LPd - 1)];
+    };
+    auto half = [](const uint32_t (&w)[ND], int j) { return (w[j >> 1] >> (16 * (j & 1))) & 0xffffu; };
+    uint32_t carry = 0;                               // padded entries of the tile blocks before this one (every thread keeps its own copy)
+    for (int g0 = 0; g0 < NG; g0 += GT) {
+        const int t0 = (g0 + gl) * T;
+        const bool mine = act && t0 < NT;
+        // pass 1: the segment's entries per tile
+        uint32_t tot[T];
 #pragma unroll
-                for (int u = 0; u < 8; u++) { segbase[(size_t)(c + u) * NT + tile] = run; run += v[u]; }
+        for (int j = 0; j < T; j++) tot[j] = 0u;
+        if (mine)
+            for (int c = cs; c < ce; c += U1) {
+                uint32_t w[U1][ND];
+#pragma unroll
+                for (int u = 0; u < U1; u++) {
+                    if (c + u < ce) load_row(c + u, t0, w[u]);
+                    else {
+#pragma unroll
+                        for (int k = 0; k < ND; k++) w[u][k] = 0u;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U1; u++)
+#pragma unroll
+                    for (int j = 0; j < T; j++) tot[j] += t0 + j < NT ? half(w[u], j + 1) - half(w[u], j) : 0u;
             }
-            for (; c < c1; c++) { const uint32_t v = segcnt[(size_t)c * NT + tile]; segbase[(size_t)c * NT + tile] = run; run += v; }
-            tile_cnt[(size_t)slice * NT + tile] = run;
+        if (act) {
+#pragma unroll
+            for (int j = 0; j < T; j++) segtot[(seg * T + j) * GT + gl] = tot[j];
         }
-        const uint32_t padded = (run + 15u) & ~15u;
-        uint32_t incl = (uint32_t)wave_incl_scan((int)padded);
+        __syncthreads();
+        // the earlier segments' entries (run) and the slice's (tot); the lists' bases: exclusive scan of the padded totals over the tiles,
+        // made by every segment for itself
+        uint32_t run[T], padsum = 0u;
+#pragma unroll
+        for (int j = 0; j < T; j++) {
+            uint32_t before = 0u, all = 0u;
+            if (act)
+                for (int s = 0; s < NS; s++) { const uint32_t v = segtot[(s * T + j) * GT + gl]; before += s < seg ? v : 0u; all += v; }
+            run[j] = before; tot[j] = all; padsum += (all + 15u) & ~15u;
+        }
+        const uint32_t incl = (uint32_t)wave_incl_scan((int)padsum);
         if (lane == 63) wsum[wave] = incl;
         __syncthreads();
-        uint32_t before = carry;
-        for (int w = 0; w < wave; w++) before += wsum[w];
-        if (tile < NT) tile_base[(size_t)slice * NT + tile] = before + incl - padded;
-        __syncthreads();
-        if (threadIdx.x == blockDim.x - 1) carry = before + incl;
-        __syncthreads();
+        uint32_t tb = carry + incl - padsum;
+        for (int w = seg * GW; w < wave; w++) tb += wsum[w];
+        for (int w = 0; w < GW; w++) carry += wsum[w];
+        if (mine) {
+#pragma unroll
+            for (int j = 0; j < T; j++) {
+                if (seg == 0 && t0 + j < NT) { tile_cnt[(size_t)slice * NT + t0 + j] = tot[j]; tile_base[(size_t)slice * NT + t0 + j] = tb; }
+                run[j] += tb; tb += (tot[j] + 15u) & ~15u;
+            }
+            // pass 2: gbase = list base + entries of the slice's earlier chunks - the chunk's own offset (mod 2^32)
+            for (int c = cs; c < ce; c += U2) {
+                uint32_t w[U2][ND];
+#pragma unroll
+                for (int u = 0; u < U2; u++) {
+                    if (c + u < ce) load_row(c + u, t0, w[u]);
+                    else {
+#pragma unroll
+                        for (int k = 0; k < ND; k++) w[u][k] = 0u;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U2; u++) {
+                    uint32_t o[T];
+#pragma unroll
+                    for (int j = 0; j < T; j++) { const uint32_t l = half(w[u], j); o[j] = run[j] - l; run[j] += t0 + j < NT ? half(w[u], j + 1) - l : 0u; }
+                    if (c + u < ce) {
+                        uint4* dst = (uint4*)(gbase + (size_t)(c + u) * GP + t0);      // (GP is a multiple of 4: whole 16-byte stores stay in the row)
+#pragma unroll
+                        for (int q = 0; q < T / 4; q++) if (t0 + 4 * q < NT) dst[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+                    }
+                }
+            }
+        }
+        __syncthreads();                               // (segtot and wsum are written again for the next block of tiles)
     }
 }
 
@@ -436,7 +537,7 @@ __global__ __launch_bounds__(1024) void sl_scan_kernel(const int* __restrict__ s
 __global__ __launch_bounds__(64 * kSlotScatWaves) void sl_scatter_kernel(const eorb_raw_event* __restrict__ ev, const ChunkDesc* __restrict__ chunks,
                                                                          const uint2* __restrict__ slot_tab, int stride, int LW, int LH, int TX, int TY,
                                                                          int NT, int chunk_cap, const int64_t* __restrict__ slice_ebase,
-                                                                         const uint32_t* __restrict__ segbase, const uint32_t* __restrict__ tile_base,
+                                                                         const uint32_t* __restrict__ gbase_rows, int GP,
                                                                          slot_entry* __restrict__ entries)
 {
     extern __shared__ unsigned char sm2[];
@@ -509,7 +610,7 @@ __global__ __launch_bounds__(64 * kSlotScatWaves) void sl_scatter_kernel(const e
             for (int w = 0; w < kSlotScatWaves; w++) { const uint32_t v = cntw[w * NTp + t]; cntw[w * NTp + t] = (uint16_t)run; run += v; }
             loff[t] = (uint16_t)run;
             mine += run;
-            gbase[t] = tile_base[(size_t)cd.slice * NT + t] + segbase[(size_t)chunk * NT + t];
+            gbase[t] = gbase_rows[(size_t)chunk * GP + t];            // (the scan's word: the run's place in the list minus its offset in the chunk)
         }
         uint32_t incl = (uint32_t)wave_incl_scan((int)mine);
         if (lane == 63) s_wsum[wave] = incl;
@@ -568,7 +669,7 @@ __global__ __launch_bounds__(64 * kSlotScatWaves) void sl_scatter_kernel(const e
         const uint32_t r0 = prng[k];
         const int t = ((int)(r0 >> 8) + dy) * TX + (int)(r0 & 0xff) + dx;
         const uint32_t slot = (pay[k] >> (8 * (dy * 2 + dx))) & 0xffu;
-        out[(size_t)gbase[t] + (uint32_t)(p - (int)loff[t])] = (slot_entry)(kEntryTag | slot);
+        out[(size_t)(uint32_t)(gbase[t] + (uint32_t)p)] = (slot_entry)(kEntryTag | slot);      // (gbase holds base - loff mod 2^32)
     }
 }
 
@@ -582,7 +683,7 @@ template <int stride, int NW /* wavefronts = 256-event shares of a chunk: 8 (2 0
 __global__ __launch_bounds__(64 * NW) void sl_scatter_rank_kernel(const eorb_raw_event* __restrict__ ev, const ChunkDesc* __restrict__ chunks,
                                                                               const uint2* __restrict__ slot_tab, int LW, int LH, int TX, int NT,
                                                                               int chunk_cap, const int64_t* __restrict__ slice_ebase,
-                                                                              const uint32_t* __restrict__ segbase, const uint32_t* __restrict__ tile_base,
+                                                                              const uint32_t* __restrict__ gbase_rows, int GP,
                                                                               slot_entry* __restrict__ entries)
 {
     extern __shared__ unsigned char sm2[];
@@ -665,7 +766,7 @@ __global__ __launch_bounds__(64 * NW) void sl_scatter_rank_kernel(const eorb_raw
         for (int w = 0; w < wave; w++) before += s_wsum[w];
         for (int t = t0; t < t1; t++) {
             const uint32_t v = loff[t]; loff[t] = (uint16_t)before;
-            gbase[t] = tile_base[(size_t)cd.slice * NT + t] + segbase[(size_t)chunk * NT + t] - before;
+            gbase[t] = gbase_rows[(size_t)chunk * GP + t];            // (the scan's word: base - loff mod 2^32, loff being the `before` of this loop)
             before += v;
         }
         if (tid == NTHR - 1) loff[NT] = (uint16_t)before;
@@ -707,17 +808,17 @@ __global__ __launch_bounds__(64 * NW) void sl_scatter_rank_kernel(const eorb_raw
 }
 
 // ---- K1c, with the ranks of the count pass (sl_count_lds_kernel<.., RANKS>): an 8-byte record per event { sensor index : 16, rank in the
-// chunk's run of the event's tile of class j : 12 bits each }.  Nothing is counted here: the chunk's tile offsets are the prefix of
-// the count pass's own counts (segcnt), an entry's place in the chunk's tile-sorted order is offset + rank.  Phases C and D as above.
+// chunk's run of the event's tile of class j : 12 bits each }.  Nothing is counted or scanned here: the chunk's tile offsets are the
+// row the count pass left (loff), the lists' bases the row the scan left (gbase); an entry's place in the chunk's tile-sorted order is
+// offset + rank.  Phases C and D as above.
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void sl_scatter_pre_kernel(const uint64_t* __restrict__ rec, const ChunkDesc* __restrict__ chunks,
                                                                  const uint2* __restrict__ slot_tab, int nsrc, int TX, int NT, int chunk_cap,
-                                                                 const int64_t* __restrict__ slice_ebase, const uint16_t* __restrict__ segcnt,
-                                                                 const uint32_t* __restrict__ segbase, const uint32_t* __restrict__ tile_base,
+                                                                 const int64_t* __restrict__ slice_ebase, const uint16_t* __restrict__ loff_rows, int LP,
+                                                                 const uint32_t* __restrict__ gbase_rows, int GP,
                                                                  slot_entry* __restrict__ entries)
 {
     extern __shared__ unsigned char sm2[];
-    __shared__ uint32_t s_wsum[NW];
     constexpr int NTHR = 64 * NW;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int chunk = blockIdx.x;
@@ -737,31 +838,25 @@ __global__ __launch_bounds__(64 * NW) void sl_scatter_pre_kernel(const uint64_t*
         const int k = wave * Q + s * 64 + lane;
         rr[s] = (s < S && k < cd.n) ? rec[cd.start + k] : 0xffffull;
     }
+    // (B' starts here: the first words of the chunk's two rows are requested with the records, ahead of the table rows that wait for them)
+    const uint32_t* lrow = (const uint32_t*)(loff_rows + (size_t)chunk * LP);
+    const uint32_t* grow = gbase_rows + (size_t)chunk * GP;
+    uint32_t* loff32 = (uint32_t*)loff;
+    const int LPd = LP >> 1;
+    const uint32_t l0 = tid < LPd ? lrow[tid] : 0u, g0 = tid < NT ? grow[tid] : 0u;
 #pragma unroll
     for (int s = 0; s < SMAX; s++) {
         const uint32_t row = (uint32_t)(rr[s] & 0xffffull);
         rst[s] = (row != 0xffffu && row < (uint32_t)nsrc) ? slot_tab[row] : make_uint2(0u, 0xffffffffu);
     }
-    // ---- B': the chunk's tile offsets = exclusive scan of the count pass's counts over the tiles ----
-    {
-        const int per = (NT + NTHR - 1) / NTHR;
-        const int t0 = tid * per, t1 = min(t0 + per, NT);
-        const uint16_t* sc = segcnt + (size_t)chunk * NT;
-        uint32_t mine = 0;
-        for (int t = t0; t < t1; t++) mine += sc[t];
-        uint32_t incl = (uint32_t)wave_incl_scan((int)mine);
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        uint32_t before = incl - mine;
-        for (int w = 0; w < wave; w++) before += s_wsum[w];
-        for (int t = t0; t < t1; t++) {
-            const uint32_t v = sc[t];
-            loff[t] = (uint16_t)before;
-            gbase[t] = tile_base[(size_t)cd.slice * NT + t] + segbase[(size_t)chunk * NT + t] - before;
-            before += v;
-        }
-        if (tid == NTHR - 1) loff[NT] = (uint16_t)before;
-    }
+#if defined(EORB_KO_SCAT) && EORB_KO_SCAT == 1          // (experiment builds: the kernel cut short after a phase)
+    if (rst[0].x == 0x12345678u || l0 + g0 == 0x12345678u) entries[0] = 0; return;
+#endif
+    // ---- B': the chunk's tile offsets and list bases are the count pass's and the scan's rows (loff, gbase): two coalesced copies ----
+    if (tid < LPd) loff32[tid] = l0;
+    if (tid < NT) gbase[tid] = g0;
+    for (int i = tid + NTHR; i < LPd; i += NTHR) loff32[i] = lrow[i];
+    for (int i = tid + NTHR; i < NT; i += NTHR) gbase[i] = grow[i];
     __syncthreads();
 #if defined(EORB_KO_SCAT) && EORB_KO_SCAT == 2
     if (rst[0].x == 0x12345678u) entries[0] = 0; return;
@@ -1358,7 +1453,7 @@ static int slots_layout(SlotPart& p)
     const BinLayout& L = p.L;
     int rc;
     if ((rc = ensure(c, ws.chunks, L.chunks_bytes()))) return rc;
-    if ((rc = ensure(c, ws.segoff, L.segoff_bytes()))) return rc;
+    if ((rc = ensure(c, ws.segoff, L.slot_rows_bytes()))) return rc;      // (the count pass's loff rows | the scan's gbase rows)
     if ((rc = ensure(c, ws.entries, sizeof(slot_entry) * (size_t)hb.entries + 8192))) return rc;      // + slack: the gather requests blocks past a list's end
     if ((rc = ensure(c, ws.tile_order, sizeof(uint32_t) * 2 * (size_t)L.nb))) return rc;
     if ((rc = ensure(c, ws.plan, p.plan_bytes()))) return rc;
@@ -1376,6 +1471,7 @@ static int slots_layout(SlotPart& p)
     }
     else if ((rc = bin_chunks_upload(c, L, hb, ws.chunks.p, p.M))) return rc;
     p.L.view(ws.chunks.p, ws.segoff.p, ws.tile_order.p);
+    p.L.view_slot_rows(ws.segoff.p);
     return EORB_OK;
 }
 
@@ -1389,7 +1485,7 @@ static int slots_count_scan(const SlotPart& p)
         ProfScope ps(c, "ev_count");
         if (L.nchunks && bp.count == kCountGlobal) {
             const SlCountFn fn = sl_count_fn(bp.stride);
-            fn<<<L.nchunks, 256, bp.lds_count, p.M>>>((const eorb_raw_event*)p.d_events, L.d_chunks, p.d_tab(), T.w, T.h, p.TX, p.NT, L.d_segcnt);
+            fn<<<L.nchunks, 256, bp.lds_count, p.M>>>((const eorb_raw_event*)p.d_events, L.d_chunks, p.d_tab(), T.w, T.h, p.TX, p.NT, L.lp, L.d_loff);
         }
         else if (L.nchunks) {
             // the tile ranges of all positions + one set of counters per wavefront in the LDS of one workgroup per CU; with a dictionary
@@ -1397,12 +1493,12 @@ static int slots_count_scan(const SlotPart& p)
             const SlCountLdsFn fn = sl_count_lds_fn(bp);
             if ((rc = sl_optin(c, (const void*)fn, 159 * 1024))) return rc;
             fn<<<std::min(p.ncu, (L.nchunks + kSlotCountWaves - 1) / kSlotCountWaves), 64 * kSlotCountWaves, bp.lds_count, p.M>>>(
-                (const eorb_raw_event*)p.d_events, L.d_chunks, L.nchunks, p.d_geo(), T.w, T.h, p.TX, p.NT, L.d_segcnt,
+                (const eorb_raw_event*)p.d_events, L.d_chunks, L.nchunks, p.d_geo(), T.w, T.h, p.TX, p.NT, L.lp, L.d_loff,
                 p.dict ? *p.dict : SlotDict{nullptr, 0u, nullptr, nullptr, 0}, bp.record != kRecAsIs ? (uint16_t*)p.ws.rec16.p : nullptr);
         }
     }
     ProfScope ps(c, "ev_scan");
-    sl_scan_kernel<<<p.B, 1024, 0, p.M>>>(L.d_slice_c0, L.d_segcnt, p.NT, L.d_segbase, L.d_tile_cnt, L.d_tile_base);
+    sl_scan_kernel<<<p.B, 1024, 0, p.M>>>(L.d_slice_c0, L.d_loff, p.NT, L.lp, L.gp, L.d_gbase, L.d_tile_cnt, L.d_tile_base);
     return EORB_OK;
 }
 
@@ -1418,17 +1514,17 @@ static int slots_scatter(const SlotPart& p)
         if (L.nchunks && bp.scatter == kScatPre) {
             const SlScatPreFn fn = sl_scatter_pre_fn(waves);
             if ((rc = sl_optin(c, (const void*)fn, 159 * 1024))) return rc;
-            fn<<<L.nchunks, 64 * waves, bp.lds_scatter, p.M>>>((const uint64_t*)p.ws.rec16.p, L.d_chunks, p.d_tab(), T.w * T.h, p.TX, p.NT, chunk, L.d_slice_eb, L.d_segcnt, L.d_segbase,
-                                                               L.d_tile_base, p.d_entries());
+            fn<<<L.nchunks, 64 * waves, bp.lds_scatter, p.M>>>((const uint64_t*)p.ws.rec16.p, L.d_chunks, p.d_tab(), T.w * T.h, p.TX, p.NT, chunk, L.d_slice_eb, L.d_loff, L.lp,
+                                                               L.d_gbase, L.gp, p.d_entries());
         }
         else if (L.nchunks && bp.scatter == kScatRank) {
             const SlScatRankFn fn = sl_scatter_rank_fn(bp.scat_stride, waves);
             if ((rc = sl_optin(c, (const void*)fn, 159 * 1024))) return rc;
-            fn<<<L.nchunks, 64 * waves, bp.lds_scatter, p.M>>>(d_ev, L.d_chunks, p.d_tab(), T.w, T.h, p.TX, p.NT, chunk, L.d_slice_eb, L.d_segbase, L.d_tile_base, p.d_entries());
+            fn<<<L.nchunks, 64 * waves, bp.lds_scatter, p.M>>>(d_ev, L.d_chunks, p.d_tab(), T.w, T.h, p.TX, p.NT, chunk, L.d_slice_eb, L.d_gbase, L.gp, p.d_entries());
         }
         else if (L.nchunks)
-            sl_scatter_kernel<<<L.nchunks, 64 * kSlotScatWaves, bp.lds_scatter, p.M>>>(d_ev, L.d_chunks, p.d_tab(), bp.scat_stride, T.w, T.h, p.TX, p.TY, p.NT, chunk, L.d_slice_eb, L.d_segbase,
-                                                                                         L.d_tile_base, p.d_entries());
+            sl_scatter_kernel<<<L.nchunks, 64 * kSlotScatWaves, bp.lds_scatter, p.M>>>(d_ev, L.d_chunks, p.d_tab(), bp.scat_stride, T.w, T.h, p.TX, p.TY, p.NT, chunk, L.d_slice_eb, L.d_gbase,
+                                                                                         L.gp, p.d_entries());
         EORB_LAUNCH_CHECK(c, "ev_bin (slot) kernels");
     }
     EORB_HIP(c, hipEventRecord(p.E[2], p.M));                            // the part's entries are in place
