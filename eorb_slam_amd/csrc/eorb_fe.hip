@@ -3643,6 +3643,9 @@ int eorb_bow_transform(eorb_ctx* c, const uint8_t* desc, int n, int stride, int 
     if (n < 0 || stride < 32 || weighting < 0 || weighting > 3 || norm < 0 || norm > 2 || !n_words || !n_fvnodes || !fv_off ||
         (n > 0 && (!desc || !bow_word || !bow_val || !fv_node || !fv_idx)))
         return set_err(c, EORB_E_ARG, "bow_transform: bad arguments");
+    // the limit, from n alone: before the arena is built or uploaded and before any of the caller's arrays is written
+    if (!plan_bow_transform(n).ok)
+        return set_err(c, EORB_E_CAPACITY, "bow_transform: %d features, at most %d per call (the LDS sort)", n, kBowMaxFeatures);
     fe_enter(c);
     *n_words = 0; *n_fvnodes = 0; fv_off[0] = 0;
     if (n == 0 || c->voc_nnodes <= 1) return EORB_OK;                       // empty() (:1132)

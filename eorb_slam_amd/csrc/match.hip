@@ -1868,8 +1868,9 @@ __device__ __forceinline__ void block_bitonic_sort(uint64_t* keys, int P)
     __syncthreads();
 }
 
-// run heads of the sorted keys (upper 32 bits = run id) -> exclusive run index per element, number of runs; wave 0 scans
-__device__ __forceinline__ int block_run_index(const uint64_t* keys, int m, uint32_t* ridx)
+// run heads of the sorted keys (upper 32 bits = run id) -> exclusive run index per element, number of runs; wave 0 scans.  A run index
+// is below m <= 8192 (bow_plan.h), so 16 bits hold it
+__device__ __forceinline__ int block_run_index(const uint64_t* keys, int m, uint16_t* ridx)
 {
     __shared__ int s_runs;
     if (threadIdx.x < 64) {
@@ -1880,7 +1881,7 @@ __device__ __forceinline__ int block_run_index(const uint64_t* keys, int m, uint
             int incl = head;
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d, 64); if ((int)threadIdx.x >= d) incl += t; }
-            if (i < m) ridx[i] = (uint32_t)(run + incl - 1);
+            if (i < m) ridx[i] = (uint16_t)(run + incl - 1);
             run += __shfl(incl, 63, 64);
         }
         if (threadIdx.x == 0) s_runs = run;
@@ -1901,7 +1902,7 @@ __global__ __launch_bounds__(1024) void bow_assemble_kernel(const uint32_t* __re
     extern __shared__ unsigned char smem[];
     uint64_t* keys = (uint64_t*)smem;                       // P
     double* vals = (double*)(keys + P);                     // P: the words' values (summed for the norm from here, not from global memory)
-    uint32_t* ridx = (uint32_t*)(vals + P);                 // P
+    uint16_t* ridx = (uint16_t*)(vals + P);                 // P (bow_plan.h: 18 bytes per key)
     __shared__ int s_m;
     __shared__ double s_norm;
     // ---- BowVector ----
@@ -1957,11 +1958,12 @@ int bow_transform_dev(eorb_ctx* c, const uint8_t* d_desc, int n, int stride, con
                       uint32_t* d_word_of, double* d_w_of, uint32_t* d_node_of, uint32_t* d_bow_word, double* d_bow_val,
                       uint32_t* d_fv_node, int32_t* d_fv_off, int32_t* d_fv_idx, int32_t* d_counts)
 {
-    int P = 64; while (P < n) P <<= 1;
-    const size_t lds = (size_t)P * 20;
-    if (lds > 150 * 1024) return set_err(c, EORB_E_CAPACITY, "bow_transform: %d features exceed the LDS sort", n);
+    const BowPlan B = plan_bow_transform(n);
+    if (!B.ok) return set_err(c, EORB_E_CAPACITY, "bow_transform: %d features, at most %d per call (the LDS sort)", n, kBowMaxFeatures);
+    const int P = B.P;
+    const size_t lds = B.lds;
     int rc;
-    if ((rc = lds_optin(c, kOptBowAssemble, (const void*)bow_assemble_kernel, 150 * 1024))) return rc;
+    if ((rc = lds_optin(c, kOptBowAssemble, (const void*)bow_assemble_kernel, kBowLdsOptin))) return rc;
     ProfScope ps(c, "bow_transform");
     bow_descend_kernel<<<(n + 3) / 4, 256, 0, c->stream>>>(d_desc, n, stride, V, V.L - levelsup, d_word_of, d_w_of, d_node_of);
     bow_assemble_kernel<<<1, 1024, lds, c->stream>>>(d_word_of, d_w_of, d_node_of, n, P, weighting, norm, d_bow_word, d_bow_val,

@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 #include "eorb_ctx.h"
+#include "bow_plan.h"
 
 namespace eorb {
 

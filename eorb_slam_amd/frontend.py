@@ -1957,7 +1957,9 @@ def feed_chunks(builder, events, mci_poses=None, max_chunks=10 ** 9):
 
 class ORBVocabulary:
     """DBoW2 vocabulary resident on the device (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h); voc = dict(L, child_off, child_ids,
-    node_desc, word_id, weight) as TemplatedVocabulary::loadFromTextFile leaves m_nodes (node 0 = root)."""
+    node_desc, word_id, weight) as TemplatedVocabulary::loadFromTextFile leaves m_nodes (node 0 = root).  transform() takes at most
+    MAX_FEATURES descriptors per call (EORB_BOW_MAX_FEATURES; EorbError with EORB_E_CAPACITY beyond, nothing written)."""
+    MAX_FEATURES = 8192
 
     def __init__(self, voc, weighting=0, norm=1, ctx=None):
         self.ctx = ctx or default_context()

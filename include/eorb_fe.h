@@ -1232,7 +1232,13 @@ int eorb_bow_set_vocabulary(eorb_ctx* ctx, int nnodes, int L, const int32_t* chi
  * ScoringObject::mustNormalize of the vocabulary's scoring type (ORBvoc.txt: TF_IDF + L1_NORM -> 0, 1).
  * BowVector out: ascending (bow_word, bow_val)[*n_words]; FeatureVector out: CSR (fv_node ascending, fv_off[*n_fvnodes + 1],
  * fv_idx in push_back order) -- the layout eorb_search_by_bow takes.  Output arrays sized n (fv_off n + 1).
- * word_of / node_of (n, may be NULL): word and nid-level node of every feature, -1 for stopped words. */
+ * word_of / node_of (n, may be NULL): word and nid-level node of every feature, -1 for stopped words.
+ * A feature whose descent ends on a leaf above level L - levelsup has node 0 (the reference leaves nid unset there, :1151, :1251), as
+ * has every feature when L - levelsup <= 0 (:1227).
+ * Limit, decided from n before any array is read or written: EORB_BOW_MAX_FEATURES features per call (one workgroup sorts them in
+ * LDS), EORB_E_CAPACITY beyond; the monocular initialiser's 5 x nFeatures frames (Tracking.cc:4216, :1482-1483) fit up to
+ * nFeatures = 1638.  A BowVector of more than EORB_KFDB_MAX_QUERY_WORDS words is refused by the KeyFrameDatabase queries. */
+#define EORB_BOW_MAX_FEATURES  8192
 int eorb_bow_transform(eorb_ctx* ctx, const uint8_t* desc, int n, int stride, int levelsup, int weighting, int norm,
                        uint32_t* bow_word, double* bow_val, int* n_words, uint32_t* fv_node, int32_t* fv_off, int32_t* fv_idx,
                        int* n_fvnodes, int32_t* word_of, int32_t* node_of);
