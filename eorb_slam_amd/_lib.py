@@ -11,7 +11,7 @@ EORB_OK, EORB_E_EMPTY, EORB_E_CONFIG, EORB_E_CAPACITY, EORB_E_ARG, EORB_E_HIP, E
 
 # every symbol include/eorb_fe.h declares (checked by tests/test_abi.py)
 EXPORTS = [
-    "eorb_create", "eorb_destroy", "eorb_sync", "eorb_debug_option", "eorb_debug_counter", "eorb_debug_stage", "eorb_last_error", "eorb_version",
+    "eorb_create", "eorb_destroy", "eorb_sync", "eorb_debug_option", "eorb_debug_option_get", "eorb_debug_counter", "eorb_debug_stage", "eorb_last_error", "eorb_version",
     "eorb_prof_enable", "eorb_prof_reset", "eorb_prof_only", "eorb_prof_count", "eorb_prof_get",
     "eorb_ev2im", "eorb_ev2im_gauss", "eorb_set_undistort_maps", "eorb_undistort_events", "eorb_parse_events_text", "eorb_ev2im_gauss_raw", "eorb_ev2im_raw", "eorb_fe_run_batch_raw_dev", "eorb_fe_run_batch_raw4_dev", "eorb_fe_run_batch_raw2_dev", "eorb_fe_run_batch_images_dev", "eorb_ev2mci_se3", "eorb_ev2mci_se2", "eorb_ev2mci_se3_cam", "eorb_ev2mci_se2_cam", "eorb_measure_image_focus", "eorb_measure_image_focus_n", "eorb_normalize_minmax_u8",
     "eorb_set_calibration", "eorb_undistort_keypoints", "eorb_undistort_points", "eorb_generate_undistort_maps", "eorb_frame_mono",
@@ -260,6 +260,7 @@ def lib():
     L.eorb_destroy.restype = None; L.eorb_destroy.argtypes = [vp]
     L.eorb_sync.restype = ci; L.eorb_sync.argtypes = [vp]
     L.eorb_debug_option.restype = ci; L.eorb_debug_option.argtypes = [vp, C.c_char_p, ci]
+    L.eorb_debug_option_get.restype = ci; L.eorb_debug_option_get.argtypes = [vp, C.c_char_p, C.POINTER(C.c_longlong)]
     L.eorb_debug_counter.restype = C.c_longlong; L.eorb_debug_counter.argtypes = [vp, C.c_char_p]
     L.eorb_debug_stage.restype = ci; L.eorb_debug_stage.argtypes = [vp, C.c_char_p, ci, ci, vp, C.c_size_t, pi, pi]
     L.eorb_last_error.restype = C.c_char_p; L.eorb_last_error.argtypes = [vp]

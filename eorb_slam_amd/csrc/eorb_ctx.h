@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/eorb_fe.h"
 #include "ev_plan.h"
+#include "eorb_options.h"
 
 namespace eorb {
 
@@ -97,8 +98,6 @@ struct KfdbState {
     int n_slots = 0, n_live = 0; uint32_t next_seq = 0;
     std::vector<KfdbSlot> h_tab;                // the host's copy of tab
     std::vector<int> free_slots;                // min-heap: the lowest free slot is reused first
-    int dbg_initial_slots = 0;                  // test hook "kfdb_initial_slots": first capacity in slots (and 64 words per slot); 0: default
-    int dbg_finish_lds = 0;                     // test hook "kfdb_finish_lds_entries": scored entries sorted in LDS (0: as many as fit), to force the sort in global memory
 };
 
 // A set of positions and the device tables derived from it.  The context holds three (eorb_ctx: maps, dd, pd); every function that builds
@@ -160,7 +159,6 @@ struct eorb_ctx {
     int dd_keep = 0;                             // the per-call position table holds an earlier call's positions and is extended, not cleared
     long long pd_hits = 0, pd_misses = 0;        // calls served by the dictionary / calls that found a new position (eorb_debug_counter)
     eorb::DevBuf focus_sd;                       // measureImageFocus: per-patch deviations
-    int64_t dbg_dd_min = (int64_t)1 << 20;       // events from which the positions are deduplicated (test hook: "dedupe_min_events")
     // extractor workspaces
     eorb::OrbState orb;
     eorb::DevBuf pyr, score, blur, cell_cnt, cell_cand, lvl_cnt, lvl_kp, kp_angle, out_kp, out_desc, out_oob,
@@ -203,20 +201,9 @@ struct eorb_ctx {
     // sticky device status word (bits OR-ed by kernels of the *_dev paths: candidate / node-pool / keypoint overflow);
     // read back by eorb_sync / eorb_fe_status
     eorb::DevBuf status;
-    // test hooks (eorb_debug_option): shrink the octree node pool to force an overflow; force the octree's global-memory layout
-    int dbg_pool_shrink = 0, dbg_force_global = 0, dbg_oct_list = 0;      // (dbg_oct_list: the octree's list algorithm for every pass; applies at the next eorb_orb_configure)
-    int dbg_gather_form = 0;                     // raw Gaussian accumulation: 0 by batch shape, 1 K2r, 2 K2s, 3 K2d (<= 4 slices), 4 slot lists (K2p)
-    int dbg_orb_three_launches = 0;              // extraction: orientation, descriptors and output order as three kernels (the path of a lapping area) for every call
-    int dbg_win_lds_ents = 0;                    // window matchers: entries phase 2 stages in LDS (to force its reads from global memory)
-    int dbg_win_wcap = 0, dbg_win_ecap = 0;      // window matchers: list capacity per query / pool per pair (to force the full-scan path)
-    int dbg_slot_rank = -1;                      // slot form: -1 by the device check / EORB_SLOT_RANK, 0 ballot scatter, 1 rank scatter (if the check passed)
-    long long dbg_slot_hot_min = -1;             // slot form: list length from which the register-row kernel takes a list (-1: default / EORB_SLOT_HOT_MIN)
-    int dbg_slot_hot_cap = 0;                    // slot form: lists per length bucket of the register-row kernel (0: kHotCap), to force the overflow branch
-    int dbg_slot_hot_waves = 0;                  // slot form: wavefronts of the register-row kernel (0: default / EORB_SLOT_HOT_WAVES)
-    int dbg_slot_prerank = -1;                   // slot form: ranks kept by the count pass, sl_scatter_pre_kernel (-1: default / EORB_SLOT_PRERANK, 0 / 1: test hook)
-    int dbg_pd = 1;                              // float events in bulk: 0 = never freeze / use the position dictionary (test hook "position_dict")
-    int dbg_slot_halves = -1;                    // slot form: -1 by the batch's shape / EORB_SLOT_HALVES, 0 one part, 1 two halves whatever the shape
-    int dbg_dirty_fill = -1;                     // "dirty_fill": -1 off; 0..255 the byte that new allocations (ensure), the call arena and its staging slot (Arena::upload) and the landing buffer (download_begin) are filled with before use
+    // every switch the context runs with (eorb_options.h): opt_created as eorb_create read it from the environment, opt with what
+    // eorb_debug_option has set since
+    eorb::Options opt, opt_created;
 };
 
 namespace eorb {
@@ -240,11 +227,12 @@ struct ProfScope {
 #define EORB_LAUNCH_CHECK(c, what) do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return eorb::hip_check((c), e__, what); } while (0)
 
 // ev_accum.hip
-AccumKnobs accum_knobs(const eorb_ctx* c);      // the knobs of the accumulation forms: test hooks of the context over the environment (one table, there)
+AccumKnobs accum_knobs(const eorb_ctx* c);      // accum_knobs(c->opt, the build's gather workgroup)
 int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
                       float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized,
-                      uint32_t* d_minmax_enc, bool mm_preset = false);
+                      uint32_t* d_minmax_enc, bool mm_preset = false, bool distinct_positions = false);
 // mm_preset: the caller has initialised the running extremes (the per-slice calls; only the binning-free form takes its word for it)
+// distinct_positions: no two float events share a position (warped events): the call runs with dd_min = 0, nothing is tabulated
 int ev_direct_slices_dev(eorb_ctx* c, const AccumShape& S, const void* d_events, int raw, const int64_t* beg, const int64_t* end, int B, int W, int H,
                          float sigma, int pol, float* d_f32, uint8_t* d_u8, int normalized, uint32_t* d_minmax_enc, bool mm_preset = false);
 int ev_undistort_dev(eorb_ctx* c, const eorb_raw_event* d_raw, size_t n, int W, int H, double tsFactor, eorb_event* d_out, uint32_t* d_blk);

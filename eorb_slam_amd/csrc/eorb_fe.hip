@@ -40,8 +40,8 @@ int ensure(eorb_ctx* c, DevBuf& b, size_t bytes)
     if (e != hipSuccess) { b.p = nullptr; return hip_check(c, e, "hipMalloc"); }
     b.cap = want;
     // test hook "dirty_fill": the allocation starts out as the byte, whole, before anyone (on any stream) can use it
-    if (c && c->dbg_dirty_fill >= 0) {
-        if ((e = hipMemset(b.p, c->dbg_dirty_fill, want)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) return hip_check(c, e, "hipMemset (dirty_fill)");
+    if (c && c->opt.dirty_fill >= 0) {
+        if ((e = hipMemset(b.p, c->opt.dirty_fill, want)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) return hip_check(c, e, "hipMemset (dirty_fill)");
     }
     return EORB_OK;
 }
@@ -182,13 +182,13 @@ struct Arena {
         if (rc) return rc;
         c->arena_gen++;                              // (whatever an earlier call left in the arena is gone)
         c->arena_calls++; c->arena_bytes += (long long)total; c->arena_in_bytes += (long long)in_end;
-        const int dirty = c->dbg_dirty_fill;         // test hook "dirty_fill": the whole arena and the staging slot hold the byte before any input goes in
+        const int dirty = c->opt.dirty_fill;        // test hook "dirty_fill": the whole arena and the staging slot hold the byte before any input goes in
         if (dirty >= 0) EORB_HIP(c, hipMemsetAsync(c->arena.p, dirty, c->arena.cap, c->stream));
         if (!in_end) return EORB_OK;
         char* hp = (char*)pinned(c, in_end);
         if (!hp) return set_err(c, EORB_E_HIP, "pinned alloc failed");
         if (dirty >= 0) memset(hp, dirty, in_end);
-        static const long kmax = [] { const char* e = getenv("EORB_UPLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }();      // (bytes; 0: always the copy engine)
+        const long kmax = (long)c->opt.upload_kernel_max;      // (bytes; 0: always the copy engine)
         // the copy engine takes the staging buffer in pieces of kPiece as it fills: tens of MB are copied in while the host packs the rest;
         // an array of kPiece or more goes straight from the caller's buffer (the runtime copies pageable memory of that size in place,
         // twice as fast as through a staging buffer: 16 MB in 0.30 ms against 0.50 ms)
@@ -227,7 +227,7 @@ struct Arena {
     // the LK reference kept for the next call) runs after the copy and is not waited for.
     size_t dl_off = 0;
     void count_download(size_t off, size_t bytes) { c->arena_downloads++; c->arena_download_bytes += (long long)bytes; c->arena_download_first += (long long)off; }
-    static long download_kmax() { static const long k = [] { const char* e = getenv("EORB_DOWNLOAD_KERNEL_MAX"); return e ? atol(e) : (1L << 20); }(); return k; }      // (bytes; 0: always the copy engine)
+    long download_kmax() const { return (long)c->opt.download_kernel_max; }      // (bytes; 0: always the copy engine)
     int landing(size_t bytes)
     {
         if (c->dl_cap >= bytes) return EORB_OK;
@@ -242,7 +242,7 @@ struct Arena {
         int rc = landing(bytes);
         if (rc) return rc;
         count_download(off, bytes);
-        if (c->dbg_dirty_fill >= 0) memset(c->dl_pinned, c->dbg_dirty_fill, c->dl_cap);      // (test hook: a host read outside the downloaded range sees the byte)
+        if (c->opt.dirty_fill >= 0) memset(c->dl_pinned, c->opt.dirty_fill, c->dl_cap);      // (test hook: a host read outside the downloaded range sees the byte)
         // (the way back like the way in: up to a few hundred KB a kernel writes the pinned buffer; offsets of the arena are multiples of
         // 256 and both buffers longer than the rounded size)
         if ((long)bytes <= download_kmax() && !(off & 15)) {
@@ -258,10 +258,9 @@ struct Arena {
     }
     int download_wait(const char** host)
     {
-        // EORB_SYNC_SPIN=1: poll instead of blocking (one 2 000-event slice through ev2im_gauss + detect: p50 0.260 ->
+        // sync_spin (EORB_SYNC_SPIN=1): poll instead of blocking (one 2 000-event slice through ev2im_gauss + detect: p50 0.260 ->
         // 0.237 ms, p95 0.277 -> 0.326 ms, and a CPU core kept busy: off by default)
-        static const int spin = [] { const char* e = getenv("EORB_SYNC_SPIN"); return e ? atoi(e) : 0; }();
-        if (spin) {
+        if (c->opt.sync_spin) {
             hipError_t q;
             while ((q = hipEventQuery(c->dl_event)) == hipErrorNotReady) {}
             if (q != hipSuccess) return hip_check(c, q, "hipEventQuery");
@@ -366,6 +365,7 @@ int eorb_create(int device, void* hip_stream, eorb_ctx** out)
     if (device < 0 || device >= ndev) return EORB_E_ARG;
     if (hipSetDevice(device) != hipSuccess) return EORB_E_HIP;
     eorb_ctx* c = new eorb_ctx();
+    c->opt = c->opt_created = options_from_env();
     c->device = device;
     if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
     else {
@@ -428,28 +428,18 @@ int eorb_sync(eorb_ctx* c)
 int eorb_debug_option(eorb_ctx* c, const char* name, int value)
 {
     if (!c || !name) return EORB_E_ARG;
-    if (!strcmp(name, "octree_pool_shrink")) { c->dbg_pool_shrink = value; return EORB_OK; }
-    if (!strcmp(name, "octree_force_global")) { c->dbg_force_global = value; return EORB_OK; }
-    if (!strcmp(name, "octree_list_algorithm")) { c->dbg_oct_list = value; return EORB_OK; }
-    if (!strcmp(name, "win_list_cap")) { c->dbg_win_wcap = value; return EORB_OK; }
-    if (!strcmp(name, "win_pool_cap")) { c->dbg_win_ecap = value; return EORB_OK; }
-    if (!strcmp(name, "orb_three_launches")) { c->dbg_orb_three_launches = value; return EORB_OK; }
-    if (!strcmp(name, "win_lds_entries")) { c->dbg_win_lds_ents = value; return EORB_OK; }
-    if (!strcmp(name, "gather_form")) { c->dbg_gather_form = value; return EORB_OK; }
-    if (!strcmp(name, "dedupe_min_events")) { c->dbg_dd_min = value; return EORB_OK; }
-    if (!strcmp(name, "slot_rank")) { c->dbg_slot_rank = value; return EORB_OK; }
-    if (!strcmp(name, "slot_hot_min")) { c->dbg_slot_hot_min = value; return EORB_OK; }
-    if (!strcmp(name, "slot_hot_cap")) { c->dbg_slot_hot_cap = value; return EORB_OK; }
-    if (!strcmp(name, "slot_halves")) { c->dbg_slot_halves = value; return EORB_OK; }
-    if (!strcmp(name, "position_dict")) { c->dbg_pd = value; if (!value) { c->pd_valid = 0; c->dd_keep = 0; } return EORB_OK; }
-    if (!strcmp(name, "slot_hot_waves")) { c->dbg_slot_hot_waves = value; return EORB_OK; }
-    if (!strcmp(name, "slot_prerank")) { c->dbg_slot_prerank = value; return EORB_OK; }
-    if (!strcmp(name, "kfdb_initial_slots")) { c->kfdb.dbg_initial_slots = value; return EORB_OK; }
-    if (!strcmp(name, "kfdb_finish_lds_entries")) { c->kfdb.dbg_finish_lds = value; return EORB_OK; }
-    if (!strcmp(name, "dirty_fill")) {
-        if (value < -1 || value > 255) return set_err(c, EORB_E_ARG, "dirty_fill: -1 (off) or a byte 0..255, not %d", value);
-        c->dbg_dirty_fill = value; return EORB_OK;
+    if (!strcmp(name, "dirty_fill") && (value < -1 || value > 255)) return set_err(c, EORB_E_ARG, "dirty_fill: -1 (off) or a byte 0..255, not %d", value);
+    if (option_set(c->opt, c->opt_created, name, value)) {
+        if (!strcmp(name, "position_dict") && !value) { c->pd_valid = 0; c->dd_keep = 0; }
+        return EORB_OK;
     }
+    return set_err(c, EORB_E_ARG, "debug option '%s' unknown", name);
+}
+
+int eorb_debug_option_get(eorb_ctx* c, const char* name, long long* value)
+{
+    if (!c || !name || !value) return EORB_E_ARG;
+    if (option_get(c->opt, name, value)) return EORB_OK;
     return set_err(c, EORB_E_ARG, "debug option '%s' unknown", name);
 }
 
@@ -651,8 +641,7 @@ static int ev_host_common(eorb_ctx* c, const eorb_event* ev, size_t n, int W, in
     }
     Arena A(c);
     // (a live slice goes to the binning-free form, which reads every event once: in place, from the pinned staging buffer)
-    static const int zc_env = [] { const char* e = getenv("EORB_SLICE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
-    A.host_inputs = zc_env != 0 && plan_host_events(accum_shape(W, H, sigma, mode_count, 1, (int64_t)n), AccumRequest{raw, pol, mode_count, 1}, accum_knobs(c));
+    A.host_inputs = c->opt.slice_zero_copy != 0 && plan_host_events(accum_shape(W, H, sigma, mode_count, 1, (int64_t)n), AccumRequest{raw, pol, mode_count, 1}, accum_knobs(c));
     const size_t o_ev = A.in(raw ? (const void*)rawev : (const void*)packed.data(), sizeof(eorb_event16) * n);
     // outputs: min/max (encoded | decoded; read through the host view) | u8 image | f32 image
     const size_t o_mm = A.out(nullptr, 64), o_u8 = A.out(out_u8, npix), o_f32 = A.out(out_f32, sizeof(float) * npix);
@@ -884,9 +873,7 @@ static int mci_common(eorb_ctx* c, const eorb_event* ev, size_t n, const eorb_ca
     uint32_t* mm = A.dev<uint32_t>(o_mm);
     float* mmf = A.dev<float>(o_mm + 16);
     // (warped events: no two share a position -- the position table of the bulk float form would only be filled and thrown away)
-    const int64_t dd_saved = c->dbg_dd_min; c->dbg_dd_min = 0;
-    rc = ev_accumulate_dev(c, d_warp, 0, offs, 1, W, H, sigma, pol, 0, A.dev<float>(o_f32), A.dev<uint8_t>(o_u8), normalized, mm);
-    c->dbg_dd_min = dd_saved;
+    rc = ev_accumulate_dev(c, d_warp, 0, offs, 1, W, H, sigma, pol, 0, A.dev<float>(o_f32), A.dev<uint8_t>(o_u8), normalized, mm, false, true);
     if (rc) return rc;
     if ((rc = ev_decode_minmax(c, mm, mmf, 1))) return rc;
     return A.fetch();
@@ -970,8 +957,7 @@ static int image_check(eorb_ctx* c, const char* who, const uint8_t* img, int W, 
 // kernel, which then reads the pinned staging buffer itself (Arena::in_ptr): no upload in front of the launch
 static size_t image_in(Arena& A, const uint8_t* img, int W, int H, int stride, bool allow_zero_copy)
 {
-    static const int zc_env = [] { const char* e = getenv("EORB_IMAGE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
-    if (allow_zero_copy) A.host_inputs = zc_env != 0 && (size_t)W * H <= ((size_t)1 << 20);
+    if (allow_zero_copy) A.host_inputs = A.c->opt.image_zero_copy != 0 && (size_t)W * H <= ((size_t)1 << 20);
     return A.in2d(img, H, (size_t)W, (size_t)stride);
 }
 
@@ -1077,8 +1063,7 @@ int eorb_ev_slice_extract(eorb_ctx* c, const eorb_event* ev, const eorb_raw_even
     // u8 image | the extraction's result block
     // a live slice (the binning-free form reads every event once, in ev_pre_kernel): the events stay in pinned host memory and the
     // extremes are initialised by that kernel -- no copy in front of the first launch
-    static const int zc_env = [] { const char* e = getenv("EORB_SLICE_ZERO_COPY"); return e ? atoi(e) : 1; }();      // (A/B runs)
-    const bool zc = zc_env != 0 && plan_host_events(accum_shape(W, H, sigma, 0, 1, (int64_t)n), AccumRequest{is_raw, 0, 0, 1}, accum_knobs(c));
+    const bool zc = c->opt.slice_zero_copy != 0 && plan_host_events(accum_shape(W, H, sigma, 0, 1, (int64_t)n), AccumRequest{is_raw, 0, 0, 1}, accum_knobs(c));
     A.host_inputs = zc;
     const size_t o_mm = zc ? A.reserve(sizeof(kMinMaxPreset)) : A.in(kMinMaxPreset, sizeof(kMinMaxPreset)), o_f32 = A.reserve(sizeof(float) * npix);
     const size_t o_u8 = A.out(nullptr, npix);
@@ -1221,19 +1206,15 @@ int eorb_ev_mc_contest(eorb_ctx* c, const eorb_event* ev, size_t n, const eorb_c
     beg[half_img] = nh ? (int64_t)(n - nh) : 0; end[half_img] = (int64_t)n;
     float* d_f32 = A.dev<float>(o_f32);
     uint32_t* d_mm = A.dev<uint32_t>(o_mm);
-    static const long direct_max = [] { const char* e = getenv("EORB_CONTEST_DIRECT_MAX"); return e ? atol(e) : 49152L; }();      // (A/B runs)
-    if ((long)n <= direct_max) {
+    if ((long)n <= (long)c->opt.contest_direct_max) {
         // every reconstruction of the window in ONE launch of the binning-free kernel (float events, normalized = false).  (Beyond
         // the single-slice limit of 16 384 events too: five binned passes of 60 us each are what the alternative costs here.)
         if ((rc = ev_direct_slices_dev(c, accum_shape(W, H, sigma, 0, nimg, (int64_t)n), d_ev, 0, beg, end, nimg, W, H, sigma, 0, d_f32, nullptr, 0, d_mm))) return rc;
     } else {
-        const int64_t dd_saved = c->dbg_dd_min; c->dbg_dd_min = 0;     // (warped events: no two share a position)
-        for (int j = 0; j < nimg && !rc; j++) {
+        for (int j = 0; j < nimg; j++) {                                // (warped events: no two share a position)
             int64_t offs[2] = {0, end[j] - beg[j]};
-            rc = ev_accumulate_dev(c, d_ev + beg[j], 0, offs, 1, W, H, sigma, 0, 0, d_f32 + (size_t)j * npix, nullptr, 0, d_mm + 2 * j);
+            if ((rc = ev_accumulate_dev(c, d_ev + beg[j], 0, offs, 1, W, H, sigma, 0, 0, d_f32 + (size_t)j * npix, nullptr, 0, d_mm + 2 * j, false, true))) return rc;
         }
-        c->dbg_dd_min = dd_saved;
-        if (rc) return rc;
     }
     // measureImageFocus of every image, then cv::normalize(img, img, 255, 0, NORM_MINMAX, CV_8UC1) of every image (:972-976, :1052-1055, :1073-1076, :1137-1140)
     if ((rc = ev_focus_dev(c, d_f32, nimg, W, H, A.dev<float>(o_fimg)))) return rc;
@@ -3788,7 +3769,7 @@ static int kfdb_detect(eorb_ctx* c, const char* what, int nbest, int n_words, co
     Arena A(c);
     KfdbQuery q{};
     q.n_slots = s.n_slots; q.nq = n_words; q.family = nbest ? EORB_KFDB_PLACE : EORB_KFDB_RELOC; q.cap = cap; q.nbest = nbest; q.npad = npad;
-    q.lds_cap = s.dbg_finish_lds > 0 ? s.dbg_finish_lds : kKfdbMaxSlots;
+    q.lds_cap = c->opt.kfdb_finish_lds_entries > 0 ? c->opt.kfdb_finish_lds_entries : kKfdbMaxSlots;
     const size_t o_qw = A.in(word, sizeof(uint32_t) * (size_t)n_words), o_qv = A.in(val, sizeof(double) * (size_t)n_words);
     const size_t o_ex = exclude ? A.in(exclude, NS) : 0, o_cv = covis ? A.in(covis, sizeof(int32_t) * kKfdbCovis * NS) : 0;
     // outputs: counters | slot | si | words | acc | best_slot | keep | sorted_acc | sorted_best_slot.  The arrays hold n_scored records, known

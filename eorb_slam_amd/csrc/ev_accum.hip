@@ -2030,55 +2030,8 @@ static int ev_raw_tables(eorb_ctx* c, PosTables& T, const AccumShape& S, int W, 
 }
 
 // ---- the knobs ---------------------------------------------------------------------------------------------------------------------
-// Every switch of the accumulation forms, from its two sources: a test hook of the context (eorb_debug_option) and the environment
-// (read once per process; meant for A/B runs of one build).  Which wins, per knob:
-//
-//   knob             option (context field)             environment            rule
-//   gather_form      "gather_form"                      --                     option
-//   dd_min           "dedupe_min_events"                --                     option
-//   pd               "position_dict"                    --                     option
-//   scatter          --                                 EORB_SCATTER (2)       environment; 1: the pipeline's first scatter form
-//   gather_threads   --                                 EORB_GATHER_THREADS    environment if 192..1024 and a multiple of 64, else the build's
-//   gather_nc        --                                 EORB_GATHER_NC (0)     environment; 2 / 4, anything else: by the launch's size
-//   slot_chunk       --                                 EORB_SLOT_CHUNK (0)    environment if 256 / 1024 / 2048 / 4096, else by the slices' length
-//   slot_waves       --                                 EORB_SLOT_WAVES (0)    environment if 1..16
-//   slot_rounds      --                                 EORB_SLOT_ROUNDS (0)   environment if >= 1, else 4
-//   slot_rank        "slot_rank" (-1)                   EORB_SLOT_RANK (1)     option if >= 0, else environment; non-zero: allowed
-//   slot_hot_min     "slot_hot_min" (-1)                EORB_SLOT_HOT_MIN (-1) option if >= 0, else environment; < 0: by the batch's size
-//   slot_hot_cap     "slot_hot_cap" (0)                 --                     option; <= 0: kHotCap
-//   slot_hot_waves   "slot_hot_waves" (0)               EORB_SLOT_HOT_WAVES (0) option if > 0, else environment if > 0, else 8 per CU
-//   slot_prerank     "slot_prerank" (-1)                EORB_SLOT_PRERANK (1)  option if >= 0, else environment
-//   slot_halves      "slot_halves" (-1)                 EORB_SLOT_HALVES (-1)  option if >= 0, else environment; > 0: two halves
-AccumKnobs accum_knobs(const eorb_ctx* c)
-{
-    static const AccumKnobs env = [] {
-        auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
-        AccumKnobs k;
-        k.scatter = (int)num("EORB_SCATTER", 2);
-        const int gt = (int)num("EORB_GATHER_THREADS", kGatherThreads);
-        k.gather_threads = (gt >= 192 && gt <= 1024 && gt % 64 == 0) ? gt : kGatherThreads;
-        k.gather_nc = (int)num("EORB_GATHER_NC", 0);
-        const int sc = (int)num("EORB_SLOT_CHUNK", 0);
-        k.slot_chunk = (sc == 256 || sc == 1024 || sc == 2048 || sc == 4096) ? sc : 0;
-        k.slot_waves = (int)num("EORB_SLOT_WAVES", 0);
-        k.slot_rounds = (int)num("EORB_SLOT_ROUNDS", 0);
-        k.slot_rank = num("EORB_SLOT_RANK", 1) != 0;
-        k.slot_hot_min = num("EORB_SLOT_HOT_MIN", -1);
-        k.slot_hot_waves = std::max((int)num("EORB_SLOT_HOT_WAVES", 0), 0);
-        k.slot_prerank = (int)num("EORB_SLOT_PRERANK", 1);
-        k.slot_halves = (int)num("EORB_SLOT_HALVES", -1);
-        return k;
-    }();
-    AccumKnobs k = env;
-    k.gather_form = c->dbg_gather_form; k.dd_min = c->dbg_dd_min; k.pd = c->dbg_pd;
-    if (c->dbg_slot_rank >= 0) k.slot_rank = c->dbg_slot_rank != 0;
-    if (c->dbg_slot_hot_min >= 0) k.slot_hot_min = c->dbg_slot_hot_min;
-    k.slot_hot_cap = c->dbg_slot_hot_cap;
-    if (c->dbg_slot_hot_waves > 0) k.slot_hot_waves = c->dbg_slot_hot_waves;
-    if (c->dbg_slot_prerank >= 0) k.slot_prerank = c->dbg_slot_prerank;
-    if (c->dbg_slot_halves >= 0) k.slot_halves = c->dbg_slot_halves;
-    return k;
-}
+// the context's options (eorb_options.h: the table of every switch and where it comes from) as the rules of ev_plan.h read them
+AccumKnobs accum_knobs(const eorb_ctx* c) { return accum_knobs(c->opt, kGatherThreads); }
 
 // ---- the launches every form shares ----------------------------------------------------------------------------------------------
 static void ev_minmax_init(eorb_ctx* c, uint32_t* d_minmax_enc, int B)
@@ -2350,7 +2303,7 @@ static int ev_bulk_float(eorb_ctx* c, const AccumShape& S, const AccumRequest& Q
 
 int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t* h_offsets, int B, int W, int H,
                       float sigma, int pol, int mode_count, float* d_f32, uint8_t* d_u8, int normalized,
-                      uint32_t* d_minmax_enc, bool mm_preset)
+                      uint32_t* d_minmax_enc, bool mm_preset, bool distinct_positions)
 {
     if (B <= 0 || W <= 0 || H <= 0) return set_err(c, EORB_E_ARG, "ev_accumulate: bad size");
     if (raw && !c->maps.w) return set_err(c, EORB_E_NOTCONF, "ev_accumulate: raw events need eorb_set_undistort_maps first");
@@ -2360,7 +2313,8 @@ int ev_accumulate_dev(eorb_ctx* c, const void* d_events, int raw, const int64_t*
     // reference's running maximum then depends on visits that add nothing (see the gather kernels)
     if (pol && !mode_count && sigma < 0.2f) return set_err(c, EORB_E_CONFIG, "ev_accumulate: polarity images need sigma >= 0.2 (got %.3f)", sigma);
     if (raw == 4 && (int64_t)c->maps.w * c->maps.h > 65535) return set_err(c, EORB_E_ARG, "ev_accumulate: 2-byte records need a sensor of at most 65 535 pixels (the maps are %dx%d)", c->maps.w, c->maps.h);
-    const AccumKnobs K = accum_knobs(c);
+    AccumKnobs K = accum_knobs(c);
+    if (distinct_positions) K.dd_min = 0;                // (nothing to tabulate: the position table would only be filled and thrown away)
     const AccumRequest Q{raw, pol, mode_count, B};
     if (plan_bulk_eligible(S, Q, K)) {
         bool served = false;

@@ -240,7 +240,7 @@ int kfdb_reserve(eorb_ctx* c, int new_slots, int64_t new_words)
 {
     KfdbState& s = c->kfdb;
     int rc;
-    const int first_slots = s.dbg_initial_slots > 0 ? s.dbg_initial_slots : 1024;
+    const int first_slots = c->opt.kfdb_initial_slots > 0 ? c->opt.kfdb_initial_slots : 1024;
     const int want_slots = s.n_slots + new_slots;           // (an upper bound: free slots are reused first)
     if (want_slots > s.slot_cap) {
         int cap = std::max(s.slot_cap, first_slots);

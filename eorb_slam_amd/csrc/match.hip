@@ -920,20 +920,19 @@ static int launch_win(eorb_ctx* c, WinArgs& A, int npairs, int nq_max, const cha
 {
     if (A.cap2 >= (1 << 24) || A.capq >= 32768) return set_err(c, EORB_E_CAPACITY, "%s: too many keypoints", name);
     if (A.cap2 > 2 * kWinLdsEntries) return set_err(c, EORB_E_CAPACITY, "%s: %d keypoints in the searched frame (limit %d)", name, A.cap2, 2 * kWinLdsEntries);
-    A.wcap = c->dbg_win_wcap > 0 ? c->dbg_win_wcap : 512;
-    A.ecap = c->dbg_win_ecap > 0 ? c->dbg_win_ecap : std::max(4096, 16 * A.capq);
+    A.wcap = c->opt.win_list_cap > 0 ? c->opt.win_list_cap : 512;
+    A.ecap = c->opt.win_pool_cap > 0 ? c->opt.win_pool_cap : std::max(4096, 16 * A.capq);
     // phase 2 keeps as many of a pair's entries in LDS as fit beside its tables (one read from global memory inside a sweep is what the
     // whole workgroup then waits for at the sweep's barrier), at least kWinLdsEntries
     // phase 1: every workgroup stages the searched frame (44 B per keypoint) from the L2 before its wavefronts take a query each.  A lone
     // pair (one frame per call) is latency: 16 wavefronts per workgroup stage it in two loads per thread and 4 x fewer workgroups do so
     // (SearchByProjection 24 -> ... us); a batch of pairs fills the chip either way and keeps the small workgroups.
-    static const int cand_env = [] { const char* e = getenv("EORB_WIN_CAND_WAVES"); return e ? atoi(e) : 0; }();      // (A/B runs)
-    int cw = cand_env > 0 ? cand_env : (npairs >= 8 ? 4 : 16);
+    int cw = c->opt.win_cand_waves > 0 ? c->opt.win_cand_waves : (npairs >= 8 ? 4 : 16);
     while (cw > 4 && win_cand_lds(A.cap2, A.wcap, cw) > 159 * 1024) cw >>= 1;
     const size_t lds1 = win_cand_lds(A.cap2, A.wcap, cw), rest2 = win_resolve_lds_rest(A.cap2, A.capq);
     A.lds_ents = (int)std::min<size_t>((size_t)A.ecap, rest2 < 159 * 1024 ? (159 * 1024 - rest2) / 8 : 0);
     const bool fits = A.lds_ents >= std::min(A.ecap, kWinLdsEntries);
-    if (c->dbg_win_lds_ents > 0) A.lds_ents = std::min(A.lds_ents, std::max(c->dbg_win_lds_ents, (A.cap2 + 1) / 2));      // (the rotation histogram's bin masks reuse the buffer)
+    if (c->opt.win_lds_entries > 0) A.lds_ents = std::min(A.lds_ents, std::max(c->opt.win_lds_entries, (A.cap2 + 1) / 2));      // (the rotation histogram's bin masks reuse the buffer)
     const size_t lds2 = (size_t)A.lds_ents * 8 + rest2;
     if (lds1 > 159 * 1024 || !fits)        // (the kernels own a few words of static LDS besides)
         return set_err(c, EORB_E_CAPACITY, "%s: %zu / %zu B of LDS needed (searched frame %d, queries %d)", name, lds1, lds2, A.cap2, A.capq);
@@ -958,8 +957,7 @@ static int launch_win(eorb_ctx* c, WinArgs& A, int npairs, int nq_max, const cha
     ProfScope ps(c, name);
     // queries per phase-1 workgroup: a lone pair is spread over as many workgroups as it has queries per wavefront (one each: 0.091 ->
     // 0.085 ms per SearchForInitialization call against two each; every workgroup stages the searched frame, 57 KB, from the L2)
-    static const int qpb_env = [] { const char* e = getenv("EORB_WIN_QPB"); return e ? atoi(e) : 0; }();      // (A/B runs)
-    const int qpb = qpb_env > 0 ? qpb_env : (npairs >= 8 ? 32 : cw);
+    const int qpb = c->opt.win_qpb > 0 ? c->opt.win_qpb : (npairs >= 8 ? 32 : cw);
     win_cand_kernel<KIND><<<dim3((nq_max + qpb - 1) / qpb, npairs), 64 * cw, lds1, c->stream>>>(A, qpb);
     // (the fixed points of SearchForInitialization and SearchByProjection(cur, last) settle a window of blockDim queries at a time: the widest block)
     win_resolve_kernel<KIND><<<npairs, KIND == 2 ? 256 : 1024, lds2, c->stream>>>(A);

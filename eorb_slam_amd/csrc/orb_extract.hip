@@ -1621,8 +1621,8 @@ int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H)
     o.cand_total = cand_total; o.kp_total = kp_total; o.max_out = kp_total;
     // octree working set: greedy placement into the 160 KB of LDS (most latency-critical first), the rest into a per-(slice,
     // level) block of global scratch (346x260 with 3 000 features on one level, VGA-class frames)
-    if (c->dbg_pool_shrink > 0)                    // test hook: force node-pool overflows (sticky status of the *_dev paths)
-        for (int l = 0; l < nlevels; l++) o.lv[l].node_cap = std::max(8, o.lv[l].node_cap - c->dbg_pool_shrink);
+    if (c->opt.octree_pool_shrink > 0)                    // test hook: force node-pool overflows (sticky status of the *_dev paths)
+        for (int l = 0; l < nlevels; l++) o.lv[l].node_cap = std::max(8, o.lv[l].node_cap - c->opt.octree_pool_shrink);
     // vsp lists are sorted with a bitonic network: capacity rounded up to a power of two
     int vsp_pow2 = 1; while (vsp_pow2 < vsp_cap_max) vsp_pow2 <<= 1;
     const size_t item_bytes[7] = {(size_t)2 * node_cap_max * 16,
@@ -1633,11 +1633,11 @@ int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H)
     int oct_in_lds[2][7], oct_off[2][7];
     // placement order: the per-round arrays and the node arrays first (touched by every step), then the size lists, keys, points
     const int order[7] = {6, 0, 1, 2, 3, 4, 5};
-    static const int budget_kb = [] { const char* e = getenv("EORB_OCT_BUDGET_KB"); return e ? atoi(e) : 156; }();      // (A/B runs)
+    const int budget_kb = c->opt.octree_budget_kb;
     for (int v = 0; v < 2; v++) {
         // measured on 1 024 frames of 240x180 / 400 features: 344 us with 150 KB per workgroup, 211 us with 76 KB, 253 us with the
         // whole working set in global memory; a single frame per call is 5 % faster with everything in LDS
-        const size_t lds_budget = c->dbg_force_global ? 0 : (v == 0 ? (size_t)budget_kb * 1024 : std::min<size_t>((size_t)budget_kb, 76) * 1024);
+        const size_t lds_budget = c->opt.octree_force_global ? 0 : (v == 0 ? (size_t)budget_kb * 1024 : std::min<size_t>((size_t)budget_kb, 76) * 1024);
         size_t lds = 0, gblock = 0;
         for (int oi = 0; oi < 7; oi++) {
             const int k = order[oi];
@@ -1659,22 +1659,21 @@ int orb_configure(eorb_ctx* c, const eorb_orb_params* p, int W, int H)
     for (int v = 0; v < 2; v++) {
         g.oct_lds_bytes[v] = o.oct_lds[v]; g.oct_gblock_bytes[v] = o.oct_scratch[v];
         bool all = true; for (int k = 0; k < 7; k++) all = all && oct_in_lds[v][k];
-        static const int direct_on = [] { const char* e = getenv("EORB_OCT_DIRECT"); return e ? atoi(e) : 1; }();       // (A/B runs, parity tests of the list algorithm)
+        const bool direct_on = c->opt.octree_direct && !c->opt.octree_list_algorithm;       // (off: A/B runs, parity tests of the list algorithm)
         // the dynamic placement: the items sized by the features (6, 0, 1, 2) at fixed LDS offsets, the rest behind them
         {
-            const size_t lds_budget = c->dbg_force_global ? 0 : (v == 0 ? (size_t)budget_kb * 1024 : std::min<size_t>((size_t)budget_kb, 76) * 1024);
+            const size_t lds_budget = c->opt.octree_force_global ? 0 : (v == 0 ? (size_t)budget_kb * 1024 : std::min<size_t>((size_t)budget_kb, 76) * 1024);
             size_t lds = 0;
             const int fixed[4] = {6, 0, 1, 2};
             for (int k = 0; k < 7; k++) g.oct_off_dyn[v][k] = 0;
             for (int fi = 0; fi < 4; fi++) { g.oct_off_dyn[v][fixed[fi]] = (int)lds; lds += item_bytes[fixed[fi]]; }
             g.oct_dyn_base[v] = (int)lds; g.oct_dyn_lds[v] = (int)lds_budget;
-            static const int dyn_on = [] { const char* e = getenv("EORB_OCT_DYNAMIC"); return e ? atoi(e) : 1; }();
             // (in use when the static placement leaves something in global memory and the fixed items leave room for 1 024 candidates)
-            g.oct_dyn[v] = (dyn_on && !all && lds + 8 * 1024 <= lds_budget) ? ((direct_on && !c->dbg_oct_list) ? std::min(4096, 2 * vsp_pow2) : 1) : 0;
-            if (g.oct_dyn[v] && !(direct_on && !c->dbg_oct_list)) g.oct_dyn[v] = -1;     // (dynamic, no direct passes: the cap test `n <= -1` fails)
+            g.oct_dyn[v] = (c->opt.octree_dynamic && !all && lds + 8 * 1024 <= lds_budget) ? (direct_on ? std::min(4096, 2 * vsp_pow2) : 1) : 0;
+            if (g.oct_dyn[v] && !direct_on) g.oct_dyn[v] = -1;     // (dynamic, no direct passes: the cap test `n <= -1` fails)
             o.oct_dyn[v] = g.oct_dyn[v]; o.oct_dyn_lds[v] = g.oct_dyn_lds[v];
         }
-        o.oct_direct_cap[v] = g.oct_direct_cap[v] = (direct_on && !c->dbg_oct_list && all && oct_off[v][2] == oct_off[v][1] + (int)(sizeof(uint64_t) * vsp_pow2)) ? std::min(4096, 2 * vsp_pow2) : 0;
+        o.oct_direct_cap[v] = g.oct_direct_cap[v] = (direct_on && all && oct_off[v][2] == oct_off[v][1] + (int)(sizeof(uint64_t) * vsp_pow2)) ? std::min(4096, 2 * vsp_pow2) : 0;
     }
     g.node_cap_max = node_cap_max; g.vsp_cap_max = vsp_cap_max; g.ncap_max = ncap_max;
     int rc;
@@ -1771,9 +1770,8 @@ int orb_extract_dev(eorb_ctx* c, const uint8_t* d_img, int img_stride, size_t im
     }
     // a lapping area [lap0, lap1] that ends left of the first column a keypoint can have holds none of them, one that spans the image
     // (the monocular pipeline's (0, 1000)) all of them: one launch then does orientation, descriptor and output order (describe_kernel)
-    static const int fuse_env = [] { const char* e = getenv("EORB_ORB_DESCRIBE"); return e ? atoi(e) : 1; }();      // (A/B runs)
     const bool none_in = (float)lap1 < (float)o.lv[0].minBX, all_in = lap0 <= 0 && lap1 >= o.W;
-    const bool one_launch = fuse_env != 0 && !c->dbg_orb_three_launches && (none_in || all_in);
+    const bool one_launch = c->opt.orb_describe != 0 && !c->opt.orb_three_launches && (none_in || all_in);
     const int all_stereo = !none_in && all_in;
     if (want_desc) {
         ProfScope ps(c, "orb_blur");

@@ -62,6 +62,13 @@ class Context:
     def debug_option(self, name, value):
         self.check(self.L.eorb_debug_option(self.h, name.encode(), int(value)))
 
+    def debug_option_get(self, name):
+        """The value this context runs with for a switch (csrc/eorb_options.h): the default, the environment's at creation, or what
+        debug_option has set since."""
+        v = C.c_longlong(0)
+        self.check(self.L.eorb_debug_option_get(self.h, name.encode(), C.byref(v)))
+        return int(v.value)
+
     def debug_counter(self, name):
         return int(self.L.eorb_debug_counter(self.h, name.encode()))
 

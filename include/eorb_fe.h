@@ -120,8 +120,39 @@ int         eorb_sync(eorb_ctx* ctx);
  * to force its sort in global memory), "dirty_fill" (-1, the default: off; 0 .. 255: every device allocation of the context is filled with
  * that byte when it is made, the call arena is filled whole in front of every host-buffer call, and so are the pinned staging slot the
  * call's inputs are packed into and the pinned buffer its results land in -- what a call reads without having written it is then that
- * byte and not the zero of fresh memory or the previous call's values; tests/test_gpu_dirty.py) */
+ * byte and not the zero of fresh memory or the previous call's values; tests/test_gpu_dirty.py).
+ * These and every other switch are the rows of one table, csrc/eorb_options.h: eorb_create seeds a row from its environment variable,
+ * if the table names one and it is set, else from the default; this call overwrites the context's value, whatever the row.  The slot
+ * form's rows "slot_rank", "slot_hot_min", "slot_prerank", "slot_halves" (value < 0) and "slot_hot_waves" (value <= 0) take such a value
+ * as "not set": the row goes back to what eorb_create gave it.  The other rows, settable per context by the same names:
+ * "octree_list_algorithm" (1: the octree's list algorithm for every pass, from the next configure on).
+ * "position_dict" (0: float events in bulk never freeze or use the position dictionary; drops the one the context holds).
+ * "slot_hot_cap" (slot form: lists per length bucket of the register-row kernel, to force its overflow branch).
+ * "scatter" (EORB_SCATTER; 1: the list pipeline's first scatter form only).
+ * "gather_threads" (EORB_GATHER_THREADS; the generic gather's workgroup, 192 .. 1024 in steps of 64, else the build's).
+ * "gather_nc" (EORB_GATHER_NC; 2 / 4 tile columns per value wave of the raw gather, else by the launch's size).
+ * "slot_chunk" (EORB_SLOT_CHUNK; slot form: 256 / 1024 / 2048 / 4096 events per binning chunk, else by the slices' length).
+ * "slot_waves" (EORB_SLOT_WAVES; slot form: 1 .. 16 wavefronts of the gather's workgroup).
+ * "slot_rounds" (EORB_SLOT_ROUNDS; slot form: rounds of spare gather tasks, default 4).
+ * "slot_rank" (EORB_SLOT_RANK; 0: the ballot scatter although the device check passed).
+ * "slot_hot_min" (EORB_SLOT_HOT_MIN; list length from which the register-row kernel takes a list, 0: that kernel off).
+ * "slot_hot_waves" (EORB_SLOT_HOT_WAVES; wavefronts of the register-row kernel, default 8 per compute unit).
+ * "slot_prerank" (EORB_SLOT_PRERANK; 0: the count pass keeps no ranks, the rank scatter makes its own).
+ * "slot_halves" (EORB_SLOT_HALVES; 0: a batch runs as one part, 1: as two halves, whatever its shape).
+ * "win_cand_waves" / "win_qpb" (EORB_WIN_CAND_WAVES / EORB_WIN_QPB; window matchers: wavefronts / queries of a phase-1 workgroup).
+ * "upload_kernel_max" / "download_kernel_max" (EORB_UPLOAD_KERNEL_MAX / EORB_DOWNLOAD_KERNEL_MAX; host-buffer calls: bytes up to which a
+ * kernel, not the copy engine, moves a call's inputs / results; default 2^20).
+ * "sync_spin" (EORB_SYNC_SPIN; 1: host-buffer calls poll for their results instead of blocking).
+ * "slice_zero_copy" / "image_zero_copy" (EORB_SLICE_ZERO_COPY / EORB_IMAGE_ZERO_COPY; 0: a live slice's events / a call's one image are
+ * uploaded, not read in place from pinned host memory).
+ * "contest_direct_max" (EORB_CONTEST_DIRECT_MAX; eorb_ev_mc_contest: events up to which one launch makes every image; default 49152).
+ * "octree_budget_kb" / "octree_direct" / "octree_dynamic" (EORB_OCT_BUDGET_KB / EORB_OCT_DIRECT / EORB_OCT_DYNAMIC; the octree kernel's
+ * LDS budget, its direct passes and its dynamic placement, from the next configure on).
+ * "orb_describe" (EORB_ORB_DESCRIBE; 0: orientation, descriptors and output order never as one launch).
+ * Returns EORB_E_ARG for an unknown name. */
 int         eorb_debug_option(eorb_ctx* ctx, const char* name, int value);
+/* test hook: the value the context runs with for a row of that table; EORB_E_ARG for an unknown name */
+int         eorb_debug_option_get(eorb_ctx* ctx, const char* name, long long* value);
 /* test hook: counters a test can read to see which path served its calls.  "slot_calls": accumulation calls that took the slot
  * lists (gather_form 0 on dense batches, or 4); "slot_flags": sticky device flags of that path (0 = fine; synchronises); "slot_hot_items": lists the last such call handed to
  * the register-row kernel (synchronises); "slot_rank_ok": 1 when the scatter takes its ranks from LDS atomics; "kfdb_slot_cap" /

@@ -1783,6 +1783,7 @@ NO_CASE = {
     "eorb_destroy": "frees the context",
     "eorb_sync": "waits and reads the status word",
     "eorb_debug_option": "a setter of host fields",
+    "eorb_debug_option_get": "a getter of host fields",
     "eorb_debug_counter": "a getter: host fields, or a workspace read back",
     "eorb_debug_stage": "a getter: copies a workspace of the last extraction to the host",
     "eorb_last_error": "a getter of a host string",
